@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X ADMM engine (driver contract: see DESIGN.md).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): lasso.m on synthetic dense D 100000 x 10000 fp64, rho = 1,
@@ -9,6 +9,12 @@ lassotest.m:109-122 recipe (seed 1), fixed work via the reference's own switch d
 (admm.m:59, 711).  A "step" is one ADMM iteration (admm.m:496-743) with D, the cached factor
 and all iterates resident in HBM.  With N > 1 the SAME problem is row-sharded over the ranks
 (slicemaker(0, N, m), errorcheck.m:249-259) -> strong scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step).
+--full adds everything else: the x-solve roofline (HIP events, a run of its own), the side legs,
+the other BASELINE configs, the all-reduce latencies (N > 1), the CPU baseline and the parity check.
+--dump-outputs DIR writes what the timed run returned (xopt, zopt, uopt and the residual histories
+of its K iterations, fp64) as DIR/<name>.npy; the inputs are seeded, so runs are comparable.
 """
 from __future__ import annotations
 
@@ -50,7 +56,16 @@ def parse(argv=None):
     ap.add_argument("--one-gpu", action="store_true",
                     help="rehearsal on a single-GPU box: every rank uses HIP device 0, torch.distributed runs "
                          "over gloo and the engine over the shm transport (RCCL refuses two ranks on one device)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, side legs, other configs, all-reduce latencies, CPU baseline "
+                         "and parity (the --no-* switches above trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed run's results (xopt, zopt, uopt, pnorm, dnorm, perr, derr; fp64) as "
+                         "DIR/<name>.npy")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def dist_setup(one_gpu=False):
@@ -579,9 +594,10 @@ def main():
         L.check(L.load().admm_comm_info(comm.handle, _C.byref(_r), _C.byref(_n), _C.byref(_t)))
         comm_report = {"ranks": _n.value, "rank0_sees": _r.value,
                        "transport": {L.COMM_RCCL: "rccl", L.COMM_SHM: "shm", L.COMM_P2P: "p2p"}[_t.value]}
-        # what one per-iteration exchange costs on the links this group really has (the payloads of the legs below)
-        comm_report["allreduce_us"] = {f"{cnt}_doubles": max_over_ranks(dist, comm.allreduce_latency_us(cnt, 50))
-                                       for cnt in (1, n, 2 * n + 1, 3 * n + 16)}
+        if a.full:
+            # what one per-iteration exchange costs on the links this group really has (the payloads of the side legs)
+            comm_report["allreduce_us"] = {f"{cnt}_doubles": max_over_ranks(dist, comm.allreduce_latency_us(cnt, 50))
+                                           for cnt in (1, n, 2 * n + 1, 3 * n + 16)}
 
     t0 = time.perf_counter()
     p = make_problem(ap, dist, m, n, lo, hi)
@@ -594,14 +610,48 @@ def main():
     # ---- headline: objevals = 0 ----------------------------------------------------------
     _leg("headline")
     timed_run(eng, dist, max(1, a.warmup), rho=rho)
-    # only the dominant kernel class, every 4th iteration: the event pairs sit inside the timed region
+    dt, s_head = timed_run(eng, dist, a.steps, rho=rho)
+    value = a.steps / dt
+    if a.dump_outputs:  # what a caller of this run receives; every run starts from x = z = u = 0
+        k = int(s_head.steps)
+        dumped = {"xopt": eng.fetch(L.F_XOPT, n), "zopt": eng.fetch(L.F_ZOPT, n), "uopt": eng.fetch(L.F_UOPT, n),
+                  "pnorm": eng.fetch(L.F_PNORM, k), "dnorm": eng.fetch(L.F_DNORM, k),
+                  "perr": eng.fetch(L.F_PERR, k), "derr": eng.fetch(L.F_DERR, k)}
+        if rank == 0:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(a.dump_outputs, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    out = {
+        "metric": "ADMM iterations/sec (lasso 100k x 10k, fp64)", "value": value, "unit": "iterations/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"lasso.m cached-factor loop, D {m}x{n} fp64, rho=1, lassotest.m recipe seed=1, "
+                               f"domaxiters=1, objevals=0, xsolve={a.xsolve}",
+                   "rows": m, "cols": n, "rho": rho, "parallelism": f"rows{world}", "collective": transport,
+                   "communicator": comm_report},
+        "setup_seconds": setup_s, "datagen_seconds": t_gen,
+    }
+    if a.full:
+        full_measurements(ap, L, a, dist, eng, p, out, dt, xs, local, comm, lo, hi, m, n, rho, world, rank)
+    else:
+        eng.close()
+    if rank == 0:
+        print(json.dumps(out))
+    if comm is not None:
+        comm.close()
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(ap, L, a, dist, eng, p, out, dt, xs, local, comm, lo, hi, m, n, rho, world, rank):
+    """--full: everything past the headline, on the same resident data (eng is closed on return)."""
+    # only the dominant kernel class, every 4th iteration: K more steps with the event pairs in the stream
+    _leg("roofline")
     eng.set_profiling([L.K_XSOLVE], stride=4)
-    dt, _ = timed_run(eng, dist, a.steps, rho=rho)
+    dt_ev, _ = timed_run(eng, dist, a.steps, rho=rho)
     eng.set_profiling(False)
     xs_ms, xs_cnt = eng.kernel_time(L.K_XSOLVE)
-    value = a.steps / dt
-    # the same K steps without the HIP event records of the roofline leg in the stream
-    dt_plain, _ = timed_run(eng, dist, a.steps, rho=rho)
     if a.xsolve == "inverse":
         alg_bytes = 8.0 * n * (n + 1) / 2  # lower triangle of the symmetric inverse, read once
         kname = ("symv_lower_fin_kernel: x = inv(D'D+rho I) * y from the tile-packed lower triangle only (its first "
@@ -645,14 +695,7 @@ def main():
     scale = alg_bytes / max(1.0, float(llc + streamed))  # tile padding: stored bytes -> algorithmic bytes
     hbm_est = streamed * scale if llc + streamed > 0 else alg_bytes
     hbm_only = hbm_est / (xs_avg_ms * 1e-3) / 1e9 if xs_cnt else 0.0
-    out = {
-        "metric": "ADMM iterations/sec (lasso 100k x 10k, fp64)", "value": value, "unit": "iterations/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"lasso.m cached-factor loop, D {m}x{n} fp64, rho=1, lassotest.m recipe seed=1, "
-                               f"domaxiters=1, objevals=0, xsolve={a.xsolve}",
-                   "rows": m, "cols": n, "rho": rho, "parallelism": f"rows{world}", "collective": transport,
-                   "communicator": comm_report},
+    out.update({
         "roofline": {"bound": "hbm+infinity_cache" if llc > 0 and streamed > 0 else "hbm", "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kname,
@@ -674,10 +717,10 @@ def main():
                                      "consensus_lasso": 1 if world > 1 else 0},
             "allreduce_doubles": {"a_streaming": 3 * n + 16, "objevals1_literal": 1, "matrix_free": n,
                                   "consensus_lasso": 2 * n + 1}},
-        "setup_seconds": setup_s, "datagen_seconds": t_gen,
-        "iters_per_s_without_event_timing": a.steps / dt_plain,
+        "iters_per_s_without_event_timing": a.steps / dt,
+        "iters_per_s_with_event_timing": a.steps / dt_ev,
         "achieved_hbm_GBs_whole_iteration": (alg_bytes + 8.0 * 21 * n) * a.steps / dt / 1e9,
-    }
+    })
 
     if a.steps < 100:  # the driver's --steps 20 times 1.5 ms, of which 43 us are per-run fixed cost: also the 200-step rate
         dt200, _ = timed_run(eng, dist, 200, rho=rho)
@@ -744,13 +787,6 @@ def main():
         except Exception as exc:  # a host-side failure must not cost the measured GPU line
             out["cpu_baseline"] = {"value": None, "unit": "iterations/s", "cores": 1, "kind": "port", "error": repr(exc)}
     out.pop("_pmc_pair", None)
-    if rank == 0:
-        print(json.dumps(out))
-    if comm is not None:
-        comm.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -70,7 +70,7 @@ def main():
     keep = {k: v for k, v in traffic.items() if k.startswith(("void admm::", "admm::")) and
             v.get("fetch_bytes_per_launch", 0) + v.get("write_bytes_per_launch", 0) > 1e5}
     keep["_note"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, --kernel-trace only) of the FULL "
-                     "bench.py --steps 20 --warmup 2 --no-cpu-baseline on MI355X; FETCH_SIZE[KB]*1024*2 (gfx950 "
+                     "bench.py --steps 20 --warmup 2 --full --no-cpu-baseline on MI355X; FETCH_SIZE[KB]*1024*2 (gfx950 "
                      "wide-read correction, MI355X_MICROARCH.md), WRITE_SIZE[KB]*1024; per kernel the grid with the "
                      "largest traffic (the 100000x10000 / 4096^2 legs); avg_us_all_launches from --kernel-trace --stats "
                      "mixes every grid of that kernel")

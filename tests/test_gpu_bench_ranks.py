@@ -31,7 +31,8 @@ def test_bench_two_ranks_one_gpu_json_shape(gpu, transport):
         env["ADMM_BENCH_P2P_LEG"] = "1"  # the extra leg an RCCL run adds: the consensus problem once more over P2P
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--one-gpu", "--steps", "5",
-           "--warmup", "2", "--no-cpu-baseline", "--rows", str(rows), "--cols", str(cols), "--transport", transport]
+           "--warmup", "2", "--full", "--no-cpu-baseline", "--rows", str(rows), "--cols", str(cols),
+           "--transport", transport]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
