@@ -20,6 +20,7 @@ OK, E_INVALID, E_UNSUPPORTED, E_DEVICE, E_NUMERIC, E_COMM, E_CAPACITY = 0, -1, -
 PROB_LASSO, PROB_LASSO_CONSENSUS, PROB_LAD, PROB_HUBERFIT = 1, 2, 3, 4
 PROB_LINEARSVM, PROB_TOTALVARIATION, PROB_QP_BOUNDED, PROB_BASISPURSUIT = 5, 6, 7, 8
 PROB_MODEL, PROB_LINEARPROGRAM, PROB_QP_STANDARD, PROB_TV2D = 9, 10, 11, 12
+PROB_COVSEL = 13
 LOSS_HINGE, LOSS_01, LOSS_HINGE_OBJ01 = 0, 1, 2
 XSOLVE_AUTO, XSOLVE_TRSV, XSOLVE_INVERSE, XSOLVE_CG, XSOLVE_CALLBACK, XSOLVE_PINV = 0, 1, 2, 3, 4, 5
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -118,6 +119,7 @@ class ResultField(C.Structure):
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 F_WVALS = 23
+F_COVSEL_S = 24
 
 
 class AdmmError(RuntimeError):

@@ -210,6 +210,24 @@ def getproxops(problem, args):
                                     **objdata)
         rho = float(args.get("rho", 1.0))
         prob = _Problem("model", build(rho), dict(A=1, c=0.0, nA=n, nB=n), rebuild=build, rho=rho)
+    elif kind == "covarianceselection":
+        # getProxOps.m:669-750: args.S (n x n) and args.lambda; x = the eigen-step of 1487-1495 on the device.
+        # Engine-side extension: args.D (m x n samples) instead of S -- S = cov(D) is then formed on the device.
+        lam = float(_get(args, "lambda"))
+        if "D" in args and "S" not in args:
+            D = np.asarray(args["D"], dtype=np.float64)
+            if D.ndim != 2:
+                raise ValueError("Argument D is not a matrix!")
+            n = D.shape[1]
+            eng = Engine(L.PROB_COVSEL, D=D, lam=lam, xsolve=xs, device=dev, comm=comm)
+        else:
+            S = np.asarray(_get(args, "S"), dtype=np.float64)
+            if S.ndim != 2 or S.shape[0] != S.shape[1]:
+                raise ValueError("Argument S is not a square matrix!")
+            n = S.shape[0]
+            eng = Engine(L.PROB_COVSEL, P=S, lam=lam, xsolve=xs, device=dev, comm=comm)
+        # the loop runs on the n^2 entries; covarianceselection.m:157-163 names the side n in m, nA, nB
+        prob = _Problem("covarianceselection", eng, dict(A=1, c=0.0, nA=n * n, nB=n * n, side=n))
     else:
         raise NotImplementedError(f"problem '{kind}' is outside the engine's hot-path scope (SURVEY.md section 8)")
     return ProxOp(prob, "x"), ProxOp(prob, "z"), extra
@@ -255,7 +273,7 @@ def _check_constraint(options, prob):
         if exp["c"] == "s" and float(c) != 0.0:
             raise ValueError("scalar non-zero c is not supported")
     for key in ("nA", "nB"):
-        if key in options and int(options[key]) not in (0, exp[key]):
+        if key in options and int(options[key]) not in (0, exp[key], exp.get("side", 0)):
             raise ValueError(f"options.{key} does not match the problem size")
 
 

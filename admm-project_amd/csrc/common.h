@@ -116,6 +116,23 @@ __device__ __forceinline__ double gather_chunks(const double* __restrict__ src, 
   return ax;
 }
 
+// pair (p, q) number `k` of round `r` of the round-robin tournament over ne (even) players
+__device__ __forceinline__ void jacobi_pair(int32_t ne, int32_t r, int32_t k, int32_t& p, int32_t& q) {
+  const int32_t m1 = ne - 1;
+  if (k == 0) {
+    p = m1;
+    q = r % m1;
+  } else {
+    p = (r + k) % m1;
+    q = (r - k + m1) % m1;
+  }
+  if (p > q) {
+    const int32_t t = p;
+    p = q;
+    q = t;
+  }
+}
+
 
 
 }  // namespace admm

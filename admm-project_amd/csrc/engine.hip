@@ -1448,6 +1448,74 @@ int admm_engine_create(const admm_problem_desc* desc, admm_engine** out) {
       E_TRY(e->mem.alloc(&e->cobjpart, K * kMaxPartBlocks));
       break;
     }
+    case ADMM_PROB_COVSEL: {
+      // covarianceselection.m:145-172: A = 1, B = -1, c = 0, x/z/u the n x n matrices flattened (every norm of admm.m
+      // is 'fro', perr uses sqrt(numel)): the vector loop on n^2 elements with the lasso z-prox (getProxOps.m:750)
+      if (n < 1) return bail(fail(ADMM_E_INVALID, "covariance selection needs n >= 1 (S is n x n)"));
+      if (!(desc->lambda > 0.0))
+        return bail(fail(ADMM_E_INVALID, "lambda must be a positive real (covarianceselection.m: errorcheck 'ispositivereal')"));
+      if (e->comm) return bail(fail(ADMM_E_UNSUPPORTED, "covariance selection runs on one device (desc.comm must be NULL)"));
+      if (xs != ADMM_XSOLVE_AUTO)
+        return bail(fail(ADMM_E_UNSUPPORTED, "covariance selection has one x-update (the eigen-step): desc.xsolve must be AUTO"));
+      const int64_t nn = n * n;
+      e->a_identity = true;
+      e->nA = nn;
+      e->len = nn;
+      e->prox = PROX_SOFT;
+      e->rhs_kind = RHS_DIFF;  // the x-update reads z - u (v - uhat in fast ADMM)
+      e->cov_ld = round_up(n, 16);
+      const int64_t ld = e->cov_ld;
+      if (desc->P) {
+        E_TRY(upload(e->mem, &e->cov_S, desc->P, static_cast<size_t>(nn), mk, e->stream));
+        std::vector<double> h(static_cast<size_t>(nn));
+        E_HIP(hipMemcpyAsync(h.data(), e->cov_S, sizeof(double) * nn, hipMemcpyDeviceToHost, e->stream));
+        E_HIP(hipStreamSynchronize(e->stream));
+        double amax = 0.0, asym = 0.0;
+        for (int64_t j = 0; j < n; ++j)
+          for (int64_t i = j; i < n; ++i) {
+            const double a = h[i + j * n], b = h[j + i * n];
+            amax = std::max(amax, std::max(std::fabs(a), std::fabs(b)));
+            asym = std::max(asym, std::fabs(a - b));
+            if (!std::isfinite(a) || !std::isfinite(b)) asym = INFINITY;
+          }
+        if (!(asym <= 1e-12 * amax))
+          return bail(fail(ADMM_E_INVALID, "covariance selection: S must be a finite symmetric matrix (|S - S'| <= "
+                                           "1e-12 * max|S|)"));
+      } else if (desc->D) {  // S = cov(D), covarianceselection.m:150: centre the columns, then the Gram / (m - 1)
+        if (m < 2) return bail(fail(ADMM_E_INVALID, "covariance selection: cov(D) needs at least two samples (m >= 2)"));
+        double *Dd = nullptr, *W = nullptr;
+        int64_t ldd = 0;
+        E_TRY(upload_matrix(e->mem, &Dd, &ldd, desc->D, m, n, desc->ldD ? desc->ldD : m, mk, e->stream));  // (a copy)
+        E_TRY(e->mem.alloc(&W, static_cast<size_t>(ld) * n));
+        E_TRY(e->mem.alloc(&e->cov_S, static_cast<size_t>(nn)));
+        covsel_cov(Dd, ldd, m, n, W, ld, e->cov_S, e->stream);
+        E_HIP(hipStreamSynchronize(e->stream));
+        mem_free_one(e->mem, Dd);
+        mem_free_one(e->mem, W);
+      } else {
+        return bail(fail(ADMM_E_INVALID, "covariance selection needs S (desc.P, n x n) or the samples (desc.D, m x n)"));
+      }
+      e->ell = e->cov_S;  // the weights of trace(S*X) = sum S_ij X_ij (OBJX_DOT)
+      E_TRY(e->mem.alloc(&e->cov_V, static_cast<size_t>(ld) * n));
+      E_HIP(hipMemsetAsync(e->cov_V, 0, sizeof(double) * ld * n, e->stream));
+      E_TRY(e->mem.alloc(reinterpret_cast<double**>(&e->cov_cnt), 1));
+      if (n <= kCovselSmallMax) {
+        E_TRY(covsel_small_prepare());
+      } else {
+        CovselLarge& c = e->cov_big;
+        c.n = n;
+        c.ld = ld;
+        c.V = e->cov_V;
+        for (double** p : {&c.W, &c.B, &c.T}) {
+          E_TRY(e->mem.alloc(p, static_cast<size_t>(ld) * n));
+          E_HIP(hipMemsetAsync(*p, 0, sizeof(double) * ld * n, e->stream));
+        }
+        E_TRY(e->mem.alloc(&c.lam, static_cast<size_t>(2 * n)));
+        E_TRY(e->mem.alloc(&c.sig, static_cast<size_t>(1 + 2 * n)));
+        E_TRY(e->mem.alloc(reinterpret_cast<double**>(&c.rot), 1));
+      }
+      break;
+    }
     default:
       return bail(fail(ADMM_E_INVALID, "Invalid input for problem - not a solver (getProxOps.m:916)"));
   }
@@ -1520,7 +1588,8 @@ int admm_engine_create(const admm_problem_desc* desc, admm_engine** out) {
 
 int admm_engine_fetch(admm_engine* e, int field, double* dst, size_t cap, size_t* written) {
   if (!e || !dst) return fail(ADMM_E_INVALID, "engine/dst is NULL");
-  if (!e->has_run && field != ADMM_F_FACTOR) return fail(ADMM_E_INVALID, "no run to fetch results from");
+  if (!e->has_run && field != ADMM_F_FACTOR && field != ADMM_F_COVSEL_S)
+    return fail(ADMM_E_INVALID, "no run to fetch results from");
   ADMM_HIP_TRY(hipSetDevice(e->device));
   const size_t steps = static_cast<size_t>(e->last.steps);
   const double* src = nullptr;
@@ -1528,6 +1597,11 @@ int admm_engine_fetch(admm_engine* e, int field, double* dst, size_t cap, size_t
   bool need_vec_hist = false, need_fast = false;
   switch (field) {
     case ADMM_F_XOPT: src = e->x; count = e->nA; break;
+    case ADMM_F_COVSEL_S:
+      if (e->problem != ADMM_PROB_COVSEL) return fail(ADMM_E_INVALID, "ADMM_F_COVSEL_S: not a covariance-selection engine");
+      src = e->cov_S;
+      count = static_cast<size_t>(e->nA);
+      break;
     case ADMM_F_ZOPT: src = e->bgen ? e->zt : e->z; count = e->bgen ? e->nBz : e->len; break;
     case ADMM_F_UOPT: src = e->u; count = e->len; break;
     case ADMM_F_XVALS: src = e->xhist; count = e->nA * steps; need_vec_hist = true; break;
@@ -1652,7 +1726,7 @@ int admm_engine_info(admm_engine* e, admm_engine_info_t* info) {
   info->factor_n = has ? f->n : 0;
   info->rank = f->pinv ? f->rank : (has ? f->n : 0);
   info->trsv_blocks = (has && f->mode == ADMM_XSOLVE_TRSV) ? f->trsv.nblk : 0;
-  info->jacobi_sweeps = f->jacobi_sweeps;
+  info->jacobi_sweeps = (e->problem == ADMM_PROB_COVSEL) ? static_cast<int32_t>(e->cov_sweeps) : f->jacobi_sweeps;
   info->unwrapped_fused = e->Dp ? 1 : 0;
   info->cond_estimate = has ? f->cond_diag : NAN;
   info->probe_err_inverse = f->probed ? f->err_inv : NAN;

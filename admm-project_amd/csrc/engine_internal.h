@@ -15,6 +15,7 @@
 #include "dct.h"
 #include "consensus.h"
 #include "cg.h"
+#include "covsel.h"
 
 namespace admm {
 
@@ -200,6 +201,15 @@ struct admm_engine {
   void *altuuser = nullptr, *normsuser = nullptr;
   double *hk_uold = nullptr, *hk_bz = nullptr, *hk_unew = nullptr, *hk_zero = nullptr, *hk_norms = nullptr;
   void *xuser = nullptr, *zuser = nullptr, *ouser = nullptr;
+  // covariance selection (covsel.hip): S (n x n, ld n; also the OBJX_DOT weights of trace(S*X), = ell), the eigenvector
+  // basis the next x-update starts from (reset to I at every run: a run never depends on the one before), -log det X
+  double* cov_S = nullptr;
+  double* cov_V = nullptr;
+  int64_t cov_ld = 0;
+  CovselLarge cov_big{};       // n > kCovselSmallMax
+  int32_t* cov_cnt = nullptr;  // [0]: sweeps of the small path in this run
+  int64_t cov_sweeps = 0;      // Jacobi sweeps of the last run (both paths)
+  int cov_sweeps_host = 0;
   double* part = nullptr;     // [S_COUNT][kMaxPartBlocks]
   double* objpart = nullptr;  // [kMaxPartBlocks]
   Ctrl* ctrl = nullptr;

@@ -162,6 +162,15 @@ static int x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int6
       launch_combine(e->partSq, e->planSq.nchunk, e->planSq.ldg, 1.0, nullptr, 0.0, e->q, e->x, e->n, e->ctrl,
                      e->stream);
       break;
+    case ADMM_PROB_COVSEL:  // getProxOps.m:1487-1495: X = f(rho*(Z - U) - S) by a symmetric eigen-step (covsel.hip)
+      if (e->n <= kCovselSmallMax) {
+        CovselArgs ca{e->n, e->last_opts.rho, e->rhs, e->cov_S, e->x, e->cov_V, e->cov_ld, e->objpart, e->cov_cnt};
+        launch_covsel_small(ca, e->ctrl, e->stream);
+      } else {
+        ADMM_TRY(covsel_large_x_update(e->cov_big, e->last_opts.rho, e->rhs, e->cov_S, e->x, e->objpart, e->ctrl,
+                                       e->ctrl_host, &e->cov_sweeps_host, e->stream));
+      }
+      break;
     default:  // LAD / Huber / SVM: rhs already holds D'*(c + z - u) (row 0 of g)
       if (e->DplusT)  // row 0 of g is Dplus*(z - u) already (getProxOps.m:1067)
         launch_combine(e->g, 1, 0, 1.0, nullptr, 0.0, nullptr, e->x, e->nA, e->ctrl, e->stream);
@@ -372,6 +381,11 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   if (e->bgen && !(e->xcb && e->zcb))
     return fail(ADMM_E_INVALID, "an engine with a general B needs both the xminf and the zming callback");
   e->last_opts = o;
+  if (e->problem == ADMM_PROB_COVSEL) {  // every run starts its eigen-steps from V = I: no state from the previous run
+    launch_jacobi_identity(e->cov_V, e->cov_ld, e->n, e->stream);
+    ADMM_HIP_TRY(hipMemsetAsync(e->cov_cnt, 0, sizeof(int32_t), e->stream));
+    e->cov_sweeps_host = 0;
+  }
   const int alg = o.fast;  // 0, 1 (strong), 2 (weak)
   const bool use_h = o.convtest || o.stopcond == ADMM_STOP_HNORM || o.stopcond == ADMM_STOP_BOTH;
   const int64_t len = e->len, nA = e->nA;
@@ -465,7 +479,7 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   fa.obj_scale_part = 0.0;
   pa.objz = OBJZ_NONE;
   pa.objx = OBJX_NONE;
-  bool obj_lasso_gemv = false, obj_qp_gemv = false, obj_model_gemv = false;
+  bool obj_lasso_gemv = false, obj_qp_gemv = false, obj_model_gemv = false, obj_covsel = false;
   if (o.objevals && e->ocb) {  // options.obj is the caller's handle (admm.m:603-605)
     fa.obj_scale_part = 1.0;
   } else if (o.objevals) {
@@ -505,6 +519,14 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
       case ADMM_PROB_BASISPURSUIT:
         pa.objx = OBJX_ABS;
         fa.obj_scale_x = 1.0;
+        break;
+      case ADMM_PROB_COVSEL:  // trace(S*x) - log(det(x)) + lambda*norm(z(:),1)   (covarianceselection.m:169)
+        pa.objx = OBJX_DOT;   // sum S_ij X_ij = trace(S*X): X is symmetric
+        fa.obj_scale_x = 1.0;
+        pa.objz = OBJZ_ABS;
+        fa.obj_scale_z = e->lambda;
+        obj_covsel = true;  // -log det X = -sum log f(lambda_i), from the x-update's own eigenvalues (q27)
+        fa.obj_scale_part = 1.0;
         break;
       case ADMM_PROB_MODEL:  // 1/2||P*x - r||^2 + 1/2||Q*z - s||^2   (model.m:133-134)
         if (!e->D || !e->D2)
@@ -550,7 +572,8 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   pa.a_identity = e->a_identity ? 1 : 0;
   switch (e->prox) {
     case PROX_SOFT:
-      pa.t = (e->problem == ADMM_PROB_LASSO) ? e->lambda / o.rho : 1.0 / o.rho;  // getProxOps.m:455 | 810, 142
+      pa.t = (e->problem == ADMM_PROB_LASSO || e->problem == ADMM_PROB_COVSEL) ? e->lambda / o.rho
+                                                                              : 1.0 / o.rho;  // getProxOps.m:455, 750 | 810, 142
       break;
     case PROX_HINGE:
       pa.t = e->C / o.rho;  // getProxOps.m:1096
@@ -716,7 +739,7 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   const int64_t heavy = std::max<int64_t>(e->m * e->n, e->nF * e->nF);
   const bool use_graph = std::getenv("ADMM_HIP_GRAPH") != nullptr && !sharded && e->profiling == 0 && !uw_fused &&
                          e->xsolve != ADMM_XSOLVE_CG && heavy <= (int64_t{32} << 20) && !e->xcb && !e->zcb && !e->ocb &&
-                         !hooks;
+                         !hooks && !(e->problem == ADMM_PROB_COVSEL && e->n > kCovselSmallMax);  // (host checks per sweep)
   // A = I iterations whose finalize depends on nothing but the prox kernel's partial sums end in ONE launch
   // (prox_fin_kernel): no accelerated-ADMM decision, no split z-update, no objective kernels behind the prox, one rank
   // the lasso objective through the cached Gram matrix: always (obj_gram = 1), or once the calibration of the first
@@ -878,8 +901,8 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
       }
       fa.slots_reduced = nullptr;
       fa.objp_reduced = nullptr;
-      fa.objpart = nullptr;
-      fa.nobjpart = 0;
+      fa.objpart = obj_covsel ? e->objpart : nullptr;  // (written by this iteration's x-update)
+      fa.nobjpart = obj_covsel ? 1 : 0;
       {
         TimerScope ts(e, ADMM_K_PROX);
         pa.axsrc = axsrc;
@@ -1017,6 +1040,9 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
         if (e->ocb(e->ouser, e->x, nA, e->bgen ? e->zt : e->z, e->bgen ? e->nBz : len, e->objpart,
                    static_cast<void*>(e->stream)) != 0)
           return fail(ADMM_E_INVALID, "the objective callback reported a failure");
+        fa.objpart = e->objpart;
+        fa.nobjpart = 1;
+      } else if (obj_covsel) {
         fa.objpart = e->objpart;
         fa.nobjpart = 1;
       } else if (obj_model_gemv) {
@@ -1159,6 +1185,11 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   if (e->profiling) collect_timers(e);
   for (auto& t : e->timers) t.used = 0;
 
+  if (e->problem == ADMM_PROB_COVSEL) {
+    int32_t sw = 0;
+    ADMM_HIP_TRY(hipMemcpy(&sw, e->cov_cnt, sizeof(int32_t), hipMemcpyDeviceToHost));
+    e->cov_sweeps = sw + e->cov_sweeps_host;
+  }
   e->last = admm_run_summary{};
   e->last.steps = e->ctrl_host->steps;
   if (e->cg_st) {

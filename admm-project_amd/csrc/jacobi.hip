@@ -20,23 +20,6 @@ namespace admm {
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
-// pair (p, q) number `k` of round `r` of the round-robin tournament over ne (even) players
-__device__ __forceinline__ void jacobi_pair(int32_t ne, int32_t r, int32_t k, int32_t& p, int32_t& q) {
-  const int32_t m1 = ne - 1;
-  if (k == 0) {
-    p = m1;
-    q = r % m1;
-  } else {
-    p = (r + k) % m1;
-    q = (r - k + m1) % m1;
-  }
-  if (p > q) {
-    const int32_t t = p;
-    p = q;
-    q = t;
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void jacobi_round_kernel(double* __restrict__ B, int64_t ldb,
                                                               double* __restrict__ V, int64_t ldv, int32_t n,
                                                               int32_t ne, int32_t round, double tol, double null2,
@@ -162,6 +145,25 @@ int jacobi_eig_psd(double* W, int64_t n, int64_t ldw, double* V, int64_t ldv, do
   ADMM_HIP_TRY(hipStreamSynchronize(stream));
   if (sweeps_out) *sweeps_out = sweeps;
   return ADMM_OK;
+}
+
+// the building blocks one at a time, for the per-iteration eigen-step of covariance selection (covsel.hip)
+void launch_jacobi_identity(double* V, int64_t ldv, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(jacobi_identity_kernel, dim3(static_cast<unsigned>(n)), dim3(kBlock), 0, stream, V, ldv,
+                     static_cast<int32_t>(n));
+}
+
+void launch_jacobi_round(double* B, int64_t ldb, double* V, int64_t ldv, int64_t n, int32_t round, double tol,
+                         double null2, int32_t* rot, hipStream_t stream) {
+  const int32_t nn = static_cast<int32_t>(n);
+  const int32_t ne = (nn + 1) & ~1;
+  hipLaunchKernelGGL(jacobi_round_kernel, dim3(static_cast<unsigned>(ne / 2)), dim3(kBlock), 0, stream, B, ldb, V, ldv,
+                     nn, ne, round, tol, null2, rot);
+}
+
+void launch_jacobi_norms(const double* B, int64_t ldb, int64_t n, double* lam, hipStream_t stream) {
+  hipLaunchKernelGGL(jacobi_norms_kernel, dim3(static_cast<unsigned>(n)), dim3(kBlock), 0, stream, B, ldb,
+                     static_cast<int32_t>(n), lam);
 }
 
 void launch_scale_cols(double* V, int64_t ldv, int64_t n, const double* scale, hipStream_t stream) {

@@ -166,5 +166,11 @@ int trsv_check_error(const TrsvPlan& p, hipStream_t stream);
 int jacobi_eig_psd(double* W, int64_t n, int64_t ldw, double* V, int64_t ldv, double* lam_dev, int32_t* rot,
                    std::vector<double>* lam_host, int* sweeps_out, hipStream_t stream);
 void launch_scale_cols(double* V, int64_t ldv, int64_t n, const double* scale, hipStream_t stream);
+// one-sided Jacobi one step at a time: V <- I; one round (n/2 disjoint column pairs of B and V rotated, `round` of the
+// ne - 1 rounds of a sweep; rot counts the rotations; null2 = 0 rotates every non-zero column); lam[j] = ||B(:, j)||
+void launch_jacobi_identity(double* V, int64_t ldv, int64_t n, hipStream_t stream);
+void launch_jacobi_round(double* B, int64_t ldb, double* V, int64_t ldv, int64_t n, int32_t round, double tol,
+                         double null2, int32_t* rot, hipStream_t stream);
+void launch_jacobi_norms(const double* B, int64_t ldb, int64_t n, double* lam, hipStream_t stream);
 
 }  // namespace admm

@@ -408,9 +408,9 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
 FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
   FinArgs ff = f;
   ff.nblk = static_cast<int32_t>(ceil_div(a.len, kTailTile));
-  ff.g = nullptr;  // nothing but the block partials (and, for A = D, the x of this iteration) feeds the finalize logic
-  ff.objpart = nullptr;
-  ff.nobjpart = 0;
+  // nothing but the block partials (and, for A = D, the x of this iteration) feeds the finalize logic -- and objective
+  // partials an earlier launch of the iteration wrote when the caller passes them (covariance selection: -log det X)
+  ff.g = nullptr;
   ff.slots_reduced = nullptr;
   ff.objp_reduced = nullptr;
   return ff;

@@ -141,6 +141,8 @@ class Engine:
         self.nB = self.m if problem in (L.PROB_LAD, L.PROB_HUBERFIT, L.PROB_LINEARSVM) else self.n
         if problem == L.PROB_TV2D:
             self.nA, self.nB = self.m * self.n, 2 * self.m * self.n
+        if problem == L.PROB_COVSEL:  # X, Z, U are n x n matrices, flattened column-major
+            self.nA = self.nB = self.n * self.n
         self.mC = self.nB  # length of u, c and A*x; equals nB unless a general B was set (set_constraint_b)
         self.device = int(d.device)
         self._cb_keep = None

@@ -16,7 +16,7 @@ from .api import admm, getproxops
 from .errorcheck import is_nonnegative_real, is_positive_real, slicemaker
 
 __all__ = ["lasso", "lad", "huberfit", "linearsvm", "unwrappedadmm", "quadraticprogram", "basispursuit",
-           "totalvariation", "totalvariation2d", "model", "linearprogram"]
+           "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
 
@@ -430,5 +430,35 @@ def model(P, Q, r, s, options=None):
     options.update(A=1, B=-1, c=0, m=n, nA=n, nB=n)  # model.m:124-130
     options["obj"] = _ENGINE_OBJ
     results = admm(minx, minz, options)
+    results["solverruntime"] = time.perf_counter() - t0
+    return results
+
+
+def covarianceselection(D, lam, options=None):
+    """results = covarianceselection(D, lambda, options)   (solvers/covarianceselection.m:140-173).
+
+    Sparse inverse covariance selection: minimise trace(S*X) - log det X + lambda*||X||_1 over X with S = cov(D)
+    (D: m samples x n variables).  S is formed on the device (columns centred, then the MFMA Gram / (m - 1)); the loop
+    runs on the n^2 entries of X, Z, U with A = 1, B = -1, c = 0 and the eigen-step x-update of getProxOps.m:1487-1495.
+    xopt, zopt, uopt (and x0, z0, u0) come back as n x n matrices; histories keep their n^2-row shape.
+    """
+    if options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise TypeError("Given options is not a struct! At least pass empty struct!")
+    options = dict(options)
+    t0 = time.perf_counter()
+    D = _matrix(D, "D")
+    lam = is_positive_real(lam, "lambda")
+    n = D.shape[1]
+    args = _engine_args(options, dict(D=D))
+    args["lambda"] = lam
+    minx, minz, _ = getproxops("CovarianceSelection", args)
+    options.update(A=1, B=-1, c=0, m=n, nA=n, nB=n)  # covarianceselection.m:157-163 (x0 = z0 = u0 = zeros(n, n))
+    options["obj"] = _ENGINE_OBJ  # covarianceselection.m:169  trace(S*x) - log(det(x)) + lambda*norm(z(:), 1)
+    results = admm(minx, minz, options)
+    for key in ("xopt", "zopt", "uopt", "x0", "z0", "u0"):
+        if key in results:
+            results[key] = np.asarray(results[key]).reshape((n, n), order="F")
     results["solverruntime"] = time.perf_counter() - t0
     return results

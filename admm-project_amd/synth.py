@@ -225,6 +225,24 @@ def basispursuit_problem(seed=0, rows=2 ** 6, cols=2 ** 7):
     return dict(D=D, s=D @ testx, testx=testx)
 
 
+def covsel_problem(seed=0, rows=2 ** 9, cols=2 ** 6):
+    """testers/covarianceselectiontest.m:111-128: Sinv = I with ceil(0.001*cols^2) random entries set to one, plus its
+    transpose (so the diagonal is 2), shifted by 1.1*|min eig| when indefinite; S = inv(Sinv); D = mvnrnd(0, S, rows),
+    restated as standard normal rows times the Cholesky factor of S.  lambda = 1 (line 108)."""
+    rng = np.random.default_rng(seed)
+    Sinv = np.eye(cols)
+    idx = rng.choice(cols * cols, size=int(np.ceil(0.001 * cols * cols)), replace=False)
+    Sinv[idx % cols, idx // cols] = 1.0  # MATLAB's column-major linear indices
+    Sinv = Sinv + Sinv.T
+    emin = float(np.min(np.linalg.eigvalsh(Sinv)))
+    if emin < 0:
+        Sinv = Sinv + 1.1 * abs(emin) * np.eye(cols)
+    S = np.linalg.inv(Sinv)
+    Lc = np.linalg.cholesky(0.5 * (S + S.T))
+    D = np.asfortranarray(rng.standard_normal((rows, cols)) @ Lc.T)
+    return dict(D=D, S=S, Sinv=Sinv, lam=1.0)
+
+
 def read_idx1_labels(path, count=None):
     """examples/mnistsvm.m:215-229: big-endian idx1 label file (magic 2049)."""
     with open(path, "rb") as f:

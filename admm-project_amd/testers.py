@@ -13,7 +13,7 @@ import numpy as np
 from . import solvers, synth
 
 __all__ = ["lassotest", "ladtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
-           "linearprogramtest", "modeltest", "solvertester"]
+           "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
 def _opts(options, **forced):
@@ -150,6 +150,25 @@ def modeltest(seed=0, rows=2 ** 7, cols=2 ** 7, errtol=1e-3, quiet=1, options=No
                 objerror=abs(1.0 - obj(xopt) / obj(xt)), xerror=np.linalg.norm(xt - xopt),
                 failed=int(not (abs(1.0 - obj(xopt) / obj(xt)) <= errtol and np.linalg.norm(xt - xopt) <= errtol)),
                 steps=results["steps"])
+    return results, test
+
+
+def covarianceselectiontest(seed=0, rows=2 ** 9, cols=2 ** 6, errtol=1e-3, quiet=1, options=None):
+    """testers/covarianceselectiontest.m:91-150: pass when obj(xopt, xopt) < obj(Sinv, Sinv), obj built on the TRUE S
+    (not on cov(D)).  q28: line 107 calls errorcheck() without arguments when options.lambda is set, an error in the
+    reference; here options['lambda'] is taken."""
+    opts = dict(options or {})
+    lam = float(opts.get("lambda", 1.0))
+    p = synth.covsel_problem(seed, rows, cols)
+    S, Sinv = p["S"], p["Sinv"]
+    obj = lambda X, Z: np.trace(S @ X) - np.log(np.linalg.det(X)) + lam * np.sum(np.abs(Z))
+    results = solvers.covarianceselection(p["D"], lam, _opts(opts, objevals=1, maxiters=1000, convtest=1, quiet=quiet))
+    xopt = results["xopt"]
+    trueobj, objopt = obj(Sinv, Sinv), obj(xopt, xopt)
+    test = dict(D=p["D"], S=S, Sinv=Sinv, trueobjopt=trueobj, xopt=xopt, admmopt=results["objopt"], objopt=objopt,
+                failed=int(not objopt < trueobj), objerror=abs((trueobj - objopt) / objopt), steps=results["steps"],
+                errtol=errtol)
+    test["lambda"] = lam
     return results, test
 
 

@@ -51,6 +51,10 @@ enum {
                                      differences); x-update of I + rho*D'D spectral (column DCT + row stage) where the
                                      height has a column transform, matrix-free CG otherwise or with ADMM_XSOLVE_CG; no
                                      reference counterpart (totalvariation.m is 1-D) -- BASELINE config 5 as literally written */
+  ADMM_PROB_COVSEL = 13,          /* getProxOps.m:669-750 (z: soft threshold lambda/rho, 745-750), x: 1487-1495
+                                     (eigen-step of rho*(z-u) - S); covarianceselection.m:145-172 on the n^2 entries of
+                                     the n x n X: S = desc.P (n x n), or desc.D (m x n samples, S = cov(D) built on the
+                                     device), lambda = desc.lambda */
   ADMM_PROB_MODEL = 9             /* getProxOps.m:60-95, x: 952-979, z: 990-1013 (model.m); with both prox
                                      callbacks set and no data it is the generic admm(xminf, zming, options)
                                      of admm.m:24 for A = 1, B = -1 */
@@ -245,8 +249,10 @@ enum {
                            * its x-updates that ended on cg_maxit with the residual still above cg_tol (an inexact iterate) */
   ADMM_F_CONS_X = 21,     /* consensus lasso: the local slices' x_k, n x K column-major (closure state xi{k}, getProxOps.m:1247) */
   ADMM_F_CONS_U = 22,     /* consensus lasso: the local slices' u_k (closure state ui{k}, getProxOps.m:1296) */
-  ADMM_F_WVALS = 23       /* (nA + nB + nU) x steps: w = [x; z; rho*u] per iteration, results.wvals of the H-norm runs
+  ADMM_F_WVALS = 23,      /* (nA + nB + nU) x steps: w = [x; z; rho*u] per iteration, results.wvals of the H-norm runs
                            * (admm.m:678-681); needs the vector histories */
+  ADMM_F_COVSEL_S = 24    /* covariance selection: the n x n S the engine runs with (cov(D) when created from samples);
+                           * available before the first run */
 };
 
 /* ---- library ---------------------------------------------------------------- */
@@ -303,7 +309,7 @@ typedef struct admm_engine_info_t {
   int32_t pinv_used;         /* 1: the explicit matrix is the pseudo-inverse of a rank-deficient D'D */
   int32_t probed;            /* 1: both forms were built and compared */
   int32_t trsv_blocks;       /* coarse blocks K of the blocked substitution (0 if not in use) */
-  int32_t jacobi_sweeps;     /* sweeps of the eigen-solver (pinv) */
+  int32_t jacobi_sweeps;     /* sweeps of the eigen-solver (pinv; covariance selection: over the last run) */
   int32_t unwrapped_fused;   /* 1: the two-launch unwrapped iteration with an explicit pinv(D) is available (linear SVM) */
   int64_t factor_n;          /* order of the factor (n; m for fat lasso) */
   int64_t rank;              /* numerical rank (== factor_n unless pinv_used) */
