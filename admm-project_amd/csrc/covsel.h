@@ -33,7 +33,8 @@ struct CovselLarge {
   int32_t* rot = nullptr;
 };
 // X = f(M) through W = M + sigma*I (sigma from Gershgorin discs: W positive definite), B0 = W*V_prev, one-sided
-// Jacobi rounds on (B, V) until a sweep rotates nothing (one host check per sweep); lambda_i = ||b_i|| - sigma.
+// Jacobi rounds on (B, V) until a sweep rotates nothing (one host check per sweep); lambda_i = ||b_i|| / ||v_i|| - sigma,
+// then one Newton-Schulz step re-orthonormalises V before X is formed and V is kept for the next warm start.
 // ctrl_host receives the device control block at every check: a run that has stopped skips the rest.
 int covsel_large_x_update(const CovselLarge& c, double rho, const double* y, const double* S, double* X,
                           double* logpart, const Ctrl* ctrl, Ctrl* ctrl_host, int* sweeps, hipStream_t stream);

@@ -22,6 +22,8 @@ constexpr int kCovThreads = 512;  // 8 waves: two per SIMD
 constexpr int kCovMaxSweeps = 40;
 // (pair, row) items of one rotation phase per thread: ceil(48 * 96 / 512)
 constexpr int kCovItems = static_cast<int>((kCovselSmallMax / 2 * kCovselSmallMax + kCovThreads - 1) / kCovThreads);
+// entries of an n x n matrix per thread: ceil(96 * 96 / 512)
+constexpr int kCovCells = static_cast<int>((kCovselSmallMax * kCovselSmallMax + kCovThreads - 1) / kCovThreads);
 
 // f(l) = (l + sqrt(l^2 + 4 rho)) / (2 rho), in the form without cancellation for l < 0 (= 2 / (sqrt(l^2 + 4 rho) - l))
 __device__ __forceinline__ double covsel_f(double l, double rho) {
@@ -195,6 +197,39 @@ __global__ __launch_bounds__(kCovThreads) void covsel_small_kernel(CovselArgs a,
     atomicAdd(a.sweeps, sweeps);
   }
   __syncthreads();
+  // one Newton-Schulz step, V <- V (3I - V'V) / 2: the rotations leave V orthonormal only to their accumulated
+  // rounding, and the next x-update warm-starts from this V, so without it the loss of orthogonality grows over a run
+  // (DESIGN.md section 10).  G = V'V goes to the A slot (the eigenvalues are in fv).
+  for (int idx = tid; idx < n * n; idx += kCovThreads) {
+    const int j = idx / n, i = idx - j * n;
+    if (i < j) continue;
+    double g = 0.0;
+    for (int k = 0; k < n; ++k) g = __builtin_fma(V[k + i * ld], V[k + j * ld], g);
+    A[i + j * ld] = g;
+    A[j + i * ld] = g;
+  }
+  __syncthreads();
+  {
+    double vn[kCovCells];
+#pragma unroll
+    for (int e = 0; e < kCovCells; ++e) {
+      const int idx = tid + e * kCovThreads;
+      if (idx >= n * n) break;
+      const int j = idx / n, i = idx - j * n;
+      double t = 0.0;
+      for (int k = 0; k < n; ++k) t = __builtin_fma(V[i + k * ld], A[k + j * ld], t);
+      vn[e] = 1.5 * V[i + j * ld] - 0.5 * t;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < kCovCells; ++e) {
+      const int idx = tid + e * kCovThreads;
+      if (idx >= n * n) break;
+      const int j = idx / n, i = idx - j * n;
+      V[i + j * ld] = vn[e];
+    }
+  }
+  __syncthreads();
   // X = V f(Lambda) V': the lower triangle, stored to both halves (exactly symmetric)
   for (int idx = tid; idx < n * n; idx += kCovThreads) {
     const int j = idx / n, i = idx - j * n;
@@ -269,8 +304,10 @@ __global__ __launch_bounds__(kBlock) void covsel_shift_kernel(double* __restrict
   if (threadIdx.x == 0) sig[0] = s;
 }
 
-// lambda_i = ||b_i|| - sigma -> scale[i] = sqrt(f(lambda_i)); logpart[0] = -sum log f(lambda_i)
+// lambda_i = ||b_i|| / ||v_i|| - sigma (b_i = W v_i; G = V'V before the Newton-Schulz step, so G_ii = ||v_i||^2)
+// -> scale[i] = sqrt(f(lambda_i)); logpart[0] = -sum log f(lambda_i)
 __global__ __launch_bounds__(kBlock) void covsel_spectrum_kernel(const double* __restrict__ norms,
+                                                                 const double* __restrict__ G, int64_t ldg,
                                                                  const double* __restrict__ sig, int64_t n, double rho,
                                                                  double* __restrict__ scale,
                                                                  double* __restrict__ logpart) {
@@ -278,7 +315,7 @@ __global__ __launch_bounds__(kBlock) void covsel_spectrum_kernel(const double* _
   const double s = sig[0];
   double lsum = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += kBlock) {
-    const double f = covsel_f(norms[i] - s, rho);
+    const double f = covsel_f(norms[i] / sqrt(G[i + i * ldg]) - s, rho);
     scale[i] = sqrt(f);
     lsum += log(f);
   }
@@ -293,6 +330,13 @@ __global__ __launch_bounds__(kBlock) void covsel_scale_copy_kernel(const double*
   const int64_t j = blockIdx.x;
   const double s = scale[j];
   for (int64_t i = threadIdx.x; i < n; i += kBlock) T[i + j * ld] = V[i + j * ld] * s;
+}
+
+// V <- 1.5 V - 0.5 T, T = V*(V'V): one Newton-Schulz step towards the nearest orthonormal basis
+__global__ __launch_bounds__(kBlock) void covsel_ns_kernel(double* __restrict__ V, const double* __restrict__ T,
+                                                           int64_t ld, int64_t n) {
+  const int64_t j = blockIdx.x;
+  for (int64_t i = threadIdx.x; i < n; i += kBlock) V[i + j * ld] = 1.5 * V[i + j * ld] - 0.5 * T[i + j * ld];
 }
 
 // dst (n x n, ld n) = the lower triangle of src (ld) mirrored: exactly symmetric.  ctrl (nullable): no-op once stopped
@@ -330,8 +374,13 @@ int covsel_large_x_update(const CovselLarge& c, double rho, const double* y, con
   *sweeps += done;
   if (ctrl_host->stop) return ADMM_OK;
   launch_jacobi_norms(c.B, ld, n, c.lam, stream);
-  hipLaunchKernelGGL(covsel_spectrum_kernel, dim3(1), dim3(kBlock), 0, stream, c.lam, c.sig, n, rho, c.lam + n,
-                     logpart);
+  // one Newton-Schulz step on V (W is free until X): G = V'V, T = V*G, V <- 1.5 V - 0.5 T.  The rotations leave V
+  // orthonormal only to their accumulated rounding, and the next x-update warm-starts from it
+  launch_gemm(1, 0, n, n, n, 1.0, c.V, ld, c.V, ld, 0.0, c.W, ld, false, stream);
+  launch_gemm(0, 0, n, n, n, 1.0, c.V, ld, c.W, ld, 0.0, c.T, ld, false, stream);
+  hipLaunchKernelGGL(covsel_ns_kernel, dim3(gn), dim3(kBlock), 0, stream, c.V, c.T, ld, n);
+  hipLaunchKernelGGL(covsel_spectrum_kernel, dim3(1), dim3(kBlock), 0, stream, c.lam, c.W, ld, c.sig, n, rho,
+                     c.lam + n, logpart);
   hipLaunchKernelGGL(covsel_scale_copy_kernel, dim3(gn), dim3(kBlock), 0, stream, c.V, c.T, ld, n, c.lam + n);
   launch_gemm(0, 1, n, n, n, 1.0, c.T, ld, c.T, ld, 0.0, c.W, ld, true, stream);  // X = T*T' (lower tiles)
   hipLaunchKernelGGL(covsel_mirror_kernel, dim3(gn), dim3(kBlock), 0, stream, c.W, ld, n, 1.0, X, ctrl);
