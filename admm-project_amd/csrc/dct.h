@@ -47,12 +47,8 @@ void launch_tv2d_fused_dct(const Tv2Args& a, bool state_in, double* bhat, const 
 // inverse of the above (DCT-III with the 1/H factor): src -> dst (may alias)
 void launch_dct_cols_inverse(const double* src, double* dst, int64_t H, int64_t W, const DctTables& th,
                              const Ctrl* ctrl, hipStream_t stream);
-// t (W x H, column-major: the transposed, column-transformed image), in place: every column (one image row
-// frequency i) -> DCT-II along W, divide by 1 + rho*(lamH[i] + lamW[k]), DCT-III back
-void launch_dct_rows_solve(double* t, int64_t H, int64_t W, double rho, const DctTables& th, const DctTables& tw,
-                           const Ctrl* ctrl, hipStream_t stream);
-// the same on the untransposed image img (H x W, column-major), row pairs read and written at stride H: replaces
-// transpose -> rows_solve -> transpose
+// img (H x W, column-major: the column-transformed image), in place: every row (one vertical frequency i) -> DCT-II
+// along W, divide by 1 + rho*(lamH[i] + lamW[k]), DCT-III back; row pairs read and written at stride H
 void launch_dct_rows_solve_strided(double* img, int64_t H, int64_t W, double rho, const DctTables& th,
                                    const DctTables& tw, const Ctrl* ctrl, hipStream_t stream);
 // The row stage without a transform: dst = inv((1 + rho*lamH[i]) I + rho*L_W) applied along every row i of src (H x W,

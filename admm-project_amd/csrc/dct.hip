@@ -471,53 +471,11 @@ __global__ __launch_bounds__(kChirpMaxThreads) void dct_cols_inverse_chirp_kerne
 // 4096^2 (74 against 65 us): the transform is bound by its own instruction stream, not by the overlap of its phases.
 // Removed; the commit that carried it: "2-D TV row stage: 16 waves of a workgroup ...".)
 
-// columns of t have length W (= tw.n) and belong to the row frequencies i = 2*blockIdx.x, +1 of the image
-__global__ __launch_bounds__(kBlock) void dct_rows_solve_kernel(double* __restrict__ tm, int64_t W, double rho,
-                                                                const double* __restrict__ lamH, DctTables t,
-                                                                const Ctrl* __restrict__ ctrl) {
-  if (ctrl->stop) return;
-  extern __shared__ c64 zs[];
-  const int n = t.n, p = t.log2n;
-  double* a = tm + static_cast<int64_t>(2 * blockIdx.x) * W;
-  double* b = a + W;
-  load_pair(zs, a, b, n);
-  __syncthreads();
-  fft_network<false>(zs, n, p, t.tw);
-  const double la = lamH[2 * blockIdx.x], lb = lamH[2 * blockIdx.x + 1];
-  const double* __restrict__ lam = t.lam;
-#pragma unroll 2
-  for (int k = threadIdx.x; k <= (n >> 1); k += blockDim.x) {
-    if (k == 0) {
-      const c64 z0 = zs[0];
-      zs[0] = c64{z0.x / (1.0 + rho * la), z0.y / (1.0 + rho * lb)};  // lam[0] = 0
-    } else if (k == (n >> 1)) {
-      const c64 h = zs[1];  // X = sqrt(1/2) V and V' = sqrt(2) X': the rotation cancels
-      zs[1] = c64{h.x / (1.0 + rho * (la + lam[k])), h.y / (1.0 + rho * (lb + lam[k]))};
-    } else {
-      const int rk = swz(bitrev(k, p)), rn = swz(bitrev(n - k, p));
-      const c64 ck = t.c4[k];
-      double xak, xan, xbk, xbn;
-      spectrum_to_dct(zs[rk], zs[rn], ck, xak, xan, xbk, xbn);
-      const double lk = lam[k], ln = lam[n - k];
-      xak /= 1.0 + rho * (la + lk);
-      xan /= 1.0 + rho * (la + ln);
-      xbk /= 1.0 + rho * (lb + lk);
-      xbn /= 1.0 + rho * (lb + ln);
-      c64 zk, zn;
-      dct_to_spectrum(xak, xan, xbk, xbn, ck, zk, zn);
-      zs[rk] = zk;
-      zs[rn] = zn;
-    }
-  }
-  __syncthreads();
-  fft_network<true>(zs, n, p, t.tw);
-  store_pair(zs, a, b, n, 1.0 / static_cast<double>(n));
-}
-
-// 64 x 64 tiles through LDS (65-double pitch: conflict-free both ways); fully coalesced on both sides
-// The same solve on the image where it lies (H x W, column-major): the workgroup of row pair (i, i+1) reads, for every
-// column j, the 16 bytes img[i..i+1, j] -- already the complex pair (a_j, b_j) the joint FFT wants -- at stride H,
-// and writes them back the same way: no transposed copy of the image, two passes over it instead of six.  The access
+// The row stage by transform, on the column-transformed image where it lies (H x W, column-major): every row (one
+// vertical frequency i) -> DCT-II along W, divide by 1 + rho*(lamH[i] + lamW[k]), DCT-III back.  The workgroup of row
+// pair (i, i+1) reads, for every column j, the 16 bytes img[i..i+1, j] -- already the complex pair (a_j, b_j) the
+// joint FFT wants -- at stride H, and writes them back the same way: no transposed copy of the image, two passes over
+// it instead of six.  The access
 // is 16 bytes per 8H-byte stride; what keeps it off HBM is that the 8 workgroups sharing a 128-byte line run at the
 // same time on ONE XCD (row pairs are dealt to the XCDs in contiguous ranges: workgroup b -> XCD b mod 8 under
 // round-robin placement, speed only) and that the image (134 MB at 4096^2) sits in the 256 MB Infinity Cache right
@@ -579,6 +537,7 @@ __global__ __launch_bounds__(kBlock) void dct_rows_solve_strided_kernel(double* 
   }
 }
 
+// 64 x 64 tiles through LDS (65-double pitch: conflict-free both ways); fully coalesced on both sides
 __global__ __launch_bounds__(kBlock) void transpose_kernel(const double* __restrict__ src, double* __restrict__ dst,
                                                            int64_t rows, int64_t cols, const Ctrl* __restrict__ ctrl) {
   if (ctrl && ctrl->stop) return;
@@ -753,13 +712,6 @@ void launch_dct_cols_inverse(const double* src, double* dst, int64_t H, int64_t 
   dct_allow_lds(dct_cols_inverse_kernel, dct_lds_bytes(th.n));
   hipLaunchKernelGGL(dct_cols_inverse_kernel, dim3(col_pairs(W)), dim3(kBlock), dct_lds_bytes(th.n), stream, src, dst, H, t2,
                      ctrl);
-}
-
-void launch_dct_rows_solve(double* t, int64_t H, int64_t W, double rho, const DctTables& th, const DctTables& tw,
-                           const Ctrl* ctrl, hipStream_t stream) {
-  dct_allow_lds(dct_rows_solve_kernel, dct_lds_bytes(tw.n));
-  hipLaunchKernelGGL(dct_rows_solve_kernel, dim3(static_cast<unsigned>(H / 2)), dim3(kBlock), dct_lds_bytes(tw.n),
-                     stream, t, W, rho, th.lam, tw, ctrl);
 }
 
 void launch_dct_rows_solve_strided(double* img, int64_t H, int64_t W, double rho, const DctTables& th,
@@ -973,7 +925,7 @@ __global__ __launch_bounds__(kCoopWaves* kWave) void tv2d_rows_coop_kernel(const
 
 // the cooperative form covers truncations up to its two halo runs
 static bool tv2d_rows_coop_ok(int taps, int64_t W) {
-  return taps <= kCoopHalo * kCoopRun && W >= kCoopOut * kCoopRun && std::getenv("ADMM_HIP_TV2D_ROWS_WAVE") == nullptr;
+  return taps <= kCoopHalo * kCoopRun && W >= kCoopOut * kCoopRun;
 }
 
 int tv2d_rows_green_taps(double rho) {

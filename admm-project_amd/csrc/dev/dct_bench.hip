@@ -2,7 +2,7 @@
 // DCT kernels (../dct.hip) go?  Variants on a 4096 x 4096 image, two columns per workgroup:
 //   copy    load_pair + store_pair only (the Makhoul permutation through LDS): the memory floor of the structure
 //   fft2    + forward and inverse FFT network, no spectral step
-//   rows    the product kernel dct_rows_solve_kernel
+//   rows    the product row kernel dct_rows_solve_strided_kernel (the 99 us below: its transposed-image predecessor)
 //   fwd/inv the product column kernels
 //   hipcc -O3 --offload-arch=gfx950 -I.. -I../../../include -o dct_bench dct_bench.hip && ./dct_bench
 // MI355X, 4096 x 4096 (image MALL-resident): copy 35 us, fft2 75 us (20 us per FFT: ~50 % of the LDS peak with both
@@ -87,7 +87,7 @@ int main() {
   };
   timeit("copy", [&] { hipLaunchKernelGGL(variant_kernel<0>, dim3(H / 2), dim3(kBlock), lds, 0, img, W, t); });
   timeit("fft2", [&] { hipLaunchKernelGGL(variant_kernel<1>, dim3(H / 2), dim3(kBlock), lds, 0, img, W, t); });
-  timeit("rows", [&] { launch_dct_rows_solve(img, H, W, 1.0, t, t, ctrl, 0); });
+  timeit("rows", [&] { launch_dct_rows_solve_strided(img, H, W, 1.0, t, t, ctrl, 0); });
   timeit("fwd", [&] { launch_dct_cols_forward(img, H, W, t, ctrl, 0); });
   timeit("inv", [&] { launch_dct_cols_inverse(img, img, H, W, t, ctrl, 0); });
   timeit("transp", [&] { launch_transpose(img, img + 0, H, W, ctrl, 0); });

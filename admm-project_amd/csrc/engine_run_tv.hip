@@ -1,7 +1,5 @@
 // engine_run_tv.hip -- the iteration sequences of total variation (totalvariation.m:122-164; fused kernel, the
 // unfused fast / relaxed form) and of its 2-D extension (spectral or CG x-update), split out of admm_engine_run.
-#include <cstdlib>
-
 #include "engine_internal.h"
 
 namespace admm {
@@ -63,58 +61,64 @@ int cg_solve_tv2d(admm_engine* e, const double* y) {
 }
 
 // 2-D TV x-update, direct: x = C2' diag(1/(1 + rho*(lamH_i + lamW_j))) C2 y with the 2-D DCT-II C2 (dct.h).
-// Three passes over the image (6 N doubles of traffic): column DCT in place, the row transform + spectral division +
-// inverse row transform on row PAIRS read at stride H (dct_rows_solve_strided_kernel), inverse column DCT.  Round 1
-// transposed the image around the row pass (five passes, 10 N): 0.645 -> 0.590 ms per iteration at 4096^2 on the
-// same box (ADMM_HIP_TV2D_TRANSPOSED=1 brings that form back; e->cg_r is its scratch).
-// the Toeplitz row stage (dct.hip) covers this rho on this width
-static bool tv2d_rows_green_ok(const admm_engine* e, double rho) {
+// Three passes over the image (6 N doubles of traffic): column DCT in place, a row stage, inverse column DCT.  The row
+// stage is one of three (dct.hip), picked per run by tv2d_rows:
+enum class Tv2Rows {
+  GREEN,   // the exact Toeplitz kernel of the row operator on the mirrored row: small rho, wide image
+  DCT,     // row transform + spectral division + inverse on row PAIRS read at stride H: width a power of two, even H
+  THOMAS,  // the row systems solved as they stand (Thomas elimination): any width, any rho
+};
+static Tv2Rows tv2d_rows(const admm_engine* e, double rho) {
   const int taps = tv2d_rows_green_taps(rho);
-  return taps <= 96 && e->tv2_W >= 4 * taps;
-}
-
-// ... and it is the form dct_solve_tv2d takes by default (no environment override asks for a row transform)
-static bool tv2d_rows_green_default(const admm_engine* e, double rho) {
-  return tv2d_rows_green_ok(e, rho) && (!e->tv2_rows_dct || e->tv2_H % 2 != 0 ||
-                                        (std::getenv("ADMM_HIP_TV2D_ROWS_DCT") == nullptr &&
-                                                            std::getenv("ADMM_HIP_TV2D_TRANSPOSED") == nullptr));
-}
-
-// the exact tridiagonal row stage (dct.hip) is what is left when neither of the two applies
-static bool tv2d_rows_thomas_default(const admm_engine* e, double rho) {
-  return !tv2d_rows_green_default(e, rho) && !(e->tv2_rows_dct && e->tv2_H % 2 == 0) &&
-         std::getenv("ADMM_HIP_TV2D_NO_THOMAS") == nullptr;
+  if (taps <= 96 && e->tv2_W >= 4 * taps) return Tv2Rows::GREEN;
+  if (e->tv2_rows_dct && e->tv2_H % 2 == 0) return Tv2Rows::DCT;
+  return Tv2Rows::THOMAS;
 }
 
 // fin != nullptr: the forward transform's launch carries the finalize logic of the previous iteration (when pending)
 static int dct_solve_tv2d(admm_engine* e, double* y, const FinArgs* fin = nullptr, bool fin_pending = false) {
   TimerScope ts(e, ADMM_K_XSOLVE);
   const int64_t H = e->tv2_H, W = e->tv2_W;
+  const double rho = e->last_opts.rho;
   if (fin) launch_dct_cols_forward_fin(y, H, W, e->dctH, *fin, fin_pending, e->ctrl, e->stream);
   else launch_dct_cols_forward(y, H, W, e->dctH, e->ctrl, e->stream);            // along i, in place
-  if (tv2d_rows_green_default(e, e->last_opts.rho)) {
-    // default: no row transform at all -- the exact Toeplitz kernel of the row operator on the mirrored row (dct.hip)
-    launch_tv2d_rows_green(y, e->x, H, W, e->last_opts.rho, e->dctH, e->ctrl, e->stream);
-    launch_dct_cols_inverse(e->x, e->x, H, W, e->dctH, e->ctrl, e->stream);
-    return ADMM_OK;
+  switch (tv2d_rows(e, rho)) {
+    case Tv2Rows::GREEN:
+      launch_tv2d_rows_green(y, e->x, H, W, rho, e->dctH, e->ctrl, e->stream);
+      launch_dct_cols_inverse(e->x, e->x, H, W, e->dctH, e->ctrl, e->stream);
+      break;
+    case Tv2Rows::DCT:
+      launch_dct_rows_solve_strided(y, H, W, rho, e->dctH, e->dctW, e->ctrl, e->stream);
+      launch_dct_cols_inverse(y, e->x, H, W, e->dctH, e->ctrl, e->stream);
+      break;
+    case Tv2Rows::THOMAS:  // factors in e->cg_p / e->cg_q, set up by run_total_variation_2d
+      launch_tv2d_rows_thomas(y, e->x, H, W, rho, e->cg_p, e->cg_q, e->ctrl, e->stream);
+      launch_dct_cols_inverse(e->x, e->x, H, W, e->dctH, e->ctrl, e->stream);
+      break;
   }
-  if (tv2d_rows_thomas_default(e, e->last_opts.rho)) {
-    // neither the Toeplitz form (width / rho) nor a row transform (width not a power of two, or an odd height):
-    // the row systems solved as they stand (dct.hip: tv2d_rows_thomas_kernel; factors in e->cg_p / e->cg_q, set up by
-    // run_total_variation_2d)
-    launch_tv2d_rows_thomas(y, e->x, H, W, e->last_opts.rho, e->cg_p, e->cg_q, e->ctrl, e->stream);
-    launch_dct_cols_inverse(e->x, e->x, H, W, e->dctH, e->ctrl, e->stream);
-    return ADMM_OK;
+  return ADMM_OK;
+}
+
+// End of a run: launch errors, kernel timers, the summary with the objective at the last executed iteration
+// (admm.m:752-754).  e->ctrl_host holds the device's final control block.
+static int finish_tv_run(admm_engine* e, const admm_options& o, int32_t N, double runtime, admm_run_summary* summary) {
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
+  if (e->profiling) collect_timers(e);
+  const int32_t steps = e->ctrl_host->steps;
+  e->last = admm_run_summary{};
+  e->last.steps = steps;
+  e->last.stopped_early = (steps < N) ? 1 : 0;
+  e->last.convtest_failed_at = e->ctrl_host->convfail;
+  e->last.runtime_s = runtime;
+  e->last.objopt = NAN;
+  if (o.objevals && steps > 0) {
+    double v = NAN;
+    ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (steps - 1), sizeof(double), hipMemcpyDeviceToHost));
+    e->last.objopt = v;
   }
-  if (std::getenv("ADMM_HIP_TV2D_TRANSPOSED") == nullptr) {  // row transform on the untransposed image
-    launch_dct_rows_solve_strided(y, H, W, e->last_opts.rho, e->dctH, e->dctW, e->ctrl, e->stream);
-    launch_dct_cols_inverse(y, e->x, H, W, e->dctH, e->ctrl, e->stream);
-    return ADMM_OK;
-  }
-  launch_transpose(y, e->cg_r, H, W, e->ctrl, e->stream);                        // -> W x H
-  launch_dct_rows_solve(e->cg_r, H, W, e->last_opts.rho, e->dctH, e->dctW, e->ctrl, e->stream);
-  launch_transpose(e->cg_r, y, W, H, e->ctrl, e->stream);                        // -> H x W
-  launch_dct_cols_inverse(y, e->x, H, W, e->dctH, e->ctrl, e->stream);
+  e->has_run = true;
+  if (summary) *summary = e->last;
   return ADMM_OK;
 }
 
@@ -133,11 +137,11 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
   if (o.relax != 1.0)
     return fail(ADMM_E_INVALID, "relaxation with the 2-D total-variation prox is a dimension error (D is 2N x N)");
   const int64_t Npix = e->tv2_H * e->tv2_W;
-  // spectral x-update: the column DCT, then along the rows the Toeplitz stage (small rho, wide image), the row DCT
-  // (width a power of two, even height: it works on row PAIRS) or the exact tridiagonal solve (anything else)
-  const bool spectral = e->tv2_dct && ((e->tv2_rows_dct && e->tv2_H % 2 == 0) || tv2d_rows_green_ok(e, o.rho) ||
-                                       tv2d_rows_thomas_default(e, o.rho));
-  if (spectral && tv2d_rows_thomas_default(e, o.rho))  // the elimination factors of this run's rho
+  // spectral x-update whenever the height has a column transform (one of the three row stages always applies);
+  // CG otherwise
+  const bool spectral = e->tv2_dct;
+  const Tv2Rows rows = tv2d_rows(e, o.rho);
+  if (spectral && rows == Tv2Rows::THOMAS)  // the elimination factors of this run's rho
     launch_tv2d_rows_thomas_setup(e->tv2_H, e->tv2_W, o.rho, e->dctH, e->cg_p, e->cg_q, e->stream);
   if (e->z != e->tv_zA) {  // the initial iterates were written to e->z / e->u; make buffer A the current one
     ADMM_HIP_TRY(hipMemcpyAsync(e->tv_zA, e->z, sizeof(double) * len, hipMemcpyDeviceToDevice, e->stream));
@@ -241,14 +245,14 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
   // Deferred tail (spectral x-update): the finalize logic of iteration i rides in the first launch of iteration i + 1
   // (dct_cols_forward_fin_kernel); a batch's last iteration gets the stand-alone launch.  A stop it raises turns the
   // rest of iteration i + 1 into no-ops -- only the in-place transform of the right-hand side has run by then.
-  const bool tv2_defer = spectral && std::getenv("ADMM_HIP_NO_DEFERRED_FINALIZE") == nullptr;
-  // Default spectral form ("glued"): the fused pass hands its right-hand side to the forward column transform inside
-  // one kernel (dct.hip: tv2d_fused_dct_kernel), so e->rhs holds the TRANSFORMED right-hand side from one iteration to
-  // the next and an iteration is three launches: row stage (+ the previous iteration's finalize as a passenger) into the
-  // scratch image e->cg_r, inverse column transform into x, fused pass + forward transform.  (The row stage writes a
-  // scratch image, not x: it is the launch that carries the passenger, so it still runs when the passenger raises stop.)
-  const bool tv2_glued = spectral && tv2d_rows_green_default(e, o.rho) && e->dctH.bm == 0 &&  // (power-of-two heights)
-                         std::getenv("ADMM_HIP_TV2D_NO_GLUE") == nullptr;
+  // Glued spectral form (Toeplitz row stage, power-of-two height): the fused pass hands its right-hand side to the
+  // forward column transform inside one kernel (dct.hip: tv2d_fused_dct_kernel), so e->rhs holds the TRANSFORMED
+  // right-hand side from one iteration to the next and an iteration is three launches: row stage (+ the previous
+  // iteration's finalize as a passenger) into the scratch image e->cg_r, inverse column transform into x, fused pass +
+  // forward transform.  (The row stage writes a scratch image, not x: it is the launch that carries the passenger, so
+  // it still runs when the passenger raises stop.)  Every other spectral shape -- non-power-of-two heights (chirp
+  // column transform), the row DCT, the Thomas row stage -- takes four launches: dct_solve_tv2d, then the fused pass.
+  const bool tv2_glued = spectral && rows == Tv2Rows::GREEN && e->dctH.bm == 0;
   bool tv2_pending = false;
   while (alg == 0 && done < N && !stop_seen) {
     double* const vbuf[2] = {e->tv_zB, e->tv_uB};
@@ -264,8 +268,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
     if (tv2_glued) {
       {
         TimerScope ts(e, ADMM_K_XSOLVE);
-        launch_tv2d_rows_green(e->rhs, e->cg_r, ta.H, ta.W, o.rho, e->dctH, e->ctrl, e->stream, tv2_defer ? &fa : nullptr,
-                               tv2_pending);
+        launch_tv2d_rows_green(e->rhs, e->cg_r, ta.H, ta.W, o.rho, e->dctH, e->ctrl, e->stream, &fa, tv2_pending);
         launch_dct_cols_inverse(e->cg_r, e->x, ta.H, ta.W, e->dctH, e->ctrl, e->stream);
       }
       tv2_pending = false;
@@ -273,14 +276,14 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
       launch_tv2d_fused_dct(ta, done > 0, e->rhs, e->dctH, e->ctrl, &nblk, e->stream);
     } else {
       // (I + rho*D'D) x = s + rho*D'(z - u): spectral, or warm-started CG (polls the device)
-      if (spectral) ADMM_TRY(dct_solve_tv2d(e, e->rhs, tv2_defer ? &fa : nullptr, tv2_pending));
+      if (spectral) ADMM_TRY(dct_solve_tv2d(e, e->rhs, &fa, tv2_pending));
       else ADMM_TRY(cg_solve(e, e->rhs));
       tv2_pending = false;
       TimerScope ts(e, ADMM_K_PROX);
       launch_tv2d_fused(ta, done > 0, e->rhs, e->ctrl, &nblk, e->stream);
     }
     fa.nblk = nblk;
-    if (tv2_defer && (done + 1) % check_tv2 != 0 && done + 1 != N) {
+    if (spectral && (done + 1) % check_tv2 != 0 && done + 1 != N) {
       tv2_pending = true;  // finalized by the next iteration's first launch
     } else {
       TimerScope ts(e, ADMM_K_FINALIZE);
@@ -295,12 +298,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
       if (e->ctrl_host->stop) stop_seen = true;
     }
   }
-  {
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
-  }
   const double rt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (e->profiling) collect_timers(e);
   const int32_t steps = e->ctrl_host->steps;
   if (alg == 0 && steps > 0)  // z, u of the last executed iteration (fast ADMM updates buffer A in place)
     launch_tv2d_expand((steps - 1) & 1 ? e->tv_uB : e->tv_zB, ta.thresh, len, e->tv_zA, e->tv_uA, e->stream);
@@ -310,20 +308,20 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
   ADMM_HIP_TRY(hipMemcpy(e->cg_st_host, e->cg_st, sizeof(CgState), hipMemcpyDeviceToHost));
   e->cg_total_last = e->cg_st_host->total;
   e->cg_capped_last = e->cg_st_host->capped;
-  e->last = admm_run_summary{};
-  e->last.steps = steps;
-  e->last.stopped_early = (steps < N) ? 1 : 0;
-  e->last.convtest_failed_at = e->ctrl_host->convfail;
-  e->last.runtime_s = rt;
-  e->last.objopt = NAN;
-  if (o.objevals && steps > 0) {
-    double v = NAN;
-    ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (steps - 1), sizeof(double), hipMemcpyDeviceToHost));
-    e->last.objopt = v;
-  }
-  e->has_run = true;
-  if (summary) *summary = e->last;
-  return ADMM_OK;
+  return finish_tv_run(e, o, N, rt, summary);
+}
+
+// The form of a 1-D iteration (tv.hip), fixed for a run by the plan's halo, n and the ADMM variant
+enum class TvForm {
+  DIRECT,   // plain ADMM, halo <= 248: one launch without the y vector, 3-5 vector passes (launch_tv_direct)
+  FUSED,    // plain ADMM, halo 250..256 (too wide for the direct kernels' margin) or n = 1: tv_fused_kernel, 7 passes
+  SWEEP,    // plain ADMM, halo > 256 (rho >~ 37): two sweeps and tv_prox, three launches
+  UNFUSED,  // fast / accelerated ADMM or over-relaxation: sweeps, tv_dx, the generic prox kernel, tv_dual
+};
+static TvForm tv_form(const TvArgs& ta, int alg, double relax) {
+  if (alg != 0 || relax != 1.0) return TvForm::UNFUSED;
+  if (!tv_fused_ok(ta)) return TvForm::SWEEP;
+  return tv_direct_ok(ta) ? TvForm::DIRECT : TvForm::FUSED;
 }
 
 int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary) {
@@ -371,13 +369,8 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
   ta.zhist = e->zhist;
   ta.uhist = e->uhist;
   ta.part = e->part;
-  // one fused launch per iteration when the halo is small; the three-kernel form otherwise.  Default fused form: the
-  // direct kernel (no y vector, 5 vector passes, tv.hip: tv_direct_kernel); ADMM_HIP_TV_SCAN=1 keeps the 7-pass form
-  // whose sweeps are split over two launches
-  const bool tv_fused = tv_fused_ok(ta) && std::getenv("ADMM_HIP_TV_UNFUSED") == nullptr;
-  const bool tv_direct = tv_fused && tv_direct_ok(ta) && std::getenv("ADMM_HIP_TV_SCAN") == nullptr &&
-                         std::getenv("ADMM_HIP_TV_ONE_LAUNCH") == nullptr && alg == 0 && o.relax == 1.0;
-  if (tv_direct) {
+  const TvForm form = tv_form(ta, alg, o.relax);
+  if (form == TvForm::DIRECT) {
     ta.margin = tv_direct_margin(ta);
     ta.ftile = 256 * kTvDirectE - 2 * ta.margin;
     const double rr = o.rho / bstar;
@@ -385,32 +378,19 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
     ta.rpow[0] = rr;
     for (int k = 1; k < 8; ++k) ta.rpow[k] = ta.rpow[k - 1] * rr;
   }
-  double* tv_part = nullptr;  // per-tile partials of the fused kernel (one column per tile)
-  bool tv_one_launch = false;
-  if (tv_fused) {
-    const int64_t ntiles = ceil_div(e->n, ta.ftile);
-    ta.part_stride = round_up(ntiles, 2);
-    const int64_t ngroups = ceil_div(ntiles, kTvGroup);
-    // One launch per iteration (tile partials -> group partials -> finalize inside the fused kernel, tv.hip) is
-    // implemented and tested but NOT the default: at n = 4096^2 it measured 0.2419-0.2421 ms per iteration against
-    // 0.2405 with the two small launches (tv_pack + finalize) behind the fused kernel, on the same box -- the drain
-    // and the two arrival hops at the end of 8600 tiles cost what the two launches cost.  ADMM_HIP_TV_ONE_LAUNCH=1.
-    tv_one_launch = ngroups <= kMaxPartBlocks && std::getenv("ADMM_HIP_TV_ONE_LAUNCH") != nullptr;
-    const size_t extra = tv_one_launch ? static_cast<size_t>(S_COUNT) * kMaxPartBlocks + (ngroups + 2) / 2 + 1 : 0;
+  // one launch per iteration, tile partials (one column per tile) and the deferred tail
+  const bool one_launch = form == TvForm::DIRECT || form == TvForm::FUSED;
+  double* tv_part = nullptr;
+  if (one_launch) {
+    ta.part_stride = round_up(ceil_div(e->n, ta.ftile), 2);
     // (two sets of tile partials: the deferred tail of iteration i reads its set while iteration i + 1 writes the other)
-    const size_t want = 2 * static_cast<size_t>(S_COUNT) * ta.part_stride + extra;
+    const size_t want = 2 * static_cast<size_t>(S_COUNT) * ta.part_stride;
     if (want > e->tv_part_cap) {  // (a per-run hipMalloc / hipFree pair costs more than 100 iterations at n = 2^24)
       ADMM_TRY(e->mem.alloc(&e->tv_part, want));
       e->tv_part_cap = want;
     }
     tv_part = e->tv_part;
     ta.part = tv_part;
-    if (tv_one_launch) {
-      ta.gpart = tv_part + 2 * S_COUNT * ta.part_stride;
-      ta.gcount = reinterpret_cast<int32_t*>(ta.gpart + static_cast<size_t>(S_COUNT) * kMaxPartBlocks);
-      ta.ngroups = static_cast<int32_t>(ngroups);
-      ADMM_HIP_TRY(hipMemsetAsync(ta.gcount, 0, sizeof(int32_t) * (ngroups + 1), e->stream));
-    }
   }
   fa.g = nullptr;
   fa.x = nullptr;
@@ -422,7 +402,7 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
   }
   const int check_tv = o.check_every > 0 ? o.check_every : (o.domaxiters ? 64 : 8);
   const bool tv_relaxed = o.relax != 1.0;
-  if (alg != 0 || tv_relaxed) {
+  if (form == TvForm::UNFUSED) {
     // Fast / accelerated ADMM (admm.m:267-298, 563-600): the x-update takes (v, uhat), the generic fused prox
     // kernel does the z/u update, extrapolation, histories and partial sums on the vector D*x, and the D'
     // stencils of the dual residual come from dz = z - zprev and u.  z, u are updated in place here.
@@ -494,132 +474,90 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
     }
     ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
-    {
-      hipError_t le = hipGetLastError();
-      if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
-    }
-    if (e->profiling) collect_timers(e);
-    const int32_t stepsf = e->ctrl_host->steps;
-    e->last = admm_run_summary{};
-    e->last.steps = stepsf;
-    e->last.stopped_early = (stepsf < N) ? 1 : 0;
-    e->last.convtest_failed_at = e->ctrl_host->convfail;
-    e->last.runtime_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0f).count();
-    e->last.objopt = NAN;
-    if (o.objevals && stepsf > 0) {
-      double v = NAN;
-      ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (stepsf - 1), sizeof(double), hipMemcpyDeviceToHost));
-      e->last.objopt = v;
-    }
-    e->has_run = true;
-    if (summary) *summary = e->last;
-    return ADMM_OK;
+    return finish_tv_run(e, o, N, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0f).count(),
+                         summary);
   }
   const auto t0 = std::chrono::steady_clock::now();
   int32_t done = 0;
   bool stop_seen = false;
-  // x only leaves the fused kernel when its history is recorded; otherwise one backward sweep after the loop
-  // rebuilds the final x from the forward-sweep vector the last executed iteration read (still intact: every
-  // launch after the stop flag is a no-op, and an iteration writes the OTHER y buffer)
-  ta.skip_x = (tv_fused && !e->xhist) ? 1 : 0;
-  if (tv_direct) ta.skip_x = 0;  // (x leaves the direct kernel only as a history column)
-  if (tv_fused && !tv_direct) {  // the forward sweep of iteration 0; every later one is produced by the fused kernel
+  // x only leaves the 7-pass kernel when its history is recorded; otherwise one backward sweep after the loop rebuilds
+  // the final x from the forward-sweep vector the last executed iteration read (x leaves the direct kernels only as a
+  // history column; the final x is recomputed after the loop)
+  ta.skip_x = (form == TvForm::FUSED && !e->xhist) ? 1 : 0;
+  if (form == TvForm::FUSED) {  // the forward sweep of iteration 0; every later one is produced by the fused kernel
     TimerScope ts(e, ADMM_K_XSOLVE);
     ta.z = e->tv_zA;
     ta.u = e->tv_uA;
     ta.y = e->tv_y;
     launch_tv_sweep(ta, false, e->ctrl, e->stream);
   }
-  // Deferred tail (default for the fused kernel): the tile-partial sums and the finalize logic of iteration i are done by
-  // one extra workgroup of iteration i + 1's launch, hidden behind its tiles; a batch's last iteration gets the two
-  // small launches.  A stop raised by that workgroup makes iteration i + 2 a no-op; iteration i + 1 has run
-  // speculatively into the OTHER ping-pong buffers, and the final z, u, x are picked by the device's step count.
-  const bool tv_deferred = tv_fused && !tv_one_launch && std::getenv("ADMM_HIP_NO_DEFERRED_FINALIZE") == nullptr;
+  // Deferred tail of the one-launch forms: the tile-partial sums and the finalize logic of iteration i are done by one
+  // extra workgroup of iteration i + 1's launch, hidden behind its tiles; a batch's last iteration gets the two small
+  // launches.  A stop raised by that workgroup makes iteration i + 2 a no-op; iteration i + 1 has run speculatively
+  // into the OTHER ping-pong buffers, and the final z, u, x are picked by the device's step count.
   // ... and the forward-sweep vector iteration i read must survive iteration i + 1 (the final x is rebuilt from it when
-  // no history holds x): three y buffers in rotation instead of two.  The direct kernel has no y and carries the
+  // no history holds x): three y buffers in rotation instead of two.  The direct kernels have no y and carry the
   // compact state v = z + u (tv.hip): iteration 0 reads z, u from buffer A, iteration k reads v from vbuf[(k-1) % 3]
   // and writes vbuf[k % 3] -- three buffers, so that the speculative iteration behind a stop overwrites neither the
   // last executed iteration's output nor its input (the final x is recomputed from the z, u it read).
-  if (tv_deferred && !tv_direct && !e->tv_y3) ADMM_TRY(e->mem.alloc(&e->tv_y3, round_up(e->n, 2)));
-  if (tv_direct && !e->tv_v3) ADMM_TRY(e->mem.alloc(&e->tv_v3, round_up(e->n, 2)));
-  double* const tv_y3 = e->tv_y3;
-  double* const tv_v3 = e->tv_v3;
-  double* const ybuf[3] = {e->tv_y, e->tv_y2, tv_y3};
-  double* const vbuf[3] = {e->tv_zB, e->tv_uB, tv_v3};
-  const int64_t tv_ntiles = tv_fused ? ceil_div(e->n, ta.ftile) : 0;
+  if (form == TvForm::FUSED && !e->tv_y3) ADMM_TRY(e->mem.alloc(&e->tv_y3, round_up(e->n, 2)));
+  if (form == TvForm::DIRECT && !e->tv_v3) ADMM_TRY(e->mem.alloc(&e->tv_v3, round_up(e->n, 2)));
+  double* const ybuf[3] = {e->tv_y, e->tv_y2, e->tv_y3};
+  double* const vbuf[3] = {e->tv_zB, e->tv_uB, e->tv_v3};
+  const int64_t tv_ntiles = one_launch ? ceil_div(e->n, ta.ftile) : 0;
   const int64_t tv_pset = static_cast<int64_t>(S_COUNT) * ta.part_stride;
   bool tv_pending = false;
   while (done < N && !stop_seen) {
     const int32_t batch = (N - done < check_tv) ? N - done : check_tv;
     for (int32_t b = 0; b < batch; ++b) {
-      const bool a_cur = ((done + b) & 1) == 0;  // iteration k reads A when k is even
+      const int64_t k = done + b;
+      const bool a_cur = (k & 1) == 0;  // iteration k reads A when k is even
       ta.z = a_cur ? e->tv_zA : e->tv_zB;
       ta.u = a_cur ? e->tv_uA : e->tv_uB;
       ta.zo = a_cur ? e->tv_zB : e->tv_zA;
       ta.uo = a_cur ? e->tv_uB : e->tv_uA;
-      int nblk = 1;
-      if (tv_fused) {
-        TimerScope ts(e, ADMM_K_XSOLVE);
-        ta.yin = a_cur ? e->tv_y : e->tv_y2;
-        ta.yout = a_cur ? e->tv_y2 : e->tv_y;
-        fa.nblk = nblk;
-        if (tv_direct) {
-          const int64_t k = done + b;
-          ta.state_in = k > 0 ? 1 : 0;
-          ta.z = k > 0 ? vbuf[(k - 1) % 3] : e->tv_zA;
-          ta.u = k > 0 ? nullptr : e->tv_uA;
-          ta.zo = vbuf[k % 3];
-          ta.uo = nullptr;
-          ta.deferred = tv_deferred ? 1 : 0;
-          ta.iter_host = k;
-          ta.part = tv_part + (k & 1) * tv_pset;
-          ta.prev_part = tv_part + ((k + 1) & 1) * tv_pset;
-          ta.prev_ntiles = static_cast<int32_t>(tv_ntiles);
-          ta.slots16 = e->red;
-          ta.fin_pending = tv_pending ? 1 : 0;
-          fa.slots_reduced = e->red;
-          launch_tv_direct(ta, fa, e->ctrl, e->stream);
-          if (tv_deferred) {
-            tv_pending = true;
-            continue;
-          }
-          launch_tv_pack(ta.part, ta.part_stride, static_cast<int32_t>(tv_ntiles), e->red, e->ctrl, e->stream);
-        } else if (tv_deferred) {
-          const int64_t k = done + b;
-          ta.yin = ybuf[k % 3];
-          ta.yout = ybuf[(k + 1) % 3];
-          ta.deferred = 1;
-          ta.iter_host = k;
-          ta.part = tv_part + (k & 1) * tv_pset;
-          ta.prev_part = tv_part + ((k + 1) & 1) * tv_pset;
-          ta.prev_ntiles = static_cast<int32_t>(tv_ntiles);
-          ta.slots16 = e->red;
-          ta.fin_pending = tv_pending ? 1 : 0;
-          fa.slots_reduced = e->red;
-          launch_tv_fused(ta, fa, e->red, e->ctrl, e->stream);
-          tv_pending = true;
-          continue;
-        }
-        if (!tv_direct) launch_tv_fused(ta, fa, e->red, e->ctrl, e->stream);
-        if (tv_one_launch) continue;  // the launch ended the iteration itself
-        fa.slots_reduced = e->red;
-      } else {
+      if (form == TvForm::SWEEP) {
+        int nblk = 1;
         {
           TimerScope ts(e, ADMM_K_XSOLVE);
           launch_tv_sweep(ta, false, e->ctrl, e->stream);
           launch_tv_sweep(ta, true, e->ctrl, e->stream);
         }
-        TimerScope ts(e, ADMM_K_PROX);
-        launch_tv_prox(ta, e->ctrl, &nblk, e->stream);
-      }
-      fa.nblk = nblk;
-      {
+        {
+          TimerScope ts(e, ADMM_K_PROX);
+          launch_tv_prox(ta, e->ctrl, &nblk, e->stream);
+        }
+        fa.nblk = nblk;
         TimerScope ts(e, ADMM_K_FINALIZE);
         launch_finalize(fa, e->stream);
+        continue;
       }
+      TimerScope ts(e, ADMM_K_XSOLVE);
+      ta.deferred = 1;
+      ta.iter_host = k;
+      ta.part = tv_part + (k & 1) * tv_pset;
+      ta.prev_part = tv_part + ((k + 1) & 1) * tv_pset;
+      ta.prev_ntiles = static_cast<int32_t>(tv_ntiles);
+      ta.slots16 = e->red;
+      ta.fin_pending = tv_pending ? 1 : 0;
+      fa.nblk = 1;
+      fa.slots_reduced = e->red;
+      if (form == TvForm::DIRECT) {
+        ta.state_in = k > 0 ? 1 : 0;
+        ta.z = k > 0 ? vbuf[(k - 1) % 3] : e->tv_zA;
+        ta.u = k > 0 ? nullptr : e->tv_uA;
+        ta.zo = vbuf[k % 3];
+        ta.uo = nullptr;
+        launch_tv_direct(ta, fa, e->ctrl, e->stream);
+      } else {
+        ta.yin = ybuf[k % 3];
+        ta.yout = ybuf[(k + 1) % 3];
+        launch_tv_fused(ta, fa, e->ctrl, e->stream);
+      }
+      tv_pending = true;
     }
     done += batch;
-    if (tv_deferred && tv_pending) {  // the batch's last iteration: its tail as two small launches
+    if (tv_pending) {  // the batch's last iteration: its tail as two small launches
       launch_tv_pack(tv_part + ((done - 1) & 1) * tv_pset, ta.part_stride, static_cast<int32_t>(tv_ntiles), e->red, e->ctrl,
                      e->stream);
       fa.slots_reduced = e->red;
@@ -635,19 +573,14 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
   }
   ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
   ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
-  {
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
-  }
-  if (e->profiling) collect_timers(e);
   const int32_t steps = e->ctrl_host->steps;
-  if (tv_deferred && !tv_direct && !ta.skip_x && e->xhist && steps > 0)  // x was overwritten by the speculative iteration after a stop
-    ADMM_HIP_TRY(hipMemcpyAsync(e->x, e->xhist + static_cast<int64_t>(steps - 1) * e->n, sizeof(double) * e->n,
-                                hipMemcpyDeviceToDevice, e->stream));
   // iterations executed on the device decide which ping-pong buffer holds the final z, u
   e->z = (steps & 1) ? e->tv_zB : e->tv_zA;
   e->u = (steps & 1) ? e->tv_uB : e->tv_uA;
-  if (tv_direct) {
+  if (one_launch && e->xhist && steps > 0)  // x was overwritten by the speculative iteration after a stop
+    ADMM_HIP_TRY(hipMemcpyAsync(e->x, e->xhist + static_cast<int64_t>(steps - 1) * e->n, sizeof(double) * e->n,
+                                hipMemcpyDeviceToDevice, e->stream));
+  if (form == TvForm::DIRECT) {
     if (!e->xhist && steps > 0) {  // x of the last executed iteration, from the z, u it read: two stand-alone sweeps
       if (steps > 1) launch_tv2d_expand(vbuf[(steps - 2) % 3], ta.thresh, e->n, e->tv_zA, e->tv_uA, e->stream);
       ta.z = e->tv_zA;
@@ -657,9 +590,6 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
       ta.xhist = nullptr;
       launch_tv_sweep(ta, false, e->ctrl_idle, e->stream);  // the loop's own flag says "stopped" by now
       launch_tv_sweep(ta, true, e->ctrl_idle, e->stream);
-    } else if (e->xhist && steps > 0) {
-      ADMM_HIP_TRY(hipMemcpyAsync(e->x, e->xhist + static_cast<int64_t>(steps - 1) * e->n, sizeof(double) * e->n,
-                                  hipMemcpyDeviceToDevice, e->stream));
     }
     // z, u of the last executed iteration out of its compact state, into buffer A
     if (steps > 0) launch_tv2d_expand(vbuf[(steps - 1) % 3], ta.thresh, e->n, e->tv_zA, e->tv_uA, e->stream);
@@ -668,25 +598,11 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
   }
   if (ta.skip_x && steps > 0) {
-    ta.y = tv_deferred ? ybuf[(steps - 1) % 3] : (((steps - 1) & 1) ? e->tv_y2 : e->tv_y);
+    ta.y = ybuf[(steps - 1) % 3];
     launch_tv_sweep(ta, true, e->ctrl_idle, e->stream);  // the loop's own flag says "stopped" by now
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
   }
-  const double rt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  e->last = admm_run_summary{};
-  e->last.steps = steps;
-  e->last.stopped_early = (steps < N) ? 1 : 0;
-  e->last.convtest_failed_at = e->ctrl_host->convfail;
-  e->last.runtime_s = rt;
-  e->last.objopt = NAN;
-  if (o.objevals && steps > 0) {
-    double v = NAN;
-    ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (steps - 1), sizeof(double), hipMemcpyDeviceToHost));
-    e->last.objopt = v;
-  }
-  e->has_run = true;
-  if (summary) *summary = e->last;
-  return ADMM_OK;
+  return finish_tv_run(e, o, N, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), summary);
 }
 
 }  // namespace admm

@@ -14,16 +14,17 @@
 // instead of waiting for its predecessor -- no inter-workgroup communication, pure streaming.
 // The D / D' stencils and the rhs assembly are fused into the sweeps and the prox kernel.
 //
-// Three forms of an iteration, chosen by engine_run_tv.hip:
-//   tv_direct_kernel   (default, small halo)  one launch, 5 vector passes: away from the two ends of the matrix the
-//                      solve is the truncated two-sided exponential kernel of the Toeplitz operator, evaluated per
-//                      thread from LDS without scans; only the two end tiles run the recurrences (as block scans)
-//   tv_fused_kernel    one launch, 7 passes: this iteration's backward sweep + z/u update + the NEXT iteration's
-//                      forward sweep, the intermediate y travelling between launches (ADMM_HIP_TV_SCAN=1)
-//   tv_sweep x 2 + tv_prox   three launches (large halos: rho >~ 16), and the building blocks of the fast /
+// Forms of an iteration; engine_run_tv.hip picks one per run from the halo, n and the variant (tv_form):
+//   tv_direct2_kernel / tv_direct_kernel   (plain ADMM, halo <= 248)  one launch, 3 to 5 vector passes: away from the
+//                      two ends of the matrix the solve is the truncated two-sided exponential kernel of the Toeplitz
+//                      operator, evaluated per thread without scans.  tv_direct2 (tv_direct2.h) mirrors both ends;
+//                      tv_direct_kernel, whose end tiles run the recurrences as block scans, takes signals shorter
+//                      than two window margins, where a mirror image would reach past the other end
+//   tv_fused_kernel    (plain ADMM, halo 250..256 -- too wide for the direct kernels' margin -- or n = 1)  one launch,
+//                      7 passes: this iteration's backward sweep + z/u update + the NEXT iteration's forward sweep,
+//                      the intermediate y travelling between launches
+//   tv_sweep x 2 + tv_prox   three launches (halo > 256: rho >~ 37), and the building blocks of the fast /
 //                      accelerated / relaxed variants (tv_dx, tv_dual, tv_relax_z around the generic prox kernel)
-#include <cstdlib>
-
 #include "kernels.h"
 #include "loop_kernels.h"
 #include "tv.h"
@@ -344,10 +345,9 @@ __device__ __forceinline__ void tv_block_scan(double* __restrict__ lds, int coun
 // (r2: issuing every global load of a tile -- z, u, s pairs and the wave-boundary neighbours -- before the first scan
 // costs 40 more VGPRs: 3 workgroups per CU instead of 4 and 0.2390 against 0.2331 ms per iteration on the same box,
 // 2 workgroups 0.3165.  Residency, not the number of dependent load rounds inside a workgroup, carries this kernel.)
-template <int E, int MODE>  // MODE 0: default stores; 1: streaming stores; 2: + s kept cacheable; 3: + y kept cacheable; 4: both
+template <int E, bool NTS>  // NTS: streaming stores
 __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs fin, const Ctrl* __restrict__ ctrl) {
   if (ctrl->stop) return;
-  __shared__ int32_t tail_group, tail_all;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   constexpr int kCap = E * kBlock;
   double* __restrict__ L1 = lds;                        // y/b -> x (backward positions)
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
       const bool live0 = 2 * j < count, live1 = 2 * j + 1 < count;
       double y0 = 0.0, y1 = 0.0;
       if (live1) {
-        const admm_double2 yy = load2<!(MODE == 3 || MODE == 4)>(a.yin + i0);
+        const admm_double2 yy = load2<true>(a.yin + i0);
         y0 = yy.x;
         y1 = yy.y;
       } else if (live0) {
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
         double zp0, zp1 = 0.0;
         if (live1) {
           const admm_double2 zz = load2<true>(a.z + i0), uu = load2<true>(a.u + i0),
-                             ss = load2<!(MODE == 2 || MODE == 4)>(a.s + i0);
+                             ss = load2<true>(a.s + i0);
           zp0 = zz.x;
           zp1 = zz.y;
           uo0 = uu.x;
@@ -512,7 +512,6 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
           }
         }
         if (own0 && own1) {
-          constexpr bool NTS = MODE != 0;
           if (!a.skip_x) store2<NTS>(a.x + i0, admm_double2{x0, x1});
           store2<NTS>(a.zo + i0, admm_double2{zn0, zn1});
           store2<NTS>(a.uo + i0, admm_double2{un0, un1});
@@ -552,8 +551,7 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
     if (threadIdx.x < S_COUNT) {
       const int s = threadIdx.x;
       const double t = ((sred[0][s] + sred[1][s]) + sred[2][s]) + sred[3][s];
-      if (a.gcount) __hip_atomic_store(a.part + s * a.part_stride + blockIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else a.part[s * a.part_stride + tile_id] = t;
+      a.part[s * a.part_stride + tile_id] = t;
     }
     // ---- 3. forward scan of the next iteration's right-hand side, owned store
     tv_block_scan<E>(L2, fcount, [&](int q) { return tv_coef<false>(a, f0 + q, n, rho, cstar); }, wA, wB);
@@ -563,68 +561,13 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
       const int64_t i0 = f0 + 2 * static_cast<int64_t>(j);
       const bool own0 = 2 * j < fcount && i0 >= o0, own1 = 2 * j + 1 < fcount && i0 + 1 >= o0;
       if (own0 && own1) {
-        store2<(MODE == 1 || MODE == 2)>(a.yout + i0, admm_double2{L2[qf(i0)], L2[qf(i0 + 1)]});
+        store2<NTS>(a.yout + i0, admm_double2{L2[qf(i0)], L2[qf(i0 + 1)]});
       } else {
         if (own0) a.yout[i0] = L2[qf(i0)];
         if (own1) a.yout[i0 + 1] = L2[qf(i0 + 1)];
       }
     }
   }
-  if (!a.gcount) return;
-  // ---- 4. tail of the one-launch iteration.  This tile's partials were published write-through in step 2; once the
-  // wave that stored them has drained, the tile arrives at its group.  (Arriving mid-kernel, right after step 2, was
-  // measured slower -- 0.2446 against 0.2349 ms per iteration with the two extra launches: the drain of the z/u
-  // stores then stalls wave 0 in front of the barriers of step 3's scan, in every tile.)  The last tile to arrive
-  // implies every tile has started and read ctrl at its top, so the finalize logic may advance ctrl.
-  if (wid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0) {
-      const int32_t g = static_cast<int32_t>(blockIdx.x) / kTvGroup;
-      const int32_t ntiles = static_cast<int32_t>(gridDim.x);
-      const int32_t gsize = (ntiles - g * kTvGroup < kTvGroup) ? ntiles - g * kTvGroup : kTvGroup;
-      const int32_t old = __hip_atomic_fetch_add(a.gcount + g, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      tail_group = (old == gsize - 1) ? 1 : 0;
-      if (tail_group) __hip_atomic_store(a.gcount + g, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
-  if (!tail_group) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  {  // this workgroup arrived last in its group: the group's partials, tile order, 16 lanes per slot
-    const int32_t g = static_cast<int32_t>(blockIdx.x) / kTvGroup;
-    const int32_t t0 = g * kTvGroup;
-    const int32_t ntiles = static_cast<int32_t>(gridDim.x);
-    const int32_t gsize = (ntiles - t0 < kTvGroup) ? ntiles - t0 : kTvGroup;
-    const int slot = tid >> 4, sub = tid & 15;
-    double v = 0.0;
-    if (slot < S_COUNT) {
-      const double* __restrict__ ps = a.part + slot * a.part_stride + t0;
-      double w[kTvGroup / 16];
-#pragma unroll
-      for (int k = 0; k < kTvGroup / 16; ++k) {
-        const int b = sub + 16 * k;
-        w[k] = __hip_atomic_load(ps + (b < gsize ? b : gsize - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int k = 0; k < kTvGroup / 16; ++k)
-        if (sub + 16 * k < gsize) v += w[k];
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (slot < S_COUNT && sub == 0)
-      __hip_atomic_store(a.gpart + slot * kMaxPartBlocks + g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const int32_t old = __hip_atomic_fetch_add(a.gcount + a.ngroups, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      tail_all = (old == a.ngroups - 1) ? 1 : 0;
-      if (tail_all) __hip_atomic_store(a.gcount + a.ngroups, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-  }
-  if (!tail_all) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  finalize_body<true>(fin);  // fin.part = gpart, fin.nblk = ngroups
 }
 
 // ---------------------------------------------------------------- one launch per iteration WITHOUT the y vector
@@ -1031,9 +974,8 @@ bool tv_direct_ok(const TvArgs& a) { return a.elems == 8 && a.halo >= 2 && tv_di
 void launch_tv_direct(const TvArgs& a, const FinArgs& fin, const Ctrl* ctrl, hipStream_t stream) {
   const int64_t ntiles = ceil_div(a.n, a.ftile);
   // thread-owned runs (tv_direct2.h) unless the signal is shorter than two margins (the mirror images of an end would
-  // reach past the other end) or ADMM_HIP_TV_DIRECT1 asks for the first form
-  const bool first_form = std::getenv("ADMM_HIP_TV_DIRECT1") != nullptr;
-  if (!first_form && a.n >= 2 * static_cast<int64_t>(a.margin)) {
+  // reach past the other end): then tv_direct_kernel, whose end tiles run the exact recurrences
+  if (a.n >= 2 * static_cast<int64_t>(a.margin)) {
     const size_t lds2 = sizeof(double) * tv2_lds_doubles<4>();
     const dim3 grid2(static_cast<unsigned>(ntiles) + (a.deferred ? 1u : 0u)), block2(kBlock);
     const bool nts2 = stream_hint(8 * 8 * a.n), extra = a.objevals || a.xhist;
@@ -1161,32 +1103,15 @@ void launch_tv_dual(const double* dz, const double* u, int64_t n, double* part, 
 
 bool tv_fused_ok(const TvArgs& a) { return a.elems == 8 && a.ftile >= 512; }
 
-void launch_tv_fused(const TvArgs& a, const FinArgs& fin, double* slots16, const Ctrl* ctrl, hipStream_t stream) {
+void launch_tv_fused(const TvArgs& a, const FinArgs& fin, const Ctrl* ctrl, hipStream_t stream) {
   const int64_t ntiles = ceil_div(a.n, a.ftile);
   constexpr int kCap = 8 * kBlock;
   const size_t lds = 2 * static_cast<size_t>(kCap + (kCap >> 4) + 1) * sizeof(double);
   // streaming stores once the eight vectors of an iteration cannot stay cache-resident: +7 % at n = 4096^2
   const bool nts = stream_hint(8 * 8 * a.n);
-  FinArgs f = fin;
-  if (a.gcount) {  // one-launch iteration: the finalize logic reads the group partials
-    f.part = a.gpart;
-    f.nblk = a.ngroups;
-    f.slots_reduced = nullptr;
-  }
-  int mode = nts ? 1 : 0;
-  if (nts)
-    if (const char* env = getenv("ADMM_HIP_TV_CACHE")) mode = atoi(env);
   const dim3 grid(static_cast<unsigned>(ntiles) + (a.deferred ? 1u : 0u)), block(kBlock);
-  switch (mode) {
-    case 0: hipLaunchKernelGGL((tv_fused_kernel<8, 0>), grid, block, lds, stream, a, f, ctrl); break;
-    case 2: hipLaunchKernelGGL((tv_fused_kernel<8, 2>), grid, block, lds, stream, a, f, ctrl); break;
-    case 3: hipLaunchKernelGGL((tv_fused_kernel<8, 3>), grid, block, lds, stream, a, f, ctrl); break;
-    case 4: hipLaunchKernelGGL((tv_fused_kernel<8, 4>), grid, block, lds, stream, a, f, ctrl); break;
-    default: hipLaunchKernelGGL((tv_fused_kernel<8, 1>), grid, block, lds, stream, a, f, ctrl); break;
-  }
-  if (a.gcount || a.deferred) return;
-  hipLaunchKernelGGL(tv_pack_kernel, dim3(S_COUNT), dim3(kBlock), 0, stream, a.part, a.part_stride,
-                     static_cast<int32_t>(ntiles), slots16, ctrl);
+  if (nts) hipLaunchKernelGGL((tv_fused_kernel<8, true>), grid, block, lds, stream, a, fin, ctrl);
+  else hipLaunchKernelGGL((tv_fused_kernel<8, false>), grid, block, lds, stream, a, fin, ctrl);
 }
 
 void launch_tv_pack(const double* part, int64_t stride, int32_t ntiles, double* slots16, const Ctrl* ctrl,

@@ -502,13 +502,24 @@ def test_equality_constrained_solvers_with_a_zero_right_hand_side(gpu, rows, col
     (3, 0.21, 430.0, dict(maxiters=33, domaxiters=1)), (10, 6.0, 4800.0, dict(maxiters=23)),
     (3000, 1.0, 6000.0, dict(maxiters=12, domaxiters=1)),
     (30000, 1.0, 30000.0, dict(maxiters=6, domaxiters=1)),  # halo ~ 7200 of a workgroup's 12288 positions
+    (200, 1.0, 1.0, dict(maxiters=40)), (5000, 1.0, 1.0, dict(maxiters=40)),  # tv_direct2 (stops at 26 / runs 40)
+    (300011, 1.0, 1.0, dict(maxiters=40)),
+    (400, 1.0, 30.0, dict(maxiters=60)),            # n < 2 * margin (240): tv_direct_kernel, both ends by block scans
+    # halo 250 (rho = 35) / 256 (rho = 36.5): too wide for the direct kernels' margin, still one 8-element tile -- the
+    # 7-pass tv_fused_kernel.  With history x comes from the kernel; without, from one backward sweep after the loop.
+    # Stopping at 207 (inside a batch of 8: an iteration has run speculatively behind the stop) and at 216.
+    (4099, 1.0, 35.0, dict(stopcond="both", reltol=1e-2, maxiters=300, record_history=0)),
+    (4099, 1.0, 36.5, dict(stopcond="both", reltol=1e-2, maxiters=300)),
+    (50000, 1.0, 35.0, dict(maxiters=25, domaxiters=1)),
+    (50000, 1.0, 36.5, dict(maxiters=25, domaxiters=1, record_history=0)),
 ])
 def test_total_variation(gpu, n, lam, rho, opts):
     p = gpu.synth.tv_problem(n % 97, n)
     o = dict(objevals=1, rho=rho, **opts)
     got = gpu.totalvariation(p["s"], lam, o)
-    ref = S.totalvariation(p["s"], lam, o)
-    _compare(got, ref)
+    ref = S.totalvariation(p["s"], lam, {k: v for k, v in o.items() if k != "record_history"})
+    _compare(got, ref, HIST if o.get("record_history", 1) else ("pnorm", "dnorm", "perr", "derr", "objevals", "xopt",
+                                                                 "zopt", "uopt"))
     if n == 128:  # totalvariationtest.m:151
         obj = lambda x: 0.5 * np.sum((x - p["s"]) ** 2) + lam * np.sum(np.abs(np.diff(x)))
         assert obj(got["xopt"]) < obj(p["truex"])
@@ -684,18 +695,17 @@ def test_relax_with_svm_is_rejected(gpu):
         gpu.linearsvm(p["D"], p["ell"], p["C"], dict(relax=1.5, x0=p["x0"], z0=p["z0"], u0=p["u0"]))
 
 
-def test_tv_fused_equals_three_kernel_form_large(gpu, monkeypatch):
-    """n large enough for > 1024 tiles: the fused iteration kernel (one launch, per-tile partial sums packed
-    by a second kernel) against the forward / backward / prox kernels it replaces."""
-    n = 3_000_001  # odd: exercises the unpaired tail
+def test_total_variation_large_matches_the_banded_oracle(gpu):
+    """3e6 + 1 elements (odd: the unpaired tail and the thread run the end cuts; 1550 tiles of tv_direct2, more than
+    1024 tile partials for the deferred tail) against the oracle's banded Cholesky solve, 12 iterations"""
+    n = 3_000_001
     p = gpu.synth.tv_problem(4, n)
-    o = dict(maxiters=12, domaxiters=1, objevals=1, record_history=0)
-    a = gpu.totalvariation(p["s"], p["lam"], dict(o))
-    monkeypatch.setenv("ADMM_HIP_TV_UNFUSED", "1")
-    b = gpu.totalvariation(p["s"], p["lam"], dict(o))
-    assert a["steps"] == b["steps"] == 12
+    o = dict(maxiters=12, domaxiters=1, objevals=1)
+    got = gpu.totalvariation(p["s"], p["lam"], dict(o, record_history=0))
+    ref = S.totalvariation(p["s"], p["lam"], dict(o, banded=1))
+    assert got["steps"] == ref["steps"] == 12
     for k in ("pnorm", "dnorm", "perr", "derr", "objevals", "xopt", "zopt", "uopt"):
-        _close(k, a[k], b[k], 1e-11)
+        _close(k, got[k], ref[k], 1e-9)
 
 
 @pytest.mark.parametrize("n", [112, 113, 127, 1935, 1936, 1937, 3 * 1936 - 1, 3 * 1936, 3 * 1936 + 1, 3 * 1936 + 7,
@@ -714,18 +724,6 @@ def test_total_variation_thread_run_kernel_tile_boundaries(gpu, n, rho):
         assert got["steps"] == ref["steps"]
         for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr"):
             _close(k, got[k], ref[k], TOL, None)
-
-
-def test_total_variation_thread_run_kernel_equals_first_form(gpu, monkeypatch):
-    """the two direct kernels on 3e6 + 1 elements (odd: the cut run; 1550 tiles), 1e-11"""
-    n = 3_000_001
-    p = gpu.synth.tv_problem(5, n)
-    o = dict(maxiters=12, domaxiters=1, objevals=1, record_history=0)
-    a = gpu.totalvariation(p["s"], p["lam"], dict(o))
-    monkeypatch.setenv("ADMM_HIP_TV_DIRECT1", "1")
-    b = gpu.totalvariation(p["s"], p["lam"], dict(o))
-    for k in ("pnorm", "dnorm", "perr", "derr", "objevals", "xopt", "zopt", "uopt"):
-        _close(k, a[k], b[k], 1e-11)
 
 
 # ---------------------------------------------------------------------------- golden fixtures
@@ -778,18 +776,6 @@ def test_golden_fixture(gpu, path):
     for k in HIST:
         if k in ref:
             _close(k, got[k], ref[k], tol)
-
-
-def test_total_variation_one_launch_iteration(gpu, monkeypatch):
-    """the opt-in form of the fused TV iteration whose reduction tree and finalize logic run inside the one kernel
-    (last tile of a group sums the group, last group finalizes): same iterates and histories as the oracle"""
-    monkeypatch.setenv("ADMM_HIP_TV_ONE_LAUNCH", "1")
-    for n in (200, 5000, 300011):
-        p = gpu.synth.tv_problem(3, n)
-        o = dict(objevals=1, maxiters=40)
-        got = gpu.totalvariation(p["s"], p["lam"], dict(o))
-        ref = S.totalvariation(p["s"], p["lam"], dict(o))
-        _compare(got, ref)
 
 
 def test_consensus_lasso_partial_row_gather_path(gpu):
@@ -940,18 +926,18 @@ def test_lasso_objective_switches_to_the_gram_form_after_calibration(gpu):
 
 
 @pytest.mark.parametrize("opts", [dict(objevals=1), dict(record_history=0), dict(record_history=0, maxiters=11, domaxiters=1),
-                                  dict(stopcond="both", convtest=1, maxiters=90), dict(rho=3.0, objevals=1, maxiters=37)])
+                                  dict(stopcond="both", convtest=1, maxiters=90), dict(rho=3.0, objevals=1, maxiters=37),
+                                  dict(rho=36.0, objevals=1, maxiters=37), dict(rho=36.0, record_history=0, maxiters=29)])
 @pytest.mark.parametrize("n", [4099, 50000])
-def test_total_variation_deferred_tail_matches_the_two_small_launches(gpu, monkeypatch, n, opts):
-    """1-D TV, fused kernel: the tile-partial sums and the finalize logic of iteration i ride along with iteration i + 1's
-    launch (one extra workgroup); the iteration after a stop has then run speculatively into the other ping-pong buffers
-    (three y buffers in rotation), and z, u, x are still those of the stopping iteration -- bitwise the results of the
-    form with two small launches per iteration, and the oracle's."""
+def test_total_variation_deferred_tail_matches_the_two_small_launches(gpu, n, opts):
+    """1-D TV, one-launch forms: the tile-partial sums and the finalize logic of iteration i ride along with iteration
+    i + 1's launch (one extra workgroup); the iteration after a stop has then run speculatively into the other ping-pong
+    buffers (three v or y buffers in rotation), and z, u, x are still those of the stopping iteration -- bitwise the results of polling after every
+    iteration (check_every = 1: each iteration's tail is the two small launches, nothing runs past a stop), and the
+    oracle's."""
     p = gpu.synth.tv_problem(3, n)
     got = gpu.totalvariation(p["s"], p["lam"], dict(opts))
-    monkeypatch.setenv("ADMM_HIP_NO_DEFERRED_FINALIZE", "1")
-    two = gpu.totalvariation(p["s"], p["lam"], dict(opts))
-    monkeypatch.delenv("ADMM_HIP_NO_DEFERRED_FINALIZE")
+    two = gpu.totalvariation(p["s"], p["lam"], dict(opts, check_every=1))
     assert got["steps"] == two["steps"]
     for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr", "xvals", "zvals", "uvals", "objevals"):
         assert (k in got) == (k in two), k

@@ -198,15 +198,19 @@ def test_tv2d_compact_state_with_arbitrary_start(gpu, H, W, iters):
                                       (128, 512, dict(maxiters=21, domaxiters=1, record_history=0)),
                                       (512, 384, dict(objevals=1, rho=2.0, maxiters=12, domaxiters=1)),
                                       (8192, 192, dict(objevals=1, maxiters=5, domaxiters=1))])          # 128 KB of LDS
-def test_tv2d_fused_pass_into_the_forward_transform(gpu, H, W, opts, monkeypatch):
-    """default spectral form: the fused pass hands its right-hand side to the forward column DCT inside one kernel
+def test_tv2d_fused_pass_into_the_forward_transform(gpu, H, W, opts):
+    """glued spectral form: the fused pass hands its right-hand side to the forward column DCT inside one kernel
     (dct.hip: tv2d_fused_dct_kernel; three launches per iteration, the row stage carries the deferred finalize) --
-    the same arithmetic per pixel as the four-launch form (ADMM_HIP_TV2D_NO_GLUE=1): the same iterates bit for bit"""
+    against the oracle, and bit for bit the iterates of polling after every iteration (check_every = 1: every
+    iteration's finalize is its own launch, nothing runs past a stop)"""
     img = _image(3 * H + W, H, W)
     got = gpu.totalvariation2d(img, 0.45, dict(opts))
-    monkeypatch.setenv("ADMM_HIP_TV2D_NO_GLUE", "1")
-    old = gpu.totalvariation2d(img, 0.45, dict(opts))
-    assert got["steps"] == old["steps"] and got["cg_iters_total"] == 0
+    ref = S.totalvariation2d(img, 0.45, {k: v for k, v in opts.items() if k != "record_history"})
+    assert got["steps"] == ref["steps"] and got["cg_iters_total"] == 0
+    for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm"):
+        _close(k, got[k], ref[k], 1e-8)
+    one = gpu.totalvariation2d(img, 0.45, dict(opts, check_every=1))
+    assert one["steps"] == got["steps"]
     keys = ["xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr"]
     if opts.get("record_history", 1):
         keys += ["xvals", "zvals", "uvals"]
@@ -214,14 +218,9 @@ def test_tv2d_fused_pass_into_the_forward_transform(gpu, H, W, opts, monkeypatch
         keys += ["objevals"]
     for k in keys:
         if k in ("xopt", "zopt", "uopt", "xvals", "zvals", "uvals"):
-            assert np.array_equal(np.asarray(got[k]), np.asarray(old[k])), k
-        else:  # sums over the image: the two kernels cut it into different blocks
-            np.testing.assert_allclose(np.asarray(got[k]), np.asarray(old[k]), rtol=1e-12, atol=0, err_msg=k)
-    if H * W <= 1 << 18:
-        ref = S.totalvariation2d(img, 0.45, {k: v for k, v in opts.items() if k != "record_history"})
-        assert got["steps"] == ref["steps"]
-        for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm"):
-            _close(k, got[k], ref[k], 1e-8)
+            assert np.array_equal(np.asarray(got[k]), np.asarray(one[k])), k
+        else:  # (the passenger and the stand-alone finalize launch sum the same partials)
+            np.testing.assert_allclose(np.asarray(got[k]), np.asarray(one[k]), rtol=1e-12, atol=0, err_msg=k)
 
 
 def test_tv2d_relaxation_is_a_dimension_error(gpu):
