@@ -33,6 +33,19 @@ int fail(int code, const std::string& msg);
     if (_rc != ADMM_OK) return _rc; \
   } while (0)
 
+// ---- environment switches --------------------------------------------------------
+// The only place the library reads the environment (engine.hip has the definition, include/admm_engine.h the
+// user-facing description).  Every call reads the environment anew: tests set and unset a switch between two
+// create / run calls of one process, so nothing here may be cached.
+struct EnvSwitches {
+  bool graph;               // ADMM_HIP_GRAPH: replay batches of iterations as a captured graph (read at run)
+  int trsv_form;            // ADMM_TRSV_FORM=blocked|one: kTrsvBlocked / kTrsvOne (kernels.h), -1 = not forced (create)
+  int xsplit;               // ADMM_HIP_XSPLIT=0|1: the multi-GPU split of the x-solve, -1 = measured decision (create)
+  bool no_unwrapped_fused;  // ADMM_HIP_NO_UNWRAPPED_FUSED: the general A = D iteration, no pinv(D) built (create)
+  bool no_onepass;          // ADMM_HIP_NO_ONEPASS: the general A = D iteration instead of the one-pass form (run)
+};
+EnvSwitches env_switches();
+
 inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

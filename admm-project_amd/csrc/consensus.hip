@@ -1,7 +1,6 @@
 // consensus.hip -- vector kernels of consensus lasso (getProxOps.m:1217-1343).  Each slice k keeps
 // its own x_k, u_k and cached factor; the consensus variable z couples them through the means
 // of x_k and u_k (one all-reduce of 2n doubles when the slices live on several GPUs, X1 in SURVEY).
-#include <cstdlib>
 
 #include "consensus.h"
 #include "loop_kernels.h"
@@ -311,21 +310,13 @@ bool cons_gather_update_ok(const ConsArgs& a) { return a.K >= 1 && a.K <= 16; }
 void launch_cons_gather_update(const ConsArgs& a, const double* npart, const double* tpart, int64_t pstride, int64_t ldp,
                                int32_t ntile, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
   // elements x (slice, row-range) slots per workgroup, for the 52 MB of partial rows of 8 slices at n = 10^4:
-  // 32 x 16: 25.1 us, 64 x 16: 20.9 us (default), 128 x 8 (one slot per slice, 80 rows per thread): 25.4 us
-  static const int tile = [] {
-    const char* ev = std::getenv("ADMM_CONS_TILE");
-    return (ev && std::atoi(ev) == 32) ? 32 : 64;
-  }();
-  int64_t blocks = ceil_div(a.n, int64_t{tile});
+  // 32 x 16: 25.1 us, 64 x 16: 20.9 us (in use), 128 x 8 (one slot per slice, 80 rows per thread): 25.4 us
+  int64_t blocks = ceil_div(a.n, int64_t{64});
   if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
   *nblk_out = static_cast<int>(blocks);
   const dim3 grid(static_cast<unsigned>(blocks));
-  if (tile == 64)
-    hipLaunchKernelGGL((cons_gather_update_kernel<64, 16>), grid, dim3(1024), 0, stream, a, npart, tpart, pstride, ldp, ntile,
-                       ctrl);
-  else
-    hipLaunchKernelGGL((cons_gather_update_kernel<32, 16>), grid, dim3(512), 0, stream, a, npart, tpart, pstride, ldp, ntile,
-                       ctrl);
+  hipLaunchKernelGGL((cons_gather_update_kernel<64, 16>), grid, dim3(1024), 0, stream, a, npart, tpart, pstride, ldp, ntile,
+                     ctrl);
 }
 
 void launch_cons_update(const ConsArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {

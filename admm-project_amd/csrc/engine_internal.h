@@ -290,6 +290,9 @@ struct RunState {
 
 // engine_run.hip
 int cg_solve(admm_engine* e, const double* y);
+// the epilogue every iteration sequence ends with: launch-error check, kernel timers, e->last (and *summary) from
+// e->ctrl_host, which must hold the device's final control block
+int finish_run(admm_engine* e, const admm_options& o, int32_t N, double runtime, admm_run_summary* summary);
 // engine_run_tv.hip: total variation (totalvariation.m) and the 2-D extension
 int cg_solve_tv2d(admm_engine* e, const double* y);
 int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary);

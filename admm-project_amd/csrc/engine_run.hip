@@ -87,6 +87,29 @@ int cg_solve(admm_engine* e, const double* y) {
   return ADMM_OK;
 }
 
+// End of a run: launch errors, kernel timers, the summary with the objective at the last executed iteration
+// (admm.m:752-754).  e->ctrl_host holds the device's final control block.
+int finish_run(admm_engine* e, const admm_options& o, int32_t N, double runtime, admm_run_summary* summary) {
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
+  if (e->profiling) collect_timers(e);
+  const int32_t steps = e->ctrl_host->steps;
+  e->last = admm_run_summary{};
+  e->last.steps = steps;
+  e->last.stopped_early = (steps < N) ? 1 : 0;
+  e->last.convtest_failed_at = e->ctrl_host->convfail;
+  e->last.runtime_s = runtime;
+  e->last.objopt = NAN;
+  if (o.objevals && steps > 0) {
+    double v = NAN;
+    ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (steps - 1), sizeof(double), hipMemcpyDeviceToHost));
+    e->last.objopt = v;
+  }
+  e->has_run = true;
+  if (summary) *summary = e->last;
+  return ADMM_OK;
+}
+
 }  // namespace admm
 
 extern "C" {
@@ -639,14 +662,10 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   xa.rhs_kind = e->xcb ? RHS_NONE : e->rhs_kind;
 
   RunState rs{o, alg, N, len, pa, fa, xa};
-  auto trsv_ok = [&](int rc) -> int {  // the one-launch triangular solves report a lost tile through their plan
-    if (rc != ADMM_OK) return rc;
-    ADMM_TRY(trsv_check_error(e->xfac.trsv, e->stream));
-    ADMM_TRY(trsv_check_error(e->zfac.trsv, e->stream));
-    for (const ConsSlice& sl : e->cslices) ADMM_TRY(trsv_check_error(sl.fac.trsv, e->stream));
+  if (e->problem == ADMM_PROB_LASSO_CONSENSUS) {
+    ADMM_TRY(run_consensus_lasso(e, rs, summary));
     return comm_check_error(e->comm, e->stream);
-  };
-  if (e->problem == ADMM_PROB_LASSO_CONSENSUS) return trsv_ok(run_consensus_lasso(e, rs, summary));
+  }
   if (e->problem == ADMM_PROB_TV2D) return run_total_variation_2d(e, rs, summary);
   if (e->problem == ADMM_PROB_TOTALVARIATION) return run_total_variation(e, rs, summary);
 
@@ -700,7 +719,7 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   // iteration (unwrapped.hip) when nothing outside the fused element update is asked for: plain ADMM, no recorded dual
   // residual (unwrappedadmm.m:92 sets nodualerror), library operators, library objective, one rank.
   const bool uw_fused = e->Dp && e->problem == ADMM_PROB_LINEARSVM && alg == 0 && o.relax == 1.0 && o.nodualerror &&
-                        !sharded && !hooks && !e->xcb && !e->zcb && !e->ocb && std::getenv("ADMM_HIP_NO_UNWRAPPED_FUSED") == nullptr;
+                        !sharded && !hooks && !e->xcb && !e->zcb && !e->ocb;
   UwArgs ua{};
   if (uw_fused) {
     ua.D = e->D;
@@ -737,7 +756,7 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   // the CG x-solve (which polls the device between inner iterations), or with event timing on
   // (hipEventElapsedTime rejects events recorded by graph nodes: "invalid resource handle").
   const int64_t heavy = std::max<int64_t>(e->m * e->n, e->nF * e->nF);
-  const bool use_graph = std::getenv("ADMM_HIP_GRAPH") != nullptr && !sharded && e->profiling == 0 && !uw_fused &&
+  const bool use_graph = env_switches().graph && !sharded && e->profiling == 0 && !uw_fused &&
                          e->xsolve != ADMM_XSOLVE_CG && heavy <= (int64_t{32} << 20) && !e->xcb && !e->zcb && !e->ocb &&
                          !hooks && !(e->problem == ADMM_PROB_COVSEL && e->n > kCovselSmallMax);  // (host checks per sweep)
   // A = I iterations whose finalize depends on nothing but the prox kernel's partial sums end in ONE launch
@@ -772,8 +791,7 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   // (row-sharded A = I engines keep x, z, u replicated and exchange nothing per iteration unless the x-solve's tiles
   // are split over the ranks -- symv_apply's one all-reduce, before this tail: they run the same tail as one rank)
   bool fuse_tail = (e->a_identity || o.nodualerror) && alg != 2 && !split_z && (!sharded || e->a_identity) &&
-                         !obj_kernels && !hooks &&
-                         len <= int64_t{128} * kMaxPartBlocks && std::getenv("ADMM_HIP_NO_FUSED_TAIL") == nullptr;
+                   !obj_kernels && !hooks && len <= int64_t{128} * kMaxPartBlocks;
   // With the packed lower-triangle x-solve in front of it, the finalize logic of an A = I iteration is deferred: the
   // element update stores its block partials and ends; the next iteration's x-solve carries the finalize in one extra
   // workgroup (symv_lower_fin_kernel), where its ~6 us of serial work overlap with 60 us of streaming, and the element
@@ -782,12 +800,11 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
   const bool split_symv = sharded && e->sy_split && e->xfac.mode == ADMM_XSOLVE_INVERSE && e->xfac.Minv && !e->xcb &&
                           (e->problem == ADMM_PROB_LASSO || e->problem == ADMM_PROB_QP_BOUNDED) && !e->fat;
   bool defer_fin = fuse_tail && e->a_identity &&
-                         (((xsolve_has_partials(e) || split_symv) && e->xfac.planSy.packed) || xsolve_tri1_partials(e)) && !use_graph &&
-                         std::getenv("ADMM_HIP_NO_DEFERRED_FINALIZE") == nullptr;
+                   (((xsolve_has_partials(e) || split_symv) && e->xfac.planSy.packed) || xsolve_tri1_partials(e)) &&
+                   !use_graph;
   // A = D iterations without a dual residual (fuse_tail): the finalize logic leaves the element update's launch too and
   // runs as one extra workgroup of the partial-sum launch of D'*(c + z - u) that follows it (gemv.hip)
-  bool defer_fin_ad = fuse_tail && !e->a_identity && e->D && !(e->atcb && !e->D) && !use_graph &&
-                            std::getenv("ADMM_HIP_NO_DEFERRED_FINALIZE") == nullptr;
+  bool defer_fin_ad = fuse_tail && !e->a_identity && e->D && !(e->atcb && !e->D) && !use_graph;
   FinArgs dff{};
   e->dfin = nullptr;
   e->dfin_pending = false;
@@ -1171,10 +1188,6 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
     ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
   }
-  {
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
-  }
   if (uw_fused && e->ctrl_host->steps > 0)  // the x of the last completed iteration (double-buffered on its parity)
   {
     ADMM_HIP_TRY(hipMemcpyAsync(e->x, e->uwX + ((e->ctrl_host->steps - 1) & 1) * e->uwldg, sizeof(double) * e->n,
@@ -1182,34 +1195,22 @@ int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* 
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
   }
   const double runtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
-  if (e->profiling) collect_timers(e);
-  for (auto& t : e->timers) t.used = 0;
-
   if (e->problem == ADMM_PROB_COVSEL) {
     int32_t sw = 0;
     ADMM_HIP_TRY(hipMemcpy(&sw, e->cov_cnt, sizeof(int32_t), hipMemcpyDeviceToHost));
     e->cov_sweeps = sw + e->cov_sweeps_host;
   }
-  e->last = admm_run_summary{};
-  e->last.steps = e->ctrl_host->steps;
   if (e->cg_st) {
     ADMM_HIP_TRY(hipMemcpy(e->cg_st_host, e->cg_st, sizeof(CgState), hipMemcpyDeviceToHost));
     e->cg_total_last = e->cg_st_host->total;
     e->cg_capped_last = e->cg_st_host->capped;
   }
-  e->last.stopped_early = (e->ctrl_host->steps < N) ? 1 : 0;
-  e->last.convtest_failed_at = e->ctrl_host->convfail;
+  ADMM_TRY(finish_run(e, o, N, runtime, nullptr));
+  // (the TV and consensus runs leave a failed profiled run's unread timer events in place: only this loop drops them)
+  for (auto& t : e->timers) t.used = 0;
   e->last.obj_gram_used = (o.objevals && gram_now) ? 1 : 0;
-  e->last.runtime_s = runtime;
-  e->last.objopt = NAN;
-  if (o.objevals && e->last.steps > 0) {  // admm.m:752-754: obj(x,z) at the final iterates == last objevals entry
-    double v = NAN;
-    ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (e->last.steps - 1), sizeof(double), hipMemcpyDeviceToHost));
-    e->last.objopt = v;
-  }
-  e->has_run = true;
   if (summary) *summary = e->last;
-  return trsv_ok(ADMM_OK);
+  return comm_check_error(e->comm, e->stream);
 }
 
 }  // extern "C"

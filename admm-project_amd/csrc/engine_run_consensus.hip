@@ -1,7 +1,5 @@
 // engine_run_consensus.hip -- the iteration sequence of consensus lasso (getProxOps.m:383-442, 1217-1343; one slice
 // per rank when row-sharded), split out of admm_engine_run.
-#include <cstdlib>
-
 #include "engine_internal.h"
 
 namespace admm {
@@ -67,8 +65,7 @@ int run_consensus_lasso(admm_engine* e, RunState& rs, admm_run_summary* summary)
   bool stop_seen = false;
   // with the batched x-solve in front, the finalize logic of iteration i is deferred into iteration i + 1's batched
   // launch (one passenger workgroup; engine_run.hip: defer_fin has the reasoning); a batch's last one runs stand-alone
-  const bool batched = e->cMptr && std::getenv("ADMM_HIP_CONS_UNBATCHED") == nullptr;
-  const bool defer_fin = batched && std::getenv("ADMM_HIP_NO_DEFERRED_FINALIZE") == nullptr;
+  const bool batched = e->cMptr != nullptr;
   FinArgs fprev{};
   bool fin_pending = false;
   while (done < N && !stop_seen) {
@@ -100,7 +97,7 @@ int run_consensus_lasso(admm_engine* e, RunState& rs, admm_run_summary* summary)
       }
       const SymvPlan* gp = e->csyN ? &e->cslices[0].fac.planSy : nullptr;
       int nblk = 1;
-      const bool one_tail = !shard && gp && cons_gather_update_ok(ca) && std::getenv("ADMM_HIP_CONS_TWO_TAIL") == nullptr;
+      const bool one_tail = !shard && gp && cons_gather_update_ok(ca);
       if (one_tail) {
         TimerScope ts(e, ADMM_K_PROX);
         launch_cons_gather_update(ca, e->csyN, e->csyT, e->cpstride, gp->ldp, gp->ntile, e->ctrl, &nblk, e->stream);
@@ -148,7 +145,7 @@ int run_consensus_lasso(admm_engine* e, RunState& rs, admm_run_summary* summary)
           fa.objp_reduced = e->red + 17;
         }
       }
-      if (defer_fin) {
+      if (batched) {
         fprev = fa;
         fin_pending = true;
       } else {
@@ -173,27 +170,8 @@ int run_consensus_lasso(admm_engine* e, RunState& rs, admm_run_summary* summary)
   ADMM_HIP_TRY(hipMemcpyAsync(e->u, e->cubar, sizeof(double) * n, hipMemcpyDeviceToDevice, e->stream));
   ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
   ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
-  {
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
-  }
   const double rt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (e->profiling) collect_timers(e);
-  const int32_t steps = e->ctrl_host->steps;
-  e->last = admm_run_summary{};
-  e->last.steps = steps;
-  e->last.stopped_early = (steps < N) ? 1 : 0;
-  e->last.convtest_failed_at = e->ctrl_host->convfail;
-  e->last.runtime_s = rt;
-  e->last.objopt = NAN;
-  if (o.objevals && steps > 0) {
-    double v = NAN;
-    ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (steps - 1), sizeof(double), hipMemcpyDeviceToHost));
-    e->last.objopt = v;
-  }
-  e->has_run = true;
-  if (summary) *summary = e->last;
-  return ADMM_OK;
+  return finish_run(e, o, N, rt, summary);
 }
 
 }  // namespace admm

@@ -99,29 +99,6 @@ static int dct_solve_tv2d(admm_engine* e, double* y, const FinArgs* fin = nullpt
   return ADMM_OK;
 }
 
-// End of a run: launch errors, kernel timers, the summary with the objective at the last executed iteration
-// (admm.m:752-754).  e->ctrl_host holds the device's final control block.
-static int finish_tv_run(admm_engine* e, const admm_options& o, int32_t N, double runtime, admm_run_summary* summary) {
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return fail(ADMM_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
-  if (e->profiling) collect_timers(e);
-  const int32_t steps = e->ctrl_host->steps;
-  e->last = admm_run_summary{};
-  e->last.steps = steps;
-  e->last.stopped_early = (steps < N) ? 1 : 0;
-  e->last.convtest_failed_at = e->ctrl_host->convfail;
-  e->last.runtime_s = runtime;
-  e->last.objopt = NAN;
-  if (o.objevals && steps > 0) {
-    double v = NAN;
-    ADMM_HIP_TRY(hipMemcpy(&v, e->objv + (steps - 1), sizeof(double), hipMemcpyDeviceToHost));
-    e->last.objopt = v;
-  }
-  e->has_run = true;
-  if (summary) *summary = e->last;
-  return ADMM_OK;
-}
-
 int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summary) {
   const admm_options& o = rs.o;
   const int alg = rs.alg;
@@ -308,7 +285,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
   ADMM_HIP_TRY(hipMemcpy(e->cg_st_host, e->cg_st, sizeof(CgState), hipMemcpyDeviceToHost));
   e->cg_total_last = e->cg_st_host->total;
   e->cg_capped_last = e->cg_st_host->capped;
-  return finish_tv_run(e, o, N, rt, summary);
+  return finish_run(e, o, N, rt, summary);
 }
 
 // The form of a 1-D iteration (tv.hip), fixed for a run by the plan's halo, n and the ADMM variant
@@ -474,7 +451,7 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
     }
     ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
-    return finish_tv_run(e, o, N, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0f).count(),
+    return finish_run(e, o, N, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0f).count(),
                          summary);
   }
   const auto t0 = std::chrono::steady_clock::now();
@@ -602,7 +579,7 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
     launch_tv_sweep(ta, true, e->ctrl_idle, e->stream);  // the loop's own flag says "stopped" by now
     ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
   }
-  return finish_tv_run(e, o, N, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), summary);
+  return finish_run(e, o, N, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), summary);
 }
 
 }  // namespace admm

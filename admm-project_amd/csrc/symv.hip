@@ -25,7 +25,6 @@
 // (r2: 8-column panels -- 16 loads in flight, a three-level reduce-scatter ending in row_half_mirror -- measured
 // slower than this 4-column form: 78.4 vs 76.5 us event-timed per pass.  A pure N-part pass over the same tiles,
 // tri_step_kernel in trsv.hip, streams at 6.0 TB/s, so the T-part's cross-lane work is what holds this kernel at 5.4.)
-#include <cstdlib>
 
 #include "finalize_device.h"
 #include "kernels.h"
@@ -491,9 +490,7 @@ SymvPlan symv_plan(int64_t n) {
   p.ldp = p.npad;
   p.ntile = static_cast<int32_t>(p.npad / kSyTile);
   p.packed = false;
-  int64_t budget = kSymvCacheBytes;
-  if (const char* env = getenv("ADMM_HIP_SYMV_CACHE_MB")) budget = static_cast<int64_t>(atoll(env)) << 20;  // tuning knob
-  p.ncached = symv_cached_tiles(p, budget);
+  p.ncached = symv_cached_tiles(p, kSymvCacheBytes);
   return p;
 }
 

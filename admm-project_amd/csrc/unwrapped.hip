@@ -23,7 +23,6 @@
 // Partial rows are double-buffered on the parity of ctrl->iter; every sum runs in a fixed order (bitwise reproducible).
 // All loads are unconditional (clamped addresses, zero weights): a branch per load would serialise the round trips.
 #include <algorithm>
-#include <cstdlib>
 
 #include "finalize_device.h"
 #include "kernels.h"
@@ -328,7 +327,7 @@ __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs
 
 bool onepass_supported(int64_t m, int64_t n) {
   // (worth it where the passes over D are what an iteration costs: below ~48 MB the launches are)
-  return n >= 1 && n <= kOpMaxN && m * n * 8 >= (int64_t{48} << 20) && std::getenv("ADMM_HIP_NO_ONEPASS") == nullptr;
+  return n >= 1 && n <= kOpMaxN && m * n * 8 >= (int64_t{48} << 20) && !env_switches().no_onepass;
 }
 
 int onepass_workgroups(int64_t m) {

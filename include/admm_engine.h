@@ -11,6 +11,20 @@
  * (MATLAB layout).  Every function returns 0 on success and a negative ADMM_E_* code
  * on failure; admm_last_error() returns the thread-local message.  An engine handle
  * is not re-entrant; one host thread drives one device.
+ *
+ * Environment: the library reads five variables and no others (one reader, csrc/common.h: env_switches).  Each makes
+ * the engine take a path that it otherwise picks by measurement or by shape; they exist for the tests and for A/B
+ * measurements, not as tuning knobs, and every path they reach is a production path.  They are read when the named
+ * call runs, never cached.
+ *   ADMM_HIP_GRAPH               (run)    replay batches of iterations as a captured hipGraph where the iteration
+ *                                         allows it; the default is eager launches (never slower, EXPERIMENTS.md)
+ *   ADMM_TRSV_FORM=blocked|one   (create, admm_op_trsv_pair) the form of the triangular solves, overriding the
+ *                                         create-time accuracy probe: blocked substitution / one pre-inverted block
+ *   ADMM_HIP_XSPLIT=0|1          (create) multi-GPU explicit-inverse x-solve: keep / split the tiles over the ranks,
+ *                                         overriding the decision taken from the measured all-reduce latency
+ *   ADMM_HIP_NO_UNWRAPPED_FUSED  (create) no explicit pinv(D) is built, so the linear SVM runs the general A = D
+ *                                         iteration instead of the two-launch unwrapped one
+ *   ADMM_HIP_NO_ONEPASS          (run)    the general A = D iteration instead of the one-pass form for tall, narrow D
  */
 #ifndef ADMM_ENGINE_H
 #define ADMM_ENGINE_H

@@ -80,8 +80,8 @@ def test_cholesky_rejects_indefinite(gpu):
 @pytest.mark.parametrize("n", [1, 3, 63, 64, 65, 127, 128, 129, 130, 400, 1000, 1280, 1281, 1409, 2049, 2560, 2700, 3333, 4100,
                                6500, 10000])
 def test_trsv_pair(gpu, n):
-    """blocked substitution: one coarse block up to n = 2048, several beyond (ragged last block included; from two blocks
-    on the pair runs as ONE launch, trsv.hip: tri_persist_kernel -- 5 blocks at n = 10000);
+    """blocked substitution: one coarse block up to n = 2048, several beyond (ragged last block included; K blocks are
+    2K + 1 launches per pair, trsv.hip: tri_step_kernel -- 5 blocks at n = 10000);
     the strictly-upper part of the factor buffer holds garbage, as after an in-place Cholesky of a full matrix"""
     rng = np.random.default_rng(n)
     G = rng.standard_normal((n + 20, n)) / np.sqrt(n + 20)
@@ -114,26 +114,6 @@ def test_bad_arguments_are_errors_not_crashes(gpu):
     assert lib.admm_engine_create(C.byref(d), C.byref(h)) == gpu._lib.E_INVALID
     d.struct_size = 8
     assert lib.admm_engine_create(C.byref(d), C.byref(h)) == gpu._lib.E_INVALID
-
-
-@pytest.mark.parametrize("n", [2049, 2700, 4100, 10000])
-def test_trsv_pair_one_launch_form(gpu, n, monkeypatch):
-    """the same pair as ONE persistent launch (trsv.hip: tri_persist_kernel; opt-in, slower than the stepwise launches):
-    tickets, write-through hand-offs between workgroups, row-tile counters -- same sums in the same order"""
-    monkeypatch.setenv("ADMM_TRSV_ONE_LAUNCH", "1")
-    rng = np.random.default_rng(n)
-    G = rng.standard_normal((n + 20, n)) / np.sqrt(n + 20)
-    Lf = np.asfortranarray(sla.cholesky(G.T @ G + np.eye(n), lower=True))
-    y = rng.standard_normal(n)
-    x1, x2 = np.zeros(n), np.zeros(n)
-    gpu._lib.check(gpu._lib.load().admm_op_trsv_pair(_dp(gpu, Lf), n, n, _dp(gpu, y), _dp(gpu, x1)))
-    monkeypatch.delenv("ADMM_TRSV_ONE_LAUNCH")
-    gpu._lib.check(gpu._lib.load().admm_op_trsv_pair(_dp(gpu, Lf), n, n, _dp(gpu, y), _dp(gpu, x2)))
-    ref = sla.solve_triangular(Lf.T, sla.solve_triangular(Lf, y, lower=True), lower=False)
-    assert _rel(x1, ref) < 1e-11 and _rel(x2, ref) < 1e-11
-    # the same tiles and panels; a tile's columns are split over 4 waves here and over 1..16 in the stepwise launches
-    # (chosen per step from the grid size), so the sums associate differently: equal to rounding, not bitwise
-    assert _rel(x1, x2) < 1e-13
 
 
 @pytest.mark.parametrize("n", [256, 300, 1000, 2049, 3333, 10000])

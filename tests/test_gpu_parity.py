@@ -874,22 +874,20 @@ def test_one_pass_iteration_on_a_tall_narrow_matrix(gpu, monkeypatch, solver, m,
 @pytest.mark.parametrize("opts", [dict(), dict(objevals=1, maxiters=40), dict(fast=1, fasttype="strong", maxiters=60),
                                   dict(relax=1.6, stopcond="both", maxiters=50), dict(convtest=1, stopcond="hnorm"),
                                   dict(maxiters=13, domaxiters=1), dict(record_history=0, maxiters=70)])
-def test_lasso_deferred_finalize_on_the_packed_inverse(gpu, monkeypatch, opts):
+def test_lasso_deferred_finalize_on_the_packed_inverse(gpu, opts):
     """n = 1600 (>= 1536: tile-packed inverse, lower-triangle kernel): the finalize logic of iteration i rides along
     with the x-solve of iteration i + 1 (symv_lower_fin_kernel) and the stop decision still lands on the iteration the
     reference stops at -- early stops in the middle of a host batch, relaxation, fast ADMM, the convergence test, a
-    fixed iteration count that is not a multiple of the batch, no histories.  Compared with the oracle and with the
-    one-launch tail (ADMM_HIP_NO_DEFERRED_FINALIZE)."""
+    fixed iteration count that is not a multiple of the batch, no histories.  Compared with the oracle and with polling
+    after every iteration (check_every = 1: every iteration is its batch's last, so its finalize runs stand-alone)."""
     p = gpu.synth.lasso_problem(7, 2000, 1600)
     D, s, lam = p["D"], p["s"], p["lam"]
     got = gpu.lasso(D, s, lam, dict(opts, xsolve="inverse"))
     assert got["engine_info"]["xsolve_used"] == "inverse"
-    monkeypatch.setenv("ADMM_HIP_NO_DEFERRED_FINALIZE", "1")
-    one = gpu.lasso(D, s, lam, dict(opts, xsolve="inverse"))
-    monkeypatch.delenv("ADMM_HIP_NO_DEFERRED_FINALIZE")
+    one = gpu.lasso(D, s, lam, dict(opts, xsolve="inverse", check_every=1))
     assert got["steps"] == one["steps"]
     for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr"):
-        assert np.array_equal(got[k], one[k]), k  # the same kernels in the same order: bitwise
+        assert np.array_equal(got[k], one[k]), k  # the same finalize logic on the same partial sums: bitwise
     if opts.get("record_history", 1):
         ref = S.lasso(D, s, lam, dict(opts))
         _compare(got, ref, tol=1e-7)
