@@ -1,5 +1,6 @@
 // engine_internal.h -- the engine object behind the opaque admm_engine handle and the host helpers shared by
-// engine.hip (create / fetch / destroy: the reference solvers' one-time setup) and engine_run.hip (run: the loop).
+// engine_create.hip (create: the reference solvers' one-time setup), engine.hip (the factor machinery create builds
+// on, fetch, info, destroy) and engine_run*.hip (run: the loop).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -31,6 +32,15 @@ struct DevMem {  // owns every device allocation of an engine
     ptrs.push_back(p);
     *out = static_cast<double*>(p);
     return ADMM_OK;
+  }
+  void free_one(void* p) {  // give one allocation back early (null: nothing to do)
+    if (!p) return;
+    for (auto& q : ptrs)
+      if (q == p) {
+        (void)hipFree(p);
+        q = nullptr;
+        return;
+      }
   }
   void release() {
     for (void* p : ptrs) (void)hipFree(p);
@@ -116,20 +126,20 @@ struct admm_engine {
   double* opG = nullptr;         // one-pass A = D iteration: [workgroups][ldg] partial rows of D'*(c + z - u)
   double *v = nullptr, *uhat = nullptr, *zprev = nullptr, *uprev = nullptr;
   double *tmpA = nullptr, *tmpB = nullptr;  // fat lasso scratch (m and n long)
-  // total variation: forward-sweep intermediate, ping-pong partners of z/u, LDL' pivot prefix
   int64_t tv2_H = 0, tv2_W = 0;  // 2-D TV image shape
   Ctrl* ctrl_idle = nullptr;     // an all-zero control block for clean-up launches after the loop has stopped
-  // lasso objective through the Gram matrix (desc.obj_gram): tile-padded copy of D'D, -D's, G*x scratch, 1/2*s's
+  // lasso objective without a pass over D (desc.obj_gram; OBJX_SOLVE, prox_device.h): 1/2*s's over all shards
   double half_ssq = 0.0;
   // obj_gram = 0 (automatic): calibrate against the literal form during the first batch, then decide (engine_run.hip)
   bool obj_alt = false;  // the solve-identity form of the lasso objective is available (1/2*s's is known)
   bool obj_auto = false, obj_gram_ok = false, obj_gram_bad = false;
   double obj_bound_seen = 0.0;  // largest cancellation bound of the right-hand-side objective form over all runs
-  double* gobjpart = nullptr;  // [kMaxPartBlocks + 1] Gram-form partials during calibration; last entry: max discrepancy
-  bool tv2_dct = false;          // spectral x-update instead of CG: the height a power of two (dct.h)
-  bool tv2_rows_dct = false;     // ... and the width too: the row DCT exists as the fall-back of the Toeplitz row stage
+  double* gobjpart = nullptr;  // [kMaxPartBlocks + 2] Gram-form partials during calibration; last entry: max discrepancy
+  bool tv2_dct = false;          // spectral x-update instead of CG: the column transform supports the height (dct.h)
+  bool tv2_rows_dct = false;     // ... and the width is a power of two: the row DCT exists as the fall-back of the Toeplitz row stage
   DctTables dctH{}, dctW{};
-  double* tv_y2 = nullptr;  // ping-pong partner of tv_y (fused iteration kernel)
+  // 1-D / 2-D total variation: forward-sweep intermediate and its ping-pong partner, partners of z/u, LDL' pivot prefix
+  double* tv_y2 = nullptr;
   double *tv_y = nullptr, *tv_zA = nullptr, *tv_uA = nullptr, *tv_zB = nullptr, *tv_uB = nullptr;
   double* tv_bprefix = nullptr;
   size_t tv_bprefix_cap = 0;
@@ -242,6 +252,23 @@ int upload_matrix(DevMem& mem, double** dst, int64_t* ld_out, const double* src,
 void free_hist(admm_engine* e);
 int hist_alloc(admm_engine* e, double** out, size_t elems);
 void collect_timers(admm_engine* e);
+// *value <- its sum over the ranks, through one device double; a no-op without a multi-rank communicator.  slot: the
+// device double to use, or null: one is allocated and stays with the engine (before any other buffer exists)
+int allreduce_scalar(admm_engine* e, double* value, double* slot = nullptr);
+// *out = sum of squares of a device vector, summed on the host in index order
+int device_sumsq_host(admm_engine* e, const double* dev, int64_t count, double* out);
+// a device block shaped like T (Ctrl, CgState) inside a double allocation of the engine, zeroed on its stream
+template <class T>
+int alloc_zeroed_block(admm_engine* e, T** out) {
+  double* raw = nullptr;
+  ADMM_TRY(e->mem.alloc(&raw, (sizeof(T) + 7) / 8));
+  *out = reinterpret_cast<T*>(raw);
+  ADMM_HIP_TRY(hipMemsetAsync(raw, 0, sizeof(T), e->stream));
+  return ADMM_OK;
+}
+// W (ldW, lower triangle, zeroed first) = scale * D'*D for D (rows x cols, ldD), or scale * D*D' when of_rows
+int gram_lower(admm_engine* e, const double* D, int64_t ldD, int64_t rows, int64_t cols, bool of_rows, double scale,
+               double* W, int64_t ldW);
 // W (nF x nF, ld) holds an SPD matrix in its lower triangle -> F (in place), dinv, optionally Minv
 int factorize(admm_engine* e, double* W, int64_t nF, int64_t ld, const double* Lgiven, int memkind);
 int symv_apply(admm_engine* e, const double* y, double* out);
@@ -250,6 +277,13 @@ int build_slice_factor(admm_engine* e, SliceFactor& f, double* W, int64_t n, int
                        int memkind);
 int factorize_pinv(admm_engine* e, double* W, int64_t n, int64_t ld);
 void apply_slice_factor(admm_engine* e, const SliceFactor& f, const double* y, double* out);
+void release_slice_factor(admm_engine* e, SliceFactor& f);
+// engine.hip, for create: pinv(D) of the two-launch unwrapped iteration; the maps x = P*v + q of basis pursuit and
+// x = K*y + k0 of LP / standard-form QP from D (m x n, ldD) and s on the device
+int build_unwrapped_pinv(admm_engine* e, const double* Dp_given);
+int build_bp_projector(admm_engine* e, const double* D, int64_t m, int64_t n, int64_t ldD, const double* s_dev);
+int build_kkt_map(admm_engine* e, const double* D, int64_t m, int64_t n, int64_t ldD, const double* s_dev,
+                  const double* P /* null: LP */, int64_t ldPm, double rho);
 
 struct TimerScope {
   admm_engine* e;
