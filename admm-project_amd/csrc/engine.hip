@@ -1,7 +1,7 @@
 // engine.hip -- what create() (engine_create.hip) builds its engines from: uploads, the cached factor of the x-update
 // and the probes that choose how it is applied, the eliminated maps of basis pursuit / LP / QP -- and the rest of the
 // C ABI (include/admm_engine.h) around the loop: defaults, result fetch, info, timers, destroy.  The loop itself
-// (admm.m:252-767) is engine_run.hip.
+// (admm.m:252-767) is engine_run.hip and the engine_run_*.hip files.
 #include "engine_internal.h"
 #include "loop_kernels.h"
 
@@ -702,7 +702,7 @@ int symv_apply(admm_engine* e, const double* y, double* out) {
   const SliceFactor& f = e->xfac;
   const int nr = e->comm ? comm_nranks(e->comm) : 1;
   if (nr > 1 && e->sy_split) {
-    if (e->dfin && f.planSy.packed)  // the previous iteration's deferred finalize rides along (engine_run.hip)
+    if (e->dfin && f.planSy.packed)  // the previous iteration's deferred finalize rides along (engine_run_general.hip)
       launch_symv_lower_fin(f.planSy, f.Minv, y, e->syN, e->syT, *e->dfin, e->dfin_pending, e->ctrl, e->stream,
                             comm_rank(e->comm), nr, out);
     else

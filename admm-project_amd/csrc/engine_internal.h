@@ -130,7 +130,7 @@ struct admm_engine {
   Ctrl* ctrl_idle = nullptr;     // an all-zero control block for clean-up launches after the loop has stopped
   // lasso objective without a pass over D (desc.obj_gram; OBJX_SOLVE, prox_device.h): 1/2*s's over all shards
   double half_ssq = 0.0;
-  // obj_gram = 0 (automatic): calibrate against the literal form during the first batch, then decide (engine_run.hip)
+  // obj_gram = 0 (automatic): calibrate against the literal form during the first batch, then decide (engine_run_general.hip)
   bool obj_alt = false;  // the solve-identity form of the lasso objective is available (1/2*s's is known)
   bool obj_auto = false, obj_gram_ok = false, obj_gram_bad = false;
   double obj_bound_seen = 0.0;  // largest cancellation bound of the right-hand-side objective form over all runs
@@ -176,7 +176,8 @@ struct admm_engine {
   double* s2 = nullptr;
   GemvNPlan planD2N{};
   double* partD2N = nullptr;
-  // deferred finalize (engine_run.hip): the previous iteration's finalize arguments ride along with the packed x-solve
+  // deferred finalize (engine_run_general.hip): the previous iteration's finalize arguments ride along with the packed
+  // x-solve; dfin points into the running loop's object and is null between runs
   const FinArgs* dfin = nullptr;
   bool dfin_pending = false;
   const double** cMptr = nullptr;  // consensus: device array of the K packed slice inverses (one batched x-solve launch)
@@ -311,6 +312,11 @@ struct TimerScope {
   }
 };
 
+// which objective the library evaluates itself, and how (wire_objective in engine_run.hip)
+struct ObjForm {
+  bool obj_lasso_gemv = false, obj_qp_gemv = false, obj_model_gemv = false, obj_covsel = false;
+};
+
 // what admm_engine_run's prologue hands to the per-problem iteration sequences
 struct RunState {
   admm_options o;
@@ -320,13 +326,20 @@ struct RunState {
   ProxArgs pa;
   FinArgs fa;
   ExtrapArgs xa;
+  ObjForm obj;
+  int check_every;  // iterations between two polls of the device: options.check_every, or 8 (64 with domaxiters)
+  bool split_z;     // z comes from zming / zminModel between two kernels (PROX_GIVEN)
 };
 
 // engine_run.hip
 int cg_solve(admm_engine* e, const double* y);
+int poll_ctrl(admm_engine* e);  // e->ctrl_host <- the device's control block (synchronises the stream)
+int apply_b(admm_engine* e, const double* zin, double* wout);  // w = -B*z for a general B
 // the epilogue every iteration sequence ends with: launch-error check, kernel timers, e->last (and *summary) from
 // e->ctrl_host, which must hold the device's final control block
 int finish_run(admm_engine* e, const admm_options& o, int32_t N, double runtime, admm_run_summary* summary);
+// engine_run_general.hip: every problem but the two below
+int run_general(admm_engine* e, RunState& rs, admm_run_summary* summary);
 // engine_run_tv.hip: total variation (totalvariation.m) and the 2-D extension
 int cg_solve_tv2d(admm_engine* e, const double* y);
 int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary);

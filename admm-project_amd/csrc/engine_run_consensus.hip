@@ -59,12 +59,12 @@ int run_consensus_lasso(admm_engine* e, RunState& rs, admm_run_summary* summary)
   fa.xhist = nullptr;
   fa.obj_scale_part = o.objevals ? 0.5 : 0.0;  // lasso.m:227 with the z admm holds (zeros): 0.5*||D*x - s||^2
   fa.obj_scale_z = 0.0;
-  const int check_c = o.check_every > 0 ? o.check_every : (o.domaxiters ? 64 : 8);
+  const int check_c = rs.check_every;
   const auto t0 = std::chrono::steady_clock::now();
   int32_t done = 0;
   bool stop_seen = false;
   // with the batched x-solve in front, the finalize logic of iteration i is deferred into iteration i + 1's batched
-  // launch (one passenger workgroup; engine_run.hip: defer_fin has the reasoning); a batch's last one runs stand-alone
+  // launch (one passenger workgroup; engine_run_general.hip: defer_fin has the reasoning); a batch's last one runs stand-alone
   const bool batched = e->cMptr != nullptr;
   FinArgs fprev{};
   bool fin_pending = false;
@@ -158,9 +158,8 @@ int run_consensus_lasso(admm_engine* e, RunState& rs, admm_run_summary* summary)
       launch_finalize(fprev, e->stream);
       fin_pending = false;
     }
-    {  // poll after every batch (see engine_run.hip)
-      ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-      ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+    {  // poll after every batch (see engine_run_general.hip)
+      ADMM_TRY(poll_ctrl(e));
       if (e->ctrl_host->stop) stop_seen = true;
     }
   }
@@ -168,8 +167,7 @@ int run_consensus_lasso(admm_engine* e, RunState& rs, admm_run_summary* summary)
   ADMM_HIP_TRY(hipMemcpyAsync(e->x, e->cxave, sizeof(double) * n, hipMemcpyDeviceToDevice, e->stream));
   ADMM_HIP_TRY(hipMemsetAsync(e->z, 0, sizeof(double) * n, e->stream));
   ADMM_HIP_TRY(hipMemcpyAsync(e->u, e->cubar, sizeof(double) * n, hipMemcpyDeviceToDevice, e->stream));
-  ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+  ADMM_TRY(poll_ctrl(e));
   const double rt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return finish_run(e, o, N, rt, summary);
 }

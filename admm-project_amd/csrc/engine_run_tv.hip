@@ -145,7 +145,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
     fa.obj_scale_z = e->lambda;
   }
   (void)Npix;
-  const int check_tv2 = o.check_every > 0 ? o.check_every : (o.domaxiters ? 64 : 8);
+  const int check_tv2 = rs.check_every;
   const auto t0 = std::chrono::steady_clock::now();
   int32_t done = 0;
   bool stop_seen = false;
@@ -210,8 +210,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
       }
       done += 1;
       if (!spectral || done % check_tv2 == 0 || done == N) {
-        ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-        ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+        ADMM_TRY(poll_ctrl(e));
         if (e->ctrl_host->stop) stop_seen = true;
       }
     }
@@ -270,8 +269,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
     // the CG path synchronises inside every solve anyway; the spectral path runs check_tv2 iterations ahead
     // (everything enqueued after the stop flag is a no-op)
     if (!spectral || done % check_tv2 == 0 || done == N) {
-      ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-      ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+      ADMM_TRY(poll_ctrl(e));
       if (e->ctrl_host->stop) stop_seen = true;
     }
   }
@@ -377,7 +375,7 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
     fa.obj_scale_x = 0.5;
     fa.obj_scale_z = e->lambda;
   }
-  const int check_tv = o.check_every > 0 ? o.check_every : (o.domaxiters ? 64 : 8);
+  const int check_tv = rs.check_every;
   const bool tv_relaxed = o.relax != 1.0;
   if (form == TvForm::UNFUSED) {
     // Fast / accelerated ADMM (admm.m:267-298, 563-600): the x-update takes (v, uhat), the generic fused prox
@@ -443,14 +441,12 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
         }
       }
       donef += batch;
-      {  // poll after every batch (see engine_run.hip)
-        ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-        ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+      {  // poll after every batch (see engine_run_general.hip)
+        ADMM_TRY(poll_ctrl(e));
         if (e->ctrl_host->stop) stopf = true;
       }
     }
-    ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-    ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+    ADMM_TRY(poll_ctrl(e));
     return finish_run(e, o, N, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0f).count(),
                          summary);
   }
@@ -542,14 +538,12 @@ int run_total_variation(admm_engine* e, RunState& rs, admm_run_summary* summary)
       launch_finalize(fa, e->stream);
       tv_pending = false;
     }
-    {  // poll after every batch (see engine_run.hip)
-      ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-      ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+    {  // poll after every batch (see engine_run_general.hip)
+      ADMM_TRY(poll_ctrl(e));
       if (e->ctrl_host->stop) stop_seen = true;
     }
   }
-  ADMM_HIP_TRY(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+  ADMM_TRY(poll_ctrl(e));
   const int32_t steps = e->ctrl_host->steps;
   // iterations executed on the device decide which ping-pong buffer holds the final z, u
   e->z = (steps & 1) ? e->tv_zB : e->tv_zA;

@@ -107,7 +107,7 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a) {
       // 1/2*||D*x - s||^2 = sum_i x_i*(1/2*(y_i - rho*x_i) - (D's)_i) + 1/2*s's: terms of the size of s's that cancel down
       // to the data misfit.  eps * (sum of their magnitudes) / |objective| bounds the relative rounding error of the
       // recorded value; the host reads the run's maximum after every batch and goes back to the literal D*x pass when
-      // it leaves 1e-10 (engine_run.hip)
+      // it leaves 1e-10 (engine_run_general.hip: after_batch)
       const double bound = 2.220446049250313e-16 * (fabs(a.obj_scale_x) * S[S_OBJA] + fabs(a.obj_const)) /
                            fmax(fabs(ov), 1e-300);
       if (!(bound <= ctrl->obj_bound)) ctrl->obj_bound = bound;  // NaN-safe maximum

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void sum_partials_t_kernel(const double* __
 }
 
 // the same with a passenger: the last workgroup runs the deferred finalize logic of the iteration whose element update
-// has just run (engine_run.hip: defer_fin_ad) next to the partial sums instead of serially inside that update's launch
+// has just run (engine_run_general.hip: defer_fin_ad) next to the partial sums instead of serially inside that update's launch
 __global__ __launch_bounds__(kBlock) void sum_partials_t_fin_kernel(const double* __restrict__ gpart, int32_t nchunk,
                                                                     int nrhs, int64_t ldg, int64_t n,
                                                                     double* __restrict__ g, int64_t ldg_out, FinArgs f,

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(kWave) void symv_lower_kernel(const double* __restr
 // The packed x-solve with a passenger: workgroup 0 runs the finalize logic of the PREVIOUS iteration (norms, tolerances,
 // stop decision: ~6 us of one workgroup's serial work) while the other workgroups stream the matrix.  Nothing in this
 // launch depends on that decision, and the fused element update that follows starts after it and no-ops when it has
-// raised ctrl->stop: the tail of an iteration shrinks to the element update itself (engine_run.hip, defer_fin).
+// raised ctrl->stop: the tail of an iteration shrinks to the element update itself (engine_run_general.hip, defer_fin).
 __global__ __launch_bounds__(kWave) void symv_lower_fin_kernel(const double* __restrict__ M, int64_t n,
                                                                const double* __restrict__ x,
                                                                double* __restrict__ npart, double* __restrict__ tpart,

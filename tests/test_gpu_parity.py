@@ -1043,3 +1043,55 @@ def test_eliminated_constraint_solves_are_probed(gpu, kind):
         else:
             with pytest.raises(gpu.AdmmError, match="ill-conditioned"):
                 run()
+
+
+def _run_and_fetch(L, eng, run):
+    s = eng.run(**run)
+    out = dict(steps=s.steps, xopt=eng.fetch(L.F_XOPT, eng.nA), zopt=eng.fetch(L.F_ZOPT, eng.nB),
+               uopt=eng.fetch(L.F_UOPT, eng.nB))
+    for k, f in (("pnorm", L.F_PNORM), ("dnorm", L.F_DNORM), ("perr", L.F_PERR), ("derr", L.F_DERR)):
+        out[k] = eng.fetch(f, s.steps)
+    return out
+
+
+def _same_run(a, b, what):
+    assert a["steps"] == b["steps"], (what, a["steps"], b["steps"])
+    for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr"):
+        assert np.array_equal(a[k], b[k], equal_nan=True), (what, k)  # (dnorm is NaN where no dual residual is kept)
+
+
+def test_one_engine_through_successive_iteration_forms(gpu):
+    """What a run of the general loop decides and carries -- the iteration form, the deferred finalize and its
+    passenger, the two-launch iteration's parity -- lives in the loop object of that run and must not survive it: one
+    engine taken through runs that choose different forms gives, run by run, bit for bit what a freshly created engine
+    gives for the same run, and its last run repeats its first.  Lasso 2000 x 1600 on the packed inverse (the deferred
+    finalize; with objevals; weak fast ADMM, which has no fused tail; a count that is no multiple of the batch) and a
+    linear SVM (two-launch form, general form, two-launch form).  The objective arrays are left out: the calibration
+    of the objective's form belongs to the engine and persists, and the iterates do not depend on it."""
+    L = gpu._lib
+    p = gpu.synth.lasso_problem(7, 2000, 1600)
+    make = lambda: gpu.Engine(L.PROB_LASSO, D=p["D"], s=p["s"], lam=p["lam"], rho=1.0, xsolve=L.XSOLVE_INVERSE)
+    runs = [dict(), dict(objevals=1, maxiters=40), dict(fast=L.FAST_WEAK, maxiters=60),
+            dict(record_history=0, maxiters=13, domaxiters=1), dict()]
+    q = gpu.synth.mnist_like_problem(seed=2, m=1000, n=130)
+    start = dict(x0=q["x0"], z0=q["z0"], u0=q["u0"])  # (unwrappedadmm draws unseeded starts otherwise)
+    make_svm = lambda: gpu.Engine(L.PROB_LINEARSVM, D=q["D"], ell=q["ell"], Cval=q["C"])
+    runs_svm = [dict(start, nodualerror=1), dict(start, fast=L.FAST_STRONG), dict(start, nodualerror=1)]
+    for name, mk, seq in (("lasso", make, runs), ("svm", make_svm, runs_svm)):
+        eng = mk()
+        try:
+            assert name != "svm" or eng.info()["unwrapped_fused"]  # (the two-launch form is there to be chosen)
+            got = [_run_and_fetch(L, eng, r) for r in seq]
+        finally:
+            eng.close()
+        first = None
+        for i, r in enumerate(seq[:-1]):  # (the last run is the first one again: one fresh engine serves both)
+            fresh = mk()
+            try:
+                ref = _run_and_fetch(L, fresh, r)
+            finally:
+                fresh.close()
+            first = ref if i == 0 else first
+            _same_run(got[i], ref, (name, i))
+        _same_run(got[-1], first, (name, "last run against a fresh engine"))
+        _same_run(got[-1], got[0], (name, "last against first"))
