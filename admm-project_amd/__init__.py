@@ -7,9 +7,9 @@ per-iteration arithmetic runs in hand-written HIP kernels (csrc/) behind a plain
 from . import _lib, errorcheck, synth  # noqa: F401
 from ._lib import AdmmError  # noqa: F401
 from .api import ProxOp, admm, getproxops  # noqa: F401
-from .engine import Engine  # noqa: F401
+from .engine import Engine, SvmOvr  # noqa: F401
 from . import testers  # noqa: F401,E402
-from .solvers import (basispursuit, covarianceselection, huberfit, lad, lasso, linearprogram, linearsvm, model,  # noqa: F401
+from .solvers import (basispursuit, covarianceselection, huberfit, lad, lasso, linearprogram, linearsvm, linearsvm_ovr, model,  # noqa: F401
                       quadraticprogram, totalvariation, totalvariation2d, unwrappedadmm)
 
 __version__ = "0.1.0"

@@ -116,6 +116,26 @@ class ResultField(C.Structure):
                 ("cols", C.c_int64), ("scalar", C.c_double)]
 
 
+class SvmOvrDesc(C.Structure):  # admm_svm_ovr_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("m", C.c_int64), ("n", C.c_int64), ("D", _dp),
+                ("ldD", C.c_int64), ("ELL", _dp), ("loss", C.POINTER(C.c_int32)), ("C", C.c_double),
+                ("mem", C.c_int32), ("device", C.c_int32), ("Dplus", _dp), ("comm", C.c_void_p)]
+
+
+class SvmOvrOptions(C.Structure):  # admm_svm_ovr_options
+    _fields_ = [("struct_size", C.c_int32), ("maxiters", C.c_int32), ("rho", C.c_double), ("abstol", C.c_double),
+                ("reltol", C.c_double), ("Hnormtol", C.c_double), ("relax", C.c_double), ("fast", C.c_int32),
+                ("convtest", C.c_int32), ("domaxiters", C.c_int32), ("objevals", C.c_int32),
+                ("check_every", C.c_int32), ("reserved0", C.c_int32), ("x0", _dp), ("z0", _dp), ("u0", _dp)]
+
+
+class SvmOvrSummary(C.Structure):  # admm_svm_ovr_summary
+    _fields_ = [("steps", C.c_int32), ("stopped_early", C.c_int32), ("objopt", C.c_double)]
+
+
+OVR_F_XOPT, OVR_F_ZOPT, OVR_F_UOPT, OVR_F_PNORM, OVR_F_PERR, OVR_F_HNORMSQ, OVR_F_OBJEVALS = range(1, 8)
+SVM_OVR_MAX_N = 448
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 F_WVALS = 23
@@ -179,6 +199,14 @@ _SIGNATURES = {
     "admm_engine_create_all": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.POINTER(C.c_void_p)]),
     "admm_engine_run_all": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(Options), C.c_int,
                                       C.POINTER(RunSummary)]),
+    "admm_svm_ovr_desc_default": (None, [C.POINTER(SvmOvrDesc)]),
+    "admm_svm_ovr_options_default": (None, [C.POINTER(SvmOvrOptions)]),
+    "admm_svm_ovr_create": (C.c_int, [C.POINTER(SvmOvrDesc), C.POINTER(C.c_void_p)]),
+    "admm_svm_ovr_run": (C.c_int, [C.c_void_p, C.POINTER(SvmOvrOptions), C.POINTER(SvmOvrSummary),
+                                   C.POINTER(C.c_double)]),
+    "admm_svm_ovr_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_svm_ovr_chunk": (C.c_int, []),
+    "admm_svm_ovr_destroy": (None, [C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,0 +1,702 @@
+// svm_ovr.hip -- the linear SVM for all one-vs-rest classes at once (examples/mnistsvm.m:88-102: one linearsvm call per
+// digit and loss on the same D).  xminLinearSVM is Dplus*(z - u) (getProxOps.m:1062-1068) and does not contain ell; the
+// labels enter the element-wise z-prox (getProxOps.m:1084-1103) and the objective (linearsvm.m:231-237) alone.  K classes
+// are therefore K independent plain-ADMM runs (unwrappedadmm.m:76-92) that share D, the map (D'D)^-1 and every byte an
+// iteration reads from HBM.  Per iteration:
+//   ovr_xsolve_kernel    x_c = M g_c for every running class (M symmetric n x n, n <= 448: small)
+//   ovr_pass_kernel      ONE read of D for a chunk of kOvrChunk classes: the 64-row block in registers as in
+//                        ad_onepass_kernel (unwrapped.hip) -- lane = row, wave w owns the columns j = w (mod 8) --, then
+//                        per class (D x_c)_r, the fused element update (prox_apply: the code every loop shares), and the
+//                        block's contribution D_r' t_r to the class's next right-hand side g_c = D'(z_c - u_c)
+//   ovr_gsum_fin_kernel  sums the workgroups' partial rows of g_c; one extra workgroup per class turns the block partials
+//                        into pnorm, perr, Hnormsq, the objective and the stop decision (admm.m:612-722)
+// A class whose stop flag is set is FROZEN: every kernel skips it, so its X, Z, U columns and histories are those of an
+// independent run with that many steps.  Every sum runs in a fixed order that does not depend on which chunk or slot a
+// class occupies: runs are bitwise reproducible, and a class gets the same numbers wherever it lands.
+// All loads of D are unconditional on clamped addresses (x is zero beyond n; rows beyond m carry t = 0).
+#include <vector>
+
+#include "engine_internal.h"
+#include "prox_device.h"
+#include "svm_ovr.h"
+#include "wave_reduce.h"
+
+namespace admm {
+
+constexpr int kOvRows = 64, kOvWaves = 8, kOvCols = 56, kOvMaxN = kOvWaves * kOvCols;  // 448, as ad_onepass_kernel
+static_assert(kOvMaxN == ADMM_SVM_OVR_MAX_N, "the header states the limit");
+constexpr int kOvSlotsPerWave = (kOvrChunk + kOvWaves - 1) / kOvWaves;  // classes whose element update one wave runs
+
+// the ProxArgs of one class: plain ADMM, B = -1, c = 0, no histories (the compiler folds the constant fields)
+__device__ __forceinline__ ProxArgs ovr_prox_args(const OvrPassArgs& a, int cls, int32_t loss) {
+  ProxArgs pa{};
+  pa.len = a.m;
+  pa.z = a.Z + static_cast<int64_t>(cls) * a.ldz;
+  pa.u = a.U + static_cast<int64_t>(cls) * a.ldz;
+  pa.ell = a.ELL + static_cast<int64_t>(cls) * a.ldz;
+  pa.rho = a.rho;
+  pa.relax = 1.0;
+  pa.prox = (loss == ADMM_LOSS_01) ? PROX_01 : PROX_HINGE;                   // getProxOps.m:1094
+  pa.t = (loss == ADMM_LOSS_01) ? a.rho / a.C : a.C / a.rho;                 // getProxOps.m:1100 | 1096
+  pa.objx = !a.objevals ? OBJX_NONE : (loss == ADMM_LOSS_HINGE ? OBJX_HINGE : OBJX_ZEROONE);  // linearsvm.m:231-237
+  pa.objz = OBJZ_NONE;
+  pa.alg = 0;
+  pa.a_identity = 0;
+  pa.rhs_kind = RHS_NONE;
+  return pa;
+}
+
+// INIT: only the partial rows of D'(z0 - u0), before the first iteration
+template <int KC, bool INIT>
+__global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a) {
+  __shared__ __attribute__((aligned(16))) double xs[kOvMaxN * KC];  // [column][class]: one column's KC values contiguous
+  __shared__ double gacc[KC * kOvMaxN];
+  __shared__ double axr[kOvWaves * KC * kOvRows];
+  __shared__ double tsh[KC * kOvRows];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t n = a.n, m = a.m;
+  uint32_t actv = 0;  // bit c: class c0 + c exists and is still running
+#pragma unroll
+  for (int c = 0; c < KC; ++c) {
+    const int cls = a.c0 + c;
+    const int32_t st = a.rec[cls < a.K ? cls : a.K - 1].stop;
+    if (cls < a.K && st == 0) actv |= 1u << c;
+  }
+  const uint32_t act = __builtin_amdgcn_readfirstlane(actv);
+  if (act == 0) return;  // every class of the chunk has stopped: a no-op
+  for (int idx = tid; idx < kOvMaxN * KC; idx += kOvWaves * kWave) {
+    const int j = idx / KC, c = idx - j * KC;
+    const int cls = a.c0 + c;
+    double xv = 0.0;
+    if (!INIT && j < n && cls < a.K) xv = a.X[static_cast<int64_t>(cls) * a.ldx + j];
+    xs[idx] = xv;
+    gacc[idx] = 0.0;
+  }
+  __syncthreads();
+  // the classes whose element update this wave runs: w, w + 8, ...
+  double acc[kOvSlotsPerWave][S_COUNT];
+  ProxArgs pas[kOvSlotsPerWave];
+#pragma unroll
+  for (int s = 0; s < kOvSlotsPerWave; ++s) {
+#pragma unroll
+    for (int q = 0; q < S_COUNT; ++q) acc[s][q] = 0.0;
+    const int c = w + kOvWaves * s;
+    const int cls = (a.c0 + c < a.K) ? a.c0 + c : a.K - 1;
+    pas[s] = ovr_prox_args(a, cls, a.loss[cls]);
+  }
+  const int64_t nblocks = (m + kOvRows - 1) / kOvRows;
+  for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const int64_t r = blk * kOvRows + lane;
+    const int64_t rc = r < m ? r : m - 1;
+    const double* __restrict__ drow = a.D + rc;
+    double d[kOvCols];
+#pragma unroll
+    for (int k = 0; k < kOvCols; ++k) {  // clamped columns: the loads stay unconditional, x is zero beyond n
+      const int64_t j = w + kOvWaves * k;
+      d[k] = drow[(j < n ? j : n - 1) * a.ldD];
+    }
+    double zp[kOvSlotsPerWave], uo[kOvSlotsPerWave], el[kOvSlotsPerWave];
+#pragma unroll
+    for (int s = 0; s < kOvSlotsPerWave; ++s) {  // in flight with the block
+      zp[s] = pas[s].z[rc];
+      uo[s] = pas[s].u[rc];
+      el[s] = pas[s].ell[rc];
+    }
+    if (!INIT) {
+      double p[KC];
+#pragma unroll
+      for (int c = 0; c < KC; ++c) p[c] = 0.0;
+#pragma unroll
+      for (int k = 0; k < kOvCols; ++k) {
+        const double* __restrict__ xk = xs + (w + kOvWaves * k) * KC;  // same address in every lane: LDS broadcast
+#pragma unroll
+        for (int c = 0; c < KC; ++c) p[c] = __builtin_fma(d[k], xk[c], p[c]);
+      }
+#pragma unroll
+      for (int c = 0; c < KC; ++c) axr[(w * KC + c) * kOvRows + lane] = p[c];
+      __syncthreads();
+    }
+#pragma unroll
+    for (int s = 0; s < kOvSlotsPerWave; ++s) {
+      const int c = w + kOvWaves * s;
+      if (c < KC && ((act >> c) & 1u)) {  // wave-uniform
+        double t = 0.0;
+        if (INIT) {
+          if (r < m) t = (0.0 + zp[s]) - uo[s];  // (c + z0) - u0 with c = 0, as prox_apply forms it
+        } else {
+          double ax = axr[c * kOvRows + lane];
+#pragma unroll
+          for (int q = 1; q < kOvWaves; ++q) ax += axr[(q * KC + c) * kOvRows + lane];
+          ProxIn in{};
+          in.zp = zp[s];
+          in.u_old = uo[s];
+          in.uhat_i = uo[s];
+          in.ell_i = el[s];
+          if (r < m) prox_apply(pas[s], r, ax, 0, 0.0, in, acc[s], &t);
+        }
+        tsh[c * kOvRows + lane] = t;  // rows beyond m contribute nothing
+      }
+    }
+    __syncthreads();
+    static_assert(kOvCols % kSyPanel == 0, "column sums are taken four at a time");
+#pragma unroll 1
+    for (int c = 0; c < KC; ++c) {
+      if (!((act >> c) & 1u)) continue;  // wave-uniform
+      const double t = tsh[c * kOvRows + lane];
+#pragma unroll
+      for (int k = 0; k < kOvCols; k += kSyPanel) {  // four column sums per permlane / DPP reduce-scatter (wave_reduce.h)
+        double q[kSyPanel];
+#pragma unroll
+        for (int i = 0; i < kSyPanel; ++i) q[i] = d[k + i] * t;
+        const double sum = reduce_scatter4(q);  // lanes 16i .. 16i+15 hold the sum of column k + i
+        const int j = w + kOvWaves * (k + (lane >> 4));
+        if ((lane & 15) == 0 && j < n) gacc[c * kOvMaxN + j] += sum;  // (each wave owns its columns)
+      }
+    }
+    // (axr and tsh are rewritten only behind the next block's first barrier: every wave has left this block's reads by then)
+    if (INIT) __syncthreads();  // (no such barrier without the D*x phase)
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int c = 0; c < KC; ++c) {
+    if (!((act >> c) & 1u)) continue;
+    double* __restrict__ gout = a.gpart + (static_cast<int64_t>(blockIdx.x) * a.K + (a.c0 + c)) * a.ldx;
+    for (int j = tid; j < n; j += kOvWaves * kWave) gout[j] = gacc[c * kOvMaxN + j];
+  }
+  if (INIT) return;
+  constexpr int slot_of[OV_COUNT] = {S_R2, S_AX2, S_Z2, S_DZ2, S_DU2, S_OBJX};
+#pragma unroll
+  for (int s = 0; s < kOvSlotsPerWave; ++s) {
+    const int c = w + kOvWaves * s;
+    if (c < KC && ((act >> c) & 1u)) {
+#pragma unroll
+      for (int q = 0; q < OV_COUNT; ++q) {
+        const double v = wave_sum(acc[s][slot_of[q]]);
+        if (lane == 0) a.part[(static_cast<int64_t>(a.c0 + c) * OV_COUNT + q) * kOvrMaxWg + blockIdx.x] = v;
+      }
+    }
+  }
+}
+
+// blockIdx.y = class.  blockIdx.x < tiles: g_c[64 columns] = sum over the workgroups' partial rows, wave q takes rows
+// q, q + 4, ... sixteen loads at a time, the four wave sums added in wave order.  The extra workgroup (a.fin): the
+// finalize logic of the class's iteration -- admm.m:612-722 as oracle/admm_ref.py restates it, for plain ADMM with
+// nodualerror = 1 and stopcond = 'both'.
+__global__ __launch_bounds__(kBlock) void ovr_gsum_fin_kernel(OvrFinArgs a) {
+  const int cls = blockIdx.y;
+  OvrRec* rec = a.rec + cls;
+  const int32_t stopped = rec->stop;
+  const int32_t it = rec->iter;
+  if (stopped) return;
+  __shared__ double sq[4][kOvrTile];
+  __shared__ double S[8];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tiles = static_cast<int>((a.n + kOvrTile - 1) / kOvrTile);
+  if (static_cast<int>(blockIdx.x) < tiles) {
+    const int64_t j0 = static_cast<int64_t>(blockIdx.x) * kOvrTile;
+    const int64_t j = (j0 + lane < a.n) ? j0 + lane : a.n - 1;
+    const double* __restrict__ G = a.gpart + static_cast<int64_t>(cls) * a.ldx + j;
+    const int64_t rowstride = static_cast<int64_t>(a.K) * a.ldx;
+    double s = 0.0;
+    for (int32_t b0 = wid; b0 < a.nwg; b0 += 64) {
+      double v[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int32_t b = (b0 + 4 * k < a.nwg) ? b0 + 4 * k : a.nwg - 1;
+        v[k] = G[static_cast<int64_t>(b) * rowstride];
+      }
+#pragma unroll
+      for (int k = 0; k < 16; ++k) s += (b0 + 4 * k < a.nwg) ? v[k] : 0.0;
+    }
+    sq[wid][lane] = s;
+    __syncthreads();
+    if (wid == 0 && j0 + lane < a.n)
+      a.gsum[static_cast<int64_t>(cls) * a.ldx + j0 + lane] = ((sq[0][lane] + sq[1][lane]) + sq[2][lane]) + sq[3][lane];
+    return;
+  }
+  // ---- finalize of class cls: 32 lanes per slot stride over the block partials, then a fixed shuffle tree
+  {
+    const int slot = tid >> 5, sub = tid & 31;
+    double v = 0.0;
+    if (slot < OV_COUNT) {
+      const double* __restrict__ ps = a.part + (static_cast<int64_t>(cls) * OV_COUNT + slot) * kOvrMaxWg;
+      double wv[kOvrMaxWg / 32];
+#pragma unroll
+      for (int k = 0; k < kOvrMaxWg / 32; ++k) {
+        const int b = sub + 32 * k;
+        wv[k] = ps[b < a.nwg ? b : a.nwg - 1];
+      }
+#pragma unroll
+      for (int k = 0; k < kOvrMaxWg / 32; ++k)
+        if (sub + 32 * k < a.nwg) v += wv[k];
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (sub == 0 && slot < 8) S[slot] = v;
+  }
+  double xx = 0.0;
+  if (a.objevals) {
+    const double* __restrict__ x = a.X + static_cast<int64_t>(cls) * a.ldx;
+    for (int64_t j = tid; j < a.n; j += kBlock) xx += x[j] * x[j];
+  }
+  xx = wave_sum(xx);
+  if (lane == 0) sq[0][wid] = xx;
+  __syncthreads();
+  if (tid != 0) return;
+  const double nx2 = ((sq[0][0] + sq[0][1]) + sq[0][2]) + sq[0][3];
+  const int i1 = it + 1;  // 1-based iteration number (admm.m loop variable)
+  const int64_t h = static_cast<int64_t>(cls) * a.hist_ld + it;
+  const double hn = a.rho * S[OV_DZ2] + a.rho * (a.rho * a.rho) * S[OV_DU2];  // admm.m:305-306, w = [x; z; rho*u]
+  a.hnorm[h] = hn;
+  if (a.objevals) a.objv[h] = a.C * S[OV_OBJX] + 0.5 * nx2;  // linearsvm.m:231-237
+  const double pn = sqrt(S[OV_R2]);  // admm.m:621
+  const double pe = sqrt(static_cast<double>(a.m)) * a.abstol +
+                    a.reltol * fmax(fmax(sqrt(S[OV_AX2]), sqrt(S[OV_Z2])), 0.0);  // admm.m:644-650, c = 0
+  a.pnorm[h] = pn;
+  a.perr[h] = pe;
+  bool stop = false;
+  if (!a.domaxiters && pn < pe) stop = true;                        // admm.m:710-713, nodualerror
+  if (!a.domaxiters && i1 > 2 && hn <= a.Hnormtol) stop = true;     // admm.m:719-722
+  rec->iter = i1;
+  rec->steps = i1;
+  if (stop) rec->early = 1;
+  if (stop || i1 >= a.maxiters) rec->stop = 1;
+}
+
+// x_c(64 rows) = M(64 rows, :) g_c: lane = row (M is symmetric: column-major reads are coalesced along the row index),
+// wave q takes the columns j = q (mod 4), the four partial sums added in wave order
+__global__ __launch_bounds__(kBlock) void ovr_xsolve_kernel(OvrSolveArgs a) {
+  const int cls = blockIdx.y;
+  if (a.rec[cls].stop) return;
+  __shared__ double gs[kOvMaxN + 32];  // (the unrolled column loop reads up to 28 entries past its start: zeros)
+  __shared__ double red[4][kOvrTile];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int64_t n = a.n;
+  for (int j = tid; j < kOvMaxN + 32; j += kBlock) gs[j] = j < n ? a.gsum[static_cast<int64_t>(cls) * a.ldx + j] : 0.0;
+  __syncthreads();
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kOvrTile + lane;
+  const double* __restrict__ mrow = a.M + (i < n ? i : n - 1);
+  double s = 0.0;
+  for (int j0 = wid; j0 < n; j0 += 4 * 8) {
+    double v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t j = j0 + 4 * k;
+      v[k] = mrow[(j < n ? j : n - 1) * a.ldM];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s = __builtin_fma(v[k], gs[j0 + 4 * k], s);  // gs is zero beyond n
+  }
+  red[wid][lane] = s;
+  __syncthreads();
+  if (wid == 0 && i < n)
+    a.X[static_cast<int64_t>(cls) * a.ldx + i] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+
+__global__ __launch_bounds__(kBlock) void ovr_xcopy_kernel(const double* __restrict__ Xnew, double* __restrict__ X,
+                                                           int64_t ldx, int64_t n, const OvrRec* __restrict__ rec) {
+  const int cls = blockIdx.y;
+  if (rec[cls].stop) return;
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (j < n) X[static_cast<int64_t>(cls) * ldx + j] = Xnew[static_cast<int64_t>(cls) * ldx + j];
+}
+
+int ovr_pass_workgroups(int64_t m) {
+  return static_cast<int>(std::min<int64_t>(ceil_div(m, int64_t{kOvRows}), kOvrMaxWg));  // one per CU
+}
+
+void launch_ovr_pass(const OvrPassArgs& a, bool init, hipStream_t stream) {
+  const dim3 grid(static_cast<unsigned>(ovr_pass_workgroups(a.m))), block(kOvWaves * kWave);
+  if (init) hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, true>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false>), grid, block, 0, stream, a);
+}
+
+void launch_ovr_gsum_fin(const OvrFinArgs& a, hipStream_t stream) {
+  const unsigned tiles = static_cast<unsigned>(ceil_div(a.n, int64_t{kOvrTile}));
+  hipLaunchKernelGGL(ovr_gsum_fin_kernel, dim3(tiles + (a.fin ? 1u : 0u), static_cast<unsigned>(a.K)), dim3(kBlock), 0,
+                     stream, a);
+}
+
+void launch_ovr_xsolve(const OvrSolveArgs& a, int32_t K, hipStream_t stream) {
+  hipLaunchKernelGGL(ovr_xsolve_kernel,
+                     dim3(static_cast<unsigned>(ceil_div(a.n, int64_t{kOvrTile})), static_cast<unsigned>(K)),
+                     dim3(kBlock), 0, stream, a);
+}
+
+void launch_ovr_xcopy(const double* Xnew, double* X, int64_t ldx, int64_t n, int32_t K, const OvrRec* rec,
+                      hipStream_t stream) {
+  hipLaunchKernelGGL(ovr_xcopy_kernel, dim3(static_cast<unsigned>(ceil_div(n, int64_t{kBlock})), static_cast<unsigned>(K)),
+                     dim3(kBlock), 0, stream, Xnew, X, ldx, n, rec);
+}
+
+}  // namespace admm
+
+// ---------------------------------------------------------------------------------------------------------- the object
+struct admm_svm_ovr {
+  admm_engine* eng = nullptr;  // an ordinary ADMM_PROB_LINEARSVM engine: owns D and the factor of D'D; never run
+  hipStream_t stream = nullptr;  // = eng->stream
+  DevMem mem;
+  int device = 0;
+  int64_t m = 0, n = 0, ldx = 0, ldz = 0;
+  int32_t K = 0, nwg = 0;
+  double C = 0.0;
+  const double* M = nullptr;   // the explicit n x n map (the engine's, or Dplus*Dplus'); null: triangular solves
+  int64_t ldM = 0;
+  double *X = nullptr, *Z = nullptr, *U = nullptr, *ELL = nullptr, *gpart = nullptr, *gsum = nullptr, *part = nullptr,
+         *xtmp = nullptr;
+  int32_t* loss = nullptr;
+  OvrRec* rec = nullptr;
+  OvrRec* rec_host = nullptr;  // pinned
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // histories of the last run: [K][hist_ld]
+  double *pnorm = nullptr, *perr = nullptr, *hnorm = nullptr, *objv = nullptr;
+  int32_t hist_ld = 0;
+  bool has_run = false;
+  admm_svm_ovr_options last{};
+  std::vector<int32_t> steps;
+};
+
+namespace {
+
+const char* kPerClass = ": run one ADMM_PROB_LINEARSVM engine (admm_engine_create) per class instead";
+
+int ovr_upload_cols(admm_svm_ovr* o, double* dst, int64_t ld, const double* src, int64_t rows, int kind) {
+  if (!src) {
+    ADMM_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * ld * o->K, o->stream));
+    return ADMM_OK;
+  }
+  ADMM_HIP_TRY(hipMemcpy2DAsync(dst, ld * sizeof(double), src, rows * sizeof(double), rows * sizeof(double), o->K,
+                                kind == ADMM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o->stream));
+  return ADMM_OK;
+}
+
+int ovr_setup(admm_svm_ovr* o, const admm_svm_ovr_desc* desc) {
+  const int64_t m = desc->m, n = desc->n;
+  const int32_t K = desc->K;
+  admm_problem_desc d;
+  admm_problem_desc_default(&d);
+  d.problem = ADMM_PROB_LINEARSVM;
+  d.m = m;
+  d.n = n;
+  d.D = desc->D;
+  d.ldD = desc->ldD;
+  d.ell = desc->ELL;  // (the engine wants one label vector; it never runs)
+  d.C = desc->C;
+  d.loss = ADMM_LOSS_HINGE;
+  d.mem = desc->mem;
+  d.device = desc->device;
+  ADMM_TRY(admm_engine_create(&d, &o->eng));
+  admm_engine* e = o->eng;
+  o->stream = e->stream;
+  o->device = e->device;
+  o->m = m;
+  o->n = n;
+  o->K = K;
+  o->C = desc->C;
+  o->ldx = round_up(n, 2);
+  o->ldz = round_up(m, 2);
+  o->nwg = ovr_pass_workgroups(m);
+  if (desc->Dplus) {  // (D'D)^+ = Dplus*Dplus' from the caller's pseudo-inverse (linearsvm.m:185-186)
+    double *Dp = nullptr, *Mo = nullptr;
+    ADMM_TRY(upload(o->mem, &Dp, desc->Dplus, static_cast<size_t>(n) * m, desc->mem, o->stream));
+    const int64_t ld = round_up(n, 2);
+    ADMM_TRY(o->mem.alloc(&Mo, static_cast<size_t>(ld) * n));
+    ADMM_HIP_TRY(hipMemsetAsync(Mo, 0, sizeof(double) * ld * n, o->stream));
+    launch_gemm(0, 1, n, n, m, 1.0, Dp, n, Dp, n, 0.0, Mo, ld, false, o->stream);
+    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
+    o->mem.free_one(Dp);
+    o->M = Mo;
+    o->ldM = ld;
+  } else if (e->xfac.mode == ADMM_XSOLVE_INVERSE && e->xfac.Minv && !e->xfac.planSy.packed) {
+    o->M = e->xfac.Minv;  // (D'D)^-1, or (D'D)^+ of a rank-deficient D: full symmetric storage below kSymvHalfMin
+    o->ldM = e->xfac.ldM;
+  } else if (e->xfac.mode == ADMM_XSOLVE_TRSV && e->xfac.F) {
+    // create's accuracy probe kept the triangular solves: they run per class (K small launches), nothing is forced
+    ADMM_TRY(o->mem.alloc(&o->xtmp, static_cast<size_t>(o->ldx) * K));
+    ADMM_HIP_TRY(hipMemsetAsync(o->xtmp, 0, sizeof(double) * o->ldx * K, o->stream));
+  } else {
+    return fail(ADMM_E_UNSUPPORTED, std::string("the engine built no n x n form of the x-update for this D") + kPerClass);
+  }
+  ADMM_TRY(o->mem.alloc(&o->X, static_cast<size_t>(o->ldx) * K));
+  ADMM_TRY(o->mem.alloc(&o->gsum, static_cast<size_t>(o->ldx) * K));
+  ADMM_HIP_TRY(hipMemsetAsync(o->gsum, 0, sizeof(double) * o->ldx * K, o->stream));
+  ADMM_TRY(o->mem.alloc(&o->Z, static_cast<size_t>(o->ldz) * K));
+  ADMM_TRY(o->mem.alloc(&o->U, static_cast<size_t>(o->ldz) * K));
+  ADMM_TRY(o->mem.alloc(&o->ELL, static_cast<size_t>(o->ldz) * K));
+  ADMM_HIP_TRY(hipMemsetAsync(o->ELL, 0, sizeof(double) * o->ldz * K, o->stream));
+  ADMM_TRY(ovr_upload_cols(o, o->ELL, o->ldz, desc->ELL, m, desc->mem));
+  ADMM_TRY(o->mem.alloc(&o->gpart, static_cast<size_t>(o->nwg) * K * o->ldx));
+  ADMM_TRY(o->mem.alloc(&o->part, static_cast<size_t>(K) * OV_COUNT * kOvrMaxWg));
+  ADMM_HIP_TRY(hipMemsetAsync(o->part, 0, sizeof(double) * K * OV_COUNT * kOvrMaxWg, o->stream));
+  double* raw = nullptr;
+  ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(int32_t) + 7) / 8));
+  o->loss = reinterpret_cast<int32_t*>(raw);
+  std::vector<int32_t> lh(static_cast<size_t>(K), ADMM_LOSS_HINGE);
+  if (desc->loss)
+    for (int32_t c = 0; c < K; ++c) lh[c] = desc->loss[c];
+  ADMM_HIP_TRY(hipMemcpyAsync(o->loss, lh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
+  ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(OvrRec) + 7) / 8));
+  o->rec = reinterpret_cast<OvrRec*>(raw);
+  ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
+  ADMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&o->rec_host), sizeof(OvrRec) * K));
+  ADMM_HIP_TRY(hipEventCreate(&o->ev0));
+  ADMM_HIP_TRY(hipEventCreate(&o->ev1));
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (lh, and the caller's buffers, were read)
+  return ADMM_OK;
+}
+
+int ovr_poll(admm_svm_ovr* o, bool* all_stopped) {
+  ADMM_HIP_TRY(hipMemcpyAsync(o->rec_host, o->rec, sizeof(OvrRec) * o->K, hipMemcpyDeviceToHost, o->stream));
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
+  bool all = true;
+  for (int32_t c = 0; c < o->K; ++c) all = all && o->rec_host[c].stop != 0;
+  *all_stopped = all;
+  return ADMM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void admm_svm_ovr_desc_default(admm_svm_ovr_desc* d) {
+  if (!d) return;
+  std::memset(d, 0, sizeof(*d));
+  d->struct_size = sizeof(admm_svm_ovr_desc);
+  d->K = 1;
+}
+
+void admm_svm_ovr_options_default(admm_svm_ovr_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = sizeof(admm_svm_ovr_options);
+  o->maxiters = 1000;  // unwrappedadmm.m:90
+  o->rho = 1.0;        // admm.m:57
+  o->abstol = 1e-5;    // admm.m:71
+  o->reltol = 1e-3;    // admm.m:72
+  o->Hnormtol = 1e-6;  // admm.m:73
+  o->relax = 1.0;      // admm.m:60
+}
+
+int admm_svm_ovr_chunk(void) { return kOvrChunk; }
+
+int admm_svm_ovr_create(const admm_svm_ovr_desc* desc, admm_svm_ovr** out) {
+  if (!desc || !out) return fail(ADMM_E_INVALID, "desc/out is NULL");
+  *out = nullptr;
+  if (desc->struct_size != static_cast<int32_t>(sizeof(admm_svm_ovr_desc)))
+    return fail(ADMM_E_INVALID, "admm_svm_ovr_desc.struct_size mismatch (ABI version skew)");
+  if (desc->K < 1) return fail(ADMM_E_INVALID, "the one-vs-rest linear SVM needs at least one class (K >= 1)");
+  if (!desc->D || desc->m <= 0 || desc->n <= 0) return fail(ADMM_E_INVALID, "the linear SVM needs D (m x n)");
+  if (!desc->ELL) return fail(ADMM_E_INVALID, "the linear SVM needs the label matrix ELL (m x K)");
+  if (!(desc->C >= 0.0)) return fail(ADMM_E_INVALID, "Given regularization parameter C is not a nonnegative number!");
+  if (desc->loss)
+    for (int32_t c = 0; c < desc->K; ++c)
+      if (desc->loss[c] != ADMM_LOSS_HINGE && desc->loss[c] != ADMM_LOSS_01 && desc->loss[c] != ADMM_LOSS_HINGE_OBJ01)
+        return fail(ADMM_E_INVALID, "bad loss for class " + std::to_string(c));
+  if (desc->comm)
+    return fail(ADMM_E_UNSUPPORTED, std::string("the one-vs-rest linear SVM is not row-sharded") + kPerClass);
+  if (desc->n > kOvMaxN)
+    return fail(ADMM_E_UNSUPPORTED, "the one-vs-rest pass holds a 64-row block of D in registers: n <= " +
+                                        std::to_string(kOvMaxN) + kPerClass);
+  admm_svm_ovr* o = new admm_svm_ovr();
+  const int rc = ovr_setup(o, desc);
+  if (rc != ADMM_OK) {
+    const std::string msg = admm_last_error();
+    admm_svm_ovr_destroy(o);
+    return fail(rc, msg);
+  }
+  *out = o;
+  return ADMM_OK;
+}
+
+int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm_ovr_summary* summaries,
+                     double* runtime_s) {
+  if (!o || !opts) return fail(ADMM_E_INVALID, "object/options is NULL");
+  if (opts->struct_size != static_cast<int32_t>(sizeof(admm_svm_ovr_options)))
+    return fail(ADMM_E_INVALID, "admm_svm_ovr_options.struct_size mismatch (ABI version skew)");
+  admm_svm_ovr_options op = *opts;
+  if (op.fast != ADMM_FAST_OFF)
+    return fail(ADMM_E_UNSUPPORTED, std::string("fast / accelerated ADMM is not part of the one-vs-rest loop") + kPerClass);
+  if (op.relax != 1.0)
+    return fail(ADMM_E_UNSUPPORTED, std::string("relaxation is not part of the one-vs-rest loop") + kPerClass);
+  if (op.convtest)
+    return fail(ADMM_E_UNSUPPORTED, std::string("convtest is not part of the one-vs-rest loop") + kPerClass);
+  if (!(op.rho > 0.0)) return fail(ADMM_E_INVALID, "options.rho must be positive");
+  if (op.maxiters <= 0) op.maxiters = 1000;  // admm.m:334-339
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  const int32_t N = op.maxiters, K = o->K;
+  if (o->hist_ld != N) {
+    for (double** p : {&o->pnorm, &o->perr, &o->hnorm, &o->objv}) {
+      o->mem.free_one(*p);
+      *p = nullptr;
+      ADMM_TRY(o->mem.alloc(p, static_cast<size_t>(N) * K));
+    }
+    o->hist_ld = N;
+  }
+  o->has_run = false;
+  ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
+  ADMM_TRY(ovr_upload_cols(o, o->X, o->ldx, op.x0, o->n, ADMM_MEM_HOST));
+  ADMM_TRY(ovr_upload_cols(o, o->Z, o->ldz, op.z0, o->m, ADMM_MEM_HOST));
+  ADMM_TRY(ovr_upload_cols(o, o->U, o->ldz, op.u0, o->m, ADMM_MEM_HOST));
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (host buffers were read)
+
+  OvrPassArgs pa{};
+  pa.D = o->eng->D;
+  pa.ldD = o->eng->ldD;
+  pa.m = o->m;
+  pa.n = o->n;
+  pa.X = o->X;
+  pa.ldx = o->ldx;
+  pa.Z = o->Z;
+  pa.U = o->U;
+  pa.ELL = o->ELL;
+  pa.ldz = o->ldz;
+  pa.loss = o->loss;
+  pa.gpart = o->gpart;
+  pa.part = o->part;
+  pa.rec = o->rec;
+  pa.K = K;
+  pa.objevals = op.objevals;
+  pa.rho = op.rho;
+  pa.C = o->C;
+  OvrFinArgs fa{};
+  fa.gpart = o->gpart;
+  fa.gsum = o->gsum;
+  fa.part = o->part;
+  fa.X = o->X;
+  fa.ldx = o->ldx;
+  fa.n = o->n;
+  fa.m = o->m;
+  fa.K = K;
+  fa.nwg = o->nwg;
+  fa.rec = o->rec;
+  fa.pnorm = o->pnorm;
+  fa.perr = o->perr;
+  fa.hnorm = o->hnorm;
+  fa.objv = o->objv;
+  fa.hist_ld = N;
+  fa.rho = op.rho;
+  fa.C = o->C;
+  fa.abstol = op.abstol;
+  fa.reltol = op.reltol;
+  fa.Hnormtol = op.Hnormtol;
+  fa.domaxiters = op.domaxiters;
+  fa.objevals = op.objevals;
+  fa.maxiters = N;
+  OvrSolveArgs sa{};
+  sa.M = o->M;
+  sa.ldM = o->ldM;
+  sa.n = o->n;
+  sa.gsum = o->gsum;
+  sa.X = o->X;
+  sa.ldx = o->ldx;
+  sa.rec = o->rec;
+  const int32_t chunks = (K + kOvrChunk - 1) / kOvrChunk;
+  auto pass = [&](bool init) {
+    for (int32_t ch = 0; ch < chunks; ++ch) {
+      pa.c0 = ch * kOvrChunk;
+      launch_ovr_pass(pa, init, o->stream);
+    }
+  };
+  const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
+
+  ADMM_HIP_TRY(hipEventRecord(o->ev0, o->stream));
+  pass(true);  // g = D'(z0 - u0)
+  fa.fin = 0;
+  launch_ovr_gsum_fin(fa, o->stream);
+  fa.fin = 1;
+  bool all = false;
+  for (int32_t it = 0; it < N && !all; ++it) {
+    if (o->M) {
+      launch_ovr_xsolve(sa, K, o->stream);
+    } else {
+      for (int32_t c = 0; c < K; ++c)
+        launch_trsv_pair(o->eng->xfac.trsv, o->gsum + static_cast<int64_t>(c) * o->ldx,
+                         o->xtmp + static_cast<int64_t>(c) * o->ldx, nullptr, o->stream);
+      launch_ovr_xcopy(o->xtmp, o->X, o->ldx, o->n, K, o->rec, o->stream);
+    }
+    pass(false);
+    launch_ovr_gsum_fin(fa, o->stream);
+    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(ovr_poll(o, &all));
+  }
+  ADMM_HIP_TRY(hipEventRecord(o->ev1, o->stream));
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
+  ADMM_HIP_TRY(hipGetLastError());
+  if (!all) return fail(ADMM_E_DEVICE, "the one-vs-rest loop ended with classes still running");
+  float ms = 0.f;
+  ADMM_HIP_TRY(hipEventElapsedTime(&ms, o->ev0, o->ev1));
+  if (runtime_s) *runtime_s = 1e-3 * static_cast<double>(ms);
+  o->steps.assign(static_cast<size_t>(K), 0);
+  std::vector<double> objh;
+  if (op.objevals) {
+    objh.resize(static_cast<size_t>(N) * K);
+    ADMM_HIP_TRY(hipMemcpy(objh.data(), o->objv, sizeof(double) * N * K, hipMemcpyDeviceToHost));
+  }
+  for (int32_t c = 0; c < K; ++c) {
+    const OvrRec& r = o->rec_host[c];
+    o->steps[c] = r.steps;
+    if (summaries) {
+      summaries[c].steps = r.steps;
+      summaries[c].stopped_early = r.early;
+      summaries[c].objopt = (op.objevals && r.steps > 0) ? objh[static_cast<size_t>(c) * N + r.steps - 1]
+                                                         : __builtin_nan("");
+    }
+  }
+  o->last = op;
+  o->has_run = true;
+  return ADMM_OK;
+}
+
+int admm_svm_ovr_fetch(admm_svm_ovr* o, int field, double* dst, size_t cap, size_t* written) {
+  if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
+  if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  const int32_t K = o->K;
+  auto matrix = [&](const double* src, int64_t ld, int64_t rows) -> int {
+    const size_t need = static_cast<size_t>(rows) * K;
+    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
+    ADMM_HIP_TRY(hipMemcpy2D(dst, rows * sizeof(double), src, ld * sizeof(double), rows * sizeof(double), K,
+                             hipMemcpyDeviceToHost));
+    if (written) *written = need;
+    return ADMM_OK;
+  };
+  auto history = [&](const double* src) -> int {
+    int32_t S = 0;
+    for (int32_t s : o->steps) S = s > S ? s : S;
+    const size_t need = static_cast<size_t>(S) * K;
+    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
+    if (S > 0)
+      ADMM_HIP_TRY(hipMemcpy2D(dst, S * sizeof(double), src, o->hist_ld * sizeof(double), S * sizeof(double), K,
+                               hipMemcpyDeviceToHost));
+    for (int32_t c = 0; c < K; ++c)
+      for (int32_t i = o->steps[c]; i < S; ++i) dst[static_cast<size_t>(c) * S + i] = __builtin_nan("");
+    if (written) *written = need;
+    return ADMM_OK;
+  };
+  switch (field) {
+    case ADMM_OVR_F_XOPT: return matrix(o->X, o->ldx, o->n);
+    case ADMM_OVR_F_ZOPT: return matrix(o->Z, o->ldz, o->m);
+    case ADMM_OVR_F_UOPT: return matrix(o->U, o->ldz, o->m);
+    case ADMM_OVR_F_PNORM: return history(o->pnorm);
+    case ADMM_OVR_F_PERR: return history(o->perr);
+    case ADMM_OVR_F_HNORMSQ: return history(o->hnorm);
+    case ADMM_OVR_F_OBJEVALS:
+      if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
+      return history(o->objv);
+    default: return fail(ADMM_E_INVALID, "unknown field of the one-vs-rest linear SVM");
+  }
+}
+
+void admm_svm_ovr_destroy(admm_svm_ovr* o) {
+  if (!o) return;
+  (void)hipSetDevice(o->device);
+  if (o->stream) (void)hipStreamSynchronize(o->stream);
+  if (o->ev0) (void)hipEventDestroy(o->ev0);
+  if (o->ev1) (void)hipEventDestroy(o->ev1);
+  o->mem.release();
+  if (o->rec_host) (void)hipHostFree(o->rec_host);
+  if (o->eng) admm_engine_destroy(o->eng);
+  delete o;
+}
+
+}  // extern "C"

@@ -507,3 +507,70 @@ class Engine:
         if shape is not None:
             out = out.reshape(shape, order="F")
         return out
+
+
+_LOSS = {"hinge": L.LOSS_HINGE, "01": L.LOSS_01}
+
+
+class SvmOvr:
+    """Python owner of one ``admm_svm_ovr`` handle: the linear SVM for K one-vs-rest classes over one D."""
+
+    def __init__(self, D, ELL, C_, losses, *, Dplus=None, device=0):
+        self._h = None
+        self._lib = L.load()
+        L.require_device()
+        D = _f64(D)
+        ELL = _f64(ELL)
+        self.m, self.n = (int(v) for v in D.shape)
+        self.K = int(ELL.shape[1])
+        loss = np.ascontiguousarray([_LOSS.get(v, L.LOSS_HINGE_OBJ01) for v in losses], dtype=np.int32)
+        d = L.SvmOvrDesc()
+        self._lib.admm_svm_ovr_desc_default(C.byref(d))
+        d.K, d.m, d.n = self.K, self.m, self.n
+        d.D, d.ldD, d.ELL = L.as_dp(D), self.m, L.as_dp(ELL)
+        d.loss = loss.ctypes.data_as(C.POINTER(C.c_int32))
+        d.C, d.mem, d.device = float(C_), L.MEM_HOST, int(device)
+        if Dplus is not None:
+            Dplus = _f64(Dplus)
+            d.Dplus = L.as_dp(Dplus)
+        h = C.c_void_p()
+        L.check(self._lib.admm_svm_ovr_create(C.byref(d), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.admm_svm_ovr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, *, rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, Hnormtol=1e-6, relax=1.0, fast=L.FAST_OFF,
+            convtest=0, domaxiters=0, objevals=0, check_every=0, x0=None, z0=None, u0=None):
+        o = L.SvmOvrOptions()
+        self._lib.admm_svm_ovr_options_default(C.byref(o))
+        o.maxiters, o.rho, o.abstol, o.reltol, o.Hnormtol = int(maxiters), float(rho), float(abstol), float(reltol), \
+            float(Hnormtol)
+        o.relax, o.fast, o.convtest = float(relax), int(fast), int(bool(convtest))
+        o.domaxiters, o.objevals, o.check_every = int(bool(domaxiters)), int(bool(objevals)), int(check_every)
+        keep = [None if v is None else _f64(v) for v in (x0, z0, u0)]
+        for name, v in zip(("x0", "z0", "u0"), keep):
+            if v is not None:
+                setattr(o, name, L.as_dp(v))
+        summ = (L.SvmOvrSummary * self.K)()
+        rt = C.c_double(0)
+        L.check(self._lib.admm_svm_ovr_run(self._h, C.byref(o), summ, C.byref(rt)))
+        self.objevals = bool(objevals)
+        return dict(steps=np.array([s.steps for s in summ], dtype=np.int64),
+                    stopped_early=np.array([s.stopped_early for s in summ], dtype=np.int64),
+                    objopt=np.array([s.objopt for s in summ], dtype=np.float64), runtime=rt.value)
+
+    def fetch(self, field, rows):
+        buf = np.empty((rows, self.K), dtype=np.float64, order="F")
+        w = C.c_size_t(0)
+        L.check(self._lib.admm_svm_ovr_fetch(self._h, field, L.as_dp(buf), buf.size, C.byref(w)))
+        assert w.value == buf.size, (w.value, buf.size)
+        return buf

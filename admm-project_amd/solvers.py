@@ -15,7 +15,7 @@ import numpy as np
 from .api import admm, getproxops
 from .errorcheck import is_nonnegative_real, is_positive_real, slicemaker
 
-__all__ = ["lasso", "lad", "huberfit", "linearsvm", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "lad", "huberfit", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -192,6 +192,116 @@ def linearsvm(D, ell, C, options=None):
     results = unwrappedadmm(minz, D, options)
     results["solverruntime"] = time.perf_counter() - t0
     return results
+
+
+def ovr_label_matrix(labels, classes):
+    """ELL (m x K): ell_c = +1 where labels == classes[c], else -1 (examples/mnistsvm.m:136-142)."""
+    labels = np.asarray(labels).reshape(-1)
+    return np.asfortranarray(np.where(labels[:, None] == np.asarray(classes)[None, :], 1.0, -1.0))
+
+
+_OVR_HIST = ("pnorm", "perr", "Hnormsq", "objevals")
+
+
+def linearsvm_ovr(D, labels, C, options=None):
+    """results = linearsvm_ovr(D, labels, C, options): one linearsvm (solvers/linearsvm.m:92-246) per class of
+    ``labels`` against the rest, as examples/mnistsvm.m:88-102 trains them, in ONE run over D.
+
+    ``labels``: length-m vector of class ids.  ``options['classes']`` (default: the sorted unique labels) selects and
+    orders the K columns and may name a class more than once; ``options['lossfunction']`` is one string or a list with
+    one entry per column.  ``x0`` / ``z0`` / ``u0`` are n x K / m x K matrices (missing: random, unwrappedadmm.m:87-89).
+    The options of the plain loop apply to every class (rho, abstol, reltol, Hnormtol, domaxiters, objevals,
+    check_every); maxiters is 1000, stopcond 'both', nodualerror 1 (unwrappedadmm.m:90-92).
+    Returns classes, xopt (n x K), zopt, uopt (m x K), steps (K), pnorm / perr / Hnormsq / objevals (max(steps) x K,
+    NaN past a class's last step), objopt (K), runtime, solverruntime.  Vector histories are not recorded.
+    For n > 448 the classes run one after the other through ``linearsvm`` and the same fields come back.
+    """
+    if options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise TypeError("Given options is not a struct! At least pass empty struct!")
+    options = dict(options)
+    t0 = time.perf_counter()
+    if not np.isscalar(C) or np.real(C) < 0:  # linearsvm.m:270-274
+        raise ValueError("Given regularization parameter C is not a nonnegative number!")
+    C = float(np.real(C))
+    labels = _colvec(labels, "labels")
+    D = _matrix(D, "D")
+    m, n = D.shape
+    if labels.size != m:
+        raise ValueError("Product ell*D is not possible; sizes incompatible!")  # linearsvm.m:283-286
+    _single_column_quirk(D)
+    classes = np.asarray(options["classes"] if "classes" in options else np.unique(labels), dtype=np.float64)
+    if classes.ndim != 1 or classes.size < 1:
+        raise ValueError("options.classes is not a non-empty vector of class ids!")
+    K = int(classes.size)
+    loss = options.get("lossfunction", "hinge")  # linearsvm.m:154-158
+    losses = [loss] * K if isinstance(loss, str) else list(loss)
+    if len(losses) != K or not all(isinstance(v, str) for v in losses):
+        raise ValueError("options.lossfunction is neither one string nor a list with one string per class!")
+    starts = {}
+    rng = np.random.default_rng()
+    for key, rows in (("x0", n), ("z0", m), ("u0", m)):  # unwrappedadmm.m:87-89, per class
+        if key in options:
+            v = np.asarray(options[key], dtype=np.float64)
+            if v.shape != (rows, K):
+                raise ValueError(f"options.{key} is not a {rows} x {K} matrix (one column per class)!")
+        else:
+            v = rng.random((rows, K))
+        starts[key] = np.asfortranarray(v)
+    for key in ("fast", "convtest"):
+        if options.get(key, 0):
+            raise ValueError(f"options.{key} is not available in linearsvm_ovr: call linearsvm per class")
+    if options.get("relax", 1) != 1:
+        raise ValueError("options.relax is not available in linearsvm_ovr: call linearsvm per class")
+    ELL = ovr_label_matrix(labels, classes)
+    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "domaxiters", "objevals") if k in options}
+    if "Hreltol" in options or "Hnormtol" in options:  # admm.m:927-928 (q2): either spelling
+        loop["Hnormtol"] = options.get("Hreltol", options.get("Hnormtol"))
+    res = dict(classes=classes)
+    if n > 448:  # the one-pass kernel's limit: per-class engines, same fields
+        per = []
+        for c in range(K):
+            o = dict(loop, lossfunction=losses[c], x0=starts["x0"][:, c], z0=starts["z0"][:, c], u0=starts["u0"][:, c],
+                     record_history=0)
+            per.append(linearsvm(D, ELL[:, c], C, o))
+        steps = np.array([r["steps"] for r in per], dtype=np.int64)
+        S = int(steps.max())
+        for key in ("xopt", "zopt", "uopt"):
+            res[key] = np.asfortranarray(np.stack([r[key] for r in per], axis=1))
+        for key in _OVR_HIST:
+            if all(key in r for r in per):
+                h = np.full((S, K), np.nan, order="F")
+                for c, r in enumerate(per):
+                    h[:steps[c], c] = np.asarray(r[key])[:steps[c]]
+                res[key] = h
+        res["steps"] = steps
+        res["objopt"] = np.array([r.get("objopt", np.nan) for r in per], dtype=np.float64)
+        res["runtime"] = float(sum(r["runtime"] for r in per))
+        res["solverruntime"] = time.perf_counter() - t0
+        return res
+    from . import _lib as L
+    from .engine import SvmOvr
+    obj = SvmOvr(D, ELL, C, losses, Dplus=options.get("Dplus"), device=int(options.get("device", 0)))
+    try:
+        summ = obj.run(check_every=int(options.get("check_every", 0)), x0=starts["x0"], z0=starts["z0"],
+                       u0=starts["u0"], **loop)
+        S = int(summ["steps"].max())
+        res["xopt"] = obj.fetch(L.OVR_F_XOPT, n)
+        res["zopt"] = obj.fetch(L.OVR_F_ZOPT, m)
+        res["uopt"] = obj.fetch(L.OVR_F_UOPT, m)
+        res["steps"] = summ["steps"]
+        res["pnorm"] = obj.fetch(L.OVR_F_PNORM, S)
+        res["perr"] = obj.fetch(L.OVR_F_PERR, S)
+        res["Hnormsq"] = obj.fetch(L.OVR_F_HNORMSQ, S)
+        if loop.get("objevals", 0):
+            res["objevals"] = obj.fetch(L.OVR_F_OBJEVALS, S)
+        res["objopt"] = summ["objopt"]
+        res["runtime"] = summ["runtime"]
+    finally:
+        obj.close()
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
 
 
 def quadraticprogram(P, q, r, cons1, cons2, options=None):

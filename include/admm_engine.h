@@ -488,6 +488,87 @@ int admm_engine_create_all(int nranks, const admm_problem_desc* descs, admm_engi
 int admm_engine_run_all(int nranks, admm_engine* const* engines, const admm_options* opts, int opts_per_rank,
                         admm_run_summary* summaries);
 
+/* ---- linear SVM, all one-vs-rest classes in one pass over D (additive to ABI 5) ---------------------------------
+ * examples/mnistsvm.m:88-102 trains one linearsvm per digit and loss on the SAME matrix D: calls that differ only in
+ * the label vector and the loss.  xminLinearSVM is Dplus*(z-u) (getProxOps.m:1062-1068) and does not contain ell; the
+ * labels enter the element-wise z-prox (getProxOps.m:1084-1103) and the objective (linearsvm.m:231-237) alone.  So K
+ * classes are K independent plain-ADMM runs (unwrappedadmm.m:76-92: A = D, B = -1, c = 0, stopcond = 'both',
+ * nodualerror = 1) that share D, its pseudo-inverse and every byte an iteration reads: this object runs them side by
+ * side, one read of D per iteration for a chunk of classes (csrc/svm_ovr.hip).  A class that has met its stop
+ * condition is frozen: its result is that of an independent run with that many steps.
+ * Not available here, each refused with ADMM_E_UNSUPPORTED (use one ADMM_PROB_LINEARSVM engine per class instead):
+ * n > 448, fast ADMM, relaxation, convtest, a communicator; there are no callback or hook entry points.
+ * Vector histories (xvals, zvals, uvals) are not recorded. */
+typedef struct admm_svm_ovr admm_svm_ovr; /* opaque */
+#define ADMM_SVM_OVR_MAX_N 448
+
+/* what mnistsvm.m:88-102 passes to its linearsvm calls, for all of them at once */
+typedef struct admm_svm_ovr_desc {
+  int32_t struct_size;   /* sizeof(admm_svm_ovr_desc) */
+  int32_t K;             /* number of classes (columns of ELL), >= 1 */
+  int64_t m, n;          /* D is m x n */
+  const double* D;       /* m x n, column-major */
+  int64_t ldD;           /* leading dimension of D (0 = m) */
+  const double* ELL;     /* m x K, column-major, +-1: column c is the ell of class c (mnistsvm.m:136-142) */
+  const int32_t* loss;   /* K values ADMM_LOSS_* (linearsvm.m:154-158, 231-237); NULL = hinge for every class */
+  double C;              /* regularisation (linearsvm.m:270-274) */
+  int32_t mem;           /* ADMM_MEM_* of D, ELL, Dplus */
+  int32_t device;        /* HIP device ordinal */
+  const double* Dplus;   /* optional pinv(D), n x m column-major, ld = n (linearsvm.m:185-186): the x-update's
+                            n x n map is then Dplus*Dplus' = (D'D)^+; NULL: built from D'D as admm_engine_create does */
+  admm_comm* comm;       /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_svm_ovr_desc;
+
+/* the options the K runs share (admm.m:51-76); fields of admm_options that have no meaning here are absent, and the
+ * ones that select a variant this object does not run are refused */
+typedef struct admm_svm_ovr_options {
+  int32_t struct_size;   /* sizeof(admm_svm_ovr_options) */
+  int32_t maxiters;      /* default 1000 (unwrappedadmm.m:90 forces it) */
+  double rho;            /* default 1.0 */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double Hnormtol;       /* default 1e-6 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations enqueued between host polls of "every class has stopped" (0 = auto) */
+  int32_t reserved0;
+  const double* x0;      /* n x K host matrix (NULL = zeros; admm.m:252-254) */
+  const double* z0;      /* m x K */
+  const double* u0;      /* m x K */
+} admm_svm_ovr_options;
+
+typedef struct admm_svm_ovr_summary {  /* one per class */
+  int32_t steps;          /* results.steps of that class (admm.m:746) */
+  int32_t stopped_early;  /* 1 if a stop condition fired before maxiters (admm.m:710-722) */
+  double objopt;          /* results.objopt (admm.m:752-754), NaN if not evaluated */
+} admm_svm_ovr_summary;
+
+/* fields of admm_svm_ovr_fetch */
+enum {
+  ADMM_OVR_F_XOPT = 1,      /* n x K */
+  ADMM_OVR_F_ZOPT = 2,      /* m x K */
+  ADMM_OVR_F_UOPT = 3,      /* m x K */
+  /* scalar histories (admm.m:621-658, 305-306, 603-605): S x K column-major with S = the largest steps of any
+   * class, NaN past a class's own last step */
+  ADMM_OVR_F_PNORM = 4, ADMM_OVR_F_PERR = 5, ADMM_OVR_F_HNORMSQ = 6, ADMM_OVR_F_OBJEVALS = 7
+};
+
+void admm_svm_ovr_desc_default(admm_svm_ovr_desc* desc);
+void admm_svm_ovr_options_default(admm_svm_ovr_options* opts);
+/* the one-time setup of linearsvm.m:183-217 for all classes: uploads D and ELL, builds (D'D)^-1 or (D'D)^+ */
+int admm_svm_ovr_create(const admm_svm_ovr_desc* desc, admm_svm_ovr** out);
+/* the K loops of admm.m:496-743; summaries: K entries (may be NULL); runtime_s: the loop alone (admm.m:315 .. 756;
+ * may be NULL).  May be called again on the same object: every run starts from its own x0 / z0 / u0 */
+int admm_svm_ovr_run(admm_svm_ovr* obj, const admm_svm_ovr_options* opts, admm_svm_ovr_summary* summaries,
+                     double* runtime_s);
+int admm_svm_ovr_fetch(admm_svm_ovr* obj, int field, double* dst, size_t cap, size_t* written);
+/* classes one pass over D serves (K beyond it: ceil(K / chunk) passes per iteration) */
+int admm_svm_ovr_chunk(void);
+void admm_svm_ovr_destroy(admm_svm_ovr* obj);
+
 #ifdef __cplusplus
 }
 #endif
