@@ -22,6 +22,14 @@ CASES = (
     "qp_bounded", "basispursuit", "covsel_64", "covsel_97", "lasso_calibration", "lasso_cancelling", "lad_nodual0",
     "lad_nodual1", "huberfit_nodual0", "huberfit_nodual1", "svm_6000", "svm_24000", "svm_fast_strong",
     "consensus_4x64", "tv_5000",
+    "tv_direct_60", "tv_direct_stop_in_batch", "tv_direct_nohist_11", "tv_fused_objevals", "tv_fused_skip_x",
+    "tv_fused_n1", "tv_sweep_rho40", "tv_sweep_rho700", "tv_fast_strong", "tv_fast_weak_objevals", "tv_relax",
+    "tv_fast_weak_relax",
+    "tv2d_glued_64x200", "tv2d_glued_256x256_stop", "tv2d_glued_128x512_nohist", "tv2d_glued_64x256_stop",
+    "tv2d_chirp_100x333",
+    "tv2d_rowdct_64x32", "tv2d_thomas_24x17", "tv2d_thomas_170x110", "tv2d_cg_5x17", "tv2d_cg_64x64",
+    "tv2d_fast_strong_5x17", "tv2d_fast_weak_5x17", "tv2d_fast_strong_24x17", "tv2d_fast_weak_24x17",
+    "tv2d_fast_strong_32x64", "tv2d_fast_weak_32x64",
     "handles_lasso", "handles_lasso_fast_weak", "altu_specialnorms", "general_B_matrix", "general_B_scalar",
     "general_B_handle", "operator_handles", "lad_callers_z_relax",
     "sharded_lad", "sharded_lad_fast_weak", "sharded_svm", "sharded_lasso", "sharded_lasso_symv",
@@ -99,6 +107,72 @@ def library_cases(ap):
     yield "consensus_4x64", lambda: ap.lasso(cl["D"], cl["s"], cl["lam"], dict(parallel="both", workers=4, objevals=1))
     tv = sy.tv_problem(0, 5000)
     yield "tv_5000", lambda: ap.totalvariation(tv["s"], tv["lam"], dict(objevals=1))
+    yield from tv_form_cases(ap)
+    yield from tv2d_form_cases(ap)
+
+
+def tv_form_cases(ap):
+    """One case per iteration form of engine_run_tv.hip, 1-D: the form follows the plan's halo (44 at rho 1 and 254 at
+    rho 36: one launch, direct / fused; 268 at rho 40 and 1116 at rho 700: sweeps with 20 / 48 elements per thread)
+    and the ADMM variant."""
+    L = ap._lib
+
+    def tv(n, **o):
+        p = ap.synth.tv_problem(0, n)
+        return lambda: ap.totalvariation(p["s"], p["lam"], dict(o))
+    yield "tv_direct_60", tv(60, rho=1.0)  # shorter than two margins of 56: the block-scan direct kernel
+    # the stop lands inside a batch: a speculative iteration runs behind it
+    yield "tv_direct_stop_in_batch", tv(4099, rho=1.0, stopcond="both", convtest=1, maxiters=90)
+    yield "tv_direct_nohist_11", tv(4099, rho=1.0, record_history=0, maxiters=11, domaxiters=1)  # x rebuilt by sweeps
+    yield "tv_fused_objevals", tv(4099, rho=36.0, objevals=1, maxiters=37)
+    yield "tv_fused_skip_x", tv(4099, rho=36.0, record_history=0, maxiters=29)
+
+    def n1():  # (totalvariation() refuses a scalar as the reference does: the engine itself)
+        eng = ap.Engine(L.PROB_TOTALVARIATION, s=np.array([0.75]), lam=1.0, nvec=1)
+        try:
+            s = eng.run()
+            res = dict(steps=s.steps, xopt=eng.fetch(L.F_XOPT, 1), zopt=eng.fetch(L.F_ZOPT, 1),
+                       uopt=eng.fetch(L.F_UOPT, 1))
+            for k, f in (("pnorm", L.F_PNORM), ("dnorm", L.F_DNORM), ("perr", L.F_PERR), ("derr", L.F_DERR)):
+                res[k] = eng.fetch(f, s.steps)
+            return res
+        finally:
+            eng.close()
+    yield "tv_fused_n1", n1  # the direct form needs n >= 2
+    yield "tv_sweep_rho40", tv(4099, rho=40.0, maxiters=25)
+    yield "tv_sweep_rho700", tv(4099, rho=700.0, maxiters=25)
+    yield "tv_fast_strong", tv(3000, fast=1, fasttype="strong")
+    yield "tv_fast_weak_objevals", tv(3000, fast=1, fasttype="weak", objevals=1)
+    yield "tv_relax", tv(3000, relax=1.6)
+    yield "tv_fast_weak_relax", tv(3000, fast=1, fasttype="weak", relax=1.6)
+
+
+def _image(seed, H, W):  # as in tests/test_gpu_tv2d.py
+    rng = np.random.default_rng(seed)
+    img = np.zeros((H, W))
+    img[H // 5:H // 2, W // 6:W // 2] = 2.0
+    img[H // 3:4 * H // 5, W // 3:5 * W // 6] += 1.0
+    return img + 0.3 * rng.standard_normal((H, W))
+
+
+def tv2d_form_cases(ap):
+    """2-D: the glued three-launch iteration (Toeplitz row stage, power-of-two height), the four-launch one behind every
+    other column transform or row stage, CG, and fast ADMM on each x-update."""
+    tv2 = lambda H, W, **o: (lambda: ap.totalvariation2d(_image(H + W, H, W), 0.6, dict(o)))
+    yield "tv2d_glued_64x200", tv2(64, 200, rho=1.0, objevals=1, maxiters=30, domaxiters=1)
+    yield "tv2d_glued_256x256_stop", tv2(256, 256, stopcond="both", maxiters=200)  # (runs all 200: no stop with "both")
+    yield "tv2d_glued_128x512_nohist", tv2(128, 512, record_history=0, maxiters=21, domaxiters=1)
+    yield "tv2d_glued_64x256_stop", tv2(64, 256)  # the standard stop, inside a batch: iterations enqueued behind it
+    # chirp column transform: four launches, the deferred finalize a passenger of the forward transform
+    yield "tv2d_chirp_100x333", tv2(100, 333, maxiters=10, domaxiters=1)
+    yield "tv2d_rowdct_64x32", tv2(64, 32, rho=2.5)  # the Toeplitz stage needs 68 taps and 4 * 68 > 32: row DCT
+    yield "tv2d_thomas_24x17", tv2(24, 17, rho=1.0)
+    yield "tv2d_thomas_170x110", tv2(170, 110, rho=2381.0, maxiters=8, domaxiters=1)
+    yield "tv2d_cg_5x17", tv2(5, 17)  # no column transform for five rows
+    yield "tv2d_cg_64x64", tv2(64, 64, xsolve="cg")
+    for H, W in ((5, 17), (24, 17), (32, 64)):
+        for ft in ("strong", "weak"):
+            yield "tv2d_fast_%s_%dx%d" % (ft, H, W), tv2(H, W, fast=1, fasttype=ft)
 
 
 def handle_cases(ap):

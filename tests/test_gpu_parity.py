@@ -1060,6 +1060,28 @@ def _same_run(a, b, what):
         assert np.array_equal(a[k], b[k], equal_nan=True), (what, k)  # (dnorm is NaN where no dual residual is kept)
 
 
+def _one_engine_against_fresh_ones(L, name, mk, seq, check=lambda eng: True):
+    """seq on one engine from mk(): each run bit for bit what a fresh engine gives, the last run (the first one again,
+    so one fresh engine serves both) what the first gave"""
+    eng = mk()
+    try:
+        assert check(eng)
+        got = [_run_and_fetch(L, eng, r) for r in seq]
+    finally:
+        eng.close()
+    first = None
+    for i, r in enumerate(seq[:-1]):
+        fresh = mk()
+        try:
+            ref = _run_and_fetch(L, fresh, r)
+        finally:
+            fresh.close()
+        first = ref if i == 0 else first
+        _same_run(got[i], ref, (name, i))
+    _same_run(got[-1], first, (name, "last run against a fresh engine"))
+    _same_run(got[-1], got[0], (name, "last against first"))
+
+
 def test_one_engine_through_successive_iteration_forms(gpu):
     """What a run of the general loop decides and carries -- the iteration form, the deferred finalize and its
     passenger, the two-launch iteration's parity -- lives in the loop object of that run and must not survive it: one
@@ -1078,20 +1100,28 @@ def test_one_engine_through_successive_iteration_forms(gpu):
     make_svm = lambda: gpu.Engine(L.PROB_LINEARSVM, D=q["D"], ell=q["ell"], Cval=q["C"])
     runs_svm = [dict(start, nodualerror=1), dict(start, fast=L.FAST_STRONG), dict(start, nodualerror=1)]
     for name, mk, seq in (("lasso", make, runs), ("svm", make_svm, runs_svm)):
-        eng = mk()
-        try:
-            assert name != "svm" or eng.info()["unwrapped_fused"]  # (the two-launch form is there to be chosen)
-            got = [_run_and_fetch(L, eng, r) for r in seq]
-        finally:
-            eng.close()
-        first = None
-        for i, r in enumerate(seq[:-1]):  # (the last run is the first one again: one fresh engine serves both)
-            fresh = mk()
-            try:
-                ref = _run_and_fetch(L, fresh, r)
-            finally:
-                fresh.close()
-            first = ref if i == 0 else first
-            _same_run(got[i], ref, (name, i))
-        _same_run(got[-1], first, (name, "last run against a fresh engine"))
-        _same_run(got[-1], got[0], (name, "last against first"))
+        # (the two-launch form is there to be chosen)
+        _one_engine_against_fresh_ones(L, name, mk, seq,
+                                       check=lambda eng: name != "svm" or eng.info()["unwrapped_fused"])
+
+
+def test_one_tv_engine_through_successive_iteration_forms(gpu):
+    """The same for total variation (engine_run_tv.hip): the form of a run, the pending finalize, the buffer rotations
+    of the one-launch forms and which ping-pong buffer holds z, u belong to the run and must not survive it.  1-D,
+    n = 4099: direct (rho 1), fused (rho 36), sweeps (rho 40), unfused (weak fast ADMM; over-relaxation), direct with x
+    rebuilt by sweeps after an odd step count, direct again.  2-D, 64 x 200: glued (rho 1), the Thomas row stage
+    (rho 300), fast ADMM, glued again."""
+    L = gpu._lib
+    p = gpu.synth.tv_problem(0, 4099)
+    make = lambda: gpu.Engine(L.PROB_TOTALVARIATION, s=p["s"], lam=p["lam"], nvec=4099)
+    runs = [dict(rho=1.0), dict(rho=36.0), dict(rho=40.0), dict(fast=L.FAST_WEAK), dict(relax=1.5),
+            dict(record_history=0, maxiters=7, domaxiters=1), dict(rho=1.0)]
+    rng = np.random.default_rng(3)
+    img = np.zeros((64, 200))
+    img[12:32, 33:100] = 2.0
+    img += 0.3 * rng.standard_normal(img.shape)
+    make_2d = lambda: gpu.Engine(L.PROB_TV2D, s=np.asfortranarray(img).reshape(-1, order="F"), lam=0.6,
+                                 shape=img.shape)
+    runs_2d = [dict(rho=1.0), dict(rho=300.0), dict(fast=L.FAST_STRONG), dict(rho=1.0)]
+    for name, mk, seq in (("tv", make, runs), ("tv2d", make_2d, runs_2d)):
+        _one_engine_against_fresh_ones(L, name, mk, seq)
