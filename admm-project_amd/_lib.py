@@ -21,7 +21,19 @@ PROB_LASSO, PROB_LASSO_CONSENSUS, PROB_LAD, PROB_HUBERFIT = 1, 2, 3, 4
 PROB_LINEARSVM, PROB_TOTALVARIATION, PROB_QP_BOUNDED, PROB_BASISPURSUIT = 5, 6, 7, 8
 PROB_MODEL, PROB_LINEARPROGRAM, PROB_QP_STANDARD, PROB_TV2D = 9, 10, 11, 12
 PROB_COVSEL = 13
-LOSS_HINGE, LOSS_01, LOSS_HINGE_OBJ01 = 0, 1, 2
+LOSS_HINGE, LOSS_01, LOSS_HINGE_OBJ01, LOSS_LOGISTIC = 0, 1, 2, 3
+
+
+def loss_code(text):
+    """options.lossfunction -> ADMM_LOSS_*: 'hinge', '01' (as written), 'logistic' in any letter case (DESIGN.md q29);
+    every other string runs the hinge prox with the 0-1 objective (linearsvm.m:154-158, 231-237: q18)."""
+    if text in ("hinge", "01"):
+        return LOSS_HINGE if text == "hinge" else LOSS_01
+    if isinstance(text, str) and text.lower() == "logistic":
+        return LOSS_LOGISTIC
+    return LOSS_HINGE_OBJ01
+
+
 XSOLVE_AUTO, XSOLVE_TRSV, XSOLVE_INVERSE, XSOLVE_CG, XSOLVE_CALLBACK, XSOLVE_PINV = 0, 1, 2, 3, 4, 5
 MEM_HOST, MEM_DEVICE = 0, 1
 STOP_STANDARD, STOP_HNORM, STOP_BOTH, STOP_NONE = 0, 1, 2, 3

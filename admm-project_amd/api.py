@@ -145,7 +145,7 @@ def getproxops(problem, args):
         m, n = D.shape
         # args.Dplus (linearsvm.m:185-186), when the caller supplies it, is applied literally: x = Dplus*(z-u)
         eng = Engine(L.PROB_LINEARSVM, D=D, ell=ell, Cval=Cval,
-                     loss={"hinge": L.LOSS_HINGE, "01": L.LOSS_01}.get(loss, L.LOSS_HINGE_OBJ01), xsolve=xs,
+                     loss=L.loss_code(loss), xsolve=xs,
                      device=dev, comm=comm, Dplus=args.get("Dplus"), **cg)
         prob = _Problem("linearsvm", eng, dict(A="D", c=0.0, nA=n, nB=m))
     elif kind == "linearprogram" or (kind == "quadraticprogram" and _get(args, "constraint") == "standard"):

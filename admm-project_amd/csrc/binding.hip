@@ -136,6 +136,7 @@ int describe(const std::string& p, const View& args, const View& handles, admm_b
     d.loss = !args.get("lossfunction")            ? ADMM_LOSS_HINGE
              : args.text_is("lossfunction", "01") ? ADMM_LOSS_01
              : args.text_is("lossfunction", "hinge") ? ADMM_LOSS_HINGE
+             : args.text_is("lossfunction", "logistic") ? ADMM_LOSS_LOGISTIC
                                                      : ADMM_LOSS_HINGE_OBJ01;  // linearsvmtest.m:160
     const admm_field* Dp = args.get("Dplus");  // linearsvm.m:185-186
     if (View::dense(Dp) && Dp->rows == d.n && Dp->cols == d.m) d.Dplus = Dp->data;

@@ -208,7 +208,7 @@ static int setup_lad_huber_svm(admm_engine* e, const admm_problem_desc* desc, co
   e->rhs_kind = RHS_T1;
   if (desc->problem == ADMM_PROB_LAD) e->prox = PROX_SOFT;
   else if (desc->problem == ADMM_PROB_HUBERFIT) e->prox = PROX_HUBER;
-  else e->prox = (desc->loss == ADMM_LOSS_01) ? PROX_01 : PROX_HINGE;
+  else e->prox = (desc->loss == ADMM_LOSS_01) ? PROX_01 : (desc->loss == ADMM_LOSS_LOGISTIC) ? PROX_LOGISTIC : PROX_HINGE;
   ADMM_TRY(upload_matrix(e->mem, &e->D, &e->ldD, desc->D, m, n, src_ld(desc), mk, e->stream));
   if (!svm) {
     ADMM_TRY(upload(e->mem, &e->s, desc->s, m, mk, e->stream));

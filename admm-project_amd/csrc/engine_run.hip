@@ -300,7 +300,9 @@ static int wire_objective(admm_engine* e, const admm_options& o, ProxArgs& pa, F
         fa.obj_scale_z = 0.5;
         break;
       case ADMM_PROB_LINEARSVM:
-        pa.objx = (e->loss == ADMM_LOSS_HINGE) ? OBJX_HINGE : OBJX_ZEROONE;  // linearsvm.m:231-237
+        pa.objx = (e->loss == ADMM_LOSS_HINGE)      ? OBJX_HINGE
+                  : (e->loss == ADMM_LOSS_LOGISTIC) ? OBJX_LOGISTIC
+                                                    : OBJX_ZEROONE;  // linearsvm.m:231-237
         fa.obj_scale_x = e->C;
         fa.obj_half_xnorm = 0.5;
         break;
@@ -379,6 +381,7 @@ static void fill_arg_blocks(admm_engine* e, const admm_options& o, int alg, bool
                                                                               : 1.0 / o.rho;  // getProxOps.m:455, 750 | 810, 142
       break;
     case PROX_HINGE:
+    case PROX_LOGISTIC:
       pa.t = e->C / o.rho;  // getProxOps.m:1096
       break;
     case PROX_01:

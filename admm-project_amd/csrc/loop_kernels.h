@@ -12,6 +12,7 @@ enum ProxKind : int32_t {
   PROX_01 = 3,     // ell.*minz01(ell.*v, rho/C)                       1100, 1158-1180
   PROX_BOX = 4,    // min(ub,max(lb,v))                                1470-1474
   PROX_POS = 6,    // max(v, 0)   (CVX pos)                            1378-1382, 1422-1426
+  PROX_LOGISTIC = 7,  // ell.*s, s - ell.*v = (C/rho)/(1 + e^s)  (prox_device.h: logistic_root)
   PROX_GIVEN = 5   // z was computed outside the fused kernel (a linear solve: zminModel 990-1013,
                    // or a caller-supplied zming callback) and is read from ProxArgs::zgiven
 };
@@ -36,7 +37,8 @@ enum ObjXKind : int32_t { OBJX_NONE = 0, OBJX_HINGE = 1, OBJX_ZEROONE = 2, OBJX_
                           OBJX_SOLVE = 5,
                           // bounded QP: (P + rho*I) x = y = rho*(zx-ux) - q, so 1/2*x'Px + q'x (quadraticprogram.m:242)
                           // = sum x_i*(1/2*(y_i - rho*x_i) + q_i)
-                          OBJX_SOLVE_QP = 6 };
+                          OBJX_SOLVE_QP = 6,
+                          OBJX_LOGISTIC = 7 /* sum log(1 + exp(-ell_i * (Ax)_i)) */ };
 
 // reduction slots (per-block partials, summed in block order by the finalize kernel)
 enum Slot : int32_t {
@@ -86,7 +88,7 @@ struct ProxArgs {
   double* vhist;           // fast only
   double* uhathist;        // fast only
   double* part;            // [S_COUNT][kMaxPartBlocks]
-  double rho, relax, t;    // t: soft threshold | C/rho (hinge) | rho/C (01)
+  double rho, relax, t;    // t: soft threshold | C/rho (hinge, logistic) | rho/C (01)
   double rho_solve;        // OBJX_SOLVE: the shift of the factor the x-update solved with (a stale factor under adaptive
                            // rho keeps its own: getProxOps.m:1190-1200 caches L, U once)
   int32_t prox;

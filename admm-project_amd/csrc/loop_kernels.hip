@@ -29,6 +29,7 @@ __device__ __forceinline__ void block_reduce_slots(double (&acc)[S_COUNT], doubl
   }
 }
 
+template <bool LOGI>
 __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __restrict__ ctrl) {
   // the three control words in one scalar round trip, before the branch
   const int32_t stop = ctrl->stop;
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __
        i += static_cast<int64_t>(gridDim.x) * kBlock) {
     const ProxIn in = prox_load(a, i);
     const double ax = gather_chunks(a.axsrc, a.naxpart, a.axld, i);
-    prox_apply(a, i, ax, it, kcoef, in, acc);
+    prox_apply<LOGI>(a, i, ax, it, kcoef, in, acc);
   }
   block_reduce_slots(acc, a.part);
 }
@@ -134,8 +135,8 @@ void launch_ufix(const UFixArgs& a, const Ctrl* ctrl, hipStream_t stream) {
 
 void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
   ProxArgs a = args;  // operands this variant does not read -> null (the kernel loads every non-null one up front)
-  const bool need_ell = a.prox == PROX_HINGE || a.prox == PROX_01 || a.objx == OBJX_HINGE ||
-                        a.objx == OBJX_ZEROONE || a.objx == OBJX_DOT;
+  const bool need_ell = a.prox == PROX_HINGE || a.prox == PROX_01 || a.prox == PROX_LOGISTIC || a.objx == OBJX_HINGE ||
+                        a.objx == OBJX_ZEROONE || a.objx == OBJX_LOGISTIC || a.objx == OBJX_DOT;
   if (!need_ell) a.ell = nullptr;
   if (a.prox != PROX_GIVEN) a.zgiven = nullptr;
   if (a.prox != PROX_BOX) a.lb = a.ub = nullptr;
@@ -146,7 +147,9 @@ void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStrea
   if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
   if (blocks < 1) blocks = 1;
   *nblk_out = static_cast<int>(blocks);
-  hipLaunchKernelGGL(prox_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+  if (prox_is_logistic(a))
+    hipLaunchKernelGGL(prox_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+  else hipLaunchKernelGGL(prox_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
 }
 
 // ---------------------------------------------------------------- alg 2: decide + extrapolate
@@ -335,6 +338,7 @@ __device__ __forceinline__ double tail_gather(const ProxArgs& a, int64_t i, int3
 
 // defer = 1: the finalize logic is NOT run here; the block partials are stored plainly and the next launch on the
 // stream (the x-solve of the next iteration, or a stand-alone finalize) takes them after the kernel boundary.
+template <bool LOGI>
 __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArgs f, Ctrl* __restrict__ ctrl,
                                                               int32_t defer) {
   const int32_t stop = ctrl->stop;
@@ -370,7 +374,7 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
       const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
       kcoef = (aprev - 1.0) / acn;
     }
-    prox_apply(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
+    prox_apply<LOGI>(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
   }
   // block partials of the two waves that hold elements, published write-through
   __shared__ double sred[2][S_COUNT];
@@ -419,8 +423,8 @@ FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
 void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
                      bool defer) {
   ProxArgs a = args;
-  const bool need_ell = a.prox == PROX_HINGE || a.prox == PROX_01 || a.objx == OBJX_HINGE ||
-                        a.objx == OBJX_ZEROONE || a.objx == OBJX_DOT;
+  const bool need_ell = a.prox == PROX_HINGE || a.prox == PROX_01 || a.prox == PROX_LOGISTIC || a.objx == OBJX_HINGE ||
+                        a.objx == OBJX_ZEROONE || a.objx == OBJX_LOGISTIC || a.objx == OBJX_DOT;
   if (!need_ell) a.ell = nullptr;
   if (a.prox != PROX_GIVEN) a.zgiven = nullptr;
   if (a.prox != PROX_BOX) a.lb = a.ub = nullptr;
@@ -430,8 +434,12 @@ void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nb
   const int64_t blocks = ceil_div(a.len, kTailTile);
   *nblk_out = static_cast<int>(blocks);
   const FinArgs ff = prox_fin_args(a, f);
-  hipLaunchKernelGGL(prox_fin_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, ctrl,
-                     defer ? 1 : 0);
+  if (prox_is_logistic(a))
+    hipLaunchKernelGGL(prox_fin_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, ctrl,
+                       defer ? 1 : 0);
+  else
+    hipLaunchKernelGGL(prox_fin_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, ctrl,
+                       defer ? 1 : 0);
 }
 
 void launch_finalize(const FinArgs& a, hipStream_t stream) {

@@ -17,6 +17,34 @@ __device__ __forceinline__ double huber_cvx(double x) {
   return a <= 1.0 ? x * x : 2.0 * a - 1.0;
 }
 
+// The logistic z-prox: the root s of phi(s) = (s - w) - t/(1 + e^s) in [w, w + t] (phi' in [1, 1 + t/4]).
+// The equation maps to itself under (w, s) -> (-(w + t), -s), so the root is taken >= 0; there y = s - w solves
+// y*(1 + e^s) = t, close to y*e^y = t*e^-w: the start is a closed-form Lambert W estimate from L = log t - w (no
+// overflow), then kLogisticSteps Newton steps on phi, each clamped to [max(-w, 0), t].  e^-s <= 1 throughout.
+constexpr int kLogisticSteps = 5;
+__device__ __forceinline__ double logistic_root(double w, double t) {
+  const bool mir = (w + 0.5 * t) < 0.0;
+  const double wm = mir ? -(w + t) : w;
+  const double ylo = fmax(-wm, 0.0);
+  const double L = log(fmax(t, 1e-300)) - wm;
+  const double lx = fmax(L, 0.0) + log1p(exp(-fabs(L)));  // log(1 + t*e^-w)
+  double y = lx * (1.0 - log1p(lx) / (2.0 + lx));
+  y = fmin(fmax(y, ylo), t);
+#pragma unroll 1
+  for (int k = 0; k < kLogisticSteps; ++k) {
+    const double E = exp(-(wm + y));
+    const double q = 1.0 / (1.0 + E);
+    const double tq = t * E * q;  // t/(1 + e^s)
+    y -= (y - tq) / (1.0 + tq * q);
+    y = fmin(fmax(y, ylo), t);
+  }
+  return w + (mir ? t - y : y);
+}
+
+__host__ __device__ inline bool prox_is_logistic(const ProxArgs& a) {
+  return a.prox == PROX_LOGISTIC || a.objx == OBJX_LOGISTIC;
+}
+
 struct ProxIn {  // every input of one element (see prox_load)
   double zp, u_old, uhat_i, c_i, ell_i, zg_i, lb_i, ub_i, v_i, add_i, rhs_i;
 };
@@ -56,6 +84,10 @@ __device__ __forceinline__ ProxIn prox_load(const ProxArgs& a, int64_t i) {
 // u-update, fast-ADMM extrapolation, histories, the residual / objective partial sums and the next rhs.
 // rhs_out (optional) receives c + zx - ux, the element of the next unwrapped x-update's right-hand side (RHS_T1),
 // whatever a.rhs_kind stores.
+// LOGI: the instantiation that also knows PROX_LOGISTIC / OBJX_LOGISTIC.  An fp64 exp and a Newton loop inside the
+// runtime switch cost every kernel that inlines this 30-50 VGPRs and an occupancy step whether or not the case is taken
+// (EXPERIMENTS.md), so the launchers pick the kernel instantiation by the loss and every other one compiles without it.
+template <bool LOGI = false>
 __device__ __forceinline__ void prox_apply(const ProxArgs& a, int64_t i, double ax, int64_t it, double kcoef,
                                            const ProxIn& in, double (&acc)[S_COUNT], double* rhs_out = nullptr) {
   const double zp = in.zp, u_old = in.u_old, uhat_i = in.uhat_i, c_i = in.c_i, ell_i = in.ell_i, zg_i = in.zg_i;
@@ -70,7 +102,8 @@ __device__ __forceinline__ void prox_apply(const ProxArgs& a, int64_t i, double 
   const double axh = (a.relax != 1.0) ? a.relax * ax - (1.0 - a.relax) * ((-zp) - ci) : ax;
   const double v = (axh + uo) - ci;
   double zn;
-  switch (a.prox) {
+  if (LOGI && a.prox == PROX_LOGISTIC) zn = ell_i * logistic_root(ell_i * v, a.t);
+  else switch (a.prox) {
     case PROX_SOFT:
       zn = soft(v, a.t);
       break;
@@ -113,7 +146,10 @@ __device__ __forceinline__ void prox_apply(const ProxArgs& a, int64_t i, double 
   acc[S_DU2] += du * du;
   if (a.objz == OBJZ_ABS) acc[S_OBJZ] += fabs(zn);
   else if (a.objz == OBJZ_HUBER) acc[S_OBJZ] += huber_cvx(zn);
-  if (a.objx == OBJX_HINGE) acc[S_OBJX] += fmax(1.0 - ell_i * ax, 0.0);
+  if (LOGI && a.objx == OBJX_LOGISTIC) {
+    const double q = ell_i * ax;
+    acc[S_OBJX] += fmax(-q, 0.0) + log1p(exp(-fabs(q)));  // log(1 + e^-q)
+  } else if (a.objx == OBJX_HINGE) acc[S_OBJX] += fmax(1.0 - ell_i * ax, 0.0);
   else if (a.objx == OBJX_ZEROONE) {
     const double q = 1.0 - ell_i * ax;
     acc[S_OBJX] += (q > 0.0) ? 1.0 : 0.0;  // max(sign(q),0)

@@ -63,7 +63,7 @@ struct OvrSolveArgs {
 };
 
 int ovr_pass_workgroups(int64_t m);
-void launch_ovr_pass(const OvrPassArgs& a, bool init, hipStream_t stream);
+void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, hipStream_t stream);
 void launch_ovr_gsum_fin(const OvrFinArgs& a, hipStream_t stream);
 void launch_ovr_xsolve(const OvrSolveArgs& a, int32_t K, hipStream_t stream);
 // X(:, c) = Xnew(:, c) for every class that has not stopped (the triangular-solve form of the x-update)

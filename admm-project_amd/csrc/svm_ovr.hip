@@ -28,6 +28,7 @@ static_assert(kOvMaxN == ADMM_SVM_OVR_MAX_N, "the header states the limit");
 constexpr int kOvSlotsPerWave = (kOvrChunk + kOvWaves - 1) / kOvWaves;  // classes whose element update one wave runs
 
 // the ProxArgs of one class: plain ADMM, B = -1, c = 0, no histories (the compiler folds the constant fields)
+template <bool LOGI>
 __device__ __forceinline__ ProxArgs ovr_prox_args(const OvrPassArgs& a, int cls, int32_t loss) {
   ProxArgs pa{};
   pa.len = a.m;
@@ -39,6 +40,10 @@ __device__ __forceinline__ ProxArgs ovr_prox_args(const OvrPassArgs& a, int cls,
   pa.prox = (loss == ADMM_LOSS_01) ? PROX_01 : PROX_HINGE;                   // getProxOps.m:1094
   pa.t = (loss == ADMM_LOSS_01) ? a.rho / a.C : a.C / a.rho;                 // getProxOps.m:1100 | 1096
   pa.objx = !a.objevals ? OBJX_NONE : (loss == ADMM_LOSS_HINGE ? OBJX_HINGE : OBJX_ZEROONE);  // linearsvm.m:231-237
+  if (LOGI && loss == ADMM_LOSS_LOGISTIC) {
+    pa.prox = PROX_LOGISTIC;
+    pa.objx = a.objevals ? OBJX_LOGISTIC : OBJX_NONE;
+  }
   pa.objz = OBJZ_NONE;
   pa.alg = 0;
   pa.a_identity = 0;
@@ -46,8 +51,9 @@ __device__ __forceinline__ ProxArgs ovr_prox_args(const OvrPassArgs& a, int cls,
   return pa;
 }
 
-// INIT: only the partial rows of D'(z0 - u0), before the first iteration
-template <int KC, bool INIT>
+// INIT: only the partial rows of D'(z0 - u0), before the first iteration.  LOGI: the chunk holds a logistic class (the
+// launcher knows the losses): the instantiation whose element update carries logistic_root (prox_device.h)
+template <int KC, bool INIT, bool LOGI>
 __global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a) {
   __shared__ __attribute__((aligned(16))) double xs[kOvMaxN * KC];  // [column][class]: one column's KC values contiguous
   __shared__ double gacc[KC * kOvMaxN];
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a
     for (int q = 0; q < S_COUNT; ++q) acc[s][q] = 0.0;
     const int c = w + kOvWaves * s;
     const int cls = (a.c0 + c < a.K) ? a.c0 + c : a.K - 1;
-    pas[s] = ovr_prox_args(a, cls, a.loss[cls]);
+    pas[s] = ovr_prox_args<LOGI>(a, cls, a.loss[cls]);
   }
   const int64_t nblocks = (m + kOvRows - 1) / kOvRows;
   for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
@@ -133,7 +139,7 @@ __global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a
           in.u_old = uo[s];
           in.uhat_i = uo[s];
           in.ell_i = el[s];
-          if (r < m) prox_apply(pas[s], r, ax, 0, 0.0, in, acc[s], &t);
+          if (r < m) prox_apply<LOGI>(pas[s], r, ax, 0, 0.0, in, acc[s], &t);
         }
         tsh[c * kOvRows + lane] = t;  // rows beyond m contribute nothing
       }
@@ -306,10 +312,11 @@ int ovr_pass_workgroups(int64_t m) {
   return static_cast<int>(std::min<int64_t>(ceil_div(m, int64_t{kOvRows}), kOvrMaxWg));  // one per CU
 }
 
-void launch_ovr_pass(const OvrPassArgs& a, bool init, hipStream_t stream) {
+void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, hipStream_t stream) {
   const dim3 grid(static_cast<unsigned>(ovr_pass_workgroups(a.m))), block(kOvWaves * kWave);
-  if (init) hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, true>), grid, block, 0, stream, a);
-  else hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false>), grid, block, 0, stream, a);
+  if (init) hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, true, false>), grid, block, 0, stream, a);  // (no element update)
+  else if (logistic) hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false, true>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false, false>), grid, block, 0, stream, a);
 }
 
 void launch_ovr_gsum_fin(const OvrFinArgs& a, hipStream_t stream) {
@@ -346,6 +353,7 @@ struct admm_svm_ovr {
   double *X = nullptr, *Z = nullptr, *U = nullptr, *ELL = nullptr, *gpart = nullptr, *gsum = nullptr, *part = nullptr,
          *xtmp = nullptr;
   int32_t* loss = nullptr;
+  std::vector<char> chunk_logistic;  // per chunk of kOvrChunk classes: one of them has ADMM_LOSS_LOGISTIC
   OvrRec* rec = nullptr;
   OvrRec* rec_host = nullptr;  // pinned
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -435,6 +443,9 @@ int ovr_setup(admm_svm_ovr* o, const admm_svm_ovr_desc* desc) {
   std::vector<int32_t> lh(static_cast<size_t>(K), ADMM_LOSS_HINGE);
   if (desc->loss)
     for (int32_t c = 0; c < K; ++c) lh[c] = desc->loss[c];
+  o->chunk_logistic.assign(static_cast<size_t>((K + kOvrChunk - 1) / kOvrChunk), 0);
+  for (int32_t c = 0; c < K; ++c)
+    if (lh[c] == ADMM_LOSS_LOGISTIC) o->chunk_logistic[c / kOvrChunk] = 1;
   ADMM_HIP_TRY(hipMemcpyAsync(o->loss, lh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
   ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(OvrRec) + 7) / 8));
   o->rec = reinterpret_cast<OvrRec*>(raw);
@@ -491,7 +502,8 @@ int admm_svm_ovr_create(const admm_svm_ovr_desc* desc, admm_svm_ovr** out) {
   if (!(desc->C >= 0.0)) return fail(ADMM_E_INVALID, "Given regularization parameter C is not a nonnegative number!");
   if (desc->loss)
     for (int32_t c = 0; c < desc->K; ++c)
-      if (desc->loss[c] != ADMM_LOSS_HINGE && desc->loss[c] != ADMM_LOSS_01 && desc->loss[c] != ADMM_LOSS_HINGE_OBJ01)
+      if (desc->loss[c] != ADMM_LOSS_HINGE && desc->loss[c] != ADMM_LOSS_01 && desc->loss[c] != ADMM_LOSS_HINGE_OBJ01 &&
+          desc->loss[c] != ADMM_LOSS_LOGISTIC)
         return fail(ADMM_E_INVALID, "bad loss for class " + std::to_string(c));
   if (desc->comm)
     return fail(ADMM_E_UNSUPPORTED, std::string("the one-vs-rest linear SVM is not row-sharded") + kPerClass);
@@ -595,7 +607,7 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
   auto pass = [&](bool init) {
     for (int32_t ch = 0; ch < chunks; ++ch) {
       pa.c0 = ch * kOvrChunk;
-      launch_ovr_pass(pa, init, o->stream);
+      launch_ovr_pass(pa, init, o->chunk_logistic[ch] != 0, o->stream);
     }
   };
   const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);

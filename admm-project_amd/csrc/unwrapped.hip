@@ -107,6 +107,7 @@ __global__ __launch_bounds__(kBlock) void uw_ax_kernel(UwArgs a, FinArgs f, Ctrl
         ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
+template <bool LOGI>
 __global__ __launch_bounds__(kUwProxThreads) void uw_prox_kernel(UwArgs a, ProxArgs pa, const Ctrl* __restrict__ ctrl) {
   asm volatile("" ::"s"(a.Dp), "s"(a.ldP), "s"(a.m), "s"(a.n), "s"(a.R), "s"(a.nblk), "s"(a.G), "s"(a.ldg), "s"(a.axpart),
                "s"(a.ldax), "s"(a.nchunk), "s"(a.iter), "s"(a.init), "s"(pa.z), "s"(pa.u), "s"(pa.c), "s"(pa.ell),
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(kUwProxThreads) void uw_prox_kernel(UwArgs a, ProxA
         double ax = 0.0;
 #pragma unroll
         for (int k = 0; k < 16; ++k) ax += (k < a.nchunk) ? v[k] : 0.0;
-        if (tid < nrow) prox_apply(pa, row, ax, it, kcoef, in, acc, &w);
+        if (tid < nrow) prox_apply<LOGI>(pa, row, ax, it, kcoef, in, acc, &w);
 #pragma unroll
         for (int s = 0; s < S_COUNT; ++s) accl[s][tid] += acc[s];
       } else if (tid < nrow) {
@@ -227,14 +228,18 @@ void launch_uw_ax(const UwArgs& a, const FinArgs& f, Ctrl* ctrl, hipStream_t str
 
 void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl, hipStream_t stream) {
   ProxArgs pa = pargs;
-  const bool need_ell = pa.prox == PROX_HINGE || pa.prox == PROX_01 || pa.objx == OBJX_HINGE ||
-                        pa.objx == OBJX_ZEROONE || pa.objx == OBJX_DOT;
+  const bool need_ell = pa.prox == PROX_HINGE || pa.prox == PROX_01 || pa.prox == PROX_LOGISTIC ||
+                        pa.objx == OBJX_HINGE || pa.objx == OBJX_ZEROONE || pa.objx == OBJX_LOGISTIC || pa.objx == OBJX_DOT;
   if (!need_ell) pa.ell = nullptr;
   pa.zgiven = nullptr;
   pa.lb = pa.ub = nullptr;
   pa.rhs_add = nullptr;
-  hipLaunchKernelGGL(uw_prox_kernel, dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args, pa,
-                     ctrl);
+  if (prox_is_logistic(pa))
+    hipLaunchKernelGGL(uw_prox_kernel<true>, dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args,
+                       pa, ctrl);
+  else
+    hipLaunchKernelGGL(uw_prox_kernel<false>, dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args,
+                       pa, ctrl);
 }
 
 // ---------------------------------------------------------------- ONE pass over D per iteration (tall, narrow D)
@@ -254,6 +259,7 @@ void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl,
 // that records no dual residual (unwrappedadmm.m:92 / nodualerror: no D'*(z - zprev), no D'*u) and plain ADMM.
 constexpr int kOpRows = 64, kOpWaves = 8, kOpCols = 56, kOpMaxN = kOpWaves * kOpCols;  // 448
 
+template <bool LOGI>
 __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs a, ProxArgs pa,
                                                                     const Ctrl* __restrict__ ctrl) {
   if (ctrl->stop) return;
@@ -296,7 +302,7 @@ __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs
 #pragma unroll
       for (int q = 1; q < kOpWaves; ++q) ax += axr[q][lane];
       double t = 0.0;
-      if (r < m) prox_apply(pa, r, ax, it, 0.0, in, acc, &t);
+      if (r < m) prox_apply<LOGI>(pa, r, ax, it, 0.0, in, acc, &t);
       tsh[lane] = t;  // rows beyond m contribute nothing
     }
     __syncthreads();
@@ -337,8 +343,8 @@ int onepass_workgroups(int64_t m) {
 
 void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pargs, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
   ProxArgs pa = pargs;
-  const bool need_ell = pa.prox == PROX_HINGE || pa.prox == PROX_01 || pa.objx == OBJX_HINGE || pa.objx == OBJX_ZEROONE ||
-                        pa.objx == OBJX_DOT;
+  const bool need_ell = pa.prox == PROX_HINGE || pa.prox == PROX_01 || pa.prox == PROX_LOGISTIC ||
+                        pa.objx == OBJX_HINGE || pa.objx == OBJX_ZEROONE || pa.objx == OBJX_LOGISTIC || pa.objx == OBJX_DOT;
   if (!need_ell) pa.ell = nullptr;
   if (pa.prox != PROX_GIVEN) pa.zgiven = nullptr;
   if (pa.prox != PROX_BOX) pa.lb = pa.ub = nullptr;
@@ -347,7 +353,12 @@ void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pargs, const Ctrl* 
   pa.dz = nullptr;
   const int nwg = onepass_workgroups(a.m);
   *nblk_out = nwg;
-  hipLaunchKernelGGL(ad_onepass_kernel, dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream, a, pa, ctrl);
+  if (prox_is_logistic(pa))
+    hipLaunchKernelGGL(ad_onepass_kernel<true>, dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream, a, pa,
+                       ctrl);
+  else
+    hipLaunchKernelGGL(ad_onepass_kernel<false>, dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream, a, pa,
+                       ctrl);
 }
 
 }  // namespace admm

@@ -509,9 +509,6 @@ class Engine:
         return out
 
 
-_LOSS = {"hinge": L.LOSS_HINGE, "01": L.LOSS_01}
-
-
 class SvmOvr:
     """Python owner of one ``admm_svm_ovr`` handle: the linear SVM for K one-vs-rest classes over one D."""
 
@@ -523,7 +520,7 @@ class SvmOvr:
         ELL = _f64(ELL)
         self.m, self.n = (int(v) for v in D.shape)
         self.K = int(ELL.shape[1])
-        loss = np.ascontiguousarray([_LOSS.get(v, L.LOSS_HINGE_OBJ01) for v in losses], dtype=np.int32)
+        loss = np.ascontiguousarray([L.loss_code(v) for v in losses], dtype=np.int32)
         d = L.SvmOvrDesc()
         self._lib.admm_svm_ovr_desc_default(C.byref(d))
         d.K, d.m, d.n = self.K, self.m, self.n

@@ -168,7 +168,10 @@ def unwrappedadmm(zming, D, options=None):
 
 
 def linearsvm(D, ell, C, options=None):
-    """results = linearsvm(D, ell, C, options)   (solvers/linearsvm.m:92-246)."""
+    """results = linearsvm(D, ell, C, options)   (solvers/linearsvm.m:92-246).
+
+    ``options['lossfunction']``: 'hinge' (default), '01', or 'logistic' -- C*sum(log(1 + exp(-ell.*(D*x)))), a loss the
+    reference does not have; any other string is the reference's hinge prox with the 0-1 objective."""
     if not isinstance(options, dict):
         raise TypeError("Given options is not a struct! At least pass empty struct!")
     options = dict(options)
@@ -209,7 +212,8 @@ def linearsvm_ovr(D, labels, C, options=None):
 
     ``labels``: length-m vector of class ids.  ``options['classes']`` (default: the sorted unique labels) selects and
     orders the K columns and may name a class more than once; ``options['lossfunction']`` is one string or a list with
-    one entry per column.  ``x0`` / ``z0`` / ``u0`` are n x K / m x K matrices (missing: random, unwrappedadmm.m:87-89).
+    one entry per column ('hinge', '01', 'logistic', mixed freely; see ``linearsvm``).  ``x0`` / ``z0`` / ``u0`` are
+    n x K / m x K matrices (missing: random, unwrappedadmm.m:87-89).
     The options of the plain loop apply to every class (rho, abstol, reltol, Hnormtol, domaxiters, objevals,
     check_every); maxiters is 1000, stopcond 'both', nodualerror 1 (unwrappedadmm.m:90-92).
     Returns classes, xopt (n x K), zopt, uopt (m x K), steps (K), pnorm / perr / Hnormsq / objevals (max(steps) x K,

@@ -29,6 +29,8 @@ else:
     D = ap.synth.mnist_like_problem(seed=1, m=count, n=400)["D"]
     labels = np.random.default_rng(1).integers(0, 10, size=count).astype(np.float64)
 
+# (a third loss, not in the reference: classes = np.repeat(np.arange(10.0), 3) and
+#  lossfunction = ["hinge", "01", "logistic"] * 10 add the logistic classifier of every digit, column 3d + 2)
 classes = np.repeat(np.arange(10.0), 2)  # column 2d: digit d, hinge; column 2d + 1: digit d, 0-1
 res = ap.linearsvm_ovr(D, labels, 0.5, dict(rho=1.0, classes=classes, lossfunction=["hinge", "01"] * 10,
                                             objevals=1))  # mnistsvm.m:42-43, 88-102
