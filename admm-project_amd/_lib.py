@@ -106,7 +106,7 @@ class EngineInfo(C.Structure):
         ("unwrapped_fused", C.c_int32), ("factor_n", C.c_int64), ("rank", C.c_int64),
         ("cond_estimate", C.c_double), ("probe_err_inverse", C.c_double), ("probe_err_trsv", C.c_double),
         ("probe_diff", C.c_double), ("xsolve_cacheable_bytes", C.c_int64), ("xsolve_stream_bytes", C.c_int64),
-        ("obj_bound_max", C.c_double), ("obj_form_literal", C.c_int32), ("reserved0", C.c_int32),
+        ("obj_bound_max", C.c_double), ("obj_form_literal", C.c_int32), ("ngroups", C.c_int32),
         ("probe_err_trsv_one", C.c_double),
     ]
 
@@ -174,6 +174,7 @@ _SIGNATURES = {
     "admm_engine_set_operators": (C.c_int, [C.c_void_p, OPERATOR_CALLBACK, C.c_void_p, OPERATOR_CALLBACK, C.c_void_p]),
     "admm_engine_set_constraint_b": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int32,
                                                C.c_double, OPERATOR_CALLBACK, C.c_void_p]),
+    "admm_engine_set_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, _dp]),
     "admm_engine_run": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(RunSummary)]),
     "admm_engine_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_engine_set_hooks": (C.c_int, [C.c_void_p, ALTU_CALLBACK, C.c_void_p, NORMS_CALLBACK, C.c_void_p]),
@@ -201,6 +202,7 @@ _SIGNATURES = {
     "admm_op_cholesky": (C.c_int, [_dp, C.c_int64, C.c_int64]),
     "admm_op_trsv_pair": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp]),
     "admm_op_soft_threshold": (C.c_int, [_dp, C.c_int64, C.c_double, _dp]),
+    "admm_op_group_soft_threshold": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_double, _dp]),
     "admm_comm_unique_id": (C.c_int, [C.c_char_p]),
     "admm_comm_init": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "admm_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -108,6 +108,17 @@ def getproxops(problem, args):
     cg = {k: args[k] for k in ("cg_tol", "cg_maxit") if k in args}  # xsolve='cg' (matrix-free) knobs
 
     if kind == "lasso":
+        groups = None
+        if args.get("groups") is not None:  # group lasso (engine-side extension)
+            from .errorcheck import group_sizes
+            groups = group_sizes(args["groups"], args.get("groupweights"), np.shape(_get(args, "D"))[1])
+            if args.get("parallel", 0):
+                raise L.AdmmError(L.E_UNSUPPORTED, "args.groups with args.parallel = 1: consensus lasso has no grouped "
+                                                   "z-update")
+            if comm is not None:
+                raise L.AdmmError(L.E_UNSUPPORTED, "args.groups on a row-sharded engine")
+        elif args.get("groupweights") is not None:
+            raise ValueError("args.groupweights without args.groups")
         if args.get("parallel", 0):  # getProxOps.m:383-442: consensus over row slices
             D, s, lam = _get(args, "D"), _get(args, "s"), _get(args, "lambda")
             slices = [int(k) for k in np.atleast_1d(_get(args, "slices"))]
@@ -131,6 +142,8 @@ def getproxops(problem, args):
         # args.objgram (engine-side extension): objective through the cached Gram matrix, see admm_engine.h obj_gram
         eng = Engine(L.PROB_LASSO, D=D, s=s, lam=lam, rho=rho, Lfactor=Lf, xsolve=xs, device=dev, comm=comm,
                      obj_gram=int(args.get("objgram", 0)), **cg)
+        if groups is not None:
+            eng.set_groups(*groups)
         prob = _Problem("lasso", eng, dict(A=1, c=0.0, nA=n, nB=n))
     elif kind in ("lad", "huberfit"):
         D, s = _get(args, "D"), _get(args, "s")

@@ -18,6 +18,8 @@ struct admm_binding {
   std::string problem;
   std::vector<double> dense_L;    // args.L stored sparse (lasso.m:175) expanded column by column
   std::vector<int64_t> slices;    // args.slices (getProxOps.m:387) as integers
+  std::vector<int64_t> groups;    // args.groups: the group sizes of group lasso (admm_engine_set_groups)
+  std::vector<double> groupweights;  // args.groupweights (one per group; empty: every weight 1), copied: apply runs after create
   std::vector<double> zeros;      // c = 0 for the engines that take c as a data vector
   int64_t nA = 0, nB = 0;         // lengths of x and of z
   int64_t mC = 0;                 // length of u and c; 0 = the same as nB (every problem but a generic one with a general B)
@@ -105,6 +107,34 @@ int describe(const std::string& p, const View& args, const View& handles, admm_b
     d.s = args.vec("s");
     // the serial args struct has no s (getProxOps.m:445-451): the objective's s travels in handles.s
     if (!d.s) d.s = handles.vec("s");
+    // group lasso (engine-side extension): args.groups = the sizes of the contiguous groups, args.groupweights optional.
+    // Everything that can be checked without a device is checked here, element counts included.
+    if (args.get("groups")) {
+      size_t k = 0, kw = 0;
+      const double* gs = args.vec("groups", &k);
+      if (!gs) return fail(ADMM_E_INVALID, "args.groups must be a full real vector of group sizes");
+      if (args.scalar("parallel", 0) != 0)
+        return fail(ADMM_E_UNSUPPORTED, "args.groups with args.parallel = 1: consensus lasso has no grouped z-update");
+      b.groups.resize(k);
+      double sum = 0.0;
+      for (size_t i = 0; i < k; ++i) {
+        if (!(gs[i] >= 1.0) || gs[i] != std::floor(gs[i]) || gs[i] > 9007199254740992.0)
+          return fail(ADMM_E_INVALID, "args.groups: every size must be an integer >= 1");
+        b.groups[i] = static_cast<int64_t>(gs[i]);
+        sum += gs[i];
+      }
+      if (sum != static_cast<double>(d.n)) return fail(ADMM_E_INVALID, "args.groups: the sizes must sum to the columns of D");
+      if (args.get("groupweights")) {
+        const double* gw = args.vec("groupweights", &kw);
+        if (!gw || kw != k) return fail(ADMM_E_INVALID, "args.groupweights must have one entry per group");
+        for (size_t i = 0; i < k; ++i)
+          if (!(gw[i] >= 0.0) || !std::isfinite(gw[i]))
+            return fail(ADMM_E_INVALID, "args.groupweights: every weight must be finite and >= 0");
+        b.groupweights.assign(gw, gw + k);
+      }
+    } else if (args.get("groupweights")) {
+      return fail(ADMM_E_INVALID, "args.groupweights without args.groups");
+    }
     if (args.scalar("parallel", 0) != 0) {  // getProxOps.m:383-442
       d.problem = ADMM_PROB_LASSO_CONSENSUS;
       size_t k = 0;
@@ -330,6 +360,9 @@ int admm_binding_get_info(const admm_binding* b, admm_binding_info* info) {
 // options.B other than -1 as a scalar or a matrix: forwarded to the engine the binding was made for
 int admm_binding_apply(const admm_binding* b, admm_engine* e) {
   if (!b || !e) return fail(ADMM_E_INVALID, "NULL argument");
+  if (!b->groups.empty())
+    ADMM_TRY(admm_engine_set_groups(e, b->groups.data(), static_cast<int32_t>(b->groups.size()),
+                                    b->groupweights.empty() ? nullptr : b->groupweights.data()));
   if (b->b_kind == 1 || b->b_kind == 2)
     return admm_engine_set_constraint_b(e, b->b_matrix, b->b_ld, b->b_kind == 2 ? b->nB : 0, ADMM_MEM_HOST, b->b_scalar,
                                         nullptr, nullptr);

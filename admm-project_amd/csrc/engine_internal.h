@@ -221,6 +221,10 @@ struct admm_engine {
   int32_t* cov_cnt = nullptr;  // [0]: sweeps of the small path in this run
   int64_t cov_sweeps = 0;      // Jacobi sweeps of the last run (both paths)
   int cov_sweeps_host = 0;
+  // group lasso (admm_engine_set_groups): the workgroup plan of the grouped element update, one device block
+  GroupPlan grp{};
+  double* grp_blob = nullptr;
+  int32_t ngroups = 0;        // 0: the plain l1 prox
   double* part = nullptr;     // [S_COUNT][kMaxPartBlocks]
   double* objpart = nullptr;  // [kMaxPartBlocks]
   Ctrl* ctrl = nullptr;

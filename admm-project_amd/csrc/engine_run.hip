@@ -562,6 +562,33 @@ int admm_engine_set_constraint_b(admm_engine* e, const double* B, int64_t ldB, i
   return ADMM_OK;
 }
 
+int admm_engine_set_groups(admm_engine* e, const int64_t* sizes, int32_t ngroups, const double* weights) {
+  if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
+  if (ngroups < 0) return fail(ADMM_E_INVALID, "groups: a negative group count");
+  if (e->problem != ADMM_PROB_LASSO)
+    return fail(ADMM_E_UNSUPPORTED, "groups belong to the serial lasso (ADMM_PROB_LASSO): the block soft threshold "
+                                    "replaces its l1 prox");
+  if (e->comm) return fail(ADMM_E_UNSUPPORTED, "groups are not supported on row-sharded engines");
+  GroupPlanHost h;
+  const bool on = sizes && ngroups > 0;
+  if (on) ADMM_TRY(group_plan_build(sizes, ngroups, weights, e->len, &h));  // (a refused call changes nothing)
+  ADMM_HIP_TRY(hipSetDevice(e->device));
+  if (e->grp_blob) {
+    ADMM_HIP_TRY(hipStreamSynchronize(e->stream));
+    e->mem.free_one(e->grp_blob);
+    e->grp_blob = nullptr;
+  }
+  e->ngroups = 0;
+  e->grp = GroupPlan{};
+  if (!on) return ADMM_OK;
+  ADMM_TRY(e->mem.alloc(&e->grp_blob, h.blob.size()));
+  ADMM_HIP_TRY(hipMemcpyAsync(e->grp_blob, h.blob.data(), sizeof(double) * h.blob.size(), hipMemcpyHostToDevice, e->stream));
+  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (h is read until here)
+  e->grp = h.bind(e->grp_blob);
+  e->ngroups = ngroups;
+  return ADMM_OK;
+}
+
 int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* summary) {
   RunState rs{};
   admm_options& o = rs.o;

@@ -151,6 +151,7 @@ struct GeneralLoop {
   bool alt_qp = false, alt_ok = false;
   double alt_const = 0.0;
   bool gram_guard = false, split_symv = false;
+  bool grouped = false;  // group lasso: the grouped element update wherever the lasso's own runs (a zming callback wins)
 
   // ---- may change at a batch boundary (after_batch: nothing is pending there, so the launch sequence may change)
   bool gram_now = false, gram_calibrating = false, obj_kernels = false;
@@ -186,6 +187,7 @@ struct GeneralLoop {
     nrhs_dual = o.nodualerror ? 1 : 3;
     sharded = e->comm && comm_nranks(e->comm) > 1;
     hooks = e->altucb != nullptr || e->normscb != nullptr;
+    grouped = e->ngroups > 0 && !split_z;
     if (hooks && alg != 0)
       return fail(ADMM_E_UNSUPPORTED, "caller-supplied options.altu / options.specialnorms with fast ADMM: not supported "
                                       "(admm.m:614 overwrites fast ADMM's v with the norms: q5)");
@@ -485,21 +487,32 @@ struct GeneralLoop {
     pa.axld = ax.ld;
     pa.x_out = e->a_identity ? e->x : nullptr;
     if (defer_fin) {  // the element update alone; the finalize rides along with the next x-solve
-      launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, true);
-      dff = prox_fin_args(pa, fa);
+      launch_tail(nblk, true);
+      dff = tail_fin_args(*nblk);
       e->dfin = &dff;
       e->dfin_pending = true;
       *done = true;
     } else if (fuse_tail && defer_fin_ad) {  // A = D without a dual residual: the finalize rides along with the partial
-      launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, true);  // sums of the next right-hand side (iterate_general)
-      dff = prox_fin_args(pa, fa);
+      launch_tail(nblk, true);  // sums of the next right-hand side (iterate_general)
+      dff = tail_fin_args(*nblk);
     } else if (fuse_tail) {  // z/u update + finalize in one launch
-      launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream);
+      launch_tail(nblk, false);
       *done = e->a_identity;  // the iteration ends here
     } else {
       ADMM_TRY(element_update_plain(ax, nblk));
     }
     return ADMM_OK;
+  }
+
+  // the one-launch tail: the lasso's, or the grouped one of group lasso (its block partials: one per workgroup of the plan)
+  void launch_tail(int* nblk, bool defer) {
+    if (grouped) launch_group_prox_fin(pa, fa, e->grp, e->ctrl, nblk, e->stream, defer);
+    else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer);
+  }
+  FinArgs tail_fin_args(int nblk) {
+    FinArgs d = prox_fin_args(pa, fa);
+    if (grouped) d.nblk = nblk;
+    return d;
   }
 
   // the element update on its own, with the caller's options.altu / options.specialnorms around it
@@ -508,7 +521,8 @@ struct GeneralLoop {
       ADMM_HIP_TRY(hipMemcpyAsync(e->hk_uold, e->u, sizeof(double) * len, hipMemcpyDeviceToDevice, e->stream));
       if (!split_z) launch_prez_for(ax, e->u, nullptr, nullptr);
     }
-    launch_prox(pa, e->ctrl, nblk, e->stream);
+    if (grouped) launch_tail(nblk, true);  // (deferred = the block partials stored plainly: launch_finalize follows)
+    else launch_prox(pa, e->ctrl, nblk, e->stream);
     if (e->altucb) {
       launch_negate(e->z, e->hk_bz, len, e->ctrl, e->stream);
       if (e->altucb(e->altuuser, e->hk_uold, e->xh, e->hk_bz, e->c ? e->c : e->hk_zero, len, e->hk_unew,

@@ -1,5 +1,7 @@
 // loop_kernels.h -- argument blocks of the per-iteration fused kernels (loop_kernels.hip).
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 namespace admm {
@@ -200,6 +202,42 @@ void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t
 // a.len <= 128 * kMaxPartBlocks
 void launch_prox_fin(const ProxArgs& a, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
                      bool defer = false);
+// ---- group lasso: z_g = v_g * (||v_g|| > t_g ? 1 - t_g/||v_g|| : 0), t_g = t * w_g, over a partition of
+// the elements into G contiguous groups.  The norm of a group is needed before any of its elements can be written, so
+// the element update is planned by groups: whole groups are packed into a workgroup up to `budget` elements (and
+// kGroupMaxPerWg groups); a group larger than the budget has a workgroup of its own, which walks it twice (norm, apply).
+// The budget starts at one 128-element tile and doubles until the plan fits kMaxPartBlocks workgroups.  One group of n
+// elements is therefore ONE workgroup walking n elements twice: correct, and as slow as that sounds.
+constexpr int kGroupTile = 128;        // elements of one chunk of a workgroup's range (= the tile of the one-launch tail)
+constexpr int kGroupMaxPerWg = 1024;   // groups of one workgroup: their sums of squares / scales live in LDS
+struct GroupPlan {      // device arrays (GroupPlanHost::bind)
+  const int64_t* off;   // [G + 1] first element of each group
+  const double* w;      // [G] weights, or null: every weight is 1
+  const int32_t* gid;   // [n] group of each element
+  const int64_t* wg_e;  // [nwg + 1] first element of each workgroup
+  const int32_t* wg_g;  // [nwg + 1] first group of each workgroup
+  int32_t nwg, G;
+  int64_t n, budget;
+};
+struct GroupPlanHost {  // the plan as one block of 8-byte words, ready for a single upload
+  std::vector<double> blob;
+  size_t o_off = 0, o_w = 0, o_gid = 0, o_wge = 0, o_wgg = 0;
+  bool has_w = false;
+  int32_t nwg = 0, G = 0;
+  int64_t n = 0, budget = 0;
+  GroupPlan bind(const double* dev) const;  // the arrays inside a device copy of blob
+};
+// checks sizes (each >= 1, sum == n: ADMM_E_INVALID) and weights (finite, >= 0, or null) and builds the plan;
+// ADMM_E_UNSUPPORTED when even one workgroup per kGroupMaxPerWg groups needs more than kMaxPartBlocks workgroups
+int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int64_t n, GroupPlanHost* out);
+// The grouped element update: everything launch_prox_fin does (gather of the x-solve's partial rows, relaxation, z, u,
+// extrapolation, histories, next right-hand side, block partials, finalize in the launch or deferred) with the block
+// soft threshold as the z-prox and lambda * sum_g w_g*||z_g|| in S_OBJZ (when a.objz asks for the l1 term).  defer also
+// serves the iterations that end in a stand-alone finalize (launch_prox's place).  a.t = lambda / rho.
+void launch_group_prox_fin(const ProxArgs& a, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
+                           hipStream_t stream, bool defer);
+// out = block soft threshold of v (device pointers), the same device code over the same plan
+void launch_group_soft_threshold(const double* v, const GroupPlan& gp, double t, double* out, hipStream_t stream);
 // the finalize arguments launch_prox_fin hands to the last workgroup (or, deferred, to the next launch)
 FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f);
 void launch_fast_decide(const FinArgs& a, hipStream_t stream);   // alg 2: d, restart decision, alpha

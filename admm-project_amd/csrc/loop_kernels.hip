@@ -11,6 +11,7 @@
 #include "loop_kernels.h"
 #include "finalize_device.h"
 #include "prox_device.h"
+#include "group_device.h"
 
 namespace admm {
 
@@ -440,6 +441,248 @@ void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nb
   else
     hipLaunchKernelGGL(prox_fin_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, ctrl,
                        defer ? 1 : 0);
+}
+
+// ---------------------------------------------------------------- group lasso: the grouped one-launch tail
+// prox_fin_kernel with the block soft threshold (group_device.h) as the z-prox.  Workgroup w owns the whole groups
+// wg_g[w] .. wg_g[w + 1] = the elements wg_e[w] .. wg_e[w + 1] (loop_kernels.h: GroupPlan) and walks them in chunks of
+// 128 elements x 4 slots, twice: the first pass sums the x-solve's partial rows, forms v and the groups' norms; the second
+// applies the scale and runs the fused element update with the finished z in ProxIn::zg_i (PROX_GIVEN from a register).
+// With one chunk -- every workgroup of a plan at the starting budget whose groups fit one tile -- the second pass
+// reuses the registers of the first; longer ranges gather again (the same loads in the same order: the same bits).
+// Element i sums its partial rows exactly as prox_fin_kernel does (split into four quarters of its own tile's count).
+__device__ __forceinline__ double group_ax(const ProxArgs& a, int64_t ic, int slot, int e,
+                                           double (*quarter)[kTailTile]) {
+  const int32_t d = static_cast<int32_t>(ic / kTailTile);
+  const int32_t P = a.ax_tri ? a.naxpart - d : (a.ax_t ? a.naxpart + 1 : a.naxpart);
+  const int32_t q = (P + kTailSlots - 1) / kTailSlots;
+  const int32_t p0 = slot * q, p1 = (p0 + q < P) ? p0 + q : P;
+  const double ax = p0 < P ? tail_gather(a, ic, p0, p1) : 0.0;
+  __syncthreads();  // (the previous chunk's quarters have been read)
+  if (slot > 0) quarter[slot - 1][e] = ax;
+  __syncthreads();
+  return ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e];  // (meaningful in slot 0)
+}
+
+__global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, FinArgs f, GroupPlan gp,
+                                                                    Ctrl* __restrict__ ctrl, int32_t defer,
+                                                                    int32_t want_objz) {
+  const int32_t stop = ctrl->stop;
+  const int64_t it = ctrl->iter;
+  const double aprev = ctrl->acurr;
+  const int64_t E0 = gp.wg_e[blockIdx.x], E1 = gp.wg_e[blockIdx.x + 1];
+  const int32_t g0 = gp.wg_g[blockIdx.x], ng = gp.wg_g[blockIdx.x + 1] - g0;
+  if (stop) return;  // (uniform; the plan words above arrive in the same round trip as the control words)
+  __shared__ double quarter[kTailSlots - 1][kTailTile];
+  __shared__ double sq[kGroupTile];
+  __shared__ double gacc[kGroupMaxPerWg];
+  __shared__ int32_t last;
+  static_assert(kGroupTile == kTailTile, "one chunk of a group plan is one tile of the one-launch tail");
+  const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
+  const int32_t nch = static_cast<int32_t>((E1 - E0 + kTailTile - 1) / kTailTile);
+  double acc[S_COUNT];
+#pragma unroll
+  for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
+  ProxIn in{};
+  double ax = 0.0;
+  int32_t gi = 0;
+  int64_t i = E0 + e;
+  for (int32_t c = 0; c < nch; ++c) {  // ---- pass 1: v and the norms of the groups
+    const int64_t cs = E0 + static_cast<int64_t>(c) * kTailTile, ce = (cs + kTailTile < E1) ? cs + kTailTile : E1;
+    i = cs + e;
+    const int64_t ic = i < E1 ? i : E1 - 1;
+    if (slot == 0) {
+      in = prox_load(a, ic);  // in flight together with the partial rows
+      gi = gp.gid[ic] - g0;
+    }
+    ax = group_ax(a, ic, slot, e, quarter);
+    if (slot == 0) {
+      const double v = group_prox_v(a, ax, in);
+      sq[e] = i < E1 ? v * v : 0.0;
+    }
+    __syncthreads();
+    const double oz = group_chunk(gp, g0, ng, cs, ce, a.t, sq, gacc);
+    if (want_objz) acc[S_OBJZ] += oz;
+    __syncthreads();
+  }
+  double kcoef = 0.0;
+  if (a.alg == 1) {
+    const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
+    kcoef = (aprev - 1.0) / acn;
+  }
+  for (int32_t c = 0; c < nch; ++c) {  // ---- pass 2: z = scale_g * v and the rest of the element update
+    if (nch > 1) {
+      i = E0 + static_cast<int64_t>(c) * kTailTile + e;
+      const int64_t ic = i < E1 ? i : E1 - 1;
+      if (slot == 0) {
+        in = prox_load(a, ic);
+        gi = gp.gid[ic] - g0;
+      }
+      ax = group_ax(a, ic, slot, e, quarter);
+    }
+    if (slot == 0 && i < E1) {
+      in.zg_i = group_prox_v(a, ax, in) * gacc[gi];
+      prox_apply<false>(a, i, ax, it, kcoef, in, acc);
+    }
+  }
+  // block partials of the two waves that hold elements and group sums; from here on as prox_fin_kernel
+  __shared__ double sred[2][S_COUNT];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (wid < 2) {
+#pragma unroll
+    for (int s = 0; s < S_COUNT; ++s) {
+      const double w = wave_sum(acc[s]);
+      if (lane == 0) sred[wid][s] = w;
+    }
+  }
+  __syncthreads();
+  if (defer) {
+    if (threadIdx.x < S_COUNT) a.part[threadIdx.x * kMaxPartBlocks + blockIdx.x] = sred[0][threadIdx.x] + sred[1][threadIdx.x];
+    return;
+  }
+  if (threadIdx.x < S_COUNT) {
+    const int s = threadIdx.x;
+    __hip_atomic_store(a.part + s * kMaxPartBlocks + blockIdx.x, sred[0][s] + sred[1][s], __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains: the element stores as well
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int32_t old = __hip_atomic_fetch_add(&ctrl->arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = (old == static_cast<int32_t>(gridDim.x) - 1) ? 1 : 0;
+    if (last) __hip_atomic_store(&ctrl->arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (!last || threadIdx.x >= kBlock) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  finalize_body<true>(f);
+}
+
+void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
+                           hipStream_t stream, bool defer) {
+  ProxArgs a = args;  // (a lasso engine: no ell, no bounds)
+  a.ell = nullptr;
+  a.lb = a.ub = nullptr;
+  a.zgiven = nullptr;  // z reaches prox_apply in a register
+  a.prox = PROX_GIVEN;
+  const int32_t want_objz = a.objz == OBJZ_ABS ? 1 : 0;  // the kernel adds the penalty once per group instead
+  a.objz = OBJZ_NONE;
+  const bool need_add = (a.alg != 2 && a.rhs && (a.rhs_kind == RHS_RHO_DTS || a.rhs_kind == RHS_RHO_MINUS_Q)) ||
+                        a.objx == OBJX_SOLVE || a.objx == OBJX_SOLVE_QP;
+  if (!need_add) a.rhs_add = nullptr;
+  *nblk_out = gp.nwg;
+  FinArgs ff = prox_fin_args(a, f);
+  ff.nblk = gp.nwg;
+  hipLaunchKernelGGL(group_prox_fin_kernel, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a, ff, gp,
+                     ctrl, defer ? 1 : 0, want_objz);
+}
+
+// out = v .* scale of its group: the stand-alone operator (ops.hip), one thread per element of a chunk
+__global__ __launch_bounds__(kGroupTile) void group_soft_threshold_kernel(const double* __restrict__ v, GroupPlan gp,
+                                                                          double t, double* __restrict__ out) {
+  __shared__ double sq[kGroupTile];
+  __shared__ double gacc[kGroupMaxPerWg];
+  const int64_t E0 = gp.wg_e[blockIdx.x], E1 = gp.wg_e[blockIdx.x + 1];
+  const int32_t g0 = gp.wg_g[blockIdx.x], ng = gp.wg_g[blockIdx.x + 1] - g0;
+  const int32_t nch = static_cast<int32_t>((E1 - E0 + kGroupTile - 1) / kGroupTile);
+  for (int32_t c = 0; c < nch; ++c) {
+    const int64_t cs = E0 + static_cast<int64_t>(c) * kGroupTile, ce = (cs + kGroupTile < E1) ? cs + kGroupTile : E1;
+    const int64_t i = cs + threadIdx.x;
+    const double vi = i < E1 ? v[i] : 0.0;
+    sq[threadIdx.x] = vi * vi;
+    __syncthreads();
+    (void)group_chunk(gp, g0, ng, cs, ce, t, sq, gacc);
+    __syncthreads();
+  }
+  for (int64_t i = E0 + threadIdx.x; i < E1; i += kGroupTile) out[i] = v[i] * gacc[gp.gid[i] - g0];
+}
+
+void launch_group_soft_threshold(const double* v, const GroupPlan& gp, double t, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(group_soft_threshold_kernel, dim3(static_cast<unsigned>(gp.nwg)), dim3(kGroupTile), 0, stream, v, gp,
+                     t, out);
+}
+
+GroupPlan GroupPlanHost::bind(const double* dev) const {
+  GroupPlan p{};
+  p.off = reinterpret_cast<const int64_t*>(dev + o_off);
+  p.w = has_w ? dev + o_w : nullptr;
+  p.gid = reinterpret_cast<const int32_t*>(dev + o_gid);
+  p.wg_e = reinterpret_cast<const int64_t*>(dev + o_wge);
+  p.wg_g = reinterpret_cast<const int32_t*>(dev + o_wgg);
+  p.nwg = nwg;
+  p.G = G;
+  p.n = n;
+  p.budget = budget;
+  return p;
+}
+
+int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int64_t n, GroupPlanHost* out) {
+  if (!sizes || G < 1 || n < 1 || !out) return fail(ADMM_E_INVALID, "groups: sizes, their count and n must be given");
+  int64_t sum = 0;
+  for (int32_t g = 0; g < G; ++g) {
+    if (sizes[g] < 1) return fail(ADMM_E_INVALID, "groups: group " + std::to_string(g) + " has a size below 1");
+    if (sizes[g] > n - sum) return fail(ADMM_E_INVALID, "groups: the sizes sum to more than n = " + std::to_string(n));
+    sum += sizes[g];
+  }
+  if (sum != n)
+    return fail(ADMM_E_INVALID, "groups: the sizes sum to " + std::to_string(sum) + ", not to n = " + std::to_string(n));
+  if (weights)
+    for (int32_t g = 0; g < G; ++g)
+      if (!(weights[g] >= 0.0) || !(weights[g] <= 1.79769313486231570e308))
+        return fail(ADMM_E_INVALID, "groups: weight " + std::to_string(g) + " is negative or not finite");
+  // whole groups per workgroup, up to `budget` elements and kGroupMaxPerWg groups; a group past the budget stands alone
+  std::vector<int64_t> wge;
+  std::vector<int32_t> wgg;
+  int64_t budget = kGroupTile;
+  for (;;) {
+    wge.assign(1, 0);
+    wgg.assign(1, 0);
+    int64_t cur_e = 0, at = 0;
+    int32_t cur_g = 0;
+    for (int32_t g = 0; g < G; ++g) {
+      if (cur_g > 0 && (cur_e + sizes[g] > budget || cur_g == kGroupMaxPerWg)) {
+        wge.push_back(at);
+        wgg.push_back(g);
+        cur_e = 0;
+        cur_g = 0;
+      }
+      cur_e += sizes[g];
+      cur_g += 1;
+      at += sizes[g];
+    }
+    wge.push_back(n);
+    wgg.push_back(G);
+    if (static_cast<int64_t>(wge.size()) - 1 <= kMaxPartBlocks) break;
+    if (budget >= n)
+      return fail(ADMM_E_UNSUPPORTED, "groups: more than " + std::to_string(int64_t{kMaxPartBlocks} * kGroupMaxPerWg) +
+                                          " groups are not supported");
+    budget *= 2;
+  }
+  GroupPlanHost& h = *out;
+  h = GroupPlanHost{};
+  h.nwg = static_cast<int32_t>(wge.size()) - 1;
+  h.G = G;
+  h.n = n;
+  h.budget = budget;
+  h.has_w = weights != nullptr;
+  const size_t nG = static_cast<size_t>(G), nW = static_cast<size_t>(h.nwg) + 1;
+  h.o_off = 0;
+  h.o_w = h.o_off + nG + 1;
+  h.o_wge = h.o_w + nG;
+  h.o_gid = h.o_wge + nW;
+  h.o_wgg = h.o_gid + (static_cast<size_t>(n) + 1) / 2;
+  h.blob.assign(h.o_wgg + (nW + 1) / 2, 0.0);
+  int64_t* off = reinterpret_cast<int64_t*>(h.blob.data() + h.o_off);
+  int32_t* gid = reinterpret_cast<int32_t*>(h.blob.data() + h.o_gid);
+  off[0] = 0;
+  for (int32_t g = 0; g < G; ++g) {
+    off[g + 1] = off[g] + sizes[g];
+    for (int64_t i = off[g]; i < off[g + 1]; ++i) gid[i] = g;
+    if (weights) h.blob[h.o_w + g] = weights[g];
+  }
+  std::memcpy(h.blob.data() + h.o_wge, wge.data(), nW * sizeof(int64_t));
+  std::memcpy(h.blob.data() + h.o_wgg, wgg.data(), nW * sizeof(int32_t));
+  return ADMM_OK;
 }
 
 void launch_finalize(const FinArgs& a, hipStream_t stream) {

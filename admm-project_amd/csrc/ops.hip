@@ -175,4 +175,24 @@ int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out) {
   return ADMM_OK;
 }
 
+int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups, const double* weights,
+                                 double lambda_over_rho, double* out) {
+  if (!v || !out || n <= 0 || !(lambda_over_rho >= 0.0))
+    return fail(ADMM_E_INVALID, "group_soft_threshold: bad argument");
+  GroupPlanHost h;
+  ADMM_TRY(group_plan_build(sizes, ngroups, weights, n, &h));
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dv, *dout, *dplan;
+  ADMM_TRY(sc.alloc(&dv, n));
+  ADMM_TRY(sc.alloc(&dout, n));
+  ADMM_TRY(sc.alloc(&dplan, h.blob.size()));
+  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
+  ADMM_HIP_TRY(hipMemcpy(dplan, h.blob.data(), sizeof(double) * h.blob.size(), hipMemcpyHostToDevice));
+  launch_group_soft_threshold(dv, h.bind(dplan), lambda_over_rho, dout, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
 }  // extern "C"

@@ -399,6 +399,19 @@ class Engine:
                                                            0.0, none, None))
             self.nB = int(Bm.shape[1])
 
+    def set_groups(self, sizes=None, weights=None):
+        """Group lasso (admm_engine_set_groups): the z-prox of a lasso engine becomes the block soft threshold over
+        contiguous groups of the given sizes (weights: one per group, default 1).  ``None`` restores the l1 prox."""
+        if sizes is None:
+            L.check(self._lib.admm_engine_set_groups(self._h, None, 0, None))
+            return
+        g = np.ascontiguousarray(np.asarray(sizes, dtype=np.int64).reshape(-1))
+        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w is not None and w.size != g.size:
+            raise ValueError(f"weights has {w.size} entries for {g.size} groups")
+        L.check(self._lib.admm_engine_set_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_int64)), g.size,
+                                                 None if w is None else L.as_dp(w)))
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None):
@@ -431,7 +444,7 @@ class Engine:
                     factor_n=i.factor_n, rank=i.rank, cond_estimate=i.cond_estimate,
                     probe_err_inverse=i.probe_err_inverse, probe_err_trsv=i.probe_err_trsv, probe_err_trsv_one=i.probe_err_trsv_one, probe_diff=i.probe_diff,
                     xsolve_cacheable_bytes=i.xsolve_cacheable_bytes, xsolve_stream_bytes=i.xsolve_stream_bytes,
-                    obj_bound_max=i.obj_bound_max, obj_form_literal=bool(i.obj_form_literal))
+                    obj_bound_max=i.obj_bound_max, obj_form_literal=bool(i.obj_form_literal), ngroups=i.ngroups)
 
     def set_profiling(self, on, stride=1):
         """True/False, or an iterable of kernel classes (L.K_XSOLVE, ...) to time with HIP events; stride > 1 times

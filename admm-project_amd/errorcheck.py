@@ -63,3 +63,25 @@ def is_positive_real(v, name):
     if not np.isscalar(v) or not np.isreal(v) or v <= 0:
         raise ValueError(f"Argument {name} is not a positive real number!")
     return float(v)
+
+
+def group_sizes(groups, weights, n):
+    """args.groups / args.groupweights of group lasso: sizes as int64 (each an integer >= 1, summing to n) and the
+    weights as float64 (one finite value >= 0 per group) or None.  Raises before any device work."""
+    g = np.asarray(groups, dtype=np.float64).reshape(-1)
+    if g.size == 0:
+        raise ValueError("groups must hold at least one group size")
+    if not np.all(np.isfinite(g)) or np.any(g != np.floor(g)):
+        raise ValueError("groups: every size must be an integer")
+    if np.any(g < 1):
+        raise ValueError("groups: every size must be >= 1")
+    if int(g.sum()) != int(n):
+        raise ValueError(f"groups: the sizes sum to {int(g.sum())}, not to the {int(n)} columns of D")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w.size != g.size:
+            raise ValueError(f"groupweights has {w.size} entries for {g.size} groups")
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("groupweights: every weight must be finite and >= 0")
+    return np.ascontiguousarray(g.astype(np.int64)), w

@@ -13,9 +13,9 @@ import time
 import numpy as np
 
 from .api import admm, getproxops
-from .errorcheck import is_nonnegative_real, is_positive_real, slicemaker
+from .errorcheck import group_sizes, is_nonnegative_real, is_positive_real, slicemaker
 
-__all__ = ["lasso", "lad", "huberfit", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "grouplasso", "lad", "huberfit", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -80,6 +80,39 @@ def lasso(D, s, lam, options=None):
         minx, minz, _ = getproxops("LASSO", args)
     options["obj"] = _ENGINE_OBJ  # lasso.m:227  0.5*sum((D*x - s).^2) + lambda*norm(z,1)
     options.update(A=1, At=1, m=n, nA=n, nB=n, B=-1, c=0, parallel="none")  # lasso.m:232-239
+    results = admm(minx, minz, options)
+    results["solverruntime"] = time.perf_counter() - t0
+    return results
+
+
+def grouplasso(D, s, lam, groups, options=None):
+    """results = grouplasso(D, s, lambda, groups, options): an engine-side extension in the shape of lasso().
+
+    minimise 1/2*||D*x - s||_2^2 + lambda*sum_g w_g*||x_g||_2 over contiguous groups of coefficients: ``groups`` holds
+    their sizes (integers >= 1 that sum to the columns of D), ``options['groupweights']`` the optional w_g >= 0
+    (default 1; sqrt(p_g) is the caller's choice).  The x-update and every option are the lasso's; the z-update is the
+    block soft threshold z_g = v_g*max(0, 1 - (lambda*w_g/rho)/||v_g||) on the device (Boyd et al. 6.4.2)."""
+    if not isinstance(options, dict):
+        raise TypeError("Given options is not a struct! At least pass empty struct!")
+    options = dict(options)
+    t0 = time.perf_counter()
+    lam = is_nonnegative_real(lam, "lambda")
+    D = _matrix(D, "D")
+    s = _colvec(s, "s")
+    rho = is_positive_real(options["rho"], "options.rho") if "rho" in options else 1.0
+    m, n = D.shape
+    if s.size != m:
+        raise ValueError("The number of rows in argument D do not match size of s!")
+    sizes, weights = group_sizes(groups, options.pop("groupweights", None), n)
+    if options.get("parallel", "none") in ("both", "zming", "xminf") or "comm" in options:
+        raise ValueError("grouplasso has no consensus or row-sharded form: options.parallel / options.comm")
+    args = _engine_args(options, dict(D=D, s=s, m=m, n=n, parallel=0, rho=rho, groups=sizes))
+    if weights is not None:
+        args["groupweights"] = weights
+    args["lambda"] = lam
+    minx, minz, _ = getproxops("LASSO", args)
+    options["obj"] = _ENGINE_OBJ  # 0.5*sum((D*x - s).^2) + lambda*sum_g w_g*norm(z_g)
+    options.update(A=1, At=1, m=n, nA=n, nB=n, B=-1, c=0, parallel="none")
     results = admm(minx, minz, options)
     results["solverruntime"] = time.perf_counter() - t0
     return results

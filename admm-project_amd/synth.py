@@ -117,6 +117,25 @@ def lasso_problem(seed=0, rows=2 ** 8, cols=2 ** 6, threads=None, row_range=None
     return dict(D=D, s=s, lam=lam, testx=testx)
 
 
+def grouplasso_problem(seed=0, rows=2 ** 8, cols=2 ** 6, ngroups=8, active=2):
+    """lassotest's recipe with a group-sparse truth: ``ngroups`` contiguous groups of random sizes >= 1, ``active`` of them
+    filled with randn and every other one exactly zero; s = D*testx + sqrt(0.001)*randn; unit weights;
+    lambda = 0.1*max_g ||D_g's||_2, a tenth of the smallest lambda whose solution is x = 0."""
+    rng = np.random.default_rng(seed)
+    cuts = np.sort(rng.choice(np.arange(1, cols), size=ngroups - 1, replace=False))
+    sizes = np.diff(np.concatenate([[0], cuts, [cols]])).astype(np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    testx = np.zeros(cols)
+    for g in rng.choice(ngroups, size=active, replace=False):
+        testx[offs[g]:offs[g + 1]] = rng.standard_normal(int(sizes[g]))
+    D = _randn_cols(seed + 7919, rows, cols)
+    D /= np.sqrt(np.einsum("ij,ij->j", D, D))
+    s = D @ testx + np.sqrt(0.001) * rng.standard_normal(rows)
+    g = D.T @ s
+    lam = 0.1 * max(float(np.linalg.norm(g[offs[k]:offs[k + 1]])) for k in range(ngroups))
+    return dict(D=D, s=s, lam=lam, testx=testx, groups=sizes)
+
+
 def lad_problem(seed=0, rows=2 ** 10, cols=2 ** 7):
     """testers/ladtest.m:116-123: s = D*xtrue with 2 % of rows hit by 100*randn outliers."""
     rng = np.random.default_rng(seed)

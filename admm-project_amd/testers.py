@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "ladtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
+__all__ = ["lassotest", "grouplassotest", "ladtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -31,6 +31,23 @@ def lassotest(seed=0, rows=2 ** 8, cols=2 ** 6, errtol=1e-3, quiet=1, options=No
     xopt = results["xopt"]
     testobj, objopt = obj(testx, testx), obj(xopt, xopt)
     test = dict(D=D, s=s, testx=testx, testobj=testobj, xopt=xopt, admmopt=results["objopt"], objopt=objopt,
+                failed=int(not objopt < testobj), objerror=abs((testobj - objopt) / objopt), steps=results["steps"])
+    test["lambda"] = lam
+    return results, test
+
+
+def grouplassotest(seed=0, rows=2 ** 8, cols=2 ** 6, errtol=1e-3, quiet=1, options=None):
+    """lassotest's shape for grouplasso, on synth.grouplasso_problem (a group-sparse truth): pass when
+    obj(xopt) < obj(testx) with obj = 1/2*||D*x - s||^2 + lambda*sum_g ||x_g||_2."""
+    p = synth.grouplasso_problem(seed, rows, cols)
+    D, s, lam, testx, sizes = p["D"], p["s"], p["lam"], p["testx"], p["groups"]
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    pen = lambda z: sum(float(np.linalg.norm(z[a:b])) for a, b in zip(offs[:-1], offs[1:]))
+    obj = lambda x, z: 0.5 * np.sum((D @ x - s) ** 2) + lam * pen(z)
+    results = solvers.grouplasso(D, s, lam, sizes, _opts(options, objevals=1, quiet=quiet))
+    xopt = results["xopt"]
+    testobj, objopt = obj(testx, testx), obj(xopt, xopt)
+    test = dict(D=D, s=s, testx=testx, groups=sizes, testobj=testobj, xopt=xopt, admmopt=results["objopt"], objopt=objopt,
                 failed=int(not objopt < testobj), objerror=abs((testobj - objopt) / objopt), steps=results["steps"])
     test["lambda"] = lam
     return results, test

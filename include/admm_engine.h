@@ -315,6 +315,15 @@ int admm_engine_set_hooks(admm_engine* eng, admm_altu_callback altu, void* altu_
  * device loop carries w = -B*z and runs the same fused kernels. */
 int admm_engine_set_constraint_b(admm_engine* eng, const double* B, int64_t ldB, int64_t nB, int32_t memkind,
                                  double scalar, admm_operator_callback Bop, void* Buser);
+/* Group lasso (engine-side extension, no reference counterpart: DESIGN.md q30): the z-prox of an ADMM_PROB_LASSO
+ * engine becomes the block soft threshold of lambda * sum_g weights[g] * ||z_g||_2 over ngroups contiguous groups of
+ * the n coefficients (sizes[g] >= 1, sum == n; weights >= 0, NULL = 1 for every group), and objevals reports
+ * 1/2*||D*x - s||^2 + lambda * sum_g weights[g] * ||z_g||.  The x-update, every option and every x-solve form stay the
+ * lasso's; a zming callback still replaces the z-update.  sizes == NULL or ngroups == 0 restores the l1 prox.
+ * ADMM_E_INVALID: a size below 1, sizes that do not sum to n, a negative or non-finite weight; ADMM_E_UNSUPPORTED: any
+ * other problem (consensus lasso included), a row-sharded engine.  One group of n elements is one workgroup walking
+ * all of them twice per iteration: correct, slow. */
+int admm_engine_set_groups(admm_engine* eng, const int64_t* sizes, int32_t ngroups, const double* weights);
 int admm_engine_run(admm_engine* eng, const admm_options* opts, admm_run_summary* summary);
 int admm_engine_fetch(admm_engine* eng, int field, double* dst, size_t cap, size_t* written);
 /* what create() decided about the x-update factor (first slice for consensus lasso) */
@@ -343,7 +352,7 @@ typedef struct admm_engine_info_t {
    * 1e-10 the engine has gone back to the literal form (obj_form_literal = 1) */
   double obj_bound_max;
   int32_t obj_form_literal;
-  int32_t reserved0;
+  int32_t ngroups;           /* groups of admm_engine_set_groups in force (0: the plain l1 prox); the former reserved0 */
   /* ABI 5: the triangular solves' one-block form (the whole factor pre-inverted: two passes, two launches per pair;
    * trsv_blocks = 1 when it is in use): its forward error on the probe system next to probe_err_trsv, which is the
    * blocked substitution's (the yardstick); NaN where it was not built (n < 1536, or the explicit inverse runs) */
@@ -406,7 +415,10 @@ typedef struct admm_binding_info {
   int64_t b_ld;
 } admm_binding_info;
 int admm_binding_get_info(const admm_binding* b, admm_binding_info* info);
-/* after admm_engine_create: a scalar or matrix B goes to the engine (admm_engine_set_constraint_b) */
+/* after admm_engine_create: a scalar or matrix B goes to the engine (admm_engine_set_constraint_b), and the groups of a
+ * 'lasso' binding whose args carry `groups` (group sizes: integers >= 1 that sum to the columns of D) and optionally
+ * `groupweights` (one finite value >= 0 per group) go to admm_engine_set_groups.  admm_binding_create checks both vectors
+ * and their element counts (ADMM_E_INVALID) and refuses groups together with parallel = 1 (ADMM_E_UNSUPPORTED) */
 int admm_binding_apply(const admm_binding* b, admm_engine* eng);
 /* options struct -> admm_options (defaults of admm.m:780-971; x0 / z0 / u0 point into the fields) and the checks admm
  * makes before its loop -- callable BEFORE an engine exists, so that a refused call never holds device memory */
@@ -449,6 +461,11 @@ int admm_op_cholesky(double* A, int64_t n, int64_t ldA);
 int admm_op_trsv_pair(const double* L, int64_t n, int64_t ldL, const double* y, double* x);
 /* soft threshold sign(v).*max(abs(v)-t,0)  (getProxOps.m:933-938) */
 int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out);
+/* block soft threshold over ngroups contiguous groups of the given sizes (sum == n), t_g = lambda_over_rho * weights[g]
+ * (weights NULL = 1):  out_g = v_g * (||v_g|| > t_g ? 1 - t_g/||v_g|| : 0) -- the z-prox of group lasso (Boyd et al.
+ * 6.4.2; admm_engine_set_groups), the same device code over the same workgroup plan as the loop's element update */
+int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups,
+                                 const double* weights, double lambda_over_rho, double* out);
 
 /* ---- multi-GPU (one process per GPU; rows of D sharded; RCCL over xGMI) --------
  * unique id is created on rank 0 and handed to the other ranks by the host
