@@ -125,12 +125,7 @@ __global__ void cg_advance_kernel(CgArgs a, int nblk) {
   }
 }
 
-static int cg_blocks(int64_t n) {
-  int64_t b = ceil_div(n, kBlock);
-  if (b > kMaxPartBlocks) b = kMaxPartBlocks;
-  if (b < 1) b = 1;
-  return static_cast<int>(b);
-}
+static int cg_blocks(int64_t n) { return grid_blocks(n, kBlock, kMaxPartBlocks); }
 
 void launch_cg_q(const CgArgs& a, const double* qin, int32_t nchunk, int64_t ldq, bool with_dot, hipStream_t stream) {
   hipLaunchKernelGGL(cg_q_kernel, dim3(cg_blocks(a.n)), dim3(kBlock), 0, stream, a, qin, nchunk, ldq, with_dot ? 1 : 0);

@@ -48,6 +48,11 @@ EnvSwitches env_switches();
 
 inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// grid of a grid-stride kernel: ceil_div(len, per) workgroups, at most `cap`, at least 1
+inline int grid_blocks(int64_t len, int64_t per, int64_t cap) {
+  const int64_t b = ceil_div(len, per);
+  return static_cast<int>(b > cap ? cap : (b < 1 ? 1 : b));
+}
 
 // Device control block: lives in device memory, mirrored to pinned host memory when
 // the host polls.  Every loop kernel starts with `if (ctrl->stop) return;` so that

@@ -4,6 +4,7 @@
 
 #include "consensus.h"
 #include "loop_kernels.h"
+#include "slot_reduce.h"
 
 namespace admm {
 
@@ -115,11 +116,10 @@ int launch_cons_gather_sum(int64_t n, int64_t ldn, int32_t K, const double* npar
 // returns the number of qpart blocks written (0 when qpart is null)
 int launch_cons_sum(int64_t n, int64_t ldn, int32_t K, const double* X, const double* U, double* sums,
                     const double* center, double* qpart, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(n, kBlock);
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  hipLaunchKernelGGL(cons_sum_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, n, ldn, K, X, U,
+  const int blocks = grid_blocks(n, kBlock, kMaxPartBlocks);
+  hipLaunchKernelGGL(cons_sum_kernel, dim3(blocks), dim3(kBlock), 0, stream, n, ldn, K, X, U,
                      sums, center, qpart, ctrl);
-  return qpart ? static_cast<int>(blocks) : 0;
+  return qpart ? blocks : 0;
 }
 
 // z-update + per-slice u-update + every partial sum admm / lassonorms need:
@@ -169,17 +169,7 @@ __global__ __launch_bounds__(kBlock) void cons_update_kernel(ConsArgs a, const C
     if (a.uhist) a.uhist[it * a.n + i] = ub;
   }
   __shared__ double sred[4][S_COUNT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < S_COUNT; ++s) {
-    const double w = wave_sum(acc[s]);
-    if (lane == 0) sred[wid][s] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < S_COUNT) {
-    const int s = threadIdx.x;
-    a.part[s * kMaxPartBlocks + blockIdx.x] = ((sred[0][s] + sred[1][s]) + sred[2][s]) + sred[3][s];
-  }
+  block_reduce_slots<4>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
 }
 
 // Unsharded consensus iteration tail as ONE launch: the slices' x_k are assembled from the partial rows the batched
@@ -289,20 +279,7 @@ __global__ __launch_bounds__(kCuTile* kCuSlots) void cons_gather_update_kernel(
     }
     __syncthreads();  // part / xs / us are reused by the next tile
   }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < S_COUNT; ++s) {
-    const double w = wave_sum(acc[s]);
-    if (lane == 0) sred[wid][s] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < S_COUNT) {
-    const int s = threadIdx.x;
-    double w = sred[0][s];
-#pragma unroll
-    for (int q = 1; q < kCuTile * kCuSlots / 64; ++q) w += sred[q][s];
-    a.part[s * kMaxPartBlocks + blockIdx.x] = w;
-  }
+  block_reduce_slots<kCuTile * kCuSlots / 64>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
 }
 
 bool cons_gather_update_ok(const ConsArgs& a) { return a.K >= 1 && a.K <= 16; }
@@ -311,20 +288,16 @@ void launch_cons_gather_update(const ConsArgs& a, const double* npart, const dou
                                int32_t ntile, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
   // elements x (slice, row-range) slots per workgroup, for the 52 MB of partial rows of 8 slices at n = 10^4:
   // 32 x 16: 25.1 us, 64 x 16: 20.9 us (in use), 128 x 8 (one slot per slice, 80 rows per thread): 25.4 us
-  int64_t blocks = ceil_div(a.n, int64_t{64});
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  *nblk_out = static_cast<int>(blocks);
-  const dim3 grid(static_cast<unsigned>(blocks));
-  hipLaunchKernelGGL((cons_gather_update_kernel<64, 16>), grid, dim3(1024), 0, stream, a, npart, tpart, pstride, ldp, ntile,
+  const int blocks = grid_blocks(a.n, 64, kMaxPartBlocks);
+  *nblk_out = blocks;
+  hipLaunchKernelGGL((cons_gather_update_kernel<64, 16>), dim3(blocks), dim3(1024), 0, stream, a, npart, tpart, pstride, ldp, ntile,
                      ctrl);
 }
 
 void launch_cons_update(const ConsArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
-  int64_t blocks = ceil_div(a.n, kBlock);
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  if (blocks < 1) blocks = 1;
-  *nblk_out = static_cast<int>(blocks);
-  hipLaunchKernelGGL(cons_update_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+  const int blocks = grid_blocks(a.n, kBlock, kMaxPartBlocks);
+  *nblk_out = blocks;
+  hipLaunchKernelGGL(cons_update_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
 }
 
 }  // namespace admm

@@ -14,6 +14,7 @@
 #include "dct.h"
 #include "finalize_device.h"
 #include "kernels.h"
+#include "slot_reduce.h"
 #include "tv2d_pixel.h"
 
 namespace admm {
@@ -150,25 +151,6 @@ __device__ __forceinline__ void dct_to_spectrum(double xak, double xan, double x
   zn = c64{va.x + vb.y, vb.x - va.y};
 }
 
-// block partials of the S_COUNT sums of a 4-wave workgroup -> part[s][blockIdx.x]
-__device__ __forceinline__ void tv2_block_partials_lds(const double (&acc)[S_COUNT], double* __restrict__ part) {
-  __shared__ double sred[kBlock / kWave][S_COUNT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < S_COUNT; ++s) {
-    const double w = wave_sum(acc[s]);
-    if (lane == 0) sred[wid][s] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < S_COUNT) {
-    const int s = threadIdx.x;
-    double tot = sred[0][s];
-#pragma unroll
-    for (int w = 1; w < kBlock / kWave; ++w) tot += sred[w][s];
-    part[s * kMaxPartBlocks + blockIdx.x] = tot;
-  }
-}
-
 constexpr double kSqrtHalf = 0.70710678118654752440;
 constexpr double kSqrt2 = 1.41421356237309504880;
 
@@ -295,7 +277,8 @@ __global__ __launch_bounds__(kBlock) void tv2d_fused_dct_kernel(Tv2Args a, doubl
     dct_forward_from_lds(zs, ca, (!ODDW || j0 + 1 < W) ? ca + H : ca, t);
     __syncthreads();  // zs is the next pair's
   }
-  tv2_block_partials_lds(acc, a.part);
+  __shared__ double sred[kBlock / kWave][S_COUNT];
+  block_reduce_slots<kBlock / kWave>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
 }
 
 __global__ __launch_bounds__(kBlock) void dct_cols_forward_kernel(double* __restrict__ img, int64_t H, DctTables t,

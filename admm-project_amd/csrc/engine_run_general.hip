@@ -6,8 +6,15 @@
 namespace admm {
 namespace {
 
-int factor_x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int64_t* axld, const double** axt,
-                    int32_t* axtri, bool leave_partials);
+// where the element update finds A*x: one vector, or the partial rows the x-solve / the D*x pass left for it to sum
+struct AxSource {
+  const double* src;
+  const double* t;
+  int32_t npart, tri;
+  int64_t ld;
+};
+
+int factor_x_update(admm_engine* e, AxSource* ax, bool leave_partials);
 
 // the one-block triangular solves (symv.hip: tri1_*) leave the backward pass's partial rows to the one-launch tail
 bool xsolve_tri1_partials(const admm_engine* e) {
@@ -24,14 +31,9 @@ bool xsolve_has_partials(const admm_engine* e) {
 }
 
 // one x-update (admm.m:501-511) from e->rhs into e->x, or into chunk partials for the fused consumer
-int x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int64_t* axld, const double** axt,
-             int32_t* axtri, bool leave_partials) {
+int x_update(admm_engine* e, AxSource* ax, bool leave_partials) {
   TimerScope ts(e, ADMM_K_XSOLVE);
-  *axsrc = e->x;
-  *naxpart = 1;
-  *axld = 0;
-  *axt = nullptr;
-  *axtri = 0;
+  *ax = AxSource{e->x, nullptr, 1, 0, 0};
   if (e->xcb) {  // x = xminf(x, z, u, rho), fast ADMM: xminf(x, v, uhat, rho)   (admm.m:502, 506)
     const bool fastalg = e->last_opts.fast != ADMM_FAST_OFF;
     const double* zarg = e->bgen ? (fastalg ? e->vt : e->zt) : (fastalg ? e->v : e->z);
@@ -39,7 +41,7 @@ int x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int64_t* ax
                static_cast<void*>(e->stream)) != 0)
       return fail(ADMM_E_INVALID, "the xminf callback reported a failure");
     if (e->a_identity) {
-      *axsrc = e->xext;  // the fused kernel stores it into x (guarded by the device stop flag)
+      ax->src = e->xext;  // the fused kernel stores it into x (guarded by the device stop flag)
     } else {  // A = D: D*x follows; copy through a kernel that honours the stop flag
       launch_combine(e->xext, 1, 0, 1.0, nullptr, 0.0, nullptr, e->x, e->nA, e->ctrl, e->stream);
     }
@@ -49,7 +51,7 @@ int x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int64_t* ax
   switch (e->problem) {
     case ADMM_PROB_LASSO:
       if (!e->fat) {
-        ADMM_TRY(factor_x_update(e, axsrc, naxpart, axld, axt, axtri, leave_partials));
+        ADMM_TRY(factor_x_update(e, ax, leave_partials));
       } else {
         // getProxOps.m:1204  x = y/rho - D'*(U\(L\(D*y)))/rho^2
         launch_gemv_n(e->planDN, e->D, e->rhs, e->partDN, e->ctrl, e->stream);
@@ -63,7 +65,7 @@ int x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int64_t* ax
       break;
     case ADMM_PROB_QP_BOUNDED:  // planSq/partSq are shared with the objective GEMV; the x-update consumes them first
     case ADMM_PROB_MODEL:
-      ADMM_TRY(factor_x_update(e, axsrc, naxpart, axld, axt, axtri, leave_partials));
+      ADMM_TRY(factor_x_update(e, ax, leave_partials));
       break;
     case ADMM_PROB_LINEARPROGRAM:
     case ADMM_PROB_QP_STANDARD:  // x = K*y + k0: the KKT solve of getProxOps.m:1363 / 1410, reduced once
@@ -96,16 +98,11 @@ int x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int64_t* ax
 }
 
 // the cached-factor x-update shared by lasso (tall), bounded QP and the model problem
-int factor_x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int64_t* axld, const double** axt,
-                    int32_t* axtri, bool leave_partials) {
+int factor_x_update(admm_engine* e, AxSource* ax, bool leave_partials) {
   if (leave_partials && xsolve_tri1_partials(e)) {  // x = sum of the backward pass's rows from the diagonal tile on
     const TrsvPlan& t = e->xfac.trsv;
     launch_tri1_pair(t, e->rhs, nullptr, e->dfin, e->dfin && e->dfin_pending, e->ctrl, e->stream);
-    *axsrc = t.tp1;
-    *axt = t.tp1;
-    *axtri = 1;
-    *naxpart = t.ntile;
-    *axld = t.ldp;
+    *ax = AxSource{t.tp1, t.tp1, t.ntile, 1, t.ldp};
     return ADMM_OK;
   }
   if (leave_partials && xsolve_has_partials(e)) {  // x = sum of these rows, taken by prox_fin_kernel
@@ -114,22 +111,11 @@ int factor_x_update(admm_engine* e, const double** axsrc, int32_t* naxpart, int6
       launch_symv_lower_fin(f.planSy, f.Minv, e->rhs, e->syN, e->syT, *e->dfin, e->dfin_pending, e->ctrl, e->stream);
     else
       launch_symv_lower(f.planSy, f.Minv, f.ldM, e->rhs, e->syN, e->syT, e->x, e->ctrl, e->stream, 0, 1, false);
-    *axsrc = e->syN;
-    *axt = e->syT;
-    *naxpart = f.planSy.ntile;
-    *axld = f.planSy.ldp;
+    *ax = AxSource{e->syN, e->syT, f.planSy.ntile, 0, f.planSy.ldp};
     return ADMM_OK;
   }
   return solve_factor(e, e->rhs, e->x);
 }
-
-// where the element update finds A*x: one vector, or the partial rows the x-solve / the D*x pass left for it to sum
-struct AxSource {
-  const double* src;
-  const double* t;
-  int32_t npart, tri;
-  int64_t ld;
-};
 
 // One run of the general loop: what the lambda of the former one-function run captured, as members.
 struct GeneralLoop {
@@ -412,7 +398,7 @@ struct GeneralLoop {
   }
 
   int x_update_and_ax(AxSource* ax) {
-    ADMM_TRY(x_update(e, &ax->src, &ax->npart, &ax->ld, &ax->t, &ax->tri, fuse_tail));
+    ADMM_TRY(x_update(e, ax, fuse_tail));
     if (!e->a_identity && !e->D) {  // Ax = A(x) with options.A a function handle (admm.m:117-120, 535)
       TimerScope ts(e, ADMM_K_GEMV_N);
       if (e->acb(e->auser, e->x, nA, e->axbuf, len, static_cast<void*>(e->stream)) != 0)

@@ -197,6 +197,9 @@ struct UFixArgs {
   double rho;
 };
 void launch_ufix(const UFixArgs& a, const Ctrl* ctrl, hipStream_t stream);
+// a with the operands its variant (prox, objx, rhs_kind, alg) does not read set to null: ell, zgiven, lb / ub, rhs_add.
+// Every launcher of a kernel that inlines prox_load starts from this.
+ProxArgs pruned_prox_operands(const ProxArgs& a);
 void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream);
 // A = I, alg 0 / 1: z/u update AND the finalize logic in one launch (the last workgroup to arrive finalizes);
 // a.len <= 128 * kMaxPartBlocks

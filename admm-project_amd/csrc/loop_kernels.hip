@@ -12,23 +12,9 @@
 #include "finalize_device.h"
 #include "prox_device.h"
 #include "group_device.h"
+#include "slot_reduce.h"
 
 namespace admm {
-
-__device__ __forceinline__ void block_reduce_slots(double (&acc)[S_COUNT], double* part) {
-  __shared__ double sred[4][S_COUNT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < S_COUNT; ++s) {
-    const double w = wave_sum(acc[s]);
-    if (lane == 0) sred[wid][s] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < S_COUNT) {
-    const int s = threadIdx.x;
-    part[s * kMaxPartBlocks + blockIdx.x] = ((sred[0][s] + sred[1][s]) + sred[2][s]) + sred[3][s];
-  }
-}
 
 template <bool LOGI>
 __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __restrict__ ctrl) {
@@ -51,7 +37,8 @@ __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __
     const double ax = gather_chunks(a.axsrc, a.naxpart, a.axld, i);
     prox_apply<LOGI>(a, i, ax, it, kcoef, in, acc);
   }
-  block_reduce_slots(acc, a.part);
+  __shared__ double sred[4][S_COUNT];
+  block_reduce_slots<4>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
 }
 
 // (A variant of this kernel that gathered x_i straight from symv_lower_kernel's partial sums -- 16 elements x 16
@@ -75,10 +62,8 @@ __global__ __launch_bounds__(kBlock) void prez_kernel(PreZArgs a, const Ctrl* __
 }
 
 void launch_prez(const PreZArgs& a, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(a.len, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(prez_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+  const int blocks = grid_blocks(a.len, kBlock, 2048);
+  hipLaunchKernelGGL(prez_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
 }
 
 __global__ __launch_bounds__(kBlock) void negate_kernel(const double* __restrict__ z, double* __restrict__ bz,
@@ -90,10 +75,8 @@ __global__ __launch_bounds__(kBlock) void negate_kernel(const double* __restrict
 }
 
 void launch_negate(const double* z, double* bz, int64_t len, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(len, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(negate_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, z, bz, len, ctrl);
+  const int blocks = grid_blocks(len, kBlock, 2048);
+  hipLaunchKernelGGL(negate_kernel, dim3(blocks), dim3(kBlock), 0, stream, z, bz, len, ctrl);
 }
 
 // grid = the prox kernel's block count: slots S_U2 / S_DU2 of every block it wrote are rewritten
@@ -112,15 +95,8 @@ __global__ __launch_bounds__(kBlock) void ufix_kernel(UFixArgs a, const Ctrl* __
     su += un * un;
     const double du = un - uo;
     sdu += du * du;
-    if (a.rhs) {  // as prox_apply's epilogue (plain ADMM: zx = z, ux = u)
-      switch (a.rhs_kind) {
-        case RHS_RHO_DTS: a.rhs[i] = a.rho * (zn - un) + add; break;
-        case RHS_RHO_MINUS_Q: a.rhs[i] = a.rho * (zn - un) - add; break;
-        case RHS_DIFF: a.rhs[i] = zn - un; break;
-        case RHS_T1: a.rhs[i] = (ci + zn) - un; break;
-        default: break;
-      }
-    }
+    // as prox_apply's epilogue (plain ADMM: zx = z, ux = u)
+    if (a.rhs && a.rhs_kind != RHS_NONE) a.rhs[i] = rhs_value(a.rhs_kind, a.rho, zn, un, ci, add);
   }
   const double tu = block_sum(su, scratch);
   const double tdu = block_sum(sdu, scratch);
@@ -134,8 +110,10 @@ void launch_ufix(const UFixArgs& a, const Ctrl* ctrl, hipStream_t stream) {
   hipLaunchKernelGGL(ufix_kernel, dim3(static_cast<unsigned>(a.nblk < 1 ? 1 : a.nblk)), dim3(kBlock), 0, stream, a, ctrl);
 }
 
-void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
-  ProxArgs a = args;  // operands this variant does not read -> null (the kernel loads every non-null one up front)
+// operands this variant does not read -> null (prox_load loads every non-null one up front, and some of them are shorter
+// than len when the variant does not use them)
+ProxArgs pruned_prox_operands(const ProxArgs& args) {
+  ProxArgs a = args;
   const bool need_ell = a.prox == PROX_HINGE || a.prox == PROX_01 || a.prox == PROX_LOGISTIC || a.objx == OBJX_HINGE ||
                         a.objx == OBJX_ZEROONE || a.objx == OBJX_LOGISTIC || a.objx == OBJX_DOT;
   if (!need_ell) a.ell = nullptr;
@@ -144,13 +122,16 @@ void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStrea
   const bool need_add = (a.alg != 2 && a.rhs && (a.rhs_kind == RHS_RHO_DTS || a.rhs_kind == RHS_RHO_MINUS_Q)) ||
                         a.objx == OBJX_SOLVE || a.objx == OBJX_SOLVE_QP;
   if (!need_add) a.rhs_add = nullptr;
-  int64_t blocks = ceil_div(a.len, kBlock);
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  if (blocks < 1) blocks = 1;
-  *nblk_out = static_cast<int>(blocks);
+  return a;
+}
+
+void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
+  const ProxArgs a = pruned_prox_operands(args);
+  const int blocks = grid_blocks(a.len, kBlock, kMaxPartBlocks);
+  *nblk_out = blocks;
   if (prox_is_logistic(a))
-    hipLaunchKernelGGL(prox_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
-  else hipLaunchKernelGGL(prox_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+    hipLaunchKernelGGL(prox_kernel<true>, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
+  else hipLaunchKernelGGL(prox_kernel<false>, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
 }
 
 // ---------------------------------------------------------------- alg 2: decide + extrapolate
@@ -194,21 +175,6 @@ void launch_fast_decide(const FinArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(fast_decide_kernel, dim3(1), dim3(kBlock), 0, stream, a);
 }
 
-__device__ __forceinline__ double rhs_value(int kind, double rho, double zx, double ux, double ci, double add) {
-  switch (kind) {
-    case RHS_RHO_DTS:
-      return rho * (zx - ux) + add;
-    case RHS_RHO_MINUS_Q:
-      return rho * (zx - ux) - add;
-    case RHS_DIFF:
-      return zx - ux;
-    case RHS_T1:
-      return (ci + zx) - ux;
-    default:
-      return 0.0;
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void extrapolate_kernel(ExtrapArgs a, const Ctrl* __restrict__ ctrl) {
   if (ctrl->stop) return;
   const int64_t it = ctrl->iter;
@@ -229,10 +195,8 @@ __global__ __launch_bounds__(kBlock) void extrapolate_kernel(ExtrapArgs a, const
 }
 
 void launch_extrapolate(const ExtrapArgs& a, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(a.len, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(extrapolate_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+  const int blocks = grid_blocks(a.len, kBlock, 2048);
+  hipLaunchKernelGGL(extrapolate_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
 }
 
 __global__ __launch_bounds__(kBlock) void zstate_kernel(ZStateArgs a, const Ctrl* __restrict__ ctrl) {
@@ -268,10 +232,8 @@ __global__ __launch_bounds__(kBlock) void zstate_kernel(ZStateArgs a, const Ctrl
 }
 
 void launch_zstate(const ZStateArgs& a, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(a.len, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(zstate_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+  const int blocks = grid_blocks(a.len, kBlock, 2048);
+  hipLaunchKernelGGL(zstate_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
 }
 
 __global__ __launch_bounds__(kBlock) void initial_rhs_kernel(int64_t len, int kind, double rho,
@@ -287,10 +249,8 @@ __global__ __launch_bounds__(kBlock) void initial_rhs_kernel(int64_t len, int ki
 
 void launch_initial_rhs(int64_t len, int rhs_kind, double rho, const double* zx, const double* ux, const double* c,
                         const double* rhs_add, double* rhs, hipStream_t stream) {
-  int64_t blocks = ceil_div(len, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(initial_rhs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, len, rhs_kind,
+  const int blocks = grid_blocks(len, kBlock, 2048);
+  hipLaunchKernelGGL(initial_rhs_kernel, dim3(blocks), dim3(kBlock), 0, stream, len, rhs_kind,
                      rho, zx, ux, c, rhs_add, rhs);
 }
 
@@ -337,64 +297,34 @@ __device__ __forceinline__ double tail_gather(const ProxArgs& a, int64_t i, int3
   return s;
 }
 
-// defer = 1: the finalize logic is NOT run here; the block partials are stored plainly and the next launch on the
-// stream (the x-solve of the next iteration, or a stand-alone finalize) takes them after the kernel boundary.
-template <bool LOGI>
-__global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArgs f, Ctrl* __restrict__ ctrl,
-                                                              int32_t defer) {
-  const int32_t stop = ctrl->stop;
-  const int64_t it = ctrl->iter;
-  const double aprev = ctrl->acurr;
-  // (the stop test sits below the loads: they do not depend on it, and in front of them it costs this 9 us kernel one
-  // more memory round trip)
-  __shared__ double quarter[kTailSlots - 1][kTailTile];
-  __shared__ int32_t last;
-  const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kTailTile + e;
-  const int64_t ic = i < a.len ? i : a.len - 1;
-  ProxIn in{};
-  if (slot == 0) in = prox_load(a, ic);  // in flight together with the partial rows
-  double ax;
-  {  // partial rows of this element, split over the four slots: naxpart + 1 rows after the lower-triangle x-solve
-     // (N-part rows up to the diagonal tile, T-part rows beyond), naxpart chunk rows of a column-chunked GEMV otherwise
-    const int32_t dblk = static_cast<int32_t>(blockIdx.x);  // (kTailTile = the x-solve's tile: one diagonal tile per workgroup)
-    const int32_t P = a.ax_tri ? a.naxpart - dblk : (a.ax_t ? a.naxpart + 1 : a.naxpart);
-    const int32_t q = (P + kTailSlots - 1) / kTailSlots;
-    const int32_t p0 = slot * q, p1 = (p0 + q < P) ? p0 + q : P;
-    ax = p0 < P ? tail_gather(a, ic, p0, p1) : 0.0;
-  }
-  if (stop) return;  // (uniform; nothing has been stored yet)
-  if (slot > 0) quarter[slot - 1][e] = ax;
-  __syncthreads();
-  double acc[S_COUNT];
-#pragma unroll
-  for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
-  if (slot == 0 && i < a.len) {
-    double kcoef = 0.0;
-    if (a.alg == 1) {
-      const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
-      kcoef = (aprev - 1.0) / acn;
-    }
-    prox_apply<LOGI>(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
-  }
-  // block partials of the two waves that hold elements, published write-through
+// this slot's share of the partial rows of element ic, whose diagonal tile is d: naxpart + 1 rows after the lower-triangle
+// x-solve (N-part rows up to the diagonal tile, T-part rows beyond), naxpart - d rows after the one-block triangular
+// solves, naxpart chunk rows of a column-chunked GEMV otherwise -- split into four quarters
+__device__ __forceinline__ double tail_ax_share(const ProxArgs& a, int64_t ic, int32_t d, int slot) {
+  const int32_t P = a.ax_tri ? a.naxpart - d : (a.ax_t ? a.naxpart + 1 : a.naxpart);
+  const int32_t q = (P + kTailSlots - 1) / kTailSlots;
+  const int32_t p0 = slot * q, p1 = (p0 + q < P) ? p0 + q : P;
+  return p0 < P ? tail_gather(a, ic, p0, p1) : 0.0;
+}
+
+// The end of a one-launch tail kernel (the caller returns behind it).  Block partials of the two waves that hold
+// elements; deferred, they are stored plainly and the next launch on the stream takes them after the kernel boundary.
+// Otherwise they are published write-through, the workgroup arrives on ctrl->arrive, and the LAST workgroup to arrive
+// resets the counter and runs the finalize logic on what every workgroup published.  The only cross-workgroup memory
+// ordering of the library.
+__device__ __forceinline__ void tail_publish_finalize(const double (&acc)[S_COUNT], double* part, const FinArgs& f,
+                                                      Ctrl* __restrict__ ctrl, int32_t defer) {
   __shared__ double sred[2][S_COUNT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (wid < 2) {
-#pragma unroll
-    for (int s = 0; s < S_COUNT; ++s) {
-      const double w = wave_sum(acc[s]);
-      if (lane == 0) sred[wid][s] = w;
-    }
-  }
+  __shared__ int32_t last;
+  if ((threadIdx.x >> 6) < 2) slot_wave_sums(acc, sred);
   __syncthreads();
   if (defer) {
-    if (threadIdx.x < S_COUNT) a.part[threadIdx.x * kMaxPartBlocks + blockIdx.x] = sred[0][threadIdx.x] + sred[1][threadIdx.x];
+    if (threadIdx.x < S_COUNT) part[threadIdx.x * kMaxPartBlocks + blockIdx.x] = slot_total<2>(sred, threadIdx.x);
     return;
   }
   if (threadIdx.x < S_COUNT) {
     const int s = threadIdx.x;
-    __hip_atomic_store(a.part + s * kMaxPartBlocks + blockIdx.x, sred[0][s] + sred[1][s], __ATOMIC_RELAXED,
+    __hip_atomic_store(part + s * kMaxPartBlocks + blockIdx.x, slot_total<2>(sred, s), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains: the element stores as well
@@ -410,6 +340,41 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
   finalize_body<true>(f);
 }
 
+// defer = 1: the finalize logic is NOT run here; the block partials are stored plainly and the next launch on the
+// stream (the x-solve of the next iteration, or a stand-alone finalize) takes them after the kernel boundary.
+template <bool LOGI>
+__global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArgs f, Ctrl* __restrict__ ctrl,
+                                                              int32_t defer) {
+  const int32_t stop = ctrl->stop;
+  const int64_t it = ctrl->iter;
+  const double aprev = ctrl->acurr;
+  // (the stop test sits below the loads: they do not depend on it, and in front of them it costs this 9 us kernel one
+  // more memory round trip)
+  __shared__ double quarter[kTailSlots - 1][kTailTile];
+  const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kTailTile + e;
+  const int64_t ic = i < a.len ? i : a.len - 1;
+  ProxIn in{};
+  if (slot == 0) in = prox_load(a, ic);  // in flight together with the partial rows
+  // (kTailTile = the x-solve's tile: one diagonal tile per workgroup)
+  const double ax = tail_ax_share(a, ic, static_cast<int32_t>(blockIdx.x), slot);
+  if (stop) return;  // (uniform; nothing has been stored yet)
+  if (slot > 0) quarter[slot - 1][e] = ax;
+  __syncthreads();
+  double acc[S_COUNT];
+#pragma unroll
+  for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
+  if (slot == 0 && i < a.len) {
+    double kcoef = 0.0;
+    if (a.alg == 1) {
+      const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
+      kcoef = (aprev - 1.0) / acn;
+    }
+    prox_apply<LOGI>(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
+  }
+  tail_publish_finalize(acc, a.part, f, ctrl, defer);
+}
+
 FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
   FinArgs ff = f;
   ff.nblk = static_cast<int32_t>(ceil_div(a.len, kTailTile));
@@ -423,15 +388,7 @@ FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
 
 void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
                      bool defer) {
-  ProxArgs a = args;
-  const bool need_ell = a.prox == PROX_HINGE || a.prox == PROX_01 || a.prox == PROX_LOGISTIC || a.objx == OBJX_HINGE ||
-                        a.objx == OBJX_ZEROONE || a.objx == OBJX_LOGISTIC || a.objx == OBJX_DOT;
-  if (!need_ell) a.ell = nullptr;
-  if (a.prox != PROX_GIVEN) a.zgiven = nullptr;
-  if (a.prox != PROX_BOX) a.lb = a.ub = nullptr;
-  const bool need_add = (a.alg != 2 && a.rhs && (a.rhs_kind == RHS_RHO_DTS || a.rhs_kind == RHS_RHO_MINUS_Q)) ||
-                        a.objx == OBJX_SOLVE || a.objx == OBJX_SOLVE_QP;
-  if (!need_add) a.rhs_add = nullptr;
+  const ProxArgs a = pruned_prox_operands(args);
   const int64_t blocks = ceil_div(a.len, kTailTile);
   *nblk_out = static_cast<int>(blocks);
   const FinArgs ff = prox_fin_args(a, f);
@@ -453,11 +410,7 @@ void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nb
 // Element i sums its partial rows exactly as prox_fin_kernel does (split into four quarters of its own tile's count).
 __device__ __forceinline__ double group_ax(const ProxArgs& a, int64_t ic, int slot, int e,
                                            double (*quarter)[kTailTile]) {
-  const int32_t d = static_cast<int32_t>(ic / kTailTile);
-  const int32_t P = a.ax_tri ? a.naxpart - d : (a.ax_t ? a.naxpart + 1 : a.naxpart);
-  const int32_t q = (P + kTailSlots - 1) / kTailSlots;
-  const int32_t p0 = slot * q, p1 = (p0 + q < P) ? p0 + q : P;
-  const double ax = p0 < P ? tail_gather(a, ic, p0, p1) : 0.0;
+  const double ax = tail_ax_share(a, ic, static_cast<int32_t>(ic / kTailTile), slot);
   __syncthreads();  // (the previous chunk's quarters have been read)
   if (slot > 0) quarter[slot - 1][e] = ax;
   __syncthreads();
@@ -476,7 +429,6 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
   __shared__ double quarter[kTailSlots - 1][kTailTile];
   __shared__ double sq[kGroupTile];
   __shared__ double gacc[kGroupMaxPerWg];
-  __shared__ int32_t last;
   static_assert(kGroupTile == kTailTile, "one chunk of a group plan is one tile of the one-launch tail");
   const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
   const int32_t nch = static_cast<int32_t>((E1 - E0 + kTailTile - 1) / kTailTile);
@@ -525,51 +477,17 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
       prox_apply<false>(a, i, ax, it, kcoef, in, acc);
     }
   }
-  // block partials of the two waves that hold elements and group sums; from here on as prox_fin_kernel
-  __shared__ double sred[2][S_COUNT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (wid < 2) {
-#pragma unroll
-    for (int s = 0; s < S_COUNT; ++s) {
-      const double w = wave_sum(acc[s]);
-      if (lane == 0) sred[wid][s] = w;
-    }
-  }
-  __syncthreads();
-  if (defer) {
-    if (threadIdx.x < S_COUNT) a.part[threadIdx.x * kMaxPartBlocks + blockIdx.x] = sred[0][threadIdx.x] + sred[1][threadIdx.x];
-    return;
-  }
-  if (threadIdx.x < S_COUNT) {
-    const int s = threadIdx.x;
-    __hip_atomic_store(a.part + s * kMaxPartBlocks + blockIdx.x, sred[0][s] + sred[1][s], __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains: the element stores as well
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int32_t old = __hip_atomic_fetch_add(&ctrl->arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = (old == static_cast<int32_t>(gridDim.x) - 1) ? 1 : 0;
-    if (last) __hip_atomic_store(&ctrl->arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!last || threadIdx.x >= kBlock) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  finalize_body<true>(f);
+  tail_publish_finalize(acc, a.part, f, ctrl, defer);  // (the two waves that hold elements also hold the group sums)
 }
 
 void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
                            hipStream_t stream, bool defer) {
-  ProxArgs a = args;  // (a lasso engine: no ell, no bounds)
-  a.ell = nullptr;
-  a.lb = a.ub = nullptr;
-  a.zgiven = nullptr;  // z reaches prox_apply in a register
-  a.prox = PROX_GIVEN;
+  // groups exist on ADMM_PROB_LASSO engines only (admm_engine_set_groups) and the grouped update is not used behind a
+  // split z-update: args.prox is PROX_SOFT and objx is none or OBJX_SOLVE, so ell, the bounds and zgiven are nulled
+  ProxArgs a = pruned_prox_operands(args);
+  a.prox = PROX_GIVEN;  // z reaches prox_apply in a register
   const int32_t want_objz = a.objz == OBJZ_ABS ? 1 : 0;  // the kernel adds the penalty once per group instead
   a.objz = OBJZ_NONE;
-  const bool need_add = (a.alg != 2 && a.rhs && (a.rhs_kind == RHS_RHO_DTS || a.rhs_kind == RHS_RHO_MINUS_Q)) ||
-                        a.objx == OBJX_SOLVE || a.objx == OBJX_SOLVE_QP;
-  if (!need_add) a.rhs_add = nullptr;
   *nblk_out = gp.nwg;
   FinArgs ff = prox_fin_args(a, f);
   ff.nblk = gp.nwg;
@@ -741,11 +659,9 @@ __global__ __launch_bounds__(kBlock) void residual_sq_kernel(const double* __res
 
 void launch_residual_sq(const double* part, int32_t nchunk, int64_t ld, const double* s, int64_t len, double* objpart,
                         int* nblk_out, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(len, kBlock);
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  if (blocks < 1) blocks = 1;
-  *nblk_out = static_cast<int>(blocks);
-  hipLaunchKernelGGL(residual_sq_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, part, nchunk,
+  const int blocks = grid_blocks(len, kBlock, kMaxPartBlocks);
+  *nblk_out = blocks;
+  hipLaunchKernelGGL(residual_sq_kernel, dim3(blocks), dim3(kBlock), 0, stream, part, nchunk,
                      ld, s, len, objpart, ctrl);
 }
 
@@ -768,11 +684,9 @@ __global__ __launch_bounds__(kBlock) void qp_objective_kernel(const double* __re
 
 void launch_qp_objective(const double* part, int32_t nchunk, int64_t ld, const double* x, const double* q,
                          int64_t len, double* objpart, int* nblk_out, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(len, kBlock);
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  if (blocks < 1) blocks = 1;
-  *nblk_out = static_cast<int>(blocks);
-  hipLaunchKernelGGL(qp_objective_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, part, nchunk,
+  const int blocks = grid_blocks(len, kBlock, kMaxPartBlocks);
+  *nblk_out = blocks;
+  hipLaunchKernelGGL(qp_objective_kernel, dim3(blocks), dim3(kBlock), 0, stream, part, nchunk,
                      ld, x, q, len, objpart, ctrl);
 }
 
@@ -795,10 +709,8 @@ __global__ __launch_bounds__(kBlock) void run_init_kernel(RunInitArgs a) {
 void launch_run_init(const RunInitArgs& a, hipStream_t stream) {
   int64_t most = a.len > a.nA ? a.len : a.nA;
   if (a.N > most) most = a.N;
-  int64_t blocks = ceil_div(most, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(run_init_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a);
+  const int blocks = grid_blocks(most, kBlock, 2048);
+  hipLaunchKernelGGL(run_init_kernel, dim3(blocks), dim3(kBlock), 0, stream, a);
 }
 
 __global__ __launch_bounds__(kBlock) void obj_compare_kernel(const double* __restrict__ pa, int na, double sa, double ca,
@@ -841,10 +753,8 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(const double* __restric
 
 void launch_combine(const double* part, int32_t nchunk, int64_t ld, double alpha, const double* y, double beta,
                     const double* add, double* x, int64_t len, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(len, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(combine_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, part, nchunk, ld,
+  const int blocks = grid_blocks(len, kBlock, 2048);
+  hipLaunchKernelGGL(combine_kernel, dim3(blocks), dim3(kBlock), 0, stream, part, nchunk, ld,
                      alpha, y, beta, add, x, len, ctrl);
 }
 

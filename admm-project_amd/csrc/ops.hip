@@ -166,9 +166,8 @@ int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out) {
   ADMM_TRY(sc.alloc(&dv, n));
   ADMM_TRY(sc.alloc(&dout, n));
   ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
-  int64_t blocks = ceil_div(n, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(soft_threshold_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, nullptr, dv, n, t,
+  const int blocks = grid_blocks(n, kBlock, 2048);
+  hipLaunchKernelGGL(soft_threshold_kernel, dim3(blocks), dim3(kBlock), 0, nullptr, dv, n, t,
                      dout);
   ADMM_HIP_TRY(hipDeviceSynchronize());
   ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));

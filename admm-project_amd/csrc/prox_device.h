@@ -45,6 +45,23 @@ __host__ __device__ inline bool prox_is_logistic(const ProxArgs& a) {
   return a.prox == PROX_LOGISTIC || a.objx == OBJX_LOGISTIC;
 }
 
+// the next x-update's right-hand side from (zx, ux): the one statement of RhsKind's formulas (RHS_NONE: the caller
+// stores nothing)
+__device__ __forceinline__ double rhs_value(int kind, double rho, double zx, double ux, double ci, double add) {
+  switch (kind) {
+    case RHS_RHO_DTS:
+      return rho * (zx - ux) + add;
+    case RHS_RHO_MINUS_Q:
+      return rho * (zx - ux) - add;
+    case RHS_DIFF:
+      return zx - ux;
+    case RHS_T1:
+      return (ci + zx) - ux;
+    default:
+      return 0.0;
+  }
+}
+
 struct ProxIn {  // every input of one element (see prox_load)
   double zp, u_old, uhat_i, c_i, ell_i, zg_i, lb_i, ub_i, v_i, add_i, rhs_i;
 };
@@ -188,7 +205,7 @@ __device__ __forceinline__ void prox_apply(const ProxArgs& a, int64_t i, double 
     a.uprev[i] = u_old;
   }
   if (rhs_out) *rhs_out = (ci + zx) - ux;
-  if (a.alg != 2 && a.rhs) {
+  if (a.alg != 2 && a.rhs) {  // rhs_value's formulas, written out: through the call ad_onepass_kernel spills differently
     switch (a.rhs_kind) {
       case RHS_RHO_DTS:
         a.rhs[i] = a.rho * (zx - ux) + add_i;

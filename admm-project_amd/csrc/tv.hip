@@ -30,6 +30,7 @@
 #include "tv.h"
 #include "tv_direct2.h"
 #include "finalize_device.h"
+#include "slot_reduce.h"
 
 namespace admm {
 
@@ -267,19 +268,8 @@ __global__ __launch_bounds__(kBlock) void tv_prox_kernel(TvArgs a, const Ctrl* _
     if (a.zhist) a.zhist[it * n + i] = zn;
     if (a.uhist) a.uhist[it * n + i] = un;
   }
-  // block partials
   __shared__ double sred[4][S_COUNT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < S_COUNT; ++s) {
-    const double w = wave_sum(acc[s]);
-    if (lane == 0) sred[wid][s] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < S_COUNT) {
-    const int s = threadIdx.x;
-    a.part[s * kMaxPartBlocks + blockIdx.x] = ((sred[0][s] + sred[1][s]) + sred[2][s]) + sred[3][s];
-  }
+  block_reduce_slots<4>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -354,7 +344,7 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
   double* __restrict__ L2 = lds + kCap + (kCap >> 4) + 1;  // forward right-hand side -> next y
   __shared__ double wA[4], wB[4];
   __shared__ double sred[4][S_COUNT];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   if (a.deferred && blockIdx.x == 0) {  // the passenger (dispatched first): tail of the PREVIOUS iteration
     if (!a.fin_pending) return;
     {  // all slots at once: 16 lanes per slot stride over the tiles, 16 loads in flight per lane; fixed order
@@ -542,17 +532,7 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
       }
     }
     // block partials of the residual sums (before the second scan: keeps the accumulators short-lived)
-#pragma unroll
-    for (int s = 0; s < S_COUNT; ++s) {
-      const double w = wave_sum(acc[s]);
-      if (lane == 0) sred[wid][s] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < S_COUNT) {
-      const int s = threadIdx.x;
-      const double t = ((sred[0][s] + sred[1][s]) + sred[2][s]) + sred[3][s];
-      a.part[s * a.part_stride + tile_id] = t;
-    }
+    block_reduce_slots<4>(acc, sred, a.part, a.part_stride, tile_id);
     // ---- 3. forward scan of the next iteration's right-hand side, owned store
     tv_block_scan<E>(L2, fcount, [&](int q) { return tv_coef<false>(a, f0 + q, n, rho, cstar); }, wA, wB);
 #pragma unroll
@@ -1061,11 +1041,9 @@ __global__ __launch_bounds__(kBlock) void tv_dual_kernel(const double* __restric
 
 void launch_tv_dx(const double* x, const double* s, int64_t n, double lambda, int objevals, double* ax,
                   double* objpart, int* nobj_out, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(n, kBlock);
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  if (blocks < 1) blocks = 1;
-  *nobj_out = static_cast<int>(blocks);
-  hipLaunchKernelGGL(tv_dx_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, x, s, n, lambda,
+  const int blocks = grid_blocks(n, kBlock, kMaxPartBlocks);
+  *nobj_out = blocks;
+  hipLaunchKernelGGL(tv_dx_kernel, dim3(blocks), dim3(kBlock), 0, stream, x, s, n, lambda,
                      objevals, ax, objpart, ctrl);
 }
 
@@ -1089,10 +1067,8 @@ __global__ __launch_bounds__(kBlock) void tv_relax_z_kernel(const double* __rest
 
 void launch_tv_relax_z(const double* ax, const double* zp, const double* u, int64_t n, double relax, double t,
                        double* zgiven, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(n, kBlock);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(tv_relax_z_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, ax, zp, u, n,
+  const int blocks = grid_blocks(n, kBlock, 2048);
+  hipLaunchKernelGGL(tv_relax_z_kernel, dim3(blocks), dim3(kBlock), 0, stream, ax, zp, u, n,
                      relax, t, zgiven, ctrl);
 }
 
@@ -1201,11 +1177,9 @@ void launch_tv_sweep(const TvArgs& a, bool backward, const Ctrl* ctrl, hipStream
 }
 
 void launch_tv_prox(const TvArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
-  int64_t blocks = ceil_div(a.n, kBlock);
-  if (blocks > kMaxPartBlocks) blocks = kMaxPartBlocks;
-  if (blocks < 1) blocks = 1;
-  *nblk_out = static_cast<int>(blocks);
-  hipLaunchKernelGGL(tv_prox_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, ctrl);
+  const int blocks = grid_blocks(a.n, kBlock, kMaxPartBlocks);
+  *nblk_out = blocks;
+  hipLaunchKernelGGL(tv_prox_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
 }
 
 }  // namespace admm

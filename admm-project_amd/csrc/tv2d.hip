@@ -9,15 +9,11 @@
 #include "kernels.h"
 #include "loop_kernels.h"
 #include "tv2d.h"
+#include "slot_reduce.h"
 
 namespace admm {
 
-static int tv2_blocks(int64_t n) {
-  int64_t b = ceil_div(n, kBlock);
-  if (b > kMaxPartBlocks) b = kMaxPartBlocks;
-  if (b < 1) b = 1;
-  return static_cast<int>(b);
-}
+static int tv2_blocks(int64_t n) { return grid_blocks(n, kBlock, kMaxPartBlocks); }
 
 // w = rho * D'D p:  (D'D p)[i,j] = sum over the existing 4-neighbours of (p[i,j] - p[nb])
 __global__ __launch_bounds__(kBlock) void tv2d_laplace_kernel(int64_t H, int64_t W, double rho,
@@ -110,25 +106,6 @@ __global__ __launch_bounds__(kBlock) void tv2d_rhs_kernel(Tv2Args a, double* __r
 // sign(v)*max(|v| - t, 0) (one subtraction v -+ t), in three instructions instead of eleven
 __device__ __forceinline__ double tv2_clamp(double v, double t) {
   return __builtin_fmin(__builtin_fmax(v, -t), t);
-}
-
-template <int WAVES = 4>
-__device__ __forceinline__ void tv2_block_partials(const double (&acc)[S_COUNT], double* part, int first, int last) {
-  __shared__ double sred[WAVES][S_COUNT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < S_COUNT; ++s) {
-    const double w = wave_sum(acc[s]);
-    if (lane == 0) sred[wid][s] = w;
-  }
-  __syncthreads();
-  if (static_cast<int>(threadIdx.x) >= first && static_cast<int>(threadIdx.x) <= last) {
-    const int s = threadIdx.x;
-    double tot = sred[0][s];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) tot += sred[w][s];
-    part[s * kMaxPartBlocks + blockIdx.x] = tot;
-  }
 }
 
 // One pass per iteration instead of three: the z/u update, the D' stencils of the dual residual / tolerance AND the
@@ -262,7 +239,8 @@ __global__ __launch_bounds__(kTv2Tile, kTv2Resident * kTv2Tile / 256) void tv2d_
     acc[S_G3] += g3 * g3;
     (bnext + base)[tid] = si + a.rho * gb;
   }
-  tv2_block_partials<kTv2Tile / kWave>(acc, a.part, 0, S_COUNT - 1);
+  __shared__ double sred[kTv2Tile / kWave][S_COUNT];
+  block_reduce_slots<kTv2Tile / kWave>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
 }
 
 // u = clamp(v), z = v - u over the 2N elements of the compact state (the iterates a run hands back)
@@ -277,10 +255,8 @@ __global__ __launch_bounds__(kBlock) void tv2d_expand_kernel(const double* __res
 }
 
 void launch_tv2d_expand(const double* v, double thresh, int64_t len, double* z, double* u, hipStream_t stream) {
-  int64_t blocks = ceil_div(len, kBlock);
-  if (blocks > 16384) blocks = 16384;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(tv2d_expand_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, v, thresh, len,
+  const int blocks = grid_blocks(len, kBlock, 16384);
+  hipLaunchKernelGGL(tv2d_expand_kernel, dim3(blocks), dim3(kBlock), 0, stream, v, thresh, len,
                      z, u);
 }
 
@@ -338,7 +314,14 @@ __global__ __launch_bounds__(kBlock) void tv2d_dual_vec_kernel(int64_t H, int64_
     acc[S_G2] += g2 * g2;
     acc[S_G3] += g3 * g3;
   }
-  tv2_block_partials(acc, part, S_G2, S_G3);
+  // only the two slots this kernel makes are stored: the rest of the prox kernel's partial array stays
+  __shared__ double sred[4][S_COUNT];
+  slot_wave_sums(acc, sred);
+  __syncthreads();
+  if (static_cast<int>(threadIdx.x) >= S_G2 && static_cast<int>(threadIdx.x) <= S_G3) {
+    const int s = threadIdx.x;
+    part[s * kMaxPartBlocks + blockIdx.x] = slot_total<4>(sred, s);
+  }
 }
 
 void launch_tv2d_dual_vec(int64_t H, int64_t W, const double* dz, const double* u, double* part, int nblk,
@@ -360,9 +343,8 @@ void launch_tv2d_fused(const Tv2Args& a, bool state_in, double* bnext, const Ctr
 
 void launch_tv2d_laplace(int64_t H, int64_t W, double rho, const double* p, double* w, const Ctrl* ctrl,
                          hipStream_t stream) {
-  int64_t blocks = ceil_div(H * W, kBlock);
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(tv2d_laplace_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, H, W, rho, p, w,
+  const int blocks = grid_blocks(H * W, kBlock, 16384);
+  hipLaunchKernelGGL(tv2d_laplace_kernel, dim3(blocks), dim3(kBlock), 0, stream, H, W, rho, p, w,
                      ctrl);
 }
 
@@ -373,9 +355,8 @@ void launch_tv2d_cg_pq(int64_t H, int64_t W, double rho, const CgArgs& a, double
 }
 
 void launch_tv2d_rhs(const Tv2Args& a, double* b, const Ctrl* ctrl, hipStream_t stream) {
-  int64_t blocks = ceil_div(a.H * a.W, kBlock);
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(tv2d_rhs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, a, b, ctrl);
+  const int blocks = grid_blocks(a.H * a.W, kBlock, 16384);
+  hipLaunchKernelGGL(tv2d_rhs_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, b, ctrl);
 }
 
 }  // namespace admm

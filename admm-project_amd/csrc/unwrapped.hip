@@ -227,12 +227,9 @@ void launch_uw_ax(const UwArgs& a, const FinArgs& f, Ctrl* ctrl, hipStream_t str
 }
 
 void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl, hipStream_t stream) {
-  ProxArgs pa = pargs;
-  const bool need_ell = pa.prox == PROX_HINGE || pa.prox == PROX_01 || pa.prox == PROX_LOGISTIC ||
-                        pa.objx == OBJX_HINGE || pa.objx == OBJX_ZEROONE || pa.objx == OBJX_LOGISTIC || pa.objx == OBJX_DOT;
-  if (!need_ell) pa.ell = nullptr;
-  pa.zgiven = nullptr;
-  pa.lb = pa.ub = nullptr;
+  // GeneralLoop::plan takes this form only for ADMM_PROB_LINEARSVM without a z callback: the prox is the hinge, the 0-1 or
+  // the logistic one, never PROX_GIVEN / PROX_BOX, so zgiven and the bounds are nulled here as they always were
+  ProxArgs pa = pruned_prox_operands(pargs);
   pa.rhs_add = nullptr;
   if (prox_is_logistic(pa))
     hipLaunchKernelGGL(uw_prox_kernel<true>, dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args,
@@ -342,12 +339,7 @@ int onepass_workgroups(int64_t m) {
 }
 
 void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pargs, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
-  ProxArgs pa = pargs;
-  const bool need_ell = pa.prox == PROX_HINGE || pa.prox == PROX_01 || pa.prox == PROX_LOGISTIC ||
-                        pa.objx == OBJX_HINGE || pa.objx == OBJX_ZEROONE || pa.objx == OBJX_LOGISTIC || pa.objx == OBJX_DOT;
-  if (!need_ell) pa.ell = nullptr;
-  if (pa.prox != PROX_GIVEN) pa.zgiven = nullptr;
-  if (pa.prox != PROX_BOX) pa.lb = pa.ub = nullptr;
+  ProxArgs pa = pruned_prox_operands(pargs);
   pa.rhs_add = nullptr;
   pa.rhs = nullptr;  // t = c + z - u never leaves the kernel
   pa.dz = nullptr;

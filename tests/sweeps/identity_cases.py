@@ -21,6 +21,9 @@ CASES = (
     "lasso_trsv", "lasso_cg", "lasso_graph", "lasso_fat", "model_trsv", "model_inverse", "lp", "qp_standard",
     "qp_bounded", "basispursuit", "covsel_64", "covsel_97", "lasso_calibration", "lasso_cancelling", "lad_nodual0",
     "lad_nodual1", "huberfit_nodual0", "huberfit_nodual1", "svm_6000", "svm_24000", "svm_fast_strong",
+    "svm_logistic_6000", "svm_logistic_24000",
+    "grouplasso_inverse", "grouplasso_trsv", "grouplasso_fast_weak", "grouplasso_256x64", "grouplasso_one_group",
+    "grouplasso_weights",
     "consensus_4x64", "tv_5000",
     "tv_direct_60", "tv_direct_stop_in_batch", "tv_direct_nohist_11", "tv_fused_objevals", "tv_fused_skip_x",
     "tv_fused_n1", "tv_sweep_rho40", "tv_sweep_rho700", "tv_fast_strong", "tv_fast_weak_objevals", "tv_relax",
@@ -96,19 +99,41 @@ def library_cases(ap):
         for nd in (0, 1):
             yield "%s_nodual%d" % (solver, nd), (lambda solver=solver, prob=prob, nd=nd: getattr(ap, solver)(
                 prob["D"], prob["s"], dict(objevals=1, nodualerror=nd, maxiters=40)))
-    for rows in (6000, 24000):
-        q = sy.mnist_like_problem(seed=2, m=rows, n=400, digit=1)
+    svm = {rows: sy.mnist_like_problem(seed=2, m=rows, n=400, digit=1) for rows in (6000, 24000)}
+    for rows, q in svm.items():
         yield "svm_%d" % rows, (lambda q=q: ap.linearsvm(q["D"], q["ell"], q["C"], dict(
             objevals=1, maxiters=60, x0=q["x0"], z0=q["z0"], u0=q["u0"])))
     q = sy.mnist_like_problem(seed=2, m=1000, n=130, digit=1)
     yield "svm_fast_strong", lambda: ap.linearsvm(q["D"], q["ell"], q["C"], dict(
         fast=1, fasttype="strong", nodualerror=0, maxiters=40, x0=q["x0"], z0=q["z0"], u0=q["u0"]))
+    for rows, q in svm.items():  # 6000 rows: the two-launch form; 24000: one pass over D
+        yield "svm_logistic_%d" % rows, (lambda q=q: ap.linearsvm(q["D"], q["ell"], q["C"], dict(
+            lossfunction="logistic", objevals=1, maxiters=60, x0=q["x0"], z0=q["z0"], u0=q["u0"])))
+    yield from grouplasso_cases(ap)
     cl = sy.lasso_problem(5, 4 * 64, 32)
     yield "consensus_4x64", lambda: ap.lasso(cl["D"], cl["s"], cl["lam"], dict(parallel="both", workers=4, objevals=1))
     tv = sy.tv_problem(0, 5000)
     yield "tv_5000", lambda: ap.totalvariation(tv["s"], tv["lam"], dict(objevals=1))
     yield from tv_form_cases(ap)
     yield from tv2d_form_cases(ap)
+
+
+def grouplasso_cases(ap):
+    """The grouped one-launch tail: deferred behind the packed x-solve and behind the one-block triangular solves,
+    followed by a stand-alone finalize (accelerated ADMM), with the finalize inside the launch (a small problem), one
+    workgroup walking several chunks twice (one group of 300), and weighted groups."""
+    sy = ap.synth
+    g = sy.grouplasso_problem(7, rows=2000, cols=1600, ngroups=40, active=4)
+
+    def gl(p, groups=None, **o):
+        groups = p["groups"] if groups is None else groups
+        return lambda: ap.grouplasso(p["D"], p["s"], p["lam"], groups, dict(o))
+    yield "grouplasso_inverse", gl(g, xsolve="inverse", objevals=1)
+    yield "grouplasso_trsv", gl(g, xsolve="trsv", objevals=1)
+    yield "grouplasso_fast_weak", gl(g, xsolve="inverse", objevals=1, fast=1, fasttype="weak")
+    yield "grouplasso_256x64", gl(sy.grouplasso_problem(0), objevals=1)
+    yield "grouplasso_one_group", gl(sy.lasso_problem(3, 600, 300), groups=[300], objevals=1)
+    yield "grouplasso_weights", gl(g, xsolve="inverse", objevals=1, groupweights=np.sqrt(g["groups"].astype(float)))
 
 
 def tv_form_cases(ap):
