@@ -203,6 +203,12 @@ _SIGNATURES = {
     "admm_op_trsv_pair": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp]),
     "admm_op_soft_threshold": (C.c_int, [_dp, C.c_int64, C.c_double, _dp]),
     "admm_op_group_soft_threshold": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_double, _dp]),
+    "admm_op_symv": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp]),
+    "admm_op_symv_batch": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int64, C.c_int64, _dp, C.c_int64]),
+    "admm_op_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_double, _dp, C.c_int64, _dp,
+                               C.c_int64, C.c_double, _dp, C.c_int64, C.c_int32]),
+    "admm_op_trtri": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int64]),
+    "admm_op_llt_apply": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp]),
     "admm_comm_unique_id": (C.c_int, [C.c_char_p]),
     "admm_comm_init": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "admm_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -133,6 +133,9 @@ struct Tri1Args {
 void launch_tri1_forward(const Tri1Args& a, const FinArgs* fin, bool fin_pending, const Ctrl* ctrl, hipStream_t stream);
 void launch_tri1_backward(const Tri1Args& a, const Ctrl* ctrl, hipStream_t stream);
 void launch_tri1_reduce(const Tri1Args& a, double* x, const Ctrl* ctrl, hipStream_t stream);
+// y = the fixed-order sum of the partial rows a symv_lower_* launch of plan p left in npart / tpart
+void launch_symv_reduce(const SymvPlan& p, const double* npart, const double* tpart, double* y, const Ctrl* ctrl,
+                        hipStream_t stream);
 Tri1Args tri1_args(const TrsvPlan& p, const double* y);
 // both passes; x == nullptr leaves the backward pass's partial rows to the consumer (prox_fin_kernel)
 void launch_tri1_pair(const TrsvPlan& p, const double* y, double* x, const FinArgs* fin, bool fin_pending,

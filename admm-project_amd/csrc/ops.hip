@@ -16,12 +16,13 @@ struct Scratch {  // frees everything on scope exit
   ~Scratch() {
     for (void* p : ptrs) (void)hipFree(p);
   }
-  int alloc(double** out, size_t elems) {
+  template <typename T = double>
+  int alloc(T** out, size_t elems) {
     void* p = nullptr;
-    hipError_t e = hipMalloc(&p, (elems ? elems : 1) * sizeof(double));
+    hipError_t e = hipMalloc(&p, (elems ? elems : 1) * sizeof(T));
     if (e != hipSuccess) return fail(ADMM_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
     ptrs.push_back(p);
-    *out = static_cast<double*>(p);
+    *out = static_cast<T*>(p);
     return ADMM_OK;
   }
 };
@@ -38,6 +39,25 @@ int put_matrix(Scratch& sc, double** dst, int64_t* ld, const double* src, int64_
   ADMM_TRY(sc.alloc(dst, static_cast<size_t>(*ld) * cols));
   ADMM_HIP_TRY(hipMemset(*dst, 0, sizeof(double) * (*ld) * cols));
   ADMM_HIP_TRY(hipMemcpy2D(*dst, (*ld) * sizeof(double), src, ld_src * sizeof(double), rows * sizeof(double), cols,
+                           hipMemcpyHostToDevice));
+  return ADMM_OK;
+}
+
+// a column-major host matrix with the caller's leading dimension VERBATIM (put_matrix rounds it up): an odd ld must
+// reach the kernel, it selects the guarded tile loader of the GEMM.  The device buffer is ld x cols and starts as
+// all-ones bytes (NaN), so an element a kernel reads past the rows the caller gave poisons its result.
+int put_verbatim(Scratch& sc, double** dst, const double* src, int64_t rows, int64_t cols, int64_t ld) {
+  const size_t elems = static_cast<size_t>(ld) * cols;
+  ADMM_TRY(sc.alloc(dst, elems));
+  ADMM_HIP_TRY(hipMemset(*dst, 0xFF, sizeof(double) * elems));
+  ADMM_HIP_TRY(hipMemcpy(*dst, src, sizeof(double) * (static_cast<size_t>(ld) * (cols - 1) + rows),
+                         hipMemcpyHostToDevice));
+  return ADMM_OK;
+}
+
+// the n x n part of a host matrix, exactly as given, into zero-filled npad x npad storage (SymvPlan's contract)
+int put_padded(double* dst, int64_t npad, const double* src, int64_t n, int64_t ld_src) {
+  ADMM_HIP_TRY(hipMemcpy2D(dst, npad * sizeof(double), src, ld_src * sizeof(double), n * sizeof(double), n,
                            hipMemcpyHostToDevice));
   return ADMM_OK;
 }
@@ -191,6 +211,161 @@ int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* size
   launch_group_soft_threshold(dv, h.bind(dplan), lambda_over_rho, dout, nullptr);
   ADMM_HIP_TRY(hipDeviceSynchronize());
   ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
+int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32_t form, int64_t ncached,
+                 int32_t part_count, double* y) {
+  if (!M || !x || !y || n <= 0 || ldM < n || form < 0 || form > 3 || ncached < -1 || part_count < 1 ||
+      (form == 0 && (part_count > 1 || (ldM & 1))))
+    return fail(ADMM_E_INVALID, "symv: bad argument (form 0..3, ncached >= -1, part_count >= 1; form 0: one part, even ldM)");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dM, *dx, *dy;
+  ADMM_TRY(sc.alloc(&dx, round_up(n, 2)));
+  ADMM_TRY(sc.alloc(&dy, round_up(n, 2)));
+  ADMM_HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  if (form == 0) {
+    ADMM_TRY(put_verbatim(sc, &dM, M, n, n, ldM));
+    launch_symv_small(dM, n, ldM, dx, dy, nullptr, nullptr);
+    ADMM_HIP_TRY(hipDeviceSynchronize());
+    ADMM_HIP_TRY(hipMemcpy(y, dy, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return ADMM_OK;
+  }
+  SymvPlan plan = symv_plan(n);
+  if (ncached >= 0) plan.ncached = ncached;
+  ADMM_TRY(sc.alloc(&dM, static_cast<size_t>(plan.npad) * plan.npad));
+  ADMM_HIP_TRY(hipMemset(dM, 0, sizeof(double) * plan.npad * plan.npad));
+  ADMM_TRY(put_padded(dM, plan.npad, M, n, ldM));
+  const double* dA = dM;
+  if (form >= 2) {
+    double* dP;
+    ADMM_TRY(sc.alloc(&dP, symv_packed_elems(plan)));
+    launch_symv_pack(plan, dM, plan.npad, dP, nullptr);
+    plan.packed = true;
+    dA = dP;
+  }
+  double *npart, *tpart;
+  ADMM_TRY(sc.alloc(&npart, plan.npart_elems()));
+  ADMM_TRY(sc.alloc(&tpart, plan.tpart_elems()));
+  Ctrl* ctrl = nullptr;
+  if (form == 3) {  // symv_lower_fin_kernel reads ctrl->stop without a null test: a zero-filled control block
+    ADMM_TRY(sc.alloc(&ctrl, 1));
+    ADMM_HIP_TRY(hipMemset(ctrl, 0, sizeof(Ctrl)));
+  }
+  // one part: every partial slot the sum reads is written by a tile, so the slots start as NaN and a missed one shows;
+  // several parts: the launcher asks for zero-filled slots (the tiles of the other ranks stay zero)
+  const int fill = part_count > 1 ? 0 : 0xFF;
+  std::vector<double> part(static_cast<size_t>(n));
+  for (int32_t r = 0; r < part_count; ++r) {
+    ADMM_HIP_TRY(hipMemset(npart, fill, sizeof(double) * plan.npart_elems()));
+    ADMM_HIP_TRY(hipMemset(tpart, fill, sizeof(double) * plan.tpart_elems()));
+    if (form == 3)
+      launch_symv_lower_fin(plan, dA, dx, npart, tpart, FinArgs{}, false, ctrl, nullptr, r, part_count, dy);
+    else
+      launch_symv_lower(plan, dA, plan.npad, dx, npart, tpart, dy, ctrl, nullptr, r, part_count);
+    ADMM_HIP_TRY(hipDeviceSynchronize());
+    ADMM_HIP_TRY(hipMemcpy(r == 0 ? y : part.data(), dy, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (r > 0)
+      for (int64_t i = 0; i < n; ++i) y[i] += part[i];  // the ranks' partial results, in rank order
+  }
+  return ADMM_OK;
+}
+
+int admm_op_symv_batch(const double* Ms, int64_t n, int64_t ldM, int32_t K, const double* X, int64_t ldX,
+                       int64_t ncached, double* Y, int64_t ldY) {
+  if (!Ms || !X || !Y || n <= 0 || ldM < n || K < 1 || ldX < n || ldY < n || ncached < -1)
+    return fail(ADMM_E_INVALID, "symv_batch: bad argument (K >= 1, ncached >= -1)");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  SymvPlan plan = symv_plan(n);
+  if (ncached >= 0) plan.ncached = ncached;
+  plan.packed = true;
+  const int64_t npad = plan.npad;
+  const size_t pelems = symv_packed_elems(plan), pstride = plan.npart_elems();
+  double *dM, *dP, *dX, *dY, *npart, *tpart;
+  const double** dptr;  // the K matrix pointers of the batched launch
+  ADMM_TRY(sc.alloc(&dM, static_cast<size_t>(npad) * npad));
+  ADMM_TRY(sc.alloc(&dP, pelems * K));
+  ADMM_TRY(sc.alloc(&dptr, K));
+  ADMM_TRY(sc.alloc(&dX, static_cast<size_t>(npad) * K));
+  ADMM_TRY(sc.alloc(&dY, static_cast<size_t>(npad) * K));
+  ADMM_TRY(sc.alloc(&npart, pstride * K));
+  ADMM_TRY(sc.alloc(&tpart, pstride * K));
+  ADMM_HIP_TRY(hipMemset(dM, 0, sizeof(double) * npad * npad));
+  ADMM_HIP_TRY(hipMemset(dX, 0, sizeof(double) * npad * K));
+  ADMM_HIP_TRY(hipMemset(npart, 0xFF, sizeof(double) * pstride * K));  // (as in admm_op_symv: one part)
+  ADMM_HIP_TRY(hipMemset(tpart, 0xFF, sizeof(double) * pstride * K));
+  std::vector<const double*> ptrs(static_cast<size_t>(K));
+  for (int32_t k = 0; k < K; ++k) {
+    ADMM_TRY(put_padded(dM, npad, Ms + static_cast<size_t>(k) * ldM * n, n, ldM));
+    launch_symv_pack(plan, dM, npad, dP + pelems * k, nullptr);
+    ADMM_HIP_TRY(hipDeviceSynchronize());  // dM is overwritten by the next slice
+    ptrs[k] = dP + pelems * k;
+  }
+  ADMM_HIP_TRY(hipMemcpy(dptr, ptrs.data(), sizeof(const double*) * K, hipMemcpyHostToDevice));
+  ADMM_HIP_TRY(hipMemcpy2D(dX, npad * sizeof(double), X, ldX * sizeof(double), n * sizeof(double), K,
+                           hipMemcpyHostToDevice));
+  launch_symv_lower_batch(plan, dptr, K, dX, npad, npart, tpart,
+                          static_cast<int64_t>(pstride), nullptr, nullptr, nullptr);
+  for (int32_t k = 0; k < K; ++k)
+    launch_symv_reduce(plan, npart + pstride * k, tpart + pstride * k, dY + npad * k, nullptr, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy2D(Y, ldY * sizeof(double), dY, npad * sizeof(double), n * sizeof(double), K,
+                           hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
+int admm_op_gemm(int32_t transA, int32_t transB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,
+                 int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int32_t lower_only) {
+  const bool flags_ok = (transA == 0 || transA == 1) && (transB == 0 || transB == 1) && (lower_only == 0 || lower_only == 1);
+  if (!A || !B || !C || !flags_ok || M <= 0 || N <= 0 || K < 1 || lda < (transA ? K : M) || ldb < (transB ? N : K) ||
+      ldc < M || (lower_only && M != N))
+    return fail(ADMM_E_INVALID, "gemm: bad argument (K >= 1, ld >= stored rows, lower_only needs a square C)");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dA, *dB, *dC;
+  ADMM_TRY(put_verbatim(sc, &dA, A, transA ? K : M, transA ? M : K, lda));
+  ADMM_TRY(put_verbatim(sc, &dB, B, transB ? N : K, transB ? K : N, ldb));
+  ADMM_TRY(sc.alloc(&dC, static_cast<size_t>(ldc) * N));
+  ADMM_HIP_TRY(hipMemcpy(dC, C, sizeof(double) * ldc * N, hipMemcpyHostToDevice));
+  launch_gemm(transA, transB, M, N, K, alpha, dA, lda, dB, ldb, beta, dC, ldc, lower_only != 0, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(C, dC, sizeof(double) * ldc * N, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
+int admm_op_trtri(const double* L, int64_t n, int64_t ldL, double* X, int64_t ldX) {
+  if (!L || !X || n <= 0 || ldL < n || ldX < n) return fail(ADMM_E_INVALID, "trtri: bad argument");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dL, *dX, *dinv;
+  ADMM_TRY(put_verbatim(sc, &dL, L, n, n, ldL));
+  ADMM_TRY(sc.alloc(&dX, static_cast<size_t>(ldX) * n));
+  ADMM_HIP_TRY(hipMemset(dX, 0xFF, sizeof(double) * ldX * n));
+  ADMM_TRY(sc.alloc(&dinv, static_cast<size_t>(ceil_div(n, 64)) * 64 * 64));
+  launch_trtri_diag(dL, n, ldL, dinv, nullptr);
+  ADMM_TRY(trtri_lower_from_diag(dL, n, ldL, dinv, dX, ldX, nullptr, true));
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  // the whole ldX x n buffer: the launcher clears it, padding rows included (padded storage wants them zero), and no
+  // kernel behind the clear may store into those rows
+  ADMM_HIP_TRY(hipMemcpy(X, dX, sizeof(double) * ldX * n, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
+int admm_op_llt_apply(const double* L, int64_t n, int64_t ldL, const double* x, double* y) {
+  if (!L || !x || !y || n <= 0 || ldL < n) return fail(ADMM_E_INVALID, "llt_apply: bad argument");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dL, *dx, *dt, *dy;
+  ADMM_TRY(put_verbatim(sc, &dL, L, n, n, ldL));
+  ADMM_TRY(sc.alloc(&dx, n));
+  ADMM_TRY(sc.alloc(&dt, n));
+  ADMM_TRY(sc.alloc(&dy, n));
+  ADMM_HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  launch_llt_apply(dL, n, ldL, dx, dt, dy, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(y, dy, sizeof(double) * n, hipMemcpyDeviceToHost));
   return ADMM_OK;
 }
 

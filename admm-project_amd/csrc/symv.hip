@@ -508,6 +508,12 @@ void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P,
   hipLaunchKernelGGL(symv_pack_kernel, dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kBlock), 0, stream, M, ld, P);
 }
 
+void launch_symv_reduce(const SymvPlan& p, const double* npart, const double* tpart, double* y, const Ctrl* ctrl,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(symv_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(p.n, 16))), dim3(kBlock), 0, stream, npart,
+                     tpart, p.ldp, p.n, p.ntile, y, ctrl);
+}
+
 void launch_symv_lower(const SymvPlan& p, const double* M, int64_t ld, const double* x, double* npart, double* tpart,
                        double* y, const Ctrl* ctrl, hipStream_t stream, int part_rank, int part_count, bool reduce) {
   const uint32_t ncached = static_cast<uint32_t>(p.ncached < 0 ? 0 : p.ncached);
@@ -518,10 +524,7 @@ void launch_symv_lower(const SymvPlan& p, const double* M, int64_t ld, const dou
     hipLaunchKernelGGL(symv_lower_kernel<false>, dim3(static_cast<unsigned>(p.ntile), static_cast<unsigned>(p.ntile)),
                        dim3(kWave), 0, stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached,
                        ctrl);
-  if (!reduce) return;  // the consumer sums the partial rows itself (prox_fin_kernel)
-  const int64_t blocks = ceil_div(p.n, 16);
-  hipLaunchKernelGGL(symv_reduce_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, npart, tpart,
-                     p.ldp, p.n, p.ntile, y, ctrl);
+  if (reduce) launch_symv_reduce(p, npart, tpart, y, ctrl, stream);  // else the consumer sums the rows (prox_fin_kernel)
 }
 
 void launch_symv_lower_batch(const SymvPlan& p, const double* const* Ms_dev, int32_t K, const double* x0, int64_t xstride,
@@ -541,10 +544,7 @@ void launch_symv_lower_fin(const SymvPlan& p, const double* M, const double* x, 
   const dim3 grid(static_cast<unsigned>(symv_tiles(p)) + 1u);
   hipLaunchKernelGGL(symv_lower_fin_kernel, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp, part_rank,
                      part_count, ncached, f, fin_pending ? 1 : 0, ctrl);
-  if (!y) return;  // the consumer sums the partial rows itself
-  const int64_t blocks = ceil_div(p.n, 16);
-  hipLaunchKernelGGL(symv_reduce_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, npart, tpart,
-                     p.ldp, p.n, p.ntile, y, ctrl);
+  if (y) launch_symv_reduce(p, npart, tpart, y, ctrl, stream);  // else the consumer sums the partial rows itself
 }
 
 }  // namespace admm

@@ -466,6 +466,36 @@ int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out);
  * 6.4.2; admm_engine_set_groups), the same device code over the same workgroup plan as the loop's element update */
 int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups,
                                  const double* weights, double lambda_over_rho, double* out);
+/* y = M*x for a symmetric n x n M by the kernels of the explicit-inverse x-update (getProxOps.m:1200).  form selects
+ * the launcher: 0 = the small form (one wave per column; reads FULL storage, ldM must be even), 1 = the 128 x 128 tile
+ * kernel on padded column-major storage, 2 = the same on tile-packed storage, 3 = the tile-packed launch that carries
+ * the deferred finalize step (here without one).  Forms 1 - 3 read the LOWER triangle only: what the caller stores
+ * strictly above the diagonal reaches the device as given and must not matter.  ncached: -1 = the plan's cache split,
+ * k >= 0 = the first k lower-triangle tiles (row-major triangle order) are read with default loads, the rest
+ * non-temporally.  part_count = P >= 1: P launches, launch r taking every P-th tile as rank r of P does in a multi-GPU
+ * run, each into zero-filled partial rows; y is the sum of the P partial results in rank order (form 0: P = 1 only). */
+int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32_t form, int64_t ncached,
+                 int32_t part_count, double* y);
+/* Y(:,k) = M_k * X(:,k), k < K: K symmetric n x n matrices stored back to back (matrix k at Ms + k*ldM*n), tile-packed
+ * and multiplied in ONE batched launch (the slice inverses of consensus lasso); lower triangles only, ncached as above */
+int admm_op_symv_batch(const double* Ms, int64_t n, int64_t ldM, int32_t K, const double* X, int64_t ldX,
+                       int64_t ncached, double* Y, int64_t ldY);
+/* C = alpha*op(A)*op(B) + beta*C (M x N, inner length K; transX: 0 = N, 1 = T) on the fp64 matrix cores, the GEMM of the
+ * setup (`D'*D`, the Cholesky updates, the factor inverse).  A, B and C go to the device with the caller's leading
+ * dimensions: an odd one selects the guarded tile loader.  A and B are read as (cols-1)*ld + rows doubles; C must hold
+ * ldc*N doubles and comes back whole (rows M .. ldc-1 are never written).  beta == 0 never reads C.  lower_only (M == N):
+ * only the lower triangle, diagonal included, is defined on return. */
+int admm_op_gemm(int32_t transA, int32_t transB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,
+                 int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int32_t lower_only);
+/* X = inv(L) for the lower factor L (what it stores above the diagonal is ignored): the 64 x 64 diagonal blocks by
+ * substitution, the rest by recursive doubling over batched GEMMs -- every explicit inverse and every pre-inverted
+ * panel of the triangular solves is built this way.  X must hold ldX*n doubles and comes back whole: the inverse in its
+ * n x n block (zero above the diagonal) and +0.0 in the padding rows n .. ldX-1, which the launcher clears and no kernel
+ * writes afterwards. */
+int admm_op_trtri(const double* L, int64_t n, int64_t ldL, double* X, int64_t ldX);
+/* y = L*(L'*x) for the lower factor L (above the diagonal ignored): the right-hand side of the setup probe that picks
+ * the x-solve form, whose exact solution is x */
+int admm_op_llt_apply(const double* L, int64_t n, int64_t ldL, const double* x, double* y);
 
 /* ---- multi-GPU (one process per GPU; rows of D sharded; RCCL over xGMI) --------
  * unique id is created on rank 0 and handed to the other ranks by the host

@@ -68,6 +68,71 @@ def test_no_cpu_fallback_without_device(ap):
     assert rc == ap._lib.E_DEVICE
 
 
+def _dense_op_calls(ap):
+    """(name, call(**overrides) -> rc) for the operator entry points of the symmetric product and the dense setup
+    kernels, each with valid small arguments unless overridden"""
+    L, dp = ap._lib.load(), ap._lib.as_dp
+    n = 4
+    M = np.asfortranarray(np.eye(n) * 2.0)
+    Ms = np.asfortranarray(np.tile(np.eye(n), (1, 2)))
+    x, y = np.ones(n), np.zeros(n)
+    X2, Y2 = np.ones((n, 2), order="F"), np.zeros((n, 2), order="F")
+    Cm, Xi = np.zeros((n, n), order="F"), np.zeros((n, n), order="F")
+
+    def symv(M=dp(M), n=n, ld=n, x=dp(x), form=1, ncached=-1, parts=1, y=dp(y)):
+        return L.admm_op_symv(M, n, ld, x, form, ncached, parts, y)
+
+    def symv_batch(Ms=dp(Ms), n=n, ld=n, K=2, X=dp(X2), ldX=n, ncached=-1, Y=dp(Y2), ldY=n):
+        return L.admm_op_symv_batch(Ms, n, ld, K, X, ldX, ncached, Y, ldY)
+
+    def gemm(ta=0, tb=0, M=n, N=n, K=n, A=dp(M), lda=n, B=dp(M), ldb=n, C=dp(Cm), ldc=n, lower=0):
+        return L.admm_op_gemm(ta, tb, M, N, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, lower)
+
+    def trtri(Lf=dp(M), n=n, ld=n, X=dp(Xi), ldX=n):
+        return L.admm_op_trtri(Lf, n, ld, X, ldX)
+
+    def llt_apply(Lf=dp(M), n=n, ld=n, x=dp(x), y=dp(y)):
+        return L.admm_op_llt_apply(Lf, n, ld, x, y)
+
+    keep = (M, Ms, x, y, X2, Y2, Cm, Xi)  # the defaults above hold pointers into these
+    return dict(symv=symv, symv_batch=symv_batch, gemm=gemm, trtri=trtri, llt_apply=llt_apply), keep
+
+
+def test_dense_ops_reject_bad_arguments_before_touching_the_device(ap):
+    """E_INVALID for null pointers, ld < rows, and every out-of-range selector -- decided on the host, so the answer is
+    the same with and without a device"""
+    ops, _keep = _dense_op_calls(ap)
+    bad = [
+        ("symv", dict(M=None)), ("symv", dict(x=None)), ("symv", dict(y=None)), ("symv", dict(n=0)),
+        ("symv", dict(ld=3)), ("symv", dict(form=-1)), ("symv", dict(form=4)), ("symv", dict(parts=0)),
+        ("symv", dict(form=0, parts=2)), ("symv", dict(ncached=-2)), ("symv", dict(form=0, n=3, ld=3)),
+        ("symv_batch", dict(Ms=None)), ("symv_batch", dict(X=None)), ("symv_batch", dict(Y=None)),
+        ("symv_batch", dict(ld=3)), ("symv_batch", dict(ldX=3)), ("symv_batch", dict(ldY=3)),
+        ("symv_batch", dict(K=0)), ("symv_batch", dict(ncached=-2)),
+        ("gemm", dict(A=None)), ("gemm", dict(B=None)), ("gemm", dict(C=None)), ("gemm", dict(lda=3)),
+        ("gemm", dict(ldb=3)), ("gemm", dict(ldc=3)), ("gemm", dict(K=0)), ("gemm", dict(ta=2)), ("gemm", dict(tb=-1)),
+        ("gemm", dict(ta=1, K=5, lda=4)), ("gemm", dict(tb=1, N=5, ldb=4)), ("gemm", dict(M=3, lower=1)),
+        ("trtri", dict(Lf=None)), ("trtri", dict(X=None)), ("trtri", dict(ld=3)), ("trtri", dict(ldX=3)),
+        ("trtri", dict(n=0)),
+        ("llt_apply", dict(Lf=None)), ("llt_apply", dict(x=None)), ("llt_apply", dict(y=None)),
+        ("llt_apply", dict(ld=3)), ("llt_apply", dict(n=0)),
+    ]
+    for name, kw in bad:
+        assert ops[name](**kw) == ap._lib.E_INVALID, (name, kw)
+    for name in ops:
+        assert f"admm_op_{name}" in ap._lib.EXPORTED_SYMBOLS
+
+
+def test_dense_ops_have_no_cpu_fallback(ap):
+    """valid arguments: the result of a device, or E_DEVICE -- never a host computation"""
+    ops, _keep = _dense_op_calls(ap)
+    expected = ap._lib.OK if ap._lib.device_count() > 0 else ap._lib.E_DEVICE
+    for name, call in ops.items():
+        assert call() == expected, name
+    if expected != ap._lib.OK:
+        assert b"no CPU fallback" in ap._lib.load().admm_last_error()
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "admm-project_amd")
     for dirpath, _, files in os.walk(pkg):
