@@ -332,6 +332,35 @@ __device__ __forceinline__ void tv_block_scan(double* __restrict__ lds, int coun
   __syncthreads();
 }
 
+// The passenger workgroup of the one-launch forms (a.deferred: block 0, dispatched first) does the tail of the PREVIOUS
+// iteration: that iteration's tile partials summed into a.slots16 -- all slots at once, 16 lanes per slot striding over
+// the tiles, 16 loads in flight per lane, fixed order -- then its finalize logic (fin.slots_reduced = a.slots16).
+// tv_fused_kernel and tv_direct2_kernel call it; tv_direct_kernel has the same text written out.
+__device__ __forceinline__ void tv_passenger_tail(const TvArgs& a, const FinArgs& fin) {
+  const int slot = threadIdx.x >> 4, sub = threadIdx.x & 15;
+  double v = 0.0;
+  if (slot < S_COUNT) {
+    const double* __restrict__ ps = a.prev_part + slot * a.part_stride;
+    for (int32_t b0 = 0; b0 < a.prev_ntiles; b0 += 256) {
+      double w[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int32_t b = b0 + sub + 16 * k;
+        w[k] = ps[b < a.prev_ntiles ? b : a.prev_ntiles - 1];
+      }
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (b0 + sub + 16 * k < a.prev_ntiles) v += w[k];
+    }
+  }
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if (slot < S_COUNT && sub == 0) a.slots16[slot] = v;
+  __threadfence_block();
+  __syncthreads();
+  finalize_body<false>(fin);
+}
+
 // (r2: issuing every global load of a tile -- z, u, s pairs and the wave-boundary neighbours -- before the first scan
 // costs 40 more VGPRs: 3 workgroups per CU instead of 4 and 0.2390 against 0.2331 ms per iteration on the same box,
 // 2 workgroups 0.3165.  Residency, not the number of dependent load rounds inside a workgroup, carries this kernel.)
@@ -347,30 +376,7 @@ __global__ __launch_bounds__(kBlock, 4) void tv_fused_kernel(TvArgs a, FinArgs f
   const int tid = threadIdx.x, lane = tid & 63;
   if (a.deferred && blockIdx.x == 0) {  // the passenger (dispatched first): tail of the PREVIOUS iteration
     if (!a.fin_pending) return;
-    {  // all slots at once: 16 lanes per slot stride over the tiles, 16 loads in flight per lane; fixed order
-      const int slot = tid >> 4, sub = tid & 15;
-      double v = 0.0;
-      if (slot < S_COUNT) {
-        const double* __restrict__ ps = a.prev_part + slot * a.part_stride;
-        for (int32_t b0 = 0; b0 < a.prev_ntiles; b0 += 256) {
-          double w[16];
-#pragma unroll
-          for (int k = 0; k < 16; ++k) {
-            const int32_t b = b0 + sub + 16 * k;
-            w[k] = ps[b < a.prev_ntiles ? b : a.prev_ntiles - 1];
-          }
-#pragma unroll
-          for (int k = 0; k < 16; ++k)
-            if (b0 + sub + 16 * k < a.prev_ntiles) v += w[k];
-        }
-      }
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (slot < S_COUNT && sub == 0) a.slots16[slot] = v;
-    }
-    __threadfence_block();
-    __syncthreads();
-    finalize_body<false>(fin);  // fin.slots_reduced = a.slots16
+    tv_passenger_tail(a, fin);
     return;
   }
   const unsigned tile_id = a.deferred ? blockIdx.x - 1u : blockIdx.x;
@@ -602,7 +608,7 @@ __global__ __launch_bounds__(kBlock, 4) void tv_direct_kernel(TvArgs a, FinArgs 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   if (a.deferred && blockIdx.x == 0) {  // the passenger (dispatched first): tail of the PREVIOUS iteration
     if (ctrl->stop || !a.fin_pending) return;  // (its own read: `stop` must not be needed before the tiles' loads)
-    {
+    {  // tv_passenger_tail written out: the call costs this kernel 14 VGPRs (VIN) of the 128 it has (EXPERIMENTS.md)
       const int slot = tid >> 4, sub = tid & 15;
       double v = 0.0;
       if (slot < S_COUNT) {
@@ -907,33 +913,9 @@ __global__ __launch_bounds__(kBlock, (EXTRA || !VIN) ? 4 : 6) void tv_direct2_ke
   int32_t stop;
   asm volatile("s_load_dword %0, %1, 0x0" : "=s"(stop) : "s"(ctrl));
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int tid = threadIdx.x;
   if (a.deferred && blockIdx.x == 0) {  // the passenger (dispatched first): tail of the PREVIOUS iteration
     if (ctrl->stop || !a.fin_pending) return;  // (its own read: `stop` must not be needed before the tiles' loads)
-    {
-      const int slot = tid >> 4, sub = tid & 15;
-      double v = 0.0;
-      if (slot < S_COUNT) {
-        const double* __restrict__ ps = a.prev_part + slot * a.part_stride;
-        for (int32_t b0 = 0; b0 < a.prev_ntiles; b0 += 256) {
-          double w[16];
-#pragma unroll
-          for (int k = 0; k < 16; ++k) {
-            const int32_t b = b0 + sub + 16 * k;
-            w[k] = ps[b < a.prev_ntiles ? b : a.prev_ntiles - 1];
-          }
-#pragma unroll
-          for (int k = 0; k < 16; ++k)
-            if (b0 + sub + 16 * k < a.prev_ntiles) v += w[k];
-        }
-      }
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (slot < S_COUNT && sub == 0) a.slots16[slot] = v;
-    }
-    __threadfence_block();
-    __syncthreads();
-    finalize_body<false>(fin);  // fin.slots_reduced = a.slots16
+    tv_passenger_tail(a, fin);
     return;
   }
   const unsigned bid = a.deferred ? blockIdx.x - 1u : blockIdx.x;

@@ -952,12 +952,61 @@ def test_total_variation_deferred_tail_matches_the_two_small_launches(gpu, n, op
 @pytest.mark.parametrize("n,rho", [(1936, 1.0), (1937, 1.0), (1993, 1.0), (3872, 1.0), (3873, 1.0), (3929, 1.0), (5809, 1.0),
                                    (20000, 10.0), (12001, 30.0), (7000, 0.05)])
 def test_total_variation_direct_kernel_tile_boundaries(gpu, n, rho):
-    """tv_direct_kernel: lengths around multiples of the owned tile (1936 positions at rho = 1: the last tile is then
-    empty-but-one, exactly full, or ends inside the margin of the tile before it -- every such tile must take the exact
-    scan path), and slowly decaying kernels (rho = 10, 30: 124 / 216 taps per side)."""
+    """tv_direct2_kernel: lengths around multiples of the owned tile (1936 positions at rho = 1: the last tile is then
+    empty-but-one, exactly full, or ends inside the margin of the tile before it -- every such tile fills its ghost
+    positions from mirror images), and slowly decaying kernels (rho = 10, 30: 124 / 216 taps per side)."""
     p = gpu.synth.tv_problem(n % 89, n)
     o = dict(objevals=1, rho=rho, maxiters=25)
     _compare(gpu.totalvariation(p["s"], 1.0, dict(o)), S.totalvariation(p["s"], 1.0, dict(o)), tol=1e-7)
+
+
+# Signals shorter than two window margins of the direct form (the margin is 56 at rho = 1 and 240 at rho = 30: 111 and
+# 479 are one element short) run as ONE tile of tv_direct_kernel, both ends by block scans -- a mirror image of one end
+# (tv_direct2.h) would reach past the other.
+_TV_SHORT = [(2, 1.0), (3, 1.0), (59, 1.0), (60, 1.0), (111, 1.0), (479, 30.0)]
+
+
+@pytest.mark.parametrize("n,rho", _TV_SHORT + [(480, 30.0)])  # 480 = two margins: the first tv_direct2 length at rho = 30
+def test_total_variation_signals_shorter_than_two_margins(gpu, n, rho):
+    """Against the oracle: with history and objective; stopping by tolerance inside a batch; without history after an
+    odd forced count (x rebuilt by two sweeps from the z, u the last iteration read, z and u expanded from the third
+    state buffer)."""
+    p = gpu.synth.tv_problem(n % 89, n)
+    for o in (dict(rho=rho, objevals=1), dict(rho=rho)):
+        _compare(gpu.totalvariation(p["s"], p["lam"], dict(o)), S.totalvariation(p["s"], p["lam"], dict(o)))
+    o = dict(rho=rho, maxiters=11, domaxiters=1)
+    got = gpu.totalvariation(p["s"], p["lam"], dict(o, record_history=0))
+    ref = S.totalvariation(p["s"], p["lam"], dict(o))
+    assert got["steps"] == ref["steps"] == 11
+    for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr"):
+        _close(k, got[k], ref[k], TOL, None)
+
+
+@pytest.mark.parametrize("history", [1, 0])
+@pytest.mark.parametrize("n,rho,seed,extra", [(60, 1.0, 3, dict()), (479, 30.0, 105, dict(reltol=0.7))])
+def test_total_variation_short_signal_speculative_iteration_behind_a_stop(gpu, n, rho, seed, extra, history):
+    """The stop lands inside a batch of 8 (step 33 / step 11 on the oracle), so tv_direct_kernel has run one iteration
+    past it into the next state buffer: iterates bitwise those of polling after every iteration, norms to the
+    1e-12 of test_total_variation_deferred_tail_matches_the_two_small_launches.  (At rho = 30 the reference's
+    convergence test aborts the run before the default tolerance is met, whatever the seed: reltol = 0.7 and seed 105
+    give a stop by tolerance in the second batch.)"""
+    p = gpu.synth.tv_problem(seed, n)
+    opts = dict(rho=rho, stopcond="both", convtest=1, maxiters=90, **extra)
+    ref = S.totalvariation(p["s"], p["lam"], dict(opts))
+    assert "steps" in ref and ref["steps"] < 90 and ref["steps"] % 8 != 0, "the input must stop inside a batch"
+    if not history:
+        opts["record_history"] = 0
+    got = gpu.totalvariation(p["s"], p["lam"], dict(opts))
+    two = gpu.totalvariation(p["s"], p["lam"], dict(opts, check_every=1))
+    assert got["steps"] == two["steps"] == ref["steps"]
+    for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr", "xvals", "zvals", "uvals"):
+        assert (k in got) == (k in two), k
+        if k in got and k in ("xopt", "zopt", "uopt", "xvals", "zvals", "uvals"):
+            assert np.array_equal(got[k], two[k]), k
+        elif k in got:
+            _close(k, got[k], two[k], 1e-12)
+    for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr"):
+        _close(k, got[k], ref[k], TOL, None)
 
 
 @pytest.mark.parametrize("m,n", [(161, 231), (40, 400), (3, 17)])
@@ -1125,3 +1174,13 @@ def test_one_tv_engine_through_successive_iteration_forms(gpu):
     runs_2d = [dict(rho=1.0), dict(rho=300.0), dict(fast=L.FAST_STRONG), dict(rho=1.0)]
     for name, mk, seq in (("tv", make, runs), ("tv2d", make_2d, runs_2d)):
         _one_engine_against_fresh_ones(L, name, mk, seq)
+
+
+def test_one_tv_engine_between_the_two_direct_kernels(gpu):
+    """n = 300 is a tv_direct2 length at rho = 1 (two margins = 112) and too short for it at rho = 30 (480): one engine
+    through tv_direct2_kernel, tv_direct_kernel, tv_direct2_kernel -- buffer A made current again, the third state
+    buffer, the tile partials' capacity -- gives run by run what a fresh engine gives."""
+    L = gpu._lib
+    p = gpu.synth.tv_problem(0, 300)
+    make = lambda: gpu.Engine(L.PROB_TOTALVARIATION, s=p["s"], lam=p["lam"], nvec=300)
+    _one_engine_against_fresh_ones(L, "tv 300", make, [dict(rho=1.0), dict(rho=30.0), dict(rho=1.0)])
