@@ -175,6 +175,7 @@ _SIGNATURES = {
     "admm_engine_set_constraint_b": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int32,
                                                C.c_double, OPERATOR_CALLBACK, C.c_void_p]),
     "admm_engine_set_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, _dp]),
+    "admm_engine_set_tv2d_isotropic": (C.c_int, [C.c_void_p, C.c_int32]),
     "admm_engine_run": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(RunSummary)]),
     "admm_engine_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_engine_set_hooks": (C.c_int, [C.c_void_p, ALTU_CALLBACK, C.c_void_p, NORMS_CALLBACK, C.c_void_p]),
@@ -202,6 +203,7 @@ _SIGNATURES = {
     "admm_op_cholesky": (C.c_int, [_dp, C.c_int64, C.c_int64]),
     "admm_op_trsv_pair": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp]),
     "admm_op_soft_threshold": (C.c_int, [_dp, C.c_int64, C.c_double, _dp]),
+    "admm_op_pair_soft_threshold": (C.c_int, [_dp, C.c_int64, C.c_double, _dp]),
     "admm_op_group_soft_threshold": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_double, _dp]),
     "admm_op_symv": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp]),
     "admm_op_symv_batch": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int64, C.c_int64, _dp, C.c_int64]),

@@ -197,8 +197,13 @@ def getproxops(problem, args):
         if img.ndim != 2:
             raise ValueError("Argument s is not an image (2-D array)!")
         H, W = img.shape
+        iso = args.get("isotropic", 0)  # 0 / 1: the isotropic norm (engine-side extension)
+        if np.ndim(iso) != 0 or iso not in (0, 1):
+            raise L.AdmmError(L.E_INVALID, "args.isotropic must be the scalar 0 or 1")
         eng = Engine(L.PROB_TV2D, s=np.asfortranarray(img).reshape(-1, order="F"), lam=float(_get(args, "lambda")),
                      shape=(H, W), xsolve=xs, device=dev, **cg)
+        if iso:
+            eng.set_tv2d_isotropic(True)
         prob = _Problem("totalvariation2d", eng, dict(A="D", c=0.0, nA=H * W, nB=2 * H * W))
     elif kind == "basispursuit":
         if "P" in args:  # getProxOps.m:137-138: the projector and offset computed by the caller (basispursuit.m:116-120)

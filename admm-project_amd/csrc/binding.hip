@@ -20,6 +20,7 @@ struct admm_binding {
   std::vector<int64_t> slices;    // args.slices (getProxOps.m:387) as integers
   std::vector<int64_t> groups;    // args.groups: the group sizes of group lasso (admm_engine_set_groups)
   std::vector<double> groupweights;  // args.groupweights (one per group; empty: every weight 1), copied: apply runs after create
+  int32_t tv2d_isotropic = 0;     // args.isotropic of totalvariation2d (admm_engine_set_tv2d_isotropic)
   std::vector<double> zeros;      // c = 0 for the engines that take c as a data vector
   int64_t nA = 0, nB = 0;         // lengths of x and of z
   int64_t mC = 0;                 // length of u and c; 0 = the same as nB (every problem but a generic one with a general B)
@@ -189,6 +190,12 @@ int describe(const std::string& p, const View& args, const View& handles, admm_b
     d.m = S->rows;
     d.n = S->cols;
     d.lambda = args.scalar("lambda", 0.0);
+    if (args.get("isotropic")) {  // 0 / 1: the isotropic norm; anything else is refused
+      const admm_field* iso = args.get("isotropic");
+      if (!View::dense(iso) || iso->rows * iso->cols != 1 || (iso->data[0] != 0.0 && iso->data[0] != 1.0))
+        return fail(ADMM_E_INVALID, "args.isotropic must be the scalar 0 or 1");
+      b.tv2d_isotropic = static_cast<int32_t>(iso->data[0]);
+    }
     b.nA = d.m * d.n;
     b.nB = 2 * b.nA;
   } else if (p == "quadraticprogram" && !args.text_is("constraint", "standard")) {  // getProxOps.m:631-641
@@ -363,6 +370,7 @@ int admm_binding_apply(const admm_binding* b, admm_engine* e) {
   if (!b->groups.empty())
     ADMM_TRY(admm_engine_set_groups(e, b->groups.data(), static_cast<int32_t>(b->groups.size()),
                                     b->groupweights.empty() ? nullptr : b->groupweights.data()));
+  if (b->tv2d_isotropic) ADMM_TRY(admm_engine_set_tv2d_isotropic(e, 1));
   if (b->b_kind == 1 || b->b_kind == 2)
     return admm_engine_set_constraint_b(e, b->b_matrix, b->b_ld, b->b_kind == 2 ? b->nB : 0, ADMM_MEM_HOST, b->b_scalar,
                                         nullptr, nullptr);

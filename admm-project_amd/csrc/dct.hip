@@ -195,8 +195,8 @@ __device__ __forceinline__ void dct_cols_forward_body(double* __restrict__ img, 
 // (tv2d_pixel.h: the same arithmetic; x, v, s from global memory, the neighbours' reads are cache hits), drops b into
 // the FFT's LDS image at its Makhoul position, transforms, and stores the coefficients where the row stage expects
 // them.  Against the two kernels it replaces: one write and one read of the image less per iteration (11 N doubles
-// instead of 13 N), one launch less.
-template <bool VIN, bool ODDW>
+// instead of 13 N), one launch less.  ISO: the isotropic pixel (tv2d_pixel.h).
+template <bool VIN, bool ODDW, bool ISO>
 __global__ __launch_bounds__(kBlock) void tv2d_fused_dct_kernel(Tv2Args a, double* __restrict__ bhat, DctTables t,
                                                                 const Ctrl* __restrict__ ctrl) {
   if (ctrl->stop) return;
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kBlock) void tv2d_fused_dct_kernel(Tv2Args a, doubl
           const int64_t j = (!ODDW || j0 + c < W) ? j0 + c : j0;
           base[h][c] = j * H + r0;
           const int64_t lbase = j > 0 ? base[h][c] - H : base[h][c], rbase = j < W - 1 ? base[h][c] + H : base[h][c];
-          tv2px_load<VIN>(a, N, base[h][c], lbase, rbase, tid, o_up[h], o_dn[h], px[h][c]);
+          tv2px_load<VIN, ISO>(a, N, base[h][c], lbase, rbase, tid, o_up[h], o_dn[h], px[h][c]);
         }
       }
 #pragma unroll
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void tv2d_fused_dct_kernel(Tv2Args a, doubl
         for (int c = 0; c < 2; ++c) {
           const int64_t j = j0 + c;
           if (!ODDW || j < W) {  // (uniform)
-            const double bv = tv2px_apply<VIN>(a, N, it, base[h][c], tid, hasv[h], up[h], j < W - 1, j > 0, px[h][c], acc);
+            const double bv = tv2px_apply<VIN, ISO>(a, N, it, base[h][c], tid, hasv[h], up[h], j < W - 1, j > 0, px[h][c], acc);
             if (c == 0) bv0 = bv;
             reinterpret_cast<double*>(&zs[pos])[c] = bv;
           } else {
@@ -665,8 +665,11 @@ void launch_tv2d_fused_dct(const Tv2Args& a, bool state_in, double* bhat, const 
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nb)), dim3(kBlock), lds, stream, a, bhat, th, ctrl);
   };
   const bool odd = (a.W & 1) != 0;
-  if (state_in) odd ? go(tv2d_fused_dct_kernel<true, true>) : go(tv2d_fused_dct_kernel<true, false>);
-  else odd ? go(tv2d_fused_dct_kernel<false, true>) : go(tv2d_fused_dct_kernel<false, false>);
+  if (a.isotropic) {
+    if (state_in) odd ? go(tv2d_fused_dct_kernel<true, true, true>) : go(tv2d_fused_dct_kernel<true, false, true>);
+    else odd ? go(tv2d_fused_dct_kernel<false, true, true>) : go(tv2d_fused_dct_kernel<false, false, true>);
+  } else if (state_in) odd ? go(tv2d_fused_dct_kernel<true, true, false>) : go(tv2d_fused_dct_kernel<true, false, false>);
+  else odd ? go(tv2d_fused_dct_kernel<false, true, false>) : go(tv2d_fused_dct_kernel<false, false, false>);
 }
 
 void launch_dct_cols_forward_fin(double* img, int64_t H, int64_t W, const DctTables& th, const FinArgs& f,

@@ -136,6 +136,7 @@ struct admm_engine {
   double obj_bound_seen = 0.0;  // largest cancellation bound of the right-hand-side objective form over all runs
   double* gobjpart = nullptr;  // [kMaxPartBlocks + 2] Gram-form partials during calibration; last entry: max discrepancy
   bool tv2_dct = false;          // spectral x-update instead of CG: the column transform supports the height (dct.h)
+  int32_t tv2_isotropic = 0;     // admm_engine_set_tv2d_isotropic: the pair prox of the isotropic norm
   bool tv2_rows_dct = false;     // ... and the width is a power of two: the row DCT exists as the fall-back of the Toeplitz row stage
   DctTables dctH{}, dctW{};
   // 1-D / 2-D total variation: forward-sweep intermediate and its ping-pong partner, partners of z/u, LDL' pivot prefix

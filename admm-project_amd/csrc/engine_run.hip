@@ -589,6 +589,15 @@ int admm_engine_set_groups(admm_engine* e, const int64_t* sizes, int32_t ngroups
   return ADMM_OK;
 }
 
+int admm_engine_set_tv2d_isotropic(admm_engine* e, int32_t on) {
+  if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
+  if (e->problem != ADMM_PROB_TV2D)
+    return fail(ADMM_E_INVALID, "the isotropic norm belongs to 2-D total variation (ADMM_PROB_TV2D)");
+  if (on != 0 && on != 1) return fail(ADMM_E_INVALID, "isotropic must be 0 or 1");
+  e->tv2_isotropic = on;  // read by the next run (engine_run_tv.hip: run_total_variation_2d)
+  return ADMM_OK;
+}
+
 int admm_engine_run(admm_engine* e, const admm_options* opts, admm_run_summary* summary) {
   RunState rs{};
   admm_options& o = rs.o;

@@ -195,7 +195,7 @@ int run_tv2d_fast(admm_engine* e, RunState& rs, Tv2Args& ta, bool spectral, admm
   xa.u = e->tv_uA;
   xa.rhs = nullptr;
   pa.dz = e->dz;
-  pa.prox = PROX_SOFT;
+  pa.prox = ta.isotropic ? PROX_PAIR : PROX_SOFT;
   pa.t = e->lambda / o.rho;  // getProxOps.m:199
   pa.objz = OBJZ_NONE;
   pa.objx = OBJX_NONE;
@@ -209,6 +209,7 @@ int run_tv2d_fast(admm_engine* e, RunState& rs, Tv2Args& ta, bool spectral, admm
   fa.obj_scale_x = 0.0;
   fa.obj_scale_z = 0.0;
   fa.obj_scale_part = o.objevals ? 1.0 : 0.0;
+  if (pa.prox == PROX_PAIR && !prox_pair_ok(pa)) return fail(ADMM_E_INVALID, "the pair prox needs a vector of two halves");
   auto x_solve = [&]() -> int {
     ta.z = e->v;  // x = xminf(x, v, uhat, rho)   admm.m:506
     ta.u = e->uhat;
@@ -220,7 +221,7 @@ int run_tv2d_fast(admm_engine* e, RunState& rs, Tv2Args& ta, bool spectral, admm
   };
   auto dx = [&](int* nob) {
     launch_tv2d_dx(ta.H, ta.W, e->lambda, o.objevals, e->x, e->s, e->tmpA, e->objpart, nob, e->xhist, e->ctrl,
-                   e->stream);
+                   e->stream, ta.isotropic != 0);
   };
   auto dual = [&](int nblk) { launch_tv2d_dual_vec(ta.H, ta.W, e->dz, e->tv_uA, e->part, nblk, e->ctrl, e->stream); };
   ADMM_TRY(run_batches(e, rs.N, tv2d_poll_every(rs, spectral), [&](int32_t, bool) {
@@ -252,7 +253,8 @@ struct Tv2dPlainLoop {
     const double runtime = seconds_since(t0);
     const int32_t steps = e->ctrl_host->steps;
     if (steps > 0)  // z, u of the last executed iteration
-      launch_tv2d_expand((steps - 1) & 1 ? e->tv_uB : e->tv_zB, ta.thresh, rs.len, e->tv_zA, e->tv_uA, e->stream);
+      launch_tv2d_expand((steps - 1) & 1 ? e->tv_uB : e->tv_zB, ta.thresh, rs.len, e->tv_zA, e->tv_uA, e->stream,
+                         ta.isotropic != 0);
     return finish_tv2d(e, rs, runtime, summary);
   }
 
@@ -331,6 +333,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
   ta.s = e->s;
   ta.x = e->x;
   ta.objevals = o.objevals;
+  ta.isotropic = e->tv2_isotropic;  // admm_engine_set_tv2d_isotropic: the pair prox and the pair norms in S_OBJZ
   ta.xhist = e->xhist;
   ta.zhist = e->zhist;
   ta.uhist = e->uhist;
@@ -339,7 +342,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
   fa.x = nullptr;
   fa.xhist = nullptr;
   fa.dual_from_slots = 1;
-  if (o.objevals) {  // 1/2*||x - s||^2 + lambda*||D x||_1
+  if (o.objevals) {  // 1/2*||x - s||^2 + lambda*||D x||_1 (isotropic: lambda * the sum of the pair norms, the same scales)
     fa.obj_scale_x = 0.5;
     fa.obj_scale_z = e->lambda;
   }

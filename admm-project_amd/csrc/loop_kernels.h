@@ -15,6 +15,8 @@ enum ProxKind : int32_t {
   PROX_BOX = 4,    // min(ub,max(lb,v))                                1470-1474
   PROX_POS = 6,    // max(v, 0)   (CVX pos)                            1378-1382, 1422-1426
   PROX_LOGISTIC = 7,  // ell.*s, s - ell.*v = (C/rho)/(1 + e^s)  (prox_device.h: logistic_root)
+  PROX_PAIR = 8,   // isotropic 2-D TV: element k shrunk together with its partner at +-len/2 (tv2d_pixel.h:
+                   // tv2px_pair_shrink).  launch_prox only, an even len (prox_pair_ok)
   PROX_GIVEN = 5   // z was computed outside the fused kernel (a linear solve: zminModel 990-1013,
                    // or a caller-supplied zming callback) and is read from ProxArgs::zgiven
 };
@@ -200,6 +202,9 @@ void launch_ufix(const UFixArgs& a, const Ctrl* ctrl, hipStream_t stream);
 // a with the operands its variant (prox, objx, rhs_kind, alg) does not read set to null: ell, zgiven, lb / ub, rhs_add.
 // Every launcher of a kernel that inlines prox_load starts from this.
 ProxArgs pruned_prox_operands(const ProxArgs& a);
+// PROX_PAIR pairs the two halves of the vector: len must be even.  A caller checks this before launch_prox (which
+// returns nothing); c and relaxation go into both elements' v as for every other prox.
+inline bool prox_pair_ok(const ProxArgs& a) { return a.len > 0 && (a.len & 1) == 0; }
 void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream);
 // A = I, alg 0 / 1: z/u update AND the finalize logic in one launch (the last workgroup to arrive finalizes);
 // a.len <= 128 * kMaxPartBlocks

@@ -12,6 +12,7 @@
 #include "finalize_device.h"
 #include "prox_device.h"
 #include "group_device.h"
+#include "tv2d_pixel.h"
 #include "slot_reduce.h"
 
 namespace admm {
@@ -36,6 +37,38 @@ __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __
     const ProxIn in = prox_load(a, i);
     const double ax = gather_chunks(a.axsrc, a.naxpart, a.axld, i);
     prox_apply<LOGI>(a, i, ax, it, kcoef, in, acc);
+  }
+  __shared__ double sred[4][S_COUNT];
+  block_reduce_slots<4>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
+}
+
+// PROX_PAIR: prox_kernel with the pair shrink of isotropic 2-D TV as the z-prox.  One thread per PAIR: it loads the
+// inputs of element k and of its partner k + len/2, shrinks once and runs prox_apply for both with z in ProxIn::zg_i
+// (PROX_GIVEN from a register).  No thread reads what another one writes in this launch -- fast ADMM (alg 1) stores the
+// extrapolated v, uhat in place from prox_apply -- and both elements of a pair get one scale.
+__global__ __launch_bounds__(kBlock) void pair_prox_kernel(ProxArgs a, const Ctrl* __restrict__ ctrl) {
+  const int32_t stop = ctrl->stop;
+  const int64_t it = ctrl->iter;
+  const double aprev = ctrl->acurr;
+  if (stop) return;
+  double acc[S_COUNT];
+#pragma unroll
+  for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
+  double kcoef = 0.0;
+  if (a.alg == 1) {
+    const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
+    kcoef = (aprev - 1.0) / acn;
+  }
+  const int64_t half = a.len >> 1;
+  for (int64_t k = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; k < half;
+       k += static_cast<int64_t>(gridDim.x) * kBlock) {
+    ProxIn in0 = prox_load(a, k), in1 = prox_load(a, k + half);
+    const double ax0 = gather_chunks(a.axsrc, a.naxpart, a.axld, k);
+    const double ax1 = gather_chunks(a.axsrc, a.naxpart, a.axld, k + half);
+    double u0, u1;  // (prox_apply forms u its own way, as for every other prox)
+    tv2px_pair_shrink(group_prox_v(a, ax0, in0), group_prox_v(a, ax1, in1), a.t, in0.zg_i, in1.zg_i, u0, u1);
+    prox_apply<false>(a, k, ax0, it, kcoef, in0, acc);
+    prox_apply<false>(a, k + half, ax1, it, kcoef, in1, acc);
   }
   __shared__ double sred[4][S_COUNT];
   block_reduce_slots<4>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
@@ -127,6 +160,14 @@ ProxArgs pruned_prox_operands(const ProxArgs& args) {
 
 void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
   const ProxArgs a = pruned_prox_operands(args);
+  if (a.prox == PROX_PAIR) {  // one thread per pair; len is even (prox_pair_ok: the caller has checked)
+    ProxArgs ap = a;
+    ap.prox = PROX_GIVEN;  // z reaches prox_apply in a register
+    const int pblocks = grid_blocks(a.len / 2, kBlock, kMaxPartBlocks);
+    *nblk_out = pblocks;
+    hipLaunchKernelGGL(pair_prox_kernel, dim3(pblocks), dim3(kBlock), 0, stream, ap, ctrl);
+    return;
+  }
   const int blocks = grid_blocks(a.len, kBlock, kMaxPartBlocks);
   *nblk_out = blocks;
   if (prox_is_logistic(a))

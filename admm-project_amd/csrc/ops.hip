@@ -6,6 +6,7 @@
 
 #include "kernels.h"
 #include "loop_kernels.h"
+#include "tv2d.h"
 
 using namespace admm;
 
@@ -191,6 +192,20 @@ int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out) {
                      dout);
   ADMM_HIP_TRY(hipDeviceSynchronize());
   ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
+int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* out) {
+  if (!v || !out || N <= 0 || !(t >= 0.0)) return fail(ADMM_E_INVALID, "pair_soft_threshold: bad argument");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dv, *dout;
+  ADMM_TRY(sc.alloc(&dv, 2 * N));
+  ADMM_TRY(sc.alloc(&dout, 2 * N));
+  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+  launch_tv2d_pair_soft_threshold(dv, N, t, dout, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * 2 * N, hipMemcpyDeviceToHost));
   return ADMM_OK;
 }
 

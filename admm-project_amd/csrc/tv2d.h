@@ -10,6 +10,9 @@ namespace admm {
 //   (Dv x)[i,j] = x[i,j] - x[i+1,j]   (i < H-1, else 0)      first  N rows
 //   (Dh x)[i,j] = x[i,j] - x[i,j+1]   (j < W-1, else 0)      second N rows
 // so z, u have 2N elements and D'D is the 5-point Neumann Laplacian.
+// The penalty is lambda*||D x||_1 (anisotropic), or with `isotropic` lambda * sum_k sqrt((Dx)[k]^2 + (Dx)[N+k]^2): the
+// z-update is then the block soft threshold of the pairs (k, N + k), k = 0 .. N-1 (tv2d_pixel.h: tv2px_pair_shrink),
+// and everything else -- D, the x-update, the u-update, the residuals -- is the same.
 struct Tv2Args {
   int64_t H, W;
   double rho, thresh;      // thresh = lambda/rho
@@ -19,6 +22,7 @@ struct Tv2Args {
   const double* u;
   double* zo;              // next compact state v = z + u (2N, written by the fused kernel; ping-pong)
   int32_t objevals;
+  int32_t isotropic;       // the pair prox and the pair norm in S_OBJZ
   double* xhist;
   double* zhist;
   double* uhist;
@@ -41,13 +45,18 @@ void launch_tv2d_rhs(const Tv2Args& a, double* b, const Ctrl* ctrl, hipStream_t 
 // first iteration), true reads v from a.z; a.zo receives the new v either way.
 void launch_tv2d_fused(const Tv2Args& a, bool state_in, double* bnext, const Ctrl* ctrl, int* nblk_out,
                        hipStream_t stream);
-// z = soft(v, thresh), u = v - z   (len = 2N): the iterates behind a compact state
-void launch_tv2d_expand(const double* v, double thresh, int64_t len, double* z, double* u, hipStream_t stream);
+// z = soft(v, thresh), u = v - z   (len = 2N): the iterates behind a compact state; isotropic: z = the pair shrink of
+// (v[k], v[len/2 + k])
+void launch_tv2d_expand(const double* v, double thresh, int64_t len, double* z, double* u, hipStream_t stream,
+                        bool isotropic = false);
+// out = the pair shrink of v (2N device elements, halves paired): the stand-alone operator (ops.hip)
+void launch_tv2d_pair_soft_threshold(const double* v, int64_t N, double t, double* out, hipStream_t stream);
 
 // Unfused building blocks for the fast / accelerated ADMM variants: ax = D*x (2N) with the objective in block partials
 // and the x history column; the D' stencils of the dual residual / tolerance from dz = z - zprev and u
 void launch_tv2d_dx(int64_t H, int64_t W, double lambda, int objevals, const double* x, const double* s, double* ax,
-                    double* objpart, int* nobj_out, double* xhist, const Ctrl* ctrl, hipStream_t stream);
+                    double* objpart, int* nobj_out, double* xhist, const Ctrl* ctrl, hipStream_t stream,
+                    bool isotropic = false);
 void launch_tv2d_dual_vec(int64_t H, int64_t W, const double* dz, const double* u, double* part, int nblk,
                           const Ctrl* ctrl, hipStream_t stream);
 

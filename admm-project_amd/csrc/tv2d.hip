@@ -1,14 +1,17 @@
-// tv2d.hip -- 2-D anisotropic total-variation ADMM kernels (engine-side extension of totalvariation.m to the
+// tv2d.hip -- 2-D total-variation ADMM kernels, anisotropic and isotropic (engine-side extension of totalvariation.m to the
 // "4096 x 4096 image, matrix-free x-update" of BASELINE config 5; the reference's solver is 1-D).
 //
 //   minimise 1/2*||x - s||^2 + lambda*||D x||_1,   D = [Dv; Dh]  (vertical / horizontal forward differences)
 //   x-update   (I + rho*D'D) x = s + rho*D'(z - u)      5-point Neumann Laplacian: warm-started CG (cg.hip),
 //                                                       the operator is the stencil below, nothing is stored
 //   z-update   z = soft(u + D x, lambda/rho);  u += D x - z       (getProxOps.m:199 / admm.m:548, c = 0)
+//   isotropic  lambda * sum_k ||((Dx)[k], (Dx)[N+k])||_2 in place of the l1 norm: z = the pair shrink of u + D x
+//              (tv2d_pixel.h: tv2px_pair_shrink), the rest unchanged
 // Everything is a streaming stencil over the image; neighbour reads hit L2.
 #include "kernels.h"
 #include "loop_kernels.h"
 #include "tv2d.h"
+#include "tv2d_pixel.h"
 #include "slot_reduce.h"
 
 namespace admm {
@@ -121,9 +124,10 @@ __device__ __forceinline__ double tv2_clamp(double v, double t) {
 // 11N with z and u stored apart (and 9N + 6N + 6N for separate prox, dual and rhs kernels).  VIN = false is a run's
 // first iteration: z, u come from the engine's iterates as given (warm starts need not satisfy z = soft(z + u)).
 // launch_tv2d_expand writes z, u back out of the last v when the run ends.
+// ISO: the same walk with the isotropic pixel of tv2d_pixel.h (four more cache-hit loads).
 constexpr int kTv2Tile = 256;      // rows of a column per workgroup step of the fused pass
 constexpr int kTv2Resident = 4;    // workgroups per CU (512-row tiles with 3 per CU, 6 waves per SIMD: 201 against 196 us)
-template <bool VIN>
+template <bool VIN, bool ISO>
 __global__ __launch_bounds__(kTv2Tile, kTv2Resident * kTv2Tile / 256) void tv2d_fused_kernel(Tv2Args a, double* __restrict__ bnext,
                                                             const Ctrl* __restrict__ ctrl) {
   if (ctrl->stop) return;
@@ -154,6 +158,12 @@ __global__ __launch_bounds__(kTv2Tile, kTv2Resident * kTv2Tile / 256) void tv2d_
     const uint32_t o_up = up ? tid : tid + 1;   // relative to the element before the tile: own row when there is none
     const uint32_t o_dn = hasv ? tid + 1 : tid;
     const int64_t lbase = left ? base - H : base, rbase = hash ? base + H : base;
+    if (ISO) {
+      Tv2Px px;
+      tv2px_load<VIN, true>(a, N, base, lbase, rbase, tid, o_up, o_dn, px);
+      (bnext + base)[tid] = tv2px_apply<VIN, true>(a, N, it, base, tid, hasv, up, hash, left, px, acc);
+      continue;
+    }
     const double* __restrict__ xc = a.x + base;
     const double* __restrict__ zc = a.z + base;  // VIN: v
     const double xi = xc[tid], x_dn = xc[o_dn], x_up = (xc - 1)[o_up];
@@ -254,14 +264,44 @@ __global__ __launch_bounds__(kBlock) void tv2d_expand_kernel(const double* __res
   }
 }
 
-void launch_tv2d_expand(const double* v, double thresh, int64_t len, double* z, double* u, hipStream_t stream) {
+// the pair form: elements k and N + k together (z, u of the isotropic state; u = nullptr: the operator, z alone)
+__global__ __launch_bounds__(kBlock) void tv2d_expand_pair_kernel(const double* __restrict__ v, double t, int64_t N,
+                                                                  double* __restrict__ z, double* __restrict__ u) {
+  for (int64_t k = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; k < N;
+       k += static_cast<int64_t>(gridDim.x) * kBlock) {
+    double z0, z1, u0, u1;
+    tv2px_pair_shrink(v[k], v[N + k], t, z0, z1, u0, u1);
+    z[k] = z0;
+    z[N + k] = z1;
+    if (u) {
+      u[k] = u0;
+      u[N + k] = u1;
+    }
+  }
+}
+
+void launch_tv2d_expand(const double* v, double thresh, int64_t len, double* z, double* u, hipStream_t stream,
+                        bool isotropic) {
+  if (isotropic) {
+    const int blocks = grid_blocks(len / 2, kBlock, 16384);
+    hipLaunchKernelGGL(tv2d_expand_pair_kernel, dim3(blocks), dim3(kBlock), 0, stream, v, thresh, len / 2, z, u);
+    return;
+  }
   const int blocks = grid_blocks(len, kBlock, 16384);
   hipLaunchKernelGGL(tv2d_expand_kernel, dim3(blocks), dim3(kBlock), 0, stream, v, thresh, len,
                      z, u);
 }
 
+void launch_tv2d_pair_soft_threshold(const double* v, int64_t N, double t, double* out, hipStream_t stream) {
+  const int blocks = grid_blocks(N, kBlock, 16384);
+  hipLaunchKernelGGL(tv2d_expand_pair_kernel, dim3(blocks), dim3(kBlock), 0, stream, v, t, N, out,
+                     static_cast<double*>(nullptr));
+}
+
 // ---- building blocks of the fast / accelerated ADMM variants (the generic prox kernel does z, u, v, uhat)
 // ax = D*x as a 2N-vector, the objective 1/2||x - s||^2 + lambda*||D x||_1 in block partials, the x history column
+// (ISO: lambda * the pair norms in place of the l1 norm)
+template <bool ISO>
 __global__ __launch_bounds__(kBlock) void tv2d_dx_kernel(int64_t H, int64_t W, double lambda, int objevals,
                                                          const double* __restrict__ x, const double* __restrict__ s,
                                                          double* __restrict__ ax, double* __restrict__ objpart,
@@ -280,7 +320,8 @@ __global__ __launch_bounds__(kBlock) void tv2d_dx_kernel(int64_t H, int64_t W, d
     ax[N + idx] = dh;
     if (objevals) {
       const double e = xi - s[idx];
-      acc += 0.5 * (e * e) + lambda * (fabs(dv) + fabs(dh));
+      if (ISO) acc += 0.5 * (e * e) + lambda * tv2px_pair_norm(dv, dh);
+      else acc += 0.5 * (e * e) + lambda * (fabs(dv) + fabs(dh));
     }
     if (xhist) xhist[it * N + idx] = xi;
   }
@@ -289,11 +330,13 @@ __global__ __launch_bounds__(kBlock) void tv2d_dx_kernel(int64_t H, int64_t W, d
 }
 
 void launch_tv2d_dx(int64_t H, int64_t W, double lambda, int objevals, const double* x, const double* s, double* ax,
-                    double* objpart, int* nobj_out, double* xhist, const Ctrl* ctrl, hipStream_t stream) {
+                    double* objpart, int* nobj_out, double* xhist, const Ctrl* ctrl, hipStream_t stream, bool isotropic) {
   const int nb = tv2_blocks(H * W);
   *nobj_out = nb;
-  hipLaunchKernelGGL(tv2d_dx_kernel, dim3(nb), dim3(kBlock), 0, stream, H, W, lambda, objevals, x, s, ax, objpart, xhist,
-                     ctrl);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, stream, H, W, lambda, objevals, x, s, ax, objpart, xhist, ctrl);
+  };
+  isotropic ? go(tv2d_dx_kernel<true>) : go(tv2d_dx_kernel<false>);
 }
 
 // ||D'dz||^2 (admm.m:624, 632) and ||D'u||^2 (admm.m:654) from the vectors dz = z - zprev and u, into the S_G2 / S_G3
@@ -337,8 +380,9 @@ void launch_tv2d_fused(const Tv2Args& a, bool state_in, double* bnext, const Ctr
   if (cap > kMaxPartBlocks) cap = kMaxPartBlocks;
   const int nb = static_cast<int>(tiles < cap ? tiles : cap);
   *nblk_out = nb;
-  if (state_in) hipLaunchKernelGGL(tv2d_fused_kernel<true>, dim3(nb), dim3(kTv2Tile), 0, stream, a, bnext, ctrl);
-  else hipLaunchKernelGGL(tv2d_fused_kernel<false>, dim3(nb), dim3(kTv2Tile), 0, stream, a, bnext, ctrl);
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nb), dim3(kTv2Tile), 0, stream, a, bnext, ctrl); };
+  if (a.isotropic) state_in ? go(tv2d_fused_kernel<true, true>) : go(tv2d_fused_kernel<false, true>);
+  else state_in ? go(tv2d_fused_kernel<true, false>) : go(tv2d_fused_kernel<false, false>);
 }
 
 void launch_tv2d_laplace(int64_t H, int64_t W, double rho, const double* p, double* w, const Ctrl* ctrl,

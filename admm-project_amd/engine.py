@@ -412,6 +412,12 @@ class Engine:
         L.check(self._lib.admm_engine_set_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_int64)), g.size,
                                                  None if w is None else L.as_dp(w)))
 
+    def set_tv2d_isotropic(self, on=True):
+        """Isotropic 2-D total variation (admm_engine_set_tv2d_isotropic): the z-prox of a TV2D engine becomes the block
+        soft threshold of each pixel's pair of differences (the Rudin-Osher-Fatemi norm); ``False`` restores the
+        anisotropic l1 prox."""
+        L.check(self._lib.admm_engine_set_tv2d_isotropic(self._h, int(on)))
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None):

@@ -502,11 +502,17 @@ def totalvariation(s, lam, options=None):
 
 def totalvariation2d(S, lam, options=None):
     """results = totalvariation2d(S, lambda, options) -- engine-side extension (the reference's
-    totalvariation.m is 1-D): anisotropic TV denoising of an image,
+    totalvariation.m is 1-D): TV denoising of an image, anisotropic by default,
 
         minimise 1/2*||X - S||_F^2 + lambda*(sum|X[i+1,j] - X[i,j]| + sum|X[i,j+1] - X[i,j]|),
 
-    as ADMM on D*x - z = 0 with D = [Dv; Dh] (2N x N forward differences, x = X(:) column-major).  The
+    or with ``options['isotropic'] = 1`` the isotropic (Rudin-Osher-Fatemi) norm, which does not favour axis-aligned edges,
+
+        minimise 1/2*||X - S||_F^2 + lambda*sum_ij sqrt((X[i+1,j] - X[i,j])^2 + (X[i,j+1] - X[i,j])^2)
+
+    (a difference that leaves the image counts as 0) -- as ADMM on D*x - z = 0 with D = [Dv; Dh] (2N x N forward
+    differences, x = X(:) column-major).  The isotropic z-update shrinks each pixel's pair of differences as a block;
+    everything else is shared.  The
     x-update (I + rho*D'D) x = s + rho*D'(z - u) is solved spectrally where the height has a column transform (8 to
     4096 rows, or a power of two up to 8192): column DCT, a row stage (Toeplitz kernel, row DCT or exact tridiagonal
     solve, whichever applies to this width and rho), inverse column DCT -- and matrix-free by warm-started CG otherwise
@@ -528,6 +534,8 @@ def totalvariation2d(S, lam, options=None):
     N = H * W
     args = _engine_args(options, dict(s=img))
     args["lambda"] = float(np.real(lam))
+    if "isotropic" in options:
+        args["isotropic"] = options.pop("isotropic")
     xmin, zmin, _ = getproxops("TotalVariation2D", args)
     options.update(A=_ShapeOnly((2 * N, N)), At=None, B=-1, nA=N, nB=2 * N, c=0, m=2 * N)
     options["obj"] = _ENGINE_OBJ

@@ -61,8 +61,8 @@ enum {
   ADMM_PROB_BASISPURSUIT = 8,     /* getProxOps.m:98-142, 1027-1032 */
   ADMM_PROB_LINEARPROGRAM = 10,   /* getProxOps.m:459-542, x: 1357-1366 (KKT solve), z: 1378-1382 */
   ADMM_PROB_QP_STANDARD = 11,     /* getProxOps.m:624-630, x: 1397-1412 (KKT solve), z: 1422-1426 */
-  ADMM_PROB_TV2D = 12,            /* engine-side extension: 2-D anisotropic TV of an m x n image (D = [Dv; Dh] forward
-                                     differences); x-update of I + rho*D'D spectral (column DCT + row stage) where the
+  ADMM_PROB_TV2D = 12,            /* engine-side extension: 2-D TV of an m x n image (D = [Dv; Dh] forward
+                                     differences), anisotropic or -- admm_engine_set_tv2d_isotropic -- isotropic; x-update of I + rho*D'D spectral (column DCT + row stage) where the
                                      height has a column transform, matrix-free CG otherwise or with ADMM_XSOLVE_CG; no
                                      reference counterpart (totalvariation.m is 1-D) -- BASELINE config 5 as literally written */
   ADMM_PROB_COVSEL = 13,          /* getProxOps.m:669-750 (z: soft threshold lambda/rho, 745-750), x: 1487-1495
@@ -324,6 +324,15 @@ int admm_engine_set_constraint_b(admm_engine* eng, const double* B, int64_t ldB,
  * other problem (consensus lasso included), a row-sharded engine.  One group of n elements is one workgroup walking
  * all of them twice per iteration: correct, slow. */
 int admm_engine_set_groups(admm_engine* eng, const int64_t* sizes, int32_t ngroups, const double* weights);
+/* Isotropic 2-D total variation (engine-side extension: DESIGN.md q31): with on = 1 an ADMM_PROB_TV2D engine minimises
+ * 1/2*||x - s||^2 + lambda * sum_k sqrt((Dx)[k]^2 + (Dx)[N+k]^2), k over the N pixels (the Rudin-Osher-Fatemi norm),
+ * instead of the anisotropic lambda*||Dx||_1.  Only the z-update changes: for every pixel k -- those of the last image
+ * row / column, whose row of D is zero, included -- the pair v = (u + Dx)[k], (u + Dx)[N+k] is shrunk as a block,
+ * z = v * (||v|| > t ? 1 - t/||v|| : 0), t = lambda/rho, u+ = v - z; objevals reports the objective above.  D, the
+ * x-update (spectral or CG), the residuals, every option and fast / accelerated ADMM stay as they are; relaxation stays
+ * the dimension error it is.  on = 0 (the default) restores the anisotropic prox, bit for bit.  ADMM_E_INVALID: any
+ * other problem, on outside {0, 1}. */
+int admm_engine_set_tv2d_isotropic(admm_engine* eng, int32_t on);
 int admm_engine_run(admm_engine* eng, const admm_options* opts, admm_run_summary* summary);
 int admm_engine_fetch(admm_engine* eng, int field, double* dst, size_t cap, size_t* written);
 /* what create() decided about the x-update factor (first slice for consensus lasso) */
@@ -466,6 +475,9 @@ int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out);
  * 6.4.2; admm_engine_set_groups), the same device code over the same workgroup plan as the loop's element update */
 int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups,
                                  const double* weights, double lambda_over_rho, double* out);
+/* out = the pair shrink of isotropic 2-D total variation (admm_engine_set_tv2d_isotropic) over a 2N-vector whose halves
+ * are paired: (out[k], out[N+k]) = (v[k], v[N+k]) * (||.|| > t ? 1 - t/||.|| : 0); the device function of the loop */
+int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* out);
 /* y = M*x for a symmetric n x n M by the kernels of the explicit-inverse x-update (getProxOps.m:1200).  form selects
  * the launcher: 0 = the small form (one wave per column; reads FULL storage, ldM must be even), 1 = the 128 x 128 tile
  * kernel on padded column-major storage, 2 = the same on tile-packed storage, 3 = the tile-packed launch that carries
