@@ -8,10 +8,10 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "tri_tile.h"  // double2_t
 
 namespace admm {
 
-typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 16;

@@ -926,7 +926,7 @@ int admm_engine_info(admm_engine* e, admm_engine_info_t* info) {
   info->probe_diff = f->probed ? f->probe_diff : NAN;
   // what one iteration's x-solve reads, by cache policy (symv.hip / trsv.hip: tiles below ncached use default loads)
   auto tally = [&](const SliceFactor& s) {
-    const int64_t tile_bytes = int64_t{8} * 128 * 128;  // kSyTile = kTsTile = 128
+    const int64_t tile_bytes = int64_t{8} * 128 * 128;  // kTile (tri_tile.h)
     if (s.mode == ADMM_XSOLVE_INVERSE && s.Minv && s.n >= kSymvHalfMin) {
       const int64_t tiles = symv_tiles(s.planSy);
       const int64_t cached = std::min<int64_t>(tiles, std::max<int64_t>(0, s.planSy.ncached));

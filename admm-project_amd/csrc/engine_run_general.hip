@@ -16,7 +16,7 @@ struct AxSource {
 
 int factor_x_update(admm_engine* e, AxSource* ax, bool leave_partials);
 
-// the one-block triangular solves (symv.hip: tri1_*) leave the backward pass's partial rows to the one-launch tail
+// the one-block triangular solves (trsv.hip: tri1_*) leave the backward pass's partial rows to the one-launch tail
 bool xsolve_tri1_partials(const admm_engine* e) {
   return e->xfac.mode == ADMM_XSOLVE_TRSV && e->xfac.trsv.one && !e->xcb && e->xsolve != ADMM_XSOLVE_CG && !e->fat &&
          (e->problem == ADMM_PROB_LASSO || e->problem == ADMM_PROB_QP_BOUNDED);

@@ -11,10 +11,10 @@
 // results are bitwise reproducible (no float atomics).
 #include "finalize_device.h"
 #include "kernels.h"
+#include "slot_reduce.h"
+#include "tri_tile.h"
 
 namespace admm {
-
-typedef double double2_t __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------------------------
 // gemv_n: thread owns a pair of rows, loops over the columns of its chunk.
@@ -268,32 +268,29 @@ void launch_gemv_t(const GemvTPlan& p, const double* D, const double* v0, const 
 #undef ADMM_LAUNCH_GEMV_T
 }
 
-// g[r][j] = sum_c gpart[c][r][j].  Workgroup = 16 consecutive columns x 16 slots that split the chunk
-// index; the slots are combined through LDS in a fixed order (bitwise reproducible).  A serial loop over
-// the chunks per column (the first version) cost 30 us at 235 chunks -- a fifth of an SVM 60000x400 iteration.
-__global__ __launch_bounds__(kBlock) void sum_partials_t_kernel(const double* __restrict__ gpart, int32_t nchunk,
-                                                                int nrhs, int64_t ldg, int64_t n,
-                                                                double* __restrict__ g, int64_t ldg_out,
-                                                                const Ctrl* __restrict__ ctrl) {
-  if (ctrl && ctrl->stop) return;
-  __shared__ double sacc[16][17];
-  const int jj = threadIdx.x & 15, slot = threadIdx.x >> 4;
+// g[r][j] = sum_c gpart[c][r][j].  The 16 slots of a workgroup split the chunk index (slot_reduce.h:
+// fold_slots_store; bitwise reproducible).  A serial loop over the chunks per column (the first version) cost 30 us
+// at 235 chunks -- a fifth of an SVM 60000x400 iteration.
+__device__ __forceinline__ void sum_partials_t_body(const double* __restrict__ gpart, int32_t nchunk, int nrhs,
+                                                    int64_t ldg, int64_t n, double* __restrict__ g, int64_t ldg_out) {
+  const int slot = threadIdx.x >> 4;
   const int64_t tiles_per_rhs = (n + 15) / 16;
   const int r = static_cast<int>(blockIdx.x / tiles_per_rhs);
-  const int64_t j = (blockIdx.x - static_cast<int64_t>(r) * tiles_per_rhs) * 16 + jj;
+  const int64_t j = (blockIdx.x - static_cast<int64_t>(r) * tiles_per_rhs) * 16 + (threadIdx.x & 15);
   double s = 0.0;
   if (j < n) {
 #pragma unroll 4
     for (int32_t c = slot; c < nchunk; c += 16) s += gpart[(static_cast<int64_t>(c) * nrhs + r) * ldg + j];
   }
-  sacc[slot][jj] = s;
-  __syncthreads();
-  if (slot == 0 && j < n) {
-    double t = sacc[0][jj];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += sacc[k][jj];
-    g[r * ldg_out + j] = t;
-  }
+  fold_slots_store(s, g, r * ldg_out + j, j < n);
+}
+
+__global__ __launch_bounds__(kBlock) void sum_partials_t_kernel(const double* __restrict__ gpart, int32_t nchunk,
+                                                                int nrhs, int64_t ldg, int64_t n,
+                                                                double* __restrict__ g, int64_t ldg_out,
+                                                                const Ctrl* __restrict__ ctrl) {
+  if (ctrl && ctrl->stop) return;
+  sum_partials_t_body(gpart, nchunk, nrhs, ldg, n, g, ldg_out);
 }
 
 // the same with a passenger: the last workgroup runs the deferred finalize logic of the iteration whose element update
@@ -307,24 +304,7 @@ __global__ __launch_bounds__(kBlock) void sum_partials_t_fin_kernel(const double
     finalize_body<false>(f);
     return;
   }
-  __shared__ double sacc[16][17];
-  const int jj = threadIdx.x & 15, slot = threadIdx.x >> 4;
-  const int64_t tiles_per_rhs = (n + 15) / 16;
-  const int r = static_cast<int>(blockIdx.x / tiles_per_rhs);
-  const int64_t j = (blockIdx.x - static_cast<int64_t>(r) * tiles_per_rhs) * 16 + jj;
-  double s = 0.0;
-  if (j < n) {
-#pragma unroll 4
-    for (int32_t c = slot; c < nchunk; c += 16) s += gpart[(static_cast<int64_t>(c) * nrhs + r) * ldg + j];
-  }
-  sacc[slot][jj] = s;
-  __syncthreads();
-  if (slot == 0 && j < n) {
-    double t = sacc[0][jj];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += sacc[k][jj];
-    g[r * ldg_out + j] = t;
-  }
+  sum_partials_t_body(gpart, nchunk, nrhs, ldg, n, g, ldg_out);
 }
 
 void launch_sum_partials_t_fin(const GemvTPlan& p, const double* gpart, int nrhs, double* g, int64_t ldg_out,

@@ -18,8 +18,6 @@
 
 namespace admm {
 
-typedef double double2_t __attribute__((ext_vector_type(2)));
-
 __global__ __launch_bounds__(kBlock) void jacobi_round_kernel(double* __restrict__ B, int64_t ldb,
                                                               double* __restrict__ V, int64_t ldv, int32_t n,
                                                               int32_t ne, int32_t round, double tol, double null2,

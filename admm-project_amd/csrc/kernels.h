@@ -109,7 +109,7 @@ struct TrsvPlan {
   double* P[2];              // [bt][npad] column-tile partials: the step in flight and the previous one
   double *v, *w;             // running right-hand sides (npad)
   bool streaming;            // non-temporal matrix loads (matrix larger than the caches)
-  // one-block form (symv.hip: tri1_*): the whole factor as ONE pre-inverted block, X = inv(L) tile-packed, applied as
+  // one-block form (tri1_*): the whole factor as ONE pre-inverted block, X = inv(L) tile-packed, applied as
   // w = X y (N-part pass + fold) and x = X' w (T-part pass): 3 launches per pair.  When built, Fm / Um / P above
   // are absent (nblk = 1 and they would be the same matrix twice).
   bool one;
@@ -151,6 +151,9 @@ size_t trsv_plan_elems(int64_t n, int form = kTrsvBlocked);
 int trsv_build(const double* L, int64_t n, int64_t ldl, const double* dinv64, double* buf, TrsvPlan* plan,
                hipStream_t stream, int form = kTrsvBlocked);
 void launch_trsv_pair(const TrsvPlan& p, const double* y, double* x, const Ctrl* ctrl, hipStream_t stream);
+// P <- the ntri 128 x 128 tiles of a triangle of the padded column-major M (ld), back to back in row-major triangle
+// order: tile t = (bi, bj), bi >= bj, is M's tile (bi, bj) (upper = 0) or (bj, bi) (upper = 1)
+void launch_tri_pack(const double* M, int64_t ld, double* P, unsigned ntri, int upper, hipStream_t stream);
 
 // ---------------------------------------------------------------- symmetric eigen-decomposition (jacobi.hip)
 // W (n x n symmetric PSD, FULL storage) is overwritten by W*V; V gets the eigenvectors, lam_host the eigenvalues

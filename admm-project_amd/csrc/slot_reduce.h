@@ -1,4 +1,5 @@
-// slot_reduce.h -- the block reduction of the S_COUNT residual slots every element-update kernel ends with.
+// slot_reduce.h -- the block reduction of the S_COUNT residual slots every element-update kernel ends with, and the
+// fixed-order fold of partial rows behind the x-solves and the transposed GEMV.
 #pragma once
 #include "loop_kernels.h"
 
@@ -32,6 +33,23 @@ __device__ __forceinline__ void block_reduce_slots(const double (&acc)[S_COUNT],
   __syncthreads();
   const int s = threadIdx.x;
   if (s < S_COUNT) part[s * stride + block] = slot_total<WAVES>(sred, s);
+}
+
+// The fold of partial ROWS (symv.hip, trsv.hip, gemv.hip): a workgroup of kBlock threads = 16 consecutive elements
+// (threadIdx & 15) x 16 slots (threadIdx >> 4) that split the partial rows of an element.  Every thread hands in the sum
+// s of its slot's rows (each kernel has its own loop over them); the slots are added through LDS in slot order and the
+// slot-0 thread of a live element stores out[i].  Bitwise reproducible.
+__device__ __forceinline__ void fold_slots_store(double s, double* __restrict__ out, int64_t i, bool live) {
+  __shared__ double sacc[16][17];
+  const int ii = threadIdx.x & 15, slot = threadIdx.x >> 4;
+  sacc[slot][ii] = s;
+  __syncthreads();
+  if (slot == 0 && live) {
+    double t = sacc[0][ii];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) t += sacc[k][ii];
+    out[i] = t;
+  }
 }
 
 }  // namespace admm

@@ -25,104 +25,18 @@
 // (r2: 8-column panels -- 16 loads in flight, a three-level reduce-scatter ending in row_half_mirror -- measured
 // slower than this 4-column form: 78.4 vs 76.5 us event-timed per pass.  A pure N-part pass over the same tiles,
 // tri_step_kernel in trsv.hip, streams at 6.0 TB/s, so the T-part's cross-lane work is what holds this kernel at 5.4.)
+// The tile pass itself (SyLane, sy_tile) is in tri_tile.h: the backward pass of the one-block triangular solve
+// (trsv.hip: tri1_backward_kernel) is its T-part alone.
 
 #include "finalize_device.h"
 #include "kernels.h"
-#include "wave_reduce.h"
+#include "slot_reduce.h"
+#include "tri_tile.h"
 
 namespace admm {
 
-typedef double double2_t __attribute__((ext_vector_type(2)));
-
-constexpr int kSyTile = 128;  // rows per wave (64 lanes x 2) = columns per tile
-// (kSyPanel = 4 columns per panel = loads per buffer = T-part accumulators: wave_reduce.h)
-
-struct SyLane {  // per-lane constants of a tile
-  const double* M;
-  const double* x;
-  int64_t ld, n;
-  int r;  // this lane's row pair (r, r+1), also its element offset from a column base
-  double xr0, xr1;
-};
-
-template <bool NT>
-__device__ __forceinline__ void sy_load(const SyLane& s, int64_t cp, double2_t (&d)[kSyPanel]) {
-#pragma unroll
-  for (int k = 0; k < kSyPanel; ++k) d[k] = load2<NT>(s.M + (cp + k) * s.ld + s.r);  // wave-uniform column base
-}
-
-// DIAG: the tile intersects the diagonal -> mask element-wise (N-part j <= row, T-part row > j)
-// NP / TP: which of the two uses of an element are taken (both for the symmetric product; one each for the two
-// passes over a triangular inverse further down, whose diagonal tiles store their zeros: DIAG = false there)
-template <bool DIAG, bool NP = true, bool TP = true>
-__device__ __forceinline__ void sy_compute(const SyLane& s, int64_t cp, const double2_t (&d)[kSyPanel], double& n0,
-                                           double& n1, double* __restrict__ tout, int lane) {
-  double tacc[kSyPanel];
-#pragma unroll
-  for (int k = 0; k < kSyPanel; ++k) {
-    const int64_t j = cp + k;
-    const double xj = NP ? s.x[j < s.n ? j : s.n - 1] : 0.0;  // wave-uniform -> scalar load; padding columns are 0
-    double a0 = d[k].x, a1 = d[k].y;
-    double t0 = a0, t1 = a1;
-    if (DIAG) {
-      t0 = (s.r > j) ? a0 : 0.0;
-      t1 = (s.r + 1 > j) ? a1 : 0.0;
-      a0 = (j <= s.r) ? a0 : 0.0;
-      a1 = (j <= s.r + 1) ? a1 : 0.0;
-    }
-    if (TP) tacc[k] = __builtin_fma(t0, s.xr0, t1 * s.xr1);
-    if (NP) {
-      n0 = __builtin_fma(a0, xj, n0);
-      n1 = __builtin_fma(a1, xj, n1);
-    }
-  }
-  if (TP) {
-    const double sum = reduce_scatter4(tacc);
-    if ((lane & 15) == 0) tout[cp + (lane >> 4)] = sum;
-  }
-}
-
-// the 32 panels of one tile, next panel's loads issued before this panel's reduction
-// NBUF panel buffers: NBUF - 1 panels (4 KB each per wave) in flight while one is consumed.  The launch is ONE
-// generation of one-tile waves (3160 tiles on 256 CUs at n = 10^4: 12.3 waves per CU, set by the tile count, not by
-// registers), so the bytes in flight per CU are 12.3 x (NBUF - 1) x 4 KB (+ the panel being waited for).
-template <bool DIAG, bool NT, bool NP = true, bool TP = true, int NBUF = 2>
-__device__ __forceinline__ void sy_tile(const SyLane& s, int64_t c0, double& n0, double& n1,
-                                        double* __restrict__ tout, int lane) {
-  constexpr int kPanels = kSyTile / kSyPanel, kFull = (kPanels / NBUF) * NBUF;
-  static_assert(NBUF >= 2 && NBUF <= 8, "ring of panel buffers");
-  double2_t buf[NBUF][kSyPanel];
-#pragma unroll
-  for (int b = 0; b + 1 < NBUF; ++b) sy_load<NT>(s, c0 + b * kSyPanel, buf[b]);
-#pragma unroll 1
-  for (int g = 0; g < kFull; g += NBUF) {
-#pragma unroll
-    for (int b = 0; b < NBUF; ++b) {
-      // panel g + b is consumed from buf[b]; the panel NBUF - 1 ahead goes into the buffer freed last
-      const int nxt = g + b + NBUF - 1;
-      if (kFull - NBUF + b + NBUF - 1 < kPanels || nxt < kPanels)  // (first test: compile time, true for every g)
-        sy_load<NT>(s, c0 + nxt * kSyPanel, buf[(b + NBUF - 1) % NBUF]);
-      sy_compute<DIAG, NP, TP>(s, c0 + (g + b) * kSyPanel, buf[b], n0, n1, tout, lane);
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < kPanels - kFull; ++b) {  // the panels a ring that does not divide 32 leaves over
-    if (kFull + b + NBUF - 1 < kPanels) sy_load<NT>(s, c0 + (kFull + b + NBUF - 1) * kSyPanel, buf[(b + NBUF - 1) % NBUF]);
-    sy_compute<DIAG, NP, TP>(s, c0 + (kFull + b) * kSyPanel, buf[b], n0, n1, tout, lane);
-  }
-}
-
-// tile t of the lower triangle in row-major order (0,0), (1,0), (1,1), (2,0), ... -> (bi, bj)
-__device__ __forceinline__ void tri_decode(unsigned t, unsigned& bi, unsigned& bj) {
-  unsigned r = static_cast<unsigned>((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-  while (r * (r + 1u) / 2u > t) --r;
-  while ((r + 1u) * (r + 2u) / 2u <= t) ++r;
-  bi = r;
-  bj = t - r * (r + 1u) / 2u;
-}
-
 // PACKED = false: M is npad x npad (npad = round_up(n, 128)) column-major with ld >= npad, zero outside n x n; grid
-// (ntile, ntile).  PACKED = true: M holds the lower-triangle tiles back to back (symv_pack_kernel); grid = their count.
+// (ntile, ntile).  PACKED = true: M holds the lower-triangle tiles back to back (launch_symv_pack); grid = their count.
 // x: n elements.  Tiles with linear index < ncached use default loads, the others non-temporal ones.
 template <bool PACKED, int NBUF = 2>
 __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block_y, const double* __restrict__ M,
@@ -143,16 +57,16 @@ __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block
   // does not own stay at their initial zero and the partial results are summed by one all-reduce of n doubles
   if (part_count > 1 && static_cast<int32_t>(lin % static_cast<unsigned>(part_count)) != part_rank) return;
   const int lane = threadIdx.x & 63;
-  const int64_t w0 = static_cast<int64_t>(bi) * kSyTile;  // wave's first row
-  const int64_t c0 = static_cast<int64_t>(bj) * kSyTile;
+  const int64_t w0 = static_cast<int64_t>(bi) * kTile;  // wave's first row
+  const int64_t c0 = static_cast<int64_t>(bj) * kTile;
   const int64_t gr = w0 + 2 * lane;  // this lane's row pair
   SyLane s;
   int64_t cbase;  // first column as sy_tile counts it
   double* __restrict__ tout = tpart + static_cast<int64_t>(bi) * ldp;
   if (PACKED) {  // the tile is its own 128 x 128 matrix: local row / column numbers, x and tout shifted to its columns
-    s.M = M + static_cast<int64_t>(lin) * (kSyTile * kSyTile);
+    s.M = M + static_cast<int64_t>(lin) * (kTile * kTile);
     s.x = x + c0;
-    s.ld = kSyTile;
+    s.ld = kTile;
     s.n = n - c0;
     s.r = 2 * lane;
     cbase = 0;
@@ -232,209 +146,18 @@ __global__ __launch_bounds__(kWave) void symv_lower_batch_kernel(const double* c
                         ldp, 0, 1, ncached);
 }
 
-// ---------------------------------------------------------------- x = X' (X y),  X = inv(L) tile-packed: the two
-// triangular solves of getProxOps.m:1200 `U \ (L \ y)` with the WHOLE factor as one pre-inverted block (trsv.hip has the
-// blocked substitution this is the one-block case of, and the reason: dependent steps, not bytes, bound a triangular
-// solve here).  Two passes over the same 8 n(n+1)/2 bytes -- the N-part alone (w = X y: rows in registers), then the
-// T-part alone (x = X' w: column sums by the reduce-scatter above) -- so both sweeps share ONE array and its
-// Infinity-Cache resident share.  Forward: tile (bi, bj) writes the partial row npart[bj][rows of bi]; w = their sum
-// over bj <= bi, by tri1_fold_kernel (the backward pass needs w as a vector: two values per lane).  Tiles are dealt in
-// DEscending order and the backward pass in ascending order: what one pass read last the next one reads first.
-// Backward: tile (bi, bj) writes tpart[bi][columns of bj]; x = sum over bi >= bj, taken by the consumer
-// (prox_fin_kernel's gather, or tri1_reduce_kernel).  Every sum in a fixed order.
-// (Measured, n = 10^4: forward 60 us + fold + backward 62 us = 6.4 TB/s per pass, the ceiling of a read stream that
-// does not fit L2 on this part (dev/gemv_pattern: 6.8 - 7.0).  A last-arriver fold inside the forward pass -- write-through
-// partial rows, a drained counter add per tile, the row tile's last tile summing it -- was built first and is gone:
-// 74 us for the pass instead of 60 + 4; 3 or 4 panel buffers instead of 2 change nothing, here and in symv_lower_*.)
-constexpr int kT1Panel = 4;  // forward pass: columns per load group (8: 144 VGPRs = 3 waves per SIMD = 12 tile slots per CU
-                             // for 12.3 tiles per CU at n = 10^4: a second generation for the last 88 tiles)
-
-__device__ __forceinline__ double t1_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-template <bool NT>
-__device__ __forceinline__ void t1_load(const double* __restrict__ Mr, int c, double2_t (&d)[kT1Panel]) {
-#pragma unroll
-  for (int k = 0; k < kT1Panel; ++k) d[k] = load2<NT>(Mr + (c + k) * kSyTile);
-}
-// yp: lane l holds the input pair of the tile's columns (2l, 2l + 1)
-__device__ __forceinline__ void t1_fma(double2_t yp, int co, const double2_t (&d)[kT1Panel], double& a0, double& a1) {
-#pragma unroll
-  for (int k = 0; k < kT1Panel; ++k) {
-    const double yj = t1_readlane((k & 1) ? yp.y : yp.x, (co + k) >> 1);
-    a0 = __builtin_fma(d[k].x, yj, a0);
-    a1 = __builtin_fma(d[k].y, yj, a1);
-  }
-}
-template <bool NT, int NBUF>
-__device__ __forceinline__ void t1_forward_tile(const double* __restrict__ Mr, double2_t yp, double& a0, double& a1) {
-  constexpr int kPanels = kSyTile / kT1Panel, kFull = (kPanels / NBUF) * NBUF;
-  double2_t buf[NBUF][kT1Panel];
-#pragma unroll
-  for (int b = 0; b + 1 < NBUF; ++b) t1_load<NT>(Mr, b * kT1Panel, buf[b]);
-#pragma unroll 1
-  for (int g = 0; g < kFull; g += NBUF) {
-#pragma unroll
-    for (int b = 0; b < NBUF; ++b) {  // (the ring of sy_tile)
-      const int nxt = g + b + NBUF - 1;
-      if (kFull + b - 1 < kPanels || nxt < kPanels) t1_load<NT>(Mr, nxt * kT1Panel, buf[(b + NBUF - 1) % NBUF]);
-      t1_fma(yp, (g + b) * kT1Panel, buf[b], a0, a1);
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < kPanels - kFull; ++b) {
-    if (kFull + b + NBUF - 1 < kPanels) t1_load<NT>(Mr, (kFull + b + NBUF - 1) * kT1Panel, buf[(b + NBUF - 1) % NBUF]);
-    t1_fma(yp, (kFull + b) * kT1Panel, buf[b], a0, a1);
-  }
-}
-
-template <int NBUF>
-__device__ __forceinline__ void tri1_forward_body(unsigned lin, const Tri1Args& a) {
-  unsigned bi, bj;
-  tri_decode(lin, bi, bj);
-  const int lane = threadIdx.x & 63;
-  const int64_t gr = static_cast<int64_t>(bi) * kSyTile + 2 * lane;  // this lane's row pair
-  double* __restrict__ po = a.npart + static_cast<int64_t>(bj) * a.ldp + gr;
-  const double* __restrict__ Mr = a.X + static_cast<int64_t>(lin) * (kSyTile * kSyTile) + 2 * lane;
-  const int64_t e = static_cast<int64_t>(bj) * kSyTile + 2 * lane;  // the tile's input columns: pair (2l, 2l + 1)
-  double2_t yp{0.0, 0.0};  // (the caller's vector is only 8-byte aligned and not padded)
-  yp.x = a.y[e < a.n ? e : a.n - 1];
-  yp.y = a.y[e + 1 < a.n ? e + 1 : a.n - 1];
-  if (e >= a.n) yp.x = 0.0;
-  if (e + 1 >= a.n) yp.y = 0.0;
-  double a0 = 0.0, a1 = 0.0;
-  if (lin < a.ncached) t1_forward_tile<false, NBUF>(Mr, yp, a0, a1);
-  else t1_forward_tile<true, NBUF>(Mr, yp, a0, a1);
-  *reinterpret_cast<double2_t*>(po) = double2_t{a0, a1};
-}
-
-// workgroup 0 is the passenger of symv_lower_fin_kernel: the deferred finalize logic of the previous iteration
-__global__ __launch_bounds__(kWave) void tri1_forward_kernel(Tri1Args a, FinArgs f, int32_t fin_pending,
-                                                             const Ctrl* __restrict__ ctrl) {
-  asm volatile("" ::"s"(a.X), "s"(a.n), "s"(a.npart), "s"(a.ldp), "s"(a.ncached), "s"(a.ntri), "s"(fin_pending),
-               "s"(ctrl));
-  if (ctrl && ctrl->stop) return;
-  if (blockIdx.x == 0) {
-    if (fin_pending) finalize_body<false, kWave>(f);
-    return;
-  }
-  tri1_forward_body<2>(a.ntri - blockIdx.x, a);  // blockIdx 1 .. ntri -> tiles ntri - 1 .. 0
-}
-
-__global__ __launch_bounds__(kWave) void tri1_backward_kernel(Tri1Args a, const Ctrl* __restrict__ ctrl) {
-  asm volatile("" ::"s"(a.X), "s"(a.n), "s"(a.tpart), "s"(a.ldp), "s"(a.ncached), "s"(ctrl));
-  if (ctrl && ctrl->stop) return;
-  const unsigned lin = blockIdx.x;
-  unsigned bi, bj;
-  tri_decode(lin, bi, bj);
-  const int lane = threadIdx.x & 63;
-  const int64_t gr = static_cast<int64_t>(bi) * kSyTile + 2 * lane;
-  SyLane s;
-  s.M = a.X + static_cast<int64_t>(lin) * (kSyTile * kSyTile);
-  s.x = nullptr;
-  s.ld = kSyTile;
-  s.n = 0;
-  s.r = 2 * lane;
-  const double2_t wr = *reinterpret_cast<const double2_t*>(a.w + gr);
-  s.xr0 = wr.x;
-  s.xr1 = wr.y;
-  double* __restrict__ tout = a.tpart + static_cast<int64_t>(bi) * a.ldp + static_cast<int64_t>(bj) * kSyTile;
-  double n0 = 0.0, n1 = 0.0;
-  if (lin < a.ncached) sy_tile<false, false, false, true>(s, 0, n0, n1, tout, lane);
-  else sy_tile<false, true, false, true>(s, 0, n0, n1, tout, lane);
-}
-
-// x[i] = sum_{p >= d} tpart[p][i],  d = i / 128  (the stand-alone form of what prox_fin_kernel's gather does)
-__global__ __launch_bounds__(kBlock) void tri1_reduce_kernel(const double* __restrict__ tpart, int64_t ldp, int64_t n,
-                                                             int32_t ntile, double* __restrict__ x,
-                                                             const Ctrl* __restrict__ ctrl) {
-  if (ctrl && ctrl->stop) return;
-  __shared__ double sacc[16][17];
-  const int ii = threadIdx.x & 15, slot = threadIdx.x >> 4;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + ii;
-  double s = 0.0;
-  if (i < n) {
-    const int32_t d = static_cast<int32_t>(i / kSyTile);
-#pragma unroll 4
-    for (int32_t p = d + slot; p < ntile; p += 16) s += tpart[static_cast<int64_t>(p) * ldp + i];
-  }
-  sacc[slot][ii] = s;
-  __syncthreads();
-  if (slot == 0 && i < n) {
-    double t = sacc[0][ii];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += sacc[k][ii];
-    x[i] = t;
-  }
-}
-
-// w[i] = sum_{p <= d} npart[p][i], d = i / 128
-__global__ __launch_bounds__(kBlock) void tri1_fold_kernel(const double* __restrict__ npart, int64_t ldp, int64_t npad,
-                                                           double* __restrict__ w, const Ctrl* __restrict__ ctrl) {
-  if (ctrl && ctrl->stop) return;
-  __shared__ double sacc[16][17];
-  const int ii = threadIdx.x & 15, slot = threadIdx.x >> 4;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + ii;
-  double s = 0.0;
-  if (i < npad) {
-    const int32_t d = static_cast<int32_t>(i / kSyTile);
-#pragma unroll 4
-    for (int32_t p = slot; p <= d; p += 16) s += npart[static_cast<int64_t>(p) * ldp + i];
-  }
-  sacc[slot][ii] = s;
-  __syncthreads();
-  if (slot == 0 && i < npad) {
-    double t = sacc[0][ii];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += sacc[k][ii];
-    w[i] = t;
-  }
-}
-
-void launch_tri1_forward(const Tri1Args& a, const FinArgs* fin, bool fin_pending, const Ctrl* ctrl, hipStream_t stream) {
-  const FinArgs f = fin ? *fin : FinArgs{};
-  hipLaunchKernelGGL(tri1_forward_kernel, dim3(a.ntri + 1u), dim3(kWave), 0, stream, a, f, (fin && fin_pending) ? 1 : 0,
-                     ctrl);
-  const int64_t npad = static_cast<int64_t>(a.ntile) * kSyTile;
-  hipLaunchKernelGGL(tri1_fold_kernel, dim3(static_cast<unsigned>(ceil_div(npad, int64_t{16}))), dim3(kBlock), 0, stream,
-                     a.npart, a.ldp, npad, a.w, ctrl);
-}
-void launch_tri1_backward(const Tri1Args& a, const Ctrl* ctrl, hipStream_t stream) {
-  hipLaunchKernelGGL(tri1_backward_kernel, dim3(a.ntri), dim3(kWave), 0, stream, a, ctrl);
-}
-void launch_tri1_reduce(const Tri1Args& a, double* x, const Ctrl* ctrl, hipStream_t stream) {
-  hipLaunchKernelGGL(tri1_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(a.n, int64_t{16}))), dim3(kBlock), 0,
-                     stream, a.tpart, a.ldp, a.n, a.ntile, x, ctrl);
-}
-
-// column-major padded storage -> tile-packed storage (one workgroup per lower-triangle tile)
-__global__ __launch_bounds__(kBlock) void symv_pack_kernel(const double* __restrict__ M, int64_t ld,
-                                                           double* __restrict__ P) {
-  unsigned bi, bj;
-  tri_decode(blockIdx.x, bi, bj);
-  const double* src = M + static_cast<int64_t>(bj) * kSyTile * ld + static_cast<int64_t>(bi) * kSyTile;
-  double* dst = P + static_cast<int64_t>(blockIdx.x) * (kSyTile * kSyTile);
-  for (int e = 2 * threadIdx.x; e < kSyTile * kSyTile; e += 2 * kBlock)
-    *reinterpret_cast<double2_t*>(dst + e) =
-        *reinterpret_cast<const double2_t*>(src + static_cast<int64_t>(e / kSyTile) * ld + (e % kSyTile));
-}
-
 // y[i] = sum_{g <= d} npart[g][i] + sum_{w >= d} tpart[w][i],  d = i / 128 (i's diagonal tile).
-// Workgroup = 16 consecutive elements x 16 slots that split the T+1 partial rows; the slots are
-// combined through LDS in a fixed order.
+// The 16 slots of a workgroup split the T+1 partial rows (slot_reduce.h: fold_slots_store).
 __global__ __launch_bounds__(kBlock) void symv_reduce_kernel(const double* __restrict__ npart,
                                                              const double* __restrict__ tpart, int64_t ldp,
                                                              int64_t n, int32_t ntile, double* __restrict__ y,
                                                              const Ctrl* __restrict__ ctrl) {
   if (ctrl && ctrl->stop) return;
-  __shared__ double sacc[16][17];
-  const int ii = threadIdx.x & 15, slot = threadIdx.x >> 4;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + ii;
+  const int slot = threadIdx.x >> 4;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + (threadIdx.x & 15);
   double s = 0.0;
   if (i < n) {
-    const int32_t d = static_cast<int32_t>(i / kSyTile);
+    const int32_t d = static_cast<int32_t>(i / kTile);
     // unified partial index p in [0, ntile]: p <= d -> npart[p], else tpart[p - 1]
 #pragma unroll 4
     for (int32_t p = slot; p <= ntile; p += 16) {
@@ -442,14 +165,7 @@ __global__ __launch_bounds__(kBlock) void symv_reduce_kernel(const double* __res
       s += src[i];
     }
   }
-  sacc[slot][ii] = s;
-  __syncthreads();
-  if (slot == 0 && i < n) {
-    double t = sacc[0][ii];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += sacc[k][ii];
-    y[i] = t;
-  }
+  fold_slots_store(s, y, i, i < n);
 }
 
 // Small symmetric M (n < ~1500: cache-resident, latency-bound): y_j = column j of M dot x, one wave per
@@ -486,26 +202,26 @@ void launch_symv_small(const double* M, int64_t n, int64_t ld, const double* x, 
 SymvPlan symv_plan(int64_t n) {
   SymvPlan p{};
   p.n = n;
-  p.npad = round_up(n, kSyTile);
+  p.npad = round_up(n, kTile);
   p.ldp = p.npad;
-  p.ntile = static_cast<int32_t>(p.npad / kSyTile);
+  p.ntile = static_cast<int32_t>(p.npad / kTile);
   p.packed = false;
   p.ncached = symv_cached_tiles(p, kSymvCacheBytes);
   return p;
 }
 
 int64_t symv_tiles(const SymvPlan& p) { return static_cast<int64_t>(p.ntile) * (p.ntile + 1) / 2; }
-size_t symv_packed_elems(const SymvPlan& p) { return static_cast<size_t>(symv_tiles(p)) * kSyTile * kSyTile; }
+size_t symv_packed_elems(const SymvPlan& p) { return static_cast<size_t>(symv_tiles(p)) * kTile * kTile; }
 
 int64_t symv_cached_tiles(const SymvPlan& p, int64_t budget_bytes) {
-  const int64_t tiles = symv_tiles(p), tile_bytes = int64_t{8} * kSyTile * kSyTile;
+  const int64_t tiles = symv_tiles(p), tile_bytes = int64_t{8} * kTile * kTile;
   if (!stream_hint(tiles * tile_bytes)) return tiles;  // small enough to stay cache-resident as a whole
   const int64_t fit = budget_bytes / tile_bytes;
   return fit < tiles ? fit : tiles;
 }
 
 void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P, hipStream_t stream) {
-  hipLaunchKernelGGL(symv_pack_kernel, dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kBlock), 0, stream, M, ld, P);
+  launch_tri_pack(M, ld, P, static_cast<unsigned>(symv_tiles(p)), 0, stream);
 }
 
 void launch_symv_reduce(const SymvPlan& p, const double* npart, const double* tpart, double* y, const Ctrl* ctrl,

@@ -1,5 +1,7 @@
 // trsv.hip -- x = L' \ (L \ y): the cached-factor x-update (getProxOps.m:1200 `U \ (L \ y)`,
-// 1514 `Rt \ (R \ .)`, 1455, 1247) on a dense lower Cholesky factor, as blocked substitution.
+// 1514 `Rt \ (R \ .)`, 1455, 1247) on a dense lower Cholesky factor.  Two forms, both over tile-packed triangles of
+// 128 x 128 tiles (tri_tile.h): blocked substitution (tri_step_kernel; described here) and, further down, the one-block
+// form (tri1_*: the whole factor as one pre-inverted block, two passes).
 //
 // A triangular solve is a dependent chain; what bounds it on this part is the number of dependent steps, not
 // bytes (round 1: 2*n/64 launches of 6 us = 0.05 of the HBM roofline).  So the chain is cut into K COARSE blocks
@@ -23,15 +25,17 @@
 // atomics, no reduce launches.  2K + 1 launches per solve pair (K = 5 at n = 10^4); the explicit inverses are
 // only of the K diagonal blocks (forward error eps*cond(L_kk), like any blocked TRSV with pre-inverted diagonal
 // blocks), so this is the numerically safe fallback of the `inverse` form.
+// (Split cache policy of the tile loads -- the first ncached tiles default, the rest non-temporal: symv.hip.)
 #include <algorithm>
 
+#include "finalize_device.h"
 #include "kernels.h"
+#include "slot_reduce.h"
+#include "tri_tile.h"
 
 namespace admm {
 
-typedef double double2_t __attribute__((ext_vector_type(2)));
-constexpr int kTsTile = 128;   // rows per wave = tile granularity of the blocks
-constexpr int kTsPanel = 8;    // columns per load group
+constexpr int kTsPanel = 8;    // columns per load group (kTile rows per wave = tile granularity of the blocks)
 constexpr int kTsBlockTiles = 16;  // 2048-row blocks: K = 5 at n = 10^4 (per-launch fixed cost ~6 us: 10 -> 217 us, 16 -> 182 us, 27 -> 177 us per pair)
 
 struct TriStepArgs {
@@ -101,36 +105,14 @@ __device__ __forceinline__ void ts_store_vec(double* __restrict__ b, int64_t e, 
   if (e + 1 < n) b[e + 1] = v.y;
 }
 
-__device__ __forceinline__ double ts_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
-template <bool NT>
-__device__ __forceinline__ void ts_load(const double* __restrict__ Mr, int64_t ld, int64_t c, double2_t (&d)[kTsPanel]) {
-#pragma unroll
-  for (int k = 0; k < kTsPanel; ++k) d[k] = load2<NT>(Mr + (c + k) * ld);
-}
-
-// xp: lane l holds the input pair of this wave's columns (2l, 2l+1); co = first column of the panel within the wave
-__device__ __forceinline__ void ts_fma(double2_t xp, int co, const double2_t (&d)[kTsPanel], double& a0, double& a1) {
-#pragma unroll
-  for (int k = 0; k < kTsPanel; ++k) {
-    const double xj = ts_readlane((k & 1) ? xp.y : xp.x, (co + k) >> 1);
-    a0 = __builtin_fma(d[k].x, xj, a0);
-    a1 = __builtin_fma(d[k].y, xj, a1);
-  }
-}
-
 // the tile itself: lc0 = this wave's first column inside the tile, cw0 = the same as a global column
 template <int WAVES, bool NT>
 __device__ __forceinline__ void tri_tile(const TriStepArgs& a, const double* __restrict__ Mr, int lc0, int64_t cw0,
                                          int64_t r, int32_t R, int32_t c, bool diag, int lane, int wave,
                                          double2_t (*red)[kWave]) {
-  constexpr int WC = kTsTile / WAVES;
+  constexpr int WC = kTile / WAVES;
   double2_t bufA[kTsPanel], bufB[kTsPanel];
-  ts_load<NT>(Mr, kTsTile, lc0, bufA);  // the matrix does not depend on the vectors: in flight during the prologue
+  panel_load<kTsPanel, NT>(Mr, kTile, lc0, bufA);  // the matrix does not depend on the vectors: in flight during the prologue
   // input block of this wave's columns: (base +) the previous step's partial sums, pair (2l, 2l+1) in lane l
   double2_t xp{0.0, 0.0};
   {
@@ -151,13 +133,13 @@ __device__ __forceinline__ void tri_tile(const TriStepArgs& a, const double* __r
   if (WC > kTsPanel) {
 #pragma unroll 1
     for (int co = 0; co < WC; co += 2 * kTsPanel) {
-      ts_load<NT>(Mr, kTsTile, lc0 + co + kTsPanel, bufB);
-      ts_fma(xp, co, bufA, a0, a1);
-      if (co + 2 * kTsPanel < WC) ts_load<NT>(Mr, kTsTile, lc0 + co + 2 * kTsPanel, bufA);
-      ts_fma(xp, co + kTsPanel, bufB, a0, a1);
+      panel_load<kTsPanel, NT>(Mr, kTile, lc0 + co + kTsPanel, bufB);
+      panel_fma(xp, co, bufA, a0, a1);
+      if (co + 2 * kTsPanel < WC) panel_load<kTsPanel, NT>(Mr, kTile, lc0 + co + 2 * kTsPanel, bufA);
+      panel_fma(xp, co + kTsPanel, bufB, a0, a1);
     }
   } else {
-    ts_fma(xp, 0, bufA, a0, a1);
+    panel_fma(xp, 0, bufA, a0, a1);
   }
   double2_t acc{a0, a1};
   if (WAVES > 1) {
@@ -179,7 +161,7 @@ __global__ __launch_bounds__(WAVES * kWave) void tri_step_kernel(TriStepArgs a) 
   asm volatile("" ::"s"(a.M), "s"(a.ncached), "s"(a.n), "s"(a.Pprev), "s"(a.Pcur), "s"(a.ldp), "s"(a.dt0), "s"(a.dt1),
                "s"(a.rt0), "s"(a.rt1), "s"(a.upper), "s"(a.ctrl));
   if (a.ctrl && a.ctrl->stop) return;
-  constexpr int WC = kTsTile / WAVES;  // columns per wave
+  constexpr int WC = kTile / WAVES;  // columns per wave
   __shared__ double2_t red[WAVES > 1 ? WAVES : 1][kWave];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int32_t nrows = a.rt1 - a.rt0;
@@ -189,18 +171,18 @@ __global__ __launch_bounds__(WAVES * kWave) void tri_step_kernel(TriStepArgs a) 
     const int32_t T = a.ext0 + static_cast<int32_t>(blockIdx.x) - nrows;
     int32_t q0, q1;
     ts_prev_range(a, T, q0, q1);
-    const int64_t e = static_cast<int64_t>(T) * kTsTile + 2 * lane;
+    const int64_t e = static_cast<int64_t>(T) * kTile + 2 * lane;
     ts_store_vec(a.diag_out, e, a.n, ts_sum_prev(a, q0, q1, e));
     return;
   }
   const int32_t R = a.rt0 + static_cast<int32_t>(blockIdx.x);  // row tile
   const bool diag = R >= a.dt0 && R < a.dt1;
   if (diag && (a.upper ? c < R - a.dt0 : c > R - a.dt0)) return;  // all-zero tile of the triangular block
-  const int64_t r = static_cast<int64_t>(R) * kTsTile + 2 * lane;  // this lane's row pair
-  const int64_t cw0 = static_cast<int64_t>(a.dt0 + c) * kTsTile + wave * WC;  // this wave's first column
+  const int64_t r = static_cast<int64_t>(R) * kTile + 2 * lane;  // this lane's row pair
+  const int64_t cw0 = static_cast<int64_t>(a.dt0 + c) * kTile + wave * WC;  // this wave's first column
   const uint32_t Ct = static_cast<uint32_t>(a.dt0 + c), Rt = static_cast<uint32_t>(R);
   const uint32_t lin = a.upper ? Ct * (Ct + 1u) / 2u + Rt : Rt * (Rt + 1u) / 2u + Ct;
-  const double* __restrict__ Mr = a.M + static_cast<int64_t>(lin) * (kTsTile * kTsTile) + 2 * lane;
+  const double* __restrict__ Mr = a.M + static_cast<int64_t>(lin) * (kTile * kTile) + 2 * lane;
   if (NT && lin >= a.ncached) tri_tile<WAVES, true>(a, Mr, wave * WC, cw0, r, R, c, diag, lane, wave, red);
   else tri_tile<WAVES, false>(a, Mr, wave * WC, cw0, r, R, c, diag, lane, wave, red);
 }
@@ -211,7 +193,7 @@ __global__ __launch_bounds__(kWave) void tri_fold_kernel(TriStepArgs a) {
   const int32_t T = a.ext0 + static_cast<int32_t>(blockIdx.x);
   int32_t q0, q1;
   ts_prev_range(a, T, q0, q1);
-  const int64_t e = static_cast<int64_t>(T) * kTsTile + 2 * static_cast<int>(threadIdx.x);
+  const int64_t e = static_cast<int64_t>(T) * kTile + 2 * static_cast<int>(threadIdx.x);
   ts_store_vec(a.diag_out, e, a.n, ts_sum_prev(a, q0, q1, e));
 }
 
@@ -238,16 +220,17 @@ __global__ __launch_bounds__(kBlock) void ts_transpose_block_kernel(const double
 __global__ __launch_bounds__(kBlock) void ts_pack_kernel(const double* __restrict__ M, int64_t ld, double* __restrict__ P,
                                                          int upper) {
   const unsigned t = blockIdx.x;
-  unsigned bi = static_cast<unsigned>((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-  while (bi * (bi + 1u) / 2u > t) --bi;
-  while ((bi + 1u) * (bi + 2u) / 2u <= t) ++bi;
-  const unsigned bj = t - bi * (bi + 1u) / 2u;
+  unsigned bi, bj;
+  tri_decode(t, bi, bj);
   const int64_t tr = upper ? bj : bi, tc = upper ? bi : bj;  // tile row / column in M
-  const double* src = M + tc * kTsTile * ld + tr * kTsTile;
-  double* dst = P + static_cast<int64_t>(t) * (kTsTile * kTsTile);
-  for (int e = 2 * threadIdx.x; e < kTsTile * kTsTile; e += 2 * kBlock)
+  const double* src = M + tc * kTile * ld + tr * kTile;
+  double* dst = P + static_cast<int64_t>(t) * (kTile * kTile);
+  for (int e = 2 * threadIdx.x; e < kTile * kTile; e += 2 * kBlock)
     *reinterpret_cast<double2_t*>(dst + e) =
-        *reinterpret_cast<const double2_t*>(src + static_cast<int64_t>(e / kTsTile) * ld + (e % kTsTile));
+        *reinterpret_cast<const double2_t*>(src + static_cast<int64_t>(e / kTile) * ld + (e % kTile));
+}
+void launch_tri_pack(const double* M, int64_t ld, double* P, unsigned ntri, int upper, hipStream_t stream) {
+  hipLaunchKernelGGL(ts_pack_kernel, dim3(ntri), dim3(kBlock), 0, stream, M, ld, P, upper);
 }
 
 // geometry shared by trsv_plan_elems and trsv_build
@@ -257,19 +240,19 @@ struct TsGeom {
 };
 static TsGeom ts_geom(int64_t n) {
   TsGeom g{};
-  g.npad = round_up(n, kTsTile);
-  g.ntile = g.npad / kTsTile;
+  g.npad = round_up(n, kTile);
+  g.ntile = g.npad / kTile;
   g.bt = std::min<int64_t>(kTsBlockTiles, g.ntile);
   g.nblk = ceil_div(g.ntile, g.bt);
   g.bt = ceil_div(g.ntile, g.nblk);  // balanced blocks
-  g.base_elems = static_cast<size_t>(g.ntile * (g.ntile + 1) * kTsTile * kTsTile + 2 * g.bt * g.npad + 2 * g.npad);
+  g.base_elems = static_cast<size_t>(g.ntile * (g.ntile + 1) * kTile * kTile + 2 * g.bt * g.npad + 2 * g.npad);
   return g;
 }
 
-// ---------------------------------------------------------------- the one-block form (kernels: symv.hip, tri1_*)
+// ---------------------------------------------------------------- the one-block form (tri1_*)
 // With the whole factor as ONE pre-inverted block the chain has no steps left: w = X y and x = X' w, X = inv(L), are
 // two bandwidth-bound passes over the same tile-packed triangle (8 n(n+1) bytes per pair, what the substitution reads)
-// and two launches.  The price is numerical: X is an explicit triangular inverse, forward error ~ eps * cond(L) per
+// and two launches (+ the fold between them).  The price is numerical: X is an explicit triangular inverse, forward error ~ eps * cond(L) per
 // pass where the blocked form has eps * cond(L_kk) -- still the SQUARE ROOT of what the explicit inverse of L L' costs
 // (`inverse` form).  Which of the two runs is decided by measurement at create (engine.hip: choose_trsv_form).
 int trsv_resolve_form(int64_t n, int form) {
@@ -284,10 +267,10 @@ struct T1Geom {
 };
 static T1Geom t1_geom(int64_t n) {
   T1Geom g{};
-  g.npad = round_up(n, kTsTile);
-  g.ntile = g.npad / kTsTile;
+  g.npad = round_up(n, kTile);
+  g.ntile = g.npad / kTile;
   g.ntri = g.ntile * (g.ntile + 1) / 2;
-  g.x_elems = static_cast<size_t>(g.ntri) * kTsTile * kTsTile;
+  g.x_elems = static_cast<size_t>(g.ntri) * kTile * kTile;
   g.part_elems = static_cast<size_t>(g.ntile * g.npad);
   g.w_elems = static_cast<size_t>(g.npad);
   return g;
@@ -299,6 +282,148 @@ size_t trsv_plan_elems(int64_t n, int form) {
     return g.x_elems + 2 * g.part_elems + g.w_elems;
   }
   return ts_geom(n).base_elems;
+}
+
+// The two passes: the N-part alone (w = X y: rows in registers, the panel of the blocked form at 4 columns), then the
+// T-part alone (x = X' w: sy_tile's column sums, tri_tile.h) -- so both sweeps share ONE array and its Infinity-Cache
+// resident share.  Forward: tile (bi, bj) writes the partial row npart[bj][rows of bi]; w = their sum over bj <= bi, by
+// tri1_fold_kernel (the backward pass needs w as a vector: two values per lane).  Tiles are dealt in DEscending order
+// and the backward pass in ascending order: what one pass read last the next one reads first.
+// Backward: tile (bi, bj) writes tpart[bi][columns of bj]; x = sum over bi >= bj, taken by the consumer
+// (prox_fin_kernel's gather, or tri1_reduce_kernel).  Every sum in a fixed order.
+// (Measured, n = 10^4: forward 60 us + fold + backward 62 us = 6.4 TB/s per pass, the ceiling of a read stream that
+// does not fit L2 on this part (dev/gemv_pattern: 6.8 - 7.0).  A last-arriver fold inside the forward pass -- write-through
+// partial rows, a drained counter add per tile, the row tile's last tile summing it -- was built first and is gone:
+// 74 us for the pass instead of 60 + 4; 3 or 4 panel buffers instead of 2 change nothing, here and in symv_lower_*.)
+constexpr int kT1Panel = 4;  // forward pass: columns per load group (8: 144 VGPRs = 3 waves per SIMD = 12 tile slots per CU
+                             // for 12.3 tiles per CU at n = 10^4: a second generation for the last 88 tiles)
+
+// yp: lane l holds the input pair of the tile's columns (2l, 2l + 1)
+template <bool NT, int NBUF>
+__device__ __forceinline__ void t1_forward_tile(const double* __restrict__ Mr, double2_t yp, double& a0, double& a1) {
+  constexpr int kPanels = kTile / kT1Panel, kFull = (kPanels / NBUF) * NBUF;
+  double2_t buf[NBUF][kT1Panel];
+#pragma unroll
+  for (int b = 0; b + 1 < NBUF; ++b) panel_load<kT1Panel, NT>(Mr, kTile, b * kT1Panel, buf[b]);
+#pragma unroll 1
+  for (int g = 0; g < kFull; g += NBUF) {
+#pragma unroll
+    for (int b = 0; b < NBUF; ++b) {  // (the ring of sy_tile)
+      const int nxt = g + b + NBUF - 1;
+      if (kFull + b - 1 < kPanels || nxt < kPanels)
+        panel_load<kT1Panel, NT>(Mr, kTile, nxt * kT1Panel, buf[(b + NBUF - 1) % NBUF]);
+      panel_fma(yp, (g + b) * kT1Panel, buf[b], a0, a1);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < kPanels - kFull; ++b) {
+    if (kFull + b + NBUF - 1 < kPanels)
+      panel_load<kT1Panel, NT>(Mr, kTile, (kFull + b + NBUF - 1) * kT1Panel, buf[(b + NBUF - 1) % NBUF]);
+    panel_fma(yp, (kFull + b) * kT1Panel, buf[b], a0, a1);
+  }
+}
+
+template <int NBUF>
+__device__ __forceinline__ void tri1_forward_body(unsigned lin, const Tri1Args& a) {
+  unsigned bi, bj;
+  tri_decode(lin, bi, bj);
+  const int lane = threadIdx.x & 63;
+  const int64_t gr = static_cast<int64_t>(bi) * kTile + 2 * lane;  // this lane's row pair
+  double* __restrict__ po = a.npart + static_cast<int64_t>(bj) * a.ldp + gr;
+  const double* __restrict__ Mr = a.X + static_cast<int64_t>(lin) * (kTile * kTile) + 2 * lane;
+  const int64_t e = static_cast<int64_t>(bj) * kTile + 2 * lane;  // the tile's input columns: pair (2l, 2l + 1)
+  double2_t yp{0.0, 0.0};  // (the caller's vector is only 8-byte aligned and not padded)
+  yp.x = a.y[e < a.n ? e : a.n - 1];
+  yp.y = a.y[e + 1 < a.n ? e + 1 : a.n - 1];
+  if (e >= a.n) yp.x = 0.0;
+  if (e + 1 >= a.n) yp.y = 0.0;
+  double a0 = 0.0, a1 = 0.0;
+  if (lin < a.ncached) t1_forward_tile<false, NBUF>(Mr, yp, a0, a1);
+  else t1_forward_tile<true, NBUF>(Mr, yp, a0, a1);
+  *reinterpret_cast<double2_t*>(po) = double2_t{a0, a1};
+}
+
+// workgroup 0 is the passenger of symv_lower_fin_kernel: the deferred finalize logic of the previous iteration
+__global__ __launch_bounds__(kWave) void tri1_forward_kernel(Tri1Args a, FinArgs f, int32_t fin_pending,
+                                                             const Ctrl* __restrict__ ctrl) {
+  asm volatile("" ::"s"(a.X), "s"(a.n), "s"(a.npart), "s"(a.ldp), "s"(a.ncached), "s"(a.ntri), "s"(fin_pending),
+               "s"(ctrl));
+  if (ctrl && ctrl->stop) return;
+  if (blockIdx.x == 0) {
+    if (fin_pending) finalize_body<false, kWave>(f);
+    return;
+  }
+  tri1_forward_body<2>(a.ntri - blockIdx.x, a);  // blockIdx 1 .. ntri -> tiles ntri - 1 .. 0
+}
+
+__global__ __launch_bounds__(kWave) void tri1_backward_kernel(Tri1Args a, const Ctrl* __restrict__ ctrl) {
+  asm volatile("" ::"s"(a.X), "s"(a.n), "s"(a.tpart), "s"(a.ldp), "s"(a.ncached), "s"(ctrl));
+  if (ctrl && ctrl->stop) return;
+  const unsigned lin = blockIdx.x;
+  unsigned bi, bj;
+  tri_decode(lin, bi, bj);
+  const int lane = threadIdx.x & 63;
+  const int64_t gr = static_cast<int64_t>(bi) * kTile + 2 * lane;
+  SyLane s;
+  s.M = a.X + static_cast<int64_t>(lin) * (kTile * kTile);
+  s.x = nullptr;
+  s.ld = kTile;
+  s.n = 0;
+  s.r = 2 * lane;
+  const double2_t wr = *reinterpret_cast<const double2_t*>(a.w + gr);
+  s.xr0 = wr.x;
+  s.xr1 = wr.y;
+  double* __restrict__ tout = a.tpart + static_cast<int64_t>(bi) * a.ldp + static_cast<int64_t>(bj) * kTile;
+  double n0 = 0.0, n1 = 0.0;
+  if (lin < a.ncached) sy_tile<false, false, false, true>(s, 0, n0, n1, tout, lane);
+  else sy_tile<false, true, false, true>(s, 0, n0, n1, tout, lane);
+}
+
+// x[i] = sum_{p >= d} tpart[p][i],  d = i / 128  (the stand-alone form of what prox_fin_kernel's gather does)
+__global__ __launch_bounds__(kBlock) void tri1_reduce_kernel(const double* __restrict__ tpart, int64_t ldp, int64_t n,
+                                                             int32_t ntile, double* __restrict__ x,
+                                                             const Ctrl* __restrict__ ctrl) {
+  if (ctrl && ctrl->stop) return;
+  const int slot = threadIdx.x >> 4;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + (threadIdx.x & 15);
+  double s = 0.0;
+  if (i < n) {
+    const int32_t d = static_cast<int32_t>(i / kTile);
+#pragma unroll 4
+    for (int32_t p = d + slot; p < ntile; p += 16) s += tpart[static_cast<int64_t>(p) * ldp + i];
+  }
+  fold_slots_store(s, x, i, i < n);
+}
+
+// w[i] = sum_{p <= d} npart[p][i], d = i / 128
+__global__ __launch_bounds__(kBlock) void tri1_fold_kernel(const double* __restrict__ npart, int64_t ldp, int64_t npad,
+                                                           double* __restrict__ w, const Ctrl* __restrict__ ctrl) {
+  if (ctrl && ctrl->stop) return;
+  const int slot = threadIdx.x >> 4;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + (threadIdx.x & 15);
+  double s = 0.0;
+  if (i < npad) {
+    const int32_t d = static_cast<int32_t>(i / kTile);
+#pragma unroll 4
+    for (int32_t p = slot; p <= d; p += 16) s += npart[static_cast<int64_t>(p) * ldp + i];
+  }
+  fold_slots_store(s, w, i, i < npad);
+}
+
+void launch_tri1_forward(const Tri1Args& a, const FinArgs* fin, bool fin_pending, const Ctrl* ctrl, hipStream_t stream) {
+  const FinArgs f = fin ? *fin : FinArgs{};
+  hipLaunchKernelGGL(tri1_forward_kernel, dim3(a.ntri + 1u), dim3(kWave), 0, stream, a, f, (fin && fin_pending) ? 1 : 0,
+                     ctrl);
+  const int64_t npad = static_cast<int64_t>(a.ntile) * kTile;
+  hipLaunchKernelGGL(tri1_fold_kernel, dim3(static_cast<unsigned>(ceil_div(npad, int64_t{16}))), dim3(kBlock), 0, stream,
+                     a.npart, a.ldp, npad, a.w, ctrl);
+}
+void launch_tri1_backward(const Tri1Args& a, const Ctrl* ctrl, hipStream_t stream) {
+  hipLaunchKernelGGL(tri1_backward_kernel, dim3(a.ntri), dim3(kWave), 0, stream, a, ctrl);
+}
+void launch_tri1_reduce(const Tri1Args& a, double* x, const Ctrl* ctrl, hipStream_t stream) {
+  hipLaunchKernelGGL(tri1_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(a.n, int64_t{16}))), dim3(kBlock), 0,
+                     stream, a.tpart, a.ldp, a.n, a.ntile, x, ctrl);
 }
 
 static int tri1_build(const double* L, int64_t n, int64_t ldl, const double* dinv64, double* buf, TrsvPlan* plan,
@@ -320,7 +445,7 @@ static int tri1_build(const double* L, int64_t n, int64_t ldl, const double* din
   p.w1 = p.tp1 + g.part_elems;
   p.streaming = stream_hint(static_cast<int64_t>(g.x_elems) * 8);
   // ONE array serves both passes: the whole Infinity-Cache budget of symv.hip goes to its first tiles
-  p.ncached = p.streaming ? static_cast<int64_t>(kSymvCacheBytes / (8 * kTsTile * kTsTile)) : INT64_MAX;
+  p.ncached = p.streaming ? static_cast<int64_t>(kSymvCacheBytes / (8 * kTile * kTile)) : INT64_MAX;
   ADMM_HIP_TRY(hipMemsetAsync(buf, 0, trsv_plan_elems(n, kTrsvOne) * sizeof(double), stream));
   double* dense = nullptr;  // X = inv(L) as a padded column-major square (zero above the diagonal and outside n x n)
   const size_t msz = static_cast<size_t>(p.npad) * p.npad;
@@ -329,7 +454,7 @@ static int tri1_build(const double* L, int64_t n, int64_t ldl, const double* din
   int rc = (se == hipSuccess) ? trtri_lower_from_diag(L, n, ldl, dinv64, dense, p.ldm, stream, false)
                               : fail(ADMM_E_DEVICE, "hipMemsetAsync failed");
   if (rc == ADMM_OK)
-    hipLaunchKernelGGL(ts_pack_kernel, dim3(static_cast<unsigned>(g.ntri)), dim3(kBlock), 0, stream, dense, p.ldm, p.X1, 0);
+    launch_tri_pack(dense, p.ldm, p.X1, static_cast<unsigned>(g.ntri), 0, stream);
   se = hipStreamSynchronize(stream);
   (void)hipFree(dense);
   ADMM_TRY(rc);
@@ -376,7 +501,7 @@ int trsv_build(const double* L, int64_t n, int64_t ldl, const double* dinv64, do
   p.ldm = p.npad;
   p.ldp = p.npad;
   const size_t msz = static_cast<size_t>(p.npad) * p.npad;                                // the dense squares they are built in
-  const size_t psz = static_cast<size_t>(p.ntile) * (p.ntile + 1) / 2 * kTsTile * kTsTile;  // a packed triangle
+  const size_t psz = static_cast<size_t>(p.ntile) * (p.ntile + 1) / 2 * kTile * kTile;  // a packed triangle
   double* const packedF = buf;
   double* const packedU = buf + psz;
   p.P[0] = packedU + psz;
@@ -385,7 +510,7 @@ int trsv_build(const double* L, int64_t n, int64_t ldl, const double* dinv64, do
   p.w = p.v + p.npad;
   p.streaming = stream_hint(static_cast<int64_t>(psz) * 2 * 8);
   // the split cache policy of symv.hip: both triangles are read once per solve pair and share the budget
-  p.ncached = p.streaming ? static_cast<int64_t>(kSymvCacheBytes / 2 / (8 * kTsTile * kTsTile)) : INT64_MAX;
+  p.ncached = p.streaming ? static_cast<int64_t>(kSymvCacheBytes / 2 / (8 * kTile * kTile)) : INT64_MAX;
   ADMM_HIP_TRY(hipMemsetAsync(buf, 0, trsv_plan_elems(n, kTrsvBlocked) * sizeof(double), stream));
   double* dense = nullptr;  // Fm | Um as padded column-major squares: GEMM outputs, packed below
   ADMM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dense), 2 * msz * sizeof(double)));
@@ -393,8 +518,8 @@ int trsv_build(const double* L, int64_t n, int64_t ldl, const double* dinv64, do
   p.Fm = dense;
   p.Um = dense + msz;
   for (int32_t k = 0; k < p.nblk; ++k) {
-    const int64_t k0 = static_cast<int64_t>(k) * p.bt * kTsTile;
-    const int64_t nb = std::min<int64_t>(static_cast<int64_t>(p.bt) * kTsTile, n - k0);
+    const int64_t k0 = static_cast<int64_t>(k) * p.bt * kTile;
+    const int64_t nb = std::min<int64_t>(static_cast<int64_t>(p.bt) * kTile, n - k0);
     if (nb <= 0) break;
     double* Xk = p.Fm + k0 + k0 * p.ldm;
     // X_k = inv(L_kk) into Fm's (already zero) diagonal block
@@ -410,8 +535,8 @@ int trsv_build(const double* L, int64_t n, int64_t ldl, const double* dinv64, do
       launch_gemm(1, 1, k0, nb, nb, -1.0, L + k0, ldl, Xk, p.ldm, 0.0, p.Um + k0 * p.ldm, p.ldm, false, stream);
   }
   const unsigned ntri = static_cast<unsigned>(p.ntile) * static_cast<unsigned>(p.ntile + 1) / 2u;
-  hipLaunchKernelGGL(ts_pack_kernel, dim3(ntri), dim3(kBlock), 0, stream, p.Fm, p.ldm, packedF, 0);
-  hipLaunchKernelGGL(ts_pack_kernel, dim3(ntri), dim3(kBlock), 0, stream, p.Um, p.ldm, packedU, 1);
+  launch_tri_pack(p.Fm, p.ldm, packedF, ntri, 0, stream);
+  launch_tri_pack(p.Um, p.ldm, packedU, ntri, 1, stream);
   const hipError_t se = hipStreamSynchronize(stream);
   (void)hipFree(dense);
   ADMM_HIP_TRY(se);

@@ -31,10 +31,9 @@
 #include "tv_direct2.h"
 #include "finalize_device.h"
 #include "slot_reduce.h"
+#include "tri_tile.h"  // double2_t
 
 namespace admm {
-
-typedef double double2_t __attribute__((ext_vector_type(2)));
 
 // recurrence multiplier: forward a_i = rho/b_{i-1} (a_0 = 0); backward a_i = rho/b_i, 0 for the last row
 template <bool BWD>

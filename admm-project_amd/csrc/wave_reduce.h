@@ -1,6 +1,6 @@
 // wave_reduce.h -- cross-lane sums of a 64-lane wave WITHOUT the LDS crossbar: gfx950 v_permlane{32,16}_swap exchange
 // steps and a DPP butterfly inside each 16-lane row (measured in the symmetric x-solve: 25 us cheaper per 400 MB pass
-// than the ds_bpermute / __shfl_xor form).  Shared by symv.hip and unwrapped.hip.
+// than the ds_bpermute / __shfl_xor form).  Shared by tri_tile.h (symv.hip, trsv.hip) and unwrapped.hip.
 #pragma once
 #include "common.h"
 

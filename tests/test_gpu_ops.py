@@ -116,9 +116,9 @@ def test_bad_arguments_are_errors_not_crashes(gpu):
     assert lib.admm_engine_create(C.byref(d), C.byref(h)) == gpu._lib.E_INVALID
 
 
-@pytest.mark.parametrize("n", [256, 300, 1000, 2049, 3333, 10000])
+@pytest.mark.parametrize("n", [256, 257, 300, 385, 1000, 2049, 3333, 10000])
 def test_trsv_pair_one_block_form(gpu, n, monkeypatch):
-    """the triangular solves with the whole factor as ONE pre-inverted block (symv.hip: tri1_*): w = X y by the N-part
+    """the triangular solves with the whole factor as ONE pre-inverted block (trsv.hip: tri1_*): w = X y by the N-part
     pass + fold, x = X' w by the T-part pass + reduce; against LAPACK's substitution, against the blocked form, and
     twice in a row (fixed-order sums: bitwise the same)"""
     rng = np.random.default_rng(n + 7)
