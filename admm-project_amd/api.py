@@ -119,6 +119,14 @@ def getproxops(problem, args):
                 raise L.AdmmError(L.E_UNSUPPORTED, "args.groups on a row-sharded engine")
         elif args.get("groupweights") is not None:
             raise ValueError("args.groupweights without args.groups")
+        from .errorcheck import penalty_fields  # the penalty family (engine-side extension)
+        penalty = penalty_fields(args, np.shape(_get(args, "D"))[1])
+        if penalty is not None:
+            if args.get("parallel", 0):
+                raise L.AdmmError(L.E_UNSUPPORTED, "args.l1weights / ridge / l1 / nonnegative with args.parallel = 1: "
+                                                   "consensus lasso has no penalty family")
+            if comm is not None:
+                raise L.AdmmError(L.E_UNSUPPORTED, "args.l1weights / ridge / l1 / nonnegative on a row-sharded engine")
         if args.get("parallel", 0):  # getProxOps.m:383-442: consensus over row slices
             D, s, lam = _get(args, "D"), _get(args, "s"), _get(args, "lambda")
             slices = [int(k) for k in np.atleast_1d(_get(args, "slices"))]
@@ -144,6 +152,8 @@ def getproxops(problem, args):
                      obj_gram=int(args.get("objgram", 0)), **cg)
         if groups is not None:
             eng.set_groups(*groups)
+        if penalty is not None:
+            eng.set_penalty(**penalty)
         prob = _Problem("lasso", eng, dict(A=1, c=0.0, nA=n, nB=n))
     elif kind in ("lad", "huberfit"):
         D, s = _get(args, "D"), _get(args, "s")

@@ -20,6 +20,10 @@ struct admm_binding {
   std::vector<int64_t> slices;    // args.slices (getProxOps.m:387) as integers
   std::vector<int64_t> groups;    // args.groups: the group sizes of group lasso (admm_engine_set_groups)
   std::vector<double> groupweights;  // args.groupweights (one per group; empty: every weight 1), copied: apply runs after create
+  std::vector<double> l1weights;  // args.l1weights (one per column of D; empty: every weight 1), copied as well
+  double pen_l1 = 0.0, pen_ridge = 0.0;  // args.l1, args.ridge
+  int32_t pen_nonneg = 0;                // args.nonnegative
+  bool has_penalty = false;              // any of the four was given (admm_engine_set_penalty)
   int32_t tv2d_isotropic = 0;     // args.isotropic of totalvariation2d (admm_engine_set_tv2d_isotropic)
   std::vector<double> zeros;      // c = 0 for the engines that take c as a data vector
   int64_t nA = 0, nB = 0;         // lengths of x and of z
@@ -135,6 +139,33 @@ int describe(const std::string& p, const View& args, const View& handles, admm_b
       }
     } else if (args.get("groupweights")) {
       return fail(ADMM_E_INVALID, "args.groupweights without args.groups");
+    }
+    // the penalty family (engine-side extension, admm_engine_set_penalty): args.l1weights, args.ridge, args.l1,
+    // args.nonnegative -- element counts and values are checked here
+    if (args.get("l1weights") || args.get("ridge") || args.get("l1") || args.get("nonnegative")) {
+      if (args.scalar("parallel", 0) != 0)
+        return fail(ADMM_E_UNSUPPORTED, "args.l1weights / ridge / l1 / nonnegative with args.parallel = 1: consensus lasso "
+                                        "has no penalty family");
+      const auto ok = [](double v) { return v >= 0.0 && std::isfinite(v); };
+      if (args.get("l1weights")) {
+        size_t k = 0;
+        const double* w = args.vec("l1weights", &k);
+        if (!w || k != static_cast<size_t>(d.n))
+          return fail(ADMM_E_INVALID, "args.l1weights must have one entry per column of D");
+        for (size_t i = 0; i < k; ++i)
+          if (!ok(w[i])) return fail(ADMM_E_INVALID, "args.l1weights: every weight must be finite and >= 0");
+        b.l1weights.assign(w, w + k);
+      }
+      for (const char* name : {"ridge", "l1", "nonnegative"}) {
+        if (!args.get(name)) continue;
+        const double v = args.scalar(name, std::nan(""));
+        if (!ok(v)) return fail(ADMM_E_INVALID, std::string("args.") + name + " must be a finite real scalar >= 0");
+        if (name[0] == 'r') b.pen_ridge = v;
+        else if (name[0] == 'l') b.pen_l1 = v;
+        else if (v != 0.0 && v != 1.0) return fail(ADMM_E_INVALID, "args.nonnegative must be 0 or 1");
+        else b.pen_nonneg = static_cast<int32_t>(v);
+      }
+      b.has_penalty = true;
     }
     if (args.scalar("parallel", 0) != 0) {  // getProxOps.m:383-442
       d.problem = ADMM_PROB_LASSO_CONSENSUS;
@@ -371,6 +402,10 @@ int admm_binding_apply(const admm_binding* b, admm_engine* e) {
     ADMM_TRY(admm_engine_set_groups(e, b->groups.data(), static_cast<int32_t>(b->groups.size()),
                                     b->groupweights.empty() ? nullptr : b->groupweights.data()));
   if (b->tv2d_isotropic) ADMM_TRY(admm_engine_set_tv2d_isotropic(e, 1));
+  if (b->has_penalty) {
+    const admm_penalty_desc pd{b->l1weights.empty() ? nullptr : b->l1weights.data(), b->pen_l1, b->pen_ridge, b->pen_nonneg};
+    ADMM_TRY(admm_engine_set_penalty(e, &pd));
+  }
   if (b->b_kind == 1 || b->b_kind == 2)
     return admm_engine_set_constraint_b(e, b->b_matrix, b->b_ld, b->b_kind == 2 ? b->nB : 0, ADMM_MEM_HOST, b->b_scalar,
                                         nullptr, nullptr);

@@ -226,6 +226,11 @@ struct admm_engine {
   GroupPlan grp{};
   double* grp_blob = nullptr;
   int32_t ngroups = 0;        // 0: the plain l1 prox
+  // the penalty family (admm_engine_set_penalty): defaults = today's prox, bit for bit
+  double* pen_w = nullptr;    // [len] l1 weights, or null: every weight is 1
+  double pen_l1 = 0.0;        // the l1 weight beside the groups (read only while groups are in force)
+  double pen_ridge = 0.0;     // mu
+  int32_t pen_nonneg = 0;
   double* part = nullptr;     // [S_COUNT][kMaxPartBlocks]
   double* objpart = nullptr;  // [kMaxPartBlocks]
   Ctrl* ctrl = nullptr;

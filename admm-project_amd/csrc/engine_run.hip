@@ -589,6 +589,47 @@ int admm_engine_set_groups(admm_engine* e, const int64_t* sizes, int32_t ngroups
   return ADMM_OK;
 }
 
+int admm_engine_set_penalty(admm_engine* e, const admm_penalty_desc* d) {
+  if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
+  if (e->problem != ADMM_PROB_LASSO)
+    return fail(ADMM_E_UNSUPPORTED, "the penalty family belongs to the serial lasso (ADMM_PROB_LASSO): it replaces the "
+                                    "l1 prox of its z-update");
+  if (e->comm) return fail(ADMM_E_UNSUPPORTED, "the penalty family is not supported on row-sharded engines");
+  const auto ok = [](double v) { return v >= 0.0 && v <= 1.79769313486231570e308; };  // finite, >= 0, not NaN
+  if (d) {  // (a refused call changes nothing)
+    if (!ok(d->l1)) return fail(ADMM_E_INVALID, "penalty: l1 must be finite and >= 0");
+    if (!ok(d->ridge)) return fail(ADMM_E_INVALID, "penalty: ridge must be finite and >= 0");
+    if (d->nonnegative != 0 && d->nonnegative != 1) return fail(ADMM_E_INVALID, "penalty: nonnegative must be 0 or 1");
+    if (d->l1weights)
+      for (int64_t i = 0; i < e->len; ++i)
+        if (!ok(d->l1weights[i]))
+          return fail(ADMM_E_INVALID, "penalty: l1 weight " + std::to_string(i) + " is negative or not finite");
+  }
+  ADMM_HIP_TRY(hipSetDevice(e->device));
+  double* w = nullptr;
+  if (d && d->l1weights) {
+    ADMM_TRY(e->mem.alloc(&w, static_cast<size_t>(e->len)));
+    ADMM_HIP_TRY(hipMemcpyAsync(w, d->l1weights, sizeof(double) * e->len, hipMemcpyHostToDevice, e->stream));
+  }
+  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (the caller's weights are read until here; no run uses the old ones)
+  if (e->pen_w) e->mem.free_one(e->pen_w);
+  e->pen_w = w;
+  e->pen_l1 = d ? d->l1 : 0.0;
+  e->pen_ridge = d ? d->ridge : 0.0;
+  e->pen_nonneg = d ? d->nonnegative : 0;
+  return ADMM_OK;
+}
+
+int admm_engine_get_penalty(admm_engine* e, admm_penalty_desc* out, int32_t* has_l1weights) {
+  if (!e || !out) return fail(ADMM_E_INVALID, "NULL argument");
+  out->l1weights = nullptr;
+  out->l1 = e->pen_l1;
+  out->ridge = e->pen_ridge;
+  out->nonnegative = e->pen_nonneg;
+  if (has_l1weights) *has_l1weights = e->pen_w ? 1 : 0;
+  return ADMM_OK;
+}
+
 int admm_engine_set_tv2d_isotropic(admm_engine* e, int32_t on) {
   if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
   if (e->problem != ADMM_PROB_TV2D)

@@ -138,6 +138,8 @@ struct GeneralLoop {
   double alt_const = 0.0;
   bool gram_guard = false, split_symv = false;
   bool grouped = false;  // group lasso: the grouped element update wherever the lasso's own runs (a zming callback wins)
+  bool penalized = false;  // a non-default admm_engine_set_penalty: the penalised element update in the same places
+  PenaltyArgs pen{};
 
   // ---- may change at a batch boundary (after_batch: nothing is pending there, so the launch sequence may change)
   bool gram_now = false, gram_calibrating = false, obj_kernels = false;
@@ -174,6 +176,7 @@ struct GeneralLoop {
     sharded = e->comm && comm_nranks(e->comm) > 1;
     hooks = e->altucb != nullptr || e->normscb != nullptr;
     grouped = e->ngroups > 0 && !split_z;
+    ADMM_TRY(plan_penalty());
     if (hooks && alg != 0)
       return fail(ADMM_E_UNSUPPORTED, "caller-supplied options.altu / options.specialnorms with fast ADMM: not supported "
                                       "(admm.m:614 overwrites fast ADMM's v with the norms: q5)");
@@ -200,6 +203,27 @@ struct GeneralLoop {
                 !(e->problem == ADMM_PROB_COVSEL && e->n > kCovselSmallMax);  // (host checks per sweep)
     plan_objective_form();
     plan_tail();
+    return ADMM_OK;
+  }
+
+  // the penalty family.  Every field at its default leaves today's kernels in place, bit for bit; l1 is
+  // read only beside groups, where lambda is the groups' weight.  The finalize takes the whole of g(z) from S_OBJZ.
+  int plan_penalty() {
+    penalized = e->problem == ADMM_PROB_LASSO && !split_z &&
+                (e->pen_w || e->pen_ridge != 0.0 || e->pen_nonneg || (grouped && e->pen_l1 != 0.0));
+    if (!penalized) return ADMM_OK;
+    if (!grouped && len > int64_t{128} * kMaxPartBlocks)
+      return fail(ADMM_E_UNSUPPORTED, "a penalised lasso of more than " + std::to_string(128 * kMaxPartBlocks) +
+                                          " coefficients is not supported");
+    const double l1 = grouped ? e->pen_l1 : e->lambda;
+    pen.w = e->pen_w;
+    pen.tau = l1 / o.rho;
+    pen.kappa = o.rho / (o.rho + e->pen_ridge);
+    pen.l1 = l1;
+    pen.lam_group = grouped ? e->lambda : 0.0;
+    pen.half_mu = 0.5 * e->pen_ridge;
+    pen.nonneg = e->pen_nonneg;
+    if (pa.objz == OBJZ_ABS) fa.obj_scale_z = 1.0;
     return ADMM_OK;
   }
 
@@ -492,7 +516,9 @@ struct GeneralLoop {
 
   // the one-launch tail: the lasso's, or the grouped one of group lasso (its block partials: one per workgroup of the plan)
   void launch_tail(int* nblk, bool defer) {
-    if (grouped) launch_group_prox_fin(pa, fa, e->grp, e->ctrl, nblk, e->stream, defer);
+    if (grouped && penalized) launch_group_penalty_prox_fin(pa, fa, e->grp, pen, e->ctrl, nblk, e->stream, defer);
+    else if (grouped) launch_group_prox_fin(pa, fa, e->grp, e->ctrl, nblk, e->stream, defer);
+    else if (penalized) launch_penalty_prox_fin(pa, fa, pen, e->ctrl, nblk, e->stream, defer);
     else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer);
   }
   FinArgs tail_fin_args(int nblk) {
@@ -507,7 +533,7 @@ struct GeneralLoop {
       ADMM_HIP_TRY(hipMemcpyAsync(e->hk_uold, e->u, sizeof(double) * len, hipMemcpyDeviceToDevice, e->stream));
       if (!split_z) launch_prez_for(ax, e->u, nullptr, nullptr);
     }
-    if (grouped) launch_tail(nblk, true);  // (deferred = the block partials stored plainly: launch_finalize follows)
+    if (grouped || penalized) launch_tail(nblk, true);  // (deferred = the block partials stored plainly: launch_finalize follows)
     else launch_prox(pa, e->ctrl, nblk, e->stream);
     if (e->altucb) {
       launch_negate(e->z, e->hk_bz, len, e->ctrl, e->stream);

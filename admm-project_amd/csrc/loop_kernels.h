@@ -246,6 +246,31 @@ void launch_group_prox_fin(const ProxArgs& a, const FinArgs& f, const GroupPlan&
                            hipStream_t stream, bool defer);
 // out = block soft threshold of v (device pointers), the same device code over the same plan
 void launch_group_soft_threshold(const double* v, const GroupPlan& gp, double t, double* out, hipStream_t stream);
+// ---- the lasso's penalty family (penalty_device.h):
+//   g(z) = l1 * sum_i w_i*|z_i| + lamG * sum_g omega_g*||z_g|| + mu/2*||z||^2 + [z >= 0 when nonneg]
+// prox_{g/rho}(v): e_i = soft(v_i, tau*w_i) (max(v_i - tau*w_i, 0) with nonneg), with groups e_g *= scale_g from ||e_g||
+// and t_g = t*omega_g (group_chunk's rule on the squares of e), z = kappa*e.
+struct PenaltyArgs {
+  const double* w;    // [n] l1 weights on the device, or null: every weight is 1
+  double tau;         // l1 / rho
+  double kappa;       // rho / (rho + mu); mu = 0 gives exactly 1
+  double l1;          // objective: the weight of sum_i w_i*|z_i| (0 drops the term)
+  double lam_group;   // objective: the weight of sum_g omega_g*||z_g|| (grouped form only)
+  double half_mu;     // objective: mu / 2
+  int32_t nonneg;
+};
+// The penalised element update without groups: launch_prox_fin's kernel with z = kappa*e_i formed in a register
+// (PROX_GIVEN) and the whole of g(z) in S_OBJZ (the caller sets FinArgs::obj_scale_z = 1).  defer also serves the
+// iterations that end in a stand-alone finalize (launch_prox's place).  a.len <= 128 * kMaxPartBlocks.
+void launch_penalty_prox_fin(const ProxArgs& a, const FinArgs& f, const PenaltyArgs& pen, Ctrl* ctrl, int* nblk_out,
+                             hipStream_t stream, bool defer);
+// ... and with groups: launch_group_prox_fin with the elementwise stage before the squares go to LDS and kappa behind the
+// scale.  a.t = lambda / rho is the groups' threshold.
+void launch_group_penalty_prox_fin(const ProxArgs& a, const FinArgs& f, const GroupPlan& gp, const PenaltyArgs& pen,
+                                   Ctrl* ctrl, int* nblk_out, hipStream_t stream, bool defer);
+// out = prox_{g/rho}(v) (device pointers): the same device functions; gp = null: no groups.  t = the groups' threshold
+void launch_penalty_prox(const double* v, int64_t n, const GroupPlan* gp, double t, const PenaltyArgs& pen, double* out,
+                         hipStream_t stream);
 // the finalize arguments launch_prox_fin hands to the last workgroup (or, deferred, to the next launch)
 FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f);
 void launch_fast_decide(const FinArgs& a, hipStream_t stream);   // alg 2: d, restart decision, alpha

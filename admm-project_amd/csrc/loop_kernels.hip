@@ -12,6 +12,7 @@
 #include "finalize_device.h"
 #include "prox_device.h"
 #include "group_device.h"
+#include "penalty_device.h"
 #include "tv2d_pixel.h"
 #include "slot_reduce.h"
 
@@ -458,9 +459,13 @@ __device__ __forceinline__ double group_ax(const ProxArgs& a, int64_t ic, int sl
   return ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e];  // (meaningful in slot 0)
 }
 
+// PEN: the instantiation with the elementwise stage of the penalty family in front of the squares (penalty_device.h:
+// e_i = soft(v_i, tau*w_i) or its positive part), kappa behind the scale and the whole of g(z) in S_OBJZ; the plain
+// group lasso compiles without any of it and never reads pen.
+template <bool PEN>
 __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, FinArgs f, GroupPlan gp,
                                                                     Ctrl* __restrict__ ctrl, int32_t defer,
-                                                                    int32_t want_objz) {
+                                                                    int32_t want_objz, PenaltyArgs pen) {
   const int32_t stop = ctrl->stop;
   const int64_t it = ctrl->iter;
   const double aprev = ctrl->acurr;
@@ -477,25 +482,31 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
 #pragma unroll
   for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
   ProxIn in{};
-  double ax = 0.0;
+  double ax = 0.0, wi = 1.0;
   int32_t gi = 0;
   int64_t i = E0 + e;
-  for (int32_t c = 0; c < nch; ++c) {  // ---- pass 1: v and the norms of the groups
+  for (int32_t c = 0; c < nch; ++c) {  // ---- pass 1: v (PEN: e) and the norms of the groups
     const int64_t cs = E0 + static_cast<int64_t>(c) * kTailTile, ce = (cs + kTailTile < E1) ? cs + kTailTile : E1;
     i = cs + e;
     const int64_t ic = i < E1 ? i : E1 - 1;
     if (slot == 0) {
       in = prox_load(a, ic);  // in flight together with the partial rows
       gi = gp.gid[ic] - g0;
+      if constexpr (PEN) wi = penalty_weight(pen, ic);
     }
     ax = group_ax(a, ic, slot, e, quarter);
     if (slot == 0) {
-      const double v = group_prox_v(a, ax, in);
+      double v = group_prox_v(a, ax, in);
+      if constexpr (PEN) v = penalty_elem(v, pen.tau * wi, pen.nonneg);
       sq[e] = i < E1 ? v * v : 0.0;
     }
     __syncthreads();
     const double oz = group_chunk(gp, g0, ng, cs, ce, a.t, sq, gacc);
-    if (want_objz) acc[S_OBJZ] += oz;
+    if constexpr (PEN) {
+      if (want_objz) acc[S_OBJZ] += pen.lam_group * (pen.kappa * oz);  // ||z_g|| = kappa*scale_g*||e_g||
+    } else {
+      if (want_objz) acc[S_OBJZ] += oz;
+    }
     __syncthreads();
   }
   double kcoef = 0.0;
@@ -510,19 +521,26 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
       if (slot == 0) {
         in = prox_load(a, ic);
         gi = gp.gid[ic] - g0;
+        if constexpr (PEN) wi = penalty_weight(pen, ic);
       }
       ax = group_ax(a, ic, slot, e, quarter);
     }
     if (slot == 0 && i < E1) {
-      in.zg_i = group_prox_v(a, ax, in) * gacc[gi];
+      if constexpr (PEN) {
+        const double ei = penalty_elem(group_prox_v(a, ax, in), pen.tau * wi, pen.nonneg);
+        in.zg_i = pen.kappa * (ei * gacc[gi]);
+        if (want_objz) acc[S_OBJZ] += penalty_obj_elem(pen, wi, in.zg_i);
+      } else {
+        in.zg_i = group_prox_v(a, ax, in) * gacc[gi];
+      }
       prox_apply<false>(a, i, ax, it, kcoef, in, acc);
     }
   }
   tail_publish_finalize(acc, a.part, f, ctrl, defer);  // (the two waves that hold elements also hold the group sums)
 }
 
-void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
-                           hipStream_t stream, bool defer) {
+static void launch_group_tail(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, const PenaltyArgs* pen,
+                              Ctrl* ctrl, int* nblk_out, hipStream_t stream, bool defer) {
   // groups exist on ADMM_PROB_LASSO engines only (admm_engine_set_groups) and the grouped update is not used behind a
   // split z-update: args.prox is PROX_SOFT and objx is none or OBJX_SOLVE, so ell, the bounds and zgiven are nulled
   ProxArgs a = pruned_prox_operands(args);
@@ -532,13 +550,91 @@ void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPl
   *nblk_out = gp.nwg;
   FinArgs ff = prox_fin_args(a, f);
   ff.nblk = gp.nwg;
-  hipLaunchKernelGGL(group_prox_fin_kernel, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a, ff, gp,
+  if (pen)
+    hipLaunchKernelGGL(group_prox_fin_kernel<true>, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a, ff,
+                       gp, ctrl, defer ? 1 : 0, want_objz, *pen);
+  else
+    hipLaunchKernelGGL(group_prox_fin_kernel<false>, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a,
+                       ff, gp, ctrl, defer ? 1 : 0, want_objz, PenaltyArgs{});
+}
+
+void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
+                           hipStream_t stream, bool defer) {
+  launch_group_tail(args, f, gp, nullptr, ctrl, nblk_out, stream, defer);
+}
+
+void launch_group_penalty_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, const PenaltyArgs& pen,
+                                   Ctrl* ctrl, int* nblk_out, hipStream_t stream, bool defer) {
+  launch_group_tail(args, f, gp, &pen, ctrl, nblk_out, stream, defer);
+}
+
+// ---------------------------------------------------------------- the penalty family without groups
+// prox_fin_kernel<false> with z = kappa * e_i (penalty_device.h) formed in a register and handed to prox_apply as
+// PROX_GIVEN; the weight is one more coalesced load of slot 0, in flight with the rest.  S_OBJZ takes the whole of g(z).
+__global__ __launch_bounds__(kTailBlock) void penalty_prox_fin_kernel(ProxArgs a, FinArgs f, PenaltyArgs pen,
+                                                                      Ctrl* __restrict__ ctrl, int32_t defer,
+                                                                      int32_t want_objz) {
+  const int32_t stop = ctrl->stop;
+  const int64_t it = ctrl->iter;
+  const double aprev = ctrl->acurr;
+  __shared__ double quarter[kTailSlots - 1][kTailTile];
+  const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kTailTile + e;
+  const int64_t ic = i < a.len ? i : a.len - 1;
+  ProxIn in{};
+  double wi = 1.0;
+  if (slot == 0) {
+    in = prox_load(a, ic);  // in flight together with the partial rows
+    wi = penalty_weight(pen, ic);
+  }
+  const double axq = tail_ax_share(a, ic, static_cast<int32_t>(blockIdx.x), slot);
+  if (stop) return;  // (uniform; nothing has been stored yet)
+  if (slot > 0) quarter[slot - 1][e] = axq;
+  __syncthreads();
+  double acc[S_COUNT];
+#pragma unroll
+  for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
+  if (slot == 0 && i < a.len) {
+    double kcoef = 0.0;
+    if (a.alg == 1) {
+      const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
+      kcoef = (aprev - 1.0) / acn;
+    }
+    const double ax = ((axq + quarter[0][e]) + quarter[1][e]) + quarter[2][e];
+    in.zg_i = pen.kappa * penalty_elem(group_prox_v(a, ax, in), pen.tau * wi, pen.nonneg);
+    if (want_objz) acc[S_OBJZ] += penalty_obj_elem(pen, wi, in.zg_i);
+    prox_apply<false>(a, i, ax, it, kcoef, in, acc);
+  }
+  tail_publish_finalize(acc, a.part, f, ctrl, defer);
+}
+
+void launch_penalty_prox_fin(const ProxArgs& args, const FinArgs& f, const PenaltyArgs& pen, Ctrl* ctrl, int* nblk_out,
+                             hipStream_t stream, bool defer) {
+  ProxArgs a = pruned_prox_operands(args);  // (a lasso engine, as launch_group_prox_fin: PROX_SOFT, no ell, no bounds)
+  a.prox = PROX_GIVEN;  // z reaches prox_apply in a register
+  a.zgiven = nullptr;
+  const int32_t want_objz = a.objz == OBJZ_ABS ? 1 : 0;  // the kernel sums g(z) itself
+  a.objz = OBJZ_NONE;
+  const int64_t blocks = ceil_div(a.len, kTailTile);
+  *nblk_out = static_cast<int>(blocks);
+  const FinArgs ff = prox_fin_args(a, f);
+  hipLaunchKernelGGL(penalty_prox_fin_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, pen,
                      ctrl, defer ? 1 : 0, want_objz);
 }
 
+// out = prox_{g/rho}(v) without groups: the stand-alone operator (ops.hip)
+__global__ __launch_bounds__(kBlock) void penalty_prox_kernel(const double* __restrict__ v, int64_t n, PenaltyArgs pen,
+                                                              double* __restrict__ out) {
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * kBlock)
+    out[i] = pen.kappa * penalty_elem(v[i], pen.tau * penalty_weight(pen, i), pen.nonneg);
+}
+
 // out = v .* scale of its group: the stand-alone operator (ops.hip), one thread per element of a chunk
+template <bool PEN>
 __global__ __launch_bounds__(kGroupTile) void group_soft_threshold_kernel(const double* __restrict__ v, GroupPlan gp,
-                                                                          double t, double* __restrict__ out) {
+                                                                          double t, double* __restrict__ out,
+                                                                          PenaltyArgs pen) {
   __shared__ double sq[kGroupTile];
   __shared__ double gacc[kGroupMaxPerWg];
   const int64_t E0 = gp.wg_e[blockIdx.x], E1 = gp.wg_e[blockIdx.x + 1];
@@ -547,18 +643,32 @@ __global__ __launch_bounds__(kGroupTile) void group_soft_threshold_kernel(const 
   for (int32_t c = 0; c < nch; ++c) {
     const int64_t cs = E0 + static_cast<int64_t>(c) * kGroupTile, ce = (cs + kGroupTile < E1) ? cs + kGroupTile : E1;
     const int64_t i = cs + threadIdx.x;
-    const double vi = i < E1 ? v[i] : 0.0;
+    double vi = i < E1 ? v[i] : 0.0;
+    if constexpr (PEN) vi = i < E1 ? penalty_elem(vi, pen.tau * penalty_weight(pen, i), pen.nonneg) : 0.0;
     sq[threadIdx.x] = vi * vi;
     __syncthreads();
     (void)group_chunk(gp, g0, ng, cs, ce, t, sq, gacc);
     __syncthreads();
   }
-  for (int64_t i = E0 + threadIdx.x; i < E1; i += kGroupTile) out[i] = v[i] * gacc[gp.gid[i] - g0];
+  for (int64_t i = E0 + threadIdx.x; i < E1; i += kGroupTile) {
+    if constexpr (PEN)
+      out[i] = pen.kappa * (penalty_elem(v[i], pen.tau * penalty_weight(pen, i), pen.nonneg) * gacc[gp.gid[i] - g0]);
+    else out[i] = v[i] * gacc[gp.gid[i] - g0];
+  }
 }
 
 void launch_group_soft_threshold(const double* v, const GroupPlan& gp, double t, double* out, hipStream_t stream) {
-  hipLaunchKernelGGL(group_soft_threshold_kernel, dim3(static_cast<unsigned>(gp.nwg)), dim3(kGroupTile), 0, stream, v, gp,
-                     t, out);
+  hipLaunchKernelGGL(group_soft_threshold_kernel<false>, dim3(static_cast<unsigned>(gp.nwg)), dim3(kGroupTile), 0, stream,
+                     v, gp, t, out, PenaltyArgs{});
+}
+
+void launch_penalty_prox(const double* v, int64_t n, const GroupPlan* gp, double t, const PenaltyArgs& pen, double* out,
+                         hipStream_t stream) {
+  if (gp)
+    hipLaunchKernelGGL(group_soft_threshold_kernel<true>, dim3(static_cast<unsigned>(gp->nwg)), dim3(kGroupTile), 0, stream,
+                       v, *gp, t, out, pen);
+  else
+    hipLaunchKernelGGL(penalty_prox_kernel, dim3(grid_blocks(n, kBlock, 2048)), dim3(kBlock), 0, stream, v, n, pen, out);
 }
 
 GroupPlan GroupPlanHost::bind(const double* dev) const {

@@ -229,6 +229,48 @@ int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* size
   return ADMM_OK;
 }
 
+int admm_op_penalty_prox(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups, const double* groupweights,
+                         double lambda_over_rho, const admm_penalty_desc* desc, double rho, double* out) {
+  const auto ok = [](double x) { return x >= 0.0 && x <= 1.79769313486231570e308; };
+  if (!v || !out || n <= 0 || !ok(lambda_over_rho) || !(rho > 0.0) || !ok(rho) || ngroups < 0)
+    return fail(ADMM_E_INVALID, "penalty_prox: bad argument");
+  const admm_penalty_desc none{nullptr, 0.0, 0.0, 0};
+  const admm_penalty_desc& d = desc ? *desc : none;
+  if (!ok(d.l1) || !ok(d.ridge) || (d.nonnegative != 0 && d.nonnegative != 1))
+    return fail(ADMM_E_INVALID, "penalty_prox: l1 and ridge must be finite and >= 0, nonnegative 0 or 1");
+  if (d.l1weights)
+    for (int64_t i = 0; i < n; ++i)
+      if (!ok(d.l1weights[i])) return fail(ADMM_E_INVALID, "penalty_prox: an l1 weight is negative or not finite");
+  const bool groups = sizes && ngroups > 0;
+  GroupPlanHost h;
+  if (groups) ADMM_TRY(group_plan_build(sizes, ngroups, groupweights, n, &h));
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dv, *dout, *dplan = nullptr, *dw = nullptr;
+  ADMM_TRY(sc.alloc(&dv, n));
+  ADMM_TRY(sc.alloc(&dout, n));
+  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
+  if (d.l1weights) {
+    ADMM_TRY(sc.alloc(&dw, n));
+    ADMM_HIP_TRY(hipMemcpy(dw, d.l1weights, sizeof(double) * n, hipMemcpyHostToDevice));
+  }
+  PenaltyArgs pen{};  // (the objective's fields stay 0: the operator forms no objective)
+  pen.w = dw;
+  pen.tau = groups ? d.l1 / rho : lambda_over_rho;  // without groups lambda is the l1 weight itself
+  pen.kappa = rho / (rho + d.ridge);
+  pen.nonneg = d.nonnegative;
+  GroupPlan gp{};
+  if (groups) {
+    ADMM_TRY(sc.alloc(&dplan, h.blob.size()));
+    ADMM_HIP_TRY(hipMemcpy(dplan, h.blob.data(), sizeof(double) * h.blob.size(), hipMemcpyHostToDevice));
+    gp = h.bind(dplan);
+  }
+  launch_penalty_prox(dv, n, groups ? &gp : nullptr, lambda_over_rho, pen, dout, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
 int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32_t form, int64_t ncached,
                  int32_t part_count, double* y) {
   if (!M || !x || !y || n <= 0 || ldM < n || form < 0 || form > 3 || ncached < -1 || part_count < 1 ||

@@ -418,6 +418,25 @@ class Engine:
         anisotropic l1 prox."""
         L.check(self._lib.admm_engine_set_tv2d_isotropic(self._h, int(on)))
 
+    def set_penalty(self, l1weights=None, ridge=0.0, nonnegative=0, l1=0.0):
+        """The lasso's penalty family (admm_engine_set_penalty): per-coefficient l1 weights (n values >= 0), an added
+        ridge term ridge/2*||z||^2 (elastic net), the sign constraint z >= 0 and, beside set_groups, the l1 weight of
+        the sparse-group penalty.  ``set_penalty(None)`` -- every argument at its default -- restores the plain prox."""
+        if l1weights is None and ridge == 0.0 and nonnegative == 0 and l1 == 0.0:
+            L.check(self._lib.admm_engine_set_penalty(self._h, None))
+            return
+        w = None if l1weights is None else np.ascontiguousarray(np.asarray(l1weights, dtype=np.float64).reshape(-1))
+        if w is not None and w.size != self.nB:
+            raise ValueError(f"l1weights has {w.size} entries for {self.nB} coefficients")
+        d = L.PenaltyDesc(None if w is None else L.as_dp(w), float(l1), float(ridge), int(nonnegative))
+        L.check(self._lib.admm_engine_set_penalty(self._h, C.byref(d)))
+
+    def penalty(self):
+        """what set_penalty left in force: dict(l1, ridge, nonnegative, has_l1weights)"""
+        d, has = L.PenaltyDesc(), C.c_int32()
+        L.check(self._lib.admm_engine_get_penalty(self._h, C.byref(d), C.byref(has)))
+        return dict(l1=d.l1, ridge=d.ridge, nonnegative=int(d.nonnegative), has_l1weights=bool(has.value))
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None):

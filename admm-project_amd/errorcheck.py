@@ -85,3 +85,37 @@ def group_sizes(groups, weights, n):
         if not np.all(np.isfinite(w)) or np.any(w < 0):
             raise ValueError("groupweights: every weight must be finite and >= 0")
     return np.ascontiguousarray(g.astype(np.int64)), w
+
+
+PENALTY_KEYS = ("l1weights", "ridge", "nonnegative", "l1")
+
+
+def penalty_fields(src, n):
+    """The penalty family of a lasso (admm_engine_set_penalty) out of a dict of args / options: ``l1weights`` (n finite
+    values >= 0), ``ridge`` and ``l1`` (finite, >= 0), ``nonnegative`` (0 or 1).  Returns the checked fields that were
+    given (None where none was).  Raises before any device work."""
+    given = {k: src[k] for k in PENALTY_KEYS if src.get(k) is not None}
+    if not given:
+        return None
+    out = {}
+    if "l1weights" in given:
+        w = np.ascontiguousarray(np.asarray(given["l1weights"], dtype=np.float64).reshape(-1))
+        if w.size != int(n):
+            raise ValueError(f"l1weights has {w.size} entries for the {int(n)} columns of D")
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("l1weights: every weight must be finite and >= 0")
+        out["l1weights"] = w
+    for key in ("ridge", "l1"):
+        if key in given:
+            v = given[key]
+            if not np.isscalar(v) or not np.isreal(v) or not np.isfinite(v) or v < 0:
+                raise ValueError(f"{key} must be a finite real number >= 0")
+            out[key] = float(v)
+    if "nonnegative" in given:
+        v = given["nonnegative"]
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not np.isscalar(v) or v not in (0, 1):
+            raise ValueError("nonnegative must be 0 or 1")
+        out["nonnegative"] = int(v)
+    return out

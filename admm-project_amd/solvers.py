@@ -13,9 +13,9 @@ import time
 import numpy as np
 
 from .api import admm, getproxops
-from .errorcheck import group_sizes, is_nonnegative_real, is_positive_real, slicemaker
+from .errorcheck import PENALTY_KEYS, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "grouplasso", "lad", "huberfit", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -37,7 +37,8 @@ def _colvec(s, name):
     return s
 
 
-def _engine_args(options, args):
+def _engine_args(options, args, **more):
+    args.update(more)
     for key in ("xsolve", "device", "comm", "cg_tol", "cg_maxit", "objgram"):
         if key in options:
             args[key] = options[key]
@@ -49,6 +50,10 @@ def lasso(D, s, lam, options=None):
 
     minimise 1/2*||D*x - s||_2^2 + lambda*||x||_1.  Setup on the device: Dts = D'*s,
     L = chol(D'*D + rho*I) (tall) or chol(D*D'/rho + I) (fat) (lasso.m:160-176).
+
+    Engine-side extension: ``options['l1weights']`` (n values w_i >= 0: lambda*sum_i w_i*|x_i|),
+    ``options['ridge']`` (mu >= 0: + mu/2*||x||^2, the elastic net) and ``options['nonnegative']`` (1: x >= 0) change
+    the z-update alone; the serial solver only.
     """
     if not isinstance(options, dict):
         raise TypeError("Given options is not a struct! At least pass empty struct!")
@@ -61,6 +66,10 @@ def lasso(D, s, lam, options=None):
     m, n = D.shape
     if s.size != m:
         raise ValueError("The number of rows in argument D do not match size of s!")
+    penalty = penalty_fields({k: options.pop(k, None) for k in PENALTY_KEYS if k != "l1"}, n)
+    if penalty is not None and (options.get("parallel", "none") in ("both", "zming", "xminf") or "comm" in options):
+        raise ValueError("l1weights / ridge / nonnegative have no consensus or row-sharded form: options.parallel / "
+                         "options.comm")
     if options.get("parallel", "none") in ("both", "zming", "xminf"):  # lasso.m:144-156, 193-224
         # consensus lasso: row slices each with their own x_k, u_k and cached factor.  `workers`
         # stands for gcp().NumWorkers (lasso.m:203-207); with options['comm'] D, s are this rank's rows
@@ -75,10 +84,10 @@ def lasso(D, s, lam, options=None):
         options["altu"] = extra["altu"]  # lasso.m:222-223
         options["specialnorms"] = extra["specialnorms"]
     else:
-        args = _engine_args(options, dict(D=D, s=s, m=m, n=n, parallel=0, rho=rho))
+        args = _engine_args(options, dict(D=D, s=s, m=m, n=n, parallel=0, rho=rho), **(penalty or {}))
         args["lambda"] = lam
         minx, minz, _ = getproxops("LASSO", args)
-    options["obj"] = _ENGINE_OBJ  # lasso.m:227  0.5*sum((D*x - s).^2) + lambda*norm(z,1)
+    options["obj"] = _ENGINE_OBJ  # lasso.m:227  0.5*sum((D*x - s).^2) + lambda*norm(z,1)  (+ the penalty family's terms)
     options.update(A=1, At=1, m=n, nA=n, nB=n, B=-1, c=0, parallel="none")  # lasso.m:232-239
     results = admm(minx, minz, options)
     results["solverruntime"] = time.perf_counter() - t0
@@ -91,7 +100,9 @@ def grouplasso(D, s, lam, groups, options=None):
     minimise 1/2*||D*x - s||_2^2 + lambda*sum_g w_g*||x_g||_2 over contiguous groups of coefficients: ``groups`` holds
     their sizes (integers >= 1 that sum to the columns of D), ``options['groupweights']`` the optional w_g >= 0
     (default 1; sqrt(p_g) is the caller's choice).  The x-update and every option are the lasso's; the z-update is the
-    block soft threshold z_g = v_g*max(0, 1 - (lambda*w_g/rho)/||v_g||) on the device (Boyd et al. 6.4.2)."""
+    block soft threshold z_g = v_g*max(0, 1 - (lambda*w_g/rho)/||v_g||) on the device (Boyd et al. 6.4.2).
+    ``options['l1']`` > 0 adds l1*sum_i w_i*|x_i| (the sparse-group lasso); ``options['l1weights']``, ``['ridge']`` and
+    ``['nonnegative']`` are lasso()'s."""
     if not isinstance(options, dict):
         raise TypeError("Given options is not a struct! At least pass empty struct!")
     options = dict(options)
@@ -104,9 +115,10 @@ def grouplasso(D, s, lam, groups, options=None):
     if s.size != m:
         raise ValueError("The number of rows in argument D do not match size of s!")
     sizes, weights = group_sizes(groups, options.pop("groupweights", None), n)
+    penalty = penalty_fields({k: options.pop(k, None) for k in PENALTY_KEYS}, n)
     if options.get("parallel", "none") in ("both", "zming", "xminf") or "comm" in options:
         raise ValueError("grouplasso has no consensus or row-sharded form: options.parallel / options.comm")
-    args = _engine_args(options, dict(D=D, s=s, m=m, n=n, parallel=0, rho=rho, groups=sizes))
+    args = _engine_args(options, dict(D=D, s=s, m=m, n=n, parallel=0, rho=rho, groups=sizes), **(penalty or {}))
     if weights is not None:
         args["groupweights"] = weights
     args["lambda"] = lam
@@ -116,6 +128,15 @@ def grouplasso(D, s, lam, groups, options=None):
     results = admm(minx, minz, options)
     results["solverruntime"] = time.perf_counter() - t0
     return results
+
+
+def elasticnet(D, s, lam, ridge, options=None):
+    """results = elasticnet(D, s, lambda, ridge, options): minimise 1/2*||D*x - s||_2^2 + lambda*||x||_1 +
+    ridge/2*||x||_2^2 -- lasso() with options['ridge'].  The ridge term lives in the z-update
+    (z = rho/(rho + ridge) * soft threshold), so the cached factor of the x-update is the lasso's whatever ridge is."""
+    if not isinstance(options, dict):
+        raise TypeError("Given options is not a struct! At least pass empty struct!")
+    return lasso(D, s, lam, dict(options, ridge=ridge))
 
 
 def _lad_like(kind, D, s, options):

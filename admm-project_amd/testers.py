@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "grouplassotest", "ladtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
+__all__ = ["lassotest", "grouplassotest", "elasticnettest", "ladtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -48,6 +48,21 @@ def grouplassotest(seed=0, rows=2 ** 8, cols=2 ** 6, errtol=1e-3, quiet=1, optio
     xopt = results["xopt"]
     testobj, objopt = obj(testx, testx), obj(xopt, xopt)
     test = dict(D=D, s=s, testx=testx, groups=sizes, testobj=testobj, xopt=xopt, admmopt=results["objopt"], objopt=objopt,
+                failed=int(not objopt < testobj), objerror=abs((testobj - objopt) / objopt), steps=results["steps"])
+    test["lambda"] = lam
+    return results, test
+
+
+def elasticnettest(seed=0, rows=2 ** 8, cols=2 ** 6, ridge=0.5, errtol=1e-3, quiet=1, options=None):
+    """lassotest's shape for elasticnet, on lassotest's problem: pass when obj(xopt) < obj(testx) with
+    obj = 1/2*||D*x - s||^2 + lambda*||x||_1 + ridge/2*||x||^2."""
+    p = synth.lasso_problem(seed, rows, cols)
+    D, s, lam, testx = p["D"], p["s"], p["lam"], p["testx"]
+    obj = lambda x, z: 0.5 * np.sum((D @ x - s) ** 2) + lam * np.sum(np.abs(z)) + 0.5 * ridge * np.sum(z * z)
+    results = solvers.elasticnet(D, s, lam, ridge, _opts(options, objevals=1, quiet=quiet))
+    xopt = results["xopt"]
+    testobj, objopt = obj(testx, testx), obj(xopt, xopt)
+    test = dict(D=D, s=s, testx=testx, ridge=ridge, testobj=testobj, xopt=xopt, admmopt=results["objopt"], objopt=objopt,
                 failed=int(not objopt < testobj), objerror=abs((testobj - objopt) / objopt), steps=results["steps"])
     test["lambda"] = lam
     return results, test

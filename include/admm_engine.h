@@ -324,6 +324,33 @@ int admm_engine_set_constraint_b(admm_engine* eng, const double* B, int64_t ldB,
  * other problem (consensus lasso included), a row-sharded engine.  One group of n elements is one workgroup walking
  * all of them twice per iteration: correct, slow. */
 int admm_engine_set_groups(admm_engine* eng, const int64_t* sizes, int32_t ngroups, const double* weights);
+/* The lasso's penalty family (engine-side extension: DESIGN.md q32).  The z-side term of an ADMM_PROB_LASSO engine is
+ *   g(z) = lambda1 * sum_i l1weights[i]*|z_i| + lambdaG * sum_g omega_g*||z_g||_2 + ridge/2*||z||^2 + [z >= 0 if nonnegative]
+ * Without groups lambda1 is the engine's lambda and the group term is absent; with admm_engine_set_groups in force
+ * lambdaG is the engine's lambda with the groups' weights omega_g, as before, and lambda1 is the field l1 (read only
+ * then).  Adaptive lasso / an unpenalised intercept (l1weights), elastic net (ridge), non-negative lasso (nonnegative)
+ * and the sparse-group lasso (groups + l1) are its members.  Only the z-prox changes, with v = (Ax^ + u) - c:
+ *   e_i = sign(v_i)*max(|v_i| - (lambda1/rho)*l1weights[i], 0)      (nonnegative: max(v_i - (lambda1/rho)*l1weights[i], 0))
+ *   with groups: e_g *= (||e_g|| > t_g ? 1 - t_g/||e_g|| : 0),  t_g = (lambda/rho)*omega_g
+ *   z = rho/(rho + ridge) * e
+ * and objevals reports 1/2*||D*x - s||^2 + g(z).  The x-update and its cached factor (ridge never enters it), every
+ * option and every x-solve form stay the lasso's, with the plain lasso's launches per iteration; a zming callback still
+ * replaces the z-update.  Defaults: l1weights NULL (every weight 1), l1 = 0, ridge = 0, nonnegative = 0 -- with all of
+ * them the engine is the plain (or group) lasso, bit for bit.  desc == NULL restores the defaults.  The call is
+ * independent of the order of admm_engine_set_groups; l1weights (n HOST values) are copied.
+ * ADMM_E_INVALID: a negative or non-finite weight, l1 or ridge; nonnegative outside {0, 1} -- a refused call changes
+ * nothing.  ADMM_E_UNSUPPORTED: any other problem (consensus lasso included), a row-sharded engine; at run time, more
+ * than 131072 coefficients without groups. */
+typedef struct admm_penalty_desc {
+  const double* l1weights;
+  double l1;
+  double ridge;
+  int32_t nonnegative;
+} admm_penalty_desc;
+int admm_engine_set_penalty(admm_engine* eng, const admm_penalty_desc* desc);
+/* what is in force (admm_engine_info_t has no reserved field left): l1, ridge, nonnegative into *desc (its l1weights is
+ * set to NULL) and whether weights are held into *has_l1weights (nullable) */
+int admm_engine_get_penalty(admm_engine* eng, admm_penalty_desc* desc, int32_t* has_l1weights);
 /* Isotropic 2-D total variation (engine-side extension: DESIGN.md q31): with on = 1 an ADMM_PROB_TV2D engine minimises
  * 1/2*||x - s||^2 + lambda * sum_k sqrt((Dx)[k]^2 + (Dx)[N+k]^2), k over the N pixels (the Rudin-Osher-Fatemi norm),
  * instead of the anisotropic lambda*||Dx||_1.  Only the z-update changes: for every pixel k -- those of the last image
@@ -424,6 +451,9 @@ typedef struct admm_binding_info {
   int64_t b_ld;
 } admm_binding_info;
 int admm_binding_get_info(const admm_binding* b, admm_binding_info* info);
+/* a 'lasso' binding also takes the penalty family of admm_engine_set_penalty from its args: `l1weights` (one finite
+ * value >= 0 per column of D), `ridge`, `l1` (finite, >= 0) and `nonnegative` (0 or 1), checked by admm_binding_create
+ * (ADMM_E_INVALID), refused with parallel = 1 (ADMM_E_UNSUPPORTED) and handed to the engine by admm_binding_apply */
 /* after admm_engine_create: a scalar or matrix B goes to the engine (admm_engine_set_constraint_b), and the groups of a
  * 'lasso' binding whose args carry `groups` (group sizes: integers >= 1 that sum to the columns of D) and optionally
  * `groupweights` (one finite value >= 0 per group) go to admm_engine_set_groups.  admm_binding_create checks both vectors
@@ -475,6 +505,13 @@ int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out);
  * 6.4.2; admm_engine_set_groups), the same device code over the same workgroup plan as the loop's element update */
 int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups,
                                  const double* weights, double lambda_over_rho, double* out);
+/* the z-prox of the penalty family (admm_engine_set_penalty) on a host vector, by the same device functions over the
+ * same workgroup plan as the loop's element update.  sizes == NULL / ngroups == 0: no groups, and lambda_over_rho is
+ * the l1 threshold (tau_i = lambda_over_rho * l1weights[i]); with groups lambda_over_rho is theirs (t_g =
+ * lambda_over_rho * groupweights[g]) and tau_i = (desc->l1 / rho) * l1weights[i].  out = rho/(rho + ridge) * e.
+ * desc == NULL: the defaults */
+int admm_op_penalty_prox(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups, const double* groupweights,
+                         double lambda_over_rho, const admm_penalty_desc* desc, double rho, double* out);
 /* out = the pair shrink of isotropic 2-D total variation (admm_engine_set_tv2d_isotropic) over a 2N-vector whose halves
  * are paired: (out[k], out[N+k]) = (v[k], v[N+k]) * (||.|| > t ? 1 - t/||.|| : 0); the device function of the loop */
 int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* out);
