@@ -10,6 +10,6 @@ from .api import ProxOp, admm, getproxops  # noqa: F401
 from .engine import Engine, SvmOvr  # noqa: F401
 from . import testers  # noqa: F401,E402
 from .solvers import (basispursuit, covarianceselection, elasticnet, grouplasso, huberfit, lad, lasso, linearprogram, linearsvm, linearsvm_ovr, model,  # noqa: F401
-                      quadraticprogram, totalvariation, totalvariation2d, unwrappedadmm)
+                      quantilereg, quadraticprogram, totalvariation, totalvariation2d, unwrappedadmm)
 
 __version__ = "0.1.0"

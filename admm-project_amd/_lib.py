@@ -104,6 +104,11 @@ class PenaltyDesc(C.Structure):  # admm_penalty_desc
                 ("nonnegative", C.c_int32)]
 
 
+class LossDesc(C.Structure):  # admm_loss_desc
+    _fields_ = [("weights", C.POINTER(C.c_double)), ("slope_pos", C.c_double), ("slope_neg", C.c_double),
+                ("epsilon", C.c_double), ("delta", C.c_double)]
+
+
 class EngineInfo(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("xsolve_requested", C.c_int32), ("xsolve_used", C.c_int32),
@@ -182,6 +187,8 @@ _SIGNATURES = {
     "admm_engine_set_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, _dp]),
     "admm_engine_set_penalty": (C.c_int, [C.c_void_p, C.POINTER(PenaltyDesc)]),
     "admm_engine_get_penalty": (C.c_int, [C.c_void_p, C.POINTER(PenaltyDesc), C.POINTER(C.c_int32)]),
+    "admm_engine_set_loss": (C.c_int, [C.c_void_p, C.POINTER(LossDesc)]),
+    "admm_engine_get_loss": (C.c_int, [C.c_void_p, C.POINTER(LossDesc), C.POINTER(C.c_int32)]),
     "admm_engine_set_tv2d_isotropic": (C.c_int, [C.c_void_p, C.c_int32]),
     "admm_engine_run": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(RunSummary)]),
     "admm_engine_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -214,6 +221,7 @@ _SIGNATURES = {
     "admm_op_group_soft_threshold": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_double, _dp]),
     "admm_op_penalty_prox": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_double,
                                        C.POINTER(PenaltyDesc), C.c_double, _dp]),
+    "admm_op_loss_prox": (C.c_int, [_dp, C.c_int64, C.c_int32, C.POINTER(LossDesc), C.c_double, _dp]),
     "admm_op_symv": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp]),
     "admm_op_symv_batch": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int64, C.c_int64, _dp, C.c_int64]),
     "admm_op_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_double, _dp, C.c_int64, _dp,

@@ -159,8 +159,14 @@ def getproxops(problem, args):
         D, s = _get(args, "D"), _get(args, "s")
         m, n = D.shape
         code = L.PROB_LAD if kind == "lad" else L.PROB_HUBERFIT
+        from .errorcheck import loss_fields  # the loss family (engine-side extension)
+        loss = loss_fields(args, m, kind)
+        if loss is not None and comm is not None:
+            raise L.AdmmError(L.E_UNSUPPORTED, "args.weights / tau / slopes / epsilon / delta on a row-sharded engine")
         eng = Engine(code, D=D, s=s, Lfactor=args.get("R"), userelax=int(bool(args.get("userelax", 0))),
                      xsolve=xs, device=dev, comm=comm, **cg)
+        if loss is not None:
+            eng.set_loss(**loss)
         prob = _Problem(kind, eng, dict(A="D", c="s", nA=n, nB=m))
     elif kind == "linearsvm":
         D, ell, Cval = _get(args, "D"), _get(args, "ell"), _get(args, "C")

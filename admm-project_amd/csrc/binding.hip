@@ -24,6 +24,9 @@ struct admm_binding {
   double pen_l1 = 0.0, pen_ridge = 0.0;  // args.l1, args.ridge
   int32_t pen_nonneg = 0;                // args.nonnegative
   bool has_penalty = false;              // any of the four was given (admm_engine_set_penalty)
+  std::vector<double> lossweights;  // args.weights of 'lad' / 'huberfit' (one per row of D; empty: every weight 1), copied
+  double loss_a = 1.0, loss_b = 1.0, loss_eps = 0.0, loss_delta = 1.0;  // args.slopes / args.tau, args.epsilon, args.delta
+  bool has_loss = false;            // any of them was given (admm_engine_set_loss)
   int32_t tv2d_isotropic = 0;     // args.isotropic of totalvariation2d (admm_engine_set_tv2d_isotropic)
   std::vector<double> zeros;      // c = 0 for the engines that take c as a data vector
   int64_t nA = 0, nB = 0;         // lengths of x and of z
@@ -190,6 +193,47 @@ int describe(const std::string& p, const View& args, const View& handles, admm_b
     d.userelax = static_cast<int32_t>(args.scalar("userelax", 0.0));
     b.nA = d.n;
     b.nB = d.m;
+    // the loss family (engine-side extension, admm_engine_set_loss): args.weights, args.tau | args.slopes, args.epsilon
+    // ('lad'), args.delta ('huberfit') -- element counts and values are checked here
+    if (args.get("weights") || args.get("tau") || args.get("slopes") || args.get("epsilon") || args.get("delta")) {
+      if (args.get("weights")) {
+        size_t k = 0;
+        const double* w = args.vec("weights", &k);
+        if (!w || k != static_cast<size_t>(d.m)) return fail(ADMM_E_INVALID, "args.weights must have one entry per row of D");
+        for (size_t i = 0; i < k; ++i)
+          if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
+            return fail(ADMM_E_INVALID, "args.weights: every weight must be finite and >= 0");
+        b.lossweights.assign(w, w + k);
+      }
+      if (args.get("tau") && args.get("slopes")) return fail(ADMM_E_INVALID, "args.tau beside args.slopes: give one of them");
+      if (args.get("tau")) {
+        const double tau = args.scalar("tau", std::nan(""));
+        if (!(tau > 0.0 && tau < 1.0)) return fail(ADMM_E_INVALID, "args.tau must lie strictly inside (0, 1)");
+        b.loss_a = tau;
+        b.loss_b = 1.0 - tau;
+      }
+      if (args.get("slopes")) {
+        size_t k = 0;
+        const double* sl = args.vec("slopes", &k);
+        if (!sl || k != 2 || !(sl[0] > 0.0) || !(sl[1] > 0.0) || !std::isfinite(sl[0]) || !std::isfinite(sl[1]))
+          return fail(ADMM_E_INVALID, "args.slopes must hold two finite values > 0");
+        b.loss_a = sl[0];
+        b.loss_b = sl[1];
+      }
+      if (args.get("epsilon")) {
+        const double eps = args.scalar("epsilon", std::nan(""));
+        if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(ADMM_E_INVALID, "args.epsilon must be a finite real scalar >= 0");
+        if (p == "huberfit" && eps != 0.0) return fail(ADMM_E_INVALID, "args.epsilon belongs to 'lad', not to 'huberfit'");
+        b.loss_eps = eps;
+      }
+      if (args.get("delta")) {
+        const double delta = args.scalar("delta", std::nan(""));
+        if (!(delta > 0.0) || !std::isfinite(delta)) return fail(ADMM_E_INVALID, "args.delta must be a finite real scalar > 0");
+        if (p == "lad" && delta != 1.0) return fail(ADMM_E_INVALID, "args.delta belongs to 'huberfit', not to 'lad'");
+        b.loss_delta = delta;
+      }
+      b.has_loss = true;
+    }
   } else if (p == "linearsvm") {
     if (!haveD) return fail(ADMM_E_INVALID, needD);
     d.problem = ADMM_PROB_LINEARSVM;
@@ -405,6 +449,11 @@ int admm_binding_apply(const admm_binding* b, admm_engine* e) {
   if (b->has_penalty) {
     const admm_penalty_desc pd{b->l1weights.empty() ? nullptr : b->l1weights.data(), b->pen_l1, b->pen_ridge, b->pen_nonneg};
     ADMM_TRY(admm_engine_set_penalty(e, &pd));
+  }
+  if (b->has_loss) {
+    const admm_loss_desc ld{b->lossweights.empty() ? nullptr : b->lossweights.data(), b->loss_a, b->loss_b, b->loss_eps,
+                            b->loss_delta};
+    ADMM_TRY(admm_engine_set_loss(e, &ld));
   }
   if (b->b_kind == 1 || b->b_kind == 2)
     return admm_engine_set_constraint_b(e, b->b_matrix, b->b_ld, b->b_kind == 2 ? b->nB : 0, ADMM_MEM_HOST, b->b_scalar,

@@ -231,6 +231,9 @@ struct admm_engine {
   double pen_l1 = 0.0;        // the l1 weight beside the groups (read only while groups are in force)
   double pen_ridge = 0.0;     // mu
   int32_t pen_nonneg = 0;
+  // the loss family of the LAD / Huber engines (admm_engine_set_loss): defaults = today's prox, bit for bit
+  double* loss_w = nullptr;   // [len] weights, or null: every weight is 1
+  double loss_a = 1.0, loss_b = 1.0, loss_eps = 0.0, loss_delta = 1.0;
   double* part = nullptr;     // [S_COUNT][kMaxPartBlocks]
   double* objpart = nullptr;  // [kMaxPartBlocks]
   Ctrl* ctrl = nullptr;

@@ -630,6 +630,42 @@ int admm_engine_get_penalty(admm_engine* e, admm_penalty_desc* out, int32_t* has
   return ADMM_OK;
 }
 
+int admm_engine_set_loss(admm_engine* e, const admm_loss_desc* d) {
+  if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
+  if (e->problem != ADMM_PROB_LAD && e->problem != ADMM_PROB_HUBERFIT)
+    return fail(ADMM_E_INVALID, "the loss family belongs to ADMM_PROB_LAD and ADMM_PROB_HUBERFIT: it replaces the prox of "
+                                "their z-update");
+  if (e->comm) return fail(ADMM_E_UNSUPPORTED, "the loss family is not supported on row-sharded engines");
+  if (e->xsolve == ADMM_XSOLVE_CALLBACK)
+    return fail(ADMM_E_UNSUPPORTED, "the loss family is not supported on the generic callback engine");
+  if (d) ADMM_TRY(check_loss_desc(e->problem, *d, e->len));  // (a refused call changes nothing)
+  ADMM_HIP_TRY(hipSetDevice(e->device));
+  double* w = nullptr;
+  if (d && d->weights) {
+    ADMM_TRY(e->mem.alloc(&w, static_cast<size_t>(e->len)));
+    ADMM_HIP_TRY(hipMemcpyAsync(w, d->weights, sizeof(double) * e->len, hipMemcpyHostToDevice, e->stream));
+  }
+  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (the caller's weights are read until here; no run uses the old ones)
+  if (e->loss_w) e->mem.free_one(e->loss_w);
+  e->loss_w = w;
+  e->loss_a = d ? d->slope_pos : 1.0;
+  e->loss_b = d ? d->slope_neg : 1.0;
+  e->loss_eps = d ? d->epsilon : 0.0;
+  e->loss_delta = d ? d->delta : 1.0;
+  return ADMM_OK;
+}
+
+int admm_engine_get_loss(admm_engine* e, admm_loss_desc* out, int32_t* has_weights) {
+  if (!e || !out) return fail(ADMM_E_INVALID, "NULL argument");
+  out->weights = nullptr;
+  out->slope_pos = e->loss_a;
+  out->slope_neg = e->loss_b;
+  out->epsilon = e->loss_eps;
+  out->delta = e->loss_delta;
+  if (has_weights) *has_weights = e->loss_w ? 1 : 0;
+  return ADMM_OK;
+}
+
 int admm_engine_set_tv2d_isotropic(admm_engine* e, int32_t on) {
   if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
   if (e->problem != ADMM_PROB_TV2D)

@@ -140,6 +140,8 @@ struct GeneralLoop {
   bool grouped = false;  // group lasso: the grouped element update wherever the lasso's own runs (a zming callback wins)
   bool penalized = false;  // a non-default admm_engine_set_penalty: the penalised element update in the same places
   PenaltyArgs pen{};
+  bool lossy = false;  // a non-default admm_engine_set_loss: the LOSS instantiation wherever LAD's / Huber's element update runs
+  LossArgs loss{};
 
   // ---- may change at a batch boundary (after_batch: nothing is pending there, so the launch sequence may change)
   bool gram_now = false, gram_calibrating = false, obj_kernels = false;
@@ -177,6 +179,7 @@ struct GeneralLoop {
     hooks = e->altucb != nullptr || e->normscb != nullptr;
     grouped = e->ngroups > 0 && !split_z;
     ADMM_TRY(plan_penalty());
+    plan_loss();
     if (hooks && alg != 0)
       return fail(ADMM_E_UNSUPPORTED, "caller-supplied options.altu / options.specialnorms with fast ADMM: not supported "
                                       "(admm.m:614 overwrites fast ADMM's v with the norms: q5)");
@@ -226,6 +229,18 @@ struct GeneralLoop {
     if (pa.objz == OBJZ_ABS) fa.obj_scale_z = 1.0;
     return ADMM_OK;
   }
+
+  // the loss family.  Every field at its default leaves today's kernels in place, bit for bit; a zming
+  // callback (split_z) replaces the z-update as before.  The finalize takes the whole of g(z) from S_OBJZ.
+  void plan_loss() {
+    const bool huber = e->problem == ADMM_PROB_HUBERFIT;
+    lossy = (huber || e->problem == ADMM_PROB_LAD) && !split_z &&
+            (e->loss_w || e->loss_a != 1.0 || e->loss_b != 1.0 || e->loss_eps != 0.0 || e->loss_delta != 1.0);
+    if (!lossy) return;
+    loss = LossArgs{e->loss_w, e->loss_a, e->loss_b, e->loss_eps, e->loss_delta, o.rho, huber ? 1 : 0, 0};
+    if (pa.objz != OBJZ_NONE) fa.obj_scale_z = 1.0;
+  }
+  const LossArgs* loss_args() const { return lossy ? &loss : nullptr; }
 
   void plan_objective_form() {
     // the lasso objective through the cached Gram matrix: always (obj_gram = 1), or once the calibration of the first
@@ -378,7 +393,7 @@ struct GeneralLoop {
       pa.ax_t = nullptr;
       pa.ax_tri = 0;
       pa.x_out = nullptr;
-      launch_ad_onepass(opa, pa, e->ctrl, &nblk, e->stream);
+      launch_ad_onepass(opa, pa, e->ctrl, &nblk, e->stream, loss_args());
     }
     dff = prox_fin_args(pa, fa);
     dff.nblk = nblk;
@@ -519,7 +534,7 @@ struct GeneralLoop {
     if (grouped && penalized) launch_group_penalty_prox_fin(pa, fa, e->grp, pen, e->ctrl, nblk, e->stream, defer);
     else if (grouped) launch_group_prox_fin(pa, fa, e->grp, e->ctrl, nblk, e->stream, defer);
     else if (penalized) launch_penalty_prox_fin(pa, fa, pen, e->ctrl, nblk, e->stream, defer);
-    else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer);
+    else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer, loss_args());
   }
   FinArgs tail_fin_args(int nblk) {
     FinArgs d = prox_fin_args(pa, fa);
@@ -534,7 +549,7 @@ struct GeneralLoop {
       if (!split_z) launch_prez_for(ax, e->u, nullptr, nullptr);
     }
     if (grouped || penalized) launch_tail(nblk, true);  // (deferred = the block partials stored plainly: launch_finalize follows)
-    else launch_prox(pa, e->ctrl, nblk, e->stream);
+    else launch_prox(pa, e->ctrl, nblk, e->stream, loss_args());
     if (e->altucb) {
       launch_negate(e->z, e->hk_bz, len, e->ctrl, e->stream);
       if (e->altucb(e->altuuser, e->hk_uold, e->xh, e->hk_bz, e->c ? e->c : e->hk_zero, len, e->hk_unew,

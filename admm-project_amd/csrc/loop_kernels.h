@@ -205,11 +205,29 @@ ProxArgs pruned_prox_operands(const ProxArgs& a);
 // PROX_PAIR pairs the two halves of the vector: len must be even.  A caller checks this before launch_prox (which
 // returns nothing); c and relaxation go into both elements' v as for every other prox.
 inline bool prox_pair_ok(const ProxArgs& a) { return a.len > 0 && (a.len & 1) == 0; }
-void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream);
+// ---- the loss family of the LAD and Huber engines (loss_device.h): g(z) = sum_i w_i*phi(z_i) with
+//   LAD:   phi(z) = a*max(z - eps, 0) + b*max(-z - eps, 0)        (quantile: a = tau, b = 1 - tau; SVR: eps > 0)
+//   Huber: phi(z) = (z >= 0 ? a : b)*H_delta(z)
+// A launcher that gets one runs the LOSS instantiation of its kernel: z is formed in a register ahead of prox_apply
+// (PROX_GIVEN) and S_OBJZ takes the whole of g(z) (the caller sets FinArgs::obj_scale_z = 1).  Null: today's kernels.
+struct LossArgs {
+  const double* w;   // [len] weights on the device, or null: every weight is 1
+  double a, b;       // slopes of the positive and the negative side
+  double eps;        // LAD engine: the dead zone
+  double delta;      // Huber engine: the threshold
+  double rho;
+  int32_t huber;     // 0: the LAD engine's phi, 1: the Huber engine's
+  int32_t want_obj;  // sum g(z) into S_OBJZ (set by the launchers from ProxArgs::objz)
+};
+// the checks admm_engine_set_loss and admm_op_loss_prox share (ops.hip); len HOST weights when d.weights is set
+int check_loss_desc(int32_t problem, const admm_loss_desc& d, int64_t len);
+void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss = nullptr);
 // A = I, alg 0 / 1: z/u update AND the finalize logic in one launch (the last workgroup to arrive finalizes);
 // a.len <= 128 * kMaxPartBlocks
 void launch_prox_fin(const ProxArgs& a, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                     bool defer = false);
+                     bool defer = false, const LossArgs* loss = nullptr);
+// out = prox_{g/rho}(v) of the loss family (device pointers): loss_device.h's function, one thread per element
+void launch_loss_prox(const double* v, int64_t n, const LossArgs& loss, double* out, hipStream_t stream);
 // ---- group lasso: z_g = v_g * (||v_g|| > t_g ? 1 - t_g/||v_g|| : 0), t_g = t * w_g, over a partition of
 // the elements into G contiguous groups.  The norm of a group is needed before any of its elements can be written, so
 // the element update is planned by groups: whole groups are packed into a workgroup up to `budget` elements (and
@@ -337,7 +355,8 @@ struct OnePassArgs {
 };
 bool onepass_supported(int64_t m, int64_t n);
 int onepass_workgroups(int64_t m);
-void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pa, const Ctrl* ctrl, int* nblk_out, hipStream_t stream);
+void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pa, const Ctrl* ctrl, int* nblk_out, hipStream_t stream,
+                       const LossArgs* loss = nullptr);
 
 // State of the caller's z when options.B is general (the loop's z buffers hold w = -B*z): after zming returned znew,
 // zprev <- z, z <- znew, zvals(:, i) = znew and -- fast ADMM -- v = z + coef*(z - zprev) (admm.m:568, 579) or the

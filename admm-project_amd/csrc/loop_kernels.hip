@@ -13,13 +13,18 @@
 #include "prox_device.h"
 #include "group_device.h"
 #include "penalty_device.h"
+#include "loss_device.h"
 #include "tv2d_pixel.h"
 #include "slot_reduce.h"
 
 namespace admm {
 
-template <bool LOGI>
-__global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __restrict__ ctrl) {
+// Loss = LossArgs: the instantiation of the loss family (loss_device.h): the weight travels with
+// prox_load's round trip and z reaches prox_apply in a register (PROX_GIVEN).  The pack is empty for every other
+// instantiation: those keep their parameter list and their code, instruction for instruction.
+template <bool LOGI, class... Loss>
+__global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __restrict__ ctrl, Loss... la) {
+  constexpr bool LOSS = sizeof...(Loss) != 0;
   // the three control words in one scalar round trip, before the branch
   const int32_t stop = ctrl->stop;
   const int64_t it = ctrl->iter;
@@ -35,9 +40,17 @@ __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __
   }
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.len;
        i += static_cast<int64_t>(gridDim.x) * kBlock) {
-    const ProxIn in = prox_load(a, i);
-    const double ax = gather_chunks(a.axsrc, a.naxpart, a.axld, i);
-    prox_apply<LOGI>(a, i, ax, it, kcoef, in, acc);
+    if constexpr (LOSS) {
+      ProxIn in = prox_load(a, i);
+      const double wi = loss_weight(loss_of(la...), a.z, i);
+      const double ax = gather_chunks(a.axsrc, a.naxpart, a.axld, i);
+      loss_form_z(a, loss_of(la...), wi, ax, in, acc);
+      prox_apply<false>(a, i, ax, it, kcoef, in, acc);
+    } else {
+      const ProxIn in = prox_load(a, i);
+      const double ax = gather_chunks(a.axsrc, a.naxpart, a.axld, i);
+      prox_apply<LOGI>(a, i, ax, it, kcoef, in, acc);
+    }
   }
   __shared__ double sred[4][S_COUNT];
   block_reduce_slots<4>(acc, sred, a.part, kMaxPartBlocks, blockIdx.x);
@@ -159,7 +172,27 @@ ProxArgs pruned_prox_operands(const ProxArgs& args) {
   return a;
 }
 
-void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
+// the operands of a LOSS instantiation: z reaches prox_apply in a register and the kernel sums g(z) itself (a LAD or
+// Huber engine: PROX_SOFT / PROX_HUBER, no ell, no bounds)
+static ProxArgs loss_prox_operands(const ProxArgs& args, const LossArgs& loss, LossArgs* la) {
+  ProxArgs a = pruned_prox_operands(args);
+  a.prox = PROX_GIVEN;
+  a.zgiven = nullptr;
+  *la = loss;
+  la->want_obj = a.objz != OBJZ_NONE ? 1 : 0;
+  a.objz = OBJZ_NONE;
+  return a;
+}
+
+void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss) {
+  if (loss) {
+    LossArgs la;
+    const ProxArgs al = loss_prox_operands(args, *loss, &la);
+    const int lblocks = grid_blocks(al.len, kBlock, kMaxPartBlocks);
+    *nblk_out = lblocks;
+    hipLaunchKernelGGL((prox_kernel<false, LossArgs>), dim3(lblocks), dim3(kBlock), 0, stream, al, ctrl, la);
+    return;
+  }
   const ProxArgs a = pruned_prox_operands(args);
   if (a.prox == PROX_PAIR) {  // one thread per pair; len is even (prox_pair_ok: the caller has checked)
     ProxArgs ap = a;
@@ -384,9 +417,11 @@ __device__ __forceinline__ void tail_publish_finalize(const double (&acc)[S_COUN
 
 // defer = 1: the finalize logic is NOT run here; the block partials are stored plainly and the next launch on the
 // stream (the x-solve of the next iteration, or a stand-alone finalize) takes them after the kernel boundary.
-template <bool LOGI>
+// Loss: as prox_kernel's.
+template <bool LOGI, class... Loss>
 __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArgs f, Ctrl* __restrict__ ctrl,
-                                                              int32_t defer) {
+                                                              int32_t defer, Loss... la) {
+  constexpr bool LOSS = sizeof...(Loss) != 0;
   const int32_t stop = ctrl->stop;
   const int64_t it = ctrl->iter;
   const double aprev = ctrl->acurr;
@@ -397,7 +432,11 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kTailTile + e;
   const int64_t ic = i < a.len ? i : a.len - 1;
   ProxIn in{};
-  if (slot == 0) in = prox_load(a, ic);  // in flight together with the partial rows
+  double wi = 1.0;
+  if (slot == 0) {
+    in = prox_load(a, ic);  // in flight together with the partial rows
+    if constexpr (LOSS) wi = loss_weight(loss_of(la...), a.z, ic);
+  }
   // (kTailTile = the x-solve's tile: one diagonal tile per workgroup)
   const double ax = tail_ax_share(a, ic, static_cast<int32_t>(blockIdx.x), slot);
   if (stop) return;  // (uniform; nothing has been stored yet)
@@ -412,7 +451,13 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
       const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
       kcoef = (aprev - 1.0) / acn;
     }
-    prox_apply<LOGI>(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
+    if constexpr (LOSS) {
+      const double axs = ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e];
+      loss_form_z(a, loss_of(la...), wi, axs, in, acc);
+      prox_apply<false>(a, i, axs, it, kcoef, in, acc);
+    } else {
+      prox_apply<LOGI>(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
+    }
   }
   tail_publish_finalize(acc, a.part, f, ctrl, defer);
 }
@@ -429,7 +474,16 @@ FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
 }
 
 void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                     bool defer) {
+                     bool defer, const LossArgs* loss) {
+  if (loss) {
+    LossArgs la;
+    const ProxArgs al = loss_prox_operands(args, *loss, &la);
+    const int64_t lblocks = ceil_div(al.len, kTailTile);
+    *nblk_out = static_cast<int>(lblocks);
+    hipLaunchKernelGGL((prox_fin_kernel<false, LossArgs>), dim3(static_cast<unsigned>(lblocks)), dim3(kTailBlock), 0, stream, al,
+                       prox_fin_args(al, f), ctrl, defer ? 1 : 0, la);
+    return;
+  }
   const ProxArgs a = pruned_prox_operands(args);
   const int64_t blocks = ceil_div(a.len, kTailTile);
   *nblk_out = static_cast<int>(blocks);
@@ -440,6 +494,18 @@ void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nb
   else
     hipLaunchKernelGGL(prox_fin_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, ctrl,
                        defer ? 1 : 0);
+}
+
+// out = prox_{g/rho}(v) of the loss family: the stand-alone operator (ops.hip)
+__global__ __launch_bounds__(kBlock) void loss_prox_kernel(const double* __restrict__ v, int64_t n, LossArgs la,
+                                                           double* __restrict__ out) {
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * kBlock)
+    out[i] = loss_prox_elem(la, la.w ? la.w[i] : 1.0, v[i]);
+}
+
+void launch_loss_prox(const double* v, int64_t n, const LossArgs& loss, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(loss_prox_kernel, dim3(grid_blocks(n, kBlock, 2048)), dim3(kBlock), 0, stream, v, n, loss, out);
 }
 
 // ---------------------------------------------------------------- group lasso: the grouped one-launch tail

@@ -65,6 +65,29 @@ int put_padded(double* dst, int64_t npad, const double* src, int64_t n, int64_t 
 
 }  // namespace
 
+namespace admm {
+
+// the checks admm_engine_set_loss and admm_op_loss_prox share; len weights when desc->weights is set
+int check_loss_desc(int32_t problem, const admm_loss_desc& d, int64_t len) {
+  const auto fin = [](double v) { return v >= 0.0 && v <= 1.79769313486231570e308; };  // finite, >= 0, not NaN
+  if (problem != ADMM_PROB_LAD && problem != ADMM_PROB_HUBERFIT)
+    return fail(ADMM_E_INVALID, "the loss family belongs to ADMM_PROB_LAD and ADMM_PROB_HUBERFIT");
+  if (!(d.slope_pos > 0.0) || !fin(d.slope_pos) || !(d.slope_neg > 0.0) || !fin(d.slope_neg))
+    return fail(ADMM_E_INVALID, "loss: both slopes must be finite and > 0");
+  if (!fin(d.epsilon)) return fail(ADMM_E_INVALID, "loss: epsilon must be finite and >= 0");
+  if (!(d.delta > 0.0) || !fin(d.delta)) return fail(ADMM_E_INVALID, "loss: delta must be finite and > 0");
+  if (problem == ADMM_PROB_HUBERFIT && d.epsilon != 0.0)
+    return fail(ADMM_E_INVALID, "loss: epsilon belongs to the LAD engine (a Huber engine takes 0)");
+  if (problem == ADMM_PROB_LAD && d.delta != 1.0)
+    return fail(ADMM_E_INVALID, "loss: delta belongs to the Huber engine (a LAD engine takes 1)");
+  if (d.weights)
+    for (int64_t i = 0; i < len; ++i)
+      if (!fin(d.weights[i])) return fail(ADMM_E_INVALID, "loss: weight " + std::to_string(i) + " is negative or not finite");
+  return ADMM_OK;
+}
+
+}  // namespace admm
+
 extern "C" {
 
 int admm_op_gemv_n(const double* D, int64_t m, int64_t n, int64_t ldD, const double* x, double* y) {
@@ -268,6 +291,29 @@ int admm_op_penalty_prox(const double* v, int64_t n, const int64_t* sizes, int32
   launch_penalty_prox(dv, n, groups ? &gp : nullptr, lambda_over_rho, pen, dout, nullptr);
   ADMM_HIP_TRY(hipDeviceSynchronize());
   ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
+int admm_op_loss_prox(const double* v, int64_t len, int32_t problem, const admm_loss_desc* desc, double rho, double* out) {
+  if (!v || !out || len <= 0 || !(rho > 0.0) || !(rho <= 1.79769313486231570e308))
+    return fail(ADMM_E_INVALID, "loss_prox: bad argument");
+  const admm_loss_desc none{nullptr, 1.0, 1.0, 0.0, 1.0};
+  const admm_loss_desc& d = desc ? *desc : none;
+  ADMM_TRY(check_loss_desc(problem, d, len));
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dv, *dout, *dw = nullptr;
+  ADMM_TRY(sc.alloc(&dv, len));
+  ADMM_TRY(sc.alloc(&dout, len));
+  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * len, hipMemcpyHostToDevice));
+  if (d.weights) {
+    ADMM_TRY(sc.alloc(&dw, len));
+    ADMM_HIP_TRY(hipMemcpy(dw, d.weights, sizeof(double) * len, hipMemcpyHostToDevice));
+  }
+  const LossArgs la{dw, d.slope_pos, d.slope_neg, d.epsilon, d.delta, rho, problem == ADMM_PROB_HUBERFIT ? 1 : 0, 0};
+  launch_loss_prox(dv, len, la, dout, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * len, hipMemcpyDeviceToHost));
   return ADMM_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "kernels.h"
 #include "loop_kernels.h"
 #include "prox_device.h"
+#include "loss_device.h"
 #include "wave_reduce.h"
 
 namespace admm {
@@ -256,9 +257,12 @@ void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl,
 // that records no dual residual (unwrappedadmm.m:92 / nodualerror: no D'*(z - zprev), no D'*u) and plain ADMM.
 constexpr int kOpRows = 64, kOpWaves = 8, kOpCols = 56, kOpMaxN = kOpWaves * kOpCols;  // 448
 
-template <bool LOGI>
+// Loss = LossArgs: the instantiation of the loss family (loss_device.h), as prox_kernel's; an empty pack
+// everywhere else.
+template <bool LOGI, class... Loss>
 __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs a, ProxArgs pa,
-                                                                    const Ctrl* __restrict__ ctrl) {
+                                                                    const Ctrl* __restrict__ ctrl, Loss... la) {
+  constexpr bool LOSS = sizeof...(Loss) != 0;
   if (ctrl->stop) return;
   const int64_t it = ctrl->iter;
   __shared__ double xs[kOpMaxN], gacc[kOpMaxN];
@@ -288,7 +292,11 @@ __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs
       d[k] = drow[(j < n ? j : n - 1) * a.ldD];
     }
     ProxIn in{};
-    if (w == 0) in = prox_load(pa, rc);  // in flight with the block
+    double wi = 1.0;
+    if (w == 0) {
+      in = prox_load(pa, rc);  // in flight with the block
+      if constexpr (LOSS) wi = loss_weight(loss_of(la...), pa.z, rc);
+    }
     double p = 0.0;
 #pragma unroll
     for (int k = 0; k < kOpCols; ++k) p = __builtin_fma(d[k], xs[w + kOpWaves * k], p);
@@ -299,7 +307,14 @@ __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs
 #pragma unroll
       for (int q = 1; q < kOpWaves; ++q) ax += axr[q][lane];
       double t = 0.0;
-      if (r < m) prox_apply<LOGI>(pa, r, ax, it, 0.0, in, acc, &t);
+      if constexpr (LOSS) {
+        if (r < m) {
+          loss_form_z(pa, loss_of(la...), wi, ax, in, acc);
+          prox_apply<false>(pa, r, ax, it, 0.0, in, acc, &t);
+        }
+      } else {
+        if (r < m) prox_apply<LOGI>(pa, r, ax, it, 0.0, in, acc, &t);
+      }
       tsh[lane] = t;  // rows beyond m contribute nothing
     }
     __syncthreads();
@@ -338,14 +353,23 @@ int onepass_workgroups(int64_t m) {
   return static_cast<int>(std::min<int64_t>(nblocks, 256));  // one per CU: a block is 205 KB of registers' worth of loads
 }
 
-void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pargs, const Ctrl* ctrl, int* nblk_out, hipStream_t stream) {
+void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pargs, const Ctrl* ctrl, int* nblk_out, hipStream_t stream,
+                       const LossArgs* loss) {
   ProxArgs pa = pruned_prox_operands(pargs);
   pa.rhs_add = nullptr;
   pa.rhs = nullptr;  // t = c + z - u never leaves the kernel
   pa.dz = nullptr;
   const int nwg = onepass_workgroups(a.m);
   *nblk_out = nwg;
-  if (prox_is_logistic(pa))
+  if (loss) {  // z reaches prox_apply in a register and the kernel sums g(z) itself (a LAD or Huber engine)
+    LossArgs la = *loss;
+    la.want_obj = pa.objz != OBJZ_NONE ? 1 : 0;
+    pa.prox = PROX_GIVEN;
+    pa.zgiven = nullptr;
+    pa.objz = OBJZ_NONE;
+    hipLaunchKernelGGL((ad_onepass_kernel<false, LossArgs>), dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream,
+                       a, pa, ctrl, la);
+  } else if (prox_is_logistic(pa))
     hipLaunchKernelGGL(ad_onepass_kernel<true>, dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream, a, pa,
                        ctrl);
   else

@@ -437,6 +437,27 @@ class Engine:
         L.check(self._lib.admm_engine_get_penalty(self._h, C.byref(d), C.byref(has)))
         return dict(l1=d.l1, ridge=d.ridge, nonnegative=int(d.nonnegative), has_l1weights=bool(has.value))
 
+    def set_loss(self, weights=None, slopes=(1.0, 1.0), epsilon=0.0, delta=1.0):
+        """The loss family of a LAD or Huber engine (admm_engine_set_loss): per-observation weights (m values >= 0), the
+        slopes (a, b) of the positive and the negative side (the tau-quantile: (tau, 1 - tau)), the dead zone epsilon of
+        a LAD engine (support vector regression) and the threshold delta of a Huber engine.  ``set_loss(None)`` -- every
+        argument at its default -- restores the engine's own prox."""
+        a, b = (float(v) for v in slopes)
+        if weights is None and a == 1.0 and b == 1.0 and epsilon == 0.0 and delta == 1.0:
+            L.check(self._lib.admm_engine_set_loss(self._h, None))
+            return
+        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w is not None and w.size != self.nB:
+            raise ValueError(f"weights has {w.size} entries for {self.nB} observations")
+        d = L.LossDesc(None if w is None else L.as_dp(w), a, b, float(epsilon), float(delta))
+        L.check(self._lib.admm_engine_set_loss(self._h, C.byref(d)))
+
+    def loss(self):
+        """what set_loss left in force: dict(slopes, epsilon, delta, has_weights)"""
+        d, has = L.LossDesc(), C.c_int32()
+        L.check(self._lib.admm_engine_get_loss(self._h, C.byref(d), C.byref(has)))
+        return dict(slopes=(d.slope_pos, d.slope_neg), epsilon=d.epsilon, delta=d.delta, has_weights=bool(has.value))
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None):

@@ -87,6 +87,48 @@ def group_sizes(groups, weights, n):
     return np.ascontiguousarray(g.astype(np.int64)), w
 
 
+LOSS_KEYS = ("weights", "tau", "slopes", "epsilon", "delta")
+
+
+def loss_fields(src, m, kind):
+    """The loss family of lad / huberfit (admm_engine_set_loss) out of a dict of args / options: ``weights`` (m finite
+    values >= 0), ``tau`` (strictly inside (0, 1): slopes (tau, 1 - tau)) or ``slopes`` (two finite values > 0),
+    ``epsilon`` (finite, >= 0; lad only) and ``delta`` (finite, > 0; huberfit only).  Returns Engine.set_loss's keyword
+    arguments for the fields that were given (None where none was).  Raises before any device work."""
+    given = {k: src[k] for k in LOSS_KEYS if src.get(k) is not None}
+    if not given:
+        return None
+    out = {}
+    if "weights" in given:
+        w = np.ascontiguousarray(np.asarray(given["weights"], dtype=np.float64).reshape(-1))
+        if w.size != int(m):
+            raise ValueError(f"weights has {w.size} entries for the {int(m)} rows of D")
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("weights: every weight must be finite and >= 0")
+        out["weights"] = w
+    if "tau" in given and "slopes" in given:
+        raise ValueError("tau beside slopes: give one of them")
+    if "tau" in given:
+        tau = given["tau"]
+        if not np.isscalar(tau) or not np.isreal(tau) or not 0.0 < tau < 1.0:
+            raise ValueError("tau must lie strictly inside (0, 1)")
+        out["slopes"] = (float(tau), 1.0 - float(tau))
+    if "slopes" in given:
+        sl = np.asarray(given["slopes"], dtype=np.float64).reshape(-1)
+        if sl.size != 2 or not np.all(np.isfinite(sl)) or np.any(sl <= 0):
+            raise ValueError("slopes must hold two finite values > 0")
+        out["slopes"] = (float(sl[0]), float(sl[1]))
+    for key, low_ok, owner in (("epsilon", True, "lad"), ("delta", False, "huberfit")):
+        if key in given:
+            v = given[key]
+            if not np.isscalar(v) or not np.isreal(v) or not np.isfinite(v) or v < 0 or (v == 0 and not low_ok):
+                raise ValueError(f"{key} must be a finite real number {'>= 0' if low_ok else '> 0'}")
+            if kind != owner and v != (0.0 if low_ok else 1.0):
+                raise ValueError(f"{key} belongs to {owner}, not to {kind}")
+            out[key] = float(v)
+    return out
+
+
 PENALTY_KEYS = ("l1weights", "ridge", "nonnegative", "l1")
 
 

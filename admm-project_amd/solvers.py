@@ -13,9 +13,9 @@ import time
 import numpy as np
 
 from .api import admm, getproxops
-from .errorcheck import PENALTY_KEYS, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
+from .errorcheck import LOSS_KEYS, PENALTY_KEYS, loss_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -149,7 +149,10 @@ def _lad_like(kind, D, s, options):
     m, n = D.shape
     if s.size != m:
         raise ValueError("The number of rows in argument D do not match size of s!")
-    args = _engine_args(options, dict(D=D, s=s))
+    loss = loss_fields({k: options.pop(k, None) for k in LOSS_KEYS}, m, kind)
+    if loss is not None and "comm" in options:
+        raise ValueError("weights / tau / slopes / epsilon / delta have no row-sharded form: options.comm")
+    args = _engine_args(options, dict(D=D, s=s), **(loss or {}))
     if options.get("relax", 1) != 1:  # lad.m:124-126, huberfit.m:156-158
         args["userelax"] = 1
     minx, minz, _ = getproxops(kind, args)
@@ -161,13 +164,36 @@ def _lad_like(kind, D, s, options):
 
 
 def lad(D, s, options=None):
-    """results = lad(D, s, options)   (solvers/lad.m:51-154): minimise ||D*x - s||_1."""
+    """results = lad(D, s, options)   (solvers/lad.m:51-154): minimise ||D*x - s||_1.
+
+    Engine-side extension: minimise sum_i w_i*phi(D*x - s)_i with phi(r) = a*max(r - eps, 0) +
+    b*max(-r - eps, 0): ``options['weights']`` (m values w_i >= 0), ``options['slopes']`` = (a, b) or ``options['tau']``
+    (the tau-quantile: a = tau, b = 1 - tau) and ``options['epsilon']`` (the dead zone of support vector regression)
+    change the z-update alone."""
     return _lad_like("lad", D, s, options if options is not None else {})
 
 
 def huberfit(D, s, options=None):
-    """results = huberfit(D, s, options)   (solvers/huberfit.m:83-186): 1/2*sum(huber(D*x - s))."""
+    """results = huberfit(D, s, options)   (solvers/huberfit.m:83-186): 1/2*sum(huber(D*x - s)).
+
+    Engine-side extension: minimise sum_i w_i*(r_i >= 0 ? a : b)*H_delta(r_i), r = D*x - s, with
+    H_delta(r) = r^2/2 up to |r| = delta and delta*|r| - delta^2/2 beyond: ``options['weights']``, ``options['slopes']`` =
+    (a, b) and ``options['delta']`` change the z-update alone."""
     return _lad_like("huberfit", D, s, options if options is not None else {})
+
+
+def quantilereg(D, s, tau, options=None):
+    """results = quantilereg(D, s, tau, options): quantile regression, minimise sum_i w_i*phi_tau(D*x - s)_i with the
+    pinball loss phi_tau(z) = tau*max(z, 0) + (1 - tau)*max(-z, 0) on the residual z = D*x - s -- lad() with
+    options['tau'].  Where D spans the constant vector, a fraction tau of the residuals is negative at
+    the optimum: #(z < 0) <= tau*m <= #(z <= 0).  ``options['weights']`` as for lad()."""
+    if not isinstance(options, dict):
+        raise TypeError("Argument options is not a struct!")
+    if not np.isscalar(tau) or not np.isreal(tau) or not 0.0 < tau < 1.0:
+        raise ValueError("tau must lie strictly inside (0, 1)")
+    if options.get("tau") is not None or options.get("slopes") is not None:
+        raise ValueError("quantilereg sets the slopes itself: options.tau / options.slopes")
+    return lad(D, s, dict(options, tau=float(tau)))
 
 
 def _single_column_quirk(D):

@@ -148,6 +148,16 @@ def lad_problem(seed=0, rows=2 ** 10, cols=2 ** 7):
     return dict(D=D, s=s, xtrue=xtrue)
 
 
+def quantile_problem(seed=0, rows=200, cols=8):
+    """A heteroscedastic regression for quantilereg: an intercept column and cols - 1 standard normal ones, noise whose
+    scale grows with the first regressor, so the quantile fits differ in more than the intercept."""
+    rng = np.random.default_rng(seed)
+    D = np.asfortranarray(np.column_stack([np.ones(rows), rng.standard_normal((rows, cols - 1))]))
+    xtrue = rng.standard_normal(cols)
+    s = D @ xtrue + (1.0 + 0.5 * np.abs(D[:, 1])) * rng.standard_normal(rows)
+    return dict(D=D, s=s, xtrue=xtrue)
+
+
 def huber_problem(seed=0, rows=2 ** 11, cols=2 ** 7):
     """testers/huberfittest.m:122-128."""
     rng = np.random.default_rng(seed)

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "grouplassotest", "elasticnettest", "ladtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
+__all__ = ["lassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -80,6 +80,34 @@ def ladtest(seed=0, rows=2 ** 10, cols=2 ** 7, errtol=1e-5, quiet=1, options=Non
                 xresidual=xres, xerror=np.sum(np.abs(xtrue - xopt)) / xopt.size,
                 failed=int(not (xres < errtol and abs(objopt - trueobj) <= errtol * trueobj)),
                 steps=results["steps"], errtol=errtol)
+    return results, test
+
+
+# quantileregtest's allowance on the count condition, in observations: ADMM stops at the default tolerances, not at the
+# optimum (tests/test_loss_host.py measures 0 on this problem for tau = 0.1, 0.5, 0.9 and asserts it there)
+QUANTILE_COUNT_SLACK = 0
+
+
+def quantile_count_slack(z, tau):
+    """by how many observations #(z < 0) <= tau*m <= #(z < 0) + #(z == 0) fails on z (0: it holds)"""
+    z = np.asarray(z).reshape(-1)
+    neg, zero, target = int(np.sum(z < 0)), int(np.sum(z == 0)), tau * z.size
+    return max(0.0, neg - target, target - (neg + zero))
+
+
+def quantileregtest(seed=0, rows=200, cols=8, tau=0.9, quiet=1, options=None):
+    """ladtest's shape for quantilereg on synth.quantile_problem (D spans the constant vector): pass when the final z
+    satisfies the optimality condition on the signs of the residuals, #(z < 0) <= tau*m <= #(z < 0) + #(z == 0), within
+    QUANTILE_COUNT_SLACK observations."""
+    p = synth.quantile_problem(seed, rows, cols)
+    D, s = p["D"], p["s"]
+    results = solvers.quantilereg(D, s, tau, _opts(options, objevals=1, quiet=quiet))
+    xopt, z = results["xopt"], np.asarray(results["zopt"]).reshape(-1)
+    r = D @ xopt - s
+    objopt = float(np.sum(tau * np.maximum(r, 0.0) + (1.0 - tau) * np.maximum(-r, 0.0)))
+    slack = quantile_count_slack(z, tau)
+    test = dict(D=D, s=s, tau=tau, xopt=xopt, admmopt=results["objopt"], objopt=objopt, negative=int(np.sum(z < 0)),
+                zero=int(np.sum(z == 0)), slack=slack, failed=int(slack > QUANTILE_COUNT_SLACK), steps=results["steps"])
     return results, test
 
 

@@ -351,6 +351,36 @@ int admm_engine_set_penalty(admm_engine* eng, const admm_penalty_desc* desc);
 /* what is in force (admm_engine_info_t has no reserved field left): l1, ridge, nonnegative into *desc (its l1weights is
  * set to NULL) and whether weights are held into *has_l1weights (nullable) */
 int admm_engine_get_penalty(admm_engine* eng, admm_penalty_desc* desc, int32_t* has_l1weights);
+/* The loss family of the robust-regression engines (engine-side extension: DESIGN.md q33).  With the constraint
+ * D*x - z = s, the z-side term of an ADMM_PROB_LAD or ADMM_PROB_HUBERFIT engine is g(z) = sum_i weights[i]*phi(z_i):
+ *   LAD engine:    phi(z) = slope_pos*max(z - epsilon, 0) + slope_neg*max(-z - epsilon, 0)
+ *                  (LAD: 1, 1, 0; the tau-quantile: slope_pos = tau, slope_neg = 1 - tau; the epsilon-insensitive loss of
+ *                  support vector regression: 1, 1, epsilon > 0)
+ *   Huber engine:  phi(z) = (z >= 0 ? slope_pos : slope_neg)*H_delta(z),  H_delta(z) = z^2/2 for |z| <= delta and
+ *                  delta*|z| - delta^2/2 beyond (at the defaults the reference's 1/2*huber)
+ * Only the z-prox changes, with v = (Ax^ + u) - c, t_a = weights[i]*slope_pos/rho, t_b = weights[i]*slope_neg/rho:
+ *   LAD engine:    z = v - t_a (v > epsilon + t_a), epsilon (v >= epsilon), v (v > -epsilon), -epsilon (v >= -epsilon - t_b),
+ *                  v + t_b otherwise: the flats are +-epsilon exactly, the dead zone and a zero weight return v itself
+ *   Huber engine:  z = v - clamp(alpha*v/(alpha + rho), 0, alpha*delta/rho) for v >= 0 with alpha = weights[i]*slope_pos,
+ *                  z = v - clamp(alpha*v/(alpha + rho), -alpha*delta/rho, 0) for v < 0 with alpha = weights[i]*slope_neg
+ * and objevals reports g(z).  The cached factor, both products with D, every option and every iteration form stay the
+ * engine's, with its launches per iteration; a zming callback still replaces the z-update.  Defaults: weights NULL
+ * (every weight 1), slopes 1, epsilon 0, delta 1 -- with all of them the engine launches the kernels it always did, bit
+ * for bit.  desc == NULL restores the defaults.  weights (m HOST values) are copied at the call.
+ * ADMM_E_INVALID: another problem; a negative or non-finite weight; a slope <= 0; epsilon < 0, or != 0 on a Huber
+ * engine; delta <= 0, or != 1 on a LAD engine -- a refused call changes nothing.  ADMM_E_UNSUPPORTED: a row-sharded
+ * engine, the generic callback engine (ADMM_PROB_LAD with ADMM_XSOLVE_CALLBACK). */
+typedef struct admm_loss_desc {
+  const double* weights;
+  double slope_pos;
+  double slope_neg;
+  double epsilon;
+  double delta;
+} admm_loss_desc;
+int admm_engine_set_loss(admm_engine* eng, const admm_loss_desc* desc);
+/* what is in force: the four scalars into *desc (its weights is set to NULL) and whether weights are held into
+ * *has_weights (nullable) */
+int admm_engine_get_loss(admm_engine* eng, admm_loss_desc* desc, int32_t* has_weights);
 /* Isotropic 2-D total variation (engine-side extension: DESIGN.md q31): with on = 1 an ADMM_PROB_TV2D engine minimises
  * 1/2*||x - s||^2 + lambda * sum_k sqrt((Dx)[k]^2 + (Dx)[N+k]^2), k over the N pixels (the Rudin-Osher-Fatemi norm),
  * instead of the anisotropic lambda*||Dx||_1.  Only the z-update changes: for every pixel k -- those of the last image
@@ -454,6 +484,10 @@ int admm_binding_get_info(const admm_binding* b, admm_binding_info* info);
 /* a 'lasso' binding also takes the penalty family of admm_engine_set_penalty from its args: `l1weights` (one finite
  * value >= 0 per column of D), `ridge`, `l1` (finite, >= 0) and `nonnegative` (0 or 1), checked by admm_binding_create
  * (ADMM_E_INVALID), refused with parallel = 1 (ADMM_E_UNSUPPORTED) and handed to the engine by admm_binding_apply */
+/* a 'lad' or 'huberfit' binding also takes the loss family of admm_engine_set_loss from its args: `weights` (one
+ * finite value >= 0 per row of D), `slopes` (two values > 0: positive side, negative side) or its shorthand `tau`
+ * (strictly inside (0, 1): slopes tau, 1 - tau; refused beside `slopes`), `epsilon` ('lad') and `delta` ('huberfit'),
+ * checked by admm_binding_create (ADMM_E_INVALID) and handed to the engine by admm_binding_apply */
 /* after admm_engine_create: a scalar or matrix B goes to the engine (admm_engine_set_constraint_b), and the groups of a
  * 'lasso' binding whose args carry `groups` (group sizes: integers >= 1 that sum to the columns of D) and optionally
  * `groupweights` (one finite value >= 0 per group) go to admm_engine_set_groups.  admm_binding_create checks both vectors
@@ -512,6 +546,10 @@ int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* size
  * desc == NULL: the defaults */
 int admm_op_penalty_prox(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups, const double* groupweights,
                          double lambda_over_rho, const admm_penalty_desc* desc, double rho, double* out);
+/* the z-prox of the loss family (admm_engine_set_loss) on a host vector, by the device function of the loop's element
+ * update: problem = ADMM_PROB_LAD or ADMM_PROB_HUBERFIT selects phi, desc == NULL the defaults; desc->weights holds len
+ * values.  The refusals are admm_engine_set_loss's. */
+int admm_op_loss_prox(const double* v, int64_t len, int32_t problem, const admm_loss_desc* desc, double rho, double* out);
 /* out = the pair shrink of isotropic 2-D total variation (admm_engine_set_tv2d_isotropic) over a 2N-vector whose halves
  * are paired: (out[k], out[N+k]) = (v[k], v[N+k]) * (||.|| > t ? 1 - t/||.|| : 0); the device function of the loop */
 int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* out);
