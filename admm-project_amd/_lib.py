@@ -160,6 +160,7 @@ SVM_OVR_MAX_N = 448
 
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
+STORAGE_FP64, STORAGE_COMPACT = 0, 1
 F_WVALS = 23
 F_COVSEL_S = 24
 
@@ -194,6 +195,9 @@ _SIGNATURES = {
     "admm_engine_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_engine_set_hooks": (C.c_int, [C.c_void_p, ALTU_CALLBACK, C.c_void_p, NORMS_CALLBACK, C.c_void_p]),
     "admm_engine_info": (C.c_int, [C.c_void_p, C.POINTER(EngineInfo)]),
+    "admm_engine_xsolve_storage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "admm_xsolve_compact_accept": (C.c_int, [C.c_double, C.c_double, C.c_double]),
     "admm_engine_setup_seconds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "admm_engine_kernel_time": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "admm_engine_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -223,6 +227,8 @@ _SIGNATURES = {
                                        C.POINTER(PenaltyDesc), C.c_double, _dp]),
     "admm_op_loss_prox": (C.c_int, [_dp, C.c_int64, C.c_int32, C.POINTER(LossDesc), C.c_double, _dp]),
     "admm_op_symv": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp]),
+    "admm_op_symv_compact": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp, _dp,
+                                       C.c_int64]),
     "admm_op_symv_batch": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int64, C.c_int64, _dp, C.c_int64]),
     "admm_op_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_double, _dp, C.c_int64, _dp,
                                C.c_int64, C.c_double, _dp, C.c_int64, C.c_int32]),

@@ -731,6 +731,7 @@ def admm(xminf, zming, options):
 
     results["steps"] = steps
     results["engine_info"] = eng.info()  # engine extension: which x-solve form runs, probe errors, rank (not a reference field)
+    results["xsolve_storage"] = eng.xsolve_storage()  # engine extension: fp64 / compact inverse, its bytes, its probe
     try:  # matrix-free x-update: total inner CG iterations (engine extension, not a reference field)
         cg = eng.fetch(L.F_CG_ITERS, 2)
         results["cg_iters_total"] = int(cg[0])

@@ -1,14 +1,18 @@
 // symv_packed.hip -- developer microbenchmark (NOT part of libadmm_hip.so): the lower-triangle SYMV of symv.hip on
 // the column-major padded storage against the same inner loop on TILE-PACKED storage (every 128x128 tile of the
 // lower triangle contiguous, 128 KB, tiles in row-major triangle order).
-//   hipcc -O3 --offload-arch=gfx950 -I.. -o symv_packed symv_packed.hip && ./symv_packed [n]
+//   hipcc -O3 --offload-arch=gfx950 -I.. -o symv_packed symv_packed.hip && ./symv_packed [n] [compact]
+// `compact`: only the A/B of the production packed kernel on fp64 tiles against its compact instantiation (tri_tile.h:
+// 48-bit tile-scaled fixed point off the diagonal), back to back, over a sweep of the cacheable share of each.
 #include "../symv.hip"
 
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 using namespace admm;
+constexpr int kSyTile = kTile;
 
 #define CK(e)                                                                   \
   do {                                                                          \
@@ -38,6 +42,13 @@ __global__ void pack_tiles(const double* __restrict__ M, int64_t ld, double* __r
   double* dst = P + static_cast<int64_t>(t) * kSyTile * kSyTile;
   for (int e = threadIdx.x; e < kSyTile * kSyTile; e += blockDim.x) dst[e] = src[(e / kSyTile) * ld + (e % kSyTile)];
 }
+
+// symv.hip's launch_symv_pack goes through the pack kernel of trsv.hip, which this program does not link
+namespace admm {
+void launch_tri_pack(const double* M, int64_t ld, double* P, unsigned ntri, int, hipStream_t stream) {
+  hipLaunchKernelGGL(pack_tiles, dim3(ntri), dim3(256), 0, stream, M, ld, P);
+}
+}  // namespace admm
 
 template <bool NT, int ORDER>
 __global__ __launch_bounds__(kWave) void symv_packed_kernel(const double* __restrict__ P, int64_t n,
@@ -357,6 +368,7 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   const int reps = 60;
+  double last_us = 0.0;
   auto time_it = [&](const char* name, auto&& launch, double* yout) {
     CK(hipMemset(np_, 0, sizeof(double) * nt * p.ldp));
     CK(hipMemset(tp, 0, sizeof(double) * nt * p.ldp));
@@ -371,11 +383,41 @@ int main(int argc, char** argv) {
                        nullptr);
     CK(hipDeviceSynchronize());
     const double us = ms * 1e3 / reps;
+    last_us = us;
     printf("%-44s %8.2f us  %6.3f TB/s\n", name, us, ntri * 131072.0 / us * 1e-6);
   };
+  if (argc > 2 && std::string(argv[2]) == "compact") {  // fp64 tiles against the compact storage, alternating
+    SymvPlan pf = p, pc = p;
+    pf.packed = pc.packed = pc.compact = true;
+    double* C;
+    CK(hipMalloc(&C, sizeof(double) * symv_compact_elems(pc)));
+    launch_symv_compact_pack(pc, P, 0, true, C, nullptr, 0);
+    pc.scales = symv_compact_scales(pc, C);
+    CK(hipDeviceSynchronize());
+    const double cmb = symv_tile_prefix_bytes(pc, ntri) * 1e-6;
+    printf("compact storage %.1f MB (TB/s column: fp64 algorithmic bytes over time)\n", cmb);
+    std::vector<double> h1(n), h2(n);
+    for (int round = 0; round < 2; ++round)
+      for (int64_t mb : {0, 64, 105, 136, 168, 200, 232, 264, 290, 320}) {
+        char nm[96];
+        pf.ncached = symv_cached_tiles(pf, mb << 20);
+        pc.ncached = symv_cached_tiles(pc, mb << 20);
+        snprintf(nm, sizeof nm, "fp64    %3lld MB cacheable (%lld tiles)", (long long)mb, (long long)pf.ncached);
+        time_it(nm, [&] { launch_symv_lower(pf, P, 0, x, np_, tp, y, nullptr, 0, 0, 1, false); }, y);
+        snprintf(nm, sizeof nm, "compact %3lld MB cacheable (%lld tiles)", (long long)mb, (long long)pc.ncached);
+        time_it(nm, [&] { launch_symv_lower(pc, C, 0, x, np_, tp, y2, nullptr, 0, 0, 1, false); }, y2);
+        printf("   compact over stored bytes: %6.3f TB/s\n", cmb / last_us);
+      }
+    CK(hipMemcpy(h1.data(), y, sizeof(double) * n, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(h2.data(), y2, sizeof(double) * n, hipMemcpyDeviceToHost));
+    double err = 0, ymax = 0;
+    for (int64_t i = 0; i < n; ++i) err = fmax(err, fabs(h1[i] - h2[i])), ymax = fmax(ymax, fabs(h1[i]));
+    printf("max |y_compact - y_fp64| / max |y| = %.3e\n", err / ymax);
+    return 0;
+  }
   time_it("column-major padded (production)", [&] {
     hipLaunchKernelGGL(symv_lower_kernel<false>, dim3(nt, nt), dim3(kWave), 0, 0, M, n, ld, x, np_, tp, p.ldp, 0, 1, 0u,
-                       nullptr);
+                       nullptr, nullptr);
   }, y);
   time_it("tile-packed, NT", [&] {
     hipLaunchKernelGGL((symv_packed_kernel<true, 0>), dim3(ntri), dim3(kWave), 0, 0, P, n, x, np_, tp, p.ldp, nt);
@@ -470,7 +512,7 @@ int main(int argc, char** argv) {
   }
   time_it("column-major padded again", [&] {
     hipLaunchKernelGGL(symv_lower_kernel<false>, dim3(nt, nt), dim3(kWave), 0, 0, M, n, ld, x, np_, tp, p.ldp, 0, 1, 0u,
-                       nullptr);
+                       nullptr, nullptr);
   }, y);
   return 0;
 }

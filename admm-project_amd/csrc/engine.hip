@@ -361,6 +361,51 @@ int build_slice_factor(admm_engine* e, SliceFactor& f, double* W, int64_t n, int
   return ADMM_OK;
 }
 
+// The rule of choose_symv_storage: the one choose_trsv_form applies to a cheaper form against its yardstick.
+bool symv_compact_accept(double err_compact, double err_fp64, double diff) {
+  return err_compact <= std::max(1e-11, 4.0 * err_fp64) && diff <= std::max(1e-11, 8.0 * err_fp64);
+}
+
+// How the explicit inverse of the engine's own factor is STORED.  The packed x-solve of a matrix too large for the
+// caches runs at the ingest rate of the part, so its time is its byte count: the compact storage (tri_tile.h: 48-bit
+// tile-scaled fixed point off the diagonal, 3/4 of the bytes) is built where the fp64 packed triangle streams, probed
+// as form A against that triangle as form B on the two systems of probe_two_forms, and adopted -- the fp64 triangle
+// freed -- while it is as accurate (within 4x / 8x) or below 1e-11.  A cache-resident matrix is latency-bound and
+// gains nothing; the consensus slices (batched launch), the pseudo-inverse (no factor to probe with) and the
+// row-sharded split x-solve keep fp64.
+static int choose_symv_storage(admm_engine* e, SliceFactor& f) {
+  if (f.mode != ADMM_XSOLVE_INVERSE || !f.Minv || !f.F || f.pinv || !f.planSy.packed || f.planSy.compact ||
+      f.n < kSymvHalfMin || e->sy_split)
+    return ADMM_OK;
+  if (!stream_hint(symv_tile_prefix_bytes(f.planSy, symv_tiles(f.planSy)))) return ADMM_OK;
+  SymvPlan cp = f.planSy;
+  cp.compact = true;
+  double* C = nullptr;
+  ADMM_TRY(e->mem.alloc(&C, symv_compact_elems(cp)));
+  launch_symv_compact_pack(cp, f.Minv, 0, true, C, nullptr, e->stream);
+  cp.scales = symv_compact_scales(cp, C);
+  cp.ncached = symv_cached_tiles(cp, kSymvCacheBytes);
+  double ea = NAN, eb = NAN, diff = NAN;
+  const int rc = probe_two_forms(
+      e, f, [&](const double* y, double* x) { launch_symv_lower(cp, C, 0, y, e->syN, e->syT, x, nullptr, e->stream); },
+      [&](const double* y, double* x) { apply_inverse(e, f, y, x, nullptr); }, &ea, &eb, &diff);
+  if (rc != ADMM_OK) {
+    e->mem.free_one(C);
+    return rc;
+  }
+  f.err_cq = ea;
+  f.err_cq_ref = eb;
+  f.cq_diff = diff;
+  if (symv_compact_accept(ea, eb, diff)) {
+    e->mem.free_one(f.Minv);
+    f.Minv = C;
+    f.planSy = cp;
+  } else {
+    e->mem.free_one(C);
+  }
+  return ADMM_OK;
+}
+
 void release_slice_factor(admm_engine* e, SliceFactor& f) {
   e->mem.free_one(f.Minv);
   e->mem.free_one(f.work);
@@ -634,7 +679,8 @@ int factorize(admm_engine* e, double* W, int64_t nF, int64_t ld, const double* L
   e->nF = nF;
   e->ldF = ld;
   e->xsolve = f.mode;
-  return decide_sy_split(e);
+  ADMM_TRY(decide_sy_split(e));
+  return choose_symv_storage(e, f);
 }
 
 // D'D is rank deficient (or numerically so): x = pinv(D)*(z-u) = (D'D)^+ D'(z-u)  (linearsvm.m:185,
@@ -928,10 +974,11 @@ int admm_engine_info(admm_engine* e, admm_engine_info_t* info) {
   auto tally = [&](const SliceFactor& s) {
     const int64_t tile_bytes = int64_t{8} * 128 * 128;  // kTile (tri_tile.h)
     if (s.mode == ADMM_XSOLVE_INVERSE && s.Minv && s.n >= kSymvHalfMin) {
-      const int64_t tiles = symv_tiles(s.planSy);
+      const int64_t tiles = symv_tiles(s.planSy);  // (fp64 or compact tiles: the bytes of the form in use)
       const int64_t cached = std::min<int64_t>(tiles, std::max<int64_t>(0, s.planSy.ncached));
-      info->xsolve_cacheable_bytes += cached * tile_bytes;
-      info->xsolve_stream_bytes += (tiles - cached) * tile_bytes;
+      const int64_t cbytes = symv_tile_prefix_bytes(s.planSy, cached);
+      info->xsolve_cacheable_bytes += cbytes;
+      info->xsolve_stream_bytes += symv_tile_prefix_bytes(s.planSy, tiles) - cbytes;
     } else if (s.mode == ADMM_XSOLVE_INVERSE && s.Minv) {
       info->xsolve_cacheable_bytes += int64_t{8} * s.n * s.n;  // one wave per column, cache-resident
     } else if (s.mode == ADMM_XSOLVE_TRSV && s.trsv.one) {  // ONE triangle, read by both passes
@@ -956,6 +1003,27 @@ int admm_engine_info(admm_engine* e, admm_engine_info_t* info) {
     tally(*f);
   }
   return ADMM_OK;
+}
+
+int admm_engine_xsolve_storage(admm_engine* e, int32_t* form, int64_t* stored_bytes, double* probe_err_compact,
+                               double* probe_err_fp64, double* probe_diff) {
+  if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
+  const SliceFactor& f = e->xfac;
+  const bool inv = f.mode == ADMM_XSOLVE_INVERSE && f.Minv;
+  if (form) *form = (inv && f.planSy.compact) ? ADMM_STORAGE_COMPACT : ADMM_STORAGE_FP64;
+  if (stored_bytes) {
+    *stored_bytes = 0;
+    if (inv && f.planSy.packed) *stored_bytes = symv_tile_prefix_bytes(f.planSy, symv_tiles(f.planSy));
+    else if (inv) *stored_bytes = int64_t{8} * f.ldM * f.planSy.npad;
+  }
+  if (probe_err_compact) *probe_err_compact = f.err_cq;
+  if (probe_err_fp64) *probe_err_fp64 = f.err_cq_ref;
+  if (probe_diff) *probe_diff = f.cq_diff;
+  return ADMM_OK;
+}
+
+int admm_xsolve_compact_accept(double err_compact, double err_fp64, double diff) {
+  return symv_compact_accept(err_compact, err_fp64, diff) ? 1 : 0;
 }
 
 int admm_engine_setup_seconds(admm_engine* e, double* seconds) {

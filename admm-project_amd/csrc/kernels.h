@@ -46,12 +46,15 @@ struct SymvPlan {
   int32_t ntile;   // 128-row wave chunks = 128-column groups: npart and tpart are [ntile][ldp]
   bool packed;     // M is tile-packed (launch_symv_pack): lower-triangle 128x128 tiles back to back, ld unused
   int64_t ncached; // tiles (linear index < ncached) read with default loads; the rest stream non-temporally
+  bool compact;    // packed, off-diagonal tiles as 48-bit tile-scaled fixed point (tri_tile.h): M is that storage
+  const double* scales;  // compact: one power of two per tile
   size_t npart_elems() const { return static_cast<size_t>(ntile) * ldp; }
   size_t tpart_elems() const { return static_cast<size_t>(ntile) * ldp; }
 };
 SymvPlan symv_plan(int64_t n);
 // Share of a re-read symmetric matrix that can stay in the 256 MB Infinity Cache next to the rest of an iteration's
-// traffic (measured plateau 105 .. 290 MB at n = 10000, dev/symv_packed.hip)
+// traffic (measured plateau 105 .. 290 MB at n = 10000, dev/symv_packed.hip; the compact storage, 313 MB in all, has
+// the same plateau: 49.8 us at 105 MB, 48.9 at 168, 48.3 .. 48.5 at 200 .. 232, 48.8 at 264, 56 at 290)
 constexpr int64_t kSymvCacheBytes = int64_t{168} << 20;
 int64_t symv_tiles(const SymvPlan& p);          // lower-triangle tiles
 size_t symv_packed_elems(const SymvPlan& p);    // doubles of the tile-packed storage
@@ -64,6 +67,16 @@ void launch_symv_lower_batch(const SymvPlan& p, const double* const* Ms_dev, int
                              const FinArgs* fin = nullptr);
 // P (symv_packed_elems doubles) <- the lower-triangle tiles of the padded column-major M (npad x npad, ld)
 void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P, hipStream_t stream);
+// The compact storage of a packed plan (tri_tile.h): diagonal tiles fp64, off-diagonal tiles 48-bit fixed point with one
+// power-of-two scale per tile, the scales behind the tiles in the same buffer of symv_compact_elems doubles.
+// bytes of the leading t tiles in the plan's storage form (p.compact); the plan's ncached counts tiles of that form
+int64_t symv_tile_prefix_bytes(const SymvPlan& p, int64_t t);
+size_t symv_compact_elems(const SymvPlan& p);
+double* symv_compact_scales(const SymvPlan& p, double* C);
+// C <- M, either the padded column-major square (ld) or the fp64 tile-packed triangle (src_packed); deq (optional,
+// symv_packed_elems doubles): the fp64 tile-packed triangle of the matrix C stands for
+void launch_symv_compact_pack(const SymvPlan& p, const double* M, int64_t ld, bool src_packed, double* C, double* deq,
+                              hipStream_t stream);
 // y = M*x for a small symmetric M (full storage, ld even, 16-byte aligned; x 16-byte aligned): one wave per column
 void launch_symv_small(const double* M, int64_t n, int64_t ld, const double* x, double* y, const Ctrl* ctrl,
                        hipStream_t stream);

@@ -375,6 +375,59 @@ int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32
   return ADMM_OK;
 }
 
+int admm_op_symv_compact(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
+                         int32_t part_count, double* y, double* Q, int64_t ldQ) {
+  if (!M || !x || !y || n <= 0 || ldM < n || ncached < -1 || part_count < 1 || (Q && ldQ < n))
+    return fail(ADMM_E_INVALID, "symv_compact: bad argument (ncached >= -1, part_count >= 1, ldQ >= n)");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dM, *dx, *dy, *dC, *dQ = nullptr, *npart, *tpart;
+  ADMM_TRY(sc.alloc(&dx, round_up(n, 2)));
+  ADMM_TRY(sc.alloc(&dy, round_up(n, 2)));
+  ADMM_HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  SymvPlan plan = symv_plan(n);
+  plan.packed = plan.compact = true;
+  ADMM_TRY(sc.alloc(&dM, static_cast<size_t>(plan.npad) * plan.npad));
+  ADMM_HIP_TRY(hipMemset(dM, 0, sizeof(double) * plan.npad * plan.npad));
+  ADMM_TRY(put_padded(dM, plan.npad, M, n, ldM));
+  ADMM_TRY(sc.alloc(&dC, symv_compact_elems(plan)));
+  if (Q) ADMM_TRY(sc.alloc(&dQ, symv_packed_elems(plan)));
+  launch_symv_compact_pack(plan, dM, plan.npad, false, dC, dQ, nullptr);
+  plan.scales = symv_compact_scales(plan, dC);
+  plan.ncached = ncached >= 0 ? ncached : symv_cached_tiles(plan, kSymvCacheBytes);
+  ADMM_TRY(sc.alloc(&npart, plan.npart_elems()));
+  ADMM_TRY(sc.alloc(&tpart, plan.tpart_elems()));
+  Ctrl* ctrl = nullptr;
+  if (fin) {  // (as in admm_op_symv: a zero-filled control block)
+    ADMM_TRY(sc.alloc(&ctrl, 1));
+    ADMM_HIP_TRY(hipMemset(ctrl, 0, sizeof(Ctrl)));
+  }
+  const int fill = part_count > 1 ? 0 : 0xFF;  // (as in admm_op_symv: one part -> a missed slot shows as NaN)
+  std::vector<double> part(static_cast<size_t>(n));
+  for (int32_t r = 0; r < part_count; ++r) {
+    ADMM_HIP_TRY(hipMemset(npart, fill, sizeof(double) * plan.npart_elems()));
+    ADMM_HIP_TRY(hipMemset(tpart, fill, sizeof(double) * plan.tpart_elems()));
+    if (fin) launch_symv_lower_fin(plan, dC, dx, npart, tpart, FinArgs{}, false, ctrl, nullptr, r, part_count, dy);
+    else launch_symv_lower(plan, dC, 0, dx, npart, tpart, dy, ctrl, nullptr, r, part_count);
+    ADMM_HIP_TRY(hipDeviceSynchronize());
+    ADMM_HIP_TRY(hipMemcpy(r == 0 ? y : part.data(), dy, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (r > 0)
+      for (int64_t i = 0; i < n; ++i) y[i] += part[i];
+  }
+  if (Q) {  // tile (bi, bj) of the packed triangle -> Q's lower triangle, mirrored
+    std::vector<double> P(symv_packed_elems(plan));
+    ADMM_HIP_TRY(hipMemcpy(P.data(), dQ, sizeof(double) * P.size(), hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < n; ++j)
+      for (int64_t i = j; i < n; ++i) {
+        const int64_t bi = i / 128, bj = j / 128, t = bi * (bi + 1) / 2 + bj;
+        const double v = P[static_cast<size_t>(t) * 128 * 128 + (j % 128) * 128 + (i % 128)];
+        Q[i + j * ldQ] = v;
+        Q[j + i * ldQ] = v;
+      }
+  }
+  return ADMM_OK;
+}
+
 int admm_op_symv_batch(const double* Ms, int64_t n, int64_t ldM, int32_t K, const double* X, int64_t ldX,
                        int64_t ncached, double* Y, int64_t ldY) {
   if (!Ms || !X || !Y || n <= 0 || ldM < n || K < 1 || ldX < n || ldY < n || ncached < -1)

@@ -25,8 +25,14 @@
 // (r2: 8-column panels -- 16 loads in flight, a three-level reduce-scatter ending in row_half_mirror -- measured
 // slower than this 4-column form: 78.4 vs 76.5 us event-timed per pass.  A pure N-part pass over the same tiles,
 // tri_step_kernel in trsv.hip, streams at 6.0 TB/s, so the T-part's cross-lane work is what holds this kernel at 5.4.)
+// Compact storage (tri_tile.h): the kernel sits at the ingest rate of the part for the bytes it reads, so the streamed
+// explicit inverse of the engine's own x-solve is stored with its off-diagonal tiles as 48-bit tile-scaled fixed point,
+// 3/4 of the bytes (n = 10000: 313 MB for 414), decoded by two conversions and one FMA per element that hide behind
+// the loads: 64.1 -> 50.8 us per launch, the same 6.2 TB/s over the stored bytes (EXPERIMENTS.md).
 // The tile pass itself (SyLane, sy_tile) is in tri_tile.h: the backward pass of the one-block triangular solve
 // (trsv.hip: tri1_backward_kernel) is its T-part alone.
+
+#include <algorithm>
 
 #include "finalize_device.h"
 #include "kernels.h"
@@ -38,11 +44,15 @@ namespace admm {
 // PACKED = false: M is npad x npad (npad = round_up(n, 128)) column-major with ld >= npad, zero outside n x n; grid
 // (ntile, ntile).  PACKED = true: M holds the lower-triangle tiles back to back (launch_symv_pack); grid = their count.
 // x: n elements.  Tiles with linear index < ncached use default loads, the others non-temporal ones.
-template <bool PACKED, int NBUF = 2>
+// COMPACT (PACKED only): M is the compact storage of tri_tile.h -- fp64 diagonal tiles, 48-bit fixed-point off-diagonal
+// tiles -- and scales its per-tile powers of two.
+template <bool PACKED, bool COMPACT = false, int NBUF = 2>
 __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block_y, const double* __restrict__ M,
                                                 int64_t n, int64_t ld, const double* __restrict__ x,
                                                 double* __restrict__ npart, double* __restrict__ tpart, int64_t ldp,
-                                                int32_t part_rank, int32_t part_count, uint32_t ncached) {
+                                                int32_t part_rank, int32_t part_count, uint32_t ncached,
+                                                const double* __restrict__ scales = nullptr) {
+  static_assert(PACKED || !COMPACT, "the compact storage is tile-packed");
   unsigned bi, bj, lin;
   if (PACKED) {
     lin = block_x;
@@ -64,7 +74,8 @@ __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block
   int64_t cbase;  // first column as sy_tile counts it
   double* __restrict__ tout = tpart + static_cast<int64_t>(bi) * ldp;
   if (PACKED) {  // the tile is its own 128 x 128 matrix: local row / column numbers, x and tout shifted to its columns
-    s.M = M + static_cast<int64_t>(lin) * (kTile * kTile);
+    s.M = COMPACT ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(M) + cq_tile_offset(lin, bi))
+                  : M + static_cast<int64_t>(lin) * (kTile * kTile);
     s.x = x + c0;
     s.ld = kTile;
     s.n = n - c0;
@@ -84,45 +95,55 @@ __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block
   double n0 = 0.0, n1 = 0.0;
   if (lin < ncached) {
     if (bi == bj) sy_tile<true, false, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
+    else if (COMPACT) sy_tile_cq<false, NBUF>(s, scales[lin], n0, n1, tout, lane);
     else sy_tile<false, false, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
   } else {
     if (bi == bj) sy_tile<true, true, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
+    else if (COMPACT) sy_tile_cq<true, NBUF>(s, scales[lin], n0, n1, tout, lane);
     else sy_tile<false, true, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
   }
   *reinterpret_cast<double2_t*>(npart + static_cast<int64_t>(bj) * ldp + gr) = double2_t{n0, n1};
 }
 
-template <bool PACKED>
+template <bool PACKED, bool COMPACT = false>
 __global__ __launch_bounds__(kWave) void symv_lower_kernel(const double* __restrict__ M, int64_t n, int64_t ld,
                                                            const double* __restrict__ x, double* __restrict__ npart,
                                                            double* __restrict__ tpart, int64_t ldp,
                                                            int32_t part_rank, int32_t part_count, uint32_t ncached,
-                                                           const Ctrl* __restrict__ ctrl) {
+                                                           const Ctrl* __restrict__ ctrl,
+                                                           const double* __restrict__ scales) {
   if (ctrl && ctrl->stop) return;
-  symv_lower_body<PACKED>(blockIdx.x, blockIdx.y, M, n, ld, x, npart, tpart, ldp, part_rank, part_count, ncached);
+  symv_lower_body<PACKED, COMPACT>(blockIdx.x, blockIdx.y, M, n, ld, x, npart, tpart, ldp, part_rank, part_count,
+                                   ncached, scales);
 }
 
 // The packed x-solve with a passenger: workgroup 0 runs the finalize logic of the PREVIOUS iteration (norms, tolerances,
 // stop decision: ~6 us of one workgroup's serial work) while the other workgroups stream the matrix.  Nothing in this
 // launch depends on that decision, and the fused element update that follows starts after it and no-ops when it has
 // raised ctrl->stop: the tail of an iteration shrinks to the element update itself (engine_run_general.hip, defer_fin).
+template <bool COMPACT>
 __global__ __launch_bounds__(kWave) void symv_lower_fin_kernel(const double* __restrict__ M, int64_t n,
                                                                const double* __restrict__ x,
                                                                double* __restrict__ npart, double* __restrict__ tpart,
                                                                int64_t ldp, int32_t part_rank, int32_t part_count,
                                                                uint32_t ncached, FinArgs f, int32_t fin_pending,
-                                                               const Ctrl* __restrict__ ctrl) {
+                                                               const Ctrl* __restrict__ ctrl,
+                                                               const double* __restrict__ scales) {
   // Every argument of the tile path but x requested at once (fetched where first used they cost four dependent scalar
   // round trips behind the stop test, in a one-tile workgroup that lives ~15 us).  NOT x: with its pointer live this
   // early hipcc allocates 100 VGPRs instead of 84 -- five waves per SIMD instead of six, and 3 % slower, measured.
+  // The COMPACT instantiation allocates 82 (12 dwords per panel buffer instead of 16, the decoded panel in 16 more):
+  // the same occupancy as the fp64 one, scales included in the early request.
   asm volatile("" ::"s"(M), "s"(n), "s"(npart), "s"(tpart), "s"(ldp), "s"(part_rank), "s"(part_count), "s"(ncached),
                "s"(fin_pending), "s"(ctrl));
+  if (COMPACT) asm volatile("" ::"s"(scales));
   if (ctrl->stop) return;
   if (blockIdx.x == 0) {
     if (fin_pending) finalize_body<false, kWave>(f);
     return;
   }
-  symv_lower_body<true>(blockIdx.x - 1u, 0u, M, n, 0, x, npart, tpart, ldp, part_rank, part_count, ncached);
+  symv_lower_body<true, COMPACT>(blockIdx.x - 1u, 0u, M, n, 0, x, npart, tpart, ldp, part_rank, part_count, ncached,
+                                 scales);
 }
 
 // K packed matrices of one size in ONE launch (consensus lasso: the K slice inverses of a rank; blockIdx.y = slice):
@@ -199,6 +220,80 @@ void launch_symv_small(const double* M, int64_t n, int64_t ld, const double* x, 
                      ld, x, y, ctrl);
 }
 
+// ---------------------------------------------------------------- fp64 tiles -> compact storage (tri_tile.h)
+// One workgroup per tile, no atomics: the tile maximum by a wave butterfly and four LDS slots, then every thread writes
+// 16-byte pieces of the panel records.  src: the tile as a column-major 128 x 128 block (ld = 128 inside a tile-packed
+// triangle, the matrix's own ld inside the padded square).  deq (optional): the fp64 tile-packed triangle of the matrix
+// the compact storage represents (scale * q; diagonal tiles as they are) -- what the operator tests compare.
+__device__ __forceinline__ int64_t cq_quantise(double v, int shift) {  // rint(v * 2^shift), clamped
+  const double lim = 140737488355327.0;  // 2^47 - 1
+  double q = rint(ldexp(v, shift));
+  q = q > lim ? lim : (q < -lim ? -lim : q);
+  return static_cast<int64_t>(q);
+}
+
+__global__ __launch_bounds__(kBlock) void symv_compact_pack_kernel(const double* __restrict__ M, int64_t ld, int packed,
+                                                                   char* __restrict__ C, double* __restrict__ scales,
+                                                                   double* __restrict__ deq) {
+  __shared__ double wmax[kBlock / kWave];
+  const unsigned t = blockIdx.x;
+  unsigned bi, bj;
+  tri_decode(t, bi, bj);
+  const int64_t sld = packed ? kTile : ld;
+  const double* src = packed ? M + static_cast<int64_t>(t) * (kTile * kTile)
+                             : M + static_cast<int64_t>(bj) * kTile * ld + static_cast<int64_t>(bi) * kTile;
+  char* dst = C + cq_tile_offset(t, bi);
+  double* dq = deq ? deq + static_cast<int64_t>(t) * (kTile * kTile) : nullptr;
+  if (bi == bj) {  // fp64 as it is
+    for (int e = 2 * threadIdx.x; e < kTile * kTile; e += 2 * kBlock) {
+      const double2_t v = *reinterpret_cast<const double2_t*>(src + static_cast<int64_t>(e / kTile) * sld + (e % kTile));
+      *reinterpret_cast<double2_t*>(reinterpret_cast<double*>(dst) + e) = v;
+      if (dq) *reinterpret_cast<double2_t*>(dq + e) = v;
+    }
+    if (threadIdx.x == 0) scales[t] = 1.0;
+    return;
+  }
+  double mx = 0.0;
+  for (int e = 2 * threadIdx.x; e < kTile * kTile; e += 2 * kBlock) {
+    const double2_t v = *reinterpret_cast<const double2_t*>(src + static_cast<int64_t>(e / kTile) * sld + (e % kTile));
+    mx = fmax(mx, fmax(fabs(v.x), fabs(v.y)));
+  }
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
+  int ex = 0;
+  if (mx > 0.0) (void)frexp(mx, &ex);  // mx = f * 2^ex, f in [0.5, 1): mx < 2^ex.  No logarithm of an all-zero tile.
+  const int shift = kCqBits - 1 - ex;
+  const double scale = mx > 0.0 ? ldexp(1.0, -shift) : 0.0;
+  if (threadIdx.x == 0) scales[t] = scale;
+  constexpr int kRuns = 3 * kWave;  // 16-byte pieces per panel record
+  for (int c = threadIdx.x; c < (kTile / kSyPanel) * kRuns; c += kBlock) {
+    const int p = c / kRuns, run = (c % kRuns) / kWave, l = c % kWave, r = 2 * l;
+    uint4_t out;
+    if (run < 2) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int col = kSyPanel * p + 2 * run + k;
+        const double2_t v = *reinterpret_cast<const double2_t*>(src + col * sld + r);
+        const int64_t q0 = cq_quantise(v.x, shift), q1 = cq_quantise(v.y, shift);
+        out[2 * k] = static_cast<unsigned>(q0 & 0xffffffff);
+        out[2 * k + 1] = static_cast<unsigned>(q1 & 0xffffffff);
+        if (dq) *reinterpret_cast<double2_t*>(dq + col * kTile + r) =
+            double2_t{static_cast<double>(q0) * scale, static_cast<double>(q1) * scale};
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kSyPanel; ++k) {
+        const double2_t v = *reinterpret_cast<const double2_t*>(src + (kSyPanel * p + k) * sld + r);
+        const int64_t q0 = cq_quantise(v.x, shift), q1 = cq_quantise(v.y, shift);
+        out[k] = (static_cast<unsigned>(q0 >> 32) & 0xffffu) | (static_cast<unsigned>(q1 >> 32) << 16);
+      }
+    }
+    *reinterpret_cast<uint4_t*>(dst + p * kCqPanelBytes + run * 1024 + l * 16) = out;
+  }
+}
+
 SymvPlan symv_plan(int64_t n) {
   SymvPlan p{};
   p.n = n;
@@ -206,6 +301,8 @@ SymvPlan symv_plan(int64_t n) {
   p.ldp = p.npad;
   p.ntile = static_cast<int32_t>(p.npad / kTile);
   p.packed = false;
+  p.compact = false;
+  p.scales = nullptr;
   p.ncached = symv_cached_tiles(p, kSymvCacheBytes);
   return p;
 }
@@ -213,15 +310,44 @@ SymvPlan symv_plan(int64_t n) {
 int64_t symv_tiles(const SymvPlan& p) { return static_cast<int64_t>(p.ntile) * (p.ntile + 1) / 2; }
 size_t symv_packed_elems(const SymvPlan& p) { return static_cast<size_t>(symv_tiles(p)) * kTile * kTile; }
 
+int64_t symv_tile_prefix_bytes(const SymvPlan& p, int64_t t) {
+  if (!p.compact) return t * int64_t{8} * kTile * kTile;
+  unsigned bi, bj;
+  tri_decode(static_cast<unsigned>(t), bi, bj);  // (also right for t = tiles: the row after the last)
+  return cq_tile_offset(static_cast<unsigned>(t), bi);
+}
+size_t symv_compact_elems(const SymvPlan& p) {
+  SymvPlan c = p;
+  c.compact = true;
+  return static_cast<size_t>(symv_tile_prefix_bytes(c, symv_tiles(p)) / 8 + symv_tiles(p));
+}
+double* symv_compact_scales(const SymvPlan& p, double* C) {
+  SymvPlan c = p;
+  c.compact = true;
+  return C + symv_tile_prefix_bytes(c, symv_tiles(p)) / 8;
+}
+
 int64_t symv_cached_tiles(const SymvPlan& p, int64_t budget_bytes) {
-  const int64_t tiles = symv_tiles(p), tile_bytes = int64_t{8} * kTile * kTile;
-  if (!stream_hint(tiles * tile_bytes)) return tiles;  // small enough to stay cache-resident as a whole
-  const int64_t fit = budget_bytes / tile_bytes;
-  return fit < tiles ? fit : tiles;
+  const int64_t tiles = symv_tiles(p);
+  if (!stream_hint(symv_tile_prefix_bytes(p, tiles))) return tiles;  // small enough to stay cache-resident as a whole
+  if (!p.compact) return std::min(tiles, budget_bytes / (int64_t{8} * kTile * kTile));
+  int64_t lo = 0, hi = tiles;  // the largest t whose leading t tiles fit
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) / 2;
+    if (symv_tile_prefix_bytes(p, mid) <= budget_bytes) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
 }
 
 void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P, hipStream_t stream) {
   launch_tri_pack(M, ld, P, static_cast<unsigned>(symv_tiles(p)), 0, stream);
+}
+
+void launch_symv_compact_pack(const SymvPlan& p, const double* M, int64_t ld, bool src_packed, double* C, double* deq,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(symv_compact_pack_kernel, dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kBlock), 0, stream, M,
+                     ld, src_packed ? 1 : 0, reinterpret_cast<char*>(C), symv_compact_scales(p, C), deq);
 }
 
 void launch_symv_reduce(const SymvPlan& p, const double* npart, const double* tpart, double* y, const Ctrl* ctrl,
@@ -233,13 +359,17 @@ void launch_symv_reduce(const SymvPlan& p, const double* npart, const double* tp
 void launch_symv_lower(const SymvPlan& p, const double* M, int64_t ld, const double* x, double* npart, double* tpart,
                        double* y, const Ctrl* ctrl, hipStream_t stream, int part_rank, int part_count, bool reduce) {
   const uint32_t ncached = static_cast<uint32_t>(p.ncached < 0 ? 0 : p.ncached);
-  if (p.packed)
+  const double* none = nullptr;
+  if (p.packed && p.compact)
+    hipLaunchKernelGGL((symv_lower_kernel<true, true>), dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0,
+                       stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl, p.scales);
+  else if (p.packed)
     hipLaunchKernelGGL(symv_lower_kernel<true>, dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0, stream, M,
-                       p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl);
+                       p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl, none);
   else
     hipLaunchKernelGGL(symv_lower_kernel<false>, dim3(static_cast<unsigned>(p.ntile), static_cast<unsigned>(p.ntile)),
                        dim3(kWave), 0, stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached,
-                       ctrl);
+                       ctrl, none);
   if (reduce) launch_symv_reduce(p, npart, tpart, y, ctrl, stream);  // else the consumer sums the rows (prox_fin_kernel)
 }
 
@@ -258,8 +388,13 @@ void launch_symv_lower_fin(const SymvPlan& p, const double* M, const double* x, 
                            int part_count, double* y) {
   const uint32_t ncached = static_cast<uint32_t>(p.ncached < 0 ? 0 : p.ncached);
   const dim3 grid(static_cast<unsigned>(symv_tiles(p)) + 1u);
-  hipLaunchKernelGGL(symv_lower_fin_kernel, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp, part_rank,
-                     part_count, ncached, f, fin_pending ? 1 : 0, ctrl);
+  const double* none = nullptr;
+  if (p.compact)
+    hipLaunchKernelGGL(symv_lower_fin_kernel<true>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
+                       part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, p.scales);
+  else
+    hipLaunchKernelGGL(symv_lower_fin_kernel<false>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
+                       part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, none);
   if (y) launch_symv_reduce(p, npart, tpart, y, ctrl, stream);  // else the consumer sums the partial rows itself
 }
 

@@ -11,12 +11,34 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 constexpr int kTile = 128;  // rows per wave (64 lanes x 2) = columns per tile
 
 // tile t of the lower triangle in row-major order (0,0), (1,0), (1,1), (2,0), ... -> (bi, bj)
-__device__ __forceinline__ void tri_decode(unsigned t, unsigned& bi, unsigned& bj) {
+__host__ __device__ __forceinline__ void tri_decode(unsigned t, unsigned& bi, unsigned& bj) {
   unsigned r = static_cast<unsigned>((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
   while (r * (r + 1u) / 2u > t) --r;
   while ((r + 1u) * (r + 2u) / 2u <= t) ++r;
   bi = r;
   bj = t - r * (r + 1u) / 2u;
+}
+
+// ---------------------------------------------------------------- compact storage of a symmetric tile-packed triangle
+// (symv.hip: the cached explicit inverse of the streamed x-solve).  Same tiles in the same order; a DIAGONAL tile keeps
+// its fp64 layout (128 KB: its diagonal entries are hundreds of times larger than the rest of the tile), an OFF-DIAGONAL
+// tile t is 48-bit signed fixed point with one power-of-two scale per tile (96 KB):
+//   e = binary exponent of the tile's largest magnitude (max < 2^e),  scale_t = 2^(e - 47)   (all-zero tile: scale 0)
+//   q = rint(M / scale_t) clamped to +-(2^47 - 1),  q = hi * 2^32 + lo,  hi signed 16 bits, lo unsigned 32 bits
+// A tile is 32 panel records of 3 KB, record p = columns 4p .. 4p + 3 as three 1 KB runs of 16 bytes per lane:
+//   run 0: lo of (r, 4p), (r + 1, 4p), (r, 4p + 1), (r + 1, 4p + 1)   r = 2 * lane, the lane's row pair
+//   run 1: the same of columns 4p + 2, 4p + 3
+//   run 2: four dwords, dword k = hi of (r, 4p + k) in its low half and of (r + 1, 4p + k) in its high half
+// so every lane load is 16 bytes, aligned, and a wave reads one contiguous 3 KB per panel.  The row before tile
+// (bi, bj) holds bi diagonal tiles, so tile t starts at byte (3 t + bi) * 32 KB.  The scales are one double per tile
+// (diagonal tiles: 1, unused) in an array of their own.  The kernel decodes fma(cvt(hi), 2^32, cvt(lo)) -- exact, 48
+// bits fit the mantissa -- and applies the scale once per tile (cq_scale_*): the product over the quantised matrix
+// rounds exactly where the fp64 kernel's does.
+constexpr int64_t kCqUnit = 32768;         // tile offsets count in these: a diagonal tile is 4, a compact one 3
+constexpr int kCqPanelBytes = 3 * 1024;    // one panel record
+constexpr int kCqBits = 48;
+__host__ __device__ __forceinline__ int64_t cq_tile_offset(unsigned t, unsigned bi) {
+  return (int64_t{3} * t + bi) * kCqUnit;
 }
 
 // ---------------------------------------------------------------- N-part: a panel of P columns, rows in registers
@@ -60,6 +82,46 @@ __device__ __forceinline__ void sy_load(const SyLane& s, int64_t cp, double2_t (
   for (int k = 0; k < kSyPanel; ++k) d[k] = load2<NT>(s.M + (cp + k) * s.ld + s.r);  // wave-uniform column base
 }
 
+// one panel buffer of the ring in sy_tile: the fp64 form holds the panel itself, the compact form its 48 bytes per lane
+template <bool NT>
+struct SyBuf64 {
+  double2_t d[kSyPanel];
+  __device__ __forceinline__ void load(const SyLane& s, int64_t cp) { sy_load<NT>(s, cp, d); }
+  __device__ __forceinline__ void get(double2_t (&o)[kSyPanel]) const {
+#pragma unroll
+    for (int k = 0; k < kSyPanel; ++k) o[k] = d[k];
+  }
+};
+
+typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ uint4_t load16(const char* p) {
+  const uint4_t* q = reinterpret_cast<const uint4_t*>(p);
+  return NT ? __builtin_nontemporal_load(q) : *q;
+}
+__device__ __forceinline__ double cq_value(unsigned lo, int hi) {
+  return __builtin_fma(static_cast<double>(hi), 4294967296.0, static_cast<double>(lo));
+}
+// s.M: the compact tile; cp: first column of the panel within the tile (a multiple of 4)
+template <bool NT>
+struct SyBufCq {
+  uint4_t lo[2], hi;
+  __device__ __forceinline__ void load(const SyLane& s, int64_t cp) {
+    const char* p = reinterpret_cast<const char*>(s.M) + (cp >> 2) * kCqPanelBytes + s.r * 8;
+    lo[0] = load16<NT>(p);
+    lo[1] = load16<NT>(p + 1024);
+    hi = load16<NT>(p + 2048);
+  }
+  __device__ __forceinline__ void get(double2_t (&o)[kSyPanel]) const {
+#pragma unroll
+    for (int k = 0; k < kSyPanel; ++k) {
+      const int h = static_cast<int>(hi[k]);
+      o[k].x = cq_value(lo[k >> 1][2 * (k & 1)], static_cast<int>(static_cast<short>(h)));
+      o[k].y = cq_value(lo[k >> 1][2 * (k & 1) + 1], h >> 16);
+    }
+  }
+};
+
 // DIAG: the tile intersects the diagonal -> mask element-wise (N-part j <= row, T-part row > j)
 // NP / TP: which of the two uses of an element are taken (both for the symmetric product; the T-part alone for the
 // backward pass over a triangular inverse, whose diagonal tiles store their zeros: DIAG = false there)
@@ -95,14 +157,15 @@ __device__ __forceinline__ void sy_compute(const SyLane& s, int64_t cp, const do
 // NBUF panel buffers: NBUF - 1 panels (4 KB each per wave) in flight while one is consumed.  The launch is ONE
 // generation of one-tile waves (3160 tiles on 256 CUs at n = 10^4: 12.3 waves per CU, set by the tile count, not by
 // registers), so the bytes in flight per CU are 12.3 x (NBUF - 1) x 4 KB (+ the panel being waited for).
-template <bool DIAG, bool NT, bool NP = true, bool TP = true, int NBUF = 2>
-__device__ __forceinline__ void sy_tile(const SyLane& s, int64_t c0, double& n0, double& n1,
-                                        double* __restrict__ tout, int lane) {
+template <bool DIAG, class BUF, bool NP, bool TP, int NBUF>
+__device__ __forceinline__ void sy_tile_ring(const SyLane& s, int64_t c0, double& n0, double& n1,
+                                             double* __restrict__ tout, int lane) {
   constexpr int kPanels = kTile / kSyPanel, kFull = (kPanels / NBUF) * NBUF;
   static_assert(NBUF >= 2 && NBUF <= 8, "ring of panel buffers");
-  double2_t buf[NBUF][kSyPanel];
+  BUF buf[NBUF];
+  double2_t d[kSyPanel];
 #pragma unroll
-  for (int b = 0; b + 1 < NBUF; ++b) sy_load<NT>(s, c0 + b * kSyPanel, buf[b]);
+  for (int b = 0; b + 1 < NBUF; ++b) buf[b].load(s, c0 + b * kSyPanel);
 #pragma unroll 1
   for (int g = 0; g < kFull; g += NBUF) {
 #pragma unroll
@@ -110,15 +173,35 @@ __device__ __forceinline__ void sy_tile(const SyLane& s, int64_t c0, double& n0,
       // panel g + b is consumed from buf[b]; the panel NBUF - 1 ahead goes into the buffer freed last
       const int nxt = g + b + NBUF - 1;
       if (kFull - NBUF + b + NBUF - 1 < kPanels || nxt < kPanels)  // (first test: compile time, true for every g)
-        sy_load<NT>(s, c0 + nxt * kSyPanel, buf[(b + NBUF - 1) % NBUF]);
-      sy_compute<DIAG, NP, TP>(s, c0 + (g + b) * kSyPanel, buf[b], n0, n1, tout, lane);
+        buf[(b + NBUF - 1) % NBUF].load(s, c0 + nxt * kSyPanel);
+      buf[b].get(d);
+      sy_compute<DIAG, NP, TP>(s, c0 + (g + b) * kSyPanel, d, n0, n1, tout, lane);
     }
   }
 #pragma unroll
   for (int b = 0; b < kPanels - kFull; ++b) {  // the panels a ring that does not divide 32 leaves over
-    if (kFull + b + NBUF - 1 < kPanels) sy_load<NT>(s, c0 + (kFull + b + NBUF - 1) * kSyPanel, buf[(b + NBUF - 1) % NBUF]);
-    sy_compute<DIAG, NP, TP>(s, c0 + (kFull + b) * kSyPanel, buf[b], n0, n1, tout, lane);
+    if (kFull + b + NBUF - 1 < kPanels) buf[(b + NBUF - 1) % NBUF].load(s, c0 + (kFull + b + NBUF - 1) * kSyPanel);
+    buf[b].get(d);
+    sy_compute<DIAG, NP, TP>(s, c0 + (kFull + b) * kSyPanel, d, n0, n1, tout, lane);
   }
+}
+
+template <bool DIAG, bool NT, bool NP = true, bool TP = true, int NBUF = 2>
+__device__ __forceinline__ void sy_tile(const SyLane& s, int64_t c0, double& n0, double& n1,
+                                        double* __restrict__ tout, int lane) {
+  sy_tile_ring<DIAG, SyBuf64<NT>, NP, TP, NBUF>(s, c0, n0, n1, tout, lane);
+}
+
+// an off-diagonal tile of the compact storage (s.M: the tile, c0 = 0).  scale: the tile's power of two, folded into the
+// lane's x pair before the pass (T-part) and into the N accumulators after it -- four multiplications per tile, exact
+template <bool NT, int NBUF = 2>
+__device__ __forceinline__ void sy_tile_cq(SyLane& s, double scale, double& n0, double& n1, double* __restrict__ tout,
+                                           int lane) {
+  s.xr0 *= scale;
+  s.xr1 *= scale;
+  sy_tile_ring<false, SyBufCq<NT>, true, true, NBUF>(s, 0, n0, n1, tout, lane);
+  n0 *= scale;
+  n1 *= scale;
 }
 
 }  // namespace admm

@@ -33,6 +33,13 @@ __device__ __forceinline__ double dpp_mov(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// wave-wide maximum, valid in every lane (setup kernels: the tile maxima of the compact storage, tri_tile.h)
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
 // reduce-scatter of 4 per-lane values over the 64 lanes: every lane returns the wave-wide sum of
 // element (lane >> 4)  [lane bit 5 -> +2, bit 4 -> +1].
 __device__ __forceinline__ double reduce_scatter4(double (&t)[kSyPanel]) {

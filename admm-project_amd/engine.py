@@ -476,6 +476,17 @@ class Engine:
         L.check(self._lib.admm_engine_setup_seconds(self._h, C.byref(v)))
         return v.value
 
+    def xsolve_storage(self):
+        """How the explicit inverse of the x-update is stored (admm_engine_xsolve_storage): dict(form = "fp64" |
+        "compact", stored_bytes, and the three numbers of the probe that decided it -- NaN where the compact form was
+        not built)"""
+        form, nbytes = C.c_int32(), C.c_int64()
+        ea, eb, diff = C.c_double(), C.c_double(), C.c_double()
+        L.check(self._lib.admm_engine_xsolve_storage(self._h, C.byref(form), C.byref(nbytes), C.byref(ea), C.byref(eb),
+                                                     C.byref(diff)))
+        return dict(form="compact" if form.value == L.STORAGE_COMPACT else "fp64", stored_bytes=nbytes.value,
+                    probe_err_compact=ea.value, probe_err_fp64=eb.value, probe_diff=diff.value)
+
     def info(self):
         """What create() decided about the x-update factor (admm_engine_info): the form in use, the probe errors
         of both forms, the condition estimate, and rank / sweeps when the pseudo-inverse path ran."""

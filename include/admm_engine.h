@@ -425,6 +425,20 @@ typedef struct admm_engine_info_t {
   double probe_err_trsv_one;
 } admm_engine_info_t;
 int admm_engine_info(admm_engine* eng, admm_engine_info_t* info);
+/* How the explicit inverse of the engine's own x-update factor is stored: fp64 (tile-packed at order >= 1536, a padded
+ * square below), or compact -- off-diagonal 128 x 128 tiles as 48-bit fixed point with one power-of-two scale per tile,
+ * 3/4 of the bytes the streamed x-solve reads.  create() builds the compact form where the fp64 packed triangle is too
+ * large for the caches, probes it against that triangle on the two systems of the x-solve probe and keeps it while
+ * admm_xsolve_compact_accept holds.  stored_bytes: what one x-solve reads (0: no explicit inverse in use).  The three
+ * probe numbers -- max-norm relative forward error of the compact and of the fp64 product on (L L') x = L (L' x0),
+ * their relative difference on an unstructured right-hand side -- are NaN where the compact form was not built.  Any
+ * output pointer may be NULL. */
+enum { ADMM_STORAGE_FP64 = 0, ADMM_STORAGE_COMPACT = 1 };
+int admm_engine_xsolve_storage(admm_engine* eng, int32_t* form, int64_t* stored_bytes, double* probe_err_compact,
+                               double* probe_err_fp64, double* probe_diff);
+/* the acceptance rule itself (host arithmetic, no device): 1 while
+ * err_compact <= max(1e-11, 4 err_fp64) and diff <= max(1e-11, 8 err_fp64); a NaN anywhere gives 0 */
+int admm_xsolve_compact_accept(double err_compact, double err_fp64, double diff);
 /* seconds spent in create (upload + factorisation); solverruntime = setup + runtime */
 int admm_engine_setup_seconds(admm_engine* eng, double* seconds);
 /* per-kernel timing of the last run, measured with HIP events on the engine's stream:
@@ -563,6 +577,14 @@ int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* ou
  * run, each into zero-filled partial rows; y is the sum of the P partial results in rank order (form 0: P = 1 only). */
 int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32_t form, int64_t ncached,
                  int32_t part_count, double* y);
+/* y = Q*x by the compact storage of the streamed explicit-inverse x-update: the lower triangle of M is tile-packed,
+ * quantised (admm_engine_xsolve_storage) and multiplied by the compact instantiation of the tile kernel.  fin != 0: the
+ * launch that carries the deferred finalize step (here without one), else the plain tile-packed launch.  ncached and
+ * part_count as in admm_op_symv (ncached counts tiles of the compact storage).  Q (optional, ldQ >= n): the symmetric
+ * matrix the kernel actually multiplied -- every off-diagonal tile dequantised, the diagonal tiles as given, the lower
+ * triangle mirrored. */
+int admm_op_symv_compact(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
+                         int32_t part_count, double* y, double* Q, int64_t ldQ);
 /* Y(:,k) = M_k * X(:,k), k < K: K symmetric n x n matrices stored back to back (matrix k at Ms + k*ldM*n), tile-packed
  * and multiplied in ONE batched launch (the slice inverses of consensus lasso); lower triangles only, ncached as above */
 int admm_op_symv_batch(const double* Ms, int64_t n, int64_t ldM, int32_t K, const double* X, int64_t ldX,
