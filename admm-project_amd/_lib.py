@@ -22,15 +22,18 @@ PROB_LINEARSVM, PROB_TOTALVARIATION, PROB_QP_BOUNDED, PROB_BASISPURSUIT = 5, 6, 
 PROB_MODEL, PROB_LINEARPROGRAM, PROB_QP_STANDARD, PROB_TV2D = 9, 10, 11, 12
 PROB_COVSEL = 13
 LOSS_HINGE, LOSS_01, LOSS_HINGE_OBJ01, LOSS_LOGISTIC = 0, 1, 2, 3
+LOSS_SQHINGE = 5  # (4 is unassigned and refused)
 
 
 def loss_code(text):
-    """options.lossfunction -> ADMM_LOSS_*: 'hinge', '01' (as written), 'logistic' in any letter case (DESIGN.md q29);
-    every other string runs the hinge prox with the 0-1 objective (linearsvm.m:154-158, 231-237: q18)."""
+    """options.lossfunction -> ADMM_LOSS_*: 'hinge', '01' (as written), 'logistic'  and 'sqhinge'
+     in any letter case; every other string runs the hinge prox with the 0-1 objective (linearsvm.m:154-158, 231-237: q18)."""
     if text in ("hinge", "01"):
         return LOSS_HINGE if text == "hinge" else LOSS_01
     if isinstance(text, str) and text.lower() == "logistic":
         return LOSS_LOGISTIC
+    if isinstance(text, str) and text.lower() == "sqhinge":
+        return LOSS_SQHINGE
     return LOSS_HINGE_OBJ01
 
 
@@ -107,6 +110,10 @@ class PenaltyDesc(C.Structure):  # admm_penalty_desc
 class LossDesc(C.Structure):  # admm_loss_desc
     _fields_ = [("weights", C.POINTER(C.c_double)), ("slope_pos", C.c_double), ("slope_neg", C.c_double),
                 ("epsilon", C.c_double), ("delta", C.c_double)]
+
+
+class SvmCostDesc(C.Structure):  # admm_svm_cost_desc
+    _fields_ = [("weights", C.POINTER(C.c_double)), ("cost_pos", C.c_double), ("cost_neg", C.c_double)]
 
 
 class EngineInfo(C.Structure):
@@ -190,6 +197,8 @@ _SIGNATURES = {
     "admm_engine_get_penalty": (C.c_int, [C.c_void_p, C.POINTER(PenaltyDesc), C.POINTER(C.c_int32)]),
     "admm_engine_set_loss": (C.c_int, [C.c_void_p, C.POINTER(LossDesc)]),
     "admm_engine_get_loss": (C.c_int, [C.c_void_p, C.POINTER(LossDesc), C.POINTER(C.c_int32)]),
+    "admm_engine_set_svm_cost": (C.c_int, [C.c_void_p, C.POINTER(SvmCostDesc)]),
+    "admm_engine_get_svm_cost": (C.c_int, [C.c_void_p, C.POINTER(SvmCostDesc), C.POINTER(C.c_int32)]),
     "admm_engine_set_tv2d_isotropic": (C.c_int, [C.c_void_p, C.c_int32]),
     "admm_engine_run": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(RunSummary)]),
     "admm_engine_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -226,6 +235,7 @@ _SIGNATURES = {
     "admm_op_penalty_prox": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_double,
                                        C.POINTER(PenaltyDesc), C.c_double, _dp]),
     "admm_op_loss_prox": (C.c_int, [_dp, C.c_int64, C.c_int32, C.POINTER(LossDesc), C.c_double, _dp]),
+    "admm_op_svm_prox": (C.c_int, [_dp, _dp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.POINTER(SvmCostDesc), _dp]),
     "admm_op_symv": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp]),
     "admm_op_symv_compact": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp, _dp,
                                        C.c_int64]),
@@ -250,6 +260,7 @@ _SIGNATURES = {
     "admm_svm_ovr_run": (C.c_int, [C.c_void_p, C.POINTER(SvmOvrOptions), C.POINTER(SvmOvrSummary),
                                    C.POINTER(C.c_double)]),
     "admm_svm_ovr_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_svm_ovr_set_cost": (C.c_int, [C.c_void_p, _dp, _dp]),
     "admm_svm_ovr_chunk": (C.c_int, []),
     "admm_svm_ovr_destroy": (None, [C.c_void_p]),
 }

@@ -173,9 +173,15 @@ def getproxops(problem, args):
         loss = args.get("lossfunction", "hinge")
         m, n = D.shape
         # args.Dplus (linearsvm.m:185-186), when the caller supplies it, is applied literally: x = Dplus*(z-u)
+        from .errorcheck import svm_cost_fields  # the costs (engine-side extension)
+        cost = svm_cost_fields(args, ell)
+        if cost is not None and comm is not None:
+            raise L.AdmmError(L.E_UNSUPPORTED, "args.weights / classcost on a row-sharded engine")
         eng = Engine(L.PROB_LINEARSVM, D=D, ell=ell, Cval=Cval,
                      loss=L.loss_code(loss), xsolve=xs,
                      device=dev, comm=comm, Dplus=args.get("Dplus"), **cg)
+        if cost is not None:
+            eng.set_svm_cost(**cost)
         prob = _Problem("linearsvm", eng, dict(A="D", c=0.0, nA=n, nB=m))
     elif kind == "linearprogram" or (kind == "quadraticprogram" and _get(args, "constraint") == "standard"):
         # getProxOps.m:1363 / 1410 solve [M D'; D 0] \ [rho*(z-u) - q; s] every iteration (M = rho*I for the

@@ -27,6 +27,9 @@ struct admm_binding {
   std::vector<double> lossweights;  // args.weights of 'lad' / 'huberfit' (one per row of D; empty: every weight 1), copied
   double loss_a = 1.0, loss_b = 1.0, loss_eps = 0.0, loss_delta = 1.0;  // args.slopes / args.tau, args.epsilon, args.delta
   bool has_loss = false;            // any of them was given (admm_engine_set_loss)
+  std::vector<double> svmweights;   // args.weights of 'linearsvm' (one per row of D; empty: every weight 1), copied
+  double svm_cost_pos = 1.0, svm_cost_neg = 1.0;  // args.classcost
+  bool has_svm_cost = false;        // one of the two was given (admm_engine_set_svm_cost)
   int32_t tv2d_isotropic = 0;     // args.isotropic of totalvariation2d (admm_engine_set_tv2d_isotropic)
   std::vector<double> zeros;      // c = 0 for the engines that take c as a data vector
   int64_t nA = 0, nB = 0;         // lengths of x and of z
@@ -243,11 +246,33 @@ int describe(const std::string& p, const View& args, const View& handles, admm_b
              : args.text_is("lossfunction", "01") ? ADMM_LOSS_01
              : args.text_is("lossfunction", "hinge") ? ADMM_LOSS_HINGE
              : args.text_is("lossfunction", "logistic") ? ADMM_LOSS_LOGISTIC
+             : args.text_is("lossfunction", "sqhinge") ? ADMM_LOSS_SQHINGE
                                                      : ADMM_LOSS_HINGE_OBJ01;  // linearsvmtest.m:160
     const admm_field* Dp = args.get("Dplus");  // linearsvm.m:185-186
     if (View::dense(Dp) && Dp->rows == d.n && Dp->cols == d.m) d.Dplus = Dp->data;
     b.nA = d.n;
     b.nB = d.m;
+    // the costs (engine-side extension, admm_engine_set_svm_cost): args.weights, args.classcost -- element counts and
+    // values are checked here
+    if (args.get("weights")) {
+      size_t k = 0;
+      const double* w = args.vec("weights", &k);
+      if (!w || k != static_cast<size_t>(d.m)) return fail(ADMM_E_INVALID, "args.weights must have one entry per row of D");
+      for (size_t i = 0; i < k; ++i)
+        if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
+          return fail(ADMM_E_INVALID, "args.weights: every weight must be finite and >= 0");
+      b.svmweights.assign(w, w + k);
+      b.has_svm_cost = true;
+    }
+    if (args.get("classcost")) {
+      size_t k = 0;
+      const double* cc = args.vec("classcost", &k);
+      if (!cc || k != 2 || !(cc[0] >= 0.0) || !(cc[1] >= 0.0) || !std::isfinite(cc[0]) || !std::isfinite(cc[1]))
+        return fail(ADMM_E_INVALID, "args.classcost must hold two finite values >= 0 (positive class, negative class)");
+      b.svm_cost_pos = cc[0];
+      b.svm_cost_neg = cc[1];
+      b.has_svm_cost = true;
+    }
   } else if (p == "totalvariation") {  // args.D is the sparse difference operator: implicit on the device
     size_t k = 0;
     d.s = args.vec("s", &k);
@@ -454,6 +479,10 @@ int admm_binding_apply(const admm_binding* b, admm_engine* e) {
     const admm_loss_desc ld{b->lossweights.empty() ? nullptr : b->lossweights.data(), b->loss_a, b->loss_b, b->loss_eps,
                             b->loss_delta};
     ADMM_TRY(admm_engine_set_loss(e, &ld));
+  }
+  if (b->has_svm_cost) {
+    const admm_svm_cost_desc cd{b->svmweights.empty() ? nullptr : b->svmweights.data(), b->svm_cost_pos, b->svm_cost_neg};
+    ADMM_TRY(admm_engine_set_svm_cost(e, &cd));
   }
   if (b->b_kind == 1 || b->b_kind == 2)
     return admm_engine_set_constraint_b(e, b->b_matrix, b->b_ld, b->b_kind == 2 ? b->nB : 0, ADMM_MEM_HOST, b->b_scalar,

@@ -234,6 +234,9 @@ struct admm_engine {
   // the loss family of the LAD / Huber engines (admm_engine_set_loss): defaults = today's prox, bit for bit
   double* loss_w = nullptr;   // [len] weights, or null: every weight is 1
   double loss_a = 1.0, loss_b = 1.0, loss_eps = 0.0, loss_delta = 1.0;
+  // the costs of the linear SVM (admm_engine_set_svm_cost): defaults = today's prox, bit for bit
+  double* svm_w = nullptr;    // [len] weights, or null: every weight is 1
+  double svm_cost_pos = 1.0, svm_cost_neg = 1.0;
   double* part = nullptr;     // [S_COUNT][kMaxPartBlocks]
   double* objpart = nullptr;  // [kMaxPartBlocks]
   Ctrl* ctrl = nullptr;

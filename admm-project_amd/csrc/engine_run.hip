@@ -300,6 +300,7 @@ static int wire_objective(admm_engine* e, const admm_options& o, ProxArgs& pa, F
         fa.obj_scale_z = 0.5;
         break;
       case ADMM_PROB_LINEARSVM:
+        // (ADMM_LOSS_SQHINGE always runs the cost form, which sums its own objective: any value but OBJX_NONE asks for it)
         pa.objx = (e->loss == ADMM_LOSS_HINGE)      ? OBJX_HINGE
                   : (e->loss == ADMM_LOSS_LOGISTIC) ? OBJX_LOGISTIC
                                                     : OBJX_ZEROONE;  // linearsvm.m:231-237
@@ -663,6 +664,38 @@ int admm_engine_get_loss(admm_engine* e, admm_loss_desc* out, int32_t* has_weigh
   out->epsilon = e->loss_eps;
   out->delta = e->loss_delta;
   if (has_weights) *has_weights = e->loss_w ? 1 : 0;
+  return ADMM_OK;
+}
+
+int admm_engine_set_svm_cost(admm_engine* e, const admm_svm_cost_desc* d) {
+  if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
+  if (e->problem != ADMM_PROB_LINEARSVM)
+    return fail(ADMM_E_INVALID, "the costs belong to ADMM_PROB_LINEARSVM: they enter the prox of its z-update");
+  if (e->comm) return fail(ADMM_E_UNSUPPORTED, "the costs of the linear SVM are not supported on row-sharded engines");
+  if (d) {  // (a refused call changes nothing)
+    const double costs[2] = {d->cost_pos, d->cost_neg};
+    ADMM_TRY(check_svm_cost(d->weights, e->len, costs, 2));
+  }
+  ADMM_HIP_TRY(hipSetDevice(e->device));
+  double* w = nullptr;
+  if (d && d->weights) {
+    ADMM_TRY(e->mem.alloc(&w, static_cast<size_t>(e->len)));
+    ADMM_HIP_TRY(hipMemcpyAsync(w, d->weights, sizeof(double) * e->len, hipMemcpyHostToDevice, e->stream));
+  }
+  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (the caller's weights are read until here; no run uses the old ones)
+  if (e->svm_w) e->mem.free_one(e->svm_w);
+  e->svm_w = w;
+  e->svm_cost_pos = d ? d->cost_pos : 1.0;
+  e->svm_cost_neg = d ? d->cost_neg : 1.0;
+  return ADMM_OK;
+}
+
+int admm_engine_get_svm_cost(admm_engine* e, admm_svm_cost_desc* out, int32_t* has_weights) {
+  if (!e || !out) return fail(ADMM_E_INVALID, "NULL argument");
+  out->weights = nullptr;
+  out->cost_pos = e->svm_cost_pos;
+  out->cost_neg = e->svm_cost_neg;
+  if (has_weights) *has_weights = e->svm_w ? 1 : 0;
   return ADMM_OK;
 }
 

@@ -142,6 +142,9 @@ struct GeneralLoop {
   PenaltyArgs pen{};
   bool lossy = false;  // a non-default admm_engine_set_loss: the LOSS instantiation wherever LAD's / Huber's element update runs
   LossArgs loss{};
+  bool costly = false;  // a non-default admm_engine_set_svm_cost, or the squared hinge: the COST instantiation wherever the
+                        // linear SVM's element update runs
+  SvmCostArgs cost{};
 
   // ---- may change at a batch boundary (after_batch: nothing is pending there, so the launch sequence may change)
   bool gram_now = false, gram_calibrating = false, obj_kernels = false;
@@ -180,6 +183,7 @@ struct GeneralLoop {
     grouped = e->ngroups > 0 && !split_z;
     ADMM_TRY(plan_penalty());
     plan_loss();
+    plan_svm_cost();
     if (hooks && alg != 0)
       return fail(ADMM_E_UNSUPPORTED, "caller-supplied options.altu / options.specialnorms with fast ADMM: not supported "
                                       "(admm.m:614 overwrites fast ADMM's v with the norms: q5)");
@@ -241,6 +245,16 @@ struct GeneralLoop {
     if (pa.objz != OBJZ_NONE) fa.obj_scale_z = 1.0;
   }
   const LossArgs* loss_args() const { return lossy ? &loss : nullptr; }
+
+  // the costs of the linear SVM.  Defaults leave today's kernels in place, bit for bit; the squared hinge
+  // exists in the cost form only; a zming callback (split_z) replaces the z-update as before.  S_OBJX and its scale C in
+  // the finalize stay.
+  void plan_svm_cost() {
+    costly = e->problem == ADMM_PROB_LINEARSVM && !split_z &&
+             (e->svm_w || e->svm_cost_pos != 1.0 || e->svm_cost_neg != 1.0 || e->loss == ADMM_LOSS_SQHINGE);
+    if (costly) cost = SvmCostArgs{e->svm_w, e->svm_cost_pos, e->svm_cost_neg, e->C, o.rho, e->loss, 0};
+  }
+  const SvmCostArgs* cost_args() const { return costly ? &cost : nullptr; }
 
   void plan_objective_form() {
     // the lasso objective through the cached Gram matrix: always (obj_gram = 1), or once the calibration of the first
@@ -350,7 +364,7 @@ struct GeneralLoop {
       ua.iter = 0;
       ua.fin_pending = 0;
       ua.init = 1;  // partial rows of Dplus*(z0 - u0): what the first iteration sums into its x
-      launch_uw_prox(ua, pa, e->ctrl, e->stream);
+      launch_uw_prox(ua, pa, e->ctrl, e->stream, cost_args());
       ua.init = 0;
     } else if (!e->a_identity) {
       ADMM_TRY(transposed_products(1, nullptr));
@@ -393,7 +407,7 @@ struct GeneralLoop {
       pa.ax_t = nullptr;
       pa.ax_tri = 0;
       pa.x_out = nullptr;
-      launch_ad_onepass(opa, pa, e->ctrl, &nblk, e->stream, loss_args());
+      launch_ad_onepass(opa, pa, e->ctrl, &nblk, e->stream, loss_args(), cost_args());
     }
     dff = prox_fin_args(pa, fa);
     dff.nblk = nblk;
@@ -410,7 +424,7 @@ struct GeneralLoop {
     FinArgs fprev = fa;  // the previous iteration's finalize rides along with this iteration's first launch
     fprev.x = e->uwX + ((ua.iter + 1) & 1) * e->uwldg;
     launch_uw_ax(ua, fprev, e->ctrl, e->stream);
-    launch_uw_prox(ua, pa, e->ctrl, e->stream);
+    launch_uw_prox(ua, pa, e->ctrl, e->stream, cost_args());
     ua.iter += 1;
     ua.fin_pending = 1;
     return ADMM_OK;
@@ -534,7 +548,7 @@ struct GeneralLoop {
     if (grouped && penalized) launch_group_penalty_prox_fin(pa, fa, e->grp, pen, e->ctrl, nblk, e->stream, defer);
     else if (grouped) launch_group_prox_fin(pa, fa, e->grp, e->ctrl, nblk, e->stream, defer);
     else if (penalized) launch_penalty_prox_fin(pa, fa, pen, e->ctrl, nblk, e->stream, defer);
-    else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer, loss_args());
+    else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer, loss_args(), cost_args());
   }
   FinArgs tail_fin_args(int nblk) {
     FinArgs d = prox_fin_args(pa, fa);
@@ -549,7 +563,7 @@ struct GeneralLoop {
       if (!split_z) launch_prez_for(ax, e->u, nullptr, nullptr);
     }
     if (grouped || penalized) launch_tail(nblk, true);  // (deferred = the block partials stored plainly: launch_finalize follows)
-    else launch_prox(pa, e->ctrl, nblk, e->stream, loss_args());
+    else launch_prox(pa, e->ctrl, nblk, e->stream, loss_args(), cost_args());
     if (e->altucb) {
       launch_negate(e->z, e->hk_bz, len, e->ctrl, e->stream);
       if (e->altucb(e->altuuser, e->hk_uold, e->xh, e->hk_bz, e->c ? e->c : e->hk_zero, len, e->hk_unew,

@@ -221,13 +221,33 @@ struct LossArgs {
 };
 // the checks admm_engine_set_loss and admm_op_loss_prox share (ops.hip); len HOST weights when d.weights is set
 int check_loss_desc(int32_t problem, const admm_loss_desc& d, int64_t len);
-void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss = nullptr);
+// ---- the cost form of the linear SVM (svm_cost_device.h): g(z) = C*sum_i c_i*phi(ell_i*z_i) with
+// c_i = w_i*(ell_i > 0 ? cost_pos : cost_neg) and phi the hinge, the squared hinge (this form only), the logistic or the
+// 0-1 loss.  A launcher that gets one runs the COST instantiation of its kernel, as for LossArgs: z is formed in a
+// register ahead of prox_apply (PROX_GIVEN) and the kernel sums c_i*phi(ell_i*(Dx)_i) into S_OBJX itself.  Null: today's
+// kernels.
+struct SvmCostArgs {
+  const double* w;            // [len] weights on the device, or null: every weight is 1
+  double cost_pos, cost_neg;  // class costs of the rows with ell > 0 and of the others
+  double C, rho;
+  int32_t loss;               // ADMM_LOSS_*
+  int32_t want_obj;           // sum the objective into S_OBJX (set by the launchers from ProxArgs::objx)
+};
+// the checks admm_engine_set_svm_cost, admm_svm_ovr_set_cost and admm_op_svm_prox share (ops.hip)
+int check_svm_cost(const double* weights, int64_t len, const double* costs, int64_t ncosts);
+// the operands of a COST instantiation out of the engine's: prox = PROX_GIVEN, objx = OBJX_NONE, ka = cost with want_obj
+ProxArgs svm_cost_operands(const ProxArgs& a, const SvmCostArgs& cost, SvmCostArgs* ka);
+void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss = nullptr,
+                 const SvmCostArgs* cost = nullptr);
 // A = I, alg 0 / 1: z/u update AND the finalize logic in one launch (the last workgroup to arrive finalizes);
 // a.len <= 128 * kMaxPartBlocks
 void launch_prox_fin(const ProxArgs& a, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                     bool defer = false, const LossArgs* loss = nullptr);
+                     bool defer = false, const LossArgs* loss = nullptr, const SvmCostArgs* cost = nullptr);
 // out = prox_{g/rho}(v) of the loss family (device pointers): loss_device.h's function, one thread per element
 void launch_loss_prox(const double* v, int64_t n, const LossArgs& loss, double* out, hipStream_t stream);
+// out = the z-prox of the linear SVM's cost form (device pointers): svm_cost_device.h's function, one thread per element
+void launch_svm_cost_prox(const double* v, const double* ell, int64_t n, const SvmCostArgs& cost, double* out,
+                          hipStream_t stream);
 // ---- group lasso: z_g = v_g * (||v_g|| > t_g ? 1 - t_g/||v_g|| : 0), t_g = t * w_g, over a partition of
 // the elements into G contiguous groups.  The norm of a group is needed before any of its elements can be written, so
 // the element update is planned by groups: whole groups are packed into a workgroup up to `budget` elements (and
@@ -343,7 +363,8 @@ int uw_chunks(int64_t n);
 bool uw_supported(int64_t m, int64_t n);
 FinArgs uw_fin_args(const UwArgs& a, const FinArgs& f);
 void launch_uw_ax(const UwArgs& a, const FinArgs& f, Ctrl* ctrl, hipStream_t stream);
-void launch_uw_prox(const UwArgs& a, const ProxArgs& pa, const Ctrl* ctrl, hipStream_t stream);
+void launch_uw_prox(const UwArgs& a, const ProxArgs& pa, const Ctrl* ctrl, hipStream_t stream,
+                    const SvmCostArgs* cost = nullptr);
 
 // One pass over a tall, NARROW D per A = D iteration without a dual residual (unwrapped.hip: ad_onepass_kernel)
 struct OnePassArgs {
@@ -356,7 +377,7 @@ struct OnePassArgs {
 bool onepass_supported(int64_t m, int64_t n);
 int onepass_workgroups(int64_t m);
 void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pa, const Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                       const LossArgs* loss = nullptr);
+                       const LossArgs* loss = nullptr, const SvmCostArgs* cost = nullptr);
 
 // State of the caller's z when options.B is general (the loop's z buffers hold w = -B*z): after zming returned znew,
 // zprev <- z, z <- znew, zvals(:, i) = znew and -- fast ADMM -- v = z + coef*(z - zprev) (admm.m:568, 579) or the

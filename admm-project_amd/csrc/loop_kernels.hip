@@ -14,14 +14,17 @@
 #include "group_device.h"
 #include "penalty_device.h"
 #include "loss_device.h"
+#include "svm_cost_device.h"
 #include "tv2d_pixel.h"
 #include "slot_reduce.h"
 
 namespace admm {
 
 // Loss = LossArgs: the instantiation of the loss family (loss_device.h): the weight travels with
-// prox_load's round trip and z reaches prox_apply in a register (PROX_GIVEN).  The pack is empty for every other
-// instantiation: those keep their parameter list and their code, instruction for instruction.
+// prox_load's round trip and z reaches prox_apply in a register (PROX_GIVEN).  Loss = SvmCostArgs: the cost form of the
+// linear SVM (svm_cost_device.h) through the same statements, LOGI saying whether it knows the logistic
+// loss.  The pack is empty for every other instantiation: those keep their parameter list and their code, instruction
+// for instruction.
 template <bool LOGI, class... Loss>
 __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __restrict__ ctrl, Loss... la) {
   constexpr bool LOSS = sizeof...(Loss) != 0;
@@ -44,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __
       ProxIn in = prox_load(a, i);
       const double wi = loss_weight(loss_of(la...), a.z, i);
       const double ax = gather_chunks(a.axsrc, a.naxpart, a.axld, i);
-      loss_form_z(a, loss_of(la...), wi, ax, in, acc);
+      loss_form_z<LOGI>(a, loss_of(la...), wi, ax, in, acc);
       prox_apply<false>(a, i, ax, it, kcoef, in, acc);
     } else {
       const ProxIn in = prox_load(a, i);
@@ -184,7 +187,30 @@ static ProxArgs loss_prox_operands(const ProxArgs& args, const LossArgs& loss, L
   return a;
 }
 
-void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss) {
+// the operands of a COST instantiation (a linear-SVM engine: the prox is one of the SVM's, so ell stays): z reaches
+// prox_apply in a register and the kernel sums the objective's element terms into S_OBJX itself
+ProxArgs svm_cost_operands(const ProxArgs& args, const SvmCostArgs& cost, SvmCostArgs* ka) {
+  ProxArgs a = pruned_prox_operands(args);
+  a.prox = PROX_GIVEN;
+  a.zgiven = nullptr;
+  *ka = cost;
+  ka->want_obj = a.objx != OBJX_NONE ? 1 : 0;
+  a.objx = OBJX_NONE;
+  return a;
+}
+
+void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss,
+                 const SvmCostArgs* cost) {
+  if (cost) {
+    SvmCostArgs ka;
+    const ProxArgs ac = svm_cost_operands(args, *cost, &ka);
+    const int cblocks = grid_blocks(ac.len, kBlock, kMaxPartBlocks);
+    *nblk_out = cblocks;
+    if (ka.loss == ADMM_LOSS_LOGISTIC)
+      hipLaunchKernelGGL((prox_kernel<true, SvmCostArgs>), dim3(cblocks), dim3(kBlock), 0, stream, ac, ctrl, ka);
+    else hipLaunchKernelGGL((prox_kernel<false, SvmCostArgs>), dim3(cblocks), dim3(kBlock), 0, stream, ac, ctrl, ka);
+    return;
+  }
   if (loss) {
     LossArgs la;
     const ProxArgs al = loss_prox_operands(args, *loss, &la);
@@ -453,7 +479,7 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
     }
     if constexpr (LOSS) {
       const double axs = ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e];
-      loss_form_z(a, loss_of(la...), wi, axs, in, acc);
+      loss_form_z<LOGI>(a, loss_of(la...), wi, axs, in, acc);
       prox_apply<false>(a, i, axs, it, kcoef, in, acc);
     } else {
       prox_apply<LOGI>(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
@@ -474,7 +500,20 @@ FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
 }
 
 void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                     bool defer, const LossArgs* loss) {
+                     bool defer, const LossArgs* loss, const SvmCostArgs* cost) {
+  if (cost) {
+    SvmCostArgs ka;
+    const ProxArgs ac = svm_cost_operands(args, *cost, &ka);
+    const int64_t cblocks = ceil_div(ac.len, kTailTile);
+    *nblk_out = static_cast<int>(cblocks);
+    if (ka.loss == ADMM_LOSS_LOGISTIC)
+      hipLaunchKernelGGL((prox_fin_kernel<true, SvmCostArgs>), dim3(static_cast<unsigned>(cblocks)), dim3(kTailBlock), 0, stream,
+                         ac, prox_fin_args(ac, f), ctrl, defer ? 1 : 0, ka);
+    else
+      hipLaunchKernelGGL((prox_fin_kernel<false, SvmCostArgs>), dim3(static_cast<unsigned>(cblocks)), dim3(kTailBlock), 0, stream,
+                         ac, prox_fin_args(ac, f), ctrl, defer ? 1 : 0, ka);
+    return;
+  }
   if (loss) {
     LossArgs la;
     const ProxArgs al = loss_prox_operands(args, *loss, &la);
@@ -506,6 +545,25 @@ __global__ __launch_bounds__(kBlock) void loss_prox_kernel(const double* __restr
 
 void launch_loss_prox(const double* v, int64_t n, const LossArgs& loss, double* out, hipStream_t stream) {
   hipLaunchKernelGGL(loss_prox_kernel, dim3(grid_blocks(n, kBlock, 2048)), dim3(kBlock), 0, stream, v, n, loss, out);
+}
+
+// out = the z-prox of the linear SVM's cost form: the stand-alone operator (ops.hip)
+template <bool LOGI>
+__global__ __launch_bounds__(kBlock) void svm_cost_prox_kernel(const double* __restrict__ v, const double* __restrict__ ell,
+                                                               int64_t n, SvmCostArgs ka, double* __restrict__ out) {
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * kBlock) {
+    const double li = ell[i];
+    out[i] = svm_cost_prox_elem<LOGI>(ka, svm_cost_of(ka, loss_weight(ka, v, i), li), li, v[i]);
+  }
+}
+
+void launch_svm_cost_prox(const double* v, const double* ell, int64_t n, const SvmCostArgs& cost, double* out,
+                          hipStream_t stream) {
+  const dim3 grid(grid_blocks(n, kBlock, 2048));
+  if (cost.loss == ADMM_LOSS_LOGISTIC)
+    hipLaunchKernelGGL(svm_cost_prox_kernel<true>, grid, dim3(kBlock), 0, stream, v, ell, n, cost, out);
+  else hipLaunchKernelGGL(svm_cost_prox_kernel<false>, grid, dim3(kBlock), 0, stream, v, ell, n, cost, out);
 }
 
 // ---------------------------------------------------------------- group lasso: the grouped one-launch tail

@@ -50,7 +50,9 @@ __device__ __forceinline__ double loss_obj_elem(const LossArgs& l, double wi, do
 }
 
 // the element update of the family in front of prox_apply: z in a register (the launcher has set a.prox = PROX_GIVEN
-// and a.objz = OBJZ_NONE), the whole of g(z) in S_OBJZ
+// and a.objz = OBJZ_NONE), the whole of g(z) in S_OBJZ.  (The flag is the kernels' LOGI, which the linear SVM's overload
+// in svm_cost_device.h reads; this family has no use for it.)
+template <bool LOGI = false>
 __device__ __forceinline__ void loss_form_z(const ProxArgs& a, const LossArgs& l, double wi, double ax, ProxIn& in,
                                             double (&acc)[S_COUNT]) {
   const double uo = (a.alg == 0) ? in.u_old : in.uhat_i;  // v as prox_apply forms it

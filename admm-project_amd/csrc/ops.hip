@@ -86,6 +86,19 @@ int check_loss_desc(int32_t problem, const admm_loss_desc& d, int64_t len) {
   return ADMM_OK;
 }
 
+// the checks admm_engine_set_svm_cost, admm_svm_ovr_set_cost and admm_op_svm_prox share: len HOST weights (or null) and
+// ncosts HOST class costs (or null), every one finite and >= 0
+int check_svm_cost(const double* weights, int64_t len, const double* costs, int64_t ncosts) {
+  const auto fin = [](double v) { return v >= 0.0 && v <= 1.79769313486231570e308; };  // finite, >= 0, not NaN
+  if (costs)
+    for (int64_t i = 0; i < ncosts; ++i)
+      if (!fin(costs[i])) return fail(ADMM_E_INVALID, "svm cost: class cost " + std::to_string(i) + " is negative or not finite");
+  if (weights)
+    for (int64_t i = 0; i < len; ++i)
+      if (!fin(weights[i])) return fail(ADMM_E_INVALID, "svm cost: weight " + std::to_string(i) + " is negative or not finite");
+  return ADMM_OK;
+}
+
 }  // namespace admm
 
 extern "C" {
@@ -312,6 +325,37 @@ int admm_op_loss_prox(const double* v, int64_t len, int32_t problem, const admm_
   }
   const LossArgs la{dw, d.slope_pos, d.slope_neg, d.epsilon, d.delta, rho, problem == ADMM_PROB_HUBERFIT ? 1 : 0, 0};
   launch_loss_prox(dv, len, la, dout, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * len, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
+int admm_op_svm_prox(const double* v, const double* ell, int64_t len, int32_t loss, double C, double rho,
+                     const admm_svm_cost_desc* desc, double* out) {
+  if (!v || !ell || !out || len <= 0 || !(rho > 0.0) || !(rho <= 1.79769313486231570e308) || !(C >= 0.0) ||
+      !(C <= 1.79769313486231570e308))
+    return fail(ADMM_E_INVALID, "svm_prox: bad argument");
+  if (loss != ADMM_LOSS_HINGE && loss != ADMM_LOSS_01 && loss != ADMM_LOSS_HINGE_OBJ01 && loss != ADMM_LOSS_LOGISTIC &&
+      loss != ADMM_LOSS_SQHINGE)
+    return fail(ADMM_E_INVALID, "svm_prox: bad loss");
+  const admm_svm_cost_desc none{nullptr, 1.0, 1.0};
+  const admm_svm_cost_desc& d = desc ? *desc : none;
+  const double costs[2] = {d.cost_pos, d.cost_neg};
+  ADMM_TRY(check_svm_cost(d.weights, len, costs, 2));
+  ADMM_TRY(need_device());
+  Scratch sc;
+  double *dv, *dl, *dout, *dw = nullptr;
+  ADMM_TRY(sc.alloc(&dv, len));
+  ADMM_TRY(sc.alloc(&dl, len));
+  ADMM_TRY(sc.alloc(&dout, len));
+  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * len, hipMemcpyHostToDevice));
+  ADMM_HIP_TRY(hipMemcpy(dl, ell, sizeof(double) * len, hipMemcpyHostToDevice));
+  if (d.weights) {
+    ADMM_TRY(sc.alloc(&dw, len));
+    ADMM_HIP_TRY(hipMemcpy(dw, d.weights, sizeof(double) * len, hipMemcpyHostToDevice));
+  }
+  const SvmCostArgs ka{dw, d.cost_pos, d.cost_neg, C, rho, loss, 0};
+  launch_svm_cost_prox(dv, dl, len, ka, dout, nullptr);
   ADMM_HIP_TRY(hipDeviceSynchronize());
   ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * len, hipMemcpyDeviceToHost));
   return ADMM_OK;

@@ -62,8 +62,15 @@ struct OvrSolveArgs {
   const OvrRec* rec;
 };
 
+// the costs of a pass whose chunk takes the cost form of the element update
+struct OvrCostArgs {
+  const double* w;           // m weights shared by all classes, or null: every weight is 1
+  const double* class_cost;  // K x 2: (cost_pos, cost_neg) of every class
+};
+
 int ovr_pass_workgroups(int64_t m);
-void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, hipStream_t stream);
+// cost: null, or the chunk's costs (the COST instantiation of the pass)
+void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, const OvrCostArgs* cost, hipStream_t stream);
 void launch_ovr_gsum_fin(const OvrFinArgs& a, hipStream_t stream);
 void launch_ovr_xsolve(const OvrSolveArgs& a, int32_t K, hipStream_t stream);
 // X(:, c) = Xnew(:, c) for every class that has not stopped (the triangular-solve form of the x-update)

@@ -18,6 +18,7 @@
 
 #include "engine_internal.h"
 #include "prox_device.h"
+#include "svm_cost_device.h"
 #include "svm_ovr.h"
 #include "wave_reduce.h"
 
@@ -51,10 +52,17 @@ __device__ __forceinline__ ProxArgs ovr_prox_args(const OvrPassArgs& a, int cls,
   return pa;
 }
 
+// the one element of ovr_pass_kernel's Cost... parameter pack
+__device__ __forceinline__ const OvrCostArgs& ovr_cost_of(const OvrCostArgs& c) { return c; }
+
 // INIT: only the partial rows of D'(z0 - u0), before the first iteration.  LOGI: the chunk holds a logistic class (the
-// launcher knows the losses): the instantiation whose element update carries logistic_root (prox_device.h)
-template <int KC, bool INIT, bool LOGI>
-__global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a) {
+// launcher knows the losses): the instantiation whose element update carries logistic_root (prox_device.h).
+// Cost = OvrCostArgs: the chunk holds a class with costs or the squared hinge, or the run has weights:
+// every class of the chunk takes the cost form of the element update (svm_cost_device.h), the weight of a row is loaded
+// once per block beside the block of D and the class costs once per class.  An empty pack everywhere else.
+template <int KC, bool INIT, bool LOGI, class... Cost>
+__global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a, Cost... oc) {
+  constexpr bool COST = sizeof...(Cost) != 0;
   __shared__ __attribute__((aligned(16))) double xs[kOvMaxN * KC];  // [column][class]: one column's KC values contiguous
   __shared__ double gacc[KC * kOvMaxN];
   __shared__ double axr[kOvWaves * KC * kOvRows];
@@ -91,6 +99,18 @@ __global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a
     const int cls = (a.c0 + c < a.K) ? a.c0 + c : a.K - 1;
     pas[s] = ovr_prox_args<LOGI>(a, cls, a.loss[cls]);
   }
+  [[maybe_unused]] SvmCostArgs ks[COST ? kOvSlotsPerWave : 1];
+  if constexpr (COST) {
+#pragma unroll
+    for (int s = 0; s < kOvSlotsPerWave; ++s) {
+      const int c = w + kOvWaves * s;
+      const int cls = (a.c0 + c < a.K) ? a.c0 + c : a.K - 1;
+      const double* __restrict__ cc = ovr_cost_of(oc...).class_cost + 2 * cls;
+      ks[s] = SvmCostArgs{nullptr, cc[0], cc[1], a.C, a.rho, a.loss[cls], a.objevals};
+      pas[s].prox = PROX_GIVEN;  // z reaches prox_apply in a register; the objective's terms are summed beside it
+      pas[s].objx = OBJX_NONE;
+    }
+  }
   const int64_t nblocks = (m + kOvRows - 1) / kOvRows;
   for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
     const int64_t r = blk * kOvRows + lane;
@@ -108,6 +128,13 @@ __global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a
       zp[s] = pas[s].z[rc];
       uo[s] = pas[s].u[rc];
       el[s] = pas[s].ell[rc];
+    }
+    double wv = 1.0;
+    if constexpr (COST) {  // one m-vector for all classes: redirected to z without weights, so the load stays unconditional
+      const OvrCostArgs& k = ovr_cost_of(oc...);
+      const double* pw = k.w ? k.w : pas[0].z;
+      const double wl = pw[rc];
+      wv = k.w ? wl : 1.0;
     }
     if (!INIT) {
       double p[KC];
@@ -139,7 +166,14 @@ __global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a
           in.u_old = uo[s];
           in.uhat_i = uo[s];
           in.ell_i = el[s];
-          if (r < m) prox_apply<LOGI>(pas[s], r, ax, 0, 0.0, in, acc[s], &t);
+          if constexpr (COST) {
+            if (r < m) {
+              loss_form_z<LOGI>(pas[s], ks[s], wv, ax, in, acc[s]);
+              prox_apply<false>(pas[s], r, ax, 0, 0.0, in, acc[s], &t);
+            }
+          } else {
+            if (r < m) prox_apply<LOGI>(pas[s], r, ax, 0, 0.0, in, acc[s], &t);
+          }
         }
         tsh[c * kOvRows + lane] = t;  // rows beyond m contribute nothing
       }
@@ -312,9 +346,12 @@ int ovr_pass_workgroups(int64_t m) {
   return static_cast<int>(std::min<int64_t>(ceil_div(m, int64_t{kOvRows}), kOvrMaxWg));  // one per CU
 }
 
-void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, hipStream_t stream) {
+void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, const OvrCostArgs* cost, hipStream_t stream) {
   const dim3 grid(static_cast<unsigned>(ovr_pass_workgroups(a.m))), block(kOvWaves * kWave);
   if (init) hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, true, false>), grid, block, 0, stream, a);  // (no element update)
+  else if (cost && logistic)
+    hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false, true, OvrCostArgs>), grid, block, 0, stream, a, *cost);
+  else if (cost) hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false, false, OvrCostArgs>), grid, block, 0, stream, a, *cost);
   else if (logistic) hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false, true>), grid, block, 0, stream, a);
   else hipLaunchKernelGGL((ovr_pass_kernel<kOvrChunk, false, false>), grid, block, 0, stream, a);
 }
@@ -354,6 +391,12 @@ struct admm_svm_ovr {
          *xtmp = nullptr;
   int32_t* loss = nullptr;
   std::vector<char> chunk_logistic;  // per chunk of kOvrChunk classes: one of them has ADMM_LOSS_LOGISTIC
+  // costs (admm_svm_ovr_set_cost): defaults = the kernels of a run without them, bit for bit
+  std::vector<int32_t> loss_host;    // the K losses
+  std::vector<double> cost_host;     // K x 2 (cost_pos, cost_neg); all ones by default
+  double* W = nullptr;               // m shared weights on the device, or null: every weight is 1
+  double* CC = nullptr;              // cost_host on the device
+  std::vector<char> chunk_cost;      // per chunk: weights, a class cost != 1 or ADMM_LOSS_SQHINGE -> the cost form
   OvrRec* rec = nullptr;
   OvrRec* rec_host = nullptr;  // pinned
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -377,6 +420,14 @@ int ovr_upload_cols(admm_svm_ovr* o, double* dst, int64_t ld, const double* src,
   ADMM_HIP_TRY(hipMemcpy2DAsync(dst, ld * sizeof(double), src, rows * sizeof(double), rows * sizeof(double), o->K,
                                 kind == ADMM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o->stream));
   return ADMM_OK;
+}
+
+// which chunks run the cost form of the pass: the squared hinge lives there alone, and so does every cost
+void ovr_plan_cost(admm_svm_ovr* o) {
+  o->chunk_cost.assign(static_cast<size_t>((o->K + kOvrChunk - 1) / kOvrChunk), 0);
+  for (int32_t c = 0; c < o->K; ++c)
+    if (o->W || o->loss_host[c] == ADMM_LOSS_SQHINGE || o->cost_host[2 * c] != 1.0 || o->cost_host[2 * c + 1] != 1.0)
+      o->chunk_cost[c / kOvrChunk] = 1;
 }
 
 int ovr_setup(admm_svm_ovr* o, const admm_svm_ovr_desc* desc) {
@@ -447,6 +498,11 @@ int ovr_setup(admm_svm_ovr* o, const admm_svm_ovr_desc* desc) {
   for (int32_t c = 0; c < K; ++c)
     if (lh[c] == ADMM_LOSS_LOGISTIC) o->chunk_logistic[c / kOvrChunk] = 1;
   ADMM_HIP_TRY(hipMemcpyAsync(o->loss, lh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
+  o->loss_host = lh;
+  o->cost_host.assign(static_cast<size_t>(2 * K), 1.0);
+  ADMM_TRY(o->mem.alloc(&o->CC, static_cast<size_t>(2 * K)));
+  ADMM_HIP_TRY(hipMemcpyAsync(o->CC, o->cost_host.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice, o->stream));
+  ovr_plan_cost(o);
   ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(OvrRec) + 7) / 8));
   o->rec = reinterpret_cast<OvrRec*>(raw);
   ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
@@ -503,7 +559,7 @@ int admm_svm_ovr_create(const admm_svm_ovr_desc* desc, admm_svm_ovr** out) {
   if (desc->loss)
     for (int32_t c = 0; c < desc->K; ++c)
       if (desc->loss[c] != ADMM_LOSS_HINGE && desc->loss[c] != ADMM_LOSS_01 && desc->loss[c] != ADMM_LOSS_HINGE_OBJ01 &&
-          desc->loss[c] != ADMM_LOSS_LOGISTIC)
+          desc->loss[c] != ADMM_LOSS_LOGISTIC && desc->loss[c] != ADMM_LOSS_SQHINGE)
         return fail(ADMM_E_INVALID, "bad loss for class " + std::to_string(c));
   if (desc->comm)
     return fail(ADMM_E_UNSUPPORTED, std::string("the one-vs-rest linear SVM is not row-sharded") + kPerClass);
@@ -603,11 +659,12 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
   sa.X = o->X;
   sa.ldx = o->ldx;
   sa.rec = o->rec;
+  const OvrCostArgs oc{o->W, o->CC};
   const int32_t chunks = (K + kOvrChunk - 1) / kOvrChunk;
   auto pass = [&](bool init) {
     for (int32_t ch = 0; ch < chunks; ++ch) {
       pa.c0 = ch * kOvrChunk;
-      launch_ovr_pass(pa, init, o->chunk_logistic[ch] != 0, o->stream);
+      launch_ovr_pass(pa, init, o->chunk_logistic[ch] != 0, o->chunk_cost[ch] ? &oc : nullptr, o->stream);
     }
   };
   const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
@@ -656,6 +713,26 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
   }
   o->last = op;
   o->has_run = true;
+  return ADMM_OK;
+}
+
+int admm_svm_ovr_set_cost(admm_svm_ovr* o, const double* weights, const double* class_cost) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  ADMM_TRY(check_svm_cost(weights, o->m, class_cost, 2 * static_cast<int64_t>(o->K)));  // (a refused call changes nothing)
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  double* w = nullptr;
+  if (weights) {
+    ADMM_TRY(o->mem.alloc(&w, static_cast<size_t>(o->m)));
+    ADMM_HIP_TRY(hipMemcpyAsync(w, weights, sizeof(double) * o->m, hipMemcpyHostToDevice, o->stream));
+  }
+  std::vector<double> cc(static_cast<size_t>(2 * o->K), 1.0);
+  if (class_cost) cc.assign(class_cost, class_cost + 2 * o->K);
+  ADMM_HIP_TRY(hipMemcpyAsync(o->CC, cc.data(), sizeof(double) * 2 * o->K, hipMemcpyHostToDevice, o->stream));
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (the caller's buffers are read until here)
+  if (o->W) o->mem.free_one(o->W);
+  o->W = w;
+  o->cost_host = cc;
+  ovr_plan_cost(o);
   return ADMM_OK;
 }
 

@@ -29,6 +29,7 @@
 #include "loop_kernels.h"
 #include "prox_device.h"
 #include "loss_device.h"
+#include "svm_cost_device.h"
 #include "wave_reduce.h"
 
 namespace admm {
@@ -108,8 +109,13 @@ __global__ __launch_bounds__(kBlock) void uw_ax_kernel(UwArgs a, FinArgs f, Ctrl
         ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-template <bool LOGI>
-__global__ __launch_bounds__(kUwProxThreads) void uw_prox_kernel(UwArgs a, ProxArgs pa, const Ctrl* __restrict__ ctrl) {
+// Cost = SvmCostArgs: the cost form of the linear SVM (svm_cost_device.h) -- the weight travels with
+// prox_load's round trip and z reaches prox_apply in a register (PROX_GIVEN).  The pack is empty for every other
+// instantiation: those keep their parameter list and their code.
+template <bool LOGI, class... Cost>
+__global__ __launch_bounds__(kUwProxThreads) void uw_prox_kernel(UwArgs a, ProxArgs pa, const Ctrl* __restrict__ ctrl,
+                                                                 Cost... ka) {
+  constexpr bool COST = sizeof...(Cost) != 0;
   asm volatile("" ::"s"(a.Dp), "s"(a.ldP), "s"(a.m), "s"(a.n), "s"(a.R), "s"(a.nblk), "s"(a.G), "s"(a.ldg), "s"(a.axpart),
                "s"(a.ldax), "s"(a.nchunk), "s"(a.iter), "s"(a.init), "s"(pa.z), "s"(pa.u), "s"(pa.c), "s"(pa.ell),
                "s"(pa.len), "s"(pa.part), "s"(pa.t), "s"(pa.rho), "s"(ctrl));
@@ -149,11 +155,23 @@ __global__ __launch_bounds__(kUwProxThreads) void uw_prox_kernel(UwArgs a, ProxA
         double v[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) v[k] = a.axpart[static_cast<int64_t>(k < a.nchunk ? k : a.nchunk - 1) * a.ldax + row];
-        const ProxIn in = prox_load(pa, row);
-        double ax = 0.0;
+        if constexpr (COST) {
+          ProxIn in = prox_load(pa, row);
+          const double wi = loss_weight(loss_of(ka...), pa.z, row);
+          double ax = 0.0;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) ax += (k < a.nchunk) ? v[k] : 0.0;
-        if (tid < nrow) prox_apply<LOGI>(pa, row, ax, it, kcoef, in, acc, &w);
+          for (int k = 0; k < 16; ++k) ax += (k < a.nchunk) ? v[k] : 0.0;
+          if (tid < nrow) {
+            loss_form_z<LOGI>(pa, loss_of(ka...), wi, ax, in, acc);
+            prox_apply<false>(pa, row, ax, it, kcoef, in, acc, &w);
+          }
+        } else {
+          const ProxIn in = prox_load(pa, row);
+          double ax = 0.0;
+#pragma unroll
+          for (int k = 0; k < 16; ++k) ax += (k < a.nchunk) ? v[k] : 0.0;
+          if (tid < nrow) prox_apply<LOGI>(pa, row, ax, it, kcoef, in, acc, &w);
+        }
 #pragma unroll
         for (int s = 0; s < S_COUNT; ++s) accl[s][tid] += acc[s];
       } else if (tid < nrow) {
@@ -227,12 +245,22 @@ void launch_uw_ax(const UwArgs& a, const FinArgs& f, Ctrl* ctrl, hipStream_t str
   hipLaunchKernelGGL(uw_ax_kernel, grid, dim3(kBlock), 0, stream, a, uw_fin_args(a, f), ctrl);
 }
 
-void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl, hipStream_t stream) {
+void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl, hipStream_t stream,
+                    const SvmCostArgs* cost) {
   // GeneralLoop::plan takes this form only for ADMM_PROB_LINEARSVM without a z callback: the prox is the hinge, the 0-1 or
   // the logistic one, never PROX_GIVEN / PROX_BOX, so zgiven and the bounds are nulled here as they always were
   ProxArgs pa = pruned_prox_operands(pargs);
   pa.rhs_add = nullptr;
-  if (prox_is_logistic(pa))
+  if (cost) {
+    SvmCostArgs ka;
+    const ProxArgs pc = svm_cost_operands(pa, *cost, &ka);
+    if (ka.loss == ADMM_LOSS_LOGISTIC)
+      hipLaunchKernelGGL((uw_prox_kernel<true, SvmCostArgs>), dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0,
+                         stream, args, pc, ctrl, ka);
+    else
+      hipLaunchKernelGGL((uw_prox_kernel<false, SvmCostArgs>), dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0,
+                         stream, args, pc, ctrl, ka);
+  } else if (prox_is_logistic(pa))
     hipLaunchKernelGGL(uw_prox_kernel<true>, dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args,
                        pa, ctrl);
   else
@@ -257,8 +285,8 @@ void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl,
 // that records no dual residual (unwrappedadmm.m:92 / nodualerror: no D'*(z - zprev), no D'*u) and plain ADMM.
 constexpr int kOpRows = 64, kOpWaves = 8, kOpCols = 56, kOpMaxN = kOpWaves * kOpCols;  // 448
 
-// Loss = LossArgs: the instantiation of the loss family (loss_device.h), as prox_kernel's; an empty pack
-// everywhere else.
+// Loss = LossArgs: the instantiation of the loss family (loss_device.h), as prox_kernel's; Loss =
+// SvmCostArgs: the cost form of the linear SVM (svm_cost_device.h); an empty pack everywhere else.
 template <bool LOGI, class... Loss>
 __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs a, ProxArgs pa,
                                                                     const Ctrl* __restrict__ ctrl, Loss... la) {
@@ -309,7 +337,7 @@ __global__ __launch_bounds__(kOpWaves* kWave) void ad_onepass_kernel(OnePassArgs
       double t = 0.0;
       if constexpr (LOSS) {
         if (r < m) {
-          loss_form_z(pa, loss_of(la...), wi, ax, in, acc);
+          loss_form_z<LOGI>(pa, loss_of(la...), wi, ax, in, acc);
           prox_apply<false>(pa, r, ax, it, 0.0, in, acc, &t);
         }
       } else {
@@ -354,14 +382,23 @@ int onepass_workgroups(int64_t m) {
 }
 
 void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pargs, const Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                       const LossArgs* loss) {
+                       const LossArgs* loss, const SvmCostArgs* cost) {
   ProxArgs pa = pruned_prox_operands(pargs);
   pa.rhs_add = nullptr;
   pa.rhs = nullptr;  // t = c + z - u never leaves the kernel
   pa.dz = nullptr;
   const int nwg = onepass_workgroups(a.m);
   *nblk_out = nwg;
-  if (loss) {  // z reaches prox_apply in a register and the kernel sums g(z) itself (a LAD or Huber engine)
+  if (cost) {  // the same for a linear-SVM engine with costs or the squared hinge
+    SvmCostArgs ka;
+    const ProxArgs pc = svm_cost_operands(pa, *cost, &ka);
+    if (ka.loss == ADMM_LOSS_LOGISTIC)
+      hipLaunchKernelGGL((ad_onepass_kernel<true, SvmCostArgs>), dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0,
+                         stream, a, pc, ctrl, ka);
+    else
+      hipLaunchKernelGGL((ad_onepass_kernel<false, SvmCostArgs>), dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0,
+                         stream, a, pc, ctrl, ka);
+  } else if (loss) {  // z reaches prox_apply in a register and the kernel sums g(z) itself (a LAD or Huber engine)
     LossArgs la = *loss;
     la.want_obj = pa.objz != OBJZ_NONE ? 1 : 0;
     pa.prox = PROX_GIVEN;

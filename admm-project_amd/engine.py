@@ -458,6 +458,27 @@ class Engine:
         L.check(self._lib.admm_engine_get_loss(self._h, C.byref(d), C.byref(has)))
         return dict(slopes=(d.slope_pos, d.slope_neg), epsilon=d.epsilon, delta=d.delta, has_weights=bool(has.value))
 
+    def set_svm_cost(self, weights=None, classcost=(1.0, 1.0)):
+        """The costs of a linear-SVM engine (admm_engine_set_svm_cost): per-observation weights (m values >= 0) and the
+        class costs (cost_pos, cost_neg) of the rows with ell > 0 and of the others: row i costs
+        C*weights[i]*(ell[i] > 0 ? cost_pos : cost_neg).  ``set_svm_cost()`` -- both at their defaults -- restores the
+        engine's own prox."""
+        cp, cn = (float(v) for v in classcost)
+        if weights is None and cp == 1.0 and cn == 1.0:
+            L.check(self._lib.admm_engine_set_svm_cost(self._h, None))
+            return
+        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w is not None and w.size != self.nB:
+            raise ValueError(f"weights has {w.size} entries for {self.nB} observations")
+        d = L.SvmCostDesc(None if w is None else L.as_dp(w), cp, cn)
+        L.check(self._lib.admm_engine_set_svm_cost(self._h, C.byref(d)))
+
+    def svm_cost(self):
+        """what set_svm_cost left in force: dict(classcost, has_weights)"""
+        d, has = L.SvmCostDesc(), C.c_int32()
+        L.check(self._lib.admm_engine_get_svm_cost(self._h, C.byref(d), C.byref(has)))
+        return dict(classcost=(d.cost_pos, d.cost_neg), has_weights=bool(has.value))
+
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None):
@@ -603,6 +624,18 @@ class SvmOvr:
         h = C.c_void_p()
         L.check(self._lib.admm_svm_ovr_create(C.byref(d), C.byref(h)))
         self._h = h
+
+    def set_cost(self, weights=None, classcost=None):
+        """The costs of the K classes (admm_svm_ovr_set_cost): ``weights`` = m values >= 0 shared by all classes,
+        ``classcost`` = a K x 2 array, row c = (cost_pos, cost_neg) of class c.  None: the defaults (1)."""
+        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w is not None and w.size != self.m:
+            raise ValueError(f"weights has {w.size} entries for {self.m} observations")
+        cc = None if classcost is None else np.ascontiguousarray(np.asarray(classcost, dtype=np.float64))
+        if cc is not None and cc.shape != (self.K, 2):
+            raise ValueError(f"classcost is not a {self.K} x 2 array (one (pos, neg) pair per class)")
+        L.check(self._lib.admm_svm_ovr_set_cost(self._h, None if w is None else L.as_dp(w),
+                                                None if cc is None else L.as_dp(cc)))
 
     def close(self):
         if getattr(self, "_h", None):

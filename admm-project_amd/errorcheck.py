@@ -129,6 +129,49 @@ def loss_fields(src, m, kind):
     return out
 
 
+SVM_COST_KEYS = ("weights", "classcost")
+
+
+def svm_cost_fields(src, ell):
+    """The costs of linearsvm (admm_engine_set_svm_cost) out of a dict of args / options: ``weights`` (m finite values
+    >= 0) and ``classcost``, a pair (pos, neg) of finite values >= 0 or 'balanced' -> (m/(2*m_pos), m/(2*m_neg)) from the
+    signs of ``ell``.  Returns Engine.set_svm_cost's keyword arguments for the fields that were given (None where none
+    was).  Raises before any device work."""
+    given = {k: src[k] for k in SVM_COST_KEYS if src.get(k) is not None}
+    if not given:
+        return None
+    ell = np.asarray(ell, dtype=np.float64).reshape(-1)
+    out = {}
+    if "weights" in given:
+        w = np.ascontiguousarray(np.asarray(given["weights"], dtype=np.float64).reshape(-1))
+        if w.size != ell.size:
+            raise ValueError(f"weights has {w.size} entries for the {ell.size} rows of D")
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("weights: every weight must be finite and >= 0")
+        out["weights"] = w
+    if "classcost" in given:
+        out["classcost"] = class_cost_pair(given["classcost"], ell)
+    return out
+
+
+def class_cost_pair(cc, ell):
+    """(pos, neg) out of options.classcost: a pair of finite values >= 0, or 'balanced' from the label counts of ell"""
+    if isinstance(cc, str):
+        if cc.lower() != "balanced":
+            raise ValueError("classcost is neither a pair (pos, neg) nor 'balanced'")
+        m, mp = ell.size, int(np.sum(ell > 0))
+        if mp == 0 or mp == m:
+            raise ValueError("classcost = 'balanced' needs observations of both classes")
+        return (m / (2.0 * mp), m / (2.0 * (m - mp)))
+    try:
+        pair = np.asarray(cc, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("classcost is neither a pair (pos, neg) nor 'balanced'") from None
+    if pair.size != 2 or not np.all(np.isfinite(pair)) or np.any(pair < 0):
+        raise ValueError("classcost must hold two finite values >= 0 (positive class, negative class)")
+    return (float(pair[0]), float(pair[1]))
+
+
 PENALTY_KEYS = ("l1weights", "ridge", "nonnegative", "l1")
 
 

@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from .api import admm, getproxops
-from .errorcheck import LOSS_KEYS, PENALTY_KEYS, loss_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
+from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
 __all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
@@ -250,8 +250,13 @@ def unwrappedadmm(zming, D, options=None):
 def linearsvm(D, ell, C, options=None):
     """results = linearsvm(D, ell, C, options)   (solvers/linearsvm.m:92-246).
 
-    ``options['lossfunction']``: 'hinge' (default), '01', or 'logistic' -- C*sum(log(1 + exp(-ell.*(D*x)))), a loss the
-    reference does not have; any other string is the reference's hinge prox with the 0-1 objective."""
+    ``options['lossfunction']``: 'hinge' (default), '01', 'logistic' -- C*sum(log(1 + exp(-ell.*(D*x)))) -- or 'sqhinge'
+    -- C*sum(max(1 - ell.*(D*x), 0).^2), the L2-loss SVM --, two losses the reference does not have (DESIGN.md q29,
+    q34); any other string is the reference's hinge prox with the 0-1 objective.
+
+    Engine-side extension: ``options['weights']`` (m values w_i >= 0) and ``options['classcost']`` (a
+    pair (pos, neg), or 'balanced' = (m/(2*m_pos), m/(2*m_neg))) put the cost c_i = w_i*(ell_i > 0 ? pos : neg) on
+    observation i: C*sum_i c_i*phi(ell_i*(D*x)_i).  They change the z-update and the objective alone."""
     if not isinstance(options, dict):
         raise TypeError("Given options is not a struct! At least pass empty struct!")
     options = dict(options)
@@ -265,7 +270,10 @@ def linearsvm(D, ell, C, options=None):
         raise ValueError("Product ell*D is not possible; sizes incompatible!")
     _single_column_quirk(D)
     loss = options.get("lossfunction", "hinge")  # linearsvm.m:154-158
-    args = _engine_args(options, dict(D=D, Dt=None, ell=ell, C=C, lossfunction=loss))
+    cost = svm_cost_fields({k: options.pop(k, None) for k in SVM_COST_KEYS}, ell)
+    if cost is not None and "comm" in options:
+        raise ValueError("weights / classcost have no row-sharded form: options.comm")
+    args = _engine_args(options, dict(D=D, Dt=None, ell=ell, C=C, lossfunction=loss), **(cost or {}))
     if options.get("parallel", "none") in ("both", "zming", "xminf"):  # linearsvm.m:170-205
         options["parallel"] = "both"
         args["slices"] = options["slices"] = slicemaker(options.get("slices", 0), int(options.get("workers", 1)),
@@ -283,6 +291,26 @@ def ovr_label_matrix(labels, classes):
     return np.asfortranarray(np.where(labels[:, None] == np.asarray(classes)[None, :], 1.0, -1.0))
 
 
+def _ovr_costs(options, ELL):
+    """(weights, K x 2 class costs) of linearsvm_ovr out of options.weights / options.classcost (None where not given)"""
+    m, K = ELL.shape
+    w = svm_cost_fields(dict(weights=options.get("weights")), ELL[:, 0])
+    weights = None if w is None else w["weights"]
+    cc = options.get("classcost")
+    if cc is None:
+        return weights, None
+    if not isinstance(cc, str):
+        try:
+            arr = np.asarray(cc, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("classcost is neither a pair (pos, neg), 'balanced' nor a K x 2 array") from None
+        if arr.ndim == 2 and arr.shape == (K, 2):
+            return weights, np.ascontiguousarray([class_cost_pair(arr[c], ELL[:, c]) for c in range(K)])
+        if arr.ndim == 2:
+            raise ValueError(f"classcost is not a {K} x 2 array (one (pos, neg) pair per class)")
+    return weights, np.ascontiguousarray([class_cost_pair(cc, ELL[:, c]) for c in range(K)])
+
+
 _OVR_HIST = ("pnorm", "perr", "Hnormsq", "objevals")
 
 
@@ -292,7 +320,9 @@ def linearsvm_ovr(D, labels, C, options=None):
 
     ``labels``: length-m vector of class ids.  ``options['classes']`` (default: the sorted unique labels) selects and
     orders the K columns and may name a class more than once; ``options['lossfunction']`` is one string or a list with
-    one entry per column ('hinge', '01', 'logistic', mixed freely; see ``linearsvm``).  ``x0`` / ``z0`` / ``u0`` are
+    one entry per column ('hinge', '01', 'logistic', 'sqhinge', mixed freely; see ``linearsvm``).  ``options['weights']``
+    (m values >= 0) is shared by all classes; ``options['classcost']`` is one pair (pos, neg) for every class,
+    'balanced' (per class, from that class's counts) or a K x 2 array.  ``x0`` / ``z0`` / ``u0`` are
     n x K / m x K matrices (missing: random, unwrappedadmm.m:87-89).
     The options of the plain loop apply to every class (rho, abstol, reltol, Hnormtol, domaxiters, objevals,
     check_every); maxiters is 1000, stopcond 'both', nodualerror 1 (unwrappedadmm.m:90-92).
@@ -339,6 +369,7 @@ def linearsvm_ovr(D, labels, C, options=None):
     if options.get("relax", 1) != 1:
         raise ValueError("options.relax is not available in linearsvm_ovr: call linearsvm per class")
     ELL = ovr_label_matrix(labels, classes)
+    weights, class_cost = _ovr_costs(options, ELL)
     loop = {k: options[k] for k in ("rho", "abstol", "reltol", "domaxiters", "objevals") if k in options}
     if "Hreltol" in options or "Hnormtol" in options:  # admm.m:927-928 (q2): either spelling
         loop["Hnormtol"] = options.get("Hreltol", options.get("Hnormtol"))
@@ -348,6 +379,10 @@ def linearsvm_ovr(D, labels, C, options=None):
         for c in range(K):
             o = dict(loop, lossfunction=losses[c], x0=starts["x0"][:, c], z0=starts["z0"][:, c], u0=starts["u0"][:, c],
                      record_history=0)
+            if weights is not None:
+                o["weights"] = weights
+            if class_cost is not None:
+                o["classcost"] = tuple(class_cost[c])
             per.append(linearsvm(D, ELL[:, c], C, o))
         steps = np.array([r["steps"] for r in per], dtype=np.int64)
         S = int(steps.max())
@@ -368,6 +403,8 @@ def linearsvm_ovr(D, labels, C, options=None):
     from .engine import SvmOvr
     obj = SvmOvr(D, ELL, C, losses, Dplus=options.get("Dplus"), device=int(options.get("device", 0)))
     try:
+        if weights is not None or class_cost is not None:
+            obj.set_cost(weights, class_cost)
         summ = obj.run(check_every=int(options.get("check_every", 0)), x0=starts["x0"], z0=starts["z0"],
                        u0=starts["u0"], **loop)
         S = int(summ["steps"].max())

@@ -79,7 +79,11 @@ enum { ADMM_LOSS_HINGE = 0, ADMM_LOSS_01 = 1,
        ADMM_LOSS_HINGE_OBJ01 = 2 /* any other lossfunction string (e.g. linearsvmtest.m:157 passes '0-1'): the hinge
                                     prox runs, but linearsvm.m:231-237 installs the 0-1 objective */,
        ADMM_LOSS_LOGISTIC = 3 /* g(z) = C*sum log(1 + exp(-ell.*z)): not in the reference, whose unwrapped ADMM takes
-                                 any separable z-prox (unwrappedadmm.m:76-92); 'logistic'  */ };
+                                 any separable z-prox (unwrappedadmm.m:76-92); 'logistic'  */,
+       /* (4 is unassigned and refused) */
+       ADMM_LOSS_SQHINGE = 5 /* g(z) = C*sum max(1 - ell.*z, 0).^2, the L2-loss SVM: not in the reference either;
+                                'sqhinge' (DESIGN.md q34).  z = v where ell.*v >= 1, else ell.*(ell.*v + 2t)/(1 + 2t),
+                                t = C/rho */ };
 
 /* how the cached-factor x-update is applied every iteration */
 enum {
@@ -381,6 +385,32 @@ int admm_engine_set_loss(admm_engine* eng, const admm_loss_desc* desc);
 /* what is in force: the four scalars into *desc (its weights is set to NULL) and whether weights are held into
  * *has_weights (nullable) */
 int admm_engine_get_loss(admm_engine* eng, admm_loss_desc* desc, int32_t* has_weights);
+/* The costs of the linear SVM (engine-side extension: DESIGN.md q34).  With the constraint D*x - z = 0, the z-side term
+ * of an ADMM_PROB_LINEARSVM engine is g(z) = C * sum_i c_i*phi(ell_i*z_i) with
+ *   c_i = weights[i]*(ell_i > 0 ? cost_pos : cost_neg)
+ * and phi the engine's loss: max(1 - s, 0) (hinge), max(1 - s, 0)^2 (ADMM_LOSS_SQHINGE), log(1 + e^-s) (logistic),
+ * [s < 1] (0-1).  Only the z-prox changes, with v = (Ax^ + u) - c, s = ell_i*v, t_i = C*c_i/rho:
+ *   hinge     z = v + ell_i*max(min(1 - s, t_i), 0)
+ *   sqhinge   z = v (s >= 1), ell_i*(s + 2 t_i)/(1 + 2 t_i) otherwise
+ *   logistic  z = ell_i*r, r - s = t_i/(1 + e^r)
+ *   0-1       z = ell_i*y, y = s if s >= 1 or s < 1 - sqrt(2 t_i), else 1
+ * (c_i = 0 returns v itself), and objevals reports 1/2*||x||^2 + C*sum_i c_i*phi(ell_i*(D*x)_i) (linearsvm.m:231-237
+ * with the costs inside the sum; the 0-1 objective of ADMM_LOSS_01 / ADMM_LOSS_HINGE_OBJ01 counts c_i per violated row).
+ * The x-update Dplus*(z - u) holds neither ell nor C: the cached map, the one read of D per iteration, every option and
+ * every iteration form stay the engine's, with its launches per iteration; a zming callback still replaces the
+ * z-update.  Defaults: weights NULL (every weight 1), costs 1 -- with them the engine launches the kernels it always
+ * did, bit for bit.  desc == NULL restores the defaults.  weights (m HOST values) are copied at the call.
+ * ADMM_E_INVALID: another problem; a negative or non-finite weight or cost -- a refused call changes nothing.
+ * ADMM_E_UNSUPPORTED: a row-sharded engine. */
+typedef struct admm_svm_cost_desc {
+  const double* weights;
+  double cost_pos;
+  double cost_neg;
+} admm_svm_cost_desc;
+int admm_engine_set_svm_cost(admm_engine* eng, const admm_svm_cost_desc* desc);
+/* what is in force: the two costs into *desc (its weights is set to NULL) and whether weights are held into
+ * *has_weights (nullable) */
+int admm_engine_get_svm_cost(admm_engine* eng, admm_svm_cost_desc* desc, int32_t* has_weights);
 /* Isotropic 2-D total variation (engine-side extension: DESIGN.md q31): with on = 1 an ADMM_PROB_TV2D engine minimises
  * 1/2*||x - s||^2 + lambda * sum_k sqrt((Dx)[k]^2 + (Dx)[N+k]^2), k over the N pixels (the Rudin-Osher-Fatemi norm),
  * instead of the anisotropic lambda*||Dx||_1.  Only the z-update changes: for every pixel k -- those of the last image
@@ -502,6 +532,10 @@ int admm_binding_get_info(const admm_binding* b, admm_binding_info* info);
  * finite value >= 0 per row of D), `slopes` (two values > 0: positive side, negative side) or its shorthand `tau`
  * (strictly inside (0, 1): slopes tau, 1 - tau; refused beside `slopes`), `epsilon` ('lad') and `delta` ('huberfit'),
  * checked by admm_binding_create (ADMM_E_INVALID) and handed to the engine by admm_binding_apply */
+/* a 'linearsvm' binding also takes the costs of admm_engine_set_svm_cost from its args: `weights` (one finite value >= 0
+ * per row of D) and `classcost` (two finite values >= 0: cost_pos, cost_neg), checked by admm_binding_create
+ * (ADMM_E_INVALID), refused with a communicator (ADMM_E_UNSUPPORTED) and handed to the engine by admm_binding_apply;
+ * `lossfunction` = 'sqhinge' selects ADMM_LOSS_SQHINGE */
 /* after admm_engine_create: a scalar or matrix B goes to the engine (admm_engine_set_constraint_b), and the groups of a
  * 'lasso' binding whose args carry `groups` (group sizes: integers >= 1 that sum to the columns of D) and optionally
  * `groupweights` (one finite value >= 0 per group) go to admm_engine_set_groups.  admm_binding_create checks both vectors
@@ -564,6 +598,11 @@ int admm_op_penalty_prox(const double* v, int64_t n, const int64_t* sizes, int32
  * update: problem = ADMM_PROB_LAD or ADMM_PROB_HUBERFIT selects phi, desc == NULL the defaults; desc->weights holds len
  * values.  The refusals are admm_engine_set_loss's. */
 int admm_op_loss_prox(const double* v, int64_t len, int32_t problem, const admm_loss_desc* desc, double rho, double* out);
+/* the z-prox of the linear SVM with costs (admm_engine_set_svm_cost) on a host vector, by the device function of the
+ * loop's element update: out = prox of (C/rho)*c_i*phi(ell_i*.) at v, loss = ADMM_LOSS_* selects phi, desc == NULL the
+ * defaults; ell and desc->weights hold len values.  The refusals are admm_engine_set_svm_cost's. */
+int admm_op_svm_prox(const double* v, const double* ell, int64_t len, int32_t loss, double C, double rho,
+                     const admm_svm_cost_desc* desc, double* out);
 /* out = the pair shrink of isotropic 2-D total variation (admm_engine_set_tv2d_isotropic) over a 2N-vector whose halves
  * are paired: (out[k], out[N+k]) = (v[k], v[N+k]) * (||.|| > t ? 1 - t/||.|| : 0); the device function of the loop */
 int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* out);
@@ -723,6 +762,13 @@ int admm_svm_ovr_create(const admm_svm_ovr_desc* desc, admm_svm_ovr** out);
 int admm_svm_ovr_run(admm_svm_ovr* obj, const admm_svm_ovr_options* opts, admm_svm_ovr_summary* summaries,
                      double* runtime_s);
 int admm_svm_ovr_fetch(admm_svm_ovr* obj, int field, double* dst, size_t cap, size_t* written);
+/* The costs of the K classes (admm_engine_set_svm_cost states the arithmetic): weights = m HOST values
+ * shared by all classes, or NULL (every weight 1); class_cost = K x 2 HOST values, row c = (cost_pos, cost_neg) of class
+ * c, or NULL (every cost 1).  Both are copied at the call and hold for every later run; (NULL, NULL) restores the
+ * defaults, with which the pass launches the kernels it always did.  A chunk of classes takes the cost form of the pass
+ * when there are weights or one of its classes has a cost != 1 or ADMM_LOSS_SQHINGE; no m x K array is built.
+ * ADMM_E_INVALID: a negative or non-finite weight or cost -- a refused call changes nothing. */
+int admm_svm_ovr_set_cost(admm_svm_ovr* obj, const double* weights, const double* class_cost);
 /* classes one pass over D serves (K beyond it: ceil(K / chunk) passes per iteration) */
 int admm_svm_ovr_chunk(void);
 void admm_svm_ovr_destroy(admm_svm_ovr* obj);
