@@ -170,6 +170,9 @@ RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
 F_WVALS = 23
 F_COVSEL_S = 24
+F_TV2D_ROW_STAGE = 25
+TV2D_ROWS_AUTO, TV2D_ROWS_GREEN, TV2D_ROWS_COOP, TV2D_ROWS_DCT, TV2D_ROWS_THOMAS = range(5)
+TV2D_ROWS_NAMES = ("cg", "green", "coop", "dct", "thomas")  # results["tv2d_row_stage"] (0: no spectral x-update)
 
 
 class AdmmError(RuntimeError):
@@ -207,6 +210,9 @@ _SIGNATURES = {
     "admm_engine_xsolve_storage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "admm_xsolve_compact_accept": (C.c_int, [C.c_double, C.c_double, C.c_double]),
+    "admm_tv2d_row_stage": (C.c_int, [C.c_int64, C.c_int64, C.c_double]),
+    "admm_tv2d_rows_green_taps": (C.c_int, [C.c_double]),
+    "admm_dct_tables": (C.c_int, [C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     "admm_engine_setup_seconds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "admm_engine_kernel_time": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "admm_engine_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -244,6 +250,9 @@ _SIGNATURES = {
                                C.c_int64, C.c_double, _dp, C.c_int64, C.c_int32]),
     "admm_op_trtri": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int64]),
     "admm_op_llt_apply": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp]),
+    "admm_op_dct_cols": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp]),
+    "admm_op_tv2d_rows": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_double, C.c_int32, _dp]),
+    "admm_op_tv2d_xsolve": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_double, C.c_int32, _dp]),
     "admm_comm_unique_id": (C.c_int, [C.c_char_p]),
     "admm_comm_init": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "admm_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

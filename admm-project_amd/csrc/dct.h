@@ -51,13 +51,27 @@ void launch_dct_cols_inverse(const double* src, double* dst, int64_t H, int64_t 
 // along W, divide by 1 + rho*(lamH[i] + lamW[k]), DCT-III back; row pairs read and written at stride H
 void launch_dct_rows_solve_strided(double* img, int64_t H, int64_t W, double rho, const DctTables& th,
                                    const DctTables& tw, const Ctrl* ctrl, hipStream_t stream);
+// The four forms of the row stage (values: ADMM_TV2D_ROWS_* of the C ABI) and the one rule that picks among them
+enum class Tv2Rows : int32_t {
+  NONE = 0,    // (ABI: AUTO as a request; "no spectral row stage ran" as a report)
+  GREEN = 1,   // the exact Toeplitz kernel of the row operator on the mirrored row, every wave on its own: small rho, wide image
+  COOP = 2,    // the same sum with the 16 waves of a workgroup sharing the carries: truncation <= 64, width >= 384
+  DCT = 3,     // row transform + spectral division + inverse on row PAIRS read at stride H: width a power of two, even H
+  THOMAS = 4,  // the row systems solved as they stand (Thomas elimination): any width, any rho
+};
+// what a run with this height, width and rho takes; row_transform: the tables of a row transform of length W exist
+Tv2Rows tv2d_row_stage(int64_t H, int64_t W, double rho, bool row_transform);
+// whether `form` may be launched at all on this shape (weaker than the rule above: the tests force every form)
+bool tv2d_rows_form_ok(Tv2Rows form, int64_t H, int64_t W, double rho);
+
 // The row stage without a transform: dst = inv((1 + rho*lamH[i]) I + rho*L_W) applied along every row i of src (H x W,
 // column-major, the column-transformed image), as the truncated Toeplitz kernel on the mirrored row (dct.hip);
 // src != dst.  tv2d_rows_green_taps(rho) = terms per side; usable while that is well below W.
 int tv2d_rows_green_taps(double rho);
 // fin != nullptr: one extra workgroup runs the finalize logic `*fin` of the previous iteration (when fin_pending)
 void launch_tv2d_rows_green(const double* src, double* dst, int64_t H, int64_t W, double rho, const DctTables& th,
-                            const Ctrl* ctrl, hipStream_t stream, const FinArgs* fin = nullptr, bool fin_pending = false);
+                            const Ctrl* ctrl, hipStream_t stream, const FinArgs* fin = nullptr, bool fin_pending = false,
+                            Tv2Rows force = Tv2Rows::NONE);  // force: GREEN or COOP instead of the launcher's own choice
 
 // the same row stage as an exact Thomas elimination along the rows (any width, any rho): setup once per run and rho
 // (cp, inv: H x W scratch images holding the elimination factors), then src -> dst per iteration (may alias)
@@ -65,6 +79,13 @@ void launch_tv2d_rows_thomas_setup(int64_t H, int64_t W, double rho, const DctTa
                                    hipStream_t stream);
 void launch_tv2d_rows_thomas(const double* src, double* dst, int64_t H, int64_t W, double rho, const double* cp,
                              const double* inv, const Ctrl* ctrl, hipStream_t stream);
+// The spectral x-update x = inv(I + rho*D'D) y as the engine composes it: forward column transform of y in place, the
+// row stage `rows`, inverse column transform into x.  y is destroyed.  tw: the row transform's tables (DCT only);
+// cp, inv: the factors of launch_tv2d_rows_thomas_setup (THOMAS only).  fin != nullptr: the forward transform's launch
+// carries the finalize logic of the previous iteration (when fin_pending).
+void launch_tv2d_xsolve(double* y, double* x, int64_t H, int64_t W, double rho, Tv2Rows rows, const DctTables& th,
+                        const DctTables& tw, const double* cp, const double* inv, const Ctrl* ctrl, hipStream_t stream,
+                        const FinArgs* fin = nullptr, bool fin_pending = false);
 // dst (cols x rows, column-major) = src (rows x cols, column-major) transposed
 void launch_transpose(const double* src, double* dst, int64_t rows, int64_t cols, const Ctrl* ctrl,
                       hipStream_t stream);

@@ -123,13 +123,16 @@ __device__ __forceinline__ void load_pair(c64* zs, const double* a, const double
     zs[swz(n - 1 - i)] = c64{va.y, vb.y};
   }
 }
-// LDS (after the inverse network) -> (a, b), scaled
+// LDS (after the inverse network) -> (a, b), scaled.  b == a (an odd width's last column, both halves of its pair):
+// only the first half is stored -- the two halves agree to rounding, not in their bits, and with both stored the
+// column held whichever the compiler scheduled last
 __device__ __forceinline__ void store_pair(const c64* zs, double* a, double* b, int n, double scale) {
+  const bool two = b != a;  // (uniform)
 #pragma unroll 4
   for (int i = threadIdx.x; i < (n >> 1); i += blockDim.x) {
     const c64 v0 = zs[swz(i)], v1 = zs[swz(n - 1 - i)];
     store2<false>(a + 2 * i, admm_double2{v0.x * scale, v1.x * scale});
-    store2<false>(b + 2 * i, admm_double2{v0.y * scale, v1.y * scale});
+    if (two) store2<false>(b + 2 * i, admm_double2{v0.y * scale, v1.y * scale});
   }
 }
 
@@ -154,27 +157,30 @@ __device__ __forceinline__ void dct_to_spectrum(double xak, double xan, double x
 constexpr double kSqrtHalf = 0.70710678118654752440;
 constexpr double kSqrt2 = 1.41421356237309504880;
 
-// zs holds the pair (a, b) in Makhoul order (callers synchronise before): FFT, then the DCT-II coefficients to a, b
-__device__ __forceinline__ void dct_forward_from_lds(c64* zs, double* __restrict__ a, double* __restrict__ b,
-                                                     const DctTables& t) {
+// zs holds the pair (a, b) in Makhoul order (callers synchronise before): FFT, then the DCT-II coefficients to a, b.
+// b == a (an odd width's last column): the first half's coefficients alone are stored (store_pair)
+__device__ __forceinline__ void dct_forward_from_lds(c64* zs, double* a, double* b, const DctTables& t) {
   const int n = t.n, p = t.log2n;
+  const bool two = b != a;  // (uniform)
   fft_network<false>(zs, n, p, t.tw);
 #pragma unroll 2
   for (int k = threadIdx.x; k <= (n >> 1); k += blockDim.x) {
     if (k == 0) {
       a[0] = zs[0].x;
-      b[0] = zs[0].y;
+      if (two) b[0] = zs[0].y;
     } else if (k == (n >> 1)) {
       const c64 h = zs[1];  // bitrev(n/2) = 1
       a[k] = kSqrtHalf * h.x;
-      b[k] = kSqrtHalf * h.y;
+      if (two) b[k] = kSqrtHalf * h.y;
     } else {
       double xak, xan, xbk, xbn;
       spectrum_to_dct(zs[swz(bitrev(k, p))], zs[swz(bitrev(n - k, p))], t.c4[k], xak, xan, xbk, xbn);
       a[k] = xak;
       a[n - k] = xan;
-      b[k] = xbk;
-      b[n - k] = xbn;
+      if (two) {
+        b[k] = xbk;
+        b[n - k] = xbn;
+      }
     }
   }
 }
@@ -410,7 +416,7 @@ __global__ __launch_bounds__(kChirpMaxThreads) void dct_cols_forward_chirp_kerne
     const c64 vb = c64{0.5 * (zk.y + zn.y), -0.5 * (zk.x - zn.x)};
     const c64 ck = t.c4[k];
     a[k] = cmul(ck, va).x;
-    b[k] = cmul(ck, vb).x;
+    if (b != a) b[k] = cmul(ck, vb).x;  // (an odd width's last column: the first half alone, as in store_pair)
   }
 }
 
@@ -445,7 +451,7 @@ __global__ __launch_bounds__(kChirpMaxThreads) void dct_cols_inverse_chirp_kerne
     const int v = makhoul_pos(j, n);
     const c64 z = cmulc(zs[swz(v)], t.chirp[v]);
     oa[j] = z.x * scale;
-    ob[j] = z.y * scale;
+    if (!odd) ob[j] = z.y * scale;  // (as in store_pair)
   }
 }
 
@@ -913,6 +919,8 @@ __global__ __launch_bounds__(kCoopWaves* kWave) void tv2d_rows_coop_kernel(const
 static bool tv2d_rows_coop_ok(int taps, int64_t W) {
   return taps <= kCoopHalo * kCoopRun && W >= kCoopOut * kCoopRun;
 }
+// both Toeplitz kernels mirror a column index once (K < W)
+static bool tv2d_rows_green_ok(int taps, int64_t W) { return taps < W; }
 
 int tv2d_rows_green_taps(double rho) {
   const double d0 = 1.0 + 2.0 * rho;
@@ -921,9 +929,9 @@ int tv2d_rows_green_taps(double rho) {
 }
 
 void launch_tv2d_rows_green(const double* src, double* dst, int64_t H, int64_t W, double rho, const DctTables& th,
-                            const Ctrl* ctrl, hipStream_t stream, const FinArgs* fin, bool fin_pending) {
+                            const Ctrl* ctrl, hipStream_t stream, const FinArgs* fin, bool fin_pending, Tv2Rows force) {
   const int taps = tv2d_rows_green_taps(rho);
-  if (tv2d_rows_coop_ok(taps, W)) {
+  if (force == Tv2Rows::NONE ? tv2d_rows_coop_ok(taps, W) : force == Tv2Rows::COOP) {
     const unsigned cx = static_cast<unsigned>(ceil_div(H, int64_t{64})), cy = static_cast<unsigned>(ceil_div(W, int64_t{kCoopOut * kCoopRun}));
     if (fin)
       hipLaunchKernelGGL(tv2d_rows_coop_kernel<true>, dim3(cx + 1u, cy), dim3(kCoopWaves * kWave), 0, stream, src, dst, H, W,
@@ -940,6 +948,25 @@ void launch_tv2d_rows_green(const double* src, double* dst, int64_t H, int64_t W
   else
     hipLaunchKernelGGL(tv2d_rows_green_kernel<false>, dim3(gx, gy), dim3(kBlock), 0, stream, src, dst, H, W, rho, th.lam,
                        tv2d_rows_green_taps(rho), FinArgs{}, 0, ctrl);
+}
+
+// The Toeplitz stage while its truncation is short (96 terms: rho <~ 5) and well inside the width, cooperative where
+// that form applies; else the row transform where the width has one and the rows pair up; else the elimination.
+Tv2Rows tv2d_row_stage(int64_t H, int64_t W, double rho, bool row_transform) {
+  const int taps = tv2d_rows_green_taps(rho);
+  if (taps <= 96 && W >= 4 * static_cast<int64_t>(taps)) return tv2d_rows_coop_ok(taps, W) ? Tv2Rows::COOP : Tv2Rows::GREEN;
+  if (row_transform && H % 2 == 0) return Tv2Rows::DCT;
+  return Tv2Rows::THOMAS;
+}
+
+bool tv2d_rows_form_ok(Tv2Rows form, int64_t H, int64_t W, double rho) {
+  switch (form) {
+    case Tv2Rows::GREEN: return tv2d_rows_green_ok(tv2d_rows_green_taps(rho), W);
+    case Tv2Rows::COOP: return tv2d_rows_coop_ok(tv2d_rows_green_taps(rho), W);
+    case Tv2Rows::DCT: return dct_length_ok(W) && H % 2 == 0;
+    case Tv2Rows::THOMAS: return true;
+    default: return false;
+  }
 }
 
 // ---------------------------------------------------------------- the row stage as an exact tridiagonal solve
@@ -1026,6 +1053,28 @@ void launch_tv2d_rows_thomas(const double* src, double* dst, int64_t H, int64_t 
                              const double* inv, const Ctrl* ctrl, hipStream_t stream) {
   hipLaunchKernelGGL(tv2d_rows_thomas_kernel, dim3(static_cast<unsigned>(ceil_div(H, int64_t{kWave}))), dim3(kWave), 0,
                      stream, src, dst, H, W, rho, cp, inv, ctrl);
+}
+
+void launch_tv2d_xsolve(double* y, double* x, int64_t H, int64_t W, double rho, Tv2Rows rows, const DctTables& th,
+                        const DctTables& tw, const double* cp, const double* inv, const Ctrl* ctrl, hipStream_t stream,
+                        const FinArgs* fin, bool fin_pending) {
+  if (fin) launch_dct_cols_forward_fin(y, H, W, th, *fin, fin_pending, ctrl, stream);
+  else launch_dct_cols_forward(y, H, W, th, ctrl, stream);  // along i, in place
+  switch (rows) {
+    case Tv2Rows::GREEN:
+    case Tv2Rows::COOP:
+      launch_tv2d_rows_green(y, x, H, W, rho, th, ctrl, stream, nullptr, false, rows);
+      launch_dct_cols_inverse(x, x, H, W, th, ctrl, stream);
+      break;
+    case Tv2Rows::DCT:
+      launch_dct_rows_solve_strided(y, H, W, rho, th, tw, ctrl, stream);
+      launch_dct_cols_inverse(y, x, H, W, th, ctrl, stream);
+      break;
+    default:  // THOMAS
+      launch_tv2d_rows_thomas(y, x, H, W, rho, cp, inv, ctrl, stream);
+      launch_dct_cols_inverse(x, x, H, W, th, ctrl, stream);
+      break;
+  }
 }
 
 void launch_transpose(const double* src, double* dst, int64_t rows, int64_t cols, const Ctrl* ctrl,

@@ -892,6 +892,12 @@ int admm_engine_fetch(admm_engine* e, int field, double* dst, size_t cap, size_t
       if (written) *written = cap >= 2 ? 2 : 1;
       return ADMM_OK;
     }
+    case ADMM_F_TV2D_ROW_STAGE:
+      if (e->problem != ADMM_PROB_TV2D) return fail(ADMM_E_INVALID, "field exists only for 2-D total variation");
+      if (cap < 1) return fail(ADMM_E_CAPACITY, "destination too small");
+      dst[0] = static_cast<double>(e->tv2_rows_last);
+      if (written) *written = 1;
+      return ADMM_OK;
     case ADMM_F_ZCONSENSUS:
       if (e->problem != ADMM_PROB_LASSO_CONSENSUS) return fail(ADMM_E_INVALID, "field exists only for consensus lasso");
       src = e->czc;

@@ -421,8 +421,9 @@ static int setup_lp_qp_standard(admm_engine* e, const admm_problem_desc* desc, c
 }
 
 // device tables of the column / row transform of length len (dct.h): the power-of-two network, or for any other length
-// the chirp form -- an FFT of length M >= 2*len - 1 behind every column pair
-static int dct_tables_create(admm_engine* e, int64_t len, DctTables* t) {
+// the chirp form -- an FFT of length M >= 2*len - 1 behind every column pair.  (Also behind the stand-alone operators
+// of ops.hip, with a memory owner of their own.)
+int admm::dct_tables_create(DevMem& mem, hipStream_t stream, int64_t len, DctTables* t) {
   const int32_t L = static_cast<int32_t>(len);
   const bool chirp = !dct_length_ok(L);
   const int32_t M = chirp ? dct_chirp_fft_length(L) : L;  // length of the FFT network
@@ -433,7 +434,7 @@ static int dct_tables_create(admm_engine* e, int64_t len, DctTables* t) {
   else dct_fill_tables(L, tw.data(), c4.data(), lam.data());
   auto bind = [&](const std::vector<admm_double2>& host, const admm_double2** dev) -> int {
     double* d = nullptr;
-    ADMM_TRY(upload(e->mem, &d, reinterpret_cast<const double*>(host.data()), 2 * host.size(), ADMM_MEM_HOST, e->stream));
+    ADMM_TRY(upload(mem, &d, reinterpret_cast<const double*>(host.data()), 2 * host.size(), ADMM_MEM_HOST, stream));
     *dev = reinterpret_cast<const admm_double2*>(d);
     return ADMM_OK;
   };
@@ -443,7 +444,7 @@ static int dct_tables_create(admm_engine* e, int64_t len, DctTables* t) {
   double* dlam = nullptr;
   ADMM_TRY(bind(tw, &t->tw));
   ADMM_TRY(bind(c4, &t->c4));
-  ADMM_TRY(upload(e->mem, &dlam, lam.data(), L, ADMM_MEM_HOST, e->stream));
+  ADMM_TRY(upload(mem, &dlam, lam.data(), L, ADMM_MEM_HOST, stream));
   t->lam = dlam;
   if (chirp) {
     ADMM_TRY(bind(ch, &t->chirp));
@@ -452,7 +453,7 @@ static int dct_tables_create(admm_engine* e, int64_t len, DctTables* t) {
   }
   int32_t& log2len = chirp ? t->log2bm : t->log2n;
   while ((1 << log2len) < M) ++log2len;
-  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // the host vectors go out of scope
+  ADMM_HIP_TRY(hipStreamSynchronize(stream));  // the host vectors go out of scope
   return ADMM_OK;
 }
 
@@ -480,9 +481,9 @@ static int setup_tv2d(admm_engine* e, const admm_problem_desc* desc, const Creat
   ADMM_TRY(e->mem.alloc(&e->tv_zB, round_up(2 * N, 2)));
   ADMM_TRY(e->mem.alloc(&e->tv_uB, round_up(2 * N, 2)));
   if (cx.tv2_want_dct) {
-    ADMM_TRY(dct_tables_create(e, m, &e->dctH));
+    ADMM_TRY(dct_tables_create(e->mem, e->stream, m, &e->dctH));
     e->tv2_rows_dct = dct_length_ok(n);
-    if (e->tv2_rows_dct) ADMM_TRY(dct_tables_create(e, n, &e->dctW));
+    if (e->tv2_rows_dct) ADMM_TRY(dct_tables_create(e->mem, e->stream, n, &e->dctW));
     e->tv2_dct = true;
   }
   return ADMM_OK;

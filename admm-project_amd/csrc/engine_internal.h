@@ -139,6 +139,7 @@ struct admm_engine {
   int32_t tv2_isotropic = 0;     // admm_engine_set_tv2d_isotropic: the pair prox of the isotropic norm
   bool tv2_rows_dct = false;     // ... and the width is a power of two: the row DCT exists as the fall-back of the Toeplitz row stage
   DctTables dctH{}, dctW{};
+  int32_t tv2_rows_last = 0;     // the row stage of the last run (Tv2Rows as ADMM_TV2D_ROWS_*; 0: CG, no row stage)
   // 1-D / 2-D total variation: forward-sweep intermediate and its ping-pong partner, partners of z/u, LDL' pivot prefix
   double* tv_y2 = nullptr;
   double *tv_y = nullptr, *tv_zA = nullptr, *tv_uA = nullptr, *tv_zB = nullptr, *tv_uB = nullptr;
@@ -266,6 +267,8 @@ int upload(DevMem& mem, double** dst, const double* src, size_t elems, int memki
 // copy a column-major m x n matrix into a zero-padded device buffer with leading dimension ld
 int upload_matrix(DevMem& mem, double** dst, int64_t* ld_out, const double* src, int64_t rows, int64_t cols,
                   int64_t ld_src, int memkind, hipStream_t stream);
+// device tables of the column / row transform of length len (dct.h), allocated from mem (engine_create.hip)
+int dct_tables_create(DevMem& mem, hipStream_t stream, int64_t len, DctTables* t);
 void free_hist(admm_engine* e);
 int hist_alloc(admm_engine* e, double** out, size_t elems);
 void collect_timers(admm_engine* e);

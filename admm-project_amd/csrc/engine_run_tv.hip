@@ -60,41 +60,20 @@ int cg_solve_tv2d(admm_engine* e, const double* y) {
 }
 
 // 2-D TV x-update, direct: x = C2' diag(1/(1 + rho*(lamH_i + lamW_j))) C2 y with the 2-D DCT-II C2 (dct.h).
-// Three passes over the image (6 N doubles of traffic): column DCT in place, a row stage, inverse column DCT.  The row
-// stage is one of three (dct.hip), picked per run by tv2d_rows:
-enum class Tv2Rows {
-  GREEN,   // the exact Toeplitz kernel of the row operator on the mirrored row: small rho, wide image
-  DCT,     // row transform + spectral division + inverse on row PAIRS read at stride H: width a power of two, even H
-  THOMAS,  // the row systems solved as they stand (Thomas elimination): any width, any rho
-};
+// Three passes over the image (6 N doubles of traffic): column DCT in place, a row stage, inverse column DCT
+// (dct.hip: launch_tv2d_xsolve).  The row stage is one of four, picked per run by the rule of dct.hip:
 static Tv2Rows tv2d_rows(const admm_engine* e, double rho) {
-  const int taps = tv2d_rows_green_taps(rho);
-  if (taps <= 96 && e->tv2_W >= 4 * taps) return Tv2Rows::GREEN;
-  if (e->tv2_rows_dct && e->tv2_H % 2 == 0) return Tv2Rows::DCT;
-  return Tv2Rows::THOMAS;
+  return tv2d_row_stage(e->tv2_H, e->tv2_W, rho, e->tv2_rows_dct);
 }
+static bool toeplitz(Tv2Rows rows) { return rows == Tv2Rows::GREEN || rows == Tv2Rows::COOP; }
 
 // fin != nullptr: the forward transform's launch carries the finalize logic of the previous iteration (when pending)
 static int dct_solve_tv2d(admm_engine* e, double* y, const FinArgs* fin = nullptr, bool fin_pending = false) {
   TimerScope ts(e, ADMM_K_XSOLVE);
-  const int64_t H = e->tv2_H, W = e->tv2_W;
   const double rho = e->last_opts.rho;
-  if (fin) launch_dct_cols_forward_fin(y, H, W, e->dctH, *fin, fin_pending, e->ctrl, e->stream);
-  else launch_dct_cols_forward(y, H, W, e->dctH, e->ctrl, e->stream);            // along i, in place
-  switch (tv2d_rows(e, rho)) {
-    case Tv2Rows::GREEN:
-      launch_tv2d_rows_green(y, e->x, H, W, rho, e->dctH, e->ctrl, e->stream);
-      launch_dct_cols_inverse(e->x, e->x, H, W, e->dctH, e->ctrl, e->stream);
-      break;
-    case Tv2Rows::DCT:
-      launch_dct_rows_solve_strided(y, H, W, rho, e->dctH, e->dctW, e->ctrl, e->stream);
-      launch_dct_cols_inverse(y, e->x, H, W, e->dctH, e->ctrl, e->stream);
-      break;
-    case Tv2Rows::THOMAS:  // factors in e->cg_p / e->cg_q, set up by run_total_variation_2d
-      launch_tv2d_rows_thomas(y, e->x, H, W, rho, e->cg_p, e->cg_q, e->ctrl, e->stream);
-      launch_dct_cols_inverse(e->x, e->x, H, W, e->dctH, e->ctrl, e->stream);
-      break;
-  }
+  // (THOMAS: factors in e->cg_p / e->cg_q, set up by run_total_variation_2d)
+  launch_tv2d_xsolve(y, e->x, e->tv2_H, e->tv2_W, rho, tv2d_rows(e, rho), e->dctH, e->dctW, e->cg_p, e->cg_q, e->ctrl,
+                     e->stream, fin, fin_pending);
   return ADMM_OK;
 }
 
@@ -324,6 +303,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
   const Tv2Rows rows = tv2d_rows(e, o.rho);
   if (spectral && rows == Tv2Rows::THOMAS)  // the elimination factors of this run's rho
     launch_tv2d_rows_thomas_setup(e->tv2_H, e->tv2_W, o.rho, e->dctH, e->cg_p, e->cg_q, e->stream);
+  e->tv2_rows_last = spectral ? static_cast<int32_t>(rows) : 0;
   ADMM_TRY(make_buffer_a_current(e, rs.len));
   Tv2Args ta{};
   ta.H = e->tv2_H;
@@ -347,7 +327,7 @@ int run_total_variation_2d(admm_engine* e, RunState& rs, admm_run_summary* summa
     fa.obj_scale_z = e->lambda;
   }
   if (rs.alg != 0) return run_tv2d_fast(e, rs, ta, spectral, summary);
-  const bool glued = spectral && rows == Tv2Rows::GREEN && e->dctH.bm == 0;
+  const bool glued = spectral && toeplitz(rows) && e->dctH.bm == 0;
   return Tv2dPlainLoop{e, rs, ta, spectral, glued}.run(summary);
 }
 

@@ -2,8 +2,11 @@
 // Thin wrappers: upload -> the same kernels the loop uses -> download.  They exist so the
 // parity tests can pin every kernel against the oracle on its own, and for bindings that
 // keep a user prox on the host but want the heavy linear algebra on the device.
+#include <cstring>
 #include <vector>
 
+#include "dct.h"
+#include "engine_internal.h"
 #include "kernels.h"
 #include "loop_kernels.h"
 #include "tv2d.h"
@@ -60,6 +63,59 @@ int put_verbatim(Scratch& sc, double** dst, const double* src, int64_t rows, int
 int put_padded(double* dst, int64_t npad, const double* src, int64_t n, int64_t ld_src) {
   ADMM_HIP_TRY(hipMemcpy2D(dst, npad * sizeof(double), src, ld_src * sizeof(double), n * sizeof(double), n,
                            hipMemcpyHostToDevice));
+  return ADMM_OK;
+}
+
+// ---- the spectral x-update of 2-D total variation (dct.h)
+// An H x W device image with ld = H, as the engine holds it, between kGuardCols columns on either side; the whole
+// buffer starts as all-ones bytes (NaN): an element no kernel wrote shows in the result, a write outside the image in
+// guards_intact.  (Two columns: 2H doubles keep the image at the 16-byte alignment the paired loads rely on.)
+constexpr int64_t kGuardCols = 2;
+int guarded_image(Scratch& sc, double** img, int64_t H, int64_t W) {
+  const size_t elems = static_cast<size_t>(H) * (W + 2 * kGuardCols);
+  double* base = nullptr;
+  ADMM_TRY(sc.alloc(&base, elems));
+  ADMM_HIP_TRY(hipMemset(base, 0xFF, sizeof(double) * elems));
+  *img = base + kGuardCols * H;
+  return ADMM_OK;
+}
+int guards_intact(const double* img, int64_t H, int64_t W, const char* what) {
+  const size_t g = static_cast<size_t>(kGuardCols * H);
+  std::vector<uint64_t> host(2 * g);
+  ADMM_HIP_TRY(hipMemcpy(host.data(), img - g, sizeof(double) * g, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(host.data() + g, img + H * W, sizeof(double) * g, hipMemcpyDeviceToHost));
+  for (uint64_t v : host)
+    if (v != ~uint64_t{0}) return fail(ADMM_E_NUMERIC, std::string(what) + ": a kernel wrote outside the image");
+  return ADMM_OK;
+}
+int put_image(double* dst, const double* src, int64_t H, int64_t W) {
+  ADMM_HIP_TRY(hipMemcpy(dst, src, sizeof(double) * H * W, hipMemcpyHostToDevice));
+  return ADMM_OK;
+}
+int get_image(double* dst, const double* src, int64_t H, int64_t W) {
+  ADMM_HIP_TRY(hipMemcpy(dst, src, sizeof(double) * H * W, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+int zeroed_ctrl(Scratch& sc, Ctrl** ctrl) {  // the kernels read ctrl->stop without a null test
+  ADMM_TRY(sc.alloc(ctrl, 1));
+  ADMM_HIP_TRY(hipMemset(*ctrl, 0, sizeof(Ctrl)));
+  return ADMM_OK;
+}
+struct TableMem {  // owner of the device tables of dct_tables_create
+  DevMem mem;
+  ~TableMem() { mem.release(); }
+};
+bool tv2d_height_ok(int64_t H) { return dct_length_ok(H) || dct_chirp_length_ok(H); }
+bool tv2d_rho_ok(double rho) { return rho > 0.0 && rho <= 1.79769313486231570e308; }  // finite, > 0, not NaN
+
+// the form an operator call runs: AUTO through the engine's rule, a forced one checked against its own precondition
+int tv2d_op_form(const char* op, int64_t H, int64_t W, double rho, int32_t form, Tv2Rows* rows) {
+  if (H <= 0 || W <= 0 || !tv2d_height_ok(H) || !tv2d_rho_ok(rho) || form < ADMM_TV2D_ROWS_AUTO ||
+      form > ADMM_TV2D_ROWS_THOMAS)
+    return fail(ADMM_E_INVALID, std::string(op) + ": bad argument (H a column-transform length, W >= 1, rho finite and > 0, form 0..4)");
+  *rows = form == ADMM_TV2D_ROWS_AUTO ? tv2d_row_stage(H, W, rho, dct_length_ok(W)) : static_cast<Tv2Rows>(form);
+  if (!tv2d_rows_form_ok(*rows, H, W, rho))
+    return fail(ADMM_E_INVALID, std::string(op) + ": the forced row stage does not apply to this width, height and rho");
   return ADMM_OK;
 }
 
@@ -567,6 +623,130 @@ int admm_op_llt_apply(const double* L, int64_t n, int64_t ldL, const double* x, 
   ADMM_HIP_TRY(hipDeviceSynchronize());
   ADMM_HIP_TRY(hipMemcpy(y, dy, sizeof(double) * n, hipMemcpyDeviceToHost));
   return ADMM_OK;
+}
+
+int admm_tv2d_rows_green_taps(double rho) {
+  if (!tv2d_rho_ok(rho)) return fail(ADMM_E_INVALID, "tv2d_rows_green_taps: rho must be finite and > 0");
+  return tv2d_rows_green_taps(rho);
+}
+
+int admm_tv2d_row_stage(int64_t H, int64_t W, double rho) {
+  if (H <= 0 || W <= 0 || !tv2d_rho_ok(rho)) return fail(ADMM_E_INVALID, "tv2d_row_stage: bad argument");
+  if (!tv2d_height_ok(H)) return ADMM_TV2D_ROWS_AUTO;  // no column transform: the x-update is CG, there is no row stage
+  return static_cast<int>(tv2d_row_stage(H, W, rho, dct_length_ok(W)));
+}
+
+int admm_dct_tables(int64_t n, double* tw, double* c4, double* lam, double* chirp, double* hbr, int64_t counts[5]) {
+  if (!counts || !tv2d_height_ok(n)) return fail(ADMM_E_INVALID, "dct_tables: n has no transform, or counts is null");
+  const bool ch = !dct_length_ok(n);
+  const int32_t L = static_cast<int32_t>(n), M = ch ? dct_chirp_fft_length(n) : L;
+  counts[0] = M / 2;
+  counts[1] = ch ? L : L / 2 + 1;
+  counts[2] = L;
+  counts[3] = ch ? L : 0;
+  counts[4] = ch ? M : 0;
+  if (!tw) return ADMM_OK;
+  if (!c4 || !lam || (ch && (!chirp || !hbr))) return fail(ADMM_E_INVALID, "dct_tables: a table pointer is null");
+  if (ch)
+    dct_fill_chirp_tables(L, reinterpret_cast<admm_double2*>(tw), reinterpret_cast<admm_double2*>(c4), lam,
+                          reinterpret_cast<admm_double2*>(chirp), reinterpret_cast<admm_double2*>(hbr));
+  else
+    dct_fill_tables(L, reinterpret_cast<admm_double2*>(tw), reinterpret_cast<admm_double2*>(c4), lam);
+  return ADMM_OK;
+}
+
+int admm_op_dct_cols(const double* img, int64_t H, int64_t W, int32_t inverse, double* out) {
+  if (!img || !out || H <= 0 || W <= 0 || !tv2d_height_ok(H) || (inverse != 0 && inverse != 1))
+    return fail(ADMM_E_INVALID, "dct_cols: bad argument (H a power of two in 8..8192 or any other length in 8..4096, W >= 1)");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  TableMem tm;
+  DctTables th{};
+  ADMM_TRY(dct_tables_create(tm.mem, nullptr, H, &th));
+  Ctrl* ctrl;
+  ADMM_TRY(zeroed_ctrl(sc, &ctrl));
+  double *dimg, *dout = nullptr;
+  ADMM_TRY(guarded_image(sc, &dimg, H, W));
+  ADMM_TRY(put_image(dimg, img, H, W));
+  if (inverse) {
+    ADMM_TRY(guarded_image(sc, &dout, H, W));
+    launch_dct_cols_inverse(dimg, dout, H, W, th, ctrl, nullptr);
+  } else {
+    launch_dct_cols_forward(dimg, H, W, th, ctrl, nullptr);
+  }
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_TRY(guards_intact(dimg, H, W, "dct_cols"));
+  if (inverse) ADMM_TRY(guards_intact(dout, H, W, "dct_cols"));
+  return get_image(out, inverse ? dout : dimg, H, W);
+}
+
+int admm_op_tv2d_rows(const double* src, int64_t H, int64_t W, double rho, int32_t form, double* out) {
+  if (!src || !out) return fail(ADMM_E_INVALID, "tv2d_rows: null pointer");
+  Tv2Rows rows;
+  ADMM_TRY(tv2d_op_form("tv2d_rows", H, W, rho, form, &rows));
+  ADMM_TRY(need_device());
+  Scratch sc;
+  TableMem tm;
+  DctTables th{}, tw{};
+  ADMM_TRY(dct_tables_create(tm.mem, nullptr, H, &th));  // (lamH comes from the column tables)
+  Ctrl* ctrl;
+  ADMM_TRY(zeroed_ctrl(sc, &ctrl));
+  double *dsrc, *ddst;
+  ADMM_TRY(guarded_image(sc, &dsrc, H, W));
+  ADMM_TRY(guarded_image(sc, &ddst, H, W));
+  ADMM_TRY(put_image(dsrc, src, H, W));
+  const double* result = ddst;
+  switch (rows) {
+    case Tv2Rows::GREEN:
+    case Tv2Rows::COOP:
+      launch_tv2d_rows_green(dsrc, ddst, H, W, rho, th, ctrl, nullptr, nullptr, false, rows);
+      break;
+    case Tv2Rows::DCT:  // (in place)
+      ADMM_TRY(dct_tables_create(tm.mem, nullptr, W, &tw));
+      launch_dct_rows_solve_strided(dsrc, H, W, rho, th, tw, ctrl, nullptr);
+      result = dsrc;
+      break;
+    default: {
+      double *cp, *inv;
+      ADMM_TRY(sc.alloc(&cp, static_cast<size_t>(H) * W));
+      ADMM_TRY(sc.alloc(&inv, static_cast<size_t>(H) * W));
+      launch_tv2d_rows_thomas_setup(H, W, rho, th, cp, inv, nullptr);
+      launch_tv2d_rows_thomas(dsrc, ddst, H, W, rho, cp, inv, ctrl, nullptr);
+      break;
+    }
+  }
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_TRY(guards_intact(dsrc, H, W, "tv2d_rows"));
+  ADMM_TRY(guards_intact(ddst, H, W, "tv2d_rows"));
+  return get_image(out, result, H, W);
+}
+
+int admm_op_tv2d_xsolve(const double* b, int64_t H, int64_t W, double rho, int32_t form, double* x) {
+  if (!b || !x) return fail(ADMM_E_INVALID, "tv2d_xsolve: null pointer");
+  Tv2Rows rows;
+  ADMM_TRY(tv2d_op_form("tv2d_xsolve", H, W, rho, form, &rows));
+  ADMM_TRY(need_device());
+  Scratch sc;
+  TableMem tm;
+  DctTables th{}, tw{};
+  ADMM_TRY(dct_tables_create(tm.mem, nullptr, H, &th));
+  if (rows == Tv2Rows::DCT) ADMM_TRY(dct_tables_create(tm.mem, nullptr, W, &tw));
+  Ctrl* ctrl;
+  ADMM_TRY(zeroed_ctrl(sc, &ctrl));
+  double *dy, *dx, *cp = nullptr, *inv = nullptr;
+  ADMM_TRY(guarded_image(sc, &dy, H, W));
+  ADMM_TRY(guarded_image(sc, &dx, H, W));
+  ADMM_TRY(put_image(dy, b, H, W));
+  if (rows == Tv2Rows::THOMAS) {
+    ADMM_TRY(sc.alloc(&cp, static_cast<size_t>(H) * W));
+    ADMM_TRY(sc.alloc(&inv, static_cast<size_t>(H) * W));
+    launch_tv2d_rows_thomas_setup(H, W, rho, th, cp, inv, nullptr);
+  }
+  launch_tv2d_xsolve(dy, dx, H, W, rho, rows, th, tw, cp, inv, ctrl, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_TRY(guards_intact(dy, H, W, "tv2d_xsolve"));
+  ADMM_TRY(guards_intact(dx, H, W, "tv2d_xsolve"));
+  return get_image(x, dx, H, W);
 }
 
 }  // extern "C"

@@ -601,7 +601,9 @@ def totalvariation2d(S, lam, options=None):
     4096 rows, or a power of two up to 8192): column DCT, a row stage (Toeplitz kernel, row DCT or exact tridiagonal
     solve, whichever applies to this width and rho), inverse column DCT -- and matrix-free by warm-started CG otherwise
     or with ``options['xsolve'] = 'cg'`` (``options['cg_tol']``, default 1e-11 relative; ``results['cg_capped_updates']``
-    counts x-updates that ended on the step cap); nothing is factored.  ``xopt`` is returned as an image.
+    counts x-updates that ended on the step cap); nothing is factored.  ``results['tv2d_row_stage']`` names the row
+    stage the run took: 'green', 'coop', 'dct', 'thomas', or 'cg' without a spectral x-update.  ``xopt`` is returned as
+    an image.
     """
     if options is None:
         options = {}

@@ -271,8 +271,10 @@ enum {
   ADMM_F_CONS_U = 22,     /* consensus lasso: the local slices' u_k (closure state ui{k}, getProxOps.m:1296) */
   ADMM_F_WVALS = 23,      /* (nA + nB + nU) x steps: w = [x; z; rho*u] per iteration, results.wvals of the H-norm runs
                            * (admm.m:678-681); needs the vector histories */
-  ADMM_F_COVSEL_S = 24    /* covariance selection: the n x n S the engine runs with (cov(D) when created from samples);
+  ADMM_F_COVSEL_S = 24,   /* covariance selection: the n x n S the engine runs with (cov(D) when created from samples);
                            * available before the first run */
+  ADMM_F_TV2D_ROW_STAGE = 25 /* 2-D total variation: one value, the ADMM_TV2D_ROWS_* form the row stage of the last run's
+                           * spectral x-update took (the three-launch iteration included); 0 when the x-update was CG */
 };
 
 /* ---- library ---------------------------------------------------------------- */
@@ -469,6 +471,22 @@ int admm_engine_xsolve_storage(admm_engine* eng, int32_t* form, int64_t* stored_
 /* the acceptance rule itself (host arithmetic, no device): 1 while
  * err_compact <= max(1e-11, 4 err_fp64) and diff <= max(1e-11, 8 err_fp64); a NaN anywhere gives 0 */
 int admm_xsolve_compact_accept(double err_compact, double err_fp64, double diff);
+/* The row stage of the spectral x-update of 2-D total variation (csrc/dct.hip).  admm_tv2d_row_stage is the rule the
+ * engine runs (host arithmetic, no device): the form an H x W image takes at this rho -- COOP or GREEN while the
+ * Toeplitz kernel's truncation admm_tv2d_rows_green_taps(rho) is at most 96 terms and 4 x it fits the width (COOP:
+ * truncation <= 64 and W >= 384), else DCT where W is a power of two in 8 .. 8192 and H is even, else THOMAS.
+ * ADMM_E_INVALID (negative) for H, W < 1 or a rho that is not finite and > 0. */
+enum { ADMM_TV2D_ROWS_AUTO = 0, ADMM_TV2D_ROWS_GREEN = 1, ADMM_TV2D_ROWS_COOP = 2, ADMM_TV2D_ROWS_DCT = 3,
+       ADMM_TV2D_ROWS_THOMAS = 4 };
+int admm_tv2d_row_stage(int64_t H, int64_t W, double rho);
+int admm_tv2d_rows_green_taps(double rho);
+/* The host tables of a column / row transform of length n (8 <= n <= 8192 a power of two: the network; any other
+ * 8 <= n <= 4096: the chirp form), exactly as the device receives them (no device needed).  counts[0..4] = entries of
+ * tw, c4, lam, chirp, hbr (the last two 0 for the network); tw, c4, chirp and hbr are complex, two doubles per entry.
+ * With tw == NULL only the counts are returned; otherwise every table with a non-zero count must be given.
+ *   tw[k] = e^{-2 pi i k/M}, k < M/2 (M = n, chirp form: the FFT length);  c4[k] = e^{-i pi k/(2n)};
+ *   lam[k] = 4 sin^2(pi k/(2n));  chirp[j] = e^{-pi i j^2/n};  hbr[p] = FFT_M(conj chirp, wrapped)[bitrev(p)] / M */
+int admm_dct_tables(int64_t n, double* tw, double* c4, double* lam, double* chirp, double* hbr, int64_t counts[5]);
 /* seconds spent in create (upload + factorisation); solverruntime = setup + runtime */
 int admm_engine_setup_seconds(admm_engine* eng, double* seconds);
 /* per-kernel timing of the last run, measured with HIP events on the engine's stream:
@@ -644,6 +662,19 @@ int admm_op_trtri(const double* L, int64_t n, int64_t ldL, double* X, int64_t ld
 /* y = L*(L'*x) for the lower factor L (above the diagonal ignored): the right-hand side of the setup probe that picks
  * the x-solve form, whose exact solution is x */
 int admm_op_llt_apply(const double* L, int64_t n, int64_t ldL, const double* x, double* y);
+/* The kernels of the spectral x-update of 2-D total variation on host images (H x W, column-major, ld = H on both
+ * sides), through the launchers and tables the loop uses.  H must be a length the column transform supports (8 .. 8192
+ * a power of two, or any other 8 .. 4096), W >= 1, rho finite and > 0; everything else is ADMM_E_INVALID before any
+ * launch.  The device image lies between guard columns: a kernel that writes outside it gives ADMM_E_NUMERIC.
+ *   dct_cols : out = the unnormalised DCT-II of every column of img (inverse = 0), or the inverse with its 1/H
+ *   tv2d_rows: out = inv((1 + rho*lamH[i]) I + rho*L_W) along every row i of src (a column-transformed image) by the
+ *              form ADMM_TV2D_ROWS_* (AUTO: admm_tv2d_row_stage).  A forced form outside its own precondition --
+ *              GREEN: truncation < W; COOP: truncation <= 64 and W >= 384; DCT: W a power of two in 8 .. 8192 and even
+ *              H -- is ADMM_E_INVALID
+ *   tv2d_xsolve: x = inv(I + rho*D'D) b: forward columns, that row stage, inverse columns, as one x-update does */
+int admm_op_dct_cols(const double* img, int64_t H, int64_t W, int32_t inverse, double* out);
+int admm_op_tv2d_rows(const double* src, int64_t H, int64_t W, double rho, int32_t form, double* out);
+int admm_op_tv2d_xsolve(const double* b, int64_t H, int64_t W, double rho, int32_t form, double* x);
 
 /* ---- multi-GPU (one process per GPU; rows of D sharded; RCCL over xGMI) --------
  * unique id is created on rank 0 and handed to the other ranks by the host

@@ -47,10 +47,11 @@ def test_tv2d_exact_row_stage_for_any_width_and_rho(gpu, H, W, rho):
     o = dict(objevals=1, maxiters=8, domaxiters=1, rho=rho)
     got, ref = gpu.totalvariation2d(img, 0.6, dict(o)), S.totalvariation2d(img, 0.6, dict(o))
     assert got["steps"] == ref["steps"] and got["cg_iters_total"] == 0
+    assert got["tv2d_row_stage"] == "thomas"
     for k in ("xvals", "zvals", "uvals", "pnorm", "dnorm", "objevals", "xopt"):
         _close(k, got[k], ref[k], 1e-8)
     cg = gpu.totalvariation2d(img, 0.6, dict(o, maxiters=2, xsolve="cg"))  # (and the matrix-free path on the same input)
-    assert cg["cg_iters_total"] > 0 and cg["cg_capped_updates"] == 0
+    assert cg["cg_iters_total"] > 0 and cg["cg_capped_updates"] == 0 and cg["tv2d_row_stage"] == "cg"
     _close("xvals", cg["xvals"], ref["xvals"][:, :2], 1e-7)
 
 
@@ -82,6 +83,9 @@ def test_tv2d_spectral_x_update(gpu, H, W, rho):
     ref = S.totalvariation2d(img, 0.4, dict(o))
     cg = gpu.totalvariation2d(img, 0.4, dict(o, xsolve="cg"))
     assert got["cg_iters_total"] == 0 and cg["cg_iters_total"] >= 30
+    # the row stage of each shape: the row transform, or a Toeplitz kernel where 4 x its truncation fits the width
+    toeplitz = {(128, 256): "green", (8, 1024): "coop", (16, 4096): "coop", (8, 8192): "coop"}
+    assert got["tv2d_row_stage"] == toeplitz.get((H, W), "dct")
     for k in ("xvals", "zvals", "uvals", "pnorm", "dnorm", "perr", "derr", "objevals", "xopt", "zopt", "uopt"):
         _close(k, got[k], ref[k], 1e-9)
         _close(k, cg[k], ref[k], 1e-7)
@@ -103,7 +107,12 @@ def test_tv2d_denoises(gpu):
     assert r["objopt"] == pytest.approx(obj(r["xopt"]), rel=1e-9)
 
 
-@pytest.mark.parametrize("H,W", [(5, 17), (24, 17), (32, 64)])  # CG x-update / exact row stage / Toeplitz row stage
+# CG x-update / exact row stage / row DCT / Toeplitz row stage.  (32 x 64 stood here as the Toeplitz shape, but 64
+# columns are fewer than four times the 45 resp. 61 terms: it always ran the row DCT.  32 x 250 is the Toeplitz shape.)
+FAST_ROW_STAGE = {(5, 17): "cg", (24, 17): "thomas", (32, 64): "dct", (32, 250): "green"}
+
+
+@pytest.mark.parametrize("H,W", [(5, 17), (24, 17), (32, 64), (32, 250)])
 @pytest.mark.parametrize("opts", [dict(fast=1, fasttype="strong", objevals=1, maxiters=60),
                                   dict(fast=1, fasttype="weak", objevals=1, maxiters=25),
                                   dict(fast=1, fasttype="strong", stopcond="both", rho=2.0, maxiters=40)])
@@ -115,6 +124,7 @@ def test_tv2d_fast_admm(gpu, H, W, opts):
     got = gpu.totalvariation2d(img, 0.5, dict(opts))
     ref = S.totalvariation2d(img, 0.5, dict(opts))
     assert got["steps"] == ref["steps"]
+    assert got["tv2d_row_stage"] == FAST_ROW_STAGE[(H, W)]
     keys = ("xvals", "zvals", "uvals", "vvals", "uhatvals", "avals", "dvals", "restarted", "pnorm", "dnorm", "perr", "derr",
             "objevals", "xopt", "zopt", "uopt")
     for k in keys:
@@ -137,6 +147,9 @@ def test_tv2d_any_width_when_the_height_is_a_power_of_two(gpu, H, W, rho, spectr
     for k in ("xvals", "zvals", "uvals", "pnorm", "dnorm", "perr", "derr", "objevals", "xopt", "zopt", "uopt"):
         _close(k, got[k], ref[k], 1e-7)
     assert (got["cg_iters_total"] == 0) == spectral
+    # (16 x 1000: 61 terms at rho = 2 fit the cooperative Toeplitz kernel's halo, and the width its 384 columns)
+    expected = {(32, 100): "thomas", (32, 300): "thomas", (16, 1000): "coop"}
+    assert got["tv2d_row_stage"] == expected.get((H, W), "green")
 
 
 @pytest.mark.parametrize("H,W,rho", [(24, 64, 1.0), (100, 128, 0.6), (17, 256, 1.0), (1000, 240, 1.5), (3000, 64, 1.0),
@@ -151,6 +164,9 @@ def test_tv2d_any_height_through_the_chirp_transform(gpu, H, W, rho):
     got = gpu.totalvariation2d(img, 0.4, dict(o))
     ref = S.totalvariation2d(img, 0.4, dict(o))
     assert got["steps"] == ref["steps"] and got["cg_iters_total"] == 0
+    # the row stage keeps its own conditions: the row transform at 64 and 128 columns, a Toeplitz kernel at 240 and more
+    expected = {(24, 64): "dct", (100, 128): "dct", (3000, 64): "dct", (640, 480): "coop"}
+    assert got["tv2d_row_stage"] == expected.get((H, W), "green")
     for k in ("xvals", "zvals", "uvals", "pnorm", "dnorm", "perr", "derr", "objevals", "xopt", "zopt", "uopt"):
         _close(k, got[k], ref[k], 1e-9)
     stop = gpu.totalvariation2d(img, 0.4, dict(objevals=1, rho=rho, stopcond="both", maxiters=80))
@@ -165,11 +181,12 @@ def test_tv2d_any_height_through_the_chirp_transform(gpu, H, W, rho):
                                       (2048, 201, dict(maxiters=6, domaxiters=1, record_history=0))])
 def test_tv2d_odd_widths(gpu, H, W, opts):
     """the column kernels transform two real columns as one complex sequence; an odd width's last column is both halves
-    of its pair (same values written twice) -- spectral x-update, against the oracle"""
+    of its pair (the first half's result is the one stored) -- spectral x-update, against the oracle"""
     img = _image(H + 11 * W, H, W)
     got = gpu.totalvariation2d(img, 0.5, dict(opts))
     ref = S.totalvariation2d(img, 0.5, {k: v for k, v in opts.items() if k != "record_history"})
     assert got["steps"] == ref["steps"] and got["cg_iters_total"] == 0
+    assert got["tv2d_row_stage"] == ("coop" if W == 513 else "green")  # (glued or chirp: a Toeplitz row stage in all four)
     keys = ("xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr") + (("objevals",) if opts.get("objevals") else ())
     for k in keys + (("xvals", "zvals", "uvals") if opts.get("record_history", 1) else ()):
         _close(k, got[k], ref[k], 1e-9)
@@ -207,10 +224,12 @@ def test_tv2d_fused_pass_into_the_forward_transform(gpu, H, W, opts):
     got = gpu.totalvariation2d(img, 0.45, dict(opts))
     ref = S.totalvariation2d(img, 0.45, {k: v for k, v in opts.items() if k != "record_history"})
     assert got["steps"] == ref["steps"] and got["cg_iters_total"] == 0
+    # the glued form is a Toeplitz row stage: the cooperative kernel from 384 columns on (45 resp. 61 terms <= 64)
+    assert got["tv2d_row_stage"] == ("coop" if W >= 384 else "green")
     for k in ("xopt", "zopt", "uopt", "pnorm", "dnorm"):
         _close(k, got[k], ref[k], 1e-8)
     one = gpu.totalvariation2d(img, 0.45, dict(opts, check_every=1))
-    assert one["steps"] == got["steps"]
+    assert one["steps"] == got["steps"] and one["tv2d_row_stage"] == got["tv2d_row_stage"]
     keys = ["xopt", "zopt", "uopt", "pnorm", "dnorm", "perr", "derr"]
     if opts.get("record_history", 1):
         keys += ["xvals", "zvals", "uvals"]

@@ -46,33 +46,36 @@ def _opts(rho, iters):
 def test_iso_cg_x_update(gpu):
     """fewer than 8 rows: no column transform, warm-started CG"""
     got = _parity(gpu, 5, 17, _opts(1.0, 12), 1e-7)
-    assert got["cg_iters_total"] >= got["steps"]
+    assert got["cg_iters_total"] >= got["steps"] and got["tv2d_row_stage"] == "cg"
 
 
 @pytest.mark.parametrize("H,W,rho", [(24, 17, 1.0), (33, 40, 300.0)])
 def test_iso_thomas_row_stage(gpu, H, W, rho):
     """a width below four times the Toeplitz stage's tap count (45 taps at rho = 1) that is no power of two: the row
     systems are solved as they stand (engine_run_tv.hip: tv2d_rows -> THOMAS); tv2d_fused_kernel does the pixels"""
-    assert _parity(gpu, H, W, _opts(rho, 12), 1e-9)["cg_iters_total"] == 0
+    got = _parity(gpu, H, W, _opts(rho, 12), 1e-9)
+    assert got["cg_iters_total"] == 0 and got["tv2d_row_stage"] == "thomas"
 
 
 @pytest.mark.parametrize("H,W", [(64, 200), (256, 255)])
 def test_iso_glued_fused_pass_into_the_forward_transform(gpu, H, W):
     """a power-of-two height and W >= 4 * 45 taps at rho = 1: Toeplitz row stage, three launches per iteration, the
     pixels done by tv2d_fused_dct_kernel (even width; odd width: the last column is both halves of its pair)"""
-    assert _parity(gpu, H, W, _opts(1.0, 10), 1e-9)["cg_iters_total"] == 0
+    got = _parity(gpu, H, W, _opts(1.0, 10), 1e-9)
+    assert got["cg_iters_total"] == 0 and got["tv2d_row_stage"] == "green"
 
 
 def test_iso_row_dct(gpu):
     """64 x 32 at rho = 2.5 (of test_tv2d_spectral_x_update's list): 32 < 4 * taps, so tv2d_rows leaves the Toeplitz
-    stage, and the width is a power of two with an even height: the row DCT.  (The engine does not report the stage;
-    this is the rule of engine_run_tv.hip: tv2d_rows.)"""
-    assert _parity(gpu, 64, 32, _opts(2.5, 12), 1e-9)["cg_iters_total"] == 0
+    stage, and the width is a power of two with an even height: the row DCT (dct.hip: tv2d_row_stage)."""
+    got = _parity(gpu, 64, 32, _opts(2.5, 12), 1e-9)
+    assert got["cg_iters_total"] == 0 and got["tv2d_row_stage"] == "dct"
 
 
 def test_iso_chirp_height(gpu):
     """a height that is no power of two: the column transform as a Bluestein convolution"""
-    assert _parity(gpu, 100, 128, _opts(0.6, 10), 1e-9)["cg_iters_total"] == 0
+    got = _parity(gpu, 100, 128, _opts(0.6, 10), 1e-9)
+    assert got["cg_iters_total"] == 0 and got["tv2d_row_stage"] == "dct"  # (128 < 4 x 36 terms: the row transform)
 
 
 @pytest.mark.parametrize("H,W,rho", [(600, 5, 1.0), (4095, 7, 50.0)])
@@ -106,7 +109,8 @@ def test_iso_compact_state_with_arbitrary_start(gpu, H, W, iters):
 def test_iso_fast_admm(gpu, H, W, opts):
     """fast / accelerated ADMM: the generic prox kernel's pair kind (PROX_PAIR), tv2d_dx_kernel's isotropic objective"""
     keys = KEYS + ("vvals", "uhatvals", "avals", "dvals", "restarted")
-    _parity(gpu, H, W, opts, 1e-6, keys=keys)
+    got = _parity(gpu, H, W, opts, 1e-6, keys=keys)
+    assert got["tv2d_row_stage"] == {(5, 17): "cg", (24, 17): "thomas", (32, 64): "dct"}[(H, W)]
 
 
 def test_iso_fast_admm_pairs_stay_whole_past_one_grid_stride(gpu):
