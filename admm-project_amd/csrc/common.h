@@ -46,6 +46,10 @@ struct EnvSwitches {
 };
 EnvSwitches env_switches();
 
+// argument checks of the C ABI: finite and >= 0 (> 0), false for a NaN
+inline bool finite_nonneg(double v) { return v >= 0.0 && v <= 1.79769313486231570e308; }
+inline bool finite_pos(double v) { return v > 0.0 && v <= 1.79769313486231570e308; }
+
 inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // grid of a grid-stride kernel: ceil_div(len, per) workgroups, at most `cap`, at least 1

@@ -445,6 +445,21 @@ static void fill_arg_blocks(admm_engine* e, const admm_options& o, int alg, bool
   xa.rhs_kind = e->xcb ? RHS_NONE : e->rhs_kind;
 }
 
+// The device copy of a setter's weight vector (host == null: none) into *slot, the last step of a call that has
+// validated everything else: upload, synchronise, free the old copy, store -- a refused call has changed nothing.
+static int replace_device_weights(admm_engine* e, double** slot, const double* host, int64_t len) {
+  ADMM_HIP_TRY(hipSetDevice(e->device));
+  double* w = nullptr;
+  if (host) {
+    ADMM_TRY(e->mem.alloc(&w, static_cast<size_t>(len)));
+    ADMM_HIP_TRY(hipMemcpyAsync(w, host, sizeof(double) * len, hipMemcpyHostToDevice, e->stream));
+  }
+  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (the caller's weights are read until here; no run uses the old ones)
+  if (*slot) e->mem.free_one(*slot);
+  *slot = w;
+  return ADMM_OK;
+}
+
 }  // namespace admm
 
 extern "C" {
@@ -596,25 +611,16 @@ int admm_engine_set_penalty(admm_engine* e, const admm_penalty_desc* d) {
     return fail(ADMM_E_UNSUPPORTED, "the penalty family belongs to the serial lasso (ADMM_PROB_LASSO): it replaces the "
                                     "l1 prox of its z-update");
   if (e->comm) return fail(ADMM_E_UNSUPPORTED, "the penalty family is not supported on row-sharded engines");
-  const auto ok = [](double v) { return v >= 0.0 && v <= 1.79769313486231570e308; };  // finite, >= 0, not NaN
   if (d) {  // (a refused call changes nothing)
-    if (!ok(d->l1)) return fail(ADMM_E_INVALID, "penalty: l1 must be finite and >= 0");
-    if (!ok(d->ridge)) return fail(ADMM_E_INVALID, "penalty: ridge must be finite and >= 0");
+    if (!finite_nonneg(d->l1)) return fail(ADMM_E_INVALID, "penalty: l1 must be finite and >= 0");
+    if (!finite_nonneg(d->ridge)) return fail(ADMM_E_INVALID, "penalty: ridge must be finite and >= 0");
     if (d->nonnegative != 0 && d->nonnegative != 1) return fail(ADMM_E_INVALID, "penalty: nonnegative must be 0 or 1");
     if (d->l1weights)
       for (int64_t i = 0; i < e->len; ++i)
-        if (!ok(d->l1weights[i]))
+        if (!finite_nonneg(d->l1weights[i]))
           return fail(ADMM_E_INVALID, "penalty: l1 weight " + std::to_string(i) + " is negative or not finite");
   }
-  ADMM_HIP_TRY(hipSetDevice(e->device));
-  double* w = nullptr;
-  if (d && d->l1weights) {
-    ADMM_TRY(e->mem.alloc(&w, static_cast<size_t>(e->len)));
-    ADMM_HIP_TRY(hipMemcpyAsync(w, d->l1weights, sizeof(double) * e->len, hipMemcpyHostToDevice, e->stream));
-  }
-  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (the caller's weights are read until here; no run uses the old ones)
-  if (e->pen_w) e->mem.free_one(e->pen_w);
-  e->pen_w = w;
+  ADMM_TRY(replace_device_weights(e, &e->pen_w, d ? d->l1weights : nullptr, e->len));
   e->pen_l1 = d ? d->l1 : 0.0;
   e->pen_ridge = d ? d->ridge : 0.0;
   e->pen_nonneg = d ? d->nonnegative : 0;
@@ -640,15 +646,7 @@ int admm_engine_set_loss(admm_engine* e, const admm_loss_desc* d) {
   if (e->xsolve == ADMM_XSOLVE_CALLBACK)
     return fail(ADMM_E_UNSUPPORTED, "the loss family is not supported on the generic callback engine");
   if (d) ADMM_TRY(check_loss_desc(e->problem, *d, e->len));  // (a refused call changes nothing)
-  ADMM_HIP_TRY(hipSetDevice(e->device));
-  double* w = nullptr;
-  if (d && d->weights) {
-    ADMM_TRY(e->mem.alloc(&w, static_cast<size_t>(e->len)));
-    ADMM_HIP_TRY(hipMemcpyAsync(w, d->weights, sizeof(double) * e->len, hipMemcpyHostToDevice, e->stream));
-  }
-  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (the caller's weights are read until here; no run uses the old ones)
-  if (e->loss_w) e->mem.free_one(e->loss_w);
-  e->loss_w = w;
+  ADMM_TRY(replace_device_weights(e, &e->loss_w, d ? d->weights : nullptr, e->len));
   e->loss_a = d ? d->slope_pos : 1.0;
   e->loss_b = d ? d->slope_neg : 1.0;
   e->loss_eps = d ? d->epsilon : 0.0;
@@ -676,15 +674,7 @@ int admm_engine_set_svm_cost(admm_engine* e, const admm_svm_cost_desc* d) {
     const double costs[2] = {d->cost_pos, d->cost_neg};
     ADMM_TRY(check_svm_cost(d->weights, e->len, costs, 2));
   }
-  ADMM_HIP_TRY(hipSetDevice(e->device));
-  double* w = nullptr;
-  if (d && d->weights) {
-    ADMM_TRY(e->mem.alloc(&w, static_cast<size_t>(e->len)));
-    ADMM_HIP_TRY(hipMemcpyAsync(w, d->weights, sizeof(double) * e->len, hipMemcpyHostToDevice, e->stream));
-  }
-  ADMM_HIP_TRY(hipStreamSynchronize(e->stream));  // (the caller's weights are read until here; no run uses the old ones)
-  if (e->svm_w) e->mem.free_one(e->svm_w);
-  e->svm_w = w;
+  ADMM_TRY(replace_device_weights(e, &e->svm_w, d ? d->weights : nullptr, e->len));
   e->svm_cost_pos = d ? d->cost_pos : 1.0;
   e->svm_cost_neg = d ? d->cost_neg : 1.0;
   return ADMM_OK;

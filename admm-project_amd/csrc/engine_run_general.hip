@@ -138,13 +138,9 @@ struct GeneralLoop {
   double alt_const = 0.0;
   bool gram_guard = false, split_symv = false;
   bool grouped = false;  // group lasso: the grouped element update wherever the lasso's own runs (a zming callback wins)
-  bool penalized = false;  // a non-default admm_engine_set_penalty: the penalised element update in the same places
-  PenaltyArgs pen{};
-  bool lossy = false;  // a non-default admm_engine_set_loss: the LOSS instantiation wherever LAD's / Huber's element update runs
-  LossArgs loss{};
-  bool costly = false;  // a non-default admm_engine_set_svm_cost, or the squared hinge: the COST instantiation wherever the
-                        // linear SVM's element update runs
-  SvmCostArgs cost{};
+  // the family a non-default setter (admm_engine_set_penalty / _set_loss / _set_svm_cost, or the squared hinge) puts in
+  // force wherever the problem's own element update runs; each belongs to another problem, so at most one is planned
+  ProxFamily fam{};
 
   // ---- may change at a batch boundary (after_batch: nothing is pending there, so the launch sequence may change)
   bool gram_now = false, gram_calibrating = false, obj_kernels = false;
@@ -216,13 +212,15 @@ struct GeneralLoop {
   // the penalty family.  Every field at its default leaves today's kernels in place, bit for bit; l1 is
   // read only beside groups, where lambda is the groups' weight.  The finalize takes the whole of g(z) from S_OBJZ.
   int plan_penalty() {
-    penalized = e->problem == ADMM_PROB_LASSO && !split_z &&
-                (e->pen_w || e->pen_ridge != 0.0 || e->pen_nonneg || (grouped && e->pen_l1 != 0.0));
+    const bool penalized = e->problem == ADMM_PROB_LASSO && !split_z &&
+                           (e->pen_w || e->pen_ridge != 0.0 || e->pen_nonneg || (grouped && e->pen_l1 != 0.0));
     if (!penalized) return ADMM_OK;
     if (!grouped && len > int64_t{128} * kMaxPartBlocks)
       return fail(ADMM_E_UNSUPPORTED, "a penalised lasso of more than " + std::to_string(128 * kMaxPartBlocks) +
                                           " coefficients is not supported");
     const double l1 = grouped ? e->pen_l1 : e->lambda;
+    PenaltyArgs& pen = fam.pen;
+    fam.kind = FAM_PENALTY;
     pen.w = e->pen_w;
     pen.tau = l1 / o.rho;
     pen.kappa = o.rho / (o.rho + e->pen_ridge);
@@ -238,23 +236,24 @@ struct GeneralLoop {
   // callback (split_z) replaces the z-update as before.  The finalize takes the whole of g(z) from S_OBJZ.
   void plan_loss() {
     const bool huber = e->problem == ADMM_PROB_HUBERFIT;
-    lossy = (huber || e->problem == ADMM_PROB_LAD) && !split_z &&
-            (e->loss_w || e->loss_a != 1.0 || e->loss_b != 1.0 || e->loss_eps != 0.0 || e->loss_delta != 1.0);
+    const bool lossy = (huber || e->problem == ADMM_PROB_LAD) && !split_z &&
+                       (e->loss_w || e->loss_a != 1.0 || e->loss_b != 1.0 || e->loss_eps != 0.0 || e->loss_delta != 1.0);
     if (!lossy) return;
-    loss = LossArgs{e->loss_w, e->loss_a, e->loss_b, e->loss_eps, e->loss_delta, o.rho, huber ? 1 : 0, 0};
+    fam.kind = FAM_LOSS;
+    fam.loss = LossArgs{e->loss_w, e->loss_a, e->loss_b, e->loss_eps, e->loss_delta, o.rho, huber ? 1 : 0, 0};
     if (pa.objz != OBJZ_NONE) fa.obj_scale_z = 1.0;
   }
-  const LossArgs* loss_args() const { return lossy ? &loss : nullptr; }
 
   // the costs of the linear SVM.  Defaults leave today's kernels in place, bit for bit; the squared hinge
   // exists in the cost form only; a zming callback (split_z) replaces the z-update as before.  S_OBJX and its scale C in
   // the finalize stay.
   void plan_svm_cost() {
-    costly = e->problem == ADMM_PROB_LINEARSVM && !split_z &&
-             (e->svm_w || e->svm_cost_pos != 1.0 || e->svm_cost_neg != 1.0 || e->loss == ADMM_LOSS_SQHINGE);
-    if (costly) cost = SvmCostArgs{e->svm_w, e->svm_cost_pos, e->svm_cost_neg, e->C, o.rho, e->loss, 0};
+    const bool costly = e->problem == ADMM_PROB_LINEARSVM && !split_z &&
+                        (e->svm_w || e->svm_cost_pos != 1.0 || e->svm_cost_neg != 1.0 || e->loss == ADMM_LOSS_SQHINGE);
+    if (!costly) return;
+    fam.kind = FAM_COST;
+    fam.cost = SvmCostArgs{e->svm_w, e->svm_cost_pos, e->svm_cost_neg, e->C, o.rho, e->loss, 0};
   }
-  const SvmCostArgs* cost_args() const { return costly ? &cost : nullptr; }
 
   void plan_objective_form() {
     // the lasso objective through the cached Gram matrix: always (obj_gram = 1), or once the calibration of the first
@@ -364,7 +363,7 @@ struct GeneralLoop {
       ua.iter = 0;
       ua.fin_pending = 0;
       ua.init = 1;  // partial rows of Dplus*(z0 - u0): what the first iteration sums into its x
-      launch_uw_prox(ua, pa, e->ctrl, e->stream, cost_args());
+      launch_uw_prox(ua, pa, e->ctrl, e->stream, &fam);
       ua.init = 0;
     } else if (!e->a_identity) {
       ADMM_TRY(transposed_products(1, nullptr));
@@ -407,7 +406,7 @@ struct GeneralLoop {
       pa.ax_t = nullptr;
       pa.ax_tri = 0;
       pa.x_out = nullptr;
-      launch_ad_onepass(opa, pa, e->ctrl, &nblk, e->stream, loss_args(), cost_args());
+      launch_ad_onepass(opa, pa, e->ctrl, &nblk, e->stream, &fam);
     }
     dff = prox_fin_args(pa, fa);
     dff.nblk = nblk;
@@ -424,7 +423,7 @@ struct GeneralLoop {
     FinArgs fprev = fa;  // the previous iteration's finalize rides along with this iteration's first launch
     fprev.x = e->uwX + ((ua.iter + 1) & 1) * e->uwldg;
     launch_uw_ax(ua, fprev, e->ctrl, e->stream);
-    launch_uw_prox(ua, pa, e->ctrl, e->stream, cost_args());
+    launch_uw_prox(ua, pa, e->ctrl, e->stream, &fam);
     ua.iter += 1;
     ua.fin_pending = 1;
     return ADMM_OK;
@@ -543,12 +542,11 @@ struct GeneralLoop {
     return ADMM_OK;
   }
 
-  // the one-launch tail: the lasso's, or the grouped one of group lasso (its block partials: one per workgroup of the plan)
+  // the one-launch tail with the run's family: the lasso's, or the grouped one of group lasso (its block partials: one per
+  // workgroup of the plan)
   void launch_tail(int* nblk, bool defer) {
-    if (grouped && penalized) launch_group_penalty_prox_fin(pa, fa, e->grp, pen, e->ctrl, nblk, e->stream, defer);
-    else if (grouped) launch_group_prox_fin(pa, fa, e->grp, e->ctrl, nblk, e->stream, defer);
-    else if (penalized) launch_penalty_prox_fin(pa, fa, pen, e->ctrl, nblk, e->stream, defer);
-    else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer, loss_args(), cost_args());
+    if (grouped) launch_group_prox_fin(pa, fa, e->grp, e->ctrl, nblk, e->stream, defer, &fam);
+    else launch_prox_fin(pa, fa, e->ctrl, nblk, e->stream, defer, &fam);
   }
   FinArgs tail_fin_args(int nblk) {
     FinArgs d = prox_fin_args(pa, fa);
@@ -562,8 +560,11 @@ struct GeneralLoop {
       ADMM_HIP_TRY(hipMemcpyAsync(e->hk_uold, e->u, sizeof(double) * len, hipMemcpyDeviceToDevice, e->stream));
       if (!split_z) launch_prez_for(ax, e->u, nullptr, nullptr);
     }
-    if (grouped || penalized) launch_tail(nblk, true);  // (deferred = the block partials stored plainly: launch_finalize follows)
-    else launch_prox(pa, e->ctrl, nblk, e->stream, loss_args(), cost_args());
+    // A grouped or penalised run keeps the tail kernel here, deferred (the block partials stored plainly: launch_finalize
+    // follows): a prox_kernel form of them would sum the block partials over other blocks, in another order, and change
+    // the bits.
+    if (grouped || fam.kind == FAM_PENALTY) launch_tail(nblk, true);
+    else launch_prox(pa, e->ctrl, nblk, e->stream, &fam);
     if (e->altucb) {
       launch_negate(e->z, e->hk_bz, len, e->ctrl, e->stream);
       if (e->altucb(e->altuuser, e->hk_uold, e->xh, e->hk_bz, e->c ? e->c : e->hk_zero, len, e->hk_unew,

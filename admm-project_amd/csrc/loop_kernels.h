@@ -1,4 +1,5 @@
-// loop_kernels.h -- argument blocks of the per-iteration fused kernels (loop_kernels.hip).
+// loop_kernels.h -- argument blocks and launchers of the per-iteration fused kernels (loop_kernels.hip, unwrapped.hip),
+// and the one description of the element-update family they may carry (ProxFamily).
 #pragma once
 #include <vector>
 
@@ -205,11 +206,15 @@ ProxArgs pruned_prox_operands(const ProxArgs& a);
 // PROX_PAIR pairs the two halves of the vector: len must be even.  A caller checks this before launch_prox (which
 // returns nothing); c and relaxation go into both elements' v as for every other prox.
 inline bool prox_pair_ok(const ProxArgs& a) { return a.len > 0 && (a.len & 1) == 0; }
-// ---- the loss family of the LAD and Huber engines (loss_device.h): g(z) = sum_i w_i*phi(z_i) with
+// ---- The element-update families.  A family replaces the z-prox of one problem's engine; at most one is active on an
+// engine.  The kernels carry it as the one element of their `Loss...` parameter pack: the family's weight travels with
+// prox_load's round trip, loss_form_z forms z in a register ahead of prox_apply (PROX_GIVEN) and sums the family's
+// objective term into its slot (want_obj).  An empty pack is the kernel without a family, instruction for instruction.
+//
+// The loss family of the LAD and Huber engines (loss_device.h): g(z) = sum_i w_i*phi(z_i) with
 //   LAD:   phi(z) = a*max(z - eps, 0) + b*max(-z - eps, 0)        (quantile: a = tau, b = 1 - tau; SVR: eps > 0)
 //   Huber: phi(z) = (z >= 0 ? a : b)*H_delta(z)
-// A launcher that gets one runs the LOSS instantiation of its kernel: z is formed in a register ahead of prox_apply
-// (PROX_GIVEN) and S_OBJZ takes the whole of g(z) (the caller sets FinArgs::obj_scale_z = 1).  Null: today's kernels.
+// S_OBJZ takes the whole of g(z) (the caller sets FinArgs::obj_scale_z = 1).
 struct LossArgs {
   const double* w;   // [len] weights on the device, or null: every weight is 1
   double a, b;       // slopes of the positive and the negative side
@@ -217,32 +222,54 @@ struct LossArgs {
   double delta;      // Huber engine: the threshold
   double rho;
   int32_t huber;     // 0: the LAD engine's phi, 1: the Huber engine's
-  int32_t want_obj;  // sum g(z) into S_OBJZ (set by the launchers from ProxArgs::objz)
+  int32_t want_obj;  // sum g(z) into S_OBJZ (with_prox_family sets it from ProxArgs::objz)
 };
 // the checks admm_engine_set_loss and admm_op_loss_prox share (ops.hip); len HOST weights when d.weights is set
 int check_loss_desc(int32_t problem, const admm_loss_desc& d, int64_t len);
-// ---- the cost form of the linear SVM (svm_cost_device.h): g(z) = C*sum_i c_i*phi(ell_i*z_i) with
+// The cost form of the linear SVM (svm_cost_device.h): g(z) = C*sum_i c_i*phi(ell_i*z_i) with
 // c_i = w_i*(ell_i > 0 ? cost_pos : cost_neg) and phi the hinge, the squared hinge (this form only), the logistic or the
-// 0-1 loss.  A launcher that gets one runs the COST instantiation of its kernel, as for LossArgs: z is formed in a
-// register ahead of prox_apply (PROX_GIVEN) and the kernel sums c_i*phi(ell_i*(Dx)_i) into S_OBJX itself.  Null: today's
-// kernels.
+// 0-1 loss.  The kernel sums c_i*phi(ell_i*(Dx)_i) into S_OBJX itself; LOGI says whether it knows the logistic loss.
 struct SvmCostArgs {
   const double* w;            // [len] weights on the device, or null: every weight is 1
   double cost_pos, cost_neg;  // class costs of the rows with ell > 0 and of the others
   double C, rho;
   int32_t loss;               // ADMM_LOSS_*
-  int32_t want_obj;           // sum the objective into S_OBJX (set by the launchers from ProxArgs::objx)
+  int32_t want_obj;           // sum the objective into S_OBJX (with_prox_family sets it from ProxArgs::objx)
 };
 // the checks admm_engine_set_svm_cost, admm_svm_ovr_set_cost and admm_op_svm_prox share (ops.hip)
 int check_svm_cost(const double* weights, int64_t len, const double* costs, int64_t ncosts);
-// the operands of a COST instantiation out of the engine's: prox = PROX_GIVEN, objx = OBJX_NONE, ka = cost with want_obj
-ProxArgs svm_cost_operands(const ProxArgs& a, const SvmCostArgs& cost, SvmCostArgs* ka);
-void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss = nullptr,
-                 const SvmCostArgs* cost = nullptr);
+// The lasso's penalty family (penalty_device.h):
+//   g(z) = l1 * sum_i w_i*|z_i| + lamG * sum_g omega_g*||z_g|| + mu/2*||z||^2 + [z >= 0 when nonneg]
+// prox_{g/rho}(v): e_i = soft(v_i, tau*w_i) (max(v_i - tau*w_i, 0) with nonneg), with groups e_g *= scale_g from ||e_g||
+// and t_g = t*omega_g (group_chunk's rule on the squares of e), z = kappa*e.  S_OBJZ takes the whole of g(z) (the caller
+// sets FinArgs::obj_scale_z = 1).  Not a member of the pack: without groups it has the one-launch tail's kernel in a form
+// of its own (penalty_prox_fin_kernel, which launch_prox_fin picks), with groups group_prox_fin_kernel's PEN instantiation.
+struct PenaltyArgs {
+  const double* w;    // [n] l1 weights on the device, or null: every weight is 1
+  double tau;         // l1 / rho
+  double kappa;       // rho / (rho + mu); mu = 0 gives exactly 1
+  double l1;          // objective: the weight of sum_i w_i*|z_i| (0 drops the term)
+  double lam_group;   // objective: the weight of sum_g omega_g*||z_g|| (grouped form only)
+  double half_mu;     // objective: mu / 2
+  int32_t nonneg;
+};
+// the family in force on an engine, as every launcher of an element update takes it (null or FAM_NONE: no family)
+enum FamilyKind : int32_t { FAM_NONE = 0, FAM_LOSS = 1, FAM_COST = 2, FAM_PENALTY = 3 };
+struct ProxFamily {
+  int32_t kind;
+  LossArgs loss;
+  SvmCostArgs cost;
+  PenaltyArgs pen;
+};
+// the operands of a kernel that forms z in a register: pruned_prox_operands, prox = PROX_GIVEN without zgiven, and the
+// objective term the kernel sums itself taken out of a -- objx for the cost form, objz otherwise -- into *want_obj
+ProxArgs register_z_operands(const ProxArgs& a, bool cost, int32_t* want_obj);
+void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const ProxFamily* fam = nullptr);
 // A = I, alg 0 / 1: z/u update AND the finalize logic in one launch (the last workgroup to arrive finalizes);
-// a.len <= 128 * kMaxPartBlocks
+// a.len <= 128 * kMaxPartBlocks.  defer also serves the iterations that end in a stand-alone finalize (launch_prox's
+// place), which is where a penalised run uses it: the ungrouped penalty exists in this tail only.
 void launch_prox_fin(const ProxArgs& a, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                     bool defer = false, const LossArgs* loss = nullptr, const SvmCostArgs* cost = nullptr);
+                     bool defer = false, const ProxFamily* fam = nullptr);
 // out = prox_{g/rho}(v) of the loss family (device pointers): loss_device.h's function, one thread per element
 void launch_loss_prox(const double* v, int64_t n, const LossArgs& loss, double* out, hipStream_t stream);
 // out = the z-prox of the linear SVM's cost form (device pointers): svm_cost_device.h's function, one thread per element
@@ -279,34 +306,14 @@ int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int
 // The grouped element update: everything launch_prox_fin does (gather of the x-solve's partial rows, relaxation, z, u,
 // extrapolation, histories, next right-hand side, block partials, finalize in the launch or deferred) with the block
 // soft threshold as the z-prox and lambda * sum_g w_g*||z_g|| in S_OBJZ (when a.objz asks for the l1 term).  defer also
-// serves the iterations that end in a stand-alone finalize (launch_prox's place).  a.t = lambda / rho.
+// serves the iterations that end in a stand-alone finalize (launch_prox's place).  a.t = lambda / rho.  With the penalty
+// family: the elementwise stage before the squares go to LDS and kappa behind the scale; a.t is the groups' threshold.
 void launch_group_prox_fin(const ProxArgs& a, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
-                           hipStream_t stream, bool defer);
+                           hipStream_t stream, bool defer, const ProxFamily* fam = nullptr);
 // out = block soft threshold of v (device pointers), the same device code over the same plan
 void launch_group_soft_threshold(const double* v, const GroupPlan& gp, double t, double* out, hipStream_t stream);
-// ---- the lasso's penalty family (penalty_device.h):
-//   g(z) = l1 * sum_i w_i*|z_i| + lamG * sum_g omega_g*||z_g|| + mu/2*||z||^2 + [z >= 0 when nonneg]
-// prox_{g/rho}(v): e_i = soft(v_i, tau*w_i) (max(v_i - tau*w_i, 0) with nonneg), with groups e_g *= scale_g from ||e_g||
-// and t_g = t*omega_g (group_chunk's rule on the squares of e), z = kappa*e.
-struct PenaltyArgs {
-  const double* w;    // [n] l1 weights on the device, or null: every weight is 1
-  double tau;         // l1 / rho
-  double kappa;       // rho / (rho + mu); mu = 0 gives exactly 1
-  double l1;          // objective: the weight of sum_i w_i*|z_i| (0 drops the term)
-  double lam_group;   // objective: the weight of sum_g omega_g*||z_g|| (grouped form only)
-  double half_mu;     // objective: mu / 2
-  int32_t nonneg;
-};
-// The penalised element update without groups: launch_prox_fin's kernel with z = kappa*e_i formed in a register
-// (PROX_GIVEN) and the whole of g(z) in S_OBJZ (the caller sets FinArgs::obj_scale_z = 1).  defer also serves the
-// iterations that end in a stand-alone finalize (launch_prox's place).  a.len <= 128 * kMaxPartBlocks.
-void launch_penalty_prox_fin(const ProxArgs& a, const FinArgs& f, const PenaltyArgs& pen, Ctrl* ctrl, int* nblk_out,
-                             hipStream_t stream, bool defer);
-// ... and with groups: launch_group_prox_fin with the elementwise stage before the squares go to LDS and kappa behind the
-// scale.  a.t = lambda / rho is the groups' threshold.
-void launch_group_penalty_prox_fin(const ProxArgs& a, const FinArgs& f, const GroupPlan& gp, const PenaltyArgs& pen,
-                                   Ctrl* ctrl, int* nblk_out, hipStream_t stream, bool defer);
-// out = prox_{g/rho}(v) (device pointers): the same device functions; gp = null: no groups.  t = the groups' threshold
+// out = prox_{g/rho}(v) of the penalty family (device pointers): the same device functions; gp = null: no groups.
+// t = the groups' threshold
 void launch_penalty_prox(const double* v, int64_t n, const GroupPlan* gp, double t, const PenaltyArgs& pen, double* out,
                          hipStream_t stream);
 // the finalize arguments launch_prox_fin hands to the last workgroup (or, deferred, to the next launch)
@@ -364,7 +371,7 @@ bool uw_supported(int64_t m, int64_t n);
 FinArgs uw_fin_args(const UwArgs& a, const FinArgs& f);
 void launch_uw_ax(const UwArgs& a, const FinArgs& f, Ctrl* ctrl, hipStream_t stream);
 void launch_uw_prox(const UwArgs& a, const ProxArgs& pa, const Ctrl* ctrl, hipStream_t stream,
-                    const SvmCostArgs* cost = nullptr);
+                    const ProxFamily* fam = nullptr);  // the cost form or none
 
 // One pass over a tall, NARROW D per A = D iteration without a dual residual (unwrapped.hip: ad_onepass_kernel)
 struct OnePassArgs {
@@ -377,7 +384,7 @@ struct OnePassArgs {
 bool onepass_supported(int64_t m, int64_t n);
 int onepass_workgroups(int64_t m);
 void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pa, const Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                       const LossArgs* loss = nullptr, const SvmCostArgs* cost = nullptr);
+                       const ProxFamily* fam = nullptr);  // the loss family, the cost form or none
 
 // State of the caller's z when options.B is general (the loop's z buffers hold w = -B*z): after zming returned znew,
 // zprev <- z, z <- znew, zvals(:, i) = znew and -- fast ADMM -- v = z + coef*(z - zprev) (admm.m:568, 579) or the

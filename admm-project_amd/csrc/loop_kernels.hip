@@ -20,11 +20,11 @@
 
 namespace admm {
 
-// Loss = LossArgs: the instantiation of the loss family (loss_device.h): the weight travels with
-// prox_load's round trip and z reaches prox_apply in a register (PROX_GIVEN).  Loss = SvmCostArgs: the cost form of the
-// linear SVM (svm_cost_device.h) through the same statements, LOGI saying whether it knows the logistic
-// loss.  The pack is empty for every other instantiation: those keep their parameter list and their code, instruction
-// for instruction.
+// Loss: the element-update family the instantiation carries (loop_kernels.h: ProxFamily; with_prox_family picks it).
+// LossArgs: the loss family (loss_device.h): the weight travels with prox_load's round trip and z reaches
+// prox_apply in a register (PROX_GIVEN).  SvmCostArgs: the cost form of the linear SVM (svm_cost_device.h; DESIGN.md
+// q34) through the same statements, LOGI saying whether it knows the logistic loss.  The pack is empty for every other
+// instantiation: those keep their parameter list and their code, instruction for instruction.
 template <bool LOGI, class... Loss>
 __global__ __launch_bounds__(kBlock) void prox_kernel(ProxArgs a, const Ctrl* __restrict__ ctrl, Loss... la) {
   constexpr bool LOSS = sizeof...(Loss) != 0;
@@ -175,64 +175,38 @@ ProxArgs pruned_prox_operands(const ProxArgs& args) {
   return a;
 }
 
-// the operands of a LOSS instantiation: z reaches prox_apply in a register and the kernel sums g(z) itself (a LAD or
-// Huber engine: PROX_SOFT / PROX_HUBER, no ell, no bounds)
-static ProxArgs loss_prox_operands(const ProxArgs& args, const LossArgs& loss, LossArgs* la) {
+// The operands of every kernel that forms z in a register ahead of prox_apply -- a family's instantiation, the grouped
+// tail -- and sums the objective term that goes with it itself.  (The cost form belongs to a linear-SVM engine: its prox
+// is one of the SVM's, so ell stays.)
+ProxArgs register_z_operands(const ProxArgs& args, bool cost, int32_t* want_obj) {
   ProxArgs a = pruned_prox_operands(args);
   a.prox = PROX_GIVEN;
   a.zgiven = nullptr;
-  *la = loss;
-  la->want_obj = a.objz != OBJZ_NONE ? 1 : 0;
-  a.objz = OBJZ_NONE;
-  return a;
-}
-
-// the operands of a COST instantiation (a linear-SVM engine: the prox is one of the SVM's, so ell stays): z reaches
-// prox_apply in a register and the kernel sums the objective's element terms into S_OBJX itself
-ProxArgs svm_cost_operands(const ProxArgs& args, const SvmCostArgs& cost, SvmCostArgs* ka) {
-  ProxArgs a = pruned_prox_operands(args);
-  a.prox = PROX_GIVEN;
-  a.zgiven = nullptr;
-  *ka = cost;
-  ka->want_obj = a.objx != OBJX_NONE ? 1 : 0;
-  a.objx = OBJX_NONE;
-  return a;
-}
-
-void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const LossArgs* loss,
-                 const SvmCostArgs* cost) {
   if (cost) {
-    SvmCostArgs ka;
-    const ProxArgs ac = svm_cost_operands(args, *cost, &ka);
-    const int cblocks = grid_blocks(ac.len, kBlock, kMaxPartBlocks);
-    *nblk_out = cblocks;
-    if (ka.loss == ADMM_LOSS_LOGISTIC)
-      hipLaunchKernelGGL((prox_kernel<true, SvmCostArgs>), dim3(cblocks), dim3(kBlock), 0, stream, ac, ctrl, ka);
-    else hipLaunchKernelGGL((prox_kernel<false, SvmCostArgs>), dim3(cblocks), dim3(kBlock), 0, stream, ac, ctrl, ka);
-    return;
+    *want_obj = a.objx != OBJX_NONE ? 1 : 0;
+    a.objx = OBJX_NONE;
+  } else {
+    *want_obj = a.objz != OBJZ_NONE ? 1 : 0;
+    a.objz = OBJZ_NONE;
   }
-  if (loss) {
-    LossArgs la;
-    const ProxArgs al = loss_prox_operands(args, *loss, &la);
-    const int lblocks = grid_blocks(al.len, kBlock, kMaxPartBlocks);
-    *nblk_out = lblocks;
-    hipLaunchKernelGGL((prox_kernel<false, LossArgs>), dim3(lblocks), dim3(kBlock), 0, stream, al, ctrl, la);
-    return;
-  }
-  const ProxArgs a = pruned_prox_operands(args);
-  if (a.prox == PROX_PAIR) {  // one thread per pair; len is even (prox_pair_ok: the caller has checked)
-    ProxArgs ap = a;
+  return a;
+}
+
+void launch_prox(const ProxArgs& args, const Ctrl* ctrl, int* nblk_out, hipStream_t stream, const ProxFamily* fam) {
+  if (args.prox == PROX_PAIR) {  // one thread per pair; len is even (prox_pair_ok: the caller has checked); no family
+    ProxArgs ap = pruned_prox_operands(args);
     ap.prox = PROX_GIVEN;  // z reaches prox_apply in a register
-    const int pblocks = grid_blocks(a.len / 2, kBlock, kMaxPartBlocks);
+    const int pblocks = grid_blocks(ap.len / 2, kBlock, kMaxPartBlocks);
     *nblk_out = pblocks;
     hipLaunchKernelGGL(pair_prox_kernel, dim3(pblocks), dim3(kBlock), 0, stream, ap, ctrl);
     return;
   }
-  const int blocks = grid_blocks(a.len, kBlock, kMaxPartBlocks);
+  const int blocks = grid_blocks(args.len, kBlock, kMaxPartBlocks);
   *nblk_out = blocks;
-  if (prox_is_logistic(a))
-    hipLaunchKernelGGL(prox_kernel<true>, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
-  else hipLaunchKernelGGL(prox_kernel<false>, dim3(blocks), dim3(kBlock), 0, stream, a, ctrl);
+  with_prox_family<FAM_LOSS, FAM_COST>(args, fam, [&](auto logi, const ProxArgs& a, const auto&... fa) {
+    hipLaunchKernelGGL((prox_kernel<decltype(logi)::value, std::decay_t<decltype(fa)>...>), dim3(blocks), dim3(kBlock), 0,
+                       stream, a, ctrl, fa...);
+  });
 }
 
 // ---------------------------------------------------------------- alg 2: decide + extrapolate
@@ -499,40 +473,25 @@ FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
   return ff;
 }
 
+__global__ void penalty_prox_fin_kernel(ProxArgs a, FinArgs f, PenaltyArgs pen, Ctrl* __restrict__ ctrl, int32_t defer,
+                                        int32_t want_objz);  // (below, behind the grouped tail)
+
 void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                     bool defer, const LossArgs* loss, const SvmCostArgs* cost) {
-  if (cost) {
-    SvmCostArgs ka;
-    const ProxArgs ac = svm_cost_operands(args, *cost, &ka);
-    const int64_t cblocks = ceil_div(ac.len, kTailTile);
-    *nblk_out = static_cast<int>(cblocks);
-    if (ka.loss == ADMM_LOSS_LOGISTIC)
-      hipLaunchKernelGGL((prox_fin_kernel<true, SvmCostArgs>), dim3(static_cast<unsigned>(cblocks)), dim3(kTailBlock), 0, stream,
-                         ac, prox_fin_args(ac, f), ctrl, defer ? 1 : 0, ka);
-    else
-      hipLaunchKernelGGL((prox_fin_kernel<false, SvmCostArgs>), dim3(static_cast<unsigned>(cblocks)), dim3(kTailBlock), 0, stream,
-                         ac, prox_fin_args(ac, f), ctrl, defer ? 1 : 0, ka);
-    return;
-  }
-  if (loss) {
-    LossArgs la;
-    const ProxArgs al = loss_prox_operands(args, *loss, &la);
-    const int64_t lblocks = ceil_div(al.len, kTailTile);
-    *nblk_out = static_cast<int>(lblocks);
-    hipLaunchKernelGGL((prox_fin_kernel<false, LossArgs>), dim3(static_cast<unsigned>(lblocks)), dim3(kTailBlock), 0, stream, al,
-                       prox_fin_args(al, f), ctrl, defer ? 1 : 0, la);
-    return;
-  }
-  const ProxArgs a = pruned_prox_operands(args);
-  const int64_t blocks = ceil_div(a.len, kTailTile);
+                     bool defer, const ProxFamily* fam) {
+  const int64_t blocks = ceil_div(args.len, kTailTile);
   *nblk_out = static_cast<int>(blocks);
-  const FinArgs ff = prox_fin_args(a, f);
-  if (prox_is_logistic(a))
-    hipLaunchKernelGGL(prox_fin_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, ctrl,
-                       defer ? 1 : 0);
-  else
-    hipLaunchKernelGGL(prox_fin_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, ctrl,
-                       defer ? 1 : 0);
+  if (fam && fam->kind == FAM_PENALTY) {  // the ungrouped penalty: a kernel of its own, older than the pack
+    int32_t want_objz = 0;
+    const ProxArgs a = register_z_operands(args, false, &want_objz);
+    hipLaunchKernelGGL(penalty_prox_fin_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a,
+                       prox_fin_args(a, f), fam->pen, ctrl, defer ? 1 : 0, want_objz);
+    return;
+  }
+  with_prox_family<FAM_LOSS, FAM_COST>(args, fam, [&](auto logi, const ProxArgs& a, const auto&... fa) {
+    hipLaunchKernelGGL((prox_fin_kernel<decltype(logi)::value, std::decay_t<decltype(fa)>...>),
+                       dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, prox_fin_args(a, f), ctrl,
+                       defer ? 1 : 0, fa...);
+  });
 }
 
 // out = prox_{g/rho}(v) of the loss family: the stand-alone operator (ops.hip)
@@ -663,38 +622,28 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
   tail_publish_finalize(acc, a.part, f, ctrl, defer);  // (the two waves that hold elements also hold the group sums)
 }
 
-static void launch_group_tail(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, const PenaltyArgs* pen,
-                              Ctrl* ctrl, int* nblk_out, hipStream_t stream, bool defer) {
+void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
+                           hipStream_t stream, bool defer, const ProxFamily* fam) {
   // groups exist on ADMM_PROB_LASSO engines only (admm_engine_set_groups) and the grouped update is not used behind a
   // split z-update: args.prox is PROX_SOFT and objx is none or OBJX_SOLVE, so ell, the bounds and zgiven are nulled
-  ProxArgs a = pruned_prox_operands(args);
-  a.prox = PROX_GIVEN;  // z reaches prox_apply in a register
-  const int32_t want_objz = a.objz == OBJZ_ABS ? 1 : 0;  // the kernel adds the penalty once per group instead
-  a.objz = OBJZ_NONE;
+  int32_t want_objz = 0;  // the kernel adds the penalty once per group instead
+  const ProxArgs a = register_z_operands(args, false, &want_objz);
   *nblk_out = gp.nwg;
   FinArgs ff = prox_fin_args(a, f);
   ff.nblk = gp.nwg;
-  if (pen)
+  if (fam && fam->kind == FAM_PENALTY)
     hipLaunchKernelGGL(group_prox_fin_kernel<true>, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a, ff,
-                       gp, ctrl, defer ? 1 : 0, want_objz, *pen);
+                       gp, ctrl, defer ? 1 : 0, want_objz, fam->pen);
   else
     hipLaunchKernelGGL(group_prox_fin_kernel<false>, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a,
                        ff, gp, ctrl, defer ? 1 : 0, want_objz, PenaltyArgs{});
 }
 
-void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
-                           hipStream_t stream, bool defer) {
-  launch_group_tail(args, f, gp, nullptr, ctrl, nblk_out, stream, defer);
-}
-
-void launch_group_penalty_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, const PenaltyArgs& pen,
-                                   Ctrl* ctrl, int* nblk_out, hipStream_t stream, bool defer) {
-  launch_group_tail(args, f, gp, &pen, ctrl, nblk_out, stream, defer);
-}
-
 // ---------------------------------------------------------------- the penalty family without groups
 // prox_fin_kernel<false> with z = kappa * e_i (penalty_device.h) formed in a register and handed to prox_apply as
 // PROX_GIVEN; the weight is one more coalesced load of slot 0, in flight with the rest.  S_OBJZ takes the whole of g(z).
+// (As prox_fin_kernel's PenaltyArgs instantiation it has the same registers, LDS and occupancy but measured 0.05 us per
+// launch slower than this kernel, whose two runs differ by 0.02: EXPERIMENTS.md, "One dispatch of the families".)
 __global__ __launch_bounds__(kTailBlock) void penalty_prox_fin_kernel(ProxArgs a, FinArgs f, PenaltyArgs pen,
                                                                       Ctrl* __restrict__ ctrl, int32_t defer,
                                                                       int32_t want_objz) {
@@ -730,20 +679,6 @@ __global__ __launch_bounds__(kTailBlock) void penalty_prox_fin_kernel(ProxArgs a
     prox_apply<false>(a, i, ax, it, kcoef, in, acc);
   }
   tail_publish_finalize(acc, a.part, f, ctrl, defer);
-}
-
-void launch_penalty_prox_fin(const ProxArgs& args, const FinArgs& f, const PenaltyArgs& pen, Ctrl* ctrl, int* nblk_out,
-                             hipStream_t stream, bool defer) {
-  ProxArgs a = pruned_prox_operands(args);  // (a lasso engine, as launch_group_prox_fin: PROX_SOFT, no ell, no bounds)
-  a.prox = PROX_GIVEN;  // z reaches prox_apply in a register
-  a.zgiven = nullptr;
-  const int32_t want_objz = a.objz == OBJZ_ABS ? 1 : 0;  // the kernel sums g(z) itself
-  a.objz = OBJZ_NONE;
-  const int64_t blocks = ceil_div(a.len, kTailTile);
-  *nblk_out = static_cast<int>(blocks);
-  const FinArgs ff = prox_fin_args(a, f);
-  hipLaunchKernelGGL(penalty_prox_fin_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, ff, pen,
-                     ctrl, defer ? 1 : 0, want_objz);
 }
 
 // out = prox_{g/rho}(v) without groups: the stand-alone operator (ops.hip)
@@ -821,7 +756,7 @@ int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int
     return fail(ADMM_E_INVALID, "groups: the sizes sum to " + std::to_string(sum) + ", not to n = " + std::to_string(n));
   if (weights)
     for (int32_t g = 0; g < G; ++g)
-      if (!(weights[g] >= 0.0) || !(weights[g] <= 1.79769313486231570e308))
+      if (!finite_nonneg(weights[g]))
         return fail(ADMM_E_INVALID, "groups: weight " + std::to_string(g) + " is negative or not finite");
   // whole groups per workgroup, up to `budget` elements and kGroupMaxPerWg groups; a group past the budget stands alone
   std::vector<int64_t> wge;

@@ -1,6 +1,7 @@
 // loss_device.h -- the loss family of the robust-regression engines as inline device functions: shared by
-// the LOSS instantiations of the element updates (loop_kernels.hip: prox_kernel, prox_fin_kernel; unwrapped.hip:
-// ad_onepass_kernel) and the stand-alone operator (ops.hip).
+// the LossArgs instantiations of the element updates (loop_kernels.hip: prox_kernel, prox_fin_kernel; unwrapped.hip:
+// ad_onepass_kernel), which with_prox_family (prox_device.h) picks for a ProxFamily of kind FAM_LOSS, and the stand-alone
+// operator (ops.hip).
 //   g(z) = sum_i w_i*phi(z_i)
 //   LAD engine:   phi(z) = a*max(z - eps, 0) + b*max(-z - eps, 0)
 //   Huber engine: phi(z) = (z >= 0 ? a : b)*H_delta(z),  H_delta(z) = z^2/2 (|z| <= delta), delta*|z| - delta^2/2 beyond

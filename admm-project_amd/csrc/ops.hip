@@ -29,7 +29,20 @@ struct Scratch {  // frees everything on scope exit
     *out = static_cast<T*>(p);
     return ADMM_OK;
   }
+  template <typename T>
+  int put(T** dev, const T* host, size_t elems) {  // alloc + the host operand
+    ADMM_TRY(alloc(dev, elems));
+    ADMM_HIP_TRY(hipMemcpy(*dev, host, sizeof(T) * elems, hipMemcpyHostToDevice));
+    return ADMM_OK;
+  }
 };
+
+// the end of a vector operator: wait for its kernels, then the result back to the host
+int fetch(double* host, const double* dev, size_t elems) {
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  ADMM_HIP_TRY(hipMemcpy(host, dev, sizeof(double) * elems, hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
 
 int need_device() {
   int c = 0;
@@ -106,11 +119,10 @@ struct TableMem {  // owner of the device tables of dct_tables_create
   ~TableMem() { mem.release(); }
 };
 bool tv2d_height_ok(int64_t H) { return dct_length_ok(H) || dct_chirp_length_ok(H); }
-bool tv2d_rho_ok(double rho) { return rho > 0.0 && rho <= 1.79769313486231570e308; }  // finite, > 0, not NaN
 
 // the form an operator call runs: AUTO through the engine's rule, a forced one checked against its own precondition
 int tv2d_op_form(const char* op, int64_t H, int64_t W, double rho, int32_t form, Tv2Rows* rows) {
-  if (H <= 0 || W <= 0 || !tv2d_height_ok(H) || !tv2d_rho_ok(rho) || form < ADMM_TV2D_ROWS_AUTO ||
+  if (H <= 0 || W <= 0 || !tv2d_height_ok(H) || !finite_pos(rho) || form < ADMM_TV2D_ROWS_AUTO ||
       form > ADMM_TV2D_ROWS_THOMAS)
     return fail(ADMM_E_INVALID, std::string(op) + ": bad argument (H a column-transform length, W >= 1, rho finite and > 0, form 0..4)");
   *rows = form == ADMM_TV2D_ROWS_AUTO ? tv2d_row_stage(H, W, rho, dct_length_ok(W)) : static_cast<Tv2Rows>(form);
@@ -125,33 +137,31 @@ namespace admm {
 
 // the checks admm_engine_set_loss and admm_op_loss_prox share; len weights when desc->weights is set
 int check_loss_desc(int32_t problem, const admm_loss_desc& d, int64_t len) {
-  const auto fin = [](double v) { return v >= 0.0 && v <= 1.79769313486231570e308; };  // finite, >= 0, not NaN
   if (problem != ADMM_PROB_LAD && problem != ADMM_PROB_HUBERFIT)
     return fail(ADMM_E_INVALID, "the loss family belongs to ADMM_PROB_LAD and ADMM_PROB_HUBERFIT");
-  if (!(d.slope_pos > 0.0) || !fin(d.slope_pos) || !(d.slope_neg > 0.0) || !fin(d.slope_neg))
+  if (!finite_pos(d.slope_pos) || !finite_pos(d.slope_neg))
     return fail(ADMM_E_INVALID, "loss: both slopes must be finite and > 0");
-  if (!fin(d.epsilon)) return fail(ADMM_E_INVALID, "loss: epsilon must be finite and >= 0");
-  if (!(d.delta > 0.0) || !fin(d.delta)) return fail(ADMM_E_INVALID, "loss: delta must be finite and > 0");
+  if (!finite_nonneg(d.epsilon)) return fail(ADMM_E_INVALID, "loss: epsilon must be finite and >= 0");
+  if (!finite_pos(d.delta)) return fail(ADMM_E_INVALID, "loss: delta must be finite and > 0");
   if (problem == ADMM_PROB_HUBERFIT && d.epsilon != 0.0)
     return fail(ADMM_E_INVALID, "loss: epsilon belongs to the LAD engine (a Huber engine takes 0)");
   if (problem == ADMM_PROB_LAD && d.delta != 1.0)
     return fail(ADMM_E_INVALID, "loss: delta belongs to the Huber engine (a LAD engine takes 1)");
   if (d.weights)
     for (int64_t i = 0; i < len; ++i)
-      if (!fin(d.weights[i])) return fail(ADMM_E_INVALID, "loss: weight " + std::to_string(i) + " is negative or not finite");
+      if (!finite_nonneg(d.weights[i])) return fail(ADMM_E_INVALID, "loss: weight " + std::to_string(i) + " is negative or not finite");
   return ADMM_OK;
 }
 
 // the checks admm_engine_set_svm_cost, admm_svm_ovr_set_cost and admm_op_svm_prox share: len HOST weights (or null) and
 // ncosts HOST class costs (or null), every one finite and >= 0
 int check_svm_cost(const double* weights, int64_t len, const double* costs, int64_t ncosts) {
-  const auto fin = [](double v) { return v >= 0.0 && v <= 1.79769313486231570e308; };  // finite, >= 0, not NaN
   if (costs)
     for (int64_t i = 0; i < ncosts; ++i)
-      if (!fin(costs[i])) return fail(ADMM_E_INVALID, "svm cost: class cost " + std::to_string(i) + " is negative or not finite");
+      if (!finite_nonneg(costs[i])) return fail(ADMM_E_INVALID, "svm cost: class cost " + std::to_string(i) + " is negative or not finite");
   if (weights)
     for (int64_t i = 0; i < len; ++i)
-      if (!fin(weights[i])) return fail(ADMM_E_INVALID, "svm cost: weight " + std::to_string(i) + " is negative or not finite");
+      if (!finite_nonneg(weights[i])) return fail(ADMM_E_INVALID, "svm cost: weight " + std::to_string(i) + " is negative or not finite");
   return ADMM_OK;
 }
 
@@ -276,15 +286,12 @@ int admm_op_soft_threshold(const double* v, int64_t n, double t, double* out) {
   ADMM_TRY(need_device());
   Scratch sc;
   double *dv, *dout;
-  ADMM_TRY(sc.alloc(&dv, n));
+  ADMM_TRY(sc.put(&dv, v, n));
   ADMM_TRY(sc.alloc(&dout, n));
-  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
   const int blocks = grid_blocks(n, kBlock, 2048);
   hipLaunchKernelGGL(soft_threshold_kernel, dim3(blocks), dim3(kBlock), 0, nullptr, dv, n, t,
                      dout);
-  ADMM_HIP_TRY(hipDeviceSynchronize());
-  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
-  return ADMM_OK;
+  return fetch(out, dout, n);
 }
 
 int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* out) {
@@ -292,13 +299,10 @@ int admm_op_pair_soft_threshold(const double* v, int64_t N, double t, double* ou
   ADMM_TRY(need_device());
   Scratch sc;
   double *dv, *dout;
-  ADMM_TRY(sc.alloc(&dv, 2 * N));
+  ADMM_TRY(sc.put(&dv, v, 2 * N));
   ADMM_TRY(sc.alloc(&dout, 2 * N));
-  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * 2 * N, hipMemcpyHostToDevice));
   launch_tv2d_pair_soft_threshold(dv, N, t, dout, nullptr);
-  ADMM_HIP_TRY(hipDeviceSynchronize());
-  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * 2 * N, hipMemcpyDeviceToHost));
-  return ADMM_OK;
+  return fetch(out, dout, 2 * N);
 }
 
 int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups, const double* weights,
@@ -310,42 +314,33 @@ int admm_op_group_soft_threshold(const double* v, int64_t n, const int64_t* size
   ADMM_TRY(need_device());
   Scratch sc;
   double *dv, *dout, *dplan;
-  ADMM_TRY(sc.alloc(&dv, n));
+  ADMM_TRY(sc.put(&dv, v, n));
   ADMM_TRY(sc.alloc(&dout, n));
-  ADMM_TRY(sc.alloc(&dplan, h.blob.size()));
-  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
-  ADMM_HIP_TRY(hipMemcpy(dplan, h.blob.data(), sizeof(double) * h.blob.size(), hipMemcpyHostToDevice));
+  ADMM_TRY(sc.put<double>(&dplan, h.blob.data(), h.blob.size()));
   launch_group_soft_threshold(dv, h.bind(dplan), lambda_over_rho, dout, nullptr);
-  ADMM_HIP_TRY(hipDeviceSynchronize());
-  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
-  return ADMM_OK;
+  return fetch(out, dout, n);
 }
 
 int admm_op_penalty_prox(const double* v, int64_t n, const int64_t* sizes, int32_t ngroups, const double* groupweights,
                          double lambda_over_rho, const admm_penalty_desc* desc, double rho, double* out) {
-  const auto ok = [](double x) { return x >= 0.0 && x <= 1.79769313486231570e308; };
-  if (!v || !out || n <= 0 || !ok(lambda_over_rho) || !(rho > 0.0) || !ok(rho) || ngroups < 0)
+  if (!v || !out || n <= 0 || !finite_nonneg(lambda_over_rho) || !finite_pos(rho) || ngroups < 0)
     return fail(ADMM_E_INVALID, "penalty_prox: bad argument");
   const admm_penalty_desc none{nullptr, 0.0, 0.0, 0};
   const admm_penalty_desc& d = desc ? *desc : none;
-  if (!ok(d.l1) || !ok(d.ridge) || (d.nonnegative != 0 && d.nonnegative != 1))
+  if (!finite_nonneg(d.l1) || !finite_nonneg(d.ridge) || (d.nonnegative != 0 && d.nonnegative != 1))
     return fail(ADMM_E_INVALID, "penalty_prox: l1 and ridge must be finite and >= 0, nonnegative 0 or 1");
   if (d.l1weights)
     for (int64_t i = 0; i < n; ++i)
-      if (!ok(d.l1weights[i])) return fail(ADMM_E_INVALID, "penalty_prox: an l1 weight is negative or not finite");
+      if (!finite_nonneg(d.l1weights[i])) return fail(ADMM_E_INVALID, "penalty_prox: an l1 weight is negative or not finite");
   const bool groups = sizes && ngroups > 0;
   GroupPlanHost h;
   if (groups) ADMM_TRY(group_plan_build(sizes, ngroups, groupweights, n, &h));
   ADMM_TRY(need_device());
   Scratch sc;
   double *dv, *dout, *dplan = nullptr, *dw = nullptr;
-  ADMM_TRY(sc.alloc(&dv, n));
+  ADMM_TRY(sc.put(&dv, v, n));
   ADMM_TRY(sc.alloc(&dout, n));
-  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
-  if (d.l1weights) {
-    ADMM_TRY(sc.alloc(&dw, n));
-    ADMM_HIP_TRY(hipMemcpy(dw, d.l1weights, sizeof(double) * n, hipMemcpyHostToDevice));
-  }
+  if (d.l1weights) ADMM_TRY(sc.put(&dw, d.l1weights, n));
   PenaltyArgs pen{};  // (the objective's fields stay 0: the operator forms no objective)
   pen.w = dw;
   pen.tau = groups ? d.l1 / rho : lambda_over_rho;  // without groups lambda is the l1 weight itself
@@ -353,18 +348,15 @@ int admm_op_penalty_prox(const double* v, int64_t n, const int64_t* sizes, int32
   pen.nonneg = d.nonnegative;
   GroupPlan gp{};
   if (groups) {
-    ADMM_TRY(sc.alloc(&dplan, h.blob.size()));
-    ADMM_HIP_TRY(hipMemcpy(dplan, h.blob.data(), sizeof(double) * h.blob.size(), hipMemcpyHostToDevice));
+    ADMM_TRY(sc.put<double>(&dplan, h.blob.data(), h.blob.size()));
     gp = h.bind(dplan);
   }
   launch_penalty_prox(dv, n, groups ? &gp : nullptr, lambda_over_rho, pen, dout, nullptr);
-  ADMM_HIP_TRY(hipDeviceSynchronize());
-  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
-  return ADMM_OK;
+  return fetch(out, dout, n);
 }
 
 int admm_op_loss_prox(const double* v, int64_t len, int32_t problem, const admm_loss_desc* desc, double rho, double* out) {
-  if (!v || !out || len <= 0 || !(rho > 0.0) || !(rho <= 1.79769313486231570e308))
+  if (!v || !out || len <= 0 || !finite_pos(rho))
     return fail(ADMM_E_INVALID, "loss_prox: bad argument");
   const admm_loss_desc none{nullptr, 1.0, 1.0, 0.0, 1.0};
   const admm_loss_desc& d = desc ? *desc : none;
@@ -372,24 +364,17 @@ int admm_op_loss_prox(const double* v, int64_t len, int32_t problem, const admm_
   ADMM_TRY(need_device());
   Scratch sc;
   double *dv, *dout, *dw = nullptr;
-  ADMM_TRY(sc.alloc(&dv, len));
+  ADMM_TRY(sc.put(&dv, v, len));
   ADMM_TRY(sc.alloc(&dout, len));
-  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * len, hipMemcpyHostToDevice));
-  if (d.weights) {
-    ADMM_TRY(sc.alloc(&dw, len));
-    ADMM_HIP_TRY(hipMemcpy(dw, d.weights, sizeof(double) * len, hipMemcpyHostToDevice));
-  }
+  if (d.weights) ADMM_TRY(sc.put(&dw, d.weights, len));
   const LossArgs la{dw, d.slope_pos, d.slope_neg, d.epsilon, d.delta, rho, problem == ADMM_PROB_HUBERFIT ? 1 : 0, 0};
   launch_loss_prox(dv, len, la, dout, nullptr);
-  ADMM_HIP_TRY(hipDeviceSynchronize());
-  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * len, hipMemcpyDeviceToHost));
-  return ADMM_OK;
+  return fetch(out, dout, len);
 }
 
 int admm_op_svm_prox(const double* v, const double* ell, int64_t len, int32_t loss, double C, double rho,
                      const admm_svm_cost_desc* desc, double* out) {
-  if (!v || !ell || !out || len <= 0 || !(rho > 0.0) || !(rho <= 1.79769313486231570e308) || !(C >= 0.0) ||
-      !(C <= 1.79769313486231570e308))
+  if (!v || !ell || !out || len <= 0 || !finite_pos(rho) || !finite_nonneg(C))
     return fail(ADMM_E_INVALID, "svm_prox: bad argument");
   if (loss != ADMM_LOSS_HINGE && loss != ADMM_LOSS_01 && loss != ADMM_LOSS_HINGE_OBJ01 && loss != ADMM_LOSS_LOGISTIC &&
       loss != ADMM_LOSS_SQHINGE)
@@ -401,20 +386,13 @@ int admm_op_svm_prox(const double* v, const double* ell, int64_t len, int32_t lo
   ADMM_TRY(need_device());
   Scratch sc;
   double *dv, *dl, *dout, *dw = nullptr;
-  ADMM_TRY(sc.alloc(&dv, len));
-  ADMM_TRY(sc.alloc(&dl, len));
+  ADMM_TRY(sc.put(&dv, v, len));
+  ADMM_TRY(sc.put(&dl, ell, len));
   ADMM_TRY(sc.alloc(&dout, len));
-  ADMM_HIP_TRY(hipMemcpy(dv, v, sizeof(double) * len, hipMemcpyHostToDevice));
-  ADMM_HIP_TRY(hipMemcpy(dl, ell, sizeof(double) * len, hipMemcpyHostToDevice));
-  if (d.weights) {
-    ADMM_TRY(sc.alloc(&dw, len));
-    ADMM_HIP_TRY(hipMemcpy(dw, d.weights, sizeof(double) * len, hipMemcpyHostToDevice));
-  }
+  if (d.weights) ADMM_TRY(sc.put(&dw, d.weights, len));
   const SvmCostArgs ka{dw, d.cost_pos, d.cost_neg, C, rho, loss, 0};
   launch_svm_cost_prox(dv, dl, len, ka, dout, nullptr);
-  ADMM_HIP_TRY(hipDeviceSynchronize());
-  ADMM_HIP_TRY(hipMemcpy(out, dout, sizeof(double) * len, hipMemcpyDeviceToHost));
-  return ADMM_OK;
+  return fetch(out, dout, len);
 }
 
 int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32_t form, int64_t ncached,
@@ -626,12 +604,12 @@ int admm_op_llt_apply(const double* L, int64_t n, int64_t ldL, const double* x, 
 }
 
 int admm_tv2d_rows_green_taps(double rho) {
-  if (!tv2d_rho_ok(rho)) return fail(ADMM_E_INVALID, "tv2d_rows_green_taps: rho must be finite and > 0");
+  if (!finite_pos(rho)) return fail(ADMM_E_INVALID, "tv2d_rows_green_taps: rho must be finite and > 0");
   return tv2d_rows_green_taps(rho);
 }
 
 int admm_tv2d_row_stage(int64_t H, int64_t W, double rho) {
-  if (H <= 0 || W <= 0 || !tv2d_rho_ok(rho)) return fail(ADMM_E_INVALID, "tv2d_row_stage: bad argument");
+  if (H <= 0 || W <= 0 || !finite_pos(rho)) return fail(ADMM_E_INVALID, "tv2d_row_stage: bad argument");
   if (!tv2d_height_ok(H)) return ADMM_TV2D_ROWS_AUTO;  // no column transform: the x-update is CG, there is no row stage
   return static_cast<int>(tv2d_row_stage(H, W, rho, dct_length_ok(W)));
 }

@@ -1,6 +1,9 @@
 // prox_device.h -- the fused element update of one ADMM iteration (admm.m:515-569, 608-654) as inline device functions:
 // shared by the generic prox kernels (loop_kernels.hip) and the one-launch unwrapped iteration (unwrapped.hip).
 #pragma once
+#include <cassert>
+#include <type_traits>
+
 #include "loop_kernels.h"
 
 namespace admm {
@@ -43,6 +46,38 @@ __device__ __forceinline__ double logistic_root(double w, double t) {
 
 __host__ __device__ inline bool prox_is_logistic(const ProxArgs& a) {
   return a.prox == PROX_LOGISTIC || a.objx == OBJX_LOGISTIC;
+}
+
+// The one dispatch of the element-update families (loop_kernels.h: ProxFamily).  Prepares the operands of the kernel's
+// instantiation and calls launch(std::bool_constant<LOGI>, operands, family-args...) once: without a family the pruned
+// operands and no further argument; with one, register_z_operands and the family's block with want_obj set.  LOGI:
+// whether the instantiation knows the logistic loss.  CARRIES lists the families the launcher has kernels for (FAM_LOSS,
+// FAM_COST: the members of the pack): no other is instantiated, and being handed one is a programming error.
+template <int32_t... CARRIES, class Launch>
+void with_prox_family(const ProxArgs& args, const ProxFamily* fam, Launch launch) {
+  const int32_t kind = fam ? fam->kind : FAM_NONE;
+  if (kind == FAM_NONE) {
+    const ProxArgs a = pruned_prox_operands(args);
+    if (prox_is_logistic(a)) launch(std::true_type{}, a);
+    else launch(std::false_type{}, a);
+    return;
+  }
+  int32_t want_obj = 0;
+  const ProxArgs a = register_z_operands(args, kind == FAM_COST, &want_obj);
+  auto carry = [&](auto fa) {
+    fa.want_obj = want_obj;
+    if constexpr (std::is_same_v<decltype(fa), SvmCostArgs>) {
+      if (fa.loss == ADMM_LOSS_LOGISTIC) return launch(std::true_type{}, a, fa);
+    }
+    launch(std::false_type{}, a, fa);
+  };
+  if constexpr (((CARRIES == FAM_LOSS) || ...)) {
+    if (kind == FAM_LOSS) return carry(fam->loss);
+  }
+  if constexpr (((CARRIES == FAM_COST) || ...)) {
+    if (kind == FAM_COST) return carry(fam->cost);
+  }
+  assert(!"this launcher has no kernel for the family");
 }
 
 // the next x-update's right-hand side from (zx, ux): the one statement of RhsKind's formulas (RHS_NONE: the caller

@@ -1,6 +1,7 @@
 // svm_cost_device.h -- the cost form of the linear SVM's element update as inline device functions: shared
-// by the COST instantiations of the element updates (loop_kernels.hip: prox_kernel, prox_fin_kernel; unwrapped.hip:
-// uw_prox_kernel, ad_onepass_kernel; svm_ovr.hip: ovr_pass_kernel) and the stand-alone operator (ops.hip).
+// by the SvmCostArgs instantiations of the element updates (loop_kernels.hip: prox_kernel, prox_fin_kernel; unwrapped.hip:
+// uw_prox_kernel, ad_onepass_kernel), which with_prox_family (prox_device.h) picks for a ProxFamily of kind FAM_COST, by
+// svm_ovr.hip's ovr_pass_kernel and by the stand-alone operator (ops.hip).
 //   g(z) = C * sum_i c_i*phi(ell_i*z_i),   c_i = w_i*(ell_i > 0 ? cost_pos : cost_neg),   t_i = C*c_i/rho
 //   hinge     phi(s) = max(1 - s, 0)       z = v + ell*max(min(1 - s, t_i), 0)
 //   sqhinge   phi(s) = max(1 - s, 0)^2     z = s >= 1 ? v : ell*(s + 2 t_i)/(1 + 2 t_i)

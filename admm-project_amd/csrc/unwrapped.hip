@@ -246,26 +246,15 @@ void launch_uw_ax(const UwArgs& a, const FinArgs& f, Ctrl* ctrl, hipStream_t str
 }
 
 void launch_uw_prox(const UwArgs& args, const ProxArgs& pargs, const Ctrl* ctrl, hipStream_t stream,
-                    const SvmCostArgs* cost) {
+                    const ProxFamily* fam) {
   // GeneralLoop::plan takes this form only for ADMM_PROB_LINEARSVM without a z callback: the prox is the hinge, the 0-1 or
-  // the logistic one, never PROX_GIVEN / PROX_BOX, so zgiven and the bounds are nulled here as they always were
-  ProxArgs pa = pruned_prox_operands(pargs);
+  // the logistic one, never PROX_GIVEN / PROX_BOX, so zgiven and the bounds are nulled (with_prox_family) as they always were
+  ProxArgs pa = pargs;
   pa.rhs_add = nullptr;
-  if (cost) {
-    SvmCostArgs ka;
-    const ProxArgs pc = svm_cost_operands(pa, *cost, &ka);
-    if (ka.loss == ADMM_LOSS_LOGISTIC)
-      hipLaunchKernelGGL((uw_prox_kernel<true, SvmCostArgs>), dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0,
-                         stream, args, pc, ctrl, ka);
-    else
-      hipLaunchKernelGGL((uw_prox_kernel<false, SvmCostArgs>), dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0,
-                         stream, args, pc, ctrl, ka);
-  } else if (prox_is_logistic(pa))
-    hipLaunchKernelGGL(uw_prox_kernel<true>, dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args,
-                       pa, ctrl);
-  else
-    hipLaunchKernelGGL(uw_prox_kernel<false>, dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args,
-                       pa, ctrl);
+  with_prox_family<FAM_COST>(pa, fam, [&](auto logi, const ProxArgs& p, const auto&... fa) {
+    hipLaunchKernelGGL((uw_prox_kernel<decltype(logi)::value, std::decay_t<decltype(fa)>...>),
+                       dim3(static_cast<unsigned>(args.nblk)), dim3(kUwProxThreads), 0, stream, args, p, ctrl, fa...);
+  });
 }
 
 // ---------------------------------------------------------------- ONE pass over D per iteration (tall, narrow D)
@@ -382,36 +371,17 @@ int onepass_workgroups(int64_t m) {
 }
 
 void launch_ad_onepass(const OnePassArgs& a, const ProxArgs& pargs, const Ctrl* ctrl, int* nblk_out, hipStream_t stream,
-                       const LossArgs* loss, const SvmCostArgs* cost) {
-  ProxArgs pa = pruned_prox_operands(pargs);
+                       const ProxFamily* fam) {
+  ProxArgs pa = pargs;
   pa.rhs_add = nullptr;
   pa.rhs = nullptr;  // t = c + z - u never leaves the kernel
   pa.dz = nullptr;
   const int nwg = onepass_workgroups(a.m);
   *nblk_out = nwg;
-  if (cost) {  // the same for a linear-SVM engine with costs or the squared hinge
-    SvmCostArgs ka;
-    const ProxArgs pc = svm_cost_operands(pa, *cost, &ka);
-    if (ka.loss == ADMM_LOSS_LOGISTIC)
-      hipLaunchKernelGGL((ad_onepass_kernel<true, SvmCostArgs>), dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0,
-                         stream, a, pc, ctrl, ka);
-    else
-      hipLaunchKernelGGL((ad_onepass_kernel<false, SvmCostArgs>), dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0,
-                         stream, a, pc, ctrl, ka);
-  } else if (loss) {  // z reaches prox_apply in a register and the kernel sums g(z) itself (a LAD or Huber engine)
-    LossArgs la = *loss;
-    la.want_obj = pa.objz != OBJZ_NONE ? 1 : 0;
-    pa.prox = PROX_GIVEN;
-    pa.zgiven = nullptr;
-    pa.objz = OBJZ_NONE;
-    hipLaunchKernelGGL((ad_onepass_kernel<false, LossArgs>), dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream,
-                       a, pa, ctrl, la);
-  } else if (prox_is_logistic(pa))
-    hipLaunchKernelGGL(ad_onepass_kernel<true>, dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream, a, pa,
-                       ctrl);
-  else
-    hipLaunchKernelGGL(ad_onepass_kernel<false>, dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream, a, pa,
-                       ctrl);
+  with_prox_family<FAM_LOSS, FAM_COST>(pa, fam, [&](auto logi, const ProxArgs& p, const auto&... fa) {
+    hipLaunchKernelGGL((ad_onepass_kernel<decltype(logi)::value, std::decay_t<decltype(fa)>...>),
+                       dim3(static_cast<unsigned>(nwg)), dim3(kOpWaves * kWave), 0, stream, a, p, ctrl, fa...);
+  });
 }
 
 }  // namespace admm

@@ -14,6 +14,16 @@ def _f64(a, order="F"):
     return np.require(np.asarray(a, dtype=np.float64), dtype=np.float64, requirements=[order, "A"])
 
 
+def _weights(w, count, what, name="weights"):
+    """a setter's weight vector ``name`` as contiguous float64 (None stays None): ``count`` entries, one per ``what``"""
+    if w is None:
+        return None
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1))
+    if w.size != count:
+        raise ValueError(f"{name} has {w.size} entries for {count} {what}")
+    return w
+
+
 class Engine:
     """Device-resident problem (data + cached factor) and its iteration loop."""
 
@@ -425,9 +435,7 @@ class Engine:
         if l1weights is None and ridge == 0.0 and nonnegative == 0 and l1 == 0.0:
             L.check(self._lib.admm_engine_set_penalty(self._h, None))
             return
-        w = None if l1weights is None else np.ascontiguousarray(np.asarray(l1weights, dtype=np.float64).reshape(-1))
-        if w is not None and w.size != self.nB:
-            raise ValueError(f"l1weights has {w.size} entries for {self.nB} coefficients")
+        w = _weights(l1weights, self.nB, "coefficients", "l1weights")
         d = L.PenaltyDesc(None if w is None else L.as_dp(w), float(l1), float(ridge), int(nonnegative))
         L.check(self._lib.admm_engine_set_penalty(self._h, C.byref(d)))
 
@@ -446,9 +454,7 @@ class Engine:
         if weights is None and a == 1.0 and b == 1.0 and epsilon == 0.0 and delta == 1.0:
             L.check(self._lib.admm_engine_set_loss(self._h, None))
             return
-        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-        if w is not None and w.size != self.nB:
-            raise ValueError(f"weights has {w.size} entries for {self.nB} observations")
+        w = _weights(weights, self.nB, "observations")
         d = L.LossDesc(None if w is None else L.as_dp(w), a, b, float(epsilon), float(delta))
         L.check(self._lib.admm_engine_set_loss(self._h, C.byref(d)))
 
@@ -467,9 +473,7 @@ class Engine:
         if weights is None and cp == 1.0 and cn == 1.0:
             L.check(self._lib.admm_engine_set_svm_cost(self._h, None))
             return
-        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-        if w is not None and w.size != self.nB:
-            raise ValueError(f"weights has {w.size} entries for {self.nB} observations")
+        w = _weights(weights, self.nB, "observations")
         d = L.SvmCostDesc(None if w is None else L.as_dp(w), cp, cn)
         L.check(self._lib.admm_engine_set_svm_cost(self._h, C.byref(d)))
 
@@ -628,9 +632,7 @@ class SvmOvr:
     def set_cost(self, weights=None, classcost=None):
         """The costs of the K classes (admm_svm_ovr_set_cost): ``weights`` = m values >= 0 shared by all classes,
         ``classcost`` = a K x 2 array, row c = (cost_pos, cost_neg) of class c.  None: the defaults (1)."""
-        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-        if w is not None and w.size != self.m:
-            raise ValueError(f"weights has {w.size} entries for {self.m} observations")
+        w = _weights(weights, self.m, "observations")
         cc = None if classcost is None else np.ascontiguousarray(np.asarray(classcost, dtype=np.float64))
         if cc is not None and cc.shape != (self.K, 2):
             raise ValueError(f"classcost is not a {self.K} x 2 array (one (pos, neg) pair per class)")
