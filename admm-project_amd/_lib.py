@@ -116,6 +116,53 @@ class SvmCostDesc(C.Structure):  # admm_svm_cost_desc
     _fields_ = [("weights", C.POINTER(C.c_double)), ("cost_pos", C.c_double), ("cost_neg", C.c_double)]
 
 
+class SparseDesc(C.Structure):  # admm_sparse_desc: real double CSC
+    _fields_ = [("struct_size", C.c_int32), ("mem", C.c_int32), ("rows", C.c_int64), ("cols", C.c_int64),
+                ("nnz", C.c_int64), ("val", C.POINTER(C.c_double)), ("ir", C.POINTER(C.c_uint64)),
+                ("jc", C.POINTER(C.c_uint64))]
+
+
+def canonical_csc(D):
+    """any scipy.sparse matrix or array -> (rows, cols, val float64, ir uint64, jc uint64) in canonical CSC: duplicates
+    summed, row indices ascending inside a column -- what admm_engine_create_sparse accepts"""
+    import numpy as np
+    import scipy.sparse as sp
+
+    if not sp.issparse(D):
+        raise TypeError("not a scipy.sparse matrix")
+    A = sp.csc_matrix(D, dtype=np.float64, copy=True)  # (a copy: the caller's matrix is never reordered in place)
+    A.sum_duplicates()
+    A.sort_indices()
+    rows, cols = A.shape
+    return (int(rows), int(cols), np.ascontiguousarray(A.data, dtype=np.float64),
+            np.ascontiguousarray(A.indices, dtype=np.uint64), np.ascontiguousarray(A.indptr, dtype=np.uint64))
+
+
+def sparse_desc(D, keep):
+    """admm_sparse_desc of a scipy.sparse matrix over host arrays appended to ``keep``"""
+    rows, cols, val, ir, jc = canonical_csc(D)
+    keep.extend((val, ir, jc))
+    d = SparseDesc()
+    d.struct_size = C.sizeof(SparseDesc)
+    d.mem = MEM_HOST
+    d.rows, d.cols, d.nnz = rows, cols, int(val.size)
+    d.val = val.ctypes.data_as(C.POINTER(C.c_double))
+    d.ir = ir.ctypes.data_as(C.POINTER(C.c_uint64))
+    d.jc = jc.ctypes.data_as(C.POINTER(C.c_uint64))
+    return d
+
+
+def is_sparse(D):
+    """True for a scipy.sparse matrix or array (scipy is imported only when D is not a NumPy array)"""
+    if D is None or isinstance(D, (list, tuple)) or type(D).__module__.startswith("numpy"):
+        return False
+    try:
+        import scipy.sparse as sp
+    except ImportError:
+        return False
+    return sp.issparse(D)
+
+
 class EngineInfo(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("xsolve_requested", C.c_int32), ("xsolve_used", C.c_int32),
@@ -171,6 +218,7 @@ STORAGE_FP64, STORAGE_COMPACT = 0, 1
 F_WVALS = 23
 F_COVSEL_S = 24
 F_TV2D_ROW_STAGE = 25
+F_SPARSE_NNZ = 26
 TV2D_ROWS_AUTO, TV2D_ROWS_GREEN, TV2D_ROWS_COOP, TV2D_ROWS_DCT, TV2D_ROWS_THOMAS = range(5)
 TV2D_ROWS_NAMES = ("cg", "green", "coop", "dct", "thomas")  # results["tv2d_row_stage"] (0: no spectral x-update)
 
@@ -190,6 +238,7 @@ _SIGNATURES = {
     "admm_options_default": (None, [C.POINTER(Options)]),
     "admm_problem_desc_default": (None, [C.POINTER(ProblemDesc)]),
     "admm_engine_create": (C.c_int, [C.POINTER(ProblemDesc), C.POINTER(C.c_void_p)]),
+    "admm_engine_create_sparse": (C.c_int, [C.POINTER(ProblemDesc), C.POINTER(SparseDesc), C.POINTER(C.c_void_p)]),
     "admm_engine_set_callbacks": (C.c_int, [C.c_void_p, PROX_CALLBACK, C.c_void_p, PROX_CALLBACK, C.c_void_p,
                                             OBJ_CALLBACK, C.c_void_p]),
     "admm_engine_set_operators": (C.c_int, [C.c_void_p, OPERATOR_CALLBACK, C.c_void_p, OPERATOR_CALLBACK, C.c_void_p]),
@@ -222,6 +271,7 @@ _SIGNATURES = {
                                       C.POINTER(C.c_void_p)]),
     "admm_binding_destroy": (None, [C.c_void_p]),
     "admm_binding_desc": (C.POINTER(ProblemDesc), [C.c_void_p]),
+    "admm_binding_sparse": (C.POINTER(SparseDesc), [C.c_void_p]),
     "admm_binding_get_info": (C.c_int, [C.c_void_p, C.POINTER(BindingInfo)]),
     "admm_binding_apply": (C.c_int, [C.c_void_p, C.c_void_p]),
     "admm_binding_options": (C.c_int, [C.c_void_p, C.POINTER(Field), C.c_int32, C.POINTER(Field), C.c_int32,
@@ -232,6 +282,7 @@ _SIGNATURES = {
     "admm_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "admm_op_gemv_n": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int64, _dp, _dp]),
     "admm_op_gemv_t": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, C.c_int64]),
+    "admm_op_spmv": (C.c_int, [C.POINTER(SparseDesc), C.c_int, _dp, _dp]),
     "admm_op_gram": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int64, C.c_double, _dp]),
     "admm_op_cholesky": (C.c_int, [_dp, C.c_int64, C.c_int64]),
     "admm_op_trsv_pair": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp]),

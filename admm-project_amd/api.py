@@ -746,6 +746,11 @@ def admm(xminf, zming, options):
             print(f"admm: {int(cg[1])} of {steps} x-updates ended on the CG iteration cap above cg_tol; raise cg_maxit")
     except L.AdmmError:
         pass
+    if getattr(eng, "sparse", False):  # a sparse design matrix (engine extension): always matrix-free
+        info = eng.sparse_info()
+        results["xsolve"] = "cg"
+        results["nnz"] = info["nnz"]
+        results["spmv_lanes"] = info["lanes"]
     if prob.kind == "totalvariation2d":  # which row stage the spectral x-update took ("cg": none), engine extension
         results["tv2d_row_stage"] = L.TV2D_ROWS_NAMES[int(eng.fetch(L.F_TV2D_ROW_STAGE, 1)[0])]
     if prob.kind == "lasso-consensus":

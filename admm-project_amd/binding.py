@@ -46,6 +46,7 @@ class Fields:
             elif isinstance(value, Sparse):
                 f.kind = L.FIELD_SPARSE
                 f.rows, f.cols = value.shape
+                f.reserved = int(value.data.size)  # the stored count travels with the field (admm_engine.h)
                 f.data = value.data.ctypes.data_as(C.POINTER(C.c_double))
                 f.ir = value.ir.ctypes.data_as(C.POINTER(C.c_uint64))
                 f.jc = value.jc.ctypes.data_as(C.POINTER(C.c_uint64))
@@ -81,6 +82,11 @@ class Binding:
     @property
     def desc(self):
         return self._lib.admm_binding_desc(self._h).contents
+
+    def sparse(self):
+        """the sparse matrix a 'lasso' binding describes (admm_binding_sparse) as dict(rows, cols, nnz), or None"""
+        p = self._lib.admm_binding_sparse(self._h)
+        return dict(rows=p.contents.rows, cols=p.contents.cols, nnz=p.contents.nnz) if p else None
 
     def info(self):
         i = L.BindingInfo()

@@ -52,6 +52,12 @@ const mxArray* field(const mxArray* s, const char* name) {
 bool is_dense_double(const mxArray* f) { return f && mxIsDouble(f) && !mxIsSparse(f) && !mxIsComplex(f); }
 bool is_handle(const mxArray* f) { return f && mxIsClass(f, "function_handle"); }
 
+// the engine a binding describes: the sparse create when args.D arrived sparse (a 'lasso' binding says so)
+int create_from_binding(const admm_binding* b, admm_engine** e) {
+  const admm_sparse_desc* sp = admm_binding_sparse(b);
+  return sp ? admm_engine_create_sparse(admm_binding_desc(b), sp, e) : admm_engine_create(admm_binding_desc(b), e);
+}
+
 void check(int rc) {
   if (rc != ADMM_OK) mexErrMsgIdAndTxt("admm:engine", "%s", admm_last_error());
 }
@@ -411,7 +417,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       registered = true;
     }
     admm_engine* e = nullptr;
-    check(admm_engine_create(admm_binding_desc(ds.b), &e));  // (a failed create leaves nothing behind)
+    check(create_from_binding(ds.b, &e));  // (a failed create leaves nothing behind)
     g_live.push_back(e);  // (only an allocation failure inside MATLAB's own mx* calls can still leave it to mexAtExit)
     RunError err;
     mxArray* res = nullptr;
@@ -430,7 +436,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     Desc* ds = new Desc();
     describe(to_string(prhs[1]), prhs[2], nrhs > 3 ? prhs[3] : nullptr, *ds);
     admm_engine* e = nullptr;
-    int rc = admm_engine_create(admm_binding_desc(ds->b), &e);
+    int rc = create_from_binding(ds->b, &e);
     if (rc == ADMM_OK && (rc = admm_binding_apply(ds->b, e)) != ADMM_OK) admm_engine_destroy(e);
     if (rc != ADMM_OK) {
       delete ds;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "spmv.h"
 
 using namespace admm;
 
@@ -32,6 +33,8 @@ struct admm_binding {
   bool has_svm_cost = false;        // one of the two was given (admm_engine_set_svm_cost)
   int32_t tv2d_isotropic = 0;     // args.isotropic of totalvariation2d (admm_engine_set_tv2d_isotropic)
   std::vector<double> zeros;      // c = 0 for the engines that take c as a data vector
+  admm_sparse_desc sparse{};      // a sparse args.D of 'lasso' (admm_engine_create_sparse); borrows the field's arrays
+  bool has_sparse = false;
   int64_t nA = 0, nB = 0;         // lengths of x and of z
   int64_t mC = 0;                 // length of u and c; 0 = the same as nB (every problem but a generic one with a general B)
   bool a_handle = false;          // generic: options.A / options.At are function handles
@@ -110,14 +113,45 @@ int describe(const std::string& p, const View& args, const View& handles, admm_b
   else if (args.text_is("xsolve", "cg")) d.xsolve = ADMM_XSOLVE_CG;
   else if (args.text_is("xsolve", "pinv")) d.xsolve = ADMM_XSOLVE_PINV;
   const char* needD = "args.D must be a full real matrix";
+  const bool sparseD = D && D->kind == ADMM_FIELD_SPARSE;
+  if (sparseD && (p == "lad" || p == "huberfit" || p == "linearsvm"))
+    return fail(ADMM_E_UNSUPPORTED, "a sparse args.D is supported for 'lasso' only, not for '" + p + "'");
 
   if (p == "lasso") {
-    if (!haveD) return fail(ADMM_E_INVALID, needD);
+    if (sparseD) {  // the sparse engine: checked here, on the host, as admm_engine_create_sparse checks it
+      if (!D->jc || D->rows < 1 || D->cols < 1) return fail(ADMM_E_INVALID, "args.D: a sparse matrix needs jc and a shape");
+      admm_sparse_desc& sp = b.sparse;
+      sp.struct_size = static_cast<int32_t>(sizeof(admm_sparse_desc));
+      sp.mem = ADMM_MEM_HOST;
+      sp.rows = D->rows;
+      sp.cols = D->cols;
+      sp.val = D->data;
+      sp.ir = D->ir;
+      sp.jc = D->jc;
+      // the stored count: the field's own (`reserved`) when it carries one, else the last column start
+      sp.nnz = D->reserved > 0 ? D->reserved : (D->cols < (int64_t{1} << 31) ? static_cast<int64_t>(D->jc[D->cols]) : -1);
+      ADMM_TRY(sparse_csc_check(&sp));
+      b.has_sparse = true;
+      d.m = sp.rows;
+      d.n = sp.cols;
+    } else if (!haveD) {
+      return fail(ADMM_E_INVALID, needD);
+    }
     d.lambda = args.scalar("lambda", 0.0);
     b.nA = b.nB = d.n;
     d.s = args.vec("s");
     // the serial args struct has no s (getProxOps.m:445-451): the objective's s travels in handles.s
     if (!d.s) d.s = handles.vec("s");
+    if (b.has_sparse) {  // element counts against the matrix, and what a sparse engine refuses
+      size_t ks = 0, kd = 0;
+      if ((args.vec("s", &ks) || handles.vec("s", &ks)) && ks != static_cast<size_t>(d.m))
+        return fail(ADMM_E_INVALID, "s must have one entry per row of the sparse args.D");
+      if (args.vec("Dts", &kd) && kd != static_cast<size_t>(d.n))
+        return fail(ADMM_E_INVALID, "args.Dts must have one entry per column of the sparse args.D");
+      if (args.scalar("parallel", 0) != 0)
+        return fail(ADMM_E_UNSUPPORTED, "a sparse args.D with args.parallel = 1: consensus lasso needs a full matrix");
+      if (args.get("L")) return fail(ADMM_E_UNSUPPORTED, "args.L with a sparse args.D: the x-update is matrix-free");
+    }
     // group lasso (engine-side extension): args.groups = the sizes of the contiguous groups, args.groupweights optional.
     // Everything that can be checked without a device is checked here, element counts included.
     if (args.get("groups")) {
@@ -447,6 +481,7 @@ int admm_binding_create(const char* problem, const admm_field* args, int32_t nar
 void admm_binding_destroy(admm_binding* b) { delete b; }
 
 const admm_problem_desc* admm_binding_desc(const admm_binding* b) { return b ? &b->d : nullptr; }
+const admm_sparse_desc* admm_binding_sparse(const admm_binding* b) { return (b && b->has_sparse) ? &b->sparse : nullptr; }
 
 int admm_binding_get_info(const admm_binding* b, admm_binding_info* info) {
   if (!b || !info) return fail(ADMM_E_INVALID, "NULL argument");

@@ -892,6 +892,16 @@ int admm_engine_fetch(admm_engine* e, int field, double* dst, size_t cap, size_t
       if (written) *written = cap >= 2 ? 2 : 1;
       return ADMM_OK;
     }
+    case ADMM_F_SPARSE_NNZ:
+      if (!e->sparse) return fail(ADMM_E_INVALID, "field exists only for an engine created from a sparse matrix");
+      if (cap < 1) return fail(ADMM_E_CAPACITY, "destination too small");
+      dst[0] = static_cast<double>(e->sp.nnz);
+      if (cap >= 3) {
+        dst[1] = static_cast<double>(e->sp.n.plan.lanes);
+        dst[2] = static_cast<double>(e->sp.t.plan.lanes);
+      }
+      if (written) *written = cap >= 3 ? 3 : 1;
+      return ADMM_OK;
     case ADMM_F_TV2D_ROW_STAGE:
       if (e->problem != ADMM_PROB_TV2D) return fail(ADMM_E_INVALID, "field exists only for 2-D total variation");
       if (cap < 1) return fail(ADMM_E_CAPACITY, "destination too small");
@@ -1065,6 +1075,7 @@ void admm_engine_destroy(admm_engine* e) {
   for (auto& t : e->timers)
     for (hipEvent_t ev : t.ev) (void)hipEventDestroy(ev);
   e->mem.release();
+  sparse_device_free(&e->sp);
   if (e->ctrl_host) (void)hipHostFree(e->ctrl_host);
   if (e->cg_st_host) (void)hipHostFree(e->cg_st_host);
   if (e->stream) (void)hipStreamDestroy(e->stream);

@@ -13,6 +13,7 @@ struct CreateCtx {  // what create's option checks compute and the setup functio
   bool sharded;       // a communicator with more than one rank
   int64_t m_global;   // rows of D over all ranks (the local m when not sharded)
   bool tv2_want_dct;  // 2-D TV: build the tables of the spectral x-update
+  const admm_sparse_desc* sparse;  // admm_engine_create_sparse: the checked matrix in HOST arrays, else null
 };
 
 struct SideStream {  // a second stream and the event that orders it behind the engine's, released on every path
@@ -147,6 +148,35 @@ static int setup_lasso(admm_engine* e, const admm_problem_desc* desc, const Crea
     ADMM_TRY(e->mem.alloc(&e->tmpA, round_up(m, 2)));
     ADMM_TRY(e->mem.alloc(&e->tmpB, round_up(m, 2)));
   }
+  return ADMM_OK;
+}
+
+// The lasso on a sparse design matrix: both orientations of D on the device, D'*s by the sparse
+// product, the matrix-free x-update.  e->D stays null: cg_apply and the literal objective run launch_spmv, and every
+// other reader of D belongs to a factor path or to an A = D problem.
+static int setup_lasso_sparse(admm_engine* e, const admm_problem_desc* desc, const CreateCtx& cx) {
+  const int64_t m = desc->m, n = desc->n;
+  if (!desc->s && !desc->Dts) return fail(ADMM_E_INVALID, "lasso needs s (or D'*s)");
+  if (desc->lambda < 0) return fail(ADMM_E_INVALID, "lambda must be a nonnegative real (lasso.m:132)");
+  e->a_identity = true;
+  e->nA = n;
+  e->len = n;
+  e->prox = PROX_SOFT;
+  e->rhs_kind = RHS_RHO_DTS;
+  e->fat = false;  // (D'D + rho I) is positive definite for every shape: one x-update form
+  e->sparse = true;
+  ADMM_TRY(sparse_device_build(cx.sparse, &e->sp, e->stream));
+  if (desc->s) ADMM_TRY(upload(e->mem, &e->s, desc->s, m, cx.mk, e->stream));
+  ADMM_TRY(e->mem.alloc(&e->rhs_add, round_up(n, 2)));
+  ADMM_HIP_TRY(hipMemsetAsync(e->rhs_add, 0, sizeof(double) * round_up(n, 2), e->stream));
+  if (desc->Dts)
+    ADMM_HIP_TRY(hipMemcpyAsync(e->rhs_add, desc->Dts, sizeof(double) * n,
+                                cx.mk == ADMM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+  else
+    launch_spmv(e->sp.t, e->s, e->rhs_add, nullptr, e->stream);  // Dts = D'*s   lasso.m:160
+  e->cg_shift_is_rho = true;
+  ADMM_TRY(e->mem.alloc(&e->tmpA, round_up(m, 2)));
+  ADMM_HIP_TRY(hipMemsetAsync(e->tmpA, 0, sizeof(double) * round_up(m, 2), e->stream));
   return ADMM_OK;
 }
 
@@ -738,7 +768,7 @@ static int check_options(admm_engine* e, const admm_problem_desc* desc, CreateCt
 
 static int setup_problem(admm_engine* e, const admm_problem_desc* desc, const CreateCtx& cx) {
   switch (desc->problem) {
-    case ADMM_PROB_LASSO: return setup_lasso(e, desc, cx);
+    case ADMM_PROB_LASSO: return cx.sparse ? setup_lasso_sparse(e, desc, cx) : setup_lasso(e, desc, cx);
     case ADMM_PROB_LAD:
     case ADMM_PROB_HUBERFIT:
     case ADMM_PROB_LINEARSVM: return setup_lad_huber_svm(e, desc, cx);
@@ -792,20 +822,12 @@ static int setup_common(admm_engine* e) {
   return ADMM_OK;
 }
 
-extern "C" int admm_engine_create(const admm_problem_desc* desc, admm_engine** out) {
-  if (!desc || !out) return fail(ADMM_E_INVALID, "desc/out is NULL");
-  if (desc->struct_size != static_cast<int32_t>(sizeof(admm_problem_desc)))
-    return fail(ADMM_E_INVALID, "admm_problem_desc.struct_size mismatch (ABI version skew)");
-  *out = nullptr;
+// sparse: null, or the checked matrix of admm_engine_create_sparse in HOST arrays
+static int create_engine(const admm_problem_desc* desc, const admm_sparse_desc* sparse, admm_engine** out) {
   const auto t0 = std::chrono::steady_clock::now();
-  int ndev = 0;
-  ADMM_TRY(admm_device_count(&ndev));
-  if (ndev <= 0) return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
-  if (desc->device < 0 || desc->device >= ndev) return fail(ADMM_E_INVALID, "bad device ordinal");
-  ADMM_HIP_TRY(hipSetDevice(desc->device));
-
   admm_engine* e = new admm_engine();
   CreateCtx cx{};
+  cx.sparse = sparse;
   int rc = check_options(e, desc, &cx);
   if (rc == ADMM_OK) rc = setup_problem(e, desc, cx);
   if (rc == ADMM_OK) rc = setup_common(e);
@@ -816,4 +838,54 @@ extern "C" int admm_engine_create(const admm_problem_desc* desc, admm_engine** o
   e->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   *out = e;
   return ADMM_OK;
+}
+
+// the checks both create entries make before an engine object exists; selects the device
+static int check_device(const admm_problem_desc* desc, admm_engine** out) {
+  if (!desc || !out) return fail(ADMM_E_INVALID, "desc/out is NULL");
+  if (desc->struct_size != static_cast<int32_t>(sizeof(admm_problem_desc)))
+    return fail(ADMM_E_INVALID, "admm_problem_desc.struct_size mismatch (ABI version skew)");
+  *out = nullptr;
+  int ndev = 0;
+  ADMM_TRY(admm_device_count(&ndev));
+  if (ndev <= 0) return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
+  if (desc->device < 0 || desc->device >= ndev) return fail(ADMM_E_INVALID, "bad device ordinal");
+  ADMM_HIP_TRY(hipSetDevice(desc->device));
+  return ADMM_OK;
+}
+
+extern "C" int admm_engine_create(const admm_problem_desc* desc, admm_engine** out) {
+  ADMM_TRY(check_device(desc, out));
+  return create_engine(desc, nullptr, out);
+}
+
+extern "C" int admm_engine_create_sparse(const admm_problem_desc* desc, const admm_sparse_desc* D, admm_engine** out) {
+  if (!desc || !out) return fail(ADMM_E_INVALID, "desc/out is NULL");
+  *out = nullptr;
+  if (!D) return fail(ADMM_E_INVALID, "the sparse matrix is NULL");
+  if (desc->struct_size != static_cast<int32_t>(sizeof(admm_problem_desc)))
+    return fail(ADMM_E_INVALID, "admm_problem_desc.struct_size mismatch (ABI version skew)");
+  // what a sparse engine does not do, before anything touches the device
+  if (desc->problem != ADMM_PROB_LASSO)
+    return fail(ADMM_E_UNSUPPORTED, "a sparse design matrix is supported for the lasso only (ADMM_PROB_LASSO)");
+  if (desc->D) return fail(ADMM_E_INVALID, "admm_engine_create_sparse: desc.D must be NULL (the matrix is the sparse one)");
+  if (desc->m != D->rows || desc->n != D->cols)
+    return fail(ADMM_E_INVALID, "admm_engine_create_sparse: desc.m / desc.n differ from the rows / cols of the matrix");
+  if (desc->xsolve != ADMM_XSOLVE_AUTO && desc->xsolve != ADMM_XSOLVE_CG)
+    return fail(ADMM_E_UNSUPPORTED, "a sparse engine runs the matrix-free x-update only (xsolve = auto or cg): nothing "
+                                    "n x n is ever formed");
+  if (desc->L) return fail(ADMM_E_UNSUPPORTED, "args.L with a sparse design matrix: no factor is used");
+  if (desc->nslices > 1) return fail(ADMM_E_UNSUPPORTED, "consensus lasso on a sparse design matrix");
+  if (desc->comm) return fail(ADMM_E_UNSUPPORTED, "a sparse design matrix on a row-sharded engine");
+  if (D->mem != ADMM_MEM_HOST && D->mem != ADMM_MEM_DEVICE) return fail(ADMM_E_INVALID, "bad admm_sparse_desc.mem");
+  if (D->mem == ADMM_MEM_HOST) ADMM_TRY(sparse_csc_check(D));  // (before the device is even looked for)
+  ADMM_TRY(check_device(desc, out));
+  admm_sparse_desc host;
+  std::vector<double> val;
+  std::vector<uint64_t> ir, jc;
+  ADMM_TRY(sparse_to_host(D, &host, &val, &ir, &jc));
+  if (D->mem == ADMM_MEM_DEVICE) ADMM_TRY(sparse_csc_check(&host));
+  admm_problem_desc d = *desc;
+  d.xsolve = ADMM_XSOLVE_CG;
+  return create_engine(&d, &host, out);
 }

@@ -17,6 +17,7 @@
 #include "consensus.h"
 #include "cg.h"
 #include "covsel.h"
+#include "spmv.h"
 
 namespace admm {
 
@@ -159,6 +160,10 @@ struct admm_engine {
   int cg_chunk = 8;         // inner iterations enqueued between polls: follows the last solve's count
   CgState* cg_st_host = nullptr;  // pinned
   int64_t cg_total_last = 0, cg_capped_last = 0;
+  // lasso on a sparse design matrix (admm_engine_create_sparse): both orientations of D and their plans;
+  // D stays null, the CG operator and the literal objective run launch_spmv
+  bool sparse = false;
+  SparseDev sp{};
   // consensus lasso (getProxOps.m:383-442, 1217-1343)
   std::vector<ConsSlice> cslices;
   int32_t cons_total = 0;  // slicenum over all ranks

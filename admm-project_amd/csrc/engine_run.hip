@@ -18,6 +18,20 @@ static int cg_apply(admm_engine* e, const double* v, const double** qin, int32_t
     return ADMM_OK;
   }
   const Ctrl* sk = e->cg_skip;  // no-ops once this solve has converged (or the run has stopped)
+  if (e->sparse) {  // D'(D v) as two sparse products, each row summed in its fixed order (spmv.hip)
+    {
+      TimerScope ts(e, ADMM_K_GEMV_N);
+      launch_spmv(e->sp.n, v, e->tmpA, sk, e->stream);
+    }
+    {
+      TimerScope ts(e, ADMM_K_GEMV_T);
+      launch_spmv(e->sp.t, e->tmpA, e->cg_tmp, sk, e->stream);
+    }
+    *qin = e->cg_tmp;
+    *nchunk = 1;
+    *ldq = 0;
+    return ADMM_OK;
+  }
   {
     TimerScope ts(e, ADMM_K_GEMV_N);
     launch_gemv_n(e->planDN, e->D, v, e->partDN, sk, e->stream);

@@ -639,8 +639,13 @@ struct GeneralLoop {
     } else if (obj.obj_lasso_gemv) {  // 0.5*||D*x - s||^2  (lasso.m:227)
       TimerScope ts(e, ADMM_K_GEMV_N);
       int nob = 0;
-      launch_gemv_n(e->planDN, e->D, e->x, e->partDN, e->ctrl, e->stream);
-      launch_residual_sq(e->partDN, e->planDN.nchunk, e->planDN.ldy, e->s, e->m, e->objpart, &nob, e->ctrl, e->stream);
+      if (e->sparse) {  // D*x by the sparse product into the length-m scratch of the CG operator: one finished chunk
+        launch_spmv(e->sp.n, e->x, e->tmpA, e->ctrl, e->stream);
+        launch_residual_sq(e->tmpA, 1, 0, e->s, e->m, e->objpart, &nob, e->ctrl, e->stream);
+      } else {
+        launch_gemv_n(e->planDN, e->D, e->x, e->partDN, e->ctrl, e->stream);
+        launch_residual_sq(e->partDN, e->planDN.nchunk, e->planDN.ldy, e->s, e->m, e->objpart, &nob, e->ctrl, e->stream);
+      }
       fa.obj_scale_part = 0.5;
       fa.obj_const = 0.0;
       fa.objpart = e->objpart;

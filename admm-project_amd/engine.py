@@ -44,7 +44,11 @@ class Engine:
             keep.append(a)
             return L.as_dp(a)
 
-        if D is not None:
+        sparse = None
+        if L.is_sparse(D):  # a scipy.sparse design matrix (lasso only: admm_engine_create_sparse)
+            sparse = L.sparse_desc(D, keep)
+            d.m, d.n = sparse.rows, sparse.cols
+        elif D is not None:
             Dm = _f64(D)
             if Dm.ndim != 2:
                 raise ValueError("D must be a matrix")
@@ -100,7 +104,7 @@ class Engine:
             d.ub = vec(ub)
         if Dplus is not None:  # args.Dplus = pinv(D) handed in by the caller (linearsvm.m:185-186)
             Dp = _f64(Dplus)
-            if D is None or Dp.shape != (d.n, d.m):
+            if D is None or sparse is not None or Dp.shape != (d.n, d.m):
                 raise ValueError("Dplus must be n x m for D m x n")
             keep.append(Dp)
             d.Dplus = L.as_dp(Dp)
@@ -134,11 +138,17 @@ class Engine:
         self._comm = comm
         self._lib = lib
         if _defer is not None:  # Engine.create_all: the native call creates every rank's engine at once
+            if sparse is not None:
+                raise L.AdmmError(L.E_UNSUPPORTED, "a sparse design matrix on a row-sharded engine")
             _defer.append((self, d, keep))
             return
         h = C.c_void_p()
-        L.check(lib.admm_engine_create(C.byref(d), C.byref(h)))
+        if sparse is not None:
+            L.check(lib.admm_engine_create_sparse(C.byref(d), C.byref(sparse), C.byref(h)))
+        else:
+            L.check(lib.admm_engine_create(C.byref(d), C.byref(h)))
         self._attach(h, d)
+        self.sparse = sparse is not None
         del keep
 
     def _attach(self, h, d):
@@ -527,6 +537,13 @@ class Engine:
                     probe_err_inverse=i.probe_err_inverse, probe_err_trsv=i.probe_err_trsv, probe_err_trsv_one=i.probe_err_trsv_one, probe_diff=i.probe_diff,
                     xsolve_cacheable_bytes=i.xsolve_cacheable_bytes, xsolve_stream_bytes=i.xsolve_stream_bytes,
                     obj_bound_max=i.obj_bound_max, obj_form_literal=bool(i.obj_form_literal), ngroups=i.ngroups)
+
+    def sparse_info(self):
+        """an engine on a sparse design matrix: dict(nnz, lanes = (lanes per row of D*v, of D'*v)); None otherwise"""
+        if not getattr(self, "sparse", False):
+            return None
+        v = self.fetch(L.F_SPARSE_NNZ, 3)
+        return dict(nnz=int(v[0]), lanes=(int(v[1]), int(v[2])))
 
     def set_profiling(self, on, stride=1):
         """True/False, or an iterable of kernel classes (L.K_XSOLVE, ...) to time with HIP events; stride > 1 times

@@ -21,7 +21,13 @@ __all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg"
 _ENGINE_OBJ = "<engine-native objective>"
 
 
-def _matrix(D, name):
+def _matrix(D, name, sparse_ok=False):
+    if sparse_ok:  # lasso, grouplasso, elasticnet: a scipy.sparse design matrix goes to the engine as it is
+        from ._lib import is_sparse
+        if is_sparse(D):
+            if len(D.shape) != 2:
+                raise ValueError(f"Argument {name} is not a matrix!")
+            return D
     D = np.asarray(D, dtype=np.float64)
     if D.ndim != 2:
         raise ValueError(f"Argument {name} is not a matrix!")
@@ -51,6 +57,12 @@ def lasso(D, s, lam, options=None):
     minimise 1/2*||D*x - s||_2^2 + lambda*||x||_1.  Setup on the device: Dts = D'*s,
     L = chol(D'*D + rho*I) (tall) or chol(D*D'/rho + I) (fat) (lasso.m:160-176).
 
+    ``D`` may be any ``scipy.sparse`` matrix or array (engine-side extension): it is converted to
+    canonical CSC and stays sparse on the device; the x-update is then the matrix-free CG of ``xsolve = 'cg'`` with two
+    sparse products per inner iteration (tall or fat D), ``results['xsolve']`` reads 'cg' and ``results['nnz']`` is the
+    stored count.  ``xsolve = 'trsv' | 'inverse'``, ``args.L``, ``options['parallel']`` and ``options['comm']`` are
+    refused by the engine.
+
     Engine-side extension: ``options['l1weights']`` (n values w_i >= 0: lambda*sum_i w_i*|x_i|),
     ``options['ridge']`` (mu >= 0: + mu/2*||x||^2, the elastic net) and ``options['nonnegative']`` (1: x >= 0) change
     the z-update alone; the serial solver only.
@@ -60,7 +72,7 @@ def lasso(D, s, lam, options=None):
     options = dict(options)
     t0 = time.perf_counter()
     lam = is_nonnegative_real(lam, "lambda")
-    D = _matrix(D, "D")
+    D = _matrix(D, "D", sparse_ok=True)
     s = _colvec(s, "s")
     rho = is_positive_real(options["rho"], "options.rho") if "rho" in options else 1.0
     m, n = D.shape
@@ -108,7 +120,7 @@ def grouplasso(D, s, lam, groups, options=None):
     options = dict(options)
     t0 = time.perf_counter()
     lam = is_nonnegative_real(lam, "lambda")
-    D = _matrix(D, "D")
+    D = _matrix(D, "D", sparse_ok=True)
     s = _colvec(s, "s")
     rho = is_positive_real(options["rho"], "options.rho") if "rho" in options else 1.0
     m, n = D.shape

@@ -117,6 +117,40 @@ def lasso_problem(seed=0, rows=2 ** 8, cols=2 ** 6, threads=None, row_range=None
     return dict(D=D, s=s, lam=lam, testx=testx)
 
 
+def sparse_lasso_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05):
+    """lasso_problem's recipe on a sparse design matrix: every entry is stored with probability ``density`` (a Bernoulli
+    pattern, drawn as geometric gaps along the column-major index), the stored values are randn and every non-empty
+    column is scaled to unit norm -- lasso_problem's normalisation, which keeps the largest eigenvalue of D'D small.
+    testx, s and lam as there.  D is returned as ``scipy.sparse.csc_matrix`` in canonical form."""
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(seed)
+    testx = np.where(rng.random(cols) < 0.6, rng.standard_normal(cols), 0.0)
+    prng = np.random.default_rng(seed + 7919)
+    total = rows * cols
+    flat = np.zeros(0, dtype=np.int64)
+    if density >= 1.0:
+        flat = np.arange(total, dtype=np.int64)
+    elif density > 0.0:
+        pos, parts = -1, []
+        while pos < total:  # gaps between stored entries of a Bernoulli(density) sequence are geometric
+            gaps = prng.geometric(density, size=int(total * density * 1.05) + 64)
+            idx = pos + np.cumsum(gaps, dtype=np.int64)
+            parts.append(idx)
+            pos = int(idx[-1])
+        flat = np.concatenate(parts)
+        flat = flat[flat < total]
+    col = flat // rows
+    val = prng.standard_normal(flat.size)
+    nrm = np.sqrt(np.bincount(col, weights=val * val, minlength=cols))
+    val /= np.where(nrm > 0.0, nrm, 1.0)[col]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(col, minlength=cols))]).astype(np.int64)
+    D = sp.csc_matrix((val, (flat % rows).astype(np.int64), indptr), shape=(rows, cols))
+    s = D @ testx + np.sqrt(0.001) * rng.standard_normal(rows)
+    lam = 0.1 * float(np.max(np.abs(D.T @ s)))
+    return dict(D=D, s=s, lam=lam, testx=testx)
+
+
 def grouplasso_problem(seed=0, rows=2 ** 8, cols=2 ** 6, ngroups=8, active=2):
     """lassotest's recipe with a group-sparse truth: ``ngroups`` contiguous groups of random sizes >= 1, ``active`` of them
     filled with randn and every other one exactly zero; s = D*testx + sqrt(0.001)*randn; unit weights;

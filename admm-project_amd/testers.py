@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
+__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -49,6 +49,22 @@ def grouplassotest(seed=0, rows=2 ** 8, cols=2 ** 6, errtol=1e-3, quiet=1, optio
     testobj, objopt = obj(testx, testx), obj(xopt, xopt)
     test = dict(D=D, s=s, testx=testx, groups=sizes, testobj=testobj, xopt=xopt, admmopt=results["objopt"], objopt=objopt,
                 failed=int(not objopt < testobj), objerror=abs((testobj - objopt) / objopt), steps=results["steps"])
+    test["lambda"] = lam
+    return results, test
+
+
+def sparselassotest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, errtol=1e-3, quiet=1, options=None):
+    """lassotest's shape for lasso on a sparse design matrix (synth.sparse_lasso_problem, D a scipy.sparse matrix that
+    stays sparse on the device): pass when obj(xopt) < obj(testx)."""
+    p = synth.sparse_lasso_problem(seed, rows, cols, density)
+    D, s, lam, testx = p["D"], p["s"], p["lam"], p["testx"]
+    obj = lambda x, z: 0.5 * np.sum((D @ x - s) ** 2) + lam * np.sum(np.abs(z))
+    results = solvers.lasso(D, s, lam, _opts(options, objevals=1, quiet=quiet))
+    xopt = results["xopt"]
+    testobj, objopt = obj(testx, testx), obj(xopt, xopt)
+    test = dict(D=D, s=s, testx=testx, testobj=testobj, xopt=xopt, admmopt=results["objopt"], objopt=objopt,
+                failed=int(not objopt < testobj), objerror=abs((testobj - objopt) / objopt), steps=results["steps"],
+                nnz=results["nnz"])
     test["lambda"] = lam
     return results, test
 

@@ -273,8 +273,11 @@ enum {
                            * (admm.m:678-681); needs the vector histories */
   ADMM_F_COVSEL_S = 24,   /* covariance selection: the n x n S the engine runs with (cov(D) when created from samples);
                            * available before the first run */
-  ADMM_F_TV2D_ROW_STAGE = 25 /* 2-D total variation: one value, the ADMM_TV2D_ROWS_* form the row stage of the last run's
+  ADMM_F_TV2D_ROW_STAGE = 25,/* 2-D total variation: one value, the ADMM_TV2D_ROWS_* form the row stage of the last run's
                            * spectral x-update took (the three-launch iteration included); 0 when the x-update was CG */
+  ADMM_F_SPARSE_NNZ = 26  /* an engine of admm_engine_create_sparse: [0] the stored nonzeros of D, [1] / [2] (capacity >= 3)
+                           * the lanes per row of the D*v and of the D'*v product (csrc/spmv.h); available before the
+                           * first run.  ADMM_E_INVALID on a dense engine */
 };
 
 /* ---- library ---------------------------------------------------------------- */
@@ -293,6 +296,30 @@ int admm_device_info(int device, char* name, size_t cap, int64_t* hbm_bytes, int
 void admm_options_default(admm_options* opts);
 void admm_problem_desc_default(admm_problem_desc* desc);
 int admm_engine_create(const admm_problem_desc* desc, admm_engine** out);
+/* A lasso engine on a SPARSE design matrix (engine-side extension: DESIGN.md q35).  D arrives as real double CSC,
+ * MATLAB's own storage; its arrays are copied at create whichever memory they live in.  The device keeps D by rows and
+ * D' by rows (12 B per nonzero each: int64 row starts, int32 indices, fp64 values); the x-update is the warm-started CG
+ * of ADMM_XSOLVE_CG on (D'D + rho I) with two sparse matrix-vector products per inner iteration (csrc/spmv.hip: no
+ * atomics, one fixed summation order per row), and the objective's 1/2*||D*x - s||^2 is evaluated literally with the
+ * same product.  Nothing n x n is formed, so tall and fat matrices are both accepted.  The z-side -- admm_engine_set_groups,
+ * admm_engine_set_penalty -- every option and every history are those of a dense xsolve = cg lasso engine.
+ *   desc: problem = ADMM_PROB_LASSO, D = NULL, m = D->rows, n = D->cols, s (or Dts) per desc->mem, lambda, rho, cg_tol,
+ *         cg_maxit, device; xsolve ADMM_XSOLVE_AUTO and ADMM_XSOLVE_CG both mean CG; obj_gram is ignored
+ * ADMM_E_INVALID (nothing is uploaded, no engine is created; the message names the first offending column): desc->D
+ * given, m / n that differ from rows / cols, rows, cols or nnz not below 2^31, jc[0] != 0, a decreasing jc,
+ * jc[cols] != nnz, a row index >= rows, row indices not strictly increasing inside a column (unsorted or duplicate
+ * entries), a value that is not finite.
+ * ADMM_E_UNSUPPORTED: xsolve TRSV / INVERSE / PINV (callback as well), desc->L, nslices > 1, desc->comm, any problem other
+ * than the lasso (LAD, Huber and the SVM on sparse data are out of scope). */
+typedef struct admm_sparse_desc {
+  int32_t struct_size;  /* sizeof(admm_sparse_desc) */
+  int32_t mem;          /* ADMM_MEM_HOST or ADMM_MEM_DEVICE: where val / ir / jc live */
+  int64_t rows, cols, nnz;
+  const double* val;    /* nnz values */
+  const uint64_t* ir;   /* their row indices */
+  const uint64_t* jc;   /* column starts, cols + 1 entries */
+} admm_sparse_desc;
+int admm_engine_create_sparse(const admm_problem_desc* desc, const admm_sparse_desc* D, admm_engine** out);
 /* replace the x- and/or z-update (and the objective hook) of an A = 1 problem (tall lasso, QP, LP, basis
  * pursuit, model) or an A = D problem (LAD, Huber, linear SVM: the zming handle of
  * unwrappedadmm(zming, D, options), unwrappedadmm.m:1) by caller-supplied callbacks; NULL keeps the
@@ -510,7 +537,8 @@ void admm_engine_destroy(admm_engine* eng);
 enum { ADMM_FIELD_NUMERIC = 0,  /* full real double array: data, rows, cols (column-major) */
        ADMM_FIELD_TEXT = 1,     /* character vector: text */
        ADMM_FIELD_HANDLE = 2,   /* a function handle (its presence is what counts; the gateway keeps the callable) */
-       ADMM_FIELD_SPARSE = 3,   /* real double CSC matrix: data = nonzeros, ir = their rows, jc = column starts (cols + 1) */
+       ADMM_FIELD_SPARSE = 3,   /* real double CSC matrix: data = nonzeros, ir = their rows, jc = column starts (cols + 1);
+                                   `reserved`, when not 0, is the number of stored values (else jc[cols] is) */
        ADMM_FIELD_OTHER = 4 };
 typedef struct admm_field {
   const char* name;
@@ -543,6 +571,12 @@ typedef struct admm_binding_info {
   int64_t b_ld;
 } admm_binding_info;
 int admm_binding_get_info(const admm_binding* b, admm_binding_info* info);
+/* a 'lasso' binding whose args.D is ADMM_FIELD_SPARSE describes the sparse engine: the matrix, checked as
+ * admm_engine_create_sparse checks it (ADMM_E_INVALID, on the host), or NULL for every other binding.  A gateway that
+ * gets a matrix here calls admm_engine_create_sparse(admm_binding_desc(b), admm_binding_sparse(b), &engine).  s / Dts of
+ * the wrong length are ADMM_E_INVALID; a sparse args.D for any other problem, with args.parallel = 1 or with args.L is
+ * ADMM_E_UNSUPPORTED */
+const admm_sparse_desc* admm_binding_sparse(const admm_binding* b);
 /* a 'lasso' binding also takes the penalty family of admm_engine_set_penalty from its args: `l1weights` (one finite
  * value >= 0 per column of D), `ridge`, `l1` (finite, >= 0) and `nonnegative` (0 or 1), checked by admm_binding_create
  * (ADMM_E_INVALID), refused with parallel = 1 (ADMM_E_UNSUPPORTED) and handed to the engine by admm_binding_apply */
@@ -592,6 +626,10 @@ int admm_op_gemv_n(const double* D, int64_t m, int64_t n, int64_t ldD, const dou
 /* G(:,k) = D'*V(:,k), k < nrhs <= 4  (admm.m:119/167 `At*v`; getProxOps.m:1514) */
 int admm_op_gemv_t(const double* D, int64_t m, int64_t n, int64_t ldD, const double* V, int64_t ldV,
                    int32_t nrhs, double* G, int64_t ldG);
+/* y = D*x (transpose = 0: x has cols, y rows elements) or y = D'*x (x rows, y cols) for a sparse D in host CSC arrays,
+ * by the kernel and the plans of the sparse lasso engine (admm_engine_create_sparse, whose checks of D apply): every
+ * row's products are added in one fixed order, so a second call returns the same bits; an empty row gives 0.0 */
+int admm_op_spmv(const admm_sparse_desc* D, int transpose, const double* x, double* y);
 /* W = D'*D (+ shift on the diagonal), n x n  (lasso.m:168, lad.m:134, unwrappedadmm.m:115) */
 int admm_op_gram(const double* D, int64_t m, int64_t n, int64_t ldD, double shift, double* W);
 /* in place lower Cholesky of the n x n SPD matrix A (chol(.,'lower'), lasso.m:168) */
