@@ -8,8 +8,9 @@ from . import _lib, errorcheck, synth  # noqa: F401
 from ._lib import AdmmError  # noqa: F401
 from .api import ProxOp, admm, getproxops  # noqa: F401
 from .engine import Engine, SvmOvr  # noqa: F401
+from .reg_multi import RegMulti  # noqa: F401
 from . import testers  # noqa: F401,E402
 from .solvers import (basispursuit, covarianceselection, elasticnet, grouplasso, huberfit, lad, lasso, linearprogram, linearsvm, linearsvm_ovr, model,  # noqa: F401
-                      quantilereg, quadraticprogram, totalvariation, totalvariation2d, unwrappedadmm)
+                      quantilereg, quantilereg_multi, quadraticprogram, robustfit_multi, totalvariation, totalvariation2d, unwrappedadmm)
 
 __version__ = "0.1.0"

@@ -212,6 +212,29 @@ class SvmOvrSummary(C.Structure):  # admm_svm_ovr_summary
 OVR_F_XOPT, OVR_F_ZOPT, OVR_F_UOPT, OVR_F_PNORM, OVR_F_PERR, OVR_F_HNORMSQ, OVR_F_OBJEVALS = range(1, 8)
 SVM_OVR_MAX_N = 448
 
+
+class RegMultiDesc(C.Structure):  # admm_reg_multi_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("m", C.c_int64), ("n", C.c_int64), ("D", _dp),
+                ("ldD", C.c_int64), ("S", _dp), ("ns", C.c_int32), ("mem", C.c_int32), ("device", C.c_int32),
+                ("reserved0", C.c_int32), ("kind", C.POINTER(C.c_int32)), ("a", _dp), ("b", _dp), ("epsilon", _dp),
+                ("delta", _dp), ("comm", C.c_void_p)]
+
+
+class RegMultiOptions(C.Structure):  # admm_reg_multi_options
+    _fields_ = [("struct_size", C.c_int32), ("maxiters", C.c_int32), ("rho", C.c_double), ("abstol", C.c_double),
+                ("reltol", C.c_double), ("relax", C.c_double), ("fast", C.c_int32), ("convtest", C.c_int32),
+                ("domaxiters", C.c_int32), ("objevals", C.c_int32), ("check_every", C.c_int32),
+                ("reserved0", C.c_int32), ("x0", _dp), ("z0", _dp), ("u0", _dp)]
+
+
+class RegMultiSummary(C.Structure):  # admm_reg_multi_summary
+    _fields_ = [("steps", C.c_int32), ("stopped_early", C.c_int32), ("objopt", C.c_double)]
+
+
+REGM_F_XOPT, REGM_F_ZOPT, REGM_F_UOPT, REGM_F_PNORM, REGM_F_PERR, REGM_F_OBJEVALS = range(1, 7)
+REG_MULTI_MAX_N = 448
+REGM_KIND_LAD, REGM_KIND_HUBER = 0, 1
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
@@ -323,6 +346,16 @@ _SIGNATURES = {
     "admm_svm_ovr_set_cost": (C.c_int, [C.c_void_p, _dp, _dp]),
     "admm_svm_ovr_chunk": (C.c_int, []),
     "admm_svm_ovr_destroy": (None, [C.c_void_p]),
+    "admm_reg_multi_desc_default": (None, [C.POINTER(RegMultiDesc)]),
+    "admm_reg_multi_options_default": (None, [C.POINTER(RegMultiOptions)]),
+    "admm_reg_multi_create": (C.c_int, [C.POINTER(RegMultiDesc), C.POINTER(C.c_void_p)]),
+    "admm_reg_multi_run": (C.c_int, [C.c_void_p, C.POINTER(RegMultiOptions), C.POINTER(RegMultiSummary),
+                                     C.POINTER(C.c_double)]),
+    "admm_reg_multi_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_reg_multi_set_weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_reg_multi_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "admm_reg_multi_chunk": (C.c_int, []),
+    "admm_reg_multi_destroy": (None, [C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

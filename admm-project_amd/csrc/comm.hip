@@ -451,12 +451,18 @@ int comm_allreduce_device(admm_comm* c, double* buf, size_t count, hipStream_t s
 // (which queue a new stream gets depends on every stream the process made before: two ranks that landed on one queue
 // trip the polling limit), so such ranks take different priorities -- a different pool each.  With more sharers than
 // priority levels (three here) the pools are shared again.  One rank per device: a plain stream.
+// The levels are dealt from both ends -- greatest, least, then inwards -- so the default priority comes last: its pool is
+// the one every other stream of the process lives in, the null stream included, and a peer's synchronous copy on the
+// null stream that lands on a waiting rank's queue blocks that peer's thread until the polling limit trips.  Two ranks
+// never touch that pool.
 int comm_stream_create(const admm_comm* comm, hipStream_t* out) {
   if (comm && comm->transport == ADMM_COMM_P2P && comm->queue_sharers > 1) {
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least > greatest) {
       const int levels = least - greatest + 1;
-      if (hipStreamCreateWithPriority(out, hipStreamNonBlocking, greatest + comm->queue_slot % levels) == hipSuccess)
+      const int k = comm->queue_slot % levels;
+      const int prio = (k & 1) ? least - k / 2 : greatest + k / 2;  // 0, 1, 2, 3 ... -> greatest, least, greatest + 1, least - 1 ...
+      if (hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio) == hipSuccess)
         return ADMM_OK;
     }
     (void)hipGetLastError();

@@ -15,7 +15,7 @@ import numpy as np
 from .api import admm, getproxops
 from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -206,6 +206,170 @@ def quantilereg(D, s, tau, options=None):
     if options.get("tau") is not None or options.get("slopes") is not None:
         raise ValueError("quantilereg sets the slopes itself: options.tau / options.slopes")
     return lad(D, s, dict(options, tau=float(tau)))
+
+
+_MULTI_HIST = ("pnorm", "perr", "objevals")
+_MULTI_FIT_KEYS = ("kind", "tau", "slopes", "epsilon", "delta")
+
+
+def _multi_fits(fits, m):
+    """``fits`` of robustfit_multi as a list of (kind, a, b, epsilon, delta): a list of dicts, or one dict of columns
+    (lists of one length; a scalar or string stands for every fit).  Checked per fit by errorcheck.loss_fields; the
+    messages name the fit.  Raises before any device work."""
+    if isinstance(fits, dict):
+        cols = {k: v for k, v in fits.items() if v is not None}
+        sizes = {k: len(v) for k, v in cols.items() if isinstance(v, (list, np.ndarray)) or
+                 (isinstance(v, tuple) and k != "slopes")}
+        if len(set(sizes.values())) > 1:
+            raise ValueError("fits: the columns have mixed lengths (" +
+                             ", ".join(f"{k}: {n}" for k, n in sorted(sizes.items())) + ")")
+        K = next(iter(sizes.values()), 1)
+        fits = [{k: (v[i] if k in sizes else v) for k, v in cols.items()} for i in range(K)]
+    if not isinstance(fits, (list, tuple)) or len(fits) < 1 or not all(isinstance(f, dict) for f in fits):
+        raise ValueError("fits is neither a non-empty list of dicts nor a dict of columns!")
+    out = []
+    for k, f in enumerate(fits):
+        unknown = sorted(set(f) - set(_MULTI_FIT_KEYS))
+        if unknown:
+            raise ValueError(f"fit {k}: unknown field {unknown[0]!r} (options['weights'] is shared by all fits)")
+        kind = f.get("kind", "lad")
+        if kind not in ("lad", "huber", "huberfit"):
+            raise ValueError(f"fit {k}: kind is neither 'lad' nor 'huber'")
+        kind = "lad" if kind == "lad" else "huberfit"
+        try:
+            lf = loss_fields({key: f.get(key) for key in LOSS_KEYS if key != "weights"}, m, kind) or {}
+        except ValueError as e:
+            raise ValueError(f"fit {k}: {e}") from None
+        a, b = lf.get("slopes", (1.0, 1.0))
+        out.append((kind, a, b, lf.get("epsilon", 0.0), lf.get("delta", 1.0)))
+    return out
+
+
+def robustfit_multi(D, S, fits, options=None):
+    """results = robustfit_multi(D, S, fits, options): K fits of the loss family of lad() / huberfit()
+    over ONE design matrix in one run: one read of D per iteration for a chunk of fits.
+
+    ``S``: the response, a vector or m x 1 (shared by all fits) or m x K (one column per fit).  ``fits``: a list of K
+    dicts with the keys ``kind`` ('lad' | 'huber'), ``tau`` or ``slopes``, ``epsilon`` (lad), ``delta`` (huber) -- or one
+    dict of such columns.  ``options['weights']`` (m values >= 0) is shared by all fits.  The options of the plain loop
+    apply to every fit (rho, abstol, reltol, maxiters, domaxiters, objevals, check_every; x0 / z0 / u0 as n x K, m x K,
+    m x K, default zeros); relax, fast and convtest are refused.  Every fit stops on pnorm < perr: the dual residual is
+    not evaluated, so fit k equals ``lad(D, s_k, {..., 'nodualerror': 1})`` / ``huberfit(...)``, not the default call.
+    Returns xopt (n x K), zopt, uopt (m x K), steps (K), objopt (K), pnorm / perr / objevals (max(steps) x K, NaN past a
+    fit's last step), runtime, solverruntime, chunk (fits per pass over D) and fallback.  For n > 448 the fits run one
+    after the other through lad / huberfit with nodualerror = 1 and ``results['fallback']`` is True."""
+    if options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise TypeError("Argument options is not a struct!")
+    options = dict(options)
+    t0 = time.perf_counter()
+    D = _matrix(D, "D")
+    m, n = D.shape
+    S = np.asarray(S, dtype=np.float64)
+    if S.ndim == 1:
+        S = S.reshape(-1, 1)
+    if S.ndim != 2:
+        raise ValueError("Argument S is neither a vector nor a matrix!")
+    if S.shape[0] != m:
+        raise ValueError("The number of rows in argument D do not match size of S!")
+    fl = _multi_fits(fits, m)
+    K = len(fl)
+    if S.shape[1] not in (1, K):
+        raise ValueError(f"S has {S.shape[1]} columns for {K} fits: one shared response or one column per fit")
+    S = np.asfortranarray(S)
+    lw = loss_fields(dict(weights=options.pop("weights", None)), m, "lad")
+    weights = None if lw is None else lw["weights"]
+    for key in ("fast", "convtest"):
+        if options.get(key, 0):
+            raise ValueError(f"options.{key} is not available in robustfit_multi: call lad / huberfit per fit")
+    if options.get("relax", 1) != 1:
+        raise ValueError("options.relax is not available in robustfit_multi: call lad / huberfit per fit")
+    if options.get("stopcond", "standard") != "standard":
+        raise ValueError("options.stopcond: robustfit_multi stops on the primal residual alone ('standard')")
+    starts = {}
+    for key, rows in (("x0", n), ("z0", m), ("u0", m)):
+        if options.get(key) is not None:
+            v = np.asarray(options[key], dtype=np.float64)
+            if v.shape != (rows, K):
+                raise ValueError(f"options.{key} is not a {rows} x {K} matrix (one column per fit)!")
+            starts[key] = np.asfortranarray(v)
+    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals") if k in options}
+    res = {}
+    if n > 448:  # the one-pass kernel's limit: per-fit engines, same fields
+        per = []
+        for k, (kind, a, b, eps, delta) in enumerate(fl):
+            o = dict(loop, nodualerror=1, slopes=(a, b), **{key: v[:, k] for key, v in starts.items()})
+            if kind == "lad":
+                o["epsilon"] = eps
+            else:
+                o["delta"] = delta
+            if weights is not None:
+                o["weights"] = weights
+            per.append(_lad_like(kind, D, S[:, k if S.shape[1] > 1 else 0], o))
+        steps = np.array([r["steps"] for r in per], dtype=np.int64)
+        Smax = int(steps.max())
+        for key in ("xopt", "zopt", "uopt"):
+            res[key] = np.asfortranarray(np.stack([np.asarray(r[key]).reshape(-1) for r in per], axis=1))
+        for key in _MULTI_HIST:
+            if all(key in r for r in per):
+                h = np.full((Smax, K), np.nan, order="F")
+                for c, r in enumerate(per):
+                    h[:steps[c], c] = np.asarray(r[key])[:steps[c]]
+                res[key] = h
+        res["steps"] = steps
+        res["objopt"] = np.array([r.get("objopt", np.nan) for r in per], dtype=np.float64)
+        res["runtime"] = float(sum(r["runtime"] for r in per))
+        res["chunk"] = 1
+        res["fallback"] = True
+        res["solverruntime"] = time.perf_counter() - t0
+        return res
+    from . import _lib as L
+    from .reg_multi import RegMulti
+    obj = RegMulti(D, S, [0 if f[0] == "lad" else 1 for f in fl], [f[1] for f in fl], [f[2] for f in fl],
+                   [f[3] for f in fl], [f[4] for f in fl], device=int(options.get("device", 0)))
+    try:
+        if weights is not None:
+            obj.set_weights(weights)
+        summ = obj.run(check_every=int(options.get("check_every", 0)), **starts, **loop)
+        Smax = int(summ["steps"].max())
+        res["xopt"] = obj.fetch(L.REGM_F_XOPT, n)
+        res["zopt"] = obj.fetch(L.REGM_F_ZOPT, m)
+        res["uopt"] = obj.fetch(L.REGM_F_UOPT, m)
+        res["steps"] = summ["steps"]
+        res["pnorm"] = obj.fetch(L.REGM_F_PNORM, Smax)
+        res["perr"] = obj.fetch(L.REGM_F_PERR, Smax)
+        if loop.get("objevals", 0):
+            res["objevals"] = obj.fetch(L.REGM_F_OBJEVALS, Smax)
+        res["objopt"] = summ["objopt"]
+        res["runtime"] = summ["runtime"]
+        res["chunk"] = obj.chunk()
+        res["fallback"] = False
+    finally:
+        obj.close()
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
+
+
+def quantilereg_multi(D, s, taus, options=None):
+    """results = quantilereg_multi(D, s, taus, options): the quantiles ``taus`` (each strictly inside (0, 1)) of one
+    response s in one run over D -- robustfit_multi with the pinball loss of quantilereg() per fit and one shared s.
+    Column k of xopt / zopt / uopt belongs to taus[k]; ``results['taus']`` repeats them."""
+    if options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise TypeError("Argument options is not a struct!")
+    taus = np.atleast_1d(np.asarray(taus, dtype=np.float64)).reshape(-1)
+    if taus.size < 1:
+        raise ValueError("taus must hold at least one quantile")
+    for k, tau in enumerate(taus):
+        if not np.isreal(tau) or not 0.0 < tau < 1.0:
+            raise ValueError(f"fit {k}: tau must lie strictly inside (0, 1)")
+    if options.get("tau") is not None or options.get("slopes") is not None:
+        raise ValueError("quantilereg_multi sets the slopes itself: options.tau / options.slopes")
+    res = robustfit_multi(D, _colvec(s, "s"), [dict(kind="lad", tau=float(t)) for t in taus], options)
+    res["taus"] = taus
+    return res
 
 
 def _single_column_quirk(D):

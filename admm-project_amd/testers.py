@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
+__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -125,6 +125,22 @@ def quantileregtest(seed=0, rows=200, cols=8, tau=0.9, quiet=1, options=None):
     test = dict(D=D, s=s, tau=tau, xopt=xopt, admmopt=results["objopt"], objopt=objopt, negative=int(np.sum(z < 0)),
                 zero=int(np.sum(z == 0)), slack=slack, failed=int(slack > QUANTILE_COUNT_SLACK), steps=results["steps"])
     return results, test
+
+
+def quantileregmultitest(seed=0, rows=200, cols=8, taus=(0.1, 0.25, 0.5, 0.75, 0.9), quiet=1, options=None):
+    """quantileregtest for quantilereg_multi: the quantiles ``taus`` of synth.quantile_problem (an intercept column) in
+    one run; pass when, for every tau, #(z < 0) <= tau*m <= #(z <= 0) holds on that fit's final z within
+    QUANTILE_COUNT_SLACK observations.  Returns the ``test`` dict alone; the solver's results are ``test['results']``."""
+    p = synth.quantile_problem(seed, rows, cols)
+    D, s = p["D"], p["s"]
+    results = solvers.quantilereg_multi(D, s, taus, _opts(options, objevals=1, quiet=quiet))
+    Z = np.asarray(results["zopt"])
+    slack = [quantile_count_slack(Z[:, k], float(tau)) for k, tau in enumerate(taus)]
+    test = dict(D=D, s=s, taus=tuple(float(t) for t in taus), xopt=results["xopt"], admmopt=results["objopt"],
+                negative=[int(np.sum(Z[:, k] < 0)) for k in range(len(taus))],
+                zero=[int(np.sum(Z[:, k] == 0)) for k in range(len(taus))], slack=slack,
+                failed=int(any(v > QUANTILE_COUNT_SLACK for v in slack)), steps=results["steps"], results=results)
+    return test
 
 
 def huberfittest(seed=0, rows=2 ** 11, cols=2 ** 7, errtol=1e-3, quiet=1, options=None):

@@ -842,6 +842,103 @@ int admm_svm_ovr_set_cost(admm_svm_ovr* obj, const double* weights, const double
 int admm_svm_ovr_chunk(void);
 void admm_svm_ovr_destroy(admm_svm_ovr* obj);
 
+/* ---- quantile / LAD / Huber regression, K fits in one pass over D (additive to ABI 5) ---------------
+ * A caller of lad.m / huberfit.m wants a set of quantiles of one design matrix, a Huber fit at several thresholds, or
+ * one loss against several response columns.  The x-update of the A = D iteration, (D'D)^-1 D'(s + z - u)
+ * (getProxOps.m:1511-1515), contains neither the loss nor its parameters; those enter the element-wise z-prox (the loss
+ * family of admm_engine_set_loss) and the objective alone.  So K fits are K independent plain-ADMM runs
+ * (admm.m:496-743: A = D, B = -1, c = s_k, stopcond = 'standard', nodualerror = 1) that share D, the map (D'D)^-1 and
+ * every byte an iteration reads: this object runs them side by side, one read of D per iteration for a chunk of fits
+ * (csrc/reg_multi.hip).  A fit that has met its stop condition is frozen: its result is that of an independent run with
+ * that many steps.
+ * The dual residual is NOT evaluated: it would need two more transposed products with D per fit and iteration -- the
+ * same restriction as the engine's one-pass form.  A fit stops when pnorm < perr, and therefore equals
+ * lad(D, s, {..., 'nodualerror': 1}) / huberfit(D, s, {..., 'nodualerror': 1}), not the default lad / huberfit.
+ * Not available here, each refused with ADMM_E_UNSUPPORTED (use one ADMM_PROB_LAD / ADMM_PROB_HUBERFIT engine per fit
+ * instead): n > 448, m < n, fast ADMM, relaxation, convtest, a communicator; there is no H-norm stop, and there are no
+ * callback or hook entry points.  Vector histories (xvals, zvals, uvals) are not recorded. */
+typedef struct admm_reg_multi admm_reg_multi; /* opaque */
+#define ADMM_REG_MULTI_MAX_N 448
+
+typedef struct admm_reg_multi_desc {
+  int32_t struct_size;   /* sizeof(admm_reg_multi_desc) */
+  int32_t K;             /* number of fits, >= 1 */
+  int64_t m, n;          /* D is m x n, m >= n */
+  const double* D;       /* m x n, column-major */
+  int64_t ldD;           /* leading dimension of D (0 = m) */
+  const double* S;       /* m x ns, column-major: the response of every fit (ns = 1) or one column per fit (ns = K) */
+  int32_t ns;            /* 1 or K */
+  int32_t mem;           /* ADMM_MEM_* of D and S */
+  int32_t device;        /* HIP device ordinal */
+  int32_t reserved0;
+  const int32_t* kind;   /* K values: 0 = the LAD engine's phi, 1 = the Huber engine's (admm_engine_set_loss); NULL = all 0 */
+  const double* a;       /* K slopes of the positive side (NULL = 1); the tau-quantile: a = tau, b = 1 - tau */
+  const double* b;       /* K slopes of the negative side (NULL = 1) */
+  const double* epsilon; /* K dead zones, LAD fits (NULL = 0) */
+  const double* delta;   /* K thresholds, Huber fits (NULL = 1) */
+  admm_comm* comm;       /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_reg_multi_desc;
+
+/* the options the K runs share (admm.m:51-76); the ones that select a variant this object does not run are refused */
+typedef struct admm_reg_multi_options {
+  int32_t struct_size;   /* sizeof(admm_reg_multi_options) */
+  int32_t maxiters;      /* default 1000 */
+  double rho;            /* default 1.0 */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations enqueued between host polls of "every fit has stopped" (0 = auto: 8; 64 with
+                            domaxiters) */
+  int32_t reserved0;
+  const double* x0;      /* n x K host matrix (NULL = zeros; admm.m:252-254) */
+  const double* z0;      /* m x K */
+  const double* u0;      /* m x K */
+} admm_reg_multi_options;
+
+typedef struct admm_reg_multi_summary {  /* one per fit */
+  int32_t steps;          /* results.steps of that fit (admm.m:746) */
+  int32_t stopped_early;  /* 1 if pnorm < perr fired before maxiters (admm.m:710-713) */
+  double objopt;          /* results.objopt = sum_i w_i*phi_k(z_i) (lad.m:148 / huberfit.m:180 with the family inside), NaN
+                             if not evaluated */
+} admm_reg_multi_summary;
+
+/* fields of admm_reg_multi_fetch */
+enum {
+  ADMM_REGM_F_XOPT = 1,      /* n x K */
+  ADMM_REGM_F_ZOPT = 2,      /* m x K */
+  ADMM_REGM_F_UOPT = 3,      /* m x K */
+  /* scalar histories (admm.m:621-658, 603-605): S x K column-major with S = the largest steps of any fit, NaN past a
+   * fit's own last step */
+  ADMM_REGM_F_PNORM = 4, ADMM_REGM_F_PERR = 5, ADMM_REGM_F_OBJEVALS = 6
+};
+
+void admm_reg_multi_desc_default(admm_reg_multi_desc* desc);
+void admm_reg_multi_options_default(admm_reg_multi_options* opts);
+/* the one-time setup of lad.m:134 for all fits: uploads D and S, builds (D'D)^-1 or keeps the Cholesky factor as
+ * admm_engine_create's probe decides.  ADMM_E_INVALID, naming the fit: a kind other than 0 / 1; a slope <= 0;
+ * epsilon < 0, or != 0 on a Huber fit; delta <= 0, or != 1 on a LAD fit; a non-finite value.  ADMM_E_NUMERIC: D'D is
+ * numerically singular (lad.m:134 calls chol: there are no pinv semantics here). */
+int admm_reg_multi_create(const admm_reg_multi_desc* desc, admm_reg_multi** out);
+/* the K loops of admm.m:496-743; summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be
+ * called again on the same object: every run starts from its own x0 / z0 / u0 */
+int admm_reg_multi_run(admm_reg_multi* obj, const admm_reg_multi_options* opts, admm_reg_multi_summary* summaries,
+                       double* runtime_s);
+int admm_reg_multi_fetch(admm_reg_multi* obj, int field, double* dst, size_t cap, size_t* written);
+/* weights = m HOST values w_i >= 0 shared by all fits, copied at the call and held for every later run; NULL restores 1.
+ * ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
+int admm_reg_multi_set_weights(admm_reg_multi* obj, const double* weights);
+/* kernel launches of the last run's iterations (the start's D'(s + z0 - u0) not counted): counts[0] iterations
+ * enqueued, [1] x-solve launches, [2] passes over D, [3] sum / finalize launches, [4] 1 where the x-solve is the one
+ * launch of the explicit map (0: two triangular solves per fit and one copy) */
+int admm_reg_multi_launches(admm_reg_multi* obj, int64_t counts[5]);
+/* fits one pass over D serves (K beyond it: ceil(K / chunk) passes per iteration) */
+int admm_reg_multi_chunk(void);
+void admm_reg_multi_destroy(admm_reg_multi* obj);
+
 #ifdef __cplusplus
 }
 #endif
