@@ -235,6 +235,25 @@ REGM_F_XOPT, REGM_F_ZOPT, REGM_F_UOPT, REGM_F_PNORM, REGM_F_PERR, REGM_F_OBJEVAL
 REG_MULTI_MAX_N = 448
 REGM_KIND_LAD, REGM_KIND_HUBER = 0, 1
 
+class SparseSvmDesc(C.Structure):  # admm_sparse_svm_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("D", C.POINTER(SparseDesc)), ("ELL", _dp),
+                ("loss", C.POINTER(C.c_int32)), ("C", C.c_double), ("device", C.c_int32), ("reserved0", C.c_int32),
+                ("comm", C.c_void_p)]
+
+
+class SparseSvmOptions(C.Structure):  # admm_sparse_svm_options
+    _fields_ = [("struct_size", C.c_int32), ("maxiters", C.c_int32), ("rho", C.c_double), ("abstol", C.c_double),
+                ("reltol", C.c_double), ("Hnormtol", C.c_double), ("relax", C.c_double), ("fast", C.c_int32),
+                ("convtest", C.c_int32), ("domaxiters", C.c_int32), ("objevals", C.c_int32),
+                ("check_every", C.c_int32), ("cg_maxit", C.c_int32), ("cg_tol", C.c_double), ("x0", _dp), ("z0", _dp),
+                ("u0", _dp)]
+
+
+class SparseSvmSummary(C.Structure):  # admm_sparse_svm_summary
+    _fields_ = [("steps", C.c_int32), ("stopped_early", C.c_int32), ("objopt", C.c_double),
+                ("cg_iters_total", C.c_int64), ("cg_capped_updates", C.c_int64)]
+
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
@@ -356,6 +375,16 @@ _SIGNATURES = {
     "admm_reg_multi_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "admm_reg_multi_chunk": (C.c_int, []),
     "admm_reg_multi_destroy": (None, [C.c_void_p]),
+    "admm_op_spmm": (C.c_int, [C.POINTER(SparseDesc), C.c_int, C.c_int, _dp, _dp]),
+    "admm_sparse_svm_desc_default": (None, [C.POINTER(SparseSvmDesc)]),
+    "admm_sparse_svm_options_default": (None, [C.POINTER(SparseSvmOptions)]),
+    "admm_sparse_svm_create": (C.c_int, [C.POINTER(SparseSvmDesc), C.POINTER(C.c_void_p)]),
+    "admm_sparse_svm_run": (C.c_int, [C.c_void_p, C.POINTER(SparseSvmOptions), C.POINTER(SparseSvmSummary),
+                                      C.POINTER(C.c_double)]),
+    "admm_sparse_svm_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_sparse_svm_set_cost": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "admm_sparse_svm_chunk": (C.c_int, []),
+    "admm_sparse_svm_destroy": (None, [C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

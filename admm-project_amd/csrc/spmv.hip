@@ -10,29 +10,6 @@ namespace admm {
 
 namespace {
 
-// the sum of v over the L consecutive lanes of a group (L a power of two), valid in every lane of the group: a
-// butterfly whose pairing depends on L alone.  Inside a 16-lane row the exchanges are DPP moves; 32 and 64 lanes add
-// the permlane swaps of wave_reduce.h.  Every lane of the wave must be active.
-template <int L>
-__device__ __forceinline__ double group_sum(double v) {
-  if constexpr (L >= 64) {
-    double w = v;
-    swap_half(v, w);  // v = the lower half's value in both halves, w = the upper half's
-    v += w;
-  }
-  if constexpr (L >= 32) {
-    double w = v;
-    swap_row(v, w);   // v = the even row's value in both rows of a pair, w = the odd row's
-    v += w;
-  }
-  if constexpr (L >= 16) v += dpp_mov<0x128>(v);      // row_ror:8
-  if constexpr (L >= 16) v += dpp_mov<0x124>(v);      // row_ror:4 (both halves of the row hold the same sums by now)
-  else if constexpr (L == 8) v += dpp_mov<0x141>(v);  // row_half_mirror: lane i <- lane 7 - i of its 8
-  if constexpr (L >= 4) v += dpp_mov<0x4E>(v);        // quad_perm [2,3,0,1]
-  if constexpr (L >= 2) v += dpp_mov<0xB1>(v);        // quad_perm [1,0,3,2]
-  return v;
-}
-
 template <int L, bool NT>
 __global__ __launch_bounds__(kBlock) void spmv_kernel(int64_t rows, const int64_t* __restrict__ start,
                                                       const int32_t* __restrict__ idx, const double* __restrict__ val,

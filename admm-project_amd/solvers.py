@@ -432,7 +432,10 @@ def linearsvm(D, ell, C, options=None):
 
     Engine-side extension: ``options['weights']`` (m values w_i >= 0) and ``options['classcost']`` (a
     pair (pos, neg), or 'balanced' = (m/(2*m_pos), m/(2*m_neg))) put the cost c_i = w_i*(ell_i > 0 ? pos : neg) on
-    observation i: C*sum_i c_i*phi(ell_i*(D*x)_i).  They change the z-update and the objective alone."""
+    observation i: C*sum_i c_i*phi(ell_i*(D*x)_i).  They change the z-update and the objective alone.
+
+    A ``scipy.sparse`` D runs the K = 1 case of ``linearsvm_ovr``'s sparse object: the same fields with
+    the class axis dropped, no vector histories, and the same refused options."""
     if not isinstance(options, dict):
         raise TypeError("Given options is not a struct! At least pass empty struct!")
     options = dict(options)
@@ -441,10 +444,13 @@ def linearsvm(D, ell, C, options=None):
         raise ValueError("Given regularization parameter C is not a nonnegative number!")
     C = float(np.real(C))
     ell = _colvec(ell, "ell")
-    D = _matrix(D, "D")
+    D = _matrix(D, "D", sparse_ok=True)
     if D.shape[0] != ell.size:
         raise ValueError("Product ell*D is not possible; sizes incompatible!")
     _single_column_quirk(D)
+    from ._lib import is_sparse
+    if is_sparse(D):
+        return _linearsvm_sparse(D, ell, C, options, t0)
     loss = options.get("lossfunction", "hinge")  # linearsvm.m:154-158
     cost = svm_cost_fields({k: options.pop(k, None) for k in SVM_COST_KEYS}, ell)
     if cost is not None and "comm" in options:
@@ -459,6 +465,37 @@ def linearsvm(D, ell, C, options=None):
     results = unwrappedadmm(minz, D, options)
     results["solverruntime"] = time.perf_counter() - t0
     return results
+
+
+def _linearsvm_sparse(D, ell, C, options, t0):
+    """linearsvm on a scipy.sparse D: the K = 1 case of the sparse one-vs-rest object, the class axis
+    dropped from every field; vector histories are not recorded"""
+    _sparse_svm_refusals(options, "linearsvm")
+    m, n = D.shape
+    loss = options.get("lossfunction", "hinge")
+    if not isinstance(loss, str):
+        raise ValueError("options.lossfunction is not a string!")
+    cost = svm_cost_fields({k: options.get(k) for k in SVM_COST_KEYS}, ell)
+    rng = np.random.default_rng()
+    starts = {}
+    for key, rows in (("x0", n), ("z0", m), ("u0", m)):  # unwrappedadmm.m:87-89
+        v = _colvec(options[key], key) if key in options else rng.random(rows)
+        if v.size != rows:
+            raise ValueError(f"options.{key} does not have {rows} entries!")
+        starts[key] = np.asfortranarray(v.reshape(rows, 1))
+    weights = class_cost = None
+    if cost is not None:
+        weights = cost.get("weights")
+        class_cost = np.array([cost.get("classcost", (1.0, 1.0))], dtype=np.float64)
+    res = _sparse_svm_run(D, np.asfortranarray(ell.reshape(m, 1)), C, [loss], options, starts, weights, class_cost)
+    for key in ("xopt", "zopt", "uopt") + _OVR_HIST:
+        if key in res:
+            res[key] = np.ascontiguousarray(res[key][:, 0])
+    for key in ("steps", "cg_iters_total", "cg_capped_updates"):
+        res[key] = int(res[key][0])
+    res["objopt"] = float(res["objopt"][0])
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
 
 
 def ovr_label_matrix(labels, classes):
@@ -490,6 +527,60 @@ def _ovr_costs(options, ELL):
 _OVR_HIST = ("pnorm", "perr", "Hnormsq", "objevals")
 
 
+def _sparse_svm_refusals(options, who):
+    """the options the sparse one-vs-rest object does not run, each named in its ValueError"""
+    for key in ("fast", "convtest", "adaptive"):
+        if options.get(key, 0):
+            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
+    if options.get("relax", 1) != 1:
+        raise ValueError(f"options.relax is not available in {who} on a sparse D")
+    xs = options.get("xsolve", "auto")
+    if not (isinstance(xs, str) and xs.lower() in ("auto", "cg")):
+        raise ValueError(f"options.xsolve = {xs!r}: {who} on a sparse D runs the matrix-free x-update ('auto' or 'cg')")
+    for key in ("Dplus", "comm"):
+        if options.get(key) is not None:
+            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
+    if options.get("parallel", "none") not in ("none", 0, None):
+        raise ValueError(f"options.parallel is not available in {who} on a sparse D")
+
+
+def _sparse_svm_run(D, ELL, C, losses, options, starts, weights, class_cost):
+    """the K runs of linearsvm_ovr on a scipy.sparse D through one SparseSvmOvr: the fields
+    linearsvm_ovr returns, plus xsolve, nnz, cg_iters_total and cg_capped_updates (K values each)"""
+    from . import _lib as L
+    from .sparse_svm import SparseSvmOvr
+    m, n = D.shape
+    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "domaxiters", "objevals", "cg_tol", "cg_maxit")
+            if k in options}
+    if "Hreltol" in options or "Hnormtol" in options:  # admm.m:927-928 (q2): either spelling
+        loop["Hnormtol"] = options.get("Hreltol", options.get("Hnormtol"))
+    res = {}
+    obj = SparseSvmOvr(D, ELL, C, losses, device=int(options.get("device", 0)))
+    try:
+        if weights is not None or class_cost is not None:
+            obj.set_cost(weights, class_cost)
+        summ = obj.run(check_every=int(options.get("check_every", 0)), z0=starts["z0"], u0=starts["u0"], **loop)
+        S = int(summ["steps"].max())
+        res["xopt"] = obj.fetch(L.OVR_F_XOPT, n)
+        res["zopt"] = obj.fetch(L.OVR_F_ZOPT, m)
+        res["uopt"] = obj.fetch(L.OVR_F_UOPT, m)
+        res["steps"] = summ["steps"]
+        res["pnorm"] = obj.fetch(L.OVR_F_PNORM, S)
+        res["perr"] = obj.fetch(L.OVR_F_PERR, S)
+        res["Hnormsq"] = obj.fetch(L.OVR_F_HNORMSQ, S)
+        if loop.get("objevals", 0):
+            res["objevals"] = obj.fetch(L.OVR_F_OBJEVALS, S)
+        res["objopt"] = summ["objopt"]
+        res["runtime"] = summ["runtime"]
+        res["xsolve"] = "cg"
+        res["nnz"] = obj.nnz
+        res["cg_iters_total"] = summ["cg_iters_total"]
+        res["cg_capped_updates"] = summ["cg_capped_updates"]
+    finally:
+        obj.close()
+    return res
+
+
 def linearsvm_ovr(D, labels, C, options=None):
     """results = linearsvm_ovr(D, labels, C, options): one linearsvm (solvers/linearsvm.m:92-246) per class of
     ``labels`` against the rest, as examples/mnistsvm.m:88-102 trains them, in ONE run over D.
@@ -505,6 +596,13 @@ def linearsvm_ovr(D, labels, C, options=None):
     Returns classes, xopt (n x K), zopt, uopt (m x K), steps (K), pnorm / perr / Hnormsq / objevals (max(steps) x K,
     NaN past a class's last step), objopt (K), runtime, solverruntime.  Vector histories are not recorded.
     For n > 448 the classes run one after the other through ``linearsvm`` and the same fields come back.
+
+    ``D`` may be any ``scipy.sparse`` matrix or array: it is converted to canonical CSC and stays sparse
+    on the device, and the x-update D^+(z - u) is conjugate gradients on D'D x = D'(z - u) for all classes in lock-step
+    (``cg_tol``, ``cg_maxit`` as for ``xsolve = 'cg'``; x0 is never read: the first solve starts from 0).  There is no
+    limit on n; the results also carry ``xsolve`` = 'cg', ``nnz``, ``cg_iters_total`` and ``cg_capped_updates`` (K values
+    each).  ``fast``, ``convtest``, ``relax`` != 1, ``adaptive``, ``xsolve`` other than auto / cg, ``Dplus``, ``comm`` and
+    ``parallel`` raise ValueError.
     """
     if options is None:
         options = {}
@@ -516,11 +614,15 @@ def linearsvm_ovr(D, labels, C, options=None):
         raise ValueError("Given regularization parameter C is not a nonnegative number!")
     C = float(np.real(C))
     labels = _colvec(labels, "labels")
-    D = _matrix(D, "D")
+    D = _matrix(D, "D", sparse_ok=True)
+    from ._lib import is_sparse
+    sparse = is_sparse(D)  # the matrix-free object, no limit on n
     m, n = D.shape
     if labels.size != m:
         raise ValueError("Product ell*D is not possible; sizes incompatible!")  # linearsvm.m:283-286
     _single_column_quirk(D)
+    if sparse:
+        _sparse_svm_refusals(options, "linearsvm_ovr")
     classes = np.asarray(options["classes"] if "classes" in options else np.unique(labels), dtype=np.float64)
     if classes.ndim != 1 or classes.size < 1:
         raise ValueError("options.classes is not a non-empty vector of class ids!")
@@ -550,6 +652,10 @@ def linearsvm_ovr(D, labels, C, options=None):
     if "Hreltol" in options or "Hnormtol" in options:  # admm.m:927-928 (q2): either spelling
         loop["Hnormtol"] = options.get("Hreltol", options.get("Hnormtol"))
     res = dict(classes=classes)
+    if sparse:
+        res.update(_sparse_svm_run(D, ELL, C, losses, options, starts, weights, class_cost))
+        res["solverruntime"] = time.perf_counter() - t0
+        return res
     if n > 448:  # the one-pass kernel's limit: per-class engines, same fields
         per = []
         for c in range(K):

@@ -151,6 +151,16 @@ def sparse_lasso_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05):
     return dict(D=D, s=s, lam=lam, testx=testx)
 
 
+def sparse_svm_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=3):
+    """A multi-class problem on sparse_lasso_problem's design matrix (sparse Gaussian, unit columns, canonical
+    ``scipy.sparse.csc_matrix``): ``classes`` planted directions W (cols x K, randn), and the label of row i is the
+    direction with the largest score (D*W)[i].  dict(D, labels, W, C)."""
+    D = sparse_lasso_problem(seed, rows, cols, density)["D"]
+    W = np.random.default_rng(seed + 104729).standard_normal((cols, classes))
+    labels = np.argmax(D @ W, axis=1).astype(np.float64)
+    return dict(D=D, labels=labels, W=W, C=1.0)
+
+
 def grouplasso_problem(seed=0, rows=2 ** 8, cols=2 ** 6, ngroups=8, active=2):
     """lassotest's recipe with a group-sparse truth: ``ngroups`` contiguous groups of random sizes >= 1, ``active`` of them
     filled with randn and every other one exactly zero; s = D*testx + sqrt(0.001)*randn; unit weights;

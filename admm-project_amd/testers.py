@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "huberfittest", "totalvariationtest", "linearsvmtest", "basispursuittest",
+__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -196,6 +196,21 @@ def linearsvmtest(seed=0, mpos=2 ** 7, mneg=2 ** 7, sep=0.2, errtol=0.05, quiet=
                           failed=int(not (objopt < trueobj and relerr <= errtol)), relerror=relerr,
                           xresidual=np.linalg.norm(x - truex), steps=r["steps"], errtol=errtol)
     return out_r, out_t
+
+
+def sparsesvmtest(seed=0, rows=2 ** 10, cols=2 ** 7, density=0.05, classes=3, errtol=0.25, quiet=1, options=None):
+    """linearsvmtest's shape for linearsvm_ovr on a sparse design matrix (synth.sparse_svm_problem, D a scipy.sparse
+    matrix that stays sparse on the device): the one-vs-rest prediction argmax_c (D*xopt)[:, c] must reproduce the
+    planted labels on at least 1 - errtol of the training rows."""
+    p = synth.sparse_svm_problem(seed, rows, cols, density, classes)
+    D, labels = p["D"], p["labels"]
+    results = solvers.linearsvm_ovr(D, labels, p["C"], _opts(options, objevals=1, quiet=quiet,
+                                                             classes=np.arange(float(classes))))
+    pred = np.argmax(D @ results["xopt"], axis=1).astype(np.float64)
+    accuracy = float(np.mean(pred == labels))
+    test = dict(D=D, labels=labels, xopt=results["xopt"], accuracy=accuracy, failed=int(not accuracy >= 1.0 - errtol),
+                steps=results["steps"], nnz=results["nnz"], cg_capped_updates=results["cg_capped_updates"], errtol=errtol)
+    return results, test
 
 
 def basispursuittest(seed=0, rows=2 ** 6, cols=2 ** 7, errtol=1e-3, quiet=1, options=None):

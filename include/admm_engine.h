@@ -630,6 +630,10 @@ int admm_op_gemv_t(const double* D, int64_t m, int64_t n, int64_t ldD, const dou
  * by the kernel and the plans of the sparse lasso engine (admm_engine_create_sparse, whose checks of D apply): every
  * row's products are added in one fixed order, so a second call returns the same bits; an empty row gives 0.0 */
 int admm_op_spmv(const admm_sparse_desc* D, int transpose, const double* x, double* y);
+/* Y = D*X (transpose = 0: X is cols x K, Y rows x K) or Y = D'*X, X and Y column-major on the host, by the multi-vector
+ * kernel of the sparse linear SVM (admm_sparse_svm_create; csrc/spmm.hip): one read of D per chunk of
+ * admm_sparse_svm_chunk() columns, and column k of Y has the bits admm_op_spmv returns for column k of X */
+int admm_op_spmm(const admm_sparse_desc* D, int transpose, int K, const double* X, double* Y);
 /* W = D'*D (+ shift on the diagonal), n x n  (lasso.m:168, lad.m:134, unwrappedadmm.m:115) */
 int admm_op_gram(const double* D, int64_t m, int64_t n, int64_t ldD, double shift, double* W);
 /* in place lower Cholesky of the n x n SPD matrix A (chol(.,'lower'), lasso.m:168) */
@@ -938,6 +942,77 @@ int admm_reg_multi_launches(admm_reg_multi* obj, int64_t counts[5]);
 /* fits one pass over D serves (K beyond it: ceil(K / chunk) passes per iteration) */
 int admm_reg_multi_chunk(void);
 void admm_reg_multi_destroy(admm_reg_multi* obj);
+
+/* ---- linear SVM on a sparse design matrix, all one-vs-rest classes over one sparse product (additive to ABI 5;
+ * DESIGN.md q37).  The K runs are those of admm_svm_ovr (plain ADMM, A = D, B = -1, c = 0, stopcond = 'both',
+ * nodualerror = 1, the losses and costs of admm_svm_ovr_set_cost) with D an admm_sparse_desc and the x-update
+ * x_c = D^+(z_c - u_c) computed as conjugate gradients on D'D x = D'(z_c - u_c): no shift, nothing factored, nothing
+ * n x n stored, so there is no limit on n.  The first x-update of a run starts CG from 0 (x0 is never read, as in the
+ * reference's x-update) and every later one from the previous x: every iterate stays in range(D'), the limit is the
+ * pseudo-inverse solution, and a column of D without nonzeros keeps x = 0.0 exactly.  The K solves run in lock-step:
+ * each inner iteration is D*P and D'*(D*P) for all classes of a chunk over ONE read of the matrix (csrc/spmm.hip); a
+ * class whose solve has converged, or whose run has stopped, is masked.  Per class ||r|| <= cg_tol*||y|| ends a solve; an
+ * x-update that ends on cg_maxit above cg_tol is counted per class.  A zero right-hand side gives x = 0, and p.q = 0 ends
+ * the class's solve, both without a division.
+ * ADMM_E_INVALID (before the device is touched): whatever admm_engine_create_sparse refuses in D, D not in host arrays,
+ * a label that is not +-1, K < 1, an unknown loss, C < 0.  ADMM_E_UNSUPPORTED: a communicator; at run: fast ADMM,
+ * relaxation, convtest.  Vector histories are not recorded and the dual residual is not evaluated. */
+typedef struct admm_sparse_svm admm_sparse_svm; /* opaque */
+
+typedef struct admm_sparse_svm_desc {
+  int32_t struct_size;        /* sizeof(admm_sparse_svm_desc) */
+  int32_t K;                  /* number of classes (columns of ELL), >= 1 */
+  const admm_sparse_desc* D;  /* rows x cols, ADMM_MEM_HOST; copied at create */
+  const double* ELL;          /* rows x K HOST values, column-major, +-1: column c is the ell of class c */
+  const int32_t* loss;        /* K values ADMM_LOSS_*; NULL = hinge for every class */
+  double C;                   /* regularisation (linearsvm.m:270-274) */
+  int32_t device;             /* HIP device ordinal */
+  int32_t reserved0;
+  admm_comm* comm;            /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_sparse_svm_desc;
+
+typedef struct admm_sparse_svm_options {
+  int32_t struct_size;   /* sizeof(admm_sparse_svm_options) */
+  int32_t maxiters;      /* default 1000 (unwrappedadmm.m:90 forces it) */
+  double rho;            /* default 1.0 */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double Hnormtol;       /* default 1e-6 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations between host polls of "every class has stopped" (0 = auto) */
+  int32_t cg_maxit;      /* cap on the inner iterations of one x-update; default 200, <= 0 = default */
+  double cg_tol;         /* relative residual of the x-update; default 1e-12, <= 0 = default */
+  const double* x0;      /* accepted and never read (see above) */
+  const double* z0;      /* rows x K host matrix (NULL = zeros) */
+  const double* u0;      /* rows x K */
+} admm_sparse_svm_options;
+
+typedef struct admm_sparse_svm_summary {  /* one per class */
+  int32_t steps;              /* results.steps of that class (admm.m:746) */
+  int32_t stopped_early;      /* 1 if a stop condition fired before maxiters (admm.m:710-722) */
+  double objopt;              /* results.objopt (admm.m:752-754), NaN if not evaluated */
+  int64_t cg_iters_total;     /* inner iterations of the class over the run */
+  int64_t cg_capped_updates;  /* x-updates of the class that ended with the residual still above cg_tol */
+} admm_sparse_svm_summary;
+
+void admm_sparse_svm_desc_default(admm_sparse_svm_desc* desc);
+void admm_sparse_svm_options_default(admm_sparse_svm_options* opts);
+int admm_sparse_svm_create(const admm_sparse_svm_desc* desc, admm_sparse_svm** out);
+/* summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be called again on the same object:
+ * every run starts from its own z0 / u0, and two runs from the same starts give the same bits */
+int admm_sparse_svm_run(admm_sparse_svm* obj, const admm_sparse_svm_options* opts, admm_sparse_svm_summary* summaries,
+                        double* runtime_s);
+/* field: ADMM_OVR_F_*, the shapes of admm_svm_ovr_fetch */
+int admm_sparse_svm_fetch(admm_sparse_svm* obj, int field, double* dst, size_t cap, size_t* written);
+/* the arguments, the arithmetic and the refusals of admm_svm_ovr_set_cost */
+int admm_sparse_svm_set_cost(admm_sparse_svm* obj, const double* weights, const double* class_cost);
+/* classes one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
+int admm_sparse_svm_chunk(void);
+void admm_sparse_svm_destroy(admm_sparse_svm* obj);
 
 #ifdef __cplusplus
 }
