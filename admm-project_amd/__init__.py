@@ -10,6 +10,7 @@ from .api import ProxOp, admm, getproxops  # noqa: F401
 from .engine import Engine, SvmOvr  # noqa: F401
 from .reg_multi import RegMulti  # noqa: F401
 from .sparse_svm import SparseSvmOvr  # noqa: F401
+from .sparse_reg import SparseRegMulti  # noqa: F401
 from . import testers  # noqa: F401,E402
 from .solvers import (basispursuit, covarianceselection, elasticnet, grouplasso, huberfit, lad, lasso, linearprogram, linearsvm, linearsvm_ovr, model,  # noqa: F401
                       quantilereg, quantilereg_multi, quadraticprogram, robustfit_multi, totalvariation, totalvariation2d, unwrappedadmm)

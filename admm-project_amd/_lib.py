@@ -254,6 +254,29 @@ class SparseSvmSummary(C.Structure):  # admm_sparse_svm_summary
                 ("cg_iters_total", C.c_int64), ("cg_capped_updates", C.c_int64)]
 
 
+class SparseRegDesc(C.Structure):  # admm_sparse_reg_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("D", C.POINTER(SparseDesc)), ("S", _dp),
+                ("ns", C.c_int32), ("device", C.c_int32), ("kind", C.POINTER(C.c_int32)), ("a", _dp), ("b", _dp),
+                ("epsilon", _dp), ("delta", _dp), ("comm", C.c_void_p)]
+
+
+class SparseRegOptions(C.Structure):  # admm_sparse_reg_options
+    _fields_ = [("struct_size", C.c_int32), ("maxiters", C.c_int32), ("rho", C.c_double), ("abstol", C.c_double),
+                ("reltol", C.c_double), ("relax", C.c_double), ("fast", C.c_int32), ("convtest", C.c_int32),
+                ("domaxiters", C.c_int32), ("objevals", C.c_int32), ("check_every", C.c_int32),
+                ("cg_maxit", C.c_int32), ("cg_tol", C.c_double), ("nodualerror", C.c_int32), ("reserved0", C.c_int32),
+                ("x0", _dp), ("z0", _dp), ("u0", _dp)]
+
+
+class SparseRegSummary(C.Structure):  # admm_sparse_reg_summary
+    _fields_ = [("steps", C.c_int32), ("stopped_early", C.c_int32), ("objopt", C.c_double),
+                ("cg_iters_total", C.c_int64), ("cg_capped_updates", C.c_int64)]
+
+
+(SRG_F_XOPT, SRG_F_ZOPT, SRG_F_UOPT, SRG_F_PNORM, SRG_F_PERR, SRG_F_OBJEVALS, SRG_F_DNORM,
+ SRG_F_DERR) = range(1, 9)
+
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
@@ -385,6 +408,15 @@ _SIGNATURES = {
     "admm_sparse_svm_set_cost": (C.c_int, [C.c_void_p, _dp, _dp]),
     "admm_sparse_svm_chunk": (C.c_int, []),
     "admm_sparse_svm_destroy": (None, [C.c_void_p]),
+    "admm_sparse_reg_desc_default": (None, [C.POINTER(SparseRegDesc)]),
+    "admm_sparse_reg_options_default": (None, [C.POINTER(SparseRegOptions)]),
+    "admm_sparse_reg_create": (C.c_int, [C.POINTER(SparseRegDesc), C.POINTER(C.c_void_p)]),
+    "admm_sparse_reg_run": (C.c_int, [C.c_void_p, C.POINTER(SparseRegOptions), C.POINTER(SparseRegSummary),
+                                      C.POINTER(C.c_double)]),
+    "admm_sparse_reg_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_sparse_reg_set_weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_sparse_reg_chunk": (C.c_int, []),
+    "admm_sparse_reg_destroy": (None, [C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -156,6 +156,9 @@ def _lad_like(kind, D, s, options):
         raise TypeError("Argument options is not a struct!")
     options = dict(options)
     t0 = time.perf_counter()
+    from ._lib import is_sparse
+    if is_sparse(D):
+        return _lad_like_sparse(kind, D, s, options, t0)
     D = _matrix(D, "D")
     s = _colvec(s, "s")
     m, n = D.shape
@@ -175,13 +178,112 @@ def _lad_like(kind, D, s, options):
     return results
 
 
+def _sparse_reg_refusals(options, who):
+    """the options the sparse multi-fit regression does not run, each named in its ValueError"""
+    for key in ("fast", "convtest", "adaptive"):
+        if options.get(key, 0):
+            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
+    if options.get("relax", 1) != 1:
+        raise ValueError(f"options.relax is not available in {who} on a sparse D")
+    xs = options.get("xsolve", "auto")
+    if not (isinstance(xs, str) and xs.lower() in ("auto", "cg")):
+        raise ValueError(f"options.xsolve = {xs!r}: {who} on a sparse D runs the matrix-free x-update ('auto' or 'cg')")
+    if options.get("comm") is not None:
+        raise ValueError(f"options.comm is not available in {who} on a sparse D")
+    if options.get("parallel", "none") not in ("none", 0, None):
+        raise ValueError(f"options.parallel is not available in {who} on a sparse D")
+    if options.get("stopcond", "standard") != "standard":
+        raise ValueError(f"options.stopcond: {who} on a sparse D runs the 'standard' stop rule alone")
+
+
+_SPARSE_REG_HIST = ("pnorm", "perr", "dnorm", "derr", "objevals")
+
+
+def _sparse_reg_run(D, S, fl, options, starts, weights, nodualerror):
+    """the K runs of robustfit_multi on a scipy.sparse D through one SparseRegMulti: the fields
+    robustfit_multi returns, plus xsolve, nnz, cg_iters_total and cg_capped_updates (K values each), and dnorm / derr
+    when the dual residual is evaluated"""
+    from . import _lib as L
+    from .sparse_reg import SparseRegMulti
+    m, n = D.shape
+    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals", "cg_tol",
+                                    "cg_maxit") if k in options}
+    res = {}
+    obj = SparseRegMulti(D, S, [0 if f[0] == "lad" else 1 for f in fl], [f[1] for f in fl], [f[2] for f in fl],
+                         [f[3] for f in fl], [f[4] for f in fl], device=int(options.get("device", 0)))
+    try:
+        if weights is not None:
+            obj.set_weights(weights)
+        summ = obj.run(check_every=int(options.get("check_every", 0)), nodualerror=int(bool(nodualerror)),
+                       z0=starts.get("z0"), u0=starts.get("u0"), **loop)
+        Smax = int(summ["steps"].max())
+        res["xopt"] = obj.fetch(L.SRG_F_XOPT, n)
+        res["zopt"] = obj.fetch(L.SRG_F_ZOPT, m)
+        res["uopt"] = obj.fetch(L.SRG_F_UOPT, m)
+        res["steps"] = summ["steps"]
+        res["pnorm"] = obj.fetch(L.SRG_F_PNORM, Smax)
+        res["perr"] = obj.fetch(L.SRG_F_PERR, Smax)
+        if not nodualerror:
+            res["dnorm"] = obj.fetch(L.SRG_F_DNORM, Smax)
+            res["derr"] = obj.fetch(L.SRG_F_DERR, Smax)
+        if loop.get("objevals", 0):
+            res["objevals"] = obj.fetch(L.SRG_F_OBJEVALS, Smax)
+        res["objopt"] = summ["objopt"]
+        res["runtime"] = summ["runtime"]
+        res["chunk"] = obj.chunk()
+        res["xsolve"] = "cg"
+        res["nnz"] = obj.nnz
+        res["cg_iters_total"] = summ["cg_iters_total"]
+        res["cg_capped_updates"] = summ["cg_capped_updates"]
+    finally:
+        obj.close()
+    return res
+
+
+def _lad_like_sparse(kind, D, s, options, t0):
+    """lad / huberfit on a scipy.sparse D: the K = 1 case of the sparse multi-fit object under the
+    reference's default nodualerror = 0, the fit axis dropped from every field; vector histories are not recorded"""
+    who = "lad" if kind == "lad" else "huberfit"
+    _sparse_reg_refusals(options, who)
+    D = _matrix(D, "D", sparse_ok=True)
+    s = _colvec(s, "s")
+    m, n = D.shape
+    if s.size != m:
+        raise ValueError("The number of rows in argument D do not match size of s!")
+    loss = loss_fields({k: options.get(k) for k in LOSS_KEYS}, m, kind) or {}
+    a, b = loss.get("slopes", (1.0, 1.0))
+    fl = [(kind, a, b, loss.get("epsilon", 0.0), loss.get("delta", 1.0))]
+    starts = {}
+    for key, rows in (("x0", n), ("z0", m), ("u0", m)):  # admm.m:252-254: zeros; x0 is checked and never read
+        if options.get(key) is not None:
+            v = _colvec(options[key], key)
+            if v.size != rows:
+                raise ValueError(f"options.{key} does not have {rows} entries!")
+            starts[key] = np.asfortranarray(v.reshape(rows, 1))
+    res = _sparse_reg_run(D, np.asfortranarray(s.reshape(m, 1)), fl, options, starts, loss.get("weights"),
+                          options.get("nodualerror", 0))
+    for key in ("xopt", "zopt", "uopt") + _SPARSE_REG_HIST:
+        if key in res:
+            res[key] = np.ascontiguousarray(res[key][:, 0])
+    for key in ("steps", "cg_iters_total", "cg_capped_updates"):
+        res[key] = int(res[key][0])
+    res["objopt"] = float(res["objopt"][0])
+    del res["chunk"]
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
+
+
 def lad(D, s, options=None):
     """results = lad(D, s, options)   (solvers/lad.m:51-154): minimise ||D*x - s||_1.
 
     Engine-side extension: minimise sum_i w_i*phi(D*x - s)_i with phi(r) = a*max(r - eps, 0) +
     b*max(-r - eps, 0): ``options['weights']`` (m values w_i >= 0), ``options['slopes']`` = (a, b) or ``options['tau']``
     (the tau-quantile: a = tau, b = 1 - tau) and ``options['epsilon']`` (the dead zone of support vector regression)
-    change the z-update alone."""
+    change the z-update alone.
+
+    A ``scipy.sparse`` D runs the K = 1 case of ``robustfit_multi``'s sparse object under the default
+    stop rule (``nodualerror = 0``): the same fields with the fit axis dropped, no vector histories, and the same refused
+    options."""
     return _lad_like("lad", D, s, options if options is not None else {})
 
 
@@ -190,7 +292,7 @@ def huberfit(D, s, options=None):
 
     Engine-side extension: minimise sum_i w_i*(r_i >= 0 ? a : b)*H_delta(r_i), r = D*x - s, with
     H_delta(r) = r^2/2 up to |r| = delta and delta*|r| - delta^2/2 beyond: ``options['weights']``, ``options['slopes']`` =
-    (a, b) and ``options['delta']`` change the z-update alone."""
+    (a, b) and ``options['delta']`` change the z-update alone.  A ``scipy.sparse`` D: as for lad()."""
     return _lad_like("huberfit", D, s, options if options is not None else {})
 
 
@@ -257,14 +359,26 @@ def robustfit_multi(D, S, fits, options=None):
     not evaluated, so fit k equals ``lad(D, s_k, {..., 'nodualerror': 1})`` / ``huberfit(...)``, not the default call.
     Returns xopt (n x K), zopt, uopt (m x K), steps (K), objopt (K), pnorm / perr / objevals (max(steps) x K, NaN past a
     fit's last step), runtime, solverruntime, chunk (fits per pass over D) and fallback.  For n > 448 the fits run one
-    after the other through lad / huberfit with nodualerror = 1 and ``results['fallback']`` is True."""
+    after the other through lad / huberfit with nodualerror = 1 and ``results['fallback']`` is True.
+
+    A ``scipy.sparse`` D stays sparse on the device and runs the matrix-free object: every x-update is
+    conjugate gradients on D'D x = D'(s + z - u), all fits in lock-step over one sparse product -- no limit on n, m < n
+    and rank-deficient D included (the minimum-norm x-update), no ``fallback``.  ``options['nodualerror']`` (default 1,
+    as above) set to 0 evaluates the dual residual as well and returns ``dnorm`` / ``derr``; ``cg_tol`` / ``cg_maxit``
+    (1e-12 / 200) bound a solve; x0 is checked and never read.  The results carry ``xsolve = 'cg'``, ``nnz``,
+    ``cg_iters_total`` and ``cg_capped_updates`` (K values each).  fast, convtest, relax, adaptive, an xsolve other than
+    'auto' / 'cg', comm, parallel and a stopcond other than 'standard' are refused by name."""
     if options is None:
         options = {}
     if not isinstance(options, dict):
         raise TypeError("Argument options is not a struct!")
     options = dict(options)
     t0 = time.perf_counter()
-    D = _matrix(D, "D")
+    from ._lib import is_sparse
+    sparse = is_sparse(D)  # DESIGN.md q38: the matrix-free object, no limit on n
+    if sparse:
+        _sparse_reg_refusals(options, "robustfit_multi")
+    D = _matrix(D, "D", sparse_ok=sparse)
     m, n = D.shape
     S = np.asarray(S, dtype=np.float64)
     if S.ndim == 1:
@@ -296,6 +410,10 @@ def robustfit_multi(D, S, fits, options=None):
             starts[key] = np.asfortranarray(v)
     loop = {k: options[k] for k in ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals") if k in options}
     res = {}
+    if sparse:
+        res = _sparse_reg_run(D, S, fl, options, starts, weights, options.get("nodualerror", 1))
+        res["solverruntime"] = time.perf_counter() - t0
+        return res
     if n > 448:  # the one-pass kernel's limit: per-fit engines, same fields
         per = []
         for k, (kind, a, b, eps, delta) in enumerate(fl):

@@ -161,6 +161,25 @@ def sparse_svm_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=
     return dict(D=D, labels=labels, W=W, C=1.0)
 
 
+def sparse_regression_problem(seed=0, rows=2 ** 10, cols=2 ** 6, density=0.05):
+    """quantile_problem's recipe on a sparse design matrix: column 0 is a dense column of ones (the intercept, which
+    the quantile property needs), the others are sparse_lasso_problem's (sparse Gaussian, unit norm); the noise's scale
+    grows with the second regressor, so the quantile fits differ in more than the intercept.  dict(D csc_matrix in
+    canonical form, s, xtrue)."""
+    import scipy.sparse as sp
+
+    D = sparse_lasso_problem(seed, rows, cols, density)["D"].tolil()
+    D[:, 0] = np.ones((rows, 1))
+    D = sp.csc_matrix(D)
+    D.sum_duplicates()
+    D.sort_indices()
+    rng = np.random.default_rng(seed + 15485863)
+    xtrue = rng.standard_normal(cols)
+    g = np.sqrt(rows) * np.asarray(D[:, 1 if cols > 1 else 0].todense()).reshape(-1)
+    s = D @ xtrue + (1.0 + 0.5 * np.abs(g)) * rng.standard_normal(rows)
+    return dict(D=D, s=s, xtrue=xtrue)
+
+
 def grouplasso_problem(seed=0, rows=2 ** 8, cols=2 ** 6, ngroups=8, active=2):
     """lassotest's recipe with a group-sparse truth: ``ngroups`` contiguous groups of random sizes >= 1, ``active`` of them
     filled with randn and every other one exactly zero; s = D*testx + sqrt(0.001)*randn; unit weights;

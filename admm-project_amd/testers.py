@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "basispursuittest",
+__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "sparsequantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -132,6 +132,24 @@ def quantileregmultitest(seed=0, rows=200, cols=8, taus=(0.1, 0.25, 0.5, 0.75, 0
     one run; pass when, for every tau, #(z < 0) <= tau*m <= #(z <= 0) holds on that fit's final z within
     QUANTILE_COUNT_SLACK observations.  Returns the ``test`` dict alone; the solver's results are ``test['results']``."""
     p = synth.quantile_problem(seed, rows, cols)
+    D, s = p["D"], p["s"]
+    results = solvers.quantilereg_multi(D, s, taus, _opts(options, objevals=1, quiet=quiet))
+    Z = np.asarray(results["zopt"])
+    slack = [quantile_count_slack(Z[:, k], float(tau)) for k, tau in enumerate(taus)]
+    test = dict(D=D, s=s, taus=tuple(float(t) for t in taus), xopt=results["xopt"], admmopt=results["objopt"],
+                negative=[int(np.sum(Z[:, k] < 0)) for k in range(len(taus))],
+                zero=[int(np.sum(Z[:, k] == 0)) for k in range(len(taus))], slack=slack,
+                failed=int(any(v > QUANTILE_COUNT_SLACK for v in slack)), steps=results["steps"], results=results)
+    return test
+
+
+def sparsequantileregtest(seed=0, rows=2 ** 10, cols=2 ** 6, density=0.05, taus=(0.1, 0.25, 0.5, 0.75, 0.9), quiet=1,
+                          options=None):
+    """quantileregmultitest on a sparse design matrix: the quantiles ``taus`` of
+    synth.sparse_regression_problem (a dense intercept column among sparse ones) in one run of quantilereg_multi on the
+    scipy.sparse D; pass when, for every tau, #(z < 0) <= tau*m <= #(z <= 0) holds on that fit's final z within
+    QUANTILE_COUNT_SLACK observations.  Returns the ``test`` dict alone; the solver's results are ``test['results']``."""
+    p = synth.sparse_regression_problem(seed, rows, cols, density)
     D, s = p["D"], p["s"]
     results = solvers.quantilereg_multi(D, s, taus, _opts(options, objevals=1, quiet=quiet))
     Z = np.asarray(results["zopt"])

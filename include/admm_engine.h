@@ -1014,6 +1014,91 @@ int admm_sparse_svm_set_cost(admm_sparse_svm* obj, const double* weights, const 
 int admm_sparse_svm_chunk(void);
 void admm_sparse_svm_destroy(admm_sparse_svm* obj);
 
+/* ---- quantile / LAD / Huber regression on a sparse design matrix, K fits over one sparse product (additive to ABI 5;
+ * DESIGN.md q38).  The K runs are those of admm_reg_multi (plain ADMM, A = D, B = -1, c = s_k, stopcond = 'standard', the
+ * loss family of admm_engine_set_loss per fit, m shared weights) with D an admm_sparse_desc and the x-update
+ * x_k = (D'D)^-1 D'(s_k + z_k - u_k) computed as admm_sparse_svm computes its own: lock-step conjugate gradients on
+ * D'D x = D'(s_k + z_k - u_k), no shift, nothing factored, nothing n x n stored, so there is no limit on n and m < n
+ * runs.  The first x-update of a run starts CG from 0 (x0 is never read) and every later one from the previous x: with
+ * full column rank that is the reference's solution; with an empty or duplicated column it is the minimum-norm one
+ * (x = 0.0 exactly on an empty column), where lad.m:134 fails in chol.
+ * nodualerror = 0 evaluates the dual residual as well -- dnorm = rho*||D'(z - zprev)||, derr = sqrt(m)*abstol +
+ * reltol*||rho*D'u|| (admm.m:624, 652-654), two more transposed products per iteration -- and a fit then stops on
+ * pnorm < perr and dnorm < derr, as the default lad / huberfit do.
+ * ADMM_E_INVALID (before the device is touched): whatever admm_engine_create_sparse refuses in D, D not in host arrays,
+ * K < 1, ns not 1 or K, and per fit (named in the message) whatever admm_engine_set_loss refuses.  ADMM_E_UNSUPPORTED: a
+ * communicator; at run: fast ADMM, relaxation, convtest.  Vector histories are not recorded. */
+typedef struct admm_sparse_reg admm_sparse_reg; /* opaque */
+
+typedef struct admm_sparse_reg_desc {
+  int32_t struct_size;        /* sizeof(admm_sparse_reg_desc) */
+  int32_t K;                  /* number of fits, >= 1 */
+  const admm_sparse_desc* D;  /* rows x cols, ADMM_MEM_HOST; copied at create */
+  const double* S;            /* rows x ns HOST values, column-major: one response for every fit, or one column per fit */
+  int32_t ns;                 /* 1 or K */
+  int32_t device;             /* HIP device ordinal */
+  const int32_t* kind;        /* K values: 0 = the LAD engine's phi, 1 = the Huber engine's; NULL = all 0 */
+  const double* a;            /* K slopes of the positive side (NULL = 1); the tau-quantile: a = tau, b = 1 - tau */
+  const double* b;            /* K slopes of the negative side (NULL = 1) */
+  const double* epsilon;      /* K dead zones, LAD fits (NULL = 0) */
+  const double* delta;        /* K thresholds, Huber fits (NULL = 1) */
+  admm_comm* comm;            /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_sparse_reg_desc;
+
+typedef struct admm_sparse_reg_options {
+  int32_t struct_size;   /* sizeof(admm_sparse_reg_options) */
+  int32_t maxiters;      /* default 1000 */
+  double rho;            /* default 1.0 */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations between host polls of "every fit has stopped" (0 = auto: 8; 64 with domaxiters) */
+  int32_t cg_maxit;      /* cap on the inner iterations of one x-update; default 200, <= 0 = default */
+  double cg_tol;         /* relative residual of the x-update; default 1e-12, <= 0 = default */
+  int32_t nodualerror;   /* default 1: stop on pnorm < perr alone, as admm_reg_multi; 0: the reference's default rule */
+  int32_t reserved0;
+  const double* x0;      /* accepted and never read (see above) */
+  const double* z0;      /* rows x K host matrix (NULL = zeros) */
+  const double* u0;      /* rows x K */
+} admm_sparse_reg_options;
+
+typedef struct admm_sparse_reg_summary {  /* one per fit */
+  int32_t steps;              /* results.steps of that fit (admm.m:746) */
+  int32_t stopped_early;      /* 1 if the stop rule fired before maxiters (admm.m:710-713) */
+  double objopt;              /* sum_i w_i*phi_k(z_i) (lad.m:148 / huberfit.m:180 with the family inside), NaN if not evaluated */
+  int64_t cg_iters_total;     /* inner iterations of the fit over the run */
+  int64_t cg_capped_updates;  /* x-updates of the fit that ended with the residual still above cg_tol */
+} admm_sparse_reg_summary;
+
+/* fields of admm_sparse_reg_fetch: 1 .. 6 are admm_reg_multi_fetch's */
+enum {
+  ADMM_SRG_F_XOPT = 1,      /* cols x K */
+  ADMM_SRG_F_ZOPT = 2,      /* rows x K */
+  ADMM_SRG_F_UOPT = 3,      /* rows x K */
+  /* scalar histories: S x K column-major with S = the largest steps of any fit, NaN past a fit's own last step; DNORM
+   * and DERR after a run with nodualerror = 0 only */
+  ADMM_SRG_F_PNORM = 4, ADMM_SRG_F_PERR = 5, ADMM_SRG_F_OBJEVALS = 6, ADMM_SRG_F_DNORM = 7, ADMM_SRG_F_DERR = 8
+};
+
+void admm_sparse_reg_desc_default(admm_sparse_reg_desc* desc);
+void admm_sparse_reg_options_default(admm_sparse_reg_options* opts);
+int admm_sparse_reg_create(const admm_sparse_reg_desc* desc, admm_sparse_reg** out);
+/* summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be called again on the same object:
+ * every run starts from its own z0 / u0, and two runs from the same starts give the same bits */
+int admm_sparse_reg_run(admm_sparse_reg* obj, const admm_sparse_reg_options* opts, admm_sparse_reg_summary* summaries,
+                        double* runtime_s);
+int admm_sparse_reg_fetch(admm_sparse_reg* obj, int field, double* dst, size_t cap, size_t* written);
+/* weights = rows HOST values w_i >= 0 shared by all fits, copied at the call and held for every later run; NULL restores
+ * 1.  ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
+int admm_sparse_reg_set_weights(admm_sparse_reg* obj, const double* weights);
+/* fits one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
+int admm_sparse_reg_chunk(void);
+void admm_sparse_reg_destroy(admm_sparse_reg* obj);
+
 #ifdef __cplusplus
 }
 #endif
