@@ -268,6 +268,8 @@ void launch_prox(const ProxArgs& a, const Ctrl* ctrl, int* nblk_out, hipStream_t
 // A = I, alg 0 / 1: z/u update AND the finalize logic in one launch (the last workgroup to arrive finalizes);
 // a.len <= 128 * kMaxPartBlocks.  defer also serves the iterations that end in a stand-alone finalize (launch_prox's
 // place), which is where a penalised run uses it: the ungrouped penalty exists in this tail only.
+// *nblk_out = the workgroups that wrote block partials: one per 128 elements, one per 64 behind the packed
+// lower-triangle x-solve (a.ax_t set, a.ax_tri clear, while they fit kMaxPartBlocks); prox_fin_args gives the same count.
 void launch_prox_fin(const ProxArgs& a, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
                      bool defer = false, const ProxFamily* fam = nullptr);
 // out = prox_{g/rho}(v) of the loss family (device pointers): loss_device.h's function, one thread per element

@@ -339,26 +339,44 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(FinArgs a) {
 
 // ---------------------------------------------------------------- one-launch tail of an A = I iteration
 // prox + finalize (and, after the lower-triangle x-solve, the sum of its partial rows) in ONE launch.  Workgroup =
-// one 128-element tile x 4 slots: every thread sums a quarter of the x-solve's partial rows of its element (all
-// loads of a thread in one round), the quarters meet in LDS, the first 128 threads run the fused element update, the
-// block partials are published write-through (sc1) and the workgroup arrives on ctrl->arrive; the LAST workgroup to
-// arrive runs the finalize logic (norms, tolerances, H-norm, stop) on the device in the same launch.  Replaces
-// three launches (symv_reduce, prox, finalize) and two kernel boundaries: 21.7 -> ~10 us on the headline loop.
-// Sums are taken in a fixed order whatever the arrival order: bitwise reproducible.
+// one tile of W elements x S slots (W * S = 512 threads): every thread sums its slot's share of the x-solve's partial
+// rows of its element (all loads of a thread in one round), the shares meet in LDS, the first W threads run the fused
+// element update, the block partials are stored (deferred) or published write-through (sc1) with an arrival on
+// ctrl->arrive, where the LAST workgroup to arrive runs the finalize logic (norms, tolerances, H-norm, stop) on the
+// device in the same launch.  Sums are taken in a fixed order whatever the arrival order: bitwise reproducible.
+// (W, S): kTailTile x kTailSlots = 128 x 4, one diagonal tile of the x-solve per workgroup, everywhere but behind the
+// packed lower-triangle x-solve.  There a workgroup's gather is W columns of every partial row, fetched from beyond
+// the L2 (other XCDs wrote them one launch earlier); at n = 10000 that is 79 workgroups of 80 KB each, on 79 of 256
+// compute units.  kTailTileWide x kTailSlotsWide = 64 x 8 halves what a compute unit takes in: dev/tail_bench.hip
+// measures the gather's cost over the same kernel on one row at 1.2 us for 128 x 4, 0.9 for 64 x 8, 0.7 for 32 x 16 and
+// 0.5 for 16 x 32, and the whole kernel 1.1 us shorter at 64 x 8 and 32 x 16 alike (16 x 32 gives 0.1 back); the
+// smaller of the two grids is built (EXPERIMENTS.md, "Lasso tail: the grid of the partial-row gather").
+constexpr int kTailBlock = 512;
 constexpr int kTailTile = 128;
-constexpr int kTailSlots = 4;                       // threads per element: each sums a quarter of the partial rows
-constexpr int kTailBlock = kTailTile * kTailSlots;  // 512 threads
-constexpr int kTailRows = 24;                       // partial rows a thread loads in one round
+constexpr int kTailSlots = kTailBlock / kTailTile;          // threads per element: each sums a quarter of the partial rows
+constexpr int kTailTileWide = 64;                           // behind the packed x-solve (tail_wide)
+constexpr int kTailSlotsWide = kTailBlock / kTailTileWide;
+constexpr int kTailXTile = 128;                             // the x-solve's tile: partial row p belongs to tile p
+// partial rows a thread loads in one round: 24 at four slots, and as many loads per element with more of them
+template <int S>
+constexpr int kTailRows = 96 / S;
 
+// the wide grid serves the gather behind the packed lower-triangle x-solve alone (the form dev/tail_bench.hip measured),
+// while its workgroups' block partials fit the part array
+static bool tail_wide(const ProxArgs& a) {
+  return a.ax_t && !a.ax_tri && ceil_div(a.len, kTailTileWide) <= kMaxPartBlocks;
+}
+
+template <int S>
 __device__ __forceinline__ double tail_gather(const ProxArgs& a, int64_t i, int32_t p0, int32_t p1) {
   // unified partial row p of element i (diagonal tile d = i / 128): p <= d -> axsrc[p] (N-part), else ax_t[p - 1]
   // (one-block triangular solves, ax_tri: the caller's p counts from the diagonal tile, rows d + p of ax_t)
-  const int32_t d = static_cast<int32_t>(i / kTailTile);
+  const int32_t d = static_cast<int32_t>(i / kTailXTile);
   double s = 0.0;
-  for (int32_t p = p0; p < p1; p += kTailRows) {
-    double v[kTailRows];
+  for (int32_t p = p0; p < p1; p += kTailRows<S>) {
+    double v[kTailRows<S>];
 #pragma unroll
-    for (int k = 0; k < kTailRows; ++k) {
+    for (int k = 0; k < kTailRows<S>; ++k) {
       const int32_t q = (p + k < p1) ? p + k : p1 - 1;
       const double* src = a.ax_tri ? a.ax_t + static_cast<int64_t>(d + q) * a.axld
                           : (!a.ax_t || q <= d) ? a.axsrc + static_cast<int64_t>(q) * a.axld
@@ -366,40 +384,57 @@ __device__ __forceinline__ double tail_gather(const ProxArgs& a, int64_t i, int3
       v[k] = src[i];
     }
 #pragma unroll
-    for (int k = 0; k < kTailRows; ++k)
+    for (int k = 0; k < kTailRows<S>; ++k)
       if (p + k < p1) s += v[k];
   }
   return s;
 }
 
-// this slot's share of the partial rows of element ic, whose diagonal tile is d: naxpart + 1 rows after the lower-triangle
-// x-solve (N-part rows up to the diagonal tile, T-part rows beyond), naxpart - d rows after the one-block triangular
-// solves, naxpart chunk rows of a column-chunked GEMV otherwise -- split into four quarters
+// share `slot` of S of the partial rows of element ic, whose diagonal tile (of the x-solve: 128 elements) is d:
+// naxpart + 1 rows after the lower-triangle x-solve (N-part rows up to the diagonal tile, T-part rows beyond),
+// naxpart - d rows after the one-block triangular solves, naxpart chunk rows of a column-chunked GEMV otherwise -- split
+// into S runs of ceil(P / S) consecutive rows, each summed in row order
+template <int S>
 __device__ __forceinline__ double tail_ax_share(const ProxArgs& a, int64_t ic, int32_t d, int slot) {
   const int32_t P = a.ax_tri ? a.naxpart - d : (a.ax_t ? a.naxpart + 1 : a.naxpart);
-  const int32_t q = (P + kTailSlots - 1) / kTailSlots;
+  const int32_t q = (P + S - 1) / S;
   const int32_t p0 = slot * q, p1 = (p0 + q < P) ? p0 + q : P;
-  return p0 < P ? tail_gather(a, ic, p0, p1) : 0.0;
+  return p0 < P ? tail_gather<S>(a, ic, p0, p1) : 0.0;
 }
 
-// The end of a one-launch tail kernel (the caller returns behind it).  Block partials of the two waves that hold
+// The shares of a workgroup of W elements x S slots meet in LDS; the slot-0 thread of element e gets their sum in slot
+// order, ((s0 + s1) + s2) + ... (the other threads' return value means nothing).  One barrier inside.
+template <int W, int S>
+__device__ __forceinline__ double tail_fold(double share, int e, int slot, double (*shares)[W]) {
+  if (slot > 0) shares[slot - 1][e] = share;
+  __syncthreads();
+  double ax = share;
+  if (slot == 0) {
+#pragma unroll
+    for (int k = 1; k < S; ++k) ax += shares[k - 1][e];
+  }
+  return ax;
+}
+
+// The end of a one-launch tail kernel (the caller returns behind it).  Block partials of the EW waves that hold
 // elements; deferred, they are stored plainly and the next launch on the stream takes them after the kernel boundary.
 // Otherwise they are published write-through, the workgroup arrives on ctrl->arrive, and the LAST workgroup to arrive
 // resets the counter and runs the finalize logic on what every workgroup published.  The only cross-workgroup memory
 // ordering of the library.
+template <int EW>
 __device__ __forceinline__ void tail_publish_finalize(const double (&acc)[S_COUNT], double* part, const FinArgs& f,
                                                       Ctrl* __restrict__ ctrl, int32_t defer) {
-  __shared__ double sred[2][S_COUNT];
+  __shared__ double sred[EW][S_COUNT];
   __shared__ int32_t last;
-  if ((threadIdx.x >> 6) < 2) slot_wave_sums(acc, sred);
+  if ((threadIdx.x >> 6) < EW) slot_wave_sums(acc, sred);
   __syncthreads();
   if (defer) {
-    if (threadIdx.x < S_COUNT) part[threadIdx.x * kMaxPartBlocks + blockIdx.x] = slot_total<2>(sred, threadIdx.x);
+    if (threadIdx.x < S_COUNT) part[threadIdx.x * kMaxPartBlocks + blockIdx.x] = slot_total<EW>(sred, threadIdx.x);
     return;
   }
   if (threadIdx.x < S_COUNT) {
     const int s = threadIdx.x;
-    __hip_atomic_store(part + s * kMaxPartBlocks + blockIdx.x, slot_total<2>(sred, s), __ATOMIC_RELAXED,
+    __hip_atomic_store(part + s * kMaxPartBlocks + blockIdx.x, slot_total<EW>(sred, s), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains: the element stores as well
@@ -418,18 +453,19 @@ __device__ __forceinline__ void tail_publish_finalize(const double (&acc)[S_COUN
 // defer = 1: the finalize logic is NOT run here; the block partials are stored plainly and the next launch on the
 // stream (the x-solve of the next iteration, or a stand-alone finalize) takes them after the kernel boundary.
 // Loss: as prox_kernel's.
-template <bool LOGI, class... Loss>
+template <int W, int S, bool LOGI, class... Loss>
 __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArgs f, Ctrl* __restrict__ ctrl,
                                                               int32_t defer, Loss... la) {
+  static_assert(W * S == kTailBlock && kTailXTile % W == 0, "a tile of the tail lies inside one tile of the x-solve");
   constexpr bool LOSS = sizeof...(Loss) != 0;
   const int32_t stop = ctrl->stop;
   const int64_t it = ctrl->iter;
   const double aprev = ctrl->acurr;
-  // (the stop test sits below the loads: they do not depend on it, and in front of them it costs this 9 us kernel one
-  // more memory round trip)
-  __shared__ double quarter[kTailSlots - 1][kTailTile];
-  const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kTailTile + e;
+  // (the stop test sits below the loads: they do not depend on it, and in front of them it costs this kernel one more
+  // memory round trip)
+  __shared__ double shares[S - 1][W];
+  const int e = threadIdx.x & (W - 1), slot = threadIdx.x / W;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * W + e;
   const int64_t ic = i < a.len ? i : a.len - 1;
   ProxIn in{};
   double wi = 1.0;
@@ -437,11 +473,10 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
     in = prox_load(a, ic);  // in flight together with the partial rows
     if constexpr (LOSS) wi = loss_weight(loss_of(la...), a.z, ic);
   }
-  // (kTailTile = the x-solve's tile: one diagonal tile per workgroup)
-  const double ax = tail_ax_share(a, ic, static_cast<int32_t>(blockIdx.x), slot);
+  // (the workgroup's elements lie in one diagonal tile of the x-solve: d is uniform)
+  const double share = tail_ax_share<S>(a, ic, static_cast<int32_t>(i / kTailXTile), slot);
   if (stop) return;  // (uniform; nothing has been stored yet)
-  if (slot > 0) quarter[slot - 1][e] = ax;
-  __syncthreads();
+  const double ax = tail_fold<W, S>(share, e, slot, shares);
   double acc[S_COUNT];
 #pragma unroll
   for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
@@ -452,19 +487,18 @@ __global__ __launch_bounds__(kTailBlock) void prox_fin_kernel(ProxArgs a, FinArg
       kcoef = (aprev - 1.0) / acn;
     }
     if constexpr (LOSS) {
-      const double axs = ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e];
-      loss_form_z<LOGI>(a, loss_of(la...), wi, axs, in, acc);
-      prox_apply<false>(a, i, axs, it, kcoef, in, acc);
+      loss_form_z<LOGI>(a, loss_of(la...), wi, ax, in, acc);
+      prox_apply<false>(a, i, ax, it, kcoef, in, acc);
     } else {
-      prox_apply<LOGI>(a, i, ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e], it, kcoef, in, acc);
+      prox_apply<LOGI>(a, i, ax, it, kcoef, in, acc);
     }
   }
-  tail_publish_finalize(acc, a.part, f, ctrl, defer);
+  tail_publish_finalize<(W + kWave - 1) / kWave>(acc, a.part, f, ctrl, defer);
 }
 
 FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
   FinArgs ff = f;
-  ff.nblk = static_cast<int32_t>(ceil_div(a.len, kTailTile));
+  ff.nblk = static_cast<int32_t>(ceil_div(a.len, tail_wide(a) ? kTailTileWide : kTailTile));
   // nothing but the block partials (and, for A = D, the x of this iteration) feeds the finalize logic -- and objective
   // partials an earlier launch of the iteration wrote when the caller passes them (covariance selection: -log det X)
   ff.g = nullptr;
@@ -473,24 +507,37 @@ FinArgs prox_fin_args(const ProxArgs& a, const FinArgs& f) {
   return ff;
 }
 
+template <int W, int S>
 __global__ void penalty_prox_fin_kernel(ProxArgs a, FinArgs f, PenaltyArgs pen, Ctrl* __restrict__ ctrl, int32_t defer,
                                         int32_t want_objz);  // (below, behind the grouped tail)
 
 void launch_prox_fin(const ProxArgs& args, const FinArgs& f, Ctrl* ctrl, int* nblk_out, hipStream_t stream,
                      bool defer, const ProxFamily* fam) {
-  const int64_t blocks = ceil_div(args.len, kTailTile);
-  *nblk_out = static_cast<int>(blocks);
+  // (the operand preparation below leaves ax_t, ax_tri and len alone: prox_fin_args sees the same grid)
+  const bool wide = tail_wide(args);
+  const dim3 grid(static_cast<unsigned>(ceil_div(args.len, wide ? kTailTileWide : kTailTile)));
+  *nblk_out = static_cast<int>(grid.x);
   if (fam && fam->kind == FAM_PENALTY) {  // the ungrouped penalty: a kernel of its own, older than the pack
     int32_t want_objz = 0;
     const ProxArgs a = register_z_operands(args, false, &want_objz);
-    hipLaunchKernelGGL(penalty_prox_fin_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a,
-                       prox_fin_args(a, f), fam->pen, ctrl, defer ? 1 : 0, want_objz);
+    const FinArgs ff = prox_fin_args(a, f);
+    if (wide)
+      hipLaunchKernelGGL((penalty_prox_fin_kernel<kTailTileWide, kTailSlotsWide>), grid, dim3(kTailBlock), 0, stream, a,
+                         ff, fam->pen, ctrl, defer ? 1 : 0, want_objz);
+    else
+      hipLaunchKernelGGL((penalty_prox_fin_kernel<kTailTile, kTailSlots>), grid, dim3(kTailBlock), 0, stream, a, ff,
+                         fam->pen, ctrl, defer ? 1 : 0, want_objz);
     return;
   }
   with_prox_family<FAM_LOSS, FAM_COST>(args, fam, [&](auto logi, const ProxArgs& a, const auto&... fa) {
-    hipLaunchKernelGGL((prox_fin_kernel<decltype(logi)::value, std::decay_t<decltype(fa)>...>),
-                       dim3(static_cast<unsigned>(blocks)), dim3(kTailBlock), 0, stream, a, prox_fin_args(a, f), ctrl,
-                       defer ? 1 : 0, fa...);
+    constexpr bool LOGI = decltype(logi)::value;
+    const FinArgs ff = prox_fin_args(a, f);
+    if (wide)
+      hipLaunchKernelGGL((prox_fin_kernel<kTailTileWide, kTailSlotsWide, LOGI, std::decay_t<decltype(fa)>...>), grid,
+                         dim3(kTailBlock), 0, stream, a, ff, ctrl, defer ? 1 : 0, fa...);
+    else
+      hipLaunchKernelGGL((prox_fin_kernel<kTailTile, kTailSlots, LOGI, std::decay_t<decltype(fa)>...>), grid,
+                         dim3(kTailBlock), 0, stream, a, ff, ctrl, defer ? 1 : 0, fa...);
   });
 }
 
@@ -532,20 +579,35 @@ void launch_svm_cost_prox(const double* v, const double* ell, int64_t n, const S
 // applies the scale and runs the fused element update with the finished z in ProxIn::zg_i (PROX_GIVEN from a register).
 // With one chunk -- every workgroup of a plan at the starting budget whose groups fit one tile -- the second pass
 // reuses the registers of the first; longer ranges gather again (the same loads in the same order: the same bits).
-// Element i sums its partial rows exactly as prox_fin_kernel does (split into four quarters of its own tile's count).
+// Element i sums its partial rows exactly as prox_fin_kernel does with S slots: the same S shares (tail_ax_share), added
+// in the same order (tail_fold's).  The chunk stays 128 elements x 4 threads whatever S is: thread `slot` of an element
+// takes the S / 4 consecutive shares from slot * S / 4 on, one after the other.
+template <int S>
 __device__ __forceinline__ double group_ax(const ProxArgs& a, int64_t ic, int slot, int e,
-                                           double (*quarter)[kTailTile]) {
-  const double ax = tail_ax_share(a, ic, static_cast<int32_t>(ic / kTailTile), slot);
-  __syncthreads();  // (the previous chunk's quarters have been read)
-  if (slot > 0) quarter[slot - 1][e] = ax;
+                                           double (*shares)[kGroupTile]) {
+  constexpr int PER = S / kTailSlots;
+  static_assert(PER * kTailSlots == S, "every thread of an element takes the same number of shares");
+  const int32_t d = static_cast<int32_t>(ic / kTailXTile);
+  double sh[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) sh[k] = tail_ax_share<S>(a, ic, d, slot * PER + k);
+  __syncthreads();  // (the previous chunk's shares have been read)
+#pragma unroll
+  for (int k = 0; k < PER; ++k)
+    if (slot * PER + k > 0) shares[slot * PER + k - 1][e] = sh[k];
   __syncthreads();
-  return ((ax + quarter[0][e]) + quarter[1][e]) + quarter[2][e];  // (meaningful in slot 0)
+  double ax = sh[0];
+  if (slot == 0) {
+#pragma unroll
+    for (int k = 1; k < S; ++k) ax += shares[k - 1][e];
+  }
+  return ax;  // (meaningful in slot 0)
 }
 
 // PEN: the instantiation with the elementwise stage of the penalty family in front of the squares (penalty_device.h:
 // e_i = soft(v_i, tau*w_i) or its positive part), kappa behind the scale and the whole of g(z) in S_OBJZ; the plain
 // group lasso compiles without any of it and never reads pen.
-template <bool PEN>
+template <bool PEN, int S>
 __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, FinArgs f, GroupPlan gp,
                                                                     Ctrl* __restrict__ ctrl, int32_t defer,
                                                                     int32_t want_objz, PenaltyArgs pen) {
@@ -555,12 +617,12 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
   const int64_t E0 = gp.wg_e[blockIdx.x], E1 = gp.wg_e[blockIdx.x + 1];
   const int32_t g0 = gp.wg_g[blockIdx.x], ng = gp.wg_g[blockIdx.x + 1] - g0;
   if (stop) return;  // (uniform; the plan words above arrive in the same round trip as the control words)
-  __shared__ double quarter[kTailSlots - 1][kTailTile];
+  __shared__ double shares[S - 1][kGroupTile];
   __shared__ double sq[kGroupTile];
   __shared__ double gacc[kGroupMaxPerWg];
-  static_assert(kGroupTile == kTailTile, "one chunk of a group plan is one tile of the one-launch tail");
-  const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
-  const int32_t nch = static_cast<int32_t>((E1 - E0 + kTailTile - 1) / kTailTile);
+  static_assert(kGroupTile * kTailSlots == kTailBlock, "a chunk of a group plan is 128 elements x 4 threads");
+  const int e = threadIdx.x & (kGroupTile - 1), slot = threadIdx.x >> 7;
+  const int32_t nch = static_cast<int32_t>((E1 - E0 + kGroupTile - 1) / kGroupTile);
   double acc[S_COUNT];
 #pragma unroll
   for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
@@ -569,7 +631,7 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
   int32_t gi = 0;
   int64_t i = E0 + e;
   for (int32_t c = 0; c < nch; ++c) {  // ---- pass 1: v (PEN: e) and the norms of the groups
-    const int64_t cs = E0 + static_cast<int64_t>(c) * kTailTile, ce = (cs + kTailTile < E1) ? cs + kTailTile : E1;
+    const int64_t cs = E0 + static_cast<int64_t>(c) * kGroupTile, ce = (cs + kGroupTile < E1) ? cs + kGroupTile : E1;
     i = cs + e;
     const int64_t ic = i < E1 ? i : E1 - 1;
     if (slot == 0) {
@@ -577,7 +639,7 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
       gi = gp.gid[ic] - g0;
       if constexpr (PEN) wi = penalty_weight(pen, ic);
     }
-    ax = group_ax(a, ic, slot, e, quarter);
+    ax = group_ax<S>(a, ic, slot, e, shares);
     if (slot == 0) {
       double v = group_prox_v(a, ax, in);
       if constexpr (PEN) v = penalty_elem(v, pen.tau * wi, pen.nonneg);
@@ -599,14 +661,14 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
   }
   for (int32_t c = 0; c < nch; ++c) {  // ---- pass 2: z = scale_g * v and the rest of the element update
     if (nch > 1) {
-      i = E0 + static_cast<int64_t>(c) * kTailTile + e;
+      i = E0 + static_cast<int64_t>(c) * kGroupTile + e;
       const int64_t ic = i < E1 ? i : E1 - 1;
       if (slot == 0) {
         in = prox_load(a, ic);
         gi = gp.gid[ic] - g0;
         if constexpr (PEN) wi = penalty_weight(pen, ic);
       }
-      ax = group_ax(a, ic, slot, e, quarter);
+      ax = group_ax<S>(a, ic, slot, e, shares);
     }
     if (slot == 0 && i < E1) {
       if constexpr (PEN) {
@@ -619,7 +681,7 @@ __global__ __launch_bounds__(kTailBlock) void group_prox_fin_kernel(ProxArgs a, 
       prox_apply<false>(a, i, ax, it, kcoef, in, acc);
     }
   }
-  tail_publish_finalize(acc, a.part, f, ctrl, defer);  // (the two waves that hold elements also hold the group sums)
+  tail_publish_finalize<2>(acc, a.part, f, ctrl, defer);  // (the two waves that hold elements also hold the group sums)
 }
 
 void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPlan& gp, Ctrl* ctrl, int* nblk_out,
@@ -631,12 +693,15 @@ void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPl
   *nblk_out = gp.nwg;
   FinArgs ff = prox_fin_args(a, f);
   ff.nblk = gp.nwg;
-  if (fam && fam->kind == FAM_PENALTY)
-    hipLaunchKernelGGL(group_prox_fin_kernel<true>, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a, ff,
-                       gp, ctrl, defer ? 1 : 0, want_objz, fam->pen);
-  else
-    hipLaunchKernelGGL(group_prox_fin_kernel<false>, dim3(static_cast<unsigned>(gp.nwg)), dim3(kTailBlock), 0, stream, a,
-                       ff, gp, ctrl, defer ? 1 : 0, want_objz, PenaltyArgs{});
+  const dim3 grid(static_cast<unsigned>(gp.nwg));
+  const bool pen = fam && fam->kind == FAM_PENALTY;
+  const PenaltyArgs pa = pen ? fam->pen : PenaltyArgs{};
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kTailBlock), 0, stream, a, ff, gp, ctrl, defer ? 1 : 0, want_objz, pa);
+  };
+  // the slots of the plain tail on the same operands: the same shares of the partial rows in the same order
+  if (tail_wide(a)) pen ? launch(group_prox_fin_kernel<true, kTailSlotsWide>) : launch(group_prox_fin_kernel<false, kTailSlotsWide>);
+  else pen ? launch(group_prox_fin_kernel<true, kTailSlots>) : launch(group_prox_fin_kernel<false, kTailSlots>);
 }
 
 // ---------------------------------------------------------------- the penalty family without groups
@@ -644,15 +709,17 @@ void launch_group_prox_fin(const ProxArgs& args, const FinArgs& f, const GroupPl
 // PROX_GIVEN; the weight is one more coalesced load of slot 0, in flight with the rest.  S_OBJZ takes the whole of g(z).
 // (As prox_fin_kernel's PenaltyArgs instantiation it has the same registers, LDS and occupancy but measured 0.05 us per
 // launch slower than this kernel, whose two runs differ by 0.02: EXPERIMENTS.md, "One dispatch of the families".)
+template <int W, int S>
 __global__ __launch_bounds__(kTailBlock) void penalty_prox_fin_kernel(ProxArgs a, FinArgs f, PenaltyArgs pen,
                                                                       Ctrl* __restrict__ ctrl, int32_t defer,
                                                                       int32_t want_objz) {
+  static_assert(W * S == kTailBlock && kTailXTile % W == 0, "a tile of the tail lies inside one tile of the x-solve");
   const int32_t stop = ctrl->stop;
   const int64_t it = ctrl->iter;
   const double aprev = ctrl->acurr;
-  __shared__ double quarter[kTailSlots - 1][kTailTile];
-  const int e = threadIdx.x & (kTailTile - 1), slot = threadIdx.x >> 7;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kTailTile + e;
+  __shared__ double shares[S - 1][W];
+  const int e = threadIdx.x & (W - 1), slot = threadIdx.x / W;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * W + e;
   const int64_t ic = i < a.len ? i : a.len - 1;
   ProxIn in{};
   double wi = 1.0;
@@ -660,10 +727,9 @@ __global__ __launch_bounds__(kTailBlock) void penalty_prox_fin_kernel(ProxArgs a
     in = prox_load(a, ic);  // in flight together with the partial rows
     wi = penalty_weight(pen, ic);
   }
-  const double axq = tail_ax_share(a, ic, static_cast<int32_t>(blockIdx.x), slot);
+  const double share = tail_ax_share<S>(a, ic, static_cast<int32_t>(i / kTailXTile), slot);
   if (stop) return;  // (uniform; nothing has been stored yet)
-  if (slot > 0) quarter[slot - 1][e] = axq;
-  __syncthreads();
+  const double ax = tail_fold<W, S>(share, e, slot, shares);
   double acc[S_COUNT];
 #pragma unroll
   for (int s = 0; s < S_COUNT; ++s) acc[s] = 0.0;
@@ -673,12 +739,11 @@ __global__ __launch_bounds__(kTailBlock) void penalty_prox_fin_kernel(ProxArgs a
       const double acn = 0.5 * (1.0 + sqrt(1.0 + 4.0 * aprev * aprev));
       kcoef = (aprev - 1.0) / acn;
     }
-    const double ax = ((axq + quarter[0][e]) + quarter[1][e]) + quarter[2][e];
     in.zg_i = pen.kappa * penalty_elem(group_prox_v(a, ax, in), pen.tau * wi, pen.nonneg);
     if (want_objz) acc[S_OBJZ] += penalty_obj_elem(pen, wi, in.zg_i);
     prox_apply<false>(a, i, ax, it, kcoef, in, acc);
   }
-  tail_publish_finalize(acc, a.part, f, ctrl, defer);
+  tail_publish_finalize<(W + kWave - 1) / kWave>(acc, a.part, f, ctrl, defer);
 }
 
 // out = prox_{g/rho}(v) without groups: the stand-alone operator (ops.hip)
