@@ -369,6 +369,8 @@ _SIGNATURES = {
     "admm_op_dct_cols": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp]),
     "admm_op_tv2d_rows": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_double, C.c_int32, _dp]),
     "admm_op_tv2d_xsolve": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_double, C.c_int32, _dp]),
+    "admm_op_consensus_tail": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, _dp, _dp,
+                                         _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
     "admm_comm_unique_id": (C.c_int, [C.c_char_p]),
     "admm_comm_init": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "admm_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -727,4 +727,141 @@ int admm_op_tv2d_xsolve(const double* b, int64_t H, int64_t W, double rho, int32
   return get_image(x, dx, H, W);
 }
 
+int admm_op_consensus_tail(int32_t form, int64_t n, int32_t K, int32_t Ntot, double rho, double lambda,
+                           const double* rows, double* X, double* U, const double* Dts, double* xave, double* ubar,
+                           const double* remote, int32_t with_q, double* Y, double* sums, double* z, double* xaveprev,
+                           double* slots, double* q) {
+  if (form < 0 || form > 2 || n < 1 || K < 1 || Ntot < K || !finite_pos(rho) || !finite_nonneg(lambda) ||
+      (with_q != 0 && with_q != 1))
+    return fail(ADMM_E_INVALID, "consensus_tail: bad argument (form 0..2, n >= 1, 1 <= K <= Ntot, rho finite and > 0, "
+                                "lambda finite and >= 0, with_q 0 or 1)");
+  if (!X || !U || !Dts || !xave || !ubar || !Y || !sums || !z || !xaveprev || !slots || (form != 0 && !rows) ||
+      (with_q && !q))
+    return fail(ADMM_E_INVALID, "consensus_tail: null pointer");
+  if (static_cast<int64_t>(K) > (int64_t{1} << 40) / n)
+    return fail(ADMM_E_INVALID, "consensus_tail: K * n is too large");
+  const int64_t ldn = round_up(n, 2);  // the engine's cldn
+  ConsArgs ca{};
+  ca.n = n;
+  ca.ldn = ldn;
+  ca.K = K;
+  ca.Ntot = Ntot;
+  ca.rho = rho;
+  ca.lambda = lambda;
+  if (form == 2 && (!cons_gather_update_ok(ca) || remote || with_q))
+    return fail(ADMM_E_INVALID, "consensus_tail: the one-launch tail takes at most 16 slices, no remote share and no q");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  const SymvPlan plan = symv_plan(n);
+  const int32_t P = plan.ntile + 1;
+  const size_t pstride = plan.npart_elems(), vec = static_cast<size_t>(K) * ldn;
+  const int nqmax = static_cast<int>(ceil_div(n, 128) > kMaxPartBlocks ? ceil_div(n, 128) : kMaxPartBlocks);
+  double *dX, *dU, *dDts, *dY, *dsums, *dz, *dxave, *dxprev, *dubar, *dpart, *dqpart, *dslots, *npart = nullptr,
+         *tpart = nullptr;
+  Ctrl* ctrl;
+  ADMM_TRY(zeroed_ctrl(sc, &ctrl));
+  // [K][ldn] and one guard row behind the last slice, all-ones bytes: the padding column of an odd n and the guard row
+  // must come back as they were (below)
+  for (double** p : {&dX, &dU, &dDts, &dY}) {
+    ADMM_TRY(sc.alloc(p, vec + ldn));
+    ADMM_HIP_TRY(hipMemset(*p, 0xFF, sizeof(double) * (vec + ldn)));
+  }
+  for (double** p : {&dz, &dxave, &dxprev, &dubar}) {
+    ADMM_TRY(sc.alloc(p, ldn));
+    ADMM_HIP_TRY(hipMemset(*p, 0xFF, sizeof(double) * ldn));
+  }
+  ADMM_TRY(sc.alloc(&dsums, 2 * ldn + 2));
+  ADMM_TRY(sc.alloc(&dpart, static_cast<size_t>(S_COUNT) * kMaxPartBlocks));
+  ADMM_TRY(sc.alloc(&dqpart, nqmax));
+  ADMM_TRY(sc.alloc(&dslots, 5));
+  ADMM_HIP_TRY(hipMemset(dsums, 0xFF, sizeof(double) * (2 * ldn + 2)));
+  ADMM_HIP_TRY(hipMemset(dpart, 0xFF, sizeof(double) * S_COUNT * kMaxPartBlocks));  // a block past nblk reads as NaN
+  ADMM_HIP_TRY(hipMemset(dqpart, 0xFF, sizeof(double) * nqmax));
+  const size_t hrow = n * sizeof(double), drow = ldn * sizeof(double);
+  if (form == 0) ADMM_HIP_TRY(hipMemcpy2D(dX, drow, X, hrow, hrow, K, hipMemcpyHostToDevice));
+  ADMM_HIP_TRY(hipMemcpy2D(dU, drow, U, hrow, hrow, K, hipMemcpyHostToDevice));
+  ADMM_HIP_TRY(hipMemcpy2D(dDts, drow, Dts, hrow, hrow, K, hipMemcpyHostToDevice));
+  ADMM_HIP_TRY(hipMemcpy(dxave, xave, hrow, hipMemcpyHostToDevice));
+  ADMM_HIP_TRY(hipMemcpy(dubar, ubar, hrow, hipMemcpyHostToDevice));
+  if (form != 0) {
+    // logical row p of element i where the lower-triangle x-solve leaves it: npart row p for p <= i / 128 (the tile
+    // row of i), tpart row p - 1 otherwise; every other double of both buffers is the all-ones NaN
+    // (one more row of it in front of either buffer: a T-part row index of -1 stays inside the allocation)
+    const size_t lead = static_cast<size_t>(plan.ldp);
+    std::vector<double> hn(lead + pstride * K), ht(lead + pstride * K);
+    std::memset(hn.data(), 0xFF, sizeof(double) * hn.size());
+    std::memset(ht.data(), 0xFF, sizeof(double) * ht.size());
+    for (int32_t k = 0; k < K; ++k)
+      for (int32_t p = 0; p < P; ++p) {
+        const double* src = rows + (static_cast<size_t>(k) * P + p) * n;
+        double* drn = hn.data() + lead + pstride * k + static_cast<size_t>(p) * plan.ldp;
+        double* drt = ht.data() + lead + pstride * k + static_cast<size_t>(p > 0 ? p - 1 : 0) * plan.ldp;
+        for (int64_t i = 0; i < n; ++i) {
+          if (p <= i / 128) drn[i] = src[i];
+          else drt[i] = src[i];
+        }
+      }
+    ADMM_TRY(sc.put(&npart, static_cast<const double*>(hn.data()), hn.size()));
+    ADMM_TRY(sc.put(&tpart, static_cast<const double*>(ht.data()), ht.size()));
+    npart += lead;
+    tpart += lead;
+  }
+  ca.sums = dsums;
+  ca.X = dX;
+  ca.U = dU;
+  ca.zc = dz;
+  ca.xave = dxave;
+  ca.xaveprev = dxprev;
+  ca.ubar = dubar;
+  ca.part = dpart;
+  ca.Dts = dDts;
+  ca.Y = dY;
+  int nblk = 0;
+  if (form == 2) {
+    launch_cons_gather_update(ca, npart, tpart, static_cast<int64_t>(pstride), plan.ldp, plan.ntile, ctrl, &nblk, nullptr);
+  } else {
+    const double* center = with_q ? dxave : nullptr;  // the sharded run: q about the mean every rank already holds
+    double* qp = with_q ? dqpart : nullptr;
+    const int nq = form == 1 ? launch_cons_gather_sum(n, ldn, K, npart, tpart, static_cast<int64_t>(pstride), plan.ldp,
+                                                      plan.ntile, dX, dU, dsums, center, qp, ctrl, nullptr)
+                             : launch_cons_sum(n, ldn, K, dX, dU, dsums, center, qp, ctrl, nullptr);
+    if (with_q) launch_pack_sum(dqpart, nq, dsums + 2 * ldn, ctrl, nullptr);
+    if (remote) {  // the other ranks' share of the all-reduce: test harness, not a kernel under test
+      std::vector<double> hs(static_cast<size_t>(2 * ldn));
+      ADMM_HIP_TRY(hipDeviceSynchronize());
+      ADMM_HIP_TRY(hipMemcpy(hs.data(), dsums, sizeof(double) * 2 * ldn, hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < n; ++i) {
+        hs[i] += remote[i];
+        hs[ldn + i] += remote[n + i];
+      }
+      ADMM_HIP_TRY(hipMemcpy(dsums, hs.data(), sizeof(double) * 2 * ldn, hipMemcpyHostToDevice));
+    }
+    launch_cons_update(ca, ctrl, &nblk, nullptr);
+  }
+  static const int kSlots[5] = {S_R2, S_AX2, S_G2, S_U2, S_DU2};
+  for (int j = 0; j < 5; ++j)  // the nblk block partials of a slot, where the finalize step reads them
+    launch_pack_sum(dpart + static_cast<size_t>(kSlots[j]) * kMaxPartBlocks, nblk, dslots + j, ctrl, nullptr);
+  ADMM_HIP_TRY(hipDeviceSynchronize());
+  {  // nothing stored past the n elements of a slice
+    std::vector<uint64_t> h(vec + ldn);
+    for (const double* d : {dX, dU, dY}) {
+      ADMM_HIP_TRY(hipMemcpy(h.data(), d, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+      for (size_t j = 0; j < h.size(); ++j)
+        if ((j >= vec || static_cast<int64_t>(j % ldn) >= n) && h[j] != ~uint64_t{0})
+          return fail(ADMM_E_NUMERIC, "consensus_tail: a kernel wrote outside the n elements of a slice");
+    }
+  }
+  ADMM_HIP_TRY(hipMemcpy2D(X, hrow, dX, drow, hrow, K, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy2D(U, hrow, dU, drow, hrow, K, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy2D(Y, hrow, dY, drow, hrow, K, hipMemcpyDeviceToHost));
+  if (form != 2) ADMM_HIP_TRY(hipMemcpy2D(sums, hrow, dsums, drow, hrow, 2, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(z, dz, hrow, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(xave, dxave, hrow, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(xaveprev, dxprev, hrow, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(ubar, dubar, hrow, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(slots, dslots, sizeof(double) * 5, hipMemcpyDeviceToHost));
+  if (with_q) ADMM_HIP_TRY(hipMemcpy(q, dsums + 2 * ldn, sizeof(double), hipMemcpyDeviceToHost));
+  return ADMM_OK;
+}
+
 }  // extern "C"

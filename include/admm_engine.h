@@ -717,6 +717,32 @@ int admm_op_llt_apply(const double* L, int64_t n, int64_t ldL, const double* x, 
 int admm_op_dct_cols(const double* img, int64_t H, int64_t W, int32_t inverse, double* out);
 int admm_op_tv2d_rows(const double* src, int64_t H, int64_t W, double rho, int32_t form, double* out);
 int admm_op_tv2d_xsolve(const double* b, int64_t H, int64_t W, double rho, int32_t form, double* x);
+/* ONE consensus-lasso iteration tail (getProxOps.m:1281-1343: the slice sums, the means, z by the soft threshold
+ * lambda/(rho*Ntot), u_k += x_k - z, the next right-hand sides y_k = rho*(z - u_k) + D_k's_k, the residual sums) on
+ * host arrays, through the launchers and in the launch sequence of the loop.  form selects the sequence:
+ *   0: cons_sum + cons_update                 x_k given in X
+ *   1: cons_gather_sum + cons_update          x_k assembled from the partial rows, X is output only
+ *   2: cons_gather_update (one launch)        the same; K <= 16, remote == NULL and with_q == 0, else ADMM_E_INVALID
+ * rows (forms 1, 2; ignored by form 0): the logical partial rows [K][P][n], P = ceil(n / 128) + 1, x_k[i] = sum_p
+ * rows[k][p][i].  They reach the device where the lower-triangle x-solve leaves them: row p of element i in row p of
+ * the N-part when p <= i / 128 and in row p - 1 of the T-part otherwise, with the row and slice strides of the
+ * engine's plan for order n; every other double of both buffers, padding columns included, is the all-ones NaN, so a
+ * wrong source row reaches the output as NaN.
+ * X, U, Dts, Y: [K][n] (slice k at + k*n); U, xave and ubar (n each) are read and updated in place; z and xaveprev
+ * receive n values.  K local slices of Ntot >= K in all.  remote (optional, [2][n]): the other ranks' sum of x_k and
+ * of u_k, added to the sums on the host between the two launches as the all-reduce of a row-sharded run would.
+ * with_q = 1 (forms 0, 1): the first launch also forms q = sum_k ||x_k - xave||^2 about the xave that came IN, folded
+ * as the sharded run folds it, and *q receives it.
+ * sums: [2][n], sum_k x_k and sum_k u_k as the update kernel read them (remote included); form 2 never stores them and
+ * leaves the buffer untouched.  slots[5]: the totals of S_R2 = sum_k ||x_k - xave||^2, S_AX2 = ||xave||^2, S_G2 =
+ * ||xave - xaveprev||^2, S_U2 = ||ubar||^2 and S_DU2 = ||ubar - ubar_in||^2 over the workgroup partials the finalize
+ * step reads.  The device X, U and Y carry the padding column of an odd n and one guard row behind the last slice, and
+ * the partial-row buffers one guard row in front: a kernel that stores past the n elements of a slice gives
+ * ADMM_E_NUMERIC.  Bad arguments are ADMM_E_INVALID before any device call. */
+int admm_op_consensus_tail(int32_t form, int64_t n, int32_t K, int32_t Ntot, double rho, double lambda,
+                           const double* rows, double* X, double* U, const double* Dts, double* xave, double* ubar,
+                           const double* remote, int32_t with_q, double* Y, double* sums, double* z, double* xaveprev,
+                           double* slots, double* q);
 
 /* ---- multi-GPU (one process per GPU; rows of D sharded; RCCL over xGMI) --------
  * unique id is created on rank 0 and handed to the other ranks by the host

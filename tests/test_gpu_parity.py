@@ -789,6 +789,20 @@ def test_consensus_lasso_partial_row_gather_path(gpu):
     assert got["engine_info"]["xsolve_used"] == "inverse"
 
 
+@pytest.mark.parametrize("workers,rows,cols", [(5, 1541, 1537), (17, 1540, 1536)])
+def test_consensus_lasso_partial_rows_through_both_tails(gpu, workers, rows, cols):
+    """The real partial rows of the batched x-solve into the one-launch tail at a slice count that leaves slots idle
+    (5 slices: 3 row ranges each, one slot unused, a ragged last 64-tile), and into the two-launch form that takes over
+    beyond 16 slices (17); a few iterations against the N-slice oracle.  tests/test_gpu_consensus_tail.py pins the same
+    kernels element by element."""
+    p = gpu.synth.lasso_problem(11, workers * rows, cols)
+    o = dict(objevals=1, parallel="both", maxiters=4, domaxiters=1)
+    got = gpu.lasso(p["D"], p["s"], p["lam"], dict(o, workers=workers, xsolve="inverse"))
+    ref = S.lasso(p["D"], p["s"], p["lam"], dict(o, slices=0), workers=workers)
+    _compare(got, ref, keys=("xvals", "zvals", "uvals", "pnorm", "dnorm", "perr", "derr", "objevals", "Hnormsq"))
+    assert got["engine_info"]["xsolve_used"] == "inverse"
+
+
 @pytest.mark.parametrize("m,n,kind", [(257, 3, "hinge"), (1000, 130, "hinge"), (1000, 130, "01"), (6000, 400, "hinge"),
                                       (900, 513, "hinge"), (1500, 400, "deficient"), (640, 96, "dplus")])
 def test_unwrapped_two_launch_iteration_matches_the_generic_path(gpu, monkeypatch, m, n, kind):
