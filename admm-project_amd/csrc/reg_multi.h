@@ -1,6 +1,6 @@
 // reg_multi.h -- argument blocks of the multi-fit robust-regression kernels (reg_multi.hip): K independent plain-ADMM
 // runs of the A = D iteration (admm.m:496-743 with B = -1, c = s_k) over ONE matrix D.  The x-solve and the per-fit
-// control record are svm_ovr.h's (ovr_xsolve_kernel, OvrRec).
+// control record are svm_ovr.h's (ovr_xsolve_kernel, MultiRec).
 #pragma once
 #include "svm_ovr.h"
 
@@ -24,8 +24,8 @@ struct RegmPassArgs {
   const double* par;    // K x 4: (a, b, epsilon, delta) of every fit
   const int32_t* kind;  // K values: 0 LAD family, 1 Huber family
   double* gpart;        // [workgroups][K][ldx] partial rows of D'((s + z) - u): the next x-update's right-hand side
-  double* part;         // [K][RM_COUNT][kOvrMaxWg] block partials of the residual sums
-  const OvrRec* rec;    // K
+  double* part;         // [K][RM_COUNT][kMultiMaxWg] block partials of the residual sums
+  const MultiRec* rec;    // K
   int32_t K, c0;        // fits c0 .. c0 + kRegmChunk - 1 belong to this launch
   int32_t ns;           // 1: every fit reads column 0 of S; K: fit k reads column k
   int32_t objevals;
@@ -40,7 +40,7 @@ struct RegmFinArgs {
   int64_t ldx, n, m;
   int32_t K, nwg;
   int32_t fin;          // 0: partial-row sums only (before the first iteration)
-  OvrRec* rec;
+  MultiRec* rec;
   double *pnorm, *perr, *objv;  // [K][hist_ld]
   int64_t hist_ld;
   double abstol, reltol;

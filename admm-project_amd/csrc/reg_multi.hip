@@ -10,7 +10,7 @@
 //                         fit (D x_k)_r, the family's z-prox in a register (loss_form_z), the fused element update
 //                         (prox_apply with PROX_GIVEN: the code every loop shares), and the block's contribution
 //                         D_r' t_r to the fit's next right-hand side g_k = D'((s_k + z_k) - u_k)
-//   regm_gsum_fin_kernel  sums the workgroups' partial rows of g_k in the fixed order of ovr_gsum_fin_kernel; one extra
+//   regm_gsum_fin_kernel  sums the workgroups' partial rows of g_k in the fixed order of multi_gsum_tile; one extra
 //                         workgroup per fit turns the block partials into pnorm, perr, the objective and the stop
 //                         decision (admm.m:612-658, 706-713)
 // The dual residual is not evaluated (two more transposed products per fit): a fit stops on pnorm < perr.
@@ -21,8 +21,8 @@
 #include <cmath>
 #include <vector>
 
-#include "engine_internal.h"
 #include "loss_device.h"
+#include "multi_host.h"
 #include "reg_multi.h"
 #include "wave_reduce.h"
 
@@ -192,68 +192,31 @@ __global__ __launch_bounds__(kRmWaves* kWave) void regm_pass_kernel(RegmPassArgs
 #pragma unroll
       for (int q = 0; q < RM_COUNT; ++q) {
         const double v = wave_sum(acc[s][slot_of[q]]);
-        if (lane == 0) a.part[(static_cast<int64_t>(a.c0 + c) * RM_COUNT + q) * kOvrMaxWg + blockIdx.x] = v;
+        if (lane == 0) a.part[(static_cast<int64_t>(a.c0 + c) * RM_COUNT + q) * kMultiMaxWg + blockIdx.x] = v;
       }
     }
   }
 }
 
-// blockIdx.y = fit.  blockIdx.x < tiles: g_k[64 columns] = sum over the workgroups' partial rows, in the order of
-// ovr_gsum_fin_kernel -- wave q takes rows q, q + 4, ... sixteen loads at a time, the four wave sums added in wave
-// order.  The extra workgroup (a.fin): the finalize logic of the fit's iteration -- admm.m:612-658, 706-713 as
+// blockIdx.y = fit.  blockIdx.x < tiles: g_k[64 columns] = sum over the workgroups' partial rows (multi_gsum_tile).
+// The extra workgroup (a.fin): the finalize logic of the fit's iteration -- admm.m:612-658, 706-713 as
 // oracle/admm_ref.py restates it, for plain ADMM with nodualerror = 1 and stopcond = 'standard'.
 __global__ __launch_bounds__(kBlock) void regm_gsum_fin_kernel(RegmFinArgs a) {
   const int fit = blockIdx.y;
-  OvrRec* rec = a.rec + fit;
+  MultiRec* rec = a.rec + fit;
   const int32_t stopped = rec->stop;
   const int32_t it = rec->iter;
   if (stopped) return;
-  __shared__ double sq[4][kOvrTile];
+  __shared__ double sq[4][kMultiTile];
   __shared__ double S[8];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int tiles = static_cast<int>((a.n + kOvrTile - 1) / kOvrTile);
+  const int tid = threadIdx.x;
+  const int tiles = static_cast<int>((a.n + kMultiTile - 1) / kMultiTile);
   if (static_cast<int>(blockIdx.x) < tiles) {
-    const int64_t j0 = static_cast<int64_t>(blockIdx.x) * kOvrTile;
-    const int64_t j = (j0 + lane < a.n) ? j0 + lane : a.n - 1;
-    const double* __restrict__ G = a.gpart + static_cast<int64_t>(fit) * a.ldx + j;
-    const int64_t rowstride = static_cast<int64_t>(a.K) * a.ldx;
-    double s = 0.0;
-    for (int32_t b0 = wid; b0 < a.nwg; b0 += 64) {
-      double v[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int32_t b = (b0 + 4 * k < a.nwg) ? b0 + 4 * k : a.nwg - 1;
-        v[k] = G[static_cast<int64_t>(b) * rowstride];
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) s += (b0 + 4 * k < a.nwg) ? v[k] : 0.0;
-    }
-    sq[wid][lane] = s;
-    __syncthreads();
-    if (wid == 0 && j0 + lane < a.n)
-      a.gsum[static_cast<int64_t>(fit) * a.ldx + j0 + lane] = ((sq[0][lane] + sq[1][lane]) + sq[2][lane]) + sq[3][lane];
+    multi_gsum_tile(a.gpart, a.gsum, fit, a.ldx, a.n, a.K, a.nwg, sq);
     return;
   }
-  // ---- finalize of fit `fit`: 32 lanes per slot stride over the block partials, then a fixed shuffle tree
-  {
-    const int slot = tid >> 5, sub = tid & 31;
-    double v = 0.0;
-    if (slot < RM_COUNT) {
-      const double* __restrict__ ps = a.part + (static_cast<int64_t>(fit) * RM_COUNT + slot) * kOvrMaxWg;
-      double wv[kOvrMaxWg / 32];
-#pragma unroll
-      for (int k = 0; k < kOvrMaxWg / 32; ++k) {
-        const int b = sub + 32 * k;
-        wv[k] = ps[b < a.nwg ? b : a.nwg - 1];
-      }
-#pragma unroll
-      for (int k = 0; k < kOvrMaxWg / 32; ++k)
-        if (sub + 32 * k < a.nwg) v += wv[k];
-    }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (sub == 0 && slot < 8) S[slot] = v;
-  }
+  // ---- finalize of fit `fit`
+  multi_slot_totals_unrolled(a.part, fit, RM_COUNT, a.nwg, S);
   __syncthreads();
   if (tid != 0) return;
   const int i1 = it + 1;  // 1-based iteration number (admm.m loop variable)
@@ -265,10 +228,7 @@ __global__ __launch_bounds__(kBlock) void regm_gsum_fin_kernel(RegmFinArgs a) {
   a.pnorm[h] = pn;
   a.perr[h] = pe;
   const bool stop = !a.domaxiters && pn < pe;  // admm.m:710-713, nodualerror
-  rec->iter = i1;
-  rec->steps = i1;
-  if (stop) rec->early = 1;
-  if (stop || i1 >= a.maxiters) rec->stop = 1;
+  multi_stop_tail(rec, stop, i1, a.maxiters);
 }
 
 // one workgroup per fit: the squares of the fit's response summed per thread in a strided order, per wave by wave_sum,
@@ -293,7 +253,7 @@ void launch_regm_pass(const RegmPassArgs& a, bool init, hipStream_t stream) {
 }
 
 void launch_regm_gsum_fin(const RegmFinArgs& a, hipStream_t stream) {
-  const unsigned tiles = static_cast<unsigned>(ceil_div(a.n, int64_t{kOvrTile}));
+  const unsigned tiles = static_cast<unsigned>(ceil_div(a.n, int64_t{kMultiTile}));
   hipLaunchKernelGGL(regm_gsum_fin_kernel, dim3(tiles + (a.fin ? 1u : 0u), static_cast<unsigned>(a.K)), dim3(kBlock), 0,
                      stream, a);
 }
@@ -305,44 +265,19 @@ void launch_regm_snorm(const double* S, int64_t ldz, int64_t m, int32_t K, int32
 }  // namespace admm
 
 // ---------------------------------------------------------------------------------------------------------- the object
-struct admm_reg_multi {
-  admm_engine* eng = nullptr;  // an ordinary ADMM_PROB_LAD engine: owns D and the factor of D'D; never run
-  hipStream_t stream = nullptr;  // = eng->stream
-  DevMem mem;
-  int device = 0;
-  int64_t m = 0, n = 0, ldx = 0, ldz = 0;
-  int32_t K = 0, ns = 1, nwg = 0;
-  const double* M = nullptr;  // the explicit n x n map (D'D)^-1 of the engine; null: triangular solves
-  int64_t ldM = 0;
-  double *X = nullptr, *Z = nullptr, *U = nullptr, *S = nullptr, *gpart = nullptr, *gsum = nullptr, *part = nullptr,
-         *xtmp = nullptr, *par = nullptr, *snorm = nullptr;
+struct admm_reg_multi : DenseMulti {  // eng: an ordinary ADMM_PROB_LAD engine
+  int32_t ns = 1;
+  double *S = nullptr, *par = nullptr, *snorm = nullptr;
   int32_t* kind = nullptr;
   double* W = nullptr;  // m shared weights on the device, or null: every weight is 1
-  OvrRec* rec = nullptr;
-  OvrRec* rec_host = nullptr;  // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // histories of the last run: [K][hist_ld]
-  double *pnorm = nullptr, *perr = nullptr, *objv = nullptr;
-  int32_t hist_ld = 0;
-  bool has_run = false;
+  double *pnorm = nullptr, *perr = nullptr, *objv = nullptr;  // histories
   admm_reg_multi_options last{};
-  std::vector<int32_t> steps;
   int64_t launches[4] = {0, 0, 0, 0};  // of the last run: iterations, x-solve, pass, sum / finalize
 };
 
 namespace {
 
 const char* kPerFit = ": run one ADMM_PROB_LAD / ADMM_PROB_HUBERFIT engine (admm_engine_create) per fit instead";
-
-int regm_upload_cols(admm_reg_multi* o, double* dst, int64_t ld, const double* src, int64_t rows, int32_t cols, int kind) {
-  if (!src) {
-    ADMM_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * ld * cols, o->stream));
-    return ADMM_OK;
-  }
-  ADMM_HIP_TRY(hipMemcpy2DAsync(dst, ld * sizeof(double), src, rows * sizeof(double), rows * sizeof(double), cols,
-                                kind == ADMM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o->stream));
-  return ADMM_OK;
-}
 
 int regm_setup(admm_reg_multi* o, const admm_reg_multi_desc* desc, const std::vector<int32_t>& kh,
                const std::vector<double>& ph) {
@@ -359,62 +294,19 @@ int regm_setup(admm_reg_multi* o, const admm_reg_multi_desc* desc, const std::ve
   d.mem = desc->mem;
   d.device = desc->device;
   ADMM_TRY(admm_engine_create(&d, &o->eng));  // ADMM_E_NUMERIC: D'D numerically singular (setup_lad_huber_svm's rule)
-  admm_engine* e = o->eng;
-  o->stream = e->stream;
-  o->device = e->device;
-  o->m = m;
-  o->n = n;
-  o->K = K;
   o->ns = desc->ns;
-  o->ldx = round_up(n, 2);
-  o->ldz = round_up(m, 2);
-  o->nwg = ovr_pass_workgroups(m);
-  if (e->xfac.mode == ADMM_XSOLVE_INVERSE && e->xfac.Minv && !e->xfac.planSy.packed) {
-    o->M = e->xfac.Minv;  // (D'D)^-1: full symmetric storage below kSymvHalfMin
-    o->ldM = e->xfac.ldM;
-  } else if (e->xfac.mode == ADMM_XSOLVE_TRSV && e->xfac.F) {
-    // create's accuracy probe kept the triangular solves: they run per fit (K small launches), nothing is forced
-    ADMM_TRY(o->mem.alloc(&o->xtmp, static_cast<size_t>(o->ldx) * K));
-    ADMM_HIP_TRY(hipMemsetAsync(o->xtmp, 0, sizeof(double) * o->ldx * K, o->stream));
-  } else {
-    return fail(ADMM_E_UNSUPPORTED, std::string("the engine built no n x n form of the x-update for this D") + kPerFit);
-  }
-  ADMM_TRY(o->mem.alloc(&o->X, static_cast<size_t>(o->ldx) * K));
-  ADMM_TRY(o->mem.alloc(&o->gsum, static_cast<size_t>(o->ldx) * K));
-  ADMM_HIP_TRY(hipMemsetAsync(o->gsum, 0, sizeof(double) * o->ldx * K, o->stream));
-  ADMM_TRY(o->mem.alloc(&o->Z, static_cast<size_t>(o->ldz) * K));
-  ADMM_TRY(o->mem.alloc(&o->U, static_cast<size_t>(o->ldz) * K));
+  ADMM_TRY(dense_setup(*o, m, n, K, RM_COUNT, kPerFit));
   ADMM_TRY(o->mem.alloc(&o->S, static_cast<size_t>(o->ldz) * o->ns));
   ADMM_HIP_TRY(hipMemsetAsync(o->S, 0, sizeof(double) * o->ldz * o->ns, o->stream));
-  ADMM_TRY(regm_upload_cols(o, o->S, o->ldz, desc->S, m, o->ns, desc->mem));
-  ADMM_TRY(o->mem.alloc(&o->gpart, static_cast<size_t>(o->nwg) * K * o->ldx));
-  ADMM_TRY(o->mem.alloc(&o->part, static_cast<size_t>(K) * RM_COUNT * kOvrMaxWg));
-  ADMM_HIP_TRY(hipMemsetAsync(o->part, 0, sizeof(double) * K * RM_COUNT * kOvrMaxWg, o->stream));
+  ADMM_TRY(upload_cols(*o, o->S, o->ldz, desc->S, m, o->ns, desc->mem));
   ADMM_TRY(o->mem.alloc(&o->par, static_cast<size_t>(4) * K));
   ADMM_HIP_TRY(hipMemcpyAsync(o->par, ph.data(), sizeof(double) * 4 * K, hipMemcpyHostToDevice, o->stream));
   ADMM_TRY(o->mem.alloc(&o->snorm, static_cast<size_t>(K)));
-  double* raw = nullptr;
-  ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(int32_t) + 7) / 8));
-  o->kind = reinterpret_cast<int32_t*>(raw);
+  ADMM_TRY(alloc_words(*o, &o->kind, static_cast<size_t>(K)));
   ADMM_HIP_TRY(hipMemcpyAsync(o->kind, kh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
-  ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(OvrRec) + 7) / 8));
-  o->rec = reinterpret_cast<OvrRec*>(raw);
-  ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
   launch_regm_snorm(o->S, o->ldz, m, K, o->ns, o->snorm, o->stream);  // perr needs max(||Dx||, ||z||, ||s_k||): once
-  ADMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&o->rec_host), sizeof(OvrRec) * K));
-  ADMM_HIP_TRY(hipEventCreate(&o->ev0));
-  ADMM_HIP_TRY(hipEventCreate(&o->ev1));
   ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (kh, ph, and the caller's buffers, were read)
   ADMM_HIP_TRY(hipGetLastError());
-  return ADMM_OK;
-}
-
-int regm_poll(admm_reg_multi* o, bool* all_stopped) {
-  ADMM_HIP_TRY(hipMemcpyAsync(o->rec_host, o->rec, sizeof(OvrRec) * o->K, hipMemcpyDeviceToHost, o->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
-  bool all = true;
-  for (int32_t c = 0; c < o->K; ++c) all = all && o->rec_host[c].stop != 0;
-  *all_stopped = all;
   return ADMM_OK;
 }
 
@@ -454,22 +346,9 @@ int admm_reg_multi_create(const admm_reg_multi_desc* desc, admm_reg_multi** out)
   if (desc->ns != 1 && desc->ns != desc->K)
     return fail(ADMM_E_INVALID, "S has " + std::to_string(desc->ns) + " columns: one shared response or one per fit (" +
                                     std::to_string(desc->K) + ")");
-  const int32_t K = desc->K;
-  std::vector<int32_t> kh(static_cast<size_t>(K), 0);
-  std::vector<double> ph(static_cast<size_t>(4) * K);
-  for (int32_t k = 0; k < K; ++k) {  // per fit, exactly as admm_engine_set_loss checks it
-    if (desc->kind) kh[k] = desc->kind[k];
-    if (kh[k] != 0 && kh[k] != 1)
-      return fail(ADMM_E_INVALID, "fit " + std::to_string(k) + ": kind must be 0 (LAD family) or 1 (Huber family)");
-    const admm_loss_desc ld{nullptr, desc->a ? desc->a[k] : 1.0, desc->b ? desc->b[k] : 1.0,
-                            desc->epsilon ? desc->epsilon[k] : 0.0, desc->delta ? desc->delta[k] : 1.0};
-    if (check_loss_desc(kh[k] ? ADMM_PROB_HUBERFIT : ADMM_PROB_LAD, ld, 0) != ADMM_OK)
-      return fail(ADMM_E_INVALID, "fit " + std::to_string(k) + ": " + std::string(admm_last_error()));
-    ph[4 * k + 0] = ld.slope_pos;
-    ph[4 * k + 1] = ld.slope_neg;
-    ph[4 * k + 2] = ld.epsilon;
-    ph[4 * k + 3] = ld.delta;
-  }
+  std::vector<int32_t> kh;
+  std::vector<double> ph;
+  ADMM_TRY(check_reg_fits(desc->K, desc->kind, desc->a, desc->b, desc->epsilon, desc->delta, &kh, &ph));
   if (desc->comm) return fail(ADMM_E_UNSUPPORTED, std::string("the multi-fit regression is not row-sharded") + kPerFit);
   if (desc->n > kRmMaxN)
     return fail(ADMM_E_UNSUPPORTED, "the multi-fit pass holds a 64-row block of D in registers: n <= " +
@@ -493,28 +372,11 @@ int admm_reg_multi_run(admm_reg_multi* o, const admm_reg_multi_options* opts, ad
   if (opts->struct_size != static_cast<int32_t>(sizeof(admm_reg_multi_options)))
     return fail(ADMM_E_INVALID, "admm_reg_multi_options.struct_size mismatch (ABI version skew)");
   admm_reg_multi_options op = *opts;
-  if (op.fast != ADMM_FAST_OFF)
-    return fail(ADMM_E_UNSUPPORTED, std::string("fast / accelerated ADMM is not part of the multi-fit loop") + kPerFit);
-  if (op.relax != 1.0) return fail(ADMM_E_UNSUPPORTED, std::string("relaxation is not part of the multi-fit loop") + kPerFit);
-  if (op.convtest) return fail(ADMM_E_UNSUPPORTED, std::string("convtest is not part of the multi-fit loop") + kPerFit);
-  if (!(op.rho > 0.0)) return fail(ADMM_E_INVALID, "options.rho must be positive");
-  if (op.maxiters <= 0) op.maxiters = 1000;  // admm.m:334-339
+  ADMM_TRY(check_run_options("multi-fit", kPerFit, &op));
   ADMM_HIP_TRY(hipSetDevice(o->device));
   const int32_t N = op.maxiters, K = o->K;
-  if (o->hist_ld != N) {
-    for (double** p : {&o->pnorm, &o->perr, &o->objv}) {
-      o->mem.free_one(*p);
-      *p = nullptr;
-      ADMM_TRY(o->mem.alloc(p, static_cast<size_t>(N) * K));
-    }
-    o->hist_ld = N;
-  }
-  o->has_run = false;
-  ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
-  ADMM_TRY(regm_upload_cols(o, o->X, o->ldx, op.x0, o->n, K, ADMM_MEM_HOST));
-  ADMM_TRY(regm_upload_cols(o, o->Z, o->ldz, op.z0, o->m, K, ADMM_MEM_HOST));
-  ADMM_TRY(regm_upload_cols(o, o->U, o->ldz, op.u0, o->m, K, ADMM_MEM_HOST));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (host buffers were read)
+  ADMM_TRY(resize_histories(*o, {&o->pnorm, &o->perr, &o->objv}, N));
+  ADMM_TRY(dense_start(*o, op.x0, op.z0, op.u0));
 
   RegmPassArgs pa{};
   pa.D = o->eng->D;
@@ -557,14 +419,6 @@ int admm_reg_multi_run(admm_reg_multi* o, const admm_reg_multi_options* opts, ad
   fa.domaxiters = op.domaxiters;
   fa.objevals = op.objevals;
   fa.maxiters = N;
-  OvrSolveArgs sa{};
-  sa.M = o->M;
-  sa.ldM = o->ldM;
-  sa.n = o->n;
-  sa.gsum = o->gsum;
-  sa.X = o->X;
-  sa.ldx = o->ldx;
-  sa.rec = o->rec;
   const int32_t chunks = (K + kRegmChunk - 1) / kRegmChunk;
   auto pass = [&](bool init) {
     for (int32_t ch = 0; ch < chunks; ++ch) {
@@ -576,53 +430,23 @@ int admm_reg_multi_run(admm_reg_multi* o, const admm_reg_multi_options* opts, ad
   int64_t* cnt = o->launches;
   cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
 
-  ADMM_HIP_TRY(hipEventRecord(o->ev0, o->stream));
+  ADMM_TRY(begin_timing(*o));
   pass(true);  // g = D'((s + z0) - u0)
   fa.fin = 0;
   launch_regm_gsum_fin(fa, o->stream);
   fa.fin = 1;
   bool all = false;
   for (int32_t it = 0; it < N && !all; ++it) {
-    if (o->M) {
-      launch_ovr_xsolve(sa, K, o->stream);
-      cnt[1] += 1;
-    } else {
-      for (int32_t c = 0; c < K; ++c)
-        launch_trsv_pair(o->eng->xfac.trsv, o->gsum + static_cast<int64_t>(c) * o->ldx,
-                         o->xtmp + static_cast<int64_t>(c) * o->ldx, nullptr, o->stream);
-      launch_ovr_xcopy(o->xtmp, o->X, o->ldx, o->n, K, o->rec, o->stream);
-      cnt[1] += K + 1;
-    }
+    cnt[1] += dense_xupdate(*o);
     pass(false);
     launch_regm_gsum_fin(fa, o->stream);
     cnt[0] += 1;
     cnt[2] += chunks;
     cnt[3] += 1;
-    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(regm_poll(o, &all));
+    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
-  ADMM_HIP_TRY(hipEventRecord(o->ev1, o->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
-  ADMM_HIP_TRY(hipGetLastError());
-  if (!all) return fail(ADMM_E_DEVICE, "the multi-fit loop ended with fits still running");
-  float ms = 0.f;
-  ADMM_HIP_TRY(hipEventElapsedTime(&ms, o->ev0, o->ev1));
-  if (runtime_s) *runtime_s = 1e-3 * static_cast<double>(ms);
-  o->steps.assign(static_cast<size_t>(K), 0);
-  std::vector<double> objh;
-  if (op.objevals) {
-    objh.resize(static_cast<size_t>(N) * K);
-    ADMM_HIP_TRY(hipMemcpy(objh.data(), o->objv, sizeof(double) * N * K, hipMemcpyDeviceToHost));
-  }
-  for (int32_t c = 0; c < K; ++c) {
-    const OvrRec& r = o->rec_host[c];
-    o->steps[c] = r.steps;
-    if (summaries) {
-      summaries[c].steps = r.steps;
-      summaries[c].stopped_early = r.early;
-      summaries[c].objopt = (op.objevals && r.steps > 0) ? objh[static_cast<size_t>(c) * N + r.steps - 1]
-                                                         : __builtin_nan("");
-    }
-  }
+  ADMM_TRY(finish_run(*o, all, "the multi-fit loop ended with fits still running", N, op.objevals != 0, o->objv, runtime_s,
+                      summaries));
   o->last = op;
   o->has_run = true;
   return ADMM_OK;
@@ -630,20 +454,7 @@ int admm_reg_multi_run(admm_reg_multi* o, const admm_reg_multi_options* opts, ad
 
 int admm_reg_multi_set_weights(admm_reg_multi* o, const double* weights) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
-  if (weights)  // (a refused call changes nothing)
-    for (int64_t i = 0; i < o->m; ++i)
-      if (!finite_nonneg(weights[i]))
-        return fail(ADMM_E_INVALID, "loss: weight " + std::to_string(i) + " is negative or not finite");
-  ADMM_HIP_TRY(hipSetDevice(o->device));
-  double* w = nullptr;
-  if (weights) {
-    ADMM_TRY(o->mem.alloc(&w, static_cast<size_t>(o->m)));
-    ADMM_HIP_TRY(hipMemcpyAsync(w, weights, sizeof(double) * o->m, hipMemcpyHostToDevice, o->stream));
-    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (the caller's buffer is read until here)
-  }
-  if (o->W) o->mem.free_one(o->W);
-  o->W = w;
-  return ADMM_OK;
+  return set_shared_weights(*o, o->m, weights, &o->W);
 }
 
 int admm_reg_multi_launches(admm_reg_multi* o, int64_t counts[5]) {
@@ -658,50 +469,22 @@ int admm_reg_multi_fetch(admm_reg_multi* o, int field, double* dst, size_t cap, 
   if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
   if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
   ADMM_HIP_TRY(hipSetDevice(o->device));
-  const int32_t K = o->K;
-  auto matrix = [&](const double* src, int64_t ld, int64_t rows) -> int {
-    const size_t need = static_cast<size_t>(rows) * K;
-    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
-    ADMM_HIP_TRY(hipMemcpy2D(dst, rows * sizeof(double), src, ld * sizeof(double), rows * sizeof(double), K,
-                             hipMemcpyDeviceToHost));
-    if (written) *written = need;
-    return ADMM_OK;
-  };
-  auto history = [&](const double* src) -> int {
-    int32_t S = 0;
-    for (int32_t s : o->steps) S = s > S ? s : S;
-    const size_t need = static_cast<size_t>(S) * K;
-    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
-    if (S > 0)
-      ADMM_HIP_TRY(hipMemcpy2D(dst, S * sizeof(double), src, o->hist_ld * sizeof(double), S * sizeof(double), K,
-                               hipMemcpyDeviceToHost));
-    for (int32_t c = 0; c < K; ++c)
-      for (int32_t i = o->steps[c]; i < S; ++i) dst[static_cast<size_t>(c) * S + i] = __builtin_nan("");
-    if (written) *written = need;
-    return ADMM_OK;
-  };
   switch (field) {
-    case ADMM_REGM_F_XOPT: return matrix(o->X, o->ldx, o->n);
-    case ADMM_REGM_F_ZOPT: return matrix(o->Z, o->ldz, o->m);
-    case ADMM_REGM_F_UOPT: return matrix(o->U, o->ldz, o->m);
-    case ADMM_REGM_F_PNORM: return history(o->pnorm);
-    case ADMM_REGM_F_PERR: return history(o->perr);
+    case ADMM_REGM_F_XOPT: return fetch_cols(*o, o->X, o->ldx, o->n, dst, cap, written);
+    case ADMM_REGM_F_ZOPT: return fetch_cols(*o, o->Z, o->ldz, o->m, dst, cap, written);
+    case ADMM_REGM_F_UOPT: return fetch_cols(*o, o->U, o->ldz, o->m, dst, cap, written);
+    case ADMM_REGM_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
+    case ADMM_REGM_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
     case ADMM_REGM_F_OBJEVALS:
       if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return history(o->objv);
+      return fetch_history(*o, o->objv, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the multi-fit regression");
   }
 }
 
 void admm_reg_multi_destroy(admm_reg_multi* o) {
   if (!o) return;
-  (void)hipSetDevice(o->device);
-  if (o->stream) (void)hipStreamSynchronize(o->stream);
-  if (o->ev0) (void)hipEventDestroy(o->ev0);
-  if (o->ev1) (void)hipEventDestroy(o->ev1);
-  o->mem.release();
-  if (o->rec_host) (void)hipHostFree(o->rec_host);
-  if (o->eng) admm_engine_destroy(o->eng);
+  dense_destroy(*o);
   delete o;
 }
 

@@ -1,10 +1,9 @@
 // sparse_reg.h -- argument blocks of the multi-fit robust regression on a sparse design matrix (sparse_reg.hip, DESIGN.md
 // q38): K independent plain-ADMM runs of the A = D iteration (admm.m:496-743 with B = -1, c = s_k, stopcond 'standard')
-// whose x-update (D'D)^-1 D'(s + z - u) is CG on D'D x = D'(s + z - u), all fits in lock-step over one sparse product.
-// The products, the CG kernels, their state and the per-fit control record are sparse_svm.h's; every multi-vector has
-// spmm.h's layout [chunks][len][kSpmmChunk] and every elementwise kernel sparse_svm.h's thread layout.
+// whose x-update (D'D)^-1 D'(s + z - u) is the lock-step CG of spmm_cg.h on D'D x = D'(s + z - u).  Every multi-vector
+// has spmm.h's layout [chunks][len][kSpmmChunk] and every elementwise kernel spmm_cg.h's thread layout.
 #pragma once
-#include "sparse_svm.h"
+#include "spmm_cg.h"
 
 namespace admm {
 
@@ -24,8 +23,8 @@ struct SrgElemArgs {
   const double* W;      // m shared weights or null
   const double* par;    // K x 4: (a, b, epsilon, delta) of every fit
   const int32_t* kind;  // K values: 0 LAD family, 1 Huber family
-  const OvrRec* rec;
-  double* part;         // [chunks * kSpmmChunk][SR_COUNT][kSsvMaxWg]
+  const MultiRec* rec;
+  double* part;         // [chunks * kSpmmChunk][SR_COUNT][kScgMaxWg]
   int32_t K, ns, objevals;
   double rho;
 };
@@ -34,8 +33,8 @@ struct SrgDualArgs {
   int64_t n;
   const double* GDZ;    // D'(z - zprev)
   const double* GU;     // D'u
-  const OvrRec* rec;
-  double* part;         // [chunks * kSpmmChunk][SD_COUNT][kSsvMaxWg]
+  const MultiRec* rec;
+  double* part;         // [chunks * kSpmmChunk][SD_COUNT][kScgMaxWg]
   int32_t K;
 };
 
@@ -46,7 +45,7 @@ struct SrgFinArgs {
   int64_t m;
   int32_t K, nwg, nwg_n;
   int32_t dual;         // the dual residual takes part in the stop rule (nodualerror = 0)
-  OvrRec* rec;
+  MultiRec* rec;
   double *pnorm, *perr, *dnorm, *derr, *objv;  // [K][hist_ld]
   int64_t hist_ld;
   double rho, abstol, reltol;

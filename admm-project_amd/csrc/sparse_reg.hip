@@ -1,13 +1,13 @@
 // sparse_reg.hip -- quantile / LAD / Huber regression, K fits at once on a SPARSE design matrix.  The loop
 // is reg_multi.hip's: K independent plain-ADMM runs (admm.m:496-743: A = D, B = -1, c = s_k, stopcond 'standard') that
 // share D; the loss and its parameters sit in the element-wise z-prox (loss_device.h: loss_prox_elem) and the objective
-// alone.  The x-update is sparse_svm.hip's: x_k = (D'D)^-1 D'(s_k + z_k - u_k) (getProxOps.m:1511-1515) as CG on
+// alone.  The x-update is spmm_cg.hip's: x_k = (D'D)^-1 D'(s_k + z_k - u_k) (getProxOps.m:1511-1515) as CG on
 // D'D x = D'(s_k + z_k - u_k), no shift, nothing n x n: the first solve of a run starts from 0 and every later one from
 // the previous x, so every iterate stays in range(D') -- with full column rank the reference's solution, otherwise the
 // minimum-norm one (a column of D without nonzeros keeps x = 0.0; lad.m:134 would fail in chol there).
 // Per iteration, every launch for all K fits at once (blockIdx.y = chunk of kSpmmChunk fits):
 //   Y = D' V                      one SpMM (spmm.hip); V = (s + z) - u, left behind by the element pass
-//   launch_ssv_cg_start / _step   the lock-step CG of sparse_svm.hip as it is, driven by srg_solve
+//   SpmmCg::solve                 the lock-step CG of spmm_cg.hip: two SpMM and four small launches per inner iteration
 //   AX = D X                      one SpMM
 //   srg_elem_kernel               the element update of every fit -- loss_form_z / prox_apply, the code of the dense pass
 //                                 -- its residual sums, V, and z - zprev when the dual residual is on
@@ -20,8 +20,8 @@
 #include <cstddef>
 #include <vector>
 
-#include "engine_internal.h"
 #include "loss_device.h"
+#include "multi_host.h"
 #include "reg_multi.h"
 #include "sparse_reg.h"
 
@@ -31,41 +31,11 @@ namespace {
 
 constexpr int KC = kSpmmChunk;
 
-// per-fit sums over the workgroup of NS per-thread values, the rows of the block added in row order (the order of
-// sparse_svm.hip's ssv_class_sums): part[(fit * NS + s) * kSsvMaxWg + blockIdx.x].  lds: NS * kSsvBlock doubles.
-template <int NS>
-__device__ __forceinline__ void srg_fit_sums(const double (&acc)[NS], double* lds, double* part) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < NS; ++s) lds[s * kSsvBlock + tid] = acc[s];
-  __syncthreads();
-  if (tid < NS * KC) {
-    const int s = tid / KC, c = tid % KC;
-    double v = 0.0;
-    for (int r = 0; r < kSsvRows; ++r) v += lds[s * kSsvBlock + r * KC + c];
-    const int64_t fit = static_cast<int64_t>(blockIdx.y) * KC + c;
-    part[(fit * NS + s) * kSsvMaxWg + blockIdx.x] = v;
-  }
-}
-
-struct SrgLane {
-  int c, r, fit;
-  bool run;  // the fit exists and its ADMM run has not stopped
-};
-__device__ __forceinline__ SrgLane srg_lane(const OvrRec* rec, int32_t K) {
-  SrgLane l;
-  l.c = threadIdx.x % KC;
-  l.r = threadIdx.x / KC;
-  l.fit = static_cast<int>(blockIdx.y) * KC + l.c;
-  l.run = l.fit < K && rec[l.fit < K ? l.fit : K - 1].stop == 0;
-  return l;
-}
-
 // INIT: only V = (s + z0) - u0, before the first iteration
 template <bool INIT>
-__global__ __launch_bounds__(kSsvBlock) void srg_elem_kernel(SrgElemArgs a) {
-  __shared__ double lds[SR_COUNT * kSsvBlock];
-  const SrgLane l = srg_lane(a.rec, a.K);
+__global__ __launch_bounds__(kScgBlock) void srg_elem_kernel(SrgElemArgs a) {
+  __shared__ double lds[SR_COUNT * kScgBlock];
+  const ScgLane l = scg_lane(a.rec, a.K);
   if (!__syncthreads_or(l.run)) return;
   const int64_t base = static_cast<int64_t>(blockIdx.y) * a.m * KC;
   double acc[S_COUNT];
@@ -91,9 +61,9 @@ __global__ __launch_bounds__(kSsvBlock) void srg_elem_kernel(SrgElemArgs a) {
   pa.alg = 0;
   pa.a_identity = 0;
   pa.rhs_kind = RHS_T1;
-  const int64_t nrb = (a.m + kSsvRows - 1) / kSsvRows;
+  const int64_t nrb = (a.m + kScgRows - 1) / kScgRows;
   for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
-    const int64_t i = rb * kSsvRows + l.r;
+    const int64_t i = rb * kScgRows + l.r;
     if (!l.run || i >= a.m) continue;
     const int64_t e = i * KC + l.c;
     const double zp = pa.z[e], uo = pa.u[e];
@@ -114,19 +84,19 @@ __global__ __launch_bounds__(kSsvBlock) void srg_elem_kernel(SrgElemArgs a) {
   }
   if (INIT) return;
   const double sums[SR_COUNT] = {acc[S_R2], acc[S_AX2], acc[S_Z2], acc[S_OBJZ]};
-  srg_fit_sums<SR_COUNT>(sums, lds, a.part);
+  scg_sums<SR_COUNT>(sums, lds, a.part, SR_COUNT, 0);
 }
 
 // per fit the partial squared norms over n of D'(z - zprev) and D'u
-__global__ __launch_bounds__(kSsvBlock) void srg_dual_kernel(SrgDualArgs a) {
-  __shared__ double lds[SD_COUNT * kSsvBlock];
-  const SrgLane l = srg_lane(a.rec, a.K);
+__global__ __launch_bounds__(kScgBlock) void srg_dual_kernel(SrgDualArgs a) {
+  __shared__ double lds[SD_COUNT * kScgBlock];
+  const ScgLane l = scg_lane(a.rec, a.K);
   if (!__syncthreads_or(l.run)) return;
   const int64_t base = static_cast<int64_t>(blockIdx.y) * a.n * KC;
   double acc[SD_COUNT] = {0.0, 0.0};
-  const int64_t nrb = (a.n + kSsvRows - 1) / kSsvRows;
+  const int64_t nrb = (a.n + kScgRows - 1) / kScgRows;
   for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
-    const int64_t i = rb * kSsvRows + l.r;
+    const int64_t i = rb * kScgRows + l.r;
     if (l.run && i < a.n) {
       const int64_t e = base + i * KC + l.c;
       const double g = a.GDZ[e], h = a.GU[e];
@@ -134,32 +104,20 @@ __global__ __launch_bounds__(kSsvBlock) void srg_dual_kernel(SrgDualArgs a) {
       acc[SD_U2] += h * h;
     }
   }
-  srg_fit_sums<SD_COUNT>(acc, lds, a.part);
+  scg_sums<SD_COUNT>(acc, lds, a.part, SD_COUNT, 0);
 }
 
 // blockIdx.x = fit: the finalize logic of the fit's iteration -- admm.m:612-658, 706-713 as oracle/admm_ref.py restates
 // it, for plain ADMM with stopcond = 'standard'; the dual residual takes part when a.dual is set
 __global__ __launch_bounds__(kBlock) void srg_fin_kernel(SrgFinArgs a) {
   const int fit = blockIdx.x;
-  OvrRec* rec = a.rec + fit;
+  MultiRec* rec = a.rec + fit;
   const int32_t it = rec->iter;
   if (rec->stop) return;
   __shared__ double S[8];
   const int tid = threadIdx.x;
-  {  // 32 lanes per slot stride over the workgroup partials, then a fixed shuffle tree
-    const int slot = tid >> 5, sub = tid & 31;
-    double v = 0.0;
-    if (slot < SR_COUNT) {
-      const double* __restrict__ ps = a.part + (static_cast<int64_t>(fit) * SR_COUNT + slot) * kSsvMaxWg;
-      for (int b = sub; b < a.nwg; b += 32) v += ps[b];
-    } else if (a.dual && slot < SR_COUNT + SD_COUNT) {
-      const double* __restrict__ ps = a.dpart + (static_cast<int64_t>(fit) * SD_COUNT + (slot - SR_COUNT)) * kSsvMaxWg;
-      for (int b = sub; b < a.nwg_n; b += 32) v += ps[b];
-    }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (sub == 0 && slot < 8) S[slot] = v;
-  }
+  multi_slot_totals(a.part, fit, SR_COUNT, a.nwg, S);
+  if (a.dual) multi_slot_totals(a.dpart, fit, SD_COUNT, a.nwg_n, S, SR_COUNT);
   __syncthreads();
   if (tid != 0) return;
   const int i1 = it + 1;  // 1-based iteration number (admm.m loop variable)
@@ -179,23 +137,20 @@ __global__ __launch_bounds__(kBlock) void srg_fin_kernel(SrgFinArgs a) {
     dual_ok = dn < de;
   }
   const bool stop = !a.domaxiters && pn < pe && dual_ok;  // admm.m:710-713
-  rec->iter = i1;
-  rec->steps = i1;
-  if (stop) rec->early = 1;
-  if (stop || i1 >= a.maxiters) rec->stop = 1;
+  multi_stop_tail(rec, stop, i1, a.maxiters);
 }
 
 }  // namespace
 
 void launch_srg_elem(const SrgElemArgs& a, bool init, hipStream_t stream) {
-  const dim3 grid(ssv_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
-  if (init) hipLaunchKernelGGL(srg_elem_kernel<true>, grid, dim3(kSsvBlock), 0, stream, a);
-  else hipLaunchKernelGGL(srg_elem_kernel<false>, grid, dim3(kSsvBlock), 0, stream, a);
+  const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
+  if (init) hipLaunchKernelGGL(srg_elem_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
+  else hipLaunchKernelGGL(srg_elem_kernel<false>, grid, dim3(kScgBlock), 0, stream, a);
 }
 
 void launch_srg_dual(const SrgDualArgs& a, hipStream_t stream) {
-  const dim3 grid(ssv_vec_workgroups(a.n), static_cast<unsigned>(spmm_chunks(a.K)));
-  hipLaunchKernelGGL(srg_dual_kernel, grid, dim3(kSsvBlock), 0, stream, a);
+  const dim3 grid(scg_vec_workgroups(a.n), static_cast<unsigned>(spmm_chunks(a.K)));
+  hipLaunchKernelGGL(srg_dual_kernel, grid, dim3(kScgBlock), 0, stream, a);
 }
 
 void launch_srg_fin(const SrgFinArgs& a, hipStream_t stream) {
@@ -205,85 +160,34 @@ void launch_srg_fin(const SrgFinArgs& a, hipStream_t stream) {
 }  // namespace admm
 
 // ---------------------------------------------------------------------------------------------------------- the object
-struct admm_sparse_reg {
-  hipStream_t stream = nullptr;
-  DevMem mem;
-  SparseDev sp;
-  int device = 0;
-  int64_t m = 0, n = 0, nnz = 0;
-  int32_t K = 0, ns = 1, chunks = 0, nwg = 0, nwg_n = 0;
-  // multi-vectors, [chunks][len][kSpmmChunk]
-  double *X = nullptr, *R = nullptr, *P = nullptr, *Q = nullptr, *Y = nullptr;  // len n (between two solves R and P hold
-                                                                                // D'(z - zprev) and D'u)
-  double *Z = nullptr, *U = nullptr, *V = nullptr, *T = nullptr, *DZ = nullptr;  // len m (T: D p and D x; DZ: with the
-                                                                                 // dual residual only)
+struct admm_sparse_reg : MultiHost {
+  SpmmCg cg;  // D, the x-update and its multi-vectors (between two solves R and P hold D'(z - zprev) and D'u)
+  int64_t m = 0, n = 0;
+  int32_t ns = 1, nwg = 0, nwg_n = 0;
+  double *Z = nullptr, *U = nullptr, *V = nullptr, *DZ = nullptr;  // multi-vectors of len m (DZ: with the dual residual only)
   double* S = nullptr;  // ns == 1: m values; ns == K: a multi-vector of len m
-  double *cgpart = nullptr, *part = nullptr, *dpart = nullptr;
+  double *part = nullptr, *dpart = nullptr;
   double *W = nullptr, *par = nullptr, *snorm = nullptr;
-  int32_t *kind = nullptr, *alldone = nullptr;
-  SsvCg* cg = nullptr;
-  OvrRec* rec = nullptr;
-  struct Poll {  // pinned
-    int32_t alldone, longest;
-  }* poll = nullptr;
-  OvrRec* rec_host = nullptr;  // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // [K][hist_ld]
-  int32_t hist_ld = 0;
-  int cg_batch = 8;  // inner iterations enqueued between two polls of the all-done word
-  bool has_run = false;
+  int32_t* kind = nullptr;
+  double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   admm_sparse_reg_options last{};
-  std::vector<int32_t> steps;
 };
 
 namespace {
 
-template <class T>
-int srg_alloc_words(admm_sparse_reg* o, T** out, size_t count) {
-  double* raw = nullptr;
-  ADMM_TRY(o->mem.alloc(&raw, (count * sizeof(T) + 7) / 8));
-  ADMM_HIP_TRY(hipMemsetAsync(raw, 0, (count * sizeof(T) + 7) / 8 * 8, o->stream));
-  *out = reinterpret_cast<T*>(raw);
-  return ADMM_OK;
-}
-
-// column-major host matrix (rows x K), or zeros, into a chunked multi-vector
-int srg_upload(admm_sparse_reg* o, double* dst, const double* src, int64_t rows) {
-  const size_t elems = static_cast<size_t>(o->chunks) * rows * kSpmmChunk;
-  if (!src) {
-    ADMM_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * elems, o->stream));
-    return ADMM_OK;
-  }
-  std::vector<double> h(elems);
-  spmm_pack(src, rows, rows, o->K, h.data());
-  ADMM_HIP_TRY(hipMemcpyAsync(dst, h.data(), sizeof(double) * elems, hipMemcpyHostToDevice, o->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (h goes out of scope)
-  return ADMM_OK;
-}
-
 int srg_setup(admm_sparse_reg* o, const admm_sparse_reg_desc* desc, const std::vector<int32_t>& kh,
               const std::vector<double>& ph) {
-  ADMM_HIP_TRY(hipSetDevice(desc->device));
-  o->device = desc->device;
-  ADMM_HIP_TRY(hipStreamCreate(&o->stream));
-  const admm_sparse_desc* D = desc->D;
-  ADMM_TRY(sparse_device_build(D, &o->sp, o->stream));
-  const int64_t m = D->rows, n = D->cols;
   const int32_t K = desc->K;
-  o->m = m;
-  o->n = n;
-  o->nnz = D->nnz;
   o->K = K;
+  ADMM_TRY(o->cg.build(o, desc->device, desc->D));
+  const int64_t m = o->cg.m;
+  o->m = m;
+  o->n = o->cg.n;
   o->ns = desc->ns;
-  o->chunks = spmm_chunks(K);
-  o->nwg = ssv_vec_workgroups(m);
-  o->nwg_n = ssv_vec_workgroups(n);
-  const size_t kp = static_cast<size_t>(o->chunks) * kSpmmChunk;
-  for (double** p : {&o->X, &o->R, &o->P, &o->Q, &o->Y}) {
-    ADMM_TRY(o->mem.alloc(p, kp * n));
-    ADMM_HIP_TRY(hipMemsetAsync(*p, 0, sizeof(double) * kp * n, o->stream));
-  }
-  for (double** p : {&o->Z, &o->U, &o->V, &o->T}) {
+  o->nwg = scg_vec_workgroups(m);
+  o->nwg_n = scg_vec_workgroups(o->n);
+  const size_t kp = static_cast<size_t>(o->cg.chunks) * kSpmmChunk;
+  for (double** p : {&o->Z, &o->U, &o->V}) {
     ADMM_TRY(o->mem.alloc(p, kp * m));
     ADMM_HIP_TRY(hipMemsetAsync(*p, 0, sizeof(double) * kp * m, o->stream));
   }
@@ -297,68 +201,22 @@ int srg_setup(admm_sparse_reg* o, const admm_sparse_reg_desc* desc, const std::v
       o->S = scol;
     } else {
       ADMM_TRY(o->mem.alloc(&o->S, kp * m));
-      ADMM_TRY(srg_upload(o, o->S, desc->S, m));
+      ADMM_TRY(o->cg.upload(o->S, desc->S, m));
       ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
       o->mem.free_one(scol);
     }
   }
-  ADMM_TRY(o->mem.alloc(&o->cgpart, kp * 2 * kSsvMaxWg));
-  ADMM_HIP_TRY(hipMemsetAsync(o->cgpart, 0, sizeof(double) * kp * 2 * kSsvMaxWg, o->stream));
-  ADMM_TRY(o->mem.alloc(&o->part, kp * SR_COUNT * kSsvMaxWg));
-  ADMM_HIP_TRY(hipMemsetAsync(o->part, 0, sizeof(double) * kp * SR_COUNT * kSsvMaxWg, o->stream));
-  ADMM_TRY(o->mem.alloc(&o->dpart, kp * SD_COUNT * kSsvMaxWg));
-  ADMM_HIP_TRY(hipMemsetAsync(o->dpart, 0, sizeof(double) * kp * SD_COUNT * kSsvMaxWg, o->stream));
+  ADMM_TRY(o->mem.alloc(&o->part, kp * SR_COUNT * kScgMaxWg));
+  ADMM_HIP_TRY(hipMemsetAsync(o->part, 0, sizeof(double) * kp * SR_COUNT * kScgMaxWg, o->stream));
+  ADMM_TRY(o->mem.alloc(&o->dpart, kp * SD_COUNT * kScgMaxWg));
+  ADMM_HIP_TRY(hipMemsetAsync(o->dpart, 0, sizeof(double) * kp * SD_COUNT * kScgMaxWg, o->stream));
   ADMM_TRY(o->mem.alloc(&o->par, static_cast<size_t>(4) * K));
   ADMM_HIP_TRY(hipMemcpyAsync(o->par, ph.data(), sizeof(double) * 4 * K, hipMemcpyHostToDevice, o->stream));
-  ADMM_TRY(srg_alloc_words(o, &o->kind, static_cast<size_t>(K)));
+  ADMM_TRY(alloc_words(*o, &o->kind, static_cast<size_t>(K)));
   ADMM_HIP_TRY(hipMemcpyAsync(o->kind, kh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
-  ADMM_TRY(srg_alloc_words(o, &o->alldone, 2));
-  ADMM_TRY(srg_alloc_words(o, &o->cg, static_cast<size_t>(K)));
-  ADMM_TRY(srg_alloc_words(o, &o->rec, static_cast<size_t>(K)));
-  ADMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&o->poll), sizeof(*o->poll)));
-  ADMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&o->rec_host), sizeof(OvrRec) * K));
-  ADMM_HIP_TRY(hipEventCreate(&o->ev0));
-  ADMM_HIP_TRY(hipEventCreate(&o->ev1));
+  ADMM_TRY(alloc_common(*o));
   ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (kh, ph and the caller's buffers were read)
   ADMM_HIP_TRY(hipGetLastError());
-  return ADMM_OK;
-}
-
-SpmmMask srg_mask(const admm_sparse_reg* o, bool with_cg) {
-  SpmmMask mk;
-  mk.flag_a = &o->rec->stop;
-  mk.stride_a = kOvrRecWords;
-  if (with_cg) {
-    mk.flag_b = reinterpret_cast<const int32_t*>(o->cg) + kSsvDoneWord;
-    mk.stride_b = kSsvCgWords;
-  }
-  mk.K = o->K;
-  return mk;
-}
-
-// X <- the CG solution of D'D x = Y for every running fit; the host polls the all-done word once per batch (the shape
-// of sparse_svm.hip's driver)
-int srg_solve(admm_sparse_reg* o, const SsvCgArgs& a, bool first) {
-  const SpmmMask run = srg_mask(o, false), live = srg_mask(o, true);
-  if (!first) {  // q = D'(D x) in front of a warm start
-    launch_spmm(o->sp.n, o->X, o->T, o->chunks, run, o->stream);
-    launch_spmm(o->sp.t, o->T, o->Q, o->chunks, run, o->stream);
-  }
-  launch_ssv_cg_start(a, first, o->stream);
-  for (int32_t done_it = 0; done_it < a.maxit;) {
-    const int32_t k = std::min(a.maxit - done_it, static_cast<int32_t>(o->cg_batch));
-    for (int32_t c = 0; c < k; ++c) {
-      launch_spmm(o->sp.n, o->P, o->T, o->chunks, live, o->stream);
-      launch_spmm(o->sp.t, o->T, o->Q, o->chunks, live, o->stream);
-      launch_ssv_cg_step(a, o->stream);
-    }
-    done_it += k;
-    ADMM_HIP_TRY(hipMemcpyAsync(o->poll, o->alldone, sizeof(*o->poll), hipMemcpyDeviceToHost, o->stream));
-    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
-    if (o->poll->alldone) break;
-  }
-  // (a batch as long as the last solve took: one or two polls per solve)
-  o->cg_batch = std::min(64, std::max(4, static_cast<int>(o->poll->longest) + 2));
   return ADMM_OK;
 }
 
@@ -404,22 +262,9 @@ int admm_sparse_reg_create(const admm_sparse_reg_desc* desc, admm_sparse_reg** o
   if (desc->ns != 1 && desc->ns != desc->K)
     return fail(ADMM_E_INVALID, "S has " + std::to_string(desc->ns) + " columns: one shared response or one per fit (" +
                                     std::to_string(desc->K) + ")");
-  const int32_t K = desc->K;
-  std::vector<int32_t> kh(static_cast<size_t>(K), 0);
-  std::vector<double> ph(static_cast<size_t>(4) * K);
-  for (int32_t k = 0; k < K; ++k) {  // per fit, exactly as admm_engine_set_loss checks it
-    if (desc->kind) kh[k] = desc->kind[k];
-    if (kh[k] != 0 && kh[k] != 1)
-      return fail(ADMM_E_INVALID, "fit " + std::to_string(k) + ": kind must be 0 (LAD family) or 1 (Huber family)");
-    const admm_loss_desc ld{nullptr, desc->a ? desc->a[k] : 1.0, desc->b ? desc->b[k] : 1.0,
-                            desc->epsilon ? desc->epsilon[k] : 0.0, desc->delta ? desc->delta[k] : 1.0};
-    if (check_loss_desc(kh[k] ? ADMM_PROB_HUBERFIT : ADMM_PROB_LAD, ld, 0) != ADMM_OK)
-      return fail(ADMM_E_INVALID, "fit " + std::to_string(k) + ": " + std::string(admm_last_error()));
-    ph[4 * k + 0] = ld.slope_pos;
-    ph[4 * k + 1] = ld.slope_neg;
-    ph[4 * k + 2] = ld.epsilon;
-    ph[4 * k + 3] = ld.delta;
-  }
+  std::vector<int32_t> kh;
+  std::vector<double> ph;
+  ADMM_TRY(check_reg_fits(desc->K, desc->kind, desc->a, desc->b, desc->epsilon, desc->delta, &kh, &ph));
   if (desc->comm) return fail(ADMM_E_UNSUPPORTED, "the sparse multi-fit regression is not row-sharded");
   int ndev = 0;
   ADMM_TRY(admm_device_count(&ndev));
@@ -442,54 +287,28 @@ int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts,
   if (opts->struct_size != static_cast<int32_t>(sizeof(admm_sparse_reg_options)))
     return fail(ADMM_E_INVALID, "admm_sparse_reg_options.struct_size mismatch (ABI version skew)");
   admm_sparse_reg_options op = *opts;
-  if (op.fast != ADMM_FAST_OFF)
-    return fail(ADMM_E_UNSUPPORTED, "fast / accelerated ADMM is not part of the sparse multi-fit loop");
-  if (op.relax != 1.0) return fail(ADMM_E_UNSUPPORTED, "relaxation is not part of the sparse multi-fit loop");
-  if (op.convtest) return fail(ADMM_E_UNSUPPORTED, "convtest is not part of the sparse multi-fit loop");
-  if (!(op.rho > 0.0)) return fail(ADMM_E_INVALID, "options.rho must be positive");
-  if (op.maxiters <= 0) op.maxiters = 1000;  // admm.m:334-339
+  ADMM_TRY(check_run_options("sparse multi-fit", "", &op));
   if (!(op.cg_tol > 0.0)) op.cg_tol = 1e-12;
   if (op.cg_maxit <= 0) op.cg_maxit = 200;
   const bool dual = op.nodualerror == 0;
   ADMM_HIP_TRY(hipSetDevice(o->device));
   const int32_t N = op.maxiters, K = o->K;
-  if (o->hist_ld != N) {
-    for (double** p : {&o->pnorm, &o->perr, &o->dnorm, &o->derr, &o->objv}) {
-      o->mem.free_one(*p);
-      *p = nullptr;
-      ADMM_TRY(o->mem.alloc(p, static_cast<size_t>(N) * K));
-    }
-    o->hist_ld = N;
-  }
+  ADMM_TRY(resize_histories(*o, {&o->pnorm, &o->perr, &o->dnorm, &o->derr, &o->objv}, N));
+  SpmmCg& cg = o->cg;
   if (dual && !o->DZ) {
-    const size_t elems = static_cast<size_t>(o->chunks) * kSpmmChunk * o->m;
+    const size_t elems = static_cast<size_t>(cg.chunks) * kSpmmChunk * o->m;
     ADMM_TRY(o->mem.alloc(&o->DZ, elems));
     ADMM_HIP_TRY(hipMemsetAsync(o->DZ, 0, sizeof(double) * elems, o->stream));
   }
-  o->has_run = false;
-  ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
-  ADMM_HIP_TRY(hipMemsetAsync(o->cg, 0, sizeof(SsvCg) * K, o->stream));
-  ADMM_TRY(srg_upload(o, o->X, nullptr, o->n));  // (x0 is never read: the first x-update starts CG from 0)
-  ADMM_TRY(srg_upload(o, o->Z, op.z0, o->m));
-  ADMM_TRY(srg_upload(o, o->U, op.u0, o->m));
+  ADMM_TRY(begin_run(*o));
+  ScgArgs ca{};
+  ADMM_TRY(cg.begin_run(op.cg_tol, op.cg_maxit, &ca));
+  ADMM_TRY(cg.upload(o->Z, op.z0, o->m));
+  ADMM_TRY(cg.upload(o->U, op.u0, o->m));
 
-  SsvCgArgs ca{};
-  ca.n = o->n;
-  ca.tol = op.cg_tol;
-  ca.maxit = op.cg_maxit;
-  ca.K = K;
-  ca.Y = o->Y;
-  ca.X = o->X;
-  ca.R = o->R;
-  ca.P = o->P;
-  ca.Q = o->Q;
-  ca.part = o->cgpart;
-  ca.st = o->cg;
-  ca.rec = o->rec;
-  ca.alldone = o->alldone;
   SrgElemArgs ea{};
   ea.m = o->m;
-  ea.AX = o->T;
+  ea.AX = cg.T;
   ea.Z = o->Z;
   ea.U = o->U;
   ea.V = o->V;
@@ -506,8 +325,8 @@ int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts,
   ea.rho = op.rho;
   SrgDualArgs da{};
   da.n = o->n;
-  da.GDZ = o->R;  // (free between two solves: launch_ssv_cg_start writes R and P before it reads them)
-  da.GU = o->P;
+  da.GDZ = cg.R;  // (free between two solves: launch_scg_start writes R and P before it reads them)
+  da.GU = cg.P;
   da.rec = o->rec;
   da.part = o->dpart;
   da.K = K;
@@ -533,58 +352,28 @@ int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts,
   fa.domaxiters = op.domaxiters;
   fa.objevals = op.objevals;
   fa.maxiters = N;
-  const SpmmMask run = srg_mask(o, false);
+  const SpmmMask run = cg.mask(false);
   const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
-  o->cg_batch = 8;  // (a run never depends on the one before it)
 
-  ADMM_HIP_TRY(hipEventRecord(o->ev0, o->stream));
+  ADMM_TRY(begin_timing(*o));
   launch_srg_elem(ea, true, o->stream);  // V = (s + z0) - u0
   bool all = false;
   for (int32_t it = 0; it < N && !all; ++it) {
-    launch_spmm(o->sp.t, o->V, o->Y, o->chunks, run, o->stream);  // y = D'((s + z) - u)
-    ADMM_TRY(srg_solve(o, ca, it == 0));
-    launch_spmm(o->sp.n, o->X, o->T, o->chunks, run, o->stream);  // D x
+    launch_spmm(cg.sp.t, o->V, cg.Y, cg.chunks, run, o->stream);  // y = D'((s + z) - u)
+    ADMM_TRY(cg.solve(ca, it == 0));
+    launch_spmm(cg.sp.n, cg.X, cg.T, cg.chunks, run, o->stream);  // D x
     launch_srg_elem(ea, false, o->stream);
     if (dual) {
-      launch_spmm(o->sp.t, o->DZ, o->R, o->chunks, run, o->stream);  // D'(z - zprev)
-      launch_spmm(o->sp.t, o->U, o->P, o->chunks, run, o->stream);   // D'u
+      launch_spmm(cg.sp.t, o->DZ, cg.R, cg.chunks, run, o->stream);  // D'(z - zprev)
+      launch_spmm(cg.sp.t, o->U, cg.P, cg.chunks, run, o->stream);   // D'u
       launch_srg_dual(da, o->stream);
     }
     launch_srg_fin(fa, o->stream);
-    if ((it + 1) % check_every == 0 || it + 1 == N) {
-      ADMM_HIP_TRY(hipMemcpyAsync(o->rec_host, o->rec, sizeof(OvrRec) * K, hipMemcpyDeviceToHost, o->stream));
-      ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
-      all = true;
-      for (int32_t c = 0; c < K; ++c) all = all && o->rec_host[c].stop != 0;
-    }
+    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
-  ADMM_HIP_TRY(hipEventRecord(o->ev1, o->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
-  ADMM_HIP_TRY(hipGetLastError());
-  if (!all) return fail(ADMM_E_DEVICE, "the sparse multi-fit loop ended with fits still running");
-  float ms = 0.f;
-  ADMM_HIP_TRY(hipEventElapsedTime(&ms, o->ev0, o->ev1));
-  if (runtime_s) *runtime_s = 1e-3 * static_cast<double>(ms);
-  o->steps.assign(static_cast<size_t>(K), 0);
-  std::vector<double> objh;
-  if (op.objevals) {
-    objh.resize(static_cast<size_t>(N) * K);
-    ADMM_HIP_TRY(hipMemcpy(objh.data(), o->objv, sizeof(double) * N * K, hipMemcpyDeviceToHost));
-  }
-  std::vector<SsvCg> cgh(static_cast<size_t>(K));
-  ADMM_HIP_TRY(hipMemcpy(cgh.data(), o->cg, sizeof(SsvCg) * K, hipMemcpyDeviceToHost));
-  for (int32_t c = 0; c < K; ++c) {
-    const OvrRec& r = o->rec_host[c];
-    o->steps[c] = r.steps;
-    if (summaries) {
-      summaries[c].steps = r.steps;
-      summaries[c].stopped_early = r.early;
-      summaries[c].objopt = (op.objevals && r.steps > 0) ? objh[static_cast<size_t>(c) * N + r.steps - 1]
-                                                         : __builtin_nan("");
-      summaries[c].cg_iters_total = cgh[c].total;
-      summaries[c].cg_capped_updates = cgh[c].capped;
-    }
-  }
+  ADMM_TRY(finish_run(*o, all, "the sparse multi-fit loop ended with fits still running", N, op.objevals != 0, o->objv,
+                      runtime_s, summaries));
+  ADMM_TRY(cg.fill_counters(summaries, K));
   o->last = op;
   o->has_run = true;
   return ADMM_OK;
@@ -592,78 +381,34 @@ int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts,
 
 int admm_sparse_reg_set_weights(admm_sparse_reg* o, const double* weights) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
-  if (weights)  // (a refused call changes nothing)
-    for (int64_t i = 0; i < o->m; ++i)
-      if (!finite_nonneg(weights[i]))
-        return fail(ADMM_E_INVALID, "loss: weight " + std::to_string(i) + " is negative or not finite");
-  ADMM_HIP_TRY(hipSetDevice(o->device));
-  double* w = nullptr;
-  if (weights) {
-    ADMM_TRY(o->mem.alloc(&w, static_cast<size_t>(o->m)));
-    ADMM_HIP_TRY(hipMemcpyAsync(w, weights, sizeof(double) * o->m, hipMemcpyHostToDevice, o->stream));
-    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (the caller's buffer is read until here)
-  }
-  if (o->W) o->mem.free_one(o->W);
-  o->W = w;
-  return ADMM_OK;
+  return set_shared_weights(*o, o->m, weights, &o->W);
 }
 
 int admm_sparse_reg_fetch(admm_sparse_reg* o, int field, double* dst, size_t cap, size_t* written) {
   if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
   if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
   ADMM_HIP_TRY(hipSetDevice(o->device));
-  const int32_t K = o->K;
-  auto matrix = [&](const double* src, int64_t rows) -> int {
-    const size_t need = static_cast<size_t>(rows) * K;
-    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
-    std::vector<double> h(static_cast<size_t>(o->chunks) * rows * kSpmmChunk);
-    ADMM_HIP_TRY(hipMemcpy(h.data(), src, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-    spmm_unpack(h.data(), rows, K, dst, rows);
-    if (written) *written = need;
-    return ADMM_OK;
-  };
-  auto history = [&](const double* src) -> int {
-    int32_t S = 0;
-    for (int32_t s : o->steps) S = s > S ? s : S;
-    const size_t need = static_cast<size_t>(S) * K;
-    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
-    if (S > 0)
-      ADMM_HIP_TRY(hipMemcpy2D(dst, S * sizeof(double), src, o->hist_ld * sizeof(double), S * sizeof(double), K,
-                               hipMemcpyDeviceToHost));
-    for (int32_t c = 0; c < K; ++c)
-      for (int32_t i = o->steps[c]; i < S; ++i) dst[static_cast<size_t>(c) * S + i] = __builtin_nan("");
-    if (written) *written = need;
-    return ADMM_OK;
-  };
   switch (field) {
-    case ADMM_SRG_F_XOPT: return matrix(o->X, o->n);
-    case ADMM_SRG_F_ZOPT: return matrix(o->Z, o->m);
-    case ADMM_SRG_F_UOPT: return matrix(o->U, o->m);
-    case ADMM_SRG_F_PNORM: return history(o->pnorm);
-    case ADMM_SRG_F_PERR: return history(o->perr);
+    case ADMM_SRG_F_XOPT: return o->cg.fetch_matrix(o->cg.X, o->n, dst, cap, written);
+    case ADMM_SRG_F_ZOPT: return o->cg.fetch_matrix(o->Z, o->m, dst, cap, written);
+    case ADMM_SRG_F_UOPT: return o->cg.fetch_matrix(o->U, o->m, dst, cap, written);
+    case ADMM_SRG_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
+    case ADMM_SRG_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
     case ADMM_SRG_F_OBJEVALS:
       if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return history(o->objv);
+      return fetch_history(*o, o->objv, dst, cap, written);
     case ADMM_SRG_F_DNORM:
     case ADMM_SRG_F_DERR:
       if (o->last.nodualerror)
         return fail(ADMM_E_INVALID, "the last run did not evaluate the dual residual (nodualerror = 1)");
-      return history(field == ADMM_SRG_F_DNORM ? o->dnorm : o->derr);
+      return fetch_history(*o, field == ADMM_SRG_F_DNORM ? o->dnorm : o->derr, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the sparse multi-fit regression");
   }
 }
 
 void admm_sparse_reg_destroy(admm_sparse_reg* o) {
   if (!o) return;
-  (void)hipSetDevice(o->device);
-  if (o->stream) (void)hipStreamSynchronize(o->stream);
-  if (o->ev0) (void)hipEventDestroy(o->ev0);
-  if (o->ev1) (void)hipEventDestroy(o->ev1);
-  o->mem.release();
-  sparse_device_free(&o->sp);
-  if (o->poll) (void)hipHostFree(o->poll);
-  if (o->rec_host) (void)hipHostFree(o->rec_host);
-  if (o->stream) (void)hipStreamDestroy(o->stream);
+  o->cg.destroy();
   delete o;
 }
 

@@ -1,24 +1,14 @@
 // svm_ovr.h -- argument blocks of the one-vs-rest linear-SVM kernels (svm_ovr.hip): K independent unwrapped-ADMM runs
 // (unwrappedadmm.m:76-92) over ONE matrix D.
 #pragma once
-#include "common.h"
+#include "multi_device.h"
 
 namespace admm {
 
 constexpr int kOvrChunk = 10;      // classes one pass over D serves (registers and LDS of the pass)
-constexpr int kOvrMaxWg = 256;     // persistent workgroups of the pass: one per CU
-constexpr int kOvrTile = 64;       // columns per workgroup of the partial-row sum / rows of the x-solve
 
 // the sums a class's stop test and objective need (admm.m:621-658, 305-306; linearsvm.m:231-237)
 enum OvrSlot : int32_t { OV_R2 = 0, OV_AX2 = 1, OV_Z2 = 2, OV_DZ2 = 3, OV_DU2 = 4, OV_OBJX = 5, OV_COUNT = 6 };
-
-// control record of ONE class (an array of K of them; the single-run Ctrl block is not involved)
-struct OvrRec {
-  int32_t stop;   // this class has met a stop condition or maxiters: frozen, every kernel skips it
-  int32_t iter;   // completed iterations
-  int32_t steps;  // results.steps (admm.m:746)
-  int32_t early;  // a stop condition fired (admm.m:710-722), as opposed to maxiters running out
-};
 
 struct OvrPassArgs {
   const double* D;     // m x n, column-major
@@ -31,8 +21,8 @@ struct OvrPassArgs {
   int64_t ldz;
   const int32_t* loss; // K values ADMM_LOSS_*
   double* gpart;       // [workgroups][K][ldx] partial rows of D'(z - u): the next x-update's right-hand side
-  double* part;        // [K][OV_COUNT][kOvrMaxWg] block partials of the residual sums
-  const OvrRec* rec;   // K
+  double* part;        // [K][OV_COUNT][kMultiMaxWg] block partials of the residual sums
+  const MultiRec* rec;   // K
   int32_t K, c0;       // classes c0 .. c0 + kOvrChunk - 1 belong to this launch
   int32_t objevals;
   double rho, C;
@@ -46,7 +36,7 @@ struct OvrFinArgs {
   int64_t ldx, n, m;
   int32_t K, nwg;
   int32_t fin;          // 0: partial-row sums only (before the first iteration)
-  OvrRec* rec;
+  MultiRec* rec;
   double *pnorm, *perr, *hnorm, *objv;  // [K][hist_ld]
   int64_t hist_ld;
   double rho, C, abstol, reltol, Hnormtol;
@@ -59,7 +49,7 @@ struct OvrSolveArgs {
   const double* gsum;
   double* X;
   int64_t ldx;
-  const OvrRec* rec;
+  const MultiRec* rec;
 };
 
 // the costs of a pass whose chunk takes the cost form of the element update
@@ -74,7 +64,7 @@ void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, const OvrCo
 void launch_ovr_gsum_fin(const OvrFinArgs& a, hipStream_t stream);
 void launch_ovr_xsolve(const OvrSolveArgs& a, int32_t K, hipStream_t stream);
 // X(:, c) = Xnew(:, c) for every class that has not stopped (the triangular-solve form of the x-update)
-void launch_ovr_xcopy(const double* Xnew, double* X, int64_t ldx, int64_t n, int32_t K, const OvrRec* rec,
+void launch_ovr_xcopy(const double* Xnew, double* X, int64_t ldx, int64_t n, int32_t K, const MultiRec* rec,
                       hipStream_t stream);
 
 }  // namespace admm

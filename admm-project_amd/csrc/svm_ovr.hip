@@ -16,7 +16,7 @@
 // All loads of D are unconditional on clamped addresses (x is zero beyond n; rows beyond m carry t = 0).
 #include <vector>
 
-#include "engine_internal.h"
+#include "multi_host.h"
 #include "prox_device.h"
 #include "svm_cost_device.h"
 #include "svm_ovr.h"
@@ -213,68 +213,31 @@ __global__ __launch_bounds__(kOvWaves* kWave) void ovr_pass_kernel(OvrPassArgs a
 #pragma unroll
       for (int q = 0; q < OV_COUNT; ++q) {
         const double v = wave_sum(acc[s][slot_of[q]]);
-        if (lane == 0) a.part[(static_cast<int64_t>(a.c0 + c) * OV_COUNT + q) * kOvrMaxWg + blockIdx.x] = v;
+        if (lane == 0) a.part[(static_cast<int64_t>(a.c0 + c) * OV_COUNT + q) * kMultiMaxWg + blockIdx.x] = v;
       }
     }
   }
 }
 
-// blockIdx.y = class.  blockIdx.x < tiles: g_c[64 columns] = sum over the workgroups' partial rows, wave q takes rows
-// q, q + 4, ... sixteen loads at a time, the four wave sums added in wave order.  The extra workgroup (a.fin): the
-// finalize logic of the class's iteration -- admm.m:612-722 as oracle/admm_ref.py restates it, for plain ADMM with
-// nodualerror = 1 and stopcond = 'both'.
+// blockIdx.y = class.  blockIdx.x < tiles: g_c[64 columns] = sum over the workgroups' partial rows (multi_gsum_tile).
+// The extra workgroup (a.fin): the finalize logic of the class's iteration -- admm.m:612-722 as oracle/admm_ref.py
+// restates it, for plain ADMM with nodualerror = 1 and stopcond = 'both'.
 __global__ __launch_bounds__(kBlock) void ovr_gsum_fin_kernel(OvrFinArgs a) {
   const int cls = blockIdx.y;
-  OvrRec* rec = a.rec + cls;
+  MultiRec* rec = a.rec + cls;
   const int32_t stopped = rec->stop;
   const int32_t it = rec->iter;
   if (stopped) return;
-  __shared__ double sq[4][kOvrTile];
+  __shared__ double sq[4][kMultiTile];
   __shared__ double S[8];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int tiles = static_cast<int>((a.n + kOvrTile - 1) / kOvrTile);
+  const int tiles = static_cast<int>((a.n + kMultiTile - 1) / kMultiTile);
   if (static_cast<int>(blockIdx.x) < tiles) {
-    const int64_t j0 = static_cast<int64_t>(blockIdx.x) * kOvrTile;
-    const int64_t j = (j0 + lane < a.n) ? j0 + lane : a.n - 1;
-    const double* __restrict__ G = a.gpart + static_cast<int64_t>(cls) * a.ldx + j;
-    const int64_t rowstride = static_cast<int64_t>(a.K) * a.ldx;
-    double s = 0.0;
-    for (int32_t b0 = wid; b0 < a.nwg; b0 += 64) {
-      double v[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int32_t b = (b0 + 4 * k < a.nwg) ? b0 + 4 * k : a.nwg - 1;
-        v[k] = G[static_cast<int64_t>(b) * rowstride];
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) s += (b0 + 4 * k < a.nwg) ? v[k] : 0.0;
-    }
-    sq[wid][lane] = s;
-    __syncthreads();
-    if (wid == 0 && j0 + lane < a.n)
-      a.gsum[static_cast<int64_t>(cls) * a.ldx + j0 + lane] = ((sq[0][lane] + sq[1][lane]) + sq[2][lane]) + sq[3][lane];
+    multi_gsum_tile(a.gpart, a.gsum, cls, a.ldx, a.n, a.K, a.nwg, sq);
     return;
   }
-  // ---- finalize of class cls: 32 lanes per slot stride over the block partials, then a fixed shuffle tree
-  {
-    const int slot = tid >> 5, sub = tid & 31;
-    double v = 0.0;
-    if (slot < OV_COUNT) {
-      const double* __restrict__ ps = a.part + (static_cast<int64_t>(cls) * OV_COUNT + slot) * kOvrMaxWg;
-      double wv[kOvrMaxWg / 32];
-#pragma unroll
-      for (int k = 0; k < kOvrMaxWg / 32; ++k) {
-        const int b = sub + 32 * k;
-        wv[k] = ps[b < a.nwg ? b : a.nwg - 1];
-      }
-#pragma unroll
-      for (int k = 0; k < kOvrMaxWg / 32; ++k)
-        if (sub + 32 * k < a.nwg) v += wv[k];
-    }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (sub == 0 && slot < 8) S[slot] = v;
-  }
+  // ---- finalize of class cls
+  multi_slot_totals_unrolled(a.part, cls, OV_COUNT, a.nwg, S);
   double xx = 0.0;
   if (a.objevals) {
     const double* __restrict__ x = a.X + static_cast<int64_t>(cls) * a.ldx;
@@ -298,10 +261,7 @@ __global__ __launch_bounds__(kBlock) void ovr_gsum_fin_kernel(OvrFinArgs a) {
   bool stop = false;
   if (!a.domaxiters && pn < pe) stop = true;                        // admm.m:710-713, nodualerror
   if (!a.domaxiters && i1 > 2 && hn <= a.Hnormtol) stop = true;     // admm.m:719-722
-  rec->iter = i1;
-  rec->steps = i1;
-  if (stop) rec->early = 1;
-  if (stop || i1 >= a.maxiters) rec->stop = 1;
+  multi_stop_tail(rec, stop, i1, a.maxiters);
 }
 
 // x_c(64 rows) = M(64 rows, :) g_c: lane = row (M is symmetric: column-major reads are coalesced along the row index),
@@ -310,12 +270,12 @@ __global__ __launch_bounds__(kBlock) void ovr_xsolve_kernel(OvrSolveArgs a) {
   const int cls = blockIdx.y;
   if (a.rec[cls].stop) return;
   __shared__ double gs[kOvMaxN + 32];  // (the unrolled column loop reads up to 28 entries past its start: zeros)
-  __shared__ double red[4][kOvrTile];
+  __shared__ double red[4][kMultiTile];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int64_t n = a.n;
   for (int j = tid; j < kOvMaxN + 32; j += kBlock) gs[j] = j < n ? a.gsum[static_cast<int64_t>(cls) * a.ldx + j] : 0.0;
   __syncthreads();
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kOvrTile + lane;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kMultiTile + lane;
   const double* __restrict__ mrow = a.M + (i < n ? i : n - 1);
   double s = 0.0;
   for (int j0 = wid; j0 < n; j0 += 4 * 8) {
@@ -335,7 +295,7 @@ __global__ __launch_bounds__(kBlock) void ovr_xsolve_kernel(OvrSolveArgs a) {
 }
 
 __global__ __launch_bounds__(kBlock) void ovr_xcopy_kernel(const double* __restrict__ Xnew, double* __restrict__ X,
-                                                           int64_t ldx, int64_t n, const OvrRec* __restrict__ rec) {
+                                                           int64_t ldx, int64_t n, const MultiRec* __restrict__ rec) {
   const int cls = blockIdx.y;
   if (rec[cls].stop) return;
   const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -343,7 +303,7 @@ __global__ __launch_bounds__(kBlock) void ovr_xcopy_kernel(const double* __restr
 }
 
 int ovr_pass_workgroups(int64_t m) {
-  return static_cast<int>(std::min<int64_t>(ceil_div(m, int64_t{kOvRows}), kOvrMaxWg));  // one per CU
+  return static_cast<int>(std::min<int64_t>(ceil_div(m, int64_t{kOvRows}), kMultiMaxWg));  // one per CU
 }
 
 void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, const OvrCostArgs* cost, hipStream_t stream) {
@@ -357,18 +317,18 @@ void launch_ovr_pass(const OvrPassArgs& a, bool init, bool logistic, const OvrCo
 }
 
 void launch_ovr_gsum_fin(const OvrFinArgs& a, hipStream_t stream) {
-  const unsigned tiles = static_cast<unsigned>(ceil_div(a.n, int64_t{kOvrTile}));
+  const unsigned tiles = static_cast<unsigned>(ceil_div(a.n, int64_t{kMultiTile}));
   hipLaunchKernelGGL(ovr_gsum_fin_kernel, dim3(tiles + (a.fin ? 1u : 0u), static_cast<unsigned>(a.K)), dim3(kBlock), 0,
                      stream, a);
 }
 
 void launch_ovr_xsolve(const OvrSolveArgs& a, int32_t K, hipStream_t stream) {
   hipLaunchKernelGGL(ovr_xsolve_kernel,
-                     dim3(static_cast<unsigned>(ceil_div(a.n, int64_t{kOvrTile})), static_cast<unsigned>(K)),
+                     dim3(static_cast<unsigned>(ceil_div(a.n, int64_t{kMultiTile})), static_cast<unsigned>(K)),
                      dim3(kBlock), 0, stream, a);
 }
 
-void launch_ovr_xcopy(const double* Xnew, double* X, int64_t ldx, int64_t n, int32_t K, const OvrRec* rec,
+void launch_ovr_xcopy(const double* Xnew, double* X, int64_t ldx, int64_t n, int32_t K, const MultiRec* rec,
                       hipStream_t stream) {
   hipLaunchKernelGGL(ovr_xcopy_kernel, dim3(static_cast<unsigned>(ceil_div(n, int64_t{kBlock})), static_cast<unsigned>(K)),
                      dim3(kBlock), 0, stream, Xnew, X, ldx, n, rec);
@@ -377,18 +337,9 @@ void launch_ovr_xcopy(const double* Xnew, double* X, int64_t ldx, int64_t n, int
 }  // namespace admm
 
 // ---------------------------------------------------------------------------------------------------------- the object
-struct admm_svm_ovr {
-  admm_engine* eng = nullptr;  // an ordinary ADMM_PROB_LINEARSVM engine: owns D and the factor of D'D; never run
-  hipStream_t stream = nullptr;  // = eng->stream
-  DevMem mem;
-  int device = 0;
-  int64_t m = 0, n = 0, ldx = 0, ldz = 0;
-  int32_t K = 0, nwg = 0;
+struct admm_svm_ovr : DenseMulti {  // eng: an ordinary ADMM_PROB_LINEARSVM engine
   double C = 0.0;
-  const double* M = nullptr;   // the explicit n x n map (the engine's, or Dplus*Dplus'); null: triangular solves
-  int64_t ldM = 0;
-  double *X = nullptr, *Z = nullptr, *U = nullptr, *ELL = nullptr, *gpart = nullptr, *gsum = nullptr, *part = nullptr,
-         *xtmp = nullptr;
+  double* ELL = nullptr;
   int32_t* loss = nullptr;
   std::vector<char> chunk_logistic;  // per chunk of kOvrChunk classes: one of them has ADMM_LOSS_LOGISTIC
   // costs (admm_svm_ovr_set_cost): defaults = the kernels of a run without them, bit for bit
@@ -396,39 +347,14 @@ struct admm_svm_ovr {
   std::vector<double> cost_host;     // K x 2 (cost_pos, cost_neg); all ones by default
   double* W = nullptr;               // m shared weights on the device, or null: every weight is 1
   double* CC = nullptr;              // cost_host on the device
-  std::vector<char> chunk_cost;      // per chunk: weights, a class cost != 1 or ADMM_LOSS_SQHINGE -> the cost form
-  OvrRec* rec = nullptr;
-  OvrRec* rec_host = nullptr;  // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // histories of the last run: [K][hist_ld]
-  double *pnorm = nullptr, *perr = nullptr, *hnorm = nullptr, *objv = nullptr;
-  int32_t hist_ld = 0;
-  bool has_run = false;
+  std::vector<int32_t> chunk_cost;   // per chunk: weights, a class cost != 1 or ADMM_LOSS_SQHINGE -> the cost form
+  double *pnorm = nullptr, *perr = nullptr, *hnorm = nullptr, *objv = nullptr;  // histories
   admm_svm_ovr_options last{};
-  std::vector<int32_t> steps;
 };
 
 namespace {
 
 const char* kPerClass = ": run one ADMM_PROB_LINEARSVM engine (admm_engine_create) per class instead";
-
-int ovr_upload_cols(admm_svm_ovr* o, double* dst, int64_t ld, const double* src, int64_t rows, int kind) {
-  if (!src) {
-    ADMM_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * ld * o->K, o->stream));
-    return ADMM_OK;
-  }
-  ADMM_HIP_TRY(hipMemcpy2DAsync(dst, ld * sizeof(double), src, rows * sizeof(double), rows * sizeof(double), o->K,
-                                kind == ADMM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o->stream));
-  return ADMM_OK;
-}
-
-// which chunks run the cost form of the pass: the squared hinge lives there alone, and so does every cost
-void ovr_plan_cost(admm_svm_ovr* o) {
-  o->chunk_cost.assign(static_cast<size_t>((o->K + kOvrChunk - 1) / kOvrChunk), 0);
-  for (int32_t c = 0; c < o->K; ++c)
-    if (o->W || o->loss_host[c] == ADMM_LOSS_SQHINGE || o->cost_host[2 * c] != 1.0 || o->cost_host[2 * c + 1] != 1.0)
-      o->chunk_cost[c / kOvrChunk] = 1;
-}
 
 int ovr_setup(admm_svm_ovr* o, const admm_svm_ovr_desc* desc) {
   const int64_t m = desc->m, n = desc->n;
@@ -446,16 +372,8 @@ int ovr_setup(admm_svm_ovr* o, const admm_svm_ovr_desc* desc) {
   d.mem = desc->mem;
   d.device = desc->device;
   ADMM_TRY(admm_engine_create(&d, &o->eng));
-  admm_engine* e = o->eng;
-  o->stream = e->stream;
-  o->device = e->device;
-  o->m = m;
-  o->n = n;
-  o->K = K;
+  o->stream = o->eng->stream;
   o->C = desc->C;
-  o->ldx = round_up(n, 2);
-  o->ldz = round_up(m, 2);
-  o->nwg = ovr_pass_workgroups(m);
   if (desc->Dplus) {  // (D'D)^+ = Dplus*Dplus' from the caller's pseudo-inverse (linearsvm.m:185-186)
     double *Dp = nullptr, *Mo = nullptr;
     ADMM_TRY(upload(o->mem, &Dp, desc->Dplus, static_cast<size_t>(n) * m, desc->mem, o->stream));
@@ -467,58 +385,23 @@ int ovr_setup(admm_svm_ovr* o, const admm_svm_ovr_desc* desc) {
     o->mem.free_one(Dp);
     o->M = Mo;
     o->ldM = ld;
-  } else if (e->xfac.mode == ADMM_XSOLVE_INVERSE && e->xfac.Minv && !e->xfac.planSy.packed) {
-    o->M = e->xfac.Minv;  // (D'D)^-1, or (D'D)^+ of a rank-deficient D: full symmetric storage below kSymvHalfMin
-    o->ldM = e->xfac.ldM;
-  } else if (e->xfac.mode == ADMM_XSOLVE_TRSV && e->xfac.F) {
-    // create's accuracy probe kept the triangular solves: they run per class (K small launches), nothing is forced
-    ADMM_TRY(o->mem.alloc(&o->xtmp, static_cast<size_t>(o->ldx) * K));
-    ADMM_HIP_TRY(hipMemsetAsync(o->xtmp, 0, sizeof(double) * o->ldx * K, o->stream));
-  } else {
-    return fail(ADMM_E_UNSUPPORTED, std::string("the engine built no n x n form of the x-update for this D") + kPerClass);
   }
-  ADMM_TRY(o->mem.alloc(&o->X, static_cast<size_t>(o->ldx) * K));
-  ADMM_TRY(o->mem.alloc(&o->gsum, static_cast<size_t>(o->ldx) * K));
-  ADMM_HIP_TRY(hipMemsetAsync(o->gsum, 0, sizeof(double) * o->ldx * K, o->stream));
-  ADMM_TRY(o->mem.alloc(&o->Z, static_cast<size_t>(o->ldz) * K));
-  ADMM_TRY(o->mem.alloc(&o->U, static_cast<size_t>(o->ldz) * K));
+  ADMM_TRY(dense_setup(*o, m, n, K, OV_COUNT, kPerClass));
   ADMM_TRY(o->mem.alloc(&o->ELL, static_cast<size_t>(o->ldz) * K));
   ADMM_HIP_TRY(hipMemsetAsync(o->ELL, 0, sizeof(double) * o->ldz * K, o->stream));
-  ADMM_TRY(ovr_upload_cols(o, o->ELL, o->ldz, desc->ELL, m, desc->mem));
-  ADMM_TRY(o->mem.alloc(&o->gpart, static_cast<size_t>(o->nwg) * K * o->ldx));
-  ADMM_TRY(o->mem.alloc(&o->part, static_cast<size_t>(K) * OV_COUNT * kOvrMaxWg));
-  ADMM_HIP_TRY(hipMemsetAsync(o->part, 0, sizeof(double) * K * OV_COUNT * kOvrMaxWg, o->stream));
-  double* raw = nullptr;
-  ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(int32_t) + 7) / 8));
-  o->loss = reinterpret_cast<int32_t*>(raw);
-  std::vector<int32_t> lh(static_cast<size_t>(K), ADMM_LOSS_HINGE);
-  if (desc->loss)
-    for (int32_t c = 0; c < K; ++c) lh[c] = desc->loss[c];
+  ADMM_TRY(upload_cols(*o, o->ELL, o->ldz, desc->ELL, m, K, desc->mem));
+  ADMM_TRY(alloc_words(*o, &o->loss, static_cast<size_t>(K)));
+  o->loss_host.assign(static_cast<size_t>(K), ADMM_LOSS_HINGE);
+  if (desc->loss) o->loss_host.assign(desc->loss, desc->loss + K);
   o->chunk_logistic.assign(static_cast<size_t>((K + kOvrChunk - 1) / kOvrChunk), 0);
   for (int32_t c = 0; c < K; ++c)
-    if (lh[c] == ADMM_LOSS_LOGISTIC) o->chunk_logistic[c / kOvrChunk] = 1;
-  ADMM_HIP_TRY(hipMemcpyAsync(o->loss, lh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
-  o->loss_host = lh;
+    if (o->loss_host[c] == ADMM_LOSS_LOGISTIC) o->chunk_logistic[c / kOvrChunk] = 1;
+  ADMM_HIP_TRY(hipMemcpyAsync(o->loss, o->loss_host.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
   o->cost_host.assign(static_cast<size_t>(2 * K), 1.0);
   ADMM_TRY(o->mem.alloc(&o->CC, static_cast<size_t>(2 * K)));
   ADMM_HIP_TRY(hipMemcpyAsync(o->CC, o->cost_host.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice, o->stream));
-  ovr_plan_cost(o);
-  ADMM_TRY(o->mem.alloc(&raw, (static_cast<size_t>(K) * sizeof(OvrRec) + 7) / 8));
-  o->rec = reinterpret_cast<OvrRec*>(raw);
-  ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
-  ADMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&o->rec_host), sizeof(OvrRec) * K));
-  ADMM_HIP_TRY(hipEventCreate(&o->ev0));
-  ADMM_HIP_TRY(hipEventCreate(&o->ev1));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (lh, and the caller's buffers, were read)
-  return ADMM_OK;
-}
-
-int ovr_poll(admm_svm_ovr* o, bool* all_stopped) {
-  ADMM_HIP_TRY(hipMemcpyAsync(o->rec_host, o->rec, sizeof(OvrRec) * o->K, hipMemcpyDeviceToHost, o->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
-  bool all = true;
-  for (int32_t c = 0; c < o->K; ++c) all = all && o->rec_host[c].stop != 0;
-  *all_stopped = all;
+  o->chunk_cost = svm_cost_chunks(K, kOvrChunk, false, o->loss_host, o->cost_host);
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (the host vectors, and the caller's buffers, were read)
   return ADMM_OK;
 }
 
@@ -556,11 +439,7 @@ int admm_svm_ovr_create(const admm_svm_ovr_desc* desc, admm_svm_ovr** out) {
   if (!desc->D || desc->m <= 0 || desc->n <= 0) return fail(ADMM_E_INVALID, "the linear SVM needs D (m x n)");
   if (!desc->ELL) return fail(ADMM_E_INVALID, "the linear SVM needs the label matrix ELL (m x K)");
   if (!(desc->C >= 0.0)) return fail(ADMM_E_INVALID, "Given regularization parameter C is not a nonnegative number!");
-  if (desc->loss)
-    for (int32_t c = 0; c < desc->K; ++c)
-      if (desc->loss[c] != ADMM_LOSS_HINGE && desc->loss[c] != ADMM_LOSS_01 && desc->loss[c] != ADMM_LOSS_HINGE_OBJ01 &&
-          desc->loss[c] != ADMM_LOSS_LOGISTIC && desc->loss[c] != ADMM_LOSS_SQHINGE)
-        return fail(ADMM_E_INVALID, "bad loss for class " + std::to_string(c));
+  ADMM_TRY(check_svm_losses(desc->K, desc->loss));
   if (desc->comm)
     return fail(ADMM_E_UNSUPPORTED, std::string("the one-vs-rest linear SVM is not row-sharded") + kPerClass);
   if (desc->n > kOvMaxN)
@@ -583,30 +462,11 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
   if (opts->struct_size != static_cast<int32_t>(sizeof(admm_svm_ovr_options)))
     return fail(ADMM_E_INVALID, "admm_svm_ovr_options.struct_size mismatch (ABI version skew)");
   admm_svm_ovr_options op = *opts;
-  if (op.fast != ADMM_FAST_OFF)
-    return fail(ADMM_E_UNSUPPORTED, std::string("fast / accelerated ADMM is not part of the one-vs-rest loop") + kPerClass);
-  if (op.relax != 1.0)
-    return fail(ADMM_E_UNSUPPORTED, std::string("relaxation is not part of the one-vs-rest loop") + kPerClass);
-  if (op.convtest)
-    return fail(ADMM_E_UNSUPPORTED, std::string("convtest is not part of the one-vs-rest loop") + kPerClass);
-  if (!(op.rho > 0.0)) return fail(ADMM_E_INVALID, "options.rho must be positive");
-  if (op.maxiters <= 0) op.maxiters = 1000;  // admm.m:334-339
+  ADMM_TRY(check_run_options("one-vs-rest", kPerClass, &op));
   ADMM_HIP_TRY(hipSetDevice(o->device));
   const int32_t N = op.maxiters, K = o->K;
-  if (o->hist_ld != N) {
-    for (double** p : {&o->pnorm, &o->perr, &o->hnorm, &o->objv}) {
-      o->mem.free_one(*p);
-      *p = nullptr;
-      ADMM_TRY(o->mem.alloc(p, static_cast<size_t>(N) * K));
-    }
-    o->hist_ld = N;
-  }
-  o->has_run = false;
-  ADMM_HIP_TRY(hipMemsetAsync(o->rec, 0, sizeof(OvrRec) * K, o->stream));
-  ADMM_TRY(ovr_upload_cols(o, o->X, o->ldx, op.x0, o->n, ADMM_MEM_HOST));
-  ADMM_TRY(ovr_upload_cols(o, o->Z, o->ldz, op.z0, o->m, ADMM_MEM_HOST));
-  ADMM_TRY(ovr_upload_cols(o, o->U, o->ldz, op.u0, o->m, ADMM_MEM_HOST));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (host buffers were read)
+  ADMM_TRY(resize_histories(*o, {&o->pnorm, &o->perr, &o->hnorm, &o->objv}, N));
+  ADMM_TRY(dense_start(*o, op.x0, op.z0, op.u0));
 
   OvrPassArgs pa{};
   pa.D = o->eng->D;
@@ -651,14 +511,6 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
   fa.domaxiters = op.domaxiters;
   fa.objevals = op.objevals;
   fa.maxiters = N;
-  OvrSolveArgs sa{};
-  sa.M = o->M;
-  sa.ldM = o->ldM;
-  sa.n = o->n;
-  sa.gsum = o->gsum;
-  sa.X = o->X;
-  sa.ldx = o->ldx;
-  sa.rec = o->rec;
   const OvrCostArgs oc{o->W, o->CC};
   const int32_t chunks = (K + kOvrChunk - 1) / kOvrChunk;
   auto pass = [&](bool init) {
@@ -669,48 +521,20 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
   };
   const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
 
-  ADMM_HIP_TRY(hipEventRecord(o->ev0, o->stream));
+  ADMM_TRY(begin_timing(*o));
   pass(true);  // g = D'(z0 - u0)
   fa.fin = 0;
   launch_ovr_gsum_fin(fa, o->stream);
   fa.fin = 1;
   bool all = false;
   for (int32_t it = 0; it < N && !all; ++it) {
-    if (o->M) {
-      launch_ovr_xsolve(sa, K, o->stream);
-    } else {
-      for (int32_t c = 0; c < K; ++c)
-        launch_trsv_pair(o->eng->xfac.trsv, o->gsum + static_cast<int64_t>(c) * o->ldx,
-                         o->xtmp + static_cast<int64_t>(c) * o->ldx, nullptr, o->stream);
-      launch_ovr_xcopy(o->xtmp, o->X, o->ldx, o->n, K, o->rec, o->stream);
-    }
+    dense_xupdate(*o);
     pass(false);
     launch_ovr_gsum_fin(fa, o->stream);
-    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(ovr_poll(o, &all));
+    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
-  ADMM_HIP_TRY(hipEventRecord(o->ev1, o->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
-  ADMM_HIP_TRY(hipGetLastError());
-  if (!all) return fail(ADMM_E_DEVICE, "the one-vs-rest loop ended with classes still running");
-  float ms = 0.f;
-  ADMM_HIP_TRY(hipEventElapsedTime(&ms, o->ev0, o->ev1));
-  if (runtime_s) *runtime_s = 1e-3 * static_cast<double>(ms);
-  o->steps.assign(static_cast<size_t>(K), 0);
-  std::vector<double> objh;
-  if (op.objevals) {
-    objh.resize(static_cast<size_t>(N) * K);
-    ADMM_HIP_TRY(hipMemcpy(objh.data(), o->objv, sizeof(double) * N * K, hipMemcpyDeviceToHost));
-  }
-  for (int32_t c = 0; c < K; ++c) {
-    const OvrRec& r = o->rec_host[c];
-    o->steps[c] = r.steps;
-    if (summaries) {
-      summaries[c].steps = r.steps;
-      summaries[c].stopped_early = r.early;
-      summaries[c].objopt = (op.objevals && r.steps > 0) ? objh[static_cast<size_t>(c) * N + r.steps - 1]
-                                                         : __builtin_nan("");
-    }
-  }
+  ADMM_TRY(finish_run(*o, all, "the one-vs-rest loop ended with classes still running", N, op.objevals != 0, o->objv,
+                      runtime_s, summaries));
   o->last = op;
   o->has_run = true;
   return ADMM_OK;
@@ -718,21 +542,8 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
 
 int admm_svm_ovr_set_cost(admm_svm_ovr* o, const double* weights, const double* class_cost) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
-  ADMM_TRY(check_svm_cost(weights, o->m, class_cost, 2 * static_cast<int64_t>(o->K)));  // (a refused call changes nothing)
-  ADMM_HIP_TRY(hipSetDevice(o->device));
-  double* w = nullptr;
-  if (weights) {
-    ADMM_TRY(o->mem.alloc(&w, static_cast<size_t>(o->m)));
-    ADMM_HIP_TRY(hipMemcpyAsync(w, weights, sizeof(double) * o->m, hipMemcpyHostToDevice, o->stream));
-  }
-  std::vector<double> cc(static_cast<size_t>(2 * o->K), 1.0);
-  if (class_cost) cc.assign(class_cost, class_cost + 2 * o->K);
-  ADMM_HIP_TRY(hipMemcpyAsync(o->CC, cc.data(), sizeof(double) * 2 * o->K, hipMemcpyHostToDevice, o->stream));
-  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (the caller's buffers are read until here)
-  if (o->W) o->mem.free_one(o->W);
-  o->W = w;
-  o->cost_host = cc;
-  ovr_plan_cost(o);
+  ADMM_TRY(set_svm_cost(*o, o->m, weights, class_cost, &o->W, o->CC, &o->cost_host));
+  o->chunk_cost = svm_cost_chunks(o->K, kOvrChunk, o->W != nullptr, o->loss_host, o->cost_host);
   return ADMM_OK;
 }
 
@@ -740,51 +551,23 @@ int admm_svm_ovr_fetch(admm_svm_ovr* o, int field, double* dst, size_t cap, size
   if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
   if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
   ADMM_HIP_TRY(hipSetDevice(o->device));
-  const int32_t K = o->K;
-  auto matrix = [&](const double* src, int64_t ld, int64_t rows) -> int {
-    const size_t need = static_cast<size_t>(rows) * K;
-    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
-    ADMM_HIP_TRY(hipMemcpy2D(dst, rows * sizeof(double), src, ld * sizeof(double), rows * sizeof(double), K,
-                             hipMemcpyDeviceToHost));
-    if (written) *written = need;
-    return ADMM_OK;
-  };
-  auto history = [&](const double* src) -> int {
-    int32_t S = 0;
-    for (int32_t s : o->steps) S = s > S ? s : S;
-    const size_t need = static_cast<size_t>(S) * K;
-    if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
-    if (S > 0)
-      ADMM_HIP_TRY(hipMemcpy2D(dst, S * sizeof(double), src, o->hist_ld * sizeof(double), S * sizeof(double), K,
-                               hipMemcpyDeviceToHost));
-    for (int32_t c = 0; c < K; ++c)
-      for (int32_t i = o->steps[c]; i < S; ++i) dst[static_cast<size_t>(c) * S + i] = __builtin_nan("");
-    if (written) *written = need;
-    return ADMM_OK;
-  };
   switch (field) {
-    case ADMM_OVR_F_XOPT: return matrix(o->X, o->ldx, o->n);
-    case ADMM_OVR_F_ZOPT: return matrix(o->Z, o->ldz, o->m);
-    case ADMM_OVR_F_UOPT: return matrix(o->U, o->ldz, o->m);
-    case ADMM_OVR_F_PNORM: return history(o->pnorm);
-    case ADMM_OVR_F_PERR: return history(o->perr);
-    case ADMM_OVR_F_HNORMSQ: return history(o->hnorm);
+    case ADMM_OVR_F_XOPT: return fetch_cols(*o, o->X, o->ldx, o->n, dst, cap, written);
+    case ADMM_OVR_F_ZOPT: return fetch_cols(*o, o->Z, o->ldz, o->m, dst, cap, written);
+    case ADMM_OVR_F_UOPT: return fetch_cols(*o, o->U, o->ldz, o->m, dst, cap, written);
+    case ADMM_OVR_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
+    case ADMM_OVR_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
+    case ADMM_OVR_F_HNORMSQ: return fetch_history(*o, o->hnorm, dst, cap, written);
     case ADMM_OVR_F_OBJEVALS:
       if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return history(o->objv);
+      return fetch_history(*o, o->objv, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the one-vs-rest linear SVM");
   }
 }
 
 void admm_svm_ovr_destroy(admm_svm_ovr* o) {
   if (!o) return;
-  (void)hipSetDevice(o->device);
-  if (o->stream) (void)hipStreamSynchronize(o->stream);
-  if (o->ev0) (void)hipEventDestroy(o->ev0);
-  if (o->ev1) (void)hipEventDestroy(o->ev1);
-  o->mem.release();
-  if (o->rec_host) (void)hipHostFree(o->rec_host);
-  if (o->eng) admm_engine_destroy(o->eng);
+  dense_destroy(*o);
   delete o;
 }
 

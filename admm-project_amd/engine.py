@@ -621,8 +621,61 @@ class Engine:
         return out
 
 
-class SvmOvr:
+class _MultiOwner:
+    """What the owners of a "K runs over one D" handle share (SvmOvr, RegMulti, SparseSvmOvr, SparseRegMulti).  A
+    subclass names its C functions (``_abi`` = their common prefix) and sets ``_lib``, ``_h``, ``m``, ``n``, ``K``."""
+
+    _abi = ""    # "admm_svm_ovr": <_abi>_destroy and <_abi>_fetch
+    _unit = ""   # what a column is, for the messages: "fit" | "class"
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._abi + "_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def fetch(self, field, rows):
+        buf = np.empty((rows, self.K), dtype=np.float64, order="F")
+        w = C.c_size_t(0)
+        L.check(getattr(self._lib, self._abi + "_fetch")(self._h, field, L.as_dp(buf), buf.size, C.byref(w)))
+        assert w.value == buf.size, (w.value, buf.size)
+        return buf
+
+    def _start_vectors(self, o, check=True, **vectors):
+        """options.x0 / z0 / u0 from rows x K matrices (None: zeros); returns what must outlive the run"""
+        keep = []
+        for name, v in vectors.items():
+            if v is None:
+                continue
+            v = _f64(v)
+            rows = self.n if name == "x0" else self.m
+            if check and v.shape != (rows, self.K):
+                raise ValueError(f"{name} is not a {rows} x {self.K} matrix (one column per {self._unit})")
+            keep.append(v)
+            setattr(o, name, L.as_dp(v))
+        return keep
+
+    @staticmethod
+    def _summary(summ, rt, cg=False):
+        out = dict(steps=np.array([s.steps for s in summ], dtype=np.int64),
+                   stopped_early=np.array([s.stopped_early for s in summ], dtype=np.int64),
+                   objopt=np.array([s.objopt for s in summ], dtype=np.float64))
+        if cg:
+            out.update(cg_iters_total=np.array([s.cg_iters_total for s in summ], dtype=np.int64),
+                       cg_capped_updates=np.array([s.cg_capped_updates for s in summ], dtype=np.int64))
+        out["runtime"] = rt.value
+        return out
+
+
+class SvmOvr(_MultiOwner):
     """Python owner of one ``admm_svm_ovr`` handle: the linear SVM for K one-vs-rest classes over one D."""
+
+    _abi, _unit = "admm_svm_ovr", "class"
 
     def __init__(self, D, ELL, C_, losses, *, Dplus=None, device=0):
         self._h = None
@@ -656,17 +709,6 @@ class SvmOvr:
         L.check(self._lib.admm_svm_ovr_set_cost(self._h, None if w is None else L.as_dp(w),
                                                 None if cc is None else L.as_dp(cc)))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.admm_svm_ovr_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def run(self, *, rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, Hnormtol=1e-6, relax=1.0, fast=L.FAST_OFF,
             convtest=0, domaxiters=0, objevals=0, check_every=0, x0=None, z0=None, u0=None):
         o = L.SvmOvrOptions()
@@ -675,21 +717,9 @@ class SvmOvr:
             float(Hnormtol)
         o.relax, o.fast, o.convtest = float(relax), int(fast), int(bool(convtest))
         o.domaxiters, o.objevals, o.check_every = int(bool(domaxiters)), int(bool(objevals)), int(check_every)
-        keep = [None if v is None else _f64(v) for v in (x0, z0, u0)]
-        for name, v in zip(("x0", "z0", "u0"), keep):
-            if v is not None:
-                setattr(o, name, L.as_dp(v))
+        keep = self._start_vectors(o, check=False, x0=x0, z0=z0, u0=u0)  # noqa: F841 (alive until the run returns)
         summ = (L.SvmOvrSummary * self.K)()
         rt = C.c_double(0)
         L.check(self._lib.admm_svm_ovr_run(self._h, C.byref(o), summ, C.byref(rt)))
         self.objevals = bool(objevals)
-        return dict(steps=np.array([s.steps for s in summ], dtype=np.int64),
-                    stopped_early=np.array([s.stopped_early for s in summ], dtype=np.int64),
-                    objopt=np.array([s.objopt for s in summ], dtype=np.float64), runtime=rt.value)
-
-    def fetch(self, field, rows):
-        buf = np.empty((rows, self.K), dtype=np.float64, order="F")
-        w = C.c_size_t(0)
-        L.check(self._lib.admm_svm_ovr_fetch(self._h, field, L.as_dp(buf), buf.size, C.byref(w)))
-        assert w.value == buf.size, (w.value, buf.size)
-        return buf
+        return self._summary(summ, rt)

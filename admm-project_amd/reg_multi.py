@@ -7,15 +7,17 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _f64, _weights
+from .engine import _MultiOwner, _f64, _weights
 
 KINDS = {"lad": L.REGM_KIND_LAD, "huber": L.REGM_KIND_HUBER, "huberfit": L.REGM_KIND_HUBER}
 
 
-class RegMulti:
+class RegMulti(_MultiOwner):
     """``RegMulti(D, S, kinds, a, b, epsilon, delta)``: ``S`` is m x 1 (one response shared by all fits) or m x K (one
     column per fit); ``kinds`` holds K entries 0 | 1 (or 'lad' | 'huber'); ``a``, ``b``, ``epsilon``, ``delta`` K values
     each, or None for the defaults 1, 1, 0, 1."""
+
+    _abi, _unit = "admm_reg_multi", "fit"
 
     def __init__(self, D, S, kinds, a=None, b=None, epsilon=None, delta=None, *, device=0):
         self._h = None
@@ -56,17 +58,6 @@ class RegMulti:
         w = _weights(weights, self.m, "observations")
         L.check(self._lib.admm_reg_multi_set_weights(self._h, None if w is None else L.as_dp(w)))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.admm_reg_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def run(self, *, rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, relax=1.0, fast=L.FAST_OFF, convtest=0,
             domaxiters=0, objevals=0, check_every=0, x0=None, z0=None, u0=None):
         o = L.RegMultiOptions()
@@ -74,28 +65,12 @@ class RegMulti:
         o.maxiters, o.rho, o.abstol, o.reltol = int(maxiters), float(rho), float(abstol), float(reltol)
         o.relax, o.fast, o.convtest = float(relax), int(fast), int(bool(convtest))
         o.domaxiters, o.objevals, o.check_every = int(bool(domaxiters)), int(bool(objevals)), int(check_every)
-        keep = []
-        for name, v, rows in (("x0", x0, self.n), ("z0", z0, self.m), ("u0", u0, self.m)):
-            if v is not None:
-                v = _f64(v)
-                if v.shape != (rows, self.K):
-                    raise ValueError(f"{name} is not a {rows} x {self.K} matrix (one column per fit)")
-                keep.append(v)
-                setattr(o, name, L.as_dp(v))
+        keep = self._start_vectors(o, x0=x0, z0=z0, u0=u0)  # noqa: F841 (alive until the run returns)
         summ = (L.RegMultiSummary * self.K)()
         rt = C.c_double(0)
         L.check(self._lib.admm_reg_multi_run(self._h, C.byref(o), summ, C.byref(rt)))
         self.objevals = bool(objevals)
-        return dict(steps=np.array([s.steps for s in summ], dtype=np.int64),
-                    stopped_early=np.array([s.stopped_early for s in summ], dtype=np.int64),
-                    objopt=np.array([s.objopt for s in summ], dtype=np.float64), runtime=rt.value)
-
-    def fetch(self, field, rows):
-        buf = np.empty((rows, self.K), dtype=np.float64, order="F")
-        w = C.c_size_t(0)
-        L.check(self._lib.admm_reg_multi_fetch(self._h, field, L.as_dp(buf), buf.size, C.byref(w)))
-        assert w.value == buf.size, (w.value, buf.size)
-        return buf
+        return self._summary(summ, rt)
 
     def launches(self):
         """kernel launches of the last run's iterations: dict(iterations, xsolve, passes, finalize, explicit_map)"""

@@ -8,12 +8,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _f64, _weights
+from .engine import _MultiOwner, _f64, _weights
 
 
-class SparseSvmOvr:
+class SparseSvmOvr(_MultiOwner):
     """``SparseSvmOvr(D, ELL, C, losses)``: ``D`` any ``scipy.sparse`` matrix or array (converted to canonical CSC),
     ``ELL`` m x K labels +-1, ``losses`` K strings ('hinge', '01', 'logistic', 'sqhinge')."""
+
+    _abi, _unit = "admm_sparse_svm", "class"
 
     def __init__(self, D, ELL, C_, losses, *, device=0):
         self._h = None
@@ -54,17 +56,6 @@ class SparseSvmOvr:
         L.check(self._lib.admm_sparse_svm_set_cost(self._h, None if w is None else L.as_dp(w),
                                                    None if cc is None else L.as_dp(cc)))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.admm_sparse_svm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def run(self, *, rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, Hnormtol=1e-6, relax=1.0, fast=L.FAST_OFF,
             convtest=0, domaxiters=0, objevals=0, check_every=0, cg_tol=0.0, cg_maxit=0, z0=None, u0=None):
         o = L.SparseSvmOptions()
@@ -74,27 +65,9 @@ class SparseSvmOvr:
         o.relax, o.fast, o.convtest = float(relax), int(fast), int(bool(convtest))
         o.domaxiters, o.objevals, o.check_every = int(bool(domaxiters)), int(bool(objevals)), int(check_every)
         o.cg_tol, o.cg_maxit = float(cg_tol), int(cg_maxit)  # (<= 0: the defaults 1e-12, 200)
-        keep = []
-        for name, v in (("z0", z0), ("u0", u0)):
-            if v is not None:
-                v = _f64(v)
-                if v.shape != (self.m, self.K):
-                    raise ValueError(f"{name} is not a {self.m} x {self.K} matrix (one column per class)")
-                keep.append(v)
-                setattr(o, name, L.as_dp(v))
+        keep = self._start_vectors(o, z0=z0, u0=u0)  # noqa: F841 (alive until the run returns)
         summ = (L.SparseSvmSummary * self.K)()
         rt = C.c_double(0)
         L.check(self._lib.admm_sparse_svm_run(self._h, C.byref(o), summ, C.byref(rt)))
         self.objevals = bool(objevals)
-        return dict(steps=np.array([s.steps for s in summ], dtype=np.int64),
-                    stopped_early=np.array([s.stopped_early for s in summ], dtype=np.int64),
-                    objopt=np.array([s.objopt for s in summ], dtype=np.float64),
-                    cg_iters_total=np.array([s.cg_iters_total for s in summ], dtype=np.int64),
-                    cg_capped_updates=np.array([s.cg_capped_updates for s in summ], dtype=np.int64), runtime=rt.value)
-
-    def fetch(self, field, rows):
-        buf = np.empty((rows, self.K), dtype=np.float64, order="F")
-        w = C.c_size_t(0)
-        L.check(self._lib.admm_sparse_svm_fetch(self._h, field, L.as_dp(buf), buf.size, C.byref(w)))
-        assert w.value == buf.size, (w.value, buf.size)
-        return buf
+        return self._summary(summ, rt, cg=True)
