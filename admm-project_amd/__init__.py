@@ -11,8 +11,9 @@ from .engine import Engine, SvmOvr  # noqa: F401
 from .reg_multi import RegMulti  # noqa: F401
 from .sparse_svm import SparseSvmOvr  # noqa: F401
 from .sparse_reg import SparseRegMulti  # noqa: F401
+from .sparse_lasso import SparseLassoMulti  # noqa: F401
 from . import testers  # noqa: F401,E402
-from .solvers import (basispursuit, covarianceselection, elasticnet, grouplasso, huberfit, lad, lasso, linearprogram, linearsvm, linearsvm_ovr, model,  # noqa: F401
+from .solvers import (basispursuit, covarianceselection, elasticnet, grouplasso, huberfit, lad, lasso, lasso_multi, lasso_path, linearprogram, linearsvm, linearsvm_ovr, model,  # noqa: F401
                       quantilereg, quantilereg_multi, quadraticprogram, robustfit_multi, totalvariation, totalvariation2d, unwrappedadmm)
 
 __version__ = "0.1.0"

@@ -277,6 +277,24 @@ class SparseRegSummary(C.Structure):  # admm_sparse_reg_summary
  SRG_F_DERR) = range(1, 9)
 
 
+class SparseLassoDesc(C.Structure):  # admm_sparse_lasso_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("D", C.POINTER(SparseDesc)), ("S", _dp),
+                ("ns", C.c_int32), ("device", C.c_int32), ("lam", _dp), ("ridge", _dp),
+                ("nonneg", C.POINTER(C.c_int32)), ("weights", _dp), ("comm", C.c_void_p)]
+
+
+class SparseLassoOptions(C.Structure):  # admm_sparse_lasso_options
+    _fields_ = list(SparseRegOptions._fields_)
+
+
+class SparseLassoSummary(C.Structure):  # admm_sparse_lasso_summary
+    _fields_ = list(SparseRegSummary._fields_)
+
+
+(SLM_F_XOPT, SLM_F_ZOPT, SLM_F_UOPT, SLM_F_PNORM, SLM_F_PERR, SLM_F_OBJEVALS, SLM_F_DNORM,
+ SLM_F_DERR) = range(1, 9)
+
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
@@ -419,6 +437,15 @@ _SIGNATURES = {
     "admm_sparse_reg_set_weights": (C.c_int, [C.c_void_p, _dp]),
     "admm_sparse_reg_chunk": (C.c_int, []),
     "admm_sparse_reg_destroy": (None, [C.c_void_p]),
+    "admm_sparse_lasso_desc_default": (None, [C.POINTER(SparseLassoDesc)]),
+    "admm_sparse_lasso_options_default": (None, [C.POINTER(SparseLassoOptions)]),
+    "admm_sparse_lasso_create": (C.c_int, [C.POINTER(SparseLassoDesc), C.POINTER(C.c_void_p)]),
+    "admm_sparse_lasso_run": (C.c_int, [C.c_void_p, C.POINTER(SparseLassoOptions), C.POINTER(SparseLassoSummary),
+                                        C.POINTER(C.c_double)]),
+    "admm_sparse_lasso_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_sparse_lasso_set_weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_sparse_lasso_chunk": (C.c_int, []),
+    "admm_sparse_lasso_destroy": (None, [C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

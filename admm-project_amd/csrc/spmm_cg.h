@@ -1,6 +1,11 @@
-// spmm_cg.h -- the x-update of a multi-fit solver on a sparse design matrix: CG on D'D x = y for K
-// right-hand sides in lock-step over one sparse product with kSpmmChunk columns (spmm.h).  The kernels know nothing about
-// the loss: sparse_svm.hip and sparse_reg.hip both drive them through SpmmCg.
+// spmm_cg.h -- the x-update of a multi-fit solver on a sparse design matrix: CG on
+// (D'D + shift*I) x = y for K right-hand sides in lock-step over one sparse product with kSpmmChunk columns (spmm.h).  The
+// kernels know nothing about the loss: sparse_svm.hip and sparse_reg.hip (shift = 0) and sparse_lasso.hip (shift = rho)
+// drive them through SpmmCg.
+// The shift never gets a pass of its own over Q: the three elementwise kernels that read Q form qv = Q + shift*V (V = P in
+// an inner iteration, X in front of a warm start) through scg_qv, ONE explicit fma -- a single rounding whatever the
+// compiler contracts around it, so the dot product and the update see the same bits of qv.  It is a template parameter:
+// shift == 0 launches the SHIFT = false instantiations, which never read V for it and are the kernels as they were.
 // Every multi-vector has spmm.h's layout [chunks][len][kSpmmChunk]; an elementwise kernel runs one thread per stored
 // value: workgroup (b, chunk) of kScgRows * kSpmmChunk threads takes the row blocks b, b + gridDim.x, ... of its chunk,
 // thread t the row t / kSpmmChunk of the block and the fit t % kSpmmChunk -- consecutive threads read consecutive
@@ -49,12 +54,14 @@ struct ScgArgs {
   ScgState* st;      // K
   const MultiRec* rec;  // K: a stopped fit is skipped
   int32_t* alldone;  // [0] the word the host polls: every fit is done or stopped; [1] the most inner iterations of a fit
+  double shift;      // q = D'(D p) + shift*p; 0: no shift (the SHIFT = false kernels)
 };
 
 int scg_vec_workgroups(int64_t len);
-// r = y - q (first: x = 0, r = y), p = r, then per fit rs, ||y||, iters = 0, done if already converged
+// r = y - (q + shift*x) (first: x = 0, r = y), p = r, then per fit rs, ||y||, iters = 0, done if already converged
 void launch_scg_start(const ScgArgs& a, bool first, hipStream_t stream);
-// one inner iteration behind Q = D'(D P): p.q, alpha, x and r, beta, p, the scalar state and the all-done word
+// one inner iteration behind Q = D'(D P): p.qv with qv = q + shift*p, alpha, x and r, beta, p, the scalar state and the
+// all-done word
 void launch_scg_step(const ScgArgs& a, hipStream_t stream);
 
 // what a sparse multi-fit solver owns for its x-update: D both ways, the n-length multi-vectors of CG, the m-length
@@ -82,8 +89,8 @@ struct SpmmCg {
   int upload(double* dst, const double* src, int64_t rows);
   int fetch_matrix(const double* src, int64_t rows, double* dst, size_t cap, size_t* written);
   // the CG state and x zeroed, the batch reset (a run never depends on the one before it), *a filled in
-  int begin_run(double tol, int32_t maxit, ScgArgs* a);
-  // X <- the CG solution of D'D x = Y for every running fit; the host polls the all-done word once per batch
+  int begin_run(double tol, int32_t maxit, ScgArgs* a, double shift = 0.0);
+  // X <- the CG solution of (D'D + shift*I) x = Y for every running fit; the host polls the all-done word once per batch
   int solve(const ScgArgs& a, bool first);
   int fetch_counters(std::vector<ScgState>* out) const;
   template <class Summary>

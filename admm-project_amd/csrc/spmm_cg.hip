@@ -1,6 +1,6 @@
-// spmm_cg.hip -- lock-step CG on D'D x = y for K right-hand sides over one sparse product (spmm_cg.h).
-// No shift, nothing n x n: the first solve of a run starts from 0 and every later one from the previous x, so every
-// iterate stays in range(D').  Per solve, every launch for all K fits at once (blockIdx.y = chunk of kSpmmChunk fits):
+// spmm_cg.hip -- lock-step CG on (D'D + shift*I) x = y for K right-hand sides over one sparse product (spmm_cg.h;
+// DESIGN.md q37, q39).  Nothing n x n: the first solve of a run starts from 0 and every later one from the previous x, so
+// without a shift every iterate stays in range(D'); with shift > 0 the matrix is positive definite.  Per solve, every launch for all K fits at once (blockIdx.y = chunk of kSpmmChunk fits):
 //   scg_init / _start             r = y - D'(D x), p = r, per-fit rs and ||y||
 //   per inner iteration           T = D P, Q = D' T (two SpMM), scg_dot / _update / _direction / _advance
 // A fit whose stop flag is set is FROZEN, and a fit whose solve is done is masked until the next solve: every kernel and
@@ -32,8 +32,15 @@ __device__ __forceinline__ double scg_total(const double* part, int nstot, int s
   return lds[threadIdx.x % KC];
 }
 
-// r = y - q, p = r, partials of r.r and y.y.  FIRST: the first x-update of a run starts from x = 0 (r = y)
-template <bool FIRST>
+// qv = Q[e] + shift * V[e] as ONE fma (spmm_cg.h); without SHIFT it is Q[e] and V is never read
+template <bool SHIFT>
+__device__ __forceinline__ double scg_qv(const ScgArgs& a, const double* V, int64_t e) {
+  if constexpr (SHIFT) return fma(a.shift, V[e], a.Q[e]);
+  else return a.Q[e];
+}
+
+// r = y - qv, p = r, partials of r.r and y.y.  FIRST: the first x-update of a run starts from x = 0 (r = y)
+template <bool FIRST, bool SHIFT>
 __global__ __launch_bounds__(kScgBlock) void scg_init_kernel(ScgArgs a) {
   __shared__ double lds[2 * kScgBlock];
   const ScgLane l = scg_lane(a.rec, a.K);
@@ -48,7 +55,7 @@ __global__ __launch_bounds__(kScgBlock) void scg_init_kernel(ScgArgs a) {
       const double yv = a.Y[e];
       double rv = yv;
       if (FIRST) a.X[e] = 0.0;
-      else rv = yv - a.Q[e];
+      else rv = yv - scg_qv<SHIFT>(a, a.X, e);
       a.R[e] = rv;
       a.P[e] = rv;
       acc[0] += rv * rv;
@@ -78,6 +85,7 @@ __global__ __launch_bounds__(kScgBlock) void scg_start_kernel(ScgArgs a, int nb)
   }
 }
 
+template <bool SHIFT>
 __global__ __launch_bounds__(kScgBlock) void scg_dot_kernel(ScgArgs a) {
   __shared__ double lds[kScgBlock];
   const ScgLane l = scg_lane(a.rec, a.K);
@@ -90,13 +98,14 @@ __global__ __launch_bounds__(kScgBlock) void scg_dot_kernel(ScgArgs a) {
     const int64_t i = rb * kScgRows + l.r;
     if (live && i < a.n) {
       const int64_t e = base + i * KC + l.c;
-      acc[0] += a.P[e] * a.Q[e];
+      acc[0] += a.P[e] * scg_qv<SHIFT>(a, a.P, e);
     }
   }
   scg_sums<1>(acc, lds, a.part, 2, 0);
 }
 
-// alpha = rs / (p.q); x += alpha p; r -= alpha q; partial r.r.  p.q == 0: nothing is divided or updated, the fit ends
+// alpha = rs / (p.qv); x += alpha p; r -= alpha qv; partial r.r.  p.qv == 0: nothing is divided or updated, the fit ends
+template <bool SHIFT>
 __global__ __launch_bounds__(kScgBlock) void scg_update_kernel(ScgArgs a, int nb) {
   __shared__ double lds[kScgBlock];
   __shared__ double lt[KC];
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(kScgBlock) void scg_update_kernel(ScgArgs a, int nb
     if (zero) a.X[e] = 0.0;
     if (live && !brk) {
       a.X[e] = a.X[e] + alpha * a.P[e];
-      const double rv = a.R[e] - alpha * a.Q[e];
+      const double rv = a.R[e] - alpha * scg_qv<SHIFT>(a, a.P, e);
       a.R[e] = rv;
       acc[0] += rv * rv;
     }
@@ -192,8 +201,10 @@ int scg_vec_workgroups(int64_t len) {
 void launch_scg_start(const ScgArgs& a, bool first, hipStream_t stream) {
   const int nb = scg_vec_workgroups(a.n);
   const unsigned chunks = static_cast<unsigned>(spmm_chunks(a.K));
-  if (first) hipLaunchKernelGGL(scg_init_kernel<true>, dim3(nb, chunks), dim3(kScgBlock), 0, stream, a);
-  else hipLaunchKernelGGL(scg_init_kernel<false>, dim3(nb, chunks), dim3(kScgBlock), 0, stream, a);
+  const dim3 grid(nb, chunks);
+  if (first) hipLaunchKernelGGL((scg_init_kernel<true, false>), grid, dim3(kScgBlock), 0, stream, a);  // (r = y: no q)
+  else if (a.shift != 0.0) hipLaunchKernelGGL((scg_init_kernel<false, true>), grid, dim3(kScgBlock), 0, stream, a);
+  else hipLaunchKernelGGL((scg_init_kernel<false, false>), grid, dim3(kScgBlock), 0, stream, a);
   hipLaunchKernelGGL(scg_start_kernel, dim3(1, chunks), dim3(kScgBlock), 0, stream, a, nb);
 }
 
@@ -201,8 +212,13 @@ void launch_scg_step(const ScgArgs& a, hipStream_t stream) {
   const int nb = scg_vec_workgroups(a.n);
   const int chunks = spmm_chunks(a.K);
   const dim3 grid(nb, static_cast<unsigned>(chunks));
-  hipLaunchKernelGGL(scg_dot_kernel, grid, dim3(kScgBlock), 0, stream, a);
-  hipLaunchKernelGGL(scg_update_kernel, grid, dim3(kScgBlock), 0, stream, a, nb);
+  if (a.shift != 0.0) {
+    hipLaunchKernelGGL(scg_dot_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
+    hipLaunchKernelGGL(scg_update_kernel<true>, grid, dim3(kScgBlock), 0, stream, a, nb);
+  } else {
+    hipLaunchKernelGGL(scg_dot_kernel<false>, grid, dim3(kScgBlock), 0, stream, a);
+    hipLaunchKernelGGL(scg_update_kernel<false>, grid, dim3(kScgBlock), 0, stream, a, nb);
+  }
   hipLaunchKernelGGL(scg_direction_kernel, grid, dim3(kScgBlock), 0, stream, a, nb);
   hipLaunchKernelGGL(scg_advance_kernel, dim3(1), dim3(kScgBlock), 0, stream, a, nb, chunks);
 }
@@ -275,11 +291,11 @@ int SpmmCg::fetch_matrix(const double* src, int64_t rows, double* dst, size_t ca
   return ADMM_OK;
 }
 
-int SpmmCg::begin_run(double tol, int32_t maxit, ScgArgs* a) {
+int SpmmCg::begin_run(double tol, int32_t maxit, ScgArgs* a, double shift) {
   ADMM_HIP_TRY(hipMemsetAsync(cg, 0, sizeof(ScgState) * h->K, h->stream));
   ADMM_TRY(upload(X, nullptr, n));  // (x0 is never read: the first x-update starts CG from 0)
   cg_batch = 8;                     // (a run never depends on the one before it)
-  *a = ScgArgs{n, tol, maxit, h->K, Y, X, R, P, Q, cgpart, cg, h->rec, alldone};
+  *a = ScgArgs{n, tol, maxit, h->K, Y, X, R, P, Q, cgpart, cg, h->rec, alldone, shift};
   return ADMM_OK;
 }
 

@@ -15,7 +15,7 @@ import numpy as np
 from .api import admm, getproxops
 from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "lasso_multi", "lasso_path", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -149,6 +149,159 @@ def elasticnet(D, s, lam, ridge, options=None):
     if not isinstance(options, dict):
         raise TypeError("Given options is not a struct! At least pass empty struct!")
     return lasso(D, s, lam, dict(options, ridge=ridge))
+
+
+def _per_fit(value, K, name, check):
+    """a scalar (for every fit) or K values, each passed through ``check`` (a penalty_fields field); messages name the fit"""
+    vals = [value] * K if np.isscalar(value) or isinstance(value, (bool, np.bool_)) else list(np.asarray(value).reshape(-1))
+    if len(vals) != K:
+        raise ValueError(f"{name} has {len(vals)} entries for {K} fits")
+    out = []
+    for k, v in enumerate(vals):
+        try:
+            out.append(check(v.item() if isinstance(v, np.generic) else v))
+        except ValueError as e:
+            raise ValueError(f"fit {k}: {e}") from None
+    return out
+
+
+def _lambda_max(D, S, w):
+    """per column of S the smallest lambda whose lasso solution is x = 0: max over w_i > 0 of |(D's)_i| / w_i"""
+    g = np.abs(np.asarray(D.T @ S, dtype=np.float64)).reshape(D.shape[1], -1)
+    if w is not None:
+        live = w > 0
+        g = g[live] / w[live][:, None]
+    return g.max(axis=0) if g.size else np.zeros(S.shape[1] if S.ndim == 2 else 1)
+
+
+def lasso_multi(D, S, lams, options=None):
+    """results = lasso_multi(D, S, lams, options): K lasso fits over ONE sparse design matrix in one run
+    -- a regularisation path, a cross-validation grid, or one D against several response columns:
+
+        minimise 1/2*||D*x - s_k||^2 + lambda_k*sum_i w_i*|x_i| + ridge_k/2*||x||^2   (x >= 0 where nonnegative_k)
+
+    ``D``: any ``scipy.sparse`` matrix or array; a dense D raises ValueError (call ``lasso`` per fit).  ``S``: a vector
+    or m x 1 (shared by all fits) or m x K (one column per fit).  ``lams``: the K values lambda_k >= 0.
+    ``options['ridge']`` and ``options['nonnegative']`` are scalars or K values, ``options['l1weights']`` (n values >= 0)
+    is shared by all fits.  rho, abstol, reltol, maxiters, domaxiters, objevals and check_every apply to every fit;
+    ``z0`` / ``u0`` are n x K (default zeros), x0 (n x K) is checked and never read; ``nodualerror`` (default 0: the
+    reference lasso's stop rule on both residuals) set to 1 stops on the primal residual alone; ``cg_tol`` / ``cg_maxit``
+    (1e-12 / 200) bound a solve.  Every x-update is conjugate gradients on (D'D + rho*I) x = D's_k + rho*(z - u), all fits
+    in lock-step over one sparse product.
+
+    Returns xopt, zopt, uopt (n x K), steps (K), pnorm / perr (max(steps) x K, NaN past a fit's last step), dnorm / derr
+    unless nodualerror = 1, objevals with options['objevals'], objopt (K), runtime, solverruntime, chunk, lams,
+    ``xsolve = 'cg'``, ``nnz``, ``cg_iters_total`` and ``cg_capped_updates`` (K values each).  fast, convtest, relax,
+    adaptive, an xsolve other than 'auto' / 'cg', comm, parallel and a stopcond other than 'standard' are refused by
+    name."""
+    if options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise TypeError("Argument options is not a struct!")
+    options = dict(options)
+    t0 = time.perf_counter()
+    from . import _lib as L
+    if not L.is_sparse(D):
+        raise ValueError("lasso_multi runs on a scipy.sparse D: call lasso per fit on a dense design matrix")
+    _sparse_reg_refusals(options, "lasso_multi")
+    D = _matrix(D, "D", sparse_ok=True)
+    m, n = D.shape
+    S = np.asarray(S, dtype=np.float64)
+    if S.ndim == 1:
+        S = S.reshape(-1, 1)
+    if S.ndim != 2:
+        raise ValueError("Argument S is neither a vector nor a matrix!")
+    if S.shape[0] != m:
+        raise ValueError("The number of rows in argument D do not match size of S!")
+    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
+    K = int(lam.size)
+    if K < 1:
+        raise ValueError("lams must hold at least one lambda")
+    for k, v in enumerate(lam):
+        if not np.isfinite(v) or v < 0:
+            raise ValueError(f"fit {k}: lambda is not a nonnegative real number")
+    if S.shape[1] not in (1, K):
+        raise ValueError(f"S has {S.shape[1]} columns for {K} fits: one shared response or one column per fit")
+    S = np.asfortranarray(S)
+    ridge = _per_fit(options.get("ridge", 0.0), K, "ridge", lambda v: penalty_fields(dict(ridge=v), n)["ridge"])
+    nonneg = _per_fit(options.get("nonnegative", 0), K, "nonnegative",
+                      lambda v: penalty_fields(dict(nonnegative=v), n)["nonnegative"])
+    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
+    w = None if pw is None else pw["l1weights"]
+    if "rho" in options:
+        is_positive_real(options["rho"], "options.rho")
+    starts = {}
+    for key in ("x0", "z0", "u0"):
+        if options.get(key) is not None:
+            v = np.asarray(options[key], dtype=np.float64)
+            if v.shape != (n, K):
+                raise ValueError(f"options.{key} is not a {n} x {K} matrix (one column per fit)!")
+            starts[key] = np.asfortranarray(v)
+    nodual = int(bool(options.get("nodualerror", 0)))
+    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals", "cg_tol",
+                                    "cg_maxit") if k in options}
+    from .sparse_lasso import SparseLassoMulti
+    res = {}
+    obj = SparseLassoMulti(D, S, lam, ridge, nonneg, w, device=int(options.get("device", 0)))
+    try:
+        summ = obj.run(check_every=int(options.get("check_every", 0)), nodualerror=nodual, z0=starts.get("z0"),
+                       u0=starts.get("u0"), **loop)
+        Smax = int(summ["steps"].max())
+        for key, field in (("xopt", L.SLM_F_XOPT), ("zopt", L.SLM_F_ZOPT), ("uopt", L.SLM_F_UOPT)):
+            res[key] = obj.fetch(field, n)
+        res["steps"] = summ["steps"]
+        res["pnorm"] = obj.fetch(L.SLM_F_PNORM, Smax)
+        res["perr"] = obj.fetch(L.SLM_F_PERR, Smax)
+        if not nodual:
+            res["dnorm"] = obj.fetch(L.SLM_F_DNORM, Smax)
+            res["derr"] = obj.fetch(L.SLM_F_DERR, Smax)
+        if loop.get("objevals", 0):
+            res["objevals"] = obj.fetch(L.SLM_F_OBJEVALS, Smax)
+        res["objopt"] = summ["objopt"]
+        res["runtime"] = summ["runtime"]
+        res["chunk"] = obj.chunk()
+        res["xsolve"] = "cg"
+        res["nnz"] = obj.nnz
+        res["cg_iters_total"] = summ["cg_iters_total"]
+        res["cg_capped_updates"] = summ["cg_capped_updates"]
+    finally:
+        obj.close()
+    res["lams"] = lam.copy()
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
+
+
+def lasso_path(D, s, lams=None, options=None):
+    """results = lasso_path(D, s, lams, options): the lasso's regularisation path on a sparse D, every lambda side by side
+    in one run of ``lasso_multi``.  ``lams = None``: ``options['nlambda']`` values (default: the chunk of
+    the sparse product, 10), log-spaced from lambda_max = max over w_i > 0 of |(D's)_i| / w_i -- the smallest lambda whose
+    solution is x = 0 -- down to ``options['lambda_min_ratio']`` * lambda_max (default 1e-2).  Returns lasso_multi's
+    fields plus ``df``, the number of nonzeros of each zopt column."""
+    if options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise TypeError("Argument options is not a struct!")
+    options = dict(options)
+    from . import _lib as L
+    if not L.is_sparse(D):
+        raise ValueError("lasso_path runs on a scipy.sparse D: call lasso per lambda on a dense design matrix")
+    s = _colvec(s, "s")
+    nlambda = options.pop("nlambda", None)
+    ratio = options.pop("lambda_min_ratio", 1e-2)
+    if lams is None:
+        if s.size != D.shape[0]:
+            raise ValueError("The number of rows in argument D do not match size of s!")
+        nlambda = 10 if nlambda is None else nlambda  # (kSpmmChunk: one pass over D per product)
+        if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
+            raise ValueError("options.nlambda must be an integer >= 1")
+        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
+            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
+        pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
+        lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"])[0])
+        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+    res = lasso_multi(D, s, lams, options)
+    res["df"] = np.count_nonzero(res["zopt"], axis=0).astype(np.int64)
+    return res
 
 
 def _lad_like(kind, D, s, options):

@@ -161,6 +161,27 @@ def sparsequantileregtest(seed=0, rows=2 ** 10, cols=2 ** 6, density=0.05, taus=
     return test
 
 
+def sparselassopathtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, nlambda=10, quiet=1, options=None):
+    """The lasso's regularisation path on a sparse design matrix: lasso_path on
+    synth.sparse_lasso_path_problem over ``nlambda`` values, the first one 1.25*lambda_max and the others log-spaced from
+    0.8*lambda_max down to 0.01*lambda_max, all in one run.  Pass when the fit above lambda_max returns z = 0.0 exactly
+    with ||x|| below its own primal tolerance, and the number of nonzeros of z does not shrink as lambda falls.  Returns
+    the ``test`` dict alone; the solver's results are ``test['results']``."""
+    p = synth.sparse_lasso_path_problem(seed, rows, cols, density)
+    D, s, lmax = p["D"], p["s"], p["lmax"]
+    lams = lmax * np.concatenate([[1.25], np.logspace(np.log10(0.8), -2.0, int(nlambda) - 1)])
+    results = solvers.lasso_path(D, s, lams, _opts(options, objevals=1, quiet=quiet))
+    Z, X = np.asarray(results["zopt"]), np.asarray(results["xopt"])
+    df = [int(v) for v in results["df"]]
+    last = int(results["steps"][0]) - 1
+    zero = bool(np.all(Z[:, 0] == 0.0)) and float(np.linalg.norm(X[:, 0])) < float(results["perr"][last, 0])
+    grows = all(b >= a for a, b in zip(df[:-1], df[1:]))
+    test = dict(D=D, s=s, testx=p["testx"], lmax=lmax, lams=lams, df=df, xopt=X, admmopt=results["objopt"],
+                zero_above_lmax=zero, support_grows=grows, failed=int(not (zero and grows)), steps=results["steps"],
+                results=results)
+    return test
+
+
 def huberfittest(seed=0, rows=2 ** 11, cols=2 ** 7, errtol=1e-3, quiet=1, options=None):
     """testers/huberfittest.m:43-188: ADMM's objective is below the planted solution's (line 154)."""
     p = synth.huber_problem(seed, rows, cols)

@@ -1125,6 +1125,93 @@ int admm_sparse_reg_set_weights(admm_sparse_reg* obj, const double* weights);
 int admm_sparse_reg_chunk(void);
 void admm_sparse_reg_destroy(admm_sparse_reg* obj);
 
+/* ---- the lasso on a sparse design matrix, K fits over one sparse product (additive to ABI 5): a
+ * regularisation path, a cross-validation grid or several response columns in one run.  The K runs are plain ADMM as
+ * lasso.m:227-239 poses it (A = 1, B = -1, c = 0, sizes cols, stopcond = 'standard'); they share D, rho and cols l1
+ * weights w_i >= 0 and differ in (lambda_k, mu_k, nonneg_k) and, with ns = K, in their column of S:
+ *   minimise 1/2*||D x - s_k||^2 + lambda_k*sum_i w_i*|z_i| + mu_k/2*||z||^2 + [z >= 0 when nonneg_k]  s.t. x = z
+ * (the penalty family of admm_engine_set_penalty without groups).  The x-update (D'D + rho*I) x = D's_k + rho*(z - u)
+ * (lasso.m:28-30) is the lock-step conjugate gradients of admm_sparse_svm / admm_sparse_reg with the shift rho: nothing
+ * factored, nothing cols x cols stored.  The first x-update of a run starts CG from 0 (x0 is never read) and every later
+ * one from the previous x.  A fit stops on pnorm = ||x - z|| < perr = sqrt(cols)*abstol + reltol*max(||x||, ||z||) and
+ * dnorm = rho*||z - zprev|| < derr = sqrt(cols)*abstol + reltol*rho*||u|| (admm.m:621-654), the reference lasso's rule and
+ * the default here (the dual residual costs no product); nodualerror = 1 stops on the primal residual alone.  The
+ * objective (objevals = 1: one more sparse product per iteration) is 1/2*||D x - s_k||^2 + g_k(z).
+ * ADMM_E_INVALID (before the device is touched): whatever admm_engine_create_sparse refuses in D, D not in host arrays,
+ * K < 1, ns not 1 or K, per fit (named in the message) a negative or non-finite lambda or ridge, nonneg other than
+ * 0 | 1, and a negative or non-finite weight (its index named).  ADMM_E_UNSUPPORTED: a communicator; at run: fast ADMM, relaxation, convtest.  Vector histories are not
+ * recorded. */
+typedef struct admm_sparse_lasso admm_sparse_lasso; /* opaque */
+
+typedef struct admm_sparse_lasso_desc {
+  int32_t struct_size;        /* sizeof(admm_sparse_lasso_desc) */
+  int32_t K;                  /* number of fits, >= 1 */
+  const admm_sparse_desc* D;  /* rows x cols, ADMM_MEM_HOST; copied at create */
+  const double* S;            /* rows x ns HOST values, column-major: one response for every fit, or one column per fit */
+  int32_t ns;                 /* 1 or K */
+  int32_t device;             /* HIP device ordinal */
+  const double* lambda;       /* K values lambda_k >= 0 */
+  const double* ridge;        /* K values mu_k >= 0 (NULL = 0) */
+  const int32_t* nonneg;      /* K values 0 | 1 (NULL = 0) */
+  const double* weights;      /* cols l1 weights w_i >= 0 shared by all fits (NULL = 1); admm_sparse_lasso_set_weights
+                                 replaces them */
+  admm_comm* comm;           /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_sparse_lasso_desc;
+
+typedef struct admm_sparse_lasso_options {
+  int32_t struct_size;   /* sizeof(admm_sparse_lasso_options) */
+  int32_t maxiters;      /* default 1000 */
+  double rho;            /* default 1.0: the shift of every x-update */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations between host polls of "every fit has stopped" (0 = auto: 8; 64 with domaxiters) */
+  int32_t cg_maxit;      /* cap on the inner iterations of one x-update; default 200, <= 0 = default */
+  double cg_tol;         /* relative residual of the x-update; default 1e-12, <= 0 = default */
+  int32_t nodualerror;   /* default 0: the reference lasso's rule; 1: stop on pnorm < perr alone */
+  int32_t reserved0;
+  const double* x0;      /* accepted and never read (see above) */
+  const double* z0;      /* cols x K host matrix (NULL = zeros) */
+  const double* u0;      /* cols x K */
+} admm_sparse_lasso_options;
+
+typedef struct admm_sparse_lasso_summary {  /* one per fit */
+  int32_t steps;              /* results.steps of that fit (admm.m:746) */
+  int32_t stopped_early;      /* 1 if the stop rule fired before maxiters (admm.m:710-713) */
+  double objopt;              /* the objective at the fit's last step, NaN if not evaluated */
+  int64_t cg_iters_total;     /* inner iterations of the fit over the run */
+  int64_t cg_capped_updates;  /* x-updates of the fit that ended with the residual still above cg_tol */
+} admm_sparse_lasso_summary;
+
+/* fields of admm_sparse_lasso_fetch: the numbers of admm_sparse_reg_fetch */
+enum {
+  ADMM_SLM_F_XOPT = 1,      /* cols x K */
+  ADMM_SLM_F_ZOPT = 2,      /* cols x K */
+  ADMM_SLM_F_UOPT = 3,      /* cols x K */
+  /* scalar histories: S x K column-major with S = the largest steps of any fit, NaN past a fit's own last step; DNORM
+   * and DERR after a run with nodualerror = 0 only, OBJEVALS after a run with objevals = 1 only */
+  ADMM_SLM_F_PNORM = 4, ADMM_SLM_F_PERR = 5, ADMM_SLM_F_OBJEVALS = 6, ADMM_SLM_F_DNORM = 7, ADMM_SLM_F_DERR = 8
+};
+
+void admm_sparse_lasso_desc_default(admm_sparse_lasso_desc* desc);
+void admm_sparse_lasso_options_default(admm_sparse_lasso_options* opts);
+int admm_sparse_lasso_create(const admm_sparse_lasso_desc* desc, admm_sparse_lasso** out);
+/* summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be called again on the same object:
+ * every run starts from its own z0 / u0, and two runs from the same starts give the same bits */
+int admm_sparse_lasso_run(admm_sparse_lasso* obj, const admm_sparse_lasso_options* opts,
+                          admm_sparse_lasso_summary* summaries, double* runtime_s);
+int admm_sparse_lasso_fetch(admm_sparse_lasso* obj, int field, double* dst, size_t cap, size_t* written);
+/* weights = cols HOST values w_i >= 0 shared by all fits (the l1 weights), copied at the call and held for every later
+ * run; NULL restores 1.  ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
+int admm_sparse_lasso_set_weights(admm_sparse_lasso* obj, const double* weights);
+/* fits one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
+int admm_sparse_lasso_chunk(void);
+void admm_sparse_lasso_destroy(admm_sparse_lasso* obj);
+
 #ifdef __cplusplus
 }
 #endif
