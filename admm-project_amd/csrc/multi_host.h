@@ -1,8 +1,11 @@
 // multi_host.h -- the host scaffold of the "K runs over one D" solvers (svm_ovr.hip, reg_multi.hip, sparse_svm.hip,
-// sparse_reg.hip): the part of an object every one of them has, the option refusals, the histories, the poll of the
-// per-fit records, the bookkeeping around a run and the teardown -- and what only a pair shares: the regression's fit
-// parameters and weights, the SVM's cost plan, the dense pair's n x n x-update.
-// A solver keeps its kernels, its argument blocks, its create-time checks and the body of its iteration loop.
+// sparse_reg.hip, sparse_lasso.hip): the part of an object every one of them has, the option refusals and defaults, the
+// histories, the poll of the per-fit records, the bookkeeping around a run and the teardown; the frame of the C ABI
+// around an object -- the create-time checks of a sparse D, of the response columns and of the placement, the tail of
+// create, the head of fetch, the gated histories, and the end of a run and the destroy of the sparse three; and what only
+// a pair shares: the regression's fit parameters and weights, the SVM's cost plan, the dense pair's n x n x-update.
+// A solver keeps its kernels, its argument blocks, the create-time checks of its own fields and the body of its
+// iteration loop.
 #pragma once
 #include <initializer_list>
 #include <string>
@@ -51,6 +54,15 @@ int check_run_options(const char* label, const char* suffix, Options* op) {
   if (op->convtest) return fail(ADMM_E_UNSUPPORTED, "convtest" + tail);
   if (!(op->rho > 0.0)) return fail(ADMM_E_INVALID, "options.rho must be positive");
   if (op->maxiters <= 0) op->maxiters = 1000;  // admm.m:334-339
+  if (op->check_every <= 0) op->check_every = op->domaxiters ? 64 : 8;  // iterations between two polls of the records
+  return ADMM_OK;
+}
+// the same for the sparse three, whose loop names carry no suffix, and the bounds of a CG solve left open
+template <class Options>
+int check_sparse_run_options(const char* label, Options* op) {
+  ADMM_TRY(check_run_options(label, "", op));
+  if (!(op->cg_tol > 0.0)) op->cg_tol = 1e-12;
+  if (op->cg_maxit <= 0) op->cg_maxit = 200;
   return ADMM_OK;
 }
 
@@ -78,6 +90,49 @@ int finish_run(MultiHost& h, bool all_stopped, const char* unfinished, int32_t N
   }
   return ADMM_OK;
 }
+
+// ---- the frame of the C ABI around an object
+// D of a sparse object: "<who> needs D (admm_sparse_desc)", "<who> takes D in host arrays", then the CSC rules
+int check_sparse_D(const char* who, const admm_sparse_desc* D);
+// "S has <ns> columns: one shared response or one per fit (<K>)"
+int check_response_columns(int32_t ns, int32_t K);
+// the last checks of a sparse create, so that every refusal above them needs no device: "<who> is not row-sharded", a
+// visible device and the ordinal
+int check_placement(const char* who, const admm_comm* comm, int device);
+// the tail of every create: a new object, its setup, and on failure the object destroyed behind the setup's own message
+template <class Obj, class Setup>
+int create_object(Obj** out, void (*destroy)(Obj*), Setup setup) {
+  Obj* o = new Obj();
+  const int rc = setup(o);
+  if (rc != ADMM_OK) {
+    const std::string msg = admm_last_error();
+    destroy(o);
+    return fail(rc, msg);
+  }
+  *out = o;
+  return ADMM_OK;
+}
+// the end of a sparse run behind finish_run: the CG counters, and the options fetch consults
+template <class Obj, class Options, class Summary>
+int end_sparse_run(Obj* o, const Options& op, Summary* summaries) {
+  ADMM_TRY(o->cg.fill_counters(summaries, o->K));
+  o->last = op;
+  o->has_run = true;
+  return ADMM_OK;
+}
+template <class Obj>
+void destroy_sparse(Obj* o) {  // (SpmmCg::destroy is the whole teardown of its host)
+  if (!o) return;
+  o->cg.destroy();
+  delete o;
+}
+// the head of every fetch: the object and dst given, a run behind it, its device current
+int fetch_head(const MultiHost* h, const double* dst);
+// a history the last run kept only with `kept`; otherwise ADMM_E_INVALID with `refusal`
+constexpr const char* kNoObjevals = "the last run did not evaluate the objective (objevals = 0)";
+constexpr const char* kNoDual = "the last run did not evaluate the dual residual (nodualerror = 1)";
+int fetch_kept_history(const MultiHost& h, bool kept, const char* refusal, const double* src, double* dst, size_t cap,
+                       size_t* written);
 
 // ---- the regression pair
 // per fit, exactly as admm_engine_set_loss checks it: kh[k] the kind, ph[4k ..] = (a, b, epsilon, delta)

@@ -1,6 +1,7 @@
 // multi_host.hip -- the host scaffold of the multi-fit solvers (multi_host.h).
 #include "multi_host.h"
 
+#include "spmv.h"
 #include "svm_ovr.h"
 
 namespace admm {
@@ -91,6 +92,42 @@ int finish_run_core(MultiHost& h, bool all_stopped, const char* unfinished, int3
     if (objevals && r.steps > 0) (*objopt)[c] = objh[static_cast<size_t>(c) * N + r.steps - 1];
   }
   return ADMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------- the frame of the C ABI
+int check_sparse_D(const char* who, const admm_sparse_desc* D) {
+  if (!D) return fail(ADMM_E_INVALID, std::string(who) + " needs D (admm_sparse_desc)");
+  if (D->mem != ADMM_MEM_HOST) return fail(ADMM_E_INVALID, std::string(who) + " takes D in host arrays");
+  return sparse_csc_check(D);
+}
+
+int check_response_columns(int32_t ns, int32_t K) {
+  if (ns != 1 && ns != K)
+    return fail(ADMM_E_INVALID, "S has " + std::to_string(ns) + " columns: one shared response or one per fit (" +
+                                    std::to_string(K) + ")");
+  return ADMM_OK;
+}
+
+int check_placement(const char* who, const admm_comm* comm, int device) {
+  if (comm) return fail(ADMM_E_UNSUPPORTED, std::string(who) + " is not row-sharded");
+  int ndev = 0;
+  ADMM_TRY(admm_device_count(&ndev));
+  if (ndev <= 0) return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
+  if (device < 0 || device >= ndev) return fail(ADMM_E_INVALID, "bad device ordinal");
+  return ADMM_OK;
+}
+
+int fetch_head(const MultiHost* h, const double* dst) {
+  if (!h || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
+  if (!h->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
+  ADMM_HIP_TRY(hipSetDevice(h->device));
+  return ADMM_OK;
+}
+
+int fetch_kept_history(const MultiHost& h, bool kept, const char* refusal, const double* src, double* dst, size_t cap,
+                       size_t* written) {
+  if (!kept) return fail(ADMM_E_INVALID, refusal);
+  return fetch_history(h, src, dst, cap, written);
 }
 
 // ---------------------------------------------------------------------------------------------- the regression pair

@@ -343,9 +343,7 @@ int admm_reg_multi_create(const admm_reg_multi_desc* desc, admm_reg_multi** out)
   if (desc->K < 1) return fail(ADMM_E_INVALID, "the multi-fit regression needs at least one fit (K >= 1)");
   if (!desc->D || desc->m <= 0 || desc->n <= 0) return fail(ADMM_E_INVALID, "the multi-fit regression needs D (m x n)");
   if (!desc->S) return fail(ADMM_E_INVALID, "the multi-fit regression needs the responses S (m x ns)");
-  if (desc->ns != 1 && desc->ns != desc->K)
-    return fail(ADMM_E_INVALID, "S has " + std::to_string(desc->ns) + " columns: one shared response or one per fit (" +
-                                    std::to_string(desc->K) + ")");
+  ADMM_TRY(check_response_columns(desc->ns, desc->K));
   std::vector<int32_t> kh;
   std::vector<double> ph;
   ADMM_TRY(check_reg_fits(desc->K, desc->kind, desc->a, desc->b, desc->epsilon, desc->delta, &kh, &ph));
@@ -355,15 +353,7 @@ int admm_reg_multi_create(const admm_reg_multi_desc* desc, admm_reg_multi** out)
                                         std::to_string(kRmMaxN) + kPerFit);
   if (desc->m < desc->n)
     return fail(ADMM_E_UNSUPPORTED, "D must have full column rank (m >= n) for chol(D'*D) (lad.m:134)");
-  admm_reg_multi* o = new admm_reg_multi();
-  const int rc = regm_setup(o, desc, kh, ph);
-  if (rc != ADMM_OK) {
-    const std::string msg = admm_last_error();
-    admm_reg_multi_destroy(o);
-    return fail(rc, msg);
-  }
-  *out = o;
-  return ADMM_OK;
+  return create_object(out, admm_reg_multi_destroy, [&](admm_reg_multi* o) { return regm_setup(o, desc, kh, ph); });
 }
 
 int admm_reg_multi_run(admm_reg_multi* o, const admm_reg_multi_options* opts, admm_reg_multi_summary* summaries,
@@ -426,7 +416,6 @@ int admm_reg_multi_run(admm_reg_multi* o, const admm_reg_multi_options* opts, ad
       launch_regm_pass(pa, init, o->stream);
     }
   };
-  const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
   int64_t* cnt = o->launches;
   cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
 
@@ -443,7 +432,7 @@ int admm_reg_multi_run(admm_reg_multi* o, const admm_reg_multi_options* opts, ad
     cnt[0] += 1;
     cnt[2] += chunks;
     cnt[3] += 1;
-    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
+    if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
   ADMM_TRY(finish_run(*o, all, "the multi-fit loop ended with fits still running", N, op.objevals != 0, o->objv, runtime_s,
                       summaries));
@@ -466,18 +455,14 @@ int admm_reg_multi_launches(admm_reg_multi* o, int64_t counts[5]) {
 }
 
 int admm_reg_multi_fetch(admm_reg_multi* o, int field, double* dst, size_t cap, size_t* written) {
-  if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
-  if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
-  ADMM_HIP_TRY(hipSetDevice(o->device));
+  ADMM_TRY(fetch_head(o, dst));
   switch (field) {
     case ADMM_REGM_F_XOPT: return fetch_cols(*o, o->X, o->ldx, o->n, dst, cap, written);
     case ADMM_REGM_F_ZOPT: return fetch_cols(*o, o->Z, o->ldz, o->m, dst, cap, written);
     case ADMM_REGM_F_UOPT: return fetch_cols(*o, o->U, o->ldz, o->m, dst, cap, written);
     case ADMM_REGM_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
     case ADMM_REGM_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
-    case ADMM_REGM_F_OBJEVALS:
-      if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return fetch_history(*o, o->objv, dst, cap, written);
+    case ADMM_REGM_F_OBJEVALS: return fetch_kept_history(*o, o->last.objevals, kNoObjevals, o->objv, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the multi-fit regression");
   }
 }

@@ -181,6 +181,8 @@ namespace {
 
 using namespace admm;
 
+const char* kWho = "the sparse multi-lasso";
+
 int slm_setup(admm_sparse_lasso* o, const admm_sparse_lasso_desc* desc, const std::vector<double>& ph,
               const std::vector<int32_t>& nh) {
   const int32_t K = desc->K;
@@ -260,13 +262,9 @@ int admm_sparse_lasso_create(const admm_sparse_lasso_desc* desc, admm_sparse_las
   if (desc->struct_size != static_cast<int32_t>(sizeof(admm_sparse_lasso_desc)))
     return fail(ADMM_E_INVALID, "admm_sparse_lasso_desc.struct_size mismatch (ABI version skew)");
   if (desc->K < 1) return fail(ADMM_E_INVALID, "the sparse multi-lasso needs at least one fit (K >= 1)");
-  if (!desc->D) return fail(ADMM_E_INVALID, "the sparse multi-lasso needs D (admm_sparse_desc)");
-  if (desc->D->mem != ADMM_MEM_HOST) return fail(ADMM_E_INVALID, "the sparse multi-lasso takes D in host arrays");
-  ADMM_TRY(sparse_csc_check(desc->D));
+  ADMM_TRY(check_sparse_D(kWho, desc->D));
   if (!desc->S) return fail(ADMM_E_INVALID, "the sparse multi-lasso needs the responses S (rows x ns)");
-  if (desc->ns != 1 && desc->ns != desc->K)
-    return fail(ADMM_E_INVALID, "S has " + std::to_string(desc->ns) + " columns: one shared response or one per fit (" +
-                                    std::to_string(desc->K) + ")");
+  ADMM_TRY(check_response_columns(desc->ns, desc->K));
   if (!desc->lambda) return fail(ADMM_E_INVALID, "the sparse multi-lasso needs lambda (K values)");
   std::vector<double> ph(static_cast<size_t>(2) * desc->K, 0.0);
   std::vector<int32_t> nh(static_cast<size_t>(desc->K), 0);
@@ -283,20 +281,8 @@ int admm_sparse_lasso_create(const admm_sparse_lasso_desc* desc, admm_sparse_las
     for (int64_t i = 0; i < desc->D->cols; ++i)
       if (!finite_nonneg(desc->weights[i]))
         return fail(ADMM_E_INVALID, "penalty: weight " + std::to_string(i) + " is negative or not finite");
-  if (desc->comm) return fail(ADMM_E_UNSUPPORTED, "the sparse multi-lasso is not row-sharded");
-  int ndev = 0;
-  ADMM_TRY(admm_device_count(&ndev));
-  if (ndev <= 0) return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
-  if (desc->device < 0 || desc->device >= ndev) return fail(ADMM_E_INVALID, "bad device ordinal");
-  admm_sparse_lasso* o = new admm_sparse_lasso();
-  const int rc = slm_setup(o, desc, ph, nh);
-  if (rc != ADMM_OK) {
-    const std::string msg = admm_last_error();
-    admm_sparse_lasso_destroy(o);
-    return fail(rc, msg);
-  }
-  *out = o;
-  return ADMM_OK;
+  ADMM_TRY(check_placement(kWho, desc->comm, desc->device));
+  return create_object(out, admm_sparse_lasso_destroy, [&](admm_sparse_lasso* o) { return slm_setup(o, desc, ph, nh); });
 }
 
 int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options* opts,
@@ -305,9 +291,7 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
   if (opts->struct_size != static_cast<int32_t>(sizeof(admm_sparse_lasso_options)))
     return fail(ADMM_E_INVALID, "admm_sparse_lasso_options.struct_size mismatch (ABI version skew)");
   admm_sparse_lasso_options op = *opts;
-  ADMM_TRY(check_run_options("sparse multi-lasso", "", &op));
-  if (!(op.cg_tol > 0.0)) op.cg_tol = 1e-12;
-  if (op.cg_maxit <= 0) op.cg_maxit = 200;
+  ADMM_TRY(check_sparse_run_options("sparse multi-lasso", &op));
   const bool dual = op.nodualerror == 0;
   ADMM_HIP_TRY(hipSetDevice(o->device));
   const int32_t N = op.maxiters, K = o->K;
@@ -365,7 +349,6 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
   fa.objevals = op.objevals;
   fa.maxiters = N;
   const SpmmMask run = cg.mask(false);
-  const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
 
   ADMM_TRY(begin_timing(*o));
   launch_slm_elem(ea, true, o->stream);  // y = rho*(z0 - u0) + D's
@@ -378,14 +361,11 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
       launch_slm_fit(ta, o->stream);
     }
     launch_slm_fin(fa, o->stream);
-    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
+    if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
   ADMM_TRY(finish_run(*o, all, "the sparse multi-lasso loop ended with fits still running", N, op.objevals != 0, o->objv,
                       runtime_s, summaries));
-  ADMM_TRY(cg.fill_counters(summaries, K));
-  o->last = op;
-  o->has_run = true;
-  return ADMM_OK;
+  return end_sparse_run(o, op, summaries);
 }
 
 int admm_sparse_lasso_set_weights(admm_sparse_lasso* o, const double* weights) {
@@ -394,31 +374,20 @@ int admm_sparse_lasso_set_weights(admm_sparse_lasso* o, const double* weights) {
 }
 
 int admm_sparse_lasso_fetch(admm_sparse_lasso* o, int field, double* dst, size_t cap, size_t* written) {
-  if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
-  if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
-  ADMM_HIP_TRY(hipSetDevice(o->device));
+  ADMM_TRY(fetch_head(o, dst));
   switch (field) {
     case ADMM_SLM_F_XOPT: return o->cg.fetch_matrix(o->cg.X, o->n, dst, cap, written);
     case ADMM_SLM_F_ZOPT: return o->cg.fetch_matrix(o->Z, o->n, dst, cap, written);
     case ADMM_SLM_F_UOPT: return o->cg.fetch_matrix(o->U, o->n, dst, cap, written);
     case ADMM_SLM_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
     case ADMM_SLM_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
-    case ADMM_SLM_F_OBJEVALS:
-      if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return fetch_history(*o, o->objv, dst, cap, written);
-    case ADMM_SLM_F_DNORM:
-    case ADMM_SLM_F_DERR:
-      if (o->last.nodualerror)
-        return fail(ADMM_E_INVALID, "the last run did not evaluate the dual residual (nodualerror = 1)");
-      return fetch_history(*o, field == ADMM_SLM_F_DNORM ? o->dnorm : o->derr, dst, cap, written);
+    case ADMM_SLM_F_OBJEVALS: return fetch_kept_history(*o, o->last.objevals, kNoObjevals, o->objv, dst, cap, written);
+    case ADMM_SLM_F_DNORM: return fetch_kept_history(*o, !o->last.nodualerror, kNoDual, o->dnorm, dst, cap, written);
+    case ADMM_SLM_F_DERR: return fetch_kept_history(*o, !o->last.nodualerror, kNoDual, o->derr, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the sparse multi-lasso");
   }
 }
 
-void admm_sparse_lasso_destroy(admm_sparse_lasso* o) {
-  if (!o) return;
-  o->cg.destroy();
-  delete o;
-}
+void admm_sparse_lasso_destroy(admm_sparse_lasso* o) { destroy_sparse(o); }
 
 }  // extern "C"

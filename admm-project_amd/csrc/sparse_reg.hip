@@ -175,6 +175,8 @@ struct admm_sparse_reg : MultiHost {
 
 namespace {
 
+const char* kWho = "the sparse multi-fit regression";
+
 int srg_setup(admm_sparse_reg* o, const admm_sparse_reg_desc* desc, const std::vector<int32_t>& kh,
               const std::vector<double>& ph) {
   const int32_t K = desc->K;
@@ -254,31 +256,14 @@ int admm_sparse_reg_create(const admm_sparse_reg_desc* desc, admm_sparse_reg** o
   if (desc->struct_size != static_cast<int32_t>(sizeof(admm_sparse_reg_desc)))
     return fail(ADMM_E_INVALID, "admm_sparse_reg_desc.struct_size mismatch (ABI version skew)");
   if (desc->K < 1) return fail(ADMM_E_INVALID, "the sparse multi-fit regression needs at least one fit (K >= 1)");
-  if (!desc->D) return fail(ADMM_E_INVALID, "the sparse multi-fit regression needs D (admm_sparse_desc)");
-  if (desc->D->mem != ADMM_MEM_HOST)
-    return fail(ADMM_E_INVALID, "the sparse multi-fit regression takes D in host arrays");
-  ADMM_TRY(sparse_csc_check(desc->D));
+  ADMM_TRY(check_sparse_D(kWho, desc->D));
   if (!desc->S) return fail(ADMM_E_INVALID, "the sparse multi-fit regression needs the responses S (rows x ns)");
-  if (desc->ns != 1 && desc->ns != desc->K)
-    return fail(ADMM_E_INVALID, "S has " + std::to_string(desc->ns) + " columns: one shared response or one per fit (" +
-                                    std::to_string(desc->K) + ")");
+  ADMM_TRY(check_response_columns(desc->ns, desc->K));
   std::vector<int32_t> kh;
   std::vector<double> ph;
   ADMM_TRY(check_reg_fits(desc->K, desc->kind, desc->a, desc->b, desc->epsilon, desc->delta, &kh, &ph));
-  if (desc->comm) return fail(ADMM_E_UNSUPPORTED, "the sparse multi-fit regression is not row-sharded");
-  int ndev = 0;
-  ADMM_TRY(admm_device_count(&ndev));
-  if (ndev <= 0) return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
-  if (desc->device < 0 || desc->device >= ndev) return fail(ADMM_E_INVALID, "bad device ordinal");
-  admm_sparse_reg* o = new admm_sparse_reg();
-  const int rc = srg_setup(o, desc, kh, ph);
-  if (rc != ADMM_OK) {
-    const std::string msg = admm_last_error();
-    admm_sparse_reg_destroy(o);
-    return fail(rc, msg);
-  }
-  *out = o;
-  return ADMM_OK;
+  ADMM_TRY(check_placement(kWho, desc->comm, desc->device));
+  return create_object(out, admm_sparse_reg_destroy, [&](admm_sparse_reg* o) { return srg_setup(o, desc, kh, ph); });
 }
 
 int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts, admm_sparse_reg_summary* summaries,
@@ -287,9 +272,7 @@ int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts,
   if (opts->struct_size != static_cast<int32_t>(sizeof(admm_sparse_reg_options)))
     return fail(ADMM_E_INVALID, "admm_sparse_reg_options.struct_size mismatch (ABI version skew)");
   admm_sparse_reg_options op = *opts;
-  ADMM_TRY(check_run_options("sparse multi-fit", "", &op));
-  if (!(op.cg_tol > 0.0)) op.cg_tol = 1e-12;
-  if (op.cg_maxit <= 0) op.cg_maxit = 200;
+  ADMM_TRY(check_sparse_run_options("sparse multi-fit", &op));
   const bool dual = op.nodualerror == 0;
   ADMM_HIP_TRY(hipSetDevice(o->device));
   const int32_t N = op.maxiters, K = o->K;
@@ -353,7 +336,6 @@ int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts,
   fa.objevals = op.objevals;
   fa.maxiters = N;
   const SpmmMask run = cg.mask(false);
-  const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
 
   ADMM_TRY(begin_timing(*o));
   launch_srg_elem(ea, true, o->stream);  // V = (s + z0) - u0
@@ -369,14 +351,11 @@ int admm_sparse_reg_run(admm_sparse_reg* o, const admm_sparse_reg_options* opts,
       launch_srg_dual(da, o->stream);
     }
     launch_srg_fin(fa, o->stream);
-    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
+    if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
   ADMM_TRY(finish_run(*o, all, "the sparse multi-fit loop ended with fits still running", N, op.objevals != 0, o->objv,
                       runtime_s, summaries));
-  ADMM_TRY(cg.fill_counters(summaries, K));
-  o->last = op;
-  o->has_run = true;
-  return ADMM_OK;
+  return end_sparse_run(o, op, summaries);
 }
 
 int admm_sparse_reg_set_weights(admm_sparse_reg* o, const double* weights) {
@@ -385,31 +364,20 @@ int admm_sparse_reg_set_weights(admm_sparse_reg* o, const double* weights) {
 }
 
 int admm_sparse_reg_fetch(admm_sparse_reg* o, int field, double* dst, size_t cap, size_t* written) {
-  if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
-  if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
-  ADMM_HIP_TRY(hipSetDevice(o->device));
+  ADMM_TRY(fetch_head(o, dst));
   switch (field) {
     case ADMM_SRG_F_XOPT: return o->cg.fetch_matrix(o->cg.X, o->n, dst, cap, written);
     case ADMM_SRG_F_ZOPT: return o->cg.fetch_matrix(o->Z, o->m, dst, cap, written);
     case ADMM_SRG_F_UOPT: return o->cg.fetch_matrix(o->U, o->m, dst, cap, written);
     case ADMM_SRG_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
     case ADMM_SRG_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
-    case ADMM_SRG_F_OBJEVALS:
-      if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return fetch_history(*o, o->objv, dst, cap, written);
-    case ADMM_SRG_F_DNORM:
-    case ADMM_SRG_F_DERR:
-      if (o->last.nodualerror)
-        return fail(ADMM_E_INVALID, "the last run did not evaluate the dual residual (nodualerror = 1)");
-      return fetch_history(*o, field == ADMM_SRG_F_DNORM ? o->dnorm : o->derr, dst, cap, written);
+    case ADMM_SRG_F_OBJEVALS: return fetch_kept_history(*o, o->last.objevals, kNoObjevals, o->objv, dst, cap, written);
+    case ADMM_SRG_F_DNORM: return fetch_kept_history(*o, !o->last.nodualerror, kNoDual, o->dnorm, dst, cap, written);
+    case ADMM_SRG_F_DERR: return fetch_kept_history(*o, !o->last.nodualerror, kNoDual, o->derr, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the sparse multi-fit regression");
   }
 }
 
-void admm_sparse_reg_destroy(admm_sparse_reg* o) {
-  if (!o) return;
-  o->cg.destroy();
-  delete o;
-}
+void admm_sparse_reg_destroy(admm_sparse_reg* o) { destroy_sparse(o); }
 
 }  // extern "C"

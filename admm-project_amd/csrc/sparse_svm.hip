@@ -242,9 +242,7 @@ int admm_sparse_svm_create(const admm_sparse_svm_desc* desc, admm_sparse_svm** o
   if (desc->struct_size != static_cast<int32_t>(sizeof(admm_sparse_svm_desc)))
     return fail(ADMM_E_INVALID, "admm_sparse_svm_desc.struct_size mismatch (ABI version skew)");
   if (desc->K < 1) return fail(ADMM_E_INVALID, "the one-vs-rest linear SVM needs at least one class (K >= 1)");
-  if (!desc->D) return fail(ADMM_E_INVALID, "the sparse linear SVM needs D (admm_sparse_desc)");
-  if (desc->D->mem != ADMM_MEM_HOST) return fail(ADMM_E_INVALID, "the sparse linear SVM takes D in host arrays");
-  ADMM_TRY(sparse_csc_check(desc->D));
+  ADMM_TRY(check_sparse_D("the sparse linear SVM", desc->D));
   if (!desc->ELL) return fail(ADMM_E_INVALID, "the linear SVM needs the label matrix ELL (m x K)");
   if (!(desc->C >= 0.0) || !finite_nonneg(desc->C))
     return fail(ADMM_E_INVALID, "Given regularization parameter C is not a nonnegative number!");
@@ -253,20 +251,8 @@ int admm_sparse_svm_create(const admm_sparse_svm_desc* desc, admm_sparse_svm** o
   for (int64_t i = 0; i < mk; ++i)
     if (desc->ELL[i] != 1.0 && desc->ELL[i] != -1.0)
       return fail(ADMM_E_INVALID, "a label of class " + std::to_string(i / desc->D->rows) + " is neither +1 nor -1");
-  if (desc->comm) return fail(ADMM_E_UNSUPPORTED, "the sparse one-vs-rest linear SVM is not row-sharded");
-  int ndev = 0;
-  ADMM_TRY(admm_device_count(&ndev));
-  if (ndev <= 0) return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
-  if (desc->device < 0 || desc->device >= ndev) return fail(ADMM_E_INVALID, "bad device ordinal");
-  admm_sparse_svm* o = new admm_sparse_svm();
-  const int rc = ssv_setup(o, desc);
-  if (rc != ADMM_OK) {
-    const std::string msg = admm_last_error();
-    admm_sparse_svm_destroy(o);
-    return fail(rc, msg);
-  }
-  *out = o;
-  return ADMM_OK;
+  ADMM_TRY(check_placement("the sparse one-vs-rest linear SVM", desc->comm, desc->device));
+  return create_object(out, admm_sparse_svm_destroy, [&](admm_sparse_svm* o) { return ssv_setup(o, desc); });
 }
 
 int admm_sparse_svm_run(admm_sparse_svm* o, const admm_sparse_svm_options* opts, admm_sparse_svm_summary* summaries,
@@ -275,9 +261,7 @@ int admm_sparse_svm_run(admm_sparse_svm* o, const admm_sparse_svm_options* opts,
   if (opts->struct_size != static_cast<int32_t>(sizeof(admm_sparse_svm_options)))
     return fail(ADMM_E_INVALID, "admm_sparse_svm_options.struct_size mismatch (ABI version skew)");
   admm_sparse_svm_options op = *opts;
-  ADMM_TRY(check_run_options("sparse one-vs-rest", "", &op));
-  if (!(op.cg_tol > 0.0)) op.cg_tol = 1e-12;
-  if (op.cg_maxit <= 0) op.cg_maxit = 200;
+  ADMM_TRY(check_sparse_run_options("sparse one-vs-rest", &op));
   ADMM_HIP_TRY(hipSetDevice(o->device));
   const int32_t N = op.maxiters, K = o->K;
   ADMM_TRY(resize_histories(*o, {&o->pnorm, &o->perr, &o->hnorm, &o->objv}, N));
@@ -327,7 +311,6 @@ int admm_sparse_svm_run(admm_sparse_svm* o, const admm_sparse_svm_options* opts,
   fa.objevals = op.objevals;
   fa.maxiters = N;
   const SpmmMask run = cg.mask(false);
-  const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
 
   ADMM_TRY(begin_timing(*o));
   launch_ssv_elem(ea, true, o->stream);  // V = z0 - u0
@@ -338,14 +321,11 @@ int admm_sparse_svm_run(admm_sparse_svm* o, const admm_sparse_svm_options* opts,
     launch_spmm(cg.sp.n, cg.X, cg.T, cg.chunks, run, o->stream);  // D x
     launch_ssv_elem(ea, false, o->stream);
     launch_ssv_fin(fa, o->stream);
-    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
+    if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
   ADMM_TRY(finish_run(*o, all, "the sparse one-vs-rest loop ended with classes still running", N, op.objevals != 0,
                       o->objv, runtime_s, summaries));
-  ADMM_TRY(cg.fill_counters(summaries, K));
-  o->last = op;
-  o->has_run = true;
-  return ADMM_OK;
+  return end_sparse_run(o, op, summaries);
 }
 
 int admm_sparse_svm_set_cost(admm_sparse_svm* o, const double* weights, const double* class_cost) {
@@ -355,9 +335,7 @@ int admm_sparse_svm_set_cost(admm_sparse_svm* o, const double* weights, const do
 }
 
 int admm_sparse_svm_fetch(admm_sparse_svm* o, int field, double* dst, size_t cap, size_t* written) {
-  if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
-  if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
-  ADMM_HIP_TRY(hipSetDevice(o->device));
+  ADMM_TRY(fetch_head(o, dst));
   switch (field) {
     case ADMM_OVR_F_XOPT: return o->cg.fetch_matrix(o->cg.X, o->n, dst, cap, written);
     case ADMM_OVR_F_ZOPT: return o->cg.fetch_matrix(o->Z, o->m, dst, cap, written);
@@ -365,17 +343,11 @@ int admm_sparse_svm_fetch(admm_sparse_svm* o, int field, double* dst, size_t cap
     case ADMM_OVR_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
     case ADMM_OVR_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
     case ADMM_OVR_F_HNORMSQ: return fetch_history(*o, o->hnorm, dst, cap, written);
-    case ADMM_OVR_F_OBJEVALS:
-      if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return fetch_history(*o, o->objv, dst, cap, written);
+    case ADMM_OVR_F_OBJEVALS: return fetch_kept_history(*o, o->last.objevals, kNoObjevals, o->objv, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the sparse one-vs-rest linear SVM");
   }
 }
 
-void admm_sparse_svm_destroy(admm_sparse_svm* o) {
-  if (!o) return;
-  o->cg.destroy();
-  delete o;
-}
+void admm_sparse_svm_destroy(admm_sparse_svm* o) { destroy_sparse(o); }
 
 }  // extern "C"

@@ -445,15 +445,7 @@ int admm_svm_ovr_create(const admm_svm_ovr_desc* desc, admm_svm_ovr** out) {
   if (desc->n > kOvMaxN)
     return fail(ADMM_E_UNSUPPORTED, "the one-vs-rest pass holds a 64-row block of D in registers: n <= " +
                                         std::to_string(kOvMaxN) + kPerClass);
-  admm_svm_ovr* o = new admm_svm_ovr();
-  const int rc = ovr_setup(o, desc);
-  if (rc != ADMM_OK) {
-    const std::string msg = admm_last_error();
-    admm_svm_ovr_destroy(o);
-    return fail(rc, msg);
-  }
-  *out = o;
-  return ADMM_OK;
+  return create_object(out, admm_svm_ovr_destroy, [&](admm_svm_ovr* o) { return ovr_setup(o, desc); });
 }
 
 int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm_ovr_summary* summaries,
@@ -519,7 +511,6 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
       launch_ovr_pass(pa, init, o->chunk_logistic[ch] != 0, o->chunk_cost[ch] ? &oc : nullptr, o->stream);
     }
   };
-  const int check_every = op.check_every > 0 ? op.check_every : (op.domaxiters ? 64 : 8);
 
   ADMM_TRY(begin_timing(*o));
   pass(true);  // g = D'(z0 - u0)
@@ -531,7 +522,7 @@ int admm_svm_ovr_run(admm_svm_ovr* o, const admm_svm_ovr_options* opts, admm_svm
     dense_xupdate(*o);
     pass(false);
     launch_ovr_gsum_fin(fa, o->stream);
-    if ((it + 1) % check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
+    if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
   ADMM_TRY(finish_run(*o, all, "the one-vs-rest loop ended with classes still running", N, op.objevals != 0, o->objv,
                       runtime_s, summaries));
@@ -548,9 +539,7 @@ int admm_svm_ovr_set_cost(admm_svm_ovr* o, const double* weights, const double* 
 }
 
 int admm_svm_ovr_fetch(admm_svm_ovr* o, int field, double* dst, size_t cap, size_t* written) {
-  if (!o || !dst) return fail(ADMM_E_INVALID, "object/dst is NULL");
-  if (!o->has_run) return fail(ADMM_E_INVALID, "fetch before the first run");
-  ADMM_HIP_TRY(hipSetDevice(o->device));
+  ADMM_TRY(fetch_head(o, dst));
   switch (field) {
     case ADMM_OVR_F_XOPT: return fetch_cols(*o, o->X, o->ldx, o->n, dst, cap, written);
     case ADMM_OVR_F_ZOPT: return fetch_cols(*o, o->Z, o->ldz, o->m, dst, cap, written);
@@ -558,9 +547,7 @@ int admm_svm_ovr_fetch(admm_svm_ovr* o, int field, double* dst, size_t cap, size
     case ADMM_OVR_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
     case ADMM_OVR_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
     case ADMM_OVR_F_HNORMSQ: return fetch_history(*o, o->hnorm, dst, cap, written);
-    case ADMM_OVR_F_OBJEVALS:
-      if (!o->last.objevals) return fail(ADMM_E_INVALID, "the last run did not evaluate the objective (objevals = 0)");
-      return fetch_history(*o, o->objv, dst, cap, written);
+    case ADMM_OVR_F_OBJEVALS: return fetch_kept_history(*o, o->last.objevals, kNoObjevals, o->objv, dst, cap, written);
     default: return fail(ADMM_E_INVALID, "unknown field of the one-vs-rest linear SVM");
   }
 }

@@ -621,12 +621,59 @@ class Engine:
         return out
 
 
-class _MultiOwner:
-    """What the owners of a "K runs over one D" handle share (SvmOvr, RegMulti, SparseSvmOvr, SparseRegMulti).  A
-    subclass names its C functions (``_abi`` = their common prefix) and sets ``_lib``, ``_h``, ``m``, ``n``, ``K``."""
+# what every multi-fit loop takes (run's keywords beside the start vectors and a class's own), and the on / off fields
+_LOOP = dict(rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, relax=1.0, fast=L.FAST_OFF, convtest=0, domaxiters=0,
+             objevals=0, check_every=0)
+_FLAGS = ("convtest", "domaxiters", "objevals", "nodualerror")
 
-    _abi = ""    # "admm_svm_ovr": <_abi>_destroy and <_abi>_fetch
-    _unit = ""   # what a column is, for the messages: "fit" | "class"
+
+class _MultiOwner:
+    """What the owners of a "K runs over one D" handle share (SvmOvr, RegMulti, SparseSvmOvr, SparseRegMulti,
+    SparseLassoMulti): the handle's life (``_desc``, ``_create``, ``close``), ``chunk``, the run (``_run``: the options,
+    the start vectors, ``<abi>_run``, the summary), ``fetch`` and ``results``, the dict the solvers return.  A subclass
+    declares the data below, builds its desc in ``__init__`` (which sets ``m``, ``n``, ``K``; the sparse three through
+    ``_sparse_D``), and keeps ``run`` for the keywords that are its own."""
+
+    _abi = ""      # "admm_svm_ovr": the prefix of <_abi>_create / _run / _fetch / _chunk / _destroy / _*_default
+    _unit = ""     # what a column is, for the messages: "fit" | "class"
+    _types = ()    # the ctypes structs (desc, options, summary)
+    _rows = dict(x0="n", z0="m", u0="m")  # the attribute that holds the row count of a start matrix
+    # result name -> (field code, rows): "n" | "m", or a history of max(steps) rows: "hist", kept by every run, "objevals"
+    # / "dual", kept only when the run evaluated the objective / the dual residual
+    _fields = {}
+    _cg = False            # the x-update is the sparse CG: cg_tol / cg_maxit, nnz and the CG counters
+    _chunk_result = True   # results() reports chunk
+
+    def _desc(self):
+        """the library loaded, a device required, and a desc at its defaults"""
+        self._h = None
+        self._lib = L.load()
+        L.require_device()
+        d = self._types[0]()
+        getattr(self._lib, self._abi + "_desc_default")(C.byref(d))
+        return d
+
+    def _sparse_D(self, D, Y, keep, mismatch):
+        """(admm_sparse_desc of D in canonical CSC, Y as an m x columns matrix: the responses or the labels); sets m, n
+        and nnz.  ``mismatch`` is the message when Y has not m rows"""
+        sd = L.sparse_desc(D, keep)
+        Y = np.asarray(Y, dtype=np.float64)
+        Y = _f64(Y.reshape(-1, 1) if Y.ndim == 1 else Y)
+        self.m, self.n, self.nnz = int(sd.rows), int(sd.cols), int(sd.nnz)
+        if Y.ndim != 2 or Y.shape[0] != self.m:
+            raise ValueError(mismatch)
+        return sd, Y
+
+    def _create(self, d):
+        h = C.c_void_p()
+        L.check(getattr(self._lib, self._abi + "_create")(C.byref(d), C.byref(h)))
+        self._h = h
+        self.objevals = False
+
+    @classmethod
+    def chunk(cls):
+        """columns (fits or classes) one pass over D, or one sparse product, serves"""
+        return int(getattr(L.load(), cls._abi + "_chunk")())
 
     def close(self):
         if getattr(self, "_h", None):
@@ -653,12 +700,32 @@ class _MultiOwner:
             if v is None:
                 continue
             v = _f64(v)
-            rows = self.n if name == "x0" else self.m
+            rows = getattr(self, self._rows[name])
             if check and v.shape != (rows, self.K):
                 raise ValueError(f"{name} is not a {rows} x {self.K} matrix (one column per {self._unit})")
             keep.append(v)
             setattr(o, name, L.as_dp(v))
         return keep
+
+    def _run(self, loop, starts, check=True, **own):
+        """One run: ``loop`` holds keywords of _LOOP (any other is a TypeError), ``own`` the option fields of the class
+        (Hnormtol, cg_tol, cg_maxit, nodualerror), ``starts`` the start matrices.  Returns _summary."""
+        for key in loop:
+            if key not in _LOOP:
+                raise TypeError(f"run() got an unexpected keyword argument {key!r}")
+        _, Options, Summary = self._types
+        o = Options()
+        getattr(self._lib, self._abi + "_options_default")(C.byref(o))
+        for name, v in dict(_LOOP, **loop, **own).items():
+            setattr(o, name, int(bool(v)) if name in _FLAGS else type(getattr(o, name))(v))
+        keep = self._start_vectors(o, check, **starts)  # noqa: F841 (alive until the run returns)
+        summ = (Summary * self.K)()
+        rt = C.c_double(0)
+        L.check(getattr(self._lib, self._abi + "_run")(self._h, C.byref(o), summ, C.byref(rt)))
+        self.objevals = bool(o.objevals)
+        if "nodualerror" in own:
+            self.dual = not o.nodualerror
+        return self._summary(summ, rt, cg=self._cg)
 
     @staticmethod
     def _summary(summ, rt, cg=False):
@@ -671,23 +738,59 @@ class _MultiOwner:
         out["runtime"] = rt.value
         return out
 
+    def results(self, summ):
+        """The result dict of the run whose summary is ``summ``: xopt / zopt / uopt, steps, the histories the run kept
+        cut to max(steps) rows, objopt and runtime, then chunk and, for the CG objects, xsolve = 'cg', nnz and the CG
+        counters"""
+        kept = dict(n=self.n, m=self.m, hist=int(summ["steps"].max()))
+        if self.objevals:
+            kept["objevals"] = kept["hist"]
+        if getattr(self, "dual", False):
+            kept["dual"] = kept["hist"]
+        res = {key: self.fetch(field, kept[rows]) for key, (field, rows) in self._fields.items() if rows in ("n", "m")}
+        res["steps"] = summ["steps"]
+        res.update({key: self.fetch(field, kept[rows]) for key, (field, rows) in self._fields.items()
+                    if rows not in ("n", "m") and rows in kept})
+        res.update(objopt=summ["objopt"], runtime=summ["runtime"])
+        if self._chunk_result:
+            res["chunk"] = self.chunk()
+        if self._cg:
+            res.update(xsolve="cg", nnz=self.nnz, cg_iters_total=summ["cg_iters_total"],
+                       cg_capped_updates=summ["cg_capped_updates"])
+        return res
+
+
+def _set_svm_cost(self, weights=None, classcost=None):
+    """The costs of the K classes (<abi>_set_cost): ``weights`` = m values >= 0 shared by all classes, ``classcost`` = a
+    K x 2 array, row c = (cost_pos, cost_neg) of class c.  None: the defaults (1)."""
+    w = _weights(weights, self.m, "observations")
+    cc = None if classcost is None else np.ascontiguousarray(np.asarray(classcost, dtype=np.float64))
+    if cc is not None and cc.shape != (self.K, 2):
+        raise ValueError(f"classcost is not a {self.K} x 2 array (one (pos, neg) pair per class)")
+    L.check(getattr(self._lib, self._abi + "_set_cost")(self._h, None if w is None else L.as_dp(w),
+                                                        None if cc is None else L.as_dp(cc)))
+
+
+_OVR_FIELDS = dict(xopt=(L.OVR_F_XOPT, "n"), zopt=(L.OVR_F_ZOPT, "m"), uopt=(L.OVR_F_UOPT, "m"),
+                   pnorm=(L.OVR_F_PNORM, "hist"), perr=(L.OVR_F_PERR, "hist"), Hnormsq=(L.OVR_F_HNORMSQ, "hist"),
+                   objevals=(L.OVR_F_OBJEVALS, "objevals"))
+
 
 class SvmOvr(_MultiOwner):
     """Python owner of one ``admm_svm_ovr`` handle: the linear SVM for K one-vs-rest classes over one D."""
 
     _abi, _unit = "admm_svm_ovr", "class"
+    _types = (L.SvmOvrDesc, L.SvmOvrOptions, L.SvmOvrSummary)
+    _fields, _chunk_result = _OVR_FIELDS, False
+    set_cost = _set_svm_cost
 
     def __init__(self, D, ELL, C_, losses, *, Dplus=None, device=0):
-        self._h = None
-        self._lib = L.load()
-        L.require_device()
+        d = self._desc()
         D = _f64(D)
         ELL = _f64(ELL)
         self.m, self.n = (int(v) for v in D.shape)
         self.K = int(ELL.shape[1])
         loss = np.ascontiguousarray([L.loss_code(v) for v in losses], dtype=np.int32)
-        d = L.SvmOvrDesc()
-        self._lib.admm_svm_ovr_desc_default(C.byref(d))
         d.K, d.m, d.n = self.K, self.m, self.n
         d.D, d.ldD, d.ELL = L.as_dp(D), self.m, L.as_dp(ELL)
         d.loss = loss.ctypes.data_as(C.POINTER(C.c_int32))
@@ -695,31 +798,8 @@ class SvmOvr(_MultiOwner):
         if Dplus is not None:
             Dplus = _f64(Dplus)
             d.Dplus = L.as_dp(Dplus)
-        h = C.c_void_p()
-        L.check(self._lib.admm_svm_ovr_create(C.byref(d), C.byref(h)))
-        self._h = h
+        self._create(d)
 
-    def set_cost(self, weights=None, classcost=None):
-        """The costs of the K classes (admm_svm_ovr_set_cost): ``weights`` = m values >= 0 shared by all classes,
-        ``classcost`` = a K x 2 array, row c = (cost_pos, cost_neg) of class c.  None: the defaults (1)."""
-        w = _weights(weights, self.m, "observations")
-        cc = None if classcost is None else np.ascontiguousarray(np.asarray(classcost, dtype=np.float64))
-        if cc is not None and cc.shape != (self.K, 2):
-            raise ValueError(f"classcost is not a {self.K} x 2 array (one (pos, neg) pair per class)")
-        L.check(self._lib.admm_svm_ovr_set_cost(self._h, None if w is None else L.as_dp(w),
-                                                None if cc is None else L.as_dp(cc)))
-
-    def run(self, *, rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, Hnormtol=1e-6, relax=1.0, fast=L.FAST_OFF,
-            convtest=0, domaxiters=0, objevals=0, check_every=0, x0=None, z0=None, u0=None):
-        o = L.SvmOvrOptions()
-        self._lib.admm_svm_ovr_options_default(C.byref(o))
-        o.maxiters, o.rho, o.abstol, o.reltol, o.Hnormtol = int(maxiters), float(rho), float(abstol), float(reltol), \
-            float(Hnormtol)
-        o.relax, o.fast, o.convtest = float(relax), int(fast), int(bool(convtest))
-        o.domaxiters, o.objevals, o.check_every = int(bool(domaxiters)), int(bool(objevals)), int(check_every)
-        keep = self._start_vectors(o, check=False, x0=x0, z0=z0, u0=u0)  # noqa: F841 (alive until the run returns)
-        summ = (L.SvmOvrSummary * self.K)()
-        rt = C.c_double(0)
-        L.check(self._lib.admm_svm_ovr_run(self._h, C.byref(o), summ, C.byref(rt)))
-        self.objevals = bool(objevals)
-        return self._summary(summ, rt)
+    def run(self, *, Hnormtol=1e-6, x0=None, z0=None, u0=None, **loop):
+        """``loop``: rho, maxiters, abstol, reltol, relax, fast, convtest, domaxiters, objevals, check_every"""
+        return self._run(loop, dict(x0=x0, z0=z0, u0=u0), check=False, Hnormtol=Hnormtol)

@@ -18,59 +18,44 @@ class RegMulti(_MultiOwner):
     each, or None for the defaults 1, 1, 0, 1."""
 
     _abi, _unit = "admm_reg_multi", "fit"
+    _types = (L.RegMultiDesc, L.RegMultiOptions, L.RegMultiSummary)
+    _fields = dict(xopt=(L.REGM_F_XOPT, "n"), zopt=(L.REGM_F_ZOPT, "m"), uopt=(L.REGM_F_UOPT, "m"),
+                   pnorm=(L.REGM_F_PNORM, "hist"), perr=(L.REGM_F_PERR, "hist"), objevals=(L.REGM_F_OBJEVALS, "objevals"))
 
     def __init__(self, D, S, kinds, a=None, b=None, epsilon=None, delta=None, *, device=0):
-        self._h = None
-        self._lib = L.load()
-        L.require_device()
+        d = self._desc()
         D = _f64(D)
         S = np.asarray(S, dtype=np.float64)
         S = _f64(S.reshape(-1, 1) if S.ndim == 1 else S)
         if S.ndim != 2 or S.shape[0] != D.shape[0]:
             raise ValueError("The number of rows in argument D do not match size of S!")
         self.m, self.n = (int(v) for v in D.shape)
+        d.m, d.n, d.D, d.ldD, d.mem = self.m, self.n, L.as_dp(D), self.m, L.MEM_HOST
+        keep = self._fit_fields(d, S, kinds, a, b, epsilon, delta, device)  # noqa: F841 (alive until create returns)
+        self._create(d)
+
+    def _fit_fields(self, d, S, kinds, a, b, epsilon, delta, device):
+        """d.K, S, ns, kind, a, b, epsilon, delta and device of either regression desc; sets K and returns what must
+        outlive create"""
         kind = np.ascontiguousarray([KINDS.get(v, v) if isinstance(v, str) else int(v) for v in kinds], dtype=np.int32)
         self.K = int(kind.size)
-        d = L.RegMultiDesc()
-        self._lib.admm_reg_multi_desc_default(C.byref(d))
-        d.K, d.m, d.n = self.K, self.m, self.n
-        d.D, d.ldD, d.S, d.ns = L.as_dp(D), self.m, L.as_dp(S), int(S.shape[1])
+        d.K, d.S, d.ns, d.device = self.K, L.as_dp(S), int(S.shape[1]), int(device)
         d.kind = kind.ctypes.data_as(C.POINTER(C.c_int32))
-        d.mem, d.device = L.MEM_HOST, int(device)
-        keep = []
+        keep = [kind]
         for name, v in (("a", a), ("b", b), ("epsilon", epsilon), ("delta", delta)):
             if v is not None:
-                arr = _weights(v, self.K, "fits", name)
-                keep.append(arr)
-                setattr(d, name, L.as_dp(arr))
-        h = C.c_void_p()
-        L.check(self._lib.admm_reg_multi_create(C.byref(d), C.byref(h)))
-        self._h = h
-        self.objevals = False
-
-    @staticmethod
-    def chunk():
-        """fits one pass over D serves"""
-        return int(L.load().admm_reg_multi_chunk())
+                keep.append(_weights(v, self.K, "fits", name))
+                setattr(d, name, L.as_dp(keep[-1]))
+        return keep
 
     def set_weights(self, weights=None):
-        """m observation weights >= 0 shared by all fits (admm_reg_multi_set_weights); None restores 1"""
+        """m observation weights >= 0 shared by all fits (<abi>_set_weights); None restores 1"""
         w = _weights(weights, self.m, "observations")
-        L.check(self._lib.admm_reg_multi_set_weights(self._h, None if w is None else L.as_dp(w)))
+        L.check(getattr(self._lib, self._abi + "_set_weights")(self._h, None if w is None else L.as_dp(w)))
 
-    def run(self, *, rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, relax=1.0, fast=L.FAST_OFF, convtest=0,
-            domaxiters=0, objevals=0, check_every=0, x0=None, z0=None, u0=None):
-        o = L.RegMultiOptions()
-        self._lib.admm_reg_multi_options_default(C.byref(o))
-        o.maxiters, o.rho, o.abstol, o.reltol = int(maxiters), float(rho), float(abstol), float(reltol)
-        o.relax, o.fast, o.convtest = float(relax), int(fast), int(bool(convtest))
-        o.domaxiters, o.objevals, o.check_every = int(bool(domaxiters)), int(bool(objevals)), int(check_every)
-        keep = self._start_vectors(o, x0=x0, z0=z0, u0=u0)  # noqa: F841 (alive until the run returns)
-        summ = (L.RegMultiSummary * self.K)()
-        rt = C.c_double(0)
-        L.check(self._lib.admm_reg_multi_run(self._h, C.byref(o), summ, C.byref(rt)))
-        self.objevals = bool(objevals)
-        return self._summary(summ, rt)
+    def run(self, *, x0=None, z0=None, u0=None, **loop):
+        """``loop``: rho, maxiters, abstol, reltol, relax, fast, convtest, domaxiters, objevals, check_every"""
+        return self._run(loop, dict(x0=x0, z0=z0, u0=u0))
 
     def launches(self):
         """kernel launches of the last run's iterations: dict(iterations, xsolve, passes, finalize, explicit_map)"""

@@ -51,6 +51,135 @@ def _engine_args(options, args, **more):
     return args
 
 
+def _options(options, message, optional=False):
+    """a copy of the caller's options (``optional``: None stands for an empty dict); ``message``: the solver's TypeError"""
+    if optional and options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise TypeError(message)
+    return dict(options)
+
+
+# ---- shared by the multi-fit solvers (K runs over one D: DESIGN.md q36-q39)
+_LOOP_KEYS = ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals")
+_CG_KEYS = ("cg_tol", "cg_maxit")
+
+
+def _pick(options, keys):
+    return {k: options[k] for k in keys if k in options}
+
+
+def _response_matrix(S, m):
+    """the responses as a matrix of m rows: a vector stands for one column"""
+    S = np.asarray(S, dtype=np.float64)
+    if S.ndim == 1:
+        S = S.reshape(-1, 1)
+    if S.ndim != 2:
+        raise ValueError("Argument S is neither a vector nor a matrix!")
+    if S.shape[0] != m:
+        raise ValueError("The number of rows in argument D do not match size of S!")
+    return S
+
+
+def _response_columns(S, K):
+    if S.shape[1] not in (1, K):
+        raise ValueError(f"S has {S.shape[1]} columns for {K} fits: one shared response or one column per fit")
+    return np.asfortranarray(S)
+
+
+def _start_matrices(options, rows_by_key, K, unit, default=None):
+    """options.x0 / z0 / u0 as rows x K matrices, one column per ``unit``.  Without ``default`` a start that is missing
+    or None is left out (zeros); with it, a missing one is ``default((rows, K))``"""
+    starts = {}
+    for key, rows in rows_by_key.items():
+        if key in options if default else options.get(key) is not None:
+            v = np.asarray(options[key], dtype=np.float64)
+            if v.shape != (rows, K):
+                raise ValueError(f"options.{key} is not a {rows} x {K} matrix (one column per {unit})!")
+        elif default:
+            v = default((rows, K))
+        else:
+            continue
+        starts[key] = np.asfortranarray(v)
+    return starts
+
+
+def _start_columns(options, rows_by_key, default=None):
+    """the K = 1 case from vectors: options.x0 / z0 / u0 as rows x 1 matrices"""
+    starts = {}
+    for key, rows in rows_by_key.items():
+        if key in options if default else options.get(key) is not None:
+            v = _colvec(options[key], key)
+        elif default:
+            v = default(rows)
+        else:
+            continue
+        if v.size != rows:
+            raise ValueError(f"options.{key} does not have {rows} entries!")
+        starts[key] = np.asfortranarray(v.reshape(rows, 1))
+    return starts
+
+
+def _sparse_refusals(options, who, also=(), stopcond=False):
+    """the options no sparse multi-fit object runs, each named in its ValueError; ``also``: keys
+    refused beside comm, ``stopcond``: the object runs the 'standard' stop rule alone"""
+    for key in ("fast", "convtest", "adaptive"):
+        if options.get(key, 0):
+            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
+    if options.get("relax", 1) != 1:
+        raise ValueError(f"options.relax is not available in {who} on a sparse D")
+    xs = options.get("xsolve", "auto")
+    if not (isinstance(xs, str) and xs.lower() in ("auto", "cg")):
+        raise ValueError(f"options.xsolve = {xs!r}: {who} on a sparse D runs the matrix-free x-update ('auto' or 'cg')")
+    for key in also + ("comm",):
+        if options.get(key) is not None:
+            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
+    if options.get("parallel", "none") not in ("none", 0, None):
+        raise ValueError(f"options.parallel is not available in {who} on a sparse D")
+    if stopcond and options.get("stopcond", "standard") != "standard":
+        raise ValueError(f"options.stopcond: {who} on a sparse D runs the 'standard' stop rule alone")
+
+
+def _run_and_close(obj, prepare=None, **run):
+    """``prepare(obj)`` (the weights or costs, if any), one run and the owner's results (engine._MultiOwner.results);
+    the owner is closed in any case"""
+    try:
+        if prepare is not None:
+            prepare(obj)
+        return obj.results(obj.run(**run))
+    finally:
+        obj.close()
+
+
+def _stack_fits(per, hist_keys):
+    """the results of K single-fit runs side by side, as a multi-fit owner returns them: a column per fit, the
+    histories NaN past a fit's last step"""
+    steps = np.array([r["steps"] for r in per], dtype=np.int64)
+    res = {key: np.asfortranarray(np.stack([np.asarray(r[key]).reshape(-1) for r in per], axis=1))
+           for key in ("xopt", "zopt", "uopt")}
+    for key in hist_keys:
+        if all(key in r for r in per):
+            res[key] = np.full((int(steps.max()), len(per)), np.nan, order="F")
+            for c, r in enumerate(per):
+                res[key][:steps[c], c] = np.asarray(r[key])[:steps[c]]
+    res["steps"] = steps
+    res["objopt"] = np.array([r.get("objopt", np.nan) for r in per], dtype=np.float64)
+    res["runtime"] = float(sum(r["runtime"] for r in per))
+    return res
+
+
+def _drop_fit_axis(res, hist_keys):
+    """a K = 1 result as the single-fit solvers return it: vectors, and Python scalars for steps, objopt and the CG
+    counters"""
+    for key in ("xopt", "zopt", "uopt") + hist_keys:
+        if key in res:
+            res[key] = np.ascontiguousarray(res[key][:, 0])
+    for key in ("steps", "cg_iters_total", "cg_capped_updates"):
+        res[key] = int(res[key][0])
+    res["objopt"] = float(res["objopt"][0])
+    return res
+
+
 def lasso(D, s, lam, options=None):
     """results = lasso(D, s, lambda, options)   (solvers/lasso.m:77-245)
 
@@ -67,9 +196,7 @@ def lasso(D, s, lam, options=None):
     ``options['ridge']`` (mu >= 0: + mu/2*||x||^2, the elastic net) and ``options['nonnegative']`` (1: x >= 0) change
     the z-update alone; the serial solver only.
     """
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!")
     t0 = time.perf_counter()
     lam = is_nonnegative_real(lam, "lambda")
     D = _matrix(D, "D", sparse_ok=True)
@@ -115,9 +242,7 @@ def grouplasso(D, s, lam, groups, options=None):
     block soft threshold z_g = v_g*max(0, 1 - (lambda*w_g/rho)/||v_g||) on the device (Boyd et al. 6.4.2).
     ``options['l1']`` > 0 adds l1*sum_i w_i*|x_i| (the sparse-group lasso); ``options['l1weights']``, ``['ridge']`` and
     ``['nonnegative']`` are lasso()'s."""
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!")
     t0 = time.perf_counter()
     lam = is_nonnegative_real(lam, "lambda")
     D = _matrix(D, "D", sparse_ok=True)
@@ -194,25 +319,15 @@ def lasso_multi(D, S, lams, options=None):
     ``xsolve = 'cg'``, ``nnz``, ``cg_iters_total`` and ``cg_capped_updates`` (K values each).  fast, convtest, relax,
     adaptive, an xsolve other than 'auto' / 'cg', comm, parallel and a stopcond other than 'standard' are refused by
     name."""
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Argument options is not a struct!")
-    options = dict(options)
+    options = _options(options, "Argument options is not a struct!", optional=True)
     t0 = time.perf_counter()
-    from . import _lib as L
-    if not L.is_sparse(D):
+    from ._lib import is_sparse
+    if not is_sparse(D):
         raise ValueError("lasso_multi runs on a scipy.sparse D: call lasso per fit on a dense design matrix")
-    _sparse_reg_refusals(options, "lasso_multi")
+    _sparse_refusals(options, "lasso_multi", stopcond=True)
     D = _matrix(D, "D", sparse_ok=True)
     m, n = D.shape
-    S = np.asarray(S, dtype=np.float64)
-    if S.ndim == 1:
-        S = S.reshape(-1, 1)
-    if S.ndim != 2:
-        raise ValueError("Argument S is neither a vector nor a matrix!")
-    if S.shape[0] != m:
-        raise ValueError("The number of rows in argument D do not match size of S!")
+    S = _response_matrix(S, m)
     lam = np.asarray(lams, dtype=np.float64).reshape(-1)
     K = int(lam.size)
     if K < 1:
@@ -220,9 +335,7 @@ def lasso_multi(D, S, lams, options=None):
     for k, v in enumerate(lam):
         if not np.isfinite(v) or v < 0:
             raise ValueError(f"fit {k}: lambda is not a nonnegative real number")
-    if S.shape[1] not in (1, K):
-        raise ValueError(f"S has {S.shape[1]} columns for {K} fits: one shared response or one column per fit")
-    S = np.asfortranarray(S)
+    S = _response_columns(S, K)
     ridge = _per_fit(options.get("ridge", 0.0), K, "ridge", lambda v: penalty_fields(dict(ridge=v), n)["ridge"])
     nonneg = _per_fit(options.get("nonnegative", 0), K, "nonnegative",
                       lambda v: penalty_fields(dict(nonnegative=v), n)["nonnegative"])
@@ -230,42 +343,11 @@ def lasso_multi(D, S, lams, options=None):
     w = None if pw is None else pw["l1weights"]
     if "rho" in options:
         is_positive_real(options["rho"], "options.rho")
-    starts = {}
-    for key in ("x0", "z0", "u0"):
-        if options.get(key) is not None:
-            v = np.asarray(options[key], dtype=np.float64)
-            if v.shape != (n, K):
-                raise ValueError(f"options.{key} is not a {n} x {K} matrix (one column per fit)!")
-            starts[key] = np.asfortranarray(v)
-    nodual = int(bool(options.get("nodualerror", 0)))
-    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals", "cg_tol",
-                                    "cg_maxit") if k in options}
+    starts = _start_matrices(options, dict(x0=n, z0=n, u0=n), K, "fit")
     from .sparse_lasso import SparseLassoMulti
-    res = {}
-    obj = SparseLassoMulti(D, S, lam, ridge, nonneg, w, device=int(options.get("device", 0)))
-    try:
-        summ = obj.run(check_every=int(options.get("check_every", 0)), nodualerror=nodual, z0=starts.get("z0"),
-                       u0=starts.get("u0"), **loop)
-        Smax = int(summ["steps"].max())
-        for key, field in (("xopt", L.SLM_F_XOPT), ("zopt", L.SLM_F_ZOPT), ("uopt", L.SLM_F_UOPT)):
-            res[key] = obj.fetch(field, n)
-        res["steps"] = summ["steps"]
-        res["pnorm"] = obj.fetch(L.SLM_F_PNORM, Smax)
-        res["perr"] = obj.fetch(L.SLM_F_PERR, Smax)
-        if not nodual:
-            res["dnorm"] = obj.fetch(L.SLM_F_DNORM, Smax)
-            res["derr"] = obj.fetch(L.SLM_F_DERR, Smax)
-        if loop.get("objevals", 0):
-            res["objevals"] = obj.fetch(L.SLM_F_OBJEVALS, Smax)
-        res["objopt"] = summ["objopt"]
-        res["runtime"] = summ["runtime"]
-        res["chunk"] = obj.chunk()
-        res["xsolve"] = "cg"
-        res["nnz"] = obj.nnz
-        res["cg_iters_total"] = summ["cg_iters_total"]
-        res["cg_capped_updates"] = summ["cg_capped_updates"]
-    finally:
-        obj.close()
+    res = _run_and_close(SparseLassoMulti(D, S, lam, ridge, nonneg, w, device=int(options.get("device", 0))),
+                         check_every=int(options.get("check_every", 0)), z0=starts.get("z0"), u0=starts.get("u0"),
+                         nodualerror=int(bool(options.get("nodualerror", 0))), **_pick(options, _LOOP_KEYS + _CG_KEYS))
     res["lams"] = lam.copy()
     res["solverruntime"] = time.perf_counter() - t0
     return res
@@ -277,13 +359,9 @@ def lasso_path(D, s, lams=None, options=None):
     the sparse product, 10), log-spaced from lambda_max = max over w_i > 0 of |(D's)_i| / w_i -- the smallest lambda whose
     solution is x = 0 -- down to ``options['lambda_min_ratio']`` * lambda_max (default 1e-2).  Returns lasso_multi's
     fields plus ``df``, the number of nonzeros of each zopt column."""
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Argument options is not a struct!")
-    options = dict(options)
-    from . import _lib as L
-    if not L.is_sparse(D):
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    from ._lib import is_sparse
+    if not is_sparse(D):
         raise ValueError("lasso_path runs on a scipy.sparse D: call lasso per lambda on a dense design matrix")
     s = _colvec(s, "s")
     nlambda = options.pop("nlambda", None)
@@ -305,9 +383,7 @@ def lasso_path(D, s, lams=None, options=None):
 
 
 def _lad_like(kind, D, s, options):
-    if not isinstance(options, dict):
-        raise TypeError("Argument options is not a struct!")
-    options = dict(options)
+    options = _options(options, "Argument options is not a struct!")
     t0 = time.perf_counter()
     from ._lib import is_sparse
     if is_sparse(D):
@@ -331,24 +407,6 @@ def _lad_like(kind, D, s, options):
     return results
 
 
-def _sparse_reg_refusals(options, who):
-    """the options the sparse multi-fit regression does not run, each named in its ValueError"""
-    for key in ("fast", "convtest", "adaptive"):
-        if options.get(key, 0):
-            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
-    if options.get("relax", 1) != 1:
-        raise ValueError(f"options.relax is not available in {who} on a sparse D")
-    xs = options.get("xsolve", "auto")
-    if not (isinstance(xs, str) and xs.lower() in ("auto", "cg")):
-        raise ValueError(f"options.xsolve = {xs!r}: {who} on a sparse D runs the matrix-free x-update ('auto' or 'cg')")
-    if options.get("comm") is not None:
-        raise ValueError(f"options.comm is not available in {who} on a sparse D")
-    if options.get("parallel", "none") not in ("none", 0, None):
-        raise ValueError(f"options.parallel is not available in {who} on a sparse D")
-    if options.get("stopcond", "standard") != "standard":
-        raise ValueError(f"options.stopcond: {who} on a sparse D runs the 'standard' stop rule alone")
-
-
 _SPARSE_REG_HIST = ("pnorm", "perr", "dnorm", "derr", "objevals")
 
 
@@ -356,48 +414,27 @@ def _sparse_reg_run(D, S, fl, options, starts, weights, nodualerror):
     """the K runs of robustfit_multi on a scipy.sparse D through one SparseRegMulti: the fields
     robustfit_multi returns, plus xsolve, nnz, cg_iters_total and cg_capped_updates (K values each), and dnorm / derr
     when the dual residual is evaluated"""
-    from . import _lib as L
     from .sparse_reg import SparseRegMulti
-    m, n = D.shape
-    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals", "cg_tol",
-                                    "cg_maxit") if k in options}
-    res = {}
-    obj = SparseRegMulti(D, S, [0 if f[0] == "lad" else 1 for f in fl], [f[1] for f in fl], [f[2] for f in fl],
-                         [f[3] for f in fl], [f[4] for f in fl], device=int(options.get("device", 0)))
-    try:
-        if weights is not None:
-            obj.set_weights(weights)
-        summ = obj.run(check_every=int(options.get("check_every", 0)), nodualerror=int(bool(nodualerror)),
-                       z0=starts.get("z0"), u0=starts.get("u0"), **loop)
-        Smax = int(summ["steps"].max())
-        res["xopt"] = obj.fetch(L.SRG_F_XOPT, n)
-        res["zopt"] = obj.fetch(L.SRG_F_ZOPT, m)
-        res["uopt"] = obj.fetch(L.SRG_F_UOPT, m)
-        res["steps"] = summ["steps"]
-        res["pnorm"] = obj.fetch(L.SRG_F_PNORM, Smax)
-        res["perr"] = obj.fetch(L.SRG_F_PERR, Smax)
-        if not nodualerror:
-            res["dnorm"] = obj.fetch(L.SRG_F_DNORM, Smax)
-            res["derr"] = obj.fetch(L.SRG_F_DERR, Smax)
-        if loop.get("objevals", 0):
-            res["objevals"] = obj.fetch(L.SRG_F_OBJEVALS, Smax)
-        res["objopt"] = summ["objopt"]
-        res["runtime"] = summ["runtime"]
-        res["chunk"] = obj.chunk()
-        res["xsolve"] = "cg"
-        res["nnz"] = obj.nnz
-        res["cg_iters_total"] = summ["cg_iters_total"]
-        res["cg_capped_updates"] = summ["cg_capped_updates"]
-    finally:
-        obj.close()
-    return res
+    return _run_and_close(SparseRegMulti(D, S, *_reg_columns(fl), device=int(options.get("device", 0))),
+                          _weights_setter(weights), check_every=int(options.get("check_every", 0)),
+                          nodualerror=int(bool(nodualerror)), z0=starts.get("z0"), u0=starts.get("u0"),
+                          **_pick(options, _LOOP_KEYS + _CG_KEYS))
+
+
+def _reg_columns(fl):
+    """_multi_fits' list as the columns RegMulti / SparseRegMulti take: kinds, a, b, epsilon, delta"""
+    return ([0 if f[0] == "lad" else 1 for f in fl],) + tuple([f[i] for f in fl] for i in (1, 2, 3, 4))
+
+
+def _weights_setter(weights):
+    return None if weights is None else lambda obj: obj.set_weights(weights)
 
 
 def _lad_like_sparse(kind, D, s, options, t0):
     """lad / huberfit on a scipy.sparse D: the K = 1 case of the sparse multi-fit object under the
     reference's default nodualerror = 0, the fit axis dropped from every field; vector histories are not recorded"""
     who = "lad" if kind == "lad" else "huberfit"
-    _sparse_reg_refusals(options, who)
+    _sparse_refusals(options, who, stopcond=True)
     D = _matrix(D, "D", sparse_ok=True)
     s = _colvec(s, "s")
     m, n = D.shape
@@ -406,21 +443,10 @@ def _lad_like_sparse(kind, D, s, options, t0):
     loss = loss_fields({k: options.get(k) for k in LOSS_KEYS}, m, kind) or {}
     a, b = loss.get("slopes", (1.0, 1.0))
     fl = [(kind, a, b, loss.get("epsilon", 0.0), loss.get("delta", 1.0))]
-    starts = {}
-    for key, rows in (("x0", n), ("z0", m), ("u0", m)):  # admm.m:252-254: zeros; x0 is checked and never read
-        if options.get(key) is not None:
-            v = _colvec(options[key], key)
-            if v.size != rows:
-                raise ValueError(f"options.{key} does not have {rows} entries!")
-            starts[key] = np.asfortranarray(v.reshape(rows, 1))
+    starts = _start_columns(options, dict(x0=n, z0=m, u0=m))  # admm.m:252-254: zeros; x0 is checked and never read
     res = _sparse_reg_run(D, np.asfortranarray(s.reshape(m, 1)), fl, options, starts, loss.get("weights"),
                           options.get("nodualerror", 0))
-    for key in ("xopt", "zopt", "uopt") + _SPARSE_REG_HIST:
-        if key in res:
-            res[key] = np.ascontiguousarray(res[key][:, 0])
-    for key in ("steps", "cg_iters_total", "cg_capped_updates"):
-        res[key] = int(res[key][0])
-    res["objopt"] = float(res["objopt"][0])
+    _drop_fit_axis(res, _SPARSE_REG_HIST)
     del res["chunk"]
     res["solverruntime"] = time.perf_counter() - t0
     return res
@@ -521,30 +547,18 @@ def robustfit_multi(D, S, fits, options=None):
     (1e-12 / 200) bound a solve; x0 is checked and never read.  The results carry ``xsolve = 'cg'``, ``nnz``,
     ``cg_iters_total`` and ``cg_capped_updates`` (K values each).  fast, convtest, relax, adaptive, an xsolve other than
     'auto' / 'cg', comm, parallel and a stopcond other than 'standard' are refused by name."""
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Argument options is not a struct!")
-    options = dict(options)
+    options = _options(options, "Argument options is not a struct!", optional=True)
     t0 = time.perf_counter()
     from ._lib import is_sparse
     sparse = is_sparse(D)  # DESIGN.md q38: the matrix-free object, no limit on n
     if sparse:
-        _sparse_reg_refusals(options, "robustfit_multi")
+        _sparse_refusals(options, "robustfit_multi", stopcond=True)
     D = _matrix(D, "D", sparse_ok=sparse)
     m, n = D.shape
-    S = np.asarray(S, dtype=np.float64)
-    if S.ndim == 1:
-        S = S.reshape(-1, 1)
-    if S.ndim != 2:
-        raise ValueError("Argument S is neither a vector nor a matrix!")
-    if S.shape[0] != m:
-        raise ValueError("The number of rows in argument D do not match size of S!")
+    S = _response_matrix(S, m)
     fl = _multi_fits(fits, m)
     K = len(fl)
-    if S.shape[1] not in (1, K):
-        raise ValueError(f"S has {S.shape[1]} columns for {K} fits: one shared response or one column per fit")
-    S = np.asfortranarray(S)
+    S = _response_columns(S, K)
     lw = loss_fields(dict(weights=options.pop("weights", None)), m, "lad")
     weights = None if lw is None else lw["weights"]
     for key in ("fast", "convtest"):
@@ -554,15 +568,8 @@ def robustfit_multi(D, S, fits, options=None):
         raise ValueError("options.relax is not available in robustfit_multi: call lad / huberfit per fit")
     if options.get("stopcond", "standard") != "standard":
         raise ValueError("options.stopcond: robustfit_multi stops on the primal residual alone ('standard')")
-    starts = {}
-    for key, rows in (("x0", n), ("z0", m), ("u0", m)):
-        if options.get(key) is not None:
-            v = np.asarray(options[key], dtype=np.float64)
-            if v.shape != (rows, K):
-                raise ValueError(f"options.{key} is not a {rows} x {K} matrix (one column per fit)!")
-            starts[key] = np.asfortranarray(v)
-    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "maxiters", "domaxiters", "objevals") if k in options}
-    res = {}
+    starts = _start_matrices(options, dict(x0=n, z0=m, u0=m), K, "fit")
+    loop = _pick(options, _LOOP_KEYS)
     if sparse:
         res = _sparse_reg_run(D, S, fl, options, starts, weights, options.get("nodualerror", 1))
         res["solverruntime"] = time.perf_counter() - t0
@@ -578,47 +585,13 @@ def robustfit_multi(D, S, fits, options=None):
             if weights is not None:
                 o["weights"] = weights
             per.append(_lad_like(kind, D, S[:, k if S.shape[1] > 1 else 0], o))
-        steps = np.array([r["steps"] for r in per], dtype=np.int64)
-        Smax = int(steps.max())
-        for key in ("xopt", "zopt", "uopt"):
-            res[key] = np.asfortranarray(np.stack([np.asarray(r[key]).reshape(-1) for r in per], axis=1))
-        for key in _MULTI_HIST:
-            if all(key in r for r in per):
-                h = np.full((Smax, K), np.nan, order="F")
-                for c, r in enumerate(per):
-                    h[:steps[c], c] = np.asarray(r[key])[:steps[c]]
-                res[key] = h
-        res["steps"] = steps
-        res["objopt"] = np.array([r.get("objopt", np.nan) for r in per], dtype=np.float64)
-        res["runtime"] = float(sum(r["runtime"] for r in per))
-        res["chunk"] = 1
-        res["fallback"] = True
-        res["solverruntime"] = time.perf_counter() - t0
+        res = _stack_fits(per, _MULTI_HIST)
+        res.update(chunk=1, fallback=True, solverruntime=time.perf_counter() - t0)
         return res
-    from . import _lib as L
     from .reg_multi import RegMulti
-    obj = RegMulti(D, S, [0 if f[0] == "lad" else 1 for f in fl], [f[1] for f in fl], [f[2] for f in fl],
-                   [f[3] for f in fl], [f[4] for f in fl], device=int(options.get("device", 0)))
-    try:
-        if weights is not None:
-            obj.set_weights(weights)
-        summ = obj.run(check_every=int(options.get("check_every", 0)), **starts, **loop)
-        Smax = int(summ["steps"].max())
-        res["xopt"] = obj.fetch(L.REGM_F_XOPT, n)
-        res["zopt"] = obj.fetch(L.REGM_F_ZOPT, m)
-        res["uopt"] = obj.fetch(L.REGM_F_UOPT, m)
-        res["steps"] = summ["steps"]
-        res["pnorm"] = obj.fetch(L.REGM_F_PNORM, Smax)
-        res["perr"] = obj.fetch(L.REGM_F_PERR, Smax)
-        if loop.get("objevals", 0):
-            res["objevals"] = obj.fetch(L.REGM_F_OBJEVALS, Smax)
-        res["objopt"] = summ["objopt"]
-        res["runtime"] = summ["runtime"]
-        res["chunk"] = obj.chunk()
-        res["fallback"] = False
-    finally:
-        obj.close()
-    res["solverruntime"] = time.perf_counter() - t0
+    res = _run_and_close(RegMulti(D, S, *_reg_columns(fl), device=int(options.get("device", 0))),
+                         _weights_setter(weights), check_every=int(options.get("check_every", 0)), **starts, **loop)
+    res.update(fallback=False, solverruntime=time.perf_counter() - t0)
     return res
 
 
@@ -626,10 +599,7 @@ def quantilereg_multi(D, s, taus, options=None):
     """results = quantilereg_multi(D, s, taus, options): the quantiles ``taus`` (each strictly inside (0, 1)) of one
     response s in one run over D -- robustfit_multi with the pinball loss of quantilereg() per fit and one shared s.
     Column k of xopt / zopt / uopt belongs to taus[k]; ``results['taus']`` repeats them."""
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Argument options is not a struct!")
+    options = _options(options, "Argument options is not a struct!", optional=True)
     taus = np.atleast_1d(np.asarray(taus, dtype=np.float64)).reshape(-1)
     if taus.size < 1:
         raise ValueError("taus must hold at least one quantile")
@@ -707,9 +677,7 @@ def linearsvm(D, ell, C, options=None):
 
     A ``scipy.sparse`` D runs the K = 1 case of ``linearsvm_ovr``'s sparse object: the same fields with
     the class axis dropped, no vector histories, and the same refused options."""
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!")
     t0 = time.perf_counter()
     if not np.isscalar(C) or np.real(C) < 0:  # linearsvm.m:270-274
         raise ValueError("Given regularization parameter C is not a nonnegative number!")
@@ -741,30 +709,19 @@ def linearsvm(D, ell, C, options=None):
 def _linearsvm_sparse(D, ell, C, options, t0):
     """linearsvm on a scipy.sparse D: the K = 1 case of the sparse one-vs-rest object, the class axis
     dropped from every field; vector histories are not recorded"""
-    _sparse_svm_refusals(options, "linearsvm")
+    _sparse_refusals(options, "linearsvm", also=("Dplus",))
     m, n = D.shape
     loss = options.get("lossfunction", "hinge")
     if not isinstance(loss, str):
         raise ValueError("options.lossfunction is not a string!")
     cost = svm_cost_fields({k: options.get(k) for k in SVM_COST_KEYS}, ell)
-    rng = np.random.default_rng()
-    starts = {}
-    for key, rows in (("x0", n), ("z0", m), ("u0", m)):  # unwrappedadmm.m:87-89
-        v = _colvec(options[key], key) if key in options else rng.random(rows)
-        if v.size != rows:
-            raise ValueError(f"options.{key} does not have {rows} entries!")
-        starts[key] = np.asfortranarray(v.reshape(rows, 1))
+    starts = _start_columns(options, dict(x0=n, z0=m, u0=m), np.random.default_rng().random)  # unwrappedadmm.m:87-89
     weights = class_cost = None
     if cost is not None:
         weights = cost.get("weights")
         class_cost = np.array([cost.get("classcost", (1.0, 1.0))], dtype=np.float64)
     res = _sparse_svm_run(D, np.asfortranarray(ell.reshape(m, 1)), C, [loss], options, starts, weights, class_cost)
-    for key in ("xopt", "zopt", "uopt") + _OVR_HIST:
-        if key in res:
-            res[key] = np.ascontiguousarray(res[key][:, 0])
-    for key in ("steps", "cg_iters_total", "cg_capped_updates"):
-        res[key] = int(res[key][0])
-    res["objopt"] = float(res["objopt"][0])
+    _drop_fit_axis(res, _OVR_HIST)
     res["solverruntime"] = time.perf_counter() - t0
     return res
 
@@ -798,58 +755,25 @@ def _ovr_costs(options, ELL):
 _OVR_HIST = ("pnorm", "perr", "Hnormsq", "objevals")
 
 
-def _sparse_svm_refusals(options, who):
-    """the options the sparse one-vs-rest object does not run, each named in its ValueError"""
-    for key in ("fast", "convtest", "adaptive"):
-        if options.get(key, 0):
-            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
-    if options.get("relax", 1) != 1:
-        raise ValueError(f"options.relax is not available in {who} on a sparse D")
-    xs = options.get("xsolve", "auto")
-    if not (isinstance(xs, str) and xs.lower() in ("auto", "cg")):
-        raise ValueError(f"options.xsolve = {xs!r}: {who} on a sparse D runs the matrix-free x-update ('auto' or 'cg')")
-    for key in ("Dplus", "comm"):
-        if options.get(key) is not None:
-            raise ValueError(f"options.{key} is not available in {who} on a sparse D")
-    if options.get("parallel", "none") not in ("none", 0, None):
-        raise ValueError(f"options.parallel is not available in {who} on a sparse D")
+def _ovr_loop(options):
+    """the loop options of the one-vs-rest pair; maxiters is unwrappedadmm's 1000"""
+    loop = _pick(options, ("rho", "abstol", "reltol", "domaxiters", "objevals"))
+    if "Hreltol" in options or "Hnormtol" in options:  # admm.m:927-928 (q2): either spelling
+        loop["Hnormtol"] = options.get("Hreltol", options.get("Hnormtol"))
+    return loop
+
+
+def _cost_setter(weights, class_cost):
+    return None if weights is None and class_cost is None else lambda obj: obj.set_cost(weights, class_cost)
 
 
 def _sparse_svm_run(D, ELL, C, losses, options, starts, weights, class_cost):
     """the K runs of linearsvm_ovr on a scipy.sparse D through one SparseSvmOvr: the fields
     linearsvm_ovr returns, plus xsolve, nnz, cg_iters_total and cg_capped_updates (K values each)"""
-    from . import _lib as L
     from .sparse_svm import SparseSvmOvr
-    m, n = D.shape
-    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "domaxiters", "objevals", "cg_tol", "cg_maxit")
-            if k in options}
-    if "Hreltol" in options or "Hnormtol" in options:  # admm.m:927-928 (q2): either spelling
-        loop["Hnormtol"] = options.get("Hreltol", options.get("Hnormtol"))
-    res = {}
-    obj = SparseSvmOvr(D, ELL, C, losses, device=int(options.get("device", 0)))
-    try:
-        if weights is not None or class_cost is not None:
-            obj.set_cost(weights, class_cost)
-        summ = obj.run(check_every=int(options.get("check_every", 0)), z0=starts["z0"], u0=starts["u0"], **loop)
-        S = int(summ["steps"].max())
-        res["xopt"] = obj.fetch(L.OVR_F_XOPT, n)
-        res["zopt"] = obj.fetch(L.OVR_F_ZOPT, m)
-        res["uopt"] = obj.fetch(L.OVR_F_UOPT, m)
-        res["steps"] = summ["steps"]
-        res["pnorm"] = obj.fetch(L.OVR_F_PNORM, S)
-        res["perr"] = obj.fetch(L.OVR_F_PERR, S)
-        res["Hnormsq"] = obj.fetch(L.OVR_F_HNORMSQ, S)
-        if loop.get("objevals", 0):
-            res["objevals"] = obj.fetch(L.OVR_F_OBJEVALS, S)
-        res["objopt"] = summ["objopt"]
-        res["runtime"] = summ["runtime"]
-        res["xsolve"] = "cg"
-        res["nnz"] = obj.nnz
-        res["cg_iters_total"] = summ["cg_iters_total"]
-        res["cg_capped_updates"] = summ["cg_capped_updates"]
-    finally:
-        obj.close()
-    return res
+    return _run_and_close(SparseSvmOvr(D, ELL, C, losses, device=int(options.get("device", 0))),
+                          _cost_setter(weights, class_cost), check_every=int(options.get("check_every", 0)),
+                          z0=starts["z0"], u0=starts["u0"], **_ovr_loop(options), **_pick(options, _CG_KEYS))
 
 
 def linearsvm_ovr(D, labels, C, options=None):
@@ -875,11 +799,7 @@ def linearsvm_ovr(D, labels, C, options=None):
     each).  ``fast``, ``convtest``, ``relax`` != 1, ``adaptive``, ``xsolve`` other than auto / cg, ``Dplus``, ``comm`` and
     ``parallel`` raise ValueError.
     """
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!", optional=True)
     t0 = time.perf_counter()
     if not np.isscalar(C) or np.real(C) < 0:  # linearsvm.m:270-274
         raise ValueError("Given regularization parameter C is not a nonnegative number!")
@@ -893,7 +813,7 @@ def linearsvm_ovr(D, labels, C, options=None):
         raise ValueError("Product ell*D is not possible; sizes incompatible!")  # linearsvm.m:283-286
     _single_column_quirk(D)
     if sparse:
-        _sparse_svm_refusals(options, "linearsvm_ovr")
+        _sparse_refusals(options, "linearsvm_ovr", also=("Dplus",))
     classes = np.asarray(options["classes"] if "classes" in options else np.unique(labels), dtype=np.float64)
     if classes.ndim != 1 or classes.size < 1:
         raise ValueError("options.classes is not a non-empty vector of class ids!")
@@ -902,16 +822,8 @@ def linearsvm_ovr(D, labels, C, options=None):
     losses = [loss] * K if isinstance(loss, str) else list(loss)
     if len(losses) != K or not all(isinstance(v, str) for v in losses):
         raise ValueError("options.lossfunction is neither one string nor a list with one string per class!")
-    starts = {}
-    rng = np.random.default_rng()
-    for key, rows in (("x0", n), ("z0", m), ("u0", m)):  # unwrappedadmm.m:87-89, per class
-        if key in options:
-            v = np.asarray(options[key], dtype=np.float64)
-            if v.shape != (rows, K):
-                raise ValueError(f"options.{key} is not a {rows} x {K} matrix (one column per class)!")
-        else:
-            v = rng.random((rows, K))
-        starts[key] = np.asfortranarray(v)
+    starts = _start_matrices(options, dict(x0=n, z0=m, u0=m), K, "class",  # unwrappedadmm.m:87-89, per class
+                             np.random.default_rng().random)
     for key in ("fast", "convtest"):
         if options.get(key, 0):
             raise ValueError(f"options.{key} is not available in linearsvm_ovr: call linearsvm per class")
@@ -919,9 +831,7 @@ def linearsvm_ovr(D, labels, C, options=None):
         raise ValueError("options.relax is not available in linearsvm_ovr: call linearsvm per class")
     ELL = ovr_label_matrix(labels, classes)
     weights, class_cost = _ovr_costs(options, ELL)
-    loop = {k: options[k] for k in ("rho", "abstol", "reltol", "domaxiters", "objevals") if k in options}
-    if "Hreltol" in options or "Hnormtol" in options:  # admm.m:927-928 (q2): either spelling
-        loop["Hnormtol"] = options.get("Hreltol", options.get("Hnormtol"))
+    loop = _ovr_loop(options)
     res = dict(classes=classes)
     if sparse:
         res.update(_sparse_svm_run(D, ELL, C, losses, options, starts, weights, class_cost))
@@ -937,43 +847,12 @@ def linearsvm_ovr(D, labels, C, options=None):
             if class_cost is not None:
                 o["classcost"] = tuple(class_cost[c])
             per.append(linearsvm(D, ELL[:, c], C, o))
-        steps = np.array([r["steps"] for r in per], dtype=np.int64)
-        S = int(steps.max())
-        for key in ("xopt", "zopt", "uopt"):
-            res[key] = np.asfortranarray(np.stack([r[key] for r in per], axis=1))
-        for key in _OVR_HIST:
-            if all(key in r for r in per):
-                h = np.full((S, K), np.nan, order="F")
-                for c, r in enumerate(per):
-                    h[:steps[c], c] = np.asarray(r[key])[:steps[c]]
-                res[key] = h
-        res["steps"] = steps
-        res["objopt"] = np.array([r.get("objopt", np.nan) for r in per], dtype=np.float64)
-        res["runtime"] = float(sum(r["runtime"] for r in per))
-        res["solverruntime"] = time.perf_counter() - t0
+        res.update(_stack_fits(per, _OVR_HIST), solverruntime=time.perf_counter() - t0)
         return res
-    from . import _lib as L
     from .engine import SvmOvr
-    obj = SvmOvr(D, ELL, C, losses, Dplus=options.get("Dplus"), device=int(options.get("device", 0)))
-    try:
-        if weights is not None or class_cost is not None:
-            obj.set_cost(weights, class_cost)
-        summ = obj.run(check_every=int(options.get("check_every", 0)), x0=starts["x0"], z0=starts["z0"],
-                       u0=starts["u0"], **loop)
-        S = int(summ["steps"].max())
-        res["xopt"] = obj.fetch(L.OVR_F_XOPT, n)
-        res["zopt"] = obj.fetch(L.OVR_F_ZOPT, m)
-        res["uopt"] = obj.fetch(L.OVR_F_UOPT, m)
-        res["steps"] = summ["steps"]
-        res["pnorm"] = obj.fetch(L.OVR_F_PNORM, S)
-        res["perr"] = obj.fetch(L.OVR_F_PERR, S)
-        res["Hnormsq"] = obj.fetch(L.OVR_F_HNORMSQ, S)
-        if loop.get("objevals", 0):
-            res["objevals"] = obj.fetch(L.OVR_F_OBJEVALS, S)
-        res["objopt"] = summ["objopt"]
-        res["runtime"] = summ["runtime"]
-    finally:
-        obj.close()
+    res.update(_run_and_close(SvmOvr(D, ELL, C, losses, Dplus=options.get("Dplus"), device=int(options.get("device", 0))),
+                              _cost_setter(weights, class_cost), check_every=int(options.get("check_every", 0)),
+                              **starts, **loop))
     res["solverruntime"] = time.perf_counter() - t0
     return res
 
@@ -985,9 +864,7 @@ def quadraticprogram(P, q, r, cons1, cons2, options=None):
     (either order, quadraticprogram.m:321-329) for D*x = s, x >= 0.  ``options['altproxg']`` (a handle on
     device tensors) replaces the z-prox as in quadraticprogram.m:221-227.
     """
-    if not isinstance(options, dict):
-        raise TypeError("Argument options is not a struct!")
-    options = dict(options)
+    options = _options(options, "Argument options is not a struct!")
     t0 = time.perf_counter()
     P = _matrix(P, "P")
     if P.shape[0] != P.shape[1]:
@@ -1049,11 +926,7 @@ def linearprogram(b, D, s, options=None):
     every x-update (getProxOps.m:1363); here it is reduced once on the host to x = K*y + k0 and the
     per-iteration n x n GEMV, the pos() prox, the u-update and the residuals run on the device.
     """
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!", optional=True)
     t0 = time.perf_counter()
     D = _matrix(D, "D")
     b = _colvec(b, "b")
@@ -1082,9 +955,7 @@ def basispursuit(D, s, options=None):
     engine on the device (MFMA GEMMs + Cholesky + explicit m x m inverse); the per-iteration n x n GEMV and the
     shrinkage run on the device.
     """
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!")
     t0 = time.perf_counter()
     D = _matrix(D, "D")
     s = _colvec(s, "s")
@@ -1113,9 +984,7 @@ def totalvariation(s, lam, options=None):
     """
     import scipy.sparse as sp
 
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!")
     t0 = time.perf_counter()
     if not np.isscalar(lam) or np.real(lam) < 0:  # totalvariation.m:190-194
         raise ValueError("Given lambda parameter is not a nonnegative number!")
@@ -1158,11 +1027,7 @@ def totalvariation2d(S, lam, options=None):
     stage the run took: 'green', 'coop', 'dct', 'thomas', or 'cg' without a spectral x-update.  ``xopt`` is returned as
     an image.
     """
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!", optional=True)
     t0 = time.perf_counter()
     if not np.isscalar(lam) or np.real(lam) < 0:
         raise ValueError("Given lambda parameter is not a nonnegative number!")
@@ -1199,11 +1064,7 @@ def model(P, Q, r, s, options=None):
     matrices themselves travel along (engine-side extension) so that the device can evaluate the
     objective of model.m:133-134 when ``objevals`` is set.
     """
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!", optional=True)
     t0 = time.perf_counter()
     P = _matrix(P, "P")
     Q = _matrix(Q, "Q")
@@ -1236,11 +1097,7 @@ def covarianceselection(D, lam, options=None):
     runs on the n^2 entries of X, Z, U with A = 1, B = -1, c = 0 and the eigen-step x-update of getProxOps.m:1487-1495.
     xopt, zopt, uopt (and x0, z0, u0) come back as n x n matrices; histories keep their n^2-row shape.
     """
-    if options is None:
-        options = {}
-    if not isinstance(options, dict):
-        raise TypeError("Given options is not a struct! At least pass empty struct!")
-    options = dict(options)
+    options = _options(options, "Given options is not a struct! At least pass empty struct!", optional=True)
     t0 = time.perf_counter()
     D = _matrix(D, "D")
     lam = is_positive_real(lam, "lambda")

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _MultiOwner, _f64, _weights
+from .engine import _MultiOwner, _weights
 
 
 class SparseLassoMulti(_MultiOwner):
@@ -18,23 +18,19 @@ class SparseLassoMulti(_MultiOwner):
     ``lams`` holds the K values lambda_k >= 0; ``ridge`` (mu_k >= 0) and ``nonnegative`` (0 | 1) K values each, or None
     for 0; ``l1weights`` n values w_i >= 0 shared by all fits, or None for 1."""
 
-    _abi, _unit = "admm_sparse_lasso", "fit"
+    _abi, _unit, _cg = "admm_sparse_lasso", "fit", True
+    _types = (L.SparseLassoDesc, L.SparseLassoOptions, L.SparseLassoSummary)
+    _rows = dict(x0="n", z0="n", u0="n")  # z and u live on the coefficients
+    _fields = dict(xopt=(L.SLM_F_XOPT, "n"), zopt=(L.SLM_F_ZOPT, "n"), uopt=(L.SLM_F_UOPT, "n"),
+                   pnorm=(L.SLM_F_PNORM, "hist"), perr=(L.SLM_F_PERR, "hist"), dnorm=(L.SLM_F_DNORM, "dual"),
+                   derr=(L.SLM_F_DERR, "dual"), objevals=(L.SLM_F_OBJEVALS, "objevals"))
 
     def __init__(self, D, S, lams, ridge=None, nonnegative=None, l1weights=None, *, device=0):
-        self._h = None
-        self._lib = L.load()
-        L.require_device()
+        d = self._desc()
         keep = []
-        sd = L.sparse_desc(D, keep)
-        S = np.asarray(S, dtype=np.float64)
-        S = _f64(S.reshape(-1, 1) if S.ndim == 1 else S)
-        self.m, self.n, self.nnz = int(sd.rows), int(sd.cols), int(sd.nnz)
-        if S.ndim != 2 or S.shape[0] != self.m:
-            raise ValueError("The number of rows in argument D do not match size of S!")
+        sd, S = self._sparse_D(D, S, keep, "The number of rows in argument D do not match size of S!")
         lam = np.ascontiguousarray(np.asarray(lams, dtype=np.float64).reshape(-1))
         self.K = int(lam.size)
-        d = L.SparseLassoDesc()
-        self._lib.admm_sparse_lasso_desc_default(C.byref(d))
         d.K, d.D, d.S, d.ns = self.K, C.pointer(sd), L.as_dp(S), int(S.shape[1])
         d.lam = L.as_dp(lam)
         d.device = int(device)
@@ -51,43 +47,15 @@ class SparseLassoMulti(_MultiOwner):
         w = _weights(l1weights, self.n, "coefficients", "l1weights")
         if w is not None:
             d.weights = L.as_dp(w)
-        h = C.c_void_p()
-        L.check(self._lib.admm_sparse_lasso_create(C.byref(d), C.byref(h)))
-        self._h = h
-        self.objevals = False
+        self._create(d)
         self.dual = True
-
-    @staticmethod
-    def chunk():
-        """fits one sparse product serves"""
-        return int(L.load().admm_sparse_lasso_chunk())
 
     def set_weights(self, l1weights=None):
         """n l1 weights >= 0 shared by all fits (admm_sparse_lasso_set_weights); None restores 1"""
         w = _weights(l1weights, self.n, "coefficients", "l1weights")
         L.check(self._lib.admm_sparse_lasso_set_weights(self._h, None if w is None else L.as_dp(w)))
 
-    def run(self, *, rho=1.0, maxiters=1000, abstol=1e-5, reltol=1e-3, relax=1.0, fast=L.FAST_OFF, convtest=0,
-            domaxiters=0, objevals=0, check_every=0, cg_tol=0.0, cg_maxit=0, nodualerror=0, z0=None, u0=None):
-        o = L.SparseLassoOptions()
-        self._lib.admm_sparse_lasso_options_default(C.byref(o))
-        o.maxiters, o.rho, o.abstol, o.reltol = int(maxiters), float(rho), float(abstol), float(reltol)
-        o.relax, o.fast, o.convtest = float(relax), int(fast), int(bool(convtest))
-        o.domaxiters, o.objevals, o.check_every = int(bool(domaxiters)), int(bool(objevals)), int(check_every)
-        o.cg_tol, o.cg_maxit = float(cg_tol), int(cg_maxit)  # (<= 0: the defaults 1e-12, 200)
-        o.nodualerror = int(bool(nodualerror))
-        keep = []  # (alive until the run returns)
-        for name, v in (("z0", z0), ("u0", u0)):  # z and u live on the coefficients: n x K
-            if v is None:
-                continue
-            v = _f64(v)
-            if v.shape != (self.n, self.K):
-                raise ValueError(f"{name} is not a {self.n} x {self.K} matrix (one column per {self._unit})")
-            keep.append(v)
-            setattr(o, name, L.as_dp(v))
-        summ = (L.SparseLassoSummary * self.K)()
-        rt = C.c_double(0)
-        L.check(self._lib.admm_sparse_lasso_run(self._h, C.byref(o), summ, C.byref(rt)))
-        self.objevals = bool(objevals)
-        self.dual = not bool(nodualerror)
-        return self._summary(summ, rt, cg=True)
+    def run(self, *, cg_tol=0.0, cg_maxit=0, nodualerror=0, z0=None, u0=None, **loop):
+        """``loop``: rho, maxiters, abstol, reltol, relax, fast, convtest, domaxiters, objevals, check_every;
+        cg_tol / cg_maxit <= 0: the defaults 1e-12, 200"""
+        return self._run(loop, dict(z0=z0, u0=u0), cg_tol=cg_tol, cg_maxit=cg_maxit, nodualerror=nodualerror)
