@@ -295,6 +295,28 @@ class SparseLassoSummary(C.Structure):  # admm_sparse_lasso_summary
  SLM_F_DERR) = range(1, 9)
 
 
+class LassoMultiDesc(C.Structure):  # admm_lasso_multi_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("m", C.c_int64), ("n", C.c_int64), ("D", _dp),
+                ("ldD", C.c_int64), ("S", _dp), ("ns", C.c_int32), ("device", C.c_int32), ("rho", C.c_double),
+                ("xsolve", C.c_int32), ("reserved0", C.c_int32), ("lam", _dp), ("ridge", _dp),
+                ("nonneg", C.POINTER(C.c_int32)), ("weights", _dp), ("comm", C.c_void_p)]
+
+
+class LassoMultiOptions(C.Structure):  # admm_lasso_multi_options
+    _fields_ = [("struct_size", C.c_int32), ("maxiters", C.c_int32), ("rho", C.c_double), ("abstol", C.c_double),
+                ("reltol", C.c_double), ("relax", C.c_double), ("fast", C.c_int32), ("convtest", C.c_int32),
+                ("domaxiters", C.c_int32), ("objevals", C.c_int32), ("check_every", C.c_int32),
+                ("nodualerror", C.c_int32), ("x0", _dp), ("z0", _dp), ("u0", _dp)]
+
+
+class LassoMultiSummary(C.Structure):  # admm_lasso_multi_summary
+    _fields_ = [("steps", C.c_int32), ("stopped_early", C.c_int32), ("objopt", C.c_double), ("xsolve", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+(LM_F_XOPT, LM_F_ZOPT, LM_F_UOPT, LM_F_PNORM, LM_F_PERR, LM_F_OBJEVALS, LM_F_DNORM, LM_F_DERR) = range(1, 9)
+
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
@@ -446,6 +468,18 @@ _SIGNATURES = {
     "admm_sparse_lasso_set_weights": (C.c_int, [C.c_void_p, _dp]),
     "admm_sparse_lasso_chunk": (C.c_int, []),
     "admm_sparse_lasso_destroy": (None, [C.c_void_p]),
+    "admm_lasso_multi_desc_default": (None, [C.POINTER(LassoMultiDesc)]),
+    "admm_lasso_multi_options_default": (None, [C.POINTER(LassoMultiOptions)]),
+    "admm_lasso_multi_create": (C.c_int, [C.POINTER(LassoMultiDesc), C.POINTER(C.c_void_p)]),
+    "admm_lasso_multi_run": (C.c_int, [C.c_void_p, C.POINTER(LassoMultiOptions), C.POINTER(LassoMultiSummary),
+                                       C.POINTER(C.c_double)]),
+    "admm_lasso_multi_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_lasso_multi_set_weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_lasso_multi_chunk": (C.c_int, []),
+    "admm_lasso_multi_product_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int64)]),
+    "admm_lasso_multi_destroy": (None, [C.c_void_p]),
+    "admm_op_symm_packed": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.POINTER(C.c_int32), _dp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

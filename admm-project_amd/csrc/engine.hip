@@ -375,7 +375,7 @@ bool symv_compact_accept(double err_compact, double err_fp64, double diff) {
 // row-sharded split x-solve keep fp64.
 static int choose_symv_storage(admm_engine* e, SliceFactor& f) {
   if (f.mode != ADMM_XSOLVE_INVERSE || !f.Minv || !f.F || f.pinv || !f.planSy.packed || f.planSy.compact ||
-      f.n < kSymvHalfMin || e->sy_split)
+      f.n < kSymvHalfMin || e->sy_split || e->keep_fp64)
     return ADMM_OK;
   if (!stream_hint(symv_tile_prefix_bytes(f.planSy, symv_tiles(f.planSy)))) return ADMM_OK;
   SymvPlan cp = f.planSy;

@@ -823,9 +823,11 @@ static int setup_common(admm_engine* e) {
 }
 
 // sparse: null, or the checked matrix of admm_engine_create_sparse in HOST arrays
-static int create_engine(const admm_problem_desc* desc, const admm_sparse_desc* sparse, admm_engine** out) {
+static int create_engine(const admm_problem_desc* desc, const admm_sparse_desc* sparse, admm_engine** out,
+                         bool keep_fp64 = false) {
   const auto t0 = std::chrono::steady_clock::now();
   admm_engine* e = new admm_engine();
+  e->keep_fp64 = keep_fp64;
   CreateCtx cx{};
   cx.sparse = sparse;
   int rc = check_options(e, desc, &cx);
@@ -857,6 +859,11 @@ static int check_device(const admm_problem_desc* desc, admm_engine** out) {
 extern "C" int admm_engine_create(const admm_problem_desc* desc, admm_engine** out) {
   ADMM_TRY(check_device(desc, out));
   return create_engine(desc, nullptr, out);
+}
+
+int admm::engine_create_keep_fp64(const admm_problem_desc* desc, admm_engine** out) {
+  ADMM_TRY(check_device(desc, out));
+  return create_engine(desc, nullptr, out, true);
 }
 
 extern "C" int admm_engine_create_sparse(const admm_problem_desc* desc, const admm_sparse_desc* D, admm_engine** out) {

@@ -119,6 +119,7 @@ struct admm_engine {
   double *syN = nullptr, *syT = nullptr;  // partial-sum buffers of the lower-triangle kernel (shared by all factors)
   size_t sy_elems = 0;
   bool sy_split = false;  // multi-GPU: split the tiles of the x-solve over the ranks (decided by measurement at create)
+  bool keep_fp64 = false;  // choose_symv_storage leaves the fp64 packed inverse in place (engine_create_keep_fp64)
   double *partDN = nullptr, *partDT = nullptr, *partSq = nullptr;
 
   // iterates
@@ -303,6 +304,9 @@ int build_slice_factor(admm_engine* e, SliceFactor& f, double* W, int64_t n, int
 int factorize_pinv(admm_engine* e, double* W, int64_t n, int64_t ld);
 void apply_slice_factor(admm_engine* e, const SliceFactor& f, const double* y, double* out);
 void release_slice_factor(admm_engine* e, SliceFactor& f);
+// admm_engine_create for an owner that multiplies with the fp64 tile-packed inverse itself (lasso_multi.hip): the same
+// engine, except that the compact storage is never adopted in its place
+int engine_create_keep_fp64(const admm_problem_desc* desc, admm_engine** out);
 // engine.hip, for create: pinv(D) of the two-launch unwrapped iteration; the maps x = P*v + q of basis pursuit and
 // x = K*y + k0 of LP / standard-form QP from D (m x n, ldD) and s on the device
 int build_unwrapped_pinv(admm_engine* e, const double* Dp_given);

@@ -86,6 +86,16 @@ void launch_symv_lower(const SymvPlan& p, const double* M, int64_t ld, const dou
                        double* y, const Ctrl* ctrl, hipStream_t stream, int part_rank = 0, int part_count = 1,
                        bool reduce = true);
 
+// ---------------------------------------------------------------- symmetric M x a chunk of vectors (symm.hip)
+// X(:, k) = M * Y(:, k) for every running fit k < K: M the fp64 tile-packed lower triangle of a packed plan (never the
+// compact storage), X and Y multi-vectors of n rows in spmm.h's layout [chunks][n][kSpmmChunk], part the partial rows
+// (symm_part_elems doubles; nothing in it has to be initialised).  rec: K records, or null when every fit runs; a fit
+// whose stop word is set keeps its column of X, and a chunk without a running fit reads nothing.  One form for every n.
+struct MultiRec;
+size_t symm_part_elems(const SymvPlan& p, int32_t K);
+void launch_symm_packed(const SymvPlan& p, const double* P, const double* Y, double* X, double* part,
+                        const MultiRec* rec, int32_t K, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense setup (dense.hip)
 // C = alpha*op(A)*op(B) + beta*C, column-major fp64 on the MFMA f64 path.  transA/transB: 0 = N, 1 = T.
 // lower_only: compute only tiles that touch the lower triangle (SYRK-style symmetric results).

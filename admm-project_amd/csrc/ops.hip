@@ -9,6 +9,8 @@
 #include "engine_internal.h"
 #include "kernels.h"
 #include "loop_kernels.h"
+#include "multi_device.h"
+#include "spmm.h"
 #include "tv2d.h"
 
 using namespace admm;
@@ -450,6 +452,41 @@ int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32
     if (r > 0)
       for (int64_t i = 0; i < n; ++i) y[i] += part[i];  // the ranks' partial results, in rank order
   }
+  return ADMM_OK;
+}
+
+int admm_op_symm_packed(const double* M, int64_t n, int64_t ldM, double* X, int32_t K, const int32_t* stop_mask,
+                        const double* Y) {
+  if (!M || !X || !Y || n <= 0 || ldM < n || K < 1)
+    return fail(ADMM_E_INVALID, "symm_packed: bad argument (n >= 1, ldM >= n, K >= 1)");
+  ADMM_TRY(need_device());
+  Scratch sc;
+  SymvPlan plan = symv_plan(n);
+  double *dM, *dP, *dX, *dY, *part;
+  ADMM_TRY(sc.alloc(&dM, static_cast<size_t>(plan.npad) * plan.npad));
+  ADMM_HIP_TRY(hipMemset(dM, 0, sizeof(double) * plan.npad * plan.npad));
+  ADMM_TRY(put_padded(dM, plan.npad, M, n, ldM));
+  ADMM_TRY(sc.alloc(&dP, symv_packed_elems(plan)));
+  launch_symv_pack(plan, dM, plan.npad, dP, nullptr);
+  plan.packed = true;
+  const size_t elems = static_cast<size_t>(spmm_chunks(K)) * kSpmmChunk * n;
+  std::vector<double> hb(elems);
+  spmm_pack(Y, n, n, K, hb.data());
+  ADMM_TRY(sc.put(&dY, static_cast<const double*>(hb.data()), elems));
+  spmm_pack(X, n, n, K, hb.data());
+  ADMM_TRY(sc.put(&dX, static_cast<const double*>(hb.data()), elems));
+  // every partial slot the sum reads is written by a tile: the slots start as NaN, so a missed one shows
+  ADMM_TRY(sc.alloc(&part, symm_part_elems(plan, K)));
+  ADMM_HIP_TRY(hipMemset(part, 0xFF, sizeof(double) * symm_part_elems(plan, K)));
+  MultiRec* rec = nullptr;
+  if (stop_mask) {
+    std::vector<MultiRec> rh(static_cast<size_t>(K), MultiRec{0, 0, 0, 0});
+    for (int32_t k = 0; k < K; ++k) rh[k].stop = stop_mask[k] != 0;
+    ADMM_TRY(sc.put(&rec, static_cast<const MultiRec*>(rh.data()), rh.size()));
+  }
+  launch_symm_packed(plan, dP, dY, dX, part, rec, K, nullptr);
+  ADMM_TRY(fetch(hb.data(), dX, elems));
+  spmm_unpack(hb.data(), n, K, X, n);
   return ADMM_OK;
 }
 

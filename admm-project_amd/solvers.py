@@ -299,13 +299,53 @@ def _lambda_max(D, S, w):
     return g.max(axis=0) if g.size else np.zeros(S.shape[1] if S.ndim == 2 else 1)
 
 
+def _multi_lasso_fits(D, S, lams, options):
+    """what lasso_multi and lasso_multi_dense check alike: (S as m x ns, lambda, ridge, nonneg, l1weights, starts)"""
+    m, n = D.shape
+    S = _response_matrix(S, m)
+    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
+    K = int(lam.size)
+    if K < 1:
+        raise ValueError("lams must hold at least one lambda")
+    for k, v in enumerate(lam):
+        if not np.isfinite(v) or v < 0:
+            raise ValueError(f"fit {k}: lambda is not a nonnegative real number")
+    S = _response_columns(S, K)
+    ridge = _per_fit(options.get("ridge", 0.0), K, "ridge", lambda v: penalty_fields(dict(ridge=v), n)["ridge"])
+    nonneg = _per_fit(options.get("nonnegative", 0), K, "nonnegative",
+                      lambda v: penalty_fields(dict(nonnegative=v), n)["nonnegative"])
+    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
+    w = None if pw is None else pw["l1weights"]
+    if "rho" in options:
+        is_positive_real(options["rho"], "options.rho")
+    starts = _start_matrices(options, dict(x0=n, z0=n, u0=n), K, "fit")
+    return S, lam, ridge, nonneg, w, starts
+
+
+def _lambda_grid(D, s, options, default_n):
+    """lasso_path's automatic grid: options.nlambda values (popped; default ``default_n``) log-spaced from lambda_max down
+    to options.lambda_min_ratio * lambda_max (popped; default 1e-2).  lams given: the two options are popped and ignored"""
+    nlambda = options.pop("nlambda", None)
+    ratio = options.pop("lambda_min_ratio", 1e-2)
+    if s.size != D.shape[0]:
+        raise ValueError("The number of rows in argument D do not match size of s!")
+    nlambda = default_n if nlambda is None else nlambda
+    if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
+        raise ValueError("options.nlambda must be an integer >= 1")
+    if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
+        raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
+    pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
+    lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"])[0])
+    return lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+
+
 def lasso_multi(D, S, lams, options=None):
     """results = lasso_multi(D, S, lams, options): K lasso fits over ONE sparse design matrix in one run
     -- a regularisation path, a cross-validation grid, or one D against several response columns:
 
         minimise 1/2*||D*x - s_k||^2 + lambda_k*sum_i w_i*|x_i| + ridge_k/2*||x||^2   (x >= 0 where nonnegative_k)
 
-    ``D``: any ``scipy.sparse`` matrix or array; a dense D raises ValueError (call ``lasso`` per fit).  ``S``: a vector
+    ``D``: any ``scipy.sparse`` matrix or array; a dense D raises ValueError (``lasso_multi_dense`` is its form).  ``S``: a vector
     or m x 1 (shared by all fits) or m x K (one column per fit).  ``lams``: the K values lambda_k >= 0.
     ``options['ridge']`` and ``options['nonnegative']`` are scalars or K values, ``options['l1weights']`` (n values >= 0)
     is shared by all fits.  rho, abstol, reltol, maxiters, domaxiters, objevals and check_every apply to every fit;
@@ -326,24 +366,7 @@ def lasso_multi(D, S, lams, options=None):
         raise ValueError("lasso_multi runs on a scipy.sparse D: call lasso per fit on a dense design matrix")
     _sparse_refusals(options, "lasso_multi", stopcond=True)
     D = _matrix(D, "D", sparse_ok=True)
-    m, n = D.shape
-    S = _response_matrix(S, m)
-    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
-    K = int(lam.size)
-    if K < 1:
-        raise ValueError("lams must hold at least one lambda")
-    for k, v in enumerate(lam):
-        if not np.isfinite(v) or v < 0:
-            raise ValueError(f"fit {k}: lambda is not a nonnegative real number")
-    S = _response_columns(S, K)
-    ridge = _per_fit(options.get("ridge", 0.0), K, "ridge", lambda v: penalty_fields(dict(ridge=v), n)["ridge"])
-    nonneg = _per_fit(options.get("nonnegative", 0), K, "nonnegative",
-                      lambda v: penalty_fields(dict(nonnegative=v), n)["nonnegative"])
-    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
-    w = None if pw is None else pw["l1weights"]
-    if "rho" in options:
-        is_positive_real(options["rho"], "options.rho")
-    starts = _start_matrices(options, dict(x0=n, z0=n, u0=n), K, "fit")
+    S, lam, ridge, nonneg, w, starts = _multi_lasso_fits(D, S, lams, options)
     from .sparse_lasso import SparseLassoMulti
     res = _run_and_close(SparseLassoMulti(D, S, lam, ridge, nonneg, w, device=int(options.get("device", 0))),
                          check_every=int(options.get("check_every", 0)), z0=starts.get("z0"), u0=starts.get("u0"),
@@ -358,26 +381,85 @@ def lasso_path(D, s, lams=None, options=None):
     in one run of ``lasso_multi``.  ``lams = None``: ``options['nlambda']`` values (default: the chunk of
     the sparse product, 10), log-spaced from lambda_max = max over w_i > 0 of |(D's)_i| / w_i -- the smallest lambda whose
     solution is x = 0 -- down to ``options['lambda_min_ratio']`` * lambda_max (default 1e-2).  Returns lasso_multi's
-    fields plus ``df``, the number of nonzeros of each zopt column."""
+    fields plus ``df``, the number of nonzeros of each zopt column.  A dense D raises ValueError: ``lasso_path_dense``."""
     options = _options(options, "Argument options is not a struct!", optional=True)
     from ._lib import is_sparse
     if not is_sparse(D):
         raise ValueError("lasso_path runs on a scipy.sparse D: call lasso per lambda on a dense design matrix")
     s = _colvec(s, "s")
-    nlambda = options.pop("nlambda", None)
-    ratio = options.pop("lambda_min_ratio", 1e-2)
     if lams is None:
-        if s.size != D.shape[0]:
-            raise ValueError("The number of rows in argument D do not match size of s!")
-        nlambda = 10 if nlambda is None else nlambda  # (kSpmmChunk: one pass over D per product)
-        if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
-            raise ValueError("options.nlambda must be an integer >= 1")
-        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
-            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-        pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
-        lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"])[0])
-        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+        lams = _lambda_grid(D, s, options, 10)  # (kSpmmChunk: one pass over D per product)
+    else:
+        options.pop("nlambda", None)
+        options.pop("lambda_min_ratio", None)
     res = lasso_multi(D, s, lams, options)
+    res["df"] = np.count_nonzero(res["zopt"], axis=0).astype(np.int64)
+    return res
+
+
+def _dense_multi_refusals(options, who):
+    """the options the dense multi-lasso does not run, each named in its ValueError"""
+    for key in ("fast", "convtest", "adaptive"):
+        if options.get(key, 0):
+            raise ValueError(f"options.{key} is not available in {who}")
+    if options.get("relax", 1) != 1:
+        raise ValueError(f"options.relax is not available in {who}")
+    from .lasso_multi import xsolve_code
+    xsolve_code(options.get("xsolve", "auto"))
+    if options.get("comm") is not None:
+        raise ValueError(f"options.comm is not available in {who}")
+    if options.get("parallel", "none") not in ("none", 0, None):
+        raise ValueError(f"options.parallel is not available in {who}")
+    if options.get("stopcond", "standard") != "standard":
+        raise ValueError(f"options.stopcond: {who} runs the 'standard' stop rule alone")
+
+
+def lasso_multi_dense(D, S, lams, options=None):
+    """results = lasso_multi_dense(D, S, lams, options): ``lasso_multi``'s K fits on a DENSE design matrix, m >= n, in one
+    run over one cached inverse.  The arguments, ``ridge`` / ``nonnegative`` / ``l1weights``, ``z0`` /
+    ``u0`` (n x K), ``nodualerror`` and the loop options are lasso_multi's; ``options['rho']`` (default 1) is fixed when
+    the factor of D'D + rho*I is built; ``options['xsolve']`` is 'auto' (the engine's accuracy probe decides), 'inverse'
+    (the explicit inverse, read once per chunk of fits) or 'trsv' (K pairs of triangular solves).
+
+    Returns lasso_multi's fields without nnz and the CG counters; ``xsolve`` reads 'inverse' or 'trsv'.  A scipy.sparse D
+    raises ValueError (``lasso_multi`` is its form), and so does m < n: the fat lasso stays with ``lasso``."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    t0 = time.perf_counter()
+    from ._lib import is_sparse
+    if is_sparse(D):
+        raise ValueError("lasso_multi_dense runs on a dense D: call lasso_multi on a scipy.sparse design matrix")
+    _dense_multi_refusals(options, "lasso_multi_dense")
+    D = _matrix(D, "D")
+    S, lam, ridge, nonneg, w, starts = _multi_lasso_fits(D, S, lams, options)
+    if D.shape[0] < D.shape[1]:
+        raise ValueError("lasso_multi_dense needs m >= n: the fat lasso's x-update (two dense products per fit) stays "
+                         "with lasso, one call per fit")
+    from .lasso_multi import LassoMulti
+    res = _run_and_close(LassoMulti(D, S, lam, ridge, nonneg, w, rho=float(options.get("rho", 1.0)),
+                                    xsolve=options.get("xsolve", "auto"), device=int(options.get("device", 0))),
+                         check_every=int(options.get("check_every", 0)), z0=starts.get("z0"), u0=starts.get("u0"),
+                         nodualerror=int(bool(options.get("nodualerror", 0))), **_pick(options, _LOOP_KEYS))
+    res["lams"] = lam.copy()
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
+
+
+def lasso_path_dense(D, s, lams=None, options=None):
+    """results = lasso_path_dense(D, s, lams, options): ``lasso_path`` on a dense D through ``lasso_multi_dense`` -- the
+    same automatic grid (``nlambda``, default 10 = one chunk of the product; ``lambda_min_ratio``, default 1e-2; the same
+    lambda_max) and the same ``df``."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    from ._lib import is_sparse
+    if is_sparse(D):
+        raise ValueError("lasso_path_dense runs on a dense D: call lasso_path (lasso_multi) on a scipy.sparse design matrix")
+    D = _matrix(D, "D")
+    s = _colvec(s, "s")
+    if lams is None:
+        lams = _lambda_grid(D, s, options, 10)
+    else:
+        options.pop("nlambda", None)
+        options.pop("lambda_min_ratio", None)
+    res = lasso_multi_dense(D, s, lams, options)
     res["df"] = np.count_nonzero(res["zopt"], axis=0).astype(np.int64)
     return res
 

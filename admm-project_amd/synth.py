@@ -163,6 +163,17 @@ def sparse_lasso_path_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, a
     return dict(D=D, s=s, testx=testx, lmax=float(np.max(np.abs(D.T @ s))))
 
 
+def lasso_path_problem(seed=0, rows=2 ** 9, cols=2 ** 7, active=0.1):
+    """sparse_lasso_path_problem's recipe on lasso_problem's DENSE design matrix (randn, unit columns): a truth with a
+    fraction ``active`` of nonzero coefficients of size 1 .. 3 and both signs, s = D*testx + sqrt(0.001)*randn, and
+    ``lmax`` = ||D's||_inf.  dict(D, s, testx, lmax)."""
+    D = lasso_problem(seed, rows, cols)["D"]
+    rng = np.random.default_rng(seed + 32452843)
+    testx = np.where(rng.random(cols) < active, rng.choice([-1.0, 1.0], cols) * rng.uniform(1.0, 3.0, cols), 0.0)
+    s = D @ testx + np.sqrt(0.001) * rng.standard_normal(rows)
+    return dict(D=D, s=s, testx=testx, lmax=float(np.max(np.abs(D.T @ s))))
+
+
 def sparse_svm_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=3):
     """A multi-class problem on sparse_lasso_problem's design matrix (sparse Gaussian, unit columns, canonical
     ``scipy.sparse.csc_matrix``): ``classes`` planted directions W (cols x K, randn), and the label of row i is the

@@ -171,6 +171,12 @@ def sparselassopathtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, nlambda
     D, s, lmax = p["D"], p["s"], p["lmax"]
     lams = lmax * np.concatenate([[1.25], np.logspace(np.log10(0.8), -2.0, int(nlambda) - 1)])
     results = solvers.lasso_path(D, s, lams, _opts(options, objevals=1, quiet=quiet))
+    return _path_test(p, lams, results)
+
+
+def _path_test(p, lams, results):
+    """the pass criteria of a regularisation path whose first lambda lies above lambda_max"""
+    D, s, lmax = p["D"], p["s"], p["lmax"]
     Z, X = np.asarray(results["zopt"]), np.asarray(results["xopt"])
     df = [int(v) for v in results["df"]]
     last = int(results["steps"][0]) - 1
@@ -180,6 +186,18 @@ def sparselassopathtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, nlambda
                 zero_above_lmax=zero, support_grows=grows, failed=int(not (zero and grows)), steps=results["steps"],
                 results=results)
     return test
+
+
+def lassopathtest(seed=0, rows=2 ** 9, cols=2 ** 7, nlambda=10, quiet=1, options=None):
+    """sparselassopathtest on a dense design matrix: lasso_path_dense on synth.lasso_path_problem over
+    ``nlambda`` values, the first one 1.25*lambda_max and the others log-spaced from 0.8*lambda_max down to
+    0.01*lambda_max, all in one run over one cached inverse.  The pass criteria and the ``test`` dict are those of
+    sparselassopathtest."""
+    p = synth.lasso_path_problem(seed, rows, cols)
+    D, s, lmax = p["D"], p["s"], p["lmax"]
+    lams = lmax * np.concatenate([[1.25], np.logspace(np.log10(0.8), -2.0, int(nlambda) - 1)])
+    results = solvers.lasso_path_dense(D, s, lams, _opts(options, objevals=1, quiet=quiet))
+    return _path_test(p, lams, results)
 
 
 def huberfittest(seed=0, rows=2 ** 11, cols=2 ** 7, errtol=1e-3, quiet=1, options=None):

@@ -1212,6 +1212,107 @@ int admm_sparse_lasso_set_weights(admm_sparse_lasso* obj, const double* weights)
 int admm_sparse_lasso_chunk(void);
 void admm_sparse_lasso_destroy(admm_sparse_lasso* obj);
 
+/* ---- the lasso on a DENSE design matrix, K fits over one cached inverse (additive to ABI 5): the family,
+ * the arithmetic, the stop rule and the histories of admm_sparse_lasso above, fit for fit --
+ *   minimise 1/2*||D x - s_k||^2 + lambda_k*sum_i w_i*|z_i| + mu_k/2*||z||^2 + [z >= 0 when nonneg_k]  s.t. x = z
+ * -- with the x-update x = inv(D'D + rho*I) (D's_k + rho*(z - u)) (lasso.m:28-30, getProxOps.m:1195-1200) applied from
+ * the cached factor of an ordinary ADMM_PROB_LASSO engine that the object creates and never runs.  Where that engine
+ * holds the explicit inverse, every iteration reads its fp64 tile-packed lower triangle ONCE per chunk of
+ * admm_lasso_multi_chunk() fits (csrc/symm.hip), whatever K is; where create's accuracy probe kept the triangular
+ * solves, the x-update is K pairs of them.  The inverse depends on D and rho alone, so rho belongs to the desc and
+ * options.rho must repeat it.  The objective (objevals = 1: one dense product D X per chunk and iteration) is
+ * 1/2*||D x - s_k||^2 + g_k(z).  x0 is accepted and never read: the first x-update defines x.
+ * ADMM_E_INVALID (before the device is touched): K < 1, no D / S / lambda, ns not 1 or K, per fit (named in the message)
+ * a negative or non-finite lambda or ridge, nonneg other than 0 | 1, a negative or non-finite weight (its index named), a
+ * rho that is not finite and > 0; at run: options.rho other than desc.rho.  ADMM_E_UNSUPPORTED: a communicator, an xsolve
+ * other than AUTO / INVERSE / TRSV, m < n (the fat lasso's Woodbury form needs two dense multi-products per iteration
+ * and stays with one engine per fit); at run: fast ADMM, relaxation, convtest.  Vector histories are not recorded. */
+typedef struct admm_lasso_multi admm_lasso_multi; /* opaque */
+
+typedef struct admm_lasso_multi_desc {
+  int32_t struct_size;        /* sizeof(admm_lasso_multi_desc) */
+  int32_t K;                  /* number of fits, >= 1 */
+  int64_t m, n;               /* D is m x n, m >= n */
+  const double* D;            /* HOST, column-major; copied at create */
+  int64_t ldD;                /* >= m */
+  const double* S;            /* m x ns HOST values, column-major: one response for every fit, or one column per fit */
+  int32_t ns;                 /* 1 or K */
+  int32_t device;             /* HIP device ordinal */
+  double rho;                 /* default 1.0: the rho the factor is built for, and the rho of every run */
+  int32_t xsolve;             /* ADMM_XSOLVE_AUTO (default: the engine's probe decides), _INVERSE or _TRSV */
+  int32_t reserved0;
+  const double* lambda;       /* K values lambda_k >= 0 */
+  const double* ridge;        /* K values mu_k >= 0 (NULL = 0) */
+  const int32_t* nonneg;      /* K values 0 | 1 (NULL = 0) */
+  const double* weights;      /* n l1 weights w_i >= 0 shared by all fits (NULL = 1); admm_lasso_multi_set_weights
+                                 replaces them */
+  admm_comm* comm;            /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_lasso_multi_desc;
+
+typedef struct admm_lasso_multi_options {
+  int32_t struct_size;   /* sizeof(admm_lasso_multi_options) */
+  int32_t maxiters;      /* default 1000 */
+  double rho;            /* default 1.0; must equal desc.rho */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations between host polls of "every fit has stopped" (0 = auto: 8; 64 with domaxiters) */
+  int32_t nodualerror;   /* default 0: the reference lasso's rule; 1: stop on pnorm < perr alone */
+  const double* x0;      /* accepted and never read (see above) */
+  const double* z0;      /* n x K host matrix (NULL = zeros) */
+  const double* u0;      /* n x K */
+} admm_lasso_multi_options;
+
+typedef struct admm_lasso_multi_summary {  /* one per fit */
+  int32_t steps;              /* results.steps of that fit (admm.m:746) */
+  int32_t stopped_early;      /* 1 if the stop rule fired before maxiters (admm.m:710-713) */
+  double objopt;              /* the objective at the fit's last step, NaN if not evaluated */
+  int32_t xsolve;             /* ADMM_XSOLVE_INVERSE (the packed product) or ADMM_XSOLVE_TRSV, the same for every fit */
+  int32_t reserved0;
+} admm_lasso_multi_summary;
+
+/* fields of admm_lasso_multi_fetch: the numbers of admm_sparse_lasso_fetch */
+enum {
+  ADMM_LM_F_XOPT = 1,      /* n x K */
+  ADMM_LM_F_ZOPT = 2,      /* n x K */
+  ADMM_LM_F_UOPT = 3,      /* n x K */
+  /* scalar histories: S x K column-major with S = the largest steps of any fit, NaN past a fit's own last step; DNORM
+   * and DERR after a run with nodualerror = 0 only, OBJEVALS after a run with objevals = 1 only */
+  ADMM_LM_F_PNORM = 4, ADMM_LM_F_PERR = 5, ADMM_LM_F_OBJEVALS = 6, ADMM_LM_F_DNORM = 7, ADMM_LM_F_DERR = 8
+};
+
+void admm_lasso_multi_desc_default(admm_lasso_multi_desc* desc);
+void admm_lasso_multi_options_default(admm_lasso_multi_options* opts);
+int admm_lasso_multi_create(const admm_lasso_multi_desc* desc, admm_lasso_multi** out);
+/* summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be called again on the same object:
+ * every run starts from its own z0 / u0, and two runs from the same starts give the same bits */
+int admm_lasso_multi_run(admm_lasso_multi* obj, const admm_lasso_multi_options* opts, admm_lasso_multi_summary* summaries,
+                         double* runtime_s);
+int admm_lasso_multi_fetch(admm_lasso_multi* obj, int field, double* dst, size_t cap, size_t* written);
+/* weights = n HOST values w_i >= 0 shared by all fits (the l1 weights), copied at the call and held for every later
+ * run; NULL restores 1.  ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
+int admm_lasso_multi_set_weights(admm_lasso_multi* obj, const double* weights);
+/* fits one read of the inverse serves (K beyond it: ceil(K / chunk) chunks per launch) */
+int admm_lasso_multi_chunk(void);
+/* measurement: the x-update's packed product alone (tile pass + partial-row sum over the object's own buffers, every fit
+ * running), event-timed: the median of reps calls in microseconds, the bytes of the stored triangle that one call reads
+ * per chunk, and the fused multiply-adds one call issues.  Overwrites x; ADMM_E_UNSUPPORTED where the object applies
+ * triangular solves. */
+int admm_lasso_multi_product_time(admm_lasso_multi* obj, int32_t reps, double* us_per_call, int64_t* stored_bytes,
+                                  int64_t* fma_count);
+void admm_lasso_multi_destroy(admm_lasso_multi* obj);
+
+/* X(:, k) = M * Y(:, k) for the columns k < K whose stop_mask[k] is 0 (stop_mask == NULL: every column) through the
+ * multi-lasso's product kernel (csrc/symm.hip): M symmetric n x n (ldM >= n), only its lower triangle is read (the
+ * operator builds the tile-packed triangle from it); X and Y are n x K column-major HOST matrices.  X is in/out: a masked
+ * column keeps the caller's values bit for bit.  The kernel streams every tile non-temporally: there is no cache split. */
+int admm_op_symm_packed(const double* M, int64_t n, int64_t ldM, double* X, int32_t K, const int32_t* stop_mask,
+                        const double* Y);
+
 #ifdef __cplusplus
 }
 #endif
