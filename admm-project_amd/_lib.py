@@ -466,6 +466,7 @@ _SIGNATURES = {
                                         C.POINTER(C.c_double)]),
     "admm_sparse_lasso_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_sparse_lasso_set_weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_sparse_lasso_set_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
     "admm_sparse_lasso_chunk": (C.c_int, []),
     "admm_sparse_lasso_destroy": (None, [C.c_void_p]),
     "admm_lasso_multi_desc_default": (None, [C.POINTER(LassoMultiDesc)]),
@@ -475,11 +476,16 @@ _SIGNATURES = {
                                        C.POINTER(C.c_double)]),
     "admm_lasso_multi_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_lasso_multi_set_weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_lasso_multi_set_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
     "admm_lasso_multi_chunk": (C.c_int, []),
     "admm_lasso_multi_product_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                                 C.POINTER(C.c_int64)]),
     "admm_lasso_multi_destroy": (None, [C.c_void_p]),
     "admm_op_symm_packed": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.POINTER(C.c_int32), _dp]),
+    "admm_op_group_soft_threshold_multi": (C.c_int, [_dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp, _dp,
+                                                     C.POINTER(C.c_int32), _dp]),
+    "admm_group_multi_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64), C.c_int32,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

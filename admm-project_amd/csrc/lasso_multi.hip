@@ -10,6 +10,7 @@
 // fit-interleaved layout.  Per iteration, for all fits:
 //   launch_symm_packed            X from Y, two launches
 //   launch_slm_elem               z, u, the next right-hand side rho*(z - u) + D's_k, six partial sums per fit
+//                                 (launch_slm_group_elem with groups set: admm_lasso_multi_set_groups, q41)
 //   (objevals = 1)                T = D X per chunk through launch_gemm (T' = X' D'), then launch_slm_fit
 //   launch_slm_fin                the fit's residuals, tolerances, objective and stop decision
 // Freezing, determinism and the histories are q39's: a stopped fit is skipped by every kernel, no atomics, every sum in an
@@ -21,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "group_multi.h"
 #include "multi_host.h"
 #include "sparse_lasso.h"
 
@@ -68,6 +70,7 @@ struct admm_lasso_multi : MultiHost {
   double *part = nullptr, *fpart = nullptr;
   double *W = nullptr, *par = nullptr;
   int32_t* nonneg = nullptr;
+  GroupMulti grp;  // admm_lasso_multi_set_groups (q41)
   double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   admm_lasso_multi_options last{};
 };
@@ -320,7 +323,7 @@ int admm_lasso_multi_run(admm_lasso_multi* o, const admm_lasso_multi_options* op
   fa.fpart = o->fpart;
   fa.n = o->n;
   fa.K = K;
-  fa.nwg_n = o->nwg_n;
+  fa.nwg_n = o->grp.on() ? o->grp.plan.nwg : o->nwg_n;  // (the grouped kernel: one partial per workgroup of the plan)
   fa.nwg_m = o->nwg_m;
   fa.dual = dual ? 1 : 0;
   fa.rec = o->rec;
@@ -342,7 +345,8 @@ int admm_lasso_multi_run(admm_lasso_multi* o, const admm_lasso_multi_options* op
   bool all = false;
   for (int32_t it = 0; it < N && !all; ++it) {
     lm_xupdate(o);
-    launch_slm_elem(ea, false, o->stream);
+    if (o->grp.on()) launch_slm_group_elem(ea, o->grp, o->stream);
+    else launch_slm_elem(ea, false, o->stream);
     if (op.objevals) {
       for (int32_t ch = 0; ch < o->chunks; ++ch)  // T' = X' D' per chunk: (KC x n)(n x m), both of leading dimension KC
         launch_gemm(0, 1, KC, o->m, o->n, 1.0, o->X + static_cast<int64_t>(ch) * o->n * KC, KC, o->eng->D, o->eng->ldD,
@@ -367,6 +371,12 @@ int admm_lasso_multi_set_weights(admm_lasso_multi* o, const double* weights) {
       if (!finite_nonneg(weights[i]))
         return fail(ADMM_E_INVALID, "penalty: weight " + std::to_string(i) + " is negative or not finite");
   return set_shared_weights(*o, o->n, weights, &o->W);
+}
+
+int admm_lasso_multi_set_groups(admm_lasso_multi* o, int32_t G, const int64_t* sizes, const double* groupweights,
+                                const double* l1) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  return set_multi_groups(*o, o->n, G, sizes, groupweights, l1, &o->grp);
 }
 
 int admm_lasso_multi_product_time(admm_lasso_multi* o, int32_t reps, double* us_per_call, int64_t* stored_bytes,

@@ -305,6 +305,14 @@ struct GroupPlanHost {  // the plan as one block of 8-byte words, ready for a si
 // checks sizes (each >= 1, sum == n: ADMM_E_INVALID) and weights (finite, >= 0, or null) and builds the plan;
 // ADMM_E_UNSUPPORTED when even one workgroup per kGroupMaxPerWg groups needs more than kMaxPartBlocks workgroups
 int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int64_t n, GroupPlanHost* out);
+// the same checks and packing under other limits (group_multi.h): the starting budget, the groups of one workgroup and the
+// workgroups of a plan
+struct GroupPlanLimits {
+  int64_t budget0;
+  int32_t max_per_wg, max_wg;
+};
+int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int64_t n, const GroupPlanLimits& lim,
+                     GroupPlanHost* out);
 // The grouped element update: everything launch_prox_fin does (gather of the x-solve's partial rows, relaxation, z, u,
 // extrapolation, histories, next right-hand side, block partials, finalize in the launch or deferred) with the block
 // soft threshold as the z-prox and lambda * sum_g w_g*||z_g|| in S_OBJZ (when a.objz asks for the l1 term).  defer also

@@ -810,6 +810,11 @@ GroupPlan GroupPlanHost::bind(const double* dev) const {
 }
 
 int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int64_t n, GroupPlanHost* out) {
+  return group_plan_build(sizes, G, weights, n, GroupPlanLimits{kGroupTile, kGroupMaxPerWg, kMaxPartBlocks}, out);
+}
+
+int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int64_t n, const GroupPlanLimits& lim,
+                     GroupPlanHost* out) {
   if (!sizes || G < 1 || n < 1 || !out) return fail(ADMM_E_INVALID, "groups: sizes, their count and n must be given");
   int64_t sum = 0;
   for (int32_t g = 0; g < G; ++g) {
@@ -823,17 +828,17 @@ int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int
     for (int32_t g = 0; g < G; ++g)
       if (!finite_nonneg(weights[g]))
         return fail(ADMM_E_INVALID, "groups: weight " + std::to_string(g) + " is negative or not finite");
-  // whole groups per workgroup, up to `budget` elements and kGroupMaxPerWg groups; a group past the budget stands alone
+  // whole groups per workgroup, up to `budget` elements and lim.max_per_wg groups; a group past the budget stands alone
   std::vector<int64_t> wge;
   std::vector<int32_t> wgg;
-  int64_t budget = kGroupTile;
+  int64_t budget = lim.budget0;
   for (;;) {
     wge.assign(1, 0);
     wgg.assign(1, 0);
     int64_t cur_e = 0, at = 0;
     int32_t cur_g = 0;
     for (int32_t g = 0; g < G; ++g) {
-      if (cur_g > 0 && (cur_e + sizes[g] > budget || cur_g == kGroupMaxPerWg)) {
+      if (cur_g > 0 && (cur_e + sizes[g] > budget || cur_g == lim.max_per_wg)) {
         wge.push_back(at);
         wgg.push_back(g);
         cur_e = 0;
@@ -845,9 +850,9 @@ int group_plan_build(const int64_t* sizes, int32_t G, const double* weights, int
     }
     wge.push_back(n);
     wgg.push_back(G);
-    if (static_cast<int64_t>(wge.size()) - 1 <= kMaxPartBlocks) break;
+    if (static_cast<int64_t>(wge.size()) - 1 <= lim.max_wg) break;
     if (budget >= n)
-      return fail(ADMM_E_UNSUPPORTED, "groups: more than " + std::to_string(int64_t{kMaxPartBlocks} * kGroupMaxPerWg) +
+      return fail(ADMM_E_UNSUPPORTED, "groups: more than " + std::to_string(int64_t{lim.max_wg} * lim.max_per_wg) +
                                           " groups are not supported");
     budget *= 2;
   }

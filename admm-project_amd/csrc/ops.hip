@@ -3,10 +3,12 @@
 // parity tests can pin every kernel against the oracle on its own, and for bindings that
 // keep a user prox on the host but want the heavy linear algebra on the device.
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "dct.h"
 #include "engine_internal.h"
+#include "group_multi.h"
 #include "kernels.h"
 #include "loop_kernels.h"
 #include "multi_device.h"
@@ -487,6 +489,49 @@ int admm_op_symm_packed(const double* M, int64_t n, int64_t ldM, double* X, int3
   launch_symm_packed(plan, dP, dY, dX, part, rec, K, nullptr);
   ADMM_TRY(fetch(hb.data(), dX, elems));
   spmm_unpack(hb.data(), n, K, X, n);
+  return ADMM_OK;
+}
+
+int admm_op_group_soft_threshold_multi(const double* V, int64_t n, int32_t K, const int64_t* sizes, int32_t ngroups,
+                                       const double* groupweights, const double* t, const int32_t* stop_mask, double* Z) {
+  if (!V || !Z || !t || n <= 0 || K < 1)
+    return fail(ADMM_E_INVALID, "group_soft_threshold_multi: bad argument (n >= 1, K >= 1)");
+  for (int32_t k = 0; k < K; ++k)
+    if (!finite_nonneg(t[k]))
+      return fail(ADMM_E_INVALID, "group_soft_threshold_multi: t[" + std::to_string(k) + "] is negative or not finite");
+  GroupPlanHost h;
+  ADMM_TRY(group_plan_build(sizes, ngroups, groupweights, n, kGmLimits, &h));
+  ADMM_TRY(need_device());
+  Scratch sc;
+  const size_t elems = static_cast<size_t>(spmm_chunks(K)) * kSpmmChunk * n;
+  std::vector<double> hb(elems);
+  double *dV, *dZ, *dplan, *dt;
+  spmm_pack(V, n, n, K, hb.data());
+  ADMM_TRY(sc.put(&dV, static_cast<const double*>(hb.data()), elems));
+  spmm_pack(Z, n, n, K, hb.data());
+  ADMM_TRY(sc.put(&dZ, static_cast<const double*>(hb.data()), elems));
+  ADMM_TRY(sc.put<double>(&dplan, h.blob.data(), h.blob.size()));
+  ADMM_TRY(sc.put(&dt, t, static_cast<size_t>(K)));
+  MultiRec* rec = nullptr;
+  std::vector<MultiRec> rh(static_cast<size_t>(K), MultiRec{0, 0, 0, 0});
+  for (int32_t k = 0; stop_mask && k < K; ++k) rh[k].stop = stop_mask[k] != 0;
+  ADMM_TRY(sc.put(&rec, static_cast<const MultiRec*>(rh.data()), rh.size()));
+  launch_group_multi_shrink(dV, dZ, K, h.bind(dplan), dt, rec, nullptr);
+  ADMM_TRY(fetch(hb.data(), dZ, elems));
+  spmm_unpack(hb.data(), n, K, Z, n);
+  return ADMM_OK;
+}
+
+int admm_group_multi_plan(int64_t n, const int64_t* sizes, int32_t ngroups, int64_t* wg_first, int32_t cap, int32_t* nwg,
+                          int64_t* budget) {
+  GroupPlanHost h;
+  ADMM_TRY(group_plan_build(sizes, ngroups, nullptr, n, kGmLimits, &h));
+  if (nwg) *nwg = h.nwg;
+  if (budget) *budget = h.budget;
+  if (wg_first) {
+    if (cap < h.nwg + 1) return fail(ADMM_E_CAPACITY, "destination buffer too small");
+    std::memcpy(wg_first, h.blob.data() + h.o_wge, sizeof(int64_t) * (static_cast<size_t>(h.nwg) + 1));
+  }
   return ADMM_OK;
 }
 

@@ -4,6 +4,7 @@
 // (lambda_k, mu_k, nonneg_k) and optionally in their column of S:
 //   g_k(z) = lambda_k*sum_i w_i*|z_i| + mu_k/2*||z||^2 + [z >= 0],  z = kappa_k*penalty_elem(x + u, tau_k*w_i, nonneg_k),
 //   tau_k = lambda_k/rho, kappa_k = rho/(rho + mu_k)          (q32's family without groups: penalty_device.h)
+// With groups set (admm_sparse_lasso_set_groups, q41) the element kernel is group_multi.hip's slm_group_elem_kernel.
 // The x-update (D'D + rho*I) x = D's_k + rho*(z - u) (lasso.m:28-30) is spmm_cg.hip's lock-step CG with the shift rho:
 // the first solve of a run starts from 0 and every later one from the previous x.
 // Per iteration, every launch for all K fits at once (blockIdx.y = chunk of kSpmmChunk fits):
@@ -22,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "group_multi.h"
 #include "multi_host.h"
 #include "penalty_device.h"
 #include "sparse_lasso.h"
@@ -173,6 +175,7 @@ struct admm_sparse_lasso : MultiHost {
   double *part = nullptr, *fpart = nullptr;
   double *W = nullptr, *par = nullptr;
   int32_t* nonneg = nullptr;
+  GroupMulti grp;  // admm_sparse_lasso_set_groups (q41)
   double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   admm_sparse_lasso_options last{};
 };
@@ -332,7 +335,7 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
   fa.fpart = o->fpart;
   fa.n = o->n;
   fa.K = K;
-  fa.nwg_n = o->nwg_n;
+  fa.nwg_n = o->grp.on() ? o->grp.plan.nwg : o->nwg_n;  // (the grouped kernel: one partial per workgroup of the plan)
   fa.nwg_m = o->nwg_m;
   fa.dual = dual ? 1 : 0;
   fa.rec = o->rec;
@@ -355,7 +358,8 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
   bool all = false;
   for (int32_t it = 0; it < N && !all; ++it) {
     ADMM_TRY(cg.solve(ca, it == 0));
-    launch_slm_elem(ea, false, o->stream);
+    if (o->grp.on()) launch_slm_group_elem(ea, o->grp, o->stream);
+    else launch_slm_elem(ea, false, o->stream);
     if (op.objevals) {
       launch_spmm(cg.sp.n, cg.X, cg.T, cg.chunks, run, o->stream);  // D x
       launch_slm_fit(ta, o->stream);
@@ -371,6 +375,12 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
 int admm_sparse_lasso_set_weights(admm_sparse_lasso* o, const double* weights) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
   return set_shared_weights(*o, o->n, weights, &o->W);
+}
+
+int admm_sparse_lasso_set_groups(admm_sparse_lasso* o, int32_t G, const int64_t* sizes, const double* groupweights,
+                                 const double* l1) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  return set_multi_groups(*o, o->n, G, sizes, groupweights, l1, &o->grp);
 }
 
 int admm_sparse_lasso_fetch(admm_sparse_lasso* o, int field, double* dst, size_t cap, size_t* written) {

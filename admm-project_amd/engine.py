@@ -771,6 +771,24 @@ def _set_svm_cost(self, weights=None, classcost=None):
                                                         None if cc is None else L.as_dp(cc)))
 
 
+def _set_multi_groups(self, groups=None, groupweights=None, l1=None):
+    """Groups for every later run of a multi-fit lasso object (<abi>_set_groups): ``groups`` = the sizes of
+    the contiguous groups (they sum to n), ``groupweights`` = one weight >= 0 per group shared by all fits (None: 1),
+    ``l1`` = K strengths of the l1 term (None: 0).  ``groups`` None restores the ungrouped prox."""
+    fn = getattr(self._lib, self._abi + "_set_groups")
+    if groups is None:
+        L.check(fn(self._h, 0, None, None, None))
+        return
+    g = np.asarray(groups, dtype=np.float64).reshape(-1)
+    if not np.all(np.isfinite(g)) or np.any(g != np.floor(g)):  # (a cast would truncate 1.5 to 1 without a word)
+        raise ValueError("groups: every size must be an integer")
+    sizes = np.ascontiguousarray(g.astype(np.int64))  # the library checks the rest and names the culprit
+    gw = _weights(groupweights, sizes.size, "groups", "groupweights")
+    lk = _weights(l1, self.K, "fits", "l1")
+    L.check(fn(self._h, int(sizes.size), sizes.ctypes.data_as(C.POINTER(C.c_int64)),
+               None if gw is None else L.as_dp(gw), None if lk is None else L.as_dp(lk)))
+
+
 _OVR_FIELDS = dict(xopt=(L.OVR_F_XOPT, "n"), zopt=(L.OVR_F_ZOPT, "m"), uopt=(L.OVR_F_UOPT, "m"),
                    pnorm=(L.OVR_F_PNORM, "hist"), perr=(L.OVR_F_PERR, "hist"), Hnormsq=(L.OVR_F_HNORMSQ, "hist"),
                    objevals=(L.OVR_F_OBJEVALS, "objevals"))

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _MultiOwner, _f64, _weights
+from .engine import _MultiOwner, _set_multi_groups, _f64, _weights
 
 _XSOLVE = dict(auto=L.XSOLVE_AUTO, inverse=L.XSOLVE_INVERSE, trsv=L.XSOLVE_TRSV)
 
@@ -66,6 +66,8 @@ class LassoMulti(_MultiOwner):
         self.rho = float(rho)
         self.dual = True
         self.xsolve = None  # 'inverse' | 'trsv' once a run has reported it
+
+    set_groups = _set_multi_groups
 
     def set_weights(self, l1weights=None):
         """n l1 weights >= 0 shared by all fits (admm_lasso_multi_set_weights); None restores 1"""

@@ -15,7 +15,7 @@ import numpy as np
 from .api import admm, getproxops
 from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "lasso_multi", "lasso_path", "grouplasso", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "lasso_multi", "lasso_path", "grouplasso", "grouplasso_multi", "grouplasso_path", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -322,9 +322,10 @@ def _multi_lasso_fits(D, S, lams, options):
     return S, lam, ridge, nonneg, w, starts
 
 
-def _lambda_grid(D, s, options, default_n):
+def _lambda_grid(D, s, options, default_n, lmax_of=None):
     """lasso_path's automatic grid: options.nlambda values (popped; default ``default_n``) log-spaced from lambda_max down
-    to options.lambda_min_ratio * lambda_max (popped; default 1e-2).  lams given: the two options are popped and ignored"""
+    to options.lambda_min_ratio * lambda_max (popped; default 1e-2).  lams given: the two options are popped and ignored.
+    ``lmax_of()``: another lambda_max than the lasso's (grouplasso_path)"""
     nlambda = options.pop("nlambda", None)
     ratio = options.pop("lambda_min_ratio", 1e-2)
     if s.size != D.shape[0]:
@@ -334,9 +335,50 @@ def _lambda_grid(D, s, options, default_n):
         raise ValueError("options.nlambda must be an integer >= 1")
     if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
         raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-    pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
-    lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"])[0])
+    if lmax_of is None:
+        pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
+        lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"])[0])
+    else:
+        lmax = float(lmax_of())
     return lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+
+
+def _run_multi_lasso(D, S, lams, options, who, sparse, t0, groups=None):
+    """the body of lasso_multi (sparse) and lasso_multi_dense behind their refusal of the other kind of D, and of
+    grouplasso_multi on either: the refusals, the fits, the owner, one run.  ``groups``: the sizes of grouplasso_multi;
+    options.groupweights and options.l1 are read beside them alone, and the result carries ``groups``"""
+    if sparse:
+        _sparse_refusals(options, who, stopcond=True)
+    else:
+        _dense_multi_refusals(options, who)
+    D = _matrix(D, "D", sparse_ok=sparse)
+    S, lam, ridge, nonneg, w, starts = _multi_lasso_fits(D, S, lams, options)
+    n, K = D.shape[1], int(lam.size)
+    prepare = None
+    if groups is not None:
+        sizes, gw = group_sizes(groups, options.get("groupweights"), n)
+        l1 = _per_fit(options.get("l1", 0.0), K, "l1", lambda v: penalty_fields(dict(l1=v), n)["l1"])
+        prepare = lambda obj: obj.set_groups(sizes, gw, l1)
+    if not sparse and D.shape[0] < n:
+        raise ValueError(f"{who} needs m >= n: the fat lasso's x-update (two dense products per fit) stays with lasso, "
+                         "one call per fit")
+    run = dict(check_every=int(options.get("check_every", 0)), z0=starts.get("z0"), u0=starts.get("u0"),
+               nodualerror=int(bool(options.get("nodualerror", 0))))
+    if sparse:
+        from .sparse_lasso import SparseLassoMulti
+        obj = SparseLassoMulti(D, S, lam, ridge, nonneg, w, device=int(options.get("device", 0)))
+        run.update(_pick(options, _LOOP_KEYS + _CG_KEYS))
+    else:
+        from .lasso_multi import LassoMulti
+        obj = LassoMulti(D, S, lam, ridge, nonneg, w, rho=float(options.get("rho", 1.0)),
+                         xsolve=options.get("xsolve", "auto"), device=int(options.get("device", 0)))
+        run.update(_pick(options, _LOOP_KEYS))
+    res = _run_and_close(obj, prepare, **run)
+    res["lams"] = lam.copy()
+    if groups is not None:
+        res["groups"] = sizes.copy()
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
 
 
 def lasso_multi(D, S, lams, options=None):
@@ -364,16 +406,7 @@ def lasso_multi(D, S, lams, options=None):
     from ._lib import is_sparse
     if not is_sparse(D):
         raise ValueError("lasso_multi runs on a scipy.sparse D: call lasso per fit on a dense design matrix")
-    _sparse_refusals(options, "lasso_multi", stopcond=True)
-    D = _matrix(D, "D", sparse_ok=True)
-    S, lam, ridge, nonneg, w, starts = _multi_lasso_fits(D, S, lams, options)
-    from .sparse_lasso import SparseLassoMulti
-    res = _run_and_close(SparseLassoMulti(D, S, lam, ridge, nonneg, w, device=int(options.get("device", 0))),
-                         check_every=int(options.get("check_every", 0)), z0=starts.get("z0"), u0=starts.get("u0"),
-                         nodualerror=int(bool(options.get("nodualerror", 0))), **_pick(options, _LOOP_KEYS + _CG_KEYS))
-    res["lams"] = lam.copy()
-    res["solverruntime"] = time.perf_counter() - t0
-    return res
+    return _run_multi_lasso(D, S, lams, options, "lasso_multi", True, t0)
 
 
 def lasso_path(D, s, lams=None, options=None):
@@ -428,20 +461,7 @@ def lasso_multi_dense(D, S, lams, options=None):
     from ._lib import is_sparse
     if is_sparse(D):
         raise ValueError("lasso_multi_dense runs on a dense D: call lasso_multi on a scipy.sparse design matrix")
-    _dense_multi_refusals(options, "lasso_multi_dense")
-    D = _matrix(D, "D")
-    S, lam, ridge, nonneg, w, starts = _multi_lasso_fits(D, S, lams, options)
-    if D.shape[0] < D.shape[1]:
-        raise ValueError("lasso_multi_dense needs m >= n: the fat lasso's x-update (two dense products per fit) stays "
-                         "with lasso, one call per fit")
-    from .lasso_multi import LassoMulti
-    res = _run_and_close(LassoMulti(D, S, lam, ridge, nonneg, w, rho=float(options.get("rho", 1.0)),
-                                    xsolve=options.get("xsolve", "auto"), device=int(options.get("device", 0))),
-                         check_every=int(options.get("check_every", 0)), z0=starts.get("z0"), u0=starts.get("u0"),
-                         nodualerror=int(bool(options.get("nodualerror", 0))), **_pick(options, _LOOP_KEYS))
-    res["lams"] = lam.copy()
-    res["solverruntime"] = time.perf_counter() - t0
-    return res
+    return _run_multi_lasso(D, S, lams, options, "lasso_multi_dense", False, t0)
 
 
 def lasso_path_dense(D, s, lams=None, options=None):
@@ -461,6 +481,60 @@ def lasso_path_dense(D, s, lams=None, options=None):
         options.pop("lambda_min_ratio", None)
     res = lasso_multi_dense(D, s, lams, options)
     res["df"] = np.count_nonzero(res["zopt"], axis=0).astype(np.int64)
+    return res
+
+
+def _group_lambda_max(D, s, sizes, gw):
+    """the smallest lambda whose group-lasso solution is x = 0: max over omega_g > 0 of ||(D's)_g||_2 / omega_g"""
+    g = np.asarray(D.T @ s, dtype=np.float64).reshape(-1)
+    first = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    norms = np.sqrt(np.add.reduceat(g * g, first))
+    live = np.ones(norms.size, dtype=bool) if gw is None else gw > 0
+    return float(np.max(norms[live] / (1.0 if gw is None else gw[live]))) if live.any() else 0.0
+
+
+def grouplasso_multi(D, S, lams, groups, options=None):
+    """results = grouplasso_multi(D, S, lams, groups, options): K group-lasso or sparse-group-lasso fits over ONE design
+    matrix in one run -- ``lasso_multi``'s object on a scipy.sparse D, ``lasso_multi_dense``'s on a
+    dense one (m >= n):
+
+        minimise 1/2*||D*x - s_k||^2 + lambda_k*sum_g omega_g*||x_g||_2 + l1_k*sum_i w_i*|x_i| + ridge_k/2*||x||^2
+                                                                                    (x >= 0 where nonnegative_k)
+
+    ``groups``: the sizes of the contiguous groups (integers >= 1 that sum to the columns of D), shared by all fits, as
+    ``options['groupweights']`` (omega_g >= 0, default 1) is.  ``options['l1']`` is a scalar or K values (default 0);
+    ``ridge``, ``nonnegative`` and ``l1weights`` are lasso_multi's.  S, lams, the starts, the loop options, the refusals
+    and the result are those of the underlying caller; the result also carries ``groups`` (the sizes)."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    t0 = time.perf_counter()
+    from ._lib import is_sparse
+    return _run_multi_lasso(D, S, lams, options, "grouplasso_multi", is_sparse(D), t0, groups=groups)
+
+
+def grouplasso_path(D, s, groups, lams=None, options=None):
+    """results = grouplasso_path(D, s, groups, lams, options): the group lasso's regularisation path, every lambda side by
+    side in one run of ``grouplasso_multi``.  ``lams = None`` with l1 = 0: ``options['nlambda']`` values
+    (default 10) log-spaced from lambda_max = max over omega_g > 0 of ||(D's)_g||_2 / omega_g -- the smallest lambda
+    whose solution is x = 0 -- down to ``options['lambda_min_ratio']`` * lambda_max (default 1e-2).  With any l1 != 0 that
+    lambda_max has no closed form: ``lams`` must be given (ValueError).  Returns grouplasso_multi's fields plus ``df``,
+    the nonzeros of each zopt column, and ``df_groups``, its groups with a nonzero block."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    from ._lib import is_sparse
+    D = _matrix(D, "D", sparse_ok=is_sparse(D))
+    s = _colvec(s, "s")
+    sizes, gw = group_sizes(groups, options.get("groupweights"), D.shape[1])
+    if lams is None:
+        if np.any(np.asarray(options.get("l1", 0.0), dtype=np.float64) != 0):
+            raise ValueError("grouplasso_path: with options.l1 != 0 lambda_max has no closed form: give lams")
+        lams = _lambda_grid(D, s, options, 10, lambda: _group_lambda_max(D, s, sizes, gw))
+    else:
+        options.pop("nlambda", None)
+        options.pop("lambda_min_ratio", None)
+    res = grouplasso_multi(D, s, lams, sizes, options)
+    Z = np.asarray(res["zopt"]).reshape(D.shape[1], -1)
+    res["df"] = np.count_nonzero(Z, axis=0).astype(np.int64)
+    first = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    res["df_groups"] = np.count_nonzero(np.add.reduceat(Z != 0, first, axis=0), axis=0).astype(np.int64)
     return res
 
 

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _MultiOwner, _weights
+from .engine import _MultiOwner, _set_multi_groups, _weights
 
 
 class SparseLassoMulti(_MultiOwner):
@@ -49,6 +49,8 @@ class SparseLassoMulti(_MultiOwner):
             d.weights = L.as_dp(w)
         self._create(d)
         self.dual = True
+
+    set_groups = _set_multi_groups
 
     def set_weights(self, l1weights=None):
         """n l1 weights >= 0 shared by all fits (admm_sparse_lasso_set_weights); None restores 1"""

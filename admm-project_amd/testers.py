@@ -200,6 +200,34 @@ def lassopathtest(seed=0, rows=2 ** 9, cols=2 ** 7, nlambda=10, quiet=1, options
     return _path_test(p, lams, results)
 
 
+def grouplassopathtest(seed=0, rows=2 ** 9, cols=2 ** 7, group=8, nlambda=10, quiet=1, options=None):
+    """The group lasso's regularisation path: grouplasso_path on synth.lasso_path_problem's dense matrix
+    with a group-sparse truth (every fourth group of ``group`` coefficients live) over ``nlambda`` values, the first one
+    1.25*lambda_max and the others log-spaced from 0.8*lambda_max down to 0.01*lambda_max, all in one run.  Pass when
+    every block is 0.0 exactly at the lambda above lambda_max, the number of live groups does not shrink as lambda falls,
+    and groups enter whole: in every fit a group's block is either all zero or has no zero in it."""
+    p = synth.lasso_path_problem(seed, rows, cols)
+    D = p["D"]
+    sizes = np.full(cols // group, group, dtype=np.int64)
+    sizes[-1] += cols - int(sizes.sum())
+    rng = np.random.default_rng(seed + 15485863)
+    live = np.repeat(np.arange(sizes.size) % 4 == 0, sizes)
+    testx = np.where(live, rng.choice([-1.0, 1.0], cols) * rng.uniform(1.0, 3.0, cols), 0.0)
+    s = D @ testx + np.sqrt(0.001) * rng.standard_normal(rows)
+    lmax = solvers._group_lambda_max(D, s, sizes, None)
+    lams = lmax * np.concatenate([[1.25], np.logspace(np.log10(0.8), -2.0, int(nlambda) - 1)])
+    results = solvers.grouplasso_path(D, s, sizes, lams, _opts(options, objevals=1, quiet=quiet))
+    Z = np.asarray(results["zopt"])
+    nz = np.add.reduceat(Z != 0, np.concatenate([[0], np.cumsum(sizes)[:-1]]), axis=0)
+    whole = bool(np.all((nz == 0) | (nz == sizes[:, None])))
+    dfg = [int(v) for v in results["df_groups"]]
+    zero = bool(np.all(Z[:, 0] == 0.0))
+    grows = all(b >= a for a, b in zip(dfg[:-1], dfg[1:]))
+    return dict(D=D, s=s, testx=testx, groups=sizes, lmax=lmax, lams=lams, df_groups=dfg, xopt=np.asarray(results["xopt"]),
+                admmopt=results["objopt"], zero_above_lmax=zero, groups_grow=grows, groups_enter_whole=whole,
+                failed=int(not (zero and grows and whole)), steps=results["steps"], results=results)
+
+
 def huberfittest(seed=0, rows=2 ** 11, cols=2 ** 7, errtol=1e-3, quiet=1, options=None):
     """testers/huberfittest.m:43-188: ADMM's objective is below the planted solution's (line 154)."""
     p = synth.huber_problem(seed, rows, cols)

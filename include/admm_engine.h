@@ -1208,6 +1208,17 @@ int admm_sparse_lasso_fetch(admm_sparse_lasso* obj, int field, double* dst, size
 /* weights = cols HOST values w_i >= 0 shared by all fits (the l1 weights), copied at the call and held for every later
  * run; NULL restores 1.  ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
 int admm_sparse_lasso_set_weights(admm_sparse_lasso* obj, const double* weights);
+/* Groups for every later run (additive to ABI 5): G contiguous groups of sizes[g] >= 1 coefficients that
+ * sum to cols, group weights omega_g >= 0 (NULL = 1) shared by all fits, and per fit the strength l1[k] >= 0 of the l1
+ * term (K values, NULL = 0); all HOST arrays, copied at the call.  With groups in force lambda_k weighs the group term,
+ *   g_k(z) = lambda_k*sum_g omega_g*||z_g||_2 + l1[k]*sum_i w_i*|z_i| + mu_k/2*||z||^2 + [z >= 0 when nonneg_k],
+ * and the z-update is soft threshold (or positive part), block soft threshold, scale by rho/(rho + mu_k).  G = 0 or
+ * sizes = NULL restores the ungrouped prox, where lambda_k weighs the l1 term.  ADMM_E_INVALID: a size below 1, sizes
+ * that do not sum to cols, a negative or non-finite group weight (its index named) or l1[k] (the fit named);
+ * ADMM_E_UNSUPPORTED: more than 65536 groups that the plan cannot pack (256 workgroups of at most 256 groups each).  A
+ * refused call changes nothing. */
+int admm_sparse_lasso_set_groups(admm_sparse_lasso* obj, int32_t G, const int64_t* sizes, const double* groupweights,
+                                 const double* l1);
 /* fits one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
 int admm_sparse_lasso_chunk(void);
 void admm_sparse_lasso_destroy(admm_sparse_lasso* obj);
@@ -1296,6 +1307,9 @@ int admm_lasso_multi_fetch(admm_lasso_multi* obj, int field, double* dst, size_t
 /* weights = n HOST values w_i >= 0 shared by all fits (the l1 weights), copied at the call and held for every later
  * run; NULL restores 1.  ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
 int admm_lasso_multi_set_weights(admm_lasso_multi* obj, const double* weights);
+/* admm_sparse_lasso_set_groups on the dense object: the same arguments, checks and z-update */
+int admm_lasso_multi_set_groups(admm_lasso_multi* obj, int32_t G, const int64_t* sizes, const double* groupweights,
+                                const double* l1);
 /* fits one read of the inverse serves (K beyond it: ceil(K / chunk) chunks per launch) */
 int admm_lasso_multi_chunk(void);
 /* measurement: the x-update's packed product alone (tile pass + partial-row sum over the object's own buffers, every fit
@@ -1312,6 +1326,18 @@ void admm_lasso_multi_destroy(admm_lasso_multi* obj);
  * column keeps the caller's values bit for bit.  The kernel streams every tile non-temporally: there is no cache split. */
 int admm_op_symm_packed(const double* M, int64_t n, int64_t ldM, double* X, int32_t K, const int32_t* stop_mask,
                         const double* Y);
+
+/* Z(:, k) = the block soft threshold of V(:, k) with the thresholds t[k]*omega_g, for the columns k < K whose
+ * stop_mask[k] is 0 (stop_mask == NULL: every column), through the device functions of the multi-fit lasso's grouped
+ * element kernel (csrc/group_multi.hip) over its fit-interleaved layout and its plan: stage 2 of the prox
+ * alone.  V and Z are n x K column-major HOST matrices; sizes / ngroups / groupweights as admm_op_group_soft_threshold;
+ * t holds K finite values >= 0.  Z is in/out: a masked column keeps the caller's values bit for bit. */
+int admm_op_group_soft_threshold_multi(const double* V, int64_t n, int32_t K, const int64_t* sizes, int32_t ngroups,
+                                       const double* groupweights, const double* t, const int32_t* stop_mask, double* Z);
+/* The plan of that kernel, on the host alone (no device is touched): *nwg workgroups, workgroup b owning the rows
+ * wg_first[b] .. wg_first[b + 1] (cap >= *nwg + 1 entries; wg_first may be NULL), and the row budget it was packed for. */
+int admm_group_multi_plan(int64_t n, const int64_t* sizes, int32_t ngroups, int64_t* wg_first, int32_t cap, int32_t* nwg,
+                          int64_t* budget);
 
 #ifdef __cplusplus
 }
