@@ -317,6 +317,24 @@ class LassoMultiSummary(C.Structure):  # admm_lasso_multi_summary
 (LM_F_XOPT, LM_F_ZOPT, LM_F_UOPT, LM_F_PNORM, LM_F_PERR, LM_F_OBJEVALS, LM_F_DNORM, LM_F_DERR) = range(1, 9)
 
 
+class L1ClassDesc(C.Structure):  # admm_l1class_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("m", C.c_int64), ("n", C.c_int64), ("D", _dp),
+                ("ldD", C.c_int64), ("ELL", _dp), ("nell", C.c_int32), ("device", C.c_int32), ("C", C.c_double),
+                ("xsolve", C.c_int32), ("reserved0", C.c_int32), ("loss", C.POINTER(C.c_int32)), ("lam", _dp),
+                ("ridge", _dp), ("nonneg", C.POINTER(C.c_int32)), ("l1weights", _dp), ("comm", C.c_void_p)]
+
+
+class L1ClassOptions(C.Structure):  # admm_l1class_options
+    _fields_ = list(LassoMultiOptions._fields_)
+
+
+class L1ClassSummary(C.Structure):  # admm_l1class_summary
+    _fields_ = list(LassoMultiSummary._fields_)
+
+
+(L1C_F_XOPT, L1C_F_ZOPT, L1C_F_UOPT, L1C_F_PNORM, L1C_F_PERR, L1C_F_OBJEVALS, L1C_F_DNORM, L1C_F_DERR) = range(1, 9)
+
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
@@ -481,6 +499,19 @@ _SIGNATURES = {
     "admm_lasso_multi_product_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                                 C.POINTER(C.c_int64)]),
     "admm_lasso_multi_destroy": (None, [C.c_void_p]),
+    "admm_l1class_desc_default": (None, [C.POINTER(L1ClassDesc)]),
+    "admm_l1class_options_default": (None, [C.POINTER(L1ClassOptions)]),
+    "admm_l1class_create": (C.c_int, [C.POINTER(L1ClassDesc), C.POINTER(C.c_void_p)]),
+    "admm_l1class_run": (C.c_int, [C.c_void_p, C.POINTER(L1ClassOptions), C.POINTER(L1ClassSummary),
+                                   C.POINTER(C.c_double)]),
+    "admm_l1class_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_l1class_set_cost": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "admm_l1class_set_l1weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_l1class_chunk": (C.c_int, []),
+    "admm_l1class_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "admm_l1class_pass_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "admm_l1class_destroy": (None, [C.c_void_p]),
     "admm_op_symm_packed": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.POINTER(C.c_int32), _dp]),
     "admm_op_group_soft_threshold_multi": (C.c_int, [_dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp, _dp,
                                                      C.POINTER(C.c_int32), _dp]),

@@ -742,15 +742,16 @@ class _MultiOwner:
         """The result dict of the run whose summary is ``summ``: xopt / zopt / uopt, steps, the histories the run kept
         cut to max(steps) rows, objopt and runtime, then chunk and, for the CG objects, xsolve = 'cg', nnz and the CG
         counters"""
-        kept = dict(n=self.n, m=self.m, hist=int(summ["steps"].max()))
+        vec = ("n", "m", "mn")  # ("mn": m + n stacked rows, the l1 classifier's z and u)
+        kept = dict(n=self.n, m=self.m, mn=self.n + self.m, hist=int(summ["steps"].max()))
         if self.objevals:
             kept["objevals"] = kept["hist"]
         if getattr(self, "dual", False):
             kept["dual"] = kept["hist"]
-        res = {key: self.fetch(field, kept[rows]) for key, (field, rows) in self._fields.items() if rows in ("n", "m")}
+        res = {key: self.fetch(field, kept[rows]) for key, (field, rows) in self._fields.items() if rows in vec}
         res["steps"] = summ["steps"]
         res.update({key: self.fetch(field, kept[rows]) for key, (field, rows) in self._fields.items()
-                    if rows not in ("n", "m") and rows in kept})
+                    if rows not in vec and rows in kept})
         res.update(objopt=summ["objopt"], runtime=summ["runtime"])
         if self._chunk_result:
             res["chunk"] = self.chunk()

@@ -15,7 +15,7 @@ import numpy as np
 from .api import admm, getproxops
 from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "lasso_multi", "lasso_path", "grouplasso", "grouplasso_multi", "grouplasso_path", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "lasso_multi", "lasso_path", "grouplasso", "grouplasso_multi", "grouplasso_path", "l1classifier", "l1classifier_multi", "l1classifier_path", "l1classifier_lambda_max", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
 
 _ENGINE_OBJ = "<engine-native objective>"
@@ -481,6 +481,182 @@ def lasso_path_dense(D, s, lams=None, options=None):
         options.pop("lambda_min_ratio", None)
     res = lasso_multi_dense(D, s, lams, options)
     res["df"] = np.count_nonzero(res["zopt"], axis=0).astype(np.int64)
+    return res
+
+
+# ---- sparse linear classifiers: the lasso's penalties on the linear SVM's losses
+_L1C_HIST = ("pnorm", "perr", "dnorm", "derr", "objevals")
+_L1C_SLOPE0 = dict(logistic=0.5, hinge=1.0, sqhinge=2.0)  # |phi'(0)|
+
+
+def _l1c_labels(ELL, m, K=None):
+    ELL = np.asarray(ELL, dtype=np.float64)
+    if ELL.ndim == 1:
+        ELL = ELL.reshape(-1, 1)
+    if ELL.ndim != 2:
+        raise ValueError("Argument ell is neither a vector nor a matrix!")
+    if ELL.shape[0] != m:
+        raise ValueError("The number of rows in argument D do not match size of ell!")
+    if K is not None and ELL.shape[1] not in (1, K):
+        raise ValueError(f"ELL has {ELL.shape[1]} columns for {K} fits: one shared label column or one column per fit")
+    if not np.all(np.abs(ELL) == 1.0):
+        raise ValueError("Argument ell must hold the labels +1 and -1 alone!")
+    return np.asfortranarray(ELL)
+
+
+def _l1c_costs(options, ELL, K):
+    """(weights, K x 2 class costs) out of options.weights / options.classcost (None where not given)"""
+    w = svm_cost_fields(dict(weights=options.get("weights")), ELL[:, 0])
+    weights = None if w is None else w["weights"]
+    cc = options.get("classcost")
+    if cc is None:
+        return weights, None
+    cols = [ELL[:, k if ELL.shape[1] > 1 else 0] for k in range(K)]
+    if not isinstance(cc, str):
+        arr = np.asarray(cc, dtype=np.float64)
+        if arr.ndim == 2:
+            if arr.shape != (K, 2):
+                raise ValueError(f"classcost is not a {K} x 2 array (one (pos, neg) pair per fit)")
+            return weights, np.ascontiguousarray([class_cost_pair(arr[k], cols[k]) for k in range(K)])
+    return weights, np.ascontiguousarray([class_cost_pair(cc, cols[k]) for k in range(K)])
+
+
+def l1classifier_lambda_max(D, ell, options=None):
+    """The smallest lambda whose l1 classifier is x = 0 when every coefficient is penalised:
+    C*|phi'(0)|*max over w_j > 0 of |sum_i c_i*ell_i*D_ij| / w_j, with phi'(0) = -1/2 (logistic), -1 (hinge), -2
+    (sqhinge).  With an unpenalised column (w_j = 0) the all-zero model is in general not optimal at this lambda."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    D = _matrix(D, "D")
+    ELL = _l1c_labels(ell, D.shape[0], 1)
+    loss = options.get("lossfunction", "logistic")
+    from .l1class import loss_code
+    loss_code(loss)
+    weights, cc = _l1c_costs(options, ELL, 1)
+    e = ELL[:, 0]
+    c = np.ones(e.size) if weights is None else weights.copy()
+    if cc is not None:
+        c = c * np.where(e > 0, cc[0][0], cc[0][1])
+    pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
+    g = np.abs(D.T @ (c * e))
+    if pw is not None:
+        live = pw["l1weights"] > 0
+        g = g[live] / pw["l1weights"][live]
+    Cv = is_positive_real(options.get("C", 1.0), "options.C")
+    return Cv * _L1C_SLOPE0[loss.lower()] * (float(g.max()) if g.size else 0.0)
+
+
+def l1classifier_multi(D, ELL, lams, options=None):
+    """results = l1classifier_multi(D, ELL, lams, options): K sparse linear classifiers over ONE dense D in one run
+     -- a regularisation path, a grid, several label columns or losses:
+
+        minimise C*sum_i c_ik*phi_k(ell_ik*(D*x)_i) + lambda_k*sum_j w_j*|x_j| + ridge_k/2*||x||^2   (x >= 0 where nonnegative_k)
+
+    ``D``: dense, any shape (m < n included).  ``ELL``: labels +-1, a vector or m x 1 (shared by all fits) or m x K.
+    ``lams``: the K values lambda_k >= 0.  ``options['lossfunction']`` ('logistic' by default, 'hinge', 'sqhinge') is one
+    string or K of them; ``ridge`` and ``nonnegative`` are scalars or K values; ``l1weights`` (n values >= 0; 0 leaves a
+    coefficient unpenalised -- an intercept is a column of ones with weight 0), ``weights`` (m values >= 0) and ``C``
+    (default 1) are shared; ``classcost`` is a pair, 'balanced' or a K x 2 array.  rho, abstol, reltol, maxiters,
+    domaxiters, objevals, check_every and nodualerror are the plain loop's; ``z0`` / ``u0`` are (m + n) x K (default
+    zeros: the m rows of D above the n coefficients), x0 (n x K) is checked and never read; ``xsolve`` is 'auto',
+    'inverse' or 'trsv'.  The loop is admm.m's with A = [D; I], B = -1, c = 0 and stopcond 'standard'.
+
+    Returns xopt (n x K), zopt, uopt ((m + n) x K), steps (K), pnorm / perr (max(steps) x K, NaN past a fit's last
+    step), dnorm / derr unless nodualerror = 1, objevals with options['objevals'], objopt, runtime, solverruntime, chunk,
+    lams and xsolve.  fast, convtest, relax, adaptive, comm, parallel, a stopcond other than 'standard', the loss '01'
+    and a scipy.sparse D are refused by name."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    t0 = time.perf_counter()
+    from ._lib import is_sparse
+    from .l1class import L1Classifier, loss_code
+    if is_sparse(D):
+        raise ValueError("l1classifier_multi runs on a dense D: the sparse form of this iteration is not built")
+    _dense_multi_refusals(options, "l1classifier_multi")
+    D = _matrix(D, "D")
+    m, n = D.shape
+    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
+    K = int(lam.size)
+    if K < 1:
+        raise ValueError("lams must hold at least one lambda")
+    for k, v in enumerate(lam):
+        if not np.isfinite(v) or v < 0:
+            raise ValueError(f"fit {k}: lambda is not a nonnegative real number")
+    ELL = _l1c_labels(ELL, m, K)
+    loss = options.get("lossfunction", "logistic")
+    losses = [loss] * K if isinstance(loss, str) else list(loss)
+    if len(losses) != K:
+        raise ValueError("options.lossfunction is neither one string nor a list with one string per fit!")
+    for k, v in enumerate(losses):
+        loss_code(v, k)
+    ridge = _per_fit(options.get("ridge", 0.0), K, "ridge", lambda v: penalty_fields(dict(ridge=v), n)["ridge"])
+    nonneg = _per_fit(options.get("nonnegative", 0), K, "nonnegative",
+                      lambda v: penalty_fields(dict(nonnegative=v), n)["nonnegative"])
+    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
+    w = None if pw is None else pw["l1weights"]
+    Cv = is_positive_real(options.get("C", 1.0), "options.C")
+    if "rho" in options:
+        is_positive_real(options["rho"], "options.rho")
+    weights, class_cost = _l1c_costs(options, ELL, K)
+    starts = _start_matrices(options, dict(x0=n, z0=m + n, u0=m + n), K, "fit")
+    obj = L1Classifier(D, ELL, lam, losses, ridge, nonneg, w, C=Cv, xsolve=options.get("xsolve", "auto"),
+                       device=int(options.get("device", 0)))
+    res = _run_and_close(obj, _cost_setter(weights, class_cost), check_every=int(options.get("check_every", 0)),
+                         z0=starts.get("z0"), u0=starts.get("u0"), nodualerror=int(bool(options.get("nodualerror", 0))),
+                         **_pick(options, _LOOP_KEYS))
+    res["lams"] = lam.copy()
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
+
+
+def l1classifier(D, ell, lam, options=None):
+    """results = l1classifier(D, ell, lam, options): ONE sparse linear classifier, ``l1classifier_multi`` with K = 1 --
+    l1-regularised logistic regression by default, the l1-SVM with lossfunction 'hinge' or 'sqhinge'.  ``x0`` has n
+    entries, ``z0`` / ``u0`` m + n.  Returns vectors and scalars where l1classifier_multi returns columns."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    if not np.isscalar(lam) or not np.isreal(lam):
+        raise ValueError("Argument lam is not a nonnegative real number!")
+    D = _matrix(D, "D")
+    m, n = D.shape
+    loss = options.get("lossfunction", "logistic")
+    if not isinstance(loss, str):
+        raise ValueError("options.lossfunction is not a string!")
+    for key, v in _start_columns(options, dict(x0=n, z0=m + n, u0=m + n)).items():
+        options[key] = v
+    res = l1classifier_multi(D, _colvec(ell, "ell"), [lam], options)
+    for key in ("xopt", "zopt", "uopt") + _L1C_HIST:
+        if key in res:
+            res[key] = np.ascontiguousarray(res[key][:, 0])
+    res.update(steps=int(res["steps"][0]), objopt=float(res["objopt"][0]), lam=float(res.pop("lams")[0]))
+    return res
+
+
+def l1classifier_path(D, ell, lams=None, options=None):
+    """results = l1classifier_path(D, ell, lams, options): the regularisation path of ``l1classifier``, every lambda
+    side by side in one run of ``l1classifier_multi``.  ``lams``: an array, or a count (None: ``options['nlambda']``,
+    default 10 = one chunk of the passes over D) for a grid log-spaced from ``l1classifier_lambda_max`` down to
+    ``options['lambda_min_ratio']`` (default 1e-2) times it.  lambda_max is the smallest lambda with x = 0 only when
+    every coefficient is penalised: with an unpenalised column (l1weights of 0, an intercept) the grid's first point
+    may not be the all-zero model.  Returns l1classifier_multi's fields plus ``df``, the nonzeros of each column of the
+    coefficient block of zopt."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    D = _matrix(D, "D")
+    e = _colvec(ell, "ell")
+    if lams is None or np.isscalar(lams):
+        if lams is not None:
+            options["nlambda"] = lams
+        nlambda = options.pop("nlambda", None)
+        ratio = options.pop("lambda_min_ratio", 1e-2)
+        nlambda = 10 if nlambda is None else nlambda
+        if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
+            raise ValueError("options.nlambda must be an integer >= 1")
+        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
+            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
+        lmax = l1classifier_lambda_max(D, e, options)
+        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+    else:
+        options.pop("nlambda", None)
+        options.pop("lambda_min_ratio", None)
+    res = l1classifier_multi(D, e, lams, options)
+    res["df"] = np.count_nonzero(res["zopt"][D.shape[0]:], axis=0).astype(np.int64)
     return res
 
 

@@ -174,6 +174,19 @@ def lasso_path_problem(seed=0, rows=2 ** 9, cols=2 ** 7, active=0.1):
     return dict(D=D, s=s, testx=testx, lmax=float(np.max(np.abs(D.T @ s))))
 
 
+def sparse_classifier_problem(seed=0, rows=2 ** 9, cols=2 ** 7, active=0.1, noise=0.1):
+    """A two-class problem with a sparse truth on lasso_problem's DENSE design matrix (randn, unit columns): a fraction
+    ``active`` of the coefficients is nonzero (size 1 .. 3, both signs, at least one), and the label of row i is
+    sign((D*testx)_i + noise*randn), with 0 counted as +1.  dict(D, ell, testx)."""
+    D = lasso_problem(seed, rows, cols)["D"]
+    rng = np.random.default_rng(seed + 49979687)
+    testx = np.where(rng.random(cols) < active, rng.choice([-1.0, 1.0], cols) * rng.uniform(1.0, 3.0, cols), 0.0)
+    if not np.any(testx):
+        testx[0] = 1.0
+    score = D @ testx + noise * rng.standard_normal(rows)
+    return dict(D=D, ell=np.where(score >= 0, 1.0, -1.0), testx=testx)
+
+
 def sparse_svm_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=3):
     """A multi-class problem on sparse_lasso_problem's design matrix (sparse Gaussian, unit columns, canonical
     ``scipy.sparse.csc_matrix``): ``classes`` planted directions W (cols x K, randn), and the label of row i is the

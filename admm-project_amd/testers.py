@@ -12,7 +12,7 @@ import numpy as np
 
 from . import solvers, synth
 
-__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "sparsequantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "basispursuittest",
+__all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "sparsequantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "l1classifiertest", "basispursuittest",
            "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
 
 
@@ -295,6 +295,27 @@ def sparsesvmtest(seed=0, rows=2 ** 10, cols=2 ** 7, density=0.05, classes=3, er
     accuracy = float(np.mean(pred == labels))
     test = dict(D=D, labels=labels, xopt=results["xopt"], accuracy=accuracy, failed=int(not accuracy >= 1.0 - errtol),
                 steps=results["steps"], nnz=results["nnz"], cg_capped_updates=results["cg_capped_updates"], errtol=errtol)
+    return results, test
+
+
+def l1classifiertest(seed=0, rows=2 ** 9, cols=2 ** 7, errtol=0.15, quiet=1, options=None):
+    """lassotest's shape for l1classifier (l1-regularised logistic regression on synth.sparse_classifier_problem, at a
+    tenth of lambda_max): pass when the objective at the sparse iterate z2 lies below the objective of x = 0 -- what
+    every lambda >= lambda_max returns -- and sign(D*z2) reproduces the labels on at least 1 - errtol of the rows."""
+    p = synth.sparse_classifier_problem(seed, rows, cols)
+    D, ell = p["D"], p["ell"]
+    o = _opts(options, objevals=1, quiet=quiet)
+    Cv = float(o.get("C", 1.0))
+    lam = 0.1 * solvers.l1classifier_lambda_max(D, ell, o)
+    obj = lambda x: Cv * np.sum(np.logaddexp(0.0, -ell * (D @ x))) + lam * np.sum(np.abs(x))
+    results = solvers.l1classifier(D, ell, lam, o)
+    z2 = results["zopt"][rows:]
+    objopt, zeroobj = obj(z2), obj(np.zeros(cols))
+    accuracy = float(np.mean(np.where(D @ z2 >= 0, 1.0, -1.0) == ell))
+    test = dict(D=D, ell=ell, testx=p["testx"], xopt=results["xopt"], zopt=z2, admmopt=results["objopt"], objopt=objopt,
+                zeroobj=zeroobj, accuracy=accuracy, df=int(np.count_nonzero(z2)),
+                failed=int(not (objopt < zeroobj and accuracy >= 1.0 - errtol)), steps=results["steps"], errtol=errtol)
+    test["lambda"] = lam
     return results, test
 
 

@@ -1320,6 +1320,111 @@ int admm_lasso_multi_product_time(admm_lasso_multi* obj, int32_t reps, double* u
                                   int64_t* fma_count);
 void admm_lasso_multi_destroy(admm_lasso_multi* obj);
 
+/* ---- sparse linear classifiers on a DENSE design matrix, K fits over one D (additive to ABI 5): the
+ * l1 / elastic-net penalty of the lasso family on the losses of the linear SVM,
+ *   minimise C*sum_i c_ik*phi_k(ell_ik*(D x)_i) + lambda_k*sum_j w_j*|x_j| + mu_k/2*||x||^2  [x >= 0 when nonneg_k]
+ * with phi_k hinge, squared hinge or logistic, c_ik = weights_i * (ell_ik > 0 ? cost_pos_k : cost_neg_k) and l1 weights
+ * w_j >= 0 shared by all fits (w_j = 0: an unpenalised coefficient, e.g. an intercept column of ones).  Every fit is a
+ * plain-ADMM run of admm.m with A = [D; I_n], B = -1, c = 0, z = [z1 (m); z2 (n)], stopcond 'standard':
+ *   x = inv(D'D + I) (D'(z1 - u1) + (z2 - u2))      one factor and one explicit inverse for every fit and every rho
+ *   z1 = prox of (C*c/rho)*phi at (D x + u1),  z2 = kappa*penalty_elem(x + u2, (lambda/rho)*w, nonneg)
+ * Per iteration D is read twice per chunk of admm_l1class_chunk() fits (csrc/l1class.hip: a forward pass D X with the
+ * z1 / u1 update in the launch, a transposed pass D'(z1 - u1)), whatever n is; the n x n product is csrc/symm.hip's, or
+ * K pairs of triangular solves where create's accuracy probe kept them.  rho is a run option.  The dual residual
+ * rho*||D'(z1 - z1prev) + (z2 - z2prev)|| and its tolerance widen the transposed pass to three vectors per fit; with
+ * nodualerror = 1 they are not computed.  x0 is accepted and never read: the first x-update defines x.
+ * ADMM_E_INVALID (before the device is touched): K < 1, no D / ELL / lambda, nell not 1 or K, a label that is not +-1,
+ * per fit (named in the message) a loss other than ADMM_LOSS_HINGE / _SQHINGE / _LOGISTIC (the 0-1 loss is not convex
+ * and has no lambda_max), a negative or non-finite lambda or ridge, nonneg other than 0 | 1; a negative or non-finite l1
+ * weight (its index named); C that is not finite and > 0.  ADMM_E_UNSUPPORTED: a communicator, an xsolve other than
+ * AUTO / INVERSE / TRSV; at run: fast ADMM, relaxation, convtest.  Vector histories are not recorded. */
+typedef struct admm_l1class admm_l1class; /* opaque */
+
+typedef struct admm_l1class_desc {
+  int32_t struct_size;        /* sizeof(admm_l1class_desc) */
+  int32_t K;                  /* number of fits, >= 1 */
+  int64_t m, n;               /* D is m x n, any shape */
+  const double* D;            /* HOST, column-major; copied at create */
+  int64_t ldD;                /* >= m */
+  const double* ELL;          /* m x nell HOST labels +-1, column-major: one column for every fit, or one per fit */
+  int32_t nell;               /* 1 or K */
+  int32_t device;             /* HIP device ordinal */
+  double C;                   /* default 1.0: the cost of the loss term, > 0 */
+  int32_t xsolve;             /* ADMM_XSOLVE_AUTO (default: the engine's probe decides), _INVERSE or _TRSV */
+  int32_t reserved0;
+  const int32_t* loss;        /* K values ADMM_LOSS_HINGE | _SQHINGE | _LOGISTIC (NULL = logistic for every fit) */
+  const double* lambda;       /* K values lambda_k >= 0 */
+  const double* ridge;        /* K values mu_k >= 0 (NULL = 0) */
+  const int32_t* nonneg;      /* K values 0 | 1 (NULL = 0) */
+  const double* l1weights;    /* n l1 weights w_j >= 0 shared by all fits (NULL = 1); admm_l1class_set_l1weights
+                                 replaces them */
+  admm_comm* comm;            /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_l1class_desc;
+
+typedef struct admm_l1class_options {
+  int32_t struct_size;   /* sizeof(admm_l1class_options) */
+  int32_t maxiters;      /* default 1000 */
+  double rho;            /* default 1.0; any value > 0: the factor does not depend on it */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations between host polls of "every fit has stopped" (0 = auto: 8; 64 with domaxiters) */
+  int32_t nodualerror;   /* default 0: admm.m's rule on both residuals; 1: stop on pnorm < perr alone */
+  const double* x0;      /* accepted and never read (see above) */
+  const double* z0;      /* (m + n) x K host matrix, z1 above z2 (NULL = zeros) */
+  const double* u0;      /* (m + n) x K */
+} admm_l1class_options;
+
+typedef struct admm_l1class_summary {  /* one per fit */
+  int32_t steps;              /* results.steps of that fit (admm.m:746) */
+  int32_t stopped_early;      /* 1 if the stop rule fired before maxiters (admm.m:710-713) */
+  double objopt;              /* the objective at the fit's last step, NaN if not evaluated */
+  int32_t xsolve;             /* ADMM_XSOLVE_INVERSE (the packed product) or ADMM_XSOLVE_TRSV, the same for every fit */
+  int32_t reserved0;
+} admm_l1class_summary;
+
+/* fields of admm_l1class_fetch */
+enum {
+  ADMM_L1C_F_XOPT = 1,      /* n x K */
+  ADMM_L1C_F_ZOPT = 2,      /* (m + n) x K */
+  ADMM_L1C_F_UOPT = 3,      /* (m + n) x K */
+  /* scalar histories: S x K column-major with S = the largest steps of any fit, NaN past a fit's own last step; DNORM
+   * and DERR after a run with nodualerror = 0 only, OBJEVALS after a run with objevals = 1 only */
+  ADMM_L1C_F_PNORM = 4, ADMM_L1C_F_PERR = 5, ADMM_L1C_F_OBJEVALS = 6, ADMM_L1C_F_DNORM = 7, ADMM_L1C_F_DERR = 8
+};
+
+void admm_l1class_desc_default(admm_l1class_desc* desc);
+void admm_l1class_options_default(admm_l1class_options* opts);
+int admm_l1class_create(const admm_l1class_desc* desc, admm_l1class** out);
+/* summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be called again on the same object,
+ * with another rho as well: every run starts from its own z0 / u0, and two runs from the same starts give the same bits */
+int admm_l1class_run(admm_l1class* obj, const admm_l1class_options* opts, admm_l1class_summary* summaries,
+                     double* runtime_s);
+int admm_l1class_fetch(admm_l1class* obj, int field, double* dst, size_t cap, size_t* written);
+/* admm_svm_ovr_set_cost on this object: weights = m HOST values >= 0 shared by all fits (NULL = 1), class_cost = K x 2
+ * HOST values, row k = (cost_pos, cost_neg) of fit k (NULL = 1).  ADMM_E_INVALID: a negative or non-finite weight or
+ * cost -- a refused call changes nothing. */
+int admm_l1class_set_cost(admm_l1class* obj, const double* weights, const double* class_cost);
+/* l1weights = n HOST values w_j >= 0 shared by all fits, copied at the call and held for every later run; NULL
+ * restores 1.  ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
+int admm_l1class_set_l1weights(admm_l1class* obj, const double* l1weights);
+/* fits one pass over D serves (K beyond it: ceil(K / chunk) chunks, each with its own two passes) */
+int admm_l1class_chunk(void);
+/* the last run's kernel launches, and how many of them read D (two per chunk and iteration plus one per chunk before
+ * the first; the same with and without the dual residual) */
+int admm_l1class_launches(admm_l1class* obj, int64_t* launches, int64_t* d_passes);
+/* measurement: the forward and the transposed pass alone over the object's own buffers (one chunk, every fit
+ * running, the element update included), event-timed: the medians of reps launches in microseconds and the bytes of D
+ * one pass reads.  nvec = 1 | 3: the transposed pass without / with the dual residual's vectors.  Overwrites the
+ * iterates: call it between runs. */
+int admm_l1class_pass_time(admm_l1class* obj, int32_t reps, int32_t nvec, double* forward_us, double* transposed_us,
+                           int64_t* d_bytes);
+void admm_l1class_destroy(admm_l1class* obj);
+
 /* X(:, k) = M * Y(:, k) for the columns k < K whose stop_mask[k] is 0 (stop_mask == NULL: every column) through the
  * multi-lasso's product kernel (csrc/symm.hip): M symmetric n x n (ldM >= n), only its lower triangle is read (the
  * operator builds the tile-packed triangle from it); X and Y are n x K column-major HOST matrices.  X is in/out: a masked
