@@ -335,6 +335,22 @@ class L1ClassSummary(C.Structure):  # admm_l1class_summary
 (L1C_F_XOPT, L1C_F_ZOPT, L1C_F_UOPT, L1C_F_PNORM, L1C_F_PERR, L1C_F_OBJEVALS, L1C_F_DNORM, L1C_F_DERR) = range(1, 9)
 
 
+class SparseL1ClassDesc(C.Structure):  # admm_sparse_l1class_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("D", C.POINTER(SparseDesc)), ("ELL", _dp),
+                ("nell", C.c_int32), ("device", C.c_int32), ("C", C.c_double), ("xsolve", C.c_int32),
+                ("reserved0", C.c_int32), ("loss", C.POINTER(C.c_int32)), ("lam", _dp), ("ridge", _dp),
+                ("nonneg", C.POINTER(C.c_int32)), ("l1weights", _dp), ("comm", C.c_void_p)]
+
+
+class SparseL1ClassOptions(C.Structure):  # admm_sparse_l1class_options
+    _fields_ = list(SparseRegOptions._fields_)
+
+
+class SparseL1ClassSummary(C.Structure):  # admm_sparse_l1class_summary (admm_sparse_l1class_fetch: the L1C_F_* fields)
+    _fields_ = [("steps", C.c_int32), ("stopped_early", C.c_int32), ("objopt", C.c_double), ("xsolve", C.c_int32),
+                ("reserved0", C.c_int32), ("cg_iters_total", C.c_int64), ("cg_capped_updates", C.c_int64)]
+
+
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
 STORAGE_FP64, STORAGE_COMPACT = 0, 1
@@ -512,6 +528,18 @@ _SIGNATURES = {
     "admm_l1class_pass_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                          C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "admm_l1class_destroy": (None, [C.c_void_p]),
+    "admm_sparse_l1class_desc_default": (None, [C.POINTER(SparseL1ClassDesc)]),
+    "admm_sparse_l1class_options_default": (None, [C.POINTER(SparseL1ClassOptions)]),
+    "admm_sparse_l1class_create": (C.c_int, [C.POINTER(SparseL1ClassDesc), C.POINTER(C.c_void_p)]),
+    "admm_sparse_l1class_run": (C.c_int, [C.c_void_p, C.POINTER(SparseL1ClassOptions), C.POINTER(SparseL1ClassSummary),
+                                          C.POINTER(C.c_double)]),
+    "admm_sparse_l1class_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_sparse_l1class_set_cost": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "admm_sparse_l1class_set_l1weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_sparse_l1class_chunk": (C.c_int, []),
+    "admm_sparse_l1class_kernel_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double)]),
+    "admm_sparse_l1class_destroy": (None, [C.c_void_p]),
     "admm_op_symm_packed": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.POINTER(C.c_int32), _dp]),
     "admm_op_group_soft_threshold_multi": (C.c_int, [_dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp, _dp,
                                                      C.POINTER(C.c_int32), _dp]),

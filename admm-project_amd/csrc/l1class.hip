@@ -31,8 +31,8 @@
 #include <string>
 #include <vector>
 
+#include "l1class_device.h"
 #include "multi_host.h"
-#include "penalty_device.h"
 #include "spmm.h"
 #include "svm_cost_device.h"
 #include "svm_ovr.h"
@@ -55,9 +55,6 @@ constexpr int kTrTile = 64, kTrLd = kTrTile + 1, kTrWaves = 4, kTrThreads = kTrW
 constexpr int kTrPer = kTrTile / kTrWaves;  // columns a wave loads = rows a wave sums, per block of D
 constexpr int kTrTarget = 1024;             // workgroups the row split aims at
 
-// sums of the forward pass over m, and of the element kernel over n (admm.m:621-654 over the stacked vector)
-enum L1cMSlot : int32_t { LM_R2 = 0, LM_AX2 = 1, LM_Z2 = 2, LM_LOSS = 3, LM_COUNT = 4 };
-enum L1cNSlot : int32_t { LN_R2 = 0, LN_X2 = 1, LN_Z2 = 2, LN_DZ2 = 3, LN_DU2 = 4, LN_PEN = 5, LN_COUNT = 6 };
 constexpr int kFinThreads = 512;  // multi_slot_totals: 32 lanes per slot, LM_COUNT + LN_COUNT slots
 static_assert((LM_COUNT + LN_COUNT) * 32 <= kFinThreads, "one 32-lane group per slot");
 
@@ -100,17 +97,6 @@ struct L1cElemArgs {
   double* part;         // [fit][LN_COUNT][kMultiMaxWg]
   int32_t K, Kp, dual, objevals;
   double rho;
-};
-
-struct L1cFinArgs {
-  const double *mpart, *npart;
-  int64_t m, n;
-  int32_t K, nwg_m, nwg_n, dual;
-  MultiRec* rec;
-  double *pnorm, *perr, *dnorm, *derr, *objv;  // [K][hist_ld]
-  int64_t hist_ld;
-  double rho, C, abstol, reltol;
-  int32_t domaxiters, objevals, maxiters;
 };
 
 // bit c: fit c0 + c exists and is still running
@@ -330,30 +316,7 @@ __global__ __launch_bounds__(kBlock) void l1c_elem_kernel(L1cElemArgs a) {
 #pragma unroll
   for (int q = 0; q < LN_COUNT; ++q) acc[q] = 0.0;
   for (int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + tid; j < a.n; j += static_cast<int64_t>(gridDim.x) * kBlock) {
-    const int64_t e = base + j * KC;
-    const double zp = a.Z2[e], uo = a.U2[e];
-    if constexpr (INIT) {
-      a.Y[e] = g1[j] + ((0.0 + zp) - uo);
-    } else {
-      const double xv = a.X[e];
-      const double wi = penalty_weight(pen, j);
-      const double zn = pen.kappa * penalty_elem(xv + uo, pen.tau * wi, pen.nonneg);
-      const double rr = xv - zn;
-      const double un = uo + rr;
-      acc[LN_R2] += rr * rr;
-      acc[LN_X2] += xv * xv;
-      acc[LN_Z2] += zn * zn;
-      if (a.dual) {
-        const double dz = g2[j] + (zn - zp);  // At(z - zprev) = D'(z1 - z1prev) + (z2 - z2prev)
-        const double du = g3[j] + un;         // At(u)
-        acc[LN_DZ2] += dz * dz;
-        acc[LN_DU2] += du * du;
-      }
-      if (a.objevals) acc[LN_PEN] += penalty_obj_elem(pen, wi, zn);
-      a.Z2[e] = zn;
-      a.U2[e] = un;
-      a.Y[e] = g1[j] + (zn - un);
-    }
+    l1c_elem_update<INIT>(pen, a.X, a.Z2, a.U2, a.Y, base + j * KC, j, g1, g2, g3, j, a.dual, a.objevals, acc);
   }
   if (INIT) return;
 #pragma unroll
@@ -417,6 +380,10 @@ __global__ __launch_bounds__(kBlock) void l1c_scatter_kernel(const double* __res
 }
 
 }  // namespace
+
+void launch_l1c_fin(const L1cFinArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(l1c_fin_kernel, dim3(static_cast<unsigned>(a.K)), dim3(kFinThreads), 0, stream, a);
+}
 
 }  // namespace admm
 
@@ -719,32 +686,11 @@ int admm_l1class_create(const admm_l1class_desc* desc, admm_l1class** out) {
                                 "fit (" + std::to_string(desc->K) + ")");
   if (!desc->lambda) return fail(ADMM_E_INVALID, "the l1 classifier needs lambda (K values)");
   if (!finite_pos(desc->C)) return fail(ADMM_E_INVALID, "desc.C must be positive and finite");
-  std::vector<double> ph(static_cast<size_t>(2) * desc->K, 0.0);
-  std::vector<int32_t> nh(static_cast<size_t>(desc->K), 0);
-  for (int32_t k = 0; k < desc->K; ++k) {
-    const std::string who = "fit " + std::to_string(k) + ": ";
-    const int32_t loss = desc->loss ? desc->loss[k] : ADMM_LOSS_LOGISTIC;
-    if (loss == ADMM_LOSS_01 || loss == ADMM_LOSS_HINGE_OBJ01)
-      return fail(ADMM_E_INVALID, who + "the 0-1 loss is not convex and has no lambda_max: the l1 classifier takes "
-                                        "hinge, sqhinge or logistic");
-    if (loss != ADMM_LOSS_HINGE && loss != ADMM_LOSS_SQHINGE && loss != ADMM_LOSS_LOGISTIC)
-      return fail(ADMM_E_INVALID, who + "unknown loss (ADMM_LOSS_HINGE, _SQHINGE or _LOGISTIC)");
-    ph[2 * k] = desc->lambda[k];
-    if (!finite_nonneg(ph[2 * k])) return fail(ADMM_E_INVALID, who + "lambda is negative or not finite");
-    if (desc->ridge) ph[2 * k + 1] = desc->ridge[k];
-    if (!finite_nonneg(ph[2 * k + 1])) return fail(ADMM_E_INVALID, who + "ridge is negative or not finite");
-    if (desc->nonneg) nh[k] = desc->nonneg[k];
-    if (nh[k] != 0 && nh[k] != 1) return fail(ADMM_E_INVALID, who + "nonneg must be 0 or 1");
-  }
-  const int64_t mk = desc->m * static_cast<int64_t>(desc->nell);
-  for (int64_t i = 0; i < mk; ++i)
-    if (desc->ELL[i] != 1.0 && desc->ELL[i] != -1.0)
-      return fail(ADMM_E_INVALID, "label " + std::to_string(i % desc->m) + " of column " + std::to_string(i / desc->m) +
-                                      " is neither +1 nor -1");
-  if (desc->l1weights)
-    for (int64_t i = 0; i < desc->n; ++i)
-      if (!finite_nonneg(desc->l1weights[i]))
-        return fail(ADMM_E_INVALID, "penalty: weight " + std::to_string(i) + " is negative or not finite");
+  std::vector<double> ph;
+  std::vector<int32_t> nh, lh;
+  ADMM_TRY(check_l1class_fits(desc->K, desc->loss, desc->lambda, desc->ridge, desc->nonneg, &lh, &ph, &nh));
+  ADMM_TRY(check_labels(desc->ELL, desc->m, desc->nell));
+  ADMM_TRY(check_l1_weights(desc->l1weights, desc->n));
   if (desc->xsolve != ADMM_XSOLVE_AUTO && desc->xsolve != ADMM_XSOLVE_INVERSE && desc->xsolve != ADMM_XSOLVE_TRSV)
     return fail(ADMM_E_UNSUPPORTED, std::string("the l1 classifier applies the cached factor (xsolve = auto, inverse or "
                                                 "trsv)") + kPerFit);
@@ -833,7 +779,7 @@ int admm_l1class_run(admm_l1class* o, const admm_l1class_options* opts, admm_l1c
     for (int32_t ch = 0; ch < o->chunks; ++ch) l1c_launch_transposed(o, tr, ch, nv);
     l1c_launch_gsum(o, nv);
     hipLaunchKernelGGL(l1c_elem_kernel<false>, egrid, dim3(kBlock), 0, o->stream, ea);
-    hipLaunchKernelGGL(l1c_fin_kernel, dim3(static_cast<unsigned>(K)), dim3(kFinThreads), 0, o->stream, fa);
+    launch_l1c_fin(fa, o->stream);
     launches += 2 * o->chunks + 3;
     d_passes += 2 * o->chunks;
     if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
@@ -855,10 +801,7 @@ int admm_l1class_set_cost(admm_l1class* o, const double* weights, const double* 
 
 int admm_l1class_set_l1weights(admm_l1class* o, const double* l1weights) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
-  if (l1weights)  // (the message of the create-time check; a refused call changes nothing)
-    for (int64_t i = 0; i < o->n; ++i)
-      if (!finite_nonneg(l1weights[i]))
-        return fail(ADMM_E_INVALID, "penalty: weight " + std::to_string(i) + " is negative or not finite");
+  ADMM_TRY(check_l1_weights(l1weights, o->n));  // (the message of the create-time check; a refused call changes nothing)
   return set_shared_weights(*o, o->n, l1weights, &o->LW);
 }
 

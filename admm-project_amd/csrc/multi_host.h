@@ -151,6 +151,17 @@ std::vector<int32_t> svm_cost_chunks(int32_t K, int chunk, bool weights, const s
 int set_svm_cost(MultiHost& h, int64_t m, const double* weights, const double* class_cost, double** W, double* CC,
                  std::vector<double>* cost_host);
 
+// ---- the classifier pair (l1class.hip, sparse_l1class.hip): the create-time checks of the fields both descs carry, each
+// refusal ADMM_E_INVALID with the fit, the label or the index named
+// per fit the loss (hinge, sqhinge or logistic; null = logistic), lambda, ridge (null = 0) and nonneg (null = 0):
+// lh[k] the loss, ph[2k ..] = (lambda, mu), nh[k] = nonneg
+int check_l1class_fits(int32_t K, const int32_t* loss, const double* lambda, const double* ridge, const int32_t* nonneg,
+                       std::vector<int32_t>* lh, std::vector<double>* ph, std::vector<int32_t>* nh);
+// "label <row> of column <col> is neither +1 nor -1"
+int check_labels(const double* ELL, int64_t m, int32_t nell);
+// "penalty: weight <i> is negative or not finite" (null passes)
+int check_l1_weights(const double* l1weights, int64_t n);
+
 // ---- the dense pair: D and the factor of D'D belong to an ordinary engine that never runs
 struct DenseMulti : MultiHost {
   admm_engine* eng = nullptr;  // stream = eng->stream

@@ -178,6 +178,48 @@ int check_svm_losses(int32_t K, const int32_t* loss) {
   return ADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ the classifier pair
+int check_l1class_fits(int32_t K, const int32_t* loss, const double* lambda, const double* ridge, const int32_t* nonneg,
+                       std::vector<int32_t>* lh, std::vector<double>* ph, std::vector<int32_t>* nh) {
+  lh->assign(static_cast<size_t>(K), ADMM_LOSS_LOGISTIC);
+  ph->assign(static_cast<size_t>(2) * K, 0.0);
+  nh->assign(static_cast<size_t>(K), 0);
+  for (int32_t k = 0; k < K; ++k) {
+    const std::string who = "fit " + std::to_string(k) + ": ";
+    if (loss) (*lh)[k] = loss[k];
+    const int32_t l = (*lh)[k];
+    if (l == ADMM_LOSS_01 || l == ADMM_LOSS_HINGE_OBJ01)
+      return fail(ADMM_E_INVALID, who + "the 0-1 loss is not convex and has no lambda_max: the l1 classifier takes "
+                                        "hinge, sqhinge or logistic");
+    if (l != ADMM_LOSS_HINGE && l != ADMM_LOSS_SQHINGE && l != ADMM_LOSS_LOGISTIC)
+      return fail(ADMM_E_INVALID, who + "unknown loss (ADMM_LOSS_HINGE, _SQHINGE or _LOGISTIC)");
+    (*ph)[2 * k] = lambda[k];
+    if (!finite_nonneg((*ph)[2 * k])) return fail(ADMM_E_INVALID, who + "lambda is negative or not finite");
+    if (ridge) (*ph)[2 * k + 1] = ridge[k];
+    if (!finite_nonneg((*ph)[2 * k + 1])) return fail(ADMM_E_INVALID, who + "ridge is negative or not finite");
+    if (nonneg) (*nh)[k] = nonneg[k];
+    if ((*nh)[k] != 0 && (*nh)[k] != 1) return fail(ADMM_E_INVALID, who + "nonneg must be 0 or 1");
+  }
+  return ADMM_OK;
+}
+
+int check_labels(const double* ELL, int64_t m, int32_t nell) {
+  const int64_t mk = m * static_cast<int64_t>(nell);
+  for (int64_t i = 0; i < mk; ++i)
+    if (ELL[i] != 1.0 && ELL[i] != -1.0)
+      return fail(ADMM_E_INVALID, "label " + std::to_string(i % m) + " of column " + std::to_string(i / m) +
+                                      " is neither +1 nor -1");
+  return ADMM_OK;
+}
+
+int check_l1_weights(const double* l1weights, int64_t n) {
+  if (l1weights)
+    for (int64_t i = 0; i < n; ++i)
+      if (!finite_nonneg(l1weights[i]))
+        return fail(ADMM_E_INVALID, "penalty: weight " + std::to_string(i) + " is negative or not finite");
+  return ADMM_OK;
+}
+
 std::vector<int32_t> svm_cost_chunks(int32_t K, int chunk, bool weights, const std::vector<int32_t>& loss,
                                      const std::vector<double>& cost) {
   std::vector<int32_t> cc(static_cast<size_t>((K + chunk - 1) / chunk), 0);

@@ -1,0 +1,478 @@
+// sparse_l1class.hip -- sparse linear classifiers on a SPARSE design matrix, K fits at once over one D:
+// l1class.hip's iteration (q42: the lasso's penalty family on the linear SVM's losses, plain ADMM with A = [D; I_n],
+// B = -1, c = 0, z = [z1 (m); z2 (n)], stopcond 'standard') with the one difference of the sparse objects, the x-update:
+//   x  = (D'D + I)^-1 y,  y = D'(z1 - u1) + (z2 - u2)     spmm_cg.hip's lock-step CG with the shift 1, whatever rho is:
+//                                                          nothing n x n, positive definite for every D
+//   z1 = prox of (C*c/rho)*phi at (D x + u1)              svm_cost_device.h
+//   z2 = kappa*penalty_elem(x + u2, (lambda/rho)*w)       l1class_device.h: the dense object's element update
+//   u += A x - z
+// The first solve of a run starts from 0 and every later one from the previous x.  Every multi-vector, of length m as of
+// length n, has spmm.h's layout [chunks][len][kSpmmChunk].  Per iteration, every launch for all K fits at once
+// (blockIdx.y = chunk of kSpmmChunk fits):
+//   SpmmCg::solve                 two SpMM and four small launches per inner iteration
+//   T = D X                       one SpMM
+//   sl1c_row_kernel               over m: z1, u1, T1 = z1 - u1 (and z1 - z1prev with the dual residual), the m-block's sums
+//   G = D'T1                      one SpMM; with the dual residual two more: D'(z1 - z1prev) and D'u1
+//   sl1c_elem_kernel              over n: z2, u2, the next Y = G + (z2 - u2), the n-block's sums, the dual residual's two
+//                                 norms, the penalty
+//   l1c_fin_kernel                l1class.hip's, per fit: pnorm, perr, dnorm, derr, the objective, the stop decision
+// A fit whose stop flag is set is FROZEN, and a fit whose solve is done is masked until the next solve: every kernel and
+// every product skips it.  No atomics; every sum runs in an order the sizes fix: two runs give the same bits, and a fit
+// gets the same numbers wherever it lands.
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "l1class_device.h"
+#include "multi_host.h"
+#include "spmm_cg.h"
+#include "svm_cost_device.h"
+
+namespace admm {
+
+namespace {
+
+constexpr int KC = kSpmmChunk;
+
+struct Sl1cRowArgs {
+  int64_t m;
+  const double* AX;    // D X
+  double *Z1, *U1;     // multi-vectors of len m
+  double *T1, *DZ1;    // z1 - u1; z1 - z1prev (null without the dual residual)
+  const double* ELL;   // a multi-vector of len m, or column 0 of ONE chunk (ell_shared)
+  const double* W;     // m weights or null
+  const double* CC;    // K x 2 class costs
+  const int32_t* loss;
+  const MultiRec* rec;
+  double* part;        // [fit][LM_COUNT][kScgMaxWg]
+  int32_t K, ell_shared, objevals;
+  double rho, C;
+};
+
+struct Sl1cElemArgs {
+  int64_t n;
+  const double* X;      // multi-vectors of len n
+  double *Z2, *U2, *Y;
+  const double *G, *GDZ, *GU;  // D'(z1 - u1), D'(z1 - z1prev), D'u1
+  const double* W;      // n l1 weights or null
+  const double* par;    // K x 2: (lambda, mu)
+  const int32_t* nonneg;
+  const MultiRec* rec;
+  double* part;         // [fit][LN_COUNT][kScgMaxWg]
+  int32_t K, dual, objevals;
+  double rho;
+};
+
+// thread t: row t / KC of a row block, fit t % KC of the chunk (scg_lane).  INIT: only T1 = z1 - u1 of the start vectors
+template <bool INIT>
+__global__ __launch_bounds__(kScgBlock) void sl1c_row_kernel(Sl1cRowArgs a) {
+  __shared__ double lds[LM_COUNT * kScgBlock];
+  const ScgLane l = scg_lane(a.rec, a.K);
+  if (!__syncthreads_or(l.run)) return;
+  const int64_t base = static_cast<int64_t>(blockIdx.y) * a.m * KC;
+  double acc[LM_COUNT];
+#pragma unroll
+  for (int q = 0; q < LM_COUNT; ++q) acc[q] = 0.0;
+  const int fit = l.run ? l.fit : 0;
+  const SvmCostArgs ks{nullptr, a.CC[2 * fit], a.CC[2 * fit + 1], a.C, a.rho, a.loss[fit], a.objevals};
+  const int64_t nrb = (a.m + kScgRows - 1) / kScgRows;
+  for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int64_t i = rb * kScgRows + l.r;
+    if (!l.run || i >= a.m) continue;
+    const int64_t e = base + i * KC + l.c;
+    const double zp = a.Z1[e], uo = a.U1[e];
+    if constexpr (INIT) {
+      a.T1[e] = (0.0 + zp) - uo;
+    } else {
+      const double ax = a.AX[e];
+      const double el = a.ell_shared ? a.ELL[i * KC] : a.ELL[e];
+      const double wv = a.W ? a.W[i] : 1.0;
+      const double ci = svm_cost_of(ks, wv, el);
+      const double zn = svm_cost_prox_elem<true>(ks, ci, el, ax + uo);
+      const double rr = ax - zn;      // A x + B z - c
+      const double un = uo + rr;      // admm.m:542-550
+      acc[LM_R2] += rr * rr;
+      acc[LM_AX2] += ax * ax;
+      acc[LM_Z2] += zn * zn;
+      if (a.objevals) acc[LM_LOSS] += svm_cost_obj_elem<true>(ks, ci, el * ax);
+      a.Z1[e] = zn;
+      a.U1[e] = un;
+      a.T1[e] = zn - un;
+      if (a.DZ1) a.DZ1[e] = zn - zp;
+    }
+  }
+  if (INIT) return;
+  scg_sums<LM_COUNT>(acc, lds, a.part, LM_COUNT, 0);
+}
+
+// the same thread layout over n.  INIT: only Y = D'(z1 - u1) + (z2 - u2) of the start vectors
+template <bool INIT>
+__global__ __launch_bounds__(kScgBlock) void sl1c_elem_kernel(Sl1cElemArgs a) {
+  __shared__ double lds[LN_COUNT * kScgBlock];
+  const ScgLane l = scg_lane(a.rec, a.K);
+  if (!__syncthreads_or(l.run)) return;
+  const int64_t base = static_cast<int64_t>(blockIdx.y) * a.n * KC;
+  double acc[LN_COUNT];
+#pragma unroll
+  for (int q = 0; q < LN_COUNT; ++q) acc[q] = 0.0;
+  const int fit = l.run ? l.fit : 0;
+  const double lam = a.par[2 * fit], mu = a.par[2 * fit + 1];
+  // engine_run_general.hip's own expressions for the family's numbers
+  const PenaltyArgs pen{a.W, lam / a.rho, a.rho / (a.rho + mu), lam, 0.0, 0.5 * mu, a.nonneg[fit]};
+  const int64_t nrb = (a.n + kScgRows - 1) / kScgRows;
+  for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int64_t j = rb * kScgRows + l.r;
+    if (!l.run || j >= a.n) continue;
+    const int64_t e = base + j * KC + l.c;
+    l1c_elem_update<INIT>(pen, a.X, a.Z2, a.U2, a.Y, e, j, a.G, a.GDZ, a.GU, e, a.dual, a.objevals, acc);
+  }
+  if (INIT) return;
+  scg_sums<LN_COUNT>(acc, lds, a.part, LN_COUNT, 0);
+}
+
+void launch_sl1c_row(const Sl1cRowArgs& a, bool init, hipStream_t stream) {
+  const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
+  if (init) hipLaunchKernelGGL(sl1c_row_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
+  else hipLaunchKernelGGL(sl1c_row_kernel<false>, grid, dim3(kScgBlock), 0, stream, a);
+}
+
+void launch_sl1c_elem(const Sl1cElemArgs& a, bool init, hipStream_t stream) {
+  const dim3 grid(scg_vec_workgroups(a.n), static_cast<unsigned>(spmm_chunks(a.K)));
+  if (init) hipLaunchKernelGGL(sl1c_elem_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
+  else hipLaunchKernelGGL(sl1c_elem_kernel<false>, grid, dim3(kScgBlock), 0, stream, a);
+}
+
+}  // namespace
+
+}  // namespace admm
+
+// ---------------------------------------------------------------------------------------------------------- the object
+struct admm_sparse_l1class : admm::MultiHost {
+  admm::SpmmCg cg;  // D, the x-update and its multi-vectors
+  int64_t m = 0, n = 0;
+  int32_t nwg_m = 0, nwg_n = 0, ell_shared = 0;
+  double C = 1.0;
+  double *Z1 = nullptr, *U1 = nullptr, *T1 = nullptr, *DZ1 = nullptr, *ELL = nullptr;  // len m (ELL: or one chunk)
+  double *Z2 = nullptr, *U2 = nullptr, *G = nullptr, *GDZ = nullptr, *GU = nullptr;    // len n
+  double *mpart = nullptr, *npart = nullptr;
+  double *W = nullptr, *CC = nullptr, *LW = nullptr, *par = nullptr;
+  int32_t *loss = nullptr, *nonneg = nullptr;
+  std::vector<double> cost_host;
+  double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
+  admm_sparse_l1class_options last{};
+};
+
+namespace {
+
+using namespace admm;
+
+const char* kWho = "the sparse l1 classifier";
+
+int sl1c_setup(admm_sparse_l1class* o, const admm_sparse_l1class_desc* desc, const std::vector<double>& ph,
+               const std::vector<int32_t>& nh, const std::vector<int32_t>& lh) {
+  const int32_t K = desc->K;
+  o->K = K;
+  ADMM_TRY(o->cg.build(o, desc->device, desc->D));
+  const int64_t m = o->cg.m, n = o->cg.n;
+  o->m = m;
+  o->n = n;
+  o->C = desc->C;
+  o->nwg_m = scg_vec_workgroups(m);
+  o->nwg_n = scg_vec_workgroups(n);
+  const size_t kp = static_cast<size_t>(o->cg.chunks) * KC;
+  for (double** p : {&o->Z1, &o->U1, &o->T1, &o->DZ1}) {
+    ADMM_TRY(o->mem.alloc(p, kp * m));
+    ADMM_HIP_TRY(hipMemsetAsync(*p, 0, sizeof(double) * kp * m, o->stream));
+  }
+  for (double** p : {&o->Z2, &o->U2, &o->G, &o->GDZ, &o->GU}) {
+    ADMM_TRY(o->mem.alloc(p, kp * n));
+    ADMM_HIP_TRY(hipMemsetAsync(*p, 0, sizeof(double) * kp * n, o->stream));
+  }
+  {  // the labels in the layout of the products: the shared column is column 0 of one chunk
+    o->ell_shared = desc->nell == 1 && K > 1 ? 1 : 0;
+    const int32_t ecols = o->ell_shared ? 1 : K;
+    const size_t ep = static_cast<size_t>(spmm_chunks(ecols)) * KC;
+    ADMM_TRY(o->mem.alloc(&o->ELL, ep * m));
+    std::vector<double> hb(ep * m);
+    spmm_pack(desc->ELL, m, m, ecols, hb.data());
+    ADMM_HIP_TRY(hipMemcpyAsync(o->ELL, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, o->stream));
+    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (hb goes out of scope)
+  }
+  ADMM_TRY(o->mem.alloc(&o->mpart, kp * LM_COUNT * kScgMaxWg));
+  ADMM_HIP_TRY(hipMemsetAsync(o->mpart, 0, sizeof(double) * kp * LM_COUNT * kScgMaxWg, o->stream));
+  ADMM_TRY(o->mem.alloc(&o->npart, kp * LN_COUNT * kScgMaxWg));
+  ADMM_HIP_TRY(hipMemsetAsync(o->npart, 0, sizeof(double) * kp * LN_COUNT * kScgMaxWg, o->stream));
+  ADMM_TRY(o->mem.alloc(&o->par, static_cast<size_t>(2) * K));
+  ADMM_HIP_TRY(hipMemcpyAsync(o->par, ph.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice, o->stream));
+  ADMM_TRY(alloc_words(*o, &o->nonneg, static_cast<size_t>(K)));
+  ADMM_HIP_TRY(hipMemcpyAsync(o->nonneg, nh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
+  ADMM_TRY(alloc_words(*o, &o->loss, static_cast<size_t>(K)));
+  ADMM_HIP_TRY(hipMemcpyAsync(o->loss, lh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
+  o->cost_host.assign(static_cast<size_t>(2 * K), 1.0);
+  ADMM_TRY(o->mem.alloc(&o->CC, static_cast<size_t>(2 * K)));
+  ADMM_HIP_TRY(hipMemcpyAsync(o->CC, o->cost_host.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice, o->stream));
+  ADMM_TRY(alloc_common(*o));
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (the host vectors and the caller's buffers were read)
+  ADMM_HIP_TRY(hipGetLastError());
+  if (desc->l1weights) ADMM_TRY(set_shared_weights(*o, n, desc->l1weights, &o->LW));
+  return ADMM_OK;
+}
+
+// host (m + n) x K column-major <-> V1 (len m) above V2 (len n), both chunked multi-vectors
+int sl1c_upload_stacked(admm_sparse_l1class* o, const double* src, double* V1, double* V2) {
+  if (!src) {
+    ADMM_TRY(o->cg.upload(V1, nullptr, o->m));
+    return o->cg.upload(V2, nullptr, o->n);
+  }
+  const int64_t mn = o->m + o->n;
+  const size_t kp = static_cast<size_t>(o->cg.chunks) * KC;
+  std::vector<double> h1(kp * o->m), h2(kp * o->n);
+  spmm_pack(src, mn, o->m, o->K, h1.data());
+  spmm_pack(src + o->m, mn, o->n, o->K, h2.data());
+  ADMM_HIP_TRY(hipMemcpyAsync(V1, h1.data(), sizeof(double) * h1.size(), hipMemcpyHostToDevice, o->stream));
+  ADMM_HIP_TRY(hipMemcpyAsync(V2, h2.data(), sizeof(double) * h2.size(), hipMemcpyHostToDevice, o->stream));
+  ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (h1 and h2 go out of scope)
+  return ADMM_OK;
+}
+
+int sl1c_fetch_stacked(admm_sparse_l1class* o, const double* V1, const double* V2, double* dst, size_t cap,
+                       size_t* written) {
+  const int64_t mn = o->m + o->n;
+  const size_t need = static_cast<size_t>(mn) * o->K;
+  if (cap < need) return fail(ADMM_E_CAPACITY, "destination buffer too small");
+  const size_t kp = static_cast<size_t>(o->cg.chunks) * KC;
+  std::vector<double> h1(kp * o->m), h2(kp * o->n);
+  ADMM_HIP_TRY(hipMemcpy(h1.data(), V1, sizeof(double) * h1.size(), hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(h2.data(), V2, sizeof(double) * h2.size(), hipMemcpyDeviceToHost));
+  spmm_unpack(h1.data(), o->m, o->K, dst, mn);
+  spmm_unpack(h2.data(), o->n, o->K, dst + o->m, mn);
+  if (written) *written = need;
+  return ADMM_OK;
+}
+
+Sl1cRowArgs sl1c_row_args(const admm_sparse_l1class* o, bool dual, int32_t objevals, double rho) {
+  Sl1cRowArgs a{};
+  a.m = o->m;
+  a.AX = o->cg.T;
+  a.Z1 = o->Z1;
+  a.U1 = o->U1;
+  a.T1 = o->T1;
+  a.DZ1 = dual ? o->DZ1 : nullptr;
+  a.ELL = o->ELL;
+  a.W = o->W;
+  a.CC = o->CC;
+  a.loss = o->loss;
+  a.rec = o->rec;
+  a.part = o->mpart;
+  a.K = o->K;
+  a.ell_shared = o->ell_shared;
+  a.objevals = objevals;
+  a.rho = rho;
+  a.C = o->C;
+  return a;
+}
+
+Sl1cElemArgs sl1c_elem_args(const admm_sparse_l1class* o, bool dual, int32_t objevals, double rho) {
+  Sl1cElemArgs a{};
+  a.n = o->n;
+  a.X = o->cg.X;
+  a.Z2 = o->Z2;
+  a.U2 = o->U2;
+  a.Y = o->cg.Y;
+  a.G = o->G;
+  a.GDZ = o->GDZ;
+  a.GU = o->GU;
+  a.W = o->LW;
+  a.par = o->par;
+  a.nonneg = o->nonneg;
+  a.rec = o->rec;
+  a.part = o->npart;
+  a.K = o->K;
+  a.dual = dual ? 1 : 0;
+  a.objevals = objevals;
+  a.rho = rho;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+void admm_sparse_l1class_desc_default(admm_sparse_l1class_desc* d) {
+  if (!d) return;
+  std::memset(d, 0, sizeof(*d));
+  d->struct_size = sizeof(admm_sparse_l1class_desc);
+  d->K = 1;
+  d->nell = 1;
+  d->C = 1.0;
+  d->xsolve = ADMM_XSOLVE_AUTO;
+}
+
+void admm_sparse_l1class_options_default(admm_sparse_l1class_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = sizeof(admm_sparse_l1class_options);
+  o->maxiters = 1000;  // admm.m:66
+  o->rho = 1.0;        // admm.m:57
+  o->abstol = 1e-5;    // admm.m:71
+  o->reltol = 1e-3;    // admm.m:72
+  o->relax = 1.0;      // admm.m:60
+  o->cg_tol = 1e-12;   // admm_problem_desc_default
+  o->cg_maxit = 200;
+  o->nodualerror = 0;  // admm.m:76
+}
+
+int admm_sparse_l1class_chunk(void) { return KC; }
+
+int admm_sparse_l1class_create(const admm_sparse_l1class_desc* desc, admm_sparse_l1class** out) {
+  if (!desc || !out) return fail(ADMM_E_INVALID, "desc/out is NULL");
+  *out = nullptr;
+  if (desc->struct_size != static_cast<int32_t>(sizeof(admm_sparse_l1class_desc)))
+    return fail(ADMM_E_INVALID, "admm_sparse_l1class_desc.struct_size mismatch (ABI version skew)");
+  if (desc->K < 1) return fail(ADMM_E_INVALID, "the sparse l1 classifier needs at least one fit (K >= 1)");
+  ADMM_TRY(check_sparse_D(kWho, desc->D));
+  const int64_t m = desc->D->rows, n = desc->D->cols;
+  if (!desc->ELL) return fail(ADMM_E_INVALID, "the sparse l1 classifier needs the labels ELL (rows x nell)");
+  if (desc->nell != 1 && desc->nell != desc->K)
+    return fail(ADMM_E_INVALID, "ELL has " + std::to_string(desc->nell) + " columns: one shared label column or one per "
+                                "fit (" + std::to_string(desc->K) + ")");
+  if (!desc->lambda) return fail(ADMM_E_INVALID, "the sparse l1 classifier needs lambda (K values)");
+  if (!finite_pos(desc->C)) return fail(ADMM_E_INVALID, "desc.C must be positive and finite");
+  std::vector<double> ph;
+  std::vector<int32_t> nh, lh;
+  ADMM_TRY(check_l1class_fits(desc->K, desc->loss, desc->lambda, desc->ridge, desc->nonneg, &lh, &ph, &nh));
+  ADMM_TRY(check_labels(desc->ELL, m, desc->nell));
+  ADMM_TRY(check_l1_weights(desc->l1weights, n));
+  if (desc->xsolve != ADMM_XSOLVE_AUTO && desc->xsolve != ADMM_XSOLVE_CG)
+    return fail(ADMM_E_UNSUPPORTED, "the sparse l1 classifier runs the matrix-free x-update (xsolve = auto or cg)");
+  ADMM_TRY(check_placement(kWho, desc->comm, desc->device));
+  return create_object(out, admm_sparse_l1class_destroy,
+                       [&](admm_sparse_l1class* o) { return sl1c_setup(o, desc, ph, nh, lh); });
+}
+
+int admm_sparse_l1class_run(admm_sparse_l1class* o, const admm_sparse_l1class_options* opts,
+                            admm_sparse_l1class_summary* summaries, double* runtime_s) {
+  if (!o || !opts) return fail(ADMM_E_INVALID, "object/options is NULL");
+  if (opts->struct_size != static_cast<int32_t>(sizeof(admm_sparse_l1class_options)))
+    return fail(ADMM_E_INVALID, "admm_sparse_l1class_options.struct_size mismatch (ABI version skew)");
+  admm_sparse_l1class_options op = *opts;
+  ADMM_TRY(check_sparse_run_options("sparse l1 classifier", &op));
+  if (!finite_pos(op.rho)) return fail(ADMM_E_INVALID, "options.rho must be positive and finite");
+  const bool dual = op.nodualerror == 0;
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  const int32_t N = op.maxiters, K = o->K;
+  ADMM_TRY(resize_histories(*o, {&o->pnorm, &o->perr, &o->dnorm, &o->derr, &o->objv}, N));
+  SpmmCg& cg = o->cg;
+  ADMM_TRY(begin_run(*o));
+  ScgArgs ca{};
+  ADMM_TRY(cg.begin_run(op.cg_tol, op.cg_maxit, &ca, 1.0));  // D'D + I: the shift is 1 for every rho
+  ADMM_TRY(sl1c_upload_stacked(o, op.z0, o->Z1, o->Z2));
+  ADMM_TRY(sl1c_upload_stacked(o, op.u0, o->U1, o->U2));
+
+  const Sl1cRowArgs ra = sl1c_row_args(o, dual, op.objevals, op.rho);
+  const Sl1cElemArgs ea = sl1c_elem_args(o, dual, op.objevals, op.rho);
+  L1cFinArgs fa{};
+  fa.mpart = o->mpart;
+  fa.npart = o->npart;
+  fa.m = o->m;
+  fa.n = o->n;
+  fa.K = K;
+  fa.nwg_m = o->nwg_m;
+  fa.nwg_n = o->nwg_n;
+  fa.dual = dual ? 1 : 0;
+  fa.rec = o->rec;
+  fa.pnorm = o->pnorm;
+  fa.perr = o->perr;
+  fa.dnorm = o->dnorm;
+  fa.derr = o->derr;
+  fa.objv = o->objv;
+  fa.hist_ld = N;
+  fa.rho = op.rho;
+  fa.C = o->C;
+  fa.abstol = op.abstol;
+  fa.reltol = op.reltol;
+  fa.domaxiters = op.domaxiters;
+  fa.objevals = op.objevals;
+  fa.maxiters = N;
+  const SpmmMask run = cg.mask(false);
+
+  ADMM_TRY(begin_timing(*o));
+  launch_sl1c_row(ra, true, o->stream);                          // T1 = z1 - u1 of the start vectors
+  launch_spmm(cg.sp.t, o->T1, o->G, cg.chunks, run, o->stream);  // G = D'T1
+  launch_sl1c_elem(ea, true, o->stream);                         // y = G + (z2 - u2)
+  bool all = false;
+  for (int32_t it = 0; it < N && !all; ++it) {
+    ADMM_TRY(cg.solve(ca, it == 0));
+    launch_spmm(cg.sp.n, cg.X, cg.T, cg.chunks, run, o->stream);  // D x
+    launch_sl1c_row(ra, false, o->stream);
+    launch_spmm(cg.sp.t, o->T1, o->G, cg.chunks, run, o->stream);  // D'(z1 - u1)
+    if (dual) {
+      launch_spmm(cg.sp.t, o->DZ1, o->GDZ, cg.chunks, run, o->stream);  // D'(z1 - z1prev)
+      launch_spmm(cg.sp.t, o->U1, o->GU, cg.chunks, run, o->stream);    // D'u1
+    }
+    launch_sl1c_elem(ea, false, o->stream);
+    launch_l1c_fin(fa, o->stream);
+    if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
+  }
+  ADMM_TRY(finish_run(*o, all, "the sparse l1 classifier loop ended with fits still running", N, op.objevals != 0,
+                      o->objv, runtime_s, summaries));
+  for (int32_t c = 0; summaries && c < K; ++c) summaries[c].xsolve = ADMM_XSOLVE_CG;
+  return end_sparse_run(o, op, summaries);
+}
+
+int admm_sparse_l1class_set_cost(admm_sparse_l1class* o, const double* weights, const double* class_cost) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  return set_svm_cost(*o, o->m, weights, class_cost, &o->W, o->CC, &o->cost_host);
+}
+
+int admm_sparse_l1class_set_l1weights(admm_sparse_l1class* o, const double* l1weights) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  ADMM_TRY(check_l1_weights(l1weights, o->n));  // (the message of the create-time check; a refused call changes nothing)
+  return set_shared_weights(*o, o->n, l1weights, &o->LW);
+}
+
+int admm_sparse_l1class_kernel_time(admm_sparse_l1class* o, int32_t reps, int32_t dual, double* row_us, double* elem_us) {
+  if (!o || reps < 1) return fail(ADMM_E_INVALID, "object is NULL or reps < 1");
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  ADMM_TRY(begin_run(*o));  // every fit runs; the iterates are overwritten, as the next run's start does anyway
+  const Sl1cRowArgs ra = sl1c_row_args(o, dual != 0, 1, 1.0);
+  const Sl1cElemArgs ea = sl1c_elem_args(o, dual != 0, 1, 1.0);
+  double* outs[2] = {row_us, elem_us};
+  for (int pass = 0; pass < 2; ++pass) {
+    std::vector<float> ms(static_cast<size_t>(reps));
+    for (int32_t i = -1; i < reps; ++i) {  // (i = -1: warm-up)
+      ADMM_HIP_TRY(hipEventRecord(o->ev0, o->stream));
+      if (pass == 0) launch_sl1c_row(ra, false, o->stream);
+      else launch_sl1c_elem(ea, false, o->stream);
+      ADMM_HIP_TRY(hipEventRecord(o->ev1, o->stream));
+      ADMM_HIP_TRY(hipEventSynchronize(o->ev1));
+      if (i >= 0) ADMM_HIP_TRY(hipEventElapsedTime(&ms[i], o->ev0, o->ev1));
+    }
+    std::sort(ms.begin(), ms.end());
+    if (outs[pass]) *outs[pass] = 1e3 * static_cast<double>(ms[reps / 2]);
+  }
+  ADMM_HIP_TRY(hipGetLastError());
+  return ADMM_OK;
+}
+
+int admm_sparse_l1class_fetch(admm_sparse_l1class* o, int field, double* dst, size_t cap, size_t* written) {
+  ADMM_TRY(fetch_head(o, dst));
+  switch (field) {
+    case ADMM_L1C_F_XOPT: return o->cg.fetch_matrix(o->cg.X, o->n, dst, cap, written);
+    case ADMM_L1C_F_ZOPT: return sl1c_fetch_stacked(o, o->Z1, o->Z2, dst, cap, written);
+    case ADMM_L1C_F_UOPT: return sl1c_fetch_stacked(o, o->U1, o->U2, dst, cap, written);
+    case ADMM_L1C_F_PNORM: return fetch_history(*o, o->pnorm, dst, cap, written);
+    case ADMM_L1C_F_PERR: return fetch_history(*o, o->perr, dst, cap, written);
+    case ADMM_L1C_F_OBJEVALS: return fetch_kept_history(*o, o->last.objevals, kNoObjevals, o->objv, dst, cap, written);
+    case ADMM_L1C_F_DNORM: return fetch_kept_history(*o, !o->last.nodualerror, kNoDual, o->dnorm, dst, cap, written);
+    case ADMM_L1C_F_DERR: return fetch_kept_history(*o, !o->last.nodualerror, kNoDual, o->derr, dst, cap, written);
+    default: return fail(ADMM_E_INVALID, "unknown field of the sparse l1 classifier");
+  }
+}
+
+void admm_sparse_l1class_destroy(admm_sparse_l1class* o) { destroy_sparse(o); }
+
+}  // extern "C"

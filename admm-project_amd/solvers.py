@@ -526,7 +526,8 @@ def l1classifier_lambda_max(D, ell, options=None):
     C*|phi'(0)|*max over w_j > 0 of |sum_i c_i*ell_i*D_ij| / w_j, with phi'(0) = -1/2 (logistic), -1 (hinge), -2
     (sqhinge).  With an unpenalised column (w_j = 0) the all-zero model is in general not optimal at this lambda."""
     options = _options(options, "Argument options is not a struct!", optional=True)
-    D = _matrix(D, "D")
+    from ._lib import is_sparse
+    D = _matrix(D, "D", sparse_ok=is_sparse(D))  # (a sparse D: the one product below is SciPy's)
     ELL = _l1c_labels(ell, D.shape[0], 1)
     loss = options.get("lossfunction", "logistic")
     from .l1class import loss_code
@@ -537,7 +538,7 @@ def l1classifier_lambda_max(D, ell, options=None):
     if cc is not None:
         c = c * np.where(e > 0, cc[0][0], cc[0][1])
     pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
-    g = np.abs(D.T @ (c * e))
+    g = np.abs(np.asarray(D.T @ (c * e), dtype=np.float64)).reshape(-1)
     if pw is not None:
         live = pw["l1weights"] > 0
         g = g[live] / pw["l1weights"][live]
@@ -546,12 +547,12 @@ def l1classifier_lambda_max(D, ell, options=None):
 
 
 def l1classifier_multi(D, ELL, lams, options=None):
-    """results = l1classifier_multi(D, ELL, lams, options): K sparse linear classifiers over ONE dense D in one run
-     -- a regularisation path, a grid, several label columns or losses:
+    """results = l1classifier_multi(D, ELL, lams, options): K sparse linear classifiers over ONE D, dense
+    or scipy.sparse (q43), in one run -- a regularisation path, a grid, several label columns or losses:
 
         minimise C*sum_i c_ik*phi_k(ell_ik*(D*x)_i) + lambda_k*sum_j w_j*|x_j| + ridge_k/2*||x||^2   (x >= 0 where nonnegative_k)
 
-    ``D``: dense, any shape (m < n included).  ``ELL``: labels +-1, a vector or m x 1 (shared by all fits) or m x K.
+    ``D``: dense or scipy.sparse, any shape (m < n included).  ``ELL``: labels +-1, a vector or m x 1 (shared by all fits) or m x K.
     ``lams``: the K values lambda_k >= 0.  ``options['lossfunction']`` ('logistic' by default, 'hinge', 'sqhinge') is one
     string or K of them; ``ridge`` and ``nonnegative`` are scalars or K values; ``l1weights`` (n values >= 0; 0 leaves a
     coefficient unpenalised -- an intercept is a column of ones with weight 0), ``weights`` (m values >= 0) and ``C``
@@ -562,16 +563,23 @@ def l1classifier_multi(D, ELL, lams, options=None):
 
     Returns xopt (n x K), zopt, uopt ((m + n) x K), steps (K), pnorm / perr (max(steps) x K, NaN past a fit's last
     step), dnorm / derr unless nodualerror = 1, objevals with options['objevals'], objopt, runtime, solverruntime, chunk,
-    lams and xsolve.  fast, convtest, relax, adaptive, comm, parallel, a stopcond other than 'standard', the loss '01'
-    and a scipy.sparse D are refused by name."""
+    lams and xsolve.  fast, convtest, relax, adaptive, comm, parallel, a stopcond other than 'standard' and the loss '01'
+    are refused by name.
+
+    On a scipy.sparse D every x-update is conjugate gradients on (D'D + I) x = D'(z1 - u1) + (z2 - u2), all fits in
+    lock-step over one sparse product: nothing n x n is stored.  ``xsolve`` is 'auto' or 'cg' ('inverse' and 'trsv' are
+    refused by name), ``cg_tol`` / ``cg_maxit`` (1e-12 / 200) bound a solve, and the result reads ``xsolve = 'cg'`` and
+    adds ``nnz``, ``cg_iters_total`` and ``cg_capped_updates`` (K values each)."""
     options = _options(options, "Argument options is not a struct!", optional=True)
     t0 = time.perf_counter()
     from ._lib import is_sparse
     from .l1class import L1Classifier, loss_code
-    if is_sparse(D):
-        raise ValueError("l1classifier_multi runs on a dense D: the sparse form of this iteration is not built")
-    _dense_multi_refusals(options, "l1classifier_multi")
-    D = _matrix(D, "D")
+    sparse = is_sparse(D)  # DESIGN.md q43: the matrix-free object, no limit on n
+    if sparse:
+        _sparse_refusals(options, "l1classifier_multi", stopcond=True)
+    else:
+        _dense_multi_refusals(options, "l1classifier_multi")
+    D = _matrix(D, "D", sparse_ok=sparse)
     m, n = D.shape
     lam = np.asarray(lams, dtype=np.float64).reshape(-1)
     K = int(lam.size)
@@ -597,11 +605,16 @@ def l1classifier_multi(D, ELL, lams, options=None):
         is_positive_real(options["rho"], "options.rho")
     weights, class_cost = _l1c_costs(options, ELL, K)
     starts = _start_matrices(options, dict(x0=n, z0=m + n, u0=m + n), K, "fit")
-    obj = L1Classifier(D, ELL, lam, losses, ridge, nonneg, w, C=Cv, xsolve=options.get("xsolve", "auto"),
-                       device=int(options.get("device", 0)))
+    if sparse:
+        from .sparse_l1class import SparseL1Classifier
+        obj = SparseL1Classifier(D, ELL, lam, losses, ridge, nonneg, w, C=Cv, xsolve=options.get("xsolve", "auto"),
+                                 device=int(options.get("device", 0)))
+    else:
+        obj = L1Classifier(D, ELL, lam, losses, ridge, nonneg, w, C=Cv, xsolve=options.get("xsolve", "auto"),
+                           device=int(options.get("device", 0)))
     res = _run_and_close(obj, _cost_setter(weights, class_cost), check_every=int(options.get("check_every", 0)),
                          z0=starts.get("z0"), u0=starts.get("u0"), nodualerror=int(bool(options.get("nodualerror", 0))),
-                         **_pick(options, _LOOP_KEYS))
+                         **_pick(options, _LOOP_KEYS + (_CG_KEYS if sparse else ())))
     res["lams"] = lam.copy()
     res["solverruntime"] = time.perf_counter() - t0
     return res
@@ -614,7 +627,8 @@ def l1classifier(D, ell, lam, options=None):
     options = _options(options, "Argument options is not a struct!", optional=True)
     if not np.isscalar(lam) or not np.isreal(lam):
         raise ValueError("Argument lam is not a nonnegative real number!")
-    D = _matrix(D, "D")
+    from ._lib import is_sparse
+    D = _matrix(D, "D", sparse_ok=is_sparse(D))
     m, n = D.shape
     loss = options.get("lossfunction", "logistic")
     if not isinstance(loss, str):
@@ -626,6 +640,9 @@ def l1classifier(D, ell, lam, options=None):
         if key in res:
             res[key] = np.ascontiguousarray(res[key][:, 0])
     res.update(steps=int(res["steps"][0]), objopt=float(res["objopt"][0]), lam=float(res.pop("lams")[0]))
+    for key in ("cg_iters_total", "cg_capped_updates"):  # (a sparse D)
+        if key in res:
+            res[key] = int(res[key][0])
     return res
 
 
@@ -638,7 +655,8 @@ def l1classifier_path(D, ell, lams=None, options=None):
     may not be the all-zero model.  Returns l1classifier_multi's fields plus ``df``, the nonzeros of each column of the
     coefficient block of zopt."""
     options = _options(options, "Argument options is not a struct!", optional=True)
-    D = _matrix(D, "D")
+    from ._lib import is_sparse
+    D = _matrix(D, "D", sparse_ok=is_sparse(D))
     e = _colvec(ell, "ell")
     if lams is None or np.isscalar(lams):
         if lams is not None:

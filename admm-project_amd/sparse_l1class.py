@@ -1,0 +1,90 @@
+"""Python owner of one ``admm_sparse_l1class`` handle (include/admm_engine.h): K sparse linear classifiers
+over one SPARSE design matrix -- the l1 / elastic-net penalty of the lasso family on the hinge, squared-hinge or logistic
+loss -- every fit a plain-ADMM run with A = [D; I] whose x-update is conjugate gradients on (D'D + I) x = D'(z1 - u1) +
+(z2 - u2), all fits in lock-step over one sparse product (csrc/sparse_l1class.hip)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .engine import _MultiOwner, _set_svm_cost, _weights
+from .l1class import loss_code
+
+_XSOLVE = dict(auto=L.XSOLVE_AUTO, cg=L.XSOLVE_CG)
+
+
+class SparseL1Classifier(_MultiOwner):
+    """``SparseL1Classifier(D, ELL, lams, losses, ridge, nonnegative, l1weights, C=, xsolve=)``: ``D`` any
+    ``scipy.sparse`` matrix or array (converted to canonical CSC); ``ELL`` is m x 1 (labels +-1 shared by all fits) or
+    m x K; ``lams`` holds the K values lambda_k >= 0; ``losses`` K names (or None: logistic); ``ridge`` (mu_k >= 0) and
+    ``nonnegative`` (0 | 1) K values each, or None for 0; ``l1weights`` n values w_j >= 0 shared by all fits, or None
+    for 1; ``xsolve`` 'auto' or 'cg'."""
+
+    _abi, _unit, _cg = "admm_sparse_l1class", "fit", True
+    _types = (L.SparseL1ClassDesc, L.SparseL1ClassOptions, L.SparseL1ClassSummary)
+    _rows = dict(x0="n", z0="mn", u0="mn")  # z and u stack the m rows of D above the n coefficients
+    _fields = dict(xopt=(L.L1C_F_XOPT, "n"), zopt=(L.L1C_F_ZOPT, "mn"), uopt=(L.L1C_F_UOPT, "mn"),
+                   pnorm=(L.L1C_F_PNORM, "hist"), perr=(L.L1C_F_PERR, "hist"), dnorm=(L.L1C_F_DNORM, "dual"),
+                   derr=(L.L1C_F_DERR, "dual"), objevals=(L.L1C_F_OBJEVALS, "objevals"))
+
+    def __init__(self, D, ELL, lams, losses=None, ridge=None, nonnegative=None, l1weights=None, *, C=1.0, xsolve="auto",
+                 device=0):
+        d = self._desc()
+        keep = []
+        sd, ELL = self._sparse_D(D, ELL, keep, "The number of rows in argument D do not match size of ell!")
+        self.mn = self.m + self.n
+        lam = np.ascontiguousarray(np.asarray(lams, dtype=np.float64).reshape(-1))
+        self.K = int(lam.size)
+        if not (isinstance(xsolve, str) and xsolve.lower() in _XSOLVE):
+            raise ValueError(f"xsolve = {xsolve!r}: the sparse l1 classifier runs the matrix-free x-update ('auto' or "
+                             "'cg')")
+        d.K, d.D, d.ELL, d.nell = self.K, C_pointer(sd), L.as_dp(ELL), int(ELL.shape[1])
+        d.lam = L.as_dp(lam)
+        d.C, d.xsolve, d.device = float(C), _XSOLVE[xsolve.lower()], int(device)
+        if losses is not None:
+            codes = [v if isinstance(v, (int, np.integer)) else loss_code(v, k) for k, v in enumerate(losses)]
+            lc = np.ascontiguousarray(codes, dtype=np.int32)
+            if lc.size != self.K:
+                raise ValueError(f"lossfunction has {lc.size} entries for {self.K} fits")
+            keep.append(lc)
+            d.loss = lc.ctypes.data_as(C_INT32_P)
+        if ridge is not None:
+            mu = _weights(ridge, self.K, "fits", "ridge")
+            keep.append(mu)
+            d.ridge = L.as_dp(mu)
+        if nonnegative is not None:
+            nn = np.ascontiguousarray(np.asarray(nonnegative).reshape(-1), dtype=np.int32)
+            if nn.size != self.K:
+                raise ValueError(f"nonnegative has {nn.size} entries for {self.K} fits")
+            keep.append(nn)
+            d.nonneg = nn.ctypes.data_as(C_INT32_P)
+        w = _weights(l1weights, self.n, "coefficients", "l1weights")
+        if w is not None:
+            d.l1weights = L.as_dp(w)
+        self._create(d)
+        self.dual = True
+
+    set_cost = _set_svm_cost
+
+    def set_l1weights(self, l1weights=None):
+        """n l1 weights >= 0 shared by all fits (admm_sparse_l1class_set_l1weights); None restores 1"""
+        w = _weights(l1weights, self.n, "coefficients", "l1weights")
+        L.check(self._lib.admm_sparse_l1class_set_l1weights(self._h, None if w is None else L.as_dp(w)))
+
+    def kernel_time(self, reps=20, dual=1):
+        """the row kernel and the element kernel alone, event-timed (admm_sparse_l1class_kernel_time): dict(row_us,
+        elem_us).  Overwrites the iterates: call it between runs."""
+        r, e = C.c_double(0), C.c_double(0)
+        L.check(self._lib.admm_sparse_l1class_kernel_time(self._h, int(reps), int(dual), C.byref(r), C.byref(e)))
+        return dict(row_us=r.value, elem_us=e.value)
+
+    def run(self, *, cg_tol=0.0, cg_maxit=0, nodualerror=0, z0=None, u0=None, **loop):
+        """``loop``: rho, maxiters, abstol, reltol, relax, fast, convtest, domaxiters, objevals, check_every;
+        cg_tol / cg_maxit <= 0: the defaults 1e-12, 200"""
+        return self._run(loop, dict(z0=z0, u0=u0), cg_tol=cg_tol, cg_maxit=cg_maxit, nodualerror=nodualerror)
+
+
+C_INT32_P = C.POINTER(C.c_int32)
+C_pointer = C.pointer

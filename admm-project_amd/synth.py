@@ -187,6 +187,21 @@ def sparse_classifier_problem(seed=0, rows=2 ** 9, cols=2 ** 7, active=0.1, nois
     return dict(D=D, ell=np.where(score >= 0, 1.0, -1.0), testx=testx)
 
 
+def sparse_design_classifier_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, active=0.1, noise=0.1):
+    """sparse_classifier_problem's recipe on sparse_lasso_problem's design matrix (sparse Gaussian, unit columns, canonical
+    ``scipy.sparse.csc_matrix``): a fraction ``active`` of the coefficients is nonzero (size 1 .. 3, both signs, at least
+    one), and the label of row i is sign((D*testx)_i + noise*std(D*testx)*randn), with 0 counted as +1 -- the noise is
+    relative to the scores, which shrink with the density.  dict(D, ell, testx)."""
+    D = sparse_lasso_problem(seed, rows, cols, density)["D"]
+    rng = np.random.default_rng(seed + 49979687)
+    testx = np.where(rng.random(cols) < active, rng.choice([-1.0, 1.0], cols) * rng.uniform(1.0, 3.0, cols), 0.0)
+    if not np.any(testx):
+        testx[0] = 1.0
+    clean = D @ testx
+    score = clean + noise * float(np.std(clean)) * rng.standard_normal(rows)
+    return dict(D=D, ell=np.where(score >= 0, 1.0, -1.0), testx=testx)
+
+
 def sparse_svm_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=3):
     """A multi-class problem on sparse_lasso_problem's design matrix (sparse Gaussian, unit columns, canonical
     ``scipy.sparse.csc_matrix``): ``classes`` planted directions W (cols x K, randn), and the label of row i is the

@@ -319,6 +319,27 @@ def l1classifiertest(seed=0, rows=2 ** 9, cols=2 ** 7, errtol=0.15, quiet=1, opt
     return results, test
 
 
+def sparsel1classifiertest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, errtol=0.15, quiet=1, options=None):
+    """l1classifiertest on a sparse design matrix (synth.sparse_design_classifier_problem; the matrix-free object of
+    DESIGN.md q43): the same lambda, the same two pass criteria, and no x-update that hit the inner iteration cap."""
+    p = synth.sparse_design_classifier_problem(seed, rows, cols, density)
+    D, ell = p["D"], p["ell"]
+    o = _opts(options, objevals=1, quiet=quiet)
+    Cv = float(o.get("C", 1.0))
+    lam = 0.1 * solvers.l1classifier_lambda_max(D, ell, o)
+    obj = lambda x: Cv * np.sum(np.logaddexp(0.0, -ell * (D @ x))) + lam * np.sum(np.abs(x))
+    results = solvers.l1classifier(D, ell, lam, o)
+    z2 = results["zopt"][rows:]
+    objopt, zeroobj = obj(z2), obj(np.zeros(cols))
+    accuracy = float(np.mean(np.where(D @ z2 >= 0, 1.0, -1.0) == ell))
+    ok = objopt < zeroobj and accuracy >= 1.0 - errtol and results["cg_capped_updates"] == 0
+    test = dict(D=D, ell=ell, testx=p["testx"], xopt=results["xopt"], zopt=z2, admmopt=results["objopt"], objopt=objopt,
+                zeroobj=zeroobj, accuracy=accuracy, df=int(np.count_nonzero(z2)), failed=int(not ok),
+                steps=results["steps"], nnz=results["nnz"], cg_capped_updates=results["cg_capped_updates"], errtol=errtol)
+    test["lambda"] = lam
+    return results, test
+
+
 def basispursuittest(seed=0, rows=2 ** 6, cols=2 ** 7, errtol=1e-3, quiet=1, options=None):
     """testers/basispursuittest.m:32-175: ||xopt||_1 <= ||testx||_1 and mean relative residual <= errtol (139)."""
     p = synth.basispursuit_problem(seed, rows, cols)

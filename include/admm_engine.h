@@ -1425,6 +1425,95 @@ int admm_l1class_pass_time(admm_l1class* obj, int32_t reps, int32_t nvec, double
                            int64_t* d_bytes);
 void admm_l1class_destroy(admm_l1class* obj);
 
+/* ---- sparse linear classifiers on a SPARSE design matrix, K fits over one sparse product (additive to ABI 5; DESIGN.md
+ * q43): the family, the arithmetic, the stop rule and the histories of admm_l1class above, fit for fit --
+ *   minimise C*sum_i c_ik*phi_k(ell_ik*(D x)_i) + lambda_k*sum_j w_j*|x_j| + mu_k/2*||x||^2  [x >= 0 when nonneg_k]
+ * as plain ADMM with A = [D; I_cols], B = -1, c = 0, z = [z1 (rows); z2 (cols)], stopcond 'standard' -- with the x-update
+ * (D'D + I) x = D'(z1 - u1) + (z2 - u2) solved by the lock-step conjugate gradients of admm_sparse_lasso with the shift
+ * 1, whatever rho is: nothing factored, nothing cols x cols stored, no limit on cols, positive definite for every D.  The
+ * first x-update of a run starts CG from 0 (x0 is never read) and every later one from the previous x.  Per iteration
+ * beside the solve: one product D X, one product D'(z1 - u1); the dual residual rho*||D'(z1 - z1prev) + (z2 - z2prev)||
+ * and its tolerance rho*||D'u1 + u2|| cost two more transposed products, which nodualerror = 1 leaves out.  rho is a run
+ * option.
+ * ADMM_E_INVALID (before the device is touched): whatever admm_engine_create_sparse refuses in D, D not in host arrays,
+ * and everything admm_l1class_create refuses (K < 1, nell not 1 or K, a label that is not +-1, per fit -- named in the
+ * message -- a loss other than ADMM_LOSS_HINGE / _SQHINGE / _LOGISTIC, a negative or non-finite lambda or ridge, nonneg
+ * other than 0 | 1; a negative or non-finite l1 weight, its index named; C that is not finite and > 0).
+ * ADMM_E_UNSUPPORTED: a communicator, an xsolve other than AUTO / CG; at run: fast ADMM, relaxation, convtest.  Vector
+ * histories are not recorded. */
+typedef struct admm_sparse_l1class admm_sparse_l1class; /* opaque */
+
+typedef struct admm_sparse_l1class_desc {
+  int32_t struct_size;        /* sizeof(admm_sparse_l1class_desc) */
+  int32_t K;                  /* number of fits, >= 1 */
+  const admm_sparse_desc* D;  /* rows x cols, ADMM_MEM_HOST; copied at create */
+  const double* ELL;          /* rows x nell HOST labels +-1, column-major: one column for every fit, or one per fit */
+  int32_t nell;               /* 1 or K */
+  int32_t device;             /* HIP device ordinal */
+  double C;                   /* default 1.0: the cost of the loss term, > 0 */
+  int32_t xsolve;             /* ADMM_XSOLVE_AUTO (default) or ADMM_XSOLVE_CG: the matrix-free x-update */
+  int32_t reserved0;
+  const int32_t* loss;        /* K values ADMM_LOSS_HINGE | _SQHINGE | _LOGISTIC (NULL = logistic for every fit) */
+  const double* lambda;       /* K values lambda_k >= 0 */
+  const double* ridge;        /* K values mu_k >= 0 (NULL = 0) */
+  const int32_t* nonneg;      /* K values 0 | 1 (NULL = 0) */
+  const double* l1weights;    /* cols l1 weights w_j >= 0 shared by all fits (NULL = 1); admm_sparse_l1class_set_l1weights
+                                 replaces them */
+  admm_comm* comm;            /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_sparse_l1class_desc;
+
+typedef struct admm_sparse_l1class_options {
+  int32_t struct_size;   /* sizeof(admm_sparse_l1class_options) */
+  int32_t maxiters;      /* default 1000 */
+  double rho;            /* default 1.0; any value > 0: the x-update's matrix does not depend on it */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations between host polls of "every fit has stopped" (0 = auto: 8; 64 with domaxiters) */
+  int32_t cg_maxit;      /* cap on the inner iterations of one x-update; default 200, <= 0 = default */
+  double cg_tol;         /* relative residual of the x-update; default 1e-12, <= 0 = default */
+  int32_t nodualerror;   /* default 0: admm.m's rule on both residuals; 1: stop on pnorm < perr alone */
+  int32_t reserved0;
+  const double* x0;      /* accepted and never read (see above) */
+  const double* z0;      /* (rows + cols) x K host matrix, z1 above z2 (NULL = zeros) */
+  const double* u0;      /* (rows + cols) x K */
+} admm_sparse_l1class_options;
+
+typedef struct admm_sparse_l1class_summary {  /* one per fit */
+  int32_t steps;              /* results.steps of that fit (admm.m:746) */
+  int32_t stopped_early;      /* 1 if the stop rule fired before maxiters (admm.m:710-713) */
+  double objopt;              /* the objective at the fit's last step, NaN if not evaluated */
+  int32_t xsolve;             /* ADMM_XSOLVE_CG */
+  int32_t reserved0;
+  int64_t cg_iters_total;     /* inner iterations of the fit over the run */
+  int64_t cg_capped_updates;  /* x-updates of the fit that ended with the residual still above cg_tol */
+} admm_sparse_l1class_summary;
+
+/* admm_sparse_l1class_fetch takes the fields of admm_l1class_fetch (ADMM_L1C_F_*): XOPT cols x K, ZOPT and UOPT
+ * (rows + cols) x K, the scalar histories as there */
+void admm_sparse_l1class_desc_default(admm_sparse_l1class_desc* desc);
+void admm_sparse_l1class_options_default(admm_sparse_l1class_options* opts);
+int admm_sparse_l1class_create(const admm_sparse_l1class_desc* desc, admm_sparse_l1class** out);
+/* summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be called again on the same object,
+ * with another rho as well: every run starts from its own z0 / u0, and two runs from the same starts give the same bits */
+int admm_sparse_l1class_run(admm_sparse_l1class* obj, const admm_sparse_l1class_options* opts,
+                            admm_sparse_l1class_summary* summaries, double* runtime_s);
+int admm_sparse_l1class_fetch(admm_sparse_l1class* obj, int field, double* dst, size_t cap, size_t* written);
+/* admm_l1class_set_cost and admm_l1class_set_l1weights on this object: rows weights, K x 2 class costs; cols l1 weights */
+int admm_sparse_l1class_set_cost(admm_sparse_l1class* obj, const double* weights, const double* class_cost);
+int admm_sparse_l1class_set_l1weights(admm_sparse_l1class* obj, const double* l1weights);
+/* fits one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
+int admm_sparse_l1class_chunk(void);
+/* measurement: the row kernel and the element kernel alone over the object's own buffers (every fit running, the dual
+ * residual's sums included with dual != 0), event-timed: the medians of reps launches in microseconds.  Overwrites the
+ * iterates: call it between runs. */
+int admm_sparse_l1class_kernel_time(admm_sparse_l1class* obj, int32_t reps, int32_t dual, double* row_us, double* elem_us);
+void admm_sparse_l1class_destroy(admm_sparse_l1class* obj);
+
 /* X(:, k) = M * Y(:, k) for the columns k < K whose stop_mask[k] is 0 (stop_mask == NULL: every column) through the
  * multi-lasso's product kernel (csrc/symm.hip): M symmetric n x n (ldM >= n), only its lower triangle is read (the
  * operator builds the tile-packed triangle from it); X and Y are n x K column-major HOST matrices.  X is in/out: a masked
