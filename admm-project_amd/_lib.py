@@ -317,6 +317,28 @@ class LassoMultiSummary(C.Structure):  # admm_lasso_multi_summary
 (LM_F_XOPT, LM_F_ZOPT, LM_F_UOPT, LM_F_PNORM, LM_F_PERR, LM_F_OBJEVALS, LM_F_DNORM, LM_F_DERR) = range(1, 9)
 
 
+class CovselMultiDesc(C.Structure):  # admm_covsel_multi_desc
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("m", C.c_int64), ("n", C.c_int64), ("D", _dp),
+                ("ldD", C.c_int64), ("S", _dp), ("lam", _dp), ("device", C.c_int32), ("reserved0", C.c_int32),
+                ("comm", C.c_void_p)]
+
+
+class CovselMultiOptions(C.Structure):  # admm_covsel_multi_options
+    _fields_ = [("struct_size", C.c_int32), ("maxiters", C.c_int32), ("rho", C.c_double), ("abstol", C.c_double),
+                ("reltol", C.c_double), ("relax", C.c_double), ("fast", C.c_int32), ("convtest", C.c_int32),
+                ("domaxiters", C.c_int32), ("objevals", C.c_int32), ("check_every", C.c_int32),
+                ("nodualerror", C.c_int32), ("rhos", _dp), ("z0", _dp), ("u0", _dp)]
+
+
+class CovselMultiSummary(C.Structure):  # admm_covsel_multi_summary
+    _fields_ = [("steps", C.c_int32), ("stopped_early", C.c_int32), ("objopt", C.c_double),
+                ("jacobi_sweeps", C.c_int32), ("reserved0", C.c_int32)]
+
+
+(CM_F_XOPT, CM_F_ZOPT, CM_F_UOPT, CM_F_PNORM, CM_F_PERR, CM_F_OBJEVALS, CM_F_DNORM, CM_F_DERR, CM_F_COV) = range(1, 10)
+COVSEL_SMALL_MAX = 96  # csrc/covsel.h: kCovselSmallMax, the largest n of a fit that stays in one workgroup's LDS
+
+
 class L1ClassDesc(C.Structure):  # admm_l1class_desc
     _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("m", C.c_int64), ("n", C.c_int64), ("D", _dp),
                 ("ldD", C.c_int64), ("ELL", _dp), ("nell", C.c_int32), ("device", C.c_int32), ("C", C.c_double),
@@ -515,6 +537,13 @@ _SIGNATURES = {
     "admm_lasso_multi_product_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                                 C.POINTER(C.c_int64)]),
     "admm_lasso_multi_destroy": (None, [C.c_void_p]),
+    "admm_covsel_multi_desc_default": (None, [C.POINTER(CovselMultiDesc)]),
+    "admm_covsel_multi_options_default": (None, [C.POINTER(CovselMultiOptions)]),
+    "admm_covsel_multi_create": (C.c_int, [C.POINTER(CovselMultiDesc), C.POINTER(C.c_void_p)]),
+    "admm_covsel_multi_run": (C.c_int, [C.c_void_p, C.POINTER(CovselMultiOptions), C.POINTER(CovselMultiSummary),
+                                        C.POINTER(C.c_double)]),
+    "admm_covsel_multi_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "admm_covsel_multi_destroy": (None, [C.c_void_p]),
     "admm_l1class_desc_default": (None, [C.POINTER(L1ClassDesc)]),
     "admm_l1class_options_default": (None, [C.POINTER(L1ClassOptions)]),
     "admm_l1class_create": (C.c_int, [C.POINTER(L1ClassDesc), C.POINTER(C.c_void_p)]),

@@ -16,7 +16,8 @@ from .api import admm, getproxops
 from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
 __all__ = ["lasso", "lasso_multi", "lasso_path", "grouplasso", "grouplasso_multi", "grouplasso_path", "l1classifier", "l1classifier_multi", "l1classifier_path", "l1classifier_lambda_max", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
-           "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection"]
+           "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection", "covarianceselection_multi",
+           "covarianceselection_path", "covarianceselection_lambda_max"]
 
 _ENGINE_OBJ = "<engine-native objective>"
 
@@ -1463,3 +1464,174 @@ def covarianceselection(D, lam, options=None):
             results[key] = np.asarray(results[key]).reshape((n, n), order="F")
     results["solverruntime"] = time.perf_counter() - t0
     return results
+
+
+# ---- covariance selection, K fits over one S
+_COVSEL_HIST = ("pnorm", "perr", "dnorm", "derr", "objevals")
+
+
+def _covsel_S(D, options):
+    """(D, S): the samples as a matrix, or options['S'] (popped) in their place -- exactly one of the two"""
+    S = options.pop("S", None)
+    if (D is None) == (S is None):
+        raise ValueError("covariance selection takes either the samples D or options.S, not both and not neither")
+    if S is None:
+        D = _matrix(D, "D")
+        if D.shape[0] < 2:
+            raise ValueError("cov(D) needs at least two samples (rows of D)")
+        return D, None
+    S = _matrix(S, "S")
+    if S.shape[0] != S.shape[1]:
+        raise ValueError("options.S is not a square matrix!")
+    return None, S
+
+
+def _host_cov(D, S):
+    if S is not None:
+        return S
+    C = np.atleast_2d(np.cov(D, rowvar=False))
+    return 0.5 * (C + C.T)
+
+
+def covarianceselection_lambda_max(D, options=None):
+    """lambda_max = max over i != j of |S_ij| with S = cov(D) (or ``options['S']`` in place of D): at and above it the
+    covariance-selection fit is diagonal.  0 for n = 1."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    S = _host_cov(*_covsel_S(D, options))
+    off = np.abs(S - np.diag(np.diag(S)))
+    return float(off.max()) if off.size else 0.0
+
+
+def _covsel_multi_refusals(options):
+    for key in ("fast", "convtest", "adaptive"):
+        if options.get(key, 0):
+            raise ValueError(f"options.{key} is not available in covarianceselection_multi: call covarianceselection "
+                             "per fit")
+    if options.get("relax", 1) != 1:
+        raise ValueError("options.relax is not available in covarianceselection_multi: call covarianceselection per fit")
+    for key in ("comm",):
+        if options.get(key) is not None:
+            raise ValueError(f"options.{key} is not available in covarianceselection_multi")
+    if options.get("parallel", "none") not in ("none", 0, None):
+        raise ValueError("options.parallel is not available in covarianceselection_multi")
+    if options.get("stopcond", "standard") != "standard":
+        raise ValueError("options.stopcond: covarianceselection_multi runs the 'standard' stop rule alone")
+
+
+def covarianceselection_multi(D, lams, options=None):
+    """results = covarianceselection_multi(D, lams, options): K covariance-selection fits (``covarianceselection``) over
+    one S = cov(D) in ONE run -- a regularisation path or a cross-validation grid of
+
+        minimise trace(S*X) - log det X + lambda_k*||X||_1
+
+    ``lams``: the K values lambda_k > 0.  ``options['rho']`` is a scalar or K values (the eigen-step caches no factor, so
+    every fit may have its own); ``options['S']`` (n x n, symmetric) replaces D (pass ``D = None``).  ``z0`` / ``u0`` are
+    n x n x K (default zeros); ``nodualerror`` (default 0: both residuals) set to 1 stops on the primal residual alone;
+    abstol, reltol, maxiters, domaxiters, objevals and check_every apply to every fit.  For n <= 96 every fit runs in a
+    workgroup of its own, the whole iteration in one kernel; for n > 96 the fits run one after the other through
+    ``covarianceselection`` and the same fields come back.
+
+    Returns xopt, zopt, uopt (n x n x K), steps (K), pnorm / perr (max(steps) x K, NaN past a fit's last step), dnorm /
+    derr unless nodualerror = 1, objevals with options['objevals'], objopt (K), runtime, solverruntime, lams, rhos and
+    jacobi_sweeps (K).  fast, convtest, relax, adaptive, comm, parallel and a stopcond other than 'standard' are refused
+    by name."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    t0 = time.perf_counter()
+    _covsel_multi_refusals(options)
+    D, S = _covsel_S(D, options)
+    n = int((D if S is None else S).shape[1])
+    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
+    K = int(lam.size)
+    if K < 1:
+        raise ValueError("lams must hold at least one lambda")
+    for k, v in enumerate(lam):
+        if not np.isfinite(v) or not v > 0:
+            raise ValueError(f"fit {k}: lambda is not a positive real number")
+    rhos = np.asarray(_per_fit(options.get("rho", 1.0), K, "rho", lambda v: is_positive_real(v, "options.rho")),
+                      dtype=np.float64)
+    if not np.all(np.isfinite(rhos)):
+        raise ValueError("options.rho is not finite")
+    starts = {}
+    for key in ("z0", "u0"):
+        if options.get(key) is not None:
+            v = np.asarray(options[key], dtype=np.float64)
+            if v.shape != (n, n, K):
+                raise ValueError(f"options.{key} is not an {n} x {n} x {K} array (one n x n start per fit)!")
+            starts[key] = v
+    nodual = int(bool(options.get("nodualerror", 0)))
+    loop = _pick(options, ("abstol", "reltol", "maxiters", "domaxiters", "objevals"))
+    from ._lib import COVSEL_SMALL_MAX
+    if n > COVSEL_SMALL_MAX:  # a fit no longer fits one workgroup's LDS: per-fit engines, same fields
+        per = []
+        for k in range(K):
+            o = dict(loop, rho=float(rhos[k]), nodualerror=nodual, record_history=0,
+                     **{key: v[:, :, k] for key, v in starts.items()})
+            if "device" in options:
+                o["device"] = options["device"]
+            if "check_every" in options:
+                o["check_every"] = options["check_every"]
+            per.append(covarianceselection(D, float(lam[k]), o) if S is None else _covsel_single_S(S, float(lam[k]), o))
+        hist = tuple(h for h in _COVSEL_HIST if not (nodual and h in ("dnorm", "derr")))
+        res = _stack_fits(per, hist)
+        for key in ("xopt", "zopt", "uopt"):
+            res[key] = res[key].reshape((n, n, K), order="F")
+        res["jacobi_sweeps"] = np.array([r["engine_info"]["jacobi_sweeps"] for r in per], dtype=np.int64)
+    else:
+        from .covsel_multi import CovselMulti
+        obj = CovselMulti(lam, D=D, S=S, device=int(options.get("device", 0)))
+        res = _run_and_close(obj, rhos=rhos, nodualerror=nodual, check_every=int(options.get("check_every", 0)),
+                             **starts, **loop)
+    res["lams"] = lam.copy()
+    res["rhos"] = rhos.copy()
+    res["solverruntime"] = time.perf_counter() - t0
+    return res
+
+
+def _covsel_single_S(S, lam, options):
+    """``covarianceselection`` on a given S (the per-fit route of covarianceselection_multi for n > 96)"""
+    t0 = time.perf_counter()
+    options = dict(options)
+    n = S.shape[0]
+    args = _engine_args(options, dict(S=S))
+    args["lambda"] = lam
+    minx, minz, _ = getproxops("CovarianceSelection", args)
+    options.update(A=1, B=-1, c=0, m=n, nA=n, nB=n, obj=_ENGINE_OBJ)
+    results = admm(minx, minz, options)
+    for key in ("xopt", "zopt", "uopt", "x0", "z0", "u0"):
+        if key in results:
+            results[key] = np.asarray(results[key]).reshape((n, n), order="F")
+    results["solverruntime"] = time.perf_counter() - t0
+    return results
+
+
+def covarianceselection_path(D, lams=None, options=None):
+    """results = covarianceselection_path(D, lams, options): the regularisation path of covariance selection, every
+    lambda side by side in one run of ``covarianceselection_multi``.  ``lams = None``:
+    ``options['nlambda']`` values (default 10), log-spaced from lambda_max = max over i != j of |S_ij| -- at and above it
+    the fit is diagonal -- down to ``options['lambda_min_ratio']`` * lambda_max (default 1e-2), with S = cov(D) formed on
+    the host.  Returns covarianceselection_multi's fields plus ``df``: per fit the number of pairs i < j with
+    z_ij != 0, the edges of the selected graph."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    nlambda = options.pop("nlambda", None)
+    ratio = options.pop("lambda_min_ratio", 1e-2)
+    if lams is None:
+        nlambda = 10 if nlambda is None else nlambda
+        if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
+            raise ValueError("options.nlambda must be an integer >= 1")
+        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
+            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
+        lmax = covarianceselection_lambda_max(D, {"S": options["S"]} if "S" in options else None)
+        if not lmax > 0:
+            raise ValueError("lambda_max is 0 (S is diagonal): there is no path to follow; pass lams")
+        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+    res = covarianceselection_multi(D, lams, options)
+    res["df"] = covsel_df(res["zopt"])
+    return res
+
+
+def covsel_df(zopt):
+    """per fit of an n x n x K array the number of off-diagonal pairs i < j with z_ij != 0"""
+    Z = np.asarray(zopt)
+    Z = Z.reshape(Z.shape[0], Z.shape[1], -1)
+    iu = np.triu_indices(Z.shape[0], k=1)
+    return np.count_nonzero(Z[iu[0], iu[1], :], axis=0).astype(np.int64)

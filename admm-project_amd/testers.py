@@ -13,7 +13,7 @@ import numpy as np
 from . import solvers, synth
 
 __all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "sparsequantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "l1classifiertest", "basispursuittest",
-           "linearprogramtest", "modeltest", "covarianceselectiontest", "solvertester"]
+           "linearprogramtest", "modeltest", "covarianceselectiontest", "covarianceselectionpathtest", "solvertester"]
 
 
 def _opts(options, **forced):
@@ -403,6 +403,36 @@ def covarianceselectiontest(seed=0, rows=2 ** 9, cols=2 ** 6, errtol=1e-3, quiet
                 failed=int(not objopt < trueobj), objerror=abs((trueobj - objopt) / objopt), steps=results["steps"],
                 errtol=errtol)
     test["lambda"] = lam
+    return results, test
+
+
+def covarianceselectionpathtest(seed=0, rows=2 ** 9, cols=2 ** 5, nlambda=6, lambda_min_ratio=0.2, errtol=1e-3, quiet=1,
+                                options=None):
+    """The regularisation path of covarianceselectiontest's problem through ``covarianceselection_path``:
+    ``nlambda`` values log-spaced from 1.25*lambda_max down to ``lambda_min_ratio`` times that, lambda_max = max over
+    i != j of |cov(D)_ij|.  Passes when the first fit's Z is exactly diagonal, ``df`` does not decrease as lambda falls,
+    and every fit meets covarianceselectiontest's criterion at its own lambda: obj(xopt, xopt) < obj(Sinv, Sinv) on the
+    TRUE S.  The grid ends at 0.2 of its top because that criterion judges a fit to cov(D) on the true S: below about
+    0.1*lambda_max the penalty no longer covers the sampling noise of 512 rows (|cov(D) - S| ~ 1/sqrt(rows)), and the
+    exact minimiser of the sampled problem itself loses to Sinv there (seen on the CPU oracle, seeds 0-4)."""
+    opts = dict(options or {})
+    p = synth.covsel_problem(seed, rows, cols)
+    S, Sinv = p["S"], p["Sinv"]
+    lmax = solvers.covarianceselection_lambda_max(p["D"])
+    lams = 1.25 * lmax * np.logspace(0.0, np.log10(float(lambda_min_ratio)), int(nlambda))
+    results = solvers.covarianceselection_path(p["D"], lams, _opts(opts, objevals=1, maxiters=1000, quiet=quiet))
+    obj = lambda X, Z, lam: np.trace(S @ X) - np.log(np.linalg.det(X)) + lam * np.sum(np.abs(Z))
+    trueobj = np.array([obj(Sinv, Sinv, lam) for lam in lams])
+    objopt = np.array([obj(results["xopt"][:, :, k], results["xopt"][:, :, k], lam) for k, lam in enumerate(lams)])
+    Z0 = results["zopt"][:, :, 0]
+    diagonal = bool(np.all(Z0 == np.diag(np.diag(Z0))))
+    df = results["df"]
+    monotone = bool(np.all(np.diff(df) >= 0))
+    worse = ~(objopt < trueobj)
+    test = dict(D=p["D"], S=S, Sinv=Sinv, lams=lams, lambda_max=lmax, trueobjopt=trueobj, objopt=objopt,
+                admmopt=results["objopt"], df=df, diagonal_at_top=diagonal, df_monotone=monotone,
+                objerror=np.abs((trueobj - objopt) / objopt), steps=results["steps"], errtol=errtol,
+                failed=int(not diagonal) + int(not monotone) + int(np.count_nonzero(worse)))
     return results, test
 
 

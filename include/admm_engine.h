@@ -1514,6 +1514,81 @@ int admm_sparse_l1class_chunk(void);
 int admm_sparse_l1class_kernel_time(admm_sparse_l1class* obj, int32_t reps, int32_t dual, double* row_us, double* elem_us);
 void admm_sparse_l1class_destroy(admm_sparse_l1class* obj);
 
+/* ---- covariance selection, K fits over one S in one run (additive to ABI 5): a regularisation path or a
+ * cross-validation grid of
+ *   minimise trace(S*X) - log det X + lambda_k*||Z||_1  s.t. X = Z,   S = cov(D) or given,
+ * every fit the plain-ADMM run an ADMM_PROB_COVSEL engine makes (A = 1, B = -1, c = 0 on the n^2 entries, 'fro' norms,
+ * stopcond 'standard').  One kernel carries a fit's whole iteration -- the eigen-step of the engine's one-workgroup path
+ * (csrc/covsel_device.h), the soft threshold, the residual sums and the stop decision -- in ONE workgroup per fit, and
+ * one launch runs up to check_every iterations of every fit.  The fits share nothing but S; the eigen-step caches no
+ * factor, so rho may differ per fit (options.rhos).  Iterates are n x n column-major, fit after fit.
+ * ADMM_E_INVALID (before the device is touched): K < 1, n < 1, neither or both of D and S, m < 2 with D, an S that is
+ * not finite and symmetric, per fit (named in the message) a lambda that is not positive and finite; at run a rho_k that
+ * is not positive and finite.  ADMM_E_UNSUPPORTED: n > 96 (a fit has to fit one workgroup's LDS: run one ADMM_PROB_COVSEL
+ * engine per fit), a communicator; at run: fast ADMM, relaxation, convtest.  Vector histories are not recorded. */
+typedef struct admm_covsel_multi admm_covsel_multi; /* opaque */
+
+typedef struct admm_covsel_multi_desc {
+  int32_t struct_size;        /* sizeof(admm_covsel_multi_desc) */
+  int32_t K;                  /* number of fits, >= 1 */
+  int64_t m, n;               /* D is m x n (m samples of n variables); S is n x n, n <= 96 */
+  const double* D;            /* HOST, column-major; S = cov(D) is built on the device at create.  Or NULL with S */
+  int64_t ldD;                /* >= m */
+  const double* S;            /* HOST n x n symmetric, leading dimension n, in place of D.  Or NULL with D */
+  const double* lambda;       /* K values lambda_k > 0 */
+  int32_t device;             /* HIP device ordinal */
+  int32_t reserved0;
+  admm_comm* comm;            /* must be NULL (row sharding: ADMM_E_UNSUPPORTED) */
+} admm_covsel_multi_desc;
+
+typedef struct admm_covsel_multi_options {
+  int32_t struct_size;   /* sizeof(admm_covsel_multi_options) */
+  int32_t maxiters;      /* default 1000 */
+  double rho;            /* default 1.0: the rho of every fit unless rhos is given */
+  double abstol;         /* default 1e-5 */
+  double reltol;         /* default 1e-3 */
+  double relax;          /* default 1.0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t fast;          /* default ADMM_FAST_OFF; anything else: ADMM_E_UNSUPPORTED */
+  int32_t convtest;      /* default 0; anything else: ADMM_E_UNSUPPORTED */
+  int32_t domaxiters;    /* default 0 */
+  int32_t objevals;      /* default 0 */
+  int32_t check_every;   /* iterations of every fit in one launch, between two host polls (0 = auto: 8; 64 with domaxiters) */
+  int32_t nodualerror;   /* default 0: admm.m's rule on both residuals; 1: stop on pnorm < perr alone */
+  const double* rhos;    /* K values rho_k > 0, or NULL: rho for every fit */
+  const double* z0;      /* n*n x K host matrix, one n x n column-major start per fit (NULL = zeros) */
+  const double* u0;      /* n*n x K */
+} admm_covsel_multi_options;
+
+typedef struct admm_covsel_multi_summary {  /* one per fit */
+  int32_t steps;              /* results.steps of that fit (admm.m:746) */
+  int32_t stopped_early;      /* 1 if the stop rule fired before maxiters (admm.m:710-713) */
+  double objopt;              /* the objective at the fit's last step, NaN if not evaluated */
+  int32_t jacobi_sweeps;      /* sweeps of the fit's eigen-steps over the run */
+  int32_t reserved0;
+} admm_covsel_multi_summary;
+
+/* fields of admm_covsel_multi_fetch */
+enum {
+  ADMM_CM_F_XOPT = 1,      /* n*n x K */
+  ADMM_CM_F_ZOPT = 2,      /* n*n x K */
+  ADMM_CM_F_UOPT = 3,      /* n*n x K */
+  /* scalar histories: S x K column-major with S = the largest steps of any fit, NaN past a fit's own last step; DNORM
+   * and DERR after a run with nodualerror = 0 only, OBJEVALS after a run with objevals = 1 only */
+  ADMM_CM_F_PNORM = 4, ADMM_CM_F_PERR = 5, ADMM_CM_F_OBJEVALS = 6, ADMM_CM_F_DNORM = 7, ADMM_CM_F_DERR = 8,
+  ADMM_CM_F_COV = 9        /* S as the object holds it, n x n (cap >= n*n): available from create on */
+};
+
+void admm_covsel_multi_desc_default(admm_covsel_multi_desc* desc);
+void admm_covsel_multi_options_default(admm_covsel_multi_options* opts);
+int admm_covsel_multi_create(const admm_covsel_multi_desc* desc, admm_covsel_multi** out);
+/* summaries: K entries (may be NULL); runtime_s: the loop alone (may be NULL).  May be called again on the same object,
+ * with other rhos as well: every run starts from its own z0 / u0 and from the eigenvector basis I, and two runs from the
+ * same starts give the same bits.  A fit's results do not depend on K or on the other fits. */
+int admm_covsel_multi_run(admm_covsel_multi* obj, const admm_covsel_multi_options* opts,
+                          admm_covsel_multi_summary* summaries, double* runtime_s);
+int admm_covsel_multi_fetch(admm_covsel_multi* obj, int field, double* dst, size_t cap, size_t* written);
+void admm_covsel_multi_destroy(admm_covsel_multi* obj);
+
 /* X(:, k) = M * Y(:, k) for the columns k < K whose stop_mask[k] is 0 (stop_mask == NULL: every column) through the
  * multi-lasso's product kernel (csrc/symm.hip): M symmetric n x n (ldM >= n), only its lower triangle is read (the
  * operator builds the tile-packed triangle from it); X and Y are n x K column-major HOST matrices.  X is in/out: a masked
