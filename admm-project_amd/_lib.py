@@ -497,6 +497,9 @@ _SIGNATURES = {
     "admm_reg_multi_chunk": (C.c_int, []),
     "admm_reg_multi_destroy": (None, [C.c_void_p]),
     "admm_op_spmm": (C.c_int, [C.POINTER(SparseDesc), C.c_int, C.c_int, _dp, _dp]),
+    "admm_op_spmm_cg": (C.c_int, [C.POINTER(SparseDesc), C.c_int32, _dp, _dp, C.c_double, C.c_double, C.c_int32,
+                                  C.c_int32, C.POINTER(C.c_int32), _dp, _dp, C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int32)]),
     "admm_sparse_svm_desc_default": (None, [C.POINTER(SparseSvmDesc)]),
     "admm_sparse_svm_options_default": (None, [C.POINTER(SparseSvmOptions)]),
     "admm_sparse_svm_create": (C.c_int, [C.POINTER(SparseSvmDesc), C.POINTER(C.c_void_p)]),

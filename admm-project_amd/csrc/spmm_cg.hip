@@ -5,9 +5,12 @@
 //   per inner iteration           T = D P, Q = D' T (two SpMM), scg_dot / _update / _direction / _advance
 // A fit whose stop flag is set is FROZEN, and a fit whose solve is done is masked until the next solve: every kernel and
 // every product skips it.  Every sum runs in a fixed order that depends on the sizes alone.
+// The stand-alone operator admm_op_spmm_cg runs SpmmCg::solve once on host arrays.
 #include "spmm_cg.h"
 
 #include <algorithm>
+#include <cstring>
+#include <string>
 
 #include "multi_host.h"
 
@@ -329,4 +332,132 @@ int SpmmCg::fetch_counters(std::vector<ScgState>* out) const {
   return ADMM_OK;
 }
 
+// ------------------------------------------------------------------------------------- the stand-alone operator (q45)
+namespace {
+
+// what a frozen fit's column of buffer `which` (0 X, 1 R, 2 P) holds before the solve: finite, nonzero, and different
+// for every (buffer, fit, row)
+double frozen_pattern(int which, int32_t k, int64_t i) {
+  return -(1.0 + which) * 1024.0 - static_cast<double>(k) - static_cast<double>(i % 1021) / 1024.0;
+}
+
+struct ScgOpIn {
+  const admm_sparse_desc* D;
+  int32_t K;
+  const double *Y, *X0;
+  double shift, tol;
+  int32_t maxit, batch;
+  const int32_t* stop;
+};
+
+// one solve of the production path on a host of its own, then the operator's own checks of what the caller cannot see
+int scg_op_run(MultiHost& h, SpmmCg& cg, const ScgOpIn& in, double* X, double* R, int64_t* state, int32_t* next_batch) {
+  const int32_t K = in.K;
+  h.K = K;
+  ADMM_TRY(cg.build(&h, 0, in.D));
+  ADMM_TRY(alloc_common(h));
+  ADMM_TRY(begin_run(h));
+  ScgArgs a{};
+  ADMM_TRY(cg.begin_run(in.tol, in.maxit, &a, in.shift));
+  if (in.batch > 0) cg.cg_batch = in.batch;
+  const int64_t n = cg.n;
+  ADMM_TRY(cg.upload(cg.Y, in.Y, n));
+  if (in.X0) ADMM_TRY(cg.upload(cg.X, in.X0, n));
+
+  const size_t elems = static_cast<size_t>(cg.chunks) * n * kSpmmChunk;
+  auto at = [&](int32_t k, int64_t i) {
+    return static_cast<size_t>(k / kSpmmChunk) * n * kSpmmChunk + static_cast<size_t>(i) * kSpmmChunk + k % kSpmmChunk;
+  };
+  double* const bufs[4] = {cg.X, cg.R, cg.P, cg.Q};
+  static const char* const names[4] = {"X", "R", "P", "Q"};
+  std::vector<double> before[3];
+  bool frozen = false;
+  for (int32_t k = 0; in.stop && k < K; ++k) frozen = frozen || in.stop[k] != 0;
+  if (frozen) {  // the flags into the records, the pattern into the frozen fits' columns of X, R and P
+    std::vector<MultiRec> rec(static_cast<size_t>(K), MultiRec{0, 0, 0, 0});
+    for (int32_t k = 0; k < K; ++k) rec[k].stop = in.stop[k] != 0 ? 1 : 0;
+    ADMM_HIP_TRY(hipMemcpyAsync(h.rec, rec.data(), sizeof(MultiRec) * K, hipMemcpyHostToDevice, h.stream));
+    ADMM_HIP_TRY(hipStreamSynchronize(h.stream));  // (X0 is up, rec goes out of scope)
+    for (int b = 0; b < 3; ++b) {
+      before[b].resize(elems);
+      ADMM_HIP_TRY(hipMemcpy(before[b].data(), bufs[b], sizeof(double) * elems, hipMemcpyDeviceToHost));
+      for (int32_t k = 0; k < K; ++k)
+        if (in.stop[k] != 0)
+          for (int64_t i = 0; i < n; ++i) before[b][at(k, i)] = frozen_pattern(b, k, i);
+      ADMM_HIP_TRY(hipMemcpy(bufs[b], before[b].data(), sizeof(double) * elems, hipMemcpyHostToDevice));
+    }
+  }
+
+  ADMM_TRY(cg.solve(a, in.X0 == nullptr));
+  ADMM_HIP_TRY(hipStreamSynchronize(h.stream));
+  ADMM_HIP_TRY(hipGetLastError());
+
+  std::vector<ScgState> st;
+  ADMM_TRY(cg.fetch_counters(&st));
+  std::vector<double> after(elems);
+  const int32_t kpad = cg.chunks * kSpmmChunk;
+  for (int b = 0; b < 4; ++b) {
+    ADMM_HIP_TRY(hipMemcpy(after.data(), bufs[b], sizeof(double) * elems, hipMemcpyDeviceToHost));
+    for (int32_t k = K; k < kpad; ++k)  // the padding columns of the last chunk: exactly +0.0, as build left them
+      for (int64_t i = 0; i < n; ++i) {
+        uint64_t bits;
+        std::memcpy(&bits, &after[at(k, i)], sizeof(bits));
+        if (bits != 0)
+          return fail(ADMM_E_NUMERIC, std::string("spmm_cg: padding column ") + std::to_string(k) + " of " + names[b] +
+                                          " is no longer 0.0 at row " + std::to_string(i));
+      }
+    for (int32_t k = 0; frozen && b < 3 && k < K; ++k) {
+      if (in.stop[k] == 0) continue;
+      for (int64_t i = 0; i < n; ++i)
+        if (std::memcmp(&after[at(k, i)], &before[b][at(k, i)], sizeof(double)) != 0)
+          return fail(ADMM_E_NUMERIC, std::string("spmm_cg: the frozen fit ") + std::to_string(k) + " changed in " +
+                                          names[b] + " at row " + std::to_string(i));
+    }
+  }
+  for (int32_t k = 0; frozen && k < K; ++k) {
+    static const ScgState zero{};
+    if (in.stop[k] != 0 && std::memcmp(&st[k], &zero, sizeof(ScgState)) != 0)
+      return fail(ADMM_E_NUMERIC, "spmm_cg: the CG state of the frozen fit " + std::to_string(k) + " moved");
+  }
+
+  ADMM_TRY(cg.fetch_matrix(cg.X, n, X, static_cast<size_t>(n) * K, nullptr));
+  if (R) ADMM_TRY(cg.fetch_matrix(cg.R, n, R, static_cast<size_t>(n) * K, nullptr));
+  for (int32_t k = 0; k < K; ++k) {
+    int64_t* s = state + static_cast<size_t>(6) * k;
+    s[0] = st[k].iters;
+    s[1] = st[k].total;
+    s[2] = st[k].capped;
+    s[3] = st[k].done;
+    s[4] = st[k].brk;
+    s[5] = st[k].zero;
+  }
+  if (next_batch) *next_batch = cg.cg_batch;
+  return ADMM_OK;
+}
+
+}  // namespace
+
 }  // namespace admm
+
+using namespace admm;
+
+extern "C" int admm_op_spmm_cg(const admm_sparse_desc* D, int32_t K, const double* Y, const double* X0, double shift,
+                               double tol, int32_t maxit, int32_t batch, const int32_t* stop, double* X, double* R,
+                               int64_t* state, int32_t* next_batch) {
+  if (!Y || !X || !state) return fail(ADMM_E_INVALID, "spmm_cg: Y, X or state is NULL");
+  if (K < 1) return fail(ADMM_E_INVALID, "spmm_cg: K must be at least 1");
+  if (!finite_pos(tol)) return fail(ADMM_E_INVALID, "spmm_cg: tol must be positive and finite");
+  if (maxit < 1) return fail(ADMM_E_INVALID, "spmm_cg: maxit must be at least 1");
+  if (!finite_nonneg(shift)) return fail(ADMM_E_INVALID, "spmm_cg: shift is negative or not finite");
+  ADMM_TRY(check_sparse_D("spmm_cg", D));
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
+  MultiHost h;
+  SpmmCg cg;
+  const ScgOpIn in{D, K, Y, X0, shift, tol, maxit, batch, stop};
+  const int rc = scg_op_run(h, cg, in, X, R, state, next_batch);
+  const std::string msg = rc != ADMM_OK ? std::string(admm_last_error()) : std::string();
+  cg.destroy();  // (the whole teardown of h; nothing to do before build)
+  return rc != ADMM_OK ? fail(rc, msg) : ADMM_OK;
+}

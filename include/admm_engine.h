@@ -634,6 +634,23 @@ int admm_op_spmv(const admm_sparse_desc* D, int transpose, const double* x, doub
  * kernel of the sparse linear SVM (admm_sparse_svm_create; csrc/spmm.hip): one read of D per chunk of
  * admm_sparse_svm_chunk() columns, and column k of Y has the bits admm_op_spmv returns for column k of X */
 int admm_op_spmm(const admm_sparse_desc* D, int transpose, int K, const double* X, double* Y);
+/* X(:, k) = conjugate gradients on (D'D + shift*I) x = Y(:, k) for K right-hand sides in lock-step: ONE solve of the
+ * x-update the sparse multi-fit solvers share (csrc/spmm_cg.hip), through the object, the host loop and
+ * the kernels of a run.  Y, X0, X and R are cols x K, column-major on the host.  X0 == NULL: from x = 0 (the first solve
+ * of a run); otherwise from X0 (every later one).  A fit ends on ||r|| <= tol*||y||, after maxit inner iterations, on a
+ * zero right-hand side (x = 0) or on p.q = 0.  batch > 0 sets the inner iterations enqueued between two polls of the
+ * host, batch <= 0 leaves a run's first value; *next_batch (nullable) is the value the solve left for the next one.
+ * stop (nullable, K values): nonzero freezes the fit as a stopped ADMM run is frozen -- its columns of X and R come back
+ * as a fixed pattern the operator wrote in front of the solve.  R (nullable) is the residual of the recurrence.
+ * state holds six values per fit: inner iterations of this solve, inner iterations in total, solves that ended above
+ * tol, done, the p.q = 0 exit, the zero right-hand side.
+ * The operator itself checks that the columns past K of the last chunk of X, R, P and Q are still +0.0 and that a
+ * frozen fit's columns of X, R and P and its state hold the bits they held before the solve (ADMM_E_NUMERIC).
+ * ADMM_E_INVALID without a device: a NULL D, Y, X or state, K < 1, tol not positive and finite, maxit < 1, shift negative
+ * or not finite, D not in host arrays, and the checks of admm_engine_create_sparse on D */
+int admm_op_spmm_cg(const admm_sparse_desc* D, int32_t K, const double* Y, const double* X0, double shift, double tol,
+                    int32_t maxit, int32_t batch, const int32_t* stop, double* X, double* R, int64_t* state,
+                    int32_t* next_batch);
 /* W = D'*D (+ shift on the diagonal), n x n  (lasso.m:168, lad.m:134, unwrappedadmm.m:115) */
 int admm_op_gram(const double* D, int64_t m, int64_t n, int64_t ldD, double shift, double* W);
 /* in place lower Cholesky of the n x n SPD matrix A (chol(.,'lower'), lasso.m:168) */

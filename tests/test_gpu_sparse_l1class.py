@@ -182,7 +182,8 @@ def test_two_runs_of_one_object_with_different_rho_match_fresh_objects(gpu):
 # ---------------------------------------------------------------------------------------------- 5. several row blocks
 @pytest.mark.parametrize("shape, fits, loop", [(R.WIDE, R.WIDE_FITS, R.WIDE_LOOP), (R.TALL, R.TALL_FITS, R.TALL_LOOP)])
 def test_a_workgroup_takes_several_row_blocks(gpu, shape, fits, loop):
-    """60 x 8300: the n-length element and CG kernels; 8200 x 40 with objevals = 1: the row kernel"""
+    """60 x 8300: the n-length element and CG kernels; 8200 x 40 with objevals = 1: the row kernel
+    (the CG kernels' own row-block edges, one solve at a time: test_gpu_spmm_cg.test_row_block_edges)"""
     c = R.case(gpu, shape, "shared")
     assert max(c["A"].shape) > 32 * 256 and loop["objevals"] == 1
     got = _device(gpu, c, fits, loop, 0)

@@ -151,7 +151,8 @@ def test_two_chunks(gpu):
 @pytest.mark.parametrize("shape,fits,maxiters", [(R.WIDE, R.WIDE_FITS, R.WIDE_MAXITERS),
                                                  (R.TALL, R.TALL_FITS, R.TALL_MAXITERS)])
 def test_a_workgroup_takes_several_row_blocks(gpu, shape, fits, maxiters):
-    """60 x 8300: the n-length element pass and CG kernels; 8200 x 40 with objevals = 1: the m-length fit kernel"""
+    """60 x 8300: the n-length element pass and CG kernels; 8200 x 40 with objevals = 1: the m-length fit kernel
+    (the CG kernels' own row-block edges, one solve at a time: test_gpu_spmm_cg.test_row_block_edges)"""
     c = R.big_case(gpu, shape)
     assert max(c["A"].shape) > 32 * 256
     got = _multi(gpu, c, 0, fits, maxiters=maxiters)

@@ -140,6 +140,7 @@ def test_two_chunks(gpu):
 
 # ---------------------------------------------------------------------------------------------- 4. several row blocks
 def test_a_workgroup_takes_several_row_blocks(gpu):
+    """(the CG kernels' own row-block edges, one solve at a time: test_gpu_spmm_cg.test_row_block_edges)"""
     c = R.tall_case(gpu)
     assert c["A"].shape[0] > 32 * 256
     got = _multi(gpu, c, 1, R.TALL_FITS, maxiters=R.TALL_MAXITERS)

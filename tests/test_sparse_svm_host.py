@@ -111,7 +111,7 @@ def test_csc_canonicalisation(ap):
 def test_abi_symbols_structs_and_defaults(ap):
     L = ap._lib
     lib = L.load()
-    for name in ("admm_op_spmm", "admm_sparse_svm_desc_default", "admm_sparse_svm_options_default",
+    for name in ("admm_op_spmm", "admm_op_spmm_cg", "admm_sparse_svm_desc_default", "admm_sparse_svm_options_default",
                  "admm_sparse_svm_create", "admm_sparse_svm_run", "admm_sparse_svm_fetch", "admm_sparse_svm_set_cost",
                  "admm_sparse_svm_chunk", "admm_sparse_svm_destroy"):
         assert name in L.EXPORTED_SYMBOLS and hasattr(lib, name)
@@ -171,3 +171,10 @@ def test_abi_refusals_fire_before_the_device_is_touched(ap):
     x = np.zeros((65, 2), order="F")
     y = np.zeros((257, 2), order="F")
     assert L.load().admm_op_spmm(C.byref(d), 0, 0, L.as_dp(x), L.as_dp(y)) == L.E_INVALID  # K = 0
+    # admm_op_spmm_cg (every refusal: test_spmm_cg_host): K = 0, tol = 0, and D with jc[0] != 0
+    state = np.zeros((2, 6), dtype=np.int64)
+    sp_ = state.ctypes.data_as(C.POINTER(C.c_int64))
+    cg = lambda dd, K, tol: L.load().admm_op_spmm_cg(C.byref(dd), K, L.as_dp(x), None, 1.0, tol, 10, 0, None, L.as_dp(x),
+                                                     None, sp_, None)
+    assert cg(d, 0, 1e-10) == L.E_INVALID and cg(d, 2, 0.0) == L.E_INVALID
+    assert cg(desc_of(L, refusal_cases(L, p)[0][2][0]), 2, 1e-10) == L.E_INVALID
