@@ -497,6 +497,8 @@ _SIGNATURES = {
     "admm_reg_multi_chunk": (C.c_int, []),
     "admm_reg_multi_destroy": (None, [C.c_void_p]),
     "admm_op_spmm": (C.c_int, [C.POINTER(SparseDesc), C.c_int, C.c_int, _dp, _dp]),
+    "admm_op_spmm_weighted": (C.c_int, [C.POINTER(SparseDesc), C.c_int32, _dp, _dp, C.c_int32, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), _dp]),
     "admm_op_spmm_cg": (C.c_int, [C.POINTER(SparseDesc), C.c_int32, _dp, _dp, C.c_double, C.c_double, C.c_int32,
                                   C.c_int32, C.POINTER(C.c_int32), _dp, _dp, C.POINTER(C.c_int64),
                                   C.POINTER(C.c_int32)]),
@@ -526,6 +528,9 @@ _SIGNATURES = {
     "admm_sparse_lasso_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_sparse_lasso_set_weights": (C.c_int, [C.c_void_p, _dp]),
     "admm_sparse_lasso_set_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
+    "admm_sparse_lasso_set_observations": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.POINTER(C.c_int32),
+                                                     C.POINTER(C.c_int32)]),
+    "admm_sparse_lasso_heldout": (C.c_int, [C.c_void_p, _dp, _dp]),
     "admm_sparse_lasso_chunk": (C.c_int, []),
     "admm_sparse_lasso_destroy": (None, [C.c_void_p]),
     "admm_lasso_multi_desc_default": (None, [C.POINTER(LassoMultiDesc)]),

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kScgBlock) void slm_group_elem_kernel(SlmElemArgs a
     in.zp = pa.z[e];
     in.u_old = pa.u[e];
     in.uhat_i = in.u_old;
-    in.add_i = (a.ns == 1) ? a.DTS[i * KC] : a.DTS[base + e];
+    in.add_i = (a.dts_ns == 1) ? a.DTS[i * KC] : a.DTS[base + e];
     const double ei = penalty_elem(group_prox_v(pa, xv, in), pen.tau * wi, pen.nonneg);
     in.zg_i = pen.kappa * (ei * gacc[(gp.gid[i] - g0) * KC + l.c]);
     if (a.objevals) obj += penalty_obj_elem(pen, wi, in.zg_i);

@@ -308,6 +308,7 @@ int admm_lasso_multi_run(admm_lasso_multi* o, const admm_lasso_multi_options* op
   ea.part = o->part;
   ea.K = K;
   ea.ns = o->ns;
+  ea.dts_ns = o->ns;
   ea.objevals = op.objevals;
   ea.rho = op.rho;
   SlmFitArgs ta{};
@@ -338,6 +339,7 @@ int admm_lasso_multi_run(admm_lasso_multi* o, const admm_lasso_multi_options* op
   fa.reltol = op.reltol;
   fa.domaxiters = op.domaxiters;
   fa.objevals = op.objevals;
+  fa.fit_slots = 1;
   fa.maxiters = N;
 
   ADMM_TRY(begin_timing(*o));

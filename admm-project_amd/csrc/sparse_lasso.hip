@@ -5,6 +5,9 @@
 //   g_k(z) = lambda_k*sum_i w_i*|z_i| + mu_k/2*||z||^2 + [z >= 0],  z = kappa_k*penalty_elem(x + u, tau_k*w_i, nonneg_k),
 //   tau_k = lambda_k/rho, kappa_k = rho/(rho + mu_k)          (q32's family without groups: penalty_device.h)
 // With groups set (admm_sparse_lasso_set_groups, q41) the element kernel is group_multi.hip's slm_group_elem_kernel.
+// With observations set (admm_sparse_lasso_set_observations, q46) fit k weighs row i by omega_ik = obsw_i * [fold_i !=
+// held_k]: the CG's forward product stores omega_k o (D p) (SpmmCg::weighted), D's becomes the K-column D'(Omega_k s_k),
+// slm_fit_weighted_kernel sums the weighted fit term and, behind the loop at T = D z, the held-out error and weight.
 // The x-update (D'D + rho*I) x = D's_k + rho*(z - u) (lasso.m:28-30) is spmm_cg.hip's lock-step CG with the shift rho:
 // the first solve of a run starts from 0 and every later one from the previous x.
 // Per iteration, every launch for all K fits at once (blockIdx.y = chunk of kSpmmChunk fits):
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(kScgBlock) void slm_elem_kernel(SlmElemArgs a) {
     if (!l.run || i >= a.n) continue;
     const int64_t e = i * KC + l.c;
     const double zp = pa.z[e], uo = pa.u[e];
-    const double dts = (a.ns == 1) ? a.DTS[i * KC] : a.DTS[base + e];
+    const double dts = (a.dts_ns == 1) ? a.DTS[i * KC] : a.DTS[base + e];
     if constexpr (INIT) {
       pa.rhs[e] = rhs_value(RHS_RHO_DTS, a.rho, zp, uo, 0.0, dts);
     } else {
@@ -112,6 +115,64 @@ __global__ __launch_bounds__(kScgBlock) void slm_fit_kernel(SlmFitArgs a) {
   scg_sums<1>(acc, lds, a.part, 1, 0);
 }
 
+// the weighted form (observations set, q46): three sums per fit over m (SlmFitSlot).  Every weight is a select on the
+// fold, never a product with 0; a.all: every fit, stopped or not
+__global__ __launch_bounds__(kScgBlock) void slm_fit_weighted_kernel(SlmFitArgs a) {
+  __shared__ double lds[SLW_COUNT * kScgBlock];
+  ScgLane l = scg_lane(a.rec, a.K);
+  if (a.all) l.run = l.fit < a.K;
+  if (!__syncthreads_or(l.run)) return;
+  const int64_t base = static_cast<int64_t>(blockIdx.y) * a.m * KC;
+  const int32_t hk = a.held[l.run ? l.fit : 0];
+  double acc[SLW_COUNT] = {0.0, 0.0, 0.0};
+  const int64_t nrb = (a.m + kScgRows - 1) / kScgRows;
+  for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int64_t i = rb * kScgRows + l.r;
+    if (l.run && i < a.m) {
+      const int64_t e = base + i * KC + l.c;
+      const double sv = (a.ns == 1) ? a.S[i * KC] : a.S[e];
+      const double d = a.T[e] - sv;
+      const double w = a.obsw ? a.obsw[i] : 1.0;
+      const bool out = a.fold && a.fold[i] == hk;
+      const double wd2 = w * (d * d);
+      acc[SLW_FIT] += out ? 0.0 : wd2;
+      acc[SLW_HELD_SSE] += out ? wd2 : 0.0;
+      acc[SLW_HELD_W] += out ? w : 0.0;
+    }
+  }
+  scg_sums<SLW_COUNT>(acc, lds, a.part, SLW_COUNT, 0);
+}
+
+// T(:, k) = omega_k o s_k for every fit (the columns past K stay as they are: +0.0)
+__global__ __launch_bounds__(kScgBlock) void slm_obs_rhs_kernel(SlmObsRhsArgs a) {
+  const int c = threadIdx.x % KC, r = threadIdx.x / KC;
+  const int fit = static_cast<int>(blockIdx.y) * KC + c;
+  if (fit >= a.K) return;
+  const int64_t base = static_cast<int64_t>(blockIdx.y) * a.m * KC;
+  const int32_t hk = a.held[fit];
+  const int64_t nrb = (a.m + kScgRows - 1) / kScgRows;
+  for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int64_t i = rb * kScgRows + r;
+    if (i >= a.m) continue;
+    const int64_t e = base + i * KC + c;
+    const double sv = (a.ns == 1) ? a.S[i * KC] : a.S[e];
+    const bool out = a.fold && a.fold[i] == hk;
+    a.T[e] = out ? 0.0 : (a.obsw ? sv * a.obsw[i] : sv);
+  }
+}
+
+// blockIdx.x = fit: the two held-out totals in multi_slot_totals' order
+__global__ __launch_bounds__(kBlock) void slm_heldout_kernel(const double* part, int32_t nwg_m, double* heldout) {
+  __shared__ double S[8];
+  const int fit = blockIdx.x;
+  multi_slot_totals(part, fit, SLW_COUNT, nwg_m, S);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    heldout[2 * fit] = S[SLW_HELD_SSE];
+    heldout[2 * fit + 1] = S[SLW_HELD_W];
+  }
+}
+
 // blockIdx.x = fit: the finalize logic of the fit's iteration -- admm.m:612-658, 706-713 as oracle/admm_ref.py restates
 // it for A = 1, B = -1, c = 0, plain ADMM with stopcond = 'standard'; the dual residual takes part when a.dual is set
 __global__ __launch_bounds__(kBlock) void slm_fin_kernel(SlmFinArgs a) {
@@ -122,7 +183,8 @@ __global__ __launch_bounds__(kBlock) void slm_fin_kernel(SlmFinArgs a) {
   __shared__ double S[8];
   const int tid = threadIdx.x;
   multi_slot_totals(a.part, fit, SL_COUNT, a.nwg_n, S);
-  if (a.objevals) multi_slot_totals(a.fpart, fit, 1, a.nwg_m, S, SL_COUNT);
+  // (fit_slots = SLW_COUNT: the 32-lane groups 6 and 7 total the slots 0 and 1 into S[6] and S[7]; S[SL_COUNT] is read)
+  if (a.objevals) multi_slot_totals(a.fpart, fit, a.fit_slots, a.nwg_m, S, SL_COUNT);
   __syncthreads();
   if (tid != 0) return;
   const int i1 = it + 1;  // 1-based iteration number (admm.m loop variable)
@@ -158,6 +220,20 @@ void launch_slm_fit(const SlmFitArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(slm_fit_kernel, grid, dim3(kScgBlock), 0, stream, a);
 }
 
+void launch_slm_fit_weighted(const SlmFitArgs& a, hipStream_t stream) {
+  const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
+  hipLaunchKernelGGL(slm_fit_weighted_kernel, grid, dim3(kScgBlock), 0, stream, a);
+}
+
+void launch_slm_obs_rhs(const SlmObsRhsArgs& a, hipStream_t stream) {
+  const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
+  hipLaunchKernelGGL(slm_obs_rhs_kernel, grid, dim3(kScgBlock), 0, stream, a);
+}
+
+void launch_slm_heldout(const double* part, int32_t K, int32_t nwg_m, double* heldout, hipStream_t stream) {
+  hipLaunchKernelGGL(slm_heldout_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, stream, part, nwg_m, heldout);
+}
+
 void launch_slm_fin(const SlmFinArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(slm_fin_kernel, dim3(static_cast<unsigned>(a.K)), dim3(kBlock), 0, stream, a);
 }
@@ -176,6 +252,15 @@ struct admm_sparse_lasso : MultiHost {
   double *W = nullptr, *par = nullptr;
   int32_t* nonneg = nullptr;
   GroupMulti grp;  // admm_sparse_lasso_set_groups (q41)
+  // admm_sparse_lasso_set_observations (q46); all null: the unweighted object
+  bool obs = false;
+  double* obsw = nullptr;     // m observation weights or null
+  int32_t* fold = nullptr;    // m fold ids or null
+  int32_t* held = nullptr;    // K values (-1: nothing held out)
+  double* DTSK = nullptr;     // D'(Omega_k s_k), a multi-vector of len n
+  double* wpart = nullptr;    // the weighted fit pass's partials, SLW_COUNT per fit
+  double* held_dev = nullptr; // K x 2: the held-out error and weight of the last run
+  std::vector<double> held_sse, held_w;  // the same on the host; empty: no run under observations behind the object
   double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   admm_sparse_lasso_options last{};
 };
@@ -312,7 +397,7 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
   ea.Z = o->Z;
   ea.U = o->U;
   ea.Y = cg.Y;
-  ea.DTS = o->DTS;
+  ea.DTS = o->obs ? o->DTSK : o->DTS;
   ea.W = o->W;
   ea.par = o->par;
   ea.nonneg = o->nonneg;
@@ -320,6 +405,7 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
   ea.part = o->part;
   ea.K = K;
   ea.ns = o->ns;
+  ea.dts_ns = o->obs ? K : o->ns;
   ea.objevals = op.objevals;
   ea.rho = op.rho;
   SlmFitArgs ta{};
@@ -330,9 +416,16 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
   ta.part = o->fpart;
   ta.K = K;
   ta.ns = o->ns;
+  if (o->obs) {  // the weighted fit pass and its own partials
+    ta.part = o->wpart;
+    ta.obsw = o->obsw;
+    ta.fold = o->fold;
+    ta.held = o->held;
+  }
   SlmFinArgs fa{};
   fa.part = o->part;
-  fa.fpart = o->fpart;
+  fa.fpart = o->obs ? o->wpart : o->fpart;
+  fa.fit_slots = o->obs ? SLW_COUNT : 1;
   fa.n = o->n;
   fa.K = K;
   fa.nwg_n = o->grp.on() ? o->grp.plan.nwg : o->nwg_n;  // (the grouped kernel: one partial per workgroup of the plan)
@@ -362,14 +455,97 @@ int admm_sparse_lasso_run(admm_sparse_lasso* o, const admm_sparse_lasso_options*
     else launch_slm_elem(ea, false, o->stream);
     if (op.objevals) {
       launch_spmm(cg.sp.n, cg.X, cg.T, cg.chunks, run, o->stream);  // D x
-      launch_slm_fit(ta, o->stream);
+      if (o->obs) launch_slm_fit_weighted(ta, o->stream);
+      else launch_slm_fit(ta, o->stream);
     }
     launch_slm_fin(fa, o->stream);
     if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
+  o->held_sse.clear();
+  o->held_w.clear();
+  if (o->obs && all) {  // T = D z for every fit, stopped or not (z: the sparse iterate df counts), and the held-out sums
+    SpmmMask every;
+    every.K = K;
+    launch_spmm(cg.sp.n, o->Z, cg.T, cg.chunks, every, o->stream);
+    ta.all = 1;
+    launch_slm_fit_weighted(ta, o->stream);
+    launch_slm_heldout(o->wpart, K, o->nwg_m, o->held_dev, o->stream);
+  }
   ADMM_TRY(finish_run(*o, all, "the sparse multi-lasso loop ended with fits still running", N, op.objevals != 0, o->objv,
                       runtime_s, summaries));
+  if (o->obs) {
+    std::vector<double> hb(static_cast<size_t>(2) * K);
+    ADMM_HIP_TRY(hipMemcpy(hb.data(), o->held_dev, sizeof(double) * hb.size(), hipMemcpyDeviceToHost));
+    o->held_sse.resize(static_cast<size_t>(K));
+    o->held_w.resize(static_cast<size_t>(K));
+    for (int32_t k = 0; k < K; ++k) {
+      o->held_sse[k] = hb[2 * k];
+      o->held_w[k] = hb[2 * k + 1];
+    }
+  }
   return end_sparse_run(o, op, summaries);
+}
+
+int admm_sparse_lasso_set_observations(admm_sparse_lasso* o, const double* obsweights, int32_t nfolds, const int32_t* fold,
+                                       const int32_t* heldout) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  const int64_t m = o->m, n = o->n;
+  const int32_t K = o->K;
+  ADMM_TRY(check_observations(m, K, obsweights, nfolds, fold, heldout));  // (a refused call changes nothing)
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  const bool on = obsweights || fold;
+  double* w = nullptr;
+  int32_t *f = nullptr, *hd = nullptr;
+  if (on) {
+    const size_t kp = static_cast<size_t>(o->cg.chunks) * kSpmmChunk;
+    if (!o->DTSK) {  // what every weighted object needs, once
+      ADMM_TRY(o->mem.alloc(&o->DTSK, kp * n));
+      ADMM_HIP_TRY(hipMemsetAsync(o->DTSK, 0, sizeof(double) * kp * n, o->stream));
+      ADMM_TRY(o->mem.alloc(&o->wpart, kp * SLW_COUNT * kScgMaxWg));
+      ADMM_HIP_TRY(hipMemsetAsync(o->wpart, 0, sizeof(double) * kp * SLW_COUNT * kScgMaxWg, o->stream));
+      ADMM_TRY(o->mem.alloc(&o->held_dev, static_cast<size_t>(2) * K));
+    }
+    std::vector<int32_t> hh(static_cast<size_t>(K), -1);
+    for (int32_t k = 0; heldout && k < K; ++k) hh[k] = heldout[k];
+    ADMM_TRY(alloc_words(*o, &hd, static_cast<size_t>(K)));
+    ADMM_HIP_TRY(hipMemcpyAsync(hd, hh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
+    if (fold) {
+      ADMM_TRY(alloc_words(*o, &f, static_cast<size_t>(m)));
+      ADMM_HIP_TRY(hipMemcpyAsync(f, fold, sizeof(int32_t) * m, hipMemcpyHostToDevice, o->stream));
+    }
+    if (obsweights) {
+      ADMM_TRY(o->mem.alloc(&w, static_cast<size_t>(m)));
+      ADMM_HIP_TRY(hipMemcpyAsync(w, obsweights, sizeof(double) * m, hipMemcpyHostToDevice, o->stream));
+    }
+    // D'(Omega_k s_k) per fit: T = omega_k o s_k, one transposed product over all K fits
+    const SlmObsRhsArgs ra{m, o->S, o->cg.T, w, f, hd, K, o->ns};
+    launch_slm_obs_rhs(ra, o->stream);
+    SpmmMask every;
+    every.K = K;
+    launch_spmm(o->cg.sp.t, o->cg.T, o->DTSK, o->cg.chunks, every, o->stream);
+    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (hh and the caller's buffers were read)
+    ADMM_HIP_TRY(hipGetLastError());
+  }
+  for (void* p : {static_cast<void*>(o->obsw), static_cast<void*>(o->fold), static_cast<void*>(o->held)})
+    o->mem.free_one(p);
+  o->obsw = w;
+  o->fold = f;
+  o->held = hd;
+  o->obs = on;
+  o->cg.weighted = on;
+  o->cg.roww = SpmmRowWeights{w, f, hd, K};
+  o->held_sse.clear();
+  o->held_w.clear();
+  return ADMM_OK;
+}
+
+int admm_sparse_lasso_heldout(admm_sparse_lasso* o, double* sse, double* weight) {
+  if (!o || !sse || !weight) return fail(ADMM_E_INVALID, "object, sse or weight is NULL");
+  if (!o->has_run || o->held_sse.empty())
+    return fail(ADMM_E_INVALID, "the held-out sums need a run with observations set (admm_sparse_lasso_set_observations)");
+  std::memcpy(sse, o->held_sse.data(), sizeof(double) * o->K);
+  std::memcpy(weight, o->held_w.data(), sizeof(double) * o->K);
+  return ADMM_OK;
 }
 
 int admm_sparse_lasso_set_weights(admm_sparse_lasso* o, const double* weights) {

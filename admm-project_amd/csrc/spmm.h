@@ -28,6 +28,28 @@ struct SpmmMask {
 // column k alone.  An empty row stores +0.0.  No LDS, no atomics.
 void launch_spmm(const SpmvMat& M, const double* X, double* Y, int32_t chunks, const SpmmMask& mask, hipStream_t stream);
 
+// row weights of a forward product, one operator per column: column k stores omega_ik * (M X)_ik with
+// omega_ik = obsw_i * [fold_i != held_k].  obsw null: 1; fold null: no row is held out; held_k = -1: column k holds
+// nothing out.  All three live on the device.
+struct SpmmRowWeights {
+  const double* obsw = nullptr;   // rows shared observation weights >= 0
+  const int32_t* fold = nullptr;  // rows fold ids >= 0
+  const int32_t* held = nullptr;  // K values: the fold column k holds out, or -1 (never null)
+  int32_t K = 0;
+};
+
+// launch_spmm with the row-weighted store: the lane that stores row i writes, per live column k, +0.0 where
+// held[k] == fold[i] (a select: whatever the accumulator holds, NaN included) and otherwise acc * obsw[i] (one rounding
+// on top of launch_spmm's bits), or acc itself without obsw.  4 B (+ 8 B with obsw) more per row read; no LDS, no atomics.
+void launch_spmm_weighted(const SpmvMat& M, const double* X, double* Y, int32_t chunks, const SpmmMask& mask,
+                          const SpmmRowWeights& roww, hipStream_t stream);
+
+// what admm_sparse_lasso_set_observations and admm_op_spmm_weighted refuse, in the same words (ADMM_E_INVALID; host
+// arrays, rows and K the sizes): a negative or non-finite weight (its index named), nfolds < 1 with fold given, a fold id
+// outside [0, nfolds) (its row named), a heldout outside [-1, nfolds) (its fit named), heldout without fold
+int check_observations(int64_t rows, int32_t K, const double* obsweights, int32_t nfolds, const int32_t* fold,
+                       const int32_t* heldout);
+
 // host <-> device layout: column-major src (ld x K) into [chunks][len][kSpmmChunk] (padding columns zero) and back
 void spmm_pack(const double* src, int64_t ld, int64_t len, int32_t K, double* dst);
 void spmm_unpack(const double* src, int64_t len, int32_t K, double* dst, int64_t ld);

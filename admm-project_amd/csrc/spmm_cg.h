@@ -80,6 +80,12 @@ struct SpmmCg {
     int32_t alldone, longest;
   }* poll = nullptr;
   int cg_batch = 8;  // inner iterations enqueued between two polls of the all-done word
+  // row weights of the forward product, one operator per fit (spmm.h): with `weighted` set, solve() stores
+  // omega_k o (D V) into T for V = X in front of a warm start and V = P in an inner iteration, so that fit k solves
+  // (D' Omega_k D + shift*I) x = y_k; the transposed product and the elementwise kernels are the same.  Unset: the
+  // launches as they were.  The arrays belong to the solver.
+  bool weighted = false;
+  SpmmRowWeights roww;
 
   // the host's device and a stream of its own, D on the device, every buffer above zeroed (host->K is set)
   int build(MultiHost* host, int device, const admm_sparse_desc* D);

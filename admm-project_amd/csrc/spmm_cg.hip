@@ -304,15 +304,20 @@ int SpmmCg::begin_run(double tol, int32_t maxit, ScgArgs* a, double shift) {
 
 int SpmmCg::solve(const ScgArgs& a, bool first) {
   const SpmmMask run = mask(false), live = mask(true);
+  // T = D V, or omega_k o (D V) per fit under row weights (spmm_cg.h)
+  auto forward = [&](const double* V, const SpmmMask& mk) {
+    if (weighted) launch_spmm_weighted(sp.n, V, T, chunks, mk, roww, h->stream);
+    else launch_spmm(sp.n, V, T, chunks, mk, h->stream);
+  };
   if (!first) {  // q = D'(D x) in front of a warm start
-    launch_spmm(sp.n, X, T, chunks, run, h->stream);
+    forward(X, run);
     launch_spmm(sp.t, T, Q, chunks, run, h->stream);
   }
   launch_scg_start(a, first, h->stream);
   for (int32_t done_it = 0; done_it < a.maxit;) {
     const int32_t k = std::min(a.maxit - done_it, static_cast<int32_t>(cg_batch));
     for (int32_t c = 0; c < k; ++c) {
-      launch_spmm(sp.n, P, T, chunks, live, h->stream);
+      forward(P, live);
       launch_spmm(sp.t, T, Q, chunks, live, h->stream);
       launch_scg_step(a, h->stream);
     }

@@ -15,7 +15,7 @@ import numpy as np
 from .api import admm, getproxops
 from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "lasso_multi", "lasso_path", "grouplasso", "grouplasso_multi", "grouplasso_path", "l1classifier", "l1classifier_multi", "l1classifier_path", "l1classifier_lambda_max", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "lasso_multi", "lasso_path", "lasso_cv", "cv_folds", "cv_summary", "grouplasso", "grouplasso_multi", "grouplasso_path", "l1classifier", "l1classifier_multi", "l1classifier_path", "l1classifier_lambda_max", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection", "covarianceselection_multi",
            "covarianceselection_path", "covarianceselection_lambda_max"]
 
@@ -121,9 +121,12 @@ def _start_columns(options, rows_by_key, default=None):
     return starts
 
 
-def _sparse_refusals(options, who, also=(), stopcond=False):
+def _sparse_refusals(options, who, also=(), stopcond=False, observations=False):
     """the options no sparse multi-fit object runs, each named in its ValueError; ``also``: keys
-    refused beside comm, ``stopcond``: the object runs the 'standard' stop rule alone"""
+    refused beside comm, ``stopcond``: the object runs the 'standard' stop rule alone, ``observations``: the object takes
+    obsweights / foldid / heldout (the multi-lasso alone: q46)"""
+    if not observations:
+        _no_observations(options, who)
     for key in ("fast", "convtest", "adaptive"):
         if options.get(key, 0):
             raise ValueError(f"options.{key} is not available in {who} on a sparse D")
@@ -141,15 +144,30 @@ def _sparse_refusals(options, who, also=(), stopcond=False):
         raise ValueError(f"options.stopcond: {who} on a sparse D runs the 'standard' stop rule alone")
 
 
-def _run_and_close(obj, prepare=None, **run):
-    """``prepare(obj)`` (the weights or costs, if any), one run and the owner's results (engine._MultiOwner.results);
-    the owner is closed in any case"""
+def _run_and_close(obj, prepare=None, finish=None, **run):
+    """``prepare(obj)`` (the weights or costs, if any), one run and the owner's results (engine._MultiOwner.results),
+    which ``finish(obj, results)`` may add to while the owner lives; the owner is closed in any case"""
     try:
         if prepare is not None:
             prepare(obj)
-        return obj.results(obj.run(**run))
+        res = obj.results(obj.run(**run))
+        if finish is not None:
+            finish(obj, res)
+        return res
     finally:
         obj.close()
+
+
+_OBSERVATION_KEYS = ("obsweights", "foldid", "heldout")
+
+
+def _no_observations(options, who):
+    """observation weights and held-out folds live on the sparse multi-lasso alone: every other
+    multi-fit family names the option it refuses"""
+    for key in _OBSERVATION_KEYS:
+        if options.get(key) is not None:
+            raise ValueError(f"options.{key} is not available in {who}: observation weights and held-out folds are "
+                             "lasso_multi's, on a scipy.sparse D")
 
 
 def _stack_fits(per, hist_keys):
@@ -291,8 +309,11 @@ def _per_fit(value, K, name, check):
     return out
 
 
-def _lambda_max(D, S, w):
-    """per column of S the smallest lambda whose lasso solution is x = 0: max over w_i > 0 of |(D's)_i| / w_i"""
+def _lambda_max(D, S, w, obsw=None):
+    """per column of S the smallest lambda whose lasso solution is x = 0: max over w_i > 0 of |(D's)_i| / w_i; under
+    observation weights ``obsw`` the product is D'(obsw o s)"""
+    if obsw is not None:
+        S = np.asarray(S, dtype=np.float64) * (obsw if np.ndim(S) == 1 else obsw[:, None])
     g = np.abs(np.asarray(D.T @ S, dtype=np.float64)).reshape(D.shape[1], -1)
     if w is not None:
         live = w > 0
@@ -338,7 +359,11 @@ def _lambda_grid(D, s, options, default_n, lmax_of=None):
         raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
     if lmax_of is None:
         pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
-        lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"])[0])
+        obsw = options.get("obsweights")
+        if obsw is not None:
+            from .sparse_lasso import observation_arrays
+            obsw = observation_arrays(obsw, None, None, D.shape[0], 1)[0]
+        lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"], obsw)[0])
     else:
         lmax = float(lmax_of())
     return lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
@@ -349,17 +374,30 @@ def _run_multi_lasso(D, S, lams, options, who, sparse, t0, groups=None):
     grouplasso_multi on either: the refusals, the fits, the owner, one run.  ``groups``: the sizes of grouplasso_multi;
     options.groupweights and options.l1 are read beside them alone, and the result carries ``groups``"""
     if sparse:
-        _sparse_refusals(options, who, stopcond=True)
+        _sparse_refusals(options, who, stopcond=True, observations=True)
     else:
         _dense_multi_refusals(options, who)
     D = _matrix(D, "D", sparse_ok=sparse)
     S, lam, ridge, nonneg, w, starts = _multi_lasso_fits(D, S, lams, options)
     n, K = D.shape[1], int(lam.size)
-    prepare = None
+    prepare, finish = None, None
+    obs = None
+    if sparse and any(options.get(key) is not None for key in _OBSERVATION_KEYS):
+        from .sparse_lasso import observation_arrays
+        obs = observation_arrays(options.get("obsweights"), options.get("foldid"), options.get("heldout"), D.shape[0], K)
     if groups is not None:
         sizes, gw = group_sizes(groups, options.get("groupweights"), n)
         l1 = _per_fit(options.get("l1", 0.0), K, "l1", lambda v: penalty_fields(dict(l1=v), n)["l1"])
-        prepare = lambda obj: obj.set_groups(sizes, gw, l1)
+
+    def prepare(obj):
+        if groups is not None:
+            obj.set_groups(sizes, gw, l1)
+        if obs is not None:
+            obj.set_observations(obs[0], obs[1], obs[2])
+
+    if obs is not None:
+        def finish(obj, res):
+            res["heldout_sse"], res["heldout_weight"] = obj.heldout()
     if not sparse and D.shape[0] < n:
         raise ValueError(f"{who} needs m >= n: the fat lasso's x-update (two dense products per fit) stays with lasso, "
                          "one call per fit")
@@ -374,7 +412,7 @@ def _run_multi_lasso(D, S, lams, options, who, sparse, t0, groups=None):
         obj = LassoMulti(D, S, lam, ridge, nonneg, w, rho=float(options.get("rho", 1.0)),
                          xsolve=options.get("xsolve", "auto"), device=int(options.get("device", 0)))
         run.update(_pick(options, _LOOP_KEYS))
-    res = _run_and_close(obj, prepare, **run)
+    res = _run_and_close(obj, prepare, finish, **run)
     res["lams"] = lam.copy()
     if groups is not None:
         res["groups"] = sizes.copy()
@@ -401,7 +439,13 @@ def lasso_multi(D, S, lams, options=None):
     unless nodualerror = 1, objevals with options['objevals'], objopt (K), runtime, solverruntime, chunk, lams,
     ``xsolve = 'cg'``, ``nnz``, ``cg_iters_total`` and ``cg_capped_updates`` (K values each).  fast, convtest, relax,
     adaptive, an xsolve other than 'auto' / 'cg', comm, parallel and a stopcond other than 'standard' are refused by
-    name."""
+    name.
+
+    Observations: ``options['obsweights']`` (m values >= 0 shared by all fits), ``options['foldid']`` (m
+    integer fold ids >= 0) and ``options['heldout']`` (K integers: the fold fit k leaves out, -1 for none) turn the fit
+    term of fit k into 1/2*sum_i omega_ik*(d_i'x - s_ik)^2 with omega_ik = obsweights_i * [foldid_i != heldout_k].  The
+    result then carries ``heldout_sse`` and ``heldout_weight`` (K values each): the weighted squared error of zopt on
+    the rows the fit held out, and their total weight.  ``lasso_cv`` builds a cross-validation out of them."""
     options = _options(options, "Argument options is not a struct!", optional=True)
     t0 = time.perf_counter()
     from ._lib import is_sparse
@@ -415,7 +459,8 @@ def lasso_path(D, s, lams=None, options=None):
     in one run of ``lasso_multi``.  ``lams = None``: ``options['nlambda']`` values (default: the chunk of
     the sparse product, 10), log-spaced from lambda_max = max over w_i > 0 of |(D's)_i| / w_i -- the smallest lambda whose
     solution is x = 0 -- down to ``options['lambda_min_ratio']`` * lambda_max (default 1e-2).  Returns lasso_multi's
-    fields plus ``df``, the number of nonzeros of each zopt column.  A dense D raises ValueError: ``lasso_path_dense``."""
+    fields plus ``df``, the number of nonzeros of each zopt column.  A dense D raises ValueError: ``lasso_path_dense``.
+    Under ``options['obsweights']`` lambda_max is taken from D'(obsweights o s)."""
     options = _options(options, "Argument options is not a struct!", optional=True)
     from ._lib import is_sparse
     if not is_sparse(D):
@@ -431,6 +476,137 @@ def lasso_path(D, s, lams=None, options=None):
     return res
 
 
+def cv_folds(m, nfolds, seed=0):
+    """the default fold of each of m observations: ``np.random.default_rng(seed).permutation(m) % nfolds``"""
+    return (np.random.default_rng(seed).permutation(int(m)) % int(nfolds)).astype(np.int64)
+
+
+def cv_summary(sse, weight, lams):
+    """The cross-validation curve from the held-out sums.  ``sse`` and ``weight`` are F x L (fold f, lambda
+    l): the weighted squared error on the rows fold f held out and their total weight; ``lams`` the L values.  Returns
+
+        cvm        L values: sum_f sse_fl / sum_f weight_fl, the weighted mean of the folds' own errors e_fl = sse_fl / weight_fl
+        cvsd       the weighted standard error over folds: sqrt(sum_f weight_fl*(e_fl - cvm_l)^2 / sum_f weight_fl / (F - 1))
+                   (NaN for F = 1)
+        index_min  where cvm is smallest; among equal values the largest lambda
+        lam_min    lams[index_min]
+        index_1se  the largest lambda with cvm <= cvm[index_min] + cvsd[index_min] (index_min itself when cvsd is NaN)
+        lam_1se    lams[index_1se]
+
+    A fold of zero weight takes no part in either sum."""
+    sse = np.atleast_2d(np.asarray(sse, dtype=np.float64))
+    weight = np.atleast_2d(np.asarray(weight, dtype=np.float64))
+    lams = np.asarray(lams, dtype=np.float64).reshape(-1)
+    if sse.shape != weight.shape or sse.shape[1] != lams.size:
+        raise ValueError(f"sse {sse.shape} and weight {weight.shape} must both be folds x {lams.size} lambdas")
+    F = sse.shape[0]
+    wsum = weight.sum(axis=0)
+    cvm = sse.sum(axis=0) / wsum
+    live = weight > 0
+    e = np.divide(sse, weight, out=np.zeros_like(sse), where=live)
+    dev = np.where(live, weight * (e - cvm[None, :]) ** 2, 0.0)
+    cvsd = np.sqrt(dev.sum(axis=0) / wsum / (F - 1)) if F > 1 else np.full(lams.size, np.nan)
+
+    def largest_lambda(mask):
+        idx = np.flatnonzero(mask)
+        return int(idx[np.argmax(lams[idx])])
+
+    index_min = largest_lambda(cvm == np.min(cvm))
+    bar = cvm[index_min] + cvsd[index_min]
+    index_1se = largest_lambda(cvm <= bar) if np.isfinite(bar) else index_min
+    return dict(cvm=cvm, cvsd=cvsd, index_min=index_min, lam_min=float(lams[index_min]), index_1se=index_1se,
+                lam_1se=float(lams[index_1se]))
+
+
+def lasso_cv(D, s, lams=None, options=None):
+    """results = lasso_cv(D, s, lams, options): F-fold cross-validation of the lasso's regularisation path on a sparse D,
+    every fold fit and every full-data fit side by side in ONE run of ``lasso_multi`` over one upload of D (DESIGN.md
+    q46).  ``lams = None``: ``lasso_path``'s grid (``nlambda``, default 10; ``lambda_min_ratio``, default 1e-2;
+    lambda_max under ``obsweights`` from D'(obsweights o s)).  With L lambdas and F = ``options['nfolds']`` (default 5)
+    the object holds (F + 1)*L fits: fit f*L + l leaves fold f out at lambda_l, fits F*L + l see every row.
+
+    ``options['foldid']``: m fold ids in [0, nfolds); absent: ``cv_folds(m, nfolds, options.get('seed', 0))``.  A fold fit
+    runs at lambda_l * (training weight of fold f / total weight): one lambda sequence on the per-observation scale, as
+    glmnet poses it, written for this unnormalised objective; ``options['scale_lambda'] = 0`` runs every fold at
+    lambda_l itself.  ``obsweights``, ``l1weights``, ``ridge`` and ``nonnegative`` (scalars or L values), and the loop /
+    CG options are lasso_multi's; ``z0`` / ``u0`` (n x L) start every fold alike.
+
+    Returns lams, foldid, ``cv_summary``'s cvm, cvsd, index_min, lam_min, index_1se, lam_1se; xopt, zopt, uopt (n x L),
+    df, steps, objopt of the full-data fits; fold_steps, fold_lams, heldout_sse, heldout_weight (F x L); nnz,
+    cg_iters_total and cg_capped_updates over all (F + 1)*L fits, runtime and solverruntime."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    t0 = time.perf_counter()
+    from ._lib import is_sparse
+    if not is_sparse(D):
+        raise ValueError("lasso_cv runs on a scipy.sparse D")
+    s = _colvec(s, "s")
+    m, n = D.shape
+    F = options.pop("nfolds", 5)
+    if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or F < 2:
+        raise ValueError("options.nfolds must be an integer >= 2")
+    F = int(F)
+    seed = options.pop("seed", 0)
+    scale = bool(options.pop("scale_lambda", 1))
+    if options.get("heldout") is not None:
+        raise ValueError("options.heldout is lasso_cv's own to set: give options.foldid")
+    options.pop("heldout", None)
+    if s.size != m:
+        raise ValueError("The number of rows in argument D do not match size of s!")
+    from .sparse_lasso import observation_arrays
+    if options.get("foldid") is None:
+        foldid = cv_folds(m, F, seed)
+    else:
+        foldid = observation_arrays(None, options["foldid"], None, m, 1)[1].astype(np.int64)
+        if foldid.min() < 0 or foldid.max() >= F:
+            raise ValueError(f"options.foldid: every fold id must lie in [0, nfolds = {F})")
+    obsw = observation_arrays(options.get("obsweights"), None, None, m, 1)[0]
+    if lams is None:
+        lams = _lambda_grid(D, s, options, 10)
+    else:
+        options.pop("nlambda", None)
+        options.pop("lambda_min_ratio", None)
+    lams = np.asarray(lams, dtype=np.float64).reshape(-1)
+    L = int(lams.size)
+    if L < 1:
+        raise ValueError("lams must hold at least one lambda")
+    w = np.ones(m) if obsw is None else obsw
+    total = float(w.sum())
+    train = np.array([total - float(w[foldid == f].sum()) for f in range(F)])
+    if not total > 0.0:
+        raise ValueError("options.obsweights: the total weight must be positive")
+    frac = train / total if scale else np.ones(F)
+    fold_lams = frac[:, None] * lams[None, :]
+    o = dict(options)
+    o["foldid"] = foldid
+    o["heldout"] = np.concatenate([np.repeat(np.arange(F), L), np.full(L, -1)])
+    for key in ("ridge", "nonnegative"):  # scalars, or L values for every fold alike
+        if key in o and not (np.isscalar(o[key]) or isinstance(o[key], (bool, np.bool_))):
+            v = np.asarray(o[key]).reshape(-1)
+            if v.size != L:
+                raise ValueError(f"{key} has {v.size} entries for {L} lambdas")
+            o[key] = np.tile(v, F + 1)
+    for key in ("x0", "z0", "u0"):
+        if o.get(key) is not None:
+            v = np.asarray(o[key], dtype=np.float64)
+            if v.shape != (n, L):
+                raise ValueError(f"options.{key} is not a {n} x {L} matrix (one column per lambda)!")
+            o[key] = np.asfortranarray(np.tile(v, (1, F + 1)))
+    res = lasso_multi(D, s, np.concatenate([fold_lams.reshape(-1), lams]), o)
+    full = slice(F * L, (F + 1) * L)
+    sse = res["heldout_sse"][:F * L].reshape(F, L)
+    wt = res["heldout_weight"][:F * L].reshape(F, L)
+    out = dict(lams=lams.copy(), foldid=foldid, **cv_summary(sse, wt, lams))
+    for key in ("xopt", "zopt", "uopt"):
+        out[key] = np.asfortranarray(res[key][:, full])
+    out["df"] = np.count_nonzero(out["zopt"], axis=0).astype(np.int64)
+    out.update(steps=res["steps"][full], objopt=res["objopt"][full], fold_steps=res["steps"][:F * L].reshape(F, L),
+               fold_lams=fold_lams, heldout_sse=sse, heldout_weight=wt, nnz=res["nnz"],
+               cg_iters_total=res["cg_iters_total"], cg_capped_updates=res["cg_capped_updates"], chunk=res["chunk"],
+               runtime=res["runtime"])
+    out["solverruntime"] = time.perf_counter() - t0
+    return out
+
+
 def _dense_multi_refusals(options, who):
     """the options the dense multi-lasso does not run, each named in its ValueError"""
     for key in ("fast", "convtest", "adaptive"):
@@ -440,6 +616,7 @@ def _dense_multi_refusals(options, who):
         raise ValueError(f"options.relax is not available in {who}")
     from .lasso_multi import xsolve_code
     xsolve_code(options.get("xsolve", "auto"))
+    _no_observations(options, who)  # (one Gram matrix serves all fits of a dense object: q46)
     if options.get("comm") is not None:
         raise ValueError(f"options.comm is not available in {who}")
     if options.get("parallel", "none") not in ("none", 0, None):

@@ -12,6 +12,35 @@ from . import _lib as L
 from .engine import _MultiOwner, _set_multi_groups, _weights
 
 
+def _int_ids(a, count, what, name):
+    """integer ids as contiguous int32: ``count`` entries, one per ``what``; a non-integer value is a ValueError (a cast
+    would truncate 1.5 to 1 without a word)"""
+    v = np.asarray(a)
+    if v.dtype == object or not (np.issubdtype(v.dtype, np.integer) or np.issubdtype(v.dtype, np.floating)
+                                 or v.dtype == np.bool_):
+        raise ValueError(f"{name} must hold integers")
+    v = v.reshape(-1)
+    if v.size != count:
+        raise ValueError(f"{name} has {v.size} entries for {count} {what}")
+    g = v.astype(np.float64)
+    if not np.all(np.isfinite(g)) or np.any(g != np.floor(g)) or np.any(np.abs(g) >= 2.0 ** 31):
+        raise ValueError(f"{name} must hold integers")
+    return np.ascontiguousarray(g.astype(np.int32))
+
+
+def observation_arrays(obsweights, fold, heldout, m, K):
+    """(obsweights float64 | None, fold int32 | None, heldout int32 | None, nfolds) with the shape and dtype checks of
+    ``SparseLassoMulti.set_observations``, each a ValueError that names its argument; the values are the library's to
+    check, except what needs no device and no library: heldout without fold"""
+    w = _weights(obsweights, m, "observations", "obsweights")
+    f = None if fold is None else _int_ids(fold, m, "observations", "foldid")
+    h = None if heldout is None else _int_ids(heldout, K, "fits", "heldout")
+    if h is not None and f is None:
+        raise ValueError("heldout needs foldid: the fold of every observation")
+    nfolds = 0 if f is None else int(max(int(f.max(initial=-1)) + 1, 1))
+    return w, f, h, nfolds
+
+
 class SparseLassoMulti(_MultiOwner):
     """``SparseLassoMulti(D, S, lams, ridge, nonnegative, l1weights)``: ``D`` any ``scipy.sparse`` matrix or array
     (converted to canonical CSC); ``S`` is m x 1 (one response shared by all fits) or m x K (one column per fit);
@@ -56,6 +85,23 @@ class SparseLassoMulti(_MultiOwner):
         """n l1 weights >= 0 shared by all fits (admm_sparse_lasso_set_weights); None restores 1"""
         w = _weights(l1weights, self.n, "coefficients", "l1weights")
         L.check(self._lib.admm_sparse_lasso_set_weights(self._h, None if w is None else L.as_dp(w)))
+
+    def set_observations(self, obsweights=None, fold=None, heldout=None):
+        """Observation weights and held-out folds for every later run (admm_sparse_lasso_set_observations; DESIGN.md
+        q46): ``obsweights`` = m values >= 0 shared by all fits (None: 1), ``fold`` = m integer fold ids >= 0 (None: no
+        row is held out), ``heldout`` = K integers, the fold fit k leaves out or -1 (None: -1 everywhere).  All None
+        restores the unweighted object."""
+        w, f, h, nfolds = observation_arrays(obsweights, fold, heldout, self.m, self.K)
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        L.check(self._lib.admm_sparse_lasso_set_observations(self._h, None if w is None else L.as_dp(w), nfolds, ip(f),
+                                                             ip(h)))
+
+    def heldout(self):
+        """(sse, weight) of the last run under observations, K values each: the weighted squared error of zopt on the
+        rows fit k held out and their total weight (admm_sparse_lasso_heldout)"""
+        sse, wt = np.empty(self.K), np.empty(self.K)
+        L.check(self._lib.admm_sparse_lasso_heldout(self._h, L.as_dp(sse), L.as_dp(wt)))
+        return sse, wt
 
     def run(self, *, cg_tol=0.0, cg_maxit=0, nodualerror=0, z0=None, u0=None, **loop):
         """``loop``: rho, maxiters, abstol, reltol, relax, fast, convtest, domaxiters, objevals, check_every;

@@ -13,7 +13,7 @@ import numpy as np
 from . import solvers, synth
 
 __all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "sparsequantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "l1classifiertest", "basispursuittest",
-           "linearprogramtest", "modeltest", "covarianceselectiontest", "covarianceselectionpathtest", "solvertester"]
+           "linearprogramtest", "modeltest", "covarianceselectiontest", "covarianceselectionpathtest", "sparselassocvtest", "solvertester"]
 
 
 def _opts(options, **forced):
@@ -172,6 +172,38 @@ def sparselassopathtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, nlambda
     lams = lmax * np.concatenate([[1.25], np.logspace(np.log10(0.8), -2.0, int(nlambda) - 1)])
     results = solvers.lasso_path(D, s, lams, _opts(options, objevals=1, quiet=quiet))
     return _path_test(p, lams, results)
+
+
+def sparselassocvtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, nfolds=5, nlambda=10, quiet=1, options=None):
+    """Cross-validation of the lasso's path on a sparse design matrix: lasso_cv on
+    synth.sparse_lasso_path_problem with ``nfolds`` folds over ``nlambda`` values, the first one 1.25*lambda_max and the
+    others log-spaced from 0.8*lambda_max down to 0.01*lambda_max -- (nfolds + 1)*nlambda fits in one run.  Pass when
+    every fold fit whose lambda lies above the lambda_max of its own training rows predicts 0 on its held-out rows (its
+    held-out error is the sum of s^2 there), the held-out weights are the fold sizes, the selected lambda lies inside the
+    path (cvm[index_min] < cvm[0]), lam_1se >= lam_min, and the full-data fits meet the path's own criteria.  Returns
+    the ``test`` dict alone; the solver's results are ``test['results']``."""
+    p = synth.sparse_lasso_path_problem(seed, rows, cols, density)
+    D, s, lmax = p["D"], p["s"], p["lmax"]
+    lams = lmax * np.concatenate([[1.25], np.logspace(np.log10(0.8), -2.0, int(nlambda) - 1)])
+    results = solvers.lasso_cv(D, s, lams, _opts(options, nfolds=int(nfolds), seed=seed, objevals=1, quiet=quiet))
+    fold = results["foldid"]
+    sizes = np.bincount(fold, minlength=int(nfolds)).astype(np.float64)
+    null = np.array([float(np.sum(s[fold == f] ** 2)) for f in range(int(nfolds))])
+    weights_ok = bool(np.array_equal(results["heldout_weight"], np.repeat(sizes[:, None], lams.size, axis=1)))
+    own = np.array([float(np.max(np.abs(D.T @ (s * (fold != f))))) for f in range(int(nfolds))])
+    above = results["fold_lams"] >= own[:, None]  # (F x L: the fold fit's solution is z = 0)
+    null_ok = bool(np.all(np.abs(results["heldout_sse"] - null[:, None])[above] <= 1e-12 * np.repeat(
+        null[:, None], lams.size, axis=1)[above]))
+    selects = bool(results["cvm"][results["index_min"]] < results["cvm"][0]) and results["lam_1se"] >= results["lam_min"]
+    path = dict(results)
+    path["perr"] = np.full((int(results["steps"][0]), lams.size), np.inf)  # (lasso_cv keeps no histories)
+    test = _path_test(p, lams, path)
+    zero_x = bool(np.all(results["zopt"][:, 0] == 0.0))
+    test.update(results=results, cvm=results["cvm"], cvsd=results["cvsd"], lam_min=results["lam_min"],
+                lam_1se=results["lam_1se"], weights_ok=weights_ok, null_ok=null_ok, null_fits=int(above.sum()),
+                selects=selects,
+                failed=int(not (zero_x and test["support_grows"] and weights_ok and null_ok and selects)))
+    return test
 
 
 def _path_test(p, lams, results):

@@ -634,6 +634,14 @@ int admm_op_spmv(const admm_sparse_desc* D, int transpose, const double* x, doub
  * kernel of the sparse linear SVM (admm_sparse_svm_create; csrc/spmm.hip): one read of D per chunk of
  * admm_sparse_svm_chunk() columns, and column k of Y has the bits admm_op_spmv returns for column k of X */
 int admm_op_spmm(const admm_sparse_desc* D, int transpose, int K, const double* X, double* Y);
+/* Y(:, k) = omega_k o (D*X(:, k)), omega_ik = obsweights[i] * [fold[i] != heldout[k]]: the forward product of the lasso
+ * under observations (admm_sparse_lasso_set_observations, whose arguments and refusals these are) on host
+ * arrays, X cols x K and Y rows x K column-major.  Column k has admm_op_spmm's bits times obsweights[i] (one rounding),
+ * or those bits themselves without obsweights; a held-out row is +0.0 whatever the product holds (a select, not a
+ * multiplication by zero).  The operator itself checks that the columns past K of the last chunk stay +0.0
+ * (ADMM_E_NUMERIC).  Every refusal fires before a device is touched. */
+int admm_op_spmm_weighted(const admm_sparse_desc* D, int32_t K, const double* X, const double* obsweights, int32_t nfolds,
+                          const int32_t* fold, const int32_t* heldout, double* Y);
 /* X(:, k) = conjugate gradients on (D'D + shift*I) x = Y(:, k) for K right-hand sides in lock-step: ONE solve of the
  * x-update the sparse multi-fit solvers share (csrc/spmm_cg.hip), through the object, the host loop and
  * the kernels of a run.  Y, X0, X and R are cols x K, column-major on the host.  X0 == NULL: from x = 0 (the first solve
@@ -1236,6 +1244,24 @@ int admm_sparse_lasso_set_weights(admm_sparse_lasso* obj, const double* weights)
  * refused call changes nothing. */
 int admm_sparse_lasso_set_groups(admm_sparse_lasso* obj, int32_t G, const int64_t* sizes, const double* groupweights,
                                  const double* l1);
+/* Observation weights and held-out folds for every later run (additive to ABI 5): the fit term of fit k
+ * becomes 1/2*sum_i omega_ik*(d_i'x - s_ik)^2 with omega_ik = obsweights[i] * [fold[i] != heldout[k]] -- weighted least
+ * squares under the same penalties, and K fits that each leave one fold of rows out, over one D.  obsweights: rows HOST
+ * values >= 0 shared by all fits (NULL = 1); fold: rows fold ids in [0, nfolds) (NULL: no row is held out); heldout: K
+ * values in [-1, nfolds), -1 (and NULL) = the fit holds nothing out.  All copied at the call.  The x-update solves
+ * (D'Omega_k D + rho*I) x = D'(Omega_k s_k) + rho*(z - u) by the same lock-step CG, whose forward product stores
+ * omega_ik*(D p)_i per fit (a held-out row stores +0.0 by a select); the z-update, the residuals and the stop rule are
+ * unchanged, the objective (objevals = 1) carries the weighted fit term, and groups (admm_sparse_lasso_set_groups)
+ * combine with it.  All three NULL restore the unweighted object, bit for bit.  ADMM_E_INVALID, the culprit named: a
+ * negative or non-finite weight (its index), nfolds < 1 with fold given, a fold id outside [0, nfolds) (its row), a
+ * heldout outside [-1, nfolds) (its fit), heldout without fold.  A refused call changes nothing. */
+int admm_sparse_lasso_set_observations(admm_sparse_lasso* obj, const double* obsweights, int32_t nfolds,
+                                       const int32_t* fold, const int32_t* heldout);
+/* The held-out sums of the last run under observations, K doubles each, evaluated behind the loop at z (the sparse
+ * iterate) for every fit: sse[k] = sum_i obsweights[i]*[fold[i] = heldout[k]]*(d_i'z_k - s_ik)^2 and weight[k] =
+ * sum_i obsweights[i]*[fold[i] = heldout[k]] (both 0.0 for a fit that holds nothing out).  ADMM_E_INVALID before a run
+ * or when the last run had no observations set. */
+int admm_sparse_lasso_heldout(admm_sparse_lasso* obj, double* sse, double* weight);
 /* fits one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
 int admm_sparse_lasso_chunk(void);
 void admm_sparse_lasso_destroy(admm_sparse_lasso* obj);
