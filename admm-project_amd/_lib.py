@@ -573,6 +573,8 @@ _SIGNATURES = {
     "admm_sparse_l1class_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_sparse_l1class_set_cost": (C.c_int, [C.c_void_p, _dp, _dp]),
     "admm_sparse_l1class_set_l1weights": (C.c_int, [C.c_void_p, _dp]),
+    "admm_sparse_l1class_set_folds": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "admm_sparse_l1class_heldout": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "admm_sparse_l1class_chunk": (C.c_int, []),
     "admm_sparse_l1class_kernel_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                                   C.POINTER(C.c_double)]),

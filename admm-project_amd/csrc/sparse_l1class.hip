@@ -16,6 +16,9 @@
 //   sl1c_elem_kernel              over n: z2, u2, the next Y = G + (z2 - u2), the n-block's sums, the dual residual's two
 //                                 norms, the penalty
 //   l1c_fin_kernel                l1class.hip's, per fit: pnorm, perr, dnorm, derr, the objective, the stop decision
+// With folds set (admm_sparse_l1class_set_folds, q47) fit k's cost on row i is 0 where fold_i = held_k -- a select in the
+// row kernel's FOLD instantiation; D'D + I holds no cost, so nothing else of the iteration changes -- and behind the loop
+// one product T = D Z2 over every fit and sl1c_heldout_kernel give the held-out loss, weighted errors and weight.
 // A fit whose stop flag is set is FROZEN, and a fit whose solve is done is masked until the next solve: every kernel and
 // every product skips it.  No atomics; every sum runs in an order the sizes fix: two runs give the same bits, and a fit
 // gets the same numbers wherever it lands.
@@ -50,6 +53,28 @@ struct Sl1cRowArgs {
   double* part;        // [fit][LM_COUNT][kScgMaxWg]
   int32_t K, ell_shared, objevals;
   double rho, C;
+  // held-out folds (admm_sparse_l1class_set_folds, q47), read by the FOLD instantiation alone; behind every other member,
+  // so that the kernels without folds load their arguments from the offsets they always had
+  const int32_t* fold;  // m fold ids, or null: no folds
+  const int32_t* held;  // K values: the fold fit k holds out, or -1
+};
+
+// the sums of the held-out pass over m (q47), per fit over the rows with fold_i = held_k, c = w_i * class cost: the loss
+// sum c*phi(ell*t) without the factor C, the weighted errors sum c*[ell*t <= 0] and the weight sum c
+enum Sl1cHeldSlot : int32_t { LH_LOSS = 0, LH_ERR = 1, LH_W = 2, LH_COUNT = 3 };
+
+struct Sl1cHeldArgs {
+  int64_t m;
+  const double* T;     // D Z2
+  const double* ELL;   // as Sl1cRowArgs
+  const double* W;     // m weights or null
+  const double* CC;    // K x 2 class costs
+  const int32_t* loss;
+  const int32_t* fold;  // m fold ids (never null)
+  const int32_t* held;  // K values
+  const MultiRec* rec;
+  double* part;        // [fit][LH_COUNT][kScgMaxWg]
+  int32_t K, ell_shared;
 };
 
 struct Sl1cElemArgs {
@@ -66,8 +91,10 @@ struct Sl1cElemArgs {
   double rho;
 };
 
-// thread t: row t / KC of a row block, fit t % KC of the chunk (scg_lane).  INIT: only T1 = z1 - u1 of the start vectors
-template <bool INIT>
+// thread t: row t / KC of a row block, fit t % KC of the chunk (scg_lane).  INIT: only T1 = z1 - u1 of the start vectors.
+// FOLD (q47): the row's weight is +0.0 where the fit holds the row's fold out -- a select in front of svm_cost_of, so the
+// cost is 0 and the prox returns D x + u1 bit for bit; 4 B more per row, one word per thread in front of the loop
+template <bool INIT, bool FOLD = false>
 __global__ __launch_bounds__(kScgBlock) void sl1c_row_kernel(Sl1cRowArgs a) {
   __shared__ double lds[LM_COUNT * kScgBlock];
   const ScgLane l = scg_lane(a.rec, a.K);
@@ -78,6 +105,8 @@ __global__ __launch_bounds__(kScgBlock) void sl1c_row_kernel(Sl1cRowArgs a) {
   for (int q = 0; q < LM_COUNT; ++q) acc[q] = 0.0;
   const int fit = l.run ? l.fit : 0;
   const SvmCostArgs ks{nullptr, a.CC[2 * fit], a.CC[2 * fit + 1], a.C, a.rho, a.loss[fit], a.objevals};
+  int32_t hk = -1;
+  if constexpr (FOLD) hk = a.held[fit];
   const int64_t nrb = (a.m + kScgRows - 1) / kScgRows;
   for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
     const int64_t i = rb * kScgRows + l.r;
@@ -89,7 +118,8 @@ __global__ __launch_bounds__(kScgBlock) void sl1c_row_kernel(Sl1cRowArgs a) {
     } else {
       const double ax = a.AX[e];
       const double el = a.ell_shared ? a.ELL[i * KC] : a.ELL[e];
-      const double wv = a.W ? a.W[i] : 1.0;
+      double wv = a.W ? a.W[i] : 1.0;
+      if constexpr (FOLD) wv = (hk == a.fold[i]) ? 0.0 : wv;
       const double ci = svm_cost_of(ks, wv, el);
       const double zn = svm_cost_prox_elem<true>(ks, ci, el, ax + uo);
       const double rr = ax - zn;      // A x + B z - c
@@ -106,6 +136,45 @@ __global__ __launch_bounds__(kScgBlock) void sl1c_row_kernel(Sl1cRowArgs a) {
   }
   if (INIT) return;
   scg_sums<LM_COUNT>(acc, lds, a.part, LM_COUNT, 0);
+}
+
+// behind the loop, at T = D Z2 (q47): the three held-out sums of EVERY fit, stopped or not, in the row kernel's thread
+// layout and scg_sums' order.  A row the fit does not hold out adds +0.0 by a select; held = -1 matches no fold id
+__global__ __launch_bounds__(kScgBlock) void sl1c_heldout_kernel(Sl1cHeldArgs a) {
+  __shared__ double lds[LH_COUNT * kScgBlock];
+  ScgLane l = scg_lane(a.rec, a.K);
+  l.run = l.fit < a.K;
+  if (!__syncthreads_or(l.run)) return;
+  const int64_t base = static_cast<int64_t>(blockIdx.y) * a.m * KC;
+  double acc[LH_COUNT] = {0.0, 0.0, 0.0};
+  const int fit = l.run ? l.fit : 0;
+  const SvmCostArgs ks{nullptr, a.CC[2 * fit], a.CC[2 * fit + 1], 1.0, 1.0, a.loss[fit], 1};
+  const int32_t hk = a.held[fit];
+  const int64_t nrb = (a.m + kScgRows - 1) / kScgRows;
+  for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int64_t i = rb * kScgRows + l.r;
+    if (!l.run || i >= a.m) continue;
+    const int64_t e = base + i * KC + l.c;
+    const double el = a.ell_shared ? a.ELL[i * KC] : a.ELL[e];
+    const double wv = a.W ? a.W[i] : 1.0;
+    const double ci = svm_cost_of(ks, wv, el);
+    const double q = el * a.T[e];
+    const bool out = a.fold[i] == hk;
+    const double lv = svm_cost_obj_elem<true>(ks, ci, q);
+    acc[LH_LOSS] += out ? lv : 0.0;
+    acc[LH_ERR] += (out && q <= 0.0) ? ci : 0.0;
+    acc[LH_W] += out ? ci : 0.0;
+  }
+  scg_sums<LH_COUNT>(acc, lds, a.part, LH_COUNT, 0);
+}
+
+// blockIdx.x = fit: the three held-out totals in multi_slot_totals' order
+__global__ __launch_bounds__(kBlock) void sl1c_heldout_total_kernel(const double* part, int32_t nwg_m, double* heldout) {
+  __shared__ double S[8];
+  const int fit = blockIdx.x;
+  multi_slot_totals(part, fit, LH_COUNT, nwg_m, S);
+  __syncthreads();
+  if (threadIdx.x < LH_COUNT) heldout[LH_COUNT * fit + threadIdx.x] = S[threadIdx.x];
 }
 
 // the same thread layout over n.  INIT: only Y = D'(z1 - u1) + (z2 - u2) of the start vectors
@@ -136,7 +205,15 @@ __global__ __launch_bounds__(kScgBlock) void sl1c_elem_kernel(Sl1cElemArgs a) {
 void launch_sl1c_row(const Sl1cRowArgs& a, bool init, hipStream_t stream) {
   const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
   if (init) hipLaunchKernelGGL(sl1c_row_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
+  else if (a.fold) hipLaunchKernelGGL((sl1c_row_kernel<false, true>), grid, dim3(kScgBlock), 0, stream, a);
   else hipLaunchKernelGGL(sl1c_row_kernel<false>, grid, dim3(kScgBlock), 0, stream, a);
+}
+
+void launch_sl1c_heldout(const Sl1cHeldArgs& a, int32_t nwg_m, double* heldout, hipStream_t stream) {
+  const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
+  hipLaunchKernelGGL(sl1c_heldout_kernel, grid, dim3(kScgBlock), 0, stream, a);
+  hipLaunchKernelGGL(sl1c_heldout_total_kernel, dim3(static_cast<unsigned>(a.K)), dim3(kBlock), 0, stream, a.part, nwg_m,
+                     heldout);
 }
 
 void launch_sl1c_elem(const Sl1cElemArgs& a, bool init, hipStream_t stream) {
@@ -161,6 +238,10 @@ struct admm_sparse_l1class : admm::MultiHost {
   double *W = nullptr, *CC = nullptr, *LW = nullptr, *par = nullptr;
   int32_t *loss = nullptr, *nonneg = nullptr;
   std::vector<double> cost_host;
+  // admm_sparse_l1class_set_folds (q47); fold null: the object without folds
+  int32_t *fold = nullptr, *held = nullptr;  // m fold ids; K values (-1: nothing held out)
+  double *hpart = nullptr, *held_dev = nullptr;  // the held-out pass's own partials; K x LH_COUNT totals
+  std::vector<double> held_host;  // the same on the host; empty: no run under folds behind the object
   double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   admm_sparse_l1class_options last{};
 };
@@ -272,6 +353,8 @@ Sl1cRowArgs sl1c_row_args(const admm_sparse_l1class* o, bool dual, int32_t objev
   a.objevals = objevals;
   a.rho = rho;
   a.C = o->C;
+  a.fold = o->fold;
+  a.held = o->held;
   return a;
 }
 
@@ -417,8 +500,20 @@ int admm_sparse_l1class_run(admm_sparse_l1class* o, const admm_sparse_l1class_op
     launch_l1c_fin(fa, o->stream);
     if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
+  o->held_host.clear();
+  if (o->fold && all) {  // T = D z2 for every fit, stopped or not (z2: the sparse block df counts), and the held-out sums
+    SpmmMask every;
+    every.K = K;
+    launch_spmm(cg.sp.n, o->Z2, cg.T, cg.chunks, every, o->stream);
+    const Sl1cHeldArgs ha{o->m, cg.T, o->ELL, o->W, o->CC, o->loss, o->fold, o->held, o->rec, o->hpart, K, o->ell_shared};
+    launch_sl1c_heldout(ha, o->nwg_m, o->held_dev, o->stream);
+  }
   ADMM_TRY(finish_run(*o, all, "the sparse l1 classifier loop ended with fits still running", N, op.objevals != 0,
                       o->objv, runtime_s, summaries));
+  if (o->fold) {
+    o->held_host.resize(static_cast<size_t>(LH_COUNT) * K);
+    ADMM_HIP_TRY(hipMemcpy(o->held_host.data(), o->held_dev, sizeof(double) * o->held_host.size(), hipMemcpyDeviceToHost));
+  }
   for (int32_t c = 0; summaries && c < K; ++c) summaries[c].xsolve = ADMM_XSOLVE_CG;
   return end_sparse_run(o, op, summaries);
 }
@@ -426,6 +521,47 @@ int admm_sparse_l1class_run(admm_sparse_l1class* o, const admm_sparse_l1class_op
 int admm_sparse_l1class_set_cost(admm_sparse_l1class* o, const double* weights, const double* class_cost) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
   return set_svm_cost(*o, o->m, weights, class_cost, &o->W, o->CC, &o->cost_host);
+}
+
+int admm_sparse_l1class_set_folds(admm_sparse_l1class* o, int32_t nfolds, const int32_t* fold, const int32_t* heldout) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  const int64_t m = o->m;
+  const int32_t K = o->K;
+  ADMM_TRY(check_observations(m, K, nullptr, nfolds, fold, heldout));  // (the lasso's own checks; a refused call changes nothing)
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  int32_t *f = nullptr, *hd = nullptr;
+  if (fold) {
+    if (!o->hpart) {  // what every object with folds needs, once
+      const size_t kp = static_cast<size_t>(o->cg.chunks) * KC;
+      ADMM_TRY(o->mem.alloc(&o->hpart, kp * LH_COUNT * kScgMaxWg));
+      ADMM_HIP_TRY(hipMemsetAsync(o->hpart, 0, sizeof(double) * kp * LH_COUNT * kScgMaxWg, o->stream));
+      ADMM_TRY(o->mem.alloc(&o->held_dev, static_cast<size_t>(LH_COUNT) * K));
+    }
+    std::vector<int32_t> hh(static_cast<size_t>(K), -1);
+    for (int32_t k = 0; heldout && k < K; ++k) hh[k] = heldout[k];
+    ADMM_TRY(alloc_words(*o, &hd, static_cast<size_t>(K)));
+    ADMM_HIP_TRY(hipMemcpyAsync(hd, hh.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, o->stream));
+    ADMM_TRY(alloc_words(*o, &f, static_cast<size_t>(m)));
+    ADMM_HIP_TRY(hipMemcpyAsync(f, fold, sizeof(int32_t) * m, hipMemcpyHostToDevice, o->stream));
+    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));  // (hh and the caller's buffer were read)
+  }
+  for (void* p : {static_cast<void*>(o->fold), static_cast<void*>(o->held)}) o->mem.free_one(p);
+  o->fold = f;
+  o->held = hd;
+  o->held_host.clear();
+  return ADMM_OK;
+}
+
+int admm_sparse_l1class_heldout(admm_sparse_l1class* o, double* loss, double* errors, double* weight) {
+  if (!o || !loss || !errors || !weight) return fail(ADMM_E_INVALID, "object, loss, errors or weight is NULL");
+  if (!o->has_run || o->held_host.empty())
+    return fail(ADMM_E_INVALID, "the held-out sums need a run with folds set (admm_sparse_l1class_set_folds)");
+  for (int32_t k = 0; k < o->K; ++k) {
+    loss[k] = o->held_host[LH_COUNT * k + LH_LOSS];
+    errors[k] = o->held_host[LH_COUNT * k + LH_ERR];
+    weight[k] = o->held_host[LH_COUNT * k + LH_W];
+  }
+  return ADMM_OK;
 }
 
 int admm_sparse_l1class_set_l1weights(admm_sparse_l1class* o, const double* l1weights) {

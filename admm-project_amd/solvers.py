@@ -15,7 +15,7 @@ import numpy as np
 from .api import admm, getproxops
 from .errorcheck import LOSS_KEYS, PENALTY_KEYS, SVM_COST_KEYS, class_cost_pair, loss_fields, svm_cost_fields, group_sizes, is_nonnegative_real, is_positive_real, penalty_fields, slicemaker
 
-__all__ = ["lasso", "lasso_multi", "lasso_path", "lasso_cv", "cv_folds", "cv_summary", "grouplasso", "grouplasso_multi", "grouplasso_path", "l1classifier", "l1classifier_multi", "l1classifier_path", "l1classifier_lambda_max", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
+__all__ = ["lasso", "lasso_multi", "lasso_path", "lasso_cv", "cv_folds", "cv_summary", "grouplasso", "grouplasso_multi", "grouplasso_path", "l1classifier", "l1classifier_multi", "l1classifier_path", "l1classifier_cv", "l1classifier_lambda_max", "elasticnet", "lad", "huberfit", "quantilereg", "robustfit_multi", "quantilereg_multi", "linearsvm", "linearsvm_ovr", "unwrappedadmm", "quadraticprogram", "basispursuit",
            "totalvariation", "totalvariation2d", "model", "linearprogram", "covarianceselection", "covarianceselection_multi",
            "covarianceselection_path", "covarianceselection_lambda_max"]
 
@@ -121,11 +121,16 @@ def _start_columns(options, rows_by_key, default=None):
     return starts
 
 
-def _sparse_refusals(options, who, also=(), stopcond=False, observations=False):
+def _sparse_refusals(options, who, also=(), stopcond=False, observations=False, folds=False):
     """the options no sparse multi-fit object runs, each named in its ValueError; ``also``: keys
     refused beside comm, ``stopcond``: the object runs the 'standard' stop rule alone, ``observations``: the object takes
-    obsweights / foldid / heldout (the multi-lasso alone: q46)"""
-    if not observations:
+    obsweights / foldid / heldout (the multi-lasso: q46), ``folds``: it takes foldid / heldout and has observation
+    weights under a name of its own (the classifier's ``weights``: q47)"""
+    if folds:
+        if options.get("obsweights") is not None:
+            raise ValueError(f"options.obsweights is not available in {who}: the classifier's observation weights are "
+                             "options.weights")
+    elif not observations:
         _no_observations(options, who)
     for key in ("fast", "convtest", "adaptive"):
         if options.get(key, 0):
@@ -747,14 +752,23 @@ def l1classifier_multi(D, ELL, lams, options=None):
     On a scipy.sparse D every x-update is conjugate gradients on (D'D + I) x = D'(z1 - u1) + (z2 - u2), all fits in
     lock-step over one sparse product: nothing n x n is stored.  ``xsolve`` is 'auto' or 'cg' ('inverse' and 'trsv' are
     refused by name), ``cg_tol`` / ``cg_maxit`` (1e-12 / 200) bound a solve, and the result reads ``xsolve = 'cg'`` and
-    adds ``nnz``, ``cg_iters_total`` and ``cg_capped_updates`` (K values each)."""
+    adds ``nnz``, ``cg_iters_total`` and ``cg_capped_updates`` (K values each).
+
+    Held-out folds, on a scipy.sparse D: ``options['foldid']`` (m integer fold ids >= 0) together with
+    ``options['heldout']`` (K integers: the fold fit k leaves out, -1 for none) give fit k the cost c_ik*[foldid_i !=
+    heldout_k]: its minimiser is that of the classifier on the rows it keeps.  The result then carries ``heldout_loss``,
+    ``heldout_errors`` and ``heldout_weight`` (K values each) over the rows the fit held out, at D*z2 with z2 the
+    coefficient block of zopt: sum c_i*phi(ell_i*t_i) (without C), sum c_i*[ell_i*t_i <= 0] and sum c_i, c_i = weights_i *
+    class cost.  One of the two options without the other is refused; ``options['obsweights']`` is refused by name (the
+    classifier's option is ``weights``), and on a dense D both options are.  ``l1classifier_cv`` builds a
+    cross-validation out of them."""
     options = _options(options, "Argument options is not a struct!", optional=True)
     t0 = time.perf_counter()
     from ._lib import is_sparse
     from .l1class import L1Classifier, loss_code
     sparse = is_sparse(D)  # DESIGN.md q43: the matrix-free object, no limit on n
     if sparse:
-        _sparse_refusals(options, "l1classifier_multi", stopcond=True)
+        _sparse_refusals(options, "l1classifier_multi", stopcond=True, folds=True)
     else:
         _dense_multi_refusals(options, "l1classifier_multi")
     D = _matrix(D, "D", sparse_ok=sparse)
@@ -783,6 +797,23 @@ def l1classifier_multi(D, ELL, lams, options=None):
         is_positive_real(options["rho"], "options.rho")
     weights, class_cost = _l1c_costs(options, ELL, K)
     starts = _start_matrices(options, dict(x0=n, z0=m + n, u0=m + n), K, "fit")
+    prepare, finish = _cost_setter(weights, class_cost), None
+    if sparse and (options.get("foldid") is not None or options.get("heldout") is not None):
+        if options.get("foldid") is None:
+            raise ValueError("options.heldout needs options.foldid: the fold of every observation")
+        if options.get("heldout") is None:
+            raise ValueError("options.foldid needs options.heldout: the fold every fit leaves out (K values, -1 for none)")
+        from .sparse_lasso import observation_arrays
+        fold, held = observation_arrays(None, options["foldid"], options["heldout"], m, K)[1:3]
+        set_cost = prepare
+
+        def prepare(obj):
+            if set_cost is not None:
+                set_cost(obj)
+            obj.set_folds(fold, held)
+
+        def finish(obj, res):
+            res["heldout_loss"], res["heldout_errors"], res["heldout_weight"] = obj.heldout()
     if sparse:
         from .sparse_l1class import SparseL1Classifier
         obj = SparseL1Classifier(D, ELL, lam, losses, ridge, nonneg, w, C=Cv, xsolve=options.get("xsolve", "auto"),
@@ -790,7 +821,7 @@ def l1classifier_multi(D, ELL, lams, options=None):
     else:
         obj = L1Classifier(D, ELL, lam, losses, ridge, nonneg, w, C=Cv, xsolve=options.get("xsolve", "auto"),
                            device=int(options.get("device", 0)))
-    res = _run_and_close(obj, _cost_setter(weights, class_cost), check_every=int(options.get("check_every", 0)),
+    res = _run_and_close(obj, prepare, finish, check_every=int(options.get("check_every", 0)),
                          z0=starts.get("z0"), u0=starts.get("u0"), nodualerror=int(bool(options.get("nodualerror", 0))),
                          **_pick(options, _LOOP_KEYS + (_CG_KEYS if sparse else ())))
     res["lams"] = lam.copy()
@@ -854,6 +885,128 @@ def l1classifier_path(D, ell, lams=None, options=None):
     res = l1classifier_multi(D, e, lams, options)
     res["df"] = np.count_nonzero(res["zopt"][D.shape[0]:], axis=0).astype(np.int64)
     return res
+
+
+def l1classifier_cv(D, ell, lams=None, options=None):
+    """results = l1classifier_cv(D, ell, lams, options): F-fold cross-validation of ``l1classifier_path`` on a
+    scipy.sparse D, every fold fit and every full-data fit side by side in ONE run of ``l1classifier_multi`` over one
+    upload of D (DESIGN.md q47).  ``lams = None`` or a count: l1classifier_path's grid (``nlambda``, default 10;
+    ``lambda_min_ratio``, default 1e-2) from the full-data ``l1classifier_lambda_max``.  With L lambdas and F =
+    ``options['nfolds']`` (default 5, at least 2) the object holds (F + 1)*L fits: fit f*L + l leaves fold f out at
+    lambda_l, fits F*L + l see every row.
+
+    ``options['foldid']``: m fold ids in [0, nfolds); absent: ``cv_folds(m, nfolds, options.get('seed', 0))``.  A fold fit
+    runs at lambda_l * (training weight of fold f / total weight), the weights being ``options['weights']`` or ones:
+    one lambda sequence on the per-observation scale, written for this unnormalised objective;
+    ``options['scale_lambda'] = 0`` runs every fold at lambda_l itself.  ``options['measure']`` is 'deviance' (the
+    default: held-out loss / held-out weight) or 'class' (held-out weighted errors / held-out weight).  ``lossfunction``
+    (one string), ``weights``, ``classcost``, ``C``, ``l1weights``, ``ridge`` and ``nonnegative`` (scalars or L values)
+    and the loop / CG options are l1classifier_multi's; ``z0`` / ``u0`` ((m + n) x L) start every fold alike.
+    ``classcost = 'balanced'`` is computed ONCE from all rows and used by every fold fit: it is not recomputed from a
+    fold's training rows.  ``options['heldout']`` is this function's own to set.
+
+    Returns lams, foldid, measure, ``cv_summary``'s cvm, cvsd, index_min, lam_min, index_1se, lam_1se from the chosen
+    sums; xopt (n x L), zopt, uopt ((m + n) x L), df, steps, objopt of the full-data fits; fold_steps, fold_lams,
+    heldout_loss, heldout_errors, heldout_weight (F x L); nnz, cg_iters_total and cg_capped_updates over all (F + 1)*L
+    fits, chunk, runtime and solverruntime.  A dense D raises ValueError."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    t0 = time.perf_counter()
+    from ._lib import is_sparse
+    if not is_sparse(D):
+        raise ValueError("l1classifier_cv runs on a scipy.sparse D: the held-out folds live on the sparse object "
+                         "(SparseL1Classifier)")
+    e = _colvec(ell, "ell")
+    m, n = D.shape
+    F = options.pop("nfolds", 5)
+    if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or F < 2:
+        raise ValueError("options.nfolds must be an integer >= 2")
+    F = int(F)
+    seed = options.pop("seed", 0)
+    scale = bool(options.pop("scale_lambda", 1))
+    measure = options.pop("measure", "deviance")
+    if not (isinstance(measure, str) and measure in ("deviance", "class")):
+        raise ValueError("options.measure must be 'deviance' or 'class'")
+    if options.get("heldout") is not None:
+        raise ValueError("options.heldout is l1classifier_cv's own to set: give options.foldid")
+    options.pop("heldout", None)
+    if e.size != m:
+        raise ValueError("The number of rows in argument D do not match size of ell!")
+    loss = options.get("lossfunction", "logistic")
+    if not isinstance(loss, str):
+        raise ValueError("options.lossfunction is not a string!")
+    from .sparse_lasso import observation_arrays
+    if options.get("foldid") is None:
+        foldid = cv_folds(m, F, seed)
+    else:
+        foldid = observation_arrays(None, options["foldid"], None, m, 1)[1].astype(np.int64)
+        if foldid.min() < 0 or foldid.max() >= F:
+            raise ValueError(f"options.foldid: every fold id must lie in [0, nfolds = {F})")
+    if lams is None or np.isscalar(lams):
+        if lams is not None:
+            options["nlambda"] = lams
+        nlambda = options.pop("nlambda", None)
+        ratio = options.pop("lambda_min_ratio", 1e-2)
+        nlambda = 10 if nlambda is None else nlambda
+        if isinstance(nlambda, bool) or not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
+            raise ValueError("options.nlambda must be an integer >= 1")
+        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
+            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
+        lmax = l1classifier_lambda_max(D, e, _pick(options, ("lossfunction", "weights", "classcost", "l1weights", "C")))
+        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+    else:
+        options.pop("nlambda", None)
+        options.pop("lambda_min_ratio", None)
+    lams = np.asarray(lams, dtype=np.float64).reshape(-1)
+    L = int(lams.size)
+    if L < 1:
+        raise ValueError("lams must hold at least one lambda")
+    ELL = _l1c_labels(e, m, 1)
+    wf = svm_cost_fields(dict(weights=options.get("weights")), ELL[:, 0])
+    w = np.ones(m) if wf is None else wf["weights"]
+    total = float(w.sum())
+    if not total > 0.0:
+        raise ValueError("options.weights: the total weight must be positive")
+    train = np.array([total - float(w[foldid == f].sum()) for f in range(F)])
+    frac = train / total if scale else np.ones(F)
+    fold_lams = frac[:, None] * lams[None, :]
+    o = dict(options)
+    o["foldid"] = foldid
+    o["heldout"] = np.concatenate([np.repeat(np.arange(F), L), np.full(L, -1)])
+    cc = o.get("classcost")
+    if cc is not None:  # one pair for every fit, 'balanced' from all rows
+        if not isinstance(cc, str) and np.ndim(cc) == 2:
+            raise ValueError("classcost is one (pos, neg) pair or 'balanced' in l1classifier_cv")
+        o["classcost"] = class_cost_pair(cc, ELL[:, 0])
+    for key in ("ridge", "nonnegative"):  # scalars, or L values for every fold alike
+        if key in o and not (np.isscalar(o[key]) or isinstance(o[key], (bool, np.bool_))):
+            v = np.asarray(o[key]).reshape(-1)
+            if v.size != L:
+                raise ValueError(f"{key} has {v.size} entries for {L} lambdas")
+            o[key] = np.tile(v, F + 1)
+    for key in ("z0", "u0"):
+        if o.get(key) is not None:
+            v = np.asarray(o[key], dtype=np.float64)
+            if v.shape != (m + n, L):
+                raise ValueError(f"options.{key} is not a {m + n} x {L} matrix (one column per lambda)!")
+            o[key] = np.asfortranarray(np.tile(v, (1, F + 1)))
+    if o.get("x0") is not None:
+        v = np.asarray(o["x0"], dtype=np.float64)
+        if v.shape != (n, L):
+            raise ValueError(f"options.x0 is not a {n} x {L} matrix (one column per lambda)!")
+        o["x0"] = np.asfortranarray(np.tile(v, (1, F + 1)))
+    res = l1classifier_multi(D, e, np.concatenate([fold_lams.reshape(-1), lams]), o)
+    full = slice(F * L, (F + 1) * L)
+    held = {key: res[key][:F * L].reshape(F, L) for key in ("heldout_loss", "heldout_errors", "heldout_weight")}
+    chosen = held["heldout_loss"] if measure == "deviance" else held["heldout_errors"]
+    out = dict(lams=lams.copy(), foldid=foldid, measure=measure, **cv_summary(chosen, held["heldout_weight"], lams))
+    for key in ("xopt", "zopt", "uopt"):
+        out[key] = np.asfortranarray(res[key][:, full])
+    out["df"] = np.count_nonzero(out["zopt"][m:], axis=0).astype(np.int64)
+    out.update(steps=res["steps"][full], objopt=res["objopt"][full], fold_steps=res["steps"][:F * L].reshape(F, L),
+               fold_lams=fold_lams, **held, nnz=res["nnz"], cg_iters_total=res["cg_iters_total"],
+               cg_capped_updates=res["cg_capped_updates"], chunk=res["chunk"], runtime=res["runtime"])
+    out["solverruntime"] = time.perf_counter() - t0
+    return out
 
 
 def _group_lambda_max(D, s, sizes, gw):

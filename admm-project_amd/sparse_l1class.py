@@ -73,9 +73,30 @@ class SparseL1Classifier(_MultiOwner):
         w = _weights(l1weights, self.n, "coefficients", "l1weights")
         L.check(self._lib.admm_sparse_l1class_set_l1weights(self._h, None if w is None else L.as_dp(w)))
 
+    def set_folds(self, fold=None, heldout=None):
+        """Held-out folds for every later run (admm_sparse_l1class_set_folds): ``fold`` = m integer fold
+        ids >= 0 (None: no row is held out), ``heldout`` = K integers, the fold fit k leaves out or -1 (None: -1
+        everywhere); a fold that no row belongs to is allowed.  A held-out row has cost 0 in its fit.  Both None restore the
+        object without folds."""
+        from .sparse_lasso import observation_arrays
+        _, f, h, nfolds = observation_arrays(None, fold, heldout, self.m, self.K)
+        if h is not None:  # (a fold without rows is a fold: its fit holds nothing out and its sums are 0)
+            nfolds = max(nfolds, int(h.max(initial=-1)) + 1)
+        ip = lambda a: None if a is None else a.ctypes.data_as(C_INT32_P)
+        L.check(self._lib.admm_sparse_l1class_set_folds(self._h, nfolds, ip(f), ip(h)))
+
+    def heldout(self):
+        """(loss, errors, weight) of the last run under folds, K values each, over the rows fit k held out, at D*z2 (z2:
+        the coefficient block of zopt) with c_i = weights_i * class cost: sum c_i*phi(ell_i*t_i) without the factor C,
+        sum c_i*[ell_i*t_i <= 0] and sum c_i (admm_sparse_l1class_heldout)"""
+        loss, err, wt = np.empty(self.K), np.empty(self.K), np.empty(self.K)
+        L.check(self._lib.admm_sparse_l1class_heldout(self._h, L.as_dp(loss), L.as_dp(err), L.as_dp(wt)))
+        return loss, err, wt
+
     def kernel_time(self, reps=20, dual=1):
-        """the row kernel and the element kernel alone, event-timed (admm_sparse_l1class_kernel_time): dict(row_us,
-        elem_us).  Overwrites the iterates: call it between runs."""
+        """the row kernel (the form the object would run: with folds set, the one that reads them) and the element
+        kernel alone, event-timed (admm_sparse_l1class_kernel_time): dict(row_us, elem_us).  Overwrites the iterates:
+        call it between runs."""
         r, e = C.c_double(0), C.c_double(0)
         L.check(self._lib.admm_sparse_l1class_kernel_time(self._h, int(reps), int(dual), C.byref(r), C.byref(e)))
         return dict(row_us=r.value, elem_us=e.value)

@@ -13,7 +13,7 @@ import numpy as np
 from . import solvers, synth
 
 __all__ = ["lassotest", "sparselassotest", "grouplassotest", "elasticnettest", "ladtest", "quantileregtest", "quantileregmultitest", "sparsequantileregtest", "huberfittest", "totalvariationtest", "linearsvmtest", "sparsesvmtest", "l1classifiertest", "basispursuittest",
-           "linearprogramtest", "modeltest", "covarianceselectiontest", "covarianceselectionpathtest", "sparselassocvtest", "solvertester"]
+           "linearprogramtest", "modeltest", "covarianceselectiontest", "covarianceselectionpathtest", "sparselassocvtest", "sparsel1classifiercvtest", "solvertester"]
 
 
 def _opts(options, **forced):
@@ -370,6 +370,42 @@ def sparsel1classifiertest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, errt
                 steps=results["steps"], nnz=results["nnz"], cg_capped_updates=results["cg_capped_updates"], errtol=errtol)
     test["lambda"] = lam
     return results, test
+
+
+def sparsel1classifiercvtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, nfolds=5, nlambda=8, errtol=0.2, quiet=1,
+                             options=None):
+    """Cross-validation of the l1-regularised logistic regression's path on a sparse design matrix:
+    l1classifier_cv on synth.sparse_design_classifier_problem with ``nfolds`` folds over ``nlambda`` values, the first one
+    1.25*lambda_max and the others log-spaced from 0.8*lambda_max down to 0.01*lambda_max -- (nfolds + 1)*nlambda fits
+    in one run.  Pass when the held-out weights are the fold sizes, every fold fit whose lambda lies 1 % above the
+    lambda_max of its own training rows predicts 0 on its held-out rows (a deviance of log 2 per row, every row an
+    error), the selected
+    lambda lies inside the path (cvm[index_min] < cvm[0]), lam_1se >= lam_min, the held-out error rate at lam_min is at
+    most ``errtol``, and no x-update hit the inner iteration cap.  Returns the ``test`` dict alone; the solver's results
+    are ``test['results']``."""
+    p = synth.sparse_design_classifier_problem(seed, rows, cols, density)
+    D, ell = p["D"], p["ell"]
+    o = _opts(options, nfolds=int(nfolds), seed=seed, objevals=1, quiet=quiet)
+    o.pop("quiet", None)
+    lmax = solvers.l1classifier_lambda_max(D, ell)
+    lams = lmax * np.concatenate([[1.25], np.logspace(np.log10(0.8), -2.0, int(nlambda) - 1)])
+    results = solvers.l1classifier_cv(D, ell, lams, o)
+    fold = results["foldid"]
+    sizes = np.bincount(fold, minlength=int(nfolds)).astype(np.float64)
+    L = lams.size
+    full = np.repeat(sizes[:, None], L, axis=1)
+    weights_ok = bool(np.array_equal(results["heldout_weight"], full))
+    own = np.array([0.5 * float(np.max(np.abs(D.T @ (ell * (fold != f))))) for f in range(int(nfolds))])
+    above = results["fold_lams"] >= 1.01 * own[:, None]  # (F x L: the fold fit's solution is z2 = 0)
+    null_ok = bool(above.any() and np.all(np.abs(results["heldout_loss"] - np.log(2.0) * full)[above] <= 1e-12 * full[above])
+                   and np.array_equal(results["heldout_errors"][above], full[above]))
+    selects = bool(results["cvm"][results["index_min"]] < results["cvm"][0]) and results["lam_1se"] >= results["lam_min"]
+    rate = float(results["heldout_errors"][:, results["index_min"]].sum() / sizes.sum())
+    capped = int(np.sum(results["cg_capped_updates"]))
+    ok = weights_ok and null_ok and selects and rate <= errtol and capped == 0
+    return dict(results=results, cvm=results["cvm"], cvsd=results["cvsd"], lam_min=results["lam_min"],
+                lam_1se=results["lam_1se"], df=results["df"], error_rate=rate, weights_ok=weights_ok, null_ok=null_ok,
+                selects=selects, cg_capped_updates=capped, errtol=errtol, failed=int(not ok))
 
 
 def basispursuittest(seed=0, rows=2 ** 6, cols=2 ** 7, errtol=1e-3, quiet=1, options=None):

@@ -1549,6 +1549,23 @@ int admm_sparse_l1class_fetch(admm_sparse_l1class* obj, int field, double* dst, 
 /* admm_l1class_set_cost and admm_l1class_set_l1weights on this object: rows weights, K x 2 class costs; cols l1 weights */
 int admm_sparse_l1class_set_cost(admm_sparse_l1class* obj, const double* weights, const double* class_cost);
 int admm_sparse_l1class_set_l1weights(admm_sparse_l1class* obj, const double* l1weights);
+/* Held-out folds for every later run (additive to ABI 5): fit k gets the cost c_ik = weights[i] * (class
+ * cost of fit k by the sign of ell_ik) * [fold[i] != heldout[k]] -- K classifiers that each leave one fold of rows out,
+ * over one D.  fold: rows HOST fold ids in [0, nfolds); heldout: K values in [-1, nfolds), -1 (and NULL) = the fit holds
+ * nothing out.  Both copied at the call.  The x-update's matrix D'D + I holds no cost, so every fit keeps the operator it
+ * had: a held-out row is a row of cost 0, a select in the row kernel.  Fit k's minimiser is that of the classifier on the
+ * rows it keeps; its iterates and its stop rule are those of the full-row problem with zero-cost rows: on a held-out row
+ * z1 = D x + u1 and u1 = 0 after one iteration, and such rows still enter ||A x||, ||z|| and the dual products.  fold and
+ * heldout both NULL restore the object without folds, bit for bit.  Combines with admm_sparse_l1class_set_cost in either
+ * order.  ADMM_E_INVALID, the culprit named, in the words of admm_sparse_lasso_set_observations: nfolds < 1 with fold
+ * given, a fold id outside [0, nfolds) (its row), a heldout outside [-1, nfolds) (its fit), heldout without fold.  A
+ * refused call changes nothing. */
+int admm_sparse_l1class_set_folds(admm_sparse_l1class* obj, int32_t nfolds, const int32_t* fold, const int32_t* heldout);
+/* The held-out sums of the last run under folds, K doubles each, evaluated behind the loop at t = D z2 (z2: the sparse
+ * coefficient block of z) for every fit over the rows with fold[i] = heldout[k], with c_i = weights[i] * class cost:
+ * loss[k] = sum c_i*phi_k(ell_ik*t_i) (without the factor C), errors[k] = sum c_i*[ell_ik*t_i <= 0], weight[k] = sum c_i
+ * (all 0.0 for a fit that holds nothing out).  ADMM_E_INVALID before a run or when the last run had no folds set. */
+int admm_sparse_l1class_heldout(admm_sparse_l1class* obj, double* loss, double* errors, double* weight);
 /* fits one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
 int admm_sparse_l1class_chunk(void);
 /* measurement: the row kernel and the element kernel alone over the object's own buffers (every fit running, the dual
