@@ -541,6 +541,8 @@ _SIGNATURES = {
     "admm_lasso_multi_fetch": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "admm_lasso_multi_set_weights": (C.c_int, [C.c_void_p, _dp]),
     "admm_lasso_multi_set_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
+    "admm_group_l1class_set_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
+    "admm_sparse_l1class_set_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
     "admm_lasso_multi_chunk": (C.c_int, []),
     "admm_lasso_multi_product_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                                 C.POINTER(C.c_int64)]),

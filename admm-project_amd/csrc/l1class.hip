@@ -21,6 +21,8 @@
 //   l1c_elem_kernel               over n: z2, u2, the next Y = D'T1 + (z2 - u2), the n-block's partial sums, the dual
 //                                 residual's two norms, the penalty
 //   l1c_fin_kernel                per fit pnorm, perr, dnorm, derr, the objective and the stop decision (admm.m:612-713)
+// With groups set (admm_group_l1class_set_groups, q48) the element kernel is l1c_group_elem_kernel, the shared body of
+// l1class_group_device.h over the plan's workgroups, reading GS; nothing else of the iteration changes.
 // A fit whose stop flag is set is FROZEN: every kernel skips it.  No atomics; every sum runs in an order the sizes fix,
 // independent of the chunk and slot a fit occupies: a fit duplicated into another chunk comes out bitwise equal.
 // All loads of D are unconditional on clamped addresses (X and T are zero beyond n and m).
@@ -32,6 +34,7 @@
 #include <vector>
 
 #include "l1class_device.h"
+#include "l1class_group_device.h"
 #include "multi_host.h"
 #include "spmm.h"
 #include "svm_cost_device.h"
@@ -330,6 +333,18 @@ __global__ __launch_bounds__(kBlock) void l1c_elem_kernel(L1cElemArgs a) {
         ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
 }
 
+// the grouped form (q48): l1class_group_device.h's body; g1, g2, g3 are the rows fit, Kp + fit and 2 Kp + fit of GS
+__global__ __launch_bounds__(kScgBlock) void l1c_group_elem_kernel(L1cGroupElemArgs a, GroupPlan gp,
+                                                                   const double* __restrict__ GS, int64_t ldx, int32_t Kp) {
+  __shared__ double lds[kL1cGroupLds];
+  __shared__ double sq[kScgBlock];
+  __shared__ double gacc[kGmMaxGroups * KC];
+  l1c_group_elem_body(
+      a, gp,
+      [&](int q, const ScgLane& l, int64_t, int64_t j) { return GS[(static_cast<int64_t>(q) * Kp + l.fit) * ldx + j]; },
+      lds, sq, gacc);
+}
+
 // blockIdx.x = fit: admm.m:612-658, 706-713 as oracle/admm_ref.py restates it for A = [D; I], B = -1, c = 0, plain ADMM
 // with stopcond = 'standard': every norm over the m + n stacked elements
 __global__ __launch_bounds__(kFinThreads) void l1c_fin_kernel(L1cFinArgs a) {
@@ -408,6 +423,7 @@ struct admm_l1class : admm::MultiHost {
   std::vector<char> chunk_logistic;
   double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   int64_t launches = 0, d_passes = 0;
+  admm::GroupMulti grp;  // admm_group_l1class_set_groups (q48)
   admm_l1class_options last{};
 };
 
@@ -743,7 +759,7 @@ int admm_l1class_run(admm_l1class* o, const admm_l1class_options* opts, admm_l1c
   fa.n = o->n;
   fa.K = K;
   fa.nwg_m = o->nwg_m;
-  fa.nwg_n = o->nwg_n;
+  fa.nwg_n = o->grp.on() ? o->grp.plan.nwg : o->nwg_n;  // the plan's workgroups wrote the n-block's partials
   fa.dual = dual ? 1 : 0;
   fa.rec = o->rec;
   fa.pnorm = o->pnorm;
@@ -760,6 +776,9 @@ int admm_l1class_run(admm_l1class* o, const admm_l1class_options* opts, admm_l1c
   fa.objevals = op.objevals;
   fa.maxiters = N;
   const dim3 egrid(static_cast<unsigned>(o->nwg_n), static_cast<unsigned>(K));
+  const L1cGroupElemArgs ga{ea.n, ea.X, ea.Z2, ea.U2, ea.Y, ea.W, ea.par, o->grp.l1, ea.nonneg, ea.rec, ea.part, K, ea.dual,
+                            ea.objevals, ea.rho};
+  const dim3 ggrid(static_cast<unsigned>(o->grp.plan.nwg), static_cast<unsigned>(o->chunks));
   int64_t launches = 0, d_passes = 0;
 
   ADMM_TRY(begin_timing(*o));
@@ -778,7 +797,10 @@ int admm_l1class_run(admm_l1class* o, const admm_l1class_options* opts, admm_l1c
     for (int32_t ch = 0; ch < o->chunks; ++ch) l1c_launch_forward(o, fw, ch);
     for (int32_t ch = 0; ch < o->chunks; ++ch) l1c_launch_transposed(o, tr, ch, nv);
     l1c_launch_gsum(o, nv);
-    hipLaunchKernelGGL(l1c_elem_kernel<false>, egrid, dim3(kBlock), 0, o->stream, ea);
+    if (o->grp.on())
+      hipLaunchKernelGGL(l1c_group_elem_kernel, ggrid, dim3(kScgBlock), 0, o->stream, ga, o->grp.plan, o->GS, o->ldx, o->Kp);
+    else
+      hipLaunchKernelGGL(l1c_elem_kernel<false>, egrid, dim3(kBlock), 0, o->stream, ea);
     launch_l1c_fin(fa, o->stream);
     launches += 2 * o->chunks + 3;
     d_passes += 2 * o->chunks;
@@ -803,6 +825,12 @@ int admm_l1class_set_l1weights(admm_l1class* o, const double* l1weights) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
   ADMM_TRY(check_l1_weights(l1weights, o->n));  // (the message of the create-time check; a refused call changes nothing)
   return set_shared_weights(*o, o->n, l1weights, &o->LW);
+}
+
+int admm_group_l1class_set_groups(admm_l1class* o, int32_t G, const int64_t* sizes, const double* groupweights,
+                            const double* l1) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  return set_multi_groups(*o, o->n, G, sizes, groupweights, l1, &o->grp);
 }
 
 int admm_l1class_launches(admm_l1class* o, int64_t* launches, int64_t* d_passes) {

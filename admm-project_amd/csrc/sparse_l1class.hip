@@ -16,6 +16,8 @@
 //   sl1c_elem_kernel              over n: z2, u2, the next Y = G + (z2 - u2), the n-block's sums, the dual residual's two
 //                                 norms, the penalty
 //   l1c_fin_kernel                l1class.hip's, per fit: pnorm, perr, dnorm, derr, the objective, the stop decision
+// With groups set (admm_sparse_l1class_set_groups, q48) the element kernel is sl1c_group_elem_kernel, the shared body of
+// l1class_group_device.h over the plan's workgroups; nothing else of the iteration changes (D'D + I holds no penalty).
 // With folds set (admm_sparse_l1class_set_folds, q47) fit k's cost on row i is 0 where fold_i = held_k -- a select in the
 // row kernel's FOLD instantiation; D'D + I holds no cost, so nothing else of the iteration changes -- and behind the loop
 // one product T = D Z2 over every fit and sl1c_heldout_kernel give the held-out loss, weighted errors and weight.
@@ -30,6 +32,7 @@
 #include <vector>
 
 #include "l1class_device.h"
+#include "l1class_group_device.h"
 #include "multi_host.h"
 #include "spmm_cg.h"
 #include "svm_cost_device.h"
@@ -202,6 +205,23 @@ __global__ __launch_bounds__(kScgBlock) void sl1c_elem_kernel(Sl1cElemArgs a) {
   scg_sums<LN_COUNT>(acc, lds, a.part, LN_COUNT, 0);
 }
 
+// the grouped form (q48): l1class_group_device.h's body; g1, g2, g3 are multi-vectors of len n
+__global__ __launch_bounds__(kScgBlock) void sl1c_group_elem_kernel(L1cGroupElemArgs a, GroupPlan gp,
+                                                                    const double* __restrict__ G,
+                                                                    const double* __restrict__ GDZ,
+                                                                    const double* __restrict__ GU) {
+  __shared__ double lds[kL1cGroupLds];
+  __shared__ double sq[kScgBlock];
+  __shared__ double gacc[kGmMaxGroups * KC];
+  l1c_group_elem_body(
+      a, gp,
+      [&](int q, const ScgLane& l, int64_t base, int64_t j) {
+        const double* __restrict__ g = q == 0 ? G : (q == 1 ? GDZ : GU);
+        return g[base + j * KC + l.c];
+      },
+      lds, sq, gacc);
+}
+
 void launch_sl1c_row(const Sl1cRowArgs& a, bool init, hipStream_t stream) {
   const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
   if (init) hipLaunchKernelGGL(sl1c_row_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
@@ -220,6 +240,15 @@ void launch_sl1c_elem(const Sl1cElemArgs& a, bool init, hipStream_t stream) {
   const dim3 grid(scg_vec_workgroups(a.n), static_cast<unsigned>(spmm_chunks(a.K)));
   if (init) hipLaunchKernelGGL(sl1c_elem_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
   else hipLaunchKernelGGL(sl1c_elem_kernel<false>, grid, dim3(kScgBlock), 0, stream, a);
+}
+
+// the iteration form of the element update the object would run: grouped with groups set (the INIT form needs none)
+void launch_sl1c_elem_iter(const Sl1cElemArgs& a, const GroupMulti& gm, hipStream_t stream) {
+  if (!gm.on()) return launch_sl1c_elem(a, false, stream);
+  const L1cGroupElemArgs ga{a.n, a.X, a.Z2, a.U2, a.Y, a.W, a.par, gm.l1, a.nonneg, a.rec, a.part, a.K, a.dual, a.objevals,
+                            a.rho};
+  const dim3 grid(static_cast<unsigned>(gm.plan.nwg), static_cast<unsigned>(spmm_chunks(a.K)));
+  hipLaunchKernelGGL(sl1c_group_elem_kernel, grid, dim3(kScgBlock), 0, stream, ga, gm.plan, a.G, a.GDZ, a.GU);
 }
 
 }  // namespace
@@ -242,6 +271,7 @@ struct admm_sparse_l1class : admm::MultiHost {
   int32_t *fold = nullptr, *held = nullptr;  // m fold ids; K values (-1: nothing held out)
   double *hpart = nullptr, *held_dev = nullptr;  // the held-out pass's own partials; K x LH_COUNT totals
   std::vector<double> held_host;  // the same on the host; empty: no run under folds behind the object
+  admm::GroupMulti grp;  // admm_sparse_l1class_set_groups (q48)
   double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   admm_sparse_l1class_options last{};
 };
@@ -464,7 +494,7 @@ int admm_sparse_l1class_run(admm_sparse_l1class* o, const admm_sparse_l1class_op
   fa.n = o->n;
   fa.K = K;
   fa.nwg_m = o->nwg_m;
-  fa.nwg_n = o->nwg_n;
+  fa.nwg_n = o->grp.on() ? o->grp.plan.nwg : o->nwg_n;  // the plan's workgroups wrote the n-block's partials
   fa.dual = dual ? 1 : 0;
   fa.rec = o->rec;
   fa.pnorm = o->pnorm;
@@ -496,7 +526,7 @@ int admm_sparse_l1class_run(admm_sparse_l1class* o, const admm_sparse_l1class_op
       launch_spmm(cg.sp.t, o->DZ1, o->GDZ, cg.chunks, run, o->stream);  // D'(z1 - z1prev)
       launch_spmm(cg.sp.t, o->U1, o->GU, cg.chunks, run, o->stream);    // D'u1
     }
-    launch_sl1c_elem(ea, false, o->stream);
+    launch_sl1c_elem_iter(ea, o->grp, o->stream);
     launch_l1c_fin(fa, o->stream);
     if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
@@ -570,6 +600,12 @@ int admm_sparse_l1class_set_l1weights(admm_sparse_l1class* o, const double* l1we
   return set_shared_weights(*o, o->n, l1weights, &o->LW);
 }
 
+int admm_sparse_l1class_set_groups(admm_sparse_l1class* o, int32_t G, const int64_t* sizes, const double* groupweights,
+                                   const double* l1) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  return set_multi_groups(*o, o->n, G, sizes, groupweights, l1, &o->grp);
+}
+
 int admm_sparse_l1class_kernel_time(admm_sparse_l1class* o, int32_t reps, int32_t dual, double* row_us, double* elem_us) {
   if (!o || reps < 1) return fail(ADMM_E_INVALID, "object is NULL or reps < 1");
   ADMM_HIP_TRY(hipSetDevice(o->device));
@@ -582,7 +618,7 @@ int admm_sparse_l1class_kernel_time(admm_sparse_l1class* o, int32_t reps, int32_
     for (int32_t i = -1; i < reps; ++i) {  // (i = -1: warm-up)
       ADMM_HIP_TRY(hipEventRecord(o->ev0, o->stream));
       if (pass == 0) launch_sl1c_row(ra, false, o->stream);
-      else launch_sl1c_elem(ea, false, o->stream);
+      else launch_sl1c_elem_iter(ea, o->grp, o->stream);
       ADMM_HIP_TRY(hipEventRecord(o->ev1, o->stream));
       ADMM_HIP_TRY(hipEventSynchronize(o->ev1));
       if (i >= 0) ADMM_HIP_TRY(hipEventElapsedTime(&ms[i], o->ev0, o->ev1));

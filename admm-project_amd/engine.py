@@ -773,10 +773,10 @@ def _set_svm_cost(self, weights=None, classcost=None):
 
 
 def _set_multi_groups(self, groups=None, groupweights=None, l1=None):
-    """Groups for every later run of a multi-fit lasso object (<abi>_set_groups): ``groups`` = the sizes of
+    """Groups for every later run of a multi-fit lasso or classifier object (<abi>_set_groups): ``groups`` = the sizes of
     the contiguous groups (they sum to n), ``groupweights`` = one weight >= 0 per group shared by all fits (None: 1),
     ``l1`` = K strengths of the l1 term (None: 0).  ``groups`` None restores the ungrouped prox."""
-    fn = getattr(self._lib, self._abi + "_set_groups")
+    fn = getattr(self._lib, getattr(self, "_set_groups_abi", self._abi + "_set_groups"))
     if groups is None:
         L.check(fn(self._h, 0, None, None, None))
         return

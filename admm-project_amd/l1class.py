@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _MultiOwner, _set_svm_cost, _f64, _weights
+from .engine import _MultiOwner, _set_multi_groups, _set_svm_cost, _f64, _weights
 from .lasso_multi import xsolve_code
 
 _LOSSES = dict(hinge=L.LOSS_HINGE, sqhinge=L.LOSS_SQHINGE, logistic=L.LOSS_LOGISTIC)
@@ -31,6 +31,7 @@ class L1Classifier(_MultiOwner):
     0; ``l1weights`` n values w_j >= 0 shared by all fits, or None for 1."""
 
     _abi, _unit = "admm_l1class", "fit"
+    _set_groups_abi = "admm_group_l1class_set_groups"  # (its own prefix: include/admm_engine.h)
     _types = (L.L1ClassDesc, L.L1ClassOptions, L.L1ClassSummary)
     _rows = dict(x0="n", z0="mn", u0="mn")  # z and u stack the m rows of D above the n coefficients
     _fields = dict(xopt=(L.L1C_F_XOPT, "n"), zopt=(L.L1C_F_ZOPT, "mn"), uopt=(L.L1C_F_UOPT, "mn"),
@@ -79,6 +80,7 @@ class L1Classifier(_MultiOwner):
         self.xsolve = None  # 'inverse' | 'trsv' once a run has reported it
 
     set_cost = _set_svm_cost
+    set_groups = _set_multi_groups  # (lambda becomes the group strength, l1 the l1 strength)
 
     def set_l1weights(self, l1weights=None):
         """n l1 weights >= 0 shared by all fits (admm_l1class_set_l1weights); None restores 1"""

@@ -709,6 +709,12 @@ def l1classifier_lambda_max(D, ell, options=None):
     C*|phi'(0)|*max over w_j > 0 of |sum_i c_i*ell_i*D_ij| / w_j, with phi'(0) = -1/2 (logistic), -1 (hinge), -2
     (sqhinge).  With an unpenalised column (w_j = 0) the all-zero model is in general not optimal at this lambda."""
     options = _options(options, "Argument options is not a struct!", optional=True)
+    return _classifier_lambda_max(D, ell, options)
+
+
+def _classifier_lambda_max(D, ell, options, groups=None):
+    """l1classifier_lambda_max's body; ``groups`` = (sizes, groupweights): groupclassifier_lambda_max's, the l1 weights
+    are not read then"""
     from ._lib import is_sparse
     D = _matrix(D, "D", sparse_ok=is_sparse(D))  # (a sparse D: the one product below is SciPy's)
     ELL = _l1c_labels(ell, D.shape[0], 1)
@@ -720,12 +726,14 @@ def l1classifier_lambda_max(D, ell, options=None):
     c = np.ones(e.size) if weights is None else weights.copy()
     if cc is not None:
         c = c * np.where(e > 0, cc[0][0], cc[0][1])
+    Cv = is_positive_real(options.get("C", 1.0), "options.C")
+    if groups is not None:
+        return Cv * _L1C_SLOPE0[loss.lower()] * _group_lambda_max(D, c * e, groups[0], groups[1])
     pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
     g = np.abs(np.asarray(D.T @ (c * e), dtype=np.float64)).reshape(-1)
     if pw is not None:
         live = pw["l1weights"] > 0
         g = g[live] / pw["l1weights"][live]
-    Cv = is_positive_real(options.get("C", 1.0), "options.C")
     return Cv * _L1C_SLOPE0[loss.lower()] * (float(g.max()) if g.size else 0.0)
 
 
@@ -763,14 +771,20 @@ def l1classifier_multi(D, ELL, lams, options=None):
     classifier's option is ``weights``), and on a dense D both options are.  ``l1classifier_cv`` builds a
     cross-validation out of them."""
     options = _options(options, "Argument options is not a struct!", optional=True)
-    t0 = time.perf_counter()
+    return _run_multi_classifier(D, ELL, lams, options, "l1classifier_multi", time.perf_counter())
+
+
+def _run_multi_classifier(D, ELL, lams, options, who, t0, groups=None):
+    """the body of l1classifier_multi and of groupclassifier_multi (q48): the refusals, the fits, the owner, one run.
+    ``groups``: the sizes of groupclassifier_multi; options.groupweights and options.l1 are read beside them alone, and
+    the result carries ``groups``"""
     from ._lib import is_sparse
     from .l1class import L1Classifier, loss_code
     sparse = is_sparse(D)  # DESIGN.md q43: the matrix-free object, no limit on n
     if sparse:
-        _sparse_refusals(options, "l1classifier_multi", stopcond=True, folds=True)
+        _sparse_refusals(options, who, stopcond=True, folds=True)
     else:
-        _dense_multi_refusals(options, "l1classifier_multi")
+        _dense_multi_refusals(options, who)
     D = _matrix(D, "D", sparse_ok=sparse)
     m, n = D.shape
     lam = np.asarray(lams, dtype=np.float64).reshape(-1)
@@ -798,6 +812,15 @@ def l1classifier_multi(D, ELL, lams, options=None):
     weights, class_cost = _l1c_costs(options, ELL, K)
     starts = _start_matrices(options, dict(x0=n, z0=m + n, u0=m + n), K, "fit")
     prepare, finish = _cost_setter(weights, class_cost), None
+    if groups is not None:
+        sizes, gw = group_sizes(groups, options.get("groupweights"), n)
+        l1 = _per_fit(options.get("l1", 0.0), K, "l1", lambda v: penalty_fields(dict(l1=v), n)["l1"])
+        set_cost0 = prepare
+
+        def prepare(obj):
+            if set_cost0 is not None:
+                set_cost0(obj)
+            obj.set_groups(sizes, gw, l1)
     if sparse and (options.get("foldid") is not None or options.get("heldout") is not None):
         if options.get("foldid") is None:
             raise ValueError("options.heldout needs options.foldid: the fold of every observation")
@@ -825,6 +848,8 @@ def l1classifier_multi(D, ELL, lams, options=None):
                          z0=starts.get("z0"), u0=starts.get("u0"), nodualerror=int(bool(options.get("nodualerror", 0))),
                          **_pick(options, _LOOP_KEYS + (_CG_KEYS if sparse else ())))
     res["lams"] = lam.copy()
+    if groups is not None:
+        res["groups"] = sizes.copy()
     res["solverruntime"] = time.perf_counter() - t0
     return res
 
@@ -834,6 +859,11 @@ def l1classifier(D, ell, lam, options=None):
     l1-regularised logistic regression by default, the l1-SVM with lossfunction 'hinge' or 'sqhinge'.  ``x0`` has n
     entries, ``z0`` / ``u0`` m + n.  Returns vectors and scalars where l1classifier_multi returns columns."""
     options = _options(options, "Argument options is not a struct!", optional=True)
+    return _single_classifier(D, ell, lam, options, "l1classifier_multi")
+
+
+def _single_classifier(D, ell, lam, options, who, groups=None):
+    """l1classifier's body, and groupclassifier's with ``groups``"""
     if not np.isscalar(lam) or not np.isreal(lam):
         raise ValueError("Argument lam is not a nonnegative real number!")
     from ._lib import is_sparse
@@ -842,9 +872,11 @@ def l1classifier(D, ell, lam, options=None):
     loss = options.get("lossfunction", "logistic")
     if not isinstance(loss, str):
         raise ValueError("options.lossfunction is not a string!")
+    if groups is not None and np.size(options.get("l1", 0.0)) != 1:
+        raise ValueError("options.l1 is not a nonnegative real number!")
     for key, v in _start_columns(options, dict(x0=n, z0=m + n, u0=m + n)).items():
         options[key] = v
-    res = l1classifier_multi(D, _colvec(ell, "ell"), [lam], options)
+    res = _run_multi_classifier(D, _colvec(ell, "ell"), [lam], options, who, time.perf_counter(), groups)
     for key in ("xopt", "zopt", "uopt") + _L1C_HIST:
         if key in res:
             res[key] = np.ascontiguousarray(res[key][:, 0])
@@ -864,10 +896,24 @@ def l1classifier_path(D, ell, lams=None, options=None):
     may not be the all-zero model.  Returns l1classifier_multi's fields plus ``df``, the nonzeros of each column of the
     coefficient block of zopt."""
     options = _options(options, "Argument options is not a struct!", optional=True)
+    return _classifier_path(D, ell, lams, options, "l1classifier_multi")
+
+
+def _group_l1_refusal(options, who):
+    """grouplasso_path's rule: with any l1 != 0 the group lambda_max has no closed form"""
+    if np.any(np.asarray(options.get("l1", 0.0), dtype=np.float64) != 0):
+        raise ValueError(f"{who}: with options.l1 != 0 lambda_max has no closed form: give lams")
+
+
+def _classifier_path(D, ell, lams, options, who, groups=None):
+    """l1classifier_path's body, and groupclassifier_path's with ``groups`` (the result then adds df_groups)"""
     from ._lib import is_sparse
     D = _matrix(D, "D", sparse_ok=is_sparse(D))
     e = _colvec(ell, "ell")
+    gs = None if groups is None else group_sizes(groups, options.get("groupweights"), D.shape[1])
     if lams is None or np.isscalar(lams):
+        if gs is not None:
+            _group_l1_refusal(options, "groupclassifier_path")
         if lams is not None:
             options["nlambda"] = lams
         nlambda = options.pop("nlambda", None)
@@ -877,14 +923,23 @@ def l1classifier_path(D, ell, lams=None, options=None):
             raise ValueError("options.nlambda must be an integer >= 1")
         if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
             raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-        lmax = l1classifier_lambda_max(D, e, options)
+        lmax = _classifier_lambda_max(D, e, options, gs)
         lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
     else:
         options.pop("nlambda", None)
         options.pop("lambda_min_ratio", None)
-    res = l1classifier_multi(D, e, lams, options)
-    res["df"] = np.count_nonzero(res["zopt"][D.shape[0]:], axis=0).astype(np.int64)
+    res = _run_multi_classifier(D, e, lams, options, who, time.perf_counter(), None if gs is None else gs[0])
+    Z2 = res["zopt"][D.shape[0]:]
+    res["df"] = np.count_nonzero(Z2, axis=0).astype(np.int64)
+    if gs is not None:
+        res["df_groups"] = _df_groups(Z2, gs[0])
     return res
+
+
+def _df_groups(Z, sizes):
+    """per column of Z the groups with a nonzero block"""
+    first = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    return np.count_nonzero(np.add.reduceat(Z != 0, first, axis=0), axis=0).astype(np.int64)
 
 
 def l1classifier_cv(D, ell, lams=None, options=None):
@@ -910,10 +965,16 @@ def l1classifier_cv(D, ell, lams=None, options=None):
     heldout_loss, heldout_errors, heldout_weight (F x L); nnz, cg_iters_total and cg_capped_updates over all (F + 1)*L
     fits, chunk, runtime and solverruntime.  A dense D raises ValueError."""
     options = _options(options, "Argument options is not a struct!", optional=True)
+    return _classifier_cv(D, ell, lams, options, "l1classifier_cv")
+
+
+def _classifier_cv(D, ell, lams, options, who, groups=None):
+    """l1classifier_cv's body, and groupclassifier_cv's with ``groups``: the same layout and arithmetic with the groups set
+    on the one object (the result then adds groups and df_groups)"""
     t0 = time.perf_counter()
     from ._lib import is_sparse
     if not is_sparse(D):
-        raise ValueError("l1classifier_cv runs on a scipy.sparse D: the held-out folds live on the sparse object "
+        raise ValueError(f"{who} runs on a scipy.sparse D: the held-out folds live on the sparse object "
                          "(SparseL1Classifier)")
     e = _colvec(ell, "ell")
     m, n = D.shape
@@ -927,7 +988,7 @@ def l1classifier_cv(D, ell, lams=None, options=None):
     if not (isinstance(measure, str) and measure in ("deviance", "class")):
         raise ValueError("options.measure must be 'deviance' or 'class'")
     if options.get("heldout") is not None:
-        raise ValueError("options.heldout is l1classifier_cv's own to set: give options.foldid")
+        raise ValueError(f"options.heldout is {who}'s own to set: give options.foldid")
     options.pop("heldout", None)
     if e.size != m:
         raise ValueError("The number of rows in argument D do not match size of ell!")
@@ -941,7 +1002,10 @@ def l1classifier_cv(D, ell, lams=None, options=None):
         foldid = observation_arrays(None, options["foldid"], None, m, 1)[1].astype(np.int64)
         if foldid.min() < 0 or foldid.max() >= F:
             raise ValueError(f"options.foldid: every fold id must lie in [0, nfolds = {F})")
+    gs = None if groups is None else group_sizes(groups, options.get("groupweights"), n)
     if lams is None or np.isscalar(lams):
+        if gs is not None:
+            _group_l1_refusal(options, who)
         if lams is not None:
             options["nlambda"] = lams
         nlambda = options.pop("nlambda", None)
@@ -951,7 +1015,7 @@ def l1classifier_cv(D, ell, lams=None, options=None):
             raise ValueError("options.nlambda must be an integer >= 1")
         if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
             raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-        lmax = l1classifier_lambda_max(D, e, _pick(options, ("lossfunction", "weights", "classcost", "l1weights", "C")))
+        lmax = _classifier_lambda_max(D, e, _pick(options, ("lossfunction", "weights", "classcost", "l1weights", "C")), gs)
         lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
     else:
         options.pop("nlambda", None)
@@ -977,7 +1041,7 @@ def l1classifier_cv(D, ell, lams=None, options=None):
         if not isinstance(cc, str) and np.ndim(cc) == 2:
             raise ValueError("classcost is one (pos, neg) pair or 'balanced' in l1classifier_cv")
         o["classcost"] = class_cost_pair(cc, ELL[:, 0])
-    for key in ("ridge", "nonnegative"):  # scalars, or L values for every fold alike
+    for key in ("ridge", "nonnegative") + (() if gs is None else ("l1",)):  # scalars, or L values for every fold alike
         if key in o and not (np.isscalar(o[key]) or isinstance(o[key], (bool, np.bool_))):
             v = np.asarray(o[key]).reshape(-1)
             if v.size != L:
@@ -994,7 +1058,8 @@ def l1classifier_cv(D, ell, lams=None, options=None):
         if v.shape != (n, L):
             raise ValueError(f"options.x0 is not a {n} x {L} matrix (one column per lambda)!")
         o["x0"] = np.asfortranarray(np.tile(v, (1, F + 1)))
-    res = l1classifier_multi(D, e, np.concatenate([fold_lams.reshape(-1), lams]), o)
+    res = _run_multi_classifier(D, e, np.concatenate([fold_lams.reshape(-1), lams]), o, who, time.perf_counter(),
+                                None if gs is None else gs[0])
     full = slice(F * L, (F + 1) * L)
     held = {key: res[key][:F * L].reshape(F, L) for key in ("heldout_loss", "heldout_errors", "heldout_weight")}
     chosen = held["heldout_loss"] if measure == "deviance" else held["heldout_errors"]
@@ -1002,6 +1067,8 @@ def l1classifier_cv(D, ell, lams=None, options=None):
     for key in ("xopt", "zopt", "uopt"):
         out[key] = np.asfortranarray(res[key][:, full])
     out["df"] = np.count_nonzero(out["zopt"][m:], axis=0).astype(np.int64)
+    if gs is not None:
+        out.update(groups=gs[0].copy(), df_groups=_df_groups(out["zopt"][m:], gs[0]))
     out.update(steps=res["steps"][full], objopt=res["objopt"][full], fold_steps=res["steps"][:F * L].reshape(F, L),
                fold_lams=fold_lams, **held, nnz=res["nnz"], cg_iters_total=res["cg_iters_total"],
                cg_capped_updates=res["cg_capped_updates"], chunk=res["chunk"], runtime=res["runtime"])
@@ -1061,6 +1128,62 @@ def grouplasso_path(D, s, groups, lams=None, options=None):
     first = np.concatenate([[0], np.cumsum(sizes)[:-1]])
     res["df_groups"] = np.count_nonzero(np.add.reduceat(Z != 0, first, axis=0), axis=0).astype(np.int64)
     return res
+
+
+def groupclassifier_lambda_max(D, ell, groups, options=None):
+    """The smallest lambda whose group classifier is x = 0 when every group is penalised and l1 = 0:
+    C*|phi'(0)|*max over omega_g > 0 of ||(D'(c o ell))_g||_2 / omega_g, c and phi'(0) as in l1classifier_lambda_max.
+    With an unpenalised group (omega_g = 0, an intercept) the all-zero model is in general not optimal at this lambda."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    from ._lib import is_sparse
+    n = _matrix(D, "D", sparse_ok=is_sparse(D)).shape[1]
+    return _classifier_lambda_max(D, ell, options, group_sizes(groups, options.get("groupweights"), n))
+
+
+def groupclassifier_multi(D, ELL, lams, groups, options=None):
+    """results = groupclassifier_multi(D, ELL, lams, groups, options): K group-lasso or sparse-group-lasso classifiers over
+    ONE D, dense or scipy.sparse, in one run -- ``l1classifier_multi``'s objects with groups set:
+
+        minimise C*sum_i c_ik*phi_k(ell_ik*(D*x)_i) + lambda_k*sum_g omega_g*||x_g||_2 + l1_k*sum_j w_j*|x_j|
+                 + ridge_k/2*||x||^2                                                (x >= 0 where nonnegative_k)
+
+    ``groups``: the sizes of the contiguous groups (integers >= 1 that sum to the columns of D), shared by all fits, as
+    ``options['groupweights']`` (omega_g >= 0, default 1; 0 leaves a group unpenalised -- an intercept is a group of one
+    with weight 0) is.  ``lams`` holds the group strengths, ``options['l1']`` (a scalar or K values, default 0) the l1
+    strengths.  This is ``grouplasso_multi``'s convention.  Everything else -- ELL, the losses, ridge, nonnegative,
+    l1weights, weights, classcost, C, the starts, the loop and CG options, foldid / heldout on a sparse D and their
+    refusal on a dense one, the refusals and the result -- is l1classifier_multi's; the result also carries ``groups``."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    return _run_multi_classifier(D, ELL, lams, options, "groupclassifier_multi", time.perf_counter(), groups=groups)
+
+
+def groupclassifier(D, ell, lam, groups, options=None):
+    """results = groupclassifier(D, ell, lam, groups, options): ONE group-lasso classifier, ``groupclassifier_multi`` with
+    K = 1 (group-lasso logistic regression by default).  Returns vectors and scalars as ``l1classifier`` does."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    return _single_classifier(D, ell, lam, options, "groupclassifier_multi", groups=groups)
+
+
+def groupclassifier_path(D, ell, groups, lams=None, options=None):
+    """results = groupclassifier_path(D, ell, groups, lams, options): the regularisation path of ``groupclassifier``, every
+    lambda side by side in one run.  ``lams``: an array, or a count (None: ``options['nlambda']``, default 10) for a grid
+    log-spaced from ``groupclassifier_lambda_max`` down to ``options['lambda_min_ratio']`` (default 1e-2) times it; with
+    any l1 != 0 that lambda_max has no closed form and ``lams`` must be an array (ValueError).  Returns
+    groupclassifier_multi's fields plus ``df``, the nonzeros of each column of the coefficient block of zopt, and
+    ``df_groups``, its groups with a nonzero."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    return _classifier_path(D, ell, lams, options, "groupclassifier_multi", groups=groups)
+
+
+def groupclassifier_cv(D, ell, groups, lams=None, options=None):
+    """results = groupclassifier_cv(D, ell, groups, lams, options): ``l1classifier_cv`` with the group penalty (DESIGN.md
+    q48) on a scipy.sparse D: the same (F + 1)*L fits in one object, the same lambda scaling by training weight,
+    ``classcost = 'balanced'`` from all rows and ``measure``; ``groups`` / ``options['groupweights']`` are shared by all
+    fits and ``options['l1']`` is a scalar or L values (for every fold alike, not scaled).  The automatic grid starts at
+    ``groupclassifier_lambda_max`` and needs l1 = 0.  Returns l1classifier_cv's fields plus ``groups`` and
+    ``df_groups`` of the full-data fits."""
+    options = _options(options, "Argument options is not a struct!", optional=True)
+    return _classifier_cv(D, ell, lams, options, "groupclassifier_cv", groups=groups)
 
 
 def _lad_like(kind, D, s, options):

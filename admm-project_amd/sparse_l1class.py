@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _MultiOwner, _set_svm_cost, _weights
+from .engine import _MultiOwner, _set_multi_groups, _set_svm_cost, _weights
 from .l1class import loss_code
 
 _XSOLVE = dict(auto=L.XSOLVE_AUTO, cg=L.XSOLVE_CG)
@@ -67,6 +67,7 @@ class SparseL1Classifier(_MultiOwner):
         self.dual = True
 
     set_cost = _set_svm_cost
+    set_groups = _set_multi_groups  # (lambda becomes the group strength, l1 the l1 strength)
 
     def set_l1weights(self, l1weights=None):
         """n l1 weights >= 0 shared by all fits (admm_sparse_l1class_set_l1weights); None restores 1"""

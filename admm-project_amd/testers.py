@@ -372,6 +372,44 @@ def sparsel1classifiertest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, errt
     return results, test
 
 
+def groupclassifiertest(seed=0, rows=2 ** 10, variables=12, levels=6, used=4, sparse=True, errtol=0.15, quiet=1,
+                        options=None):
+    """Group-lasso logistic regression on one-hot data: ``variables`` categorical variables of ``levels``
+    levels each, one-hot coded into variables*levels columns behind a column of ones (the intercept: a group of one with
+    weight 0); the labels follow a model that uses the first ``used`` variables alone.  groupclassifier at a fifth of
+    groupclassifier_lambda_max with groupweights sqrt(levels), on a scipy.sparse D (``sparse``) or a dense one.  The
+    criterion is on recovered groups: every used variable's group has a nonzero in z2, no more than a quarter of the
+    unused variables' groups have one, and sign(D*z2) reproduces the labels on at least 1 - errtol of the rows."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed + 4800)
+    cat = rng.integers(0, levels, (rows, variables))
+    n = 1 + variables * levels
+    col = 1 + cat + levels * np.arange(variables)[None, :]
+    D = sp.csc_matrix((np.ones(rows * variables), (np.repeat(np.arange(rows), variables), col.reshape(-1))), shape=(rows, n))
+    D = sp.csc_matrix(sp.hstack([sp.csc_matrix(np.ones((rows, 1))), D[:, 1:]]))
+    truth = np.zeros(n)
+    for v in range(used):
+        eff = rng.choice([-1.0, 1.0], levels) * rng.uniform(1.0, 2.0, levels)
+        truth[1 + v * levels:1 + (v + 1) * levels] = eff - eff.mean()
+    score = D @ truth
+    ell = np.where(score + 0.1 * float(np.std(score)) * rng.standard_normal(rows) >= 0, 1.0, -1.0)
+    sizes = np.array([1] + [levels] * variables, dtype=np.int64)
+    gw = np.concatenate([[0.0], np.full(variables, np.sqrt(levels))])
+    o = _opts(options, objevals=1, quiet=quiet, groupweights=gw)
+    Dd = D if sparse else np.asfortranarray(D.toarray())
+    lam = 0.2 * solvers.groupclassifier_lambda_max(Dd, ell, sizes, o)
+    results = solvers.groupclassifier(Dd, ell, lam, sizes, o)
+    z2 = results["zopt"][rows:]
+    alive = np.array([bool(np.any(z2[1 + v * levels:1 + (v + 1) * levels] != 0)) for v in range(variables)])
+    accuracy = float(np.mean(np.where(D @ z2 >= 0, 1.0, -1.0) == ell))
+    ok = alive[:used].all() and alive[used:].sum() <= (variables - used) // 4 and accuracy >= 1.0 - errtol
+    test = dict(D=Dd, ell=ell, testx=truth, groups=sizes, groupweights=gw, xopt=results["xopt"], zopt=z2, alive=alive,
+                used_found=int(alive[:used].sum()), unused_found=int(alive[used:].sum()), accuracy=accuracy,
+                failed=int(not ok), steps=results["steps"], errtol=errtol)
+    test["lambda"] = lam
+    return results, test
+
+
 def sparsel1classifiercvtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, nfolds=5, nlambda=8, errtol=0.2, quiet=1,
                              options=None):
     """Cross-validation of the l1-regularised logistic regression's path on a sparse design matrix:

@@ -1455,6 +1455,16 @@ int admm_l1class_set_cost(admm_l1class* obj, const double* weights, const double
 /* l1weights = n HOST values w_j >= 0 shared by all fits, copied at the call and held for every later run; NULL
  * restores 1.  ADMM_E_INVALID: a negative or non-finite weight -- a refused call changes nothing. */
 int admm_l1class_set_l1weights(admm_l1class* obj, const double* l1weights);
+/* Groups for every later run of an admm_l1class object (additive to ABI 5; the admm_l1class_* family
+ * itself stays the eleven functions of q42, so this entry point carries the prefix admm_group_l1class_): admm_sparse_lasso_set_groups' arguments, checks and
+ * messages on the classifier.  The penalty of fit k becomes lambda_k*sum_g omega_g*||x_g||_2 + l1[k]*sum_j w_j*|x_j| +
+ * mu_k/2*||x||^2 (x >= 0 where nonneg_k): desc.lambda is the group strength, l1 (K HOST values >= 0, NULL = 0) the l1
+ * strength; sizes = G HOST group sizes >= 1 that sum to n, groupweights = G HOST values omega_g >= 0 (NULL = 1; 0 leaves
+ * a group unpenalised).  G = 0 or sizes = NULL restores the ungrouped prox bit for bit.  ADMM_E_INVALID: a size below 1,
+ * sizes that do not sum to n, a negative or non-finite group weight (its index named) or l1[k] (the fit named);
+ * ADMM_E_UNSUPPORTED: more than 65536 groups that cannot be packed.  A refused call changes nothing. */
+int admm_group_l1class_set_groups(admm_l1class* obj, int32_t G, const int64_t* sizes, const double* groupweights,
+                                  const double* l1);
 /* fits one pass over D serves (K beyond it: ceil(K / chunk) chunks, each with its own two passes) */
 int admm_l1class_chunk(void);
 /* the last run's kernel launches, and how many of them read D (two per chunk and iteration plus one per chunk before
@@ -1549,6 +1559,10 @@ int admm_sparse_l1class_fetch(admm_sparse_l1class* obj, int field, double* dst, 
 /* admm_l1class_set_cost and admm_l1class_set_l1weights on this object: rows weights, K x 2 class costs; cols l1 weights */
 int admm_sparse_l1class_set_cost(admm_sparse_l1class* obj, const double* weights, const double* class_cost);
 int admm_sparse_l1class_set_l1weights(admm_sparse_l1class* obj, const double* l1weights);
+/* admm_group_l1class_set_groups on the sparse object (sizes sum to cols); it combines with set_cost, set_l1weights and set_folds in
+ * any order, and admm_sparse_l1class_kernel_time then times the grouped element kernel */
+int admm_sparse_l1class_set_groups(admm_sparse_l1class* obj, int32_t G, const int64_t* sizes, const double* groupweights,
+                                   const double* l1);
 /* Held-out folds for every later run (additive to ABI 5): fit k gets the cost c_ik = weights[i] * (class
  * cost of fit k by the sign of ell_ik) * [fold[i] != heldout[k]] -- K classifiers that each leave one fold of rows out,
  * over one D.  fold: rows HOST fold ids in [0, nfolds); heldout: K values in [-1, nfolds), -1 (and NULL) = the fit holds
