@@ -375,7 +375,7 @@ class SparseL1ClassSummary(C.Structure):  # admm_sparse_l1class_summary (admm_sp
 
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
-STORAGE_FP64, STORAGE_COMPACT = 0, 1
+STORAGE_FP64, STORAGE_COMPACT, STORAGE_COMPACT40 = 0, 1, 2
 F_WVALS = 23
 F_COVSEL_S = 24
 F_TV2D_ROW_STAGE = 25
@@ -457,6 +457,8 @@ _SIGNATURES = {
     "admm_op_symv": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp]),
     "admm_op_symv_compact": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp, _dp,
                                        C.c_int64]),
+    "admm_op_symv_compact_bits": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, C.c_int32, _dp, _dp,
+                                            C.c_int64, C.c_int32]),
     "admm_op_symv_batch": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int64, C.c_int64, _dp, C.c_int64]),
     "admm_op_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_double, _dp, C.c_int64, _dp,
                                C.c_int64, C.c_double, _dp, C.c_int64, C.c_int32]),

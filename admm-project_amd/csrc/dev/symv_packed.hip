@@ -1,9 +1,10 @@
 // symv_packed.hip -- developer microbenchmark (NOT part of libadmm_hip.so): the lower-triangle SYMV of symv.hip on
 // the column-major padded storage against the same inner loop on TILE-PACKED storage (every 128x128 tile of the
 // lower triangle contiguous, 128 KB, tiles in row-major triangle order).
-//   hipcc -O3 --offload-arch=gfx950 -I.. -o symv_packed symv_packed.hip && ./symv_packed [n] [compact]
+//   hipcc -O3 --offload-arch=gfx950 -I.. -o symv_packed symv_packed.hip && ./symv_packed [n] [compact | compact40]
 // `compact`: only the A/B of the production packed kernel on fp64 tiles against its compact instantiation (tri_tile.h:
 // 48-bit tile-scaled fixed point off the diagonal), back to back, over a sweep of the cacheable share of each.
+// `compact40`: the same with the 40-bit instantiation as a third form in the alternation.
 #include "../symv.hip"
 
 #include <cstdio>
@@ -386,33 +387,44 @@ int main(int argc, char** argv) {
     last_us = us;
     printf("%-44s %8.2f us  %6.3f TB/s\n", name, us, ntri * 131072.0 / us * 1e-6);
   };
-  if (argc > 2 && std::string(argv[2]) == "compact") {  // fp64 tiles against the compact storage, alternating
-    SymvPlan pf = p, pc = p;
-    pf.packed = pc.packed = pc.compact = true;
-    double* C;
-    CK(hipMalloc(&C, sizeof(double) * symv_compact_elems(pc)));
-    launch_symv_compact_pack(pc, P, 0, true, C, nullptr, 0);
-    pc.scales = symv_compact_scales(pc, C);
+  const std::string mode = argc > 2 ? argv[2] : "";
+  if (mode == "compact" || mode == "compact40") {  // fp64 tiles against the compact storage(s), alternating
+    const bool c40 = mode == "compact40";
+    SymvPlan pf = p, pc[2] = {p, p};
+    pf.packed = true;
+    double* C[2] = {nullptr, nullptr};
+    double cmb[2] = {0.0, 0.0};
+    const int nform = c40 ? 2 : 1;
+    for (int k = 0; k < nform; ++k) {
+      pc[k].packed = true;
+      pc[k].cbits = k ? 40 : 48;
+      CK(hipMalloc(&C[k], sizeof(double) * symv_compact_elems(pc[k])));
+      launch_symv_compact_pack(pc[k], P, 0, true, C[k], nullptr, 0);
+      pc[k].scales = symv_compact_scales(pc[k], C[k]);
+      cmb[k] = symv_tile_prefix_bytes(pc[k], ntri) * 1e-6;
+      printf("compact storage, %d bits: %.1f MB (TB/s column: fp64 algorithmic bytes over time)\n", pc[k].cbits, cmb[k]);
+    }
     CK(hipDeviceSynchronize());
-    const double cmb = symv_tile_prefix_bytes(pc, ntri) * 1e-6;
-    printf("compact storage %.1f MB (TB/s column: fp64 algorithmic bytes over time)\n", cmb);
     std::vector<double> h1(n), h2(n);
     for (int round = 0; round < 2; ++round)
       for (int64_t mb : {0, 64, 105, 136, 168, 200, 232, 264, 290, 320}) {
         char nm[96];
         pf.ncached = symv_cached_tiles(pf, mb << 20);
-        pc.ncached = symv_cached_tiles(pc, mb << 20);
-        snprintf(nm, sizeof nm, "fp64    %3lld MB cacheable (%lld tiles)", (long long)mb, (long long)pf.ncached);
+        snprintf(nm, sizeof nm, "fp64      %3lld MB cacheable (%lld tiles)", (long long)mb, (long long)pf.ncached);
         time_it(nm, [&] { launch_symv_lower(pf, P, 0, x, np_, tp, y, nullptr, 0, 0, 1, false); }, y);
-        snprintf(nm, sizeof nm, "compact %3lld MB cacheable (%lld tiles)", (long long)mb, (long long)pc.ncached);
-        time_it(nm, [&] { launch_symv_lower(pc, C, 0, x, np_, tp, y2, nullptr, 0, 0, 1, false); }, y2);
-        printf("   compact over stored bytes: %6.3f TB/s\n", cmb / last_us);
+        for (int k = 0; k < nform; ++k) {
+          pc[k].ncached = symv_cached_tiles(pc[k], mb << 20);
+          snprintf(nm, sizeof nm, "compact%s %3lld MB cacheable (%lld tiles)", k ? "40" : "  ", (long long)mb,
+                   (long long)pc[k].ncached);
+          time_it(nm, [&] { launch_symv_lower(pc[k], C[k], 0, x, np_, tp, y2, nullptr, 0, 0, 1, false); }, y2);
+          printf("   compact%s over stored bytes: %6.3f TB/s\n", k ? "40" : "", cmb[k] / last_us);
+        }
       }
     CK(hipMemcpy(h1.data(), y, sizeof(double) * n, hipMemcpyDeviceToHost));
     CK(hipMemcpy(h2.data(), y2, sizeof(double) * n, hipMemcpyDeviceToHost));
     double err = 0, ymax = 0;
     for (int64_t i = 0; i < n; ++i) err = fmax(err, fabs(h1[i] - h2[i])), ymax = fmax(ymax, fabs(h1[i]));
-    printf("max |y_compact - y_fp64| / max |y| = %.3e\n", err / ymax);
+    printf("max |y_%s - y_fp64| / max |y| = %.3e\n", c40 ? "compact40" : "compact", err / ymax);
     return 0;
   }
   time_it("column-major padded (production)", [&] {

@@ -370,16 +370,28 @@ bool symv_compact_accept(double err_compact, double err_fp64, double diff) {
 // caches runs at the ingest rate of the part, so its time is its byte count: the compact storage (tri_tile.h: 48-bit
 // tile-scaled fixed point off the diagonal, 3/4 of the bytes) is built where the fp64 packed triangle streams, probed
 // as form A against that triangle as form B on the two systems of probe_two_forms, and adopted -- the fp64 triangle
-// freed -- while it is as accurate (within 4x / 8x) or below 1e-11.  A cache-resident matrix is latency-bound and
-// gains nothing; the consensus slices (batched launch), the pseudo-inverse (no factor to probe with) and the
-// row-sharded split x-solve keep fp64.
+// freed -- while it is as accurate (within 4x / 8x) or below 1e-11.  Where even the 48-bit store is larger than
+// kSymvCacheBytes -- part of it comes from HBM in every iteration -- the 40-bit form (5/8 of the bytes) is tried first,
+// under the same rule.  A cache-resident matrix is latency-bound and gains nothing; the consensus slices (batched
+// launch), the pseudo-inverse (no factor to probe with) and the row-sharded split x-solve keep fp64.
+static int try_symv_storage(admm_engine* e, SliceFactor& f, int bits, bool* kept);
 static int choose_symv_storage(admm_engine* e, SliceFactor& f) {
-  if (f.mode != ADMM_XSOLVE_INVERSE || !f.Minv || !f.F || f.pinv || !f.planSy.packed || f.planSy.compact ||
+  if (f.mode != ADMM_XSOLVE_INVERSE || !f.Minv || !f.F || f.pinv || !f.planSy.packed || f.planSy.cbits ||
       f.n < kSymvHalfMin || e->sy_split || e->keep_fp64)
     return ADMM_OK;
   if (!stream_hint(symv_tile_prefix_bytes(f.planSy, symv_tiles(f.planSy)))) return ADMM_OK;
+  SymvPlan c48 = f.planSy;
+  c48.cbits = 48;
+  bool kept = false;
+  if (symv_tile_prefix_bytes(c48, symv_tiles(c48)) > kSymvCacheBytes) ADMM_TRY(try_symv_storage(e, f, 40, &kept));
+  if (!kept) ADMM_TRY(try_symv_storage(e, f, 48, &kept));
+  return ADMM_OK;
+}
+
+// build the compact form of that width, probe it, adopt it or free it; the probe numbers of the last form tried stay
+static int try_symv_storage(admm_engine* e, SliceFactor& f, int bits, bool* kept) {
   SymvPlan cp = f.planSy;
-  cp.compact = true;
+  cp.cbits = bits;
   double* C = nullptr;
   ADMM_TRY(e->mem.alloc(&C, symv_compact_elems(cp)));
   launch_symv_compact_pack(cp, f.Minv, 0, true, C, nullptr, e->stream);
@@ -396,7 +408,8 @@ static int choose_symv_storage(admm_engine* e, SliceFactor& f) {
   f.err_cq = ea;
   f.err_cq_ref = eb;
   f.cq_diff = diff;
-  if (symv_compact_accept(ea, eb, diff)) {
+  *kept = symv_compact_accept(ea, eb, diff);
+  if (*kept) {
     e->mem.free_one(f.Minv);
     f.Minv = C;
     f.planSy = cp;
@@ -1026,7 +1039,8 @@ int admm_engine_xsolve_storage(admm_engine* e, int32_t* form, int64_t* stored_by
   if (!e) return fail(ADMM_E_INVALID, "engine is NULL");
   const SliceFactor& f = e->xfac;
   const bool inv = f.mode == ADMM_XSOLVE_INVERSE && f.Minv;
-  if (form) *form = (inv && f.planSy.compact) ? ADMM_STORAGE_COMPACT : ADMM_STORAGE_FP64;
+  if (form)
+    *form = !(inv && f.planSy.cbits) ? ADMM_STORAGE_FP64 : f.planSy.cbits == 40 ? ADMM_STORAGE_COMPACT40 : ADMM_STORAGE_COMPACT;
   if (stored_bytes) {
     *stored_bytes = 0;
     if (inv && f.planSy.packed) *stored_bytes = symv_tile_prefix_bytes(f.planSy, symv_tiles(f.planSy));

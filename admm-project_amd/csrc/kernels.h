@@ -46,7 +46,8 @@ struct SymvPlan {
   int32_t ntile;   // 128-row wave chunks = 128-column groups: npart and tpart are [ntile][ldp]
   bool packed;     // M is tile-packed (launch_symv_pack): lower-triangle 128x128 tiles back to back, ld unused
   int64_t ncached; // tiles (linear index < ncached) read with default loads; the rest stream non-temporally
-  bool compact;    // packed, off-diagonal tiles as 48-bit tile-scaled fixed point (tri_tile.h): M is that storage
+  int32_t cbits;   // 40 / 48: packed, off-diagonal tiles as tile-scaled fixed point of that width (tri_tile.h), M is
+                   // that storage; 0: fp64 tiles
   const double* scales;  // compact: one power of two per tile
   size_t npart_elems() const { return static_cast<size_t>(ntile) * ldp; }
   size_t tpart_elems() const { return static_cast<size_t>(ntile) * ldp; }
@@ -54,7 +55,8 @@ struct SymvPlan {
 SymvPlan symv_plan(int64_t n);
 // Share of a re-read symmetric matrix that can stay in the 256 MB Infinity Cache next to the rest of an iteration's
 // traffic (measured plateau 105 .. 290 MB at n = 10000, dev/symv_packed.hip; the compact storage, 313 MB in all, has
-// the same plateau: 49.8 us at 105 MB, 48.9 at 168, 48.3 .. 48.5 at 200 .. 232, 48.8 at 264, 56 at 290)
+// the same plateau: 49.8 us at 105 MB, 48.9 at 168, 48.3 .. 48.5 at 200 .. 232, 48.8 at 264, 56 at 290; the 40-bit store, 263 MB: 42.0 at 168, 41.5 at 232, 42.5 read
+// with default loads throughout -- no cliff, and not measured inside the loop)
 constexpr int64_t kSymvCacheBytes = int64_t{168} << 20;
 int64_t symv_tiles(const SymvPlan& p);          // lower-triangle tiles
 size_t symv_packed_elems(const SymvPlan& p);    // doubles of the tile-packed storage
@@ -67,9 +69,9 @@ void launch_symv_lower_batch(const SymvPlan& p, const double* const* Ms_dev, int
                              const FinArgs* fin = nullptr);
 // P (symv_packed_elems doubles) <- the lower-triangle tiles of the padded column-major M (npad x npad, ld)
 void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P, hipStream_t stream);
-// The compact storage of a packed plan (tri_tile.h): diagonal tiles fp64, off-diagonal tiles 48-bit fixed point with one
-// power-of-two scale per tile, the scales behind the tiles in the same buffer of symv_compact_elems doubles.
-// bytes of the leading t tiles in the plan's storage form (p.compact); the plan's ncached counts tiles of that form
+// The compact storage of a packed plan (tri_tile.h): diagonal tiles fp64, off-diagonal tiles p.cbits-bit fixed point with
+// one power-of-two scale per tile, the scales behind the tiles in the same buffer of symv_compact_elems doubles.
+// bytes of the leading t tiles in the plan's storage form (p.cbits); the plan's ncached counts tiles of that form
 int64_t symv_tile_prefix_bytes(const SymvPlan& p, int64_t t);
 size_t symv_compact_elems(const SymvPlan& p);
 double* symv_compact_scales(const SymvPlan& p, double* C);

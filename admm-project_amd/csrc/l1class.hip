@@ -483,7 +483,7 @@ int l1c_setup(admm_l1class* o, const admm_l1class_desc* desc, const std::vector<
   }
   const SliceFactor& f = e->xfac;
   const size_t kp = static_cast<size_t>(o->Kp);
-  if (f.mode == ADMM_XSOLVE_INVERSE && f.Minv && !f.pinv && !f.planSy.compact) {
+  if (f.mode == ADMM_XSOLVE_INVERSE && f.Minv && !f.pinv && !f.planSy.cbits) {
     o->plan = f.planSy;
     if (f.planSy.packed) {
       o->P = f.Minv;

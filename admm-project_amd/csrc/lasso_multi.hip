@@ -137,7 +137,7 @@ int lm_setup(admm_lasso_multi* o, const admm_lasso_multi_desc* desc, const std::
   o->ldt = round_up(n, 2);
   const SliceFactor& f = e->xfac;
   const size_t kp = static_cast<size_t>(o->chunks) * KC;
-  if (f.mode == ADMM_XSOLVE_INVERSE && f.Minv && !f.pinv && !f.planSy.compact) {
+  if (f.mode == ADMM_XSOLVE_INVERSE && f.Minv && !f.pinv && !f.planSy.cbits) {
     o->plan = f.planSy;
     if (f.planSy.packed) {
       o->P = f.Minv;

@@ -537,8 +537,14 @@ int admm_group_multi_plan(int64_t n, const int64_t* sizes, int32_t ngroups, int6
 
 int admm_op_symv_compact(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
                          int32_t part_count, double* y, double* Q, int64_t ldQ) {
+  return admm_op_symv_compact_bits(M, n, ldM, x, fin, ncached, part_count, y, Q, ldQ, 48);
+}
+
+int admm_op_symv_compact_bits(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
+                              int32_t part_count, double* y, double* Q, int64_t ldQ, int32_t bits) {
   if (!M || !x || !y || n <= 0 || ldM < n || ncached < -1 || part_count < 1 || (Q && ldQ < n))
     return fail(ADMM_E_INVALID, "symv_compact: bad argument (ncached >= -1, part_count >= 1, ldQ >= n)");
+  if (bits != 40 && bits != 48) return fail(ADMM_E_INVALID, "symv_compact: the compact tile widths are 40 and 48 bits");
   ADMM_TRY(need_device());
   Scratch sc;
   double *dM, *dx, *dy, *dC, *dQ = nullptr, *npart, *tpart;
@@ -546,7 +552,8 @@ int admm_op_symv_compact(const double* M, int64_t n, int64_t ldM, const double* 
   ADMM_TRY(sc.alloc(&dy, round_up(n, 2)));
   ADMM_HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
   SymvPlan plan = symv_plan(n);
-  plan.packed = plan.compact = true;
+  plan.packed = true;
+  plan.cbits = bits;
   ADMM_TRY(sc.alloc(&dM, static_cast<size_t>(plan.npad) * plan.npad));
   ADMM_HIP_TRY(hipMemset(dM, 0, sizeof(double) * plan.npad * plan.npad));
   ADMM_TRY(put_padded(dM, plan.npad, M, n, ldM));

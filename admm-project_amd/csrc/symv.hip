@@ -28,7 +28,9 @@
 // Compact storage (tri_tile.h): the kernel sits at the ingest rate of the part for the bytes it reads, so the streamed
 // explicit inverse of the engine's own x-solve is stored with its off-diagonal tiles as 48-bit tile-scaled fixed point,
 // 3/4 of the bytes (n = 10000: 313 MB for 414), decoded by two conversions and one FMA per element that hide behind
-// the loads: 64.1 -> 50.8 us per launch, the same 6.2 TB/s over the stored bytes (EXPERIMENTS.md).
+// the loads: 64.1 -> 50.8 us per launch, the same 6.2 TB/s over the stored bytes (EXPERIMENTS.md).  Where even that store
+// is larger than kSymvCacheBytes the engine tries the 40-bit width of the same format first (5/8 of the bytes, n = 10000:
+// 263 MB; engine.hip: choose_symv_storage): one code path, the width a template parameter.
 // The tile pass itself (SyLane, sy_tile) is in tri_tile.h: the backward pass of the one-block triangular solve
 // (trsv.hip: tri1_backward_kernel) is its T-part alone.
 
@@ -44,15 +46,17 @@ namespace admm {
 // PACKED = false: M is npad x npad (npad = round_up(n, 128)) column-major with ld >= npad, zero outside n x n; grid
 // (ntile, ntile).  PACKED = true: M holds the lower-triangle tiles back to back (launch_symv_pack); grid = their count.
 // x: n elements.  Tiles with linear index < ncached use default loads, the others non-temporal ones.
-// COMPACT (PACKED only): M is the compact storage of tri_tile.h -- fp64 diagonal tiles, 48-bit fixed-point off-diagonal
-// tiles -- and scales its per-tile powers of two.
-template <bool PACKED, bool COMPACT = false, int NBUF = 2>
+// CBITS = 40 / 48 (PACKED only): M is the compact storage of tri_tile.h -- fp64 diagonal tiles, fixed-point off-diagonal
+// tiles of that width -- and scales its per-tile powers of two.  CBITS = 0: fp64 tiles.
+template <bool PACKED, int CBITS = 0, int NBUF = 2>
 __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block_y, const double* __restrict__ M,
                                                 int64_t n, int64_t ld, const double* __restrict__ x,
                                                 double* __restrict__ npart, double* __restrict__ tpart, int64_t ldp,
                                                 int32_t part_rank, int32_t part_count, uint32_t ncached,
                                                 const double* __restrict__ scales = nullptr) {
-  static_assert(PACKED || !COMPACT, "the compact storage is tile-packed");
+  static_assert(PACKED || !CBITS, "the compact storage is tile-packed");
+  constexpr bool COMPACT = CBITS != 0;
+  constexpr int BITS = COMPACT ? CBITS : 48;  // (names a format where the compact branches are compiled out)
   unsigned bi, bj, lin;
   if (PACKED) {
     lin = block_x;
@@ -74,7 +78,7 @@ __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block
   int64_t cbase;  // first column as sy_tile counts it
   double* __restrict__ tout = tpart + static_cast<int64_t>(bi) * ldp;
   if (PACKED) {  // the tile is its own 128 x 128 matrix: local row / column numbers, x and tout shifted to its columns
-    s.M = COMPACT ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(M) + cq_tile_offset(lin, bi))
+    s.M = COMPACT ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(M) + cq_tile_offset<BITS>(lin, bi))
                   : M + static_cast<int64_t>(lin) * (kTile * kTile);
     s.x = x + c0;
     s.ld = kTile;
@@ -95,17 +99,17 @@ __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block
   double n0 = 0.0, n1 = 0.0;
   if (lin < ncached) {
     if (bi == bj) sy_tile<true, false, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
-    else if (COMPACT) sy_tile_cq<false, NBUF>(s, scales[lin], n0, n1, tout, lane);
+    else if (COMPACT) sy_tile_cq<false, BITS, NBUF>(s, scales[lin], n0, n1, tout, lane);
     else sy_tile<false, false, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
   } else {
     if (bi == bj) sy_tile<true, true, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
-    else if (COMPACT) sy_tile_cq<true, NBUF>(s, scales[lin], n0, n1, tout, lane);
+    else if (COMPACT) sy_tile_cq<true, BITS, NBUF>(s, scales[lin], n0, n1, tout, lane);
     else sy_tile<false, true, true, true, NBUF>(s, cbase, n0, n1, tout, lane);
   }
   *reinterpret_cast<double2_t*>(npart + static_cast<int64_t>(bj) * ldp + gr) = double2_t{n0, n1};
 }
 
-template <bool PACKED, bool COMPACT = false>
+template <bool PACKED, int CBITS = 0>
 __global__ __launch_bounds__(kWave) void symv_lower_kernel(const double* __restrict__ M, int64_t n, int64_t ld,
                                                            const double* __restrict__ x, double* __restrict__ npart,
                                                            double* __restrict__ tpart, int64_t ldp,
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(kWave) void symv_lower_kernel(const double* __restr
                                                            const Ctrl* __restrict__ ctrl,
                                                            const double* __restrict__ scales) {
   if (ctrl && ctrl->stop) return;
-  symv_lower_body<PACKED, COMPACT>(blockIdx.x, blockIdx.y, M, n, ld, x, npart, tpart, ldp, part_rank, part_count,
+  symv_lower_body<PACKED, CBITS>(blockIdx.x, blockIdx.y, M, n, ld, x, npart, tpart, ldp, part_rank, part_count,
                                    ncached, scales);
 }
 
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(kWave) void symv_lower_kernel(const double* __restr
 // stop decision: ~6 us of one workgroup's serial work) while the other workgroups stream the matrix.  Nothing in this
 // launch depends on that decision, and the fused element update that follows starts after it and no-ops when it has
 // raised ctrl->stop: the tail of an iteration shrinks to the element update itself (engine_run_general.hip, defer_fin).
-template <bool COMPACT>
+template <int CBITS>
 __global__ __launch_bounds__(kWave) void symv_lower_fin_kernel(const double* __restrict__ M, int64_t n,
                                                                const double* __restrict__ x,
                                                                double* __restrict__ npart, double* __restrict__ tpart,
@@ -132,17 +136,17 @@ __global__ __launch_bounds__(kWave) void symv_lower_fin_kernel(const double* __r
   // Every argument of the tile path but x requested at once (fetched where first used they cost four dependent scalar
   // round trips behind the stop test, in a one-tile workgroup that lives ~15 us).  NOT x: with its pointer live this
   // early hipcc allocates 100 VGPRs instead of 84 -- five waves per SIMD instead of six, and 3 % slower, measured.
-  // The COMPACT instantiation allocates 82 (12 dwords per panel buffer instead of 16, the decoded panel in 16 more):
-  // the same occupancy as the fp64 one, scales included in the early request.
+  // The compact instantiations allocate 82, both widths (12 / 10 dwords per panel buffer instead of 16, the decoded
+  // panel in 16 more): the same occupancy as the fp64 one, scales included in the early request.
   asm volatile("" ::"s"(M), "s"(n), "s"(npart), "s"(tpart), "s"(ldp), "s"(part_rank), "s"(part_count), "s"(ncached),
                "s"(fin_pending), "s"(ctrl));
-  if (COMPACT) asm volatile("" ::"s"(scales));
+  if (CBITS) asm volatile("" ::"s"(scales));
   if (ctrl->stop) return;
   if (blockIdx.x == 0) {
     if (fin_pending) finalize_body<false, kWave>(f);
     return;
   }
-  symv_lower_body<true, COMPACT>(blockIdx.x - 1u, 0u, M, n, 0, x, npart, tpart, ldp, part_rank, part_count, ncached,
+  symv_lower_body<true, CBITS>(blockIdx.x - 1u, 0u, M, n, 0, x, npart, tpart, ldp, part_rank, part_count, ncached,
                                  scales);
 }
 
@@ -225,13 +229,15 @@ void launch_symv_small(const double* M, int64_t n, int64_t ld, const double* x, 
 // 16-byte pieces of the panel records.  src: the tile as a column-major 128 x 128 block (ld = 128 inside a tile-packed
 // triangle, the matrix's own ld inside the padded square).  deq (optional): the fp64 tile-packed triangle of the matrix
 // the compact storage represents (scale * q; diagonal tiles as they are) -- what the operator tests compare.
+template <int BITS>
 __device__ __forceinline__ int64_t cq_quantise(double v, int shift) {  // rint(v * 2^shift), clamped
-  const double lim = 140737488355327.0;  // 2^47 - 1
+  constexpr double lim = static_cast<double>((int64_t{1} << (BITS - 1)) - 1);
   double q = rint(ldexp(v, shift));
   q = q > lim ? lim : (q < -lim ? -lim : q);
   return static_cast<int64_t>(q);
 }
 
+template <int BITS>
 __global__ __launch_bounds__(kBlock) void symv_compact_pack_kernel(const double* __restrict__ M, int64_t ld, int packed,
                                                                    char* __restrict__ C, double* __restrict__ scales,
                                                                    double* __restrict__ deq) {
@@ -242,7 +248,8 @@ __global__ __launch_bounds__(kBlock) void symv_compact_pack_kernel(const double*
   const int64_t sld = packed ? kTile : ld;
   const double* src = packed ? M + static_cast<int64_t>(t) * (kTile * kTile)
                              : M + static_cast<int64_t>(bj) * kTile * ld + static_cast<int64_t>(bi) * kTile;
-  char* dst = C + cq_tile_offset(t, bi);
+  typedef CqFormat<BITS> F;
+  char* dst = C + cq_tile_offset<BITS>(t, bi);
   double* dq = deq ? deq + static_cast<int64_t>(t) * (kTile * kTile) : nullptr;
   if (bi == bj) {  // fp64 as it is
     for (int e = 2 * threadIdx.x; e < kTile * kTile; e += 2 * kBlock) {
@@ -264,33 +271,39 @@ __global__ __launch_bounds__(kBlock) void symv_compact_pack_kernel(const double*
   mx = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
   int ex = 0;
   if (mx > 0.0) (void)frexp(mx, &ex);  // mx = f * 2^ex, f in [0.5, 1): mx < 2^ex.  No logarithm of an all-zero tile.
-  const int shift = kCqBits - 1 - ex;
+  const int shift = BITS - 1 - ex;
   const double scale = mx > 0.0 ? ldexp(1.0, -shift) : 0.0;
   if (threadIdx.x == 0) scales[t] = scale;
-  constexpr int kRuns = 3 * kWave;  // 16-byte pieces per panel record
+  constexpr int kRuns = 3 * kWave;  // lane pieces per panel record: 16 bytes in runs 0 and 1, the hi dwords in run 2
   for (int c = threadIdx.x; c < (kTile / kSyPanel) * kRuns; c += kBlock) {
     const int p = c / kRuns, run = (c % kRuns) / kWave, l = c % kWave, r = 2 * l;
-    uint4_t out;
+    char* rec = dst + p * F::kPanelBytes + run * 1024;
     if (run < 2) {
+      uint4_t out;
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int col = kSyPanel * p + 2 * run + k;
         const double2_t v = *reinterpret_cast<const double2_t*>(src + col * sld + r);
-        const int64_t q0 = cq_quantise(v.x, shift), q1 = cq_quantise(v.y, shift);
+        const int64_t q0 = cq_quantise<BITS>(v.x, shift), q1 = cq_quantise<BITS>(v.y, shift);
         out[2 * k] = static_cast<unsigned>(q0 & 0xffffffff);
         out[2 * k + 1] = static_cast<unsigned>(q1 & 0xffffffff);
         if (dq) *reinterpret_cast<double2_t*>(dq + col * kTile + r) =
             double2_t{static_cast<double>(q0) * scale, static_cast<double>(q1) * scale};
       }
+      *reinterpret_cast<uint4_t*>(rec + l * 16) = out;
     } else {
+      uintn_t<F::kHiDwords> out = {};
+      constexpr unsigned mask = (1u << F::kHiBits) - 1u;
 #pragma unroll
       for (int k = 0; k < kSyPanel; ++k) {
         const double2_t v = *reinterpret_cast<const double2_t*>(src + (kSyPanel * p + k) * sld + r);
-        const int64_t q0 = cq_quantise(v.x, shift), q1 = cq_quantise(v.y, shift);
-        out[k] = (static_cast<unsigned>(q0 >> 32) & 0xffffu) | (static_cast<unsigned>(q1 >> 32) << 16);
+        const int64_t q0 = cq_quantise<BITS>(v.x, shift), q1 = cq_quantise<BITS>(v.y, shift);
+        const int bit = 2 * k * F::kHiBits;  // fields 2k and 2k + 1 of the lane share a dword
+        out[bit / 32] |= ((static_cast<unsigned>(q0 >> 32) & mask) << (bit % 32)) |
+                         ((static_cast<unsigned>(q1 >> 32) & mask) << (bit % 32 + F::kHiBits));
       }
+      *reinterpret_cast<uintn_t<F::kHiDwords>*>(rec + l * (4 * F::kHiDwords)) = out;
     }
-    *reinterpret_cast<uint4_t*>(dst + p * kCqPanelBytes + run * 1024 + l * 16) = out;
   }
 }
 
@@ -301,7 +314,7 @@ SymvPlan symv_plan(int64_t n) {
   p.ldp = p.npad;
   p.ntile = static_cast<int32_t>(p.npad / kTile);
   p.packed = false;
-  p.compact = false;
+  p.cbits = 0;
   p.scales = nullptr;
   p.ncached = symv_cached_tiles(p, kSymvCacheBytes);
   return p;
@@ -311,26 +324,20 @@ int64_t symv_tiles(const SymvPlan& p) { return static_cast<int64_t>(p.ntile) * (
 size_t symv_packed_elems(const SymvPlan& p) { return static_cast<size_t>(symv_tiles(p)) * kTile * kTile; }
 
 int64_t symv_tile_prefix_bytes(const SymvPlan& p, int64_t t) {
-  if (!p.compact) return t * int64_t{8} * kTile * kTile;
+  if (!p.cbits) return t * int64_t{8} * kTile * kTile;
   unsigned bi, bj;
   tri_decode(static_cast<unsigned>(t), bi, bj);  // (also right for t = tiles: the row after the last)
-  return cq_tile_offset(static_cast<unsigned>(t), bi);
+  return p.cbits == 40 ? cq_tile_offset<40>(static_cast<unsigned>(t), bi) : cq_tile_offset<48>(static_cast<unsigned>(t), bi);
 }
-size_t symv_compact_elems(const SymvPlan& p) {
-  SymvPlan c = p;
-  c.compact = true;
-  return static_cast<size_t>(symv_tile_prefix_bytes(c, symv_tiles(p)) / 8 + symv_tiles(p));
+size_t symv_compact_elems(const SymvPlan& p) {  // (p.cbits set)
+  return static_cast<size_t>(symv_tile_prefix_bytes(p, symv_tiles(p)) / 8 + symv_tiles(p));
 }
-double* symv_compact_scales(const SymvPlan& p, double* C) {
-  SymvPlan c = p;
-  c.compact = true;
-  return C + symv_tile_prefix_bytes(c, symv_tiles(p)) / 8;
-}
+double* symv_compact_scales(const SymvPlan& p, double* C) { return C + symv_tile_prefix_bytes(p, symv_tiles(p)) / 8; }
 
 int64_t symv_cached_tiles(const SymvPlan& p, int64_t budget_bytes) {
   const int64_t tiles = symv_tiles(p);
   if (!stream_hint(symv_tile_prefix_bytes(p, tiles))) return tiles;  // small enough to stay cache-resident as a whole
-  if (!p.compact) return std::min(tiles, budget_bytes / (int64_t{8} * kTile * kTile));
+  if (!p.cbits) return std::min(tiles, budget_bytes / (int64_t{8} * kTile * kTile));
   int64_t lo = 0, hi = tiles;  // the largest t whose leading t tiles fit
   while (lo < hi) {
     const int64_t mid = (lo + hi + 1) / 2;
@@ -346,8 +353,13 @@ void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P,
 
 void launch_symv_compact_pack(const SymvPlan& p, const double* M, int64_t ld, bool src_packed, double* C, double* deq,
                               hipStream_t stream) {
-  hipLaunchKernelGGL(symv_compact_pack_kernel, dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kBlock), 0, stream, M,
-                     ld, src_packed ? 1 : 0, reinterpret_cast<char*>(C), symv_compact_scales(p, C), deq);
+  const dim3 grid(static_cast<unsigned>(symv_tiles(p)));
+  if (p.cbits == 40)
+    hipLaunchKernelGGL(symv_compact_pack_kernel<40>, grid, dim3(kBlock), 0, stream, M, ld, src_packed ? 1 : 0,
+                       reinterpret_cast<char*>(C), symv_compact_scales(p, C), deq);
+  else
+    hipLaunchKernelGGL(symv_compact_pack_kernel<48>, grid, dim3(kBlock), 0, stream, M, ld, src_packed ? 1 : 0,
+                       reinterpret_cast<char*>(C), symv_compact_scales(p, C), deq);
 }
 
 void launch_symv_reduce(const SymvPlan& p, const double* npart, const double* tpart, double* y, const Ctrl* ctrl,
@@ -360,8 +372,11 @@ void launch_symv_lower(const SymvPlan& p, const double* M, int64_t ld, const dou
                        double* y, const Ctrl* ctrl, hipStream_t stream, int part_rank, int part_count, bool reduce) {
   const uint32_t ncached = static_cast<uint32_t>(p.ncached < 0 ? 0 : p.ncached);
   const double* none = nullptr;
-  if (p.packed && p.compact)
-    hipLaunchKernelGGL((symv_lower_kernel<true, true>), dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0,
+  if (p.packed && p.cbits == 40)
+    hipLaunchKernelGGL((symv_lower_kernel<true, 40>), dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0,
+                       stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl, p.scales);
+  else if (p.packed && p.cbits)
+    hipLaunchKernelGGL((symv_lower_kernel<true, 48>), dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0,
                        stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl, p.scales);
   else if (p.packed)
     hipLaunchKernelGGL(symv_lower_kernel<true>, dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0, stream, M,
@@ -389,11 +404,14 @@ void launch_symv_lower_fin(const SymvPlan& p, const double* M, const double* x, 
   const uint32_t ncached = static_cast<uint32_t>(p.ncached < 0 ? 0 : p.ncached);
   const dim3 grid(static_cast<unsigned>(symv_tiles(p)) + 1u);
   const double* none = nullptr;
-  if (p.compact)
-    hipLaunchKernelGGL(symv_lower_fin_kernel<true>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
+  if (p.cbits == 40)
+    hipLaunchKernelGGL(symv_lower_fin_kernel<40>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
+                       part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, p.scales);
+  else if (p.cbits)
+    hipLaunchKernelGGL(symv_lower_fin_kernel<48>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
                        part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, p.scales);
   else
-    hipLaunchKernelGGL(symv_lower_fin_kernel<false>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
+    hipLaunchKernelGGL(symv_lower_fin_kernel<0>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
                        part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, none);
   if (y) launch_symv_reduce(p, npart, tpart, y, ctrl, stream);  // else the consumer sums the partial rows itself
 }

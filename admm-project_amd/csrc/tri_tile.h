@@ -22,23 +22,35 @@ __host__ __device__ __forceinline__ void tri_decode(unsigned t, unsigned& bi, un
 // ---------------------------------------------------------------- compact storage of a symmetric tile-packed triangle
 // (symv.hip: the cached explicit inverse of the streamed x-solve).  Same tiles in the same order; a DIAGONAL tile keeps
 // its fp64 layout (128 KB: its diagonal entries are hundreds of times larger than the rest of the tile), an OFF-DIAGONAL
-// tile t is 48-bit signed fixed point with one power-of-two scale per tile (96 KB):
-//   e = binary exponent of the tile's largest magnitude (max < 2^e),  scale_t = 2^(e - 47)   (all-zero tile: scale 0)
-//   q = rint(M / scale_t) clamped to +-(2^47 - 1),  q = hi * 2^32 + lo,  hi signed 16 bits, lo unsigned 32 bits
-// A tile is 32 panel records of 3 KB, record p = columns 4p .. 4p + 3 as three 1 KB runs of 16 bytes per lane:
-//   run 0: lo of (r, 4p), (r + 1, 4p), (r, 4p + 1), (r + 1, 4p + 1)   r = 2 * lane, the lane's row pair
-//   run 1: the same of columns 4p + 2, 4p + 3
-//   run 2: four dwords, dword k = hi of (r, 4p + k) in its low half and of (r + 1, 4p + k) in its high half
-// so every lane load is 16 bytes, aligned, and a wave reads one contiguous 3 KB per panel.  The row before tile
-// (bi, bj) holds bi diagonal tiles, so tile t starts at byte (3 t + bi) * 32 KB.  The scales are one double per tile
-// (diagonal tiles: 1, unused) in an array of their own.  The kernel decodes fma(cvt(hi), 2^32, cvt(lo)) -- exact, 48
-// bits fit the mantissa -- and applies the scale once per tile (cq_scale_*): the product over the quantised matrix
-// rounds exactly where the fp64 kernel's does.
-constexpr int64_t kCqUnit = 32768;         // tile offsets count in these: a diagonal tile is 4, a compact one 3
-constexpr int kCqPanelBytes = 3 * 1024;    // one panel record
-constexpr int kCqBits = 48;
+// tile t is BITS-bit signed fixed point with one power-of-two scale per tile, BITS = 48 (96 KB) or 40 (80 KB):
+//   e = binary exponent of the tile's largest magnitude (max < 2^e),  scale_t = 2^(e - (BITS - 1))   (all-zero tile: 0)
+//   q = rint(M / scale_t) clamped to +-(2^(BITS-1) - 1),  q = hi * 2^32 + lo,  hi signed BITS - 32 bits, lo unsigned 32
+// A tile is 32 panel records, record p = columns 4p .. 4p + 3 as three runs, one piece per lane in each:
+//   run 0 (1 KB, 16 bytes per lane): lo of (r, 4p), (r + 1, 4p), (r, 4p + 1), (r + 1, 4p + 1)   r = 2 * lane, the row pair
+//   run 1 (1 KB): the same of columns 4p + 2, 4p + 3
+//   run 2: the lane's eight hi fields in the order (r, 4p), (r + 1, 4p), (r, 4p + 1), ... (r + 1, 4p + 3), lowest bits
+//          first -- 48 bit: 16 bytes per lane, dword k = column 4p + k;  40 bit: 8 bytes per lane, one byte per field
+// so every lane load is aligned to its size and a wave reads one contiguous record (3 KB / 2.5 KB) per panel.  Tile
+// offsets count in units of 32 KB / 16 KB -- a diagonal tile is 4 / 8 of them, a compact one 3 / 5 -- and the rows before
+// tile (bi, bj) hold bi diagonal tiles, so tile t starts at (3 t + bi) * 32 KB / (5 t + 3 bi) * 16 KB.  The scales are one
+// double per tile (diagonal tiles: 1, unused) in an array of their own.  The kernel decodes fma(cvt(hi), 2^32, cvt(lo))
+// -- exact, BITS bits fit the mantissa -- and applies the scale once per tile (sy_tile_cq): the product over the
+// quantised matrix rounds exactly where the fp64 kernel's does.
+template <int BITS>
+struct CqFormat {
+  static_assert(BITS == 40 || BITS == 48, "compact tile widths");
+  static constexpr int kHiBits = BITS - 32;                      // one hi field
+  static constexpr int kHiDwords = 8 * kHiBits / 32;             // run 2, per lane
+  static constexpr int kPanelBytes = 2048 + 64 * 4 * kHiDwords;  // one panel record
+  static constexpr int64_t kUnit = (BITS == 48) ? 32768 : 16384;  // tile offsets count in these
+  static constexpr int kTileUnits = (kTile / 4) * kPanelBytes / kUnit;  // 3 / 5: a tile is its 32 panel records
+  static constexpr int kDiagUnits = 8 * kTile * kTile / kUnit;          // 4 / 8
+  static_assert(kTileUnits * kUnit == (kTile / 4) * kPanelBytes && kTileUnits == (BITS == 48 ? 3 : 5), "whole units");
+};
+template <int BITS>
 __host__ __device__ __forceinline__ int64_t cq_tile_offset(unsigned t, unsigned bi) {
-  return (int64_t{3} * t + bi) * kCqUnit;
+  typedef CqFormat<BITS> F;
+  return (int64_t{F::kTileUnits} * t + int64_t{F::kDiagUnits - F::kTileUnits} * bi) * F::kUnit;
 }
 
 // ---------------------------------------------------------------- N-part: a panel of P columns, rows in registers
@@ -82,7 +94,7 @@ __device__ __forceinline__ void sy_load(const SyLane& s, int64_t cp, double2_t (
   for (int k = 0; k < kSyPanel; ++k) d[k] = load2<NT>(s.M + (cp + k) * s.ld + s.r);  // wave-uniform column base
 }
 
-// one panel buffer of the ring in sy_tile: the fp64 form holds the panel itself, the compact form its 48 bytes per lane
+// one panel buffer of the ring in sy_tile: the fp64 form holds the panel itself, the compact form its 48 / 40 bytes per lane
 template <bool NT>
 struct SyBuf64 {
   double2_t d[kSyPanel];
@@ -94,30 +106,38 @@ struct SyBuf64 {
 };
 
 typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ uint4_t load16(const char* p) {
-  const uint4_t* q = reinterpret_cast<const uint4_t*>(p);
+template <int N>
+using uintn_t = unsigned __attribute__((ext_vector_type(N)));
+template <bool NT, int N>
+__device__ __forceinline__ uintn_t<N> loadn(const char* p) {  // N dwords, aligned to their size
+  const uintn_t<N>* q = reinterpret_cast<const uintn_t<N>*>(p);
   return NT ? __builtin_nontemporal_load(q) : *q;
 }
 __device__ __forceinline__ double cq_value(unsigned lo, int hi) {
   return __builtin_fma(static_cast<double>(hi), 4294967296.0, static_cast<double>(lo));
 }
 // s.M: the compact tile; cp: first column of the panel within the tile (a multiple of 4)
-template <bool NT>
+template <bool NT, int BITS>
 struct SyBufCq {
-  uint4_t lo[2], hi;
+  typedef CqFormat<BITS> F;
+  uint4_t lo[2];
+  uintn_t<F::kHiDwords> hi;
   __device__ __forceinline__ void load(const SyLane& s, int64_t cp) {
-    const char* p = reinterpret_cast<const char*>(s.M) + (cp >> 2) * kCqPanelBytes + s.r * 8;
-    lo[0] = load16<NT>(p);
-    lo[1] = load16<NT>(p + 1024);
-    hi = load16<NT>(p + 2048);
+    const char* p = reinterpret_cast<const char*>(s.M) + (cp >> 2) * F::kPanelBytes;
+    lo[0] = loadn<NT, 4>(p + s.r * 8);
+    lo[1] = loadn<NT, 4>(p + 1024 + s.r * 8);
+    hi = loadn<NT, F::kHiDwords>(p + 2048 + s.r * (2 * F::kHiDwords));
+  }
+  // hi field i of the lane (i = 2 k: row r of column k, 2 k + 1: row r + 1), sign-extended
+  __device__ __forceinline__ int hi_field(int i) const {
+    const int bit = i * F::kHiBits;
+    return static_cast<int>(hi[bit / 32] << (32 - F::kHiBits - bit % 32)) >> (32 - F::kHiBits);
   }
   __device__ __forceinline__ void get(double2_t (&o)[kSyPanel]) const {
 #pragma unroll
     for (int k = 0; k < kSyPanel; ++k) {
-      const int h = static_cast<int>(hi[k]);
-      o[k].x = cq_value(lo[k >> 1][2 * (k & 1)], static_cast<int>(static_cast<short>(h)));
-      o[k].y = cq_value(lo[k >> 1][2 * (k & 1) + 1], h >> 16);
+      o[k].x = cq_value(lo[k >> 1][2 * (k & 1)], hi_field(2 * k));
+      o[k].y = cq_value(lo[k >> 1][2 * (k & 1) + 1], hi_field(2 * k + 1));
     }
   }
 };
@@ -194,12 +214,12 @@ __device__ __forceinline__ void sy_tile(const SyLane& s, int64_t c0, double& n0,
 
 // an off-diagonal tile of the compact storage (s.M: the tile, c0 = 0).  scale: the tile's power of two, folded into the
 // lane's x pair before the pass (T-part) and into the N accumulators after it -- four multiplications per tile, exact
-template <bool NT, int NBUF = 2>
+template <bool NT, int BITS, int NBUF = 2>
 __device__ __forceinline__ void sy_tile_cq(SyLane& s, double scale, double& n0, double& n1, double* __restrict__ tout,
                                            int lane) {
   s.xr0 *= scale;
   s.xr1 *= scale;
-  sy_tile_ring<false, SyBufCq<NT>, true, true, NBUF>(s, 0, n0, n1, tout, lane);
+  sy_tile_ring<false, SyBufCq<NT, BITS>, true, true, NBUF>(s, 0, n0, n1, tout, lane);
   n0 *= scale;
   n1 *= scale;
 }

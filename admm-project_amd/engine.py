@@ -513,13 +513,14 @@ class Engine:
 
     def xsolve_storage(self):
         """How the explicit inverse of the x-update is stored (admm_engine_xsolve_storage): dict(form = "fp64" |
-        "compact", stored_bytes, and the three numbers of the probe that decided it -- NaN where the compact form was
-        not built)"""
+        "compact" (48-bit tiles) | "compact40", stored_bytes, and the three numbers of the probe that decided it -- NaN
+        where no compact form was built)"""
         form, nbytes = C.c_int32(), C.c_int64()
         ea, eb, diff = C.c_double(), C.c_double(), C.c_double()
         L.check(self._lib.admm_engine_xsolve_storage(self._h, C.byref(form), C.byref(nbytes), C.byref(ea), C.byref(eb),
                                                      C.byref(diff)))
-        return dict(form="compact" if form.value == L.STORAGE_COMPACT else "fp64", stored_bytes=nbytes.value,
+        names = {L.STORAGE_FP64: "fp64", L.STORAGE_COMPACT: "compact", L.STORAGE_COMPACT40: "compact40"}
+        return dict(form=names[form.value], stored_bytes=nbytes.value,
                     probe_err_compact=ea.value, probe_err_fp64=eb.value, probe_diff=diff.value)
 
     def info(self):

@@ -491,8 +491,10 @@ int admm_engine_info(admm_engine* eng, admm_engine_info_t* info);
  * admm_xsolve_compact_accept holds.  stored_bytes: what one x-solve reads (0: no explicit inverse in use).  The three
  * probe numbers -- max-norm relative forward error of the compact and of the fp64 product on (L L') x = L (L' x0),
  * their relative difference on an unstructured right-hand side -- are NaN where the compact form was not built.  Any
- * output pointer may be NULL. */
-enum { ADMM_STORAGE_FP64 = 0, ADMM_STORAGE_COMPACT = 1 };
+ * output pointer may be NULL.  ADMM_STORAGE_COMPACT40: the same format with 40-bit tiles, 5/8 of the bytes, tried first
+ * (same rule, then the 48-bit form) where the 48-bit store is larger than the cacheable share of the x-solve; the probe
+ * numbers are those of the form in use. */
+enum { ADMM_STORAGE_FP64 = 0, ADMM_STORAGE_COMPACT = 1, ADMM_STORAGE_COMPACT40 = 2 };
 int admm_engine_xsolve_storage(admm_engine* eng, int32_t* form, int64_t* stored_bytes, double* probe_err_compact,
                                double* probe_err_fp64, double* probe_diff);
 /* the acceptance rule itself (host arithmetic, no device): 1 while
@@ -709,6 +711,9 @@ int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32
  * triangle mirrored. */
 int admm_op_symv_compact(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
                          int32_t part_count, double* y, double* Q, int64_t ldQ);
+/* the same with the tile width chosen: bits = 48 (admm_op_symv_compact itself) or 40; any other width is ADMM_E_INVALID */
+int admm_op_symv_compact_bits(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
+                              int32_t part_count, double* y, double* Q, int64_t ldQ, int32_t bits);
 /* Y(:,k) = M_k * X(:,k), k < K: K symmetric n x n matrices stored back to back (matrix k at Ms + k*ldM*n), tile-packed
  * and multiplied in ONE batched launch (the slice inverses of consensus lasso); lower triangles only, ncached as above */
 int admm_op_symv_batch(const double* Ms, int64_t n, int64_t ldM, int32_t K, const double* X, int64_t ldX,
