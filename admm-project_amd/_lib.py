@@ -579,6 +579,8 @@ _SIGNATURES = {
     "admm_sparse_l1class_set_l1weights": (C.c_int, [C.c_void_p, _dp]),
     "admm_sparse_l1class_set_folds": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "admm_sparse_l1class_heldout": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "admm_sparse_l1class_set_multinomial": (C.c_int, [C.c_void_p, C.c_int32]),
+    "admm_op_softmax_prox": (C.c_int, [_dp, C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_int32)]),
     "admm_sparse_l1class_chunk": (C.c_int, []),
     "admm_sparse_l1class_kernel_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                                   C.POINTER(C.c_double)]),

@@ -34,6 +34,7 @@
 #include "l1class_device.h"
 #include "l1class_group_device.h"
 #include "multi_host.h"
+#include "softmax_device.h"
 #include "spmm_cg.h"
 #include "svm_cost_device.h"
 
@@ -60,6 +61,8 @@ struct Sl1cRowArgs {
   // so that the kernels without folds load their arguments from the offsets they always had
   const int32_t* fold;  // m fold ids, or null: no folds
   const int32_t* held;  // K values: the fold fit k holds out, or -1
+  // the multinomial model (admm_sparse_l1class_set_multinomial, q49), read by the launcher alone: 0, or the classes Cn
+  int32_t classes;
 };
 
 // the sums of the held-out pass over m (q47), per fit over the rows with fold_i = held_k, c = w_i * class cost: the loss
@@ -140,6 +143,139 @@ __global__ __launch_bounds__(kScgBlock) void sl1c_row_kernel(Sl1cRowArgs a) {
   if (INIT) return;
   scg_sums<LM_COUNT>(acc, lds, a.part, LM_COUNT, 0);
 }
+
+// The multinomial form (q49), CN classes per model and KC / CN models per chunk: model p of a chunk owns the slots
+// [p*CN, (p + 1)*CN).  The same grid, thread layout and sums.  The row's values of D x + u1, of D x and of the labels go
+// through LDS; the thread of a model's first slot solves the row prox of its CN values (softmax_device.h) -- its cost is
+// w_i times the class weight CC[2 k] of the true class's fit k -- writes z1 back to LDS and keeps the model's loss;
+// behind the barrier every thread finishes its own element as the per-fit kernel does.  The other classes add +0.0 to
+// the loss slot.  The slots behind the chunk's last model are stopped from the start of a run and idle here.
+template <int CN>
+__global__ __launch_bounds__(kScgBlock) void sl1c_row_multinomial_kernel(Sl1cRowArgs a) {
+  __shared__ double lds[LM_COUNT * kScgBlock];
+  __shared__ double sv[kScgBlock], sx[kScgBlock], se[kScgBlock];
+  const ScgLane l = scg_lane(a.rec, a.K);
+  if (!__syncthreads_or(l.run)) return;
+  const int tid = threadIdx.x;
+  const int64_t base = static_cast<int64_t>(blockIdx.y) * a.m * KC;
+  double acc[LM_COUNT];
+#pragma unroll
+  for (int q = 0; q < LM_COUNT; ++q) acc[q] = 0.0;
+  const int fit = l.run ? l.fit : 0;
+  const bool lead = l.run && l.c % CN == 0 && l.c + CN <= KC;
+  const int64_t nrb = (a.m + kScgRows - 1) / kScgRows;
+  for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {  // (uniform over the workgroup: the barriers are too)
+    const int64_t i = rb * kScgRows + l.r;
+    const bool on = l.run && i < a.m;
+    const int64_t e = base + i * KC + l.c;
+    double zp = 0.0, uo = 0.0, ax = 0.0;
+    if (on) {
+      zp = a.Z1[e];
+      uo = a.U1[e];
+      ax = a.AX[e];
+      sv[tid] = ax + uo;
+      sx[tid] = ax;
+      se[tid] = a.ELL[e];
+    }
+    __syncthreads();
+    if (lead && on) {
+      double v[CN], z[CN];
+      int y = 0;
+#pragma unroll
+      for (int k = 0; k < CN; ++k) {
+        v[k] = sv[tid + k];
+        y = se[tid + k] > 0.0 ? k : y;
+      }
+      const double ci = (a.W ? a.W[i] : 1.0) * a.CC[2 * (fit + y)];
+      softmax_prox<CN>(v, y, (a.C * ci) / a.rho, z);
+#pragma unroll
+      for (int k = 0; k < CN; ++k) sv[tid + k] = z[k];
+      if (a.objevals) {
+#pragma unroll
+        for (int k = 0; k < CN; ++k) v[k] = sx[tid + k];
+        acc[LM_LOSS] += ci * softmax_loss<CN>(v, y);
+      }
+    }
+    __syncthreads();
+    if (on) {
+      const double zn = sv[tid];
+      const double rr = ax - zn;  // A x + B z - c
+      const double un = uo + rr;  // admm.m:542-550
+      acc[LM_R2] += rr * rr;
+      acc[LM_AX2] += ax * ax;
+      acc[LM_Z2] += zn * zn;
+      a.Z1[e] = zn;
+      a.U1[e] = un;
+      a.T1[e] = zn - un;
+      if (a.DZ1) a.DZ1[e] = zn - zp;
+    }
+  }
+  scg_sums<LM_COUNT>(acc, lds, a.part, LM_COUNT, 0);
+}
+
+// one workgroup per model (blockIdx.x = chunk * (KC / CN) + model of the chunk): l1c_model_fin_body
+__global__ __launch_bounds__(kL1cModelFinThreads) void sl1c_model_fin_kernel(L1cFinArgs a, int32_t classes) {
+  const int per = KC / classes;
+  const int fit0 = (static_cast<int>(blockIdx.x) / per) * KC + (static_cast<int>(blockIdx.x) % per) * classes;
+  if (fit0 + classes > a.K) return;
+  l1c_model_fin_body(a, fit0, classes);
+}
+
+// blockIdx.x * blockDim.x + threadIdx.x = row: the row prox alone (admm_op_softmax_prox)
+template <int CN>
+__global__ __launch_bounds__(kBlock) void softmax_prox_op_kernel(const double* __restrict__ V, const int32_t* __restrict__ y,
+                                                                 const double* __restrict__ av, int64_t m,
+                                                                 double* __restrict__ out, int32_t* __restrict__ iters) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= m) return;
+  double v[CN], z[CN];
+#pragma unroll
+  for (int k = 0; k < CN; ++k) v[k] = V[i * CN + k];
+  iters[i] = softmax_prox<CN>(v, y[i], av[i], z);
+#pragma unroll
+  for (int k = 0; k < CN; ++k) out[i * CN + k] = z[k];
+}
+
+// f.template operator()<CN>() for the run-time classes in 2 .. KC
+template <class F>
+void with_classes(int32_t classes, F f) {
+  switch (classes) {
+    case 2: return f.template operator()<2>();
+    case 3: return f.template operator()<3>();
+    case 4: return f.template operator()<4>();
+    case 5: return f.template operator()<5>();
+    case 6: return f.template operator()<6>();
+    case 7: return f.template operator()<7>();
+    case 8: return f.template operator()<8>();
+    case 9: return f.template operator()<9>();
+    default: return f.template operator()<10>();
+  }
+}
+static_assert(KC == 10, "with_classes lists the class counts of one chunk");
+
+struct RowMultinomialLaunch {
+  const Sl1cRowArgs& a;
+  dim3 grid;
+  hipStream_t stream;
+  template <int CN>
+  void operator()() const {
+    hipLaunchKernelGGL(sl1c_row_multinomial_kernel<CN>, grid, dim3(kScgBlock), 0, stream, a);
+  }
+};
+
+struct ProxOpLaunch {
+  const double* V;
+  const int32_t* y;
+  const double* av;
+  int64_t m;
+  double* out;
+  int32_t* iters;
+  template <int CN>
+  void operator()() const {
+    hipLaunchKernelGGL(softmax_prox_op_kernel<CN>, dim3(static_cast<unsigned>((m + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       nullptr, V, y, av, m, out, iters);
+  }
+};
 
 // behind the loop, at T = D Z2 (q47): the three held-out sums of EVERY fit, stopped or not, in the row kernel's thread
 // layout and scg_sums' order.  A row the fit does not hold out adds +0.0 by a select; held = -1 matches no fold id
@@ -225,8 +361,14 @@ __global__ __launch_bounds__(kScgBlock) void sl1c_group_elem_kernel(L1cGroupElem
 void launch_sl1c_row(const Sl1cRowArgs& a, bool init, hipStream_t stream) {
   const dim3 grid(scg_vec_workgroups(a.m), static_cast<unsigned>(spmm_chunks(a.K)));
   if (init) hipLaunchKernelGGL(sl1c_row_kernel<true>, grid, dim3(kScgBlock), 0, stream, a);
+  else if (a.classes) with_classes(a.classes, RowMultinomialLaunch{a, grid, stream});
   else if (a.fold) hipLaunchKernelGGL((sl1c_row_kernel<false, true>), grid, dim3(kScgBlock), 0, stream, a);
   else hipLaunchKernelGGL(sl1c_row_kernel<false>, grid, dim3(kScgBlock), 0, stream, a);
+}
+
+void launch_sl1c_model_fin(const L1cFinArgs& a, int32_t classes, hipStream_t stream) {
+  const unsigned models = static_cast<unsigned>(spmm_chunks(a.K) * (KC / classes));
+  hipLaunchKernelGGL(sl1c_model_fin_kernel, dim3(models), dim3(kL1cModelFinThreads), 0, stream, a, classes);
 }
 
 void launch_sl1c_heldout(const Sl1cHeldArgs& a, int32_t nwg_m, double* heldout, hipStream_t stream) {
@@ -272,6 +414,10 @@ struct admm_sparse_l1class : admm::MultiHost {
   double *hpart = nullptr, *held_dev = nullptr;  // the held-out pass's own partials; K x LH_COUNT totals
   std::vector<double> held_host;  // the same on the host; empty: no run under folds behind the object
   admm::GroupMulti grp;  // admm_sparse_l1class_set_groups (q48)
+  // admm_sparse_l1class_set_multinomial (q49); classes 0: the per-fit object.  start: the records a run starts from, the
+  // idle slots behind a chunk's last model stopped
+  int32_t classes = 0;
+  std::vector<admm::MultiRec> start;
   double *pnorm = nullptr, *perr = nullptr, *dnorm = nullptr, *derr = nullptr, *objv = nullptr;  // histories
   admm_sparse_l1class_options last{};
 };
@@ -364,6 +510,16 @@ int sl1c_fetch_stacked(admm_sparse_l1class* o, const double* V1, const double* V
   return ADMM_OK;
 }
 
+// begin_run, and under the multinomial model the idle slots stopped before any kernel reads a record
+int sl1c_begin_run(admm_sparse_l1class* o) {
+  ADMM_TRY(begin_run(*o));
+  if (o->classes) {
+    ADMM_HIP_TRY(hipMemcpyAsync(o->rec, o->start.data(), sizeof(MultiRec) * o->K, hipMemcpyHostToDevice, o->stream));
+    ADMM_HIP_TRY(hipStreamSynchronize(o->stream));
+  }
+  return ADMM_OK;
+}
+
 Sl1cRowArgs sl1c_row_args(const admm_sparse_l1class* o, bool dual, int32_t objevals, double rho) {
   Sl1cRowArgs a{};
   a.m = o->m;
@@ -385,6 +541,7 @@ Sl1cRowArgs sl1c_row_args(const admm_sparse_l1class* o, bool dual, int32_t objev
   a.C = o->C;
   a.fold = o->fold;
   a.held = o->held;
+  a.classes = o->classes;
   return a;
 }
 
@@ -479,7 +636,7 @@ int admm_sparse_l1class_run(admm_sparse_l1class* o, const admm_sparse_l1class_op
   const int32_t N = op.maxiters, K = o->K;
   ADMM_TRY(resize_histories(*o, {&o->pnorm, &o->perr, &o->dnorm, &o->derr, &o->objv}, N));
   SpmmCg& cg = o->cg;
-  ADMM_TRY(begin_run(*o));
+  ADMM_TRY(sl1c_begin_run(o));
   ScgArgs ca{};
   ADMM_TRY(cg.begin_run(op.cg_tol, op.cg_maxit, &ca, 1.0));  // D'D + I: the shift is 1 for every rho
   ADMM_TRY(sl1c_upload_stacked(o, op.z0, o->Z1, o->Z2));
@@ -527,7 +684,8 @@ int admm_sparse_l1class_run(admm_sparse_l1class* o, const admm_sparse_l1class_op
       launch_spmm(cg.sp.t, o->U1, o->GU, cg.chunks, run, o->stream);    // D'u1
     }
     launch_sl1c_elem_iter(ea, o->grp, o->stream);
-    launch_l1c_fin(fa, o->stream);
+    if (o->classes) launch_sl1c_model_fin(fa, o->classes, o->stream);
+    else launch_l1c_fin(fa, o->stream);
     if ((it + 1) % op.check_every == 0 || it + 1 == N) ADMM_TRY(poll_all_stopped(*o, &all));
   }
   o->held_host.clear();
@@ -557,6 +715,8 @@ int admm_sparse_l1class_set_folds(admm_sparse_l1class* o, int32_t nfolds, const 
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
   const int64_t m = o->m;
   const int32_t K = o->K;
+  if (o->classes && fold)
+    return fail(ADMM_E_UNSUPPORTED, "held-out folds are not part of the multinomial model (admm_sparse_l1class_set_multinomial)");
   ADMM_TRY(check_observations(m, K, nullptr, nfolds, fold, heldout));  // (the lasso's own checks; a refused call changes nothing)
   ADMM_HIP_TRY(hipSetDevice(o->device));
   int32_t *f = nullptr, *hd = nullptr;
@@ -603,13 +763,114 @@ int admm_sparse_l1class_set_l1weights(admm_sparse_l1class* o, const double* l1we
 int admm_sparse_l1class_set_groups(admm_sparse_l1class* o, int32_t G, const int64_t* sizes, const double* groupweights,
                                    const double* l1) {
   if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  if (o->classes && G > 0)
+    return fail(ADMM_E_UNSUPPORTED, "groups are not part of the multinomial model (admm_sparse_l1class_set_multinomial)");
   return set_multi_groups(*o, o->n, G, sizes, groupweights, l1, &o->grp);
+}
+
+int admm_sparse_l1class_set_multinomial(admm_sparse_l1class* o, int32_t classes) {
+  if (!o) return fail(ADMM_E_INVALID, "object is NULL");
+  if (classes == 0) {
+    o->classes = 0;
+    o->start.clear();
+    return ADMM_OK;
+  }
+  if (classes < 2 || classes > KC)
+    return fail(ADMM_E_INVALID, "multinomial: classes = " + std::to_string(classes) + " is neither 0 nor in 2 .. " +
+                                    std::to_string(KC));
+  if (o->fold) return fail(ADMM_E_UNSUPPORTED, "the multinomial model does not combine with held-out folds (admm_sparse_l1class_set_folds)");
+  if (o->grp.on()) return fail(ADMM_E_UNSUPPORTED, "the multinomial model does not combine with groups (admm_sparse_l1class_set_groups)");
+  const int32_t K = o->K, per = KC / classes, rem = K % KC;
+  if (rem % classes != 0 || rem > per * classes)
+    return fail(ADMM_E_INVALID, "multinomial: the last chunk holds " + std::to_string(rem) + " fits, not a multiple of " +
+                                    std::to_string(classes) + " classes up to " + std::to_string(per * classes));
+  if (o->ell_shared) return fail(ADMM_E_INVALID, "multinomial: the model needs one label column per fit (nell = K)");
+  ADMM_HIP_TRY(hipSetDevice(o->device));
+  std::vector<int32_t> lh(static_cast<size_t>(K)), nh(static_cast<size_t>(K));
+  std::vector<double> ph(static_cast<size_t>(2) * K);
+  ADMM_HIP_TRY(hipMemcpy(lh.data(), o->loss, sizeof(int32_t) * K, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(nh.data(), o->nonneg, sizeof(int32_t) * K, hipMemcpyDeviceToHost));
+  ADMM_HIP_TRY(hipMemcpy(ph.data(), o->par, sizeof(double) * 2 * K, hipMemcpyDeviceToHost));
+  std::vector<MultiRec> start(static_cast<size_t>(K), MultiRec{0, 0, 0, 0});
+  for (int32_t k = 0; k < K; ++k) {
+    const int32_t c = k % KC;
+    if (c >= per * classes) {  // an idle slot: never run, never reported
+      start[k].stop = 1;
+      continue;
+    }
+    if (lh[k] != ADMM_LOSS_LOGISTIC)
+      return fail(ADMM_E_INVALID, "multinomial: slot " + std::to_string(k) + " does not carry the logistic loss");
+    const int32_t k0 = k - c % classes;  // the model's first slot
+    if (ph[2 * k] != ph[2 * k0] || ph[2 * k + 1] != ph[2 * k0 + 1] || nh[k] != nh[k0])
+      return fail(ADMM_E_INVALID, "multinomial: slot " + std::to_string(k) + " differs from slot " + std::to_string(k0) +
+                                      " of its model in lambda, ridge or nonneg");
+  }
+  {  // every row carries exactly one +1 among a model's label columns: ELL read back once
+    const size_t ep = static_cast<size_t>(o->cg.chunks) * KC;
+    std::vector<double> eh(ep * o->m);
+    ADMM_HIP_TRY(hipMemcpy(eh.data(), o->ELL, sizeof(double) * eh.size(), hipMemcpyDeviceToHost));
+    for (int32_t mo = 0; mo < o->cg.chunks * per; ++mo) {
+      const int32_t k0 = (mo / per) * KC + (mo % per) * classes;  // the model's first slot
+      if (k0 + classes > K) continue;
+      const double* E = eh.data() + static_cast<size_t>(k0 / KC) * o->m * KC + k0 % KC;
+      for (int64_t i = 0; i < o->m; ++i) {
+        int pos = 0;
+        for (int32_t c = 0; c < classes; ++c) pos += E[i * KC + c] > 0.0 ? 1 : 0;
+        if (pos != 1)
+          return fail(ADMM_E_INVALID, "multinomial: row " + std::to_string(i) + " carries " + std::to_string(pos) +
+                                          " labels +1 among the slots " + std::to_string(k0) + " .. " +
+                                          std::to_string(k0 + classes - 1) + " (exactly one class is the true one)");
+      }
+    }
+  }
+  o->classes = classes;
+  o->start.swap(start);
+  return ADMM_OK;
+}
+
+int admm_op_softmax_prox(const double* V, const int32_t* y, const double* a, int64_t m, int32_t Cn, double* out,
+                         int32_t* iters_out) {
+  if (!V || !y || !a || !out || !iters_out || m <= 0 || Cn < 2 || Cn > KC)
+    return fail(ADMM_E_INVALID, "softmax_prox: bad argument (m >= 1, Cn in 2 .. 10)");
+  for (int64_t i = 0; i < m; ++i) {
+    if (y[i] < 0 || y[i] >= Cn) return fail(ADMM_E_INVALID, "softmax_prox: y[" + std::to_string(i) + "] is no class");
+    if (!finite_nonneg(a[i])) return fail(ADMM_E_INVALID, "softmax_prox: a[" + std::to_string(i) + "] is negative or not finite");
+  }
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    return fail(ADMM_E_DEVICE, "no HIP device visible: the ADMM engine has no CPU fallback");
+  DevMem mem;
+  double *dV = nullptr, *da = nullptr, *dout = nullptr, *raw = nullptr;
+  const size_t words = (static_cast<size_t>(m) * sizeof(int32_t) + 7) / 8;
+  int rc = mem.alloc(&dV, static_cast<size_t>(m) * Cn);
+  if (rc == ADMM_OK) rc = mem.alloc(&da, static_cast<size_t>(m));
+  if (rc == ADMM_OK) rc = mem.alloc(&dout, static_cast<size_t>(m) * Cn);
+  if (rc == ADMM_OK) rc = mem.alloc(&raw, 2 * words);
+  hipError_t e = hipSuccess;
+  if (rc == ADMM_OK) {
+    int32_t* dy = reinterpret_cast<int32_t*>(raw);
+    int32_t* dit = reinterpret_cast<int32_t*>(raw + words);
+    e = hipMemcpy(dV, V, sizeof(double) * m * Cn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(da, a, sizeof(double) * m, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dy, y, sizeof(int32_t) * m, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      with_classes(Cn, ProxOpLaunch{dV, dy, da, m, dout, dit});
+      e = hipDeviceSynchronize();
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * m * Cn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(iters_out, dit, sizeof(int32_t) * m, hipMemcpyDeviceToHost);
+  }
+  mem.release();
+  if (rc != ADMM_OK) return rc;
+  if (e != hipSuccess) return fail(ADMM_E_DEVICE, std::string("softmax_prox: ") + hipGetErrorString(e));
+  return ADMM_OK;
 }
 
 int admm_sparse_l1class_kernel_time(admm_sparse_l1class* o, int32_t reps, int32_t dual, double* row_us, double* elem_us) {
   if (!o || reps < 1) return fail(ADMM_E_INVALID, "object is NULL or reps < 1");
   ADMM_HIP_TRY(hipSetDevice(o->device));
-  ADMM_TRY(begin_run(*o));  // every fit runs; the iterates are overwritten, as the next run's start does anyway
+  ADMM_TRY(sl1c_begin_run(o));  // every fit runs; the iterates are overwritten, as the next run's start does anyway
   const Sl1cRowArgs ra = sl1c_row_args(o, dual != 0, 1, 1.0);
   const Sl1cElemArgs ea = sl1c_elem_args(o, dual != 0, 1, 1.0);
   double* outs[2] = {row_us, elem_us};

@@ -86,6 +86,14 @@ class SparseL1Classifier(_MultiOwner):
         ip = lambda a: None if a is None else a.ctypes.data_as(C_INT32_P)
         L.check(self._lib.admm_sparse_l1class_set_folds(self._h, nfolds, ip(f), ip(h)))
 
+    def set_multinomial(self, classes=0):
+        """The multinomial (softmax) loss for every later run (admm_sparse_l1class_set_multinomial):
+        ``classes`` = Cn in 2 .. 10 turns the K fits into models of Cn neighbouring slots each, floor(10 / Cn) models
+        per chunk of ten, the slots behind a chunk's last model idle (``softmax.slot_map``); column k of ELL is +1 on
+        the rows whose class is slot k's.  A model is one ADMM problem with one stop decision, reported by each of its
+        fits.  0 restores the per-fit object.  It does not combine with folds or groups."""
+        L.check(self._lib.admm_sparse_l1class_set_multinomial(self._h, int(classes)))
+
     def heldout(self):
         """(loss, errors, weight) of the last run under folds, K values each, over the rows fit k held out, at D*z2 (z2:
         the coefficient block of zopt) with c_i = weights_i * class cost: sum c_i*phi(ell_i*t_i) without the factor C,

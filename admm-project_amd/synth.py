@@ -212,6 +212,18 @@ def sparse_svm_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=
     return dict(D=D, labels=labels, W=W, C=1.0)
 
 
+def sparse_multinomial_problem(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=4, active=0.1, noise=0.1):
+    """A multi-class problem for the multinomial model on sparse_lasso_problem's design matrix: ``classes`` planted
+    sparse coefficient columns W (cols x classes, a fraction ``active`` of each nonzero), and the label of row i is the
+    class with the largest noisy score (D*W)[i] + noise*std*randn.  dict(D, y (integers 0 .. classes - 1), W)."""
+    D = sparse_lasso_problem(seed, rows, cols, density)["D"]
+    rng = np.random.default_rng(seed + 15485863)
+    W = np.where(rng.random((cols, classes)) < active, 3.0 * rng.standard_normal((cols, classes)), 0.0)
+    score = np.asarray(D @ W)
+    y = np.argmax(score + noise * float(np.std(score)) * rng.standard_normal(score.shape), axis=1).astype(np.int64)
+    return dict(D=D, y=y, W=W)
+
+
 def sparse_regression_problem(seed=0, rows=2 ** 10, cols=2 ** 6, density=0.05):
     """quantile_problem's recipe on a sparse design matrix: column 0 is a dense column of ones (the intercept, which
     the quantile property needs), the others are sparse_lasso_problem's (sparse Gaussian, unit norm); the noise's scale

@@ -372,6 +372,41 @@ def sparsel1classifiertest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, errt
     return results, test
 
 
+def multinomialtest(seed=0, rows=2 ** 10, cols=2 ** 8, density=0.05, classes=4, errtol=0.3, quiet=1, options=None):
+    """The multinomial (softmax) model on a sparse design matrix (synth.sparse_multinomial_problem) at
+    lambda = 0.1*lambda_max: the objective at the sparse coefficient block lies below the all-zero model's, the training
+    accuracy is at least 1 - errtol, the probabilities sum to one, and no x-update hit the inner iteration cap.  Returns the test dict
+    (``failed`` 0 | 1; the solver's results under ``results``)."""
+    from . import softmax as M
+    p = synth.sparse_multinomial_problem(seed, rows, cols, density, classes)
+    D, y = p["D"], p["y"]
+    o = _opts(options, objevals=1, quiet=quiet)
+    o.pop("quiet", None)
+    Cv = float(o.get("C", 1.0))
+    lam = 0.1 * M.multinomial_lambda_max(D, y, o)
+    results = M.multinomial(D, y, lam, o)
+    cls, yi = np.unique(y, return_inverse=True)
+
+    def obj(X):
+        T = np.asarray(D @ X)
+        tm = T.max(axis=1)
+        lse = tm + np.log(np.exp(T - tm[:, None]).sum(axis=1))
+        return Cv * float(np.sum(lse - T[np.arange(rows), yi])) + lam * float(np.sum(np.abs(X)))
+
+    z2 = results["zopt"][rows:]
+    objopt, zeroobj = obj(z2), obj(np.zeros_like(z2))
+    proba = M.multinomial_proba(D, z2)
+    accuracy = float(np.mean(cls[np.argmax(proba, axis=1)] == y))
+    ok = (objopt < zeroobj and accuracy >= 1.0 - errtol and results["cg_capped_updates"] == 0
+          and bool(np.all(np.abs(proba.sum(axis=1) - 1.0) <= 1e-12)))
+    test = dict(D=D, y=y, W=p["W"], xopt=results["xopt"], zopt=z2, admmopt=results["objopt"], objopt=objopt,
+                zeroobj=zeroobj, accuracy=accuracy, df=int(np.count_nonzero(np.any(z2 != 0, axis=1))), failed=int(not ok),
+                steps=results["steps"], nnz=results["nnz"], cg_capped_updates=results["cg_capped_updates"], errtol=errtol)
+    test["lambda"] = lam
+    test["results"] = results
+    return test
+
+
 def groupclassifiertest(seed=0, rows=2 ** 10, variables=12, levels=6, used=4, sparse=True, errtol=0.15, quiet=1,
                         options=None):
     """Group-lasso logistic regression on one-hot data: ``variables`` categorical variables of ``levels``

@@ -1585,6 +1585,29 @@ int admm_sparse_l1class_set_folds(admm_sparse_l1class* obj, int32_t nfolds, cons
  * loss[k] = sum c_i*phi_k(ell_ik*t_i) (without the factor C), errors[k] = sum c_i*[ell_ik*t_i <= 0], weight[k] = sum c_i
  * (all 0.0 for a fit that holds nothing out).  ADMM_E_INVALID before a run or when the last run had no folds set. */
 int admm_sparse_l1class_heldout(admm_sparse_l1class* obj, double* loss, double* errors, double* weight);
+/* The multinomial (softmax) loss for every later run (additive to ABI 5).  classes = Cn in 2 .. 10 (the
+ * chunk) turns the K fits into models of Cn classes each: P = floor(10 / Cn) models share a chunk of ten fits, model p of
+ * a chunk owns its slots [p*Cn, (p + 1)*Cn), and the slots >= P*Cn of every chunk are idle -- never run, their summaries
+ * and histories never written (steps 0).  One model is ONE ADMM problem over x (cols x Cn):
+ *   C*sum_i c_i*(logsumexp((D x)_i,:) - (D x)_i,y_i) + sum_c [lambda*sum_j w_j*|x_jc| + mu/2*||x_c||^2]  (x >= 0 where nonneg)
+ * with c_i = weights[i] * class_cost[2 k] of the true class's fit k (admm_sparse_l1class_set_cost; the second cost of a
+ * pair is not read).  The labels stay the +-1 one-vs-rest coding: column k of ELL is +1 on the rows whose class is k's.
+ * The classes meet in the prox of a row -- the root of z - v + a*(softmax(z) - e_y), a = C*c_i/rho, by a damped Newton
+ * iteration with a Sherman-Morrison solve -- and in the stop rule: pnorm, perr, dnorm and derr run over all (m + n)*Cn
+ * stacked elements, both tolerances use sqrt((m + n)*Cn), and a model has one objective and one stop decision, reported
+ * in the summary and the histories of each of its Cn fits.  The x-update, the products and the penalties are the per-fit
+ * object's.  classes = 0 restores the per-fit object, bit for bit.
+ * ADMM_E_INVALID, the slot or the row named: classes outside {0, 2 .. 10}; K mod 10 no multiple of Cn or above P*Cn; a
+ * shared label column (nell = 1); a live fit whose loss is not logistic; lambda, ridge or nonneg that differ within a
+ * model; a row that has not exactly one +1 among a model's label columns.  ADMM_E_UNSUPPORTED: folds or groups are set --
+ * and admm_sparse_l1class_set_folds / _set_groups return it while classes > 0.  A refused call changes nothing.
+ * admm_sparse_l1class_kernel_time then times the multinomial row kernel. */
+int admm_sparse_l1class_set_multinomial(admm_sparse_l1class* obj, int32_t classes);
+/* The row prox of q49 alone, on HOST arrays: V is m x Cn row-major, y[i] in [0, Cn) the true class of row i, a[i] >= 0
+ * finite; out (m x Cn row-major) = argmin_z a[i]*(lse(z) - z_y[i]) + 1/2*||z - V_i||^2 and iters_out[i] = the Newton steps
+ * row i took (at most 100).  a[i] = 0 returns the row bit for bit.  Cn in 2 .. 10. */
+int admm_op_softmax_prox(const double* V, const int32_t* y, const double* a, int64_t m, int32_t Cn, double* out,
+                         int32_t* iters_out);
 /* fits one sparse product serves (K beyond it: ceil(K / chunk) chunks per launch) */
 int admm_sparse_l1class_chunk(void);
 /* measurement: the row kernel and the element kernel alone over the object's own buffers (every fit running, the dual
