@@ -375,7 +375,7 @@ class SparseL1ClassSummary(C.Structure):  # admm_sparse_l1class_summary (admm_sp
 
 FIELD_NUMERIC, FIELD_TEXT, FIELD_HANDLE, FIELD_SPARSE, FIELD_OTHER = 0, 1, 2, 3, 4
 RES_FETCH, RES_SCALAR, RES_START = 0, 1, 2
-STORAGE_FP64, STORAGE_COMPACT, STORAGE_COMPACT40 = 0, 1, 2
+STORAGE_FP64, STORAGE_COMPACT, STORAGE_COMPACT40, STORAGE_COMPACT38, STORAGE_COMPACT36 = 0, 1, 2, 3, 4
 F_WVALS = 23
 F_COVSEL_S = 24
 F_TV2D_ROW_STAGE = 25
@@ -420,6 +420,9 @@ _SIGNATURES = {
     "admm_engine_xsolve_storage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "admm_xsolve_compact_accept": (C.c_int, [C.c_double, C.c_double, C.c_double]),
+    "admm_engine_xsolve_rejected": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp,
+                                              _dp]),
+    "admm_symv_compact_tile_offset": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "admm_tv2d_row_stage": (C.c_int, [C.c_int64, C.c_int64, C.c_double]),
     "admm_tv2d_rows_green_taps": (C.c_int, [C.c_double]),
     "admm_dct_tables": (C.c_int, [C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),

@@ -26,9 +26,16 @@ struct SliceFactor {
   bool probed = false;      // both forms were built and compared on a system with a known solution
   double err_inv = 0.0, err_trsv = 0.0, probe_diff = 0.0;
   double err_trsv_one = __builtin_nan("");  // the one-block form's error on the same system (NaN: not built)
-  // the compact storage of the explicit inverse (planSy.compact; engine.hip: choose_symv_storage): probed against the
+  // the compact storage of the explicit inverse (planSy.cbits; engine.hip: choose_symv_storage): probed against the
   // fp64 packed inverse on the same two systems (NaN: not built)
   double err_cq = __builtin_nan(""), err_cq_ref = __builtin_nan(""), cq_diff = __builtin_nan("");
+  // the widths tried before the form in use and rejected by the rule, in the order tried, each with its three numbers
+  static constexpr int kCqRungs = 4;
+  struct CqRung {
+    int32_t bits;
+    double err, err_ref, diff;
+  } cq_rejected[kCqRungs] = {};
+  int32_t cq_nrejected = 0;
   int32_t chol_info = 0;
   bool pinv = false;        // Minv is the pseudo-inverse of a rank-deficient D'D (linear SVM)
   int64_t rank = 0;

@@ -1,10 +1,12 @@
 // symv_packed.hip -- developer microbenchmark (NOT part of libadmm_hip.so): the lower-triangle SYMV of symv.hip on
 // the column-major padded storage against the same inner loop on TILE-PACKED storage (every 128x128 tile of the
 // lower triangle contiguous, 128 KB, tiles in row-major triangle order).
-//   hipcc -O3 --offload-arch=gfx950 -I.. -o symv_packed symv_packed.hip && ./symv_packed [n] [compact | compact40]
+//   hipcc -O3 --offload-arch=gfx950 -I.. -o symv_packed symv_packed.hip
+//   ./symv_packed [n] [compact | compact40 | compact38 | compact36]
 // `compact`: only the A/B of the production packed kernel on fp64 tiles against its compact instantiation (tri_tile.h:
 // 48-bit tile-scaled fixed point off the diagonal), back to back, over a sweep of the cacheable share of each.
 // `compact40`: the same with the 40-bit instantiation as a third form in the alternation.
+// `compact38` / `compact36`: fp64, the 40-bit form and the instantiation of that width.
 #include "../symv.hip"
 
 #include <cstdio>
@@ -388,8 +390,13 @@ int main(int argc, char** argv) {
     printf("%-44s %8.2f us  %6.3f TB/s\n", name, us, ntri * 131072.0 / us * 1e-6);
   };
   const std::string mode = argc > 2 ? argv[2] : "";
-  if (mode == "compact" || mode == "compact40") {  // fp64 tiles against the compact storage(s), alternating
-    const bool c40 = mode == "compact40";
+  if (mode == "compact" || mode == "compact40" || mode == "compact38" || mode == "compact36") {
+    // fp64 tiles against the compact storage(s), alternating
+    const bool c40 = mode != "compact";
+    const int wide = (mode == "compact" || mode == "compact40") ? 48 : 40;  // first compact form
+    const int narrow = c40 ? atoi(mode.c_str() + 7) : 0;                    // second one
+    char tag[2][8] = {"  ", ""};
+    if (c40) snprintf(tag[0], sizeof tag[0], "%d", wide), snprintf(tag[1], sizeof tag[1], "%d", narrow);
     SymvPlan pf = p, pc[2] = {p, p};
     pf.packed = true;
     double* C[2] = {nullptr, nullptr};
@@ -397,7 +404,7 @@ int main(int argc, char** argv) {
     const int nform = c40 ? 2 : 1;
     for (int k = 0; k < nform; ++k) {
       pc[k].packed = true;
-      pc[k].cbits = k ? 40 : 48;
+      pc[k].cbits = k ? narrow : wide;
       CK(hipMalloc(&C[k], sizeof(double) * symv_compact_elems(pc[k])));
       launch_symv_compact_pack(pc[k], P, 0, true, C[k], nullptr, 0);
       pc[k].scales = symv_compact_scales(pc[k], C[k]);
@@ -414,17 +421,17 @@ int main(int argc, char** argv) {
         time_it(nm, [&] { launch_symv_lower(pf, P, 0, x, np_, tp, y, nullptr, 0, 0, 1, false); }, y);
         for (int k = 0; k < nform; ++k) {
           pc[k].ncached = symv_cached_tiles(pc[k], mb << 20);
-          snprintf(nm, sizeof nm, "compact%s %3lld MB cacheable (%lld tiles)", k ? "40" : "  ", (long long)mb,
+          snprintf(nm, sizeof nm, "compact%s %3lld MB cacheable (%lld tiles)", tag[k], (long long)mb,
                    (long long)pc[k].ncached);
           time_it(nm, [&] { launch_symv_lower(pc[k], C[k], 0, x, np_, tp, y2, nullptr, 0, 0, 1, false); }, y2);
-          printf("   compact%s over stored bytes: %6.3f TB/s\n", k ? "40" : "", cmb[k] / last_us);
+          printf("   compact%s over stored bytes: %6.3f TB/s\n", c40 ? tag[k] : "", cmb[k] / last_us);
         }
       }
     CK(hipMemcpy(h1.data(), y, sizeof(double) * n, hipMemcpyDeviceToHost));
     CK(hipMemcpy(h2.data(), y2, sizeof(double) * n, hipMemcpyDeviceToHost));
     double err = 0, ymax = 0;
     for (int64_t i = 0; i < n; ++i) err = fmax(err, fabs(h1[i] - h2[i])), ymax = fmax(ymax, fabs(h1[i]));
-    printf("max |y_%s - y_fp64| / max |y| = %.3e\n", c40 ? "compact40" : "compact", err / ymax);
+    printf("max |y_%s - y_fp64| / max |y| = %.3e\n", mode.c_str(), err / ymax);
     return 0;
   }
   time_it("column-major padded (production)", [&] {

@@ -372,24 +372,37 @@ bool symv_compact_accept(double err_compact, double err_fp64, double diff) {
 // as form A against that triangle as form B on the two systems of probe_two_forms, and adopted -- the fp64 triangle
 // freed -- while it is as accurate (within 4x / 8x) or below 1e-11.  Where even the 48-bit store is larger than
 // kSymvCacheBytes -- part of it comes from HBM in every iteration -- the 40-bit form (5/8 of the bytes) is tried first,
-// under the same rule.  A cache-resident matrix is latency-bound and gains nothing; the consensus slices (batched
-// launch), the pseudo-inverse (no factor to probe with) and the row-sharded split x-solve keep fp64.
+// under the same rule, and where even the 40-bit store is larger than that, the 36-bit (9/16) and 38-bit (19/32) forms
+// before it: the ladder 36, 38, 40, 48, fp64, the first width accepted kept and the others freed; a rejected rung
+// leaves its probe numbers in f.cq_rejected.  A cache-resident matrix is latency-bound and gains nothing; the
+// consensus slices (batched launch), the pseudo-inverse (no factor to probe with) and the row-sharded split x-solve keep
+// fp64.
 static int try_symv_storage(admm_engine* e, SliceFactor& f, int bits, bool* kept);
 static int choose_symv_storage(admm_engine* e, SliceFactor& f) {
   if (f.mode != ADMM_XSOLVE_INVERSE || !f.Minv || !f.F || f.pinv || !f.planSy.packed || f.planSy.cbits ||
       f.n < kSymvHalfMin || e->sy_split || e->keep_fp64)
     return ADMM_OK;
   if (!stream_hint(symv_tile_prefix_bytes(f.planSy, symv_tiles(f.planSy)))) return ADMM_OK;
-  SymvPlan c48 = f.planSy;
-  c48.cbits = 48;
+  auto streams = [&](int bits) {  // the store of that width is larger than the cacheable share
+    SymvPlan c = f.planSy;
+    c.cbits = bits;
+    return symv_tile_prefix_bytes(c, symv_tiles(c)) > kSymvCacheBytes;
+  };
   bool kept = false;
-  if (symv_tile_prefix_bytes(c48, symv_tiles(c48)) > kSymvCacheBytes) ADMM_TRY(try_symv_storage(e, f, 40, &kept));
+  f.cq_nrejected = 0;
+  if (streams(48) && streams(40)) {
+    ADMM_TRY(try_symv_storage(e, f, 36, &kept));
+    if (!kept) ADMM_TRY(try_symv_storage(e, f, 38, &kept));
+  }
+  if (!kept && streams(48)) ADMM_TRY(try_symv_storage(e, f, 40, &kept));
   if (!kept) ADMM_TRY(try_symv_storage(e, f, 48, &kept));
   return ADMM_OK;
 }
 
 // build the compact form of that width, probe it, adopt it or free it; the probe numbers of the last form tried stay
 static int try_symv_storage(admm_engine* e, SliceFactor& f, int bits, bool* kept) {
+  if (!symv_cbits_ok(bits))
+    return fail(ADMM_E_INVALID, "compact x-solve storage: no tile width of " + std::to_string(bits) + " bits");
   SymvPlan cp = f.planSy;
   cp.cbits = bits;
   double* C = nullptr;
@@ -415,6 +428,7 @@ static int try_symv_storage(admm_engine* e, SliceFactor& f, int bits, bool* kept
     f.planSy = cp;
   } else {
     e->mem.free_one(C);
+    if (f.cq_nrejected < SliceFactor::kCqRungs) f.cq_rejected[f.cq_nrejected++] = {bits, ea, eb, diff};
   }
   return ADMM_OK;
 }
@@ -1040,7 +1054,14 @@ int admm_engine_xsolve_storage(admm_engine* e, int32_t* form, int64_t* stored_by
   const SliceFactor& f = e->xfac;
   const bool inv = f.mode == ADMM_XSOLVE_INVERSE && f.Minv;
   if (form)
-    *form = !(inv && f.planSy.cbits) ? ADMM_STORAGE_FP64 : f.planSy.cbits == 40 ? ADMM_STORAGE_COMPACT40 : ADMM_STORAGE_COMPACT;
+    switch (inv ? f.planSy.cbits : 0) {
+      case 0: *form = ADMM_STORAGE_FP64; break;
+      case 48: *form = ADMM_STORAGE_COMPACT; break;
+      case 40: *form = ADMM_STORAGE_COMPACT40; break;
+      case 38: *form = ADMM_STORAGE_COMPACT38; break;
+      case 36: *form = ADMM_STORAGE_COMPACT36; break;
+      default: return fail(ADMM_E_UNSUPPORTED, "x-solve storage of an unknown width");
+    }
   if (stored_bytes) {
     *stored_bytes = 0;
     if (inv && f.planSy.packed) *stored_bytes = symv_tile_prefix_bytes(f.planSy, symv_tiles(f.planSy));
@@ -1049,6 +1070,32 @@ int admm_engine_xsolve_storage(admm_engine* e, int32_t* form, int64_t* stored_by
   if (probe_err_compact) *probe_err_compact = f.err_cq;
   if (probe_err_fp64) *probe_err_fp64 = f.err_cq_ref;
   if (probe_diff) *probe_diff = f.cq_diff;
+  return ADMM_OK;
+}
+
+int admm_engine_xsolve_rejected(admm_engine* e, int32_t cap, int32_t* count, int32_t* bits, double* err_compact,
+                                double* err_fp64, double* diff) {
+  if (!e || !count || cap < 0)
+    return fail(ADMM_E_INVALID, "xsolve_rejected: NULL engine or count, or a negative capacity");
+  const SliceFactor& f = e->xfac;
+  *count = f.cq_nrejected;
+  for (int32_t k = 0; k < f.cq_nrejected && k < cap; ++k) {
+    if (bits) bits[k] = f.cq_rejected[k].bits;
+    if (err_compact) err_compact[k] = f.cq_rejected[k].err;
+    if (err_fp64) err_fp64[k] = f.cq_rejected[k].err_ref;
+    if (diff) diff[k] = f.cq_rejected[k].diff;
+  }
+  return ADMM_OK;
+}
+
+int admm_symv_compact_tile_offset(int64_t n, int32_t bits, int64_t t, int64_t* offset) {
+  if (n <= 0 || !offset || !symv_cbits_ok(bits))
+    return fail(ADMM_E_INVALID, "symv_compact_tile_offset: bad argument (bits 36, 38, 40 or 48)");
+  SymvPlan p = symv_plan(n);
+  p.packed = true;
+  p.cbits = bits;
+  if (t < 0 || t > symv_tiles(p)) return fail(ADMM_E_INVALID, "symv_compact_tile_offset: t outside 0 .. tiles");
+  *offset = symv_tile_prefix_bytes(p, t);
   return ADMM_OK;
 }
 

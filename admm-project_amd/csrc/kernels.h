@@ -46,8 +46,8 @@ struct SymvPlan {
   int32_t ntile;   // 128-row wave chunks = 128-column groups: npart and tpart are [ntile][ldp]
   bool packed;     // M is tile-packed (launch_symv_pack): lower-triangle 128x128 tiles back to back, ld unused
   int64_t ncached; // tiles (linear index < ncached) read with default loads; the rest stream non-temporally
-  int32_t cbits;   // 40 / 48: packed, off-diagonal tiles as tile-scaled fixed point of that width (tri_tile.h), M is
-                   // that storage; 0: fp64 tiles
+  int32_t cbits;   // 36 / 38 / 40 / 48: packed, off-diagonal tiles as tile-scaled fixed point of that width
+                   // (tri_tile.h), M is that storage; 0: fp64 tiles
   const double* scales;  // compact: one power of two per tile
   size_t npart_elems() const { return static_cast<size_t>(ntile) * ldp; }
   size_t tpart_elems() const { return static_cast<size_t>(ntile) * ldp; }
@@ -73,6 +73,7 @@ void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P,
 // one power-of-two scale per tile, the scales behind the tiles in the same buffer of symv_compact_elems doubles.
 // bytes of the leading t tiles in the plan's storage form (p.cbits); the plan's ncached counts tiles of that form
 int64_t symv_tile_prefix_bytes(const SymvPlan& p, int64_t t);
+bool symv_cbits_ok(int32_t bits);  // the widths of the format: a plan's cbits is 0 or one of these
 size_t symv_compact_elems(const SymvPlan& p);
 double* symv_compact_scales(const SymvPlan& p, double* C);
 // C <- M, either the padded column-major square (ld) or the fp64 tile-packed triangle (src_packed); deq (optional,

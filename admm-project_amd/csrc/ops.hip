@@ -544,7 +544,8 @@ int admm_op_symv_compact_bits(const double* M, int64_t n, int64_t ldM, const dou
                               int32_t part_count, double* y, double* Q, int64_t ldQ, int32_t bits) {
   if (!M || !x || !y || n <= 0 || ldM < n || ncached < -1 || part_count < 1 || (Q && ldQ < n))
     return fail(ADMM_E_INVALID, "symv_compact: bad argument (ncached >= -1, part_count >= 1, ldQ >= n)");
-  if (bits != 40 && bits != 48) return fail(ADMM_E_INVALID, "symv_compact: the compact tile widths are 40 and 48 bits");
+  if (!symv_cbits_ok(bits))
+    return fail(ADMM_E_INVALID, "symv_compact: the compact tile widths are 36, 38, 40 and 48 bits");
   ADMM_TRY(need_device());
   Scratch sc;
   double *dM, *dx, *dy, *dC, *dQ = nullptr, *npart, *tpart;

@@ -30,11 +30,14 @@
 // 3/4 of the bytes (n = 10000: 313 MB for 414), decoded by two conversions and one FMA per element that hide behind
 // the loads: 64.1 -> 50.8 us per launch, the same 6.2 TB/s over the stored bytes (EXPERIMENTS.md).  Where even that store
 // is larger than kSymvCacheBytes the engine tries the 40-bit width of the same format first (5/8 of the bytes, n = 10000:
-// 263 MB; engine.hip: choose_symv_storage): one code path, the width a template parameter.
+// 263 MB; engine.hip: choose_symv_storage), and where even the 40-bit store is larger, 36 and 38 bits before it (9/16
+// and 19/32 of the bytes; n = 10000: 38 bits, 250 MB -- 36 bits fails the acceptance rule there): one code path, the
+// width a template parameter.
 // The tile pass itself (SyLane, sy_tile) is in tri_tile.h: the backward pass of the one-block triangular solve
 // (trsv.hip: tri1_backward_kernel) is its T-part alone.
 
 #include <algorithm>
+#include <type_traits>
 
 #include "finalize_device.h"
 #include "kernels.h"
@@ -46,8 +49,8 @@ namespace admm {
 // PACKED = false: M is npad x npad (npad = round_up(n, 128)) column-major with ld >= npad, zero outside n x n; grid
 // (ntile, ntile).  PACKED = true: M holds the lower-triangle tiles back to back (launch_symv_pack); grid = their count.
 // x: n elements.  Tiles with linear index < ncached use default loads, the others non-temporal ones.
-// CBITS = 40 / 48 (PACKED only): M is the compact storage of tri_tile.h -- fp64 diagonal tiles, fixed-point off-diagonal
-// tiles of that width -- and scales its per-tile powers of two.  CBITS = 0: fp64 tiles.
+// CBITS = 36 / 38 / 40 / 48 (PACKED only): M is the compact storage of tri_tile.h -- fp64 diagonal tiles, fixed-point
+// off-diagonal tiles of that width -- and scales its per-tile powers of two.  CBITS = 0: fp64 tiles.
 template <bool PACKED, int CBITS = 0, int NBUF = 2>
 __device__ __forceinline__ void symv_lower_body(unsigned block_x, unsigned block_y, const double* __restrict__ M,
                                                 int64_t n, int64_t ld, const double* __restrict__ x,
@@ -136,8 +139,8 @@ __global__ __launch_bounds__(kWave) void symv_lower_fin_kernel(const double* __r
   // Every argument of the tile path but x requested at once (fetched where first used they cost four dependent scalar
   // round trips behind the stop test, in a one-tile workgroup that lives ~15 us).  NOT x: with its pointer live this
   // early hipcc allocates 100 VGPRs instead of 84 -- five waves per SIMD instead of six, and 3 % slower, measured.
-  // The compact instantiations allocate 82, both widths (12 / 10 dwords per panel buffer instead of 16, the decoded
-  // panel in 16 more): the same occupancy as the fp64 one, scales included in the early request.
+  // The compact instantiations allocate 82, all four widths (12 / 10 / 10 / 9 dwords per panel buffer instead of 16, the
+  // decoded panel in 16 more): the same occupancy as the fp64 one, scales included in the early request.
   asm volatile("" ::"s"(M), "s"(n), "s"(npart), "s"(tpart), "s"(ldp), "s"(part_rank), "s"(part_count), "s"(ncached),
                "s"(fin_pending), "s"(ctrl));
   if (CBITS) asm volatile("" ::"s"(scales));
@@ -298,12 +301,37 @@ __global__ __launch_bounds__(kBlock) void symv_compact_pack_kernel(const double*
       for (int k = 0; k < kSyPanel; ++k) {
         const double2_t v = *reinterpret_cast<const double2_t*>(src + (kSyPanel * p + k) * sld + r);
         const int64_t q0 = cq_quantise<BITS>(v.x, shift), q1 = cq_quantise<BITS>(v.y, shift);
-        const int bit = 2 * k * F::kHiBits;  // fields 2k and 2k + 1 of the lane share a dword
-        out[bit / 32] |= ((static_cast<unsigned>(q0 >> 32) & mask) << (bit % 32)) |
-                         ((static_cast<unsigned>(q1 >> 32) & mask) << (bit % 32 + F::kHiBits));
+        const int bit = 2 * k * F::kHiBits;  // fields 2k and 2k + 1 of the lane
+        const unsigned f0 = static_cast<unsigned>(q0 >> 32) & mask, f1 = static_cast<unsigned>(q1 >> 32) & mask;
+        if (bit % 32 + 2 * F::kHiBits <= 32) {  // share a dword
+          out[bit / 32] |= (f0 << (bit % 32)) | (f1 << (bit % 32 + F::kHiBits));
+        } else {  // (38 bit, k = 2: bits 24 .. 29 and 30 .. 35) the second one straddles two
+          out[bit / 32] |= (f0 << (bit % 32)) | (f1 << (bit % 32 + F::kHiBits));
+          out[bit / 32 + 1] |= f1 >> (32 - bit % 32 - F::kHiBits);
+        }
       }
-      *reinterpret_cast<uintn_t<F::kHiDwords>*>(rec + l * (4 * F::kHiDwords)) = out;
+      if constexpr (BITS == 38) {  // the dword run, then the 16-bit run
+        *reinterpret_cast<unsigned*>(rec + l * 4) = out[0];
+        *reinterpret_cast<unsigned short*>(rec + 256 + l * 2) = static_cast<unsigned short>(out[1]);
+      } else {
+        *reinterpret_cast<uintn_t<F::kHiDwords>*>(rec + l * (4 * F::kHiDwords)) = out;
+      }
     }
+  }
+}
+
+bool symv_cbits_ok(int32_t bits) { return bits == 36 || bits == 38 || bits == 40 || bits == 48; }
+
+// fn(std::integral_constant<int, BITS>) for the plan's compact width: the one place the widths are listed.  Any other
+// value is a programming error of the caller (the engine and the operators check symv_cbits_ok): nothing is launched.
+template <class Fn>
+static bool with_cbits(int32_t bits, Fn&& fn) {
+  switch (bits) {
+    case 36: fn(std::integral_constant<int, 36>{}); return true;
+    case 38: fn(std::integral_constant<int, 38>{}); return true;
+    case 40: fn(std::integral_constant<int, 40>{}); return true;
+    case 48: fn(std::integral_constant<int, 48>{}); return true;
+    default: return false;
   }
 }
 
@@ -327,7 +355,9 @@ int64_t symv_tile_prefix_bytes(const SymvPlan& p, int64_t t) {
   if (!p.cbits) return t * int64_t{8} * kTile * kTile;
   unsigned bi, bj;
   tri_decode(static_cast<unsigned>(t), bi, bj);  // (also right for t = tiles: the row after the last)
-  return p.cbits == 40 ? cq_tile_offset<40>(static_cast<unsigned>(t), bi) : cq_tile_offset<48>(static_cast<unsigned>(t), bi);
+  int64_t bytes = -1;  // (a width with_cbits refuses)
+  with_cbits(p.cbits, [&](auto w) { bytes = cq_tile_offset<decltype(w)::value>(static_cast<unsigned>(t), bi); });
+  return bytes;
 }
 size_t symv_compact_elems(const SymvPlan& p) {  // (p.cbits set)
   return static_cast<size_t>(symv_tile_prefix_bytes(p, symv_tiles(p)) / 8 + symv_tiles(p));
@@ -354,12 +384,10 @@ void launch_symv_pack(const SymvPlan& p, const double* M, int64_t ld, double* P,
 void launch_symv_compact_pack(const SymvPlan& p, const double* M, int64_t ld, bool src_packed, double* C, double* deq,
                               hipStream_t stream) {
   const dim3 grid(static_cast<unsigned>(symv_tiles(p)));
-  if (p.cbits == 40)
-    hipLaunchKernelGGL(symv_compact_pack_kernel<40>, grid, dim3(kBlock), 0, stream, M, ld, src_packed ? 1 : 0,
-                       reinterpret_cast<char*>(C), symv_compact_scales(p, C), deq);
-  else
-    hipLaunchKernelGGL(symv_compact_pack_kernel<48>, grid, dim3(kBlock), 0, stream, M, ld, src_packed ? 1 : 0,
-                       reinterpret_cast<char*>(C), symv_compact_scales(p, C), deq);
+  with_cbits(p.cbits, [&](auto w) {
+    hipLaunchKernelGGL(symv_compact_pack_kernel<decltype(w)::value>, grid, dim3(kBlock), 0, stream, M, ld,
+                       src_packed ? 1 : 0, reinterpret_cast<char*>(C), symv_compact_scales(p, C), deq);
+  });
 }
 
 void launch_symv_reduce(const SymvPlan& p, const double* npart, const double* tpart, double* y, const Ctrl* ctrl,
@@ -372,12 +400,12 @@ void launch_symv_lower(const SymvPlan& p, const double* M, int64_t ld, const dou
                        double* y, const Ctrl* ctrl, hipStream_t stream, int part_rank, int part_count, bool reduce) {
   const uint32_t ncached = static_cast<uint32_t>(p.ncached < 0 ? 0 : p.ncached);
   const double* none = nullptr;
-  if (p.packed && p.cbits == 40)
-    hipLaunchKernelGGL((symv_lower_kernel<true, 40>), dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0,
-                       stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl, p.scales);
-  else if (p.packed && p.cbits)
-    hipLaunchKernelGGL((symv_lower_kernel<true, 48>), dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0,
-                       stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl, p.scales);
+  if (p.packed && p.cbits)
+    with_cbits(p.cbits, [&](auto w) {
+      hipLaunchKernelGGL((symv_lower_kernel<true, decltype(w)::value>), dim3(static_cast<unsigned>(symv_tiles(p))),
+                         dim3(kWave), 0, stream, M, p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached,
+                         ctrl, p.scales);
+    });
   else if (p.packed)
     hipLaunchKernelGGL(symv_lower_kernel<true>, dim3(static_cast<unsigned>(symv_tiles(p))), dim3(kWave), 0, stream, M,
                        p.n, ld, x, npart, tpart, p.ldp, part_rank, part_count, ncached, ctrl, none);
@@ -404,12 +432,11 @@ void launch_symv_lower_fin(const SymvPlan& p, const double* M, const double* x, 
   const uint32_t ncached = static_cast<uint32_t>(p.ncached < 0 ? 0 : p.ncached);
   const dim3 grid(static_cast<unsigned>(symv_tiles(p)) + 1u);
   const double* none = nullptr;
-  if (p.cbits == 40)
-    hipLaunchKernelGGL(symv_lower_fin_kernel<40>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
-                       part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, p.scales);
-  else if (p.cbits)
-    hipLaunchKernelGGL(symv_lower_fin_kernel<48>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
-                       part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, p.scales);
+  if (p.cbits)
+    with_cbits(p.cbits, [&](auto w) {
+      hipLaunchKernelGGL(symv_lower_fin_kernel<decltype(w)::value>, grid, dim3(kWave), 0, stream, M, p.n, x, npart,
+                         tpart, p.ldp, part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, p.scales);
+    });
   else
     hipLaunchKernelGGL(symv_lower_fin_kernel<0>, grid, dim3(kWave), 0, stream, M, p.n, x, npart, tpart, p.ldp,
                        part_rank, part_count, ncached, f, fin_pending ? 1 : 0, ctrl, none);

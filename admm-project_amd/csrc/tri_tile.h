@@ -22,30 +22,37 @@ __host__ __device__ __forceinline__ void tri_decode(unsigned t, unsigned& bi, un
 // ---------------------------------------------------------------- compact storage of a symmetric tile-packed triangle
 // (symv.hip: the cached explicit inverse of the streamed x-solve).  Same tiles in the same order; a DIAGONAL tile keeps
 // its fp64 layout (128 KB: its diagonal entries are hundreds of times larger than the rest of the tile), an OFF-DIAGONAL
-// tile t is BITS-bit signed fixed point with one power-of-two scale per tile, BITS = 48 (96 KB) or 40 (80 KB):
+// tile t is BITS-bit signed fixed point with one power-of-two scale per tile, BITS = 48 (96 KB), 40 (80 KB), 38 (76 KB)
+// or 36 (72 KB):
 //   e = binary exponent of the tile's largest magnitude (max < 2^e),  scale_t = 2^(e - (BITS - 1))   (all-zero tile: 0)
 //   q = rint(M / scale_t) clamped to +-(2^(BITS-1) - 1),  q = hi * 2^32 + lo,  hi signed BITS - 32 bits, lo unsigned 32
 // A tile is 32 panel records, record p = columns 4p .. 4p + 3 as three runs, one piece per lane in each:
 //   run 0 (1 KB, 16 bytes per lane): lo of (r, 4p), (r + 1, 4p), (r, 4p + 1), (r + 1, 4p + 1)   r = 2 * lane, the row pair
 //   run 1 (1 KB): the same of columns 4p + 2, 4p + 3
 //   run 2: the lane's eight hi fields in the order (r, 4p), (r + 1, 4p), (r, 4p + 1), ... (r + 1, 4p + 3), lowest bits
-//          first -- 48 bit: 16 bytes per lane, dword k = column 4p + k;  40 bit: 8 bytes per lane, one byte per field
-// so every lane load is aligned to its size and a wave reads one contiguous record (3 KB / 2.5 KB) per panel.  Tile
-// offsets count in units of 32 KB / 16 KB -- a diagonal tile is 4 / 8 of them, a compact one 3 / 5 -- and the rows before
-// tile (bi, bj) hold bi diagonal tiles, so tile t starts at (3 t + bi) * 32 KB / (5 t + 3 bi) * 16 KB.  The scales are one
+//          first, BITS - 32 bytes per lane -- 48 bit: 16 bytes, dword k = column 4p + k;  40 bit: 8 bytes, one byte per
+//          field;  36 bit: one dword, a nibble per field;  38 bit: 48 bits, stored as a dword run (bits 0 .. 31, 256 B)
+//          followed by a 16-bit run (bits 32 .. 47, 128 B) -- field 5 has its low two bits in the dword and its high
+//          four in the halfword
+// so every lane load is aligned to its size and a wave reads one contiguous record (3 KB / 2.5 KB / 2.375 KB / 2.25 KB)
+// per panel.  Tile offsets count in units of 32 / 16 / 4 / 8 KB -- a diagonal tile is 4 / 8 / 32 / 16 of them, a compact
+// one 3 / 5 / 19 / 9 -- and the rows before tile (bi, bj) hold bi diagonal tiles, so tile t starts at
+// (3 t + bi) * 32 KB / (5 t + 3 bi) * 16 KB / (19 t + 13 bi) * 4 KB / (9 t + 7 bi) * 8 KB.  The scales are one
 // double per tile (diagonal tiles: 1, unused) in an array of their own.  The kernel decodes fma(cvt(hi), 2^32, cvt(lo))
 // -- exact, BITS bits fit the mantissa -- and applies the scale once per tile (sy_tile_cq): the product over the
 // quantised matrix rounds exactly where the fp64 kernel's does.
 template <int BITS>
 struct CqFormat {
-  static_assert(BITS == 40 || BITS == 48, "compact tile widths");
+  static_assert(BITS == 36 || BITS == 38 || BITS == 40 || BITS == 48, "compact tile widths");
   static constexpr int kHiBits = BITS - 32;                      // one hi field
-  static constexpr int kHiDwords = 8 * kHiBits / 32;             // run 2, per lane
-  static constexpr int kPanelBytes = 2048 + 64 * 4 * kHiDwords;  // one panel record
-  static constexpr int64_t kUnit = (BITS == 48) ? 32768 : 16384;  // tile offsets count in these
-  static constexpr int kTileUnits = (kTile / 4) * kPanelBytes / kUnit;  // 3 / 5: a tile is its 32 panel records
-  static constexpr int kDiagUnits = 8 * kTile * kTile / kUnit;          // 4 / 8
-  static_assert(kTileUnits * kUnit == (kTile / 4) * kPanelBytes && kTileUnits == (BITS == 48 ? 3 : 5), "whole units");
+  static constexpr int kHiDwords = (8 * kHiBits + 31) / 32;      // run 2 per lane, as the kernel holds it
+  static constexpr int kPanelBytes = 2048 + 64 * kHiBits;        // one panel record (run 2: kHiBits bytes per lane)
+  // tile offsets count in these
+  static constexpr int64_t kUnit = BITS == 48 ? 32768 : BITS == 40 ? 16384 : BITS == 38 ? 4096 : 8192;
+  static constexpr int kTileUnits = (kTile / 4) * kPanelBytes / kUnit;  // 3 / 5 / 19 / 9: a tile is its 32 panel records
+  static constexpr int kDiagUnits = 8 * kTile * kTile / kUnit;          // 4 / 8 / 32 / 16
+  static_assert(kTileUnits * kUnit == (kTile / 4) * kPanelBytes && kTileUnits * kUnit * 8 == int64_t{BITS} * kTile * kTile,
+                "whole units");
 };
 template <int BITS>
 __host__ __device__ __forceinline__ int64_t cq_tile_offset(unsigned t, unsigned bi) {
@@ -94,7 +101,7 @@ __device__ __forceinline__ void sy_load(const SyLane& s, int64_t cp, double2_t (
   for (int k = 0; k < kSyPanel; ++k) d[k] = load2<NT>(s.M + (cp + k) * s.ld + s.r);  // wave-uniform column base
 }
 
-// one panel buffer of the ring in sy_tile: the fp64 form holds the panel itself, the compact form its 48 / 40 bytes per lane
+// one panel buffer of the ring in sy_tile: the fp64 form holds the panel itself, the compact form its BITS bytes per lane
 template <bool NT>
 struct SyBuf64 {
   double2_t d[kSyPanel];
@@ -126,11 +133,21 @@ struct SyBufCq {
     const char* p = reinterpret_cast<const char*>(s.M) + (cp >> 2) * F::kPanelBytes;
     lo[0] = loadn<NT, 4>(p + s.r * 8);
     lo[1] = loadn<NT, 4>(p + 1024 + s.r * 8);
-    hi = loadn<NT, F::kHiDwords>(p + 2048 + s.r * (2 * F::kHiDwords));
+    if constexpr (BITS == 38) {  // 48 bits per lane: the dword run, then the 16-bit run
+      hi[0] = loadn<NT, 1>(p + 2048 + s.r * 2)[0];
+      const unsigned short* q = reinterpret_cast<const unsigned short*>(p + 2304 + s.r);
+      hi[1] = NT ? __builtin_nontemporal_load(q) : *q;
+    } else {
+      hi = loadn<NT, F::kHiDwords>(p + 2048 + s.r * (2 * F::kHiDwords));
+    }
   }
   // hi field i of the lane (i = 2 k: row r of column k, 2 k + 1: row r + 1), sign-extended
   __device__ __forceinline__ int hi_field(int i) const {
     const int bit = i * F::kHiBits;
+    if (bit % 32 + F::kHiBits > 32) {  // (38 bit, field 5) the field straddles two dwords
+      const unsigned v = (hi[bit / 32] >> (bit % 32)) | (hi[bit / 32 + 1] << (32 - bit % 32));
+      return static_cast<int>(v << (32 - F::kHiBits)) >> (32 - F::kHiBits);
+    }
     return static_cast<int>(hi[bit / 32] << (32 - F::kHiBits - bit % 32)) >> (32 - F::kHiBits);
   }
   __device__ __forceinline__ void get(double2_t (&o)[kSyPanel]) const {

@@ -513,15 +513,22 @@ class Engine:
 
     def xsolve_storage(self):
         """How the explicit inverse of the x-update is stored (admm_engine_xsolve_storage): dict(form = "fp64" |
-        "compact" (48-bit tiles) | "compact40", stored_bytes, and the three numbers of the probe that decided it -- NaN
-        where no compact form was built)"""
+        "compact" (48-bit tiles) | "compact40" | "compact38" | "compact36", stored_bytes, and the three numbers of the
+        probe that decided it -- NaN where no compact form was built; rejected: the widths tried before it that the rule
+        turned down, in the order tried, each a dict(bits, probe_err_compact, probe_err_fp64, probe_diff))"""
         form, nbytes = C.c_int32(), C.c_int64()
         ea, eb, diff = C.c_double(), C.c_double(), C.c_double()
         L.check(self._lib.admm_engine_xsolve_storage(self._h, C.byref(form), C.byref(nbytes), C.byref(ea), C.byref(eb),
                                                      C.byref(diff)))
-        names = {L.STORAGE_FP64: "fp64", L.STORAGE_COMPACT: "compact", L.STORAGE_COMPACT40: "compact40"}
+        names = {L.STORAGE_FP64: "fp64", L.STORAGE_COMPACT: "compact", L.STORAGE_COMPACT40: "compact40",
+                 L.STORAGE_COMPACT38: "compact38", L.STORAGE_COMPACT36: "compact36"}
+        cap, cnt = 4, C.c_int32()
+        rb, ra, rf, rd = (C.c_int32 * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_double * cap)()
+        L.check(self._lib.admm_engine_xsolve_rejected(self._h, cap, C.byref(cnt), rb, ra, rf, rd))
+        rejected = [dict(bits=rb[k], probe_err_compact=ra[k], probe_err_fp64=rf[k], probe_diff=rd[k])
+                    for k in range(min(cap, cnt.value))]
         return dict(form=names[form.value], stored_bytes=nbytes.value,
-                    probe_err_compact=ea.value, probe_err_fp64=eb.value, probe_diff=diff.value)
+                    probe_err_compact=ea.value, probe_err_fp64=eb.value, probe_diff=diff.value, rejected=rejected)
 
     def info(self):
         """What create() decided about the x-update factor (admm_engine_info): the form in use, the probe errors

@@ -493,10 +493,23 @@ int admm_engine_info(admm_engine* eng, admm_engine_info_t* info);
  * their relative difference on an unstructured right-hand side -- are NaN where the compact form was not built.  Any
  * output pointer may be NULL.  ADMM_STORAGE_COMPACT40: the same format with 40-bit tiles, 5/8 of the bytes, tried first
  * (same rule, then the 48-bit form) where the 48-bit store is larger than the cacheable share of the x-solve; the probe
- * numbers are those of the form in use. */
-enum { ADMM_STORAGE_FP64 = 0, ADMM_STORAGE_COMPACT = 1, ADMM_STORAGE_COMPACT40 = 2 };
+ * numbers are those of the form in use.  ADMM_STORAGE_COMPACT38 / _COMPACT36: 38- and 36-bit tiles, 19/32 and 9/16 of
+ * the bytes, tried (36 first) before the 40-bit form where even the 40-bit store is larger than that share.  The ladder
+ * is 36, 38, 40, 48, fp64: the first width the rule accepts is kept, the others are freed. */
+enum {
+  ADMM_STORAGE_FP64 = 0,
+  ADMM_STORAGE_COMPACT = 1,
+  ADMM_STORAGE_COMPACT40 = 2,
+  ADMM_STORAGE_COMPACT38 = 3,
+  ADMM_STORAGE_COMPACT36 = 4
+};
 int admm_engine_xsolve_storage(admm_engine* eng, int32_t* form, int64_t* stored_bytes, double* probe_err_compact,
                                double* probe_err_fp64, double* probe_diff);
+/* The rungs of that ladder create() tried and rejected, in the order tried: *count of them (at most 4); the first
+ * min(*count, cap) entries of bits (the tile width), err_compact, err_fp64 and diff (the rung's three probe numbers, as
+ * above) are filled.  Any array may be NULL.  The rule gives 0 on every entry. */
+int admm_engine_xsolve_rejected(admm_engine* eng, int32_t cap, int32_t* count, int32_t* bits, double* err_compact,
+                                double* err_fp64, double* diff);
 /* the acceptance rule itself (host arithmetic, no device): 1 while
  * err_compact <= max(1e-11, 4 err_fp64) and diff <= max(1e-11, 8 err_fp64); a NaN anywhere gives 0 */
 int admm_xsolve_compact_accept(double err_compact, double err_fp64, double diff);
@@ -711,9 +724,13 @@ int admm_op_symv(const double* M, int64_t n, int64_t ldM, const double* x, int32
  * triangle mirrored. */
 int admm_op_symv_compact(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
                          int32_t part_count, double* y, double* Q, int64_t ldQ);
-/* the same with the tile width chosen: bits = 48 (admm_op_symv_compact itself) or 40; any other width is ADMM_E_INVALID */
+/* the same with the tile width chosen: bits = 48 (admm_op_symv_compact itself), 40, 38 or 36; any other width is
+ * ADMM_E_INVALID */
 int admm_op_symv_compact_bits(const double* M, int64_t n, int64_t ldM, const double* x, int32_t fin, int64_t ncached,
                               int32_t part_count, double* y, double* Q, int64_t ldQ, int32_t bits);
+/* Where the compact storage of an order-n matrix puts lower-triangle tile t (row-major triangle order) at that width,
+ * in bytes from its start; t = the tile count gives the stored bytes.  Host arithmetic, no device. */
+int admm_symv_compact_tile_offset(int64_t n, int32_t bits, int64_t t, int64_t* offset);
 /* Y(:,k) = M_k * X(:,k), k < K: K symmetric n x n matrices stored back to back (matrix k at Ms + k*ldM*n), tile-packed
  * and multiplied in ONE batched launch (the slice inverses of consensus lasso); lower triangles only, ncached as above */
 int admm_op_symv_batch(const double* Ms, int64_t n, int64_t ldM, int32_t K, const double* X, int64_t ldX,
