@@ -14,7 +14,7 @@ import time
 import numpy as np
 
 from .errorcheck import is_positive_real, penalty_fields, svm_cost_fields
-from .solvers import _CG_KEYS, _LOOP_KEYS, _matrix, _options, _pick
+from .solvers import _CG_KEYS, _LOOP_KEYS, _fit_penalties, _lambda_grid, _lambda_vector, _matrix, _options, _pick
 
 _HIST = ("pnorm", "perr", "dnorm", "derr", "objevals")
 _REFUSED = ("foldid", "heldout", "obsweights", "groups", "groupweights", "comm")
@@ -134,19 +134,10 @@ def _run_models(D, y, lams, options, who, t0):
     m, n = D.shape
     classes, yi = _labels(y, m)
     Cn = classes.size
-    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
+    lam = _lambda_vector(lams, "model")
     M = int(lam.size)
-    if M < 1:
-        raise ValueError("lams must hold at least one lambda")
-    for j, v in enumerate(lam):
-        if not np.isfinite(v) or v < 0:
-            raise ValueError(f"model {j}: lambda is not a nonnegative real number")
-    mu = penalty_fields(dict(ridge=options.get("ridge", 0.0)), n)["ridge"]
-    nn = penalty_fields(dict(nonnegative=options.get("nonnegative", 0)), n)["nonnegative"]
-    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
+    mu, nn, l1weights, _ = _fit_penalties(options, n)
     Cv = is_positive_real(options.get("C", 1.0), "options.C")
-    if "rho" in options:
-        is_positive_real(options["rho"], "options.rho")
     weights, cw = _costs(options, yi, Cn)
     first, K = slot_map(M, Cn, SparseL1Classifier.chunk())
     # the slots: the classes of model j from first[j] on; an idle slot is a valid fit that never runs (labels -1, lambda 0)
@@ -169,8 +160,8 @@ def _run_models(D, y, lams, options, who, t0):
             cost[k, 0] = cw[c]
             for v, full in starts.values():
                 full[:, k] = v[:, c]
-    obj = SparseL1Classifier(D, ELL, lk, None, rk, nk, None if pw is None else pw["l1weights"], C=Cv,
-                             xsolve=options.get("xsolve", "auto"), device=int(options.get("device", 0)))
+    obj = SparseL1Classifier(D, ELL, lk, None, rk, nk, l1weights, C=Cv, xsolve=options.get("xsolve", "auto"),
+                             device=int(options.get("device", 0)))
     try:
         obj.set_cost(weights, cost)
         obj.set_multinomial(Cn)
@@ -224,16 +215,7 @@ def multinomial_path(D, y, lams=None, options=None):
     solverruntime and ``df`` (M values): the coefficients with any nonzero class in the coefficient block of zopt."""
     options = _options(options, "Argument options is not a struct!", optional=True)
     t0 = time.perf_counter()
-    nlambda = options.pop("nlambda", None)
-    ratio = options.pop("lambda_min_ratio", 1e-2)
-    if lams is None or np.isscalar(lams):
-        nlambda = lams if lams is not None else (6 if nlambda is None else nlambda)
-        if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
-            raise ValueError("options.nlambda must be an integer >= 1")
-        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
-            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-        lmax = multinomial_lambda_max(D, y, options)
-        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+    lams = _lambda_grid(options, lams, 6, lambda: multinomial_lambda_max(D, y, options), count_ok=True)
     per = _run_models(D, y, lams, options, "multinomial_path", t0)
     m = per[0]["zopt"].shape[0] - per[0]["xopt"].shape[0]
     steps = np.array([r["steps"] for r in per], dtype=np.int64)

@@ -150,11 +150,13 @@ def _sparse_refusals(options, who, also=(), stopcond=False, observations=False, 
 
 
 def _run_and_close(obj, prepare=None, finish=None, **run):
-    """``prepare(obj)`` (the weights or costs, if any), one run and the owner's results (engine._MultiOwner.results),
-    which ``finish(obj, results)`` may add to while the owner lives; the owner is closed in any case"""
+    """``prepare``: a setter ``f(obj)`` (the weights or costs, if any) or a list of them, applied in order, None standing
+    for none; then one run and the owner's results (engine._MultiOwner.results), which ``finish(obj, results)`` may add
+    to while the owner lives; the owner is closed in any case"""
     try:
-        if prepare is not None:
-            prepare(obj)
+        for setter in prepare if isinstance(prepare, list) else [prepare]:
+            if setter is not None:
+                setter(obj)
         res = obj.results(obj.run(**run))
         if finish is not None:
             finish(obj, res)
@@ -326,52 +328,67 @@ def _lambda_max(D, S, w, obsw=None):
     return g.max(axis=0) if g.size else np.zeros(S.shape[1] if S.ndim == 2 else 1)
 
 
-def _multi_lasso_fits(D, S, lams, options):
-    """what lasso_multi and lasso_multi_dense check alike: (S as m x ns, lambda, ridge, nonneg, l1weights, starts)"""
-    m, n = D.shape
-    S = _response_matrix(S, m)
+def _lambda_vector(lams, unit="fit", zero_ok=True):
+    """lams as a vector of at least one value, each finite and >= 0 (> 0 without ``zero_ok``); ``unit`` names what a
+    value belongs to in the message, None leaves the values to the runner behind the caller"""
     lam = np.asarray(lams, dtype=np.float64).reshape(-1)
-    K = int(lam.size)
-    if K < 1:
+    if lam.size < 1:
         raise ValueError("lams must hold at least one lambda")
-    for k, v in enumerate(lam):
-        if not np.isfinite(v) or v < 0:
-            raise ValueError(f"fit {k}: lambda is not a nonnegative real number")
-    S = _response_columns(S, K)
-    ridge = _per_fit(options.get("ridge", 0.0), K, "ridge", lambda v: penalty_fields(dict(ridge=v), n)["ridge"])
-    nonneg = _per_fit(options.get("nonnegative", 0), K, "nonnegative",
-                      lambda v: penalty_fields(dict(nonnegative=v), n)["nonnegative"])
-    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
-    w = None if pw is None else pw["l1weights"]
-    if "rho" in options:
-        is_positive_real(options["rho"], "options.rho")
-    starts = _start_matrices(options, dict(x0=n, z0=n, u0=n), K, "fit")
-    return S, lam, ridge, nonneg, w, starts
+    for k, v in enumerate(lam if unit is not None else ()):
+        if not np.isfinite(v) or not (v >= 0 if zero_ok else v > 0):
+            raise ValueError(f"{unit} {k}: lambda is not a {'nonnegative' if zero_ok else 'positive'} real number")
+    return lam
 
 
-def _lambda_grid(D, s, options, default_n, lmax_of=None):
-    """lasso_path's automatic grid: options.nlambda values (popped; default ``default_n``) log-spaced from lambda_max down
-    to options.lambda_min_ratio * lambda_max (popped; default 1e-2).  lams given: the two options are popped and ignored.
-    ``lmax_of()``: another lambda_max than the lasso's (grouplasso_path)"""
+def _lambda_grid(options, lams, default_n, lmax, count_ok=False):
+    """the lambdas of a path: ``lams`` as given, or -- for None, and with ``count_ok`` for a scalar, which then is the
+    count -- options.nlambda values (default ``default_n``; an integer >= 1, not a bool) log-spaced from ``lmax()`` down
+    to options.lambda_min_ratio (default 1e-2) times it.  The two options are popped in every case; ``lmax`` is called
+    once both have passed"""
     nlambda = options.pop("nlambda", None)
     ratio = options.pop("lambda_min_ratio", 1e-2)
-    if s.size != D.shape[0]:
-        raise ValueError("The number of rows in argument D do not match size of s!")
-    nlambda = default_n if nlambda is None else nlambda
-    if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
+    if lams is not None and not (count_ok and np.isscalar(lams)):
+        return lams
+    nlambda = lams if lams is not None else default_n if nlambda is None else nlambda
+    if isinstance(nlambda, bool) or not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
         raise ValueError("options.nlambda must be an integer >= 1")
     if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
         raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-    if lmax_of is None:
+    top = float(lmax())
+    return top * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([top])
+
+
+def _lasso_grid(D, s, lams, options, lmax=None):
+    """lasso_path's ``_lambda_grid`` of 10 values from the lasso's lambda_max under options.l1weights and
+    options.obsweights; ``lmax()``: another lambda_max (grouplasso_path)"""
+    if lams is None and s.size != D.shape[0]:
+        raise ValueError("The number of rows in argument D do not match size of s!")
+
+    def lasso_lmax():
         pw = penalty_fields(dict(l1weights=options.get("l1weights")), D.shape[1])
         obsw = options.get("obsweights")
         if obsw is not None:
             from .sparse_lasso import observation_arrays
             obsw = observation_arrays(obsw, None, None, D.shape[0], 1)[0]
-        lmax = float(_lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"], obsw)[0])
-    else:
-        lmax = float(lmax_of())
-    return lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
+        return _lambda_max(D, s.reshape(-1, 1), None if pw is None else pw["l1weights"], obsw)[0]
+
+    return _lambda_grid(options, lams, 10, lmax or lasso_lmax)
+
+
+def _fit_penalties(options, n, K=None, groups=None):
+    """(ridge, nonnegative, l1weights, None | (group sizes, group weights, l1)): ridge, nonnegative and, beside ``groups``,
+    l1 are K values out of a scalar or K values (``K = None``: one value, the multinomial model), the l1 weights are
+    shared; options.rho, where given, is checked to be positive"""
+    def field(key, default):
+        check = lambda v: penalty_fields({key: v}, n)[key]
+        return check(options.get(key, default)) if K is None else _per_fit(options.get(key, default), K, key, check)
+
+    ridge, nonneg = field("ridge", 0.0), field("nonnegative", 0)
+    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
+    if "rho" in options:
+        is_positive_real(options["rho"], "options.rho")
+    grouped = None if groups is None else group_sizes(groups, options.get("groupweights"), n) + (field("l1", 0.0),)
+    return ridge, nonneg, None if pw is None else pw["l1weights"], grouped
 
 
 def _run_multi_lasso(D, S, lams, options, who, sparse, t0, groups=None):
@@ -383,27 +400,22 @@ def _run_multi_lasso(D, S, lams, options, who, sparse, t0, groups=None):
     else:
         _dense_multi_refusals(options, who)
     D = _matrix(D, "D", sparse_ok=sparse)
-    S, lam, ridge, nonneg, w, starts = _multi_lasso_fits(D, S, lams, options)
-    n, K = D.shape[1], int(lam.size)
-    prepare, finish = None, None
-    obs = None
+    m, n = D.shape
+    S = _response_matrix(S, m)
+    lam = _lambda_vector(lams)
+    K = int(lam.size)
+    S = _response_columns(S, K)
+    ridge, nonneg, w, grouped = _fit_penalties(options, n, K, groups)
+    starts = _start_matrices(options, dict(x0=n, z0=n, u0=n), K, "fit")
+    prepare, finish = [None if grouped is None else lambda obj: obj.set_groups(*grouped)], None
     if sparse and any(options.get(key) is not None for key in _OBSERVATION_KEYS):
         from .sparse_lasso import observation_arrays
-        obs = observation_arrays(options.get("obsweights"), options.get("foldid"), options.get("heldout"), D.shape[0], K)
-    if groups is not None:
-        sizes, gw = group_sizes(groups, options.get("groupweights"), n)
-        l1 = _per_fit(options.get("l1", 0.0), K, "l1", lambda v: penalty_fields(dict(l1=v), n)["l1"])
+        obs = observation_arrays(options.get("obsweights"), options.get("foldid"), options.get("heldout"), m, K)
+        prepare.append(lambda obj: obj.set_observations(*obs[:3]))
 
-    def prepare(obj):
-        if groups is not None:
-            obj.set_groups(sizes, gw, l1)
-        if obs is not None:
-            obj.set_observations(obs[0], obs[1], obs[2])
-
-    if obs is not None:
         def finish(obj, res):
             res["heldout_sse"], res["heldout_weight"] = obj.heldout()
-    if not sparse and D.shape[0] < n:
+    if not sparse and m < n:
         raise ValueError(f"{who} needs m >= n: the fat lasso's x-update (two dense products per fit) stays with lasso, "
                          "one call per fit")
     run = dict(check_every=int(options.get("check_every", 0)), z0=starts.get("z0"), u0=starts.get("u0"),
@@ -419,8 +431,8 @@ def _run_multi_lasso(D, S, lams, options, who, sparse, t0, groups=None):
         run.update(_pick(options, _LOOP_KEYS))
     res = _run_and_close(obj, prepare, finish, **run)
     res["lams"] = lam.copy()
-    if groups is not None:
-        res["groups"] = sizes.copy()
+    if grouped is not None:
+        res["groups"] = grouped[0].copy()
     res["solverruntime"] = time.perf_counter() - t0
     return res
 
@@ -471,12 +483,7 @@ def lasso_path(D, s, lams=None, options=None):
     if not is_sparse(D):
         raise ValueError("lasso_path runs on a scipy.sparse D: call lasso per lambda on a dense design matrix")
     s = _colvec(s, "s")
-    if lams is None:
-        lams = _lambda_grid(D, s, options, 10)  # (kSpmmChunk: one pass over D per product)
-    else:
-        options.pop("nlambda", None)
-        options.pop("lambda_min_ratio", None)
-    res = lasso_multi(D, s, lams, options)
+    res = lasso_multi(D, s, _lasso_grid(D, s, lams, options), options)  # (10 = kSpmmChunk: one pass over D per product)
     res["df"] = np.count_nonzero(res["zopt"], axis=0).astype(np.int64)
     return res
 
@@ -523,6 +530,78 @@ def cv_summary(sse, weight, lams):
                 lam_1se=float(lams[index_1se]))
 
 
+def _cv_folds(options, who, m, y, name):
+    """(F, foldid, scale) of a cross-validation of ``who`` over m observations: options.nfolds, seed and scale_lambda are
+    popped, options.heldout is refused, the response ``y`` (``name`` in the message) has m entries, and foldid is
+    options.foldid with every id in [0, F), or ``cv_folds``' default"""
+    F = options.pop("nfolds", 5)
+    if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or F < 2:
+        raise ValueError("options.nfolds must be an integer >= 2")
+    F = int(F)
+    seed = options.pop("seed", 0)
+    scale = bool(options.pop("scale_lambda", 1))
+    if options.get("heldout") is not None:
+        raise ValueError(f"options.heldout is {who}'s own to set: give options.foldid")
+    options.pop("heldout", None)
+    if y.size != m:
+        raise ValueError(f"The number of rows in argument D do not match size of {name}!")
+    if options.get("foldid") is None:
+        return F, cv_folds(m, F, seed), scale
+    from .sparse_lasso import observation_arrays
+    foldid = observation_arrays(None, options["foldid"], None, m, 1)[1].astype(np.int64)
+    if foldid.min() < 0 or foldid.max() >= F:
+        raise ValueError(f"options.foldid: every fold id must lie in [0, nfolds = {F})")
+    return F, foldid, scale
+
+
+def _cv_layout(options, lams, foldid, F, scale, w, wname, per_lambda, start_rows):
+    """The (F + 1)*L fits of a cross-validation over the L ``lams``, written into ``options``: fit f*L + l leaves fold f
+    out at lambda_l, fits F*L + l see every row.  Sets foldid and heldout, tiles the ``per_lambda`` options given as L
+    values and the starts (``start_rows``: the rows of each, L columns) F + 1 times, and returns fold_lams (F x L):
+    lambda_l times the training weight of fold f over the total of the observation weights ``w`` (options.``wname``),
+    or lambda_l itself without ``scale``.  The lambdas of the run are fold_lams row by row, then lams"""
+    L = int(lams.size)
+    total = float(w.sum())
+    if not total > 0.0:
+        raise ValueError(f"options.{wname}: the total weight must be positive")
+    train = np.array([total - float(w[foldid == f].sum()) for f in range(F)])
+    fold_lams = (train / total if scale else np.ones(F))[:, None] * lams[None, :]
+    options["foldid"] = foldid
+    options["heldout"] = np.concatenate([np.repeat(np.arange(F), L), np.full(L, -1)])
+    for key in per_lambda:  # scalars, or L values for every fold alike
+        if key in options and not (np.isscalar(options[key]) or isinstance(options[key], (bool, np.bool_))):
+            v = np.asarray(options[key]).reshape(-1)
+            if v.size != L:
+                raise ValueError(f"{key} has {v.size} entries for {L} lambdas")
+            options[key] = np.tile(v, F + 1)
+    for key, rows in start_rows.items():
+        if options.get(key) is not None:
+            v = np.asarray(options[key], dtype=np.float64)
+            if v.shape != (rows, L):
+                raise ValueError(f"options.{key} is not a {rows} x {L} matrix (one column per lambda)!")
+            options[key] = np.asfortranarray(np.tile(v, (1, F + 1)))
+    return fold_lams
+
+
+def _cv_results(res, lams, foldid, fold_lams, held_keys, error_key, row0=0, sizes=None, **first):
+    """the result of ``_cv_layout``'s run cut back into the F x L fold blocks (``held_keys``: the held-out sums, the
+    weight last; fold_steps) and the L full-data fits; ``cv_summary`` of ``error_key``; df (and, with the group
+    ``sizes``, groups and df_groups) of the coefficient block of zopt, which starts at ``row0``"""
+    F, L = fold_lams.shape
+    full = slice(F * L, (F + 1) * L)
+    held = {key: res[key][:F * L].reshape(F, L) for key in held_keys}
+    out = dict(lams=lams.copy(), foldid=foldid, **first, **cv_summary(held[error_key], held[held_keys[-1]], lams))
+    for key in ("xopt", "zopt", "uopt"):
+        out[key] = np.asfortranarray(res[key][:, full])
+    out["df"] = np.count_nonzero(out["zopt"][row0:], axis=0).astype(np.int64)
+    if sizes is not None:
+        out.update(groups=sizes.copy(), df_groups=_df_groups(out["zopt"][row0:], sizes))
+    out.update(steps=res["steps"][full], objopt=res["objopt"][full], fold_steps=res["steps"][:F * L].reshape(F, L),
+               fold_lams=fold_lams, **held, nnz=res["nnz"], cg_iters_total=res["cg_iters_total"],
+               cg_capped_updates=res["cg_capped_updates"], chunk=res["chunk"], runtime=res["runtime"])
+    return out
+
+
 def lasso_cv(D, s, lams=None, options=None):
     """results = lasso_cv(D, s, lams, options): F-fold cross-validation of the lasso's regularisation path on a sparse D,
     every fold fit and every full-data fit side by side in ONE run of ``lasso_multi`` over one upload of D (DESIGN.md
@@ -546,68 +625,14 @@ def lasso_cv(D, s, lams=None, options=None):
         raise ValueError("lasso_cv runs on a scipy.sparse D")
     s = _colvec(s, "s")
     m, n = D.shape
-    F = options.pop("nfolds", 5)
-    if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or F < 2:
-        raise ValueError("options.nfolds must be an integer >= 2")
-    F = int(F)
-    seed = options.pop("seed", 0)
-    scale = bool(options.pop("scale_lambda", 1))
-    if options.get("heldout") is not None:
-        raise ValueError("options.heldout is lasso_cv's own to set: give options.foldid")
-    options.pop("heldout", None)
-    if s.size != m:
-        raise ValueError("The number of rows in argument D do not match size of s!")
+    F, foldid, scale = _cv_folds(options, "lasso_cv", m, s, "s")
     from .sparse_lasso import observation_arrays
-    if options.get("foldid") is None:
-        foldid = cv_folds(m, F, seed)
-    else:
-        foldid = observation_arrays(None, options["foldid"], None, m, 1)[1].astype(np.int64)
-        if foldid.min() < 0 or foldid.max() >= F:
-            raise ValueError(f"options.foldid: every fold id must lie in [0, nfolds = {F})")
     obsw = observation_arrays(options.get("obsweights"), None, None, m, 1)[0]
-    if lams is None:
-        lams = _lambda_grid(D, s, options, 10)
-    else:
-        options.pop("nlambda", None)
-        options.pop("lambda_min_ratio", None)
-    lams = np.asarray(lams, dtype=np.float64).reshape(-1)
-    L = int(lams.size)
-    if L < 1:
-        raise ValueError("lams must hold at least one lambda")
-    w = np.ones(m) if obsw is None else obsw
-    total = float(w.sum())
-    train = np.array([total - float(w[foldid == f].sum()) for f in range(F)])
-    if not total > 0.0:
-        raise ValueError("options.obsweights: the total weight must be positive")
-    frac = train / total if scale else np.ones(F)
-    fold_lams = frac[:, None] * lams[None, :]
-    o = dict(options)
-    o["foldid"] = foldid
-    o["heldout"] = np.concatenate([np.repeat(np.arange(F), L), np.full(L, -1)])
-    for key in ("ridge", "nonnegative"):  # scalars, or L values for every fold alike
-        if key in o and not (np.isscalar(o[key]) or isinstance(o[key], (bool, np.bool_))):
-            v = np.asarray(o[key]).reshape(-1)
-            if v.size != L:
-                raise ValueError(f"{key} has {v.size} entries for {L} lambdas")
-            o[key] = np.tile(v, F + 1)
-    for key in ("x0", "z0", "u0"):
-        if o.get(key) is not None:
-            v = np.asarray(o[key], dtype=np.float64)
-            if v.shape != (n, L):
-                raise ValueError(f"options.{key} is not a {n} x {L} matrix (one column per lambda)!")
-            o[key] = np.asfortranarray(np.tile(v, (1, F + 1)))
-    res = lasso_multi(D, s, np.concatenate([fold_lams.reshape(-1), lams]), o)
-    full = slice(F * L, (F + 1) * L)
-    sse = res["heldout_sse"][:F * L].reshape(F, L)
-    wt = res["heldout_weight"][:F * L].reshape(F, L)
-    out = dict(lams=lams.copy(), foldid=foldid, **cv_summary(sse, wt, lams))
-    for key in ("xopt", "zopt", "uopt"):
-        out[key] = np.asfortranarray(res[key][:, full])
-    out["df"] = np.count_nonzero(out["zopt"], axis=0).astype(np.int64)
-    out.update(steps=res["steps"][full], objopt=res["objopt"][full], fold_steps=res["steps"][:F * L].reshape(F, L),
-               fold_lams=fold_lams, heldout_sse=sse, heldout_weight=wt, nnz=res["nnz"],
-               cg_iters_total=res["cg_iters_total"], cg_capped_updates=res["cg_capped_updates"], chunk=res["chunk"],
-               runtime=res["runtime"])
+    lams = _lambda_vector(_lasso_grid(D, s, lams, options), None)
+    fold_lams = _cv_layout(options, lams, foldid, F, scale, np.ones(m) if obsw is None else obsw, "obsweights",
+                           ("ridge", "nonnegative"), dict(x0=n, z0=n, u0=n))
+    res = lasso_multi(D, s, np.concatenate([fold_lams.reshape(-1), lams]), options)
+    out = _cv_results(res, lams, foldid, fold_lams, ("heldout_sse", "heldout_weight"), "heldout_sse")
     out["solverruntime"] = time.perf_counter() - t0
     return out
 
@@ -657,12 +682,7 @@ def lasso_path_dense(D, s, lams=None, options=None):
         raise ValueError("lasso_path_dense runs on a dense D: call lasso_path (lasso_multi) on a scipy.sparse design matrix")
     D = _matrix(D, "D")
     s = _colvec(s, "s")
-    if lams is None:
-        lams = _lambda_grid(D, s, options, 10)
-    else:
-        options.pop("nlambda", None)
-        options.pop("lambda_min_ratio", None)
-    res = lasso_multi_dense(D, s, lams, options)
+    res = lasso_multi_dense(D, s, _lasso_grid(D, s, lams, options), options)
     res["df"] = np.count_nonzero(res["zopt"], axis=0).astype(np.int64)
     return res
 
@@ -787,13 +807,8 @@ def _run_multi_classifier(D, ELL, lams, options, who, t0, groups=None):
         _dense_multi_refusals(options, who)
     D = _matrix(D, "D", sparse_ok=sparse)
     m, n = D.shape
-    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
+    lam = _lambda_vector(lams)
     K = int(lam.size)
-    if K < 1:
-        raise ValueError("lams must hold at least one lambda")
-    for k, v in enumerate(lam):
-        if not np.isfinite(v) or v < 0:
-            raise ValueError(f"fit {k}: lambda is not a nonnegative real number")
     ELL = _l1c_labels(ELL, m, K)
     loss = options.get("lossfunction", "logistic")
     losses = [loss] * K if isinstance(loss, str) else list(loss)
@@ -801,26 +816,12 @@ def _run_multi_classifier(D, ELL, lams, options, who, t0, groups=None):
         raise ValueError("options.lossfunction is neither one string nor a list with one string per fit!")
     for k, v in enumerate(losses):
         loss_code(v, k)
-    ridge = _per_fit(options.get("ridge", 0.0), K, "ridge", lambda v: penalty_fields(dict(ridge=v), n)["ridge"])
-    nonneg = _per_fit(options.get("nonnegative", 0), K, "nonnegative",
-                      lambda v: penalty_fields(dict(nonnegative=v), n)["nonnegative"])
-    pw = penalty_fields(dict(l1weights=options.get("l1weights")), n)
-    w = None if pw is None else pw["l1weights"]
+    ridge, nonneg, w, grouped = _fit_penalties(options, n, K, groups)
     Cv = is_positive_real(options.get("C", 1.0), "options.C")
-    if "rho" in options:
-        is_positive_real(options["rho"], "options.rho")
     weights, class_cost = _l1c_costs(options, ELL, K)
     starts = _start_matrices(options, dict(x0=n, z0=m + n, u0=m + n), K, "fit")
-    prepare, finish = _cost_setter(weights, class_cost), None
-    if groups is not None:
-        sizes, gw = group_sizes(groups, options.get("groupweights"), n)
-        l1 = _per_fit(options.get("l1", 0.0), K, "l1", lambda v: penalty_fields(dict(l1=v), n)["l1"])
-        set_cost0 = prepare
-
-        def prepare(obj):
-            if set_cost0 is not None:
-                set_cost0(obj)
-            obj.set_groups(sizes, gw, l1)
+    prepare, finish = [_cost_setter(weights, class_cost),
+                       None if grouped is None else lambda obj: obj.set_groups(*grouped)], None
     if sparse and (options.get("foldid") is not None or options.get("heldout") is not None):
         if options.get("foldid") is None:
             raise ValueError("options.heldout needs options.foldid: the fold of every observation")
@@ -828,12 +829,7 @@ def _run_multi_classifier(D, ELL, lams, options, who, t0, groups=None):
             raise ValueError("options.foldid needs options.heldout: the fold every fit leaves out (K values, -1 for none)")
         from .sparse_lasso import observation_arrays
         fold, held = observation_arrays(None, options["foldid"], options["heldout"], m, K)[1:3]
-        set_cost = prepare
-
-        def prepare(obj):
-            if set_cost is not None:
-                set_cost(obj)
-            obj.set_folds(fold, held)
+        prepare.append(lambda obj: obj.set_folds(fold, held))
 
         def finish(obj, res):
             res["heldout_loss"], res["heldout_errors"], res["heldout_weight"] = obj.heldout()
@@ -848,8 +844,8 @@ def _run_multi_classifier(D, ELL, lams, options, who, t0, groups=None):
                          z0=starts.get("z0"), u0=starts.get("u0"), nodualerror=int(bool(options.get("nodualerror", 0))),
                          **_pick(options, _LOOP_KEYS + (_CG_KEYS if sparse else ())))
     res["lams"] = lam.copy()
-    if groups is not None:
-        res["groups"] = sizes.copy()
+    if grouped is not None:
+        res["groups"] = grouped[0].copy()
     res["solverruntime"] = time.perf_counter() - t0
     return res
 
@@ -911,23 +907,9 @@ def _classifier_path(D, ell, lams, options, who, groups=None):
     D = _matrix(D, "D", sparse_ok=is_sparse(D))
     e = _colvec(ell, "ell")
     gs = None if groups is None else group_sizes(groups, options.get("groupweights"), D.shape[1])
-    if lams is None or np.isscalar(lams):
-        if gs is not None:
-            _group_l1_refusal(options, "groupclassifier_path")
-        if lams is not None:
-            options["nlambda"] = lams
-        nlambda = options.pop("nlambda", None)
-        ratio = options.pop("lambda_min_ratio", 1e-2)
-        nlambda = 10 if nlambda is None else nlambda
-        if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
-            raise ValueError("options.nlambda must be an integer >= 1")
-        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
-            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-        lmax = _classifier_lambda_max(D, e, options, gs)
-        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
-    else:
-        options.pop("nlambda", None)
-        options.pop("lambda_min_ratio", None)
+    if gs is not None and (lams is None or np.isscalar(lams)):
+        _group_l1_refusal(options, "groupclassifier_path")
+    lams = _lambda_grid(options, lams, 10, lambda: _classifier_lambda_max(D, e, options, gs), count_ok=True)
     res = _run_multi_classifier(D, e, lams, options, who, time.perf_counter(), None if gs is None else gs[0])
     Z2 = res["zopt"][D.shape[0]:]
     res["df"] = np.count_nonzero(Z2, axis=0).astype(np.int64)
@@ -978,100 +960,33 @@ def _classifier_cv(D, ell, lams, options, who, groups=None):
                          "(SparseL1Classifier)")
     e = _colvec(ell, "ell")
     m, n = D.shape
-    F = options.pop("nfolds", 5)
-    if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or F < 2:
-        raise ValueError("options.nfolds must be an integer >= 2")
-    F = int(F)
-    seed = options.pop("seed", 0)
-    scale = bool(options.pop("scale_lambda", 1))
+    F, foldid, scale = _cv_folds(options, who, m, e, "ell")
     measure = options.pop("measure", "deviance")
     if not (isinstance(measure, str) and measure in ("deviance", "class")):
         raise ValueError("options.measure must be 'deviance' or 'class'")
-    if options.get("heldout") is not None:
-        raise ValueError(f"options.heldout is {who}'s own to set: give options.foldid")
-    options.pop("heldout", None)
-    if e.size != m:
-        raise ValueError("The number of rows in argument D do not match size of ell!")
     loss = options.get("lossfunction", "logistic")
     if not isinstance(loss, str):
         raise ValueError("options.lossfunction is not a string!")
-    from .sparse_lasso import observation_arrays
-    if options.get("foldid") is None:
-        foldid = cv_folds(m, F, seed)
-    else:
-        foldid = observation_arrays(None, options["foldid"], None, m, 1)[1].astype(np.int64)
-        if foldid.min() < 0 or foldid.max() >= F:
-            raise ValueError(f"options.foldid: every fold id must lie in [0, nfolds = {F})")
     gs = None if groups is None else group_sizes(groups, options.get("groupweights"), n)
-    if lams is None or np.isscalar(lams):
-        if gs is not None:
-            _group_l1_refusal(options, who)
-        if lams is not None:
-            options["nlambda"] = lams
-        nlambda = options.pop("nlambda", None)
-        ratio = options.pop("lambda_min_ratio", 1e-2)
-        nlambda = 10 if nlambda is None else nlambda
-        if isinstance(nlambda, bool) or not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
-            raise ValueError("options.nlambda must be an integer >= 1")
-        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
-            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
-        lmax = _classifier_lambda_max(D, e, _pick(options, ("lossfunction", "weights", "classcost", "l1weights", "C")), gs)
-        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
-    else:
-        options.pop("nlambda", None)
-        options.pop("lambda_min_ratio", None)
-    lams = np.asarray(lams, dtype=np.float64).reshape(-1)
-    L = int(lams.size)
-    if L < 1:
-        raise ValueError("lams must hold at least one lambda")
+    if gs is not None and (lams is None or np.isscalar(lams)):
+        _group_l1_refusal(options, who)
+    cost = _pick(options, ("lossfunction", "weights", "classcost", "l1weights", "C"))
+    lams = _lambda_grid(options, lams, 10, lambda: _classifier_lambda_max(D, e, cost, gs), count_ok=True)
+    lams = _lambda_vector(lams, None)
     ELL = _l1c_labels(e, m, 1)
     wf = svm_cost_fields(dict(weights=options.get("weights")), ELL[:, 0])
-    w = np.ones(m) if wf is None else wf["weights"]
-    total = float(w.sum())
-    if not total > 0.0:
-        raise ValueError("options.weights: the total weight must be positive")
-    train = np.array([total - float(w[foldid == f].sum()) for f in range(F)])
-    frac = train / total if scale else np.ones(F)
-    fold_lams = frac[:, None] * lams[None, :]
-    o = dict(options)
-    o["foldid"] = foldid
-    o["heldout"] = np.concatenate([np.repeat(np.arange(F), L), np.full(L, -1)])
-    cc = o.get("classcost")
+    cc = options.get("classcost")
     if cc is not None:  # one pair for every fit, 'balanced' from all rows
         if not isinstance(cc, str) and np.ndim(cc) == 2:
             raise ValueError("classcost is one (pos, neg) pair or 'balanced' in l1classifier_cv")
-        o["classcost"] = class_cost_pair(cc, ELL[:, 0])
-    for key in ("ridge", "nonnegative") + (() if gs is None else ("l1",)):  # scalars, or L values for every fold alike
-        if key in o and not (np.isscalar(o[key]) or isinstance(o[key], (bool, np.bool_))):
-            v = np.asarray(o[key]).reshape(-1)
-            if v.size != L:
-                raise ValueError(f"{key} has {v.size} entries for {L} lambdas")
-            o[key] = np.tile(v, F + 1)
-    for key in ("z0", "u0"):
-        if o.get(key) is not None:
-            v = np.asarray(o[key], dtype=np.float64)
-            if v.shape != (m + n, L):
-                raise ValueError(f"options.{key} is not a {m + n} x {L} matrix (one column per lambda)!")
-            o[key] = np.asfortranarray(np.tile(v, (1, F + 1)))
-    if o.get("x0") is not None:
-        v = np.asarray(o["x0"], dtype=np.float64)
-        if v.shape != (n, L):
-            raise ValueError(f"options.x0 is not a {n} x {L} matrix (one column per lambda)!")
-        o["x0"] = np.asfortranarray(np.tile(v, (1, F + 1)))
-    res = _run_multi_classifier(D, e, np.concatenate([fold_lams.reshape(-1), lams]), o, who, time.perf_counter(),
+        options["classcost"] = class_cost_pair(cc, ELL[:, 0])
+    fold_lams = _cv_layout(options, lams, foldid, F, scale, np.ones(m) if wf is None else wf["weights"], "weights",
+                           ("ridge", "nonnegative") + (() if gs is None else ("l1",)), dict(z0=m + n, u0=m + n, x0=n))
+    res = _run_multi_classifier(D, e, np.concatenate([fold_lams.reshape(-1), lams]), options, who, time.perf_counter(),
                                 None if gs is None else gs[0])
-    full = slice(F * L, (F + 1) * L)
-    held = {key: res[key][:F * L].reshape(F, L) for key in ("heldout_loss", "heldout_errors", "heldout_weight")}
-    chosen = held["heldout_loss"] if measure == "deviance" else held["heldout_errors"]
-    out = dict(lams=lams.copy(), foldid=foldid, measure=measure, **cv_summary(chosen, held["heldout_weight"], lams))
-    for key in ("xopt", "zopt", "uopt"):
-        out[key] = np.asfortranarray(res[key][:, full])
-    out["df"] = np.count_nonzero(out["zopt"][m:], axis=0).astype(np.int64)
-    if gs is not None:
-        out.update(groups=gs[0].copy(), df_groups=_df_groups(out["zopt"][m:], gs[0]))
-    out.update(steps=res["steps"][full], objopt=res["objopt"][full], fold_steps=res["steps"][:F * L].reshape(F, L),
-               fold_lams=fold_lams, **held, nnz=res["nnz"], cg_iters_total=res["cg_iters_total"],
-               cg_capped_updates=res["cg_capped_updates"], chunk=res["chunk"], runtime=res["runtime"])
+    out = _cv_results(res, lams, foldid, fold_lams, ("heldout_loss", "heldout_errors", "heldout_weight"),
+                      "heldout_loss" if measure == "deviance" else "heldout_errors", m, None if gs is None else gs[0],
+                      measure=measure)
     out["solverruntime"] = time.perf_counter() - t0
     return out
 
@@ -1116,17 +1031,12 @@ def grouplasso_path(D, s, groups, lams=None, options=None):
     s = _colvec(s, "s")
     sizes, gw = group_sizes(groups, options.get("groupweights"), D.shape[1])
     if lams is None:
-        if np.any(np.asarray(options.get("l1", 0.0), dtype=np.float64) != 0):
-            raise ValueError("grouplasso_path: with options.l1 != 0 lambda_max has no closed form: give lams")
-        lams = _lambda_grid(D, s, options, 10, lambda: _group_lambda_max(D, s, sizes, gw))
-    else:
-        options.pop("nlambda", None)
-        options.pop("lambda_min_ratio", None)
+        _group_l1_refusal(options, "grouplasso_path")
+    lams = _lasso_grid(D, s, lams, options, lambda: _group_lambda_max(D, s, sizes, gw))
     res = grouplasso_multi(D, s, lams, sizes, options)
     Z = np.asarray(res["zopt"]).reshape(D.shape[1], -1)
     res["df"] = np.count_nonzero(Z, axis=0).astype(np.int64)
-    first = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-    res["df_groups"] = np.count_nonzero(np.add.reduceat(Z != 0, first, axis=0), axis=0).astype(np.int64)
+    res["df_groups"] = _df_groups(Z, sizes)
     return res
 
 
@@ -1993,13 +1903,8 @@ def covarianceselection_multi(D, lams, options=None):
     _covsel_multi_refusals(options)
     D, S = _covsel_S(D, options)
     n = int((D if S is None else S).shape[1])
-    lam = np.asarray(lams, dtype=np.float64).reshape(-1)
+    lam = _lambda_vector(lams, zero_ok=False)
     K = int(lam.size)
-    if K < 1:
-        raise ValueError("lams must hold at least one lambda")
-    for k, v in enumerate(lam):
-        if not np.isfinite(v) or not v > 0:
-            raise ValueError(f"fit {k}: lambda is not a positive real number")
     rhos = np.asarray(_per_fit(options.get("rho", 1.0), K, "rho", lambda v: is_positive_real(v, "options.rho")),
                       dtype=np.float64)
     if not np.all(np.isfinite(rhos)):
@@ -2065,19 +1970,13 @@ def covarianceselection_path(D, lams=None, options=None):
     the host.  Returns covarianceselection_multi's fields plus ``df``: per fit the number of pairs i < j with
     z_ij != 0, the edges of the selected graph."""
     options = _options(options, "Argument options is not a struct!", optional=True)
-    nlambda = options.pop("nlambda", None)
-    ratio = options.pop("lambda_min_ratio", 1e-2)
-    if lams is None:
-        nlambda = 10 if nlambda is None else nlambda
-        if not isinstance(nlambda, (int, np.integer)) or nlambda < 1:
-            raise ValueError("options.nlambda must be an integer >= 1")
-        if not np.isscalar(ratio) or not np.isreal(ratio) or not 0.0 < ratio <= 1.0:
-            raise ValueError("options.lambda_min_ratio must lie in (0, 1]")
+    def lambda_max():
         lmax = covarianceselection_lambda_max(D, {"S": options["S"]} if "S" in options else None)
         if not lmax > 0:
             raise ValueError("lambda_max is 0 (S is diagonal): there is no path to follow; pass lams")
-        lams = lmax * np.logspace(0.0, np.log10(float(ratio)), int(nlambda)) if nlambda > 1 else np.array([lmax])
-    res = covarianceselection_multi(D, lams, options)
+        return lmax
+
+    res = covarianceselection_multi(D, _lambda_grid(options, lams, 10, lambda_max), options)
     res["df"] = covsel_df(res["zopt"])
     return res
 

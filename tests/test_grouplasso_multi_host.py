@@ -131,7 +131,7 @@ def test_lambda_max_is_where_the_zero_solution_stops_being_optimal(ap, weighted)
     live = w > 0
     assert np.all(norms[live] <= lmax * (1 + 1e-9) * w[live])
     assert np.count_nonzero(norms[live] > lmax * (1 - 1e-3) * w[live]) == 1
-    grid = ap.solvers._lambda_grid(D, s, dict(nlambda=4, lambda_min_ratio=0.1), 10,
+    grid = ap.solvers._lambda_grid(dict(nlambda=4, lambda_min_ratio=0.1), None, 10,
                                    lambda: ap.solvers._group_lambda_max(D, s, sizes, gw))
     assert np.allclose(grid, lmax * np.logspace(0, -1, 4)) and grid[0] == lmax
 
