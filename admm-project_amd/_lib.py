@@ -446,6 +446,7 @@ _SIGNATURES = {
     "admm_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "admm_op_gemv_n": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int64, _dp, _dp]),
     "admm_op_gemv_t": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, C.c_int64]),
+    "admm_op_gemv_forms": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32)]),
     "admm_op_spmv": (C.c_int, [C.POINTER(SparseDesc), C.c_int, _dp, _dp]),
     "admm_op_gram": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int64, C.c_double, _dp]),
     "admm_op_cholesky": (C.c_int, [_dp, C.c_int64, C.c_int64]),

@@ -214,6 +214,20 @@ int admm_op_gemv_t(const double* D, int64_t m, int64_t n, int64_t ldD, const dou
   return ADMM_OK;
 }
 
+int admm_op_gemv_forms(int64_t m, int64_t n, int32_t out[5]) {
+  if (!out || m <= 0 || n <= 0 || m > (int64_t{1} << 40) / n)
+    return fail(ADMM_E_INVALID, "gemv_forms: bad argument (m, n >= 1, m * n <= 2^40)");
+  const int64_t ld = round_up(m, 16);  // (put_matrix)
+  const GemvNPlan pn = gemv_n_plan(m, n, ld);
+  const GemvTPlan pt = gemv_t_plan(m, n, ld);
+  out[0] = pn.nchunk;
+  out[1] = static_cast<int32_t>(pn.cols_per_chunk);
+  out[2] = pt.rows_per_chunk;
+  out[3] = pt.nchunk;
+  out[4] = stream_hint(8 * m * n) ? 1 : 0;  // (the launchers' own expression)
+  return ADMM_OK;
+}
+
 int admm_op_gram(const double* D, int64_t m, int64_t n, int64_t ldD, double shift, double* W) {
   if (!D || !W || m <= 0 || n <= 0 || ldD < m) return fail(ADMM_E_INVALID, "gram: bad argument");
   ADMM_TRY(need_device());

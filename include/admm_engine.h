@@ -641,6 +641,11 @@ int admm_op_gemv_n(const double* D, int64_t m, int64_t n, int64_t ldD, const dou
 /* G(:,k) = D'*V(:,k), k < nrhs <= 4  (admm.m:119/167 `At*v`; getProxOps.m:1514) */
 int admm_op_gemv_t(const double* D, int64_t m, int64_t n, int64_t ldD, const double* V, int64_t ldV,
                    int32_t nrhs, double* G, int64_t ldG);
+/* The forms those two operators run for an m x n matrix, on the host alone (no device is touched): out = {gemv_n column
+ * chunks, gemv_n columns per chunk, gemv_t rows per chunk, gemv_t row chunks, 1 if the matrix loads are non-temporal
+ * (the matrix is larger than the caches) else 0}, from the launchers' own planners with the leading dimension the
+ * operators give the device copy.  For the tests: a shape meant to reach a form says so here. */
+int admm_op_gemv_forms(int64_t m, int64_t n, int32_t out[5]);
 /* y = D*x (transpose = 0: x has cols, y rows elements) or y = D'*x (x rows, y cols) for a sparse D in host CSC arrays,
  * by the kernel and the plans of the sparse lasso engine (admm_engine_create_sparse, whose checks of D apply): every
  * row's products are added in one fixed order, so a second call returns the same bits; an empty row gives 0.0 */

@@ -695,12 +695,30 @@ def test_relax_with_svm_is_rejected(gpu):
         gpu.linearsvm(p["D"], p["ell"], p["C"], dict(relax=1.5, x0=p["x0"], z0=p["z0"], u0=p["u0"]))
 
 
-def test_total_variation_large_matches_the_banded_oracle(gpu):
+@pytest.mark.parametrize("n", [3_000_001, 3_200_001])
+def test_total_variation_large_matches_the_banded_oracle(gpu, n):
     """3e6 + 1 elements (odd: the unpaired tail and the thread run the end cuts; 1550 tiles of tv_direct2, more than
-    1024 tile partials for the deferred tail) against the oracle's banded Cholesky solve, 12 iterations"""
-    n = 3_000_001
+    1024 tile partials for the deferred tail) against the oracle's banded Cholesky solve, 12 iterations.  That length
+    still runs the plain-store instances: launch_tv_direct asks stream_hint(8 * 8 * n), 192 000 064 B there, under
+    kStreamBytes = 192 MiB.  3.2e6 + 1 elements (204 800 064 B) select the streaming-store (NTS = true) instances of
+    tv_direct2_kernel; no call reports which instance ran, so the threshold arithmetic is asserted here."""
+    assert 8 * 8 * 3_000_001 < 192 << 20 < 8 * 8 * 3_200_001 and n in (3_000_001, 3_200_001)
     p = gpu.synth.tv_problem(4, n)
     o = dict(maxiters=12, domaxiters=1, objevals=1)
+    got = gpu.totalvariation(p["s"], p["lam"], dict(o, record_history=0))
+    ref = S.totalvariation(p["s"], p["lam"], dict(o, banded=1))
+    assert got["steps"] == ref["steps"] == 12
+    for k in ("pnorm", "dnorm", "perr", "derr", "objevals", "xopt", "zopt", "uopt"):
+        _close(k, got[k], ref[k], 1e-9)
+
+
+def test_total_variation_large_fused_form_matches_the_banded_oracle(gpu):
+    """the same comparison at rho = 36 (halo 250..256: tv_fused_kernel, as the 4099-element cases above) and 3.2e6 + 1
+    elements: launch_tv_fused asks the same stream_hint(8 * 8 * n), so this runs its streaming-store instance"""
+    n = 3_200_001
+    assert 8 * 8 * n > 192 << 20
+    p = gpu.synth.tv_problem(4, n)
+    o = dict(maxiters=12, domaxiters=1, objevals=1, rho=36.0)
     got = gpu.totalvariation(p["s"], p["lam"], dict(o, record_history=0))
     ref = S.totalvariation(p["s"], p["lam"], dict(o, banded=1))
     assert got["steps"] == ref["steps"] == 12

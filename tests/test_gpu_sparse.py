@@ -91,6 +91,33 @@ def test_spmv_against_an_exactly_summed_reference(gpu, name, transpose):
     assert np.array_equal(y, _spmv(L, csc, transpose, x))
 
 
+def test_spmv_and_spmm_non_temporal_forms_are_exact_on_integers(gpu):
+    """spmv_plan streams (non-temporal index and value loads, spmv_kernel / spmm_kernel <., true>) once both stored
+    orientations pass kStreamBytes: 24 nnz + 8 (rows + cols + 2) > 192 MiB, from 8.4 million nonzeros.  30001 x 4001
+    with one entry in 14 (8.57 million; rows of ~286 and ~2143 nonzeros: 64 lanes, odd remainders), nonzero integers in
+    [-4, 4] against integers in [-8, 8]: every partial sum is an integer below 2^53, so both products are compared bit
+    for bit with SciPy's, in both orientations; the multi-vector product (K = 3) column by column."""
+    L = gpu._lib
+    rows, cols = 30001, 4001
+    rng = np.random.default_rng(31)
+    keep = rng.integers(0, 14, size=(cols, rows), dtype=np.int8) == 0
+    vals = rng.integers(1, 5, size=(cols, rows), dtype=np.int8) * (2 * rng.integers(0, 2, size=(cols, rows), dtype=np.int8) - 1)
+    A = sp.csr_matrix(np.where(keep, vals, 0).astype(np.int8)).T.astype(np.float64)  # CSR of A' = CSC of A
+    csc = csc_of(A)
+    nnz = csc.data.size
+    assert 24 * nnz + 8 * (rows + cols + 2) > 192 << 20 and csc.shape == (rows, cols)
+    for transpose in (0, 1):
+        M = A.T.tocsr() if transpose else A.tocsr()
+        X = np.asfortranarray(rng.integers(-8, 9, size=(M.shape[1], 3)).astype(np.float64))
+        ref = M @ X
+        assert np.all(ref == np.rint(ref)) and np.max(np.abs(ref)) < 2.0 ** 40
+        y = _spmv(L, csc, transpose, np.ascontiguousarray(X[:, 0]))
+        assert np.array_equal(y, ref[:, 0]), (transpose, np.flatnonzero(y != ref[:, 0])[:8])
+        Y = np.full(ref.shape, np.nan, order="F")
+        L.check(L.load().admm_op_spmm(C.byref(desc_of(L, csc)), transpose, 3, L.as_dp(X), L.as_dp(Y)))
+        assert np.array_equal(Y, ref), (transpose, np.argwhere(Y != ref)[:8])
+
+
 def _check_sparse_run(got, D):
     assert got["cg_capped_updates"] == 0
     assert got["xsolve"] == "cg" and got["nnz"] == D.nnz
